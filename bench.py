@@ -1,14 +1,23 @@
 """Throughput of the 3-layer MolKGNN training step on AID-1798-shaped synthetic molecules.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One JSON line on rank 0.  ``value`` = molecules/s of forward + backward (+ gradient all-reduce for
-N > 1, + AdamW step) over all ranks, batches already resident in HBM.  ``roofline`` prices the
-kernel-convolution forward of one N-hop layer (F = 110, the dominant kernels) against the HBM
-roofline with the algorithmic byte count of SURVEY.md 8(d); ``cpu_baseline`` times the
-reference-faithful CPU restatement (oracle/) on this box's host cores on a bounded sample.
+N > 1, + AdamW step) over all ranks, batches already resident in HBM, timed over exactly K steps
+after W warm-up steps; ``ms_per_step`` = the milliseconds one of those K steps took.
+
+``--dump-outputs DIR`` writes what the last timed step left to its caller (loss, gradients,
+parameters and buffers after the optimiser step) as ``DIR/<name>.npy``; the inputs and initial
+weights are seeded, so two builds run with the same arguments can be compared output for output.
+
+A plain run does only that.  ``--full`` adds everything else, measured after the headline:
+the spread over further timed windows, ``roofline`` (the kernel-convolution forward of one N-hop
+layer, F = 110, the dominant kernels, against the HBM roofline with the algorithmic byte count of
+SURVEY.md 8(d), and the other kernels of that layer), the exact-fp32 leg, the fresh-batch and
+small-batch legs, and ``cpu_baseline`` (the reference-faithful CPU restatement, oracle/, on the
+host cores this process may use, on a bounded sample).
 """
 import argparse
 import json
@@ -65,10 +74,17 @@ def parse():
     ap.add_argument("--distinct-batches", type=int, default=4, help="distinct resident batches cycled through")
     ap.add_argument("--no-optimizer", action="store_true", help="time forward+backward(+all-reduce) only")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying one hipGraph per resident batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--roofline-reps", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=0, help="timed windows of --steps steps each (0: as many as make >= 0.5 s of timed work, at least 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: the spread over further timed windows, the roofline "
+                         "and per-kernel figures, the exact-fp32, fresh-batch and small-batch legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, gradients and the parameters and buffers after it as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: seconds of CPU baseline work")
+    ap.add_argument("--roofline-reps", type=int, default=20, help="--full: launches per sample of the kernel timings")
+    ap.add_argument("--windows", type=int, default=0,
+                    help="--full: timed windows of --steps steps each, the headline's included, for the spread (0: as many as "
+                         "make >= 0.5 s of timed work, at least 5)")
     ap.add_argument("--dp-one-graph", action="store_true",
                     help="N > 1: capture the gradient all-reduce INTO the step's graph (one graph per batch, as on one GPU) instead "
                          "of backward graph + all-reduce + optimiser graph; recorded in the line as dp_one_graph (same as "
@@ -77,8 +93,8 @@ def parse():
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher check (no GPU needed): every rank prints its RANK / LOCAL_RANK / WORLD_SIZE as one JSON line and exits")
     ap.add_argument("--fresh-batches", type=int, default=16,
-                    help="also time an epoch of this many distinct batches (one AID-1798 epoch at batch 4096 is 16) with the "
-                         "receptive-field and index-plan build inside the timed region; 0 = skip")
+                    help="--full: also time an epoch of this many distinct batches (one AID-1798 epoch at batch 4096 is 16) with "
+                         "the receptive-field and index-plan build inside the timed region; 0 = skip")
     return ap.parse_args()
 
 
@@ -631,6 +647,28 @@ def fresh_batches_leg(args, model, opt, dev, log):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, model, loss, grads):
+    """What the last timed step leaves its caller, as ``<name>.npy``: ``loss``, ``grad.<parameter>`` (the step's gradients),
+    ``param.<parameter>`` and ``buffer.<buffer>`` (after the optimiser step).  Floating tensors as float32, counters as float64."""
+    import numpy as np
+    arrays = {"loss": loss}
+    arrays.update((f"grad.{n}", g) for n, g in grads.items() if g is not None)
+    arrays.update((f"param.{n}", p) for n, p in model.named_parameters())
+    arrays.update((f"buffer.{n}", b) for n, b in model.named_buffers() if b is not None)
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32 if v.dtype.is_floating_point else np.float64)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return {"dir": dirname, "arrays": len(arrays), "bytes": total}
+
+
 def free_port():
     import socket
     with socket.socket() as s:
@@ -871,7 +909,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            step(args.warmup + i)
+            last_loss[0] = step(args.warmup + i)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -885,6 +923,7 @@ def main():
         return el
 
     own_windows = []
+    last_loss = [None]
 
     # how many ranks the collective really spans (an all-reduce of ones), outside the timed region
     ranks_seen = None
@@ -893,29 +932,40 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         ranks_seen = int(round(float(t.item())))
 
-    first = timed_window()
-    n_windows = args.windows if args.windows > 0 else max(5, min(200, int(math.ceil(0.5 / max(first, 1e-6)))))
-    if world > 1:                                        # every rank must run the same number of windows
-        t = torch.tensor([n_windows], dtype=torch.int64, device=dev)
-        dist.broadcast(t, 0)
-        n_windows = int(t.item())
-    unsorted = [first] + [timed_window() for _ in range(n_windows - 1)]
-    windows = sorted(unsorted)
-    elapsed = windows[len(windows) // 2]                 # the median window is the reported one
-    # N > 1, for whoever has to explain the scaling curve: every rank's own time for the reported window (the slowest sets
-    # `value`), and the gradient all-reduce's own GPU time -- HIP events around the collective, one more untimed window
+    # the headline: ONE window of exactly --steps steps
+    elapsed = timed_window()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs: a replayed graph writes its loss and gradients into the same tensors next time)
+        i_last = args.warmup + args.steps - 1
+        grad_list = graphs[i_last % nb][3] if graphs is not None else reducer.grads()
+        names = {id(p_): n_ for n_, p_ in model.named_parameters()}
+        dumped = dump_outputs(args.dump_outputs, model, last_loss[0],
+                              {names[id(p_)]: g_ for p_, g_ in zip(reducer.params, grad_list)})
+        log(f"outputs of the last timed step: {dumped['arrays']} arrays, {dumped['bytes']} bytes in {args.dump_outputs}")
+    windows = [elapsed]
+    if args.full:
+        # --full: the spread over further windows of --steps steps (the headline's window is the first of them)
+        n_windows = args.windows if args.windows > 0 else max(5, min(200, int(math.ceil(0.5 / max(elapsed, 1e-6)))))
+        if world > 1:                                    # every rank must run the same number of windows
+            t = torch.tensor([n_windows], dtype=torch.int64, device=dev)
+            dist.broadcast(t, 0)
+            n_windows = int(t.item())
+        windows += [timed_window() for _ in range(n_windows - 1)]
+    windows = sorted(windows)
+    # N > 1, for whoever has to explain the scaling curve: every rank's own time for the headline window (the slowest sets
+    # `value`), and (--full) the gradient all-reduce's own GPU time -- HIP events around the collective, one more untimed window
     per_rank = None
     allreduce_ms = None
     if dist.is_initialized():
-        k_med = unsorted.index(elapsed)
         t = torch.zeros(world, dtype=torch.float64, device=dev)
-        t[rank] = own_windows[k_med]
+        t[rank] = own_windows[0]
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         per = [1e3 * float(v) / args.steps for v in t.tolist()]
         per_rank = {"ms_per_step_min": round(min(per), 4), "ms_per_step_max": round(max(per), 4),
                     "ms_per_step_by_rank": [round(v, 4) for v in per],
-                    "what": "each rank's own wall clock for the reported (median) window, barrier to barrier"}
-        if graphs is not None and flat_opt:
+                    "what": "each rank's own wall clock for the headline window, barrier to barrier"}
+        if args.full and graphs is not None and flat_opt:
             pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
             dist.barrier()
             for i, (e0, e1) in enumerate(pairs):
@@ -984,9 +1034,35 @@ def main():
         raise SystemExit(3)
     if rank != 0:
         return
-    log(f"{value:.0f} molecules/s; measuring the forward kernels")
-    out = None
-    if rank == 0:
+    out = {"metric": "molecules/sec fwd+bwd, 3-layer MolKGNN on AID 1798", "value": round(value, 1),
+           "unit": "molecules/s", "n_gpus": (ranks_seen if ranks_seen is not None else world), "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+           "windows": {"n": len(windows), "steps_each": args.steps,
+                       "statistic": "value and ms_per_step: the first window" + (", the others only for the spread" if len(windows) > 1 else ""),
+                       "ms_per_step_min": round(1e3 * windows[0] / args.steps, 4),
+                       "ms_per_step_median": round(1e3 * windows[len(windows) // 2] / args.steps, 4),
+                       "ms_per_step_max": round(1e3 * windows[-1] / args.steps, 4),
+                       "timed_seconds_total": round(sum(windows), 4)},
+           "graph_replay": graphs is not None,           # False: the capture failed (or --no-graph) and the steps were launched eagerly
+           "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": "bf16 dot products, f32 otherwise" if args.variant == "bf16" else "f32",
+           # (f32 in, f32 out, f32 accumulation; the node-feature products are formed from exact fp16 halves of the f32
+           # operands unless MKGNN_FWD_SPLIT=0 / MKGNN_BWD_SPLIT=0 -- roofline.products; fp32-grade against float64)
+           "dtype_note": products_mode(args.variant)["forward"],
+           "data": "synthetic",
+           **({"dp_replicas_max_abs_diff": replicas_diff} if replicas_diff is not None else {}),
+           **dp_info,
+           "config": {"workload": f"{'all nine assays mixed' if args.assay == 'all9' else 'AID ' + args.assay} full set shape ({n_mol_assay} molecules, ~25 atoms / ~53 directed "
+                                  f"edges each), 3 layers, hidden_dim 32, kernels 10/20/30/50 per degree, "
+                                  f"batch {args.batch_size} molecules per GPU ({atoms:.0f} atoms), "
+                                  f"{nb} resident batches cycled, fwd+bwd"
+                                  + ("" if args.no_optimizer else "+AdamW") + (", grad all-reduce" if world > 1 else "")
+                                  + (", one hipGraph per batch" if graphs is not None else ", eager launches"),
+                      "variant": args.variant, "batch_size_per_gpu": args.batch_size,
+                      "parallelism": f"dp{world}"},
+           **({"outputs": dumped} if dumped is not None else {})}
+    if args.full:
+        log(f"{value:.0f} molecules/s; measuring the forward kernels")
         # ---- roofline of the kernel-convolution forward, N-hop layer (F = 110), live HIP events on this stream
         b = batches[0]
         plan = plan_from_data(b)
@@ -1101,31 +1177,7 @@ def main():
                     # the fp16 matrix rate, three instructions of 8 cycles in place of four of 32
                     "products": products_mode(args.variant),
                     "kernels": kernels}
-        out = {"metric": "molecules/sec fwd+bwd, 3-layer MolKGNN on AID 1798", "value": round(value, 1),
-               "unit": "molecules/s", "n_gpus": (ranks_seen if ranks_seen is not None else world), "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-               "windows": {"n": len(windows), "steps_each": args.steps, "statistic": "median",
-                           "ms_per_step_min": round(1e3 * windows[0] / args.steps, 4),
-                           "ms_per_step_max": round(1e3 * windows[-1] / args.steps, 4),
-                           "timed_seconds_total": round(sum(windows), 4)},
-               "graph_replay": graphs is not None,       # False: the capture failed (or --no-graph) and the steps were launched eagerly
-               "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": "bf16 dot products, f32 otherwise" if args.variant == "bf16" else "f32",
-               # (f32 in, f32 out, f32 accumulation; the node-feature products are formed from exact fp16 halves of the f32
-               # operands unless MKGNN_FWD_SPLIT=0 / MKGNN_BWD_SPLIT=0 -- roofline.products; fp32-grade against float64)
-               "dtype_note": products_mode(args.variant)["forward"],
-               "data": "synthetic",
-               **({"dp_replicas_max_abs_diff": replicas_diff} if replicas_diff is not None else {}),
-               **dp_info,
-               "config": {"workload": f"{'all nine assays mixed' if args.assay == 'all9' else 'AID ' + args.assay} full set shape ({n_mol_assay} molecules, ~25 atoms / ~53 directed "
-                                      f"edges each), 3 layers, hidden_dim 32, kernels 10/20/30/50 per degree, "
-                                      f"batch {args.batch_size} molecules per GPU ({atoms:.0f} atoms), "
-                                      f"{nb} resident batches cycled, fwd+bwd"
-                                      + ("" if args.no_optimizer else "+AdamW") + (", grad all-reduce" if world > 1 else "")
-                                      + (", one hipGraph per batch" if graphs is not None else ", eager launches"),
-                          "variant": args.variant, "batch_size_per_gpu": args.batch_size,
-                          "parallelism": f"dp{world}"},
-               "roofline": roofline}
+        out["roofline"] = roofline
         log(f"forward kernel {ms:.4f} ms ({ms_call:.4f} ms whole call), {gbs:.1f} GB/s algorithmic")
         # the legs below train a model of their own at N > 1 (this one's optimiser reads the flat all-reduce buffer)
         leg_model, leg_opt = model, opt
@@ -1152,7 +1204,7 @@ def main():
                 out["small_batch"] = {"error": f"{type(exc).__name__}: {exc}"}
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.assay)
-        print(json.dumps(out), flush=True)
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":

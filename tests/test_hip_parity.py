@@ -1650,7 +1650,7 @@ def test_bench_two_ranks_on_one_card_reports_the_data_parallel_keys(tmp_path):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MKGNN_ALLOW_SHARED_GPU="1", MKGNN_DIST_BACKEND="gloo", MKGNN_NO_SMALL_BATCH="1", MKGNN_NO_SHARD_EPOCH="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--windows", "2",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2", "--windows", "2",
                         "--batch-size", "256", "--fresh-batches", "0", "--no-cpu-baseline", "--roofline-reps", "2"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -1664,6 +1664,36 @@ def test_bench_two_ranks_on_one_card_reports_the_data_parallel_keys(tmp_path):
     assert ar["median"] > 0 and ar["bytes"] > 4 * 120_000
     db = line["dp_buffers"]
     assert db["max_abs_diff_before_sync"] > 0 and db["max_abs_diff"] == 0.0      # the ranks' batches differ; averaged once at the end
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain ``bench.py`` run: one window of exactly --steps steps, none of the --full measurements in the line, and
+    --dump-outputs writes the last timed step's loss, gradients and parameters -- the same ones in two runs with the same
+    arguments (seeded inputs and weights)."""
+    import json
+    import subprocess
+    import sys
+    _dev()
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+                            "--batch-size", "256", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 6 and line["windows"]["n"] == 1
+        assert line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "molecules/s"
+        assert not {"roofline", "cpu_baseline", "fresh_batches", "small_batch", "exact_fp32_instructions"} & set(line)
+        files = {f.name: np.load(f) for f in d.glob("*.npy")}
+        assert line["outputs"]["arrays"] == len(files) and sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert "loss.npy" in files and np.isfinite(files["loss.npy"]).all()
+        assert any(n.startswith("grad.") for n in files) and any(n.startswith("param.") for n in files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for n, a in dumps[0].items():
+        assert np.allclose(a, dumps[1][n], rtol=1e-5, atol=1e-6), n
 
 
 def test_one_pass_index_builder_matches_the_separate_builders():

@@ -1,4 +1,4 @@
-"""Print the fields of a bench.py line that a round's notes quote: tools/diag/bench_summary.py <file with the JSON line>"""
+"""Print the fields of a `bench.py --full` line that a round's notes quote: tools/diag/bench_summary.py <file with the JSON line>"""
 import json
 import sys
 
