@@ -2189,7 +2189,10 @@ int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
     hipStream_t st = (hipStream_t)stream;
     float* const z = (float*)((char*)ws + w.z);
     float* const dz = (float*)((char*)ws + w.dz);
-    hipError_t e = hipSuccess;
+    // (a reduction an earlier call left pending and nobody took: now, in front of this call's first launch -- its kernels
+    // overwrite the workspace slabs the pending one still reads, and read the dropout generator state it advances)
+    hipError_t e = launch_pending_tail_reduce(st);
+    if (e != hipSuccess) return api_hip_fail(who, e);
     // (1) z = W1[:, block] sim[block]   (d.HP = 32: H <= 32)
     b.sim = p->sim; b.ss = p->sim_stride; b.n = p->n_atoms; b.z = z;
     if (n_focal < p->n_atoms) {                          // atoms in no bucket: their sim row is zero, and so is their z row
@@ -2266,10 +2269,9 @@ int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
     add(m.slab + TAIL_BH, TAIL_SLAB, nbm, 1, 1, 1, p->grad_head_bias, 0);
     add(m.slab + TAIL_LOSS, TAIL_SLAB, nbm, 1, 1, 1, p->loss, 0);
     r.drop_p = p->dropout_p; r.rng = p->rng_state; r.rng_used = p->rng_used;
-    // (a reduction an earlier call left pending and nobody took: now, in front of this one)
-    e = launch_pending_tail_reduce(st);
-    if (e != hipSuccess) return api_hip_fail(who, e);
     if (p->defer_reduce && blk > 0) {                    // round 6: off the critical chain -- see mkgnn_tail_args.defer_reduce
+        e = hipGetLastError();                           // (this call's launches so far: a failed one is reported, not left pending)
+        if (e != hipSuccess) return api_hip_fail(who, e);
         std::lock_guard<std::mutex> lock(g_pending_reduce_mutex);
         PendingReduce* slot = pending_reduce_slot();
         slot->r = r; slot->blk = blk;

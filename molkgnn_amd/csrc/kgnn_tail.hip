@@ -70,7 +70,7 @@ __device__ __forceinline__ void gather_rows(const int* rp, const int* ec, const 
     int lo[NA], hi[NA], col[NA][4];
 #pragma unroll
     for (int u = 0; u < NA; ++u) {
-        const int at = at0 + 32 * u, ac = at < A ? at : A - 1;
+        const int at = at0 + 32 * u, ac = at < A ? at : max(A - 1, 0);
         lo[u] = rp[ac]; hi[u] = at < A ? rp[ac + 1] : lo[u];
     }
 #pragma unroll
@@ -201,9 +201,12 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
         m_next = m0 + nm;
         const int a0 = mptr[0], A = mptr[nm] - a0;
         const int ein0 = mein[0], nin = mein[nm] - ein0, eout0 = meout[0], nout = meout[nm] - eout0;
+        // (A == 0: a chunk of empty molecules only -- the padding of a batch with fewer padding atoms than padding molecules,
+        // molkgnn_amd.padding -- whose a0 may be one past the last atom and ein0 / eout0 one past the last edge.  No load below
+        // leaves the arrays then: the per-atom phases find no atom, the per-molecule one gives the molecules their rows)
         // ---- P1: per atom -- molecule, edge offsets; the z rows (one coalesced 128-byte row per slot and pass)
         if (t <= A) {
-            const int n = a0 + (t < A ? t : A - 1);
+            const int n = A > 0 ? a0 + (t < A ? t : A - 1) : 0;
             const int mol = a.atom_mol[n] - (int)m0;
             const int ri = a.rin[a0 + t] - ein0, ro = a.rout[a0 + t] - eout0;      // (t == A: the end of the last atom's edges)
             if (t < A) amol[t] = mol;
@@ -211,18 +214,19 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
         }
         {
             f32x4 zr[AC / 32];
+            const int zlast = A > 0 ? a0 + A - 1 : 0;
 #pragma unroll
-            for (int q = 0; q < AC / 32; ++q) { const int at = as + 32 * q; zr[q] = *(const f32x4*)(a.z + (int64_t)(a0 + (at < A ? at : A - 1)) * 32 + 4 * l); }
+            for (int q = 0; q < AC / 32; ++q) { const int at = as + 32 * q; zr[q] = *(const f32x4*)(a.z + (int64_t)(at < A ? a0 + at : zlast) * 32 + 4 * l); }
 #pragma unroll
             for (int q = 0; q < AC / 32; ++q) { const int at = as + 32 * q; if (at < A) *(f32x4*)(dzb + at * HP + 4 * l) = zr[q]; }
         }
         {
             int ci[EC / NT], co[EC / NT];                // (all four loads in flight: EC / NT = 2 edges each way per thread)
 #pragma unroll
-            for (int u = 0; u < EC / NT; ++u) {
+            for (int u = 0; u < EC / NT; ++u) {          // (no edge one way: nothing to read -- ein0 may be the end of cin)
                 const int i = t + NT * u;
-                ci[u] = a.cin[ein0 + (i < nin ? i : 0)];
-                co[u] = a.cout[eout0 + (i < nout ? i : 0)];
+                ci[u] = a.cin[nin > 0 ? ein0 + (i < nin ? i : 0) : 0];
+                co[u] = a.cout[nout > 0 ? eout0 + (i < nout ? i : 0) : 0];
             }
 #pragma unroll
             for (int u = 0; u < EC / NT; ++u) {
@@ -321,9 +325,9 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
             f32x4 p[AC / 32], de[AC / 32];
 #pragma unroll
             for (int u = 0; u < AC / 32; ++u) {
-                const int at = as + 32 * u, ac = at < A ? at : A - 1;
+                const int at = as + 32 * u, ac = at < A ? at : A - 1;        // (A == 0: row -1 of zp is W2s' last, inside LDS)
                 p[u] = *(const f32x4*)(zp + ac * HP + 4 * l);
-                de[u] = *(const f32x4*)(emol + amol[ac] * HP + 4 * l);
+                de[u] = *(const f32x4*)(emol + (A > 0 ? amol[ac] : 0) * HP + 4 * l);      // (A == 0: amol holds nothing of this chunk)
             }
 #pragma unroll
             for (int u = 0; u < AC / 32; ++u) {

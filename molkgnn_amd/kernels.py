@@ -69,8 +69,11 @@ class KernelConv(Module):
     def degree(self):
         return self.x_support.shape[1]
 
+    OP_PARAM_NAMES = ("x_center", "x_support", "edge_attr_support", "p_support",
+                      "support_attr_sc_weight", "center_attr_sc_weight", "edge_attr_support_sc_weight")
+
     def op_params(self):
-        """The seven tensors the HIP operator takes for this degree."""
+        """The seven tensors the HIP operator takes for this degree (``OP_PARAM_NAMES``, in this order)."""
         return [self.x_center, self.x_support, self.edge_attr_support, self.p_support,
                 self.support_attr_sc_weight, self.center_attr_sc_weight, self.edge_attr_support_sc_weight]
 
@@ -169,7 +172,9 @@ class BaseKernelSetConv(Module):
         convs = self.fixed_kernelconv_set if which == "fixed" else self.trainable_kernelconv_set
         if hit is not None:
             params, E, owners = hit
-            if all(c is o and (c is None or c._parameters.get("x_center") is params[7 * i])
+            # (every one of a degree's seven entries: a re-assigned x_support or sc weight is a new object the kernels must read)
+            if all(c is o and (c is None or all(c._parameters.get(name) is params[7 * i + k]
+                                                for k, name in enumerate(KernelConv.OP_PARAM_NAMES)))
                    for i, (c, o) in enumerate(zip(convs, owners))):
                 return list(params), E
         some = next(c for c in convs if c is not None)

@@ -690,6 +690,15 @@ class deferred_tail_reduce:
 _TAIL_DEFER_ENABLED = os.environ.get("MKGNN_TAIL_DEFER", "1") != "0"
 
 
+def _tail_grads_adopted(params) -> bool:
+    """Nothing reads a deferred tail gradient before the reduction has written it: no parameter has a tensor hook
+    (``register_hook``) or a post-accumulate hook (``register_post_accumulate_grad_hook``), and every one is contiguous, so
+    AccumulateGrad adopts the gradient tensor as ``.grad`` instead of copying it into the parameter's strides.  (A hook on the
+    AccumulateGrad node itself is not visible from here: see ``train.training_step``.)"""
+    return all(p is None or (not p._backward_hooks and not getattr(p, "_post_accumulate_grad_hooks", None) and p.is_contiguous())
+               for p in params)
+
+
 class _TailFn(torch.autograd.Function):
     """``BCEWithLogitsLoss()(ffn(dropout(readout(propagate(sim)))), y)`` with every gradient for d loss = 1 in the same launch
     (``mkgnn_tail_fused``); the backward hands them out (scaled, if the incoming gradient is not the registered unit seed)."""
@@ -734,8 +743,9 @@ class _TailFn(torch.autograd.Function):
         a.grad_lin1_weight, a.grad_lin1_bias = gw1.data_ptr(), _lib.ptr(gb1)
         a.grad_lin2_weight, a.grad_lin2_bias = gw2.data_ptr(), _lib.ptr(gb2)
         a.grad_head_weight, a.grad_head_bias = gwh.data_ptr(), _lib.ptr(gbh)
-        # (deferred only where a backward will follow in the same region: the caller of deferred_tail_reduce promises it)
-        ctx.deferred = bool(_DEFER_TAIL_REDUCE and ctx.needs_input_grad[0])
+        # (deferred only where a backward will follow in the same region: the caller of deferred_tail_reduce promises it -- and only
+        # where autograd hands the six gradients straight to .grad: see _tail_grads_adopted)
+        ctx.deferred = bool(_DEFER_TAIL_REDUCE and ctx.needs_input_grad[0] and _tail_grads_adopted((w1, b1, w2, b2, wh, bh)))
         a.defer_reduce = 1 if ctx.deferred else 0
         ctx.params = (w1, b1, w2, b2, wh, bh)
         ctx.dev = dev

@@ -8,6 +8,7 @@ name (``model.py:373-382``).  Logging, checkpoints, metrics and the LR schedule 
 """
 from __future__ import annotations
 
+import weakref
 from typing import Optional
 
 import torch
@@ -102,7 +103,13 @@ def training_step(model, batch, optimizer=None) -> torch.Tensor:
     """``loss = model.loss(batch); backward(loss); optimizer.step()`` as ONE unit (gradients start out as None): what a training loop
     does per batch, with the licence that gives -- nothing reads the loss or a parameter gradient between the forward and the
     optimiser, so the fused tail's last reduction leaves the critical chain (``readout.deferred_tail_reduce``).  Returns the loss
-    (complete, in stream order, when this returns).  Same kernels, same arithmetic, same bits as the three calls."""
+    (complete, in stream order, when this returns).  Same kernels, same arithmetic, same bits as the three calls.
+
+    The deferral is skipped (the reduction runs in the forward, as outside a region) when a tail parameter -- the readout's
+    ``graph_embedding_lin1`` / ``graph_embedding_lin2`` and ``ffn`` -- has a tensor hook or a post-accumulate-grad hook, or is
+    not contiguous.  A hook registered on a parameter's AccumulateGrad node (``p.view_as(p).grad_fn.next_functions[0][0]``, the
+    older DDP mechanism) cannot be seen from the parameter: such code opts out with ``MKGNN_TAIL_DEFER=0`` or calls
+    ``model.loss`` + ``backward`` itself, outside ``training_step``."""
     from .readout import deferred_tail_reduce
     model.zero_grad(set_to_none=True)
     with deferred_tail_reduce(batch.x.device if batch.x.is_cuda else None):
@@ -160,17 +167,23 @@ class CapturedSteps:
             for batch in resident_batches:
                 loss = steps(batch)            # a 0-d tensor, valid until the next call with the SAME batch
 
-    A batch is recognised by the identity of its object and of its ``x`` storage; it must stay alive and unchanged (a batch whose
-    tensors are refilled in place belongs in ``padding.StaticBatch``, which is built for that).  Each captured batch keeps its own
-    graph (and the memory of one step's activations): ``max_graphs`` bounds their number, batches beyond it stay eager.
-    ``optimizer`` must be capturable (``configure_optimizer(..., capturable=True)`` or the fused AdamW)."""
+    A batch is recognised by the identity of its object and of its ``x`` tensor (held weakly until it is captured: a batch that
+    is freed leaves no count behind, and a new batch at a recycled address starts from zero); it must stay alive and unchanged to
+    be captured (a batch whose tensors are refilled in place belongs in ``padding.StaticBatch``, which is built for that).  Each
+    captured batch keeps its own graph (and the memory of one step's activations): ``max_graphs`` bounds their number, batches
+    beyond it stay eager.  At most ``4 * max_graphs`` uncaptured batches are counted; beyond that the least recently seen is
+    forgotten.  A streaming loader whose batches are seen once is therefore never captured and runs ``training_step``.
+    ``optimizer`` must be capturable to be captured at all (``configure_optimizer(..., capturable=True)`` or the fused AdamW);
+    with any other optimiser every step stays eager."""
 
     def __init__(self, model: torch.nn.Module, optimizer=None, warmup: int = 2, max_graphs: int = 64):
         self.model, self.optimizer = model, optimizer
         self.warmup, self.max_graphs = int(warmup), int(max_graphs)
-        self._seen: dict = {}
-        self._graphs: dict = {}
+        self.max_seen = 4 * self.max_graphs
+        self._seen: dict = {}          # key -> [visits, weakref to the batch, weakref to its x], least recently seen first
+        self._graphs: dict = {}        # key -> (graph, loss, batch, x)
         self._stream = None
+        self._capturable = _optimizer_capturable(optimizer)
 
     def _key(self, batch):
         return (id(batch), batch.x.data_ptr(), batch.x._version)
@@ -178,17 +191,36 @@ class CapturedSteps:
     def _eager(self, batch):
         return training_step(self.model, batch, self.optimizer).detach()
 
+    def _count(self, key, batch) -> int:
+        """Visits of ``batch`` before this one (and this one recorded)."""
+        hit = self._seen.pop(key, None)
+        n = hit[0] if hit is not None and hit[1]() is batch and hit[2]() is batch.x else 0
+        if n == 0:
+            me = weakref.ref(self)
+
+            def forget(ref, key=key):              # (the batch or its x is gone: so is its count -- unless the slot was reused)
+                d = None if me() is None else me()._seen
+                entry = None if d is None else d.get(key)
+                if entry is not None and (entry[1] is ref or entry[2] is ref):
+                    del d[key]
+            hit = [0, weakref.ref(batch, forget), weakref.ref(batch.x, forget)]
+        hit[0] = n + 1
+        self._seen[key] = hit
+        while len(self._seen) > self.max_seen:
+            del self._seen[next(iter(self._seen))]
+        return n
+
     def __call__(self, batch):
         key = self._key(batch)
         hit = self._graphs.get(key)
-        if hit is not None:
-            graph, static_loss, _keep = hit
+        if hit is not None and hit[2] is batch and hit[3] is batch.x:
+            graph, static_loss = hit[0], hit[1]
             graph.replay()
             return static_loss
-        n = self._seen.get(key, 0)
-        self._seen[key] = n + 1
-        if n < self.warmup or len(self._graphs) >= self.max_graphs or not batch.x.is_cuda:
+        n = self._count(key, batch)
+        if n < self.warmup or len(self._graphs) >= self.max_graphs or not batch.x.is_cuda or not self._capturable:
             return self._eager(batch)
+        self._seen.pop(key, None)
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=batch.x.device)
         side = self._stream
@@ -199,6 +231,17 @@ class CapturedSteps:
             with torch.cuda.graph(graph, stream=side):
                 static_loss = training_step(self.model, batch, self.optimizer).detach()
         torch.cuda.current_stream(batch.x.device).wait_stream(side)
-        self._graphs[key] = (graph, static_loss, batch)      # (the batch object is kept: its id stays its own)
+        self._graphs[key] = (graph, static_loss, batch, batch.x)     # (the batch is kept: its id and x's address stay its own)
         graph.replay()                                        # (a capture launches nothing: this visit's step)
         return static_loss
+
+
+def _optimizer_capturable(optimizer) -> bool:
+    """Can ``optimizer.step()`` be captured and replayed: the fused AdamW (step counters on the device), or a torch optimiser
+    with ``capturable=True`` in every parameter group.  (None: no optimiser step to capture.)"""
+    if optimizer is None:
+        return True
+    from .optim import FusedAdamW
+    if isinstance(optimizer, FusedAdamW):
+        return True
+    return all(g.get("capturable", False) for g in optimizer.param_groups)

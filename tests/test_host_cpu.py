@@ -474,3 +474,32 @@ def test_split_fp16_scales_are_exact_powers_of_two_over_every_exponent():
     def prop(eb, mant):
         check(eb, mant)
     prop()
+
+
+def test_bank_params_cache_follows_every_reassigned_parameter():
+    """``KernelSetConv._bank_params`` remembers its flat parameter list while the banks still hold the very Parameter objects
+    it was made of -- all seven of a degree, not only ``x_center``: a re-assigned ``x_support`` or score weight (a re-init, a
+    parametrisation) must reach the kernels, which would otherwise read the old tensor while the optimiser updates the new."""
+    from molkgnn_amd.kernels import KernelSetConv
+    names = ("x_center", "x_support", "edge_attr_support", "p_support", "support_attr_sc_weight", "center_attr_sc_weight",
+             "edge_attr_support_sc_weight")                      # KernelConv.op_params(), in its order
+    torch.manual_seed(0)
+    ksc = KernelSetConv(10, 20, 30, 50, D=3, node_attr_dim=28, edge_attr_dim=7)
+    x = torch.zeros(4, 28)
+    first, E = ksc._bank_params("train", x)
+    again, E2 = ksc._bank_params("train", x)
+    assert E2 == E and len(again) == len(first) == 28
+    assert all(a is b for a, b in zip(again, first))              # nothing re-assigned: the cached objects
+    for d in range(4):
+        conv = ksc.trainable_kernelconv_set[d]
+        assert all(p is getattr(conv, n) for p, n in zip(conv.op_params(), names))
+        for k, name in enumerate(names):
+            old = getattr(conv, name)
+            new = torch.nn.Parameter(torch.randn_like(old), requires_grad=old.requires_grad)
+            setattr(conv, name, new)
+            params, _ = ksc._bank_params("train", x)
+            assert params[7 * d + k] is new, (d, name)
+            assert params[7 * d + k] is not old
+            assert all(p is q for p, q in zip(params, ksc._bank_params("train", x)[0]))    # (and cached again)
+    expect = [p for c in ksc.trainable_kernelconv_set for p in c.op_params()]
+    assert all(p is q for p, q in zip(ksc._bank_params("train", x)[0], expect))
