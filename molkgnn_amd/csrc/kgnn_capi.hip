@@ -630,7 +630,8 @@ int mkgnn_kernelsetconv_backward(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE]
     for (int i = 0; i < 4; ++i) { L[i] = banks[i].num_kernels; K += L[i]; }
     if (grad_out_stride < K || (n_atoms && !grad_out)) return fail("%s: bad grad_out", who);
     if (grad_x && grad_x_stride < F) return fail("%s: bad grad_x stride", who);
-    if (grad_x && n_atoms && (!scatter_rowptr || !scatter_rows)) return fail("%s: scatter CSR is null", who);
+    // (no atom of degree 1..4 -- a batch without bonds: nothing reaches x, the gradient is zero and no CSR is read)
+    if (grad_x && n_atoms && n_edges > 0 && (!scatter_rowptr || !scatter_rows)) return fail("%s: scatter CSR is null", who);
     WorkspaceLayout w = make_layout(L, F, E, n_atoms, n_edges);
     if (workspace_bytes < w.total || !workspace) return fail("%s: workspace of %zu bytes, need %zu", who, workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
@@ -833,7 +834,10 @@ int mkgnn_kernelsetconv_backward(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE]
     }
     { BwdTimer t(st_reduce, 3); e = launch_bank_reduce_all(reduce, st_reduce); }   // one launch for the four banks
     if (e != hipSuccess) return hip_fail("bank gradient reduce launch", e);
-    if (grad_x) {
+    if (grad_x && n_edges == 0) {
+        if (n_atoms) e = hipMemset2DAsync(grad_x, (size_t)grad_x_stride * sizeof(float), 0, (size_t)F * sizeof(float), (size_t)n_atoms, st);
+        if (e != hipSuccess) return hip_fail("zero input gradient", e);
+    } else if (grad_x) {
         BwdTimer t(st, 4);
         e = launch_backward_gather((const float*)(ws + w.contrib), (F + 3) / 4 * 4, base, scatter_rowptr, scatter_rows, x,
                                    x_stride, inv_norm, n_atoms, F, grad_x, grad_x_stride, !force_generic, st, rows_split);

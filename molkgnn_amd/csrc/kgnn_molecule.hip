@@ -887,7 +887,8 @@ __device__ __forceinline__ void molecule_step_body(MolArgsP ap, float* lds) {
         for (int p = 0; p < 2; ++p) {
             const int RT = Y.pass_rows[p] >> 4;
             if (p == 1 && d4_valu) { MOL_STAMP(); MOL_STAMP(); continue; }
-            if (RT == 0) continue;
+            // (a pass without rows -- no kernels of degree 1..3, or none of degree 4 -- has no products, but pass 0 still fetches
+            // pass 1's bank rows and runs the degree-4 pairs on the vector pipe: it is not skipped)
 #pragma unroll
             for (int t = 0; t < MOL_TPW; ++t) {
                 const int nt = wave + MOL_NW * t;

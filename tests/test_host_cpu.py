@@ -426,6 +426,87 @@ def test_molecule_chunk_table_and_abi_structs():
     assert lib.mkgnn_molecule_workspace_bytes(ctypes.byref(net(3, (10, 20, 30, 50))), 28, 400, 16) > 7_000_000
 
 
+
+def _molecule_net(counts, layers, x_dim, E, H, G):
+    """``mkgnn_molecule_net`` of a MolKGNNNet shape (kernel counts of every layer = ``counts``), for the shape query."""
+    from molkgnn_amd import _lib
+    st = _lib.MoleculeNet()
+    st.num_layers, st.E = layers, E
+    F = x_dim
+    for li in range(min(layers, 4)):
+        st.layer[li].F = F
+        for d in range(4):
+            st.layer[li].bank[d].num_kernels = counts[d]
+        F = sum(counts)
+    st.readout.F, st.readout.H, st.readout.G = F, H, G
+    return st
+
+
+def test_molecule_shape_query_at_and_one_step_past_every_limit():
+    """``mkgnn_molecule_supported`` takes every shape AT a limit and refuses each one step past it: x_dim 33, E 9, L_d 65,
+    K 113, first-pass rows 272, 5 * L4 = 260, H or G 65, 5 layers.  ``mkgnn_tail_supported`` takes H, G <= 32 only."""
+    from molkgnn_amd import _lib
+    from tests._molecule_oracle import MOLECULE_LIMIT_SHAPES
+    lib = _lib.load()
+
+    def ok(x_dim, E, counts, layers, H, G=None):
+        return lib.mkgnn_molecule_supported(ctypes.byref(_molecule_net(counts, layers, x_dim, E, H, H if G is None else G)), x_dim)
+    for name, (x_dim, E, counts, layers, H) in MOLECULE_LIMIT_SHAPES.items():
+        assert ok(x_dim, E, counts, layers, H) == 1, name
+    assert ok(32, 8, (20, 24, 36, 32), 4, 64) == 1                 # 4 layers at the widest shape
+    assert ok(33, 8, (20, 24, 36, 32), 3, 64) == 0                 # x_dim 33
+    assert ok(32, 9, (20, 24, 36, 32), 3, 64) == 0                 # E 9
+    assert ok(5, 3, (65, 0, 0, 0), 2, 5) == 0                      # L_d 65
+    assert ok(5, 3, (0, 0, 0, 65), 2, 5) == 0
+    assert ok(32, 8, (20, 24, 36, 33), 3, 64) == 0                 # K 113
+    assert ok(32, 8, (21, 24, 36, 31), 3, 64) == 0                 # 2*21 + 3*24 + 4*36 = 258 -> 272 rows (K = 112)
+    assert ok(28, 7, (0, 0, 0, 52), 2, 33) == 0                    # 5 * 52 = 260 -> 272 rows
+    assert ok(32, 8, (20, 24, 36, 32), 3, 65) == 0                 # H = G = 65
+    assert ok(32, 8, (20, 24, 36, 32), 3, 64, 65) == 0             # G 65
+    assert ok(32, 8, (20, 24, 36, 32), 3, 65, 64) == 0             # H 65
+    assert ok(32, 8, (20, 24, 36, 32), 5, 64) == 0                 # 5 layers
+    assert ok(1, 1, (0, 0, 0, 0), 1, 1) == 0                       # no kernel at all
+    # the fused tail: H, G <= 32 with the block-row readout's K <= 255, L_d <= 64
+    for H, G, Ls in ((1, 1, (10, 20, 30, 50)), (5, 7, (5, 10, 15, 25)), (17, 32, (1, 1, 1, 1)), (32, 1, (3, 0, 5, 0)),
+                     (32, 32, (64, 64, 64, 63))):
+        assert lib.mkgnn_tail_supported(sum(Ls), H, G, _lib.Int32x4(*Ls)) == 1, (H, G, Ls)
+    for H, G, Ls in ((33, 32, (10, 20, 30, 50)), (32, 33, (10, 20, 30, 50)), (32, 32, (65, 0, 0, 0)), (32, 32, (64, 64, 64, 64))):
+        assert lib.mkgnn_tail_supported(sum(Ls), H, G, _lib.Int32x4(*Ls)) == 0, (H, G, Ls)
+
+
+def test_topology_builder():
+    """tests/_topologies.py: every bond stored once in each direction (two consecutive edges, one attribute row), the sizes
+    and degrees asked for, molecules contiguous, receptive fields for every atom of degree 1..4 and for no other."""
+    from tests import _topologies as T
+    specs = [T.single(), T.pair(), T.tree(12), T.star(4), T.circulant(128), T.tree(32), T.tree(33), T.tree(64), T.tree(65),
+             T.star(5), T.single()]
+    b = T.batch_of(specs, F=9, E=3, seed=4)
+    sizes = T.molecule_sizes(b)
+    assert sizes == [1, 2, 12, 5, 128, 32, 33, 64, 65, 6, 1] and b.num_graphs == len(specs)
+    assert torch.equal(b.batch, torch.repeat_interleave(torch.arange(len(specs)), torch.tensor(sizes)))     # contiguous
+    ei = b.edge_index
+    assert b.x.shape == (sum(sizes), 9) and b.edge_attr.shape == (ei.shape[1], 3) and b.p.shape == (sum(sizes), 3)
+    assert torch.equal(ei[0, 0::2], ei[1, 1::2]) and torch.equal(ei[1, 0::2], ei[0, 1::2])   # both directions, consecutive
+    assert torch.equal(b.edge_attr[0::2], b.edge_attr[1::2])
+    keys = (ei[0] * b.x.shape[0] + ei[1]).tolist()
+    assert len(set(keys)) == len(keys) and bool((ei[0] != ei[1]).all())                       # each direction once, no loops
+    assert bool((b.batch[ei[0]] == b.batch[ei[1]]).all())
+    deg = T.degrees(b)
+    ptr = [0] + np.cumsum(sizes).tolist()
+    per_mol = [deg[a:c] for a, c in zip(ptr, ptr[1:])]
+    assert per_mol[0].tolist() == [0] and per_mol[1].tolist() == [1, 1] and per_mol[10].tolist() == [0]
+    assert per_mol[3].tolist() == [4, 1, 1, 1, 1]
+    assert per_mol[9].tolist() == [5, 1, 1, 1, 1, 1]                                          # the degree-5 hub
+    assert per_mol[4].tolist() == [4] * 128 and int((ei[0] >= ptr[4]).logical_and(ei[0] < ptr[5]).sum()) == 512
+    for m in (2, 5, 6, 7, 8):
+        assert int(per_mol[m].max()) == 4 and int(per_mol[m].min()) >= 1, m                   # trees: degree-4 atoms present
+    assert int(ei.shape[1]) // 2 == sum(len(bonds) for _, bonds in specs)
+    for d in range(1, 5):
+        sel = b.__dict__[f"selected_index_deg{d}"]
+        assert torch.equal(sel, (deg == d).nonzero().view(-1)), d
+        assert b.__dict__[f"nei_index_deg{d}"].numel() == d * sel.numel()
+    assert T.batch_of(specs, F=9, E=3, seed=4).x.equal(b.x)                                   # deterministic from the seed
+
 def test_split_fp16_scales_are_exact_powers_of_two_over_every_exponent():
     """The power-of-two scales of the split-fp16 products (csrc/kgnn_split.h), evaluated on the host by the
     very functions the kernels compile (``mkgnn_debug_split_scales``): for EVERY biased exponent and random mantissas --

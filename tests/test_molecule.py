@@ -10,9 +10,10 @@ import torch
 
 from oracle import kgnn_oracle as O
 
-pytestmark = pytest.mark.gpu
+from tests import _f64 as F64
+from tests._molecule_oracle import _check_against_oracle, _forced_from_capture
 
-FWD_TOL = 1e-5
+pytestmark = pytest.mark.gpu
 
 
 def _dev():
@@ -35,54 +36,6 @@ def _model(counts, layers, hidden, seed, dev, train_bn):
     model = model.to(dev)
     model.train(train_bn)
     return model, state
-
-
-def _forced_from_capture(cap, layers):
-    forced = []
-    for li in range(layers):
-        idx = []
-        for d in range(4):
-            sv = cap["saved"][li][d]
-            idx.append(None if sv is None else sv[0][..., 3].contiguous().view(torch.int32).t().cpu().long())
-        forced.append(idx)
-    return forced
-
-
-def _check_against_oracle(model, state, b, layers, train_bn, emb, cap, cot, grads_of):
-    """Layer by layer (tie-aware) and end to end (embedding, every parameter gradient) against the oracle replayed with the
-    build's permutation choices."""
-    forced = _forced_from_capture(cap, layers)
-    ostate = {k: v.clone() for k, v in state.items()}
-    h_o = O.batch_norm(b.x, ostate["node_batch_norm.weight"], ostate["node_batch_norm.bias"],
-                       ostate["node_batch_norm.running_mean"].clone(), ostate["node_batch_norm.running_var"].clone(), train_bn)
-    for i in range(layers):
-        per_degree = O.kernelset_params(ostate, f"gnn.layers.{i}.")
-        sim = cap["sims"][i].cpu()
-        assert O.kernelset_tie_aware_mismatch(per_degree, h_o, b, i == layers - 1, sim, forced[i]) == 0, f"layer {i}"
-        sim_o = O.kernelsetconv(per_degree, h_o, b, i == layers - 1, form="faithful", forced_idx=forced[i])
-        assert torch.allclose(sim, sim_o, atol=FWD_TOL, rtol=0), (i, float((sim - sim_o).abs().max()))
-        h_o = O.propagate_add(b.edge_index, sim_o)
-    ostate = {k: (v.requires_grad_(True) if v.dtype.is_floating_point and "running" not in k else v) for k, v in ostate.items()}
-    if "node_batch_norm.running_mean" in ostate:
-        ostate["node_batch_norm.running_mean"] = ostate["node_batch_norm.running_mean"].clone()
-        ostate["node_batch_norm.running_var"] = ostate["node_batch_norm.running_var"].clone()
-    emb_o = O.molkgnnnet(ostate, b, layers, training_bn=train_bn, form="faithful", forced_idx=forced)
-    scale = max(1.0, float(emb_o.detach().abs().max()))
-    assert float((emb.detach().cpu() - emb_o.detach()).abs().max()) <= 5e-5 * scale
-    if cot is None:
-        return ostate, emb_o
-    (emb_o * cot).sum().backward()
-    checked = 0
-    for nm, got in grads_of.items():
-        ref = ostate[nm].grad
-        if got is None:
-            assert ref is None or float(ref.abs().max()) == 0.0, nm
-            continue
-        assert ref is not None, nm
-        err = float((got.cpu() - ref).abs().max())
-        assert err <= 5e-5 * max(1.0, float(ref.abs().max())) + 1e-3 * float(ref.abs().max()), (nm, err, float(ref.abs().max()))
-        checked += 1
-    return checked
 
 
 @pytest.mark.parametrize("mols,train_bn,counts,layers,hidden", [
@@ -110,7 +63,8 @@ def test_network_forward_and_backward_against_the_oracle(mols, train_bn, counts,
     (emb * cot.to(dev)).sum().backward()
     assert calls == [0, 6], calls                          # ... and their backward (recompute + gradient of the embedding)
     grads = {nm: prm.grad for nm, prm in model.named_parameters()}
-    checked = _check_against_oracle(model, state, b, layers, train_bn, emb, fwd_cap, cot, grads)
+    checked = _check_against_oracle(model, state, b, layers, train_bn, emb, fwd_cap, cot, grads,
+                                    tag=f"network/{mols}/{train_bn}/{counts}/{layers}/{hidden}")
     present = sum(1 for d in range(1, 5) if getattr(b, f"selected_index_deg{d}").numel() > 0)
     assert checked >= 6 * present * layers + 6
     if train_bn:                                            # running statistics moved once (the recompute does not move them again)
@@ -155,7 +109,7 @@ def test_large_molecules_and_packed_chunks(monkeypatch):
     cot = torch.randn(24, 32, generator=torch.Generator().manual_seed(2))
     (emb * cot.to(dev)).sum().backward()
     grads = {nm: prm.grad for nm, prm in model.named_parameters()}
-    assert _check_against_oracle(model, state, b, 3, True, emb, fwd_cap, cot, grads) > 60
+    assert _check_against_oracle(model, state, b, 3, True, emb, fwd_cap, cot, grads, tag="large_molecules") > 60
 
 
 @pytest.mark.parametrize("mols,p_drop", [(16, 0.0), (256, 0.0), (16, 0.25)])
@@ -211,6 +165,12 @@ def test_training_step_loss_and_gradients(mols, p_drop, monkeypatch):
             assert err <= 2e-6 * max(1.0, float(ref.abs().max())) + 1e-3 * float(ref.abs().max()), (nm, err, float(ref.abs().max()))
             checked += 1
         assert checked >= 70
+        # the float64 leg: loss, pred and every gradient
+        f64 = F64.network(gstate, b, 3, True, forced, torch.float64, head=(state["ffn.weight"], state["ffn.bias"], b.y))
+        f32 = {"loss": loss_o.detach(), "pred": pred_o.detach().view(-1), "ffn.weight": w.grad, "ffn.bias": bias.grad,
+               **{nm: ostate[nm].grad for nm in grads if ostate[nm].grad is not None}}
+        got = {"loss": loss, "pred": cap["pred"], **grads, "ffn.weight": model.ffn.weight.grad, "ffn.bias": model.ffn.bias.grad}
+        assert F64.check(got, f32, f64, f"training_step/{mols}") == checked + 2
     else:
         # the per-operator head on the SAME embedding with the same generator state draws the same mask
         emb = cap["emb"].detach().clone().requires_grad_(True)
@@ -345,7 +305,7 @@ def test_zero_norm_rows_through_the_one_launch_step(monkeypatch):
     assert int((x0.norm(dim=1) == 0).sum()) >= b.x.shape[0] // 2 - 1 and int((x0.norm(dim=1) > 1e-3).sum()) >= b.x.shape[0] // 2 - 1
     grads = {nm: prm.grad for nm, prm in model.named_parameters()}
     # (gradients through 1 / eps are 1e7-sized: the relative part of the criterion carries them)
-    assert _check_against_oracle(model, state, b, 3, False, emb, fwd_cap, cot, grads) > 60
+    assert _check_against_oracle(model, state, b, 3, False, emb, fwd_cap, cot, grads, tag="zero_norm_rows") > 60
 
 
 @pytest.mark.parametrize("mols", [24, 64, 256])
