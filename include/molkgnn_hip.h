@@ -38,7 +38,15 @@ extern "C" {
 #endif
 
 #define MKGNN_MAX_DEGREE 4
-#define MKGNN_ABI_VERSION 7
+#define MKGNN_ABI_VERSION 8
+
+/* Loss kinds of the single-task head (ABI v8): the loss over the n counted molecules and its d loss / d pred_g.
+ *   BCE_MEAN    mean of BCEWithLogits (data.py:37)          (sigmoid(p) - y) / n
+ *   SQERR_MEAN  sum (p - y)^2 / n     (MSELoss())           2 (p - y) / n
+ *   SQERR_SUM   sum (p - y)^2         (MSELoss(reduction='sum'): the docking-score task, data.py:49-53)   2 (p - y) */
+#define MKGNN_LOSS_BCE_MEAN 0
+#define MKGNN_LOSS_SQERR_MEAN 1
+#define MKGNN_LOSS_SQERR_SUM 2
 
 /* One KernelConv's parameters (reference kernels.py:50-84).  The three score
  * weights are the 0-d parameters support_attr_sc_weight, center_attr_sc_weight
@@ -394,6 +402,8 @@ typedef struct mkgnn_tail_args {
      * layer's gradient waits for), or by mkgnn_tail_flush, whichever comes first.  grad_sim is complete when this call's launches
      * are.  The caller MUST call mkgnn_tail_flush(stream) before anything reads those outputs on `stream`. */
     int32_t defer_reduce;
+    /* (ABI v8) MKGNN_LOSS_*: the loss of the head (0: BCE with logits, mean -- as before) */
+    int32_t loss_kind;
 } mkgnn_tail_args;
 int mkgnn_tail_supported(int32_t K, int32_t H, int32_t G, const int32_t num_kernels[MKGNN_MAX_DEGREE]);
 size_t mkgnn_tail_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols);
@@ -564,6 +574,31 @@ int mkgnn_bce_head_fused(const float* emb, int64_t emb_stride, int64_t n_rows, i
                          float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI v8) The five entry points above for any loss kind (MKGNN_LOSS_*; an unknown kind is an error): same arguments behind
+ * loss_kind, same workspace (mkgnn_bce_head_workspace_bytes), same dropout generator protocol and mask, same fixed-order
+ * reductions.  loss_kind = MKGNN_LOSS_BCE_MEAN gives the mkgnn_bce_head_* results bit for bit. */
+int mkgnn_head_loss_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                            const float* weight, const float* bias, const float* target,
+                            float* pred, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int mkgnn_head_loss_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                             const float* weight, const float* target, const float* pred, const float* grad_loss,
+                             float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int mkgnn_head_loss_dropout_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                                    const float* weight, const float* bias, const float* target, float dropout_p,
+                                    int64_t* rng_state, int64_t* rng_used, float* pred, float* loss,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int mkgnn_head_loss_dropout_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                                     const float* weight, const float* target, const float* pred,
+                                     const float* grad_loss, float dropout_p, const int64_t* rng_used,
+                                     float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int mkgnn_head_loss_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                          const float* weight, const float* bias, const float* target, float dropout_p,
+                          int64_t* rng_state, int64_t* rng_used, float* pred, float* loss,
+                          float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* AdamW step over all trainable tensors of the model in one launch (reference model.py:368-385: torch.optim.AdamW,
  * two parameter groups -- kernel banks without weight decay).  Per tensor: param / grad [numel] fp32 contiguous,
  * state [mkgnn_adamw_state_floats(numel)] = exp_avg, exp_avg_sq, step count (as a float, advanced by this call), two reserved
@@ -678,6 +713,8 @@ typedef struct mkgnn_molecule_batch {
 #define MKGNN_MOLECULE_HEAD      1   /* dropout -> ffn -> BCE-with-logits against `target`; writes pred, loss */
 #define MKGNN_MOLECULE_BACKWARD  2   /* gradients of every parameter (d loss = 1 with HEAD, else from grad_emb) */
 #define MKGNN_MOLECULE_GRAD_EMB  4   /* BACKWARD without HEAD: d loss / d graph embedding is given */
+#define MKGNN_MOLECULE_SQERR     8   /* (ABI v8) with HEAD: squared error in place of BCE-with-logits (MKGNN_LOSS_SQERR_MEAN) */
+#define MKGNN_MOLECULE_SUM      16   /* (ABI v8) with SQERR: summed, not averaged, over the molecules (MKGNN_LOSS_SQERR_SUM) */
 
 int mkgnn_molecule_supported(const mkgnn_molecule_net* net, int32_t x_dim);
 size_t mkgnn_molecule_workspace_bytes(const mkgnn_molecule_net* net, int32_t x_dim, int64_t n_atoms, int64_t n_chunks);

@@ -161,8 +161,9 @@ class MolKGNNNet(torch.nn.Module):
             # (private: train.GNNModel.loss asks for the loss itself -- readout, head, loss and all their gradients in one
             # launch, readout.tail_loss -- where that applies; it gets ("loss", value) back, or the embedding as usual)
             if want_tail and sim_sc.requires_grad and R._tail_limits_ok(seg, plan):
-                ffn, target, p_head, n_rows = _tail
-                return ("loss", R.tail_loss(sim_sc, plan, Ls, lin1, lin2, ffn, target, seg, p_head, n_rows))
+                ffn, target, p_head, n_rows, *kind = _tail       # (ffn, y, dropout p, real molecules[, loss kind: "bce"])
+                loss = kind[0] if kind else "bce"
+                return ("loss", R.tail_loss(sim_sc, plan, Ls, lin1, lin2, ffn, target, seg, p_head, n_rows, loss))
             return R.readout_blocks(sim_sc, plan, Ls, lin1, lin2, self.dropout, seg)
         # pool(lin2(dropout(act(lin1(h)))), batch) -- MolKGNNNet.py:144-146 -- as one operator
         return R.readout(node_representation, lin1, lin2, self.dropout, data.batch, getattr(data, 'num_graphs', None), segments=seg)

@@ -16,7 +16,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MKGNN_LIB: a diagnostic build of the same library (make VARIANT=... in csrc/), e.g. with cycle stamps compiled in
 LIB_PATH = os.environ.get("MKGNN_LIB") or os.path.join(_HERE, "libmolkgnn_hip.so")
 MAX_DEGREE = 4
-ABI_VERSION = 7
+ABI_VERSION = 8
+# MKGNN_LOSS_*: the loss kinds of the single-task head (mkgnn_tail_args.loss_kind, mkgnn_head_loss_*)
+LOSS_BCE_MEAN, LOSS_SQERR_MEAN, LOSS_SQERR_SUM = 0, 1, 2
 
 
 class KernelBank(C.Structure):
@@ -57,7 +59,8 @@ class TailArgs(C.Structure):
                 ("emb", C.c_void_p), ("emb_stride", C.c_int64), ("pred", C.c_void_p), ("loss", C.c_void_p),
                 ("grad_sim", C.c_void_p), ("grad_sim_stride", C.c_int64), ("grad_lin1_weight", C.c_void_p),
                 ("grad_lin1_bias", C.c_void_p), ("grad_lin2_weight", C.c_void_p), ("grad_lin2_bias", C.c_void_p),
-                ("grad_head_weight", C.c_void_p), ("grad_head_bias", C.c_void_p), ("defer_reduce", C.c_int32)]
+                ("grad_head_weight", C.c_void_p), ("grad_head_bias", C.c_void_p), ("defer_reduce", C.c_int32),
+                ("loss_kind", C.c_int32)]
 
 
 TAIL_MAX_ATOMS, TAIL_MAX_EDGES = 128, 512      # MKGNN_TAIL_MAX_ATOMS / _EDGES
@@ -95,7 +98,7 @@ Int32x4 = C.c_int32 * MAX_DEGREE
 MOLECULE_MAX_LAYERS = 4
 MOLECULE_MAX_ATOMS = 64
 MOLECULE_MAX_MOLS = 16
-MOLECULE_HEAD, MOLECULE_BACKWARD, MOLECULE_GRAD_EMB = 1, 2, 4
+MOLECULE_HEAD, MOLECULE_BACKWARD, MOLECULE_GRAD_EMB, MOLECULE_SQERR, MOLECULE_SUM = 1, 2, 4, 8, 16
 
 
 class MoleculeLayer(C.Structure):
@@ -142,7 +145,9 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_readout_blocks_workspace_bytes", "mkgnn_molecule_supported", "mkgnn_molecule_workspace_bytes",
            "mkgnn_molecule_step", "mkgnn_batchnorm_stats_workspace_bytes", "mkgnn_batchnorm_update_stats",
            "mkgnn_batchnorm_forward_with_stats", "mkgnn_index_workspace_bytes", "mkgnn_index_build",
-           "mkgnn_rows_split_supported", "mkgnn_rows_presplit", "mkgnn_tail_supported", "mkgnn_tail_workspace_bytes", "mkgnn_tail_fused", "mkgnn_tail_flush", "mkgnn_flat_copy")
+           "mkgnn_rows_split_supported", "mkgnn_rows_presplit", "mkgnn_tail_supported", "mkgnn_tail_workspace_bytes", "mkgnn_tail_fused", "mkgnn_tail_flush", "mkgnn_flat_copy",
+           "mkgnn_head_loss_forward", "mkgnn_head_loss_backward", "mkgnn_head_loss_dropout_forward",
+           "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -278,6 +283,13 @@ def load() -> C.CDLL:
     lib.mkgnn_bce_head_dropout_backward.argtypes = [P, I64, I64, I32, P, P, P, P, C.c_float, P, P, I64, P, P, P, C.c_size_t, P]
     lib.mkgnn_bce_head_fused.restype = C.c_int
     lib.mkgnn_bce_head_fused.argtypes = [P, I64, I64, I32, P, P, P, C.c_float, P, P, P, P, P, I64, P, P, P, C.c_size_t, P]
+    for name, args in (("mkgnn_head_loss_forward", lib.mkgnn_bce_head_forward.argtypes),
+                       ("mkgnn_head_loss_backward", lib.mkgnn_bce_head_backward.argtypes),
+                       ("mkgnn_head_loss_dropout_forward", lib.mkgnn_bce_head_dropout_forward.argtypes),
+                       ("mkgnn_head_loss_dropout_backward", lib.mkgnn_bce_head_dropout_backward.argtypes),
+                       ("mkgnn_head_loss_fused", lib.mkgnn_bce_head_fused.argtypes)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [I32] + list(args)          # (loss_kind, then the mkgnn_bce_head_* arguments)
     lib.mkgnn_bce_head_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_bce_head_workspace_bytes.argtypes = [I64, I32]
     lib.mkgnn_rf_workspace_bytes.restype = C.c_size_t

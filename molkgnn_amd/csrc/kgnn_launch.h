@@ -205,7 +205,7 @@ constexpr int TAIL_B1 = 0, TAIL_W2 = 32, TAIL_B2 = 32 + 1024, TAIL_WH = TAIL_B2 
 hipError_t launch_pending_tail_reduce(hipStream_t st, bool* launched = nullptr);
 int tail_group_size(int64_t n_loss_mols);
 int tail_middle_blocks(int64_t n_loss_mols);
-hipError_t launch_tail_middle(const TailMidArgs& a, int nb, hipStream_t st);
+hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st);   // loss_kind: MKGNN_LOSS_*
 
 struct BankStreamLaunch { BankStreamArgs a; int nb, prep_blocks, KC; size_t lds_bytes; int x_split; };
 // block split and arguments once; then the pre-pass (coefficient records in tile order, score-weight partials) and the

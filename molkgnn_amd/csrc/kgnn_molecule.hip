@@ -983,7 +983,8 @@ __device__ __forceinline__ void molecule_step_body(MolArgsP ap, float* lds) {
     MOL_STAMP();   // readout forward
     // ----------------------------------------------------------------------------------------------------- head ----
     if (do_head) {
-        // dropout -> ffn -> BCE with logits (model.py:150, 169, 190-198); a half-wave per molecule
+        // dropout -> ffn -> BCE with logits (model.py:150, 169, 190-198) -- or, with MKGNN_MOLECULE_SQERR, the squared error
+        // (mean, or sum with MKGNN_MOLECULE_SUM: the docking-score task, data.py:49-53); a half-wave per molecule
         const int g = tid >> 5, h32 = tid & 31;
         const bool drop = a.head_drop > 0.f;
         const uint64_t seed = drop ? (uint64_t)a.rng[0] : 0, offset = drop ? (uint64_t)a.rng[1] : 0;
@@ -1004,8 +1005,14 @@ __device__ __forceinline__ void molecule_step_body(MolArgsP ap, float* lds) {
         if (g < nm) {
             x += a.ffn_b ? a.ffn_b[0] : 0.f;
             const float yv = a.y[m0 + g];
-            dv = (sigmoid_m(x) - yv) / (float)a.n_mols;
-            ls = fmaxf(x, 0.f) - x * yv + log1pf(expf(-fabsf(x)));
+            if (!(a.mode & MKGNN_MOLECULE_SQERR)) {
+                dv = (sigmoid_m(x) - yv) / (float)a.n_mols;
+                ls = fmaxf(x, 0.f) - x * yv + log1pf(expf(-fabsf(x)));
+            } else {
+                const float r = x - yv;
+                dv = (a.mode & MKGNN_MOLECULE_SUM) ? 2.f * r : (2.f * r) / (float)a.n_mols;
+                ls = r * r;
+            }
             if (h32 == 0) a.pred[m0 + g] = x;
 #pragma unroll
             for (int k = 0; k < 2; ++k) { const int o = h32 + 32 * k; if (o < G) dembs[g * 64 + o] = dv * a.ffn_w[o] * ks[k]; }
@@ -1362,7 +1369,7 @@ __global__ void __launch_bounds__(256) molecule_reduce_kernel(MolReduceArgs a) {
         const bool head = (a.mode & MKGNN_MOLECULE_HEAD) != 0, bwd = (a.mode & MKGNN_MOLECULE_BACKWARD) != 0;
         long long off = -1; float* dst = nullptr; float scale = 1.f;
         int k = e;
-        if (k == 0) { if (head && a.loss) { off = a.s_loss; dst = a.loss; scale = 1.f / (float)a.n_mols; } }
+        if (k == 0) { if (head && a.loss) { off = a.s_loss; dst = a.loss; scale = (a.mode & MKGNN_MOLECULE_SUM) ? 1.f : 1.f / (float)a.n_mols; } }
         else if (!bwd) {}
         else if (k == 1) { if (head && a.g_ffn_b) { off = a.s_loss + 1; dst = a.g_ffn_b; } }
         else if ((k -= 2) < n_ffn) { if (head && a.g_ffn_w) { off = a.s_ffn + k; dst = a.g_ffn_w + k; } }
@@ -1595,6 +1602,9 @@ int mkgnn_molecule_step(const mkgnn_molecule_net* net, const mkgnn_molecule_batc
     if (!emb) return api_fail("%s: emb is null", who);
     if (head && (!target || !pred || !loss || !net->ffn_weight)) return api_fail("%s: HEAD needs target, pred, loss and the ffn weight", who);
     if (head && ext) return api_fail("%s: HEAD and GRAD_EMB exclude each other", who);
+    if (mode & ~31) return api_fail("%s: unknown mode bits 0x%x", who, (unsigned)mode);
+    if ((mode & (MKGNN_MOLECULE_SQERR | MKGNN_MOLECULE_SUM)) && !head) return api_fail("%s: SQERR / SUM need HEAD", who);
+    if ((mode & MKGNN_MOLECULE_SUM) && !(mode & MKGNN_MOLECULE_SQERR)) return api_fail("%s: SUM needs SQERR", who);
     if (bwd && !head && (!ext || !grad_emb)) return api_fail("%s: BACKWARD needs HEAD or GRAD_EMB with grad_emb", who);
     if (head && net->head_dropout > 0.f && !net->rng_state) return api_fail("%s: head dropout needs rng_state", who);
     if (!(net->head_dropout >= 0.f && net->head_dropout < 1.f)) return api_fail("%s: head dropout outside [0, 1)", who);
@@ -1732,7 +1742,7 @@ int mkgnn_molecule_step(const mkgnn_molecule_net* net, const mkgnn_molecule_batc
     ra.s_loss = s.s_loss; ra.s_ffn = s.s_ffn; ra.s_lin2 = s.s_lin2; ra.s_lin1b = s.s_lin1b; ra.s_bn = s.s_bn;
     ra.g_w1 = net->grad_lin1_weight; ra.g_b1 = net->grad_lin1_bias; ra.g_w2 = net->grad_lin2_weight; ra.g_b2 = net->grad_lin2_bias;
     ra.g_ffn_w = net->grad_ffn_weight; ra.g_ffn_b = net->grad_ffn_bias; ra.g_bn_w = net->grad_bn_weight; ra.g_bn_b = net->grad_bn_bias;
-    ra.loss = loss; ra.n_mols = (int)batch->n_mols; ra.mode = mode & 7;
+    ra.loss = loss; ra.n_mols = (int)batch->n_mols; ra.mode = mode & 31;
     ra.rng = net->rng_state; ra.rng_used = net->rng_used; ra.head_drop = head ? net->head_dropout : 0.f;
     if (head || bwd) molecule_reduce_kernel<<<rtask, 256, 0, st>>>(ra);
     hipError_t e = hipGetLastError();

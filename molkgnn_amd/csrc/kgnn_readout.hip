@@ -21,6 +21,7 @@
 #include <cstdint>
 #include "kgnn_common.h"
 #include <mutex>
+#include <type_traits>
 
 #include "kgnn_launch.h"
 #include "kgnn_philox.h"
@@ -1530,7 +1531,34 @@ __device__ __forceinline__ float half_wave_sum(float v) {   // xor tree over the
     return v;
 }
 
-__global__ void __launch_bounds__(256) bce_head_forward_kernel(HeadArgs a) {
+// The loss kind LK (MKGNN_LOSS_*, ABI v8) is a template parameter of every head kernel: the BCE instantiations are the code
+// that was there before.  A row's loss term and its d loss / d pred, both before the 1 / B of the mean kinds:
+template <int LK>
+__device__ __forceinline__ float head_loss_term(float x, float y) {
+    if constexpr (LK == MKGNN_LOSS_BCE_MEAN) return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));   // torch's stable form
+    else { const float r = x - y; return r * r; }
+}
+template <int LK>
+__device__ __forceinline__ float head_dloss(float x, float y) {
+    if constexpr (LK == MKGNN_LOSS_BCE_MEAN) return 1.f / (1.f + expf(-x)) - y;
+    else return 2.f * (x - y);
+}
+template <int LK>
+__device__ __forceinline__ float head_mean(float v, int64_t B) { return LK == MKGNN_LOSS_SQERR_SUM ? v : v / (float)B; }
+// the loss kind (MKGNN_LOSS_*) of a call as a template argument: f(std::integral_constant<int, LK>{}); false: unknown kind
+template <typename Fn>
+static bool with_loss_kind(int32_t lk, Fn&& f) {
+    switch (lk) {
+    case MKGNN_LOSS_BCE_MEAN: f(std::integral_constant<int, MKGNN_LOSS_BCE_MEAN>{}); return true;
+    case MKGNN_LOSS_SQERR_MEAN: f(std::integral_constant<int, MKGNN_LOSS_SQERR_MEAN>{}); return true;
+    case MKGNN_LOSS_SQERR_SUM: f(std::integral_constant<int, MKGNN_LOSS_SQERR_SUM>{}); return true;
+    default: return false;
+    }
+}
+
+
+template <int LK>
+__global__ void __launch_bounds__(256) head_forward_kernel(HeadArgs a) {
     __shared__ float red[8];
     const int t = threadIdx.x, h = t & 31, g = t >> 5;          // 8 rows x 32 lanes per pass
     const float bias = a.b ? a.b[0] : 0.f;
@@ -1564,7 +1592,7 @@ __global__ void __launch_bounds__(256) bce_head_forward_kernel(HeadArgs a) {
         x = half_wave_sum(x) + bias;
         if (h == 0 && i < a.B) {
             a.pred[i] = x;
-            s += fmaxf(x, 0.f) - x * yv[k] + log1pf(expf(-fabsf(x)));   // torch's stable form
+            s += head_loss_term<LK>(x, yv[k]);
         }
     }
     if (h == 0) red[g] = s;
@@ -1579,7 +1607,8 @@ __global__ void __launch_bounds__(256) bce_head_forward_kernel(HeadArgs a) {
 // second launch of the forward: the block partials in a fixed tree -> loss; advances the dropout generator.
 // (A "last block done" counter inside the first kernel did this in one launch, but the two device-scope fences it
 // needs cost 10-15 us on this part -- more than a second, dependent launch: 4.7 us.)
-__global__ void __launch_bounds__(256) bce_head_forward_final_kernel(HeadArgs a, int nblk) {
+template <int LK>
+__global__ void __launch_bounds__(256) head_forward_final_kernel(HeadArgs a, int nblk) {
     __shared__ float fin[256];
     const int t = threadIdx.x;
     float v = 0.f;
@@ -1591,7 +1620,7 @@ __global__ void __launch_bounds__(256) bce_head_forward_final_kernel(HeadArgs a,
         __syncthreads();
     }
     if (t == 0) {
-        a.loss[0] = fin[0] / (float)a.B;
+        a.loss[0] = head_mean<LK>(fin[0], a.B);
         if (a.drop_p > 0.f) {
             const int64_t seed = a.rng[0], offset = a.rng[1];
             a.rng_used[0] = seed; a.rng_used[1] = offset;
@@ -1600,11 +1629,12 @@ __global__ void __launch_bounds__(256) bce_head_forward_final_kernel(HeadArgs a,
     }
 }
 
-__global__ void __launch_bounds__(256) bce_head_backward_kernel(HeadArgs a) {
+template <int LK>
+__global__ void __launch_bounds__(256) head_backward_kernel(HeadArgs a) {
     __shared__ float red[8][33];
     __shared__ float redb[8];
     const int t = threadIdx.x, h = t & 31, g = t >> 5;
-    const float gl = a.gloss[0] / (float)a.B;
+    const float gl = head_mean<LK>(a.gloss[0], a.B);
     const int PW = a.H + 1;                                   // partial row: dW[0..H), db
     float db = 0.f;
     constexpr int NP = HEAD_ROWS / 8;
@@ -1624,7 +1654,7 @@ __global__ void __launch_bounds__(256) bce_head_backward_kernel(HeadArgs a) {
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
             const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-            dv[k] = i < a.B ? gl * (1.f / (1.f + expf(-pv[k])) - yv[k]) : 0.f;
+            dv[k] = i < a.B ? gl * head_dloss<LK>(pv[k], yv[k]) : 0.f;
             if (h == 0) db += dv[k];
         }
     }
@@ -1669,7 +1699,7 @@ __global__ void __launch_bounds__(256) bce_head_backward_kernel(HeadArgs a) {
 
 // second launch of the backward: column c of the block partials, four row parts per column, eight loads in flight
 // per thread; parts combined in a fixed order
-__global__ void __launch_bounds__(256) bce_head_backward_final_kernel(HeadArgs a, int nb) {
+__global__ void __launch_bounds__(256) head_backward_final_kernel(HeadArgs a, int nb) {
     __shared__ float fin[4][64];
     const int t = threadIdx.x;
     const int PW = a.H + 1;
@@ -1703,7 +1733,8 @@ __global__ void __launch_bounds__(256) bce_head_backward_final_kernel(HeadArgs a
 // grad_bias; ONE final kernel sums the loss and the gradient partials.  Two launches where forward + backward took four
 // (the four are kept: a caller whose d loss is not 1 scales these, or runs the separate backward).
 // partial row of a block: [dW[0..H) | db | loss]
-__global__ void __launch_bounds__(256) bce_head_fused_kernel(HeadArgs a) {
+template <int LK>
+__global__ void __launch_bounds__(256) head_fused_kernel(HeadArgs a) {
     __shared__ float red[8][33];
     __shared__ float redb[8], redl[8];
     const int t = threadIdx.x, h = t & 31, g = t >> 5;
@@ -1714,7 +1745,7 @@ __global__ void __launch_bounds__(256) bce_head_fused_kernel(HeadArgs a) {
     const float w0 = h < a.H ? a.w[h] : 0.f;
     const bool drop = a.drop_p > 0.f;
     const uint64_t seed = drop ? (uint64_t)a.rng[0] : 0, offset = drop ? (uint64_t)a.rng[1] : 0;
-    const float invB = 1.f / (float)a.B;
+    const float invB = head_mean<LK>(1.f, a.B);
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
@@ -1737,10 +1768,10 @@ __global__ void __launch_bounds__(256) bce_head_fused_kernel(HeadArgs a) {
                 x = fmaf(e, a.w[h0 + h], x);
             }
         x = half_wave_sum(x) + bias;                            // (the xor tree leaves the sum in every lane of the row)
-        dv[k] = i < a.B ? invB * (1.f / (1.f + expf(-x)) - yv[k]) : 0.f;
+        dv[k] = i < a.B ? invB * head_dloss<LK>(x, yv[k]) : 0.f;
         if (h == 0 && i < a.B) {
             a.pred[i] = x;
-            ls += fmaxf(x, 0.f) - x * yv[k] + log1pf(expf(-fabsf(x)));   // torch's stable form
+            ls += head_loss_term<LK>(x, yv[k]);
             db += dv[k];
         }
     }
@@ -1783,7 +1814,8 @@ __global__ void __launch_bounds__(256) bce_head_fused_kernel(HeadArgs a) {
 
 // columns of the block partials (dW, db, loss), four row parts per column, eight loads in flight; fixed order; advances
 // the dropout generator
-__global__ void __launch_bounds__(256) bce_head_fused_final_kernel(HeadArgs a, int nb) {
+template <int LK>
+__global__ void __launch_bounds__(256) head_fused_final_kernel(HeadArgs a, int nb) {
     __shared__ float fin[4][64];
     const int t = threadIdx.x;
     const int PW = a.H + 2;
@@ -1806,7 +1838,7 @@ __global__ void __launch_bounds__(256) bce_head_fused_final_kernel(HeadArgs a, i
             const float r = (fin[0][t] + fin[1][t]) + (fin[2][t] + fin[3][t]);
             if (c < a.H) a.gw[c] = r;
             else if (c == a.H) { if (a.gb) a.gb[0] = r; }
-            else a.loss[0] = r / (float)a.B;
+            else a.loss[0] = head_mean<LK>(r, a.B);
         }
         __syncthreads();
     }
@@ -2180,6 +2212,7 @@ int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
     if (p->dropout_p < 0.f || p->dropout_p >= 1.f) return api_fail("%s: dropout probability %g outside [0, 1)", who, (double)p->dropout_p);
     if (p->dropout_p > 0.f && (!p->rng_state || !p->rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
     if (p->emb && p->emb_stride < ro->G) return api_fail("%s: bad emb stride", who);
+    if (p->loss_kind < MKGNN_LOSS_BCE_MEAN || p->loss_kind > MKGNN_LOSS_SQERR_SUM) return api_fail("%s: unknown loss kind %d", who, (int)p->loss_kind);
     BlockProjArgs b{};
     int64_t n_focal = 0;
     if (int rc = check_blocks(who, ro, p->num_kernels, p->buckets, p->n_atoms, p->sim_stride, p->sim, b, d, &n_focal)) return rc;
@@ -2215,7 +2248,7 @@ int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
     m.slab = (float*)((char*)ws + w.slab_tail); m.slab_stride = TAIL_SLAB;
     m.mg = tail_group_size(p->n_loss_mols);
     const int nbm = tail_middle_blocks(p->n_loss_mols);
-    e = launch_tail_middle(m, nbm, st);
+    e = launch_tail_middle(m, nbm, p->loss_kind, st);
     if (e != hipSuccess) return api_hip_fail(who, e);
     // (3) d sim[block] = W1[:, block]^T d z,  dW1 partials   (as mkgnn_readout_blocks_backward)
     b.dz = dz; b.dsim = p->grad_sim; b.dss = p->grad_sim_stride;
@@ -2455,11 +2488,10 @@ size_t mkgnn_bce_head_workspace_bytes(int64_t n_rows, int32_t H) {
     return 16 + (size_t)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS) * (H + 2) * 4;
 }
 
-int mkgnn_bce_head_fused(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight, const float* bias,
-                         const float* target, float dropout_p, int64_t* rng_state, int64_t* rng_used, float* pred, float* loss,
-                         float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws,
-                         size_t ws_bytes, void* stream) {
-    const char* who = "mkgnn_bce_head_fused";
+static int head_fused(const char* who, int32_t lk, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                      const float* weight, const float* bias, const float* target, float dropout_p, int64_t* rng_state,
+                      int64_t* rng_used, float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
+                      float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
     if (n_rows < 1 || H < 1 || emb_stride < H) return api_fail("%s: bad shape", who);
     if (!emb || !weight || !target || !pred || !loss || !grad_weight) return api_fail("%s: null pointer", who);
     if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
@@ -2473,10 +2505,29 @@ int mkgnn_bce_head_fused(const float* emb, int64_t emb_stride, int64_t n_rows, i
     a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
     a.drop_p = dropout_p; a.rng = rng_state; a.rng_used = rng_used;
     const int nblk = (int)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS);
-    bce_head_fused_kernel<<<nblk, 256, 0, (hipStream_t)stream>>>(a);
-    bce_head_fused_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
+    if (!with_loss_kind(lk, [&](auto K) {
+            head_fused_kernel<decltype(K)::value><<<nblk, 256, 0, (hipStream_t)stream>>>(a);
+            head_fused_final_kernel<decltype(K)::value><<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
+        }))
+        return api_fail("%s: unknown loss kind %d", who, (int)lk);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+int mkgnn_bce_head_fused(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight, const float* bias,
+                         const float* target, float dropout_p, int64_t* rng_state, int64_t* rng_used, float* pred, float* loss,
+                         float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws,
+                         size_t ws_bytes, void* stream) {
+    return head_fused("mkgnn_bce_head_fused", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target, dropout_p,
+                      rng_state, rng_used, pred, loss, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
+}
+
+int mkgnn_head_loss_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
+                          const float* bias, const float* target, float dropout_p, int64_t* rng_state, int64_t* rng_used,
+                          float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
+                          float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
+    return head_fused("mkgnn_head_loss_fused", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, dropout_p,
+                      rng_state, rng_used, pred, loss, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
 }
 
 static int head_ws(const char* who, int64_t n_rows, int32_t H, void* ws, size_t ws_bytes, HeadArgs& a) {
@@ -2486,9 +2537,9 @@ static int head_ws(const char* who, int64_t n_rows, int32_t H, void* ws, size_t 
     return 0;
 }
 
-static int head_forward(const char* who, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
-                        const float* bias, const float* target, float p, int64_t* rng_state, int64_t* rng_used, float* pred,
-                        float* loss, void* ws, size_t ws_bytes, void* stream) {
+static int head_forward(const char* who, int32_t lk, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                        const float* weight, const float* bias, const float* target, float p, int64_t* rng_state,
+                        int64_t* rng_used, float* pred, float* loss, void* ws, size_t ws_bytes, void* stream) {
     if (n_rows < 1 || H < 1 || emb_stride < H) return api_fail("%s: bad shape", who);
     if (!emb || !weight || !target || !pred || !loss) return api_fail("%s: null pointer", who);
     if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, p);
@@ -2498,16 +2549,19 @@ static int head_forward(const char* who, const float* emb, int64_t emb_stride, i
     a.emb = emb; a.es = emb_stride; a.B = n_rows; a.H = H; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss;
     a.drop_p = p; a.rng = rng_state; a.rng_used = rng_used;
     const int nblk = (int)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS);
-    bce_head_forward_kernel<<<nblk, 256, 0, (hipStream_t)stream>>>(a);
-    bce_head_forward_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
+    if (!with_loss_kind(lk, [&](auto K) {
+            head_forward_kernel<decltype(K)::value><<<nblk, 256, 0, (hipStream_t)stream>>>(a);
+            head_forward_final_kernel<decltype(K)::value><<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
+        }))
+        return api_fail("%s: unknown loss kind %d", who, (int)lk);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }
 
-static int head_backward(const char* who, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
-                         const float* target, const float* pred, const float* grad_loss, float p, const int64_t* rng_used,
-                         float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws,
-                         size_t ws_bytes, void* stream) {
+static int head_backward(const char* who, int32_t lk, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                         const float* weight, const float* target, const float* pred, const float* grad_loss, float p,
+                         const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias,
+                         void* ws, size_t ws_bytes, void* stream) {
     if (n_rows < 1 || H < 1 || emb_stride < H) return api_fail("%s: bad shape", who);
     if (!emb || !weight || !target || !pred || !grad_loss || !grad_weight) return api_fail("%s: null pointer", who);
     if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
@@ -2519,8 +2573,9 @@ static int head_backward(const char* who, const float* emb, int64_t emb_stride, 
     a.gloss = grad_loss; a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
     a.drop_p = p; a.rng_used = (int64_t*)rng_used;
     const int nblk = (int)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS);
-    bce_head_backward_kernel<<<nblk, 256, 0, (hipStream_t)stream>>>(a);
-    bce_head_backward_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
+    if (!with_loss_kind(lk, [&](auto K) { head_backward_kernel<decltype(K)::value><<<nblk, 256, 0, (hipStream_t)stream>>>(a); }))
+        return api_fail("%s: unknown loss kind %d", who, (int)lk);
+    head_backward_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }
@@ -2528,31 +2583,62 @@ static int head_backward(const char* who, const float* emb, int64_t emb_stride, 
 int mkgnn_bce_head_forward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
                            const float* bias, const float* target, float* pred, float* loss, void* ws, size_t ws_bytes,
                            void* stream) {
-    return head_forward("mkgnn_bce_head_forward", emb, emb_stride, n_rows, H, weight, bias, target, 0.f, nullptr, nullptr,
-                        pred, loss, ws, ws_bytes, stream);
+    return head_forward("mkgnn_bce_head_forward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target, 0.f,
+                        nullptr, nullptr, pred, loss, ws, ws_bytes, stream);
 }
 
 int mkgnn_bce_head_backward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
                             const float* target, const float* pred, const float* grad_loss, float* grad_emb,
                             int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws, size_t ws_bytes,
                             void* stream) {
-    return head_backward("mkgnn_bce_head_backward", emb, emb_stride, n_rows, H, weight, target, pred, grad_loss, 0.f, nullptr,
-                         grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
+    return head_backward("mkgnn_bce_head_backward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, target, pred,
+                         grad_loss, 0.f, nullptr, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
 }
 
 int mkgnn_bce_head_dropout_forward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
                                    const float* bias, const float* target, float dropout_p, int64_t* rng_state,
                                    int64_t* rng_used, float* pred, float* loss, void* ws, size_t ws_bytes, void* stream) {
-    return head_forward("mkgnn_bce_head_dropout_forward", emb, emb_stride, n_rows, H, weight, bias, target, dropout_p, rng_state,
-                        rng_used, pred, loss, ws, ws_bytes, stream);
+    return head_forward("mkgnn_bce_head_dropout_forward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target,
+                        dropout_p, rng_state, rng_used, pred, loss, ws, ws_bytes, stream);
 }
 
 int mkgnn_bce_head_dropout_backward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
                                     const float* target, const float* pred, const float* grad_loss, float dropout_p,
                                     const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
                                     float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
-    return head_backward("mkgnn_bce_head_dropout_backward", emb, emb_stride, n_rows, H, weight, target, pred, grad_loss, dropout_p,
-                         rng_used, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
+    return head_backward("mkgnn_bce_head_dropout_backward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, target, pred,
+                         grad_loss, dropout_p, rng_used, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
+}
+
+int mkgnn_head_loss_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                            const float* weight, const float* bias, const float* target, float* pred, float* loss, void* ws,
+                            size_t ws_bytes, void* stream) {
+    return head_forward("mkgnn_head_loss_forward", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, 0.f, nullptr,
+                        nullptr, pred, loss, ws, ws_bytes, stream);
+}
+
+int mkgnn_head_loss_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                             const float* weight, const float* target, const float* pred, const float* grad_loss,
+                             float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws,
+                             size_t ws_bytes, void* stream) {
+    return head_backward("mkgnn_head_loss_backward", loss_kind, emb, emb_stride, n_rows, H, weight, target, pred, grad_loss, 0.f,
+                         nullptr, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
+}
+
+int mkgnn_head_loss_dropout_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                                    const float* weight, const float* bias, const float* target, float dropout_p,
+                                    int64_t* rng_state, int64_t* rng_used, float* pred, float* loss, void* ws, size_t ws_bytes,
+                                    void* stream) {
+    return head_forward("mkgnn_head_loss_dropout_forward", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, dropout_p,
+                        rng_state, rng_used, pred, loss, ws, ws_bytes, stream);
+}
+
+int mkgnn_head_loss_dropout_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                                     const float* weight, const float* target, const float* pred, const float* grad_loss,
+                                     float dropout_p, const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride,
+                                     float* grad_weight, float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
+    return head_backward("mkgnn_head_loss_dropout_backward", loss_kind, emb, emb_stride, n_rows, H, weight, target, pred,
+                         grad_loss, dropout_p, rng_used, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

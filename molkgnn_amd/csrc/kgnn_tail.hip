@@ -3,6 +3,7 @@
 //   h = propagate(sim_sc)                                   reference KernelLayer.py:119-123
 //   emb_g = pool_g( lin2( swish( lin1(h) ) ) )              reference MolKGNNNet.py:144-146
 //   loss = BCEWithLogits( ffn( dropout(emb) ), y )          reference model.py:147-150, 169, 190-198; data.py:37
+//          (or the squared error, mean or sum -- the docking-score task, data.py:49-53: the template parameter LK, ABI v8)
 //
 // -- forward AND backward in FOUR launches instead of nine (mkgnn_tail_fused, kgnn_readout.hip).  The loss is a mean over
 // molecules, so d loss / d logit_g = (sigmoid(logit_g) - y_g) / B needs nothing but the molecule's own logit, and the chain back
@@ -100,6 +101,8 @@ __device__ unsigned long long* g_tail_stamps = nullptr;
 constexpr int LDS_FLOATS = 32 * WP + 2 * AC * HP + 3 * MC * HP + 96;
 constexpr int LDS_INTS = AC + 2 * (AC + 1) + 2 * EC + 3 * (MC + 1) + 4;
 
+// LK: the loss kind (MKGNN_LOSS_*), a template parameter so that the BCE instantiation's code stays as it was
+template <int LK>
 __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
     __shared__ __align__(16) float lds[LDS_FLOATS + LDS_INTS];
     float* const W2s = lds;                              // [32][HP]
@@ -296,11 +299,21 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
             float d = 0.f;
             if (counted) {
                 const float yv = a.y[gi];
-                d = invB * (sigmoidf_(x) - yv);
-                if (j == 0) {
-                    a.pred[gi] = x;
-                    acc_loss += invB * (fmaxf(x, 0.f) - x * yv + log1pf(expf(-fabsf(x))));      // torch's stable form
-                    acc_bh += d;
+                if constexpr (LK == MKGNN_LOSS_BCE_MEAN) {
+                    d = invB * (sigmoidf_(x) - yv);
+                    if (j == 0) {
+                        a.pred[gi] = x;
+                        acc_loss += invB * (fmaxf(x, 0.f) - x * yv + log1pf(expf(-fabsf(x))));      // torch's stable form
+                        acc_bh += d;
+                    }
+                } else {                                 // squared error: d = 2 (x - y), / B for the mean
+                    const float r = x - yv;
+                    d = LK == MKGNN_LOSS_SQERR_MEAN ? invB * (2.f * r) : 2.f * r;
+                    if (j == 0) {
+                        a.pred[gi] = x;
+                        acc_loss += LK == MKGNN_LOSS_SQERR_MEAN ? invB * (r * r) : r * r;
+                        acc_bh += d;
+                    }
                 }
             }
             acc_wh = fmaf(d, emb * ks, acc_wh);
@@ -391,7 +404,7 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
     if (t == 0) {
         float v = 0.f;
         for (int s8 = 0; s8 < 8; ++s8) v += vec[s8];
-        so[TAIL_LOSS] = v;                               // (already divided by B)
+        so[TAIL_LOSS] = v;                               // (already divided by B for the mean kinds)
     }
     TAIL_PHASE(8);                                       // epilogue
     if (stamps && t == 0)
@@ -419,9 +432,14 @@ extern "C" int mkgnn_debug_set_tail_stamps(void* device_ptr) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(tail::g_tail_stamps), &device_ptr, sizeof(void*));
 }
 
-hipError_t launch_tail_middle(const TailMidArgs& a, int nb, hipStream_t st) {
+hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st) {
     if (a.mg < tail::MG_MIN || a.mg > tail::MG_MAX || a.mg > tail::MC) return hipErrorInvalidValue;
-    tail::tail_middle_kernel<<<nb, tail::NT, 0, st>>>(a);
+    switch (loss_kind) {
+    case MKGNN_LOSS_BCE_MEAN: tail::tail_middle_kernel<MKGNN_LOSS_BCE_MEAN><<<nb, tail::NT, 0, st>>>(a); break;
+    case MKGNN_LOSS_SQERR_MEAN: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_MEAN><<<nb, tail::NT, 0, st>>>(a); break;
+    case MKGNN_LOSS_SQERR_SUM: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_SUM><<<nb, tail::NT, 0, st>>>(a); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

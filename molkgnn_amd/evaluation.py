@@ -120,3 +120,15 @@ def calculate_f1_score(true_y, predicted_score) -> float:
     tn, fp, fn, tp = _confusion(true_y, predicted_score, 0.5)
     den = 2 * tp + fp + fn
     return 2 * tp / den if den != 0 else 0.0
+
+
+def calculate_rmse(true_y, predicted_score) -> float:
+    """Root mean squared error of the docking-score task (reference ``model.py:504-507``:
+    ``mean_squared_error(true_y, predicted_score, squared=False)``), in float64 on the predictions' device."""
+    s = torch.as_tensor(predicted_score).reshape(-1).to(torch.float64)
+    y = torch.as_tensor(true_y).reshape(-1).to(device=s.device, dtype=torch.float64)
+    if y.numel() != s.numel():
+        raise ValueError("true_y and predicted_score differ in length")
+    if y.numel() == 0:
+        raise ValueError("calculate_rmse needs at least one sample")
+    return math.sqrt(float(((y - s) ** 2).mean()))

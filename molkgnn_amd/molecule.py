@@ -472,14 +472,15 @@ class _MoleculeNetFn(torch.autograd.Function):
 
 
 class _MoleculeLossFn(torch.autograd.Function):
-    """``GNNModel.loss`` as one operator: forward, BCE head and -- when a gradient will be asked for -- the whole backward in
-    the same launch (d loss = 1; any other incoming gradient scales the stored ones)."""
+    """``GNNModel.loss`` as one operator: forward, head and loss and -- when a gradient will be asked for -- the whole backward
+    in the same launch (d loss = 1; any other incoming gradient scales the stored ones).  ``kind``: the loss (MKGNN_LOSS_*) as
+    the molecule step's mode bits."""
 
     @staticmethod
-    def forward(ctx, net, ffn, p_drop, target, plan, mp, es, x, *params):
+    def forward(ctx, net, ffn, p_drop, target, plan, mp, es, kind, x, *params):
         params = list(params)
-        need = any(ctx.needs_input_grad[8:])
-        mode = _lib.MOLECULE_HEAD | (_lib.MOLECULE_BACKWARD if need else 0)
+        need = any(ctx.needs_input_grad[9:])
+        mode = _lib.MOLECULE_HEAD | (_lib.MOLECULE_BACKWARD if need else 0) | _KIND_MODE[kind]
         _, pred, loss, flat = _run(net, ffn, params, plan, mp, x, mode, target.reshape(-1).float().contiguous(), None, p_drop, True, es)
         ctx.flat, ctx.params = flat, params
         ctx.pred = pred
@@ -494,7 +495,11 @@ class _MoleculeLossFn(torch.autograd.Function):
         if not _is_unit_seed(grad_loss):
             gl = grad_loss.reshape(()).float()
             flat = [None if g is None else g * gl for g in flat]
-        return (None,) * 8 + tuple(_shape_like(g, p) if p is not None else None for g, p in zip(flat, ctx.params))
+        return (None,) * 9 + tuple(_shape_like(g, p) if p is not None else None for g, p in zip(flat, ctx.params))
+
+
+_KIND_MODE = {_lib.LOSS_BCE_MEAN: 0, _lib.LOSS_SQERR_MEAN: _lib.MOLECULE_SQERR,
+              _lib.LOSS_SQERR_SUM: _lib.MOLECULE_SQERR | _lib.MOLECULE_SUM}
 
 
 def _plan_of(data) -> BatchPlan:
@@ -568,8 +573,11 @@ def net_forward(net, data) -> Optional[torch.Tensor]:
     return _MoleculeNetFn.apply(net, plan, mp, es, data.x, *params)
 
 
-def loss_forward(model, data, p_drop: float) -> Optional[torch.Tensor]:
-    """``GNNModel.loss(data)`` (single task, BCE with logits) through the molecule-resident kernels, or ``None``."""
+def loss_forward(model, data, p_drop: float, loss: str = "bce") -> Optional[torch.Tensor]:
+    """``GNNModel.loss(data)`` (single task; ``loss``: a kind of ``readout.LOSS_KINDS``, BCE with logits by default) through
+    the molecule-resident kernels, or ``None``."""
+    from .readout import loss_kind
+    kind = loss_kind(loss)
     net, ffn = model.gnn_model, model.ffn
     r = _ready(net, data, ffn)
     if r is None or data.y.numel() != r[1].n_mols:
@@ -582,4 +590,4 @@ def loss_forward(model, data, p_drop: float) -> Optional[torch.Tensor]:
         from .readout import update_running_stats
         update_running_stats(*es)
         es = None
-    return _MoleculeLossFn.apply(net, ffn, float(p_drop), data.y, plan, mp, es, data.x, *params)
+    return _MoleculeLossFn.apply(net, ffn, float(p_drop), data.y, plan, mp, es, kind, data.x, *params)

@@ -511,10 +511,30 @@ def _is_unit_seed(grad: torch.Tensor) -> bool:
     return False
 
 
+# the head's loss kinds (MKGNN_LOSS_*): BCEWithLogitsLoss() (the QSAR assays, reference data.py:37), MSELoss() and
+# MSELoss(reduction='sum') (the docking-score task, data.py:49-53)
+LOSS_KINDS = {"bce": _lib.LOSS_BCE_MEAN, "mse": _lib.LOSS_SQERR_MEAN, "mse_sum": _lib.LOSS_SQERR_SUM}
+
+
+def loss_kind(loss: str) -> int:
+    if loss not in LOSS_KINDS:
+        raise ValueError(f"unknown loss {loss!r}: one of {sorted(LOSS_KINDS)}")
+    return LOSS_KINDS[loss]
+
+
+def _head_call(lib, name: str, kind: Optional[int], *args) -> None:
+    """``mkgnn_bce_head_<name>(*args)`` (kind None: the BCE entry points as they were), else ``mkgnn_head_loss_<name>(kind, *args)``."""
+    if kind is None:
+        _lib.check(getattr(lib, "mkgnn_bce_head_" + name)(*args), "mkgnn_bce_head_" + name)
+    else:
+        _lib.check(getattr(lib, "mkgnn_head_loss_" + name)(int(kind), *args), "mkgnn_head_loss_" + name)
+
+
 class _BceHeadFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, emb, weight, bias, target, p_drop, n_rows):
+    def forward(ctx, emb, weight, bias, target, p_drop, n_rows, kind=None):
         lib = _lib.load()
+        ctx.kind = kind
         emb = _row_major(emb if emb.dtype == torch.float32 else emb.float())
         ctx.rows_total = emb.shape[0]
         B, H = int(n_rows), emb.shape[1]         # the leading n_rows rows enter the loss (the rest: padding molecules)
@@ -537,10 +557,10 @@ class _BceHeadFn(torch.autograd.Function):
             gb = torch.empty(1, dtype=torch.float32, device=dev) if bias is not None else None
             with torch.cuda.device(dev):
                 ws = _head_workspace(dev, int(lib.mkgnn_bce_head_workspace_bytes(B, H)))
-                _lib.check(lib.mkgnn_bce_head_fused(
-                    emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), float(p_drop),
-                    _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), _lib.ptr(gemb), H, gw.data_ptr(),
-                    _lib.ptr(gb), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_bce_head_fused")
+                _head_call(lib, "fused", kind,
+                           emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), float(p_drop),
+                           _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), _lib.ptr(gemb), H, gw.data_ptr(),
+                           _lib.ptr(gb), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
             ctx.unit = (gemb, gw, gb)
             # (references only: a second backward over a retained graph takes the separate backward kernel below)
             ctx.save_for_backward(emb, w, y, pred, used)
@@ -551,10 +571,10 @@ class _BceHeadFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             nbytes = int(lib.mkgnn_bce_head_workspace_bytes(B, H))
             ws = _head_workspace(dev, nbytes)
-            _lib.check(lib.mkgnn_bce_head_dropout_forward(
-                emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), float(p_drop),
-                _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(),
-                _lib.stream_ptr(dev)), "mkgnn_bce_head_dropout_forward")
+            _head_call(lib, "dropout_forward", kind,
+                       emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), float(p_drop),
+                       _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(),
+                       _lib.stream_ptr(dev))
         ctx.save_for_backward(emb, w, y, pred, used)
         ctx.wshape = weight.shape
         ctx.has_bias = bias is not None
@@ -571,7 +591,7 @@ class _BceHeadFn(torch.autograd.Function):
                 gemb = None if gemb is None else gemb * gl
                 gw = gw * gl
                 gb = None if gb is None else gb * gl
-            return gemb, gw.reshape(ctx.wshape), gb, None, None, None
+            return gemb, gw.reshape(ctx.wshape), gb, None, None, None, None
         lib = _lib.load()
         emb, w, y, pred, used = ctx.saved_tensors
         B, H = y.numel(), emb.shape[1]
@@ -587,11 +607,11 @@ class _BceHeadFn(torch.autograd.Function):
         gb = torch.empty(1, dtype=torch.float32, device=dev) if ctx.has_bias else None
         with torch.cuda.device(dev):
             ws = _head_workspace(dev, int(lib.mkgnn_bce_head_workspace_bytes(B, H)))
-            _lib.check(lib.mkgnn_bce_head_dropout_backward(
-                emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), y.data_ptr(), pred.data_ptr(), gl.data_ptr(),
-                ctx.p_drop, _lib.ptr(used), _lib.ptr(gemb), H, gw.data_ptr(), _lib.ptr(gb), ws.data_ptr(), ws.numel(),
-                _lib.stream_ptr(dev)), "mkgnn_bce_head_dropout_backward")
-        return gemb, gw.reshape(ctx.wshape), gb, None, None, None
+            _head_call(lib, "dropout_backward", ctx.kind,
+                       emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), y.data_ptr(), pred.data_ptr(), gl.data_ptr(),
+                       ctx.p_drop, _lib.ptr(used), _lib.ptr(gemb), H, gw.data_ptr(), _lib.ptr(gb), ws.data_ptr(), ws.numel(),
+                       _lib.stream_ptr(dev))
+        return gemb, gw.reshape(ctx.wshape), gb, None, None, None, None
 
 
 def bce_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, dropout_p: float = 0.0,
@@ -607,7 +627,23 @@ def bce_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor,
         raise ValueError("bce_head_loss needs a one-output linear layer and one target per (leading) row")
     if not 0.0 <= dropout_p < 1.0:
         raise ValueError(f"dropout probability {dropout_p} outside [0, 1)")
-    return _BceHeadFn.apply(emb, ffn.weight, ffn.bias, target, float(dropout_p), n_rows)
+    return _BceHeadFn.apply(emb, ffn.weight, ffn.bias, target, float(dropout_p), n_rows, None)     # (None: the v7 entry points)
+
+
+def head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, loss: str = "bce", dropout_p: float = 0.0,
+              n_rows: Optional[int] = None) -> torch.Tensor:
+    """``bce_head_loss`` for any loss kind of ``LOSS_KINDS``: ``"bce"`` (``BCEWithLogitsLoss()``, the same bits as
+    ``bce_head_loss``), ``"mse"`` (``MSELoss()``) or ``"mse_sum"`` (``MSELoss(reduction='sum')``, the reference's docking-score
+    task) of ``ffn(dropout(emb)).view(-1)`` against ``target.view(-1).float()``.  Same kernels (the kind a template parameter),
+    same dropout mask for the same generator state, same padding rule."""
+    kind = loss_kind(loss)
+    _lib.require_gpu_tensor(emb, "graph_embedding")
+    n_rows = emb.shape[0] if n_rows is None else int(n_rows)
+    if ffn.out_features != 1 or emb.dim() != 2 or n_rows <= 0 or n_rows > emb.shape[0] or target.numel() != n_rows:
+        raise ValueError("head_loss needs a one-output linear layer and one target per (leading) row")
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"dropout probability {dropout_p} outside [0, 1)")
+    return _BceHeadFn.apply(emb, ffn.weight, ffn.bias, target, float(dropout_p), n_rows, kind)
 
 
 # ------------------------------------------------------------------- the tail of a training step, fused --
@@ -704,7 +740,7 @@ class _TailFn(torch.autograd.Function):
     (``mkgnn_tail_fused``); the backward hands them out (scaled, if the incoming gradient is not the registered unit seed)."""
 
     @staticmethod
-    def forward(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows):
+    def forward(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind=_lib.LOSS_BCE_MEAN):
         lib = _lib.load()
         _lib.require_gpu_tensor(sim, "sim_sc")
         n, K = sim.shape
@@ -747,6 +783,7 @@ class _TailFn(torch.autograd.Function):
         # where autograd hands the six gradients straight to .grad: see _tail_grads_adopted)
         ctx.deferred = bool(_DEFER_TAIL_REDUCE and ctx.needs_input_grad[0] and _tail_grads_adopted((w1, b1, w2, b2, wh, bh)))
         a.defer_reduce = 1 if ctx.deferred else 0
+        a.loss_kind = int(kind)
         ctx.params = (w1, b1, w2, b2, wh, bh)
         ctx.dev = dev
         with torch.cuda.device(dev):
@@ -775,16 +812,18 @@ class _TailFn(torch.autograd.Function):
         if not _is_unit_seed(grad_loss):                     # d loss is not the registered 1: scale
             gl = grad_loss.reshape(()).float()
             grads = tuple(None if g is None else g * gl for g in grads)
-        return (*grads, None, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None, None)
 
 
 def tail_loss(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torch.nn.Linear, ffn: torch.nn.Linear,
-              target: torch.Tensor, seg: "MoleculeSegments", dropout_p: float = 0.0, n_rows: Optional[int] = None) -> torch.Tensor:
-    """``bce_head_loss(readout_blocks(sim, ...), ffn, target, dropout_p, n_rows)`` as ONE operator whose forward also takes
+              target: torch.Tensor, seg: "MoleculeSegments", dropout_p: float = 0.0, n_rows: Optional[int] = None,
+              loss: str = "bce") -> torch.Tensor:
+    """``head_loss(readout_blocks(sim, ...), ffn, target, loss, dropout_p, n_rows)`` as ONE operator whose forward also takes
     every gradient (``_TailFn``).  The caller has checked ``tail_supported``, ``_tail_limits_ok`` and that the readout has
     no dropout of its own."""
+    kind = loss_kind(loss)
     n_rows = seg.size if n_rows is None else int(n_rows)
     if ffn.out_features != 1 or n_rows <= 0 or n_rows > seg.size or target.numel() != n_rows:
         raise ValueError("tail_loss needs a one-output linear layer and one target per (leading) molecule")
     return _TailFn.apply(sim, lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight, ffn.bias, target, seg, plan,
-                         tuple(blocks), float(dropout_p), n_rows)
+                         tuple(blocks), float(dropout_p), n_rows, kind)

@@ -11,7 +11,10 @@ molecules with the shape statistics fixed in SURVEY.md section 8(d):
   (reference ``wrapper.py:152-156``);
 * ``x ~ N(0,1)^28`` (stand-in for batch-normalised atom features),
   ``edge_attr`` = one-hot(4 bond types) + 3 Bernoulli flags (``wrapper.py:139-150``),
-  ``p ~ N(0, 1.5^2)^3``, ``y ~ Bernoulli(active fraction)``.
+  ``p ~ N(0, 1.5^2)^3``, ``y ~ Bernoulli(active fraction)`` -- or, with
+  ``make_batch(..., target="docking_score")``, a continuous docking-like score
+  around -8 +- 1.5 that depends on the molecule (the regression task of the
+  reference's D4 docking set, ``data.py:49-53``).
 
 Assay sizes (reference ``utils/data_split.py:68-79``).
 """
@@ -122,8 +125,12 @@ def _random_graphs(rng: np.random.Generator, n_atoms: np.ndarray):
 
 def make_batch(num_molecules: int, seed: int, *, assay: str = "1798",
                duplicate_fraction: float = 0.0, device: Optional[torch.device] = None,
-               with_receptive_fields: bool = True) -> GraphBatch:
+               with_receptive_fields: bool = True, target: str = "activity") -> GraphBatch:
     """One collated batch of ``num_molecules`` synthetic molecules.
+
+    ``target``: ``"activity"`` (binary labels at the assay's active rate) or
+    ``"docking_score"`` (``docking_scores``: a seeded continuous score per
+    molecule).  Everything else in the batch is the same for either.
 
     ``duplicate_fraction`` > 0 copies the feature row of one neighbour onto a
     sibling for that fraction of atoms, which creates the permutation ties the
@@ -189,6 +196,10 @@ def make_batch(num_molecules: int, seed: int, *, assay: str = "1798",
         assay_id = np.full(num_molecules, int(assay) if str(assay).isdigit() else 0, dtype=np.int64)
     y = (rng.random(num_molecules) < rate).astype(np.float32)
     batch_vec = np.repeat(np.arange(num_molecules, dtype=np.int64), n_atoms)
+    if target == "docking_score":
+        y = docking_scores(seed, n_atoms, batch_vec, np.bincount(edge_index[0], minlength=n), x)
+    elif target != "activity":
+        raise ValueError(f"unknown target {target!r}: 'activity' or 'docking_score'")
     out = GraphBatch(
         x=torch.from_numpy(x), p=torch.from_numpy(p),
         edge_index=torch.from_numpy(edge_index), edge_attr=torch.from_numpy(edge_attr),
@@ -199,6 +210,18 @@ def make_batch(num_molecules: int, seed: int, *, assay: str = "1798",
     if with_receptive_fields:
         attach_receptive_fields(out)
     return out
+
+
+def docking_scores(seed: int, n_atoms: np.ndarray, batch_vec: np.ndarray, degree: np.ndarray, x: np.ndarray) -> np.ndarray:
+    """A docking-like score per molecule (kcal/mol-shaped: about -8 +- 1.5, lower for larger and more branched
+    molecules) from its atom count, the share of its atoms with three or four bonds and its mean first atom feature, plus
+    noise from a generator of its own (the batch's other draws stay what they are for the seed)."""
+    m = n_atoms.shape[0]
+    branched = np.bincount(batch_vec, weights=(degree >= 3).astype(np.float64), minlength=m) / n_atoms
+    feat = np.bincount(batch_vec, weights=x[:, 0].astype(np.float64), minlength=m) / n_atoms
+    noise = np.random.default_rng([int(seed), 0xD0C]).normal(0.0, 0.6, size=m)
+    score = -8.0 - 0.15 * (n_atoms - 25.0) - 4.0 * (branched - 0.34) + 1.5 * feat + noise
+    return score.astype(np.float32)
 
 
 def degree_histogram(batch: GraphBatch):

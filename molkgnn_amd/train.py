@@ -3,8 +3,9 @@
 
 Only what a forward + backward (+ optimiser) step needs is restated here: the module tree with the
 reference's parameter names (``gnn_model.*``, ``lin1``, ``lin2``, ``ffn``; 132 300 parameters), the
-``BCEWithLogitsLoss`` the data module selects (``data.py:37``) and the AdamW groups chosen by parameter
-name (``model.py:373-382``).  Logging, checkpoints, metrics and the LR schedule are out of scope.
+loss the data module selects -- ``BCEWithLogitsLoss()`` for the QSAR assays (``data.py:37``), ``MSELoss(reduction='sum')``
+for the docking-score set (``data.py:49-53``) -- and the AdamW groups chosen by parameter name (``model.py:373-382``).
+Logging, checkpoints, metrics and the LR schedule are out of scope.
 """
 from __future__ import annotations
 
@@ -12,7 +13,7 @@ import weakref
 from typing import Optional
 
 import torch
-from torch.nn import BCEWithLogitsLoss, Dropout, Linear, ReLU
+from torch.nn import BCEWithLogitsLoss, Dropout, Linear, MSELoss, ReLU
 
 from .MolKGNNNet import MolKGNNNet
 
@@ -22,7 +23,7 @@ KERNEL_COUNTS = (10, 20, 30, 50)    # paper / README kernels per degree
 class GNNModel(torch.nn.Module):
     def __init__(self, num_layers=3, kernels_1hop=KERNEL_COUNTS, kernels_Nhop=KERNEL_COUNTS, node_feature_dim=28,
                  edge_feature_dim=7, hidden_dim=32, dropout_ratio=0.0, ffn_dropout_rate=0.25, ffn_hidden_dim=64,
-                 task_dim=1):
+                 task_dim=1, loss_func=None):
         super().__init__()
         kw = {f"num_kernel{d}_1hop": k for d, k in zip(range(1, 5), kernels_1hop)}
         kw.update({f"num_kernel{d}_Nhop": k for d, k in zip(range(1, 5), kernels_Nhop)})
@@ -33,7 +34,7 @@ class GNNModel(torch.nn.Module):
         self.ffn = Linear(hidden_dim, task_dim)
         self.dropout = Dropout(p=ffn_dropout_rate)
         self.activate_func = ReLU()
-        self.loss_func = BCEWithLogitsLoss()
+        self.loss_func = BCEWithLogitsLoss() if loss_func is None else loss_func     # model.py:156: the data module's loss
 
     def forward(self, data):
         graph_embedding = self.dropout(self.gnn_model(data))
@@ -45,29 +46,40 @@ class GNNModel(torch.nn.Module):
             pred = self.ffn(graph_embedding)
         return pred, graph_embedding
 
+    def _loss_kind(self) -> Optional[str]:
+        """The loss as a kind of the HIP head (``readout.LOSS_KINDS``), or None: any other loss takes the PyTorch route."""
+        lf = self.loss_func
+        if type(lf) is BCEWithLogitsLoss and lf.reduction == "mean" and lf.pos_weight is None and lf.weight is None:
+            return "bce"
+        if type(lf) is MSELoss and lf.reduction in ("mean", "sum"):
+            return "mse" if lf.reduction == "mean" else "mse_sum"
+        return None
+
     def loss(self, data):
-        if self.ffn.out_features == 1 and type(self.loss_func) is BCEWithLogitsLoss and self.loss_func.reduction == "mean" \
-                and self.loss_func.pos_weight is None and self.loss_func.weight is None and data.x.is_cuda:
-            from .readout import bce_head_loss
+        kind = self._loss_kind() if self.ffn.out_features == 1 else None
+        if kind is not None and data.x.is_cuda:
+            from .readout import bce_head_loss, head_loss
             # dropout -> ffn -> loss in one kernel each way (same formula, 2 kernels instead of ~25; the dropout mask
             # comes from the kernels' own counter-based generator, see readout.head_rng_state)
             p = self.dropout.p if (self.training and self.dropout.p < 1.0) else 0.0
             if not (self.training and self.dropout.p >= 1.0):
                 # small batches: forward, loss and (when a gradient will be asked for) the whole backward in one launch
                 from . import molecule as _mol
-                fused = _mol.loss_forward(self, data, p)
+                fused = _mol.loss_forward(self, data, p, kind)
                 if fused is not None:
                     return fused
             nreal = getattr(data, 'n_valid_molecules', None)
             # large batches: everything behind the last convolution -- readout, head, loss and their gradients -- in one launch
             # (readout.tail_loss) where the model and the batch qualify; the embedding otherwise
-            tail = None if (self.training and self.dropout.p >= 1.0) else (self.ffn, data.y, p, nreal)
+            tail = None if (self.training and self.dropout.p >= 1.0) else (self.ffn, data.y, p, nreal, kind)
             graph_embedding = self.gnn_model(data, _tail=tail)
             if isinstance(graph_embedding, tuple):
                 return graph_embedding[1]
             if self.training and self.dropout.p >= 1.0:
                 graph_embedding = self.dropout(graph_embedding)
             # (a padded batch: the padding molecules' rows take no part in the loss -- the head reads the first nreal rows)
+            if kind != "bce":
+                return head_loss(graph_embedding, self.ffn, data.y, kind, dropout_p=p, n_rows=nreal)
             return bce_head_loss(graph_embedding, self.ffn, data.y, dropout_p=p, n_rows=nreal)
         pred, _ = self(data)
         return self.loss_func(pred.view(-1), data.y.view(-1).float())
