@@ -357,7 +357,7 @@ int mkgnn_readout_blocks_backward(const mkgnn_readout_params* params, const floa
 /* ---- the tail of a training step, fused (ABI v6) ----------------------------------------------------------------------
  * Everything behind the last kernel convolution, forward AND backward:
  *     h = propagate(sim)                                  KernelLayer.py:119-123
- *     emb_g = pool_g( lin2( swish( lin1(h) ) ) )          MolKGNNNet.py:144-146   (no dropout inside the readout)
+ *     emb_g = pool_g( lin2( swish( lin1(h) ) ) )          MolKGNNNet.py:144-146   (its dropout: the _readout_dropout entry)
  *     loss = mean_g BCEWithLogits( ffn( dropout(emb_g) ), target_g )     model.py:147-150, 169, 190-198; data.py:37
  * and, for d loss = 1, d loss / d sim (block rows: only every atom's own column block is written -- what the last
  * convolution's backward reads) and the six parameter gradients.  The loss is a mean over molecules, so a molecule's chain
@@ -408,6 +408,21 @@ typedef struct mkgnn_tail_args {
 int mkgnn_tail_supported(int32_t K, int32_t H, int32_t G, const int32_t num_kernels[MKGNN_MAX_DEGREE]);
 size_t mkgnn_tail_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols);
 int mkgnn_tail_fused(const mkgnn_tail_args* args, void* workspace, size_t workspace_bytes, void* stream);
+/* The readout's dropout (MolKGNNNet.py:144-146, drop_ratio: between swish(lin1(h)) and lin2), drawn inside the kernels from the
+ * head's generator -- the mask convention below.  A call with head dropout (args->dropout_p), readout dropout or both reads
+ * args->rng_state once, copies it to args->rng_used and advances its offset by exactly one (the deferred reduction included);
+ * both masks come from that one pair.  readout_dropout_p in [0, 1); 0: mkgnn_tail_fused, bit for bit. */
+int mkgnn_tail_fused_readout_dropout(const mkgnn_tail_args* args, float readout_dropout_p, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+/* The readout dropout mask convention (ABI v8, shared by mkgnn_tail_fused_readout_dropout and mkgnn_molecule_step with
+ * MKGNN_MOLECULE_READOUT_DROPOUT): Philox4x32-10 keyed by seed, counter (element / 4, offset), word element % 4 -- the
+ * generator of the head's dropout -- at  element = 2^62 + atom * H + h  (atom: the atom's row in the batch; the head's elements
+ * are mol * G + j, below 2^62).  u = (word >> 8) / 2^24; dropped when u < p, else scaled by 1 / (1 - p).  A function of
+ * (seed, offset, atom, h) alone: not of chunking, and appended padding atoms leave the real atoms' masks as they are.
+ * mkgnn_readout_dropout_mask writes those multipliers, keep [n_rows, H] (row stride keep_stride), for the {seed, offset}
+ * pair at rng_pair on the device (the rng_used of a call, say); it reads the pair and advances nothing. */
+int mkgnn_readout_dropout_mask(const int64_t* rng_pair, int64_t n_rows, int32_t H, float p, float* keep, int64_t keep_stride,
+                               void* stream);
 /* Launches a reduction that a mkgnn_tail_fused call with defer_reduce left pending on this thread, on `stream` (no-op: none). */
 int mkgnn_tail_flush(void* stream);
 
@@ -689,8 +704,9 @@ typedef struct mkgnn_molecule_net {
     const float* ffn_weight; const float* ffn_bias;
     float* grad_ffn_weight; float* grad_ffn_bias;
     float head_dropout;                              /* 0 = none */
-    int32_t reserved2;
-    int64_t* rng_state;                              /* {seed, offset} of the head's dropout (offset advanced by the call) */
+    float readout_dropout;                           /* (ABI v8) read with MKGNN_MOLECULE_READOUT_DROPOUT only: p in [0, 1) */
+    int64_t* rng_state;                              /* {seed, offset} of the head's and the readout's dropout (offset advanced
+                                                        by the call; not with GRAD_EMB: see MKGNN_MOLECULE_READOUT_DROPOUT) */
     int64_t* rng_used;                               /* optional: the {seed, offset} this call's mask was drawn with */
     /* edge_batch_norm's side effect (MolKGNNNet.py:116; ABI v5): when not NULL
      * (the caller leaves it NULL on a backward-only call), the bond rows' statistics -- 1..8192 rows, C <= 8; anything else
@@ -715,6 +731,11 @@ typedef struct mkgnn_molecule_batch {
 #define MKGNN_MOLECULE_GRAD_EMB  4   /* BACKWARD without HEAD: d loss / d graph embedding is given */
 #define MKGNN_MOLECULE_SQERR     8   /* (ABI v8) with HEAD: squared error in place of BCE-with-logits (MKGNN_LOSS_SQERR_MEAN) */
 #define MKGNN_MOLECULE_SUM      16   /* (ABI v8) with SQERR: summed, not averaged, over the molecules (MKGNN_LOSS_SQERR_SUM) */
+/* (ABI v8) the readout's dropout, net->readout_dropout in [0, 1), its mask the convention of mkgnn_readout_dropout_mask; needs
+ * rng_state.  Without GRAD_EMB the call draws it from rng_state and advances the offset by one (once, with head dropout too),
+ * rng_used receiving the pair.  With GRAD_EMB -- the backward of a forward-only call -- it reads rng_state and advances
+ * nothing: the caller passes the pair that forward recorded, and the recomputed forward draws the same mask. */
+#define MKGNN_MOLECULE_READOUT_DROPOUT 32
 
 int mkgnn_molecule_supported(const mkgnn_molecule_net* net, int32_t x_dim);
 size_t mkgnn_molecule_workspace_bytes(const mkgnn_molecule_net* net, int32_t x_dim, int64_t n_atoms, int64_t n_chunks);

@@ -140,8 +140,9 @@ class MolKGNNNet(torch.nn.Module):
             # (from _PROJECT_FIRST_ATOMS atoms on -- or at any size where the dense readout kernels do not take the shape, e.g. 160
             # kernels per layer: the block-row form takes up to 255 columns and keeps such a model off the PyTorch-operator path)
             # (... or at any size when the caller wants the loss itself: the fused tail -- readout.tail_loss -- starts from block rows)
-            no_drop = self.dropout is None or not self.dropout.training or self.dropout.p == 0.0
-            want_tail = (_tail is not None and R._FUSED_TAIL and torch.is_grad_enabled() and no_drop and x.is_cuda
+            # (the readout's dropout, p < 1, runs inside the fused tail; p >= 1 keeps the separate operators)
+            p_readout = self.dropout.p if (self.dropout is not None and self.dropout.training) else 0.0
+            want_tail = (_tail is not None and R._FUSED_TAIL and torch.is_grad_enabled() and p_readout < 1.0 and x.is_cuda
                          and R.tail_supported(*dims, Ls))
             want = x.is_cuda and not save_score and (_PROJECT_FIRST == '1' or (_PROJECT_FIRST != '0' and (
                 x.shape[0] >= _PROJECT_FIRST_ATOMS or not R.readout_supported(*dims) or want_tail)))
@@ -163,7 +164,8 @@ class MolKGNNNet(torch.nn.Module):
             if want_tail and sim_sc.requires_grad and R._tail_limits_ok(seg, plan):
                 ffn, target, p_head, n_rows, *kind = _tail       # (ffn, y, dropout p, real molecules[, loss kind: "bce"])
                 loss = kind[0] if kind else "bce"
-                return ("loss", R.tail_loss(sim_sc, plan, Ls, lin1, lin2, ffn, target, seg, p_head, n_rows, loss))
+                return ("loss", R.tail_loss(sim_sc, plan, Ls, lin1, lin2, ffn, target, seg, p_head, n_rows, loss,
+                                            readout_dropout_p=p_readout))
             return R.readout_blocks(sim_sc, plan, Ls, lin1, lin2, self.dropout, seg)
         # pool(lin2(dropout(act(lin1(h)))), batch) -- MolKGNNNet.py:144-146 -- as one operator
         return R.readout(node_representation, lin1, lin2, self.dropout, data.batch, getattr(data, 'num_graphs', None), segments=seg)

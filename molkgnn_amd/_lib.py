@@ -99,6 +99,7 @@ MOLECULE_MAX_LAYERS = 4
 MOLECULE_MAX_ATOMS = 64
 MOLECULE_MAX_MOLS = 16
 MOLECULE_HEAD, MOLECULE_BACKWARD, MOLECULE_GRAD_EMB, MOLECULE_SQERR, MOLECULE_SUM = 1, 2, 4, 8, 16
+MOLECULE_READOUT_DROPOUT = 32
 
 
 class MoleculeLayer(C.Structure):
@@ -123,7 +124,7 @@ class MoleculeNet(C.Structure):
                 ("grad_lin1_weight", C.c_void_p), ("grad_lin1_bias", C.c_void_p), ("grad_lin2_weight", C.c_void_p),
                 ("grad_lin2_bias", C.c_void_p),
                 ("ffn_weight", C.c_void_p), ("ffn_bias", C.c_void_p), ("grad_ffn_weight", C.c_void_p),
-                ("grad_ffn_bias", C.c_void_p), ("head_dropout", C.c_float), ("reserved2", C.c_int32),
+                ("grad_ffn_bias", C.c_void_p), ("head_dropout", C.c_float), ("readout_dropout", C.c_float),
                 ("rng_state", C.c_void_p), ("rng_used", C.c_void_p), ("edge_stats", C.POINTER(BnStats))]
 
 
@@ -146,6 +147,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_molecule_step", "mkgnn_batchnorm_stats_workspace_bytes", "mkgnn_batchnorm_update_stats",
            "mkgnn_batchnorm_forward_with_stats", "mkgnn_index_workspace_bytes", "mkgnn_index_build",
            "mkgnn_rows_split_supported", "mkgnn_rows_presplit", "mkgnn_tail_supported", "mkgnn_tail_workspace_bytes", "mkgnn_tail_fused", "mkgnn_tail_flush", "mkgnn_flat_copy",
+           "mkgnn_tail_fused_readout_dropout", "mkgnn_readout_dropout_mask",
            "mkgnn_head_loss_forward", "mkgnn_head_loss_backward", "mkgnn_head_loss_dropout_forward",
            "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused")
 
@@ -211,6 +213,10 @@ def load() -> C.CDLL:
     lib.mkgnn_tail_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
     lib.mkgnn_tail_fused.restype = C.c_int
     lib.mkgnn_tail_fused.argtypes = [C.POINTER(TailArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mkgnn_tail_fused_readout_dropout.restype = C.c_int
+    lib.mkgnn_tail_fused_readout_dropout.argtypes = [C.POINTER(TailArgs), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mkgnn_readout_dropout_mask.restype = C.c_int
+    lib.mkgnn_readout_dropout_mask.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]
     lib.mkgnn_flat_copy.restype = C.c_int
     lib.mkgnn_flat_copy.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     lib.mkgnn_tail_flush.restype = C.c_int

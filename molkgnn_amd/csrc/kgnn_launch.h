@@ -196,6 +196,7 @@ struct TailMidArgs {
     float* pred;
     float* slab; int slab_stride;           // [blocks][slab_stride]: TAIL_* below
     int mg;                                 // molecules per group: tail_group_size(n_loss)
+    float rdrop_p;                          // the readout's dropout (only the readout-dropout instantiations read it)
 };
 constexpr int TAIL_MAX_BLOCKS = 768;        // (three workgroups per CU)
 // a workgroup's slab (floats): b1 [32] | W2 [32][32] | b2 [32] | wh [32] | bh | loss
@@ -205,7 +206,8 @@ constexpr int TAIL_B1 = 0, TAIL_W2 = 32, TAIL_B2 = 32 + 1024, TAIL_WH = TAIL_B2 
 hipError_t launch_pending_tail_reduce(hipStream_t st, bool* launched = nullptr);
 int tail_group_size(int64_t n_loss_mols);
 int tail_middle_blocks(int64_t n_loss_mols);
-hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st);   // loss_kind: MKGNN_LOSS_*
+// loss_kind: MKGNN_LOSS_*; a.rdrop_p > 0: the instantiations with the readout's dropout mask
+hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st);
 
 struct BankStreamLaunch { BankStreamArgs a; int nb, prep_blocks, KC; size_t lds_bytes; int x_split; };
 // block split and arguments once; then the pre-pass (coefficient records in tile order, score-weight partials) and the

@@ -64,6 +64,7 @@ struct MolArgs {
     int nl; MolLayer layer[MKGNN_MOLECULE_MAX_LAYERS];
     // readout
     const float *w1p, *w1pt; const float *b1, *w2, *b2; int H, G, HP, K3;
+    float rdrop;                       // the readout's dropout (MKGNN_MOLECULE_READOUT_DROPOUT; 0: none), mask from rng
     // head
     int mode; const float *ffn_w, *ffn_b, *y; float head_drop; const int64_t* rng;
     const float* demb; float* emb; float* pred;
@@ -325,6 +326,10 @@ __device__ __forceinline__ uint32_t mol_philox_word(uint64_t seed, uint64_t offs
 __device__ __forceinline__ float mol_keep_scale(uint64_t seed, uint64_t offset, uint64_t element, float p) {
     const float u = (float)(mol_philox_word(seed, offset, element) >> 8) * (1.f / 16777216.f);
     return u >= p ? 1.f / (1.f - p) : 0.f;
+}
+// the readout's mask: element 2^62 + atom * H + h, atom the batch row (kgnn_philox.h readout_drop_element: the fused tail's mask)
+__device__ __forceinline__ float mol_readout_keep(uint64_t seed, uint64_t offset, int64_t atom, int H, int h, float p) {
+    return mol_keep_scale(seed, offset, ((uint64_t)1 << 62) + (uint64_t)atom * (uint64_t)H + (uint64_t)h, p);
 }
 
 // 1 / max(|row|, eps) of the NAP rows of `buf` (stride XS, FP columns): eight threads per row
@@ -667,7 +672,8 @@ __device__ __forceinline__ void mol_bwd4_bank(MolLayerK& Y, const float* gtab, c
 // the one full barrier at the forward -> backward transition.
 #define MOL_BAR() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
 
-template <int NT, int NTR>
+// RD: the readout's dropout (a.rdrop > 0), a template parameter so that the step without it stays as it was
+template <int NT, int NTR, bool RD>
 __device__ __forceinline__ void molecule_step_body(MolArgsP ap, float* lds) {
     const MOL_K MolArgs& a = *ap;
     constexpr int NAP = 16 * NT;
@@ -957,11 +963,17 @@ __device__ __forceinline__ void molecule_step_body(MolArgsP ap, float* lds) {
             for (int i = 0; i < 4; ++i) pre[(mt * 16 + 4 * q + i) * MOL_HS + ht * 16 + r] = acc[i] + bias;
         }
         MOL_BAR();
-        // the molecules' sums of swish(pre): 8 threads per (molecule, hidden unit)
+        // the molecules' sums of swish(pre) -- times the readout's keep with RD: 8 threads per (molecule, hidden unit)
+        const uint64_t rseed = RD ? (uint64_t)a.rng[0] : 0, roff = RD ? (uint64_t)a.rng[1] : 0;
         for (int it = tid; it < nm * H * 8; it += MOL_THREADS) {
             const int s8 = it & 7, gh = it >> 3, g = gh / H, h = gh - g * H;
             float s = 0.f;
-            for (int j = m.mol_first[g] + s8; j < m.mol_first[g + 1]; j += 8) { const float x = pre[j * MOL_HS + h]; s += x * sigmoid_m(x); }
+            for (int j = m.mol_first[g] + s8; j < m.mol_first[g + 1]; j += 8) {
+                const float x = pre[j * MOL_HS + h];
+                float sw = x * sigmoid_m(x);
+                if constexpr (RD) sw *= mol_readout_keep(rseed, roff, a0 + j, H, h, a.rdrop);
+                s += sw;
+            }
             s += __shfl_xor(s, 4, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 1, 64);
             if (s8 == 0) pooled[g * 64 + h] = s;
         }
@@ -1068,12 +1080,15 @@ __device__ __forceinline__ void molecule_step_body(MolArgsP ap, float* lds) {
         }
     }
     MOL_BAR();
-    for (int it = tid; it < NR * HP; it += MOL_THREADS) {        // d pre = d pooled[mol] * swish'(pre), in place
+    const uint64_t rseed = RD ? (uint64_t)a.rng[0] : 0, roff = RD ? (uint64_t)a.rng[1] : 0;     // (RD: the forward's mask, again)
+    for (int it = tid; it < NR * HP; it += MOL_THREADS) {        // d pre = d pooled[mol] (* keep) * swish'(pre), in place
         const int j = it / HP, h = it - j * HP;
         float v = 0.f;
         if (j < NA && h < H) {
             const float x = pre[j * MOL_HS + h], sg = sigmoid_m(x);
-            v = dpool[m.mol[j] * 64 + h] * (sg * (1.f + x * (1.f - sg)));
+            float dp = dpool[m.mol[j] * 64 + h];
+            if constexpr (RD) dp *= mol_readout_keep(rseed, roff, a0 + j, H, h, a.rdrop);
+            v = dp * (sg * (1.f + x * (1.f - sg)));
         }
         pre[j * MOL_HS + h] = v;
     }
@@ -1298,17 +1313,17 @@ __device__ __forceinline__ void molecule_step_body(MolArgsP ap, float* lds) {
 #undef MOL_STAMP
 }
 
-template <int NT>
+template <int NT, bool RD>
 __global__ void __launch_bounds__(MOL_THREADS) molecule_step_kernel(MolArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     MolArgsP ap = (MolArgsP)__builtin_amdgcn_kernarg_segment_ptr();        // (`a` is the kernel's first and only argument)
     if constexpr (NT > 2) {
         const int m0 = a.chunk_ptr[blockIdx.x], m1 = a.chunk_ptr[blockIdx.x + 1];
         const int64_t na = a.mol_ptr[m1] - a.mol_ptr[m0];
-        if (na > 48) { molecule_step_body<NT, NT>(ap, lds); return; }
-        if (na > 32) { molecule_step_body<NT, 3>(ap, lds); return; }      // (molecules of 33 .. 48 atoms: three atom tiles, not four)
+        if (na > 48) { molecule_step_body<NT, NT, RD>(ap, lds); return; }
+        if (na > 32) { molecule_step_body<NT, 3, RD>(ap, lds); return; }      // (molecules of 33 .. 48 atoms: three atom tiles, not four)
     }
-    molecule_step_body<NT, 2>(ap, lds);
+    molecule_step_body<NT, 2, RD>(ap, lds);
 }
 
 // ------------------------------------------------------------------------------------------------ reduction ----
@@ -1326,7 +1341,7 @@ struct MolReduceArgs {
     int H, G, HP, K3, C; size_t s_dw1; int s_loss, s_ffn, s_lin2, s_lin1b, s_bn;
     float *g_w1, *g_b1, *g_w2, *g_b2, *g_ffn_w, *g_ffn_b, *g_bn_w, *g_bn_b;
     float* loss; int n_mols; int mode;
-    int64_t* rng; int64_t* rng_used; float head_drop;
+    int64_t* rng; int64_t* rng_used; int advance;     // advance: the call drew a dropout mask (head, readout or both) from rng
 };
 
 // sum of element `e` (offset inside a chunk's slab) over the chunks [c0, c1), ascending, eight loads in flight
@@ -1395,7 +1410,7 @@ __global__ void __launch_bounds__(256) molecule_reduce_kernel(MolReduceArgs a) {
         sh[wv * 64 + lane] = off >= 0 ? mol_sum_range(a.slab, a.slab_floats, c0, c1, (size_t)off) : 0.f;
         __syncthreads();
         if (wv == 0 && off >= 0) dst[0] = ((sh[lane] + sh[64 + lane]) + (sh[128 + lane] + sh[192 + lane])) * scale;
-        if (e == 0 && wv == 0 && head && a.head_drop > 0.f && a.rng) {
+        if (e == 0 && wv == 0 && a.advance && a.rng) {
             const int64_t seed = a.rng[0], offset = a.rng[1];
             if (a.rng_used) { a.rng_used[0] = seed; a.rng_used[1] = offset; }
             a.rng[1] = offset + 1;
@@ -1602,12 +1617,16 @@ int mkgnn_molecule_step(const mkgnn_molecule_net* net, const mkgnn_molecule_batc
     if (!emb) return api_fail("%s: emb is null", who);
     if (head && (!target || !pred || !loss || !net->ffn_weight)) return api_fail("%s: HEAD needs target, pred, loss and the ffn weight", who);
     if (head && ext) return api_fail("%s: HEAD and GRAD_EMB exclude each other", who);
-    if (mode & ~31) return api_fail("%s: unknown mode bits 0x%x", who, (unsigned)mode);
+    if (mode & ~63) return api_fail("%s: unknown mode bits 0x%x", who, (unsigned)mode);
     if ((mode & (MKGNN_MOLECULE_SQERR | MKGNN_MOLECULE_SUM)) && !head) return api_fail("%s: SQERR / SUM need HEAD", who);
     if ((mode & MKGNN_MOLECULE_SUM) && !(mode & MKGNN_MOLECULE_SQERR)) return api_fail("%s: SUM needs SQERR", who);
     if (bwd && !head && (!ext || !grad_emb)) return api_fail("%s: BACKWARD needs HEAD or GRAD_EMB with grad_emb", who);
     if (head && net->head_dropout > 0.f && !net->rng_state) return api_fail("%s: head dropout needs rng_state", who);
     if (!(net->head_dropout >= 0.f && net->head_dropout < 1.f)) return api_fail("%s: head dropout outside [0, 1)", who);
+    const bool rdrop_bit = (mode & MKGNN_MOLECULE_READOUT_DROPOUT) != 0;
+    if (rdrop_bit && !(net->readout_dropout >= 0.f && net->readout_dropout < 1.f)) return api_fail("%s: readout dropout outside [0, 1)", who);
+    if (rdrop_bit && !net->rng_state) return api_fail("%s: readout dropout needs rng_state", who);
+    const float rdrop = rdrop_bit ? net->readout_dropout : 0.f;
     if (!net->bn_training && (!net->bn_running_mean || !net->bn_running_var)) return api_fail("%s: eval-mode batch norm needs running statistics", who);
     for (int i = 0; i < 4; ++i) {
         const mkgnn_degree_bucket& b = batch->buckets[i];
@@ -1689,7 +1708,7 @@ int mkgnn_molecule_step(const mkgnn_molecule_net* net, const mkgnn_molecule_batc
         Y.slab_bank = s.slab_bank[li]; Y.slab_edge = s.slab_edge[li]; Y.theta_slot = s.theta_slot[li];
     }
     a.w1p = pa.w1p; a.w1pt = pa.w1pt; a.b1 = net->readout.lin1_bias; a.w2 = net->readout.lin2_weight; a.b2 = net->readout.lin2_bias;
-    a.H = s.H; a.G = s.G; a.HP = s.HP; a.K3 = s.K3;
+    a.H = s.H; a.G = s.G; a.HP = s.HP; a.K3 = s.K3; a.rdrop = rdrop;
     a.mode = mode; a.ffn_w = net->ffn_weight; a.ffn_b = net->ffn_bias; a.y = target; a.head_drop = head ? net->head_dropout : 0.f; a.rng = net->rng_state;
     a.demb = grad_emb; a.emb = emb; a.pred = pred;
     a.stamps = g_mol_stamps;
@@ -1699,8 +1718,10 @@ int mkgnn_molecule_step(const mkgnn_molecule_net* net, const mkgnn_molecule_batc
     {   // (the LDS ceiling is a per-device function attribute)
         static PerDeviceOnce attr_set;
         if (const int slot = attr_set.pending(); slot >= 0) {
-            hipError_t e2 = hipFuncSetAttribute((const void*)molecule_step_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MOL_LDS_MAX);
-            if (e2 == hipSuccess) e2 = hipFuncSetAttribute((const void*)molecule_step_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MOL_LDS_MAX);
+            const void* fns[4] = {(const void*)molecule_step_kernel<2, false>, (const void*)molecule_step_kernel<4, false>,
+                                  (const void*)molecule_step_kernel<2, true>, (const void*)molecule_step_kernel<4, true>};
+            hipError_t e2 = hipSuccess;
+            for (int i = 0; i < 4 && e2 == hipSuccess; ++i) e2 = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)MOL_LDS_MAX);
             if (e2 != hipSuccess) return api_hip_fail(who, e2);
             attr_set.set(slot);
         }
@@ -1718,8 +1739,11 @@ int mkgnn_molecule_step(const mkgnn_molecule_net* net, const mkgnn_molecule_batc
         a.cache_on = mol_lds_bytes(small_chunks ? 2 : 4) + (size_t)o * 4 <= MOL_LDS_MAX ? 1 : 0;
     }
     const size_t lds_bytes = mol_lds_bytes(small_chunks ? 2 : 4) + (a.cache_on ? (size_t)a.cache_floats * 4 : 0);
-    if (small_chunks) molecule_step_kernel<2><<<(unsigned)batch->n_chunks, MOL_THREADS, lds_bytes, st>>>(a);
-    else molecule_step_kernel<4><<<(unsigned)batch->n_chunks, MOL_THREADS, lds_bytes, st>>>(a);
+    if (rdrop > 0.f) {
+        if (small_chunks) molecule_step_kernel<2, true><<<(unsigned)batch->n_chunks, MOL_THREADS, lds_bytes, st>>>(a);
+        else molecule_step_kernel<4, true><<<(unsigned)batch->n_chunks, MOL_THREADS, lds_bytes, st>>>(a);
+    } else if (small_chunks) molecule_step_kernel<2, false><<<(unsigned)batch->n_chunks, MOL_THREADS, lds_bytes, st>>>(a);
+    else molecule_step_kernel<4, false><<<(unsigned)batch->n_chunks, MOL_THREADS, lds_bytes, st>>>(a);
 
     // ---- reduction of the chunks' partials (and the loss; the head's generator moves on)
     MolReduceArgs ra{};
@@ -1743,8 +1767,10 @@ int mkgnn_molecule_step(const mkgnn_molecule_net* net, const mkgnn_molecule_batc
     ra.g_w1 = net->grad_lin1_weight; ra.g_b1 = net->grad_lin1_bias; ra.g_w2 = net->grad_lin2_weight; ra.g_b2 = net->grad_lin2_bias;
     ra.g_ffn_w = net->grad_ffn_weight; ra.g_ffn_b = net->grad_ffn_bias; ra.g_bn_w = net->grad_bn_weight; ra.g_bn_b = net->grad_bn_bias;
     ra.loss = loss; ra.n_mols = (int)batch->n_mols; ra.mode = mode & 31;
-    ra.rng = net->rng_state; ra.rng_used = net->rng_used; ra.head_drop = head ? net->head_dropout : 0.f;
-    if (head || bwd) molecule_reduce_kernel<<<rtask, 256, 0, st>>>(ra);
+    // (the generator moves on once per drawn mask; not with GRAD_EMB, whose recomputed forward redraws its forward's)
+    ra.rng = net->rng_state; ra.rng_used = net->rng_used;
+    ra.advance = ((head && net->head_dropout > 0.f) || (rdrop > 0.f && !ext)) ? 1 : 0;
+    if (head || bwd || ra.advance) molecule_reduce_kernel<<<rtask, 256, 0, st>>>(ra);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }

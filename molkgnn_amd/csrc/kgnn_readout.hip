@@ -2197,8 +2197,8 @@ size_t mkgnn_tail_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_ato
     return tail_ws(d, n_atoms, n_mols).total;
 }
 
-int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "mkgnn_tail_fused";
+// rp: the readout's dropout (mkgnn_tail_fused_readout_dropout), 0 for mkgnn_tail_fused
+static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void* ws, size_t ws_bytes, void* stream) {
     if (!p) return api_fail("%s: null argument", who);
     const mkgnn_readout_params* ro = &p->readout;
     ReadoutDims d;
@@ -2211,6 +2211,8 @@ int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
         return api_fail("%s: null pointer", who);
     if (p->dropout_p < 0.f || p->dropout_p >= 1.f) return api_fail("%s: dropout probability %g outside [0, 1)", who, (double)p->dropout_p);
     if (p->dropout_p > 0.f && (!p->rng_state || !p->rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
+    if (!(rp >= 0.f && rp < 1.f)) return api_fail("%s: readout dropout probability %g outside [0, 1)", who, (double)rp);
+    if (rp > 0.f && (!p->rng_state || !p->rng_used)) return api_fail("%s: readout dropout needs rng_state and rng_used", who);
     if (p->emb && p->emb_stride < ro->G) return api_fail("%s: bad emb stride", who);
     if (p->loss_kind < MKGNN_LOSS_BCE_MEAN || p->loss_kind > MKGNN_LOSS_SQERR_SUM) return api_fail("%s: unknown loss kind %d", who, (int)p->loss_kind);
     BlockProjArgs b{};
@@ -2243,7 +2245,7 @@ int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
     m.z = z; m.dz = dz; m.rin = p->in_rowptr; m.cin = p->in_col; m.rout = p->out_rowptr; m.cout = p->out_col;
     m.mol_ptr = p->mol_ptr; m.atom_mol = p->atom_mol; m.n_atoms = p->n_atoms; m.n_mols = p->n_mols; m.n_loss = p->n_loss_mols;
     m.b1 = ro->lin1_bias; m.w2 = ro->lin2_weight; m.b2 = ro->lin2_bias; m.wh = p->head_weight; m.bh = p->head_bias; m.y = p->target;
-    m.H = ro->H; m.G = ro->G; m.drop_p = p->dropout_p; m.rng = p->rng_state;
+    m.H = ro->H; m.G = ro->G; m.drop_p = p->dropout_p; m.rng = p->rng_state; m.rdrop_p = rp;
     m.emb = p->emb; m.es = p->emb_stride; m.pred = p->pred;
     m.slab = (float*)((char*)ws + w.slab_tail); m.slab_stride = TAIL_SLAB;
     m.mg = tail_group_size(p->n_loss_mols);
@@ -2270,7 +2272,7 @@ int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
         const size_t lds = ((size_t)d.HP * 68 + (img > 4096 ? img : 4096)) * 4;
         block_project_bwd_mfma_kernel<2><<<(unsigned)nb, 256, lds, st>>>(b, tpw);
     }
-    // (4) every partial slab -> its gradient, the loss; the dropout generator advances
+    // (4) every partial slab -> its gradient, the loss; the dropout generator advances (once, for either dropout or both)
     SlabReduceArgs r{};
     int blk = 0;
     auto add = [&](const float* src, int stride, int count, int src_cols, int rows, int cols, float* dst, int dst_stride) {
@@ -2301,7 +2303,7 @@ int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
     add(m.slab + TAIL_WH, TAIL_SLAB, nbm, 32, 1, ro->G, p->grad_head_weight, 0);
     add(m.slab + TAIL_BH, TAIL_SLAB, nbm, 1, 1, 1, p->grad_head_bias, 0);
     add(m.slab + TAIL_LOSS, TAIL_SLAB, nbm, 1, 1, 1, p->loss, 0);
-    r.drop_p = p->dropout_p; r.rng = p->rng_state; r.rng_used = p->rng_used;
+    r.drop_p = p->dropout_p > 0.f ? p->dropout_p : rp; r.rng = p->rng_state; r.rng_used = p->rng_used;
     if (p->defer_reduce && blk > 0) {                    // round 6: off the critical chain -- see mkgnn_tail_args.defer_reduce
         e = hipGetLastError();                           // (this call's launches so far: a failed one is reported, not left pending)
         if (e != hipSuccess) return api_hip_fail(who, e);
@@ -2312,6 +2314,39 @@ int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
     }
     if (blk > 0) slab_reduce_kernel<<<blk, 256, 0, st>>>(r);
     e = hipGetLastError();
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* stream) {
+    return tail_fused("mkgnn_tail_fused", p, 0.f, ws, ws_bytes, stream);
+}
+
+int mkgnn_tail_fused_readout_dropout(const mkgnn_tail_args* p, float readout_dropout_p, void* ws, size_t ws_bytes, void* stream) {
+    return tail_fused("mkgnn_tail_fused_readout_dropout", p, readout_dropout_p, ws, ws_bytes, stream);
+}
+
+// keep[r][h] of the readout's dropout: what the fused tail and the molecule-resident step draw for batch atom r (kgnn_philox.h)
+struct ReadoutMaskArgs { const int64_t* rng; int64_t n; int H; float p; float* keep; int64_t ks; };
+__global__ void __launch_bounds__(256) readout_dropout_mask_kernel(ReadoutMaskArgs a) {
+    const int64_t total = a.n * a.H;
+    const uint64_t seed = (uint64_t)a.rng[0], offset = (uint64_t)a.rng[1];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / a.H;
+        const int h = (int)(i - r * a.H);
+        a.keep[r * a.ks + h] = keep_scale_of(seed, offset, readout_drop_element(r, a.H, h), a.p);
+    }
+}
+
+int mkgnn_readout_dropout_mask(const int64_t* rng_pair, int64_t n_rows, int32_t H, float p, float* keep, int64_t keep_stride, void* stream) {
+    const char* who = "mkgnn_readout_dropout_mask";
+    if (!rng_pair || !keep) return api_fail("%s: null pointer", who);
+    if (n_rows < 0 || H < 1 || keep_stride < H) return api_fail("%s: bad sizes", who);
+    if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, (double)p);
+    if (n_rows == 0) return 0;
+    ReadoutMaskArgs a{rng_pair, n_rows, H, p, keep, keep_stride};
+    const int64_t blocks = (n_rows * H + 255) / 256;
+    readout_dropout_mask_kernel<<<(unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, (hipStream_t)stream>>>(a);
+    const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }
 

@@ -12,8 +12,8 @@
 // latency (a dependent kernel costs ~5 us in a captured graph on this chip whatever it does).  Now:
 //     z = W1[:, block] sim[block]                                        block_project_mfma_kernel        (matrix cores, as before)
 //     THIS FILE: per chunk of whole molecules, on the H-wide rows --     tail_middle_kernel
-//         pre = b1 + sum of z over the in-edges;  e_g = sum_n swish(pre_n);  emb_g = W2 e_g + |g| b2;  logit, loss, d logit;
-//         d emb, d e_g;  d pre = d e_g * swish'(pre);  d z = sum of d pre over the out-edges;  partial dW2, db1, db2, d head
+//         pre = b1 + sum of z over the in-edges;  e_g = sum_n keep_n swish(pre_n);  emb_g = W2 e_g + |g| b2;  logit, loss, d logit;
+//         d emb, d e_g;  d pre = d e_g * keep * swish'(pre);  d z = sum of d pre over the out-edges;  partial dW2, db1, db2, d head
 //     d sim[block] = W1[:, block]^T d z,  dW1 += d z (x) sim              block_project_bwd_mfma_kernel    (matrix cores, as before)
 //     all partial slabs -> the gradients, the loss                       slab_reduce_kernel
 // (A first version did the two projections here too, on the vector pipe out of LDS: 530 us -- three 98 MFLOP products with an
@@ -23,11 +23,12 @@
 // <= MC molecules): bulk loads of the chunk's indices and z rows, block-wide barriers between the phases.  Molecules never
 // share atoms or edges, so a chunk needs nothing from outside.  No float atomics: every sum runs in a fixed order, the
 // per-workgroup partial gradients go to slabs that the reduction adds up in block order.  The dropout mask of the head comes
-// from the same counter-based generator, element for element, as mkgnn_bce_head_fused (kgnn_philox.h).
+// from the same counter-based generator, element for element, as mkgnn_bce_head_fused (kgnn_philox.h); so does the readout's
+// (keep above: mkgnn_tail_fused_readout_dropout, the template parameter RD), drawn in P3 and drawn again in P5 -- one Philox
+// block gives a lane its four hidden units -- instead of being stored.
 //
-// Limits (mkgnn_tail_supported; the host falls back to the nine launches otherwise): H <= 32, G <= 32, no dropout inside the
-// readout, and -- checked per batch by the host, which knows the molecule sizes -- no single molecule beyond a chunk (128
-// atoms, 512 edges).  A molecule that breaks the last promise is skipped and the loss comes back NaN: loud, not wrong.
+// Limits (mkgnn_tail_supported; the host falls back to the nine launches otherwise): H <= 32, G <= 32, and -- checked per
+// batch by the host, which knows the molecule sizes -- no single molecule beyond a chunk (128 atoms, 512 edges).  A molecule that breaks the last promise is skipped and the loss comes back NaN: loud, not wrong.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <math.h>
@@ -93,6 +94,16 @@ __device__ __forceinline__ void gather_rows(const int* rp, const int* ec, const 
     }
 }
 
+// the readout's keep multipliers of hidden units 4 l .. 4 l + 3 of batch atom `atom` (kgnn_philox.h; 1 at and beyond H)
+__device__ __forceinline__ void readout_keep4(uint64_t seed, uint64_t offset, int64_t atom, int H, int l, float p, float (&ks)[4]) {
+    if ((H & 3) == 0 && 4 * l < H) {                     // (H = 32: always -- a 4-aligned element, one Philox block)
+        keep_scale4_of(seed, offset, readout_drop_element(atom, H, 4 * l), p, ks);
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) ks[c] = 4 * l + c < H ? keep_scale_of(seed, offset, readout_drop_element(atom, H, 4 * l + c), p) : 1.f;
+}
+
 // Diagnostics (always compiled, off unless mkgnn_debug_set_tail_stamps gave a buffer): cycle totals of the middle kernel's phases,
 // thread 0 of every workgroup -> [block][16] (tools/tail_stamps.py)
 __device__ unsigned long long* g_tail_stamps = nullptr;
@@ -101,8 +112,9 @@ __device__ unsigned long long* g_tail_stamps = nullptr;
 constexpr int LDS_FLOATS = 32 * WP + 2 * AC * HP + 3 * MC * HP + 96;
 constexpr int LDS_INTS = AC + 2 * (AC + 1) + 2 * EC + 3 * (MC + 1) + 4;
 
-// LK: the loss kind (MKGNN_LOSS_*), a template parameter so that the BCE instantiation's code stays as it was
-template <int LK>
+// LK: the loss kind (MKGNN_LOSS_*), a template parameter so that the BCE instantiation's code stays as it was; RD: the readout's
+// dropout (a.rdrop_p), one too, so that the instantiations without it stay as they were
+template <int LK, bool RD>
 __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
     __shared__ __align__(16) float lds[LDS_FLOATS + LDS_INTS];
     float* const W2s = lds;                              // [32][HP]
@@ -140,7 +152,7 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
     }
     const float bh = a.bh ? a.bh[0] : 0.f;
     const bool drop = a.drop_p > 0.f;
-    const uint64_t seed = drop ? (uint64_t)a.rng[0] : 0, offset = drop ? (uint64_t)a.rng[1] : 0;
+    const uint64_t seed = (drop || RD) ? (uint64_t)a.rng[0] : 0, offset = (drop || RD) ? (uint64_t)a.rng[1] : 0;
     const float invB = 1.f / (float)a.n_loss;
     for (int i = t; i < 32 * WP; i += NT) W2s[i] = 0.f;
     if (t < 96) vec[t] = vr;
@@ -245,7 +257,7 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
         __syncthreads();
         continue;
 #endif
-        // ---- P3: pre = b1 + sum of z over the in-edges; swish
+        // ---- P3: pre = b1 + sum of z over the in-edges; swish (times the readout's keep with RD)
         f32x4 sw[AC / 32];
         {
             // (all of a pass's index reads, then all of its row reads, then the sums: written atom by atom the two dependent LDS
@@ -262,6 +274,12 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
                     *(f32x4*)(zp + at * HP + 4 * l) = pv;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) sw[u][c] = pv[c] * sigmoidf_(pv[c]);
+                    if constexpr (RD) {
+                        float ks[4];
+                        readout_keep4(seed, offset, (int64_t)a0 + at, H, l, a.rdrop_p, ks);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) sw[u][c] *= ks[c];
+                    }
                 }
             }
         }
@@ -333,7 +351,7 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
             const int i = (t + NT * u) >> 5, k = (t + NT * u) & 31;
             for (int g = 0; g < nm; ++g) accW2[u] = fmaf(emol_d[g * HP + i], emol_e[g * HP + k], accW2[u]);
         }
-        // ---- P5: d pre = d e_g * swish'(pre)   (in place of pre)
+        // ---- P5: d pre = d e_g * swish'(pre)   (in place of pre; times the readout's keep, drawn again, with RD)
         {
             f32x4 p[AC / 32], de[AC / 32];
 #pragma unroll
@@ -346,6 +364,12 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
             for (int u = 0; u < AC / 32; ++u) {
                 const int at = as + 32 * u;
                 if (at < A) {
+                    if constexpr (RD) {
+                        float ks[4];
+                        readout_keep4(seed, offset, (int64_t)a0 + at, H, l, a.rdrop_p, ks);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) de[u][c] *= ks[c];
+                    }
                     f32x4 dp;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) { const float sg = sigmoidf_(p[u][c]); dp[c] = de[u][c] * (sg * (1.f + p[u][c] * (1.f - sg))); }
@@ -432,15 +456,21 @@ extern "C" int mkgnn_debug_set_tail_stamps(void* device_ptr) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(tail::g_tail_stamps), &device_ptr, sizeof(void*));
 }
 
-hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st) {
-    if (a.mg < tail::MG_MIN || a.mg > tail::MG_MAX || a.mg > tail::MC) return hipErrorInvalidValue;
+template <bool RD>
+static hipError_t launch_tail_middle_rd(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st) {
     switch (loss_kind) {
-    case MKGNN_LOSS_BCE_MEAN: tail::tail_middle_kernel<MKGNN_LOSS_BCE_MEAN><<<nb, tail::NT, 0, st>>>(a); break;
-    case MKGNN_LOSS_SQERR_MEAN: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_MEAN><<<nb, tail::NT, 0, st>>>(a); break;
-    case MKGNN_LOSS_SQERR_SUM: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_SUM><<<nb, tail::NT, 0, st>>>(a); break;
+    case MKGNN_LOSS_BCE_MEAN: tail::tail_middle_kernel<MKGNN_LOSS_BCE_MEAN, RD><<<nb, tail::NT, 0, st>>>(a); break;
+    case MKGNN_LOSS_SQERR_MEAN: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_MEAN, RD><<<nb, tail::NT, 0, st>>>(a); break;
+    case MKGNN_LOSS_SQERR_SUM: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_SUM, RD><<<nb, tail::NT, 0, st>>>(a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st) {
+    if (a.mg < tail::MG_MIN || a.mg > tail::MG_MAX || a.mg > tail::MC) return hipErrorInvalidValue;
+    if (a.rdrop_p > 0.f && !a.rng) return hipErrorInvalidValue;
+    return a.rdrop_p > 0.f ? launch_tail_middle_rd<true>(a, nb, loss_kind, st) : launch_tail_middle_rd<false>(a, nb, loss_kind, st);
 }
 
 }  // namespace mkgnn

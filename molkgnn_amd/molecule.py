@@ -181,8 +181,8 @@ def model_qualifies(net, data, ffn=None) -> bool:
         return False
     if len(net.gnn.layers) > _lib.MOLECULE_MAX_LAYERS:
         return False
-    if net.dropout.training and net.dropout.p > 0.0:
-        return False                                     # readout dropout: not in these kernels (the reference's default is 0)
+    if net.dropout.training and net.dropout.p >= 1.0:
+        return False                                     # (readout dropout p < 1 runs in the kernels: MKGNN_MOLECULE_READOUT_DROPOUT)
     bn = net.node_batch_norm
     if bn.momentum is None or (not bn.training and bn.running_mean is None):
         return False
@@ -231,9 +231,11 @@ def _edge_stats_in_launch(es) -> bool:
             and bn.momentum is not None and bn.running_mean is not None and bn.running_mean.dtype == torch.float32)
 
 
-def _net_struct(net, ffn, params, grads, saved, sims, head_dropout, update_running, rng=None, rng_used=None, edge_stats=None):
+def _net_struct(net, ffn, params, grads, saved, sims, head_dropout, update_running, rng=None, rng_used=None, edge_stats=None,
+                readout_dropout=0.0):
     """``mkgnn_molecule_net`` for the model; ``grads`` / ``saved`` / ``sims``: lists parallel to the layers (or None);
-    ``edge_stats``: ``MolKGNNNet._edge_stats(data)`` where ``_edge_stats_in_launch`` holds."""
+    ``edge_stats``: ``MolKGNNNet._edge_stats(data)`` where ``_edge_stats_in_launch`` holds; ``readout_dropout``: read by the
+    step with ``MOLECULE_READOUT_DROPOUT``."""
     st = _lib.MoleculeNet()
     layers = net.gnn.layers
     st.num_layers = len(layers)
@@ -285,7 +287,8 @@ def _net_struct(net, ffn, params, grads, saved, sims, head_dropout, update_runni
     if ffn is not None:
         st.ffn_weight, st.ffn_bias = _lib.ptr(params[k + 6]), _lib.ptr(params[k + 7])
         st.head_dropout = float(head_dropout)
-        st.rng_state, st.rng_used = _lib.ptr(rng), _lib.ptr(rng_used)
+    st.readout_dropout = float(readout_dropout)
+    st.rng_state, st.rng_used = _lib.ptr(rng), _lib.ptr(rng_used)
     if edge_stats is not None and update_running:
         from .readout import _bn_stats_struct
         es, es_keep = _bn_stats_struct(*edge_stats)
@@ -385,7 +388,16 @@ def _alloc_state(net, plan: BatchPlan, params, want_grads: bool, want_sims: bool
     return saved, grads, sims
 
 
-def _run(net, ffn, params, plan, mp, x, mode, target, grad_emb, head_dropout, update_running, edge_stats=None):
+def _readout_p(net) -> float:
+    """The readout's dropout probability in the network's current mode (``MolKGNNNet.py:144-146``)."""
+    return float(net.dropout.p) if net.dropout.training else 0.0
+
+
+def _run(net, ffn, params, plan, mp, x, mode, target, grad_emb, head_dropout, update_running, edge_stats=None,
+         readout_dropout=0.0, rng_pair=None, rng_used=None):
+    """One ``mkgnn_molecule_step``.  With head or readout dropout the mask comes from ``head_rng_state`` (advanced by the step;
+    ``rng_used``, if given, receives the pair), or -- ``rng_pair``: the backward of a forward-only call -- from that pair, which
+    is not advanced."""
     lib = _lib.load()
     dev = x.device
     want_grads = bool(mode & _lib.MOLECULE_BACKWARD)
@@ -399,13 +411,14 @@ def _run(net, ffn, params, plan, mp, x, mode, target, grad_emb, head_dropout, up
         if ffn is not None:
             small["ffn_w"] = torch.empty_like(params[k + 6])
             small["ffn_b"] = None if params[k + 7] is None else torch.empty_like(params[k + 7])
-    rng = used = None
-    if ffn is not None and head_dropout > 0.0:
+    rng, used = rng_pair, rng_used
+    if rng is None and ((ffn is not None and head_dropout > 0.0) or readout_dropout > 0.0):
         from .readout import head_rng_state
         rng = head_rng_state(dev)
-        used = torch.empty(2, dtype=torch.int64, device=dev)
+        if used is None:
+            used = torch.empty(2, dtype=torch.int64, device=dev)
     st, keep = _net_struct(net, ffn, params, grads if want_grads else None, saved, sims if cap is not None else None,
-                           head_dropout, update_running, rng, used, edge_stats)
+                           head_dropout, update_running, rng, used, edge_stats, readout_dropout)
     if want_grads:
         st.grad_bn_weight, st.grad_bn_bias = _lib.ptr(small["bn_w"]), _lib.ptr(small["bn_b"])
         st.grad_lin1_weight, st.grad_lin1_bias = _lib.ptr(small["w1"]), _lib.ptr(small["b1"])
@@ -457,18 +470,24 @@ class _MoleculeNetFn(torch.autograd.Function):
     launch that runs the backward (nothing but the parameters is kept)."""
 
     @staticmethod
-    def forward(ctx, net, plan, mp, es, x, *params):
+    def forward(ctx, net, plan, mp, es, p_readout, x, *params):
         params = list(params)
-        emb, _, _, _ = _run(net, None, params, plan, mp, x, 0, None, None, 0.0, True, es)
+        # (readout dropout: the backward's recomputed forward redraws this call's mask from the pair it records here)
+        rd = _lib.MOLECULE_READOUT_DROPOUT if p_readout > 0.0 else 0
+        used = torch.empty(2, dtype=torch.int64, device=x.device) if rd else None
+        emb, _, _, _ = _run(net, None, params, plan, mp, x, rd, None, None, 0.0, True, es, readout_dropout=p_readout, rng_used=used)
         ctx.net, ctx.plan, ctx.mp, ctx.x, ctx.params = net, plan, mp, x, params
+        ctx.p_readout, ctx.rng_used = p_readout, used
         return emb
 
     @staticmethod
     def backward(ctx, grad_emb):
         g = grad_emb.contiguous().float()
+        rd = _lib.MOLECULE_READOUT_DROPOUT if ctx.p_readout > 0.0 else 0
         _, _, _, flat = _run(ctx.net, None, ctx.params, ctx.plan, ctx.mp, ctx.x,
-                             _lib.MOLECULE_BACKWARD | _lib.MOLECULE_GRAD_EMB, None, g, 0.0, False)
-        return (None, None, None, None, None) + tuple(_shape_like(gr, p) if p is not None else None for gr, p in zip(flat, ctx.params))
+                             _lib.MOLECULE_BACKWARD | _lib.MOLECULE_GRAD_EMB | rd, None, g, 0.0, False,
+                             readout_dropout=ctx.p_readout, rng_pair=ctx.rng_used)
+        return (None,) * 6 + tuple(_shape_like(gr, p) if p is not None else None for gr, p in zip(flat, ctx.params))
 
 
 class _MoleculeLossFn(torch.autograd.Function):
@@ -477,11 +496,14 @@ class _MoleculeLossFn(torch.autograd.Function):
     the molecule step's mode bits."""
 
     @staticmethod
-    def forward(ctx, net, ffn, p_drop, target, plan, mp, es, kind, x, *params):
+    def forward(ctx, net, ffn, p_drop, target, plan, mp, es, kind, p_readout, x, *params):
         params = list(params)
-        need = any(ctx.needs_input_grad[9:])
+        need = any(ctx.needs_input_grad[10:])
         mode = _lib.MOLECULE_HEAD | (_lib.MOLECULE_BACKWARD if need else 0) | _KIND_MODE[kind]
-        _, pred, loss, flat = _run(net, ffn, params, plan, mp, x, mode, target.reshape(-1).float().contiguous(), None, p_drop, True, es)
+        if p_readout > 0.0:
+            mode |= _lib.MOLECULE_READOUT_DROPOUT         # (one generator pair for both masks, advanced once)
+        _, pred, loss, flat = _run(net, ffn, params, plan, mp, x, mode, target.reshape(-1).float().contiguous(), None, p_drop, True, es,
+                                   readout_dropout=p_readout)
         ctx.flat, ctx.params = flat, params
         ctx.pred = pred
         return loss
@@ -495,7 +517,7 @@ class _MoleculeLossFn(torch.autograd.Function):
         if not _is_unit_seed(grad_loss):
             gl = grad_loss.reshape(()).float()
             flat = [None if g is None else g * gl for g in flat]
-        return (None,) * 9 + tuple(_shape_like(g, p) if p is not None else None for g, p in zip(flat, ctx.params))
+        return (None,) * 10 + tuple(_shape_like(g, p) if p is not None else None for g, p in zip(flat, ctx.params))
 
 
 _KIND_MODE = {_lib.LOSS_BCE_MEAN: 0, _lib.LOSS_SQERR_MEAN: _lib.MOLECULE_SQERR,
@@ -570,7 +592,7 @@ def net_forward(net, data) -> Optional[torch.Tensor]:
         from .readout import update_running_stats
         update_running_stats(*es)
         es = None
-    return _MoleculeNetFn.apply(net, plan, mp, es, data.x, *params)
+    return _MoleculeNetFn.apply(net, plan, mp, es, _readout_p(net), data.x, *params)
 
 
 def loss_forward(model, data, p_drop: float, loss: str = "bce") -> Optional[torch.Tensor]:
@@ -590,4 +612,4 @@ def loss_forward(model, data, p_drop: float, loss: str = "bce") -> Optional[torc
         from .readout import update_running_stats
         update_running_stats(*es)
         es = None
-    return _MoleculeLossFn.apply(net, ffn, float(p_drop), data.y, plan, mp, es, kind, data.x, *params)
+    return _MoleculeLossFn.apply(net, ffn, float(p_drop), data.y, plan, mp, es, kind, _readout_p(net), data.x, *params)

@@ -740,7 +740,7 @@ class _TailFn(torch.autograd.Function):
     (``mkgnn_tail_fused``); the backward hands them out (scaled, if the incoming gradient is not the registered unit seed)."""
 
     @staticmethod
-    def forward(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind=_lib.LOSS_BCE_MEAN):
+    def forward(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind=_lib.LOSS_BCE_MEAN, p_readout=0.0):
         lib = _lib.load()
         _lib.require_gpu_tensor(sim, "sim_sc")
         n, K = sim.shape
@@ -758,8 +758,11 @@ class _TailFn(torch.autograd.Function):
         gb1 = torch.empty_like(b1) if b1 is not None else None
         gb2 = torch.empty_like(b2) if b2 is not None else None
         gbh = torch.empty(1, dtype=torch.float32, device=dev) if bh is not None else None
-        rng = head_rng_state(dev) if p_drop > 0.0 else None
-        used = torch.empty(2, dtype=torch.int64, device=dev) if p_drop > 0.0 else None
+        # (one generator state for the head's dropout and the readout's: read once, advanced by one -- mkgnn_readout_dropout_mask
+        # gives the readout's mask for the pair left in ctx.rng_used)
+        drop = p_drop > 0.0 or p_readout > 0.0
+        rng = head_rng_state(dev) if drop else None
+        used = torch.empty(2, dtype=torch.int64, device=dev) if drop else None
         a = _lib.TailArgs()
         a.sim, a.sim_stride = sim.data_ptr(), _stride0(sim)
         for i, L in enumerate(blocks):
@@ -788,13 +791,17 @@ class _TailFn(torch.autograd.Function):
         ctx.dev = dev
         with torch.cuda.device(dev):
             ws = _tail_workspace(dev, int(lib.mkgnn_tail_workspace_bytes(K, H, G, n, seg.size)))
-            _lib.check(lib.mkgnn_tail_fused(ctypes.byref(a), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_tail_fused")
+            if p_readout > 0.0:
+                _lib.check(lib.mkgnn_tail_fused_readout_dropout(ctypes.byref(a), float(p_readout), ws.data_ptr(), ws.numel(),
+                                                                _lib.stream_ptr(dev)), "mkgnn_tail_fused_readout_dropout")
+            else:
+                _lib.check(lib.mkgnn_tail_fused(ctypes.byref(a), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_tail_fused")
         if ctx.deferred:
             # (their STORAGES: a second reference to a gradient TENSOR would make autograd copy it into .grad instead of adopting
             # it -- a copy made before the reduction has written it)
             _TAIL_HELD.extend(t.untyped_storage() for t in (loss, gw1, gb1, gw2, gb2, gwh, gbh, rng, used, ws) if t is not None)
         ctx.unit = (gsim, gw1, gb1, gw2, gb2, gwh.reshape(wh.shape), gbh)
-        ctx.pred = pred
+        ctx.pred, ctx.rng_used = pred, used
         return loss
 
     @staticmethod
@@ -812,18 +819,44 @@ class _TailFn(torch.autograd.Function):
         if not _is_unit_seed(grad_loss):                     # d loss is not the registered 1: scale
             gl = grad_loss.reshape(()).float()
             grads = tuple(None if g is None else g * gl for g in grads)
-        return (*grads, None, None, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None, None, None)
 
 
 def tail_loss(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torch.nn.Linear, ffn: torch.nn.Linear,
               target: torch.Tensor, seg: "MoleculeSegments", dropout_p: float = 0.0, n_rows: Optional[int] = None,
-              loss: str = "bce") -> torch.Tensor:
+              loss: str = "bce", readout_dropout_p: float = 0.0) -> torch.Tensor:
     """``head_loss(readout_blocks(sim, ...), ffn, target, loss, dropout_p, n_rows)`` as ONE operator whose forward also takes
-    every gradient (``_TailFn``).  The caller has checked ``tail_supported``, ``_tail_limits_ok`` and that the readout has
-    no dropout of its own."""
+    every gradient (``_TailFn``).  ``readout_dropout_p``: the readout's own dropout (``MolKGNNNet``'s ``drop_ratio`` in training
+    mode), its mask drawn in the kernels from ``head_rng_state`` as ``readout_dropout_mask`` gives it.  The caller has checked
+    ``tail_supported`` and ``_tail_limits_ok``."""
     kind = loss_kind(loss)
     n_rows = seg.size if n_rows is None else int(n_rows)
     if ffn.out_features != 1 or n_rows <= 0 or n_rows > seg.size or target.numel() != n_rows:
         raise ValueError("tail_loss needs a one-output linear layer and one target per (leading) molecule")
+    if not 0.0 <= readout_dropout_p < 1.0:
+        raise ValueError(f"readout dropout probability {readout_dropout_p} outside [0, 1)")
     return _TailFn.apply(sim, lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight, ffn.bias, target, seg, plan,
-                         tuple(blocks), float(dropout_p), n_rows, kind)
+                         tuple(blocks), float(dropout_p), n_rows, kind, float(readout_dropout_p))
+
+
+def readout_dropout_mask(rng_pair: torch.Tensor, n_rows: int, H: int, p: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The keep multipliers ``[n_rows, H]`` (0, or 1 / (1 - p)) of the readout's dropout that the fused tail and the
+    molecule-resident step draw for the generator pair ``rng_pair`` (``{seed, offset}``, int64 on the device -- the ``rng_used``
+    of a call, or ``head_rng_state`` before it): row r is the batch's atom r (``mkgnn_readout_dropout_mask``).  Fed to
+    ``_ReadoutFn`` / ``_ReadoutBlocksFn`` as ``keep``, the separate operators apply the fused paths' mask."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"readout dropout probability {p} outside [0, 1)")
+    _lib.require_gpu_tensor(rng_pair, "rng_pair")
+    if rng_pair.dtype != torch.int64 or rng_pair.numel() != 2 or not rng_pair.is_contiguous():
+        raise ValueError("rng_pair: two contiguous int64 values {seed, offset}")
+    dev = rng_pair.device
+    if out is None:
+        out = torch.empty((int(n_rows), int(H)), dtype=torch.float32, device=dev)
+    if out.shape != (n_rows, H) or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != dev:
+        raise ValueError("out: [n_rows, H] float32 rows on the generator's device")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkgnn_readout_dropout_mask(rng_pair.data_ptr(), int(n_rows), int(H), float(p), out.data_ptr(),
+                                                  _stride0(out) if n_rows > 0 else int(H), _lib.stream_ptr(dev)),
+                   "mkgnn_readout_dropout_mask")
+    return out
