@@ -425,6 +425,21 @@ int mkgnn_readout_dropout_mask(const int64_t* rng_pair, int64_t n_rows, int32_t 
                                void* stream);
 /* Launches a reduction that a mkgnn_tail_fused call with defer_reduce left pending on this thread, on `stream` (no-op: none). */
 int mkgnn_tail_flush(void* stream);
+/* The tail in evaluation mode, forward only (additive; the ABI version stays 8): pred_g = ffn( emb_g ) and emb_g of the formulas
+ * above, no dropout, no loss, no gradient -- TWO launches: z = W1 sim on the matrix cores, then the forward phases of the training
+ * tail's middle kernel with its work distribution and every summation order.  For the same inputs pred and emb are BIT FOR BIT
+ * what mkgnn_tail_fused writes with dropout_p = 0, batches padded to a fixed shape included.
+ * Takes mkgnn_tail_args as it is and READS: sim, sim_stride, num_kernels, buckets, in_rowptr, in_col, mol_ptr, atom_mol (must not be
+ * NULL; the forward phases do not need its contents), n_atoms, n_mols, n_loss_mols (the leading molecules whose pred is
+ * written), readout, head_weight, head_bias (or NULL), emb + emb_stride ([n_mols, G], every row written; or NULL) and pred
+ * [n_loss_mols].  EVERYTHING ELSE IS IGNORED and may be NULL / 0: out_rowptr, out_col, target, dropout_p, rng_state, rng_used, loss,
+ * grad_*, defer_reduce, loss_kind -- nothing behind those pointers is read or written, and the generator does not advance.
+ * Limits: those of mkgnn_tail_fused; a molecule beyond MKGNN_TAIL_MAX_ATOMS / MKGNN_TAIL_MAX_EDGES gets NaN in its pred and its
+ * emb row, the others their values.  A reduction that a mkgnn_tail_fused call with defer_reduce left pending on this thread is
+ * launched first, on `stream` (as mkgnn_tail_fused does: the workspace may be the one it reads).
+ * workspace: mkgnn_tail_score_workspace_bytes (the z rows only; a mkgnn_tail_workspace_bytes buffer is large enough). */
+size_t mkgnn_tail_score_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols);
+int mkgnn_tail_score(const mkgnn_tail_args* args, void* workspace, size_t workspace_bytes, void* stream);
 
 /* BatchNorm1d over atom rows, reference MolKGNNNet.py:115 (torch.nn.BatchNorm1d semantics: biased
  * variance for the normalisation, unbiased for running_var, running <- running + momentum (batch - running)).

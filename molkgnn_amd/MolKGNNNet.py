@@ -77,7 +77,7 @@ class MolKGNNNet(torch.nn.Module):
         src = data.edge_index[0]
         return (ea, bn, src if src.is_contiguous() else src.contiguous(), nv)
 
-    def forward(self, *argv, save_score=False, _tail=None):
+    def forward(self, *argv, save_score=False, _tail=None, _score=None):
         if len(argv) != 1:
             # the reference's 33-positional-argument form reads ``data`` afterwards and cannot work
             # (MolKGNNNet.py:70-89 then :115); only the single-``data`` form is meaningful
@@ -144,8 +144,12 @@ class MolKGNNNet(torch.nn.Module):
             p_readout = self.dropout.p if (self.dropout is not None and self.dropout.training) else 0.0
             want_tail = (_tail is not None and R._FUSED_TAIL and torch.is_grad_enabled() and p_readout < 1.0 and x.is_cuda
                          and R.tail_supported(*dims, Ls))
+            # (private: train.GNNModel.predict asks for the predictions themselves -- the forward-only tail, readout.tail_score --
+            # with grad mode off and no readout dropout to draw, i.e. in evaluation mode)
+            want_score = (_score is not None and R._FUSED_TAIL and R._SCORE_TAIL and not torch.is_grad_enabled() and p_readout == 0.0
+                          and x.is_cuda and R.tail_supported(*dims, Ls))
             want = x.is_cuda and not save_score and (_PROJECT_FIRST == '1' or (_PROJECT_FIRST != '0' and (
-                x.shape[0] >= _PROJECT_FIRST_ATOMS or not R.readout_supported(*dims) or want_tail)))
+                x.shape[0] >= _PROJECT_FIRST_ATOMS or not R.readout_supported(*dims) or want_tail or want_score)))
             if want:
                 want = R.readout_blocks_supported(*dims, Ls)
             if want and seg is None:
@@ -166,6 +170,9 @@ class MolKGNNNet(torch.nn.Module):
                 loss = kind[0] if kind else "bce"
                 return ("loss", R.tail_loss(sim_sc, plan, Ls, lin1, lin2, ffn, target, seg, p_head, n_rows, loss,
                                             readout_dropout_p=p_readout))
+            if want_score and R._tail_limits_ok(seg, plan):      # ("score", pred, embedding), or the embedding as usual
+                ffn, n_rows = _score
+                return ("score", *R.tail_score(sim_sc, plan, Ls, lin1, lin2, ffn, seg, n_rows))
             return R.readout_blocks(sim_sc, plan, Ls, lin1, lin2, self.dropout, seg)
         # pool(lin2(dropout(act(lin1(h)))), batch) -- MolKGNNNet.py:144-146 -- as one operator
         return R.readout(node_representation, lin1, lin2, self.dropout, data.batch, getattr(data, 'num_graphs', None), segments=seg)

@@ -50,7 +50,7 @@ class ReadoutParams(C.Structure):
 
 
 class TailArgs(C.Structure):
-    """``mkgnn_tail_args`` (include/molkgnn_hip.h): the fused tail of a training step."""
+    """``mkgnn_tail_args`` (include/molkgnn_hip.h): the fused tail of a training step (and, forward only, ``mkgnn_tail_score``)."""
     _fields_ = [("sim", C.c_void_p), ("sim_stride", C.c_int64), ("num_kernels", C.c_int32 * 4), ("buckets", C.c_void_p),
                 ("in_rowptr", C.c_void_p), ("in_col", C.c_void_p), ("out_rowptr", C.c_void_p), ("out_col", C.c_void_p),
                 ("mol_ptr", C.c_void_p), ("atom_mol", C.c_void_p), ("n_atoms", C.c_int64), ("n_mols", C.c_int64),
@@ -147,7 +147,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_molecule_step", "mkgnn_batchnorm_stats_workspace_bytes", "mkgnn_batchnorm_update_stats",
            "mkgnn_batchnorm_forward_with_stats", "mkgnn_index_workspace_bytes", "mkgnn_index_build",
            "mkgnn_rows_split_supported", "mkgnn_rows_presplit", "mkgnn_tail_supported", "mkgnn_tail_workspace_bytes", "mkgnn_tail_fused", "mkgnn_tail_flush", "mkgnn_flat_copy",
-           "mkgnn_tail_fused_readout_dropout", "mkgnn_readout_dropout_mask",
+           "mkgnn_tail_fused_readout_dropout", "mkgnn_readout_dropout_mask", "mkgnn_tail_score", "mkgnn_tail_score_workspace_bytes",
            "mkgnn_head_loss_forward", "mkgnn_head_loss_backward", "mkgnn_head_loss_dropout_forward",
            "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused")
 
@@ -213,6 +213,10 @@ def load() -> C.CDLL:
     lib.mkgnn_tail_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
     lib.mkgnn_tail_fused.restype = C.c_int
     lib.mkgnn_tail_fused.argtypes = [C.POINTER(TailArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mkgnn_tail_score_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_tail_score_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
+    lib.mkgnn_tail_score.restype = C.c_int
+    lib.mkgnn_tail_score.argtypes = [C.POINTER(TailArgs), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mkgnn_tail_fused_readout_dropout.restype = C.c_int
     lib.mkgnn_tail_fused_readout_dropout.argtypes = [C.POINTER(TailArgs), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mkgnn_readout_dropout_mask.restype = C.c_int

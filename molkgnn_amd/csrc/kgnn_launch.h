@@ -208,6 +208,8 @@ int tail_group_size(int64_t n_loss_mols);
 int tail_middle_blocks(int64_t n_loss_mols);
 // loss_kind: MKGNN_LOSS_*; a.rdrop_p > 0: the instantiations with the readout's dropout mask
 hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st);
+// the forward-only form (mkgnn_tail_score): reads z, rin, cin, mol_ptr, the weights, H, G, n_mols, n_loss, mg; writes pred and emb
+hipError_t launch_tail_score(const TailMidArgs& a, int nb, hipStream_t st);
 
 struct BankStreamLaunch { BankStreamArgs a; int nb, prep_blocks, KC; size_t lds_bytes; int x_split; };
 // block split and arguments once; then the pre-pass (coefficient records in tile order, score-weight partials) and the

@@ -2325,6 +2325,59 @@ int mkgnn_tail_fused_readout_dropout(const mkgnn_tail_args* p, float readout_dro
     return tail_fused("mkgnn_tail_fused_readout_dropout", p, readout_dropout_p, ws, ws_bytes, stream);
 }
 
+// ---- the forward-only tail (evaluation mode): project | the middle's forward phases -- two launches, pred and emb only ----
+size_t mkgnn_tail_score_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols) {
+    ReadoutDims d;
+    if (!blocks_dims(K, H, G, d) || n_atoms < 1 || n_mols < 1) return 0;
+    return tail_ws(d, n_atoms, n_mols).dz;               // (the z rows: where the training tail's d z rows would begin)
+}
+
+int mkgnn_tail_score(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "mkgnn_tail_score";
+    if (!p) return api_fail("%s: null argument", who);
+    const mkgnn_readout_params* ro = &p->readout;
+    ReadoutDims d;
+    if (!mkgnn_tail_supported(ro->F, ro->H, ro->G, p->num_kernels) || !blocks_dims(ro->F, ro->H, ro->G, d))
+        return api_fail("%s: K=%d H=%d G=%d outside the fused tail (the block-row readout's shapes with H, G <= 32)", who, ro->F, ro->H, ro->G);
+    if (p->n_atoms < 1 || p->n_mols < 1 || p->n_loss_mols < 1 || p->n_loss_mols > p->n_mols || p->n_atoms >= (int64_t)1 << 31)
+        return api_fail("%s: bad sizes", who);
+    if (!p->in_rowptr || !p->in_col || !p->mol_ptr || !p->atom_mol || !ro->lin1_weight || !ro->lin2_weight || !p->head_weight || !p->pred)
+        return api_fail("%s: null pointer", who);
+    if (p->emb && p->emb_stride < ro->G) return api_fail("%s: bad emb stride", who);
+    BlockProjArgs b{};
+    int64_t n_focal = 0;
+    if (int rc = check_blocks(who, ro, p->num_kernels, p->buckets, p->n_atoms, p->sim_stride, p->sim, b, d, &n_focal)) return rc;
+    const size_t need = tail_ws(d, p->n_atoms, p->n_mols).dz;
+    if (!ws || ws_bytes < need) return api_fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    float* const z = (float*)ws;
+    // (a reduction a training call left pending: first, as mkgnn_tail_fused does -- the workspace may be the one it still reads)
+    hipError_t e = launch_pending_tail_reduce(st);
+    if (e != hipSuccess) return api_hip_fail(who, e);
+    // (1) z = W1[:, block] sim[block], exactly as mkgnn_tail_fused launches it
+    b.sim = p->sim; b.ss = p->sim_stride; b.n = p->n_atoms; b.z = z;
+    if (n_focal < p->n_atoms) {
+        e = hipMemsetAsync(z, 0, (size_t)p->n_atoms * d.HP * 4, st);
+        if (e != hipSuccess) return api_hip_fail(who, e);
+    }
+    int64_t grid = 0;
+    for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) if (b.L[i] > 0) grid += ((b.cnt[i] + 15) / 16 + 3) / 4;
+    if (grid > 0) {
+        const size_t lds = ((size_t)d.HP * 68 + 4 * 16 * (d.HP + 4)) * 4;
+        block_project_mfma_kernel<2><<<(unsigned)grid, 256, lds, st>>>(b);
+    }
+    // (2) propagate, swish, pool, lin2, head: the training middle's forward phases, its groups and its grid
+    TailMidArgs m{};
+    m.z = z; m.rin = p->in_rowptr; m.cin = p->in_col; m.mol_ptr = p->mol_ptr; m.atom_mol = p->atom_mol;
+    m.n_atoms = p->n_atoms; m.n_mols = p->n_mols; m.n_loss = p->n_loss_mols;
+    m.b1 = ro->lin1_bias; m.w2 = ro->lin2_weight; m.b2 = ro->lin2_bias; m.wh = p->head_weight; m.bh = p->head_bias;
+    m.H = ro->H; m.G = ro->G;
+    m.emb = p->emb; m.es = p->emb_stride; m.pred = p->pred;
+    m.mg = tail_group_size(p->n_loss_mols);
+    e = launch_tail_score(m, tail_middle_blocks(p->n_loss_mols), st);      // (hipGetLastError: both launches)
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
 // keep[r][h] of the readout's dropout: what the fused tail and the molecule-resident step draw for batch atom r (kgnn_philox.h)
 struct ReadoutMaskArgs { const int64_t* rng; int64_t n; int H; float p; float* keep; int64_t ks; };
 __global__ void __launch_bounds__(256) readout_dropout_mask_kernel(ReadoutMaskArgs a) {

@@ -111,28 +111,38 @@ __device__ unsigned long long* g_tail_stamps = nullptr;
 
 constexpr int LDS_FLOATS = 32 * WP + 2 * AC * HP + 3 * MC * HP + 96;
 constexpr int LDS_INTS = AC + 2 * (AC + 1) + 2 * EC + 3 * (MC + 1) + 4;
+// ... of the forward-only form: no pre / d pre rows, no per-molecule gradient rows, nothing by source (26 236 bytes against 52 468)
+constexpr int LDS_FLOATS_FWD = 32 * WP + AC * HP + 96;
+constexpr int LDS_INTS_FWD = AC + (AC + 1) + EC + 2 * (MC + 1) + 4;
 
 // LK: the loss kind (MKGNN_LOSS_*), a template parameter so that the BCE instantiation's code stays as it was; RD: the readout's
-// dropout (a.rdrop_p), one too, so that the instantiations without it stay as they were
-template <int LK, bool RD>
+// dropout (a.rdrop_p), one too, so that the instantiations without it stay as they were.
+// FWD: the forward-only form (mkgnn_tail_score; evaluation mode, so no dropout) -- the window, P1 without the out-edges, P3 and
+// the forward half of P4, in the training form's own statements: pred and emb come out bit for bit as the training form
+// writes them at dropout 0.  It reads no target, no generator state and nothing by source (a molecule has as many edges by
+// source as by target -- its edges lie inside it -- so the window cuts the same chunks without them), keeps neither pre nor any
+// gradient row or accumulator, and writes no slab and no d z.  The grid stays tail_middle_blocks': at most three workgroups per
+// CU exist, so the halved LDS cannot become occupancy and the bound stays 3 waves per SIMD.
+template <int LK, bool RD, bool FWD = false>
 __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
-    __shared__ __align__(16) float lds[LDS_FLOATS + LDS_INTS];
+    static_assert(!FWD || (LK == MKGNN_LOSS_BCE_MEAN && !RD), "the forward-only form has no loss and no dropout");
+    __shared__ __align__(16) float lds[FWD ? LDS_FLOATS_FWD + LDS_INTS_FWD : LDS_FLOATS + LDS_INTS];
     float* const W2s = lds;                              // [32][HP]
     float* const zp = W2s + 32 * WP;                     // [AC][HP]: pre, later d pre   (32 * 33 floats = 4 224 bytes: 16-byte aligned)
-    float* const dzb = zp + AC * HP;                     // [AC][HP]: z, then swish(pre), then d z
-    float* const emol = dzb + AC * HP;                   // [MC][HP]: d e_g
+    float* const dzb = FWD ? zp : zp + AC * HP;          // [AC][HP]: z, then swish(pre), then d z   (FWD: there is no zp)
+    float* const emol = dzb + AC * HP;                   // [MC][HP]: d e_g                          (FWD: none of the three)
     float* const emol_e = emol + MC * HP;                // [MC][HP]: e_g
     float* const emol_d = emol_e + MC * HP;              // [MC][HP]: d emb_g
-    float* const vec = emol_d + MC * HP;                 // b1 | b2 | wh
+    float* const vec = FWD ? emol : emol_d + MC * HP;    // b1 | b2 | wh
     int* const amol = (int*)(vec + 96);                  // [AC] molecule of the chunk
     int* const rpin = amol + AC;                         // [AC + 1] local edge offsets, by target
-    int* const rpout = rpin + AC + 1;                    // [AC + 1] by source
-    int* const ecin = rpout + AC + 1;                    // [EC] local source of every in-edge (-1: outside the chunk)
-    int* const ecout = ecin + EC;                        // [EC]
-    int* const mptr = ecout + EC;                        // [MC + 1] first atom of every molecule of the window
+    int* const rpout = rpin + AC + 1;                    // [AC + 1] by source                       (FWD: none)
+    int* const ecin = FWD ? rpout : rpout + AC + 1;      // [EC] local source of every in-edge (-1: outside the chunk)
+    int* const ecout = ecin + EC;                        // [EC]                                     (FWD: none)
+    int* const mptr = FWD ? ecout : ecout + EC;          // [MC + 1] first atom of every molecule of the window
     int* const mein = mptr + MC + 1;                     // [MC + 1] first in-edge
-    int* const meout = mein + MC + 1;                    // [MC + 1] first out-edge
-    int* const ctl = meout + MC + 1;                     // [0] molecules of this chunk
+    int* const meout = mein + MC + 1;                    // [MC + 1] first out-edge                  (FWD: none)
+    int* const ctl = FWD ? meout : meout + MC + 1;       // [0] molecules of this chunk
     const int t = threadIdx.x, j = t & 31, slot = t >> 5;      // the per-molecule phase: (row slot of 8, hidden unit)
     const int l = t & 7, as = t >> 3;                          // the per-atom phases: (atom slot of 32, 16-byte lane of 8)
     const int H = a.H, G = a.G;
@@ -151,7 +161,7 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
         if (t < 96 && vp && k < lim) vr = vp[k];         // (three short segments: one load each, no chain)
     }
     const float bh = a.bh ? a.bh[0] : 0.f;
-    const bool drop = a.drop_p > 0.f;
+    const bool drop = !FWD && a.drop_p > 0.f;
     const uint64_t seed = (drop || RD) ? (uint64_t)a.rng[0] : 0, offset = (drop || RD) ? (uint64_t)a.rng[1] : 0;
     const float invB = 1.f / (float)a.n_loss;
     for (int i = t; i < 32 * WP; i += NT) W2s[i] = 0.f;
@@ -192,13 +202,14 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
             const int at = a.mol_ptr[m];
             mptr[t] = at;
             mein[t] = a.rin[at];
-            meout[t] = a.rout[at];
+            if constexpr (!FWD) meout[t] = a.rout[at];
         }
         __syncthreads();
         if (t == 0) {
             int nm = 0;
             const int lim = (int)(m_hi - m0 < MC ? m_hi - m0 : MC);
-            while (nm < lim && mptr[nm + 1] - mptr[0] <= AC && mein[nm + 1] - mein[0] <= EC && meout[nm + 1] - meout[0] <= EC) ++nm;
+            if constexpr (FWD) while (nm < lim && mptr[nm + 1] - mptr[0] <= AC && mein[nm + 1] - mein[0] <= EC) ++nm;
+            else while (nm < lim && mptr[nm + 1] - mptr[0] <= AC && mein[nm + 1] - mein[0] <= EC && meout[nm + 1] - meout[0] <= EC) ++nm;
             ctl[0] = nm;
         }
         __syncthreads();
@@ -206,21 +217,28 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
         const int nm = ctl[0];
         if (nm == 0) {                                   // (block-uniform) one molecule beyond a chunk: skipped, reported as NaN.
             // Its atoms still get a d z row (zero): the projection kernel behind this one reads every row.
-            const int a0 = mptr[0], A = mptr[1] - a0;
-            for (int i = t; i < A * 32; i += NT) a.dz[(int64_t)a0 * 32 + i] = 0.f;
-            if (t == 0) acc_loss = __builtin_nanf("");
+            if constexpr (FWD) {                         // (forward only: NaN in its prediction and its embedding row)
+                if (t == 0 && m0 < a.n_loss) a.pred[m0] = __builtin_nanf("");
+                if (a.emb && t < G) a.emb[m0 * a.es + t] = __builtin_nanf("");
+            } else {
+                const int a0 = mptr[0], A = mptr[1] - a0;
+                for (int i = t; i < A * 32; i += NT) a.dz[(int64_t)a0 * 32 + i] = 0.f;
+                if (t == 0) acc_loss = __builtin_nanf("");
+            }
             m_next = m0 + 1;
             __syncthreads();
             continue;
         }
         m_next = m0 + nm;
         const int a0 = mptr[0], A = mptr[nm] - a0;
-        const int ein0 = mein[0], nin = mein[nm] - ein0, eout0 = meout[0], nout = meout[nm] - eout0;
+        const int ein0 = mein[0], nin = mein[nm] - ein0, eout0 = FWD ? 0 : meout[0], nout = FWD ? 0 : meout[nm] - eout0;
         // (A == 0: a chunk of empty molecules only -- the padding of a batch with fewer padding atoms than padding molecules,
         // molkgnn_amd.padding -- whose a0 may be one past the last atom and ein0 / eout0 one past the last edge.  No load below
         // leaves the arrays then: the per-atom phases find no atom, the per-molecule one gives the molecules their rows)
         // ---- P1: per atom -- molecule, edge offsets; the z rows (one coalesced 128-byte row per slot and pass)
-        if (t <= A) {
+        if constexpr (FWD) {                             // (no gradient to hand back to an atom's molecule: offsets by target only)
+            if (t <= A) rpin[t] = a.rin[a0 + t] - ein0;
+        } else if (t <= A) {
             const int n = A > 0 ? a0 + (t < A ? t : A - 1) : 0;
             const int mol = a.atom_mol[n] - (int)m0;
             const int ri = a.rin[a0 + t] - ein0, ro = a.rout[a0 + t] - eout0;      // (t == A: the end of the last atom's edges)
@@ -241,13 +259,13 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
             for (int u = 0; u < EC / NT; ++u) {          // (no edge one way: nothing to read -- ein0 may be the end of cin)
                 const int i = t + NT * u;
                 ci[u] = a.cin[nin > 0 ? ein0 + (i < nin ? i : 0) : 0];
-                co[u] = a.cout[nout > 0 ? eout0 + (i < nout ? i : 0) : 0];
+                if constexpr (!FWD) co[u] = a.cout[nout > 0 ? eout0 + (i < nout ? i : 0) : 0];
             }
 #pragma unroll
             for (int u = 0; u < EC / NT; ++u) {
                 const int i = t + NT * u;
                 if (i < nin) { const int s = ci[u] - a0; ecin[i] = (s >= 0 && s < A) ? s : -1; }
-                if (i < nout) { const int s = co[u] - a0; ecout[i] = (s >= 0 && s < A) ? s : -1; }
+                if constexpr (!FWD) if (i < nout) { const int s = co[u] - a0; ecout[i] = (s >= 0 && s < A) ? s : -1; }
             }
         }
         __syncthreads();
@@ -271,7 +289,7 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
                 const f32x4 pv = b1v + p[u];
                 sw[u] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (at < A) {
-                    *(f32x4*)(zp + at * HP + 4 * l) = pv;
+                    if constexpr (!FWD) *(f32x4*)(zp + at * HP + 4 * l) = pv;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) sw[u][c] = pv[c] * sigmoidf_(pv[c]);
                     if constexpr (RD) {
@@ -314,6 +332,10 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
             const float ks = (drop && j < G) ? keep_scale_of(seed, offset, (uint64_t)(counted ? gi : 0) * G + j, a.drop_p) : 1.f;
             const float wv = vec[64 + j];
             const float x = half_sum(j < G ? emb * ks * wv : 0.f) + bh;
+            if constexpr (FWD) {                         // the prediction, and that is all
+                if (counted && j == 0) a.pred[gi] = x;
+                continue;
+            }
             float d = 0.f;
             if (counted) {
                 const float yv = a.y[gi];
@@ -343,6 +365,11 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
             emol[g * HP + j] = de;
             emol_e[g * HP + j] = e;
             emol_d[g * HP + j] = demb;
+        }
+        if constexpr (FWD) {                             // (the next chunk may overwrite the images once everybody has read them:
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      //  as behind P6 below, not a wait for the stores)
+            TAIL_PHASE(4);
+            continue;
         }
         __syncthreads();
         TAIL_PHASE(4);                                   // P4
@@ -397,6 +424,11 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
     }
     __syncthreads();
     TAIL_PHASE(7);
+    if constexpr (FWD) {                                 // (no gradients, no loss: no slab)
+        if (stamps && t == 0)
+            for (int i = 0; i < 12; ++i) stamps[(size_t)blockIdx.x * 16 + i] = ph[i];
+        return;
+    }
 
     // ---- the workgroup's slab: everything summed over the eight row slots in slot order
     float* const so = a.slab + (size_t)blockIdx.x * a.slab_stride;
@@ -464,6 +496,12 @@ static hipError_t launch_tail_middle_rd(const TailMidArgs& a, int nb, int loss_k
     case MKGNN_LOSS_SQERR_SUM: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_SUM, RD><<<nb, tail::NT, 0, st>>>(a); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_tail_score(const TailMidArgs& a, int nb, hipStream_t st) {
+    if (a.mg < tail::MG_MIN || a.mg > tail::MG_MAX || a.mg > tail::MC) return hipErrorInvalidValue;
+    tail::tail_middle_kernel<MKGNN_LOSS_BCE_MEAN, false, true><<<nb, tail::NT, 0, st>>>(a);
     return hipGetLastError();
 }
 

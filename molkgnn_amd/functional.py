@@ -7,6 +7,7 @@ device memory.  There is no CPU or eager-PyTorch fallback.
 """
 from __future__ import annotations
 
+import threading
 from typing import List, Optional, Sequence, Tuple
 
 import os
@@ -467,13 +468,19 @@ class deferred_bank_gradients:
         return False
 
 
+# Grad mode where ``kernelsetconv`` was CALLED (inside ``Function.forward`` it is always off, and ``ctx.needs_input_grad`` is
+# True for a parameter that requires a gradient even under ``torch.no_grad()``): with it off no backward can follow, so the
+# kernels write no pair records and the bank workspace is not kept -- evaluation (``GNNModel.predict``) pays for neither
+_CALL = threading.local()
+
+
 class _KernelSetConvFn(torch.autograd.Function):
     """BaseKernelSetConv.forward (reference kernels.py:610-751) as one differentiable operator."""
 
     @staticmethod
     def forward(ctx, x, plan: BatchPlan, is_last_layer: bool, variant: int, out_pad: int, E: int, inv, bwd_variant: int,
                 propagate, prepared, *params):
-        need_grad = any(ctx.needs_input_grad)
+        need_grad = any(ctx.needs_input_grad) and getattr(_CALL, "grad_enabled", True)
         ctx.bwd_variant = int(bwd_variant)
         x, out_full, inv, saved_t, Ls, ws, x_split = _forward_impl(x, plan, is_last_layer, variant, out_pad, E, params, need_grad,
                                                                    inv, prepared)
@@ -617,6 +624,7 @@ def kernelsetconv(x: torch.Tensor, plan: BatchPlan, is_last_layer: bool, params:
         raise ValueError("block_rows needs the default padded storage")
     if backward_variant is None:
         backward_variant = "generic" if variant == "generic" else "auto"
+    _CALL.grad_enabled = torch.is_grad_enabled()          # (read by _KernelSetConvFn.forward, which runs inside the apply below)
     if propagate:
         if not block_rows:
             raise ValueError("propagate=True continues on block rows: block_rows=True is required")

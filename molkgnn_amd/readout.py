@@ -14,7 +14,7 @@ from __future__ import annotations
 import ctypes
 
 import weakref
-from typing import Optional
+from typing import Optional, Tuple
 
 import os
 
@@ -837,6 +837,55 @@ def tail_loss(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torc
         raise ValueError(f"readout dropout probability {readout_dropout_p} outside [0, 1)")
     return _TailFn.apply(sim, lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight, ffn.bias, target, seg, plan,
                          tuple(blocks), float(dropout_p), n_rows, kind, float(readout_dropout_p))
+
+
+# MKGNN_SCORE_TAIL=0: GNNModel.predict runs the separate operators (readout_blocks, dropout, head) as before it existed (A/B)
+_SCORE_TAIL = os.environ.get("MKGNN_SCORE_TAIL", "1") != "0"
+
+
+def tail_score(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torch.nn.Linear, ffn: torch.nn.Linear,
+               seg: "MoleculeSegments", n_rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(pred [n_rows], emb [seg.size, G])``: ``ffn(readout_blocks(sim, ...))`` in evaluation mode as two launches
+    (``mkgnn_tail_score``) -- no dropout, no loss, no gradient, and bit for bit the ``pred`` / ``emb`` of the training tail
+    (``tail_loss``) at dropout 0.  ``n_rows``: the leading molecules whose prediction is wanted (a padded batch's real ones).
+    It has no autograd node: called where a gradient is being recorded for one of its inputs it raises instead of dropping
+    it (``tail_loss`` is the differentiable operator).  The caller has checked ``tail_supported`` and ``_tail_limits_ok``."""
+    params = (lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight, ffn.bias)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (sim, *params)):
+        raise RuntimeError("tail_score is forward only: call it under torch.no_grad() (or on detached inputs); "
+                           "tail_loss is the operator with gradients")
+    lib = _lib.load()
+    _lib.require_gpu_tensor(sim, "sim_sc")
+    n_rows = seg.size if n_rows is None else int(n_rows)
+    if ffn.out_features != 1 or n_rows <= 0 or n_rows > seg.size:
+        raise ValueError("tail_score needs a one-output linear layer and 1 <= n_rows <= the batch's molecules")
+    n, K = sim.shape
+    dev = sim.device
+    w1, b1, w2, b2, wh, bh = (None if t is None else t.detach() for t in params)
+    w1c, w2c, whc = w1.contiguous(), w2.contiguous(), wh.reshape(-1).contiguous()
+    H, G = w1c.shape[0], w2c.shape[0]
+    pred = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    emb = torch.empty((seg.size, G), dtype=torch.float32, device=dev)
+    a = _lib.TailArgs()                                  # (everything not set here stays NULL / 0: the call ignores it)
+    a.sim, a.sim_stride = sim.data_ptr(), _stride0(sim)
+    for i, L in enumerate(blocks):
+        a.num_kernels[i] = int(L)
+    bk = _sel_buckets(plan)
+    a.buckets = ctypes.cast(bk, ctypes.c_void_p)
+    rin, cin = plan.csr_in
+    a.in_rowptr, a.in_col = rin.data_ptr(), cin.data_ptr()
+    a.mol_ptr, a.atom_mol = seg.mol_ptr.data_ptr(), seg.atom_mol.data_ptr()
+    a.n_atoms, a.n_mols, a.n_loss_mols = n, seg.size, n_rows
+    a.readout = _params(w1c, b1, w2c, b2)
+    a.head_weight, a.head_bias = whc.data_ptr(), _lib.ptr(bh)
+    a.emb, a.emb_stride = emb.data_ptr(), G
+    a.pred = pred.data_ptr()
+    with torch.cuda.device(dev):
+        # (the training tail's scratch: its first bytes are the z rows there too, and a reduction still pending on its slabs
+        # is launched by the call before anything is overwritten)
+        ws = _tail_workspace(dev, int(lib.mkgnn_tail_score_workspace_bytes(K, H, G, n, seg.size)))
+        _lib.check(lib.mkgnn_tail_score(ctypes.byref(a), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_tail_score")
+    return pred, emb
 
 
 def readout_dropout_mask(rng_pair: torch.Tensor, n_rows: int, H: int, p: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:

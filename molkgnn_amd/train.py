@@ -5,7 +5,8 @@ Only what a forward + backward (+ optimiser) step needs is restated here: the mo
 reference's parameter names (``gnn_model.*``, ``lin1``, ``lin2``, ``ffn``; 132 300 parameters), the
 loss the data module selects -- ``BCEWithLogitsLoss()`` for the QSAR assays (``data.py:37``), ``MSELoss(reduction='sum')``
 for the docking-score set (``data.py:49-53``) -- and the AdamW groups chosen by parameter name (``model.py:373-382``).
-Logging, checkpoints, metrics and the LR schedule are out of scope.
+Scoring: ``GNNModel.predict`` and ``evaluate`` (the reference's validation / test loop, ``model.py:221-358, 483-522``).
+Logging, checkpoints, file output and the LR schedule are out of scope.
 """
 from __future__ import annotations
 
@@ -37,7 +38,9 @@ class GNNModel(torch.nn.Module):
         self.loss_func = BCEWithLogitsLoss() if loss_func is None else loss_func     # model.py:156: the data module's loss
 
     def forward(self, data):
-        graph_embedding = self.dropout(self.gnn_model(data))
+        return self._head(self.dropout(self.gnn_model(data)))
+
+    def _head(self, graph_embedding):
         if self.ffn.out_features == 1 and self.ffn.bias is not None and graph_embedding.dim() == 2:
             # ffn(graph_embedding) for a single task as multiply + row sum: the [1 x B] @ [B x H] weight gradient of
             # the GEMM form runs a 25 us rocBLAS kernel at B = 4096 (the gemv form 29 us), this takes a few
@@ -45,6 +48,27 @@ class GNNModel(torch.nn.Module):
         else:
             pred = self.ffn(graph_embedding)
         return pred, graph_embedding
+
+    def predict(self, data):
+        """``(pred [n, 1], graph_embedding [n, G])`` of a model in evaluation mode, under ``torch.no_grad()``: what the reference's
+        ``validation_step`` / ``test_step`` take from ``self(batch)`` (``model.py:221-232, 299-305``).  ``n``: the batch's real
+        molecules, as ``loss`` counts them (``n_valid_molecules`` of a batch padded to a fixed shape).  Where the model and the batch
+        qualify (one task, CUDA, the fused tail's shapes and molecule sizes) everything behind the last convolution is the
+        forward-only tail -- two launches, ``readout.tail_score``; ``MKGNN_SCORE_TAIL=0`` or ``MKGNN_FUSED_TAIL=0``: never --
+        and the separate operators of ``self(data)`` otherwise.  The mode is the caller's: in training mode this raises."""
+        if self.training:
+            raise ValueError("GNNModel.predict needs evaluation mode: call model.eval() first (train.evaluate does)")
+        with torch.no_grad():
+            nreal = getattr(data, 'n_valid_molecules', None)
+            score = (self.ffn, nreal) if (self.ffn.out_features == 1 and data.x.is_cuda) else None
+            out = self.gnn_model(data, _score=score)
+            if isinstance(out, tuple):
+                _, pred, graph_embedding = out
+                pred = pred.view(-1, 1)
+            else:                                        # (the embedding: the head of forward(); its dropout is the identity here)
+                pred, graph_embedding = self._head(self.dropout(out))
+            n = pred.shape[0] if nreal is None else int(nreal)
+            return pred[:n], graph_embedding[:n]
 
     def _loss_kind(self) -> Optional[str]:
         """The loss as a kind of the HIP head (``readout.LOSS_KINDS``), or None: any other loss takes the PyTorch route."""
@@ -130,6 +154,59 @@ def training_step(model, batch, optimizer=None) -> torch.Tensor:
     if optimizer is not None:
         optimizer.step()
     return loss
+
+
+def _metric_functions() -> dict:
+    """The metric names of the reference's ``get_evaluations`` (``model.py:499-522``) -> ``f(true_y, pred_y)`` of
+    ``molkgnn_amd.evaluation``."""
+    from . import evaluation as E
+    return {
+        'accuracy': E.calculate_accuracy,
+        'RMSE': E.calculate_rmse,
+        'logAUC_0.001_0.1': E.calculate_logAUC,
+        'logAUC_0.001_1': lambda true_y, pred_y: E.calculate_logAUC(true_y, pred_y, FPR_range=(0.001, 1)),
+        'ppv': E.calculate_ppv,
+        'f1_score': E.calculate_f1_score,
+        'AUC': E.calculate_auc,
+    }
+
+
+def evaluate(model, batches, metrics=()) -> dict:
+    """The reference's validation / test loop without Lightning: ``validation_step`` per batch (``model.py:221-244``:
+    ``pred_y = self(batch)[0].view(-1)``, ``true_y = batch.y.view(-1)``), then ``validation_epoch_end`` + ``get_evaluations``
+    (``model.py:246-296, 483-522``) on the concatenated vectors: ``loss = model.loss_func(all_pred, all_true.float())`` and
+    every metric named in ``metrics`` (``accuracy``, ``RMSE``, ``logAUC_0.001_0.1``, ``logAUC_0.001_1``, ``ppv``, ``f1_score``,
+    ``AUC``; any other name raises ``ValueError`` before a batch is run) through ``molkgnn_amd.evaluation``.  The result also
+    holds ``pred_y`` and ``true_y``, the two vectors ``record_valid_pred`` writes out.
+
+    The model is put in evaluation mode and handed back in the mode it came in, also when a batch raises.  Predictions come
+    from ``model.predict``; they and the labels (the first ``len(pred)`` of a batch's ``y``: a padded batch's real molecules)
+    stay on their device, and nothing synchronises with the host before the last batch is launched.  Writing files and
+    logging are the caller's."""
+    table = _metric_functions()
+    unknown = [m for m in metrics if m not in table]
+    if unknown:
+        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(table)}")
+    was_training = model.training
+    model.eval()
+    try:
+        all_pred, all_true = [], []
+        for batch in batches:
+            pred, _ = model.predict(batch)
+            pred = pred.view(-1)
+            all_pred.append(pred)
+            all_true.append(batch.y.view(-1)[:pred.shape[0]])
+        if not all_pred:
+            raise ValueError("evaluate needs at least one batch")
+        pred_y, true_y = torch.cat(all_pred), torch.cat(all_true)
+        with torch.no_grad():
+            results = {'loss': model.loss_func(pred_y, true_y.float())}
+        for m in metrics:
+            results[m] = table[m](true_y, pred_y)
+        results['pred_y'], results['true_y'] = pred_y, true_y
+        return results
+    finally:
+        model.train(was_training)
 
 
 def tune_torch_backends() -> None:
