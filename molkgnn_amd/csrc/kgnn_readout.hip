@@ -781,6 +781,7 @@ struct BnArgs {
     float* out; int64_t os;
     float *save_mean, *save_invstd;
     float* part1; float* part2;    // [nblk, C] each
+    float* part3;                  // forward statistics: the blocks' residual sums about their own (rounded) means
     // backward
     const float* gout; int64_t gos;
     float* gx; int64_t gxs;
@@ -863,7 +864,7 @@ __device__ __forceinline__ void bn_share(int64_t nv, int nblk, int b, int64_t& l
     if (lo > hi) lo = hi;
 }
 
-// One pass over rows [lo, hi) of x (and g): per-thread partial sums.  MODE 0: s0 += x;  1: s0 += (x - mu)^2;  2: s0 += g,
+// One pass over rows [lo, hi) of x (and g): per-thread partial sums.  MODE 0: s0 += x;  1: s0 += (x - mu)^2, s1 += x - mu;  2: s0 += g,
 // s1 += g (x - mu) is.  VEC: thread = (row lane rsub of RS, column group col .. col + 3), float4 loads; else one column c.
 // All loads of a trip are issued before anything is consumed (clamped addresses, masked use).
 template <int MODE, int U>
@@ -883,7 +884,7 @@ __device__ __forceinline__ void bn_pass_vec(const float* x, int64_t xs, const fl
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     if (MODE == 0) s0[e] += v[u][e];
-                    if (MODE == 1) { const float d = v[u][e] - mu[e]; s0[e] = fmaf(d, d, s0[e]); }
+                    if (MODE == 1) { const float d = v[u][e] - mu[e]; s0[e] = fmaf(d, d, s0[e]); s1[e] += d; }
                     if (MODE == 2) { s0[e] += gg[u][e]; s1[e] = fmaf(gg[u][e], (v[u][e] - mu[e]) * is[e], s1[e]); }
                 }
             }
@@ -905,7 +906,7 @@ __device__ __forceinline__ void bn_pass_col(const float* x, int64_t xs, const fl
         for (int u = 0; u < 8; ++u) {
             if (r0 + u * RS < hi) {
                 if (MODE == 0) s0 += v[u];
-                if (MODE == 1) { const float d = v[u] - mu; s0 = fmaf(d, d, s0); }
+                if (MODE == 1) { const float d = v[u] - mu; s0 = fmaf(d, d, s0); s1 += d; }
                 if (MODE == 2) { s0 += gg[u]; s1 = fmaf(gg[u], (v[u] - mu) * is, s1); }
             }
         }
@@ -916,7 +917,9 @@ __device__ __forceinline__ void bn_pass_col(const float* x, int64_t xs, const fl
 static inline bool bn_vec_rows(const void* p, int64_t stride, int C) { return p && C % 4 == 0 && stride % 4 == 0 && ((uintptr_t)p & 15) == 0; }
 
 // Forward statistics of block blockIdx.x: part1[b][c] = column sums of its counted rows, part2[b][c] = squares about the
-// block's own column means.  sh: 1024 floats.
+// block's own column means, part3[b][c] = the sum of the same centred values.  The block's mean is an fp32 number: for a column
+// with |mean| >> std (1e3 against 1e-1) it is off the true block mean by up to half an ulp of the MEAN, and that sum -- zero for the
+// true mean -- is what the merge needs to stay exact about the pivot actually used (bn_total_m2).  sh: 1024 floats.
 template <bool VEC>
 __device__ __forceinline__ void bn_block_stats(const BnArgs& a, int CL, float* sh) {
     __shared__ float bmean[256];
@@ -930,6 +933,7 @@ __device__ __forceinline__ void bn_block_stats(const BnArgs& a, int CL, float* s
     const float cnt = (float)(hi - lo);
     float* const p1 = a.part1 + (int64_t)blockIdx.x * a.C;
     float* const p2 = a.part2 + (int64_t)blockIdx.x * a.C;
+    float* const p3 = a.part3 + (int64_t)blockIdx.x * a.C;
     if constexpr (VEC) {
         const int LW = CL >= 4 ? CL / 4 : 1, g = t % LW, rsub = t / LW, RS = 256 / LW, col = 4 * g;
         const bool act = col < a.C;
@@ -947,9 +951,10 @@ __device__ __forceinline__ void bn_block_stats(const BnArgs& a, int CL, float* s
         s0 = z;
         bn_pass_vec<1, BN_U>(a.x, a.xs, nullptr, 0, lo, hi, rsub, RS, cb, mu, z, s0, s1);
         const f32x4 m2 = bn_reduce_rows(s0, LW, (f32x4*)sh);
+        const f32x4 m1 = bn_reduce_rows(s1, LW, (f32x4*)sh);
         if (t < LW && act) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) p2[col + e] = m2[e];
+            for (int e = 0; e < 4; ++e) { p2[col + e] = m2[e]; p3[col + e] = m1[e]; }
         }
     } else {
         const int c = t & (CL - 1), rsub = t / CL, RS = 256 / CL;
@@ -964,7 +969,8 @@ __device__ __forceinline__ void bn_block_stats(const BnArgs& a, int CL, float* s
         s0 = 0.f;
         bn_pass_col<1>(a.x, a.xs, nullptr, 0, lo, hi, rsub, RS, cc, mu, 0.f, s0, s1);
         const float m2 = bn_reduce_rows(s0, CL, sh);
-        if (t < CL && act) p2[c] = m2;
+        const float m1 = bn_reduce_rows(s1, CL, sh);
+        if (t < CL && act) { p2[c] = m2; p3[c] = m1; }
     }
 }
 
@@ -998,19 +1004,23 @@ __device__ __forceinline__ void bn_total_of(int nblk, int C, int CL, float* sh, 
 __device__ __forceinline__ void bn_total(const float* part, int nblk, int C, int CL, float* sh, float* sh_out) {
     bn_total_of(nblk, C, CL, sh, sh_out, [&](int b, int c) { return part[(int64_t)b * C + c]; });
 }
-// squares about the BATCH mean (mean[c]) out of the blocks' (count, sum, squares about their own means)
-__device__ __forceinline__ void bn_total_m2(const float* part1, const float* part2, int nblk, int64_t nv, int C, int CL, const float* mean,
-                                            float* sh, float* sh_out) {
+// squares about the BATCH mean (mean[c]) out of the blocks' (count, sum, squares and sum about their own means).  With m_b the
+// pivot block b used -- the fp32 quotient sum_b / count_b, formed here by the same division -- r_b = sum (x - m_b) and d = m_b - mean:
+//     sum (x - mean)^2 = sum (x - m_b)^2 + 2 d r_b + count_b d^2 = M2_b + d (2 r_b + count_b d)
+// exactly, whatever m_b is.  Without the r_b term (until this change) the rounding of m_b entered as 2 d r_b: 2e-5 of invstd for
+// a column of 1e3 +- 1e-1 in shares of two rows, ten times what the bound of tests/test_batch_norm_f64.py allows.
+__device__ __forceinline__ void bn_total_m2(const float* part1, const float* part2, const float* part3, int nblk, int64_t nv, int C, int CL,
+                                            const float* mean, float* sh, float* sh_out) {
     const int64_t per = (nv + nblk - 1) / nblk;          // (one 64-bit division per thread, not one per term)
     const float mu = mean[(threadIdx.x & (CL - 1)) < C ? (threadIdx.x & (CL - 1)) : 0];
     bn_total_of(nblk, C, CL, sh, sh_out, [&](int b, int c) {
         int64_t left = nv - per * b;                     // rows of block b: what bn_share deals it
         left = left < 0 ? 0 : (left > per ? per : left);
         // (both loads unconditional: a load under a condition would be issued -- and waited for -- on its own, term after term)
-        const float p1 = part1[(int64_t)b * C + c], p2 = part2[(int64_t)b * C + c];
+        const float p1 = part1[(int64_t)b * C + c], p2 = part2[(int64_t)b * C + c], p3 = part3[(int64_t)b * C + c];
         const float cnt = (float)left;
-        const float d = p1 / fmaxf(cnt, 1.f) - mu;       // (an empty block: p1 = 0, weight 0)
-        return fmaf(cnt * d, d, p2);
+        const float d = left > 0 ? p1 / cnt - mu : 0.f;  // (an empty block: nothing)
+        return fmaf(d, fmaf(cnt, d, 2.f * p3), p2);
     });
 }
 
@@ -1285,7 +1295,7 @@ __device__ __forceinline__ void bn_apply_body(const BnArgs& a, int CL, float* sh
         bn_total(a.part1, bn_nblk(), a.C, CL, sh, mean);
         if (t < a.C) mean[t] = mean[t] / (float)nv;
         __syncthreads();
-        bn_total_m2(a.part1, a.part2, bn_nblk(), nv, a.C, CL, mean, sh, invstd);
+        bn_total_m2(a.part1, a.part2, a.part3, bn_nblk(), nv, a.C, CL, mean, sh, invstd);
         if (t < a.C) {
             const float mu = mean[t], var = invstd[t] / (float)nv;
             invstd[t] = 1.f / sqrtf(var + a.eps);
@@ -2424,7 +2434,7 @@ extern "C" int mkgnn_tail_flush(void* stream) {
     return e == hipSuccess ? 0 : api_hip_fail("mkgnn_tail_flush", e);
 }
 
-size_t mkgnn_batchnorm_workspace_bytes(int32_t C) { return C > 0 ? (size_t)2 * BN_BLOCKS * C * 4 : 0; }
+size_t mkgnn_batchnorm_workspace_bytes(int32_t C) { return C > 0 ? (size_t)3 * BN_BLOCKS * C * 4 : 0; }
 
 static int bn_common(const char* who, int64_t n, int32_t C, int& CL) {
     if (C < 1 || C > 256) return api_fail("%s: channel count C=%d outside 1..256", who, C);
@@ -2504,6 +2514,7 @@ int mkgnn_batchnorm_forward_with_stats(const float* x, int64_t x_stride, int64_t
         return api_fail("mkgnn_batchnorm_forward: inv_norm needs C <= 32, a multiple of 4, and 16-byte aligned rows of x and out (C=%d)", C);
     a.inv_out = inv_norm; a.split_out = split_rows ? 1 : 0; a.nbt = num_batches_tracked; a.nvalid = n_valid_rows;
     a.part1 = (float*)ws; a.part2 = a.part1 ? a.part1 + (size_t)BN_BLOCKS * C : nullptr;
+    a.part3 = a.part1 ? a.part1 + (size_t)2 * BN_BLOCKS * C : nullptr;
     static_assert(BN_BLOCKS == BN_MAIN_BLOCKS, "the companion's blocks sit behind the batch norm's own");
     bool side_single = false;
     if (companion) {
