@@ -14,6 +14,7 @@
 // Reference: models/MolKGNN/kernels.py:353-425 (scores), :279-350 (chirality), :610-751 (KernelSetConv),
 // KernelLayer.py:109-123 (layer loop, propagate), MolKGNNNet.py:115-146 (batch norm, readout), model.py:150,169,190-198 (head).
 #include "kgnn_launch.h"
+#include "kgnn_philox.h"
 
 namespace mkgnn {
 
@@ -307,30 +308,6 @@ __device__ __forceinline__ v4 mfma4(const v4 a, const v4 b, v4 acc) {
 }
 
 __device__ __forceinline__ float sigmoid_m(float p) { return 1.f / (1.f + expf(-p)); }
-
-// Philox4x32-10, the head's generator (kgnn_readout.hip): the same (seed, offset, element) gives the same mask as
-// mkgnn_bce_head_fused, so the two paths agree on a step with dropout
-__device__ __forceinline__ uint32_t mol_philox_word(uint64_t seed, uint64_t offset, uint64_t element) {
-    uint32_t c0 = (uint32_t)(element >> 2), c1 = (uint32_t)(element >> 34), c2 = (uint32_t)offset, c3 = (uint32_t)(offset >> 32);
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const uint32_t w[4] = {c0, c1, c2, c3};
-    return w[element & 3];
-}
-__device__ __forceinline__ float mol_keep_scale(uint64_t seed, uint64_t offset, uint64_t element, float p) {
-    const float u = (float)(mol_philox_word(seed, offset, element) >> 8) * (1.f / 16777216.f);
-    return u >= p ? 1.f / (1.f - p) : 0.f;
-}
-// the readout's mask: element 2^62 + atom * H + h, atom the batch row (kgnn_philox.h readout_drop_element: the fused tail's mask)
-__device__ __forceinline__ float mol_readout_keep(uint64_t seed, uint64_t offset, int64_t atom, int H, int h, float p) {
-    return mol_keep_scale(seed, offset, ((uint64_t)1 << 62) + (uint64_t)atom * (uint64_t)H + (uint64_t)h, p);
-}
 
 // 1 / max(|row|, eps) of the NAP rows of `buf` (stride XS, FP columns): eight threads per row
 __device__ __forceinline__ void mol_row_norms(const float* buf, int NAP, int XS, int FP, MolMeta& m, int tid) {
@@ -971,7 +948,11 @@ __device__ __forceinline__ void molecule_step_body(MolArgsP ap, float* lds) {
             for (int j = m.mol_first[g] + s8; j < m.mol_first[g + 1]; j += 8) {
                 const float x = pre[j * MOL_HS + h];
                 float sw = x * sigmoid_m(x);
-                if constexpr (RD) sw *= mol_readout_keep(rseed, roff, a0 + j, H, h, a.rdrop);
+                if constexpr (RD) {                          // (the row, then the probability, then the element: the order the
+                    const int64_t atom = a0 + j;             // kernel's instruction schedule was measured with)
+                    const float rp = a.rdrop;
+                    sw *= keep_scale_of(rseed, roff, readout_drop_element(atom, H, h), rp);
+                }
                 s += sw;
             }
             s += __shfl_xor(s, 4, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 1, 64);
@@ -1006,7 +987,7 @@ __device__ __forceinline__ void molecule_step_body(MolArgsP ap, float* lds) {
             for (int k = 0; k < 2; ++k) {
                 const int o = h32 + 32 * k;
                 if (o < G) {
-                    if (drop) ks[k] = mol_keep_scale(seed, offset, (uint64_t)(m0 + g) * G + o, a.head_drop);
+                    if (drop) ks[k] = keep_scale_of(seed, offset, (uint64_t)(m0 + g) * G + o, a.head_drop);
                     x = fmaf(embs[g * 64 + o] * ks[k], a.ffn_w[o], x);
                 }
             }
@@ -1087,7 +1068,11 @@ __device__ __forceinline__ void molecule_step_body(MolArgsP ap, float* lds) {
         if (j < NA && h < H) {
             const float x = pre[j * MOL_HS + h], sg = sigmoid_m(x);
             float dp = dpool[m.mol[j] * 64 + h];
-            if constexpr (RD) dp *= mol_readout_keep(rseed, roff, a0 + j, H, h, a.rdrop);
+            if constexpr (RD) {
+                const int64_t atom = a0 + j;
+                const float rp = a.rdrop;
+                dp *= keep_scale_of(rseed, roff, readout_drop_element(atom, H, h), rp);
+            }
             v = dp * (sg * (1.f + x * (1.f - sg)));
         }
         pre[j * MOL_HS + h] = v;

@@ -1,4 +1,5 @@
-// The counter-based dropout generator of the head kernels (kgnn_readout.hip) and of the fused tail (kgnn_tail.hip).
+// The counter-based dropout generator: the head kernels (kgnn_head.hip), the fused tail (kgnn_tail.hip), the molecule-resident
+// step (kgnn_molecule.hip) and mkgnn_readout_dropout_mask (kgnn_readout.hip) all draw from this one copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

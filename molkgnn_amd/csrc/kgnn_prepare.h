@@ -1,6 +1,6 @@
 // The parameter-only preparation of the kernel banks as device code two launches share (round 6): mkgnn_bank_prepare's own kernel
 // (kgnn_generic.hip) and -- a preparation left pending by mkgnn_bank_prepare_deferred -- blocks behind the batch norm's statistics
-// launch (kgnn_readout.hip), where the 5 us this launch costs the step's critical chain are hidden.
+// launch (kgnn_batchnorm.hip), where the 5 us this launch costs the step's critical chain are hidden.
 #pragma once
 #include "kgnn_common.h"
 #include "kgnn_launch.h"

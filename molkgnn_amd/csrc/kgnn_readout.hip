@@ -1,7 +1,6 @@
-// The two consumers either side of the kernel-convolution stack:
+// The readout behind the kernel-convolution stack (the batch norm in front of it: kgnn_batchnorm.hip):
 //
 //   readout     pool_g( lin2( dropout( swish( lin1(h) ) ) ) )      reference MolKGNNNet.py:144-146
-//   batch norm  BatchNorm1d over the atom rows                      reference MolKGNNNet.py:115
 //
 // Readout.  lin2 and the add-pool are both linear, so the molecule sum is taken first and lin2 is
 // applied to one row per molecule: out_g = W2 (sum_{n in g} keep_n * swish(W1 h_n + b1)) + |g| b2.
@@ -14,19 +13,13 @@
 // Backward per 16-atom tile: dpre = dA[mol] * keep * swish'(pre) in registers, then two tile products,
 // dh = dpre W1 (stored) and dW1 += dpre^T h (kept in accumulators for the whole kernel), followed by a
 // fixed-order reduction block -> slab -> parameter.  No float atomics anywhere: results are reproducible.
-//
-// Batch norm.  Tall and skinny ([1e5, 28]): three short launches (column sums, centred squares, apply),
-// every block re-deriving the column statistics from the per-block partials in a fixed order.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "kgnn_common.h"
 #include <mutex>
-#include <type_traits>
 
 #include "kgnn_launch.h"
 #include "kgnn_philox.h"
-#include "kgnn_prepare.h"
-#include "kgnn_split.h"
 #include "../../include/molkgnn_hip.h"
 
 namespace mkgnn {
@@ -753,1112 +746,6 @@ __global__ void __launch_bounds__(256) block_project_bwd_mfma_kernel(BlockProjAr
     }
 }
 
-// ------------------------------------------------------------------------------------ batch norm ----
-// Statistics-only companion of a batch norm (mkgnn_bn_stats): the reference runs edge_batch_norm(data.edge_attr) in every
-// forward (MolKGNNNet.py:116) although its output never reaches the kernel convolution; what remains of the
-// call is its side effect in training mode -- running_mean / running_var / num_batches_tracked move.  The rows are summed
-// by extra blocks of the node batch norm's own two launches (no launch of their own in a step), or by
-// mkgnn_batchnorm_update_stats alone.  part: [3][nblk][C] = column sums | squares about the block's own means | counted rows.
-#ifndef MKGNN_BN_BLOCKS                  // (A/B builds)
-#define MKGNN_BN_BLOCKS 256
-#endif
-constexpr int BN_MAIN_BLOCKS = MKGNN_BN_BLOCKS;        // (= BN_BLOCKS: the grid of the batch norm's own passes)
-constexpr int BN_SIDE_BLOCKS = 1024;                   // companion blocks at most (one loop trip per pass each where that is enough)
-struct BnSide {
-    const float* x; int64_t xs; int64_t n; int C, CL, nblk;
-    int flat;                                          // contiguous narrow rows: the 16-byte form (bn_side_block_stats_flat)
-    float *running_mean, *running_var; float momentum;
-    int64_t* nbt;
-    const int64_t* key; const int64_t* key_limit;      // both or neither: row r counts iff key[r] < *key_limit
-    float* part;
-};
-
-struct BnArgs {
-    const float* x; int64_t xs; int64_t n; int C;
-    const float *weight, *bias;
-    float *running_mean, *running_var;
-    float momentum, eps; int training;
-    float* out; int64_t os;
-    float *save_mean, *save_invstd;
-    float* part1; float* part2;    // [nblk, C] each
-    float* part3;                  // forward statistics: the blocks' residual sums about their own (rounded) means
-    // backward
-    const float* gout; int64_t gos;
-    float* gx; int64_t gxs;
-    float *gweight, *gbias;
-    float* inv_out;                // forward: 1 / max(|out row|, eps) for the convolution that reads out next (17 <= C <= 32)
-    int split_out;                 // ... and the rows themselves written PRE-SPLIT for it (kgnn_split.h; MKGNN_BN_SPLIT_ROWS)
-    int touch_first;               // blocks from here on of the statistics launch read `touch` and throw it away (mkgnn_touch_hint)
-    TouchArgs touch;
-    int64_t* nbt;                  // forward, training: BatchNorm1d.num_batches_tracked, incremented
-    const int64_t* nvalid;         // device scalar or null: only rows [0, *nvalid) enter the batch statistics (padded batches)
-    BnSide side;                   // statistics-only companion (blocks gridDim.x - side.nblk .. of the same launches); nblk = 0: none
-};
-
-// blocks that work on the batch norm's own rows: the grid, less the companion's extra blocks (BnSide) behind them
-__device__ __forceinline__ int bn_nblk() { return (int)gridDim.x < BN_MAIN_BLOCKS ? (int)gridDim.x : BN_MAIN_BLOCKS; }
-
-// rows that count for the statistics: all of them, or the leading *nvalid (the rest is padding: normalised like any
-// row, excluded from every sum)
-__device__ __forceinline__ int64_t bn_valid(const BnArgs& a) {
-    if (!a.nvalid) return a.n;
-    const int64_t v = *a.nvalid;
-    return v < 1 ? 1 : (v < a.n ? v : a.n);
-}
-
-// rows of this block: [lo, hi)
-__device__ __forceinline__ void bn_rows(const BnArgs& a, int64_t& lo, int64_t& hi) {
-    const int64_t per = (a.n + bn_nblk() - 1) / bn_nblk();
-    lo = per * blockIdx.x;
-    hi = lo + per < a.n ? lo + per : a.n;
-    if (lo > hi) lo = hi;
-}
-
-// ---- round 6: statistics in ONE launch, 16-byte row passes ------------------------------------------------------------------
-// Rounds 1-5 took the batch statistics in two launches (column sums; then, with the batch mean known, centred squares) and
-// applied them in a third; every row pass was 4-byte loads, eight in flight per thread -- 8.6 + 8.9 + 14.2 us for an 11.5 MB
-// tensor at batch 4096, bound by load latency times loop trips.  Now a block sums its share of the counted rows (pass A), takes
-// ITS OWN mean, and sums the squares about that (pass B: the rows the block has just pulled into L2).  The batch statistics
-// follow exactly from the block triples (count_b, sum_b, M2_b):
-//     mean = (sum_b sum_b) / n,     M2 = sum_b [ M2_b + count_b (sum_b / count_b - mean)^2 ]          (Chan, Golub, LeVeque 1979)
-// evaluated in a fixed order by every block of the apply launch -- centred sums throughout, like the two-pass form over the
-// whole batch it replaces; one launch less, and the mean itself is bit for bit the old one (the same partial sums).  Rows that
-// are 16-byte aligned with C a multiple of 4 are read as float4, BN_U rows in flight per thread.
-constexpr int BN_U = 16;                               // float4 row loads in flight per thread (statistics passes)
-constexpr int BN_UA = 8;                               // ... in the passes that also write rows
-
-__device__ __forceinline__ float bn_shfl_xor(float v, int o) { return __shfl_xor(v, o, 64); }
-__device__ __forceinline__ f32x4 bn_shfl_xor(f32x4 v, int o) {
-    return f32x4{__shfl_xor(v[0], o, 64), __shfl_xor(v[1], o, 64), __shfl_xor(v[2], o, 64), __shfl_xor(v[3], o, 64)};
-}
-__device__ __forceinline__ void bn_zero(float& v) { v = 0.f; }
-__device__ __forceinline__ void bn_zero(f32x4& v) { v = f32x4{0.f, 0.f, 0.f, 0.f}; }
-
-// Sum of v over the threads of the block that share threadIdx.x % LW (LW a power of two, 1 .. 256), in a fixed order: an xor
-// tree over the lanes of a wave, then the waves (or row lanes) in ascending order.  Valid in threads < LW.  shv: 256 V's.
-template <typename V> __device__ __forceinline__ V bn_reduce_rows(V v, int LW, V* shv) {
-    const int t = threadIdx.x;
-    for (int o = 32; o >= LW; o >>= 1) v = v + bn_shfl_xor(v, o);
-    __syncthreads();                                     // (shv may still be read from an earlier reduction)
-    int parts;
-    if (LW <= 64) {
-        if ((t & 63) < LW) shv[(t >> 6) * LW + (t & 63)] = v;
-        parts = 4;
-    } else {
-        shv[t] = v;
-        parts = 256 / LW;
-    }
-    __syncthreads();
-    V r;
-    bn_zero(r);
-    if (t < LW)
-        for (int k = 0; k < parts; ++k) r = r + shv[k * LW + t];
-    return r;
-}
-
-// rows of block b of nblk, the counted rows [0, nv) dealt in equal runs: [lo, hi)
-__device__ __forceinline__ void bn_share(int64_t nv, int nblk, int b, int64_t& lo, int64_t& hi) {
-    const int64_t per = (nv + nblk - 1) / nblk;
-    lo = per * b;
-    hi = lo + per < nv ? lo + per : nv;
-    if (lo > hi) lo = hi;
-}
-
-// One pass over rows [lo, hi) of x (and g): per-thread partial sums.  MODE 0: s0 += x;  1: s0 += (x - mu)^2, s1 += x - mu;  2: s0 += g,
-// s1 += g (x - mu) is.  VEC: thread = (row lane rsub of RS, column group col .. col + 3), float4 loads; else one column c.
-// All loads of a trip are issued before anything is consumed (clamped addresses, masked use).
-template <int MODE, int U>
-__device__ __forceinline__ void bn_pass_vec(const float* x, int64_t xs, const float* g, int64_t gs, int64_t lo, int64_t hi, int rsub, int RS,
-                                            int col, f32x4 mu, f32x4 is, f32x4& s0, f32x4& s1) {
-    for (int64_t r0 = lo + rsub; r0 < hi; r0 += (int64_t)U * RS) {
-        f32x4 v[U], gg[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t rr = r0 + (int64_t)u * RS < hi ? r0 + (int64_t)u * RS : hi - 1;
-            v[u] = *(const f32x4*)(x + rr * xs + col);
-            if (MODE == 2) gg[u] = *(const f32x4*)(g + rr * gs + col);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (r0 + (int64_t)u * RS < hi) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (MODE == 0) s0[e] += v[u][e];
-                    if (MODE == 1) { const float d = v[u][e] - mu[e]; s0[e] = fmaf(d, d, s0[e]); s1[e] += d; }
-                    if (MODE == 2) { s0[e] += gg[u][e]; s1[e] = fmaf(gg[u][e], (v[u][e] - mu[e]) * is[e], s1[e]); }
-                }
-            }
-        }
-    }
-}
-template <int MODE>
-__device__ __forceinline__ void bn_pass_col(const float* x, int64_t xs, const float* g, int64_t gs, int64_t lo, int64_t hi, int rsub, int RS,
-                                            int c, float mu, float is, float& s0, float& s1) {
-    for (int64_t r0 = lo + rsub; r0 < hi; r0 += 8 * RS) {
-        float v[8], gg[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int64_t rr = r0 + u * RS < hi ? r0 + u * RS : hi - 1;
-            v[u] = x[rr * xs + c];
-            if (MODE == 2) gg[u] = g[rr * gs + c];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            if (r0 + u * RS < hi) {
-                if (MODE == 0) s0 += v[u];
-                if (MODE == 1) { const float d = v[u] - mu; s0 = fmaf(d, d, s0); s1 += d; }
-                if (MODE == 2) { s0 += gg[u]; s1 = fmaf(gg[u], (v[u] - mu) * is, s1); }
-            }
-        }
-    }
-}
-
-// can the rows of a [*, C] tensor be read as float4?
-static inline bool bn_vec_rows(const void* p, int64_t stride, int C) { return p && C % 4 == 0 && stride % 4 == 0 && ((uintptr_t)p & 15) == 0; }
-
-// Forward statistics of block blockIdx.x: part1[b][c] = column sums of its counted rows, part2[b][c] = squares about the
-// block's own column means, part3[b][c] = the sum of the same centred values.  The block's mean is an fp32 number: for a column
-// with |mean| >> std (1e3 against 1e-1) it is off the true block mean by up to half an ulp of the MEAN, and that sum -- zero for the
-// true mean -- is what the merge needs to stay exact about the pivot actually used (bn_total_m2).  sh: 1024 floats.
-template <bool VEC>
-__device__ __forceinline__ void bn_block_stats(const BnArgs& a, int CL, float* sh) {
-    __shared__ float bmean[256];
-    const int t = threadIdx.x;
-    int64_t lo, hi;
-    // the block's share of the rows that COUNT (not of all rows): the partial sums, and with them the statistics, are then
-    // bit for bit those of the same batch without its padding rows -- a padded batch (molkgnn_amd.padding) reproduces the
-    // unpadded forward exactly, which matters more than it looks: an ulp in x decides thousands of mathematically tied
-    // neighbour orders the other way two layers later
-    bn_share(bn_valid(a), bn_nblk(), blockIdx.x, lo, hi);
-    const float cnt = (float)(hi - lo);
-    float* const p1 = a.part1 + (int64_t)blockIdx.x * a.C;
-    float* const p2 = a.part2 + (int64_t)blockIdx.x * a.C;
-    float* const p3 = a.part3 + (int64_t)blockIdx.x * a.C;
-    if constexpr (VEC) {
-        const int LW = CL >= 4 ? CL / 4 : 1, g = t % LW, rsub = t / LW, RS = 256 / LW, col = 4 * g;
-        const bool act = col < a.C;
-        const int cb = act ? col : 0;
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        f32x4 s0 = z, s1 = z;
-        bn_pass_vec<0, BN_U>(a.x, a.xs, nullptr, 0, lo, hi, rsub, RS, cb, z, z, s0, s1);
-        const f32x4 tot = bn_reduce_rows(s0, LW, (f32x4*)sh);
-        if (t < LW && act) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { p1[col + e] = tot[e]; bmean[col + e] = cnt > 0.f ? tot[e] / cnt : 0.f; }
-        }
-        __syncthreads();
-        const f32x4 mu = {bmean[cb], bmean[cb + 1], bmean[cb + 2], bmean[cb + 3]};
-        s0 = z;
-        bn_pass_vec<1, BN_U>(a.x, a.xs, nullptr, 0, lo, hi, rsub, RS, cb, mu, z, s0, s1);
-        const f32x4 m2 = bn_reduce_rows(s0, LW, (f32x4*)sh);
-        const f32x4 m1 = bn_reduce_rows(s1, LW, (f32x4*)sh);
-        if (t < LW && act) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { p2[col + e] = m2[e]; p3[col + e] = m1[e]; }
-        }
-    } else {
-        const int c = t & (CL - 1), rsub = t / CL, RS = 256 / CL;
-        const bool act = c < a.C;
-        const int cc = act ? c : 0;
-        float s0 = 0.f, s1 = 0.f;
-        bn_pass_col<0>(a.x, a.xs, nullptr, 0, lo, hi, rsub, RS, cc, 0.f, 0.f, s0, s1);
-        const float tot = bn_reduce_rows(s0, CL, sh);
-        if (t < CL && act) { p1[c] = tot; bmean[c] = cnt > 0.f ? tot / cnt : 0.f; }
-        __syncthreads();
-        const float mu = bmean[cc];
-        s0 = 0.f;
-        bn_pass_col<1>(a.x, a.xs, nullptr, 0, lo, hi, rsub, RS, cc, mu, 0.f, s0, s1);
-        const float m2 = bn_reduce_rows(s0, CL, sh);
-        const float m1 = bn_reduce_rows(s1, CL, sh);
-        if (t < CL && act) { p2[c] = m2; p3[c] = m1; }
-    }
-}
-
-// sum over blocks b of term(b, c) for every column c, identically in every block (fixed order), result in sh_out[c];
-// sh: 256 floats
-template <typename Term>
-__device__ __forceinline__ void bn_total_of(int nblk, int C, int CL, float* sh, float* sh_out, Term&& term) {
-    const int c = threadIdx.x & (CL - 1), rsub = threadIdx.x / CL, RS = 256 / CL;
-    float s = 0.f;
-    if (c < C) {
-        // eight terms in flight (every block repeats this sum: serial loads made it the slowest part of the pass)
-        float v[8], t[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int b = rsub; b < nblk; b += 8 * RS) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = term(b + u * RS < nblk ? b + u * RS : b, c);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) if (b + u * RS < nblk) t[u] += v[u];
-        }
-        s = ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
-    }
-    __syncthreads();
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    if (rsub == 0 && c < C) {
-        float t = 0.f;
-        for (int k = 0; k < RS; ++k) t += sh[k * CL + c];
-        sh_out[c] = t;
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ void bn_total(const float* part, int nblk, int C, int CL, float* sh, float* sh_out) {
-    bn_total_of(nblk, C, CL, sh, sh_out, [&](int b, int c) { return part[(int64_t)b * C + c]; });
-}
-// squares about the BATCH mean (mean[c]) out of the blocks' (count, sum, squares and sum about their own means).  With m_b the
-// pivot block b used -- the fp32 quotient sum_b / count_b, formed here by the same division -- r_b = sum (x - m_b) and d = m_b - mean:
-//     sum (x - mean)^2 = sum (x - m_b)^2 + 2 d r_b + count_b d^2 = M2_b + d (2 r_b + count_b d)
-// exactly, whatever m_b is.  Without the r_b term (until this change) the rounding of m_b entered as 2 d r_b: 2e-5 of invstd for
-// a column of 1e3 +- 1e-1 in shares of two rows, ten times what the bound of tests/test_batch_norm_f64.py allows.
-__device__ __forceinline__ void bn_total_m2(const float* part1, const float* part2, const float* part3, int nblk, int64_t nv, int C, int CL,
-                                            const float* mean, float* sh, float* sh_out) {
-    const int64_t per = (nv + nblk - 1) / nblk;          // (one 64-bit division per thread, not one per term)
-    const float mu = mean[(threadIdx.x & (CL - 1)) < C ? (threadIdx.x & (CL - 1)) : 0];
-    bn_total_of(nblk, C, CL, sh, sh_out, [&](int b, int c) {
-        int64_t left = nv - per * b;                     // rows of block b: what bn_share deals it
-        left = left < 0 ? 0 : (left > per ? per : left);
-        // (both loads unconditional: a load under a condition would be issued -- and waited for -- on its own, term after term)
-        const float p1 = part1[(int64_t)b * C + c], p2 = part2[(int64_t)b * C + c], p3 = part3[(int64_t)b * C + c];
-        const float cnt = (float)left;
-        const float d = left > 0 ? p1 / cnt - mu : 0.f;  // (an empty block: nothing)
-        return fmaf(d, fmaf(cnt, d, 2.f * p3), p2);
-    });
-}
-
-// Companion statistics, block `blk` of s.nblk: plane 0 column sums, plane 1 squares about the block's own column means,
-// plane 2 counted rows (every column of the plane holds the count).  Fixed order everywhere.  sh: 1024 floats
-__device__ __forceinline__ void bn_side_block_stats(const BnSide& s, int blk, float* sh) {
-    __shared__ float smean[256];
-    const int CL = s.CL, t = threadIdx.x, c = t & (CL - 1), rsub = t / CL, RS = 256 / CL;
-    const bool act = c < s.C;
-    const int cc = act ? c : 0;
-    int64_t lo, hi;
-    bn_share(s.n, s.nblk, blk, lo, hi);
-    const int64_t lim = s.key ? *s.key_limit : 0;
-    float mu = 0.f, m2 = 0.f;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        float s0 = 0.f, cnt = 0.f;
-        for (int64_t r0 = lo + rsub; r0 < hi; r0 += 8 * RS) {
-            float v[8];
-            bool ok[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int64_t rr = r0 + u * RS < hi ? r0 + u * RS : hi - 1;
-                v[u] = s.x[rr * s.xs + cc];
-                ok[u] = r0 + u * RS < hi && (!s.key || s.key[rr] < lim);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (ok[u]) {
-                    if (pass == 0) { s0 += v[u]; cnt += 1.f; }
-                    else { const float d = v[u] - mu; s0 = fmaf(d, d, s0); }
-                }
-            }
-        }
-        const float tot = bn_reduce_rows(s0, CL, sh);
-        if (pass == 0) {
-            const float n_b = bn_reduce_rows(cnt, CL, sh);          // counts: exact below 2^24 rows per block
-            if (t < CL && act) {
-                s.part[((size_t)0 * s.nblk + blk) * s.C + c] = tot;
-                s.part[((size_t)2 * s.nblk + blk) * s.C + c] = n_b;
-                smean[c] = n_b > 0.f ? tot / n_b : 0.f;
-            }
-            __syncthreads();
-            mu = smean[cc];
-        } else {
-            m2 = tot;
-            if (t < CL && act) s.part[((size_t)1 * s.nblk + blk) * s.C + c] = m2;
-        }
-    }
-}
-
-// The same for narrow contiguous rows (x_stride == C <= 8, 16-byte aligned base: the reference's bond rows, [n, 7]): four rows
-// are C whole float4s, so a thread takes groups of four rows with C 16-byte loads each, SIDE_G groups in flight -- 4 096 rows per
-// block and loop trip where the column-per-thread form above takes 256 (a batch of 4 096 molecules has 216 k bond rows: 53
-// blocks of one trip per pass instead of 844, and a final merge over 53 partials instead of 844).
-constexpr int SIDE_G = 4;
-constexpr int SIDE_FLAT_ROWS = 256 * 4 * SIDE_G;       // rows per block and loop trip
-template <int C>
-__device__ __forceinline__ void bn_side_block_stats_flat(const BnSide& s, int blk, float* sh) {
-    __shared__ float smean[8];
-    const int t = threadIdx.x;
-    int64_t lo, hi;
-    bn_share(s.n / 4, s.nblk, blk, lo, hi);              // in units of four rows: the whole groups; the last n % 4 rows below
-    const int64_t lim = s.key ? *s.key_limit : 0;
-    float mu[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) mu[c] = 0.f;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        float acc[C], cnt = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = 0.f;
-        for (int64_t q0 = lo + t; q0 - t < hi && lo < hi; q0 += 256 * SIDE_G) {
-            f32x4 v[SIDE_G][C];
-            bool ok[SIDE_G][4];
-#pragma unroll
-            for (int g = 0; g < SIDE_G; ++g) {
-                const int64_t q = q0 + 256 * g;                       // rows 4 q .. 4 q + 3
-                const int64_t qc = q < hi ? q : hi - 1;
-#pragma unroll
-                for (int c = 0; c < C; ++c) v[g][c] = *(const f32x4*)(s.x + 4 * qc * C + 4 * c);      // (all loads unconditional)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ok[g][r] = q < hi && (!s.key || s.key[4 * qc + r] < lim);
-            }
-#pragma unroll
-            for (int g = 0; g < SIDE_G; ++g)
-#pragma unroll
-                for (int e = 0; e < 4 * C; ++e) {                     // element e of the group: row e / C, column e % C
-                    if (ok[g][e / C]) {
-                        const float x = v[g][e / 4][e % 4];
-                        if (pass == 0) { acc[e % C] += x; if (e % C == 0) cnt += 1.f; }
-                        else { const float d = x - mu[e % C]; acc[e % C] = fmaf(d, d, acc[e % C]); }
-                    }
-                }
-        }
-        if (blk == s.nblk - 1 && t == 0) {                            // the tensor's last n % 4 rows: a few scalar loads of one thread
-            for (int64_t row = s.n / 4 * 4; row < s.n; ++row) {
-                if (s.key && !(s.key[row] < lim)) continue;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float x = s.x[row * C + c];
-                    if (pass == 0) acc[c] += x;
-                    else { const float d = x - mu[c]; acc[c] = fmaf(d, d, acc[c]); }
-                }
-                if (pass == 0) cnt += 1.f;
-            }
-        }
-        // every thread holds every column: an xor tree over the wave, the four waves in order -- all C + 1 sums behind ONE pair of
-        // barriers (one reduction per column cost more than the row pass itself)
-        float tot[C], n_b = cnt;
-#pragma unroll
-        for (int c = 0; c < C; ++c) tot[c] = acc[c];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) tot[c] += __shfl_xor(tot[c], o, 64);
-            n_b += __shfl_xor(n_b, o, 64);
-        }
-        __syncthreads();
-        if ((t & 63) == 0) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) sh[(t >> 6) * 16 + c] = tot[c];
-            sh[(t >> 6) * 16 + 8] = n_b;
-        }
-        __syncthreads();
-        if (t == 0) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) tot[c] = ((sh[c] + sh[16 + c]) + sh[32 + c]) + sh[48 + c];
-            n_b = ((sh[8] + sh[24]) + sh[40]) + sh[56];
-        }
-        if (t == 0) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                if (pass == 0) {
-                    s.part[((size_t)0 * s.nblk + blk) * C + c] = tot[c];
-                    s.part[((size_t)2 * s.nblk + blk) * C + c] = n_b;
-                    smean[c] = n_b > 0.f ? tot[c] / n_b : 0.f;
-                } else {
-                    s.part[((size_t)1 * s.nblk + blk) * C + c] = tot[c];
-                }
-            }
-        }
-        __syncthreads();
-        if (pass == 0) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) mu[c] = smean[c];
-        }
-    }
-}
-__device__ __forceinline__ bool bn_side_is_flat(const BnSide& s) { return s.flat != 0; }
-__device__ __forceinline__ void bn_side_stats_any(const BnSide& s, int blk, float* sh) {
-    if (!bn_side_is_flat(s)) { bn_side_block_stats(s, blk, sh); return; }
-    switch (s.C) {
-        case 1: bn_side_block_stats_flat<1>(s, blk, sh); break;
-        case 2: bn_side_block_stats_flat<2>(s, blk, sh); break;
-        case 3: bn_side_block_stats_flat<3>(s, blk, sh); break;
-        case 4: bn_side_block_stats_flat<4>(s, blk, sh); break;
-        case 5: bn_side_block_stats_flat<5>(s, blk, sh); break;
-        case 6: bn_side_block_stats_flat<6>(s, blk, sh); break;
-        case 7: bn_side_block_stats_flat<7>(s, blk, sh); break;
-        default: bn_side_block_stats_flat<8>(s, blk, sh); break;
-    }
-}
-
-// running <- running + momentum (batch - running), unbiased variance, counter + 1 (one block)
-__device__ __forceinline__ void bn_side_final(const BnSide& s, float* sh) {
-    __shared__ float tot_sh[256], sq_sh[256], cnt_sh[256], mu_sh[256];
-    const float* const sums = s.part;
-    const float* const sqs = s.part + (size_t)s.nblk * s.C;
-    const float* const cnts = s.part + (size_t)2 * s.nblk * s.C;
-    bn_total(sums, s.nblk, s.C, s.CL, sh, tot_sh);
-    bn_total(cnts, s.nblk, s.C, s.CL, sh, cnt_sh);
-    const int col = threadIdx.x;
-    const float cnt = cnt_sh[0];
-    if (col < s.C) mu_sh[col] = cnt > 0.f ? tot_sh[col] / cnt : 0.f;
-    __syncthreads();
-    bn_total_of(s.nblk, s.C, s.CL, sh, sq_sh, [&](int b, int c) {
-        const float n_b = cnts[(size_t)b * s.C + c], s_b = sums[(size_t)b * s.C + c], q_b = sqs[(size_t)b * s.C + c];     // (unconditional loads)
-        const float d = s_b / fmaxf(n_b, 1.f) - mu_sh[c];
-        return fmaf(n_b * d, d, q_b);
-    });
-    // (BatchNorm1d raises on fewer than two values per channel in training mode; a kernel cannot: such a degenerate batch -- a
-    // padded batch without a single real bond -- leaves the statistics AND the counter where they are: ADVICE round 5)
-    if (col < s.C && cnt > 1.f) {
-        const float mu = mu_sh[col], var = sq_sh[col] / cnt;
-        if (s.running_mean) s.running_mean[col] = fmaf(s.momentum, mu - s.running_mean[col], s.running_mean[col]);
-        if (s.running_var) {
-            const float unbiased = cnt > 1.f ? var * (cnt / (cnt - 1.f)) : var;
-            s.running_var[col] = fmaf(s.momentum, unbiased - s.running_var[col], s.running_var[col]);
-        }
-    }
-    if (threadIdx.x == 0 && s.nbt && cnt > 1.f) s.nbt[0] += 1;
-}
-
-// the companion alone: two launches (phase 0: block statistics, phase 2: totals), or -- one block's worth of rows -- one (phase 3)
-__global__ void __launch_bounds__(256) bn_side_kernel(BnSide s, int phase) {
-    __shared__ float sh[1024];
-    if (phase == 0 || phase == 3) bn_side_stats_any(s, blockIdx.x, sh);
-    if (phase == 3) __syncthreads();                     // (one block: its own global stores are visible to it behind a barrier)
-    if (phase == 2 || phase == 3) bn_side_final(s, sh);
-}
-
-// what rides behind the statistics launch's own blocks: [touch_first, prep_first) read the hinted arrays (mkgnn_touch_hint),
-// [prep_first, grid) run a pending bank preparation (mkgnn_bank_prepare_deferred) -- both independent of the batch norm, both
-// otherwise paid for on the chain in front of the first convolution
-template <bool VEC>
-__global__ void __launch_bounds__(256) bn_stats_kernel(BnArgs a, int CL) {
-    __shared__ float sh[1024];
-    if (a.touch.count > 0 && (int)blockIdx.x >= a.touch_first) {     // (behind the batch norm's and the companion's own blocks)
-        touch_body(a.touch, blockIdx.x - a.touch_first, gridDim.x - a.touch_first);
-        return;
-    }
-    if (blockIdx.x >= BN_MAIN_BLOCKS) {
-        bn_side_stats_any(a.side, blockIdx.x - BN_MAIN_BLOCKS, sh);
-        if (a.side.nblk == 1) {                          // a companion of one block's worth of rows: all of it here, in this launch
-            __syncthreads();                             // (its own global stores are visible to the block behind a barrier)
-            bn_side_final(a.side, sh);
-        }
-        return;
-    }
-    bn_block_stats<VEC>(a, CL, sh);
-}
-
-template <bool VEC>
-__global__ void __launch_bounds__(256) bn_stats_prep_kernel(BnArgs a, int CL, PrepManyArgs pm, int prep_first) {
-    __shared__ float sh[1024];
-    if ((int)blockIdx.x >= prep_first) { bank_prepare_many_block(pm, blockIdx.x - prep_first); return; }
-    if ((int)blockIdx.x >= a.touch_first) {
-        touch_body(a.touch, blockIdx.x - a.touch_first, prep_first - a.touch_first);
-        return;
-    }
-    if (blockIdx.x >= BN_MAIN_BLOCKS) {
-        bn_side_stats_any(a.side, blockIdx.x - BN_MAIN_BLOCKS, sh);
-        if (a.side.nblk == 1) {
-            __syncthreads();
-            bn_side_final(a.side, sh);
-        }
-        return;
-    }
-    bn_block_stats<VEC>(a, CL, sh);
-}
-
-// Round 6, second step: ONE launch for the training forward, one for the backward -- statistics | grid-wide barrier | apply.  The
-// two phases need every block's partial sums, which until now meant a kernel boundary (~5 us in a captured graph on this chip,
-// for kernels that take 14 and 17).  All blocks of these launches are resident at once (at most 256 + 54 blocks of 256 threads and
-// a few KB of LDS on 256 CUs), so a counter in device memory does: a block's thread 0 releases its partials (__threadfence),
-// adds 1, spins until the count is the grid's size, acquires; the last block to LEAVE resets the counters.  The spin is bounded: a
-// grid that is not resident within ~a second falls through (its output is then wrong, but it ends).
-// MEASURED (batch 4096, profiles/r06 notes in DESIGN 4.4): 47 us for the fused forward against 14 + 17 for the two launches, the step
-// 0.723 against 0.708 ms -- the agent-scope release / acquire around the counter writes back and invalidates the L2 of every XCD (the
-// apply phase then re-reads from memory the rows the statistics phase had just pulled in), and 310 waves polling one counter across
-// eight XCDs are slow to see it move.  Correct (the 56 batch-norm / network tests pass with it on), not faster: opt-in only,
-// MKGNN_BN_ONE_LAUNCH=1.
-__device__ unsigned g_bn_barrier[8];                   // {arrived, left} of the forward launch, of the backward launch
-__device__ __forceinline__ void bn_grid_barrier(unsigned* ctr) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        atomicAdd(&ctr[0], 1u);
-        for (unsigned spins = 0; atomicAdd(&ctr[0], 0u) < gridDim.x && spins < (1u << 24); ++spins) __builtin_amdgcn_s_sleep(1);
-        __threadfence();
-        if (atomicAdd(&ctr[1], 1u) == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }      // (everybody has seen the count)
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void bn_apply_body(const BnArgs& a, int CL, float* sh) {
-    __shared__ float mean[256], invstd[256], scale[256], shift[256];
-    const int t = threadIdx.x;
-    if (a.training) {
-        const int64_t nv = bn_valid(a);
-        bn_total(a.part1, bn_nblk(), a.C, CL, sh, mean);
-        if (t < a.C) mean[t] = mean[t] / (float)nv;
-        __syncthreads();
-        bn_total_m2(a.part1, a.part2, a.part3, bn_nblk(), nv, a.C, CL, mean, sh, invstd);
-        if (t < a.C) {
-            const float mu = mean[t], var = invstd[t] / (float)nv;
-            invstd[t] = 1.f / sqrtf(var + a.eps);
-            if (blockIdx.x == 0) {
-                a.save_mean[t] = mu;
-                a.save_invstd[t] = invstd[t];
-                if (a.running_mean) a.running_mean[t] = fmaf(a.momentum, mu - a.running_mean[t], a.running_mean[t]);
-                if (a.running_var) {
-                    const float unbiased = nv > 1 ? var * ((float)nv / (float)(nv - 1)) : var;
-                    a.running_var[t] = fmaf(a.momentum, unbiased - a.running_var[t], a.running_var[t]);
-                }
-            }
-        }
-    } else if (t < a.C) {
-        mean[t] = a.running_mean[t];
-        invstd[t] = 1.f / sqrtf(a.running_var[t] + a.eps);
-        if (blockIdx.x == 0 && a.save_mean) { a.save_mean[t] = mean[t]; a.save_invstd[t] = invstd[t]; }
-    }
-    __syncthreads();
-    if (t < a.C) {
-        const float w = a.weight ? a.weight[t] : 1.f, b = a.bias ? a.bias[t] : 0.f;
-        scale[t] = invstd[t] * w;
-        shift[t] = b;
-    }
-    __syncthreads();
-    int64_t lo, hi;
-    bn_rows(a, lo, hi);
-    const int c = t & (CL - 1), rsub = t / CL, RS = 256 / CL;       // same thread layout as the column sums
-    if (blockIdx.x == 0 && t == 0 && a.nbt && a.training) a.nbt[0] += 1;
-    if (a.inv_out) {
-        // also the row norms of the output, for the kernel convolution that reads it next.  Thread layout of
-        // row_inv_norm_aligned_kernel<8> (kgnn_csr.hip): eight lanes per row, four consecutive channels each (16-byte
-        // loads and stores; the host checks the alignment), the same FMA chain and xor tree on the stored values --
-        // bit-identical to mkgnn_row_inv_norm on `out`.
-        const int l = t & 7, rs8 = t >> 3, col = 4 * l;
-        const bool act = col < a.C;                       // (C is a multiple of 4 here: a lane's four channels exist or do not)
-        const int cb = act ? col : 0;
-        f32x4 mu4, sc4, sh4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { mu4[e] = mean[cb + e]; sc4[e] = scale[cb + e]; sh4[e] = shift[cb + e]; }
-        for (int64_t r0 = lo + rs8; r0 - rs8 < hi; r0 += BN_UA * 32) {
-            f32x4 v[BN_UA];
-#pragma unroll
-            for (int u = 0; u < BN_UA; ++u) v[u] = *(const f32x4*)(a.x + (r0 + u * 32 < hi ? r0 + u * 32 : hi - 1) * a.xs + cb);
-#pragma unroll
-            for (int u = 0; u < BN_UA; ++u) {
-                const bool ok = r0 + u * 32 < hi;
-                f32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = act ? fmaf(v[u][e] - mu4[e], sc4[e], sh4[e]) : 0.f;
-                float ss = o[0] * o[0];
-                ss = fmaf(o[1], o[1], ss); ss = fmaf(o[2], o[2], ss); ss = fmaf(o[3], o[3], ss);
-                ss += __shfl_xor(ss, 4, 64); ss += __shfl_xor(ss, 2, 64); ss += __shfl_xor(ss, 1, 64);
-                const float inv = 1.f / fmaxf(sqrtf(ss), MKGNN_EPS);      // (every lane of the row holds the sum)
-                if (ok && l == 0) a.inv_out[r0 + u * 32] = inv;
-                if (ok && act) *(f32x4*)(a.out + (r0 + u * 32) * a.os + col) = a.split_out ? split_row_store(o, inv) : o;
-            }
-        }
-    } else if (c < a.C) {
-        const float mu = mean[c], sc = scale[c], sh0 = shift[c];
-        for (int64_t r0 = lo + rsub; r0 < hi; r0 += 8 * RS) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = a.x[(r0 + u * RS < hi ? r0 + u * RS : hi - 1) * a.xs + c];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (r0 + u * RS < hi) a.out[(r0 + u * RS) * a.os + c] = fmaf(v[u] - mu, sc, sh0);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) bn_apply_kernel(BnArgs a, int CL) {
-    __shared__ float sh[1024];
-    if (blockIdx.x >= BN_MAIN_BLOCKS) { bn_side_final(a.side, sh); return; }      // (one extra block, training mode only)
-    bn_apply_body(a, CL, sh);
-}
-
-// statistics | barrier | apply: the grid is BN_MAIN_BLOCKS + the companion's blocks (its first block does the companion's totals)
-template <bool VEC>
-__global__ void __launch_bounds__(256) bn_forward_fused_kernel(BnArgs a, int CL) {
-    __shared__ float sh[1024];
-    const bool side = blockIdx.x >= BN_MAIN_BLOCKS;
-    if (side) {
-        bn_side_stats_any(a.side, blockIdx.x - BN_MAIN_BLOCKS, sh);
-        if (a.side.nblk == 1) { __syncthreads(); bn_side_final(a.side, sh); }
-    } else {
-        bn_block_stats<VEC>(a, CL, sh);
-    }
-    bn_grid_barrier(&g_bn_barrier[0]);
-    if (side) {
-        if (blockIdx.x == BN_MAIN_BLOCKS && a.side.nblk > 1) bn_side_final(a.side, sh);
-        return;
-    }
-    bn_apply_body(a, CL, sh);
-}
-
-// backward: per-block column sums of dy and dy * xhat over the block's counted rows -> part1, part2
-template <bool VEC>
-__device__ __forceinline__ void bn_bwd_partial_body(const BnArgs& a, int CL, float* sh) {
-    const int t = threadIdx.x;
-    int64_t lo, hi;
-    bn_share(bn_valid(a), bn_nblk(), blockIdx.x, lo, hi);
-    float* const p1 = a.part1 + (int64_t)blockIdx.x * a.C;
-    float* const p2 = a.part2 + (int64_t)blockIdx.x * a.C;
-    if constexpr (VEC) {
-        const int LW = CL >= 4 ? CL / 4 : 1, g = t % LW, rsub = t / LW, RS = 256 / LW, col = 4 * g;
-        const bool act = col < a.C;
-        const int cb = act ? col : 0;
-        const f32x4 mu = {a.save_mean[cb], a.save_mean[cb + 1], a.save_mean[cb + 2], a.save_mean[cb + 3]};
-        const f32x4 is = {a.save_invstd[cb], a.save_invstd[cb + 1], a.save_invstd[cb + 2], a.save_invstd[cb + 3]};
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-        bn_pass_vec<2, BN_UA>(a.x, a.xs, a.gout, a.gos, lo, hi, rsub, RS, cb, mu, is, s0, s1);
-        const f32x4 t0 = bn_reduce_rows(s0, LW, (f32x4*)sh);
-        const f32x4 t1 = bn_reduce_rows(s1, LW, (f32x4*)sh);
-        if (t < LW && act) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { p1[col + e] = t0[e]; p2[col + e] = t1[e]; }
-        }
-    } else {
-        const int c = t & (CL - 1), rsub = t / CL, RS = 256 / CL;
-        const bool act = c < a.C;
-        const int cc = act ? c : 0;
-        float s0 = 0.f, s1 = 0.f;
-        bn_pass_col<2>(a.x, a.xs, a.gout, a.gos, lo, hi, rsub, RS, cc, a.save_mean[cc], a.save_invstd[cc], s0, s1);
-        const float t0 = bn_reduce_rows(s0, CL, sh);
-        const float t1 = bn_reduce_rows(s1, CL, sh);
-        if (t < CL && act) { p1[c] = t0; p2[c] = t1; }
-    }
-}
-
-template <bool VEC>
-__global__ void __launch_bounds__(256) bn_bwd_partial_kernel(BnArgs a, int CL) {
-    __shared__ float sh[1024];
-    bn_bwd_partial_body<VEC>(a, CL, sh);
-}
-
-template <bool VEC>
-__device__ __forceinline__ void bn_bwd_final_body(const BnArgs& a, int CL, int nblk_part, float* sh) {
-    __shared__ float sdy[256], sdyx[256];
-    bn_total(a.part1, nblk_part, a.C, CL, sh, sdy);
-    bn_total(a.part2, nblk_part, a.C, CL, sh, sdyx);
-    const int t = threadIdx.x;
-    if (blockIdx.x == 0 && t < a.C) {
-        if (a.gbias) a.gbias[t] = sdy[t];
-        if (a.gweight) a.gweight[t] = sdyx[t];
-    }
-    if (!a.gx) return;
-    int64_t lo, hi;
-    bn_rows(a, lo, hi);
-    const float invn = 1.f / (float)bn_valid(a);
-    if constexpr (VEC) {
-        const int LW = CL >= 4 ? CL / 4 : 1, g = t % LW, rsub = t / LW, RS = 256 / LW, col = 4 * g;
-        const bool act = col < a.C;
-        const int cb = act ? col : 0;
-        f32x4 k0, is, mu, s0, s1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float w = a.weight ? a.weight[cb + e] : 1.f;
-            is[e] = a.save_invstd[cb + e]; mu[e] = a.save_mean[cb + e];
-            k0[e] = w * is[e]; s0[e] = sdy[cb + e] * invn; s1[e] = sdyx[cb + e] * invn;
-        }
-        for (int64_t r0 = lo + rsub; r0 < hi; r0 += (int64_t)BN_UA * RS) {
-            f32x4 dy[BN_UA], xv[BN_UA];
-#pragma unroll
-            for (int u = 0; u < BN_UA; ++u) {
-                const int64_t rr = r0 + (int64_t)u * RS < hi ? r0 + (int64_t)u * RS : hi - 1;
-                dy[u] = *(const f32x4*)(a.gout + rr * a.gos + cb);
-                xv[u] = *(const f32x4*)(a.x + rr * a.xs + cb);
-            }
-#pragma unroll
-            for (int u = 0; u < BN_UA; ++u) {
-                if (r0 + (int64_t)u * RS < hi && act) {
-                    f32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float xh = (xv[u][e] - mu[e]) * is[e];
-                        o[e] = a.training ? k0[e] * (dy[u][e] - (s0[e] + xh * s1[e])) : k0[e] * dy[u][e];
-                    }
-                    *(f32x4*)(a.gx + (r0 + (int64_t)u * RS) * a.gxs + col) = o;
-                }
-            }
-        }
-    } else {
-        const int c = t & (CL - 1), rsub = t / CL, RS = 256 / CL;
-        if (c < a.C) {
-            const float w = a.weight ? a.weight[c] : 1.f;
-            const float is = a.save_invstd[c], mu = a.save_mean[c];
-            const float k0 = w * is, s0 = sdy[c] * invn, s1 = sdyx[c] * invn;
-            for (int64_t r0 = lo + rsub; r0 < hi; r0 += 4 * RS) {
-                float dy[4], xv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int64_t rr = r0 + u * RS < hi ? r0 + u * RS : hi - 1;
-                    dy[u] = a.gout[rr * a.gos + c];
-                    xv[u] = a.x[rr * a.xs + c];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (r0 + u * RS < hi) {
-                        const float xh = (xv[u] - mu) * is;
-                        a.gx[(r0 + u * RS) * a.gxs + c] = a.training ? k0 * (dy[u] - (s0 + xh * s1)) : k0 * dy[u];
-                    }
-                }
-            }
-        }
-    }
-}
-
-template <bool VEC>
-__global__ void __launch_bounds__(256) bn_bwd_final_kernel(BnArgs a, int CL, int nblk_part) {
-    __shared__ float sh[1024];
-    bn_bwd_final_body<VEC>(a, CL, nblk_part, sh);
-}
-
-// partial sums | barrier | gradient rows   (grad_x wanted: every block has rows to write)
-template <bool VEC>
-__global__ void __launch_bounds__(256) bn_backward_fused_kernel(BnArgs a, int CL) {
-    __shared__ float sh[1024];
-    bn_bwd_partial_body<VEC>(a, CL, sh);
-    bn_grid_barrier(&g_bn_barrier[2]);
-    bn_bwd_final_body<VEC>(a, CL, (int)gridDim.x, sh);
-}
-
-// ------------------------------------------------------------------ single-task head + BCE-with-logits ----
-// The tail of the training step (reference model.py: ffn(graph_embedding) -> BCEWithLogitsLoss, mean reduction),
-// ~20 tiny PyTorch kernels at B = 4096.  Two launches per pass: 32 lanes per row, 64 rows per block, per-block
-// partials; a one-block kernel sums them in a fixed order.
-struct HeadArgs {
-    const float* emb; int64_t es; int64_t B; int H;
-    const float* w; const float* b; const float* y;
-    float* pred; float* loss;
-    const float* gloss; float* gemb; int64_t ges; float* gw; float* gb;
-    float* partial;
-    float drop_p;                  // dropout on emb ahead of the product (model.py:150,169), 0 = none
-    int64_t* rng;                  // forward: {seed, offset}, offset advanced by one per launch
-    int64_t* rng_used;             // forward writes / backward reads the {seed, offset} of this call's mask
-};
-constexpr int HEAD_ROWS = 16;       // rows per block (two per half-wave: the block's latency is one row's chain, mostly its Philox rounds)
-
-__device__ __forceinline__ float half_wave_sum(float v) {   // xor tree over the 32 lanes of a row
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// The loss kind LK (MKGNN_LOSS_*, ABI v8) is a template parameter of every head kernel: the BCE instantiations are the code
-// that was there before.  A row's loss term and its d loss / d pred, both before the 1 / B of the mean kinds:
-template <int LK>
-__device__ __forceinline__ float head_loss_term(float x, float y) {
-    if constexpr (LK == MKGNN_LOSS_BCE_MEAN) return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));   // torch's stable form
-    else { const float r = x - y; return r * r; }
-}
-template <int LK>
-__device__ __forceinline__ float head_dloss(float x, float y) {
-    if constexpr (LK == MKGNN_LOSS_BCE_MEAN) return 1.f / (1.f + expf(-x)) - y;
-    else return 2.f * (x - y);
-}
-template <int LK>
-__device__ __forceinline__ float head_mean(float v, int64_t B) { return LK == MKGNN_LOSS_SQERR_SUM ? v : v / (float)B; }
-// the loss kind (MKGNN_LOSS_*) of a call as a template argument: f(std::integral_constant<int, LK>{}); false: unknown kind
-template <typename Fn>
-static bool with_loss_kind(int32_t lk, Fn&& f) {
-    switch (lk) {
-    case MKGNN_LOSS_BCE_MEAN: f(std::integral_constant<int, MKGNN_LOSS_BCE_MEAN>{}); return true;
-    case MKGNN_LOSS_SQERR_MEAN: f(std::integral_constant<int, MKGNN_LOSS_SQERR_MEAN>{}); return true;
-    case MKGNN_LOSS_SQERR_SUM: f(std::integral_constant<int, MKGNN_LOSS_SQERR_SUM>{}); return true;
-    default: return false;
-    }
-}
-
-
-template <int LK>
-__global__ void __launch_bounds__(256) head_forward_kernel(HeadArgs a) {
-    __shared__ float red[8];
-    const int t = threadIdx.x, h = t & 31, g = t >> 5;          // 8 rows x 32 lanes per pass
-    const float bias = a.b ? a.b[0] : 0.f;
-    float s = 0.f;
-    constexpr int NP = HEAD_ROWS / 8;
-    // all loads of the block's 64 rows first (unconditional, clamped), then the arithmetic: one global round trip
-    // per block instead of one per pass
-    float xv[NP], yv[NP];
-    const float w0 = h < a.H ? a.w[h] : 0.f;
-    const bool drop = a.drop_p > 0.f;
-    const uint64_t seed = drop ? (uint64_t)a.rng[0] : 0, offset = drop ? (uint64_t)a.rng[1] : 0;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-        const int64_t ic = i < a.B ? i : a.B - 1;
-        xv[k] = a.emb[ic * a.es + (h < a.H ? h : 0)];
-        yv[k] = a.y[ic];
-    }
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-        const int64_t ic = i < a.B ? i : a.B - 1;
-        float x = h < a.H ? xv[k] * w0 : 0.f;
-        if (drop) x *= keep_scale_of(seed, offset, (uint64_t)ic * a.H + (h < a.H ? h : 0), a.drop_p);
-        for (int h0 = 32; h0 < a.H; h0 += 32)                   // (wider embeddings: the rare path)
-            if (h0 + h < a.H) {
-                float e = a.emb[ic * a.es + h0 + h];
-                if (drop) e *= keep_scale_of(seed, offset, (uint64_t)ic * a.H + h0 + h, a.drop_p);
-                x = fmaf(e, a.w[h0 + h], x);
-            }
-        x = half_wave_sum(x) + bias;
-        if (h == 0 && i < a.B) {
-            a.pred[i] = x;
-            s += head_loss_term<LK>(x, yv[k]);
-        }
-    }
-    if (h == 0) red[g] = s;
-    __syncthreads();
-    if (t == 0) {
-        float p = 0.f;
-        for (int k = 0; k < 8; ++k) p += red[k];
-        a.partial[blockIdx.x] = p;
-    }
-}
-
-// second launch of the forward: the block partials in a fixed tree -> loss; advances the dropout generator.
-// (A "last block done" counter inside the first kernel did this in one launch, but the two device-scope fences it
-// needs cost 10-15 us on this part -- more than a second, dependent launch: 4.7 us.)
-template <int LK>
-__global__ void __launch_bounds__(256) head_forward_final_kernel(HeadArgs a, int nblk) {
-    __shared__ float fin[256];
-    const int t = threadIdx.x;
-    float v = 0.f;
-    for (int bk = t; bk < nblk; bk += 256) v += a.partial[bk];
-    fin[t] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) fin[t] += fin[t + w];
-        __syncthreads();
-    }
-    if (t == 0) {
-        a.loss[0] = head_mean<LK>(fin[0], a.B);
-        if (a.drop_p > 0.f) {
-            const int64_t seed = a.rng[0], offset = a.rng[1];
-            a.rng_used[0] = seed; a.rng_used[1] = offset;
-            a.rng[1] = offset + 1;
-        }
-    }
-}
-
-template <int LK>
-__global__ void __launch_bounds__(256) head_backward_kernel(HeadArgs a) {
-    __shared__ float red[8][33];
-    __shared__ float redb[8];
-    const int t = threadIdx.x, h = t & 31, g = t >> 5;
-    const float gl = head_mean<LK>(a.gloss[0], a.B);
-    const int PW = a.H + 1;                                   // partial row: dW[0..H), db
-    float db = 0.f;
-    constexpr int NP = HEAD_ROWS / 8;
-    const bool drop = a.drop_p > 0.f;
-    const uint64_t seed = drop ? (uint64_t)a.rng_used[0] : 0, offset = drop ? (uint64_t)a.rng_used[1] : 0;
-    // d loss / d pred of the block's rows: loads first (unconditional, clamped), then the arithmetic
-    float dv[NP];
-    {
-        float pv[NP], yv[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-            const int64_t ic = i < a.B ? i : a.B - 1;
-            pv[k] = a.pred[ic];
-            yv[k] = a.y[ic];
-        }
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-            dv[k] = i < a.B ? gl * head_dloss<LK>(pv[k], yv[k]) : 0.f;
-            if (h == 0) db += dv[k];
-        }
-    }
-    for (int h0 = 0; h0 < a.H; h0 += 32) {
-        const int hh = h0 + h;
-        const bool ok = hh < a.H;
-        const float wv = ok ? a.w[hh] : 0.f;
-        float dw = 0.f;
-        float ev[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-            const int64_t ic = i < a.B ? i : a.B - 1;
-            ev[k] = a.emb[ic * a.es + (ok ? hh : 0)];
-        }
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-            if (i < a.B && ok) {
-                const float ks = drop ? keep_scale_of(seed, offset, (uint64_t)i * a.H + hh, a.drop_p) : 1.f;
-                dw = fmaf(dv[k], ev[k] * ks, dw);
-                if (a.gemb) a.gemb[i * a.ges + hh] = dv[k] * wv * ks;
-            }
-        }
-        red[g][h] = dw;
-        __syncthreads();
-        if (g == 0 && ok) {
-            float p = 0.f;
-            for (int k = 0; k < 8; ++k) p += red[k][h];
-            a.partial[(size_t)blockIdx.x * PW + hh] = p;
-        }
-        __syncthreads();
-    }
-    if (h == 0) redb[g] = db;
-    __syncthreads();
-    if (t == 0) {
-        float p = 0.f;
-        for (int k = 0; k < 8; ++k) p += redb[k];
-        a.partial[(size_t)blockIdx.x * PW + a.H] = p;
-    }
-}
-
-// second launch of the backward: column c of the block partials, four row parts per column, eight loads in flight
-// per thread; parts combined in a fixed order
-__global__ void __launch_bounds__(256) head_backward_final_kernel(HeadArgs a, int nb) {
-    __shared__ float fin[4][64];
-    const int t = threadIdx.x;
-    const int PW = a.H + 1;
-    const float* part = a.partial;
-    for (int c0 = 0; c0 < PW; c0 += 64) {
-        const int c = c0 + (t & 63), pr = t >> 6;
-        float tot = 0.f;
-        if (c < PW) {
-            for (int bk = pr; bk < nb; bk += 32) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(bk + 4 * u < nb ? bk + 4 * u : bk) * PW + c];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) if (bk + 4 * u < nb) tot += v[u];
-            }
-        }
-        fin[pr][t & 63] = tot;
-        __syncthreads();
-        if (pr == 0 && c < PW) {
-            const float r = (fin[0][t] + fin[1][t]) + (fin[2][t] + fin[3][t]);
-            if (c < a.H) a.gw[c] = r;
-            else if (a.gb) a.gb[0] = r;
-        }
-        __syncthreads();
-    }
-}
-
-// ---- forward AND the gradients for d loss = 1 in one pass (mkgnn_bce_head_fused): the loss is the end of the graph, its
-// own gradient is 1 in every training step, and d loss / d pred = (sigmoid(pred) - y) / B needs nothing but the row's pred --
-// so the block that computes a row's pred also writes its row of grad_emb and adds to its partials of grad_weight /
-// grad_bias; ONE final kernel sums the loss and the gradient partials.  Two launches where forward + backward took four
-// (the four are kept: a caller whose d loss is not 1 scales these, or runs the separate backward).
-// partial row of a block: [dW[0..H) | db | loss]
-template <int LK>
-__global__ void __launch_bounds__(256) head_fused_kernel(HeadArgs a) {
-    __shared__ float red[8][33];
-    __shared__ float redb[8], redl[8];
-    const int t = threadIdx.x, h = t & 31, g = t >> 5;
-    const float bias = a.b ? a.b[0] : 0.f;
-    const int PW = a.H + 2;
-    constexpr int NP = HEAD_ROWS / 8;
-    float xv[NP], yv[NP], ks0[NP], dv[NP];
-    const float w0 = h < a.H ? a.w[h] : 0.f;
-    const bool drop = a.drop_p > 0.f;
-    const uint64_t seed = drop ? (uint64_t)a.rng[0] : 0, offset = drop ? (uint64_t)a.rng[1] : 0;
-    const float invB = head_mean<LK>(1.f, a.B);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-        const int64_t ic = i < a.B ? i : a.B - 1;
-        xv[k] = a.emb[ic * a.es + (h < a.H ? h : 0)];
-        yv[k] = a.y[ic];
-    }
-    float ls = 0.f, db = 0.f;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-        const int64_t ic = i < a.B ? i : a.B - 1;
-        ks0[k] = drop ? keep_scale_of(seed, offset, (uint64_t)ic * a.H + (h < a.H ? h : 0), a.drop_p) : 1.f;
-        float x = h < a.H ? xv[k] * w0 : 0.f;
-        if (drop) x *= ks0[k];
-        for (int h0 = 32; h0 < a.H; h0 += 32)                   // (wider embeddings: the rare path)
-            if (h0 + h < a.H) {
-                float e = a.emb[ic * a.es + h0 + h];
-                if (drop) e *= keep_scale_of(seed, offset, (uint64_t)ic * a.H + h0 + h, a.drop_p);
-                x = fmaf(e, a.w[h0 + h], x);
-            }
-        x = half_wave_sum(x) + bias;                            // (the xor tree leaves the sum in every lane of the row)
-        dv[k] = i < a.B ? invB * head_dloss<LK>(x, yv[k]) : 0.f;
-        if (h == 0 && i < a.B) {
-            a.pred[i] = x;
-            ls += head_loss_term<LK>(x, yv[k]);
-            db += dv[k];
-        }
-    }
-    for (int h0 = 0; h0 < a.H; h0 += 32) {
-        const int hh = h0 + h;
-        const bool ok = hh < a.H;
-        const float wv = ok ? a.w[hh] : 0.f;
-        float dw = 0.f;
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-            if (i < a.B && ok) {
-                float e = xv[k], ks = ks0[k];
-                if (h0 > 0) {
-                    e = a.emb[i * a.es + hh];
-                    ks = drop ? keep_scale_of(seed, offset, (uint64_t)i * a.H + hh, a.drop_p) : 1.f;
-                }
-                dw = fmaf(dv[k], e * ks, dw);
-                if (a.gemb) a.gemb[i * a.ges + hh] = dv[k] * wv * ks;
-            }
-        }
-        red[g][h] = dw;
-        __syncthreads();
-        if (g == 0 && ok) {
-            float p = 0.f;
-            for (int k = 0; k < 8; ++k) p += red[k][h];
-            a.partial[(size_t)blockIdx.x * PW + hh] = p;
-        }
-        __syncthreads();
-    }
-    if (h == 0) { redb[g] = db; redl[g] = ls; }
-    __syncthreads();
-    if (t == 0) {
-        float p = 0.f, q = 0.f;
-        for (int k = 0; k < 8; ++k) { p += redb[k]; q += redl[k]; }
-        a.partial[(size_t)blockIdx.x * PW + a.H] = p;
-        a.partial[(size_t)blockIdx.x * PW + a.H + 1] = q;
-    }
-}
-
-// columns of the block partials (dW, db, loss), four row parts per column, eight loads in flight; fixed order; advances
-// the dropout generator
-template <int LK>
-__global__ void __launch_bounds__(256) head_fused_final_kernel(HeadArgs a, int nb) {
-    __shared__ float fin[4][64];
-    const int t = threadIdx.x;
-    const int PW = a.H + 2;
-    const float* part = a.partial;
-    for (int c0 = 0; c0 < PW; c0 += 64) {
-        const int c = c0 + (t & 63), pr = t >> 6;
-        float tot = 0.f;
-        if (c < PW) {
-            for (int bk = pr; bk < nb; bk += 32) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(bk + 4 * u < nb ? bk + 4 * u : bk) * PW + c];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) if (bk + 4 * u < nb) tot += v[u];
-            }
-        }
-        fin[pr][t & 63] = tot;
-        __syncthreads();
-        if (pr == 0 && c < PW) {
-            const float r = (fin[0][t] + fin[1][t]) + (fin[2][t] + fin[3][t]);
-            if (c < a.H) a.gw[c] = r;
-            else if (c == a.H) { if (a.gb) a.gb[0] = r; }
-            else a.loss[0] = head_mean<LK>(r, a.B);
-        }
-        __syncthreads();
-    }
-    if (t == 0 && a.drop_p > 0.f) {
-        const int64_t seed = a.rng[0], offset = a.rng[1];
-        a.rng_used[0] = seed; a.rng_used[1] = offset;
-        a.rng[1] = offset + 1;
-    }
-}
-
 }  // namespace mkgnn
 
 using namespace mkgnn;
@@ -1879,7 +766,6 @@ bool readout_dims(int F, int H, int G, ReadoutDims& d) {
 
 constexpr int RO_ATOM_BLOCKS = 256;
 constexpr int RO_MOL_BLOCKS = 256;      // 16 molecules per block at batch 4096: one LDS chunk each
-constexpr int BN_BLOCKS = BN_MAIN_BLOCKS;
 
 struct ReadoutWs { size_t dA, slab_atoms, slab_mol, total; int slab_atoms_stride, slab_mol_stride; };
 
@@ -2038,6 +924,24 @@ static int check_blocks(const char* who, const mkgnn_readout_params* p, const in
     return 0;
 }
 
+// z = W1[:, block] sim[block] for the blocks check_blocks filled in (d.NT = 2: H <= 32)
+static hipError_t project_blocks(BlockProjArgs& b, const ReadoutDims& d, int64_t n_focal, const float* sim, int64_t sim_stride,
+                                 int64_t n_atoms, float* z, hipStream_t st) {
+    b.sim = sim; b.ss = sim_stride; b.n = n_atoms; b.z = z;
+    if (n_focal < n_atoms) {                             // atoms in no bucket: their sim row is zero, and so is their z row
+        const hipError_t e = hipMemsetAsync(z, 0, (size_t)n_atoms * d.HP * 4, st);
+        if (e != hipSuccess) return e;
+    }
+    int64_t grid = 0;
+    for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) if (b.L[i] > 0) grid += ((b.cnt[i] + 15) / 16 + 3) / 4;
+    if (grid > 0) {
+        const size_t lds = ((size_t)d.HP * 68 + 4 * 16 * (d.HP + 4)) * 4;
+        if (d.NT == 2) block_project_mfma_kernel<2><<<(unsigned)grid, 256, lds, st>>>(b);
+        else block_project_mfma_kernel<4><<<(unsigned)grid, 256, lds, st>>>(b);
+    }
+    return hipSuccess;
+}
+
 size_t mkgnn_readout_blocks_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_mols) {
     ReadoutDims d;
     if (!blocks_dims(K, H, G, d) || n_mols < 0) return 0;
@@ -2068,19 +972,8 @@ int mkgnn_readout_blocks_forward(const mkgnn_readout_params* p, const float* sim
     int64_t n_focal = 0;
     if (int rc = check_blocks(who, p, num_kernels, buckets, n_atoms, sim_stride, sim, b, d, &n_focal)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    b.sim = sim; b.ss = sim_stride; b.n = n_atoms; b.z = z;
-    hipError_t e = hipSuccess;
-    if (n_focal < n_atoms) {                             // atoms in no bucket: their sim row is zero, and so is their z row
-        e = hipMemsetAsync(z, 0, (size_t)n_atoms * d.HP * 4, st);
-        if (e != hipSuccess) return api_hip_fail(who, e);
-    }
-    int64_t grid = 0;
-    for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) if (b.L[i] > 0) grid += ((b.cnt[i] + 15) / 16 + 3) / 4;
-    if (grid > 0) {
-        const size_t lds = ((size_t)d.HP * 68 + 4 * 16 * (d.HP + 4)) * 4;
-        if (d.NT == 2) block_project_mfma_kernel<2><<<(unsigned)grid, 256, lds, st>>>(b);
-        else block_project_mfma_kernel<4><<<(unsigned)grid, 256, lds, st>>>(b);
-    }
+    hipError_t e = project_blocks(b, d, n_focal, sim, sim_stride, n_atoms, z, st);
+    if (e != hipSuccess) return api_hip_fail(who, e);
     // pre = propagate(z): the propagate step on H-wide rows (+ b1 where pre is read)
     e = launch_segment_sum(z, d.HP, in_rowptr, in_col, n_atoms, d.HP, pre, d.HP, nullptr, st);
     if (e != hipSuccess) return api_hip_fail(who, e);
@@ -2207,49 +1100,54 @@ size_t mkgnn_tail_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_ato
     return tail_ws(d, n_atoms, n_mols).total;
 }
 
-// rp: the readout's dropout (mkgnn_tail_fused_readout_dropout), 0 for mkgnn_tail_fused
-static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void* ws, size_t ws_bytes, void* stream) {
+// The front half of both tail entry points: the checks they share, with the caller's own (`own`) in their place behind the
+// sizes; a reduction an earlier call left pending and nobody took, in front of this call's first launch (its kernels overwrite
+// the workspace slabs the pending one still reads, and read the dropout generator state it advances); then
+// (1) z = W1[:, block] sim[block] into the head of the workspace.  `need`: the caller's mkgnn_tail*_workspace_bytes.
+extern "C++" template <typename Own>
+static int tail_project(const char* who, const mkgnn_tail_args* p, Own&& own, size_t (*need)(int32_t, int32_t, int32_t, int64_t, int64_t),
+                        void* ws, size_t ws_bytes, hipStream_t st, BlockProjArgs& b, ReadoutDims& d) {
     if (!p) return api_fail("%s: null argument", who);
     const mkgnn_readout_params* ro = &p->readout;
-    ReadoutDims d;
     if (!mkgnn_tail_supported(ro->F, ro->H, ro->G, p->num_kernels) || !blocks_dims(ro->F, ro->H, ro->G, d))
         return api_fail("%s: K=%d H=%d G=%d outside the fused tail (the block-row readout's shapes with H, G <= 32)", who, ro->F, ro->H, ro->G);
     if (p->n_atoms < 1 || p->n_mols < 1 || p->n_loss_mols < 1 || p->n_loss_mols > p->n_mols || p->n_atoms >= (int64_t)1 << 31)
         return api_fail("%s: bad sizes", who);
-    if (!p->in_rowptr || !p->in_col || !p->out_rowptr || !p->out_col || !p->mol_ptr || !p->atom_mol || !ro->lin1_weight ||
-        !ro->lin2_weight || !p->head_weight || !p->target || !p->pred || !p->loss || !p->grad_sim)
-        return api_fail("%s: null pointer", who);
-    if (p->dropout_p < 0.f || p->dropout_p >= 1.f) return api_fail("%s: dropout probability %g outside [0, 1)", who, (double)p->dropout_p);
-    if (p->dropout_p > 0.f && (!p->rng_state || !p->rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
-    if (!(rp >= 0.f && rp < 1.f)) return api_fail("%s: readout dropout probability %g outside [0, 1)", who, (double)rp);
-    if (rp > 0.f && (!p->rng_state || !p->rng_used)) return api_fail("%s: readout dropout needs rng_state and rng_used", who);
+    if (int rc = own()) return rc;
     if (p->emb && p->emb_stride < ro->G) return api_fail("%s: bad emb stride", who);
-    if (p->loss_kind < MKGNN_LOSS_BCE_MEAN || p->loss_kind > MKGNN_LOSS_SQERR_SUM) return api_fail("%s: unknown loss kind %d", who, (int)p->loss_kind);
-    BlockProjArgs b{};
     int64_t n_focal = 0;
     if (int rc = check_blocks(who, ro, p->num_kernels, p->buckets, p->n_atoms, p->sim_stride, p->sim, b, d, &n_focal)) return rc;
-    if (p->grad_sim_stride < b.K) return api_fail("%s: bad grad_sim stride", who);
-    const TailWs w = tail_ws(d, p->n_atoms, p->n_mols);
-    if (!ws || ws_bytes < w.total) return api_fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total);
+    const size_t total = need(ro->F, ro->H, ro->G, p->n_atoms, p->n_mols);
+    if (!ws || ws_bytes < total) return api_fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, total);
+    hipError_t e = launch_pending_tail_reduce(st);
+    if (e == hipSuccess) e = project_blocks(b, d, n_focal, p->sim, p->sim_stride, p->n_atoms, (float*)ws, st);
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+// rp: the readout's dropout (mkgnn_tail_fused_readout_dropout), 0 for mkgnn_tail_fused
+static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void* ws, size_t ws_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    BlockProjArgs b{};
+    ReadoutDims d;
+    auto own = [&]() {                                   // what the training tail asks beyond the scoring one
+        const mkgnn_readout_params* ro = &p->readout;
+        if (!p->in_rowptr || !p->in_col || !p->out_rowptr || !p->out_col || !p->mol_ptr || !p->atom_mol || !ro->lin1_weight ||
+            !ro->lin2_weight || !p->head_weight || !p->target || !p->pred || !p->loss || !p->grad_sim)
+            return api_fail("%s: null pointer", who);
+        if (p->dropout_p < 0.f || p->dropout_p >= 1.f) return api_fail("%s: dropout probability %g outside [0, 1)", who, (double)p->dropout_p);
+        if (p->dropout_p > 0.f && (!p->rng_state || !p->rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
+        if (!(rp >= 0.f && rp < 1.f)) return api_fail("%s: readout dropout probability %g outside [0, 1)", who, (double)rp);
+        if (rp > 0.f && (!p->rng_state || !p->rng_used)) return api_fail("%s: readout dropout needs rng_state and rng_used", who);
+        if (p->loss_kind < MKGNN_LOSS_BCE_MEAN || p->loss_kind > MKGNN_LOSS_SQERR_SUM) return api_fail("%s: unknown loss kind %d", who, (int)p->loss_kind);
+        if (p->grad_sim_stride < ro->F) return api_fail("%s: bad grad_sim stride", who);
+        return 0;
+    };
+    if (int rc = tail_project(who, p, own, mkgnn_tail_workspace_bytes, ws, ws_bytes, st, b, d)) return rc;
+    const mkgnn_readout_params* ro = &p->readout;
+    const TailWs w = tail_ws(d, p->n_atoms, p->n_mols);
     float* const z = (float*)((char*)ws + w.z);
     float* const dz = (float*)((char*)ws + w.dz);
-    // (a reduction an earlier call left pending and nobody took: now, in front of this call's first launch -- its kernels
-    // overwrite the workspace slabs the pending one still reads, and read the dropout generator state it advances)
-    hipError_t e = launch_pending_tail_reduce(st);
-    if (e != hipSuccess) return api_hip_fail(who, e);
-    // (1) z = W1[:, block] sim[block]   (d.HP = 32: H <= 32)
-    b.sim = p->sim; b.ss = p->sim_stride; b.n = p->n_atoms; b.z = z;
-    if (n_focal < p->n_atoms) {                          // atoms in no bucket: their sim row is zero, and so is their z row
-        e = hipMemsetAsync(z, 0, (size_t)p->n_atoms * d.HP * 4, st);
-        if (e != hipSuccess) return api_hip_fail(who, e);
-    }
-    int64_t grid = 0;
-    for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) if (b.L[i] > 0) grid += ((b.cnt[i] + 15) / 16 + 3) / 4;
-    if (grid > 0) {
-        const size_t lds = ((size_t)d.HP * 68 + 4 * 16 * (d.HP + 4)) * 4;
-        block_project_mfma_kernel<2><<<(unsigned)grid, 256, lds, st>>>(b);
-    }
+    hipError_t e = hipSuccess;
     // (2) the middle: propagate, swish, pool, lin2, head, loss and the way back to d z, per chunk of whole molecules
     TailMidArgs m{};
     m.z = z; m.dz = dz; m.rin = p->in_rowptr; m.cin = p->in_col; m.rout = p->out_rowptr; m.cout = p->out_col;
@@ -2344,38 +1242,18 @@ size_t mkgnn_tail_score_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t
 
 int mkgnn_tail_score(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "mkgnn_tail_score";
-    if (!p) return api_fail("%s: null argument", who);
-    const mkgnn_readout_params* ro = &p->readout;
-    ReadoutDims d;
-    if (!mkgnn_tail_supported(ro->F, ro->H, ro->G, p->num_kernels) || !blocks_dims(ro->F, ro->H, ro->G, d))
-        return api_fail("%s: K=%d H=%d G=%d outside the fused tail (the block-row readout's shapes with H, G <= 32)", who, ro->F, ro->H, ro->G);
-    if (p->n_atoms < 1 || p->n_mols < 1 || p->n_loss_mols < 1 || p->n_loss_mols > p->n_mols || p->n_atoms >= (int64_t)1 << 31)
-        return api_fail("%s: bad sizes", who);
-    if (!p->in_rowptr || !p->in_col || !p->mol_ptr || !p->atom_mol || !ro->lin1_weight || !ro->lin2_weight || !p->head_weight || !p->pred)
-        return api_fail("%s: null pointer", who);
-    if (p->emb && p->emb_stride < ro->G) return api_fail("%s: bad emb stride", who);
-    BlockProjArgs b{};
-    int64_t n_focal = 0;
-    if (int rc = check_blocks(who, ro, p->num_kernels, p->buckets, p->n_atoms, p->sim_stride, p->sim, b, d, &n_focal)) return rc;
-    const size_t need = tail_ws(d, p->n_atoms, p->n_mols).dz;
-    if (!ws || ws_bytes < need) return api_fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
+    BlockProjArgs b{};
+    ReadoutDims d;
+    auto own = [&]() {
+        const mkgnn_readout_params* ro = &p->readout;
+        if (!p->in_rowptr || !p->in_col || !p->mol_ptr || !p->atom_mol || !ro->lin1_weight || !ro->lin2_weight || !p->head_weight || !p->pred)
+            return api_fail("%s: null pointer", who);
+        return 0;
+    };
+    if (int rc = tail_project(who, p, own, mkgnn_tail_score_workspace_bytes, ws, ws_bytes, st, b, d)) return rc;
+    const mkgnn_readout_params* ro = &p->readout;
     float* const z = (float*)ws;
-    // (a reduction a training call left pending: first, as mkgnn_tail_fused does -- the workspace may be the one it still reads)
-    hipError_t e = launch_pending_tail_reduce(st);
-    if (e != hipSuccess) return api_hip_fail(who, e);
-    // (1) z = W1[:, block] sim[block], exactly as mkgnn_tail_fused launches it
-    b.sim = p->sim; b.ss = p->sim_stride; b.n = p->n_atoms; b.z = z;
-    if (n_focal < p->n_atoms) {
-        e = hipMemsetAsync(z, 0, (size_t)p->n_atoms * d.HP * 4, st);
-        if (e != hipSuccess) return api_hip_fail(who, e);
-    }
-    int64_t grid = 0;
-    for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) if (b.L[i] > 0) grid += ((b.cnt[i] + 15) / 16 + 3) / 4;
-    if (grid > 0) {
-        const size_t lds = ((size_t)d.HP * 68 + 4 * 16 * (d.HP + 4)) * 4;
-        block_project_mfma_kernel<2><<<(unsigned)grid, 256, lds, st>>>(b);
-    }
     // (2) propagate, swish, pool, lin2, head: the training middle's forward phases, its groups and its grid
     TailMidArgs m{};
     m.z = z; m.rin = p->in_rowptr; m.cin = p->in_col; m.mol_ptr = p->mol_ptr; m.atom_mol = p->atom_mol;
@@ -2384,7 +1262,7 @@ int mkgnn_tail_score(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
     m.H = ro->H; m.G = ro->G;
     m.emb = p->emb; m.es = p->emb_stride; m.pred = p->pred;
     m.mg = tail_group_size(p->n_loss_mols);
-    e = launch_tail_score(m, tail_middle_blocks(p->n_loss_mols), st);      // (hipGetLastError: both launches)
+    const hipError_t e = launch_tail_score(m, tail_middle_blocks(p->n_loss_mols), st);      // (hipGetLastError: both launches)
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }
 
@@ -2432,312 +1310,6 @@ hipError_t launch_pending_tail_reduce(hipStream_t st, bool* launched) {
 extern "C" int mkgnn_tail_flush(void* stream) {
     const hipError_t e = launch_pending_tail_reduce((hipStream_t)stream);
     return e == hipSuccess ? 0 : api_hip_fail("mkgnn_tail_flush", e);
-}
-
-size_t mkgnn_batchnorm_workspace_bytes(int32_t C) { return C > 0 ? (size_t)3 * BN_BLOCKS * C * 4 : 0; }
-
-static int bn_common(const char* who, int64_t n, int32_t C, int& CL) {
-    if (C < 1 || C > 256) return api_fail("%s: channel count C=%d outside 1..256", who, C);
-    if (n < 1) return api_fail("%s: batch norm needs at least one row", who);
-    CL = 1;
-    while (CL < C) CL <<= 1;
-    return 0;
-}
-
-size_t mkgnn_batchnorm_stats_workspace_bytes(int32_t C) { return C > 0 ? (size_t)3 * BN_SIDE_BLOCKS * C * 4 : 0; }
-
-// checks a companion and turns it into the kernels' form; s.nblk blocks
-static int bn_side_setup(const char* who, const mkgnn_bn_stats* c, void* ws, size_t ws_bytes, BnSide& s) {
-    if (!c->x || c->n_rows < 1 || c->C < 1 || c->C > 256 || c->x_stride < c->C) return api_fail("%s: bad companion tensor", who);
-    if ((c->row_key != nullptr) != (c->key_limit != nullptr)) return api_fail("%s: row_key and key_limit come together", who);
-    if (!ws || ws_bytes < mkgnn_batchnorm_stats_workspace_bytes(c->C)) return api_fail("%s: companion workspace too small", who);
-    s.x = c->x; s.xs = c->x_stride; s.n = c->n_rows; s.C = c->C;
-    s.CL = 1;
-    while (s.CL < s.C) s.CL <<= 1;
-    s.running_mean = c->running_mean; s.running_var = c->running_var; s.momentum = c->momentum; s.nbt = c->num_batches_tracked;
-    s.key = c->row_key; s.key_limit = c->key_limit; s.part = (float*)ws;
-    s.flat = (c->C <= 8 && c->x_stride == c->C && ((uintptr_t)c->x & 15) == 0) ? 1 : 0;
-    const int64_t rows_per_pass = s.flat ? SIDE_FLAT_ROWS : 8 * (256 / s.CL);      // rows a block takes per loop trip
-    int64_t nb = (c->n_rows + rows_per_pass - 1) / rows_per_pass;
-    s.nblk = (int)(nb < 1 ? 1 : (nb > BN_SIDE_BLOCKS ? BN_SIDE_BLOCKS : nb));
-    return 0;
-}
-
-int mkgnn_batchnorm_update_stats(const mkgnn_bn_stats* c, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "mkgnn_batchnorm_update_stats";
-    if (!c) return api_fail("%s: null argument", who);
-    BnSide s{};
-    if (int rc = bn_side_setup(who, c, ws, ws_bytes, s)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if ((int64_t)c->n_rows * s.CL <= 64 * 1024) {         // one block does all three steps in one launch
-        s.nblk = 1;
-        bn_side_kernel<<<1, 256, 0, st>>>(s, 3);
-    } else {
-        bn_side_kernel<<<s.nblk, 256, 0, st>>>(s, 0);
-        bn_side_kernel<<<1, 256, 0, st>>>(s, 2);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail(who, e);
-}
-
-int mkgnn_batchnorm_forward(const float* x, int64_t x_stride, int64_t n_rows, int32_t C, const float* weight,
-                            const float* bias, float* running_mean, float* running_var, float momentum, float eps,
-                            int32_t training, float* out, int64_t out_stride, float* save_mean, float* save_invstd,
-                            float* inv_norm, int64_t* num_batches_tracked, const int64_t* n_valid_rows, void* ws, size_t ws_bytes,
-                            void* stream) {
-    return mkgnn_batchnorm_forward_with_stats(x, x_stride, n_rows, C, weight, bias, running_mean, running_var, momentum, eps, training,
-                                              out, out_stride, save_mean, save_invstd, inv_norm, num_batches_tracked, n_valid_rows,
-                                              ws, ws_bytes, nullptr, nullptr, 0, stream);
-}
-
-int mkgnn_batchnorm_forward_with_stats(const float* x, int64_t x_stride, int64_t n_rows, int32_t C, const float* weight,
-                            const float* bias, float* running_mean, float* running_var, float momentum, float eps,
-                            int32_t training, float* out, int64_t out_stride, float* save_mean, float* save_invstd,
-                            float* inv_norm, int64_t* num_batches_tracked, const int64_t* n_valid_rows, void* ws, size_t ws_bytes,
-                            const mkgnn_bn_stats* companion, void* companion_ws, size_t companion_ws_bytes, void* stream) {
-    int CL;
-    if (int rc = bn_common("mkgnn_batchnorm_forward", n_rows, C, CL)) return rc;
-    const bool split_rows = (training & MKGNN_BN_SPLIT_ROWS) != 0;       // out is written pre-split (kgnn_split.h)
-    training &= 1;
-    if (split_rows && !inv_norm) return api_fail("mkgnn_batchnorm_forward: MKGNN_BN_SPLIT_ROWS needs inv_norm");
-    if (companion && !training) return api_fail("mkgnn_batchnorm_forward: a statistics companion needs training mode (nothing moves in eval mode)");
-    if (!x || !out || x_stride < C || out_stride < C) return api_fail("mkgnn_batchnorm_forward: bad x/out");
-    if (training && (!save_mean || !save_invstd)) return api_fail("mkgnn_batchnorm_forward: save_mean/save_invstd is null");
-    if (!training && (!running_mean || !running_var)) return api_fail("mkgnn_batchnorm_forward: eval mode needs running statistics");
-    if (training && (!ws || ws_bytes < mkgnn_batchnorm_workspace_bytes(C))) return api_fail("mkgnn_batchnorm_forward: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    BnArgs a{};
-    a.x = x; a.xs = x_stride; a.n = n_rows; a.C = C; a.weight = weight; a.bias = bias;
-    a.running_mean = running_mean; a.running_var = running_var; a.momentum = momentum; a.eps = eps; a.training = training;
-    a.out = out; a.os = out_stride; a.save_mean = save_mean; a.save_invstd = save_invstd;
-    if (inv_norm && (C > 32 || C % 4 || x_stride % 4 || out_stride % 4 || ((uintptr_t)x & 15) || ((uintptr_t)out & 15)))
-        return api_fail("mkgnn_batchnorm_forward: inv_norm needs C <= 32, a multiple of 4, and 16-byte aligned rows of x and out (C=%d)", C);
-    a.inv_out = inv_norm; a.split_out = split_rows ? 1 : 0; a.nbt = num_batches_tracked; a.nvalid = n_valid_rows;
-    a.part1 = (float*)ws; a.part2 = a.part1 ? a.part1 + (size_t)BN_BLOCKS * C : nullptr;
-    a.part3 = a.part1 ? a.part1 + (size_t)2 * BN_BLOCKS * C : nullptr;
-    static_assert(BN_BLOCKS == BN_MAIN_BLOCKS, "the companion's blocks sit behind the batch norm's own");
-    bool side_single = false;
-    if (companion) {
-        if (int rc = bn_side_setup("mkgnn_batchnorm_forward", companion, companion_ws, companion_ws_bytes, a.side)) return rc;
-        if ((int64_t)companion->n_rows * a.side.CL <= 64 * 1024) { a.side.nblk = 1; side_single = true; }
-    }
-    static const bool one_launch = [] { const char* e = getenv("MKGNN_BN_ONE_LAUNCH"); return e && e[0] == '1'; }();      // (opt-in: it lost)
-    if (training && one_launch) {                        // statistics | grid barrier | apply  (MKGNN_BN_ONE_LAUNCH=0: two launches)
-        if (bn_vec_rows(x, x_stride, C)) bn_forward_fused_kernel<true><<<BN_BLOCKS + a.side.nblk, 256, 0, st>>>(a, CL);
-        else bn_forward_fused_kernel<false><<<BN_BLOCKS + a.side.nblk, 256, 0, st>>>(a, CL);
-    } else {
-        if (training) {                                  // block statistics (the companion's blocks behind the batch norm's own)
-            // ... and behind those the blocks of a pending mkgnn_touch_hint: this launch is bound by the latency of its two passes
-            // over 11 MB, not by bandwidth -- the batch's index arrays are read beside them for nothing
-            a.touch.count = 0;
-            a.touch_first = BN_BLOCKS + a.side.nblk;
-            const int extra = take_touch_hint(a.touch) ? TOUCH_BLOCKS : 0;
-            PrepManyArgs pm;
-            if (take_pending_prepare(pm)) {              // ... and behind those a pending bank preparation's tasks
-                pm.touch.count = 0;
-                const int prep_first = a.touch_first + extra;
-                if (bn_vec_rows(x, x_stride, C)) bn_stats_prep_kernel<true><<<prep_first + pm.prep_blocks, 256, 0, st>>>(a, CL, pm, prep_first);
-                else bn_stats_prep_kernel<false><<<prep_first + pm.prep_blocks, 256, 0, st>>>(a, CL, pm, prep_first);
-            } else if (bn_vec_rows(x, x_stride, C)) bn_stats_kernel<true><<<BN_BLOCKS + a.side.nblk + extra, 256, 0, st>>>(a, CL);
-            else bn_stats_kernel<false><<<BN_BLOCKS + a.side.nblk + extra, 256, 0, st>>>(a, CL);
-            a.touch.count = 0;
-        }
-        bn_apply_kernel<<<BN_BLOCKS + ((a.side.nblk && !side_single) ? 1 : 0), 256, 0, st>>>(a, CL);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail("mkgnn_batchnorm_forward", e);
-}
-
-int mkgnn_batchnorm_backward(const float* grad_out, int64_t grad_out_stride, const float* x, int64_t x_stride,
-                             int64_t n_rows, int32_t C, const float* weight, const float* save_mean,
-                             const float* save_invstd, int32_t training, float* grad_x, int64_t grad_x_stride, float* grad_weight, float* grad_bias,
-                             const int64_t* n_valid_rows, void* ws, size_t ws_bytes, void* stream) {
-    int CL;
-    if (int rc = bn_common("mkgnn_batchnorm_backward", n_rows, C, CL)) return rc;
-    if (!grad_out || !x || grad_out_stride < C || x_stride < C) return api_fail("mkgnn_batchnorm_backward: bad grad_out/x");
-    if (!save_mean || !save_invstd) return api_fail("mkgnn_batchnorm_backward: saved statistics are null");
-    if (grad_x && grad_x_stride < C) return api_fail("mkgnn_batchnorm_backward: bad grad_x stride");
-    if (!ws || ws_bytes < mkgnn_batchnorm_workspace_bytes(C)) return api_fail("mkgnn_batchnorm_backward: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    BnArgs a{};
-    a.x = x; a.xs = x_stride; a.n = n_rows; a.C = C; a.weight = weight;
-    a.training = training;
-    a.save_mean = (float*)save_mean; a.save_invstd = (float*)save_invstd;
-    a.part1 = (float*)ws; a.part2 = a.part1 + (size_t)BN_BLOCKS * C;
-    a.gout = grad_out; a.gos = grad_out_stride; a.gx = grad_x; a.gxs = grad_x_stride;
-    a.gweight = grad_weight; a.gbias = grad_bias; a.nvalid = n_valid_rows;
-    static const bool one_launch = [] { const char* e = getenv("MKGNN_BN_ONE_LAUNCH"); return e && e[0] == '1'; }();      // (opt-in: it lost)
-    const bool vec = bn_vec_rows(x, x_stride, C) && bn_vec_rows(grad_out, grad_out_stride, C) && (!grad_x || bn_vec_rows(grad_x, grad_x_stride, C));
-    if (one_launch && grad_x) {                          // partial sums | grid barrier | gradient rows
-        if (vec) bn_backward_fused_kernel<true><<<BN_BLOCKS, 256, 0, st>>>(a, CL);
-        else bn_backward_fused_kernel<false><<<BN_BLOCKS, 256, 0, st>>>(a, CL);
-    } else if (vec) {
-        bn_bwd_partial_kernel<true><<<BN_BLOCKS, 256, 0, st>>>(a, CL);
-        bn_bwd_final_kernel<true><<<grad_x ? BN_BLOCKS : 1, 256, 0, st>>>(a, CL, BN_BLOCKS);
-    } else {
-        bn_bwd_partial_kernel<false><<<BN_BLOCKS, 256, 0, st>>>(a, CL);
-        bn_bwd_final_kernel<false><<<grad_x ? BN_BLOCKS : 1, 256, 0, st>>>(a, CL, BN_BLOCKS);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail("mkgnn_batchnorm_backward", e);
-}
-
-size_t mkgnn_bce_head_workspace_bytes(int64_t n_rows, int32_t H) {
-    if (n_rows < 1 || H < 1) return 0;
-    return 16 + (size_t)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS) * (H + 2) * 4;
-}
-
-static int head_fused(const char* who, int32_t lk, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
-                      const float* weight, const float* bias, const float* target, float dropout_p, int64_t* rng_state,
-                      int64_t* rng_used, float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
-                      float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
-    if (n_rows < 1 || H < 1 || emb_stride < H) return api_fail("%s: bad shape", who);
-    if (!emb || !weight || !target || !pred || !loss || !grad_weight) return api_fail("%s: null pointer", who);
-    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
-    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, dropout_p);
-    if (dropout_p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
-    HeadArgs a{};
-    if (!ws || ws_bytes < mkgnn_bce_head_workspace_bytes(n_rows, H) || ((uintptr_t)ws & 3))
-        return api_fail("%s: workspace too small or misaligned", who);
-    a.partial = (float*)((char*)ws + 16);
-    a.emb = emb; a.es = emb_stride; a.B = n_rows; a.H = H; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss;
-    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
-    a.drop_p = dropout_p; a.rng = rng_state; a.rng_used = rng_used;
-    const int nblk = (int)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS);
-    if (!with_loss_kind(lk, [&](auto K) {
-            head_fused_kernel<decltype(K)::value><<<nblk, 256, 0, (hipStream_t)stream>>>(a);
-            head_fused_final_kernel<decltype(K)::value><<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
-        }))
-        return api_fail("%s: unknown loss kind %d", who, (int)lk);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail(who, e);
-}
-
-int mkgnn_bce_head_fused(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight, const float* bias,
-                         const float* target, float dropout_p, int64_t* rng_state, int64_t* rng_used, float* pred, float* loss,
-                         float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws,
-                         size_t ws_bytes, void* stream) {
-    return head_fused("mkgnn_bce_head_fused", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target, dropout_p,
-                      rng_state, rng_used, pred, loss, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
-}
-
-int mkgnn_head_loss_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
-                          const float* bias, const float* target, float dropout_p, int64_t* rng_state, int64_t* rng_used,
-                          float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
-                          float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
-    return head_fused("mkgnn_head_loss_fused", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, dropout_p,
-                      rng_state, rng_used, pred, loss, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
-}
-
-static int head_ws(const char* who, int64_t n_rows, int32_t H, void* ws, size_t ws_bytes, HeadArgs& a) {
-    if (!ws || ws_bytes < mkgnn_bce_head_workspace_bytes(n_rows, H) || ((uintptr_t)ws & 3))
-        return api_fail("%s: workspace too small or misaligned", who);
-    a.partial = (float*)((char*)ws + 16);
-    return 0;
-}
-
-static int head_forward(const char* who, int32_t lk, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
-                        const float* weight, const float* bias, const float* target, float p, int64_t* rng_state,
-                        int64_t* rng_used, float* pred, float* loss, void* ws, size_t ws_bytes, void* stream) {
-    if (n_rows < 1 || H < 1 || emb_stride < H) return api_fail("%s: bad shape", who);
-    if (!emb || !weight || !target || !pred || !loss) return api_fail("%s: null pointer", who);
-    if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, p);
-    if (p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
-    HeadArgs a{};
-    if (int rc = head_ws(who, n_rows, H, ws, ws_bytes, a)) return rc;
-    a.emb = emb; a.es = emb_stride; a.B = n_rows; a.H = H; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss;
-    a.drop_p = p; a.rng = rng_state; a.rng_used = rng_used;
-    const int nblk = (int)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS);
-    if (!with_loss_kind(lk, [&](auto K) {
-            head_forward_kernel<decltype(K)::value><<<nblk, 256, 0, (hipStream_t)stream>>>(a);
-            head_forward_final_kernel<decltype(K)::value><<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
-        }))
-        return api_fail("%s: unknown loss kind %d", who, (int)lk);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail(who, e);
-}
-
-static int head_backward(const char* who, int32_t lk, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
-                         const float* weight, const float* target, const float* pred, const float* grad_loss, float p,
-                         const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias,
-                         void* ws, size_t ws_bytes, void* stream) {
-    if (n_rows < 1 || H < 1 || emb_stride < H) return api_fail("%s: bad shape", who);
-    if (!emb || !weight || !target || !pred || !grad_loss || !grad_weight) return api_fail("%s: null pointer", who);
-    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
-    if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, p);
-    if (p > 0.f && !rng_used) return api_fail("%s: dropout needs the forward's rng_used", who);
-    HeadArgs a{};
-    if (int rc = head_ws(who, n_rows, H, ws, ws_bytes, a)) return rc;
-    a.emb = emb; a.es = emb_stride; a.B = n_rows; a.H = H; a.w = weight; a.y = target; a.pred = (float*)pred;
-    a.gloss = grad_loss; a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
-    a.drop_p = p; a.rng_used = (int64_t*)rng_used;
-    const int nblk = (int)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS);
-    if (!with_loss_kind(lk, [&](auto K) { head_backward_kernel<decltype(K)::value><<<nblk, 256, 0, (hipStream_t)stream>>>(a); }))
-        return api_fail("%s: unknown loss kind %d", who, (int)lk);
-    head_backward_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail(who, e);
-}
-
-int mkgnn_bce_head_forward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
-                           const float* bias, const float* target, float* pred, float* loss, void* ws, size_t ws_bytes,
-                           void* stream) {
-    return head_forward("mkgnn_bce_head_forward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target, 0.f,
-                        nullptr, nullptr, pred, loss, ws, ws_bytes, stream);
-}
-
-int mkgnn_bce_head_backward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
-                            const float* target, const float* pred, const float* grad_loss, float* grad_emb,
-                            int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws, size_t ws_bytes,
-                            void* stream) {
-    return head_backward("mkgnn_bce_head_backward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, target, pred,
-                         grad_loss, 0.f, nullptr, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
-}
-
-int mkgnn_bce_head_dropout_forward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
-                                   const float* bias, const float* target, float dropout_p, int64_t* rng_state,
-                                   int64_t* rng_used, float* pred, float* loss, void* ws, size_t ws_bytes, void* stream) {
-    return head_forward("mkgnn_bce_head_dropout_forward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target,
-                        dropout_p, rng_state, rng_used, pred, loss, ws, ws_bytes, stream);
-}
-
-int mkgnn_bce_head_dropout_backward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
-                                    const float* target, const float* pred, const float* grad_loss, float dropout_p,
-                                    const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
-                                    float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
-    return head_backward("mkgnn_bce_head_dropout_backward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, target, pred,
-                         grad_loss, dropout_p, rng_used, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
-}
-
-int mkgnn_head_loss_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
-                            const float* weight, const float* bias, const float* target, float* pred, float* loss, void* ws,
-                            size_t ws_bytes, void* stream) {
-    return head_forward("mkgnn_head_loss_forward", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, 0.f, nullptr,
-                        nullptr, pred, loss, ws, ws_bytes, stream);
-}
-
-int mkgnn_head_loss_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
-                             const float* weight, const float* target, const float* pred, const float* grad_loss,
-                             float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws,
-                             size_t ws_bytes, void* stream) {
-    return head_backward("mkgnn_head_loss_backward", loss_kind, emb, emb_stride, n_rows, H, weight, target, pred, grad_loss, 0.f,
-                         nullptr, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
-}
-
-int mkgnn_head_loss_dropout_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
-                                    const float* weight, const float* bias, const float* target, float dropout_p,
-                                    int64_t* rng_state, int64_t* rng_used, float* pred, float* loss, void* ws, size_t ws_bytes,
-                                    void* stream) {
-    return head_forward("mkgnn_head_loss_dropout_forward", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, dropout_p,
-                        rng_state, rng_used, pred, loss, ws, ws_bytes, stream);
-}
-
-int mkgnn_head_loss_dropout_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
-                                     const float* weight, const float* target, const float* pred, const float* grad_loss,
-                                     float dropout_p, const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride,
-                                     float* grad_weight, float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
-    return head_backward("mkgnn_head_loss_dropout_backward", loss_kind, emb, emb_stride, n_rows, H, weight, target, pred,
-                         grad_loss, dropout_p, rng_used, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

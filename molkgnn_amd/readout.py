@@ -562,19 +562,14 @@ class _BceHeadFn(torch.autograd.Function):
                            _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), _lib.ptr(gemb), H, gw.data_ptr(),
                            _lib.ptr(gb), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
             ctx.unit = (gemb, gw, gb)
-            # (references only: a second backward over a retained graph takes the separate backward kernel below)
-            ctx.save_for_backward(emb, w, y, pred, used)
-            ctx.wshape = weight.shape
-            ctx.has_bias = bias is not None
-            ctx.p_drop = float(p_drop)
-            return loss
-        with torch.cuda.device(dev):
-            nbytes = int(lib.mkgnn_bce_head_workspace_bytes(B, H))
-            ws = _head_workspace(dev, nbytes)
-            _head_call(lib, "dropout_forward", kind,
-                       emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), float(p_drop),
-                       _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(),
-                       _lib.stream_ptr(dev))
+        else:
+            with torch.cuda.device(dev):
+                ws = _head_workspace(dev, int(lib.mkgnn_bce_head_workspace_bytes(B, H)))
+                _head_call(lib, "dropout_forward", kind,
+                           emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), float(p_drop),
+                           _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(),
+                           _lib.stream_ptr(dev))
+        # (with ctx.unit, references only: a second backward over a retained graph takes the separate backward kernel)
         ctx.save_for_backward(emb, w, y, pred, used)
         ctx.wshape = weight.shape
         ctx.has_bias = bias is not None
@@ -614,6 +609,18 @@ class _BceHeadFn(torch.autograd.Function):
         return gemb, gw.reshape(ctx.wshape), gb, None, None, None, None
 
 
+def _head_loss(who: str, emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, kind: Optional[int], dropout_p: float,
+               n_rows: Optional[int]) -> torch.Tensor:
+    """The body of ``bce_head_loss`` (``kind`` None: the ``mkgnn_bce_head_*`` entry points) and ``head_loss``."""
+    _lib.require_gpu_tensor(emb, "graph_embedding")
+    n_rows = emb.shape[0] if n_rows is None else int(n_rows)
+    if ffn.out_features != 1 or emb.dim() != 2 or n_rows <= 0 or n_rows > emb.shape[0] or target.numel() != n_rows:
+        raise ValueError(f"{who} needs a one-output linear layer and one target per (leading) row")
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"dropout probability {dropout_p} outside [0, 1)")
+    return _BceHeadFn.apply(emb, ffn.weight, ffn.bias, target, float(dropout_p), n_rows, kind)
+
+
 def bce_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, dropout_p: float = 0.0,
                   n_rows: Optional[int] = None) -> torch.Tensor:
     """``BCEWithLogitsLoss()(ffn(dropout(emb)).view(-1), target.view(-1).float())`` for a one-output ``ffn`` (reference
@@ -621,13 +628,7 @@ def bce_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor,
     zeroing an element of ``emb`` (``nn.Dropout(ffn_dropout_rate)`` in training mode; 0 otherwise), its mask drawn
     inside the kernels from ``head_rng_state``.  ``n_rows``: only the leading rows of ``emb`` enter the loss (a padded batch's
     real molecules); the others get a zero gradient."""
-    _lib.require_gpu_tensor(emb, "graph_embedding")
-    n_rows = emb.shape[0] if n_rows is None else int(n_rows)
-    if ffn.out_features != 1 or emb.dim() != 2 or n_rows <= 0 or n_rows > emb.shape[0] or target.numel() != n_rows:
-        raise ValueError("bce_head_loss needs a one-output linear layer and one target per (leading) row")
-    if not 0.0 <= dropout_p < 1.0:
-        raise ValueError(f"dropout probability {dropout_p} outside [0, 1)")
-    return _BceHeadFn.apply(emb, ffn.weight, ffn.bias, target, float(dropout_p), n_rows, None)     # (None: the v7 entry points)
+    return _head_loss("bce_head_loss", emb, ffn, target, None, dropout_p, n_rows)             # (None: the v7 entry points)
 
 
 def head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, loss: str = "bce", dropout_p: float = 0.0,
@@ -636,14 +637,7 @@ def head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, los
     ``bce_head_loss``), ``"mse"`` (``MSELoss()``) or ``"mse_sum"`` (``MSELoss(reduction='sum')``, the reference's docking-score
     task) of ``ffn(dropout(emb)).view(-1)`` against ``target.view(-1).float()``.  Same kernels (the kind a template parameter),
     same dropout mask for the same generator state, same padding rule."""
-    kind = loss_kind(loss)
-    _lib.require_gpu_tensor(emb, "graph_embedding")
-    n_rows = emb.shape[0] if n_rows is None else int(n_rows)
-    if ffn.out_features != 1 or emb.dim() != 2 or n_rows <= 0 or n_rows > emb.shape[0] or target.numel() != n_rows:
-        raise ValueError("head_loss needs a one-output linear layer and one target per (leading) row")
-    if not 0.0 <= dropout_p < 1.0:
-        raise ValueError(f"dropout probability {dropout_p} outside [0, 1)")
-    return _BceHeadFn.apply(emb, ffn.weight, ffn.bias, target, float(dropout_p), n_rows, kind)
+    return _head_loss("head_loss", emb, ffn, target, loss_kind(loss), dropout_p, n_rows)
 
 
 # ------------------------------------------------------------------- the tail of a training step, fused --
@@ -735,6 +729,24 @@ def _tail_grads_adopted(params) -> bool:
                for p in params)
 
 
+def _tail_args(sim, plan, blocks, seg, n_rows, w1c, b1, w2c, b2, whc, bh):
+    """The ``mkgnn_tail_args`` fields the training tail and the scoring tail both set, and what they point at beyond the
+    arguments (to be kept alive across the call).  Everything not set here stays NULL / 0: a call ignores what it does not need."""
+    a = _lib.TailArgs()
+    a.sim, a.sim_stride = sim.data_ptr(), _stride0(sim)
+    for i, L in enumerate(blocks):
+        a.num_kernels[i] = int(L)
+    bk = _sel_buckets(plan)
+    a.buckets = ctypes.cast(bk, ctypes.c_void_p)
+    rin, cin = plan.csr_in
+    a.in_rowptr, a.in_col = rin.data_ptr(), cin.data_ptr()
+    a.mol_ptr, a.atom_mol = seg.mol_ptr.data_ptr(), seg.atom_mol.data_ptr()
+    a.n_atoms, a.n_mols, a.n_loss_mols = sim.shape[0], seg.size, n_rows
+    a.readout = _params(w1c, b1, w2c, b2)
+    a.head_weight, a.head_bias = whc.data_ptr(), _lib.ptr(bh)
+    return a, (bk,)
+
+
 class _TailFn(torch.autograd.Function):
     """``BCEWithLogitsLoss()(ffn(dropout(readout(propagate(sim)))), y)`` with every gradient for d loss = 1 in the same launch
     (``mkgnn_tail_fused``); the backward hands them out (scaled, if the incoming gradient is not the registered unit seed)."""
@@ -763,20 +775,11 @@ class _TailFn(torch.autograd.Function):
         drop = p_drop > 0.0 or p_readout > 0.0
         rng = head_rng_state(dev) if drop else None
         used = torch.empty(2, dtype=torch.int64, device=dev) if drop else None
-        a = _lib.TailArgs()
-        a.sim, a.sim_stride = sim.data_ptr(), _stride0(sim)
-        for i, L in enumerate(blocks):
-            a.num_kernels[i] = int(L)
-        bk = _sel_buckets(plan)
-        a.buckets = ctypes.cast(bk, ctypes.c_void_p)
-        (rin, cin), (rout, cout) = plan.csr_in, plan.csr_out
-        a.in_rowptr, a.in_col, a.out_rowptr, a.out_col = rin.data_ptr(), cin.data_ptr(), rout.data_ptr(), cout.data_ptr()
-        a.mol_ptr, a.atom_mol = seg.mol_ptr.data_ptr(), seg.atom_mol.data_ptr()
-        a.n_atoms, a.n_mols, a.n_loss_mols = n, seg.size, B
-        a.readout = _params(w1c, b1, w2c, b2)
-        a.head_weight, a.head_bias, a.target = whc.data_ptr(), _lib.ptr(bh), y.data_ptr()
+        a, keep = _tail_args(sim, plan, blocks, seg, B, w1c, b1, w2c, b2, whc, bh)
+        rout, cout = plan.csr_out
+        a.out_rowptr, a.out_col = rout.data_ptr(), cout.data_ptr()
+        a.target = y.data_ptr()
         a.dropout_p, a.rng_state, a.rng_used = float(p_drop), _lib.ptr(rng), _lib.ptr(used)
-        a.emb, a.emb_stride = None, 0
         a.pred, a.loss = pred.data_ptr(), loss.data_ptr()
         a.grad_sim, a.grad_sim_stride = gsim.data_ptr(), K4
         a.grad_lin1_weight, a.grad_lin1_bias = gw1.data_ptr(), _lib.ptr(gb1)
@@ -796,6 +799,7 @@ class _TailFn(torch.autograd.Function):
                                                                 _lib.stream_ptr(dev)), "mkgnn_tail_fused_readout_dropout")
             else:
                 _lib.check(lib.mkgnn_tail_fused(ctypes.byref(a), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_tail_fused")
+        del keep
         if ctx.deferred:
             # (their STORAGES: a second reference to a gradient TENSOR would make autograd copy it into .grad instead of adopting
             # it -- a copy made before the reduction has written it)
@@ -866,18 +870,7 @@ def tail_score(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: tor
     H, G = w1c.shape[0], w2c.shape[0]
     pred = torch.empty(n_rows, dtype=torch.float32, device=dev)
     emb = torch.empty((seg.size, G), dtype=torch.float32, device=dev)
-    a = _lib.TailArgs()                                  # (everything not set here stays NULL / 0: the call ignores it)
-    a.sim, a.sim_stride = sim.data_ptr(), _stride0(sim)
-    for i, L in enumerate(blocks):
-        a.num_kernels[i] = int(L)
-    bk = _sel_buckets(plan)
-    a.buckets = ctypes.cast(bk, ctypes.c_void_p)
-    rin, cin = plan.csr_in
-    a.in_rowptr, a.in_col = rin.data_ptr(), cin.data_ptr()
-    a.mol_ptr, a.atom_mol = seg.mol_ptr.data_ptr(), seg.atom_mol.data_ptr()
-    a.n_atoms, a.n_mols, a.n_loss_mols = n, seg.size, n_rows
-    a.readout = _params(w1c, b1, w2c, b2)
-    a.head_weight, a.head_bias = whc.data_ptr(), _lib.ptr(bh)
+    a, keep = _tail_args(sim, plan, blocks, seg, n_rows, w1c, b1, w2c, b2, whc, bh)
     a.emb, a.emb_stride = emb.data_ptr(), G
     a.pred = pred.data_ptr()
     with torch.cuda.device(dev):
@@ -885,6 +878,7 @@ def tail_score(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: tor
         # is launched by the call before anything is overwritten)
         ws = _tail_workspace(dev, int(lib.mkgnn_tail_score_workspace_bytes(K, H, G, n, seg.size)))
         _lib.check(lib.mkgnn_tail_score(ctypes.byref(a), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_tail_score")
+    del keep
     return pred, emb
 
 

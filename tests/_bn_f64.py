@@ -1,5 +1,5 @@
 """Float64 reference of ``torch.nn.BatchNorm1d`` on a 2-D input, written from the definition, and the input families the batch
-norm kernels (``csrc/kgnn_readout.hip``: ``bn_block_stats``, ``bn_total_m2``, ``bn_pass_vec`` / ``bn_pass_col``, the
+norm kernels (``csrc/kgnn_batchnorm.hip``: ``bn_block_stats``, ``bn_total_m2``, ``bn_pass_vec`` / ``bn_pass_col``, the
 statistics-only companion) are fed in ``tests/test_batch_norm_f64.py``.  CPU only: nothing here imports the package.
 
 The fp32 inputs are cast up exactly, so ``reference`` is the exact answer *for the inputs the kernel saw* (up to float64
@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 ROW_EPS = 1e-8          # torch.nn.CosineSimilarity's clamp (MKGNN_EPS): inv_norm = 1 / max(|row|, ROW_EPS)
-BN_BLOCKS = 256         # blocks of the batch norm's own passes (kgnn_readout.hip BN_MAIN_BLOCKS)
+BN_BLOCKS = 256         # blocks of the batch norm's own passes (kgnn_batchnorm.hip BN_MAIN_BLOCKS)
 
 
 def _f64(t):

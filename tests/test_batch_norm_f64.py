@@ -1,4 +1,4 @@
-"""The batch norm kernels (``csrc/kgnn_readout.hip``: ``mkgnn_batchnorm_forward_with_stats``, ``mkgnn_batchnorm_backward``,
+"""The batch norm kernels (``csrc/kgnn_batchnorm.hip``: ``mkgnn_batchnorm_forward_with_stats``, ``mkgnn_batchnorm_backward``,
 ``mkgnn_batchnorm_update_stats``) on the operator alone, against the float64 reference of ``tests/_bn_f64.py``, at every edge of
 their dispatch: widths and row alignments (16-byte row passes or column passes, mixed in the backward), row counts around the
 256-block grid, ``n_valid``, every mode of ``BatchNorm1d``, ill-conditioned columns, the statistics-only companion in both of its

@@ -1587,7 +1587,7 @@ def test_statistics_only_batch_norm_matches_torch(n, C, masked):
         if xr.shape[0] > 1:
             ref(xr)
         # (torch RAISES on one value per channel in training mode; a kernel cannot, so such a degenerate batch leaves the
-        # statistics and the counter where they are -- kgnn_readout.hip bn_side_final)
+        # statistics and the counter where they are -- kgnn_batchnorm.hip bn_side_final)
         assert torch.allclose(mine.running_mean, ref.running_mean, atol=2e-6, rtol=1e-5), step
         assert torch.allclose(mine.running_var, ref.running_var, atol=1e-5, rtol=2e-5), step
         assert int(mine.num_batches_tracked) == int(ref.num_batches_tracked) == (step + 1 if n > 1 else 0)

@@ -1,4 +1,4 @@
-"""The head's squared-error loss kinds (readout.head_loss; mkgnn_head_loss_*, csrc/kgnn_readout.hip): ``MSELoss()`` and
+"""The head's squared-error loss kinds (readout.head_loss; mkgnn_head_loss_*, csrc/kgnn_head.hip): ``MSELoss()`` and
 ``MSELoss(reduction='sum')`` of ``ffn(dropout(emb))`` -- the reference's docking-score task (data.py:49-53) -- against float64
 autograd, the fused form against the split one, the dropout mask against BCE's, and the BCE kind against ``bce_head_loss``.
 ``pytest -m gpu``."""
