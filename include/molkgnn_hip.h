@@ -786,6 +786,43 @@ size_t mkgnn_collate_compact_bytes(const int64_t shape[6], int64_t n_molecules, 
 int mkgnn_collate_compact(const mkgnn_shard_view* shard, int64_t m0, int64_t m1, const int64_t shape[6],
                           int32_t pad_molecules, void* out, size_t out_bytes);
 
+/* ---- gather-collate from a device-resident shard (additive; the ABI version stays 8): an ARBITRARY list of molecules of a shard that lives in device
+ * memory -- repeats allowed, order kept: a draw with replacement (reference data.py:136-166, WeightedRandomSampler) -- into the
+ * compact wire form above, exactly what mkgnn_collate_compact writes for a shard that holds those molecules in that order as
+ * its range [0, n_ids).  The only per-batch traffic from the host is the id list.
+ *
+ * All pointers of mkgnn_resident_shard are DEVICE pointers.  Every bond is stored once (the even-indexed directed edges of the
+ * shard file) with shard-global endpoints; mol_deg[m][d] is the number of atoms of degree d + 1 in molecule m (a shard with
+ * atoms in no degree bucket cannot be resident).
+ *
+ * Two launches on `stream`, capturable, no host round trip, integer arithmetic only, no atomics: a single-workgroup scan over
+ * the slots (exclusive atom / bond offsets and the slots' first source atom / bond into the workspace; y, mol_ptr and
+ * n_valid_atoms into the wire buffer), then a grid-wide fill in which every element of x, p, bond_ij and bond_attr has exactly
+ * one writer.  Every byte of every wire field is written; the 256-byte alignment gaps between fields are not touched.
+ *
+ * Errors the device finds are reported in the int32 status word at the start of the workspace, written by every launch:
+ *   MKGNN_GATHER_BAD_ID   an id was outside [0, n_molecules); it is clamped before use
+ *   MKGNN_GATHER_MISFIT   the molecules do not fit `shape` (a degree over its target, or the padding does not pair up);
+ *                         every copy is clamped to its field's extent and every index written stays inside the batch
+ * `shape` as for mkgnn_collate_compact; wire_bytes >= mkgnn_collate_compact_bytes(shape, n_ids, pad_molecules, dims). */
+#define MKGNN_GATHER_BAD_ID 1
+#define MKGNN_GATHER_MISFIT 2
+typedef struct mkgnn_resident_shard {
+    const float* x;                 /* [n_atoms, x_dim] */
+    const float* p;                 /* [n_atoms, p_dim] */
+    const int32_t* bond_ij;         /* [n_bonds, 2] shard-global atom ids, every bond once */
+    const uint8_t* bond_attr;       /* [n_bonds, e_dim] */
+    const float* y;                 /* [n_molecules] */
+    const int32_t* mol_atom_ptr;    /* [n_molecules + 1] */
+    const int32_t* mol_bond_ptr;    /* [n_molecules + 1] */
+    const int32_t* mol_deg;         /* [n_molecules, 4] atoms of degree 1, 2, 3, 4 */
+    int64_t n_molecules;
+    int32_t x_dim, p_dim, e_dim, reserved;
+} mkgnn_resident_shard;
+size_t mkgnn_gather_compact_workspace_bytes(int64_t n_ids);
+int mkgnn_gather_compact(const mkgnn_resident_shard* shard, const int32_t* ids, int64_t n_ids, const int64_t shape[6],
+                         int32_t pad_molecules, void* wire, size_t wire_bytes, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

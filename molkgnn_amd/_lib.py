@@ -88,6 +88,14 @@ class ShardView(C.Structure):
                 ("e_dim", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ResidentShardView(C.Structure):
+    """``mkgnn_resident_shard``: DEVICE pointers of a shard that lives in GPU memory (``shards.ResidentShard``)."""
+    _fields_ = [("x", C.c_void_p), ("p", C.c_void_p), ("bond_ij", C.c_void_p), ("bond_attr", C.c_void_p), ("y", C.c_void_p),
+                ("mol_atom_ptr", C.c_void_p), ("mol_bond_ptr", C.c_void_p), ("mol_deg", C.c_void_p), ("n_molecules", C.c_int64),
+                ("x_dim", C.c_int32), ("p_dim", C.c_int32), ("e_dim", C.c_int32), ("reserved", C.c_int32)]
+
+
+GATHER_BAD_ID, GATHER_MISFIT = 1, 2             # MKGNN_GATHER_*: bits of the gather's status word
 Int64x6 = C.c_int64 * 6
 Banks4 = KernelBank * MAX_DEGREE
 BankGrads4 = KernelBankGrad * MAX_DEGREE
@@ -149,7 +157,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_rows_split_supported", "mkgnn_rows_presplit", "mkgnn_tail_supported", "mkgnn_tail_workspace_bytes", "mkgnn_tail_fused", "mkgnn_tail_flush", "mkgnn_flat_copy",
            "mkgnn_tail_fused_readout_dropout", "mkgnn_readout_dropout_mask", "mkgnn_tail_score", "mkgnn_tail_score_workspace_bytes",
            "mkgnn_head_loss_forward", "mkgnn_head_loss_backward", "mkgnn_head_loss_dropout_forward",
-           "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused")
+           "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused", "mkgnn_gather_compact",
+           "mkgnn_gather_compact_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -243,6 +252,11 @@ def load() -> C.CDLL:
     lib.mkgnn_collate_compact_bytes.argtypes = [Int64x6, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.mkgnn_collate_compact.restype = C.c_int
     lib.mkgnn_collate_compact.argtypes = [C.POINTER(ShardView), C.c_int64, C.c_int64, Int64x6, C.c_int32, C.c_void_p, C.c_size_t]
+    lib.mkgnn_gather_compact_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_gather_compact_workspace_bytes.argtypes = [C.c_int64]
+    lib.mkgnn_gather_compact.restype = C.c_int
+    lib.mkgnn_gather_compact.argtypes = [C.POINTER(ResidentShardView), C.c_void_p, C.c_int64, Int64x6, C.c_int32, C.c_void_p,
+                                         C.c_size_t, C.c_void_p, C.c_void_p]
     lib.mkgnn_expand_batch.restype = C.c_int
     lib.mkgnn_expand_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -165,9 +165,15 @@ class CompactStaticBatch:
     ``load`` copies a ``CompactBatch`` into the wire buffer, ``expand`` -- called INSIDE the captured step, before the
     receptive-field builder -- rebuilds ``edge_index``, ``edge_attr``, ``batch`` and ``atom_mol`` with one launch
     (``mkgnn_expand_batch``).  ``data`` is the object the model consumes: ``x``, ``p``, ``y``, ``mol_ptr`` and
-    ``n_valid_atoms`` are views of the wire buffer, nothing is copied twice."""
+    ``n_valid_atoms`` are views of the wire buffer, nothing is copied twice.
 
-    def __init__(self, shape: Dict[str, int], num_molecules: int, x_dim: int, p_dim: int, e_dim: int, device):
+    ``gather`` takes the place of ``load`` when the data set lives on the device (``shards.ResidentShard``): it fills the wire
+    buffer from a list of molecule ids with ``mkgnn_gather_compact``, inside the captured step, immediately before ``expand``.
+    ``max_mol_atoms`` / ``max_mol_edges`` as for ``StaticBatch``: the caller's bound for EVERY batch these buffers will hold
+    (``shards.ResidentLoader`` computes it), which lets a step captured on them run the fused tail."""
+
+    def __init__(self, shape: Dict[str, int], num_molecules: int, x_dim: int, p_dim: int, e_dim: int, device,
+                 max_mol_atoms=None, max_mol_edges=None):
         import numpy as np
         from .shards import compact_layout
         self.shape, self.num_molecules, self.e_dim = dict(shape), int(num_molecules), int(e_dim)
@@ -185,6 +191,41 @@ class CompactStaticBatch:
             batch=torch.zeros(A, dtype=torch.int64, device=dev), atom_mol=torch.zeros(A, dtype=torch.int32, device=dev))
         self.data.n_valid_molecules, self.data.num_graphs = self.num_molecules, self.num_molecules + PAD_MOLECULES
         self.data.bucket_sizes = [shape["n1"], shape["n2"], shape["n3"], shape["n4"]]
+        if max_mol_atoms is not None or max_mol_edges is not None:
+            self.data.max_mol_atoms, self.data.max_mol_edges = max_mol_atoms, max_mol_edges
+        self.x_dim, self.p_dim = int(x_dim), int(p_dim)
+        self.ids = self._gather_ws = None                # gather's static id list and workspace, made on its first call
+
+    def gather(self, resident, ids=None) -> None:
+        """Fill the wire buffer with the molecules ``ids`` of ``resident`` (a device int32 tensor of exactly ``num_molecules``
+        entries; repeats allowed, order kept), on the current stream.  ``ids`` is first copied into the static buffer
+        ``self.ids``; ``gather(resident)`` gathers what that buffer holds -- the form to capture: refill ``self.ids`` between
+        replays.  Nothing is read back: what the device finds wrong is left in the status word (``gather_status``)."""
+        from . import _lib
+        lib = _lib.load()
+        if resident.view is None or resident.device != self.wire.device:
+            raise ValueError(f"the shard is resident on {resident.device}, the static buffers are on {self.wire.device}")
+        if (resident.x_dim, resident.p_dim, resident.e_dim) != (self.x_dim, self.p_dim, self.e_dim):
+            raise ValueError("the shard's feature widths differ from the static buffers'")
+        if self.ids is None:
+            self.ids = torch.zeros(self.num_molecules, dtype=torch.int32, device=self.wire.device)
+            self._gather_ws = torch.zeros(lib.mkgnn_gather_compact_workspace_bytes(self.num_molecules), dtype=torch.uint8,
+                                          device=self.wire.device)
+        if ids is not None and ids is not self.ids:
+            if ids.dtype != torch.int32 or ids.device != self.wire.device or ids.numel() != self.num_molecules:
+                raise ValueError(f"ids must be a device int32 tensor of exactly {self.num_molecules} entries")
+            self.ids.copy_(ids.reshape(-1), non_blocking=True)
+        s = self.shape
+        shape6 = _lib.Int64x6(s["atoms"], s["edges"], s["n1"], s["n2"], s["n3"], s["n4"])
+        with torch.cuda.device(self.wire.device):
+            _lib.check(lib.mkgnn_gather_compact(resident.view, self.ids.data_ptr(), self.num_molecules, shape6, PAD_MOLECULES,
+                                                self.wire.data_ptr(), self.wire.numel(), self._gather_ws.data_ptr(),
+                                                _lib.stream_ptr(self.wire.device)), "mkgnn_gather_compact")
+
+    def gather_status(self) -> int:
+        """The status word of the LAST gather (a host read: once per epoch, not per batch): 0, or ``_lib.GATHER_BAD_ID`` (an id
+        outside the shard, clamped) | ``_lib.GATHER_MISFIT`` (the molecules did not fit the shape; the copies were clamped)."""
+        return 0 if self._gather_ws is None else int(self._gather_ws[:4].view(torch.int32)[0])
 
     def load(self, batch) -> None:
         if list(batch.bucket_sizes) != self.data.bucket_sizes or batch.n_valid_molecules != self.num_molecules \

@@ -341,6 +341,62 @@ def collate_compact(shard: Shard, m0: int, m1: int, shape, host: np.ndarray) -> 
     f["n_valid_atoms"][0] = na
 
 
+def gather_compact(shard: Shard, ids, shape, host: np.ndarray) -> None:
+    """The molecules ``ids`` of a shard -- any integer sequence: repeats allowed, order kept -- padded to ``shape`` in the
+    compact wire form (``compact_layout(shape, len(ids), ...)``): exactly what ``collate_compact`` writes for a shard that
+    holds those molecules in that order as its range ``[0, len(ids))``.  The definition ``mkgnn_gather_compact`` (the gather
+    from a device-resident shard) is tested against, and the CPU path of ``ResidentLoader``."""
+    from .padding import PAD_MOLECULES
+    if not shard.compact_ok:
+        raise ValueError(f"{shard.path}: bonds are not reversed pairs with shared byte-valued attributes: no compact form")
+    ids = np.asarray(ids if isinstance(ids, np.ndarray) else list(ids), dtype=np.int64).reshape(-1)
+    nm = int(ids.shape[0])
+    if nm and (int(ids.min()) < 0 or int(ids.max()) >= shard.n_molecules):
+        raise ValueError(f"molecule ids outside [0, {shard.n_molecules})")
+    a_first, e_first = shard.mol_atom_ptr[ids], shard.mol_edge_ptr[ids]
+    cnt_a, cnt_b = shard.mol_atom_ptr[ids + 1] - a_first, (shard.mol_edge_ptr[ids + 1] - e_first) // 2
+    atom_ptr = np.zeros(nm + 1, dtype=np.int64)
+    atom_ptr[1:] = np.cumsum(cnt_a)
+    bond_ptr = np.zeros(nm + 1, dtype=np.int64)
+    bond_ptr[1:] = np.cumsum(cnt_b)
+    na, nb = int(atom_ptr[-1]), int(bond_ptr[-1])
+    d = (shard.mol_deg_ptr[ids + 1] - shard.mol_deg_ptr[ids]).sum(axis=0).tolist() if nm else [0] * 5
+    h = [na, d[0], d[1], d[2], d[3], d[4]]
+    need = [shape[f"n{k}"] - h[k] for k in range(1, 5)]
+    if min(need) < 0 or h[5]:
+        raise ValueError(f"{nm} gathered molecules with degree histogram {h[1:5]} (+{h[5]} in no bucket) do not fit the shape {shape}")
+    n_pad = sum(need)
+    table, total = compact_layout(shape, nm, shard.x_dim, shard.p_dim, shard.e_dim)
+    if host.shape[0] < total:
+        raise ValueError("staging buffer too small")
+    f = {k: host[off:off + nbytes].view(dt).reshape(shp) for k, off, shp, dt, nbytes in table}
+    # output atom r of slot s comes from shard atom (first atom of molecule ids[s]) + (r - atom_ptr[s]); bonds likewise
+    src_atom = np.repeat(a_first - atom_ptr[:-1], cnt_a) + np.arange(na, dtype=np.int64)
+    src_edge = np.repeat(e_first - 2 * bond_ptr[:-1], cnt_b) + 2 * np.arange(nb, dtype=np.int64)
+    shift = np.repeat(atom_ptr[:-1] - a_first, cnt_b)
+    f["x"][:na] = shard.x[src_atom]; f["x"][na:] = 0.0
+    f["p"][:na] = shard.p[src_atom]; f["p"][na:] = 0.0
+    f["bond_attr"][:nb] = shard.edge_attr[src_edge]
+    f["bond_attr"][nb:] = 0
+    f["bond_attr"][nb:, 0] = 1
+    ij = f["bond_ij"]
+    ij[:nb, 0] = shard.edge_src[src_edge] + shift
+    ij[:nb, 1] = shard.edge_dst[src_edge] + shift
+    deg_of = np.repeat(np.arange(1, 5), need)
+    stubs = np.repeat(np.arange(n_pad, dtype=np.int64), deg_of) + na
+    if stubs.shape[0] % 2 or stubs.shape[0] != shape["edges"] - 2 * nb:
+        raise ValueError("padding bond stubs do not pair up: the shape does not come from fixed_shape() over these batches")
+    ij[nb:, 0] = stubs[0::2]
+    ij[nb:, 1] = stubs[1::2]
+    f["y"][:] = shard.y[ids]
+    mp = f["mol_ptr"]
+    mp[0] = 0
+    mp[1:nm + 1] = atom_ptr[1:]
+    pad_mol = (np.arange(n_pad, dtype=np.int64) * PAD_MOLECULES) // max(n_pad, 1)
+    mp[nm + 1:] = na + np.cumsum(np.bincount(pad_mol, minlength=PAD_MOLECULES))
+    f["n_valid_atoms"][0] = na
+
+
 def collate_compact_native(shard: Shard, m0: int, m1: int, shape, host: np.ndarray) -> None:
     """``collate_compact`` by ONE call into the library (``mkgnn_collate_compact``, host code): byte for byte the same buffer
     (tested), and the interpreter lock is released for the whole batch -- the numpy form holds it through a dozen small array
@@ -577,6 +633,137 @@ class ShardLoader:
                     done = torch.cuda.Event()
                     done.record(torch.cuda.current_stream(self.device))
                     consumed[slot] = done
+
+
+class ResidentShard:
+    """One ``compact_ok`` shard held in device memory in the layout of ``mkgnn_resident_shard``: features and coordinates as
+    they are, every bond once (the even-indexed directed edges) as shard-global int32 endpoints with uint8 attributes, labels,
+    per-molecule atom / bond pointers and per-degree atom counts.  ``padding.CompactStaticBatch.gather`` forms a batch from
+    ANY list of its molecules on the device (``mkgnn_gather_compact``), so the only per-batch traffic from the host is the
+    id list.  The host keeps the per-molecule counts (``mol_atoms``, ``mol_bonds``, ``mol_deg``) for planning and ``y`` for a
+    sampler: ``sampling.oversampling_sampler(resident.y, seed)``.  With ``device="cpu"`` nothing is uploaded (the loader's CPU
+    path gathers with ``gather_compact``)."""
+
+    def __init__(self, shard_or_path, device="cpu"):
+        sh = shard_or_path if isinstance(shard_or_path, Shard) else Shard(str(shard_or_path))
+        if not sh.compact_ok:
+            raise ValueError(f"{sh.path}: bonds are not reversed pairs with shared byte-valued attributes: no compact form")
+        if int(sh.mol_deg_ptr[-1, 4]):
+            raise ValueError(f"{sh.path}: {int(sh.mol_deg_ptr[-1, 4])} atoms of degree 0 or > 4 are in no bucket")
+        self.shard, self.device = sh, torch.device(device)
+        self.n_molecules, self.x_dim, self.p_dim, self.e_dim = sh.n_molecules, sh.x_dim, sh.p_dim, sh.e_dim
+        self.mol_atoms = np.diff(sh.mol_atom_ptr)
+        self.mol_bonds = np.diff(sh.mol_edge_ptr) // 2
+        self.mol_deg = np.ascontiguousarray(np.diff(sh.mol_deg_ptr, axis=0)[:, :4])
+        self.y = torch.from_numpy(np.array(sh.y))
+        self.tensors, self.view = {}, None
+        if self.device.type == "cuda":
+            from . import _lib
+            host = {"x": sh.x, "p": sh.p, "bond_ij": np.stack([sh.edge_src[0::2], sh.edge_dst[0::2]], axis=1),
+                    "bond_attr": sh.edge_attr[0::2].astype(np.uint8), "y": sh.y,
+                    "mol_atom_ptr": sh.mol_atom_ptr.astype(np.int32), "mol_bond_ptr": (sh.mol_edge_ptr // 2).astype(np.int32),
+                    "mol_deg": self.mol_deg.astype(np.int32)}
+            self.tensors = {k: torch.from_numpy(np.array(v)).to(self.device) for k, v in host.items()}     # (np.array: a writable copy of the map)
+            self.view = _lib.ResidentShardView()
+            for k, t in self.tensors.items():
+                setattr(self.view, k, t.data_ptr())
+            self.view.n_molecules, self.view.x_dim, self.view.p_dim, self.view.e_dim = sh.n_molecules, sh.x_dim, sh.p_dim, sh.e_dim
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors.values())
+
+
+class ResidentLoader:
+    """One epoch of batches drawn from a ``ResidentShard`` by an arbitrary index stream ``indices`` (a
+    ``WeightedRandomSampler``, a permutation, a tensor ...): the stream is cut into pieces of ``batch_size`` (a short tail is
+    dropped, as ``ShardLoader(fixed_shape=True)`` does), pieces ``rank, rank + world, ...`` are this rank's.  Everything is
+    planned on the host from the per-molecule counts before anything is launched: ids out of range, every batch's degree
+    histogram, the common ``shape`` (``padding.fixed_shape`` over the plan, the four per-degree targets scaled up by
+    ``headroom`` before the parity fix; or a GIVEN shape -- e.g. the first epoch's, so that a captured graph survives a new
+    draw -- which every batch must fit) and ``max_mol_atoms`` / ``max_mol_edges``, the largest molecule of the plan with the
+    padding molecules included (what ``padding.pad_batch`` reports, maximised over the batches).
+
+    The epoch's ids are uploaded once; iterating yields one device int32 view per batch for
+    ``padding.CompactStaticBatch.gather``.  On the CPU it yields ``CompactBatch``es filled by ``gather_compact``."""
+
+    def __init__(self, resident: ResidentShard, batch_size: int, indices, device="cpu", rank: int = 0, world: int = 1,
+                 shape=None, headroom: float = 0.0):
+        if not (0 <= rank < world):
+            raise ValueError(f"rank {rank} of world {world}")
+        if headroom < 0:
+            raise ValueError("headroom is a non-negative fraction")
+        self.resident, self.batch_size, self.device = resident, int(batch_size), torch.device(device)
+        self.rank, self.world, self.headroom = rank, world, float(headroom)
+        self.shape = None if shape is None else dict(shape)
+        self._ids_host = self._ids_dev = None
+        self.set_epoch(indices)
+
+    def set_epoch(self, indices) -> None:
+        """Plan a new epoch from a new index stream; ``shape`` is kept (a batch that does not fit it raises)."""
+        from .padding import PAD_MOLECULES, fixed_shape
+        r, bs = self.resident, self.batch_size
+        ids = np.asarray(indices.tolist() if torch.is_tensor(indices) else list(indices), dtype=np.int64).reshape(-1)
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= r.n_molecules):
+            raise ValueError(f"molecule ids outside [0, {r.n_molecules})")
+        n_all = ids.shape[0] // bs
+        batches = ids[:n_all * bs].reshape(n_all, bs)[self.rank::self.world]
+        if batches.shape[0] == 0:
+            raise ValueError("no full batch for this rank")
+        atoms = r.mol_atoms[batches].sum(axis=1)
+        deg = r.mol_deg[batches].sum(axis=1)                                    # [batches, 4]
+        if self.shape is None:
+            shape = fixed_shape([[int(a), *map(int, d), 0] for a, d in zip(atoms, deg)])
+            if self.headroom > 0:
+                t = [int(np.ceil(shape[f"n{k}"] * (1.0 + self.headroom))) for k in range(1, 5)]
+                if sum((k + 1) * t[k] for k in range(4)) % 2:
+                    t[0] += 1
+                shape = {"n1": t[0], "n2": t[1], "n3": t[2], "n4": t[3], "atoms": sum(t), "edges": sum((k + 1) * t[k] for k in range(4))}
+            self.shape = shape
+        target = np.array([self.shape[f"n{k}"] for k in range(1, 5)], dtype=np.int64)
+        need = target[None, :] - deg
+        if self.shape["atoms"] != int(target.sum()) or self.shape["edges"] != int((target * np.arange(1, 5)).sum()) or self.shape["edges"] % 2:
+            raise ValueError(f"the shape {self.shape} is not a bucket shape (padding.fixed_shape)")
+        short = np.nonzero((need < 0).any(axis=1))[0]
+        if short.size:
+            k = int(short[0])
+            raise ValueError(f"batch {k} of this rank's plan, with degree histogram {deg[k].tolist()}, does not fit the shape {self.shape}")
+        # the largest molecule of the plan, padding molecules included (padding.pad_batch's figures, maximised): the padding atoms
+        # come in degree order and are dealt to the padding molecules in runs; an atom of degree d has d edges each way
+        pad_atoms = pad_edges = 0
+        for nd in {tuple(row) for row in need.tolist()}:
+            n_pad = sum(nd)
+            if n_pad:
+                mol = (np.arange(n_pad, dtype=np.int64) * PAD_MOLECULES) // n_pad
+                deg_of = np.repeat(np.arange(1, 5), nd)
+                pad_atoms = max(pad_atoms, int(np.bincount(mol).max()))
+                pad_edges = max(pad_edges, int(np.bincount(mol, weights=deg_of).max()))
+        self.max_mol_atoms = max(int(r.mol_atoms[batches].max()), pad_atoms)
+        self.max_mol_edges = max(2 * int(r.mol_bonds[batches].max()), pad_edges)
+        self._batches = batches
+        self._ids_dev = None
+        if self.device.type == "cuda":
+            # (through pinned memory, without waiting: the host plans the next epoch while the device still works on this one)
+            self._ids_host = torch.from_numpy(batches.astype(np.int32)).pin_memory()
+            self._ids_dev = self._ids_host.to(self.device, non_blocking=True)
+
+    def plan(self) -> np.ndarray:
+        """This rank's batches, in order: ``[batches, batch_size]`` molecule ids."""
+        return self._batches
+
+    def __len__(self):
+        return int(self._batches.shape[0])
+
+    def __iter__(self):
+        if self._ids_dev is not None:
+            for k in range(len(self)):
+                yield self._ids_dev[k]
+            return
+        sh = self.resident.shard
+        _, total = compact_layout(self.shape, self.batch_size, sh.x_dim, sh.p_dim, sh.e_dim)
+        for row in self._batches:
+            flat = torch.empty(total, dtype=torch.uint8)
+            gather_compact(sh, row, self.shape, flat.numpy())
+            yield CompactBatch(flat, self.shape, self.batch_size)
 
 
 def write_shards(directory: str, batches: Iterable[GraphBatch], prefix: str = "shard") -> List[str]:
