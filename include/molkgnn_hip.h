@@ -823,6 +823,32 @@ size_t mkgnn_gather_compact_workspace_bytes(int64_t n_ids);
 int mkgnn_gather_compact(const mkgnn_resident_shard* shard, const int32_t* ids, int64_t n_ids, const int64_t shape[6],
                          int32_t pad_molecules, void* wire, size_t wire_bytes, void* workspace, void* stream);
 
+/* ---- running top-k on the device (additive; the ABI version stays 8): the ranking of a screen, kept sorted across batches and
+ * shards inside the captured scoring step.  The list (top_score, top_shard, top_mol)[K] is updated IN PLACE to the best K entries
+ * of the multiset  old list  U  {(scores[i], *shard_tag, ids[i]) : i < min(max(*n_valid, 0), B)}  and is always fully sorted.
+ * n_valid and shard_tag are device int32 scalars read by the kernels, so one captured launch serves every batch and shard;
+ * scores and ids past n_valid are not read.
+ *
+ * The order is total:
+ *   1. occupied slots before empty slots.  An empty slot is (-inf, -1, -1); a real entry whose score is -inf ranks before it
+ *      (a real entry with score -inf, shard -1 AND molecule -1 cannot be told from an empty slot: tags and ids are >= 0 in use)
+ *   2. non-NaN scores before NaN scores (all NaNs rank alike, whatever their payload)
+ *   3. score descending; -0.0 and +0.0 compare equal
+ *   4. shard ascending, then molecule id ascending (signed)
+ *   5. entries alike in all of that keep their order of arrival: the old list first, then the batch by slot
+ * Repeated (shard, molecule) pairs are kept, not de-duplicated.  Score bits are copied, never recomputed (a NaN keeps its
+ * payload, a zero its sign).  A list starts out as K empty slots.
+ *
+ * Launches on `stream` (one launch for B <= 1024, two beyond), capturable; integer comparisons only, no atomics, no
+ * process-wide state; the result is a function of the inputs alone and every output has one writer.  Any B >= 1;
+ * 1 <= K <= MKGNN_TOPK_MAX_K, anything else is rejected (non-zero, mkgnn_last_error), never truncated.  The workspace
+ * (16-byte aligned, mkgnn_topk_workspace_bytes(B, K) bytes; 0 for rejected sizes) needs no initialisation: it is read only where the same call wrote it. */
+#define MKGNN_TOPK_MAX_K 1024
+size_t mkgnn_topk_workspace_bytes(int32_t B, int32_t K);
+int mkgnn_topk_update(const float* scores, const int32_t* ids, int32_t B, const int32_t* n_valid, const int32_t* shard_tag,
+                      int32_t K, float* top_score, int32_t* top_shard, int32_t* top_mol, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

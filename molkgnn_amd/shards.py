@@ -684,12 +684,23 @@ class ResidentLoader:
     padding molecules included (what ``padding.pad_batch`` reports, maximised over the batches).
 
     The epoch's ids are uploaded once; iterating yields one device int32 view per batch for
-    ``padding.CompactStaticBatch.gather``.  On the CPU it yields ``CompactBatch``es filled by ``gather_compact``."""
+    ``padding.CompactStaticBatch.gather``.  On the CPU it yields ``CompactBatch``es filled by ``gather_compact``.
+
+    ``drop_last=False`` (``world == 1`` only) keeps the short tail: the last piece is filled up to ``batch_size`` by repeating
+    its last real id, and ``n_live`` (host int32 array; ``n_live_dev``, a device int32 vector, on a GPU) holds every batch's
+    count of real molecules.  The filler molecules are planned like any other (shape fit, ``max_mol_atoms``,
+    ``max_mol_edges``).  This is for SCORING (``screening.score_resident``): in evaluation mode the batch norm uses its running
+    statistics, so a molecule's score does not depend on its neighbours in the batch and the filler cannot change the real
+    molecules' scores; the consumer ignores the slots from ``n_live`` on.  In training the filler would enter the batch
+    statistics and the loss a second time, which is why a training draw drops the tail (the default)."""
 
     def __init__(self, resident: ResidentShard, batch_size: int, indices, device="cpu", rank: int = 0, world: int = 1,
-                 shape=None, headroom: float = 0.0):
+                 shape=None, headroom: float = 0.0, drop_last: bool = True):
         if not (0 <= rank < world):
             raise ValueError(f"rank {rank} of world {world}")
+        if not drop_last and world != 1:
+            raise ValueError("drop_last=False keeps the tail of ONE stream of batches: it exists for world == 1")
+        self.drop_last = bool(drop_last)
         if headroom < 0:
             raise ValueError("headroom is a non-negative fraction")
         self.resident, self.batch_size, self.device = resident, int(batch_size), torch.device(device)
@@ -705,10 +716,18 @@ class ResidentLoader:
         ids = np.asarray(indices.tolist() if torch.is_tensor(indices) else list(indices), dtype=np.int64).reshape(-1)
         if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= r.n_molecules):
             raise ValueError(f"molecule ids outside [0, {r.n_molecules})")
-        n_all = ids.shape[0] // bs
+        n_all, tail = divmod(ids.shape[0], bs)
+        if tail and not self.drop_last:                                         # the tail, filled up with its last real id
+            ids = np.concatenate([ids, np.full(bs - tail, ids[-1], dtype=np.int64)])
+            n_all += 1
+        else:
+            tail = 0
         batches = ids[:n_all * bs].reshape(n_all, bs)[self.rank::self.world]
         if batches.shape[0] == 0:
             raise ValueError("no full batch for this rank")
+        self.n_live = np.full(batches.shape[0], bs, dtype=np.int32)
+        if tail:
+            self.n_live[-1] = tail
         atoms = r.mol_atoms[batches].sum(axis=1)
         deg = r.mol_deg[batches].sum(axis=1)                                    # [batches, 4]
         if self.shape is None:
@@ -740,8 +759,9 @@ class ResidentLoader:
         self.max_mol_atoms = max(int(r.mol_atoms[batches].max()), pad_atoms)
         self.max_mol_edges = max(2 * int(r.mol_bonds[batches].max()), pad_edges)
         self._batches = batches
-        self._ids_dev = None
+        self._ids_dev = self.n_live_dev = None
         if self.device.type == "cuda":
+            self.n_live_dev = torch.from_numpy(self.n_live).to(self.device, non_blocking=True)
             # (through pinned memory, without waiting: the host plans the next epoch while the device still works on this one)
             self._ids_host = torch.from_numpy(batches.astype(np.int32)).pin_memory()
             self._ids_dev = self._ids_host.to(self.device, non_blocking=True)

@@ -5,7 +5,8 @@ Only what a forward + backward (+ optimiser) step needs is restated here: the mo
 reference's parameter names (``gnn_model.*``, ``lin1``, ``lin2``, ``ffn``; 132 300 parameters), the
 loss the data module selects -- ``BCEWithLogitsLoss()`` for the QSAR assays (``data.py:37``), ``MSELoss(reduction='sum')``
 for the docking-score set (``data.py:49-53``) -- and the AdamW groups chosen by parameter name (``model.py:373-382``).
-Scoring: ``GNNModel.predict`` and ``evaluate`` (the reference's validation / test loop, ``model.py:221-358, 483-522``).
+Scoring: ``GNNModel.predict``, ``evaluate`` (the reference's validation / test loop, ``model.py:221-358, 483-522``) and
+``evaluate_resident`` (the same from a device-resident shard; ranking a library: ``molkgnn_amd.screening``).
 Logging, checkpoints, file output and the LR schedule are out of scope.
 """
 from __future__ import annotations
@@ -207,6 +208,26 @@ def evaluate(model, batches, metrics=()) -> dict:
         return results
     finally:
         model.train(was_training)
+
+
+def evaluate_resident(model, resident, batch_size: int, metrics=()) -> dict:
+    """``evaluate`` for a data set that lives in device memory (``shards.ResidentShard``): the same result dictionary, with
+    ``pred_y`` from ``screening.score_resident`` -- every molecule of the shard in id order, the short tail included, from one
+    captured graph -- and ``true_y`` from ``resident.y``.  Unknown metric names raise before anything is launched; the model
+    comes back in the mode it came in."""
+    from .screening import score_resident
+    table = _metric_functions()
+    unknown = [m for m in metrics if m not in table]
+    if unknown:
+        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(table)}")
+    pred_y = score_resident(model, resident, batch_size)
+    true_y = resident.y.to(pred_y.device).view(-1)
+    with torch.no_grad():
+        results = {'loss': model.loss_func(pred_y, true_y.float())}
+    for m in metrics:
+        results[m] = table[m](true_y, pred_y)
+    results['pred_y'], results['true_y'] = pred_y, true_y
+    return results
 
 
 def tune_torch_backends() -> None:

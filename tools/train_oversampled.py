@@ -4,7 +4,8 @@ sampling.oversampling_sampler (the reference's WeightedRandomSampler: a draw wit
 shards.ResidentLoader (plans the epoch on the host, uploads the ids once) -> ONE captured graph per run: CompactStaticBatch.gather
 (mkgnn_gather_compact: the batch is formed on the device from its id list), expand, receptive fields, index plan, train.training_step
 (forward, backward with deferred bank gradients, FusedAdamW), replayed for every batch of every epoch.  The only per-batch
-traffic from the host is the id list.  The loss must fall and the held-out AUC must rise if every piece is right.
+traffic from the host is the id list.  The held-out set is a resident shard as well, scored by train.evaluate_resident before and
+after.  The loss must fall and the held-out AUC must rise if every piece is right.
 tools/train_oversampled.py [--molecules 16384] [--batch-size 1024] [--epochs 6] [--headroom 0.05]"""
 import argparse
 import os
@@ -15,13 +16,12 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from molkgnn_amd import evaluation as E                                             # noqa: E402
 from molkgnn_amd import padding as P                                                # noqa: E402
 from molkgnn_amd import shards as S                                                 # noqa: E402
 from molkgnn_amd.receptive_field import attach_receptive_fields                     # noqa: E402
 from molkgnn_amd.sampling import oversampling_sampler                               # noqa: E402
 from molkgnn_amd.synthetic import make_batch                                        # noqa: E402
-from molkgnn_amd.train import GNNModel, configure_optimizer, training_step          # noqa: E402
+from molkgnn_amd.train import GNNModel, configure_optimizer, evaluate_resident, training_step   # noqa: E402
 
 
 def labelled(n, seed, min_deg4=3):
@@ -44,7 +44,9 @@ def run(molecules=16384, batch_size=1024, epochs=6, lr=3e-3, headroom=0.05, seed
         sampler = oversampling_sampler(resident.y, seed)
         # the first epoch's shape with some headroom is kept for the run, so that ONE graph serves every later draw
         loader = S.ResidentLoader(resident, batch_size, sampler, dev, headroom=headroom)
-        test = attach_receptive_fields(labelled(2048, 999).to(dev))
+        held_path = os.path.join(d, "held_out.mkgs")
+        S.write_shard(held_path, labelled(2048, 999))
+        held_out = S.ResidentShard(held_path, dev)       # (the held-out set is resident too: scored by train.evaluate_resident)
         model = GNNModel(num_layers=3).to(dev)
         opt = configure_optimizer(model, lr=lr, capturable=True)
         csb = P.CompactStaticBatch(loader.shape, batch_size, resident.x_dim, resident.p_dim, resident.e_dim, dev)
@@ -57,11 +59,8 @@ def run(molecules=16384, batch_size=1024, epochs=6, lr=3e-3, headroom=0.05, seed
             return training_step(model, csb.data, opt)
 
         def evaluate():
-            model.eval()
-            with torch.no_grad():
-                pred, _ = model(test)
-            model.train()
-            return float(E.calculate_logAUC(test.y, pred.view(-1))), float(E.calculate_auc(test.y, pred.view(-1)))
+            r = evaluate_resident(model, held_out, batch_size, metrics=("logAUC_0.001_0.1", "AUC"))
+            return float(r["logAUC_0.001_0.1"]), float(r["AUC"])
 
         before = evaluate()
         side = torch.cuda.Stream()
