@@ -823,6 +823,42 @@ size_t mkgnn_gather_compact_workspace_bytes(int64_t n_ids);
 int mkgnn_gather_compact(const mkgnn_resident_shard* shard, const int32_t* ids, int64_t n_ids, const int64_t shape[6],
                          int32_t pad_molecules, void* wire, size_t wire_bytes, void* workspace, void* stream);
 
+/* ---- the same gather from a shard whose atom features are PACKED (additive; the ABI version stays 8): every column of x whose
+ * values, over the whole shard, are integers in [-128, 127] and never -0.0 is held as one int8, the other columns as fp32, bit
+ * for bit (NaN payloads, infinities, denormals, -0.0).  The decode is exact, so the wire buffer is byte for byte what
+ * mkgnn_gather_compact writes for the same shard held unpacked, and the status word agrees.
+ *
+ * One record of rec_bytes per atom, atom a at x_rec + a * rec_bytes:
+ *   the nf fp32 columns in column order | the nq int8 columns in column order | zero bytes up to a multiple of 4
+ *   rec_bytes = 4 * nf + 4 * ceil(nq / 4)
+ * The column table x_col[x_dim] says where column c lives in the record:
+ *   x_col[c] >= 0   an fp32 at byte offset x_col[c] (a multiple of 4)
+ *   x_col[c] <  0   an int8 at byte offset -x_col[c] - 1
+ * nq == 0 and nf == 0 are both legal.  molkgnn_amd/shards.py::pack_x / unpack_x are the definition.
+ *
+ * x_rec is a DEVICE pointer, 4-byte aligned (the records are read in dwords).  x_col is a HOST pointer: the entry point checks
+ * the table against rec_bytes (every entry inside the record, fp32 offsets multiples of 4, rec_bytes as the layout makes it) and
+ * hands it to the kernel with the launch arguments, so nothing of it is read after the call returns and a captured graph holds
+ * its own copy.  x_dim <= MKGNN_PACKED_MAX_X_DIM.  Everything else -- the other arrays, ids, shape, wire, the workspace
+ * (mkgnn_gather_compact_workspace_bytes) and the status word -- is as for mkgnn_gather_compact. */
+#define MKGNN_PACKED_MAX_X_DIM 160
+typedef struct mkgnn_resident_shard_packed {
+    const uint8_t* x_rec;           /* [n_atoms, rec_bytes] packed records (device) */
+    const int32_t* x_col;           /* [x_dim] column table (HOST) */
+    const float* p;                 /* [n_atoms, p_dim] */
+    const int32_t* bond_ij;         /* [n_bonds, 2] shard-global atom ids, every bond once */
+    const uint8_t* bond_attr;       /* [n_bonds, e_dim] */
+    const float* y;                 /* [n_molecules] */
+    const int32_t* mol_atom_ptr;    /* [n_molecules + 1] */
+    const int32_t* mol_bond_ptr;    /* [n_molecules + 1] */
+    const int32_t* mol_deg;         /* [n_molecules, 4] atoms of degree 1, 2, 3, 4 */
+    int64_t n_molecules;
+    int32_t x_dim, p_dim, e_dim, rec_bytes;
+} mkgnn_resident_shard_packed;
+int mkgnn_gather_compact_packed(const mkgnn_resident_shard_packed* shard, const int32_t* ids, int64_t n_ids,
+                                const int64_t shape[6], int32_t pad_molecules, void* wire, size_t wire_bytes, void* workspace,
+                                void* stream);
+
 /* ---- running top-k on the device (additive; the ABI version stays 8): the ranking of a screen, kept sorted across batches and
  * shards inside the captured scoring step.  The list (top_score, top_shard, top_mol)[K] is updated IN PLACE to the best K entries
  * of the multiset  old list  U  {(scores[i], *shard_tag, ids[i]) : i < min(max(*n_valid, 0), B)}  and is always fully sorted.

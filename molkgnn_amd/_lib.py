@@ -95,6 +95,15 @@ class ResidentShardView(C.Structure):
                 ("x_dim", C.c_int32), ("p_dim", C.c_int32), ("e_dim", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ResidentShardPackedView(C.Structure):
+    """``mkgnn_resident_shard_packed``: ``x_rec`` and the other arrays are DEVICE pointers, ``x_col`` is a HOST pointer
+    (``shards.ResidentShard(..., packed=True)`` keeps the table alive)."""
+    _fields_ = [("x_rec", C.c_void_p), ("x_col", C.c_void_p), ("p", C.c_void_p), ("bond_ij", C.c_void_p), ("bond_attr", C.c_void_p),
+                ("y", C.c_void_p), ("mol_atom_ptr", C.c_void_p), ("mol_bond_ptr", C.c_void_p), ("mol_deg", C.c_void_p),
+                ("n_molecules", C.c_int64), ("x_dim", C.c_int32), ("p_dim", C.c_int32), ("e_dim", C.c_int32), ("rec_bytes", C.c_int32)]
+
+
+PACKED_MAX_X_DIM = 160                          # MKGNN_PACKED_MAX_X_DIM
 TOPK_MAX_K = 1024                               # MKGNN_TOPK_MAX_K
 GATHER_BAD_ID, GATHER_MISFIT = 1, 2             # MKGNN_GATHER_*: bits of the gather's status word
 Int64x6 = C.c_int64 * 6
@@ -159,7 +168,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_tail_fused_readout_dropout", "mkgnn_readout_dropout_mask", "mkgnn_tail_score", "mkgnn_tail_score_workspace_bytes",
            "mkgnn_head_loss_forward", "mkgnn_head_loss_backward", "mkgnn_head_loss_dropout_forward",
            "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused", "mkgnn_gather_compact",
-           "mkgnn_gather_compact_workspace_bytes", "mkgnn_topk_update", "mkgnn_topk_workspace_bytes")
+           "mkgnn_gather_compact_workspace_bytes", "mkgnn_gather_compact_packed", "mkgnn_topk_update", "mkgnn_topk_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -258,6 +267,9 @@ def load() -> C.CDLL:
     lib.mkgnn_gather_compact.restype = C.c_int
     lib.mkgnn_gather_compact.argtypes = [C.POINTER(ResidentShardView), C.c_void_p, C.c_int64, Int64x6, C.c_int32, C.c_void_p,
                                          C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.mkgnn_gather_compact_packed.restype = C.c_int
+    lib.mkgnn_gather_compact_packed.argtypes = [C.POINTER(ResidentShardPackedView), C.c_void_p, C.c_int64, Int64x6, C.c_int32,
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.mkgnn_topk_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_topk_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.mkgnn_topk_update.restype = C.c_int

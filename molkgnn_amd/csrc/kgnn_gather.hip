@@ -11,6 +11,10 @@
 //                       output, so the stores are contiguous and a molecule's rows are read in one run
 // What the device finds wrong goes into the status word (workspace[0]); ids and extents are clamped, so nothing is read
 // outside the shard or written outside the wire fields whatever the ids hold.
+//
+// mkgnn_gather_compact_packed is the same gather from a shard whose atom features are held as packed records
+// (mkgnn_resident_shard_packed; molkgnn_amd/shards.py::pack_x / unpack_x define the form).  The scan kernel is the same kernel;
+// the fill kernel differs in the x field of the atom half only, which it decodes column by column through the column table.
 #include <cstdint>
 #include "kgnn_launch.h"
 #include "../../include/molkgnn_hip.h"
@@ -35,6 +39,13 @@ struct GatherArgs {
     int32_t vec_x, vec_p;           // rows of x / p copied in 16-byte pieces
     float* wx; float* wp; int32_t* wij; uint8_t* wattr; float* wy; int32_t* wmp; int64_t* wnva;
     int32_t* ws;
+};
+
+// the packed form of x: the table travels with the launch (the entry point has checked it), the kernel keeps it in LDS
+struct PackedX {
+    const uint32_t* rec;            // records, read in dwords
+    int32_t rec_dwords;
+    int32_t col[MKGNN_PACKED_MAX_X_DIM];
 };
 
 __device__ __forceinline__ int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
@@ -179,7 +190,64 @@ __device__ __forceinline__ int64_t stub_atom(int64_t s, const int4 need) {
     return n_pad > 0 ? n_pad - 1 : 0;
 }
 
-__global__ void __launch_bounds__(FILL_THREADS) gather_fill_kernel(const GatherArgs a, int atom_blocks) {
+// column c of one record: an fp32 at byte offset e (e >= 0), or the int8 at byte offset -e - 1 (out of its dword by two shifts)
+__device__ __forceinline__ float decode_column(const uint32_t* __restrict__ rec, int32_t e) {
+    if (e >= 0) return __uint_as_float(rec[e >> 2]);
+    const int off = -e - 1;
+    const int32_t b = (int32_t)(rec[off >> 2] << (24 - 8 * (off & 3))) >> 24;
+    return (float)b;
+}
+
+// copy_rows for x out of packed records: the same pieces in the same places (16-byte pieces when VEC), every element decoded
+// through the column table `col` (LDS)
+template <bool VEC>
+__device__ __forceinline__ void decode_rows(float* __restrict__ dst, const PackedX& px, const int32_t* col, int x_dim, int32_t r0,
+                                            int32_t n_rows, int32_t src_row) {
+    const int lane = threadIdx.x & 63;
+    const int units = VEC ? x_dim / 4 : x_dim;
+    for (int i = 0; i < units; ++i) {
+        const int j = lane + 64 * i;
+        const int row = j / units, c = j - row * units;
+        const int32_t sr = __shfl(src_row, row, 64);
+        const uint32_t* const rec = px.rec + (size_t)(sr >= 0 ? sr : 0) * px.rec_dwords;
+        if constexpr (VEC) {
+            float4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (sr >= 0) {
+                v.x = decode_column(rec, col[4 * c]);
+                v.y = decode_column(rec, col[4 * c + 1]);
+                v.z = decode_column(rec, col[4 * c + 2]);
+                v.w = decode_column(rec, col[4 * c + 3]);
+            }
+            if (r0 + row < n_rows) ((float4*)(dst + (size_t)r0 * x_dim))[j] = v;
+        } else {
+            float v = 0.0f;
+            if (sr >= 0) v = decode_column(rec, col[c]);
+            if (r0 + row < n_rows) dst[(size_t)r0 * x_dim + j] = v;
+        }
+    }
+}
+
+// the source atom of this lane's output row r0 + lane (-1: a padding row)
+__device__ __forceinline__ int32_t source_atom(const GatherArgs& a, int32_t r0) {
+    const int lane = threadIdx.x & 63;
+    const int n = a.n;
+    const int32_t* const atom_off = a.ws + GWS_HEAD;
+    const int32_t* const src_atom = atom_off + 2 * (n + 1);
+    const int32_t r = r0 + lane;
+    int32_t sr = -1;
+    if (r < a.ws[GWS_NA]) {
+        const int s = find_slot(atom_off, n, r);
+        sr = src_atom[s] + (r - atom_off[s]);
+    }
+    return sr;
+}
+
+__device__ __forceinline__ void copy_p_rows(const GatherArgs& a, int32_t r0, int32_t sr) {
+    if (a.vec_p) copy_rows<float4>((float4*)a.wp, (const float4*)a.s.p, a.s.p_dim / 4, r0, a.A, sr);
+    else copy_rows<float>(a.wp, a.s.p, a.s.p_dim, r0, a.A, sr);
+}
+
+__device__ __forceinline__ void fill_bond_tile(const GatherArgs& a, int atom_blocks) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = a.n;
     const int32_t* const atom_off = a.ws + GWS_HEAD;
@@ -187,21 +255,6 @@ __global__ void __launch_bounds__(FILL_THREADS) gather_fill_kernel(const GatherA
     const int32_t* const src_atom = bond_off + n + 1;
     const int32_t* const src_bond = src_atom + n;
     const int32_t na = a.ws[GWS_NA], nb = a.ws[GWS_NB];
-    if ((int)blockIdx.x < atom_blocks) {
-        const int32_t r0 = ((int32_t)blockIdx.x * 4 + wave) * 64;
-        if (r0 >= a.A) return;
-        const int32_t r = r0 + lane;
-        int32_t sr = -1;
-        if (r < na) {
-            const int s = find_slot(atom_off, n, r);
-            sr = src_atom[s] + (r - atom_off[s]);
-        }
-        if (a.vec_x) copy_rows<float4>((float4*)a.wx, (const float4*)a.s.x, a.s.x_dim / 4, r0, a.A, sr);
-        else copy_rows<float>(a.wx, a.s.x, a.s.x_dim, r0, a.A, sr);
-        if (a.vec_p) copy_rows<float4>((float4*)a.wp, (const float4*)a.s.p, a.s.p_dim / 4, r0, a.A, sr);
-        else copy_rows<float>(a.wp, a.s.p, a.s.p_dim, r0, a.A, sr);
-        return;
-    }
     const int32_t b0 = (((int32_t)blockIdx.x - atom_blocks) * 4 + wave) * 64;
     if (b0 >= a.B2) return;
     const int32_t b = b0 + lane;
@@ -252,6 +305,30 @@ __global__ void __launch_bounds__(FILL_THREADS) gather_fill_kernel(const GatherA
     }
 }
 
+__global__ void __launch_bounds__(FILL_THREADS) gather_fill_kernel(const GatherArgs a, int atom_blocks) {
+    if ((int)blockIdx.x >= atom_blocks) { fill_bond_tile(a, atom_blocks); return; }
+    const int32_t r0 = ((int32_t)blockIdx.x * 4 + (int32_t)(threadIdx.x >> 6)) * 64;
+    if (r0 >= a.A) return;
+    const int32_t sr = source_atom(a, r0);
+    if (a.vec_x) copy_rows<float4>((float4*)a.wx, (const float4*)a.s.x, a.s.x_dim / 4, r0, a.A, sr);
+    else copy_rows<float>(a.wx, a.s.x, a.s.x_dim, r0, a.A, sr);
+    copy_p_rows(a, r0, sr);
+}
+
+// the same grid for a packed shard: a.s.x is null, x comes out of px
+__global__ void __launch_bounds__(FILL_THREADS) gather_fill_packed_kernel(const GatherArgs a, int atom_blocks, const PackedX px) {
+    if ((int)blockIdx.x >= atom_blocks) { fill_bond_tile(a, atom_blocks); return; }
+    __shared__ int32_t col[MKGNN_PACKED_MAX_X_DIM];
+    if ((int)threadIdx.x < a.s.x_dim) col[threadIdx.x] = px.col[threadIdx.x];
+    __syncthreads();
+    const int32_t r0 = ((int32_t)blockIdx.x * 4 + (int32_t)(threadIdx.x >> 6)) * 64;
+    if (r0 >= a.A) return;
+    const int32_t sr = source_atom(a, r0);
+    if (a.vec_x) decode_rows<true>(a.wx, px, col, a.s.x_dim, r0, a.A, sr);
+    else decode_rows<false>(a.wx, px, col, a.s.x_dim, r0, a.A, sr);
+    copy_p_rows(a, r0, sr);
+}
+
 }  // namespace
 }  // namespace mkgnn
 
@@ -262,11 +339,11 @@ extern "C" size_t mkgnn_gather_compact_workspace_bytes(int64_t n_ids) {
     return up256(((size_t)GWS_HEAD + 4 * (size_t)n_ids + 2) * sizeof(int32_t));
 }
 
-extern "C" int mkgnn_gather_compact(const mkgnn_resident_shard* s, const int32_t* ids, int64_t n_ids, const int64_t shape[6],
-                                    int32_t pad_molecules, void* wire, size_t wire_bytes, void* workspace, void* stream) {
-    const char* who = "mkgnn_gather_compact";
-    if (!s || !ids || !shape || !wire || !workspace) return api_fail("%s: null pointer", who);
-    if (!s->x || !s->p || !s->bond_ij || !s->y || !s->mol_atom_ptr || !s->mol_bond_ptr || !s->mol_deg)
+// the checks, the wire fields and the two launches of both entry points; px: the packed form of x (s->x is not used), or null
+static int gather_launch(const char* who, const mkgnn_resident_shard* s, const PackedX* px, const int32_t* ids, int64_t n_ids,
+                         const int64_t shape[6], int32_t pad_molecules, void* wire, size_t wire_bytes, void* workspace, void* stream) {
+    if (!ids || !shape || !wire || !workspace) return api_fail("%s: null pointer", who);
+    if ((!px && !s->x) || !s->p || !s->bond_ij || !s->y || !s->mol_atom_ptr || !s->mol_bond_ptr || !s->mol_deg)
         return api_fail("%s: a shard array is null", who);
     if (s->n_molecules < 1 || s->x_dim < 1 || s->p_dim < 1 || s->e_dim < 0 || (s->e_dim && !s->bond_attr))
         return api_fail("%s: empty shard or bad feature widths", who);
@@ -284,7 +361,7 @@ extern "C" int mkgnn_gather_compact(const mkgnn_resident_shard* s, const int32_t
     a.A = (int32_t)shape[0]; a.B2 = (int32_t)(shape[1] / 2);
     for (int d = 0; d < 4; ++d) a.target[d] = (int32_t)shape[2 + d];
     a.pad_molecules = pad_molecules;
-    a.vec_x = s->x_dim % 4 == 0 && (uintptr_t)s->x % 16 == 0;
+    a.vec_x = s->x_dim % 4 == 0 && (px || (uintptr_t)s->x % 16 == 0);
     a.vec_p = s->p_dim % 4 == 0 && (uintptr_t)s->p % 16 == 0;
     const size_t A = (size_t)a.A, B2 = (size_t)a.B2, G = (size_t)n_ids + (size_t)pad_molecules;
     char* o = (char*)wire;
@@ -299,9 +376,54 @@ extern "C" int mkgnn_gather_compact(const mkgnn_resident_shard* s, const int32_t
     hipStream_t st = (hipStream_t)stream;
     gather_scan_kernel<<<1, SCAN_THREADS, 0, st>>>(a);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_hip_fail("mkgnn_gather_compact: scan launch", e);
+    if (e != hipSuccess) return api_hip_fail(px ? "mkgnn_gather_compact_packed: scan launch" : "mkgnn_gather_compact: scan launch", e);
     const int atom_blocks = (int)((A + FILL_ROWS - 1) / FILL_ROWS), bond_blocks = (int)((B2 + FILL_ROWS - 1) / FILL_ROWS);
-    gather_fill_kernel<<<atom_blocks + bond_blocks, FILL_THREADS, 0, st>>>(a, atom_blocks);
+    if (px) gather_fill_packed_kernel<<<atom_blocks + bond_blocks, FILL_THREADS, 0, st>>>(a, atom_blocks, *px);
+    else gather_fill_kernel<<<atom_blocks + bond_blocks, FILL_THREADS, 0, st>>>(a, atom_blocks);
     e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail("mkgnn_gather_compact: fill launch", e);
+    return e == hipSuccess ? 0 : api_hip_fail(px ? "mkgnn_gather_compact_packed: fill launch" : "mkgnn_gather_compact: fill launch", e);
+}
+
+extern "C" int mkgnn_gather_compact(const mkgnn_resident_shard* s, const int32_t* ids, int64_t n_ids, const int64_t shape[6],
+                                    int32_t pad_molecules, void* wire, size_t wire_bytes, void* workspace, void* stream) {
+    const char* who = "mkgnn_gather_compact";
+    if (!s) return api_fail("%s: null pointer", who);
+    return gather_launch(who, s, nullptr, ids, n_ids, shape, pad_molecules, wire, wire_bytes, workspace, stream);
+}
+
+extern "C" int mkgnn_gather_compact_packed(const mkgnn_resident_shard_packed* s, const int32_t* ids, int64_t n_ids,
+                                           const int64_t shape[6], int32_t pad_molecules, void* wire, size_t wire_bytes,
+                                           void* workspace, void* stream) {
+    const char* who = "mkgnn_gather_compact_packed";
+    if (!s) return api_fail("%s: null pointer", who);
+    if (!s->x_rec || !s->x_col) return api_fail("%s: a shard array is null", who);
+    if (s->x_dim < 1 || s->x_dim > MKGNN_PACKED_MAX_X_DIM)
+        return api_fail("%s: x_dim = %d, a packed shard holds 1 .. %d columns", who, (int)s->x_dim, MKGNN_PACKED_MAX_X_DIM);
+    if ((uintptr_t)s->x_rec % 4) return api_fail("%s: x_rec must be 4-byte aligned (the records are read in dwords)", who);
+    // the table against the record: every entry inside it, floats on dword boundaries, and the record exactly as long as the
+    // layout makes it (nf floats, nq bytes, padded to a dword)
+    PackedX px;
+    int nf = 0, nq = 0;
+    for (int c = 0; c < s->x_dim; ++c) {
+        const int32_t e = s->x_col[c];
+        if (e >= 0) {
+            if (e % 4 || (int64_t)e + 4 > s->rec_bytes) return api_fail("%s: x_col[%d] = %d: no fp32 of the record", who, c, (int)e);
+            ++nf;
+        } else {
+            if (-(int64_t)e - 1 >= s->rec_bytes) return api_fail("%s: x_col[%d] = %d: no byte of the record", who, c, (int)e);
+            ++nq;
+        }
+        px.col[c] = e;
+    }
+    for (int c = s->x_dim; c < MKGNN_PACKED_MAX_X_DIM; ++c) px.col[c] = 0;
+    if (s->rec_bytes != 4 * nf + 4 * ((nq + 3) / 4))
+        return api_fail("%s: rec_bytes = %d, the table's %d fp32 and %d int8 columns make %d", who, (int)s->rec_bytes, nf, nq,
+                        4 * nf + 4 * ((nq + 3) / 4));
+    px.rec = (const uint32_t*)s->x_rec;
+    px.rec_dwords = s->rec_bytes / 4;
+    mkgnn_resident_shard u;
+    u.x = nullptr; u.p = s->p; u.bond_ij = s->bond_ij; u.bond_attr = s->bond_attr; u.y = s->y;
+    u.mol_atom_ptr = s->mol_atom_ptr; u.mol_bond_ptr = s->mol_bond_ptr; u.mol_deg = s->mol_deg;
+    u.n_molecules = s->n_molecules; u.x_dim = s->x_dim; u.p_dim = s->p_dim; u.e_dim = s->e_dim; u.reserved = 0;
+    return gather_launch(who, &u, &px, ids, n_ids, shape, pad_molecules, wire, wire_bytes, workspace, stream);
 }

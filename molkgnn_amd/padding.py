@@ -218,9 +218,11 @@ class CompactStaticBatch:
         s = self.shape
         shape6 = _lib.Int64x6(s["atoms"], s["edges"], s["n1"], s["n2"], s["n3"], s["n4"])
         with torch.cuda.device(self.wire.device):
-            _lib.check(lib.mkgnn_gather_compact(resident.view, self.ids.data_ptr(), self.num_molecules, shape6, PAD_MOLECULES,
-                                                self.wire.data_ptr(), self.wire.numel(), self._gather_ws.data_ptr(),
-                                                _lib.stream_ptr(self.wire.device)), "mkgnn_gather_compact")
+            # (a packed shard -- ResidentShard(..., packed=True) -- decodes x inside the gather: the same wire bytes)
+            fn, who = (lib.mkgnn_gather_compact_packed, "mkgnn_gather_compact_packed") if getattr(resident, "packed", False) \
+                else (lib.mkgnn_gather_compact, "mkgnn_gather_compact")
+            _lib.check(fn(resident.view, self.ids.data_ptr(), self.num_molecules, shape6, PAD_MOLECULES, self.wire.data_ptr(),
+                          self.wire.numel(), self._gather_ws.data_ptr(), _lib.stream_ptr(self.wire.device)), who)
 
     def gather_status(self) -> int:
         """The status word of the LAST gather (a host read: once per epoch, not per batch): 0, or ``_lib.GATHER_BAD_ID`` (an id

@@ -635,6 +635,71 @@ class ShardLoader:
                     consumed[slot] = done
 
 
+def classify_x_columns(x) -> np.ndarray:
+    """``bool[x_dim]``: column ``c`` of ``x`` (float32 ``[A, x_dim]``) is a BYTE column iff every value ``v`` in it is an integer
+    (``v == rint(v)``: NaN fails), lies in ``[-128, 127]`` (the infinities fail) and is not ``-0.0`` (bits ``0x80000000``: an int8
+    zero would come back as ``+0.0``).  Such a column survives the trip through int8 bit for bit; any other stays fp32."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("x must be [atoms, x_dim]")
+    ok = (x == np.rint(x)) & (x >= -128.0) & (x <= 127.0) & (x.view(np.uint32) != 0x80000000)
+    return ok.all(axis=0)
+
+
+def packed_x_layout(byte_cols):
+    """``(x_col int32[x_dim], rec_bytes)`` of the packed record for the byte-column mask ``byte_cols``: first the ``nf`` fp32
+    columns in column order, then the ``nq`` int8 columns in column order, then zero bytes to a multiple of 4
+    (``rec_bytes = 4 nf + 4 ceil(nq / 4)``).  ``x_col[c] >= 0``: fp32 at that byte offset; ``x_col[c] < 0``: int8 at byte offset
+    ``-x_col[c] - 1``."""
+    byte_cols = np.asarray(byte_cols, dtype=bool).reshape(-1)
+    nq = int(byte_cols.sum())
+    nf = int(byte_cols.shape[0]) - nq
+    x_col = np.empty(byte_cols.shape[0], dtype=np.int32)
+    x_col[~byte_cols] = 4 * np.arange(nf, dtype=np.int32)
+    x_col[byte_cols] = -(4 * nf + np.arange(nq, dtype=np.int32)) - 1
+    return x_col, 4 * nf + 4 * ((nq + 3) // 4)
+
+
+def pack_x(x, byte_cols=None):
+    """``(records uint8[A, rec_bytes], x_col)``: ``x`` with its byte columns (``classify_x_columns``; or a GIVEN mask ``byte_cols``,
+    e.g. to pack the shards of one library alike -- a column forced to byte that does not pass the rule raises) held as int8 and
+    the others as fp32, one contiguous record per atom (``packed_x_layout``).  Together with ``unpack_x`` the definition of what
+    ``mkgnn_gather_compact_packed`` decodes."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    fits = classify_x_columns(x)
+    if byte_cols is None:
+        byte_cols = fits
+    else:
+        byte_cols = np.asarray(byte_cols, dtype=bool).reshape(-1)
+        if byte_cols.shape[0] != x.shape[1]:
+            raise ValueError(f"byte_cols has {byte_cols.shape[0]} entries, x has {x.shape[1]} columns")
+        bad = np.nonzero(byte_cols & ~fits)[0]
+        if bad.size:
+            raise ValueError(f"columns {bad.tolist()} hold values that an int8 does not carry bit for bit")
+    x_col, rec_bytes = packed_x_layout(byte_cols)
+    nf = int((~byte_cols).sum())
+    nq = x.shape[1] - nf
+    records = np.zeros((x.shape[0], rec_bytes), dtype=np.uint8)
+    records[:, :4 * nf] = np.ascontiguousarray(x[:, ~byte_cols]).view(np.uint8).reshape(x.shape[0], 4 * nf)
+    records[:, 4 * nf:4 * nf + nq] = x[:, byte_cols].astype(np.int8).view(np.uint8)
+    return records, x_col
+
+
+def unpack_x(records, x_col, x_dim: int) -> np.ndarray:
+    """``float32[A, x_dim]`` out of packed records: fp32 columns bit for bit, int8 columns converted."""
+    records = np.ascontiguousarray(records, dtype=np.uint8)
+    x_col = np.asarray(x_col, dtype=np.int64).reshape(-1)
+    if x_col.shape[0] != x_dim:
+        raise ValueError(f"the column table has {x_col.shape[0]} entries for x_dim {x_dim}")
+    out = np.empty((records.shape[0], x_dim), dtype=np.float32)
+    for c, e in enumerate(x_col.tolist()):
+        if e >= 0:
+            out[:, c] = np.ascontiguousarray(records[:, e:e + 4]).view(np.float32)[:, 0]
+        else:
+            out[:, c] = records[:, -e - 1].view(np.int8)
+    return out
+
+
 class ResidentShard:
     """One ``compact_ok`` shard held in device memory in the layout of ``mkgnn_resident_shard``: features and coordinates as
     they are, every bond once (the even-indexed directed edges) as shard-global int32 endpoints with uint8 attributes, labels,
@@ -642,9 +707,16 @@ class ResidentShard:
     ANY list of its molecules on the device (``mkgnn_gather_compact``), so the only per-batch traffic from the host is the
     id list.  The host keeps the per-molecule counts (``mol_atoms``, ``mol_bonds``, ``mol_deg``) for planning and ``y`` for a
     sampler: ``sampling.oversampling_sampler(resident.y, seed)``.  With ``device="cpu"`` nothing is uploaded (the loader's CPU
-    path gathers with ``gather_compact``)."""
+    path gathers with ``gather_compact``).
 
-    def __init__(self, shard_or_path, device="cpu"):
+    ``packed=True`` holds ``x`` as packed records (``pack_x``: the columns whose values are byte-sized integers over the whole
+    shard as int8, the others as fp32) in the layout of ``mkgnn_resident_shard_packed``; the gather decodes them
+    (``mkgnn_gather_compact_packed``) into the same wire bytes, so everything downstream is unchanged.  ``x_col``, ``rec_bytes``
+    and ``byte_columns`` (the column numbers held as int8) say what was done, ``byte_cols`` forces a mask (``pack_x``), and
+    ``nbytes()`` is the device footprint of this form.  The host-side records stay in ``x_rec`` (on the CPU, too, where the loader
+    still gathers from the shard itself)."""
+
+    def __init__(self, shard_or_path, device="cpu", packed: bool = False, byte_cols=None):
         sh = shard_or_path if isinstance(shard_or_path, Shard) else Shard(str(shard_or_path))
         if not sh.compact_ok:
             raise ValueError(f"{sh.path}: bonds are not reversed pairs with shared byte-valued attributes: no compact form")
@@ -657,19 +729,41 @@ class ResidentShard:
         self.mol_deg = np.ascontiguousarray(np.diff(sh.mol_deg_ptr, axis=0)[:, :4])
         self.y = torch.from_numpy(np.array(sh.y))
         self.tensors, self.view = {}, None
+        self.packed = bool(packed)
+        self.x_col = self.x_rec = self.rec_bytes = self.byte_columns = None
+        if byte_cols is not None and not self.packed:
+            raise ValueError("byte_cols is the column mask of the packed form: packed=True is required")
+        if self.packed:
+            from . import _lib
+            if sh.x_dim > _lib.PACKED_MAX_X_DIM:
+                raise ValueError(f"{sh.path}: a packed shard holds at most {_lib.PACKED_MAX_X_DIM} feature columns, not {sh.x_dim}")
+            self.x_rec, self.x_col = pack_x(sh.x, byte_cols)
+            self.rec_bytes = int(self.x_rec.shape[1])
+            self.byte_columns = np.nonzero(self.x_col < 0)[0].tolist()
         if self.device.type == "cuda":
             from . import _lib
             host = {"x": sh.x, "p": sh.p, "bond_ij": np.stack([sh.edge_src[0::2], sh.edge_dst[0::2]], axis=1),
                     "bond_attr": sh.edge_attr[0::2].astype(np.uint8), "y": sh.y,
                     "mol_atom_ptr": sh.mol_atom_ptr.astype(np.int32), "mol_bond_ptr": (sh.mol_edge_ptr // 2).astype(np.int32),
                     "mol_deg": self.mol_deg.astype(np.int32)}
+            if self.packed:
+                del host["x"]
+                host["x_rec"] = self.x_rec
             self.tensors = {k: torch.from_numpy(np.array(v)).to(self.device) for k, v in host.items()}     # (np.array: a writable copy of the map)
-            self.view = _lib.ResidentShardView()
+            self.view = _lib.ResidentShardPackedView() if self.packed else _lib.ResidentShardView()
             for k, t in self.tensors.items():
                 setattr(self.view, k, t.data_ptr())
             self.view.n_molecules, self.view.x_dim, self.view.p_dim, self.view.e_dim = sh.n_molecules, sh.x_dim, sh.p_dim, sh.e_dim
+            if self.packed:
+                self.view.x_col, self.view.rec_bytes = self.x_col.ctypes.data, self.rec_bytes       # (a host pointer: self.x_col lives as long)
 
     def nbytes(self) -> int:
+        """Bytes of device memory the shard takes (0 for an unpacked shard on the CPU, which uploads nothing; the packed form
+        reports its device footprint wherever it is)."""
+        if self.packed:
+            sh = self.shard
+            m, a, nb = sh.n_molecules, sh.n_atoms, sh.n_edges // 2
+            return a * self.rec_bytes + 4 * a * sh.p_dim + 8 * nb + nb * sh.e_dim + 4 * m + 2 * 4 * (m + 1) + 16 * m
         return sum(t.numel() * t.element_size() for t in self.tensors.values())
 
 

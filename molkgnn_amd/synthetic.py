@@ -212,6 +212,40 @@ def make_batch(num_molecules: int, seed: int, *, assay: str = "1798",
     return out
 
 
+REFERENCE_BYTE_COLUMNS = 20       # of NODE_DIM: 12 element one-hots, 4 degree one-hots, formal charge, ring flag, aromatic flag, valence
+
+
+def with_reference_features(batch: GraphBatch, seed: int = 0) -> GraphBatch:
+    """Rewrite ``batch.x`` (in place; the batch is returned) with the column pattern of the reference's atom featuriser
+    (``wrapper.py:45-100``) -- ``make_batch`` draws every column from a normal distribution, which is what the kernels are
+    measured on but holds no byte-valued column:
+
+    * columns 0-11: a one-hot of the element (12 classes);
+    * columns 12-15: a one-hot of the atom's degree 1..4, from the batch's own graph (all zero for any other degree);
+    * column 16: formal charge in {-1, 0, 1}; columns 17, 18: ring and aromatic flags; column 19: explicit valence in 1..6;
+    * columns 20-27: fp32 draws (mass, charges, Crippen terms, TPSA, ASA, EState in the reference).
+
+    Columns 0-19 (``REFERENCE_BYTE_COLUMNS``) are what ``shards.classify_x_columns`` finds byte-valued.  The draws come from a
+    generator of their own: nothing else in the batch changes."""
+    n = int(batch.x.shape[0])
+    if int(batch.x.shape[1]) != NODE_DIM:
+        raise ValueError(f"the reference pattern has {NODE_DIM} columns, the batch has {int(batch.x.shape[1])}")
+    rng = np.random.default_rng([int(seed), 0xA70])
+    x = np.zeros((n, NODE_DIM), dtype=np.float32)
+    rows = np.arange(n)
+    x[rows, rng.choice(12, size=n, p=[0.55, 0.12, 0.14, 0.04, 0.03, 0.03, 0.02, 0.02, 0.02, 0.01, 0.01, 0.01])] = 1.0
+    deg = np.bincount(batch.edge_index[0].detach().cpu().numpy(), minlength=n)
+    in_bucket = (deg >= 1) & (deg <= 4)
+    x[rows[in_bucket], 11 + deg[in_bucket]] = 1.0
+    x[:, 16] = rng.choice([-1.0, 0.0, 1.0], size=n, p=[0.03, 0.94, 0.03])
+    x[:, 17] = rng.random(n) < 0.5
+    x[:, 18] = rng.random(n) < 0.4
+    x[:, 19] = rng.integers(1, 7, size=n)
+    x[:, REFERENCE_BYTE_COLUMNS:] = rng.standard_normal((n, NODE_DIM - REFERENCE_BYTE_COLUMNS)).astype(np.float32)
+    batch.x = torch.from_numpy(x).to(batch.x.device)
+    return batch
+
+
 def docking_scores(seed: int, n_atoms: np.ndarray, batch_vec: np.ndarray, degree: np.ndarray, x: np.ndarray) -> np.ndarray:
     """A docking-like score per molecule (kcal/mol-shaped: about -8 +- 1.5, lower for larger and more branched
     molecules) from its atom count, the share of its atoms with three or four bonds and its mean first atom feature, plus

@@ -4,7 +4,13 @@ data bench.py uses.  Per batch size (4096 and 256 molecules):
       fields -> plan -> forward + backward + AdamW, one graph),
   (b) the same captured step fed by ShardLoader(fixed_shape=True, compact=True) from contiguous shards (host staging + one
       host-to-device copy per batch), timed in the same run, windows alternating with (a),
-  (c) the gather alone (HIP events around runs of launches) next to a device-to-device copy of a buffer of the wire form's size.
+  (c) the gather alone (HIP events around runs of launches) next to a device-to-device copy of a buffer of the wire form's size,
+  (d) the packed form of the resident shard (ResidentShard(..., packed=True): byte-valued feature columns as int8, decoded by
+      mkgnn_gather_compact_packed) in the same run: its captured step in windows alternating with (a) and (b), its gather alone in
+      windows alternating with (c)'s, and the wall time of ResidentShard(...) -- host packing plus upload, what a streamed screen
+      pays per shard -- in both forms, alternating.
+The atom features carry the reference's column pattern (synthetic.with_reference_features: 20 byte-valued columns of 28), so
+that the packed form has something to pack; their values do not enter any of the times.
 Five windows each; median, min and max are reported.  One JSON line at the end.
 tools/resident_epoch_timing.py [--batch-sizes 4096,256] [--batches 16] [--out FILE]"""
 import argparse
@@ -21,7 +27,7 @@ from molkgnn_amd import padding as P                                            
 from molkgnn_amd import shards as S                                                 # noqa: E402
 from molkgnn_amd.receptive_field import GraphBatch, attach_receptive_fields         # noqa: E402
 from molkgnn_amd.sampling import oversampling_sampler                               # noqa: E402
-from molkgnn_amd.synthetic import make_batch                                        # noqa: E402
+from molkgnn_amd.synthetic import make_batch, with_reference_features               # noqa: E402
 from molkgnn_amd.train import GNNModel, configure_optimizer, training_step          # noqa: E402
 
 
@@ -56,7 +62,8 @@ def stats(ws):
 
 
 def run(B, nb, dev, log):
-    raws = [make_batch(B, seed=1798 * 1000 + 500 + i, assay="1798", with_receptive_fields=False) for i in range(nb)]
+    raws = [with_reference_features(make_batch(B, seed=1798 * 1000 + 500 + i, assay="1798", with_receptive_fields=False), seed=i)
+            for i in range(nb)]
     for i, r in enumerate(raws):
         r.y = ((torch.arange(B) + i) % 50 == 0).float()                     # (2 % active: the sampler has something to balance)
     out = {"batch_size": B, "batches_per_epoch": nb}
@@ -64,7 +71,20 @@ def run(B, nb, dev, log):
         paths = S.write_shards(d, raws)
         whole = os.path.join(d, "whole.mkgs")
         S.write_shard(whole, concat(raws))
+        # (d) construction, both forms alternating: the first pair warms up (the shard file's pages, the allocator)
+        build = {"unpacked": [], "packed": []}
+        for w in range(4):
+            for name, packed in (("unpacked", False), ("packed", True)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                r = S.ResidentShard(whole, dev, packed=packed)
+                torch.cuda.synchronize()
+                if w:
+                    build[name].append(1e3 * (time.perf_counter() - t0))
+                del r
+        out["d_construct_ms"] = {k: stats(v) for k, v in build.items()}
         resident = S.ResidentShard(whole, dev)
+        resident_p = S.ResidentShard(whole, dev, packed=True)
         sampler = oversampling_sampler(resident.y, 0)
         # five draws, made up front so that the shape (and with it the one graph) covers all of them; each timed window
         # re-plans and uploads them one after the other
@@ -73,11 +93,14 @@ def run(B, nb, dev, log):
         sl = S.ShardLoader(paths * 5, B, device=dev, prefetch=3, workers=3, fixed_shape=True, compact=True)
         dims = (resident.x_dim, resident.p_dim, resident.e_dim)
         out["resident_shard_bytes"] = resident.nbytes()
+        out["packed_shard_bytes"] = resident_p.nbytes()
+        out["packed_rec_bytes"], out["packed_byte_columns"] = resident_p.rec_bytes, len(resident_p.byte_columns)
         out["ids_bytes_per_batch"] = 4 * B
         torch.manual_seed(0)
         model = GNNModel().to(dev)
         opt = configure_optimizer(model, lr=1e-3, capturable=True)
         csb_r = P.CompactStaticBatch(rl.shape, B, *dims, dev, max_mol_atoms=rl.max_mol_atoms, max_mol_edges=rl.max_mol_edges)
+        csb_p = P.CompactStaticBatch(rl.shape, B, *dims, dev, max_mol_atoms=rl.max_mol_atoms, max_mol_edges=rl.max_mol_edges)
         csb_s = P.CompactStaticBatch(sl.shape, B, *dims, dev)
         out["wire_bytes_per_batch"] = {"resident": int(csb_r.wire.numel()), "shard_fed": int(csb_s.wire.numel())}
 
@@ -88,16 +111,18 @@ def run(B, nb, dev, log):
 
         csb_r.gather(resident, next(iter(rl)))
         g_r = capture(lambda: (csb_r.gather(resident), tail(csb_r)))
+        csb_p.gather(resident_p, next(iter(rl)))
+        g_p = capture(lambda: (csb_p.gather(resident_p), tail(csb_p)))
         csb_s.load(next(iter(sl)))
         g_s = capture(lambda: tail(csb_s))
 
-        def epoch_resident():
+        def epoch_resident(csb=csb_r, g=g_r):
             n = 0
             for draw in draws:
                 rl.set_epoch(draw)                                          # (planning and the id upload are inside the window)
                 for ids in rl:
-                    csb_r.ids.copy_(ids, non_blocking=True)
-                    g_r.replay()
+                    csb.ids.copy_(ids, non_blocking=True)
+                    g.replay()
                     n += 1
             return n
 
@@ -109,39 +134,46 @@ def run(B, nb, dev, log):
                 n += 1
             return n
 
-        wins = {"resident": [], "shard_fed": []}
-        for w in range(6):                                                  # window 0 warms both paths up
-            for name, fn in (("resident", epoch_resident), ("shard_fed", epoch_shards)):
+        wins = {"resident": [], "resident_packed": [], "shard_fed": []}
+        for w in range(6):                                                  # window 0 warms the paths up
+            for name, fn in (("resident", epoch_resident), ("resident_packed", lambda: epoch_resident(csb_p, g_p)),
+                             ("shard_fed", epoch_shards)):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 n = fn()
                 torch.cuda.synchronize()
                 if w:
                     wins[name].append(1e3 * (time.perf_counter() - t0) / n)
-        if csb_r.gather_status():
-            raise RuntimeError(f"gather status {csb_r.gather_status()}")
+        if csb_r.gather_status() or csb_p.gather_status():
+            raise RuntimeError(f"gather status {csb_r.gather_status()} / packed {csb_p.gather_status()}")
+        if not torch.equal(csb_r.wire, csb_p.wire):                         # (both ended on the same batch of the same draw)
+            raise RuntimeError("the packed gather's wire buffer differs from the unpacked gather's")
         out["a_resident_ms_per_step"] = stats(wins["resident"])
+        out["d_resident_packed_ms_per_step"] = stats(wins["resident_packed"])
         out["b_shard_fed_ms_per_step"] = stats(wins["shard_fed"])
         out["steps_per_window"] = {"resident": len(draws) * len(rl), "shard_fed": len(sl)}
         # (c) the gather alone against a copy of the same bytes
         src = torch.empty_like(csb_r.wire)
         reps = 200
 
-        def timed(fn):
-            ws = []
+        def timed(fns):
+            """Windows of `reps` launches of each of `fns`, alternating; window 0 warms up."""
+            ws = {k: [] for k in fns}
             for w in range(6):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(reps):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                if w:
-                    ws.append(1e3 * e0.elapsed_time(e1) / reps)
-            return stats(ws)
+                for k, fn in fns.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(reps):
+                        fn()
+                    e1.record()
+                    e1.synchronize()
+                    if w:
+                        ws[k].append(1e3 * e0.elapsed_time(e1) / reps)
+            return {k: stats(v) for k, v in ws.items()}
 
-        out["c_gather_us"] = timed(lambda: csb_r.gather(resident))
-        out["c_copy_us"] = timed(lambda: src.copy_(csb_r.wire))
+        t = timed({"gather": lambda: csb_r.gather(resident), "gather_packed": lambda: csb_p.gather(resident_p),
+                   "copy": lambda: src.copy_(csb_r.wire)})
+        out["c_gather_us"], out["d_gather_packed_us"], out["c_copy_us"] = t["gather"], t["gather_packed"], t["copy"]
         sl.close()
     log(json.dumps(out))
     return out

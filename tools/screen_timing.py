@@ -2,13 +2,17 @@
 shards, with K = 1024.
 
     python tools/screen_timing.py [--batches 256 4096] [--k 1024] [--shard-batches 4] [--steps 32] [--windows 5] [--timeout 300]
+                                  [--packed]
 
 Per batch size the same captured step (gather, expand, receptive fields, the model's scoring, scatter) is timed three ways:
 ``none`` (no ranking), ``hip`` (``TopK.update``: ``mkgnn_topk_update``) and ``torch`` (the PyTorch formulation in its place:
 ``torch.cat`` of the running and the batch triples, two stable sorts by the same key, the first K copied back).  ``ms_per_batch`` is
 the median of ``--windows`` windows of ``--steps`` replays each (device events; the replays cycle over the shard's batches, so the
 list is in its steady state: most of a batch ranks behind it), every window is in the line.  Each variant runs in a child
-process of its own under ``timeout -k``; nothing is started after a child that failed.  The last line holds the summary."""
+process of its own under ``timeout -k``; nothing is started after a child that failed.  The last line holds the summary.
+``--packed`` writes the library with the reference's feature column pattern (``synthetic.with_reference_features``) and holds it as
+``ResidentShard(..., packed=True)``: the same three variants, fed by ``mkgnn_gather_compact_packed``; every line says which form it is
+and how many bytes the shard takes on the device."""
 from __future__ import annotations
 
 import argparse
@@ -50,7 +54,7 @@ def torch_ranker(topk, tag: int):
     return rank
 
 
-def child(variant, shard_path, batches, k, steps, windows, warmup):
+def child(variant, shard_path, batches, k, steps, windows, warmup, packed=False):
     import torch
     sys.path.insert(0, REPO)
     from molkgnn_amd import shards as S
@@ -58,7 +62,7 @@ def child(variant, shard_path, batches, k, steps, windows, warmup):
     from molkgnn_amd.train import GNNModel, tune_torch_backends
     dev = torch.device("cuda:0")
     tune_torch_backends()
-    resident = S.ResidentShard(shard_path, dev)
+    resident = S.ResidentShard(shard_path, dev, packed=packed)
     torch.manual_seed(0)
     model = GNNModel().to(dev).eval()
     for B in batches:
@@ -85,6 +89,7 @@ def child(variant, shard_path, batches, k, steps, windows, warmup):
         top = topk.result()
         print(json.dumps({"batch": B, "variant": variant, "k": k, "ms_per_batch": round(statistics.median(ms), 5),
                           "windows_ms": [round(v, 5) for v in ms], "steps": steps, "batches_in_shard": nb, "occupied": top[3],
+                          "packed": bool(packed), "shard_bytes": resident.nbytes(),
                           "top_score_sum": float(top[0][:top[3]].double().sum()), "top_mol_sum": int(top[2][:top[3]].sum())}), flush=True)
         del scoring
 
@@ -112,24 +117,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=1, help="the variants alternate this many times")
     ap.add_argument("--timeout", type=int, default=300, help="seconds per child process")
+    ap.add_argument("--packed", action="store_true", help="hold the library with its byte-valued feature columns packed as int8")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     ap.add_argument("--shard", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        child(a.child, a.shard, a.batches, a.k, a.steps, a.windows, a.warmup)
+        child(a.child, a.shard, a.batches, a.k, a.steps, a.windows, a.warmup, a.packed)
         return
     sys.path.insert(0, REPO)
     from molkgnn_amd import shards as S
-    from molkgnn_amd.synthetic import make_batch
+    from molkgnn_amd.synthetic import make_batch, with_reference_features
     lines = []
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "library.mkgs")
-        S.write_shard(path, make_batch(a.shard_batches * max(a.batches), seed=1798000, assay="1798", with_receptive_fields=False))
+        library = make_batch(a.shard_batches * max(a.batches), seed=1798000, assay="1798", with_receptive_fields=False)
+        S.write_shard(path, with_reference_features(library) if a.packed else library)
         for rnd in range(a.rounds):
             for variant in VARIANTS:
                 cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", variant, "--shard", path,
                        "--k", str(a.k), "--steps", str(a.steps), "--windows", str(a.windows), "--warmup", str(a.warmup), "--batches",
-                       *map(str, a.batches)]
+                       *map(str, a.batches)] + (["--packed"] if a.packed else [])
                 done = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
                 sys.stdout.write(done.stdout)
                 sys.stdout.flush()
