@@ -880,7 +880,7 @@ int mkgnn_batchnorm_forward_with_stats(const float* x, int64_t x_stride, int64_t
         if (int rc = bn_side_setup("mkgnn_batchnorm_forward", companion, companion_ws, companion_ws_bytes, a.side)) return rc;
         if ((int64_t)companion->n_rows * a.side.CL <= 64 * 1024) { a.side.nblk = 1; side_single = true; }
     }
-    static const bool one_launch = [] { const char* e = getenv("MKGNN_BN_ONE_LAUNCH"); return e && e[0] == '1'; }();      // (opt-in: it lost)
+    const bool one_launch = switches().bn_one_launch;    // (opt-in: it lost)
     if (training && one_launch) {                        // statistics | grid barrier | apply  (MKGNN_BN_ONE_LAUNCH=0: two launches)
         if (bn_vec_rows(x, x_stride, C)) bn_forward_fused_kernel<true><<<BN_BLOCKS + a.side.nblk, 256, 0, st>>>(a, CL);
         else bn_forward_fused_kernel<false><<<BN_BLOCKS + a.side.nblk, 256, 0, st>>>(a, CL);
@@ -925,7 +925,7 @@ int mkgnn_batchnorm_backward(const float* grad_out, int64_t grad_out_stride, con
     a.part1 = (float*)ws; a.part2 = a.part1 + (size_t)BN_BLOCKS * C;
     a.gout = grad_out; a.gos = grad_out_stride; a.gx = grad_x; a.gxs = grad_x_stride;
     a.gweight = grad_weight; a.gbias = grad_bias; a.nvalid = n_valid_rows;
-    static const bool one_launch = [] { const char* e = getenv("MKGNN_BN_ONE_LAUNCH"); return e && e[0] == '1'; }();      // (opt-in: it lost)
+    const bool one_launch = switches().bn_one_launch;    // (opt-in: it lost)
     const bool vec = bn_vec_rows(x, x_stride, C) && bn_vec_rows(grad_out, grad_out_stride, C) && (!grad_x || bn_vec_rows(grad_x, grad_x_stride, C));
     if (one_launch && grad_x) {                          // partial sums | grid barrier | gradient rows
         if (vec) bn_backward_fused_kernel<true><<<BN_BLOCKS, 256, 0, st>>>(a, CL);

@@ -483,10 +483,10 @@ __global__ void __launch_bounds__(512) kc_backward_bank_fused(BankFusedArgs fa) 
 // ------------------------------------------------------------------ host ---
 static size_t rows_lds_bytes(int d, int FP, int L) { return ((size_t)(d + 1) * L * FP + 2 * 32 * (size_t)L + 2 * 32) * 4; }
 
-bool lds_backward_supported(int d, int F, int E, int L, int64_t xs, const void* x) {
+bool lds_backward_supported(int d, int F, int E, int L, int64_t xs, bool x_aligned) {
     if (d < 1 || d > 4 || L < 1 || E > 8 || (F & 1)) return false;
     const int FP = mfma_padded_width(F);
-    if (!FP || xs % 4 != 0 || ((uintptr_t)x & 15)) return false;
+    if (!FP || xs % 4 != 0 || !x_aligned) return false;
     if (L > 8 * bank_li(d) || 32 * L > 256 * rows_cq(d)) return false;
     return rows_lds_bytes(d, FP, L) <= 160 * 1024 - 1024;
 }
@@ -523,8 +523,7 @@ static hipError_t launch_lds_bwd(const BwdArgs& a0, int* nchunk_out, int* ntheta
         constexpr int CW = (D == 1) ? 2 : ((D == 4) ? 8 : 4);
         const size_t lds_bytes = ((size_t)TA * (D + 1) * (FP + 8) + CW * TA * (size_t)(8 * LI) + 4 * TA * (D + 1)) * 4;
         const int64_t ntiles = (a.n + TA - 1) / TA;
-        static const char* env_blocks = getenv("MKGNN_BANK_BLOCKS");          // diagnostics
-        int64_t blocks = env_blocks ? atoi(env_blocks) : BWD_BANK_BLOCKS;
+        int64_t blocks = switches().bank_blocks;         // (MKGNN_BANK_BLOCKS, diagnostics; unset = 0 = the default below)
         if (blocks < 1 || blocks > BWD_BANK_BLOCKS) blocks = BWD_BANK_BLOCKS;
         // every block ends by writing a full partial slab (115 KB for degree 4): with about one tile per block the
         // slab traffic costs as much as the tile (stamps: 15 us of work, 41 us of kernel), so a block takes at

@@ -218,10 +218,10 @@ __global__ void __launch_bounds__(NT, 2) kc_backward_rows_mfma(BwdArgs a) {
 }
 
 // ------------------------------------------------------------------ host ---
-bool mfma_backward_supported(int d, int F, int E, int L, int64_t xs, const void* x, int64_t n_atoms) {
+bool mfma_backward_supported(int d, int F, int E, int L, int64_t xs, bool x_aligned, int64_t n_atoms) {
     if (d < 1 || d > 4 || L < 1 || E > 8) return false;
     const int FP = mfma_padded_width(F);
-    if (!FP || xs % 4 != 0 || ((uintptr_t)x & 15)) return false;
+    if (!FP || xs % 4 != 0 || !x_aligned) return false;
     if ((uint64_t)n_atoms * (uint64_t)xs >= (1ull << 32)) return false;
     if (L > 4 * bwd_lq(d)) return false;
     return ((size_t)(d + 1) * L * FP) * 4 <= 150 * 1024;

@@ -444,14 +444,10 @@ template <int KC, bool SP = false> static hipError_t launch_rows_kc(const RowsSt
 
 // MKGNN_BWD_SPLIT: 1 = the backward's products as split fp16 (kgnn_split.h), 0 = v_mfma_f32_16x16x4_f32, unset = default;
 // mkgnn_debug_set_backward_products overrides (tests)
-#ifndef MKGNN_BWD_SPLIT_DEFAULT
-#define MKGNN_BWD_SPLIT_DEFAULT 1
-#endif
 static std::atomic<int> g_bwd_split_override{-1};
 int bwd_split_mode() {
-    static const int m = [] { const char* e = getenv("MKGNN_BWD_SPLIT"); return e ? atoi(e) : MKGNN_BWD_SPLIT_DEFAULT; }();
     const int o = g_bwd_split_override.load(std::memory_order_relaxed);
-    return o >= 0 ? o : m;
+    return o >= 0 ? o : switches().bwd_split;
 }
 extern "C" int mkgnn_debug_set_backward_products(int32_t mode) { g_bwd_split_override.store(mode < 0 ? -1 : (mode ? 1 : 0)); return 0; }
 
@@ -501,8 +497,8 @@ static hipError_t launch_rows_pass(const BwdArgs a4[4], const bool use[4], float
     int count[4], nb = 0;
     for (int g = 0; g < ng; ++g) { count[g] = 1; ++nb; }
     // grid cap: see launch_backward_bank_stream (the two kernels' caps were measured together)
-    static const char* env_blocks = getenv("MKGNN_ROWS_STREAM_BLOCKS");
-    const int max_blocks = grid_cap(g_grid_caps.rows, env_blocks && atoi(env_blocks) > 8 && atoi(env_blocks) <= FUSED_MAX_BLOCKS ? atoi(env_blocks) : 448);
+    const int env_blocks = switches().rows_stream_blocks;
+    const int max_blocks = grid_cap(g_grid_caps.rows, env_blocks > 8 && env_blocks <= FUSED_MAX_BLOCKS ? env_blocks : 448);
     while (nb < max_blocks) {
         int worst = -1;
         double t_worst = -1.0;

@@ -849,8 +849,8 @@ void plan_backward_bank_stream(const BwdArgs a4[4], const bool use[4], const flo
     // Grid cap.  Not every wave slot of the chip: this kernel runs beside the other chain's kernels (the gather, the next
     // layer's rows kernel), which need slots to make progress at all -- 320 blocks instead of 512 is 2.5 % of the step at
     // batch 4096 (measured together with the rows kernel's 448; MKGNN_BANK_STREAM_BLOCKS / MKGNN_ROWS_STREAM_BLOCKS to re-measure)
-    static const char* env_blocks = getenv("MKGNN_BANK_STREAM_BLOCKS");
-    const int max_blocks = grid_cap(g_grid_caps.bank, env_blocks && atoi(env_blocks) > 8 && atoi(env_blocks) <= FUSED_MAX_BLOCKS ? atoi(env_blocks) : 320);
+    const int env_blocks = switches().bank_stream_blocks;
+    const int max_blocks = grid_cap(g_grid_caps.bank, env_blocks > 8 && env_blocks <= FUSED_MAX_BLOCKS ? env_blocks : 320);
     while (nb < max_blocks) {
         int worst = -1;
         double t_worst = -1.0;

@@ -334,8 +334,7 @@ static inline int csr_grid(int64_t n, int rpw) {
     int64_t groups = (n + rpw - 1) / rpw;
     int64_t blocks = (groups + 3) / 4;
     if (blocks < 1) blocks = 1;
-    static const char* env_cap = getenv("MKGNN_CSR_BLOCKS");          // diagnostics
-    const int64_t cap = env_cap ? atoi(env_cap) : 256 * 16;
+    const int64_t cap = switches().csr_blocks;           // (MKGNN_CSR_BLOCKS, diagnostics; default 256 * 16)
     if (blocks > cap) blocks = cap;
     return (int)blocks;
 }
@@ -363,15 +362,11 @@ bool try_rows_presplit(const float* x, int64_t xs, int64_t n, int width, float* 
     return true;
 }
 
-static int csr_fixed4() {
-    static const int v = [] { const char* e = getenv("MKGNN_CSR_FIXED4"); return e ? atoi(e) : 0; }();
-    return v;
-}
 
 template <bool GATHER>
 static hipError_t launch_csr(const CsrArgs& a_in, hipStream_t st) {
     CsrArgs a = a_in;
-    a.fixed4 = csr_fixed4();
+    a.fixed4 = switches().csr_fixed4;
     switch (lanes_per_row(a.width)) {
         case 8: csr_rows_kernel<8, GATHER><<<csr_grid(a.n, 8), 256, 0, st>>>(a); break;
         case 16: csr_rows_kernel<16, GATHER><<<csr_grid(a.n, 4), 256, 0, st>>>(a); break;
@@ -384,7 +379,7 @@ static hipError_t launch_csr(const CsrArgs& a_in, hipStream_t st) {
 template <int BLK>
 static hipError_t launch_csr_blocks(const CsrArgs& a_in, hipStream_t st) {
     CsrArgs a = a_in;
-    a.fixed4 = csr_fixed4();
+    a.fixed4 = switches().csr_fixed4;
     switch (lanes_per_row(a.width)) {
         case 8: csr_rows_kernel<8, false, BLK><<<csr_grid(a.n, 8), 256, 0, st>>>(a); break;
         case 16: csr_rows_kernel<16, false, BLK><<<csr_grid(a.n, 4), 256, 0, st>>>(a); break;

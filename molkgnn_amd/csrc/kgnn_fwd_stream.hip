@@ -909,14 +909,8 @@ __device__ __forceinline__ void stream_body(const FusedFwdArgs& a, const FusedDe
 #ifndef MKGNN_EXP_OCC
 #define MKGNN_EXP_OCC 2
 #endif
-#ifndef MKGNN_FWD_PP_DEFAULT
-#define MKGNN_FWD_PP_DEFAULT 0
-#endif
 #ifndef MKGNN_PP_OCC4_KC
 #define MKGNN_PP_OCC4_KC 0                               // (experiment: ping-pong bodies up to this chunk count built for 4 waves per SIMD)
-#endif
-#ifndef MKGNN_FWD_PAIR_DEFAULT
-#define MKGNN_FWD_PAIR_DEFAULT 0
 #endif
 // (KC >= 8, rows of 113 .. 160 floats: the bank alone is up to 160 registers -- one wave per SIMD, 512 registers)
 template <int KC, int BF = 0>
@@ -1027,11 +1021,8 @@ static size_t plan_stream(FusedFwdArgs& a, const bool use[4], int KC, int* nbloc
             // 14.8 k at F = 28)
             static double split7[4] = {230.0, 337.0, 533.0, 710.0}, split2[4] = {131.0, 176.0, 303.0, 462.0};
             static const bool env_read = [] {            // diagnostics: MKGNN_STREAM_COST="c1,c2,c3,c4" (applies to both widths)
-                if (const char* e = getenv("MKGNN_STREAM_COST")) {
-                    double v[4];
-                    if (sscanf(e, "%lf,%lf,%lf,%lf", &v[0], &v[1], &v[2], &v[3]) == 4)
-                        for (int k = 0; k < 4; ++k) calib7[k] = calib2[k] = split7[k] = split2[k] = v[k];
-                }
+                if (switches().stream_cost_set)
+                    for (int k = 0; k < 4; ++k) calib7[k] = calib2[k] = split7[k] = split2[k] = switches().stream_cost[k];
                 return true;
             }();
             (void)env_read;
@@ -1072,7 +1063,7 @@ static size_t plan_stream(FusedFwdArgs& a, const bool use[4], int KC, int* nbloc
     // same degree, and the launch lasts as long as its unluckiest wave (round 5 stamps: the waves of one group, all with the
     // same number of tiles, ended between 52 and 69 us).  MKGNN_FWD_PAIR = P (diagnostics; 0 = the interleave of rounds 1-4):
     // blocks b and b + P get the same group where the counts allow it.
-    static const int pair_dist = [] { const char* e = getenv("MKGNN_FWD_PAIR"); return e ? atoi(e) : MKGNN_FWD_PAIR_DEFAULT; }();
+    const int pair_dist = switches().fwd_pair;
     int given[MG] = {};
     if (!pp && pair_dist > 0 && nb == 2 * 256 && (pair_dist == 256 || pair_dist == 8)) {
         // deal PAIRS (b, b + P): half of every group's blocks to the first member, the same groups to the second; a group
@@ -1174,21 +1165,11 @@ template <int KC, int BF = 0> static hipError_t launch_pp_kc(const FusedFwdArgs&
     return hipGetLastError();
 }
 
-// MKGNN_FWD_PP: 0 = the 4-wave blocks of rounds 2-4, 1 = ping-pong blocks wherever they apply (KC <= 7), unset = default
-static int fwd_pp_mode() {
-    static const int m = [] { const char* e = getenv("MKGNN_FWD_PP"); return e ? atoi(e) : MKGNN_FWD_PP_DEFAULT; }();
-    return m;
-}
-
 // MKGNN_FWD_SPLIT: 1 = the node-feature products as split fp16 (BF = 2), 0 = v_mfma_f32_16x16x4_f32, unset = default
-#ifndef MKGNN_FWD_SPLIT_DEFAULT
-#define MKGNN_FWD_SPLIT_DEFAULT 1
-#endif
 static std::atomic<int> g_fwd_split_override{-1};
 static int fwd_split_mode() {
-    static const int m = [] { const char* e = getenv("MKGNN_FWD_SPLIT"); return e ? atoi(e) : MKGNN_FWD_SPLIT_DEFAULT; }();
     const int o = g_fwd_split_override.load(std::memory_order_relaxed);
-    return o >= 0 ? o : m;
+    return o >= 0 ? o : switches().fwd_split;
 }
 // tests: 1 / 0 = split-fp16 / fp32 matrix instructions from the next launch on, -1 = what the environment says
 extern "C" int mkgnn_debug_set_forward_products(int32_t mode) { g_fwd_split_override.store(mode < 0 ? -1 : (mode ? 1 : 0)); return 0; }
@@ -1201,7 +1182,7 @@ hipError_t launch_forward_stream(FusedFwdArgs& a, const bool use[4], hipStream_t
     a.stamps = g_stream_stamps;
     a.FPB = bank_pitch(a.F);
     int nb = 0;
-    if (KC <= 7 && fwd_pp_mode() != 0 && !a.x_split) {
+    if (KC <= 7 && switches().fwd_pp != 0 && !a.x_split) {     // MKGNN_FWD_PP: ping-pong blocks wherever they apply, else the 4-wave blocks
         const size_t lds_pp = plan_stream(a, use, KC, &nb, true);
         if (nb == 0) return hipSuccess;
         if (nb > 0 && lds_pp <= (size_t)160 * 1024) {

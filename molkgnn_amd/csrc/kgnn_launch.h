@@ -1,6 +1,7 @@
 // Kernel argument blocks and host-side launchers shared by the C ABI and the kernel files.
 #pragma once
 #include "kgnn_common.h"
+#include "kgnn_switches.h"
 
 #include <atomic>
 
@@ -137,7 +138,7 @@ hipError_t launch_bank_prepare(const mkgnn_kernel_bank banks[4], const Workspace
 hipError_t launch_forward_generic(int d, const FwdArgs& a, hipStream_t st);
 bool mfma_forward_supported(int d, int F, int E, int L);
 int fused_group_count(int d, int F, int L);      // groups of the fused launch this degree needs (budget: FUSED_MAX_GROUPS)
-hipError_t launch_forward_fused(FusedFwdArgs& a, const bool use[4], hipStream_t st);
+hipError_t launch_forward_fused(FusedFwdArgs& a, const bool use_stream[4], const bool use_bank[4], hipStream_t st);   // (kgnn_capi.hip splits)
 // kgnn_fwd_stream.hip: bank in registers, atom rows streamed through LDS by DMA (the reference's shapes)
 bool stream_forward_supported(int d, int F, int E, int L, int64_t n_atoms, int64_t x_stride, int64_t out_stride, const float* e_unit);
 hipError_t launch_forward_stream(FusedFwdArgs& a, const bool use[4], hipStream_t st);
@@ -151,7 +152,7 @@ hipError_t launch_backward_generic(int d, const BwdArgs& a, hipStream_t st);
 struct BankReduceAllArgs { BankReduceArgs deg[4]; int blk_start[4]; };
 hipError_t launch_bank_reduce_all(const BankReduceArgs r[4], hipStream_t st);   // degrees with L == 0 are skipped
 // kgnn_bwd.hip: LDS-tiled backward for the model's shapes
-bool lds_backward_supported(int d, int F, int E, int L, int64_t xs, const void* x);
+bool lds_backward_supported(int d, int F, int E, int L, int64_t xs, bool x_aligned);       // x_aligned: x on a 16-byte boundary
 hipError_t launch_backward_lds(int d, const BwdArgs& a, int* nchunk_out, int* ntheta_out, bool rows_too, hipStream_t st);
 int bank_blocks_for(int d, int64_t n);
 hipError_t launch_backward_bank_fused(const BwdArgs a4[4], const bool use[4], int nchunk_out[4], int ntheta_out[4], hipStream_t st);
@@ -223,7 +224,7 @@ bool rows_stream_supported(int d, int F, int E, int L);
 // coefq / nct: the pre-pass's records (null: the kernel gathers its coefficients itself)
 hipError_t launch_backward_rows_stream(const BwdArgs a4[4], const bool use[4], float* const coefq[4], hipStream_t st);
 // kgnn_bwd_mfma.hip: MFMA backward for the model's shapes
-bool mfma_backward_supported(int d, int F, int E, int L, int64_t xs, const void* x, int64_t n_atoms);
+bool mfma_backward_supported(int d, int F, int E, int L, int64_t xs, bool x_aligned, int64_t n_atoms);
 hipError_t launch_backward_rows_mfma(int d, const BwdArgs& a, int* ntheta_out, hipStream_t st);
 hipError_t launch_backward_gather(const float* contrib, int64_t cs, int64_t n_contrib_rows, const int32_t* rowptr,
                                   const int32_t* rows, const float* x, int64_t xs, const float* inv, int64_t n, int F,

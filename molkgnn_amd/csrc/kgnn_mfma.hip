@@ -704,40 +704,15 @@ static size_t plan_fused(FusedFwdArgs& a, const bool use[4], int KC, int* nblock
     return lds_floats * 4;
 }
 
-hipError_t launch_forward_fused(FusedFwdArgs& a, const bool use[4], hipStream_t st) {
-    if (a.last && use[3] && a.deg[3].n > 0) {
+hipError_t launch_forward_fused(FusedFwdArgs& a, const bool use_stream[4], const bool use_bank[4], hipStream_t st) {
+    if (a.last && (use_stream[3] || use_bank[3]) && a.deg[3].n > 0) {
         int64_t blocks = (a.deg[3].n + 3) / 4;
         if (blocks > 2048) blocks = 2048;
         rows_equal_kernel<<<(int)blocks, 256, 0, st>>>(a.x, a.xs, a.deg[3].nei, a.deg[3].p_focal, a.deg[3].p_nei, a.deg[3].n, a.F,
                                                       (int8_t*)a.deg[3].eqflag, (int8_t*)a.deg[3].signflag, a.x_split);
     }
-    // The reference's bank shapes take the streamed kernel (kgnn_fwd_stream.hip); every other covered shape, and the
-    // bf16 variant, the LDS-bank kernel below.  MKGNN_FWD_STREAM=0: A/B switch (diagnostics).
-    static const char* env_stream = getenv("MKGNN_FWD_STREAM");
-    // (round 4: the bf16 variant too, for the model's row widths; MKGNN_BF16_STREAM=0 keeps it on the LDS-bank kernel)
-    static const char* env_bf = getenv("MKGNN_BF16_STREAM");
-    const bool bf_stream = !(env_bf && env_bf[0] == '0') && stream_forward_bf16_supported(a.F);
-    const bool stream_on = !(env_stream && env_stream[0] == '0') && (!a.bf16 || bf_stream);
-    bool use_stream[4], use_bank[4];
-    bool any_bank = false;
-    for (int i = 0; i < 4; ++i) {
-        use_stream[i] = use[i] && stream_on && stream_forward_supported(i + 1, a.F, a.E, a.deg[i].L, a.n_atoms, a.xs, a.os, a.deg[i].e_unit);
-        use_bank[i] = use[i] && !use_stream[i];
-        any_bank = any_bank || use_bank[i];
-    }
+    const bool any_bank = use_bank[0] || use_bank[1] || use_bank[2] || use_bank[3];
     const int KC = mfma_padded_width(a.F) / 16;          // (0: rows wider than the LDS-bank kernel takes -- streamed or nothing)
-    {   // the streamed launch holds FUSED_MAX_GROUPS (degree, column part) groups: very wide banks go to the LDS-bank kernel, widest first
-        int Ls[4];
-        for (int i = 0; i < 4; ++i) Ls[i] = a.deg[i].L;
-        while (stream_forward_groups(Ls, use_stream) > FUSED_MAX_GROUPS) {
-            int big = -1;                                    // (only a degree the LDS-bank kernel covers can move there; the caller
-            for (int i = 0; i < 4; ++i)                      //  keeps the stream-only degrees within the table by itself)
-                if (use_stream[i] && mfma_forward_supported(i + 1, a.F, a.E, Ls[i]) &&
-                    (big < 0 || stream_column_parts(i + 1, Ls[i]) > stream_column_parts(big + 1, Ls[big]))) big = i;
-            if (big < 0) return hipErrorInvalidValue;
-            use_stream[big] = false; use_bank[big] = true; any_bank = true;
-        }
-    }
     const int time_reps = g_time_fused.load() ? g_time_reps.load() : 1;
     if (g_time_fused.load()) (void)hipEventRecord(g_ev0, st);
     for (int rep = 0; rep < time_reps; ++rep) {
