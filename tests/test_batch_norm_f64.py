@@ -401,7 +401,8 @@ def test_handed_norms_and_presplit_rows(C, family):
     below 2^-3 after scaling -- 2^-11 of its row's norm -- loses its lo half to fp16 subnormals: 2^-25 scaled, absolute), and where the
     library takes pre-split rows of this width the first convolution on them is bit for bit the convolution on the fp32 rows."""
     from molkgnn_amd import functional as Fn
-    from tests.test_rows_split import _decode, _setup
+    from tests._csr_reference import decode_split
+    from tests.test_rows_split import _setup
     dev, b, plan, first, _, _ = _setup(C, dup=0.0)
     n = b.x.shape[0]
     x = B.make(family, n, C, seed=2)
@@ -420,7 +421,7 @@ def test_handed_norms_and_presplit_rows(C, family):
     assert i0 is not None and torch.equal(i0, i1) and torch.equal(i0, Fn.row_inv_norm(x0.detach()))
     ref = B.reference(x, w, bias, rm, rv, MOM, EPS, True)
     F64.check({"out": x0, "inv_norm": i0}, yardstick(x, w, bias, rm, rv, True), ref, f"bn/handoff/{family}/{C}")
-    back = _decode(x1.detach(), i1, C)
+    back = decode_split(x1.detach(), C, i1)
     e = (i1.view(torch.int32) >> 23) & 0xFF
     scale = torch.exp2((e - 127 + 8).float())[:, None]
     a0 = x0.detach().abs()

@@ -642,6 +642,10 @@ def test_csr_passes_long_and_empty_segments():
         h = Fn.propagate_add(v, plan, out_pad=(-width) % 4)
         ref = torch.zeros(n, width).index_add_(0, ei[1], store[:, :width][ei[0]])
         assert torch.allclose(h.cpu(), ref, atol=1e-5), width
+        # ... and exactly the fp32 sum in CSR order (tests/_csr_reference.py; the exact leg is tests/test_csr_rows_exact.py)
+        from tests import _csr_reference as CR
+        rowptr, col = (t.cpu().numpy() for t in plan.csr_in)
+        assert np.array_equal(h.cpu().numpy(), CR.seq_sum_f32(rowptr, col, store[:, :width].numpy())), width
         assert float(h[10].abs().max()) == 0.0 and float(h[11].abs().max()) == 0.0
         inv = Fn._handed_inv_norm(h)
         assert torch.allclose(inv.cpu(), 1.0 / ref.norm(dim=1).clamp_min(1e-8), rtol=1e-5), width

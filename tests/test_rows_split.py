@@ -17,24 +17,14 @@ import numpy as np
 import pytest
 import torch
 
+from tests._csr_reference import decode_split
+
 pytestmark = pytest.mark.gpu
 
 
 def _dev():
     assert torch.cuda.is_available(), "pytest -m gpu needs the MI355X"
     return torch.device("cuda:0")
-
-
-def _decode(h_split: torch.Tensor, inv: torch.Tensor, width: int) -> torch.Tensor:
-    """fp32 values of pre-split rows: (hi + lo) / 2^(exponent(inv) + 8)."""
-    n = h_split.shape[0]
-    store = torch.as_strided(h_split, (n, h_split.stride(0)), (h_split.stride(0), 1))
-    w4 = (width + 3) // 4 * 4
-    halves = store[:, :w4].contiguous().view(torch.float16).view(n, w4 // 4, 2, 4).float()      # [n, granule, hi|lo, 4]
-    vals = (halves[:, :, 0, :] + halves[:, :, 1, :]).reshape(n, w4)[:, :width]
-    e = (inv.view(torch.int32) >> 23) & 0xFF
-    scale = torch.exp2((e - 127 + 8).float())
-    return vals / scale[:, None]
 
 
 def _setup(width, n_mol=700, seed=31, dup=0.1):
@@ -65,7 +55,7 @@ def test_producer_writes_rows_that_decode_to_the_fp32_rows(width):
     assert Fn.is_rows_split(hs) and not Fn.is_rows_split(h)
     inv, inv_s = getattr(h, Fn._INV_ATTR)[0], getattr(hs, Fn._INV_ATTR)[0]
     assert torch.equal(inv, inv_s)
-    back = _decode(hs, inv_s, 110)
+    back = decode_split(hs, 110, inv_s)
     err = (back - h).abs()
     # two roundings to nearest of the SCALED value: 2^-22 of the element, or -- an element below 2^-3 scaled, i.e. 2^-11 of its
     # row's norm, whose lo half is an fp16 subnormal -- 2^-25 scaled = 2^-33 of the row's norm
@@ -236,7 +226,7 @@ def test_batch_norm_writes_presplit_rows_for_the_first_layer(training):
     x0, i0, o0, gx0, g0, gb0, s0 = run(False)
     x1, i1, o1, gx1, g1, gb1, s1 = run(True)
     assert torch.equal(i0, i1) and torch.equal(o0, o1)
-    back = _decode(x1, i1, 28)
+    back = decode_split(x1, 28, i1)
     e = (i1.view(torch.int32) >> 23) & 0xFF
     scale = torch.exp2((e - 127 + 8).float())[:, None]
     assert bool(((back - x0).abs() * scale <= 2.0 ** -22 * x0.abs() * scale + 2.0 ** -25).all())
