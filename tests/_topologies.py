@@ -22,6 +22,21 @@ def pair() -> Spec:
     return 2, [(0, 1)]
 
 
+def empty() -> Spec:
+    """A molecule without atoms (a loader's padding slot): a segment of length 0 in ``mol_ptr``."""
+    return 0, []
+
+
+def chain(n: int) -> Spec:
+    """A path on ``n`` atoms (atom i bonds to i + 1): two ends of degree 1, everything between of degree 2."""
+    return n, [(i, i + 1) for i in range(n - 1)]
+
+
+def repeat(specs: Sequence[Spec], times: int) -> List[Spec]:
+    """``specs`` laid end to end ``times`` times (the spec tuples are shared, not copied: ``batch_of`` only reads them)."""
+    return list(specs) * times
+
+
 def tree(n: int, ring: bool = True) -> Spec:
     """A ternary tree on ``n`` atoms (atom i bonds to (i - 1) // 3: inner atoms have degree 4 from n = 5 on), plus -- with
     ``ring`` -- one ring closure between the last two leaves that are not yet bonded."""

@@ -391,13 +391,7 @@ def test_propagate_hands_row_norms_to_next_layer():
         assert Fn._handed_inv_norm(h) is None
 
 
-def _torch_readout(h, w1, b1, w2, b2, keep, batch, size):
-    z = torch.nn.functional.linear(h, w1, b1)
-    z = z * torch.sigmoid(z)
-    if keep is not None:
-        z = z * keep
-    z = torch.nn.functional.linear(z, w2, b2)
-    return torch.zeros(size, w2.shape[0], device=h.device).index_add_(0, batch, z)
+from tests._readout_f64 import torch_readout as _torch_readout        # (shared with the float64 leg: tests/test_readout_f64.py)
 
 
 @pytest.mark.parametrize("F,H,G,bias,drop", [(110, 32, 32, True, False), (110, 32, 32, True, True), (28, 5, 7, False, False),
