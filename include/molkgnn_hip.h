@@ -629,6 +629,37 @@ int mkgnn_head_loss_fused(int32_t loss_kind, const float* emb, int64_t emb_strid
                           float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI v8, additive) The task-indexed head with masked labels: weight [T, H] and bias [T] (or NULL) of a T-output ffn, and per
+ * row i < n_rows ONE task  t_i = task[i]  (row_ids NULL; n_task >= n_rows entries)  or  t_i = task[row_ids[i]]  (task: a table of
+ * n_task entries, e.g. one per molecule of a resident shard; row_ids int32 [n_rows]; an id outside [0, n_task) is "no label").
+ * A row is labelled when 0 <= t_i < T (-1 by convention otherwise):
+ *     pred_i = labelled ? (keep_i * emb_i) . weight[t_i] + bias[t_i] : +0.0
+ *     loss   = sum over the labelled rows of the loss kind's term(pred_i, target_i) / max(n_labelled, 1)   (SQERR_SUM: no division)
+ * keep: the single-task head's dropout multipliers (element i * H + h of the same generator, same rng_state / rng_used protocol).
+ * The gradients are those of that expression: rows of grad_emb without a label, and rows of grad_weight [T, H] / grad_bias [T]
+ * (or NULL) of tasks without a labelled row, are exactly zero; with no labelled row at all the loss and every gradient are
+ * zero.  target is not used for unlabelled rows; nothing is read at rows >= n_rows.  forward / backward / fused mirror
+ * mkgnn_head_loss_dropout_forward / _dropout_backward / _fused (backward: d loss from the device, the mask regenerated from
+ * rng_used; fused: forward and the gradients for d loss = 1).  Two launches per call, fixed-order sums, bit-reproducible; T = 1
+ * with every row labelled gives the pred of mkgnn_head_loss_dropout_forward bit for bit.  1 <= T <= MKGNN_TASK_HEAD_MAX_TASKS and
+ * 1 <= H <= 64, anything else is an error.  workspace: mkgnn_task_head_workspace_bytes (0 outside the limits). */
+#define MKGNN_TASK_HEAD_MAX_TASKS 32
+size_t mkgnn_task_head_workspace_bytes(int64_t n_rows, int32_t H, int32_t T);
+int mkgnn_task_head_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                            const float* weight, const float* bias, const float* target, const int32_t* task,
+                            const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state, int64_t* rng_used,
+                            float* pred, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int mkgnn_task_head_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                             const float* weight, const float* target, const int32_t* task, const int32_t* row_ids,
+                             int64_t n_task, const float* pred, const float* grad_loss, float dropout_p,
+                             const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
+                             float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
+int mkgnn_task_head_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                          const float* weight, const float* bias, const float* target, const int32_t* task,
+                          const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state, int64_t* rng_used,
+                          float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
+                          float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 /* AdamW step over all trainable tensors of the model in one launch (reference model.py:368-385: torch.optim.AdamW,
  * two parameter groups -- kernel banks without weight decay).  Per tensor: param / grad [numel] fp32 contiguous,
  * state [mkgnn_adamw_state_floats(numel)] = exp_avg, exp_avg_sq, step count (as a float, advanced by this call), two reserved

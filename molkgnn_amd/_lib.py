@@ -19,6 +19,7 @@ MAX_DEGREE = 4
 ABI_VERSION = 8
 # MKGNN_LOSS_*: the loss kinds of the single-task head (mkgnn_tail_args.loss_kind, mkgnn_head_loss_*)
 LOSS_BCE_MEAN, LOSS_SQERR_MEAN, LOSS_SQERR_SUM = 0, 1, 2
+TASK_HEAD_MAX_TASKS, TASK_HEAD_MAX_H = 32, 64   # MKGNN_TASK_HEAD_MAX_TASKS, the task-indexed head's widest embedding
 
 
 class KernelBank(C.Structure):
@@ -168,7 +169,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_tail_fused_readout_dropout", "mkgnn_readout_dropout_mask", "mkgnn_tail_score", "mkgnn_tail_score_workspace_bytes",
            "mkgnn_head_loss_forward", "mkgnn_head_loss_backward", "mkgnn_head_loss_dropout_forward",
            "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused", "mkgnn_gather_compact",
-           "mkgnn_gather_compact_workspace_bytes", "mkgnn_gather_compact_packed", "mkgnn_topk_update", "mkgnn_topk_workspace_bytes")
+           "mkgnn_gather_compact_workspace_bytes", "mkgnn_gather_compact_packed", "mkgnn_topk_update", "mkgnn_topk_workspace_bytes",
+           "mkgnn_task_head_workspace_bytes", "mkgnn_task_head_forward", "mkgnn_task_head_backward", "mkgnn_task_head_fused")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -334,6 +336,17 @@ def load() -> C.CDLL:
         getattr(lib, name).argtypes = [I32] + list(args)          # (loss_kind, then the mkgnn_bce_head_* arguments)
     lib.mkgnn_bce_head_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_bce_head_workspace_bytes.argtypes = [I64, I32]
+    # the task-indexed head: (loss_kind, emb, stride, n_rows, H, T, weight, [bias,] target, task, row_ids, n_task, ...)
+    lib.mkgnn_task_head_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_task_head_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.mkgnn_task_head_forward.restype = C.c_int
+    lib.mkgnn_task_head_forward.argtypes = [I32, P, I64, I64, I32, I32, P, P, P, P, P, I64, C.c_float, P, P, P, P, P, C.c_size_t, P]
+    lib.mkgnn_task_head_backward.restype = C.c_int
+    lib.mkgnn_task_head_backward.argtypes = [I32, P, I64, I64, I32, I32, P, P, P, P, I64, P, P, C.c_float, P, P, I64, P, P, P,
+                                             C.c_size_t, P]
+    lib.mkgnn_task_head_fused.restype = C.c_int
+    lib.mkgnn_task_head_fused.argtypes = [I32, P, I64, I64, I32, I32, P, P, P, P, P, I64, C.c_float, P, P, P, P, P, I64, P, P, P,
+                                          C.c_size_t, P]
     lib.mkgnn_rf_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_rf_workspace_bytes.argtypes = [I64]
     lib.mkgnn_rf_count.restype = C.c_int

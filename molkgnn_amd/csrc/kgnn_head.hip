@@ -9,6 +9,7 @@
 
 #include "kgnn_launch.h"
 #include "kgnn_philox.h"
+#include "kgnn_head_terms.h"
 #include "../../include/molkgnn_hip.h"
 
 namespace mkgnn {
@@ -23,38 +24,9 @@ struct HeadArgs {
     int64_t* rng;                  // forward: {seed, offset}, offset advanced by one per launch
     int64_t* rng_used;             // forward writes / backward reads the {seed, offset} of this call's mask
 };
-constexpr int HEAD_ROWS = 16;       // rows per block (two per half-wave: the block's latency is one row's chain, mostly its Philox rounds)
-
-__device__ __forceinline__ float half_wave_sum(float v) {   // xor tree over the 32 lanes of a row
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// The loss kind LK (MKGNN_LOSS_*, ABI v8) is a template parameter of every head kernel: the BCE instantiations are the code
-// that was there before.  A row's loss term and its d loss / d pred, both before the 1 / B of the mean kinds:
-template <int LK>
-__device__ __forceinline__ float head_loss_term(float x, float y) {
-    if constexpr (LK == MKGNN_LOSS_BCE_MEAN) return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));   // torch's stable form
-    else { const float r = x - y; return r * r; }
-}
-template <int LK>
-__device__ __forceinline__ float head_dloss(float x, float y) {
-    if constexpr (LK == MKGNN_LOSS_BCE_MEAN) return 1.f / (1.f + expf(-x)) - y;
-    else return 2.f * (x - y);
-}
+// HEAD_ROWS, half_wave_sum, head_loss_term / head_dloss and with_loss_kind: kgnn_head_terms.h (shared with kgnn_task_head.hip)
 template <int LK>
 __device__ __forceinline__ float head_mean(float v, int64_t B) { return LK == MKGNN_LOSS_SQERR_SUM ? v : v / (float)B; }
-// the loss kind (MKGNN_LOSS_*) of a call as a template argument: f(std::integral_constant<int, LK>{}); false: unknown kind
-template <typename Fn>
-static bool with_loss_kind(int32_t lk, Fn&& f) {
-    switch (lk) {
-    case MKGNN_LOSS_BCE_MEAN: f(std::integral_constant<int, MKGNN_LOSS_BCE_MEAN>{}); return true;
-    case MKGNN_LOSS_SQERR_MEAN: f(std::integral_constant<int, MKGNN_LOSS_SQERR_MEAN>{}); return true;
-    case MKGNN_LOSS_SQERR_SUM: f(std::integral_constant<int, MKGNN_LOSS_SQERR_SUM>{}); return true;
-    default: return false;
-    }
-}
 
 
 template <int LK>

@@ -1,0 +1,322 @@
+// The task-indexed head with masked labels (ABI v8, additive): ffn [T, H] behind the readout, every molecule contributing the
+// loss of the ONE task it was measured in (task id per row, or through a resident table: task_table[row_ids[i]]); a task id outside
+// [0, T) is "no label".  The single-task head's block shape (kgnn_head_terms.h: HEAD_ROWS rows per block, 32 lanes per row), its
+// product and reduction order for a row's pred, its loss terms and its dropout generator protocol.  Two launches per pass:
+//   1. task_head_kernel: pred, and per block a partial [T][H + 1] (d W | d b per task) followed by {loss, labelled rows}.  The
+//      block's rows (keep * emb, d loss / d pred, task) are staged in LDS; one lane per (task, column) then walks the 16 rows IN
+//      ROW ORDER, so the order of every sum is fixed.  grad_emb is written here without the 1 / n_lab of the mean kinds.
+//   2. task_head_final_kernel: block 0 sums the loss partials in a fixed tree and advances the generator; one block per 64
+//      (task, column) entries sums the block partials in a fixed order; the remaining blocks scale grad_emb.  Every block counts the
+//      labelled rows itself from the integer-valued per-block counts (exact in any order), so nothing waits on another block.
+// No float atomics, no "last block done" counter (kgnn_head.hip records why).
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include "kgnn_common.h"
+
+#include "kgnn_launch.h"
+#include "kgnn_philox.h"
+#include "kgnn_head_terms.h"
+#include "../../include/molkgnn_hip.h"
+
+namespace mkgnn {
+
+struct TaskHeadArgs {
+    const float* emb; int64_t es; int64_t B; int H; int T;
+    const float* w; const float* b; const float* y;      // w [T, H], b [T] or null
+    const int32_t* task; const int32_t* row_ids; int64_t n_task;    // row_ids null: task [B]; else task [n_task], row i -> task[row_ids[i]]
+    float* pred; float* loss;
+    const float* gloss; float* gemb; int64_t ges; float* gw; float* gb;
+    float* partial;
+    float drop_p;
+    int64_t* rng;                  // forward / fused: {seed, offset}, offset advanced by one per call
+    int64_t* rng_used;             // forward writes / backward reads the {seed, offset} of this call's mask
+};
+enum { TH_FORWARD = 0, TH_BACKWARD = 1, TH_FUSED = 2 };
+constexpr int TH_MAX_H = 64;        // LDS row of the staged keep * emb: a wave writes two rows, one per 32-lane half (the halves never
+                                    // conflict, 32 consecutive floats fill 32 banks), and reads one row at consecutive columns: no padding
+constexpr int TH_SCALE_BLOCKS = 64; // blocks of the final kernel that scale grad_emb (at most)
+
+// a block's partial row: [T][H + 1] gradient entries (the gradient passes) | loss | labelled rows
+__device__ __host__ __forceinline__ int task_head_entries(int mode, int T, int H) { return mode == TH_FORWARD ? 0 : T * (H + 1); }
+
+template <int LK, int MODE>
+__global__ void __launch_bounds__(256) task_head_kernel(TaskHeadArgs a) {
+    __shared__ float ek[HEAD_ROWS][TH_MAX_H];    // keep * emb of the block's rows
+    __shared__ float dl[HEAD_ROWS], lt[HEAD_ROWS];   // d loss / d pred (before 1 / n_lab) and loss term: 0 for an unlabelled row
+    __shared__ int tk[HEAD_ROWS];                // task of the row, -1: unlabelled or beyond B
+    const int t = threadIdx.x, h = t & 31, g = t >> 5;          // 8 rows x 32 lanes per pass
+    constexpr int NP = HEAD_ROWS / 8;
+    const int Q = task_head_entries(MODE, a.T, a.H), PW = Q + 2;
+    const bool drop = a.drop_p > 0.f;
+    const int64_t* rs = MODE == TH_BACKWARD ? a.rng_used : a.rng;
+    const uint64_t seed = drop ? (uint64_t)rs[0] : 0, offset = drop ? (uint64_t)rs[1] : 0;
+    const float gl = MODE == TH_BACKWARD ? a.gloss[0] : 1.f;
+    // all loads of the block's rows first (unconditional, clamped): row -> task -> the task's weight row, then the arithmetic
+    int tv[NP];
+    float xv[NP], yv[NP], pv[NP], w0[NP], bv[NP], ks0[NP], dv[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
+        const int64_t ic = i < a.B ? i : a.B - 1;
+        int32_t tid;
+        if (a.row_ids) {
+            const int64_t r = a.row_ids[ic];
+            const bool in = r >= 0 && r < a.n_task;          // (an id outside the table: no label)
+            tid = a.task[in ? r : 0];
+            if (!in) tid = -1;
+        } else {
+            tid = a.task[ic];
+        }
+        tv[k] = (i < a.B && tid >= 0 && tid < a.T) ? tid : -1;
+        const int tc = tv[k] < 0 ? 0 : tv[k];
+        xv[k] = a.emb[ic * a.es + (h < a.H ? h : 0)];
+        yv[k] = a.y[ic];
+        pv[k] = MODE == TH_BACKWARD ? a.pred[ic] : 0.f;
+        w0[k] = h < a.H ? a.w[(size_t)tc * a.H + h] : 0.f;
+        bv[k] = (MODE != TH_BACKWARD && a.b) ? a.b[tc] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
+        const int64_t ic = i < a.B ? i : a.B - 1;
+        const bool lab = tv[k] >= 0;
+        const int tc = lab ? tv[k] : 0;
+        ks0[k] = drop ? keep_scale_of(seed, offset, (uint64_t)ic * a.H + (h < a.H ? h : 0), a.drop_p) : 1.f;
+        float x;
+        if (MODE == TH_BACKWARD) {
+            x = pv[k];
+        } else {
+            // (the single-task head's product and reduction order: T = 1 with every row labelled gives its pred bit for bit)
+            x = h < a.H ? xv[k] * w0[k] : 0.f;
+            if (drop) x *= ks0[k];
+            for (int h0 = 32; h0 < a.H; h0 += 32)                   // (wider embeddings: the rare path)
+                if (h0 + h < a.H) {
+                    float e = a.emb[ic * a.es + h0 + h];
+                    if (drop) e *= keep_scale_of(seed, offset, (uint64_t)ic * a.H + h0 + h, a.drop_p);
+                    x = fmaf(e, a.w[(size_t)tc * a.H + h0 + h], x);
+                }
+            x = half_wave_sum(x) + bv[k];                           // (the xor tree leaves the sum in every lane of the row)
+            if (!lab) x = 0.f;
+        }
+        dv[k] = lab ? gl * head_dloss<LK>(x, yv[k]) : 0.f;
+        if (h == 0) {
+            const int row = k * 8 + g;
+            if (MODE != TH_BACKWARD && i < a.B) a.pred[i] = x;
+            dl[row] = dv[k];
+            lt[row] = lab ? head_loss_term<LK>(x, yv[k]) : 0.f;
+            tk[row] = tv[k];
+        }
+    }
+    if (MODE != TH_FORWARD) {
+        for (int h0 = 0; h0 < a.H; h0 += 32) {
+            const int hh = h0 + h;
+            if (hh < a.H) {
+#pragma unroll
+                for (int k = 0; k < NP; ++k) {
+                    const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
+                    const bool lab = tv[k] >= 0;
+                    float e = 0.f, ks = 0.f, wv = 0.f;
+                    if (lab) {
+                        if (h0 == 0) {
+                            e = xv[k]; ks = ks0[k]; wv = w0[k];
+                        } else {
+                            e = a.emb[i * a.es + hh];
+                            ks = drop ? keep_scale_of(seed, offset, (uint64_t)i * a.H + hh, a.drop_p) : 1.f;
+                            wv = a.w[(size_t)tv[k] * a.H + hh];
+                        }
+                    }
+                    ek[k * 8 + g][hh] = lab ? e * ks : 0.f;
+                    if (a.gemb && i < a.B) a.gemb[i * a.ges + hh] = lab ? dv[k] * wv * ks : 0.f;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    float* part = a.partial + (size_t)blockIdx.x * PW;
+    const int PC = a.H + 1;                                       // a task's entries: dW[0..H), db
+    for (int q = t; q < Q; q += 256) {
+        const int task = q / PC, c = q - task * PC;
+        float acc = 0.f;
+#pragma unroll
+        for (int r = 0; r < HEAD_ROWS; ++r)                       // in row order: a fixed sum
+            if (tk[r] == task) acc = c < a.H ? fmaf(dl[r], ek[r][c], acc) : acc + dl[r];
+        part[q] = acc;
+    }
+    if (t == 0) {
+        float s = 0.f;
+        int n = 0;
+        for (int r = 0; r < HEAD_ROWS; ++r) { s += lt[r]; n += tk[r] >= 0 ? 1 : 0; }
+        part[Q] = s;
+        part[Q + 1] = (float)n;                                   // (<= 16: exact)
+    }
+}
+
+// second launch.  grid: 1 (loss, generator) + ceil(Q / 64) (the gradient entries) + the blocks that scale grad_emb
+template <int LK, int MODE>
+__global__ void __launch_bounds__(256) task_head_final_kernel(TaskHeadArgs a, int nb, int ncol) {
+    __shared__ float fin[256];
+    __shared__ int cnt[256];
+    const int t = threadIdx.x;
+    const int Q = task_head_entries(MODE, a.T, a.H), PW = Q + 2;
+    const float* part = a.partial;
+    // the labelled rows of the call: an integer sum of the blocks' counts
+    {
+        int n = 0;
+        for (int bk = t; bk < nb; bk += 256) n += (int)part[(size_t)bk * PW + Q + 1];
+        cnt[t] = n;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if (t < w) cnt[t] += cnt[t + w];
+            __syncthreads();
+        }
+    }
+    const int n_lab = cnt[0] > 1 ? cnt[0] : 1;
+    const float inv = LK == MKGNN_LOSS_SQERR_SUM ? 1.f : 1.f / (float)n_lab;
+    if (blockIdx.x == 0) {
+        if (MODE != TH_BACKWARD) {
+            float v = 0.f;
+            for (int bk = t; bk < nb; bk += 256) v += part[(size_t)bk * PW + Q];
+            fin[t] = v;
+            __syncthreads();
+            for (int w = 128; w > 0; w >>= 1) {
+                if (t < w) fin[t] += fin[t + w];
+                __syncthreads();
+            }
+            if (t == 0) {
+                a.loss[0] = LK == MKGNN_LOSS_SQERR_SUM ? fin[0] : fin[0] / (float)n_lab;
+                if (a.drop_p > 0.f) {
+                    const int64_t seed = a.rng[0], offset = a.rng[1];
+                    a.rng_used[0] = seed; a.rng_used[1] = offset;
+                    a.rng[1] = offset + 1;
+                }
+            }
+        }
+        return;
+    }
+    if ((int)blockIdx.x <= ncol) {
+        // entry q of the block partials, four row parts per entry, eight loads in flight per thread; parts combined in a fixed order
+        const int q = ((int)blockIdx.x - 1) * 64 + (t & 63), pr = t >> 6;
+        float tot = 0.f;
+        if (q < Q) {
+            for (int bk = pr; bk < nb; bk += 32) {
+                float v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(bk + 4 * u < nb ? bk + 4 * u : bk) * PW + q];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) if (bk + 4 * u < nb) tot += v[u];
+            }
+        }
+        fin[t] = tot;
+        __syncthreads();
+        if (pr == 0 && q < Q) {
+            const float r = ((fin[t] + fin[64 + t]) + (fin[128 + t] + fin[192 + t])) * inv;
+            const int PC = a.H + 1, task = q / PC, c = q - task * PC;
+            if (c < a.H) a.gw[(size_t)task * a.H + c] = r;
+            else if (a.gb) a.gb[task] = r;
+        }
+        return;
+    }
+    // grad_emb *= 1 / n_lab (launched for the mean kinds only)
+    const int64_t nsc = (int64_t)gridDim.x - 1 - ncol, sb = (int64_t)blockIdx.x - 1 - ncol;
+    const int64_t total = a.B * a.H;
+    for (int64_t e = sb * 256 + t; e < total; e += nsc * 256) {
+        const int64_t row = e / a.H;
+        const int col = (int)(e - row * a.H);
+        a.gemb[row * a.ges + col] *= inv;
+    }
+}
+
+}  // namespace mkgnn
+
+using namespace mkgnn;
+
+// ================================================================== C ABI ==========================
+static int64_t task_head_blocks(int64_t n_rows) { return (n_rows + HEAD_ROWS - 1) / HEAD_ROWS; }
+
+static int task_head_check(const char* who, int64_t n_rows, int32_t H, int32_t T, int64_t emb_stride, const int32_t* task,
+                           const int32_t* row_ids, int64_t n_task, float p, void* ws, size_t ws_bytes, TaskHeadArgs& a) {
+    if (T < 1 || T > MKGNN_TASK_HEAD_MAX_TASKS) return api_fail("%s: %d tasks outside [1, %d]", who, (int)T, MKGNN_TASK_HEAD_MAX_TASKS);
+    if (H < 1 || H > TH_MAX_H) return api_fail("%s: embedding width %d outside [1, %d]", who, (int)H, TH_MAX_H);
+    if (n_rows < 1 || emb_stride < H || task_head_blocks(n_rows) > 0x7fffff00) return api_fail("%s: bad shape", who);
+    if (!task) return api_fail("%s: null task", who);
+    if (row_ids ? n_task < 1 : n_task < n_rows) return api_fail("%s: task holds %lld entries", who, (long long)n_task);
+    if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, p);
+    if (!ws || ws_bytes < mkgnn_task_head_workspace_bytes(n_rows, H, T) || ((uintptr_t)ws & 3))
+        return api_fail("%s: workspace too small or misaligned", who);
+    a.partial = (float*)((char*)ws + 16);
+    a.B = n_rows; a.H = H; a.T = T; a.es = emb_stride; a.task = task; a.row_ids = row_ids; a.n_task = n_task; a.drop_p = p;
+    return 0;
+}
+
+template <int MODE>
+static int task_head_launch(const char* who, int32_t lk, const TaskHeadArgs& a, void* stream) {
+    const int nblk = (int)task_head_blocks(a.B);
+    const int Q = task_head_entries(MODE, a.T, a.H);
+    const int ncol = (Q + 63) / 64;
+    int nscale = 0;
+    if (MODE != TH_FORWARD && a.gemb && lk != MKGNN_LOSS_SQERR_SUM) {
+        const int64_t want = (a.B * a.H + 1023) / 1024;
+        nscale = (int)(want < TH_SCALE_BLOCKS ? want : TH_SCALE_BLOCKS);
+    }
+    if (!with_loss_kind(lk, [&](auto K) {
+            task_head_kernel<decltype(K)::value, MODE><<<nblk, 256, 0, (hipStream_t)stream>>>(a);
+            task_head_final_kernel<decltype(K)::value, MODE><<<1 + ncol + nscale, 256, 0, (hipStream_t)stream>>>(a, nblk, ncol);
+        }))
+        return api_fail("%s: unknown loss kind %d", who, (int)lk);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+extern "C" {
+
+size_t mkgnn_task_head_workspace_bytes(int64_t n_rows, int32_t H, int32_t T) {
+    if (n_rows < 1 || H < 1 || H > TH_MAX_H || T < 1 || T > MKGNN_TASK_HEAD_MAX_TASKS) return 0;
+    return 16 + (size_t)task_head_blocks(n_rows) * ((size_t)T * (H + 1) + 2) * 4;
+}
+
+int mkgnn_task_head_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                            const float* weight, const float* bias, const float* target, const int32_t* task,
+                            const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state, int64_t* rng_used,
+                            float* pred, float* loss, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "mkgnn_task_head_forward";
+    TaskHeadArgs a{};
+    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a)) return rc;
+    if (!emb || !weight || !target || !pred || !loss) return api_fail("%s: null pointer", who);
+    if (dropout_p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
+    a.emb = emb; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss; a.rng = rng_state; a.rng_used = rng_used;
+    return task_head_launch<TH_FORWARD>(who, loss_kind, a, stream);
+}
+
+int mkgnn_task_head_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                             const float* weight, const float* target, const int32_t* task, const int32_t* row_ids,
+                             int64_t n_task, const float* pred, const float* grad_loss, float dropout_p, const int64_t* rng_used,
+                             float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws,
+                             size_t ws_bytes, void* stream) {
+    const char* who = "mkgnn_task_head_backward";
+    TaskHeadArgs a{};
+    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a)) return rc;
+    if (!emb || !weight || !target || !pred || !grad_loss || !grad_weight) return api_fail("%s: null pointer", who);
+    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
+    if (dropout_p > 0.f && !rng_used) return api_fail("%s: dropout needs the forward's rng_used", who);
+    a.emb = emb; a.w = weight; a.y = target; a.pred = (float*)pred; a.gloss = grad_loss; a.rng_used = (int64_t*)rng_used;
+    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
+    return task_head_launch<TH_BACKWARD>(who, loss_kind, a, stream);
+}
+
+int mkgnn_task_head_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                          const float* weight, const float* bias, const float* target, const int32_t* task,
+                          const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state, int64_t* rng_used,
+                          float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
+                          float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "mkgnn_task_head_fused";
+    TaskHeadArgs a{};
+    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a)) return rc;
+    if (!emb || !weight || !target || !pred || !loss || !grad_weight) return api_fail("%s: null pointer", who);
+    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
+    if (dropout_p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
+    a.emb = emb; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss; a.rng = rng_state; a.rng_used = rng_used;
+    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
+    return task_head_launch<TH_FUSED>(who, loss_kind, a, stream);
+}
+
+}  // extern "C"

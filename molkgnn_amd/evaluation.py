@@ -132,3 +132,20 @@ def calculate_rmse(true_y, predicted_score) -> float:
     if y.numel() == 0:
         raise ValueError("calculate_rmse needs at least one sample")
     return math.sqrt(float(((y - s) ** 2).mean()))
+
+
+def per_task(true_y, pred_y, task, fn, num_tasks: int) -> list:
+    """``fn(true_y[rows], pred_y[rows])`` for every task ``0 .. num_tasks - 1`` over the rows labelled with it (``task`` holds one
+    task index per row; -1, or anything outside the range, is no label) -- a mixed-assay panel scored assay by assay with any
+    metric of this module.  A task without a row gives ``nan``."""
+    y = torch.as_tensor(true_y).reshape(-1)
+    s = torch.as_tensor(pred_y).reshape(-1)
+    t = torch.as_tensor(task).reshape(-1).to(s.device)
+    if not (y.numel() == s.numel() == t.numel()):
+        raise ValueError("true_y, pred_y and task differ in length")
+    y = y.to(s.device)
+    out = []
+    for k in range(int(num_tasks)):
+        rows = t == k
+        out.append(fn(y[rows], s[rows]) if bool(rows.any()) else float("nan"))
+    return out

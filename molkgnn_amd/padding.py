@@ -223,6 +223,13 @@ class CompactStaticBatch:
                 else (lib.mkgnn_gather_compact, "mkgnn_gather_compact")
             _lib.check(fn(resident.view, self.ids.data_ptr(), self.num_molecules, shape6, PAD_MOLECULES, self.wire.data_ptr(),
                           self.wire.numel(), self._gather_ws.data_ptr(), _lib.stream_ptr(self.wire.device)), who)
+        # a shard that knows its molecules' tasks (ResidentShard(..., assays=...)): the table and this batch's ids are the task of
+        # every row for GNNModel.loss -- two static addresses, nothing launched, nothing copied
+        table = resident.tensors.get("task")
+        if table is not None:
+            self.data.task_table, self.data.task_rows = table, self.ids
+        elif getattr(self.data, "task_table", None) is not None:
+            self.data.task_table = self.data.task_rows = None
 
     def gather_status(self) -> int:
         """The status word of the LAST gather (a host read: once per epoch, not per batch): 0, or ``_lib.GATHER_BAD_ID`` (an id

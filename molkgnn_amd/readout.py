@@ -640,6 +640,184 @@ def head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, los
     return _head_loss("head_loss", emb, ffn, target, loss_kind(loss), dropout_p, n_rows)
 
 
+# ---------------------------------------------------------------- task-indexed head with masked labels --
+def task_head_supported(T: int, H: int) -> bool:
+    """The shapes ``mkgnn_task_head_*`` take; anything else goes through ``task_head_reference`` on the GPU."""
+    return 1 <= T <= _lib.TASK_HEAD_MAX_TASKS and 1 <= H <= _lib.TASK_HEAD_MAX_H
+
+
+def _row_tasks(task, task_table, row_ids, n_rows: int) -> torch.Tensor:
+    """The task of each of the leading ``n_rows`` rows (int64): ``task`` itself, or ``task_table[row_ids]`` with an id outside
+    the table read as -1."""
+    if task is not None:
+        return task.reshape(-1)[:n_rows].long()
+    ids = row_ids.reshape(-1)[:n_rows].long()
+    m = task_table.numel()
+    inside = (ids >= 0) & (ids < m)
+    return torch.where(inside, task_table.reshape(-1).long()[ids.clamp(0, max(m - 1, 0))], torch.full_like(ids, -1))
+
+
+def task_head_reference(emb: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], target: torch.Tensor,
+                        task: Optional[torch.Tensor], loss: str = "bce", keep: Optional[torch.Tensor] = None,
+                        n_rows: Optional[int] = None, task_table: Optional[torch.Tensor] = None,
+                        row_ids: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(loss, pred [n_rows])`` of the task-indexed head in torch operators, in the dtype of ``emb``, differentiable: the
+    DEFINITION of ``task_head_loss`` (and what it runs for more than 32 tasks or an embedding wider than 64).
+
+    Row ``i < n_rows`` has the task ``t_i = task[i]`` (or ``task_table[row_ids[i]]``) and is labelled when ``0 <= t_i < T``
+    (-1 by convention otherwise); ``pred_i = (keep_i * emb_i) . weight[t_i] + bias[t_i]`` for a labelled row and +0.0 for any
+    other; ``loss`` is the sum of the labelled rows' terms -- ``"bce"``: BCE with logits, ``"mse"`` / ``"mse_sum"``: squared
+    error -- over ``max(n_labelled, 1)`` (``"mse_sum"``: not divided).  ``keep [n_rows, H]``: explicit dropout multipliers, or
+    None.  ``target`` of an unlabelled row is not used (a NaN there is harmless); rows from ``n_rows`` on take no part."""
+    loss_kind(loss)
+    n = emb.shape[0] if n_rows is None else int(n_rows)
+    T = weight.shape[0]
+    t = _row_tasks(task, task_table, row_ids, n).to(emb.device)
+    lab = (t >= 0) & (t < T)
+    t = torch.where(lab, t, torch.zeros_like(t))
+    e = emb[:n]
+    if keep is not None:
+        e = e * keep[:n].to(e.dtype)
+    pred = (e * weight[t]).sum(dim=1)
+    if bias is not None:
+        pred = pred + bias[t]
+    zero = torch.zeros((), dtype=pred.dtype, device=pred.device)
+    pred = torch.where(lab, pred, zero)
+    y = torch.where(lab, target.reshape(-1)[:n].to(pred.dtype), zero)
+    if loss == "bce":
+        # log(1 + e^x) - x y: torch's max(x, 0) - x y + log1p(e^-|x|) in value, with sigmoid(x) - y as its derivative at x = 0 too
+        term = torch.logaddexp(pred, torch.zeros_like(pred)) - pred * y
+    else:
+        term = (pred - y) ** 2
+    total = torch.where(lab, term, zero).sum()
+    if loss != "mse_sum":
+        total = total / lab.sum().clamp(min=1).to(pred.dtype)
+    return total, pred
+
+
+class _TaskHeadFn(torch.autograd.Function):
+    """``mkgnn_task_head_*``: the fused entry (forward and the gradients for d loss = 1 in the same two launches) when a gradient
+    is needed, the split forward / backward entries otherwise or under ``MKGNN_SPLIT_HEAD=1`` -- ``_BceHeadFn`` with a task per row."""
+
+    @staticmethod
+    def forward(ctx, emb, weight, bias, target, task, row_ids, p_drop, n_rows, kind):
+        lib = _lib.load()
+        emb = _row_major(emb if emb.dtype == torch.float32 else emb.float())
+        ctx.rows_total = emb.shape[0]
+        B, H = int(n_rows), emb.shape[1]         # the leading n_rows rows enter the loss (the rest: padding molecules)
+        T = weight.shape[0]
+        dev = emb.device
+        w = weight.contiguous()
+        y = target.reshape(-1).float().contiguous()
+        task = task.reshape(-1)
+        if task.dtype != torch.int32 or not task.is_contiguous():
+            task = task.to(torch.int32).contiguous()
+        if row_ids is not None:
+            row_ids = row_ids.reshape(-1)
+            if row_ids.dtype != torch.int32 or not row_ids.is_contiguous():
+                row_ids = row_ids.to(torch.int32).contiguous()
+        idx = (task.data_ptr(), _lib.ptr(row_ids), task.numel())
+        pred = torch.empty(B, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        rng = head_rng_state(dev) if p_drop > 0.0 else None
+        used = torch.empty(2, dtype=torch.int64, device=dev) if p_drop > 0.0 else None
+        ctx.unit = None
+        if any(ctx.needs_input_grad[:3]) and not _SPLIT_HEAD:
+            gemb = None
+            if ctx.needs_input_grad[0]:
+                gemb = torch.empty((ctx.rows_total, H), dtype=torch.float32, device=dev)
+                if ctx.rows_total > B:               # rows beyond B (padding molecules) get a zero gradient
+                    gemb[B:].zero_()
+            gw = torch.empty((T, H), dtype=torch.float32, device=dev)
+            gb = torch.empty(T, dtype=torch.float32, device=dev) if bias is not None else None
+            with torch.cuda.device(dev):
+                ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
+                _lib.check(lib.mkgnn_task_head_fused(
+                    int(kind), emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), *idx,
+                    float(p_drop), _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), _lib.ptr(gemb), H,
+                    gw.data_ptr(), _lib.ptr(gb), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_task_head_fused")
+            ctx.unit = (gemb, gw, gb)
+        else:
+            with torch.cuda.device(dev):
+                ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
+                _lib.check(lib.mkgnn_task_head_forward(
+                    int(kind), emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), *idx,
+                    float(p_drop), _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(),
+                    _lib.stream_ptr(dev)), "mkgnn_task_head_forward")
+        # (with ctx.unit, references only: a second backward over a retained graph takes the separate backward kernel)
+        ctx.save_for_backward(emb, w, y, pred, used, task, row_ids)
+        ctx.kind, ctx.n_rows = int(kind), B
+        ctx.has_bias = bias is not None
+        ctx.p_drop = float(p_drop)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        if ctx.unit is not None:
+            gemb, gw, gb = ctx.unit
+            ctx.unit = None
+            if not _is_unit_seed(grad_loss):                 # d loss is not the registered 1: scale
+                gl = grad_loss.reshape(()).float()
+                gemb = None if gemb is None else gemb * gl
+                gw = gw * gl
+                gb = None if gb is None else gb * gl
+            return gemb, gw, gb, None, None, None, None, None, None
+        lib = _lib.load()
+        emb, w, y, pred, used, task, row_ids = ctx.saved_tensors
+        B, H, T = ctx.n_rows, emb.shape[1], w.shape[0]
+        dev = emb.device
+        gl = grad_loss.reshape(1).float().contiguous()
+        gemb = None
+        if ctx.needs_input_grad[0]:
+            gemb = torch.empty((ctx.rows_total, H), dtype=torch.float32, device=dev)
+            if ctx.rows_total > B:
+                gemb[B:].zero_()
+        gw = torch.empty((T, H), dtype=torch.float32, device=dev)
+        gb = torch.empty(T, dtype=torch.float32, device=dev) if ctx.has_bias else None
+        with torch.cuda.device(dev):
+            ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
+            _lib.check(lib.mkgnn_task_head_backward(
+                ctx.kind, emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), y.data_ptr(), task.data_ptr(), _lib.ptr(row_ids),
+                task.numel(), pred.data_ptr(), gl.data_ptr(), ctx.p_drop, _lib.ptr(used), _lib.ptr(gemb), H, gw.data_ptr(),
+                _lib.ptr(gb), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_task_head_backward")
+        return gemb, gw, gb, None, None, None, None, None, None
+
+
+def task_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, task: Optional[torch.Tensor] = None,
+                   loss: str = "bce", dropout_p: float = 0.0, n_rows: Optional[int] = None,
+                   task_table: Optional[torch.Tensor] = None, row_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The masked multi-task loss of a ``T``-output ``ffn``: ``task_head_reference(dropout(emb), ffn.weight, ffn.bias, target,
+    ...)[0]`` as two launches each way (``_TaskHeadFn``).  Every row names ONE task -- ``task [>= n_rows]`` (int32; -1, or anything
+    outside ``[0, T)``: no label), or ``task_table [M]`` with ``row_ids [>= n_rows]`` (int32, on the device: row i has
+    ``task_table[row_ids[i]]``; both may be static buffers a captured step refills) -- and contributes the loss of that output
+    alone; the mean kinds divide by the number of labelled rows.  ``dropout_p``, its generator (``head_rng_state``) and mask,
+    ``n_rows`` and the loss kinds are ``head_loss``'s.  More than 32 tasks or an embedding wider than 64: the same expression
+    through torch operators on the GPU."""
+    _lib.require_gpu_tensor(emb, "graph_embedding")
+    kind = loss_kind(loss)
+    n_rows = emb.shape[0] if n_rows is None else int(n_rows)
+    if (task is None) == (task_table is None) or (task_table is None) != (row_ids is None):
+        raise ValueError("task_head_loss needs either task, or task_table together with row_ids")
+    per_row = task if task is not None else row_ids
+    if emb.dim() != 2 or ffn.in_features != emb.shape[1] or n_rows <= 0 or n_rows > emb.shape[0] or target.numel() < n_rows \
+            or per_row.numel() < n_rows or (task_table is not None and task_table.numel() < 1):
+        raise ValueError("task_head_loss needs an [n, H] embedding, an H-input linear layer and a target and a task (or row id) "
+                         "per (leading) row")
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"dropout probability {dropout_p} outside [0, 1)")
+    for name, t in (("task", task), ("task_table", task_table), ("row_ids", row_ids), ("target", target)):
+        if t is not None:
+            _lib.require_gpu_tensor(t, name)
+    T, H = ffn.weight.shape
+    if not task_head_supported(T, H):
+        keep = None
+        if dropout_p > 0.0:
+            keep = torch.empty((n_rows, H), dtype=emb.dtype, device=emb.device).bernoulli_(1.0 - dropout_p).mul_(1.0 / (1.0 - dropout_p))
+        return task_head_reference(emb, ffn.weight, ffn.bias, target, task, loss, keep, n_rows, task_table, row_ids)[0]
+    return _TaskHeadFn.apply(emb, ffn.weight, ffn.bias, target, task if task is not None else task_table, row_ids,
+                             float(dropout_p), n_rows, kind)
+
+
 # ------------------------------------------------------------------- the tail of a training step, fused --
 # MKGNN_FUSED_TAIL=0: readout_blocks + bce_head_loss as separate operators (nine launches; A/B, diagnostics)
 _FUSED_TAIL = os.environ.get("MKGNN_FUSED_TAIL", "1") != "0"

@@ -714,9 +714,13 @@ class ResidentShard:
     (``mkgnn_gather_compact_packed``) into the same wire bytes, so everything downstream is unchanged.  ``x_col``, ``rec_bytes``
     and ``byte_columns`` (the column numbers held as int8) say what was done, ``byte_cols`` forces a mask (``pack_x``), and
     ``nbytes()`` is the device footprint of this form.  The host-side records stay in ``x_rec`` (on the CPU, too, where the loader
-    still gathers from the shard itself)."""
+    still gathers from the shard itself).
 
-    def __init__(self, shard_or_path, device="cpu", packed: bool = False, byte_cols=None):
+    ``assays`` (a list of assay ids: the tasks of a mixed-assay model, in output order) keeps ``task`` -- every molecule's task
+    index on the host, ``sampling.task_index(shard.assay_id, assays)`` -- and uploads it as ``tensors["task"]`` (int32 ``[M]``):
+    ``CompactStaticBatch.gather`` hands it to the batch as the task table of the masked multi-task loss."""
+
+    def __init__(self, shard_or_path, device="cpu", packed: bool = False, byte_cols=None, assays=None):
         sh = shard_or_path if isinstance(shard_or_path, Shard) else Shard(str(shard_or_path))
         if not sh.compact_ok:
             raise ValueError(f"{sh.path}: bonds are not reversed pairs with shared byte-valued attributes: no compact form")
@@ -729,6 +733,12 @@ class ResidentShard:
         self.mol_deg = np.ascontiguousarray(np.diff(sh.mol_deg_ptr, axis=0)[:, :4])
         self.y = torch.from_numpy(np.array(sh.y))
         self.tensors, self.view = {}, None
+        # assays: every molecule's task, the position of its assay_id in the list (-1: not listed) -- sampling.task_index
+        self.assays, self.task = None, None
+        if assays is not None:
+            from .sampling import task_index
+            self.assays = tuple(int(a) for a in assays)
+            self.task = task_index(torch.from_numpy(np.array(sh.assay_id)), self.assays)
         self.packed = bool(packed)
         self.x_col = self.x_rec = self.rec_bytes = self.byte_columns = None
         if byte_cols is not None and not self.packed:
@@ -756,6 +766,8 @@ class ResidentShard:
             self.view.n_molecules, self.view.x_dim, self.view.p_dim, self.view.e_dim = sh.n_molecules, sh.x_dim, sh.p_dim, sh.e_dim
             if self.packed:
                 self.view.x_col, self.view.rec_bytes = self.x_col.ctypes.data, self.rec_bytes       # (a host pointer: self.x_col lives as long)
+            if self.task is not None:                        # (not a field of the view: the gather does not read it)
+                self.tensors["task"] = self.task.to(self.device)
 
     def nbytes(self) -> int:
         """Bytes of device memory the shard takes (0 for an unpacked shard on the CPU, which uploads nothing; the packed form

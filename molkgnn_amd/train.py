@@ -80,7 +80,27 @@ class GNNModel(torch.nn.Module):
             return "mse" if lf.reduction == "mean" else "mse_sum"
         return None
 
+    def _task_loss(self, data, kind: str):
+        """The masked multi-task loss (``readout.task_head_loss``): every molecule contributes the loss of the ONE output its task
+        names -- ``data.task`` (one int32 task index per molecule, -1: no label; ``sampling.task_index``) or ``data.task_table`` +
+        ``data.task_rows`` (a resident shard's table and the batch's molecule ids, ``padding.CompactStaticBatch.gather``).  The
+        embedding comes from the separate readout operators: the fused tail and the molecule-resident step are single-task."""
+        from .readout import task_head_loss
+        p = self.dropout.p if (self.training and self.dropout.p < 1.0) else 0.0
+        graph_embedding = self.gnn_model(data)
+        if self.training and self.dropout.p >= 1.0:
+            graph_embedding = self.dropout(graph_embedding)
+        task = getattr(data, 'task', None)                   # (given directly, it is taken before a table)
+        table, rows = (None, None) if task is not None else (data.task_table, data.task_rows)
+        return task_head_loss(graph_embedding, self.ffn, data.y, task, kind, dropout_p=p,
+                              n_rows=getattr(data, 'n_valid_molecules', None), task_table=table, row_ids=rows)
+
     def loss(self, data):
+        if data.x.is_cuda and (getattr(data, 'task', None) is not None or (
+                getattr(data, 'task_table', None) is not None and getattr(data, 'task_rows', None) is not None)):
+            kind = self._loss_kind()
+            if kind is not None:
+                return self._task_loss(data, kind)
         kind = self._loss_kind() if self.ffn.out_features == 1 else None
         if kind is not None and data.x.is_cuda:
             from .readout import bce_head_loss, head_loss
@@ -205,6 +225,59 @@ def evaluate(model, batches, metrics=()) -> dict:
         for m in metrics:
             results[m] = table[m](true_y, pred_y)
         results['pred_y'], results['true_y'] = pred_y, true_y
+        return results
+    finally:
+        model.train(was_training)
+
+
+def evaluate_tasks(model, batches, metrics=(), num_tasks: Optional[int] = None) -> dict:
+    """``evaluate`` for a multi-task model on mixed-assay batches that carry ``task`` (one task index per molecule, -1: no label;
+    ``sampling.task_index``): ``model.predict`` per batch, keeping ``pred [n, T]``.  ``results[m]`` is the list of metric ``m``
+    per task over that task's labelled molecules (``evaluation.per_task``; ``nan`` for a task without any), ``results[m + '_mean']``
+    its mean over the tasks with a defined (non-NaN) value, ``results['loss']`` the masked multi-task loss of the concatenated
+    vectors (``readout.task_head_reference`` on the model's loss kind), ``pred_y`` every molecule's prediction for ITS task (NaN
+    where it has none), ``true_y`` and ``task``.  ``num_tasks`` defaults to the model's outputs.  The model is put in evaluation
+    mode and handed back in the mode it came in, also when a batch raises."""
+    import math
+    from .evaluation import per_task
+    from .readout import task_head_reference
+    table = _metric_functions()
+    unknown = [m for m in metrics if m not in table]
+    if unknown:
+        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(table)}")
+    kind = model._loss_kind()
+    if kind is None:
+        raise ValueError("evaluate_tasks needs one of the head's loss kinds (BCEWithLogitsLoss(), MSELoss(), MSELoss('sum'))")
+    T = model.ffn.out_features if num_tasks is None else int(num_tasks)
+    was_training = model.training
+    model.eval()
+    try:
+        all_pred, all_true, all_task = [], [], []
+        for batch in batches:
+            task = getattr(batch, 'task', None)
+            if task is None:
+                raise ValueError("evaluate_tasks needs batch.task (sampling.task_index of the batch's assay ids)")
+            pred, _ = model.predict(batch)
+            n = pred.shape[0]
+            all_pred.append(pred.reshape(n, -1))
+            all_true.append(batch.y.view(-1)[:n])
+            all_task.append(task.view(-1)[:n].to(pred.device))
+        if not all_pred:
+            raise ValueError("evaluate_tasks needs at least one batch")
+        pred, true_y, task = torch.cat(all_pred), torch.cat(all_true), torch.cat(all_task).long()
+        lab = (task >= 0) & (task < min(T, pred.shape[1]))
+        col = torch.where(lab, task, torch.zeros_like(task))
+        pred_y = torch.where(lab, pred.gather(1, col[:, None]).view(-1), torch.full((), float("nan"), dtype=pred.dtype, device=pred.device))
+        with torch.no_grad():
+            # (the head's expression on the selected column: an identity "embedding" of width 1 per task is the column itself)
+            sel = torch.where(lab, pred_y, torch.zeros_like(pred_y))
+            results = {'loss': task_head_reference(sel[:, None], torch.ones(T, 1, dtype=pred.dtype, device=pred.device), None,
+                                                   true_y, torch.where(lab, task, torch.full_like(task, -1)), kind)[0]}
+        for m in metrics:
+            results[m] = per_task(true_y, pred_y, torch.where(lab, task, torch.full_like(task, -1)), table[m], T)
+            defined = [float(v) for v in results[m] if not math.isnan(float(v))]
+            results[m + '_mean'] = sum(defined) / len(defined) if defined else float("nan")
+        results['pred_y'], results['true_y'], results['task'] = pred_y, true_y, task
         return results
     finally:
         model.train(was_training)
