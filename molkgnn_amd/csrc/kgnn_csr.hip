@@ -8,7 +8,8 @@
 //
 // These passes are latency bound, not bandwidth bound, when written one row per wave with the
 // rowptr -> index -> row dependency chain exposed (three round trips per row: measured 48 us for 140 MB).
-// Here a row of W <= 256 floats is held by LPR = 8/16/32/64 lanes (one float4 each), a wave works on
+// Here a row of W <= 256 floats is held by LPR = 8/16/32/64 lanes (one float4 each; or by half as many with two
+// float4 each where that is faster: csr_chunks below), a wave works on
 // 64 / LPR rows at once, and the chain is software pipelined two deep: while the rows of group g are
 // in flight, the indices of group g + 1 and the row pointers of group g + 2 are fetched, so one group
 // costs one round trip.  All loads are unconditional (clamped addresses, masked values): a load under
@@ -21,6 +22,7 @@
 #include "kgnn_launch.h"
 #include "kgnn_split.h"
 
+#include <atomic>
 #include <type_traits>
 
 namespace mkgnn {
@@ -73,16 +75,31 @@ __device__ __forceinline__ f32x4 mask_cols(f32x4 v, int col, int width) {
 //          block in memory is never used: the producer need not zero it);
 // BLK = 2: the written rows are block rows -- only the columns of the destination's own block are summed and stored.
 // The loads stay unconditional: see row_load.
-template <int LPR, bool GATHER, int BLK = 0>
+//
+// CPL = chunks of sixteen bytes per lane.  Lane l of a row's LPR lanes holds chunk l and, CPL = 2, chunk l + LPR (columns 4 l and
+// 4 (l + LPR)): a row of W floats takes half the lanes, a wave twice the rows per group, and everything that is per (lane, row)
+// -- the row pointers, the index broadcast, the row id decode and the 64-bit row address, the norm's and the dot product's
+// tail, the store's row address -- is paid once per two chunks; the loads, adds, masks and conversions stay per chunk.
+// The results are the bits of CPL = 1 on 2 LPR lanes: the segment sums are per element, and a row reduction there begins by
+// adding the values of lanes l and l + LPR (the xor tree's first step, offset LPR) and goes on with offsets LPR / 2 .. 1 --
+// here the lane adds its two chunks' values itself (the same two operands; an fp32 add commutes) and group_sum<LPR> does the
+// rest.  A chunk beyond the width contributes +0 in both forms.
+template <int LPR, bool GATHER, int BLK = 0, int CPL = 1>
 __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
     static_assert(!(GATHER && BLK), "block rows: segment sums only");
+    static_assert(CPL == 1 || CPL == 2, "one or two chunks per lane");
     constexpr int RPW = 64 / LPR, SEG = 4;
     static_assert(LPR >= SEG, "one index per lane of a row group");
     const int lane = threadIdx.x & 63;
     const int sub = lane / LPR, l = lane % LPR;
-    const int col = 4 * l;
-    const bool active = col < a.width;                  // this lane holds columns col .. col + 3
-    const int colc = active ? col : 0;
+    int col[CPL], colc[CPL];
+    bool active[CPL];                                   // this lane holds columns col[q] .. col[q] + 3
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) {
+        col[q] = 4 * (l + q * LPR);
+        active[q] = col[q] < a.width;
+        colc[q] = active[q] ? col[q] : 0;
+    }
     // 32-bit row / group arithmetic throughout (the host launches these kernels for n < 2^31 - 2^20 rows; rowptr is
     // int32 anyway): the 64-bit compares and multiply-adds of the index bookkeeping were a third of the VALU work,
     // and the VALU is ~50 % busy in these kernels (PMC: 436 VALU instructions per wave for 3 groups of 2 rows).
@@ -108,54 +125,78 @@ __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
         b0 = (int)((a.blk_off >> (8 * (d & 7))) & 0xFF);
         b1 = b0 + (int)((a.blk_len >> (8 * (d & 7))) & 0xFF);
     };
-    // BLK == 1: this lane's columns are fixed, so what it does with a source of degree d is too: which of its four
+    // BLK == 1: this lane's columns are fixed, so what it does with a source of degree d is too: which of a chunk's four
     // elements lie in block d (4 bits) and which 16 bytes it reads (its own, or the nearest of the block).  Both
-    // tables fit one register each (degrees 0..4, 4 resp. 6 bits per entry).
-    uint32_t keep_tab = 0, col_tab = 0;
+    // tables fit one register each per chunk (degrees 0..4, 4 resp. 6 bits per entry; entry 0 -- no block -- is zero).
+    uint32_t keep_tab[CPL], col_tab[CPL];
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) keep_tab[q] = col_tab[q] = 0;
     if constexpr (BLK == 1) {
 #pragma unroll
         for (int d = 1; d <= 4; ++d) {
             int b0, b1;
             block_of(d, b0, b1);
-            uint32_t m = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) m |= (uint32_t)(col + c >= b0 && col + c < b1) << c;
             const int lo4 = b0 & ~3, hi4 = (b1 - 1) & ~3;
-            int cc = colc < lo4 ? lo4 : (colc > hi4 ? hi4 : colc);
-            if (b1 <= b0) cc = 0;
-            keep_tab |= m << (4 * d);
-            col_tab |= (uint32_t)(cc >> 2) << (6 * d);
+#pragma unroll
+            for (int q = 0; q < CPL; ++q) {
+                // bits c with b0 <= col + c < b1: a run from lo to hi - 1 (once per wave, but a wave walks only a few groups)
+                const int lo = min(max(b0 - col[q], 0), 4), hi = min(max(b1 - col[q], 0), 4);
+                const uint32_t m = hi > lo ? (1u << hi) - (1u << lo) : 0u;
+                int cc = colc[q] < lo4 ? lo4 : (colc[q] > hi4 ? hi4 : colc[q]);
+                if (b1 <= b0) cc = 0;
+                keep_tab[q] |= m << (4 * d);
+                col_tab[q] |= (uint32_t)(cc >> 2) << (6 * d);
+            }
         }
     }
-    // A lane whose four columns miss the block reads the nearest 16 bytes of the block instead -- the same cache
+    // A chunk whose four columns miss the block reads the nearest 16 bytes of the block instead -- the same cache
     // lines the other lanes of its row fetch, so it adds no traffic (a fixed dummy address made one hot spot of a
     // few lines that every wave hammered) -- and its value is masked / never stored.
-    auto row_load = [&](int rid_raw, int dst_b0, int dst_b1) -> f32x4 {
-        int row = rid_raw, c = colc;
+    auto row_load = [&](int rid_raw, int dst_b0, int dst_b1, f32x4 (&v)[CPL]) {
+        int row = rid_raw, c[CPL];
+#pragma unroll
+        for (int q = 0; q < CPL; ++q) c[q] = colc[q];
         if constexpr (BLK == 1) {
-            const uint32_t d = (uint32_t)rid_raw >> 28;
+            const uint32_t d6 = 6 * ((uint32_t)rid_raw >> 28);
             row = rid_raw & 0x0FFFFFFF;
-            c = (int)((col_tab >> (6 * d)) & 63) << 2;
+#pragma unroll
+            for (int q = 0; q < CPL; ++q) c[q] = (int)((col_tab[q] >> d6) & 63) << 2;
         } else if constexpr (BLK == 2) {
             const int lo4 = dst_b0 & ~3, hi4 = (dst_b1 - 1) & ~3;
-            c = c < lo4 ? lo4 : (c > hi4 ? hi4 : c);
-            if (dst_b1 <= dst_b0) c = 0;                  // no block at all (atom in no bucket): any valid address
-        }
-#ifdef MKGNN_CSR_NT_LOAD                                  // (A/B build, not kept: 43.5 -> 44.6 us alone, the step unchanged)
-        if constexpr (GATHER) return __builtin_nontemporal_load((const f32x4*)(a.src + (uint64_t)(uint32_t)row * (uint32_t)a.ss + (uint32_t)c));
-#endif
-        return *(const f32x4*)(a.src + (uint64_t)(uint32_t)row * (uint32_t)a.ss + (uint32_t)c);      // one v_mad_u64_u32
-    };
-    // v where the source is valid and, BLK == 1, inside the source's own block; +0 elsewhere (bit masks: see keep_if)
-    auto row_keep = [&](f32x4 v, int rid_raw, bool valid) -> f32x4 {
-        if constexpr (BLK == 1) {
-            const int m = valid ? (int)(keep_tab >> (4 * ((uint32_t)rid_raw >> 28))) : 0;
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-                v[c] = __uint_as_float(__float_as_uint(v[c]) & (uint32_t)__builtin_amdgcn_sbfe(m, c, 1));   // bit c -> 0 / ~0
-            return v;
+            for (int q = 0; q < CPL; ++q) {
+                c[q] = c[q] < lo4 ? lo4 : (c[q] > hi4 ? hi4 : c[q]);
+                if (dst_b1 <= dst_b0) c[q] = 0;           // no block at all (atom in no bucket): any valid address
+            }
+        }
+        const float* base = a.src + (uint64_t)(uint32_t)row * (uint32_t)a.ss;                       // once per (lane, row)
+#pragma unroll
+        for (int q = 0; q < CPL; ++q) {
+#ifdef MKGNN_CSR_NT_LOAD                                  // (A/B build, not kept: 43.5 -> 44.6 us alone, the step unchanged)
+            if constexpr (GATHER) { v[q] = __builtin_nontemporal_load((const f32x4*)(base + (uint32_t)c[q])); continue; }
+#endif
+            v[q] = *(const f32x4*)(base + (uint32_t)c[q]);
+        }
+    };
+    // acc (+)= v where the source is valid and, BLK == 1, inside the source's own block; +0 elsewhere (bit masks: see keep_if)
+    auto row_keep = [&](const f32x4 (&v)[CPL], int rid_raw, bool valid, f32x4 (&acc)[CPL], bool first) {
+        if constexpr (BLK == 1) {
+            const uint32_t d4 = valid ? 4 * ((uint32_t)rid_raw >> 28) : 0;          // (entry 0 of keep_tab keeps nothing)
+#pragma unroll
+            for (int q = 0; q < CPL; ++q) {
+                const int m = (int)(keep_tab[q] >> d4);
+                f32x4 w = v[q];
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    w[c] = __uint_as_float(__float_as_uint(w[c]) & (uint32_t)__builtin_amdgcn_sbfe(m, c, 1));   // bit c -> 0 / ~0
+                acc[q] = first ? w : acc[q] + w;
+            }
         } else {
-            return keep_if(v, valid);
+#pragma unroll
+            for (int q = 0; q < CPL; ++q) {
+                const f32x4 w = keep_if(v[q], valid);
+                acc[q] = first ? w : acc[q] + w;
+            }
         }
     };
     // The SEG indices of a row: ONE load instruction per wave -- lane l of the row's group fetches entry
@@ -193,69 +234,101 @@ __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
         if constexpr (BLK == 2) block_of(dg_c, d0, d1);
         int rid_c[SEG];
         idx_bcast(mine_c, rid_c);
-        f32x4 v[SEG];
+        f32x4 v[SEG][CPL];
 #pragma unroll
-        for (int u = 0; u < K; ++u) v[u] = row_load(rid_c[u], d0, d1);
-        f32x4 xv;
+        for (int u = 0; u < K; ++u) row_load(rid_c[u], d0, d1, v[u]);
+        f32x4 xv[CPL];
         float iv = 0.f;
         if constexpr (GATHER) {
-            xv = *(const f32x4*)(a.x + (uint64_t)(uint32_t)j_c * (uint32_t)a.xs + colc);
+            const float* xrow = a.x + (uint64_t)(uint32_t)j_c * (uint32_t)a.xs;
+#pragma unroll
+            for (int q = 0; q < CPL; ++q) xv[q] = *(const f32x4*)(xrow + colc[q]);
             iv = a.inv[j_c];
         }
         mine_n = idx_issue(lo_n, hi_n, lo_n);
         j_nn = segment(g + 2 * nwaves, lo_nn, hi_nn, dg_nn);
         // ---- consume
-        f32x4 acc = row_keep(v[0], rid_c[0], lo_c < hi_c);
+        f32x4 acc[CPL];
+        row_keep(v[0], rid_c[0], lo_c < hi_c, acc, true);
 #pragma unroll
-        for (int u = 1; u < K; ++u) acc += row_keep(v[u], rid_c[u], lo_c + u < hi_c);
+        for (int u = 1; u < K; ++u) row_keep(v[u], rid_c[u], lo_c + u < hi_c, acc, false);
         if (K == SEG && __any(hi_c - lo_c > SEG)) {                 // long segments: rare (more than four bonds / five roles)
             for (int k0 = lo_c + SEG; __any(k0 < hi_c); k0 += SEG) {
                 int rid[SEG];
                 idx_bcast(idx_issue(lo_c, hi_c, k0), rid);
-                f32x4 w[SEG];
+                f32x4 w[SEG][CPL];
 #pragma unroll
-                for (int u = 0; u < SEG; ++u) w[u] = row_load(rid[u], d0, d1);
+                for (int u = 0; u < SEG; ++u) row_load(rid[u], d0, d1, w[u]);
 #pragma unroll
-                for (int u = 0; u < SEG; ++u) acc += row_keep(w[u], rid[u], k0 + u < hi_c);
+                for (int u = 0; u < SEG; ++u) row_keep(w[u], rid[u], k0 + u < hi_c, acc, false);
             }
         }
-        acc = mask_cols(acc, active ? col : a.width, a.width);
+#pragma unroll
+        for (int q = 0; q < CPL; ++q) acc[q] = mask_cols(acc[q], active[q] ? col[q] : a.width, a.width);
         const bool row_ok = g * RPW + sub < n;
         if constexpr (GATHER) {
             // d/dx of x / max(|x|, eps): (acc - (acc . xh) xh) * inv, or acc * inv where the clamp is active
             // (pre-split rows: hi + lo is the scaled row to 2^-22 of an element; the power of two leaves through 1 / |x|)
-            if (a.x_split) { xv = split_row_value(xv); }
-            f32x4 xh = mask_cols(xv, active ? col : a.width, a.width) * (a.x_split ? split_row_inv(iv) : iv);
-            float dotp = acc[0] * xh[0];
-            dotp = fmaf(acc[1], xh[1], dotp); dotp = fmaf(acc[2], xh[2], dotp); dotp = fmaf(acc[3], xh[3], dotp);
+            const float xscale = a.x_split ? split_row_inv(iv) : iv;
+            f32x4 xh[CPL];
+            float dotp = 0.f;
+#pragma unroll
+            for (int q = 0; q < CPL; ++q) {
+                if (a.x_split) { xv[q] = split_row_value(xv[q]); }
+                xh[q] = mask_cols(xv[q], active[q] ? col[q] : a.width, a.width) * xscale;
+                float dq = acc[q][0] * xh[q][0];
+                dq = fmaf(acc[q][1], xh[q][1], dq); dq = fmaf(acc[q][2], xh[q][2], dq); dq = fmaf(acc[q][3], xh[q][3], dq);
+                dotp = q == 0 ? dq : dotp + dq;                     // the tree's first step (offset LPR) of the one-chunk form
+            }
             dotp = group_sum<LPR>(dotp);
             const bool clamped = iv >= (1.f / MKGNN_EPS);
-            f32x4 r;
+            float* dst = a.out + (uint64_t)(uint32_t)j_c * (uint32_t)a.os;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) r[c] = clamped ? acc[c] * iv : (acc[c] - dotp * xh[c]) * iv;
-            if (row_ok && active) *(f32x4*)(a.out + (uint64_t)(uint32_t)j_c * (uint32_t)a.os + col) = r;
+            for (int q = 0; q < CPL; ++q) {
+                f32x4 r;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) r[c] = clamped ? acc[q][c] * iv : (acc[q][c] - dotp * xh[q][c]) * iv;
+                if (row_ok && active[q]) *(f32x4*)(dst + col[q]) = r;
+            }
         } else if constexpr (BLK == 2) {
             // only the destination's own block is defined; the rest of its row is left as it is
-            if (row_ok && active && col + 3 >= d0 && col < d1) {
-                float* dst = a.out + (uint64_t)(uint32_t)j_c * (uint32_t)a.os + col;
-                if (col >= d0 && col + 3 < d1) *(f32x4*)dst = acc;
-                else {
+            float* drow = a.out + (uint64_t)(uint32_t)j_c * (uint32_t)a.os;
 #pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (col + c >= d0 && col + c < d1) dst[c] = acc[c];
+            for (int q = 0; q < CPL; ++q) {
+                if (row_ok && active[q] && col[q] + 3 >= d0 && col[q] < d1) {
+                    float* dst = drow + col[q];
+                    if (col[q] >= d0 && col[q] + 3 < d1) *(f32x4*)dst = acc[q];
+                    else {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c)
+                            if (col[q] + c >= d0 && col[q] + c < d1) dst[c] = acc[q][c];
+                    }
                 }
             }
         } else {
-            f32x4 stored = acc;                                     // alignment padding is written as zero
+            f32x4 stored[CPL];                                      // alignment padding is written as zero
+#pragma unroll
+            for (int q = 0; q < CPL; ++q) stored[q] = acc[q];
             if (a.inv_out) {
-                float ss = acc[0] * acc[0];
-                ss = fmaf(acc[1], acc[1], ss); ss = fmaf(acc[2], acc[2], ss); ss = fmaf(acc[3], acc[3], ss);
+                float ss = 0.f;
+#pragma unroll
+                for (int q = 0; q < CPL; ++q) {
+                    float sq = acc[q][0] * acc[q][0];
+                    sq = fmaf(acc[q][1], acc[q][1], sq); sq = fmaf(acc[q][2], acc[q][2], sq); sq = fmaf(acc[q][3], acc[q][3], sq);
+                    ss = q == 0 ? sq : ss + sq;                     // the tree's first step (offset LPR) of the one-chunk form
+                }
                 ss = group_sum<LPR>(ss);
                 const float inv = 1.f / fmaxf(sqrtf(ss), MKGNN_EPS);
                 if (row_ok && l == 0) a.inv_out[j_c] = inv;
-                if (a.split_out) stored = split_row_store(acc, inv);
+                if (a.split_out) {
+#pragma unroll
+                    for (int q = 0; q < CPL; ++q) stored[q] = split_row_store(acc[q], inv);
+                }
             }
-            if (row_ok && active) *(f32x4*)(a.out + (uint64_t)(uint32_t)j_c * (uint32_t)a.os + col) = stored;
+            float* dst = a.out + (uint64_t)(uint32_t)j_c * (uint32_t)a.os;
+#pragma unroll
+            for (int q = 0; q < CPL; ++q)
+                if (row_ok && active[q]) *(f32x4*)(dst + col[q]) = stored[q];
         }
     };
     for (; g < ngroups; g += nwaves) {
@@ -363,31 +436,69 @@ bool try_rows_presplit(const float* x, int64_t xs, int64_t n, int width, float* 
 }
 
 
-template <bool GATHER>
-static hipError_t launch_csr(const CsrArgs& a_in, hipStream_t st) {
+// Chunks per lane (CPL) of a csr_rows_kernel launch.  Two chunks cut the per-(lane, row) vector work but make K -- the row
+// loads a group issues, the longest segment among the wave's rows -- the maximum over twice the rows, so each kind of launch
+// takes what was measured faster inside the training step (DESIGN 4.3 has the table):
+//   `propagate` on block rows (BLK = 1, modes 1 and 3): two -- 23 % fewer vector instructions per row in the loop on the
+//       benchmark's batch (mean K 2.51 -> 2.86 included), 27.8 -> 23.4 us and 22.6 -> 19.5 us in the step;
+//   the backward gather: one -- two chunks issue 13 % (width 110) and 25 % (width 28) fewer vector instructions per launch and
+//       take 66.9 -> 68.0, 63.3 -> 64.9 and 20.1 -> 23.2 us in the step: these launches are not bound by vector issue (231 MB
+//       per launch beside the bank kernel; half as many waves to hide the latency with; mean K 3.43 -> 3.70 of 4);
+//   dense sums and BLK = 2: one (not in the step's chain, not measured).
+// MKGNN_CSR_CPL=1 / 2 and mkgnn_debug_set_csr_chunks (tests; it wins over the environment) force one form for every launch;
+// the results are the same bits either way.
+#ifndef MKGNN_CSR_CPL_GATHER
+#define MKGNN_CSR_CPL_GATHER 1
+#endif
+#ifndef MKGNN_CSR_CPL_BLOCKS_IN
+#define MKGNN_CSR_CPL_BLOCKS_IN 2
+#endif
+#ifndef MKGNN_CSR_CPL_OTHER
+#define MKGNN_CSR_CPL_OTHER 1
+#endif
+static std::atomic<int> g_csr_chunks_override{0};
+extern "C" int mkgnn_debug_set_csr_chunks(int32_t chunks) {
+    g_csr_chunks_override.store(chunks == 1 || chunks == 2 ? chunks : 0);      // anything else: back to the default
+    return 0;
+}
+
+template <bool GATHER, int BLK>
+static inline int csr_chunks() {
+    int forced = g_csr_chunks_override.load();
+    if (!forced) forced = switches().csr_cpl;
+    if (forced == 1 || forced == 2) return forced;
+    return GATHER ? MKGNN_CSR_CPL_GATHER : BLK == 1 ? MKGNN_CSR_CPL_BLOCKS_IN : MKGNN_CSR_CPL_OTHER;
+}
+
+// lanes_per_row(width) lanes hold a row one chunk each; with two chunks per lane half as many do
+template <bool GATHER, int BLK>
+static hipError_t launch_csr_rows(const CsrArgs& a_in, hipStream_t st) {
     CsrArgs a = a_in;
     a.fixed4 = switches().csr_fixed4;
-    switch (lanes_per_row(a.width)) {
-        case 8: csr_rows_kernel<8, GATHER><<<csr_grid(a.n, 8), 256, 0, st>>>(a); break;
-        case 16: csr_rows_kernel<16, GATHER><<<csr_grid(a.n, 4), 256, 0, st>>>(a); break;
-        case 32: csr_rows_kernel<32, GATHER><<<csr_grid(a.n, 2), 256, 0, st>>>(a); break;
-        default: csr_rows_kernel<64, GATHER><<<csr_grid(a.n, 1), 256, 0, st>>>(a); break;
+    const int lpr = lanes_per_row(a.width);
+    if (csr_chunks<GATHER, BLK>() == 2) {
+        switch (lpr) {
+            case 8: csr_rows_kernel<4, GATHER, BLK, 2><<<csr_grid(a.n, 16), 256, 0, st>>>(a); break;
+            case 16: csr_rows_kernel<8, GATHER, BLK, 2><<<csr_grid(a.n, 8), 256, 0, st>>>(a); break;
+            case 32: csr_rows_kernel<16, GATHER, BLK, 2><<<csr_grid(a.n, 4), 256, 0, st>>>(a); break;
+            default: csr_rows_kernel<32, GATHER, BLK, 2><<<csr_grid(a.n, 2), 256, 0, st>>>(a); break;
+        }
+    } else {
+        switch (lpr) {
+            case 8: csr_rows_kernel<8, GATHER, BLK><<<csr_grid(a.n, 8), 256, 0, st>>>(a); break;
+            case 16: csr_rows_kernel<16, GATHER, BLK><<<csr_grid(a.n, 4), 256, 0, st>>>(a); break;
+            case 32: csr_rows_kernel<32, GATHER, BLK><<<csr_grid(a.n, 2), 256, 0, st>>>(a); break;
+            default: csr_rows_kernel<64, GATHER, BLK><<<csr_grid(a.n, 1), 256, 0, st>>>(a); break;
+        }
     }
     return hipGetLastError();
 }
 
+template <bool GATHER>
+static hipError_t launch_csr(const CsrArgs& a, hipStream_t st) { return launch_csr_rows<GATHER, 0>(a, st); }
+
 template <int BLK>
-static hipError_t launch_csr_blocks(const CsrArgs& a_in, hipStream_t st) {
-    CsrArgs a = a_in;
-    a.fixed4 = switches().csr_fixed4;
-    switch (lanes_per_row(a.width)) {
-        case 8: csr_rows_kernel<8, false, BLK><<<csr_grid(a.n, 8), 256, 0, st>>>(a); break;
-        case 16: csr_rows_kernel<16, false, BLK><<<csr_grid(a.n, 4), 256, 0, st>>>(a); break;
-        case 32: csr_rows_kernel<32, false, BLK><<<csr_grid(a.n, 2), 256, 0, st>>>(a); break;
-        default: csr_rows_kernel<64, false, BLK><<<csr_grid(a.n, 1), 256, 0, st>>>(a); break;
-    }
-    return hipGetLastError();
-}
+static hipError_t launch_csr_blocks(const CsrArgs& a, hipStream_t st) { return launch_csr_rows<false, BLK>(a, st); }
 
 // Block-row segment sums (see csr_rows_kernel): no fallback, the caller checks segment_sum_blocks_supported first.
 bool segment_sum_blocks_supported(const float* in, int64_t is, int64_t n, int width, const float* out, int64_t os) {
@@ -432,6 +543,16 @@ bool try_backward_gather_aligned(const float* contrib, int64_t cs, const int32_t
     a.x = x; a.xs = xs; a.inv = inv; a.x_split = x_split ? 1 : 0;
     *err = launch_csr<true>(a, st);
     return true;
+}
+
+// tests: the pipelined gather on buffers the caller owns (the library runs it behind mkgnn_kernelsetconv_backward only);
+// -1 where the fast path declines (width, alignment), nothing launched
+extern "C" int mkgnn_debug_backward_gather(const float* contrib, int64_t cs, const int32_t* rowptr, const int32_t* rows, const float* x,
+                                           int64_t xs, const float* inv, int64_t n, int32_t F, float* gx, int64_t gxs, int32_t x_split,
+                                           void* stream) {
+    hipError_t e = hipSuccess;
+    if (!try_backward_gather_aligned(contrib, cs, rowptr, rows, x, xs, inv, n, F, gx, gxs, (hipStream_t)stream, &e, x_split != 0)) return -1;
+    return e == hipSuccess ? 0 : 1;
 }
 
 bool try_row_inv_norm_aligned(const float* x, int64_t xs, int64_t n, int width, float* inv, hipStream_t st, hipError_t* err) {

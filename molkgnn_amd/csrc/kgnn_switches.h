@@ -44,6 +44,7 @@ struct Switches {        // (bool: is set, or on unless the value starts with '0
     int bank_blocks;          // MKGNN_BANK_BLOCKS: blocks of the per-degree LDS bank kernel (0: unset; the launch checks the range)
     int csr_blocks;           // MKGNN_CSR_BLOCKS: grid cap of the segment-sum / gather kernels (unset: 4096)
     int csr_fixed4;           // MKGNN_CSR_FIXED4: fixed-degree variant of the pipelined gather (unset: 0)
+    int csr_cpl;              // MKGNN_CSR_CPL: 1 / 2 = every segment-sum / gather launch with one / two row chunks per lane (unset: per kind)
     bool stream_cost_set;     // MKGNN_STREAM_COST: cost per tile and degree for the streamed forward's block split (all four parsed)
     double stream_cost[4];
 };
@@ -65,6 +66,7 @@ inline const Switches& switches() {
         s.fwd_pair = number("MKGNN_FWD_PAIR", MKGNN_FWD_PAIR_DEFAULT); s.bank_blocks = number("MKGNN_BANK_BLOCKS", 0);
         s.rows_stream_blocks = number("MKGNN_ROWS_STREAM_BLOCKS", 0); s.bank_stream_blocks = number("MKGNN_BANK_STREAM_BLOCKS", 0);
         s.csr_blocks = number("MKGNN_CSR_BLOCKS", 256 * 16); s.csr_fixed4 = number("MKGNN_CSR_FIXED4", 0);
+        s.csr_cpl = number("MKGNN_CSR_CPL", 0);
         if (const char* e = getenv("MKGNN_STREAM_COST"))
             s.stream_cost_set = sscanf(e, "%lf,%lf,%lf,%lf", &s.stream_cost[0], &s.stream_cost[1], &s.stream_cost[2], &s.stream_cost[3]) == 4;
         return s;
