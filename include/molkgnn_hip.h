@@ -660,6 +660,21 @@ int mkgnn_task_head_fused(int32_t loss_kind, const float* emb, int64_t emb_strid
                           float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
                           float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (additive; the ABI version stays 8) Every task's logit of every row -- the T-output ffn behind the readout in evaluation mode,
+ * for ranking a library per assay:
+ *     pred[i * pred_row_stride + t * pred_task_stride] = emb_i . weight[t] + bias[t]      for every i < n_rows, t < T
+ * weight [T, H], bias [T] or NULL (then +0.0 is added).  pred[i, t] is BIT FOR BIT what mkgnn_task_head_forward writes for row i
+ * when that row is labelled with task t, at dropout_p = 0, for any loss kind: the same products (lane h: emb[h] * w[t][h], then
+ * fmaf(emb[32 + h], w[t][32 + h], .) for H > 32, +0.0 at lanes >= H), the same xor tree over the 32 lanes (offsets 16, 8, 4, 2, 1),
+ * the bias added last.  Either output layout: [n_rows, T] rows (pred_task_stride = 1, pred_row_stride >= T) or [T, n_rows]
+ * task-major (pred_row_stride = 1, pred_task_stride >= n_rows) -- any pair of positive strides under which no two (i, t) share
+ * an element; nothing else of pred is written.  One launch on `stream`, capturable; no workspace, no atomics, no process-wide
+ * state, one writer per output.  The task head's limits: 1 <= T <= MKGNN_TASK_HEAD_MAX_TASKS, 1 <= H <= 64, emb_stride >= H;
+ * anything else returns non-zero with mkgnn_last_error set.  n_rows == 0 is a no-op that returns 0. */
+int mkgnn_task_scores(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                      const float* weight, const float* bias, float* pred, int64_t pred_row_stride, int64_t pred_task_stride,
+                      void* stream);
+
 /* AdamW step over all trainable tensors of the model in one launch (reference model.py:368-385: torch.optim.AdamW,
  * two parameter groups -- kernel banks without weight decay).  Per tensor: param / grad [numel] fp32 contiguous,
  * state [mkgnn_adamw_state_floats(numel)] = exp_avg, exp_avg_sq, step count (as a float, advanced by this call), two reserved
@@ -915,6 +930,21 @@ size_t mkgnn_topk_workspace_bytes(int32_t B, int32_t K);
 int mkgnn_topk_update(const float* scores, const int32_t* ids, int32_t B, const int32_t* n_valid, const int32_t* shard_tag,
                       int32_t K, float* top_score, int32_t* top_shard, int32_t* top_mol, void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/* (additive; the ABI version stays 8) T running lists in one update -- a library ranked per assay of a multi-task model.  List t
+ * is slots [t * K, (t + 1) * K) of top_score / top_shard / top_mol ([T, K], contiguous); after the call it is exactly what
+ * mkgnn_topk_update would make of that list and the scores  scores[i * score_row_stride + t * score_task_stride]  (a [B, T] or a
+ * [T, B] tensor, or any other strides; a negative stride is rejected): the same total order, empty slots, copied score bits and
+ * stability rule.  ids, *n_valid and *shard_tag are the same for every task: every molecule enters every task's list.  The
+ * kernels of mkgnn_topk_update with the task on the grid's second dimension: one launch for B <= 1024, two beyond; blocks of
+ * different tasks share nothing, the runs of task t lie at their own offset of the workspace (16-byte aligned,
+ * mkgnn_topk_tasks_workspace_bytes(B, K, T) bytes, read only where the same call wrote it).  Any B >= 1, 1 <= K <= MKGNN_TOPK_MAX_K,
+ * 1 <= T <= MKGNN_TASK_HEAD_MAX_TASKS; everything else is rejected before a launch and has workspace size 0. */
+size_t mkgnn_topk_tasks_workspace_bytes(int32_t B, int32_t K, int32_t T);
+int mkgnn_topk_update_tasks(const float* scores, int64_t score_row_stride, int64_t score_task_stride, const int32_t* ids,
+                            int32_t B, int32_t T, const int32_t* n_valid, const int32_t* shard_tag, int32_t K,
+                            float* top_score, int32_t* top_shard, int32_t* top_mol, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 #ifdef __cplusplus
 }

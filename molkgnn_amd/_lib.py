@@ -170,7 +170,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_head_loss_forward", "mkgnn_head_loss_backward", "mkgnn_head_loss_dropout_forward",
            "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused", "mkgnn_gather_compact",
            "mkgnn_gather_compact_workspace_bytes", "mkgnn_gather_compact_packed", "mkgnn_topk_update", "mkgnn_topk_workspace_bytes",
-           "mkgnn_task_head_workspace_bytes", "mkgnn_task_head_forward", "mkgnn_task_head_backward", "mkgnn_task_head_fused")
+           "mkgnn_task_head_workspace_bytes", "mkgnn_task_head_forward", "mkgnn_task_head_backward", "mkgnn_task_head_fused",
+           "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -277,6 +278,12 @@ def load() -> C.CDLL:
     lib.mkgnn_topk_update.restype = C.c_int
     lib.mkgnn_topk_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    # T lists in one update: (scores, row stride, task stride, ids, B, T, n_valid, shard_tag, K, the [T, K] lists, workspace, stream)
+    lib.mkgnn_topk_tasks_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_topk_tasks_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.mkgnn_topk_update_tasks.restype = C.c_int
+    lib.mkgnn_topk_update_tasks.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mkgnn_expand_batch.restype = C.c_int
     lib.mkgnn_expand_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -347,6 +354,9 @@ def load() -> C.CDLL:
     lib.mkgnn_task_head_fused.restype = C.c_int
     lib.mkgnn_task_head_fused.argtypes = [I32, P, I64, I64, I32, I32, P, P, P, P, P, I64, C.c_float, P, P, P, P, P, I64, P, P, P,
                                           C.c_size_t, P]
+    # every task's logit of every row: (emb, stride, n_rows, H, T, weight, bias, pred, row stride, task stride, stream)
+    lib.mkgnn_task_scores.restype = C.c_int
+    lib.mkgnn_task_scores.argtypes = [P, I64, I64, I32, I32, P, P, P, I64, I64, P]
     lib.mkgnn_rf_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_rf_workspace_bytes.argtypes = [I64]
     lib.mkgnn_rf_count.restype = C.c_int

@@ -15,6 +15,12 @@
 //                       only tile itself: one launch.
 // Integers only (scores are compared through their bit patterns), no atomics, no process-wide state; n_valid and shard_tag are
 // read on the device.  Slot t of the list is written by thread t alone.
+//
+// mkgnn_topk_update_tasks: T lists in one update (a library ranked per assay of a multi-task model).  The same two kernels with the
+// task on blockIdx.y -- topk_runs_kernel on a (tiles, T) grid, topk_merge_kernel on a (1, T) grid: block (., y) reads the scores
+// scores[i * row_stride + y * task_stride], list y ([T, K] arrays) and the runs of task y (their own n_tiles * Kp entries of the
+// workspace).  Blocks of different tasks share nothing; the pass-over verdict is uniform inside a block, as before.
+// mkgnn_topk_update is the T = 1 call of the same launcher (strides 1 and 0).
 #include <cstdint>
 #include "kgnn_launch.h"
 #include "../../include/molkgnn_hip.h"
@@ -83,13 +89,15 @@ __device__ __forceinline__ int clamp_valid(const int32_t* n_valid, int32_t B) {
 }
 
 // batch slot i as an entry (position Kpos + i); slots at or past nv rank as empty slots behind everything
-__device__ __forceinline__ Entry batch_entry(const float* scores, const int32_t* ids, int32_t tag, int64_t i, int32_t nv, int32_t K) {
+__device__ __forceinline__ Entry batch_entry(const float* scores, int64_t row_stride, const int32_t* ids, int32_t tag, int64_t i,
+                                             int32_t nv, int32_t K) {
     const uint32_t pos = (uint32_t)K + (uint32_t)i;
     if (i >= nv) return empty_entry(pos);
-    return Entry{__float_as_uint(scores[i]), tag, ids[i], pos};
+    return Entry{__float_as_uint(scores[i * row_stride]), tag, ids[i], pos};
 }
 
-__global__ void __launch_bounds__(TOPK_THREADS) topk_runs_kernel(const float* __restrict__ scores, const int32_t* __restrict__ ids,
+__global__ void __launch_bounds__(TOPK_THREADS) topk_runs_kernel(const float* __restrict__ scores, int64_t row_stride,
+                                                                 int64_t task_stride, const int32_t* __restrict__ ids,
                                                                  int32_t B, const int32_t* __restrict__ n_valid,
                                                                  const int32_t* __restrict__ shard_tag, int32_t K, int32_t Kp,
                                                                  uint4* __restrict__ runs) {
@@ -98,12 +106,15 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_runs_kernel(const float* __
     const int64_t i0 = (int64_t)blockIdx.x * TOPK_TILE;
     if (i0 >= nv) return;                                // (uniform: the merge passes this tile over as well)
     int flip = 0;
-    Entry e = batch_entry(scores, ids, *shard_tag, i0 + threadIdx.x, nv, K);
+    scores += (int64_t)blockIdx.y * task_stride;         // (the task's scores and its own runs)
+    runs += (size_t)blockIdx.y * gridDim.x * Kp;
+    Entry e = batch_entry(scores, row_stride, ids, *shard_tag, i0 + threadIdx.x, nv, K);
     sort_tile(e, buf, flip);
     if ((int)threadIdx.x < Kp) runs[(size_t)blockIdx.x * Kp + threadIdx.x] = pack(e);
 }
 
-__global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float* __restrict__ scores, const int32_t* __restrict__ ids,
+__global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float* __restrict__ scores, int64_t row_stride,
+                                                                  int64_t task_stride, const int32_t* __restrict__ ids,
                                                                   int32_t B, const int32_t* __restrict__ n_valid,
                                                                   const int32_t* __restrict__ shard_tag, int32_t K, int32_t Kp,
                                                                   float* top_score, int32_t* top_shard, int32_t* top_mol,
@@ -113,6 +124,9 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float* _
     const int t = threadIdx.x;
     const int nv = clamp_valid(n_valid, B);
     int flip = 0;
+    scores += (int64_t)blockIdx.y * task_stride;         // (the task's scores, its list and its own runs)
+    top_score += (size_t)blockIdx.y * K; top_shard += (size_t)blockIdx.y * K; top_mol += (size_t)blockIdx.y * K;
+    runs += (size_t)blockIdx.y * n_tiles * Kp;
     // the old list: slot t in thread t; the slots from K to the tile's end rank behind every real slot
     Entry cur = empty_entry(0xFFFFFFFFu);
     if (t < K) cur = Entry{__float_as_uint(top_score[t]), top_shard[t], top_mol[t], (uint32_t)t};
@@ -121,7 +135,7 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float* _
         if (i0 >= nv) break;
         Entry run;                                       // thread t: entry Kp - 1 - t of the tile's sorted run (t < Kp)
         if (n_tiles == 1) {
-            Entry e = batch_entry(scores, ids, *shard_tag, i0 + t, nv, K);
+            Entry e = batch_entry(scores, row_stride, ids, *shard_tag, i0 + t, nv, K);
             sort_tile(e, buf, flip);
             buf[flip][t] = pack(e);
             if (t == K - 1) last = pack(cur);
@@ -157,32 +171,52 @@ inline size_t n_tiles_of(int32_t B) { return ((size_t)B + TOPK_TILE - 1) / TOPK_
 
 using namespace mkgnn;
 
-extern "C" size_t mkgnn_topk_workspace_bytes(int32_t B, int32_t K) {
-    if (B < 1 || K < 1 || K > MKGNN_TOPK_MAX_K) return 0;
+extern "C" size_t mkgnn_topk_tasks_workspace_bytes(int32_t B, int32_t K, int32_t T) {
+    if (B < 1 || K < 1 || K > MKGNN_TOPK_MAX_K || T < 1 || T > MKGNN_TASK_HEAD_MAX_TASKS) return 0;
     const size_t tiles = n_tiles_of(B);
-    return 256 + (tiles > 1 ? tiles * (size_t)pow2_at_least(K) * sizeof(uint4) : 0);
+    return 256 + (tiles > 1 ? (size_t)T * tiles * (size_t)pow2_at_least(K) * sizeof(uint4) : 0);
 }
 
-extern "C" int mkgnn_topk_update(const float* scores, const int32_t* ids, int32_t B, const int32_t* n_valid, const int32_t* shard_tag,
-                                 int32_t K, float* top_score, int32_t* top_shard, int32_t* top_mol, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-    const char* who = "mkgnn_topk_update";
+extern "C" size_t mkgnn_topk_workspace_bytes(int32_t B, int32_t K) { return mkgnn_topk_tasks_workspace_bytes(B, K, 1); }
+
+// the one launcher: T lists, the task on the grid's second dimension
+static int topk_launch(const char* who, const float* scores, int64_t row_stride, int64_t task_stride, const int32_t* ids, int32_t B,
+                       int32_t T, const int32_t* n_valid, const int32_t* shard_tag, int32_t K, float* top_score, int32_t* top_shard,
+                       int32_t* top_mol, void* workspace, size_t workspace_bytes, void* stream) {
     if (!scores || !ids || !n_valid || !shard_tag || !top_score || !top_shard || !top_mol || !workspace)
         return api_fail("%s: null pointer", who);
     if (B < 1) return api_fail("%s: B = %d", who, (int)B);
     if (K < 1 || K > MKGNN_TOPK_MAX_K) return api_fail("%s: K = %d outside [1, %d]", who, (int)K, MKGNN_TOPK_MAX_K);
+    if (T < 1 || T > MKGNN_TASK_HEAD_MAX_TASKS) return api_fail("%s: T = %d outside [1, %d]", who, (int)T, MKGNN_TASK_HEAD_MAX_TASKS);
+    if (row_stride < 0 || task_stride < 0) return api_fail("%s: negative score stride", who);
     if ((uintptr_t)workspace % 16) return api_fail("%s: workspace must be 16-byte aligned", who);
-    if (workspace_bytes < mkgnn_topk_workspace_bytes(B, K)) return api_fail("%s: workspace too small", who);
+    if (workspace_bytes < mkgnn_topk_tasks_workspace_bytes(B, K, T)) return api_fail("%s: workspace too small", who);
     const int32_t Kp = pow2_at_least(K);
     const int tiles = (int)n_tiles_of(B);
     uint4* const runs = (uint4*)((char*)workspace + 256);
     hipStream_t st = (hipStream_t)stream;
     if (tiles > 1) {
-        topk_runs_kernel<<<tiles, TOPK_THREADS, 0, st>>>(scores, ids, B, n_valid, shard_tag, K, Kp, runs);
+        topk_runs_kernel<<<dim3(tiles, T), TOPK_THREADS, 0, st>>>(scores, row_stride, task_stride, ids, B, n_valid, shard_tag, K, Kp, runs);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return api_hip_fail("mkgnn_topk_update: runs launch", e);
+        if (e != hipSuccess) return api_hip_fail(who, e);
     }
-    topk_merge_kernel<<<1, TOPK_THREADS, 0, st>>>(scores, ids, B, n_valid, shard_tag, K, Kp, top_score, top_shard, top_mol, runs, tiles);
+    topk_merge_kernel<<<dim3(1, T), TOPK_THREADS, 0, st>>>(scores, row_stride, task_stride, ids, B, n_valid, shard_tag, K, Kp, top_score,
+                                                           top_shard, top_mol, runs, tiles);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail("mkgnn_topk_update: merge launch", e);
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+extern "C" int mkgnn_topk_update(const float* scores, const int32_t* ids, int32_t B, const int32_t* n_valid, const int32_t* shard_tag,
+                                 int32_t K, float* top_score, int32_t* top_shard, int32_t* top_mol, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    return topk_launch("mkgnn_topk_update", scores, 1, 0, ids, B, 1, n_valid, shard_tag, K, top_score, top_shard, top_mol, workspace,
+                       workspace_bytes, stream);
+}
+
+extern "C" int mkgnn_topk_update_tasks(const float* scores, int64_t score_row_stride, int64_t score_task_stride, const int32_t* ids,
+                                       int32_t B, int32_t T, const int32_t* n_valid, const int32_t* shard_tag, int32_t K,
+                                       float* top_score, int32_t* top_shard, int32_t* top_mol, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    return topk_launch("mkgnn_topk_update_tasks", scores, score_row_stride, score_task_stride, ids, B, T, n_valid, shard_tag, K,
+                       top_score, top_shard, top_mol, workspace, workspace_bytes, stream);
 }

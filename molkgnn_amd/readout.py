@@ -818,6 +818,49 @@ def task_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor
                              float(dropout_p), n_rows, kind)
 
 
+def task_scores(emb: torch.Tensor, ffn: torch.nn.Linear, n_rows: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                task_major: bool = False) -> torch.Tensor:
+    """``pred [n_rows, T]`` (``task_major``: ``[T, n_rows]``): EVERY output of a ``T``-output ``ffn`` for the leading ``n_rows`` rows of
+    a float32 CUDA ``emb [n, H]`` -- ``emb_i . ffn.weight[t] + ffn.bias[t]`` as one launch (``mkgnn_task_scores``), and bit for bit
+    the ``pred`` the task-indexed head (``task_head_loss``, dropout 0) gives row ``i`` when it is labelled with task ``t``.  ``out``: a
+    float32 tensor of that shape on the device to write into (its strides are passed on; elements it holds beyond that shape are
+    not touched).  More than 32 tasks or an embedding wider than 64: the same expression through torch operators on the GPU.
+    It has no autograd node: called where a gradient is being recorded for one of its inputs it raises instead of dropping it
+    (``task_head_loss`` is the operator with gradients)."""
+    _lib.require_gpu_tensor(emb, "graph_embedding")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (emb, ffn.weight, ffn.bias)):
+        raise RuntimeError("task_scores is forward only: call it under torch.no_grad() (or on detached inputs); "
+                           "task_head_loss is the operator with gradients")
+    if emb.dim() != 2 or emb.dtype != torch.float32 or ffn.in_features != emb.shape[1]:
+        raise ValueError("task_scores needs a float32 [n, H] embedding and an H-input linear layer")
+    n = emb.shape[0] if n_rows is None else int(n_rows)
+    if not 0 <= n <= emb.shape[0]:
+        raise ValueError(f"n_rows = {n_rows} outside [0, {emb.shape[0]}]")
+    T, H = ffn.weight.shape
+    dev = emb.device
+    shape = (T, n) if task_major else (n, T)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != shape:
+        raise ValueError(f"out: a float32 tensor of shape {shape} on {dev}")
+    if n == 0:
+        return out
+    w = ffn.weight.detach()
+    b = None if ffn.bias is None else ffn.bias.detach()
+    if not task_head_supported(T, H):
+        pred = (emb[:n, None, :] * w[None]).sum(dim=2)
+        if b is not None:
+            pred = pred + b
+        out.copy_(pred.t() if task_major else pred)
+        return out
+    emb, w = _row_major(emb), w.contiguous()
+    rs, ts = (out.stride(1), out.stride(0)) if task_major else (out.stride(0), out.stride(1))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mkgnn_task_scores(emb.data_ptr(), _stride0(emb), n, H, T, w.data_ptr(), _lib.ptr(b), out.data_ptr(),
+                                                 rs, ts, _lib.stream_ptr(dev)), "mkgnn_task_scores")
+    return out
+
+
 # ------------------------------------------------------------------- the tail of a training step, fused --
 # MKGNN_FUSED_TAIL=0: readout_blocks + bce_head_loss as separate operators (nine launches; A/B, diagnostics)
 _FUSED_TAIL = os.environ.get("MKGNN_FUSED_TAIL", "1") != "0"

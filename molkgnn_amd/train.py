@@ -7,6 +7,7 @@ loss the data module selects -- ``BCEWithLogitsLoss()`` for the QSAR assays (``d
 for the docking-score set (``data.py:49-53``) -- and the AdamW groups chosen by parameter name (``model.py:373-382``).
 Scoring: ``GNNModel.predict``, ``evaluate`` (the reference's validation / test loop, ``model.py:221-358, 483-522``) and
 ``evaluate_resident`` (the same from a device-resident shard; ranking a library: ``molkgnn_amd.screening``).
+Multi-task models: ``GNNModel.predict_tasks`` (all outputs of every molecule), ``evaluate_tasks``, ``evaluate_resident_tasks``.
 Logging, checkpoints, file output and the LR schedule are out of scope.
 """
 from __future__ import annotations
@@ -70,6 +71,34 @@ class GNNModel(torch.nn.Module):
                 pred, graph_embedding = self._head(self.dropout(out))
             n = pred.shape[0] if nreal is None else int(nreal)
             return pred[:n], graph_embedding[:n]
+
+    def predict_tasks(self, data):
+        """``(pred [n, T], graph_embedding [n, G])``: ALL ``T`` outputs of every molecule, for a model in evaluation mode, under
+        ``torch.no_grad()`` -- what ranking a library per assay needs (``screening.score_resident_tasks``); ``n`` as in ``predict``.
+        The network runs once: the embedding comes from the forward-only tail under ``predict``'s conditions (the tail is handed a
+        one-row view of the head, which it needs, and its own ``pred`` is dropped) and from the separate operators otherwise; on the
+        GPU ``pred`` is ``readout.task_scores`` of it -- one launch, bit for bit the task-indexed head's ``pred`` of every (molecule,
+        task) pair.  ``predict`` keeps its own route (and bits) for a multi-task model.  In training mode this raises."""
+        if self.training:
+            raise ValueError("GNNModel.predict_tasks needs evaluation mode: call model.eval() first")
+        with torch.no_grad():
+            nreal = getattr(data, 'n_valid_molecules', None)
+            score = None
+            if data.x.is_cuda:
+                from types import SimpleNamespace
+                bias = self.ffn.bias
+                row = SimpleNamespace(weight=self.ffn.weight[:1], bias=None if bias is None else bias[:1], out_features=1)
+                score = (row, nreal)
+            out = self.gnn_model(data, _score=score)
+            graph_embedding = out[2] if isinstance(out, tuple) else self.dropout(out)     # (the dropout is the identity here)
+            n = graph_embedding.shape[0] if nreal is None else int(nreal)
+            if graph_embedding.is_cuda:
+                from .readout import task_scores
+                emb = graph_embedding if graph_embedding.dtype == torch.float32 else graph_embedding.float()
+                pred = task_scores(emb, self.ffn, n_rows=n)
+            else:
+                pred = self.ffn(graph_embedding[:n])
+            return pred, graph_embedding[:n]
 
     def _loss_kind(self) -> Optional[str]:
         """The loss as a kind of the HIP head (``readout.LOSS_KINDS``), or None: any other loss takes the PyTorch route."""
@@ -230,6 +259,29 @@ def evaluate(model, batches, metrics=()) -> dict:
         model.train(was_training)
 
 
+def _task_results(pred: torch.Tensor, true_y: torch.Tensor, task: torch.Tensor, T: int, kind: str, metrics, table: dict) -> dict:
+    """The second half of ``evaluate_tasks`` and of ``evaluate_resident_tasks``: from ``pred [n, >= 1]``, the labels and every
+    molecule's task (int64) to the result dictionary -- the column selection, ``evaluation.per_task`` per metric and the masked
+    multi-task loss (``readout.task_head_reference`` on the selected column)."""
+    import math
+    from .evaluation import per_task
+    from .readout import task_head_reference
+    lab = (task >= 0) & (task < min(T, pred.shape[1]))
+    col = torch.where(lab, task, torch.zeros_like(task))
+    pred_y = torch.where(lab, pred.gather(1, col[:, None]).view(-1), torch.full((), float("nan"), dtype=pred.dtype, device=pred.device))
+    with torch.no_grad():
+        # (the head's expression on the selected column: an identity "embedding" of width 1 per task is the column itself)
+        sel = torch.where(lab, pred_y, torch.zeros_like(pred_y))
+        results = {'loss': task_head_reference(sel[:, None], torch.ones(T, 1, dtype=pred.dtype, device=pred.device), None,
+                                               true_y, torch.where(lab, task, torch.full_like(task, -1)), kind)[0]}
+    for m in metrics:
+        results[m] = per_task(true_y, pred_y, torch.where(lab, task, torch.full_like(task, -1)), table[m], T)
+        defined = [float(v) for v in results[m] if not math.isnan(float(v))]
+        results[m + '_mean'] = sum(defined) / len(defined) if defined else float("nan")
+    results['pred_y'], results['true_y'], results['task'] = pred_y, true_y, task
+    return results
+
+
 def evaluate_tasks(model, batches, metrics=(), num_tasks: Optional[int] = None) -> dict:
     """``evaluate`` for a multi-task model on mixed-assay batches that carry ``task`` (one task index per molecule, -1: no label;
     ``sampling.task_index``): ``model.predict`` per batch, keeping ``pred [n, T]``.  ``results[m]`` is the list of metric ``m``
@@ -238,9 +290,6 @@ def evaluate_tasks(model, batches, metrics=(), num_tasks: Optional[int] = None) 
     vectors (``readout.task_head_reference`` on the model's loss kind), ``pred_y`` every molecule's prediction for ITS task (NaN
     where it has none), ``true_y`` and ``task``.  ``num_tasks`` defaults to the model's outputs.  The model is put in evaluation
     mode and handed back in the mode it came in, also when a batch raises."""
-    import math
-    from .evaluation import per_task
-    from .readout import task_head_reference
     table = _metric_functions()
     unknown = [m for m in metrics if m not in table]
     if unknown:
@@ -264,21 +313,7 @@ def evaluate_tasks(model, batches, metrics=(), num_tasks: Optional[int] = None) 
             all_task.append(task.view(-1)[:n].to(pred.device))
         if not all_pred:
             raise ValueError("evaluate_tasks needs at least one batch")
-        pred, true_y, task = torch.cat(all_pred), torch.cat(all_true), torch.cat(all_task).long()
-        lab = (task >= 0) & (task < min(T, pred.shape[1]))
-        col = torch.where(lab, task, torch.zeros_like(task))
-        pred_y = torch.where(lab, pred.gather(1, col[:, None]).view(-1), torch.full((), float("nan"), dtype=pred.dtype, device=pred.device))
-        with torch.no_grad():
-            # (the head's expression on the selected column: an identity "embedding" of width 1 per task is the column itself)
-            sel = torch.where(lab, pred_y, torch.zeros_like(pred_y))
-            results = {'loss': task_head_reference(sel[:, None], torch.ones(T, 1, dtype=pred.dtype, device=pred.device), None,
-                                                   true_y, torch.where(lab, task, torch.full_like(task, -1)), kind)[0]}
-        for m in metrics:
-            results[m] = per_task(true_y, pred_y, torch.where(lab, task, torch.full_like(task, -1)), table[m], T)
-            defined = [float(v) for v in results[m] if not math.isnan(float(v))]
-            results[m + '_mean'] = sum(defined) / len(defined) if defined else float("nan")
-        results['pred_y'], results['true_y'], results['task'] = pred_y, true_y, task
-        return results
+        return _task_results(torch.cat(all_pred), torch.cat(all_true), torch.cat(all_task).long(), T, kind, metrics, table)
     finally:
         model.train(was_training)
 
@@ -301,6 +336,30 @@ def evaluate_resident(model, resident, batch_size: int, metrics=()) -> dict:
         results[m] = table[m](true_y, pred_y)
     results['pred_y'], results['true_y'] = pred_y, true_y
     return results
+
+
+def evaluate_resident_tasks(model, resident, batch_size: int, metrics=()) -> dict:
+    """``evaluate_tasks`` for a mixed-assay data set that lives in device memory (``shards.ResidentShard(..., assays=...)``): the
+    same result dictionary, from ``screening.score_resident_tasks`` -- all ``T`` outputs of every molecule of the shard in id
+    order, the short tail included, from one captured graph -- with ``resident.y`` as the labels and ``resident.task`` as every
+    molecule's task; then exactly what ``evaluate_tasks`` does with its concatenated vectors (``_task_results``).  The predictions
+    are ``readout.task_scores``' (``evaluate_tasks`` takes ``model.predict``'s, a GEMM: equal in value, not in every bit).  Unknown
+    metric names, a shard without ``assays`` and a loss that is none of the head's kinds raise before anything is launched; the
+    model comes back in the mode it came in."""
+    from .screening import score_resident_tasks
+    table = _metric_functions()
+    unknown = [m for m in metrics if m not in table]
+    if unknown:
+        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(table)}")
+    if getattr(resident, "task", None) is None:
+        raise ValueError("evaluate_resident_tasks needs a shard that knows every molecule's task: ResidentShard(..., assays=...)")
+    kind = model._loss_kind()
+    if kind is None:
+        raise ValueError("evaluate_resident_tasks needs one of the head's loss kinds (BCEWithLogitsLoss(), MSELoss(), MSELoss('sum'))")
+    pred = score_resident_tasks(model, resident, batch_size)
+    true_y = resident.y.to(pred.device).view(-1)
+    task = resident.task.to(pred.device).view(-1).long()
+    return _task_results(pred, true_y, task, model.ffn.out_features, kind, metrics, table)
 
 
 def tune_torch_backends() -> None:
