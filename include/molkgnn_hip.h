@@ -675,6 +675,30 @@ int mkgnn_task_scores(const float* emb, int64_t emb_stride, int64_t n_rows, int3
                       const float* weight, const float* bias, float* pred, int64_t pred_row_stride, int64_t pred_task_stride,
                       void* stream);
 
+/* (additive; the ABI version stays 8) Cosine similarity of every embedding row with every query -- analogue search over a library
+ * of graph embeddings (the reference compares molecules by CosineSimilarity(dim=-1) of their graph embeddings):
+ *     sim[i * sim_row_stride + q * sim_query_stride] = (emb_i . queries_q) / (max(||emb_i||, eps) * max(||queries_q||, eps))
+ * for every i < n_rows, q < Q, with eps = 1e-8f: each vector is clamped on its own, as torch.nn.functional.cosine_similarity and
+ * mkgnn_row_inv_norm do.  emb [n_rows, H] with emb_stride >= H, queries [Q, H] with query_stride >= H, RAW: nothing is prepared
+ * ahead, every block normalises the queries itself, so one captured launch follows the contents of both inputs.  A zero row or a
+ * zero query gives +0.0; a NaN in row i makes row i's Q outputs NaN and no others, a NaN in query q column q and no others.
+ * DOMAIN: rows and queries whose sum of squares is finite in float32; outside it the result is whatever the arithmetic gives.
+ * Evaluation order, one per element: lane h of 32 forms v[h] * w[h] (a plain multiply, +0.0 at h >= H), applies
+ * fmaf(v[32 + h], w[32 + h], .) where 32 + h < H, and the 32 values go through an xor tree (offsets 16, 8, 4, 2, 1) -- for the two
+ * sums of squares (v = w) and the dot product alike; inv = 1 / fmaxf(sqrtf(sum of squares), eps), correctly rounded; the dot
+ * product gets + (+0.0); sim = (dot * inv_row) * inv_query.  The BITS of sim[i, q] therefore depend on the H values of row i and
+ * of query q only: not on n_rows, the row's place in block or grid, Q, q's index, either input stride or the output layout.
+ * Against the exact value the error is at most (2 H + 10) 2^-24 M ie iq + H 2^-149 ie iq + 2^-149, M = sum_h |e_h| |q_h|, ie and
+ * iq the two inverse clamped norms.  Either output layout: [n_rows, Q] rows (sim_query_stride = 1,
+ * sim_row_stride >= Q) or [Q, n_rows] query-major (sim_row_stride = 1, sim_query_stride >= n_rows) -- any pair of positive strides
+ * under which no two (i, q) share an element; nothing else of sim is written.  One launch on `stream`, capturable; no workspace,
+ * no atomics, no process-wide or thread-local state, one writer per output.  1 <= Q <= MKGNN_EMBED_COSINE_MAX_QUERIES (the lists
+ * of one mkgnn_topk_update_tasks), 1 <= H <= 64; anything else, a negative n_rows, a null pointer or overlapping outputs returns
+ * non-zero with mkgnn_last_error set before any launch.  n_rows == 0 is a no-op that returns 0. */
+#define MKGNN_EMBED_COSINE_MAX_QUERIES 32
+int mkgnn_embed_cosine(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* queries, int64_t query_stride,
+                       int32_t Q, float* sim, int64_t sim_row_stride, int64_t sim_query_stride, void* stream);
+
 /* AdamW step over all trainable tensors of the model in one launch (reference model.py:368-385: torch.optim.AdamW,
  * two parameter groups -- kernel banks without weight decay).  Per tensor: param / grad [numel] fp32 contiguous,
  * state [mkgnn_adamw_state_floats(numel)] = exp_avg, exp_avg_sq, step count (as a float, advanced by this call), two reserved

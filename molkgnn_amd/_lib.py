@@ -20,6 +20,7 @@ ABI_VERSION = 8
 # MKGNN_LOSS_*: the loss kinds of the single-task head (mkgnn_tail_args.loss_kind, mkgnn_head_loss_*)
 LOSS_BCE_MEAN, LOSS_SQERR_MEAN, LOSS_SQERR_SUM = 0, 1, 2
 TASK_HEAD_MAX_TASKS, TASK_HEAD_MAX_H = 32, 64   # MKGNN_TASK_HEAD_MAX_TASKS, the task-indexed head's widest embedding
+EMBED_COSINE_MAX_QUERIES, EMBED_COSINE_MAX_H = 32, 64   # MKGNN_EMBED_COSINE_MAX_QUERIES, mkgnn_embed_cosine's widest embedding
 
 
 class KernelBank(C.Structure):
@@ -171,7 +172,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused", "mkgnn_gather_compact",
            "mkgnn_gather_compact_workspace_bytes", "mkgnn_gather_compact_packed", "mkgnn_topk_update", "mkgnn_topk_workspace_bytes",
            "mkgnn_task_head_workspace_bytes", "mkgnn_task_head_forward", "mkgnn_task_head_backward", "mkgnn_task_head_fused",
-           "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks")
+           "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks", "mkgnn_embed_cosine")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -357,6 +358,9 @@ def load() -> C.CDLL:
     # every task's logit of every row: (emb, stride, n_rows, H, T, weight, bias, pred, row stride, task stride, stream)
     lib.mkgnn_task_scores.restype = C.c_int
     lib.mkgnn_task_scores.argtypes = [P, I64, I64, I32, I32, P, P, P, I64, I64, P]
+    # cosine of every row with every query: (emb, stride, n_rows, H, queries, stride, Q, sim, row stride, query stride, stream)
+    lib.mkgnn_embed_cosine.restype = C.c_int
+    lib.mkgnn_embed_cosine.argtypes = [P, I64, I64, I32, P, I64, I32, P, I64, I64, P]
     lib.mkgnn_rf_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_rf_workspace_bytes.argtypes = [I64]
     lib.mkgnn_rf_count.restype = C.c_int

@@ -861,6 +861,64 @@ def task_scores(emb: torch.Tensor, ffn: torch.nn.Linear, n_rows: Optional[int] =
     return out
 
 
+COSINE_EPS = 1e-8                     # MKGNN_EPS: the clamp of each norm (float32(1e-8) where it is applied)
+
+
+def embedding_cosine_supported(Q: int, H: int) -> bool:
+    """The shapes ``mkgnn_embed_cosine`` takes; anything else goes through torch operators on the GPU."""
+    return 1 <= Q <= _lib.EMBED_COSINE_MAX_QUERIES and 1 <= H <= _lib.EMBED_COSINE_MAX_H
+
+
+def embedding_cosine(emb: torch.Tensor, queries: torch.Tensor, n_rows: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                     query_major: bool = False) -> torch.Tensor:
+    """``sim [n_rows, Q]`` (``query_major``: ``[Q, n_rows]``): the cosine similarity of the leading ``n_rows`` rows of a float32 CUDA
+    ``emb [n, H]`` with every row of a float32 CUDA ``queries [Q, H]`` -- ``(e . q) / (max(||e||, eps) * max(||q||, eps))``, ``eps =
+    1e-8``, each vector clamped on its own (``torch.nn.functional.cosine_similarity``; ``screening.cosine_reference`` is the
+    definition in float64) -- as one launch (``mkgnn_embed_cosine``).  The queries are read raw: nothing is prepared ahead, so a
+    captured call follows the contents of both tensors.  A zero row or query gives +0.0, a NaN its own row or column of NaN.  The
+    bits of an element depend on its row's and its query's values alone.  ``out``: a float32 tensor of that shape on the device to
+    write into (its strides are passed on; elements it holds beyond that shape are not touched).  More than 32 queries or an
+    embedding wider than 64: the same definition through torch operators on the GPU.  It has no autograd node: called where a
+    gradient is being recorded for one of its inputs it raises instead of dropping it."""
+    if not (torch.is_tensor(emb) and torch.is_tensor(queries)) or emb.dim() != 2 or queries.dim() != 2 \
+            or emb.dtype != torch.float32 or queries.dtype != torch.float32 or queries.shape[1] != emb.shape[1]:
+        raise ValueError("embedding_cosine needs a float32 [n, H] embedding and float32 [Q, H] queries")
+    Q, H = queries.shape
+    if Q < 1 or H < 1:
+        raise ValueError(f"embedding_cosine needs at least one query and one column, not {Q} x {H}")
+    if not emb.is_cuda or queries.device != emb.device:
+        raise ValueError(f"embedding_cosine runs on the GPU: emb is on {emb.device}, queries on {queries.device} (there is no CPU "
+                         "path; screening.cosine_reference is the host form)")
+    if torch.is_grad_enabled() and (emb.requires_grad or queries.requires_grad):
+        raise RuntimeError("embedding_cosine is forward only: call it under torch.no_grad() (or on detached inputs)")
+    n = emb.shape[0] if n_rows is None else int(n_rows)
+    if not 0 <= n <= emb.shape[0]:
+        raise ValueError(f"n_rows = {n_rows} outside [0, {emb.shape[0]}]")
+    dev = emb.device
+    shape = (Q, n) if query_major else (n, Q)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != shape:
+        raise ValueError(f"out: a float32 tensor of shape {shape} on {dev}")
+    if n == 0:
+        return out
+    if not embedding_cosine_supported(Q, H):
+        # (in float64, rounded once at the end: well inside the float32 bound, and no product of float32 values underflows there)
+        e, q = emb[:n].detach().double(), queries.detach().double()
+        eps = float(torch.tensor(COSINE_EPS, dtype=torch.float32))
+        ie = 1.0 / e.square().sum(dim=1).sqrt().clamp_min(eps)
+        iq = 1.0 / q.square().sum(dim=1).sqrt().clamp_min(eps)
+        sim = ((e @ q.t() + 0.0) * ie[:, None] * iq[None, :]).float()
+        out.copy_(sim.t() if query_major else sim)
+        return out
+    emb, queries = _row_major(emb.detach()), _row_major(queries.detach())
+    rs, qs = (out.stride(1), out.stride(0)) if query_major else (out.stride(0), out.stride(1))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mkgnn_embed_cosine(emb.data_ptr(), _stride0(emb), n, H, queries.data_ptr(), _stride0(queries), Q,
+                                                  out.data_ptr(), rs, qs, _lib.stream_ptr(dev)), "mkgnn_embed_cosine")
+    return out
+
+
 # ------------------------------------------------------------------- the tail of a training step, fused --
 # MKGNN_FUSED_TAIL=0: readout_blocks + bce_head_loss as separate operators (nine launches; A/B, diagnostics)
 _FUSED_TAIL = os.environ.get("MKGNN_FUSED_TAIL", "1") != "0"

@@ -13,6 +13,15 @@ once per molecule, ``GNNModel.predict_tasks`` gives all ``T`` outputs, ``T`` run
 ``TopKTasks``                    ``T`` running lists on the device (``[T, k]`` tensors)
 ``score_resident_tasks``         ``scores[n_molecules, T]`` of one resident shard, optionally feeding a ``TopKTasks``
 ``screen_tasks``                 shards -> the top ``k`` per task
+
+Analogue search -- the library molecules whose graph embeddings lie closest, by cosine similarity, to a few query embeddings
+(``GNNModel.embed``, ``mkgnn_embed_cosine``; one list per query, a ``TopKTasks`` of ``Q <= 32`` lists):
+
+``cosine_reference`` / ``cosine_bound``  the similarity in float64 numpy, and the error bound of a float32 evaluation
+``embed_resident``                       ``emb[n_molecules, G]`` of one resident shard
+``nearest_resident``                     ``sim[n_molecules, Q]`` of one resident shard, optionally feeding the ``Q`` lists
+``nearest``                              shards -> the ``k`` nearest molecules per query
+``rank_embeddings``                      the same ranking from a stored embedding matrix
 """
 from __future__ import annotations
 
@@ -220,6 +229,11 @@ def _check_model(model, resident, tasks: bool = False) -> torch.device:
             raise ValueError(f"per-task screening takes a model with 1 to {_lib.TASK_HEAD_MAX_TASKS} outputs (task_dim), not {T}")
     elif T != 1:
         raise ValueError("screening ranks ONE score per molecule: a one-task model (task_dim = 1) is needed")
+    return _check_device(model, resident)
+
+
+def _check_device(model, resident) -> torch.device:
+    """The device-only part of ``_check_model``: what the embedding routes need of a model with any number of outputs."""
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise ValueError("screening runs on the GPU: move the model there (there is no CPU path)")
@@ -411,3 +425,255 @@ def screen_tasks(model, residents, k: int, batch_size: int, return_scores: bool 
     if return_scores:
         result["scores"] = kept
     return result
+
+
+# ------------------------------------------------------------------------------------------ analogue search --
+# Nearest embeddings: rank the molecules of a resident library by the cosine similarity of their graph embeddings
+# (``GNNModel.embed``) with a few query embeddings -- the reference's own comparison of molecules (its graph-embedding analysis
+# uses ``CosineSimilarity(dim=-1)``).  One running list per query: a ``TopKTasks(k, Q, dev)`` IS the ``Q`` lists.
+#
+# ``cosine_reference`` / ``cosine_bound``  the definition of ``mkgnn_embed_cosine`` in float64 numpy, and its error bound
+# ``embed_resident``                       ``emb[n_molecules, G]`` of one resident shard, for a model of any ``task_dim``
+# ``nearest_resident``                     ``sim[n_molecules, Q]`` of one resident shard, optionally feeding the ``Q`` lists
+# ``nearest``                              shards -> the ``k`` nearest molecules of every query
+# ``rank_embeddings``                      the same ranking from a stored embedding matrix, without running the network
+#
+# Three things hold for all of them.  ``cos(e, e)`` is 1 only to within ``cosine_bound`` (three float32 roundings of one vector do
+# not cancel exactly).  A query that is itself in the library is not excluded: it is found, at the head of its list or tied with
+# its duplicates.  Ties -- equal similarities, ``-0.0 == +0.0``, NaN last -- follow ``topk_update_reference``: shard ascending, then
+# molecule id ascending.
+COSINE_EPS = np.float32(1e-8)                   # MKGNN_EPS: each norm is clamped from below by it, on its own
+MAX_QUERIES = 32                                # MKGNN_EMBED_COSINE_MAX_QUERIES = the lists of one TopKTasks
+
+
+def _f64(a) -> np.ndarray:
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise ValueError("a matrix of row vectors is needed")
+    return a.astype(np.float64)
+
+
+def _inverse_norms(a: np.ndarray) -> np.ndarray:
+    return 1.0 / np.maximum(np.sqrt((a * a).sum(axis=1)), float(COSINE_EPS))
+
+
+def cosine_reference(emb, queries) -> np.ndarray:
+    """The definition of ``mkgnn_embed_cosine`` (include/molkgnn_hip.h), on the host, in float64 on the values as given:
+    ``sim[i, q] = (emb_i . queries_q) / (max(||emb_i||, eps) * max(||queries_q||, eps))`` with ``eps = float32(1e-8)`` -- each vector
+    clamped on its own, as ``torch.nn.functional.cosine_similarity`` does; float64 ``[n, Q]``.  A zero vector gives 0, a NaN its row
+    or column of NaN."""
+    e, q = _f64(emb), _f64(queries)
+    if e.shape[1] != q.shape[1]:
+        raise ValueError(f"emb [n, {e.shape[1]}] and queries [Q, {q.shape[1]}] differ in width")
+    with np.errstate(invalid="ignore"):
+        return (e @ q.T) * _inverse_norms(e)[:, None] * _inverse_norms(q)[None, :]
+
+
+def cosine_bound(emb, queries) -> np.ndarray:
+    """How far a float32 evaluation of ``cosine_reference`` may lie from it, element by element (float64 ``[n, Q]``):
+
+        ``(2 H + 10) 2^-24 M ie iq  +  H 2^-149 ie iq  +  2^-149``,   ``M = sum_h |e_h| |q_h|``, ``ie`` / ``iq`` the inverse clamped norms.
+
+    First term, the standard rounding model (Higham 3.1, first order): ``H + 1`` roundings for the dot product, ``(H + 1) / 2 + 2``
+    for each inverse norm (its sum of squares, halved by the square root; the root; the division), two multiplies -- ``2 H + 8`` units
+    of ``2^-24``, taken as ``2 H + 10`` for the second-order terms and for an order that scales the query first.  Second term: a
+    product that underflows carries up to half a denormal spacing, ``2^-150``, ``H`` of them, scaled like the dot product; the factor
+    two is margin.  Third term: the rounding of a result that is itself denormal.  It holds for EVERY element."""
+    e, q = _f64(emb), _f64(queries)
+    if e.shape[1] != q.shape[1]:
+        raise ValueError(f"emb [n, {e.shape[1]}] and queries [Q, {q.shape[1]}] differ in width")
+    H = e.shape[1]
+    scale = _inverse_norms(e)[:, None] * _inverse_norms(q)[None, :]
+    return (2 * H + 10) * 2.0 ** -24 * (np.abs(e) @ np.abs(q).T) * scale + H * 2.0 ** -149 * scale + 2.0 ** -149
+
+
+def _check_queries(who: str, query_emb, G: int, dev=None) -> int:
+    """``Q`` of a query matrix: float32 ``[Q, G]``, ``1 <= Q <= 32``, on ``dev`` (a CUDA device) -- the value checks first, the device
+    last; ``ValueError`` otherwise, before anything is loaded or launched."""
+    if not torch.is_tensor(query_emb) or query_emb.dim() != 2:
+        raise ValueError(f"{who}: the queries are a [Q, {G}] tensor of embeddings")
+    if query_emb.dtype != torch.float32:
+        raise ValueError(f"{who}: the queries are float32, not {query_emb.dtype}")
+    Q = int(query_emb.shape[0])
+    if not 1 <= Q <= MAX_QUERIES:
+        raise ValueError(f"{who}: {Q} queries outside [1, {MAX_QUERIES}] (MKGNN_EMBED_COSINE_MAX_QUERIES: one list per query; rank "
+                         "more queries group by group, screening.rank_embeddings)")
+    if int(query_emb.shape[1]) != int(G):
+        raise ValueError(f"{who}: the queries are {int(query_emb.shape[1])} wide, the embedding is {int(G)} wide")
+    if query_emb.device.type != "cuda" or (dev is not None and query_emb.device != dev):
+        raise ValueError(f"{who}: the queries are on {query_emb.device}; they belong on the GPU of the library" +
+                         ("" if dev is None else f" ({dev})"))
+    return Q
+
+
+def _embedding_width(model) -> int:
+    G = getattr(getattr(model, "ffn", None), "in_features", None)
+    if not isinstance(G, int) or G < 1:
+        raise ValueError("a model whose head (ffn) reads the graph embedding is needed")
+    return G
+
+
+def _run_shard(model, resident, bs: int, width: int, predict, rank, out) -> torch.Tensor:
+    """One captured ``_ScoringStep`` over the shard with ``predict`` (``width`` values per molecule) and ``rank``; the ``[n, width]``
+    result (into ``out`` when given); the gather's status word read once; the model handed back in its mode."""
+    n = int(resident.n_molecules)
+    was_training = model.training
+    model.eval()
+    try:
+        scoring = _ScoringStep(model, resident, bs, rank, predict=predict, width=width)
+        for b in range(len(scoring)):
+            scoring.run(b)
+        if out is None:
+            out = scoring.ext[:n]
+        else:
+            out.copy_(scoring.ext[:n])
+        status = scoring.csb.gather_status()             # (the one host read)
+        if status:
+            raise RuntimeError(f"mkgnn_gather_compact reported status {status} while embedding the shard")
+        return out
+    finally:
+        model.train(was_training)
+
+
+def _check_out(out, shape, dev) -> None:
+    if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise ValueError(f"out: a contiguous float32 tensor of shape {shape} on {dev}")
+
+
+def embed_resident(model, resident, batch_size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``emb[n_molecules, G]`` (float32, on the device): ``model.embed`` of every molecule of the ``ResidentShard``, in id order, the
+    short tail included, as ``score_resident`` does it -- one captured graph per call, replayed per batch, with the embedding in the
+    place of the score and no ranking.  ``out`` (``[n_molecules, G]``, contiguous) is filled with NaN first, so a slot that was not
+    written shows.  The model may have any ``task_dim``; it must be on the shard's GPU (``ValueError`` before a launch otherwise);
+    it is put in evaluation mode and handed back in the mode it came in.  The gather's status word is read once, at the end.
+    The matrix can be kept and ranked again and again (``rank_embeddings``) without running the network."""
+    G = _embedding_width(model)
+    dev = _check_device(model, resident)
+    bs, n = int(batch_size), int(resident.n_molecules)
+    if bs < 1:
+        raise ValueError("batch_size >= 1")
+    _check_out(out, (n, G), dev)
+    return _run_shard(model, resident, bs, G, model.embed, None, out)
+
+
+def nearest_resident(model, resident, query_emb: torch.Tensor, batch_size: int, *, topk: Optional[TopKTasks] = None,
+                     shard_tag: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``sim[n_molecules, Q]`` (float32, on the device): the cosine similarity (``cosine_reference``) of every molecule's graph
+    embedding with each of the ``Q`` rows of ``query_emb`` (float32 ``[Q, G]`` on the shard's GPU, ``1 <= Q <= 32``), in id order, the
+    short tail included.  One graph is captured per call and replayed per batch, as in ``score_resident``; the step's scoring is
+    ``readout.embedding_cosine(model.embed(data), query_emb)`` -- one ``mkgnn_embed_cosine`` behind the network, which reads the
+    queries raw -- and, with ``topk`` (a ``TopKTasks`` of ``Q`` lists), ``topk.update(sim, ids, n_valid=n_live)``: ONE
+    ``mkgnn_topk_update_tasks`` that feeds the batch's live rows to all ``Q`` lists under ``shard_tag``; fillers never enter a list.
+    ``out`` (``[n_molecules, Q]``, contiguous) is filled with NaN first.
+
+    ``cos(e, e)`` is 1 only to within ``cosine_bound``; a query that is itself in the library is not excluded; ties follow
+    ``topk_update_reference``.  A wrong ``Q``, ``G``, dtype or device, or a ``topk`` that is not a ``TopKTasks`` of ``Q`` lists, raises
+    ``ValueError`` before a launch.  The model may have any ``task_dim`` and comes back in the mode it came in."""
+    Q = _check_queries("nearest_resident", query_emb, _embedding_width(model))
+    dev = _check_device(model, resident)
+    _check_queries("nearest_resident", query_emb, query_emb.shape[1], dev)
+    bs, n = int(batch_size), int(resident.n_molecules)
+    if bs < 1:
+        raise ValueError("batch_size >= 1")
+    if topk is not None and (not isinstance(topk, TopKTasks) or topk.n_tasks != Q):
+        raise ValueError(f"nearest_resident: the running lists must be a TopKTasks of {Q} lists, one per query")
+    if topk is not None and topk.device != dev:
+        raise ValueError(f"the running lists are on {topk.device}, the model on {dev}")
+    _check_out(out, (n, Q), dev)
+    from .readout import embedding_cosine
+    queries = query_emb.detach()
+    rank = None
+    if topk is not None:
+        topk.reserve(bs)
+        topk.shard_tag.fill_(int(shard_tag))
+        rank = lambda sim, ids, n_live: topk.update(sim, ids, n_valid=n_live)     # noqa: E731
+    return _run_shard(model, resident, bs, Q, lambda data: embedding_cosine(model.embed(data), queries), rank, out)
+
+
+def nearest(model, queries, residents, k: int, batch_size: int, return_sims: bool = False) -> dict:
+    """Analogue search: the ``k`` molecules of a library whose graph embeddings lie closest, by cosine similarity, to each query.
+    ``queries``: a float32 ``[Q, G]`` tensor of embeddings on the model's GPU, or a ``ResidentShard`` of 1 to 32 query molecules
+    (known actives), which is embedded with ``embed_resident`` first.  ``residents``: a sequence of ``ResidentShard``s, or a
+    generator that uploads them one at a time; shard ``j`` carries tag ``j``.  One ``TopKTasks`` of ``Q x k`` slots is carried across
+    the shards on the device.  Returns, as ``screen_tasks`` does, ``top_sim``, ``top_shard``, ``top_mol`` as ``[Q, k]`` tensors, list
+    ``q`` nearest first with its empty slots -- ``(-inf, -1, -1)`` -- at the end; ``n_occupied`` (int64 ``[Q]``, on the host);
+    ``n_searched``; ``query_emb`` (the ``[Q, G]`` matrix that was searched for); and, with ``return_sims``, ``sims``: the per-shard
+    ``[n_molecules, Q]`` tensors.
+
+    ``cos(e, e)`` is 1 only to within ``cosine_bound``; a query that is itself in the library is not excluded (it heads its list, or
+    ties with its duplicates); ties follow ``topk_update_reference``.  More than 32 queries: embed the library once
+    (``embed_resident``) and call ``rank_embeddings`` per group of 32."""
+    from .shards import ResidentShard
+    G = _embedding_width(model)
+    if isinstance(queries, ResidentShard):
+        if not 1 <= int(queries.n_molecules) <= MAX_QUERIES:
+            raise ValueError(f"nearest: a query shard holds 1 to {MAX_QUERIES} molecules, not {int(queries.n_molecules)}")
+        query_emb = embed_resident(model, queries, batch_size)
+    else:
+        query_emb = queries
+    dev = next(model.parameters()).device
+    Q = _check_queries("nearest", query_emb, G, dev if dev.type == "cuda" else None)
+    if dev.type != "cuda":
+        raise ValueError("nearest runs on the GPU: move the model there (there is no CPU path)")
+    topk, n_searched, kept = None, 0, []
+    for tag, resident in enumerate(residents):
+        _check_device(model, resident)
+        if topk is None:
+            topk = TopKTasks(k, Q, dev)
+        sim = nearest_resident(model, resident, query_emb, batch_size, topk=topk, shard_tag=tag)
+        n_searched += int(resident.n_molecules)
+        if return_sims:
+            kept.append(sim)
+    if topk is None:
+        raise ValueError("nearest needs at least one shard")
+    top_sim, top_shard, top_mol, occupied = topk.result()
+    result = {"top_sim": top_sim, "top_shard": top_shard, "top_mol": top_mol, "n_occupied": occupied, "n_searched": n_searched,
+              "query_emb": query_emb}
+    if return_sims:
+        result["sims"] = kept
+    return result
+
+
+def rank_embeddings(emb: torch.Tensor, query_emb: torch.Tensor, topk: TopKTasks, ids: Optional[torch.Tensor] = None,
+                    shard_tag: int = 0, chunk: int = 4096) -> None:
+    """The stored-embedding route: rank the rows of ``emb`` (float32 ``[n, G]`` on the GPU, e.g. kept from ``embed_resident``) against
+    ``query_emb`` (float32 ``[Q, G]``, ``1 <= Q <= 32``) into ``topk`` (a ``TopKTasks`` of ``Q`` lists) WITHOUT running the network: per
+    chunk of ``chunk`` rows one ``mkgnn_embed_cosine`` and one ``mkgnn_topk_update_tasks``, launched eagerly.  Row ``i`` enters as
+    ``(sim[i, q], shard_tag, ids[i])``; ``ids`` (int32 ``[n]`` on the GPU) defaults to ``arange(n)``.  It makes re-querying a library
+    cheap -- the similarities are bit for bit those of ``nearest_resident`` on the same embeddings, so the lists are too.  A user with
+    more than 32 queries calls it per group of 32, with a ``TopKTasks`` per group.
+
+    ``chunk`` bounds the top-k's serial merge: an update ranks its batch in tiles in parallel and then merges the tiles' runs into
+    the list one after another (``DESIGN.md`` 4.5c), so one update over a whole library would serialise on that merge, and its
+    workspace grows with the batch; chunks of a few thousand rows keep both at a scoring step's size.
+
+    ``cos(e, e)`` is 1 only to within ``cosine_bound``; a query that is itself in the library is not excluded; ties follow
+    ``topk_update_reference``."""
+    if not torch.is_tensor(emb) or emb.dim() != 2 or emb.dtype != torch.float32 or emb.shape[1] < 1:
+        raise ValueError("rank_embeddings: emb is a float32 [n, G] tensor")
+    n, G = int(emb.shape[0]), int(emb.shape[1])
+    Q = _check_queries("rank_embeddings", query_emb, G)
+    if not emb.is_cuda:
+        raise ValueError(f"rank_embeddings: emb is on {emb.device}; the ranking runs on the GPU (there is no CPU path)")
+    dev = emb.device
+    _check_queries("rank_embeddings", query_emb, G, dev)
+    if not isinstance(topk, TopKTasks) or topk.n_tasks != Q or topk.device != dev:
+        raise ValueError(f"rank_embeddings: the running lists must be a TopKTasks of {Q} lists on {dev}")
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk >= 1")
+    if ids is None:
+        ids = torch.arange(n, dtype=torch.int32, device=dev)
+    elif not torch.is_tensor(ids) or ids.dtype != torch.int32 or ids.device != dev or ids.dim() != 1 or ids.numel() != n \
+            or not ids.is_contiguous():
+        raise ValueError(f"rank_embeddings: ids is a contiguous int32 [{n}] tensor on {dev}")
+    if n == 0:
+        return
+    from .readout import embedding_cosine
+    emb, query_emb = emb.detach(), query_emb.detach()
+    topk.reserve(min(chunk, n))
+    for a in range(0, n, chunk):
+        b = min(a + chunk, n)
+        topk.update(embedding_cosine(emb[a:b], query_emb), ids[a:b], n_valid=b - a, shard_tag=int(shard_tag))

@@ -8,6 +8,7 @@ for the docking-score set (``data.py:49-53``) -- and the AdamW groups chosen by 
 Scoring: ``GNNModel.predict``, ``evaluate`` (the reference's validation / test loop, ``model.py:221-358, 483-522``) and
 ``evaluate_resident`` (the same from a device-resident shard; ranking a library: ``molkgnn_amd.screening``).
 Multi-task models: ``GNNModel.predict_tasks`` (all outputs of every molecule), ``evaluate_tasks``, ``evaluate_resident_tasks``.
+The graph embedding alone: ``GNNModel.embed`` (analogue search: ``screening.nearest``).
 Logging, checkpoints, file output and the LR schedule are out of scope.
 """
 from __future__ import annotations
@@ -72,6 +73,32 @@ class GNNModel(torch.nn.Module):
             n = pred.shape[0] if nreal is None else int(nreal)
             return pred[:n], graph_embedding[:n]
 
+    def _embedding(self, data):
+        """``(graph_embedding [all slots, G], n)`` of a model in evaluation mode, inside the caller's ``no_grad``: the route
+        ``predict_tasks`` and ``embed`` share.  On the GPU the forward-only tail is handed a one-row view of the head (which it needs;
+        its own ``pred`` is dropped) and supplies the embedding where model and batch qualify; the separate operators otherwise."""
+        nreal = getattr(data, 'n_valid_molecules', None)
+        score = None
+        if data.x.is_cuda:
+            from types import SimpleNamespace
+            bias = self.ffn.bias
+            row = SimpleNamespace(weight=self.ffn.weight[:1], bias=None if bias is None else bias[:1], out_features=1)
+            score = (row, nreal)
+        out = self.gnn_model(data, _score=score)
+        graph_embedding = out[2] if isinstance(out, tuple) else self.dropout(out)     # (the dropout is the identity here)
+        return graph_embedding, (graph_embedding.shape[0] if nreal is None else int(nreal))
+
+    def embed(self, data):
+        """``graph_embedding [n, G]`` of a model in evaluation mode, under ``torch.no_grad()``: what the reference's embedding
+        analysis compares molecules by, and what analogue search ranks (``screening.nearest``); ``n`` as in ``predict``.  It is
+        ``predict_tasks(data)[1]`` bit for bit without the scores -- the same route (``_embedding``), for any ``task_dim``.  In
+        training mode this raises."""
+        if self.training:
+            raise ValueError("GNNModel.embed needs evaluation mode: call model.eval() first")
+        with torch.no_grad():
+            graph_embedding, n = self._embedding(data)
+            return graph_embedding[:n]
+
     def predict_tasks(self, data):
         """``(pred [n, T], graph_embedding [n, G])``: ALL ``T`` outputs of every molecule, for a model in evaluation mode, under
         ``torch.no_grad()`` -- what ranking a library per assay needs (``screening.score_resident_tasks``); ``n`` as in ``predict``.
@@ -82,16 +109,7 @@ class GNNModel(torch.nn.Module):
         if self.training:
             raise ValueError("GNNModel.predict_tasks needs evaluation mode: call model.eval() first")
         with torch.no_grad():
-            nreal = getattr(data, 'n_valid_molecules', None)
-            score = None
-            if data.x.is_cuda:
-                from types import SimpleNamespace
-                bias = self.ffn.bias
-                row = SimpleNamespace(weight=self.ffn.weight[:1], bias=None if bias is None else bias[:1], out_features=1)
-                score = (row, nreal)
-            out = self.gnn_model(data, _score=score)
-            graph_embedding = out[2] if isinstance(out, tuple) else self.dropout(out)     # (the dropout is the identity here)
-            n = graph_embedding.shape[0] if nreal is None else int(nreal)
+            graph_embedding, n = self._embedding(data)
             if graph_embedding.is_cuda:
                 from .readout import task_scores
                 emb = graph_embedding if graph_embedding.dtype == torch.float32 else graph_embedding.float()
