@@ -133,28 +133,38 @@ class TopK:
         own.fill_(int(value))
         return own
 
+    _WHOSE = "list's"
+
+    def _check_batch(self, scores: torch.Tensor, ids: torch.Tensor) -> None:
+        dev = self.device
+        if scores.dtype != torch.float32 or ids.dtype != torch.int32 or scores.device != dev or ids.device != dev:
+            raise ValueError(f"scores float32 and ids int32 on the {self._WHOSE} device")
+
+    def _launch_args(self, B: int, n_valid, shard_tag):
+        """What every update hands its kernel behind the batch: the two device scalars (filled first when given as ints), then the
+        workspace for ``B`` slots -- ``(n_valid, shard_tag, workspace, workspace bytes)`` as addresses and a size."""
+        nv, tag = self._scalar(self.n_valid, n_valid), self._scalar(self.shard_tag, shard_tag)
+        self.reserve(B)
+        ws = self.workspace
+        return nv.data_ptr(), tag.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size()
+
     def update(self, scores: torch.Tensor, ids: torch.Tensor, n_valid=None, shard_tag=None) -> None:
         """One ``mkgnn_topk_update`` on the current stream: the list becomes the best ``k`` of itself and the first ``n_valid``
         entries ``(scores[i], shard_tag, ids[i])``.  ``n_valid`` / ``shard_tag``: None -- what ``self.n_valid`` /
         ``self.shard_tag`` hold when the launch RUNS; an int -- written into them first; a one-element device int32 tensor --
         read in their place (by address: a captured update follows its contents)."""
         from . import _lib
-        dev = self.device
-        if scores.dtype != torch.float32 or ids.dtype != torch.int32 or scores.device != dev or ids.device != dev:
-            raise ValueError("scores float32 and ids int32 on the list's device")
+        self._check_batch(scores, ids)
         if not scores.is_contiguous() or not ids.is_contiguous() or scores.numel() != ids.numel():
             raise ValueError("scores and ids: contiguous, one id per score")
         B = scores.numel()
         if B < 1:
             raise ValueError("an update needs at least one slot")
-        nv, tag = self._scalar(self.n_valid, n_valid), self._scalar(self.shard_tag, shard_tag)
-        self.reserve(B)
-        ws = self.workspace
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mkgnn_topk_update(scores.data_ptr(), ids.data_ptr(), B, nv.data_ptr(), tag.data_ptr(), self.k,
-                                                     self.top_score.data_ptr(), self.top_shard.data_ptr(), self.top_mol.data_ptr(),
-                                                     ws.data_ptr(), ws.numel() * ws.element_size(), _lib.stream_ptr(dev)),
-                       "mkgnn_topk_update")
+        nv, tag, ws, ws_bytes = self._launch_args(B, n_valid, shard_tag)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().mkgnn_topk_update(scores.data_ptr(), ids.data_ptr(), B, nv, tag, self.k, self.top_score.data_ptr(),
+                                                     self.top_shard.data_ptr(), self.top_mol.data_ptr(), ws, ws_bytes,
+                                                     _lib.stream_ptr(self.device)), "mkgnn_topk_update")
 
     def result(self):
         """``(top_score, top_shard, top_mol, n_occupied)``: the three tensors (not copies) and the number of occupied slots -- they
@@ -177,6 +187,8 @@ class TopKTasks(TopK):
             raise ValueError(f"n_tasks = {n_tasks} outside [1, {_lib.TASK_HEAD_MAX_TASKS}] (MKGNN_TASK_HEAD_MAX_TASKS)")
         self._allocate(k, device, (self.n_tasks, int(k)))
 
+    _WHOSE = "lists'"
+
     def _workspace_bytes(self, batch: int) -> int:
         from . import _lib
         return int(_lib.load().mkgnn_topk_tasks_workspace_bytes(int(batch), self.k, self.n_tasks))
@@ -188,9 +200,8 @@ class TopKTasks(TopK):
         passed on, nothing is copied; any other layout (a row stride that is neither 1 nor ``T``) raises ``ValueError``.
         ``n_valid`` / ``shard_tag``: as in ``TopK.update``."""
         from . import _lib
-        dev, T = self.device, self.n_tasks
-        if scores.dtype != torch.float32 or ids.dtype != torch.int32 or scores.device != dev or ids.device != dev:
-            raise ValueError("scores float32 and ids int32 on the lists' device")
+        T = self.n_tasks
+        self._check_batch(scores, ids)
         B = ids.numel()
         if B < 1 or not ids.is_contiguous():
             raise ValueError("an update needs at least one slot and contiguous ids")
@@ -205,14 +216,11 @@ class TopKTasks(TopK):
         task_major = (B == 1 or rs == 1) and (T == 1 or ts >= B)
         if not (row_major or task_major):
             raise ValueError(f"scores: strides {tuple(scores.stride())} are neither [B, T] rows (row stride T) nor [T, B] rows (row stride 1)")
-        nv, tag = self._scalar(self.n_valid, n_valid), self._scalar(self.shard_tag, shard_tag)
-        self.reserve(B)
-        ws = self.workspace
-        with torch.cuda.device(dev):
+        nv, tag, ws, ws_bytes = self._launch_args(B, n_valid, shard_tag)
+        with torch.cuda.device(self.device):
             _lib.check(_lib.load().mkgnn_topk_update_tasks(
-                scores.data_ptr(), rs, ts, ids.data_ptr(), B, T, nv.data_ptr(), tag.data_ptr(), self.k, self.top_score.data_ptr(),
-                self.top_shard.data_ptr(), self.top_mol.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
-                _lib.stream_ptr(dev)), "mkgnn_topk_update_tasks")
+                scores.data_ptr(), rs, ts, ids.data_ptr(), B, T, nv, tag, self.k, self.top_score.data_ptr(), self.top_shard.data_ptr(),
+                self.top_mol.data_ptr(), ws, ws_bytes, _lib.stream_ptr(self.device)), "mkgnn_topk_update_tasks")
 
     def result(self):
         """``(top_score, top_shard, top_mol, n_occupied)``: the three ``[n_tasks, k]`` tensors (not copies) and the number of occupied
@@ -251,15 +259,15 @@ def static_batch_for(loader, resident):
 
 
 class _ScoringStep:
-    """The captured step of ``score_resident``: static buffers, the per-batch feed rows and ONE graph over ``gather`` ->
-    ``expand`` -> ``attach_receptive_fields`` -> ``model.predict`` -> scatter of the live slots -> ``rank``.  ``rank(pred, ids,
-    n_live)`` is called inside the capture with the batch's scores, its id view and its live count (a one-element device int32
-    view); ``score_resident`` passes ``TopK.update``, tools/screen_timing.py other formulations.  ``predict(data)`` gives the
-    batch's scores -- one row per slot -- and ``width`` their number per molecule: None (``score_resident``) is ``model.predict`` as a
-    vector and a score vector ``ext [n + 1]``; ``score_resident_tasks`` passes ``model.predict_tasks`` and ``T``: ``ext [n + 1, T]``.
-    The model is in evaluation mode already."""
+    """The captured step of a shard pass (``_run_shard``): static buffers, the per-batch feed rows and ONE graph over ``gather`` ->
+    ``expand`` -> ``attach_receptive_fields`` -> ``predict`` -> scatter of the live slots -> ``rank``.  ``predict(data)`` gives the
+    batch's result -- one row per slot -- and ``shape`` is the shape of one molecule's: ``()`` for a score vector ``ext [n + 1]``
+    (``score_resident``: ``model.predict`` as a vector), ``(T,)`` for ``ext [n + 1, T]`` (``score_resident_tasks``:
+    ``model.predict_tasks``).  ``rank(pred, ids, n_live)``, when given, is called inside the capture with the batch's result, its id
+    view and its live count (a one-element device int32 view); ``_run_shard`` passes the running list's ``update``,
+    tools/screen_timing.py other formulations.  The model is in evaluation mode already."""
 
-    def __init__(self, model, resident, batch_size: int, rank=None, predict=None, width: Optional[int] = None):
+    def __init__(self, model, resident, batch_size: int, predict, shape, rank=None):
         from .receptive_field import attach_receptive_fields
         from .shards import ResidentLoader
         dev = resident.device
@@ -277,28 +285,26 @@ class _ScoringStep:
         self.feed = feed = torch.zeros(rows.shape[1], dtype=torch.int32, device=dev)
         f_ids, f_live, f_index = feed[:bs], feed[bs:bs + 1], feed[off:].view(torch.int64)
         self.csb = csb = static_batch_for(loader, resident)
-        self.ext = ext = torch.full((n + 1,) if width is None else (n + 1, int(width)), float("nan"), dtype=torch.float32, device=dev)
+        self.ext = ext = torch.full((n + 1, *shape), float("nan"), dtype=torch.float32, device=dev)
         self.n = n
-        if predict is None:
-            predict = lambda data: model.predict(data)[0].reshape(-1)     # noqa: E731
 
-        def step(ranked: bool):
+        def step(rank):
             csb.gather(resident, f_ids)
             csb.expand()
             attach_receptive_fields(csb.data, sizes=csb.data.bucket_sizes, overlap=True)
             pred = predict(csb.data)
             ext.index_copy_(0, f_index, pred)
-            if ranked and rank is not None:
+            if rank is not None:
                 rank(pred, f_ids, f_live)
 
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             feed.copy_(self.rows[0], non_blocking=True)
-            step(False)                                  # (eager once: lazily made buffers exist before the capture; no ranking)
+            step(None)                                   # (eager once: lazily made buffers exist before the capture; no ranking)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=side):
-                step(True)
+                step(rank)
         torch.cuda.current_stream(dev).wait_stream(side)
 
     def __len__(self):
@@ -310,32 +316,38 @@ class _ScoringStep:
         self.graph.replay()
 
 
-def _score_shard(who: str, model, resident, batch_size: int, topk, shard_tag: int, out, tasks: bool) -> torch.Tensor:
-    """The body of ``score_resident`` (``tasks`` False: one score per molecule) and ``score_resident_tasks`` (all ``T`` outputs)."""
-    dev = _check_model(model, resident, tasks)
-    bs, n = int(batch_size), int(resident.n_molecules)
-    T = int(model.ffn.out_features)
-    shape = (n, T) if tasks else (n,)
-    if bs < 1:
-        raise ValueError("batch_size >= 1")
-    if topk is not None and (isinstance(topk, TopKTasks) != tasks or (tasks and topk.n_tasks != T)):
-        raise ValueError(f"{who}: the running list must be a " + (f"TopKTasks of {T} tasks" if tasks else "TopK"))
-    if topk is not None and topk.device != dev:
-        raise ValueError(f"the running list is on {topk.device}, the model on {dev}")
+def _check_out(out, shape, dev) -> None:
     if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != shape or not out.is_contiguous()):
         raise ValueError(f"out: a contiguous float32 tensor of shape {shape} on {dev}")
-    was_training = model.training
-    model.eval()
-    try:
-        rank = None
-        if topk is not None:
-            topk.reserve(bs)
-            topk.shard_tag.fill_(int(shard_tag))
-            rank = lambda pred, ids, n_live: topk.update(pred, ids, n_valid=n_live)     # noqa: E731
-        if tasks:
-            scoring = _ScoringStep(model, resident, bs, rank, predict=lambda data: model.predict_tasks(data)[0], width=T)
-        else:
-            scoring = _ScoringStep(model, resident, bs, rank)
+
+
+def _run_shard(who: str, doing: str, model, resident, dev, batch_size: int, predict, shape, topk=None, list_class=TopK,
+               n_lists: Optional[int] = None, per_query: bool = False, shard_tag: int = 0, out=None) -> torch.Tensor:
+    """The one pass over a resident shard, behind the callers' own checks of model and shard (``dev``: their device): one captured
+    ``_ScoringStep`` with ``predict`` (``shape``: the shape of one molecule's result) replayed over every batch; the ``[n, *shape]``
+    result (copied into ``out`` when given, and ``out`` returned); the gather's status word read once, at the end.  ``topk``, when
+    given, must be a ``list_class`` (a ``TopKTasks``: of ``n_lists`` lists, one per task, or ``per_query``) on ``dev``: every
+    batch's live rows enter it under ``shard_tag``.  ``who`` names the entry point in a refusal, ``doing`` what a status interrupted.
+    The model runs in evaluation mode and is handed back in the mode it came in."""
+    from .train import evaluation_mode
+    bs, n = int(batch_size), int(resident.n_molecules)
+    if bs < 1:
+        raise ValueError("batch_size >= 1")
+    if topk is not None:
+        noun, verb, unit = ("lists", "are", "lists, one per query") if per_query else ("list", "is", "tasks")
+        many = list_class is TopKTasks
+        if isinstance(topk, TopKTasks) != many or (many and topk.n_tasks != n_lists):
+            raise ValueError(f"{who}: the running {noun} must be a " + (f"TopKTasks of {n_lists} {unit}" if many else "TopK"))
+        if topk.device != dev:
+            raise ValueError(f"the running {noun} {verb} on {topk.device}, the model on {dev}")
+    _check_out(out, (n, *shape), dev)
+    rank = None
+    if topk is not None:
+        topk.reserve(bs)
+        topk.shard_tag.fill_(int(shard_tag))
+        rank = lambda pred, ids, n_live: topk.update(pred, ids, n_valid=n_live)     # noqa: E731
+    with evaluation_mode(model):
+        scoring = _ScoringStep(model, resident, bs, predict, shape, rank)
         for b in range(len(scoring)):
             scoring.run(b)
         if out is None:
@@ -344,10 +356,8 @@ def _score_shard(who: str, model, resident, batch_size: int, topk, shard_tag: in
             out.copy_(scoring.ext[:n])
         status = scoring.csb.gather_status()             # (the one host read)
         if status:
-            raise RuntimeError(f"mkgnn_gather_compact reported status {status} while scoring the shard")
+            raise RuntimeError(f"mkgnn_gather_compact reported status {status} while {doing} the shard")
         return out
-    finally:
-        model.train(was_training)
 
 
 def score_resident(model, resident, batch_size: int, *, topk: Optional[TopK] = None, shard_tag: int = 0,
@@ -364,7 +374,9 @@ def score_resident(model, resident, batch_size: int, *, topk: Optional[TopK] = N
 
     The model is put in evaluation mode and handed back in the mode it came in.  It must be a one-task model on the shard's
     GPU: anything else raises ``ValueError`` before a launch."""
-    return _score_shard("score_resident", model, resident, batch_size, topk, shard_tag, out, False)
+    dev = _check_model(model, resident)
+    return _run_shard("score_resident", "scoring", model, resident, dev, batch_size, lambda data: model.predict(data)[0].reshape(-1), (),
+                      topk, TopK, shard_tag=shard_tag, out=out)
 
 
 def score_resident_tasks(model, resident, batch_size: int, *, topk: Optional[TopKTasks] = None, shard_tag: int = 0,
@@ -376,7 +388,29 @@ def score_resident_tasks(model, resident, batch_size: int, *, topk: Optional[Top
     ``mkgnn_topk_update_tasks`` that feeds every batch's live rows to all ``T`` lists of a ``TopKTasks`` under ``shard_tag``.  ``out``
     (``[n_molecules, T]``, contiguous) is filled with NaN first.  The model needs ``1 <= T <= 32`` outputs and must be on the
     shard's GPU: anything else raises ``ValueError`` before a launch.  It comes back in the mode it came in."""
-    return _score_shard("score_resident_tasks", model, resident, batch_size, topk, shard_tag, out, True)
+    dev = _check_model(model, resident, tasks=True)
+    T = int(model.ffn.out_features)
+    return _run_shard("score_resident_tasks", "scoring", model, resident, dev, batch_size, lambda data: model.predict_tasks(data)[0], (T,),
+                      topk, TopKTasks, T, shard_tag=shard_tag, out=out)
+
+
+def _over_shards(who: str, residents, check, make_lists, per_shard, keep: bool):
+    """The loop of ``screen``, ``screen_tasks`` and ``nearest``: shard ``j`` of ``residents`` (a sequence, or a generator, consumed one
+    shard at a time) carries tag ``j``; it is checked (``check(resident)`` -> its device), the running lists are made on the first
+    shard's device (``make_lists(dev)``), and ``per_shard(resident, lists, tag)`` runs it.  Returns ``lists.result()``, the number of
+    molecules and the per-shard results (kept only with ``keep``); no shard at all raises."""
+    lists, n_molecules, kept = None, 0, []
+    for tag, resident in enumerate(residents):
+        dev = check(resident)
+        if lists is None:
+            lists = make_lists(dev)
+        result = per_shard(resident, lists, tag)
+        n_molecules += int(resident.n_molecules)
+        if keep:
+            kept.append(result)
+    if lists is None:
+        raise ValueError(f"{who} needs at least one shard")
+    return (*lists.result(), n_molecules, kept)
 
 
 def screen(model, residents, k: int, batch_size: int, return_scores: bool = False) -> dict:
@@ -384,18 +418,9 @@ def screen(model, residents, k: int, batch_size: int, return_scores: bool = Fals
     library larger than device memory); shard ``j`` carries tag ``j``.  One ``TopK`` of ``k`` slots is carried across the
     shards on the device.  Returns ``top_score``, ``top_shard``, ``top_mol`` (trimmed to the occupied slots, best first) and
     ``n_scored``; with ``return_scores`` also ``scores``, the per-shard score vectors."""
-    topk, n_scored, kept = None, 0, []
-    for tag, resident in enumerate(residents):
-        dev = _check_model(model, resident)
-        if topk is None:
-            topk = TopK(k, dev)
-        scores = score_resident(model, resident, batch_size, topk=topk, shard_tag=tag)
-        n_scored += int(resident.n_molecules)
-        if return_scores:
-            kept.append(scores)
-    if topk is None:
-        raise ValueError("screen needs at least one shard")
-    top_score, top_shard, top_mol, occupied = topk.result()
+    top_score, top_shard, top_mol, occupied, n_scored, kept = _over_shards(
+        "screen", residents, lambda r: _check_model(model, r), lambda dev: TopK(k, dev),
+        lambda r, topk, tag: score_resident(model, r, batch_size, topk=topk, shard_tag=tag), return_scores)
     result = {"top_score": top_score[:occupied], "top_shard": top_shard[:occupied], "top_mol": top_mol[:occupied],
               "n_scored": n_scored}
     if return_scores:
@@ -409,18 +434,10 @@ def screen_tasks(model, residents, k: int, batch_size: int, return_scores: bool 
     ``top_mol`` as ``[T, k]`` tensors, list ``t`` best first with its empty slots -- ``(-inf, -1, -1)`` -- at the end (not trimmed:
     the lists fill alike, but a tensor has one width), ``n_occupied`` (int64 ``[T]``, on the host), ``n_scored`` and, with
     ``return_scores``, ``scores``: the per-shard ``[n_molecules, T]`` tensors."""
-    topk, n_scored, kept = None, 0, []
-    for tag, resident in enumerate(residents):
-        dev = _check_model(model, resident, tasks=True)
-        if topk is None:
-            topk = TopKTasks(k, int(model.ffn.out_features), dev)
-        scores = score_resident_tasks(model, resident, batch_size, topk=topk, shard_tag=tag)
-        n_scored += int(resident.n_molecules)
-        if return_scores:
-            kept.append(scores)
-    if topk is None:
-        raise ValueError("screen_tasks needs at least one shard")
-    top_score, top_shard, top_mol, occupied = topk.result()
+    top_score, top_shard, top_mol, occupied, n_scored, kept = _over_shards(
+        "screen_tasks", residents, lambda r: _check_model(model, r, tasks=True),
+        lambda dev: TopKTasks(k, int(model.ffn.out_features), dev),
+        lambda r, topk, tag: score_resident_tasks(model, r, batch_size, topk=topk, shard_tag=tag), return_scores)
     result = {"top_score": top_score, "top_shard": top_shard, "top_mol": top_mol, "n_occupied": occupied, "n_scored": n_scored}
     if return_scores:
         result["scores"] = kept
@@ -515,33 +532,6 @@ def _embedding_width(model) -> int:
     return G
 
 
-def _run_shard(model, resident, bs: int, width: int, predict, rank, out) -> torch.Tensor:
-    """One captured ``_ScoringStep`` over the shard with ``predict`` (``width`` values per molecule) and ``rank``; the ``[n, width]``
-    result (into ``out`` when given); the gather's status word read once; the model handed back in its mode."""
-    n = int(resident.n_molecules)
-    was_training = model.training
-    model.eval()
-    try:
-        scoring = _ScoringStep(model, resident, bs, rank, predict=predict, width=width)
-        for b in range(len(scoring)):
-            scoring.run(b)
-        if out is None:
-            out = scoring.ext[:n]
-        else:
-            out.copy_(scoring.ext[:n])
-        status = scoring.csb.gather_status()             # (the one host read)
-        if status:
-            raise RuntimeError(f"mkgnn_gather_compact reported status {status} while embedding the shard")
-        return out
-    finally:
-        model.train(was_training)
-
-
-def _check_out(out, shape, dev) -> None:
-    if out is not None and (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != shape or not out.is_contiguous()):
-        raise ValueError(f"out: a contiguous float32 tensor of shape {shape} on {dev}")
-
-
 def embed_resident(model, resident, batch_size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``emb[n_molecules, G]`` (float32, on the device): ``model.embed`` of every molecule of the ``ResidentShard``, in id order, the
     short tail included, as ``score_resident`` does it -- one captured graph per call, replayed per batch, with the embedding in the
@@ -551,11 +541,7 @@ def embed_resident(model, resident, batch_size: int, out: Optional[torch.Tensor]
     The matrix can be kept and ranked again and again (``rank_embeddings``) without running the network."""
     G = _embedding_width(model)
     dev = _check_device(model, resident)
-    bs, n = int(batch_size), int(resident.n_molecules)
-    if bs < 1:
-        raise ValueError("batch_size >= 1")
-    _check_out(out, (n, G), dev)
-    return _run_shard(model, resident, bs, G, model.embed, None, out)
+    return _run_shard("embed_resident", "embedding", model, resident, dev, batch_size, model.embed, (G,), out=out)
 
 
 def nearest_resident(model, resident, query_emb: torch.Tensor, batch_size: int, *, topk: Optional[TopKTasks] = None,
@@ -574,22 +560,10 @@ def nearest_resident(model, resident, query_emb: torch.Tensor, batch_size: int, 
     Q = _check_queries("nearest_resident", query_emb, _embedding_width(model))
     dev = _check_device(model, resident)
     _check_queries("nearest_resident", query_emb, query_emb.shape[1], dev)
-    bs, n = int(batch_size), int(resident.n_molecules)
-    if bs < 1:
-        raise ValueError("batch_size >= 1")
-    if topk is not None and (not isinstance(topk, TopKTasks) or topk.n_tasks != Q):
-        raise ValueError(f"nearest_resident: the running lists must be a TopKTasks of {Q} lists, one per query")
-    if topk is not None and topk.device != dev:
-        raise ValueError(f"the running lists are on {topk.device}, the model on {dev}")
-    _check_out(out, (n, Q), dev)
     from .readout import embedding_cosine
     queries = query_emb.detach()
-    rank = None
-    if topk is not None:
-        topk.reserve(bs)
-        topk.shard_tag.fill_(int(shard_tag))
-        rank = lambda sim, ids, n_live: topk.update(sim, ids, n_valid=n_live)     # noqa: E731
-    return _run_shard(model, resident, bs, Q, lambda data: embedding_cosine(model.embed(data), queries), rank, out)
+    return _run_shard("nearest_resident", "embedding", model, resident, dev, batch_size,
+                      lambda data: embedding_cosine(model.embed(data), queries), (Q,), topk, TopKTasks, Q, True, shard_tag, out)
 
 
 def nearest(model, queries, residents, k: int, batch_size: int, return_sims: bool = False) -> dict:
@@ -617,18 +591,9 @@ def nearest(model, queries, residents, k: int, batch_size: int, return_sims: boo
     Q = _check_queries("nearest", query_emb, G, dev if dev.type == "cuda" else None)
     if dev.type != "cuda":
         raise ValueError("nearest runs on the GPU: move the model there (there is no CPU path)")
-    topk, n_searched, kept = None, 0, []
-    for tag, resident in enumerate(residents):
-        _check_device(model, resident)
-        if topk is None:
-            topk = TopKTasks(k, Q, dev)
-        sim = nearest_resident(model, resident, query_emb, batch_size, topk=topk, shard_tag=tag)
-        n_searched += int(resident.n_molecules)
-        if return_sims:
-            kept.append(sim)
-    if topk is None:
-        raise ValueError("nearest needs at least one shard")
-    top_sim, top_shard, top_mol, occupied = topk.result()
+    top_sim, top_shard, top_mol, occupied, n_searched, kept = _over_shards(
+        "nearest", residents, lambda r: _check_device(model, r), lambda dev: TopKTasks(k, Q, dev),
+        lambda r, topk, tag: nearest_resident(model, r, query_emb, batch_size, topk=topk, shard_tag=tag), return_sims)
     result = {"top_sim": top_sim, "top_shard": top_shard, "top_mol": top_mol, "n_occupied": occupied, "n_searched": n_searched,
               "query_emb": query_emb}
     if return_sims:

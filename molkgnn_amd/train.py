@@ -9,11 +9,13 @@ Scoring: ``GNNModel.predict``, ``evaluate`` (the reference's validation / test l
 ``evaluate_resident`` (the same from a device-resident shard; ranking a library: ``molkgnn_amd.screening``).
 Multi-task models: ``GNNModel.predict_tasks`` (all outputs of every molecule), ``evaluate_tasks``, ``evaluate_resident_tasks``.
 The graph embedding alone: ``GNNModel.embed`` (analogue search: ``screening.nearest``).
+All of them, and ``screening``'s shard passes, run the model inside ``evaluation_mode``.
 Logging, checkpoints, file output and the LR schedule are out of scope.
 """
 from __future__ import annotations
 
 import weakref
+from contextlib import contextmanager
 from typing import Optional
 
 import torch
@@ -52,6 +54,10 @@ class GNNModel(torch.nn.Module):
             pred = self.ffn(graph_embedding)
         return pred, graph_embedding
 
+    def _needs_eval(self, who: str, hint: str = "") -> None:
+        if self.training:
+            raise ValueError(f"GNNModel.{who} needs evaluation mode: call model.eval() first{hint}")
+
     def predict(self, data):
         """``(pred [n, 1], graph_embedding [n, G])`` of a model in evaluation mode, under ``torch.no_grad()``: what the reference's
         ``validation_step`` / ``test_step`` take from ``self(batch)`` (``model.py:221-232, 299-305``).  ``n``: the batch's real
@@ -59,8 +65,7 @@ class GNNModel(torch.nn.Module):
         qualify (one task, CUDA, the fused tail's shapes and molecule sizes) everything behind the last convolution is the
         forward-only tail -- two launches, ``readout.tail_score``; ``MKGNN_SCORE_TAIL=0`` or ``MKGNN_FUSED_TAIL=0``: never --
         and the separate operators of ``self(data)`` otherwise.  The mode is the caller's: in training mode this raises."""
-        if self.training:
-            raise ValueError("GNNModel.predict needs evaluation mode: call model.eval() first (train.evaluate does)")
+        self._needs_eval("predict", " (train.evaluate does)")
         with torch.no_grad():
             nreal = getattr(data, 'n_valid_molecules', None)
             score = (self.ffn, nreal) if (self.ffn.out_features == 1 and data.x.is_cuda) else None
@@ -93,8 +98,7 @@ class GNNModel(torch.nn.Module):
         analysis compares molecules by, and what analogue search ranks (``screening.nearest``); ``n`` as in ``predict``.  It is
         ``predict_tasks(data)[1]`` bit for bit without the scores -- the same route (``_embedding``), for any ``task_dim``.  In
         training mode this raises."""
-        if self.training:
-            raise ValueError("GNNModel.embed needs evaluation mode: call model.eval() first")
+        self._needs_eval("embed")
         with torch.no_grad():
             graph_embedding, n = self._embedding(data)
             return graph_embedding[:n]
@@ -106,8 +110,7 @@ class GNNModel(torch.nn.Module):
         one-row view of the head, which it needs, and its own ``pred`` is dropped) and from the separate operators otherwise; on the
         GPU ``pred`` is ``readout.task_scores`` of it -- one launch, bit for bit the task-indexed head's ``pred`` of every (molecule,
         task) pair.  ``predict`` keeps its own route (and bits) for a multi-task model.  In training mode this raises."""
-        if self.training:
-            raise ValueError("GNNModel.predict_tasks needs evaluation mode: call model.eval() first")
+        self._needs_eval("predict_tasks")
         with torch.no_grad():
             graph_embedding, n = self._embedding(data)
             if graph_embedding.is_cuda:
@@ -239,6 +242,45 @@ def _metric_functions() -> dict:
     }
 
 
+def _check_metrics(metrics) -> dict:
+    """``_metric_functions()``, once every name in ``metrics`` is known to be one of them."""
+    table = _metric_functions()
+    unknown = [m for m in metrics if m not in table]
+    if unknown:
+        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(table)}")
+    return table
+
+
+def _required_loss_kind(model, who: str) -> str:
+    kind = model._loss_kind()
+    if kind is None:
+        raise ValueError(f"{who} needs one of the head's loss kinds (BCEWithLogitsLoss(), MSELoss(), MSELoss('sum'))")
+    return kind
+
+
+@contextmanager
+def evaluation_mode(model):
+    """``with evaluation_mode(model):`` -- the model in evaluation mode inside, and back in the mode it came in afterwards, also
+    when the body raises."""
+    was_training = model.training
+    model.eval()
+    try:
+        yield model
+    finally:
+        model.train(was_training)
+
+
+def _results(model, pred_y: torch.Tensor, true_y: torch.Tensor, metrics, table: dict) -> dict:
+    """The second half of ``evaluate`` and of ``evaluate_resident``: ``validation_epoch_end`` + ``get_evaluations`` on the whole
+    vectors -- the model's loss, every metric, and the two vectors themselves."""
+    with torch.no_grad():
+        results = {'loss': model.loss_func(pred_y, true_y.float())}
+    for m in metrics:
+        results[m] = table[m](true_y, pred_y)
+    results['pred_y'], results['true_y'] = pred_y, true_y
+    return results
+
+
 def evaluate(model, batches, metrics=()) -> dict:
     """The reference's validation / test loop without Lightning: ``validation_step`` per batch (``model.py:221-244``:
     ``pred_y = self(batch)[0].view(-1)``, ``true_y = batch.y.view(-1)``), then ``validation_epoch_end`` + ``get_evaluations``
@@ -251,13 +293,8 @@ def evaluate(model, batches, metrics=()) -> dict:
     from ``model.predict``; they and the labels (the first ``len(pred)`` of a batch's ``y``: a padded batch's real molecules)
     stay on their device, and nothing synchronises with the host before the last batch is launched.  Writing files and
     logging are the caller's."""
-    table = _metric_functions()
-    unknown = [m for m in metrics if m not in table]
-    if unknown:
-        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(table)}")
-    was_training = model.training
-    model.eval()
-    try:
+    table = _check_metrics(metrics)
+    with evaluation_mode(model):
         all_pred, all_true = [], []
         for batch in batches:
             pred, _ = model.predict(batch)
@@ -266,15 +303,7 @@ def evaluate(model, batches, metrics=()) -> dict:
             all_true.append(batch.y.view(-1)[:pred.shape[0]])
         if not all_pred:
             raise ValueError("evaluate needs at least one batch")
-        pred_y, true_y = torch.cat(all_pred), torch.cat(all_true)
-        with torch.no_grad():
-            results = {'loss': model.loss_func(pred_y, true_y.float())}
-        for m in metrics:
-            results[m] = table[m](true_y, pred_y)
-        results['pred_y'], results['true_y'] = pred_y, true_y
-        return results
-    finally:
-        model.train(was_training)
+        return _results(model, torch.cat(all_pred), torch.cat(all_true), metrics, table)
 
 
 def _task_results(pred: torch.Tensor, true_y: torch.Tensor, task: torch.Tensor, T: int, kind: str, metrics, table: dict) -> dict:
@@ -308,17 +337,10 @@ def evaluate_tasks(model, batches, metrics=(), num_tasks: Optional[int] = None) 
     vectors (``readout.task_head_reference`` on the model's loss kind), ``pred_y`` every molecule's prediction for ITS task (NaN
     where it has none), ``true_y`` and ``task``.  ``num_tasks`` defaults to the model's outputs.  The model is put in evaluation
     mode and handed back in the mode it came in, also when a batch raises."""
-    table = _metric_functions()
-    unknown = [m for m in metrics if m not in table]
-    if unknown:
-        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(table)}")
-    kind = model._loss_kind()
-    if kind is None:
-        raise ValueError("evaluate_tasks needs one of the head's loss kinds (BCEWithLogitsLoss(), MSELoss(), MSELoss('sum'))")
+    table = _check_metrics(metrics)
+    kind = _required_loss_kind(model, "evaluate_tasks")
     T = model.ffn.out_features if num_tasks is None else int(num_tasks)
-    was_training = model.training
-    model.eval()
-    try:
+    with evaluation_mode(model):
         all_pred, all_true, all_task = [], [], []
         for batch in batches:
             task = getattr(batch, 'task', None)
@@ -332,8 +354,6 @@ def evaluate_tasks(model, batches, metrics=(), num_tasks: Optional[int] = None) 
         if not all_pred:
             raise ValueError("evaluate_tasks needs at least one batch")
         return _task_results(torch.cat(all_pred), torch.cat(all_true), torch.cat(all_task).long(), T, kind, metrics, table)
-    finally:
-        model.train(was_training)
 
 
 def evaluate_resident(model, resident, batch_size: int, metrics=()) -> dict:
@@ -342,18 +362,9 @@ def evaluate_resident(model, resident, batch_size: int, metrics=()) -> dict:
     captured graph -- and ``true_y`` from ``resident.y``.  Unknown metric names raise before anything is launched; the model
     comes back in the mode it came in."""
     from .screening import score_resident
-    table = _metric_functions()
-    unknown = [m for m in metrics if m not in table]
-    if unknown:
-        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(table)}")
+    table = _check_metrics(metrics)
     pred_y = score_resident(model, resident, batch_size)
-    true_y = resident.y.to(pred_y.device).view(-1)
-    with torch.no_grad():
-        results = {'loss': model.loss_func(pred_y, true_y.float())}
-    for m in metrics:
-        results[m] = table[m](true_y, pred_y)
-    results['pred_y'], results['true_y'] = pred_y, true_y
-    return results
+    return _results(model, pred_y, resident.y.to(pred_y.device).view(-1), metrics, table)
 
 
 def evaluate_resident_tasks(model, resident, batch_size: int, metrics=()) -> dict:
@@ -365,15 +376,10 @@ def evaluate_resident_tasks(model, resident, batch_size: int, metrics=()) -> dic
     metric names, a shard without ``assays`` and a loss that is none of the head's kinds raise before anything is launched; the
     model comes back in the mode it came in."""
     from .screening import score_resident_tasks
-    table = _metric_functions()
-    unknown = [m for m in metrics if m not in table]
-    if unknown:
-        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(table)}")
+    table = _check_metrics(metrics)
     if getattr(resident, "task", None) is None:
         raise ValueError("evaluate_resident_tasks needs a shard that knows every molecule's task: ResidentShard(..., assays=...)")
-    kind = model._loss_kind()
-    if kind is None:
-        raise ValueError("evaluate_resident_tasks needs one of the head's loss kinds (BCEWithLogitsLoss(), MSELoss(), MSELoss('sum'))")
+    kind = _required_loss_kind(model, "evaluate_resident_tasks")
     pred = score_resident_tasks(model, resident, batch_size)
     true_y = resident.y.to(pred.device).view(-1)
     task = resident.task.to(pred.device).view(-1).long()

@@ -6,14 +6,11 @@ import pytest
 import torch
 
 from tests import _screen_cases as SC
+from tests._resident_library import bits as _bits, build_library, eval_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 G = 32
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32).cpu().numpy()
 
 
 def _host(topk):
@@ -34,39 +31,10 @@ def library(tmp_path_factory):
     """The fixture shape of test_screen_tasks_gpu.py -- two resident shards (70 and 33 synthetic molecules), batch 32, 3-layer models
     with non-trivial running statistics: a nine-task and a one-task model -- a three-molecule query shard and, computed ONCE,
     eagerly, ``predict_tasks(data)[1]`` and ``embed(data)`` of both models on the gathered batches of each shard (live slots only)."""
-    from molkgnn_amd import shards as S
-    from molkgnn_amd.receptive_field import attach_receptive_fields
-    from molkgnn_amd.screening import static_batch_for
-    from molkgnn_amd.synthetic import make_batch
-    from molkgnn_amd.train import GNNModel
-    d = tmp_path_factory.mktemp("library_nearest")
-    residents = []
-    for j, n in enumerate((70, 33, 3)):
-        b = make_batch(n, seed=40 + j, assay="all9", with_receptive_fields=False)
-        b.y = (torch.arange(n) % 3 == 0).float()
-        path = str(d / f"lib-{j}.mkgs")
-        S.write_shard(path, b)
-        residents.append(S.ResidentShard(path, DEV))
+    nine, residents, gathered = build_library(tmp_path_factory.mktemp("library_nearest"), DEV, counts=(70, 33, 3), shard_seed=40,
+                                              labels=lambda n: (torch.arange(n) % 3 == 0).float(), model_seed=9, num_layers=3, task_dim=9)
     query_shard = residents.pop()
-    models = {}
-    for T in (9, 1):
-        torch.manual_seed(T)
-        model = GNNModel(num_layers=3, task_dim=T).to(DEV)
-        with torch.no_grad():                                      # (running statistics that are not the initial 0 / 1)
-            for m in model.modules():
-                if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
-                    m.running_mean.uniform_(-0.2, 0.2)
-                    m.running_var.uniform_(0.5, 1.5)
-        models[T] = model.eval()
-
-    def gathered(resident):
-        loader = S.ResidentLoader(resident, 32, np.arange(resident.n_molecules), DEV, drop_last=False)
-        csb = static_batch_for(loader, resident)
-        for ids, live in zip(loader, loader.n_live.tolist()):
-            csb.gather(resident, ids)
-            csb.expand()
-            attach_receptive_fields(csb.data, sizes=csb.data.bucket_sizes, overlap=True)
-            yield csb.data, live
+    models = {9: nine, 1: eval_model(DEV, 1, num_layers=3, task_dim=1)}
 
     tails = {T: [] for T in models}                                # predict_tasks(data)[1]
     embeds = {T: [] for T in models}                               # embed(data)

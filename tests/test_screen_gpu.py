@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import _screen_cases as SC
+from tests._resident_library import bits as _bits, build_library
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -135,46 +136,13 @@ def test_one_captured_update_serves_every_batch(B, K):
 def library(tmp_path_factory):
     """Two resident shards (70 and 33 synthetic molecules), a 3-layer default model with non-trivial running statistics, and
     -- computed ONCE, eagerly -- ``model.predict`` on the gathered batches of each shard (live slots only)."""
-    from molkgnn_amd import shards as S
-    from molkgnn_amd.receptive_field import attach_receptive_fields
-    from molkgnn_amd.screening import static_batch_for
-    from molkgnn_amd.synthetic import make_batch
-    from molkgnn_amd.train import GNNModel
-    d = tmp_path_factory.mktemp("library")
-    residents = []
-    for j, n in enumerate((70, 33)):
-        b = make_batch(n, seed=40 + j, assay="all9", with_receptive_fields=False)
-        b.y = (torch.arange(n) % 3 == 0).float()
-        path = str(d / f"lib-{j}.mkgs")
-        S.write_shard(path, b)
-        residents.append(S.ResidentShard(path, DEV))
-    torch.manual_seed(0)
-    model = GNNModel(num_layers=3).to(DEV)
-    with torch.no_grad():                                      # (running statistics that are not the initial 0 / 1)
-        for m in model.modules():
-            if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
-                m.running_mean.uniform_(-0.2, 0.2)
-                m.running_var.uniform_(0.5, 1.5)
-    model.eval()
-
-    def gathered(resident):
-        loader = S.ResidentLoader(resident, 32, np.arange(resident.n_molecules), DEV, drop_last=False)
-        csb = static_batch_for(loader, resident)
-        for ids, live in zip(loader, loader.n_live.tolist()):
-            csb.gather(resident, ids)
-            csb.expand()
-            attach_receptive_fields(csb.data, sizes=csb.data.bucket_sizes, overlap=True)
-            yield csb.data, live
-
+    model, residents, gathered = build_library(tmp_path_factory.mktemp("library"), DEV, counts=(70, 33), shard_seed=40,
+                                               labels=lambda n: (torch.arange(n) % 3 == 0).float(), model_seed=0, num_layers=3)
     eager = []
     for r in residents:
         eager.append(torch.cat([model.predict(data)[0].view(-1)[:live].clone() for data, live in gathered(r)]))
     model.train()
     return model, residents, eager, gathered
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32).cpu().numpy()
 
 
 def test_score_resident_equals_predict_on_the_gathered_batches(library):

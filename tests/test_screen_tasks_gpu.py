@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from tests import _screen_cases as SC
+from tests._resident_library import bits as _bits, build_library, eval_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -23,10 +24,6 @@ def _host(topk):
 
 def _dev(a, dtype):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV).to(dtype)
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32).cpu().numpy()
 
 
 def _task_inputs(B, T, seed):
@@ -189,41 +186,16 @@ def library(tmp_path_factory):
     one-task model that shares the nine-task model's network -- and, computed ONCE, eagerly, ``predict_tasks`` of the nine-task
     model and ``predict`` of the one-task model on the gathered batches of each shard (live slots only)."""
     from molkgnn_amd import shards as S
-    from molkgnn_amd.receptive_field import attach_receptive_fields
-    from molkgnn_amd.screening import static_batch_for
-    from molkgnn_amd.synthetic import NINE_ASSAYS, make_batch
+    from molkgnn_amd.synthetic import NINE_ASSAYS
     from molkgnn_amd.train import GNNModel
     d = tmp_path_factory.mktemp("library_tasks")
-    residents = []
-    for j, n in enumerate((70, 33)):
-        b = make_batch(n, seed=40 + j, assay="all9", with_receptive_fields=False)
-        b.y = (torch.arange(n) % 3 == 0).float()
-        path = str(d / f"lib-{j}.mkgs")
-        S.write_shard(path, b)
-        residents.append(S.ResidentShard(path, DEV))
+    nine, residents, gathered = build_library(d, DEV, counts=(70, 33), shard_seed=40, labels=lambda n: (torch.arange(n) % 3 == 0).float(),
+                                              model_seed=9, num_layers=3, task_dim=9)
     labelled = S.ResidentShard(str(d / "lib-0.mkgs"), DEV, assays=[int(a) for a in NINE_ASSAYS][:8])    # (one assay is not listed)
-    models = {}
-    for T in (9, 2):
-        torch.manual_seed(T)
-        model = GNNModel(num_layers=3, task_dim=T).to(DEV)
-        with torch.no_grad():                                      # (running statistics that are not the initial 0 / 1)
-            for m in model.modules():
-                if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
-                    m.running_mean.uniform_(-0.2, 0.2)
-                    m.running_var.uniform_(0.5, 1.5)
-        models[T] = model.eval()
+    models = {9: nine, 2: eval_model(DEV, 2, num_layers=3, task_dim=2)}
     one = GNNModel(num_layers=3, task_dim=1).to(DEV)
     one.gnn_model = models[9].gnn_model                            # the same network, a one-task head
     one.eval()
-
-    def gathered(resident):
-        loader = S.ResidentLoader(resident, 32, np.arange(resident.n_molecules), DEV, drop_last=False)
-        csb = static_batch_for(loader, resident)
-        for ids, live in zip(loader, loader.n_live.tolist()):
-            csb.gather(resident, ids)
-            csb.expand()
-            attach_receptive_fields(csb.data, sizes=csb.data.bucket_sizes, overlap=True)
-            yield csb.data, live
 
     eager = {T: [] for T in models}
     emb9, emb1 = [], []

@@ -55,9 +55,10 @@ def child(variant, shard_path, batches, k, steps, windows, warmup):
         if variant == "one":
             lists = TopK(k, dev)
             lists.reserve(B)
-            scoring = _ScoringStep(model, resident, B, lambda pred, ids, n_live: lists.update(pred, ids, n_valid=n_live))
+            scoring = _ScoringStep(model, resident, B, lambda data: model.predict(data)[0].reshape(-1), (),
+                                   lambda pred, ids, n_live: lists.update(pred, ids, n_valid=n_live))
         elif variant == "embed":
-            scoring = _ScoringStep(model, resident, B, None, predict=model.embed, width=G)
+            scoring = _ScoringStep(model, resident, B, model.embed, (G,))
         else:
             lists = TopKTasks(k, Q, dev)
             lists.reserve(B)
@@ -66,8 +67,8 @@ def child(variant, shard_path, batches, k, steps, windows, warmup):
             else:
                 predict = lambda data: torch.nn.functional.cosine_similarity(                                   # noqa: E731
                     model.embed(data)[:, None, :], queries[None, :, :], dim=-1).contiguous()
-            scoring = _ScoringStep(model, resident, B, lambda sim, ids, n_live: lists.update(sim, ids, n_valid=n_live),
-                                   predict=predict, width=Q)
+            scoring = _ScoringStep(model, resident, B, predict, (Q,),
+                                   lambda sim, ids, n_live: lists.update(sim, ids, n_valid=n_live))
         nb = len(scoring)
         for i in range(warmup):
             scoring.run(i % nb)

@@ -63,9 +63,9 @@ def child(variant, shard_path, batches, k, n_tasks, steps, windows, warmup):
         for top in lists:
             top.reserve(B)
         if variant == "one":
-            scoring = _ScoringStep(model, resident, B, rank)
+            scoring = _ScoringStep(model, resident, B, lambda data: model.predict(data)[0].reshape(-1), (), rank)
         else:
-            scoring = _ScoringStep(model, resident, B, rank, predict=lambda data: model.predict_tasks(data)[0], width=T)
+            scoring = _ScoringStep(model, resident, B, lambda data: model.predict_tasks(data)[0], (T,), rank)
         nb = len(scoring)
         for i in range(warmup):
             scoring.run(i % nb)

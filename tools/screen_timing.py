@@ -70,7 +70,7 @@ def child(variant, shard_path, batches, k, steps, windows, warmup, packed=False)
         topk.reserve(B)
         rank = {"none": None, "hip": lambda pred, ids, n_live: topk.update(pred, ids, n_valid=n_live),
                 "torch": torch_ranker(topk, 0)}[variant]
-        scoring = _ScoringStep(model, resident, B, rank)
+        scoring = _ScoringStep(model, resident, B, lambda data: model.predict(data)[0].reshape(-1), (), rank)
         nb = len(scoring)
         for i in range(warmup):
             scoring.run(i % nb)
