@@ -9,6 +9,7 @@ from molkgnn_amd import padding as P
 from molkgnn_amd import shards as S
 from molkgnn_amd.sampling import oversampling_sampler
 from molkgnn_amd.synthetic import make_batch
+from tests import _batch_cases as C
 
 DIMS = (28, 3, 7)
 
@@ -97,6 +98,47 @@ def test_arbitrary_ids_equal_the_recollated_molecules(whole, shard, tmp_path):
     again = np.full(total, 0xEF, dtype=np.uint8)
     S.gather_compact(shard, torch.from_numpy(ids), shape, again)
     _assert_same_wire(again, want, shape, 64)
+
+
+@pytest.mark.parametrize("e_dim", [1, 5, 12])
+def test_hand_made_molecules_equal_their_recollation(e_dim, tmp_path):
+    """The definition itself at the widths and molecule sizes the synthetic shard does not have (tests/_batch_cases.py: two-atom
+    molecules, a 300-atom chain, ``p_dim`` 4, 1 / 5 / 12 attribute bytes per bond): ``gather_compact`` of an id list equals the
+    same molecules collated again by hand, written as a shard of their own and padded by ``collate_compact`` -- for the loader's
+    shape, for the exact shape (no padding atom: all 64 padding molecules empty) and for shapes whose whole padding is fewer
+    atoms than there are padding molecules."""
+    dims = (6, 4, e_dim)
+    mols = C.molecules(*dims, seed=e_dim)
+    S.write_shard(str(tmp_path / "custom.mkgs"), C.collate(mols))
+    shard = S.Shard(str(tmp_path / "custom.mkgs"))
+    assert shard.compact_ok and shard.n_molecules == 57 and (shard.n_atoms, shard.n_edges) == (500, 886)
+    assert (shard.x_dim, shard.p_dim, shard.e_dim) == dims
+    res = S.ResidentShard(shard, "cpu")
+    for n in (1, 57, 200):
+        for name, ids in C.id_lists(n, 57).items():
+            picked = [mols[int(m)] for m in ids]
+            S.write_shard(str(tmp_path / "picked.mkgs"), C.collate(picked))
+            shard2 = S.Shard(str(tmp_path / "picked.mkgs"))
+            counts = C.degree_counts(picked)
+            assert shard2.degree_histogram(0, n)[1:5] == counts == _ids_histogram(shard, ids)[1:5]
+            shapes = {"loader": S.ResidentLoader(res, n, ids, "cpu").shape, "exact": C.shape_with_padding(counts),
+                      "3 padding atoms": C.shape_with_padding(counts, (2, 1, 0, 0)),
+                      "63 padding atoms": C.shape_with_padding(counts, (20, 20, 20, 3))}
+            for what, shape in shapes.items():
+                table, total = S.compact_layout(shape, n, *dims)
+                want = np.full(total, 0xAB, dtype=np.uint8)
+                got = np.full(total, 0xCD, dtype=np.uint8)
+                S.collate_compact(shard2, 0, n, shape, want)
+                S.gather_compact(shard, ids, shape, got)
+                for k, off, shp, dt, nbytes in table:
+                    assert got[off:off + nbytes].tobytes() == want[off:off + nbytes].tobytes(), (n, name, what, k)
+                f = {k: got[off:off + nbytes].view(dt).reshape(shp) for k, off, shp, dt, nbytes in table}
+                na = int(f["n_valid_atoms"][0])
+                assert na == sum(m["x"].shape[0] for m in picked)
+                pad = {"exact": 0, "3 padding atoms": 3, "63 padding atoms": 63}.get(what)
+                assert pad is None or shape["atoms"] - na == pad
+                if what == "exact":                         # no padding atom: every padding molecule is empty
+                    assert na == shape["atoms"] and (f["mol_ptr"][n:] == na).all() and f["mol_ptr"].shape[0] == n + P.PAD_MOLECULES + 1
 
 
 def test_errors(whole, shard, tmp_path):
