@@ -441,6 +441,48 @@ int mkgnn_tail_flush(void* stream);
 size_t mkgnn_tail_score_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols);
 int mkgnn_tail_score(const mkgnn_tail_args* args, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (additive; the ABI version stays 8) Every atom's exact share of every logit of the head, in evaluation mode -- why a molecule
+ * scores what it scores.  Behind the last kernel convolution lin2, the add-pool and the head are linear, so with
+ *     pre_n = b1 + sum_{j -> n} W1[:, block(j)] sim[j, block(j)]        (project, then propagate: the block-row readout)
+ *     V = head_weight . lin2_weight  ([T, H]),      c0[t] = head_weight[t, :] . lin2_bias
+ * every logit is  pred[g, t] = head_bias[t] + sum_{n in g} c[n, t]  with
+ *     contrib[n * contrib_stride + t] = c[n, t] = sum_h V[t, h] swish(pre_n[h]) + c0[t]        for every n < n_atoms, t < T
+ * -- exact, additive and complete for any number of tasks; no gradient is involved.  head_bias is not part of it.
+ *   sim, sim_stride, num_kernels, buckets, in_rowptr, in_col, readout: as mkgnn_tail_args (buckets: count and selected_index are
+ *   read; in_*: the edges by target, columns = sources); head_weight [T, G] with rows head_stride >= G floats apart;
+ *   lin1_bias / lin2_bias NULL count as zeros.  Needs neither mol_ptr nor atom_mol: molecules of any size, atoms in no degree
+ *   bucket (an isolated atom, a hub of degree >= 5: their z row is zero) and atoms without in-edges (V swish(b1) + c0) included.
+ * TWO launches on `stream`, capturable: z = W1 sim into the workspace (the tail's projection, on the matrix cores), then one
+ * kernel over atoms.  No atomics, no process-wide or thread-local state, one writer per output; nothing of contrib is written
+ * outside [n, 0..T).  A reduction that a mkgnn_tail_fused call with defer_reduce left pending on this thread is launched first
+ * (the workspace may be the one it reads).
+ * Evaluation order, one per output (kgnn_atom_contrib.hip): V[t][h] and c0[t] by fmaf over g = 0 .. G - 1 from +0.0, formed by
+ * every workgroup from the parameters alone; s = +0.0 plus the z rows of n's in-edges, edge by edge in CSR order; pre = s + b1;
+ * a = pre * sigmoid(pre) with the tail's sigmoid (v_exp_f32, v_rcp_f32: relative error <= 2^-22 + |pre| 2^-23); lane l of 8 forms
+ * V[t][4 l] * a[4 l], then fmaf over 4 l + 1 .. 4 l + 3 (+0.0 at h >= H); the 8 values go through an xor tree (offsets 4, 2, 1);
+ * + c0[t].  The BITS of contrib[n, t] therefore depend on the parameters, row t of head_weight and the z rows of n's
+ * in-neighbours in CSR order only: not on n_atoms, the atom's place in block or grid, other atoms, T, t's index, contrib_stride
+ * or head_stride.
+ * Error criterion (the project's own, of the fused tail): against the float64 formula on the same sim,
+ * max |got - want| <= 2e-5 max(max |want|, 1e-6) over the [n_atoms, T] result.
+ * Limits: mkgnn_tail_supported(K, H, G, num_kernels) and 1 <= T <= MKGNN_ATOM_CONTRIB_MAX_TASKS; n_atoms < 2^31.  Anything else, a
+ * null pointer, contrib_stride < T, head_stride < G, misaligned sim rows or a workspace below
+ * mkgnn_atom_contributions_workspace_bytes (the z rows: a mkgnn_tail_workspace_bytes buffer of the batch is large enough) returns
+ * non-zero with mkgnn_last_error set before any launch.  n_atoms == 0 is a no-op that returns 0. */
+#define MKGNN_ATOM_CONTRIB_MAX_TASKS 32
+typedef struct mkgnn_atom_contrib_args {
+    const float* sim; int64_t sim_stride;
+    int32_t num_kernels[MKGNN_MAX_DEGREE];
+    const mkgnn_degree_bucket* buckets;      /* [MKGNN_MAX_DEGREE] */
+    const int32_t* in_rowptr; const int32_t* in_col;
+    int64_t n_atoms;
+    mkgnn_readout_params readout;
+    const float* head_weight; int64_t head_stride; int32_t T;   /* [T, G] */
+    float* contrib; int64_t contrib_stride;                      /* [n_atoms, T] */
+} mkgnn_atom_contrib_args;
+size_t mkgnn_atom_contributions_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms);
+int mkgnn_atom_contributions(const mkgnn_atom_contrib_args* args, void* workspace, size_t workspace_bytes, void* stream);
+
 /* BatchNorm1d over atom rows, reference MolKGNNNet.py:115 (torch.nn.BatchNorm1d semantics: biased
  * variance for the normalisation, unbiased for running_var, running <- running + momentum (batch - running)).
  * training != 0: batch statistics, running_* (may be NULL) updated in place, save_* written.

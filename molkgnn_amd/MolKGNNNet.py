@@ -77,7 +77,7 @@ class MolKGNNNet(torch.nn.Module):
         src = data.edge_index[0]
         return (ea, bn, src if src.is_contiguous() else src.contiguous(), nv)
 
-    def forward(self, *argv, save_score=False, _tail=None, _score=None):
+    def forward(self, *argv, save_score=False, _tail=None, _score=None, _atoms=None):
         if len(argv) != 1:
             # the reference's 33-positional-argument form reads ``data`` afterwards and cannot work
             # (MolKGNNNet.py:70-89 then :115); only the single-``data`` form is meaningful
@@ -85,7 +85,8 @@ class MolKGNNNet(torch.nn.Module):
         data = argv[0]
         # small batches (the reference's own regime, README.md:81): batch norm, every layer and the readout in ONE launch, a
         # workgroup per chunk of whole molecules (molkgnn_amd.molecule); None where the model or the batch does not qualify
-        if data.x.is_cuda and not save_score:
+        # (_atoms: the per-atom contributions are asked for -- the molecule-resident step sums them away inside LDS)
+        if data.x.is_cuda and not save_score and _atoms is None:
             from . import molecule as _mol
             emb = _mol.net_forward(self, data)
             if emb is not None:                          # (edge_batch_norm's statistics moved inside: molecule.net_forward)
@@ -150,17 +151,29 @@ class MolKGNNNet(torch.nn.Module):
                           and x.is_cuda and R.tail_supported(*dims, Ls))
             want = x.is_cuda and not save_score and (_PROJECT_FIRST == '1' or (_PROJECT_FIRST != '0' and (
                 x.shape[0] >= _PROJECT_FIRST_ATOMS or not R.readout_supported(*dims) or want_tail or want_score)))
+            # (private: train.GNNModel.atom_contributions asks for every atom's share of every output of the head `_atoms` --
+            # readout.atom_contributions, from the block rows, where that applies, else from h through PyTorch operators; it
+            # needs no molecule segments, so none are derived, and it alone decides which of the two the last layer leaves)
+            want_atoms = (_atoms is not None and R._ATOM_CONTRIB and _PROJECT_FIRST != '0' and not torch.is_grad_enabled() and x.is_cuda
+                          and not save_score and R.atom_contributions_supported(*dims, Ls, _atoms.out_features))
+            if _atoms is not None:
+                want = False
             if want:
                 want = R.readout_blocks_supported(*dims, Ls)
             if want and seg is None:
                 seg = R.molecule_segments(data.batch, getattr(data, 'num_graphs', None))
-            want = want and seg.sorted and seg.size > 0
+            want = want_atoms or (want and seg.sorted and seg.size > 0)
             node_representation = self.gnn(x=x, edge_index=data.edge_index, edge_attr=data.edge_attr, p=data.p,
                                            save_score=save_score, **kw, **({'_defer_last_propagate': blocks_out} if want else {}))
         except BaseException:
             # the deferred bank preparation (MolGCN.prepare_banks_early) must not outlive this call: its workspaces would
             self.gnn.drop_pending_prepare(data.x.device)
             raise
+        if _atoms is not None:
+            if node_representation is None:
+                sim_sc, plan, Ls = blocks_out[0]
+                return R.atom_contributions(sim_sc, plan, Ls, lin1, lin2, _atoms)
+            return R.atom_contributions_torch(node_representation, lin1, lin2, _atoms)
         if node_representation is None:                     # the last propagate was left to the readout
             sim_sc, plan, Ls = blocks_out[0]
             # (private: train.GNNModel.loss asks for the loss itself -- readout, head, loss and all their gradients in one

@@ -66,6 +66,15 @@ class TailArgs(C.Structure):
 
 
 TAIL_MAX_ATOMS, TAIL_MAX_EDGES = 128, 512      # MKGNN_TAIL_MAX_ATOMS / _EDGES
+ATOM_CONTRIB_MAX_TASKS = 32                    # MKGNN_ATOM_CONTRIB_MAX_TASKS
+
+
+class AtomContribArgs(C.Structure):
+    """``mkgnn_atom_contrib_args`` (include/molkgnn_hip.h): every atom's share of every logit (``mkgnn_atom_contributions``)."""
+    _fields_ = [("sim", C.c_void_p), ("sim_stride", C.c_int64), ("num_kernels", C.c_int32 * 4), ("buckets", C.c_void_p),
+                ("in_rowptr", C.c_void_p), ("in_col", C.c_void_p), ("n_atoms", C.c_int64), ("readout", ReadoutParams),
+                ("head_weight", C.c_void_p), ("head_stride", C.c_int64), ("T", C.c_int32), ("contrib", C.c_void_p),
+                ("contrib_stride", C.c_int64)]
 
 
 class CopyItem(C.Structure):
@@ -172,7 +181,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused", "mkgnn_gather_compact",
            "mkgnn_gather_compact_workspace_bytes", "mkgnn_gather_compact_packed", "mkgnn_topk_update", "mkgnn_topk_workspace_bytes",
            "mkgnn_task_head_workspace_bytes", "mkgnn_task_head_forward", "mkgnn_task_head_backward", "mkgnn_task_head_fused",
-           "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks", "mkgnn_embed_cosine")
+           "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks", "mkgnn_embed_cosine",
+           "mkgnn_atom_contributions", "mkgnn_atom_contributions_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -240,6 +250,11 @@ def load() -> C.CDLL:
     lib.mkgnn_tail_score_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
     lib.mkgnn_tail_score.restype = C.c_int
     lib.mkgnn_tail_score.argtypes = [C.POINTER(TailArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+    # every atom's share of every logit: (args, workspace, workspace bytes, stream)
+    lib.mkgnn_atom_contributions_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_atom_contributions_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64]
+    lib.mkgnn_atom_contributions.restype = C.c_int
+    lib.mkgnn_atom_contributions.argtypes = [C.POINTER(AtomContribArgs), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mkgnn_tail_fused_readout_dropout.restype = C.c_int
     lib.mkgnn_tail_fused_readout_dropout.argtypes = [C.POINTER(TailArgs), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mkgnn_readout_dropout_mask.restype = C.c_int

@@ -212,6 +212,18 @@ hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipSt
 // the forward-only form (mkgnn_tail_score): reads z, rin, cin, mol_ptr, the weights, H, G, n_mols, n_loss, mg; writes pred and emb
 hipError_t launch_tail_score(const TailMidArgs& a, int nb, hipStream_t st);
 
+// kgnn_atom_contrib.hip: every atom's share of every logit (mkgnn_atom_contributions, kgnn_readout.hip) -- one launch over atoms
+struct AtomContribArgs {
+    const float* z;                         // [n, 32]: W1 sim, as block_project_mfma_kernel leaves it
+    const int32_t *rin, *cin; int64_t n;    // the edges by target (columns = sources)
+    const float *b1, *w2, *b2;              // [H] or null, [G, H], [G] or null
+    const float* wh; int64_t wh_stride;     // [T, G] head rows
+    int H, G, T;
+    float* out; int64_t os;                 // [n, T] rows, os floats apart
+};
+constexpr int ATOM_CONTRIB_MAX_BLOCKS = 1024;       // (four workgroups per CU; beyond 32 768 atoms a workgroup takes several passes)
+hipError_t launch_atom_contrib(const AtomContribArgs& a, hipStream_t st);
+
 struct BankStreamLaunch { BankStreamArgs a; int nb, prep_blocks, KC; size_t lds_bytes; int x_split; };
 // block split and arguments once; then the pre-pass (coefficient records in tile order, score-weight partials) and the
 // bank kernel, each on the stream the caller chooses

@@ -1100,6 +1100,19 @@ size_t mkgnn_tail_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_ato
     return tail_ws(d, n_atoms, n_mols).total;
 }
 
+// What every entry point that starts from the z rows ends its front half with (d: blocks_dims' of a shape mkgnn_tail_supported
+// takes): the block checks, the workspace (`total`: what the caller needs of it), a pending deferred reduction, the projection.
+static int project_into_workspace(const char* who, const mkgnn_readout_params* ro, const int32_t num_kernels[MKGNN_MAX_DEGREE],
+                                  const mkgnn_degree_bucket* buckets, const float* sim, int64_t sim_stride, int64_t n_atoms,
+                                  size_t total, void* ws, size_t ws_bytes, hipStream_t st, BlockProjArgs& b, const ReadoutDims& d) {
+    int64_t n_focal = 0;
+    if (int rc = check_blocks(who, ro, num_kernels, buckets, n_atoms, sim_stride, sim, b, d, &n_focal)) return rc;
+    if (!ws || ws_bytes < total) return api_fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, total);
+    hipError_t e = launch_pending_tail_reduce(st);
+    if (e == hipSuccess) e = project_blocks(b, d, n_focal, sim, sim_stride, n_atoms, (float*)ws, st);
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
 // The front half of both tail entry points: the checks they share, with the caller's own (`own`) in their place behind the
 // sizes; a reduction an earlier call left pending and nobody took, in front of this call's first launch (its kernels overwrite
 // the workspace slabs the pending one still reads, and read the dropout generator state it advances); then
@@ -1115,13 +1128,8 @@ static int tail_project(const char* who, const mkgnn_tail_args* p, Own&& own, si
         return api_fail("%s: bad sizes", who);
     if (int rc = own()) return rc;
     if (p->emb && p->emb_stride < ro->G) return api_fail("%s: bad emb stride", who);
-    int64_t n_focal = 0;
-    if (int rc = check_blocks(who, ro, p->num_kernels, p->buckets, p->n_atoms, p->sim_stride, p->sim, b, d, &n_focal)) return rc;
-    const size_t total = need(ro->F, ro->H, ro->G, p->n_atoms, p->n_mols);
-    if (!ws || ws_bytes < total) return api_fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, total);
-    hipError_t e = launch_pending_tail_reduce(st);
-    if (e == hipSuccess) e = project_blocks(b, d, n_focal, p->sim, p->sim_stride, p->n_atoms, (float*)ws, st);
-    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+    return project_into_workspace(who, ro, p->num_kernels, p->buckets, p->sim, p->sim_stride, p->n_atoms,
+                                  need(ro->F, ro->H, ro->G, p->n_atoms, p->n_mols), ws, ws_bytes, st, b, d);
 }
 
 // rp: the readout's dropout (mkgnn_tail_fused_readout_dropout), 0 for mkgnn_tail_fused
@@ -1263,6 +1271,42 @@ int mkgnn_tail_score(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
     m.emb = p->emb; m.es = p->emb_stride; m.pred = p->pred;
     m.mg = tail_group_size(p->n_loss_mols);
     const hipError_t e = launch_tail_score(m, tail_middle_blocks(p->n_loss_mols), st);      // (hipGetLastError: both launches)
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+// ---- every atom's share of every logit (evaluation mode): project | one kernel over atoms (kgnn_atom_contrib.hip) ----
+size_t mkgnn_atom_contributions_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms) {
+    ReadoutDims d;
+    if (!blocks_dims(K, H, G, d) || n_atoms < 1) return 0;
+    return tail_ws(d, n_atoms, 1).dz;                    // (the z rows, as mkgnn_tail_score_workspace_bytes)
+}
+
+int mkgnn_atom_contributions(const mkgnn_atom_contrib_args* p, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "mkgnn_atom_contributions";
+    if (!p) return api_fail("%s: null argument", who);
+    const mkgnn_readout_params* ro = &p->readout;
+    ReadoutDims d;
+    if (!mkgnn_tail_supported(ro->F, ro->H, ro->G, p->num_kernels) || !blocks_dims(ro->F, ro->H, ro->G, d))
+        return api_fail("%s: K=%d H=%d G=%d outside the fused tail's shapes (the block-row readout's with H, G <= 32)", who, ro->F, ro->H, ro->G);
+    if (p->T < 1 || p->T > MKGNN_ATOM_CONTRIB_MAX_TASKS)
+        return api_fail("%s: %d tasks outside [1, %d]", who, (int)p->T, MKGNN_ATOM_CONTRIB_MAX_TASKS);
+    if (p->n_atoms < 0 || p->n_atoms >= (int64_t)1 << 31) return api_fail("%s: bad sizes", who);
+    if (p->contrib_stride < p->T) return api_fail("%s: contrib stride %lld below T = %d", who, (long long)p->contrib_stride, (int)p->T);
+    if (p->head_stride < ro->G) return api_fail("%s: head stride %lld below G = %d", who, (long long)p->head_stride, ro->G);
+    if (p->n_atoms == 0) return 0;
+    if (!p->in_rowptr || !p->in_col || !ro->lin1_weight || !ro->lin2_weight || !p->head_weight || !p->contrib)
+        return api_fail("%s: null pointer", who);
+    hipStream_t st = (hipStream_t)stream;
+    BlockProjArgs b{};
+    if (int rc = project_into_workspace(who, ro, p->num_kernels, p->buckets, p->sim, p->sim_stride, p->n_atoms,
+                                        mkgnn_atom_contributions_workspace_bytes(ro->F, ro->H, ro->G, p->n_atoms), ws, ws_bytes, st, b, d))
+        return rc;
+    AtomContribArgs a{};
+    a.z = (const float*)ws; a.rin = p->in_rowptr; a.cin = p->in_col; a.n = p->n_atoms;
+    a.b1 = ro->lin1_bias; a.w2 = ro->lin2_weight; a.b2 = ro->lin2_bias; a.wh = p->head_weight; a.wh_stride = p->head_stride;
+    a.H = ro->H; a.G = ro->G; a.T = p->T;
+    a.out = p->contrib; a.os = p->contrib_stride;
+    const hipError_t e = launch_atom_contrib(a, st);
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }
 

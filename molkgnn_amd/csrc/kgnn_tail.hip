@@ -36,6 +36,7 @@
 #include "kgnn_common.h"
 #include "kgnn_launch.h"
 #include "kgnn_philox.h"
+#include "kgnn_sigmoid.h"
 #include "../../include/molkgnn_hip.h"
 
 namespace mkgnn {
@@ -48,14 +49,7 @@ constexpr int HP = 36;                  // LDS pitch of the 32-wide rows: 16-byt
 constexpr int WP = 33;                  // ... of W2's rows (read one float per lane: odd, conflict-free)
 typedef mkgnn_f32x4 f32x4;
 
-// sigmoid on the transcendental unit: v_exp_f32 and v_rcp_f32 (1 ulp each) instead of the library's expf and an IEEE division --
-// ~6 instructions for ~60.  This kernel evaluates two of them per (atom, hidden unit) and, measured by compiling the phases out,
-// was BOUND by them (31 of its 64 us).  Relative error <= 2^-22 + |v| 2^-23: 2e-6 at |v| = 16, against the 1e-5 the readout is
-// held to (tests/test_tail.py: against float64 autograd of the reference's formula).
-__device__ __forceinline__ float sigmoidf_(float v) {
-    const float e = __builtin_amdgcn_exp2f(-1.44269504088896340736f * v);      // e^-v  (inf for v << 0: the reciprocal is then 0)
-    return __builtin_amdgcn_rcpf(1.f + e);
-}
+// (sigmoidf_, the sigmoid on the transcendental unit: kgnn_sigmoid.h -- shared with kgnn_atom_contrib.hip)
 __device__ __forceinline__ float half_sum(float v) {       // xor tree over the 32 lanes of a row slot
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -1161,6 +1161,97 @@ def tail_score(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: tor
     return pred, emb
 
 
+# ------------------------------------------------------------- every atom's share of every logit (evaluation mode) --
+# MKGNN_ATOM_CONTRIB=0: GNNModel.atom_contributions runs the PyTorch operators on a dense h (atom_contributions_torch; A/B)
+_ATOM_CONTRIB = os.environ.get("MKGNN_ATOM_CONTRIB", "1") != "0"
+
+
+def atom_contributions_reference(h, w1, b1, w2, b2, wh):
+    """The definition, in float64 on the CPU and in the reference's own order: ``((swish(h W1^T + b1)) W2^T + b2) Wh^T`` --
+    ``contrib [N, T]`` (a float64 numpy array), the share of every atom in every logit: a molecule's rows sum to its ``pred``
+    minus the head's bias.  ``h [N, K]`` is the last layer's propagated output; tensors or arrays, either bias may be ``None``."""
+    import numpy as np
+
+    def f64(a):
+        return None if a is None else (a.detach().cpu().double().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64))
+
+    h, w1, b1, w2, b2, wh = (f64(a) for a in (h, w1, b1, w2, b2, wh))
+    wh = wh.reshape(-1, w2.shape[0])
+    if h.ndim != 2 or w1.ndim != 2 or w2.ndim != 2 or h.shape[1] != w1.shape[1] or w2.shape[1] != w1.shape[0]:
+        raise ValueError("atom_contributions_reference needs h [N, K], W1 [H, K], W2 [G, H] and Wh [T, G]")
+    pre = h @ w1.T
+    if b1 is not None:
+        pre = pre + b1
+    with np.errstate(over="ignore"):
+        act = pre / (1.0 + np.exp(-pre))
+    emb = act @ w2.T
+    if b2 is not None:
+        emb = emb + b2
+    return emb @ wh.T
+
+
+def atom_contributions_supported(K: int, H: int, G: int, blocks, T: int) -> bool:
+    """The shapes ``mkgnn_atom_contributions`` takes: the fused tail's, and ``1 <= T <= 32`` tasks."""
+    return 1 <= int(T) <= _lib.ATOM_CONTRIB_MAX_TASKS and tail_supported(K, H, G, blocks)
+
+
+def atom_contributions(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torch.nn.Linear, ffn: torch.nn.Linear,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``contrib [n_atoms, T]``: the exact share of every atom in every output of ``ffn(readout_blocks(sim, ...))`` in evaluation
+    mode -- ``pred[g, t] = ffn.bias[t] + sum of contrib[n, t] over the atoms of g`` -- from the last convolution's block rows as
+    two launches (``mkgnn_atom_contributions``; ``atom_contributions_reference`` is the definition).  Needs no molecule segments
+    and knows no limit on a molecule's size.  ``out``: a float32 tensor ``[n_atoms, >= T]`` on the device whose leading ``T``
+    columns are written (its row stride is passed on; the other columns are not touched) and returned as a view.  It has no
+    autograd node: called where a gradient is being recorded for one of its inputs it raises instead of dropping it.  The caller
+    has checked ``atom_contributions_supported``."""
+    params = (lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (sim, *params)):
+        raise RuntimeError("atom_contributions is forward only: call it under torch.no_grad() (or on detached inputs)")
+    lib = _lib.load()
+    _lib.require_gpu_tensor(sim, "sim_sc")
+    n, K = sim.shape
+    dev = sim.device
+    w1, b1, w2, b2, wh = (None if t is None else t.detach() for t in params)
+    w1c, w2c = w1.contiguous(), w2.contiguous()
+    whc = wh if wh.stride(1) == 1 else wh.contiguous()
+    H, G, T = w1c.shape[0], w2c.shape[0], whc.shape[0]
+    if whc.dim() != 2 or whc.shape[1] != G or not 1 <= T <= _lib.ATOM_CONTRIB_MAX_TASKS:
+        raise ValueError(f"atom_contributions needs a head of 1 to {_lib.ATOM_CONTRIB_MAX_TASKS} outputs on the G = {G} embedding columns")
+    if out is None:
+        out = torch.empty((n, T), dtype=torch.float32, device=dev)
+    elif (out.dtype != torch.float32 or out.device != dev or out.dim() != 2 or out.shape[0] != n or out.shape[1] < T
+          or (n > 0 and out.stride(1) != 1)):
+        raise ValueError(f"out: a float32 tensor [{n}, >= {T}] of rows on {dev}")
+    if n == 0:
+        return out[:, :T]
+    a = _lib.AtomContribArgs()
+    a.sim, a.sim_stride = sim.data_ptr(), _stride0(sim)
+    for i, L in enumerate(blocks):
+        a.num_kernels[i] = int(L)
+    bk = _sel_buckets(plan)
+    a.buckets = ctypes.cast(bk, ctypes.c_void_p)
+    rin, cin = plan.csr_in
+    a.in_rowptr, a.in_col, a.n_atoms = rin.data_ptr(), cin.data_ptr(), n
+    a.readout = _params(w1c, b1, w2c, b2)
+    a.head_weight, a.head_stride, a.T = whc.data_ptr(), (whc.stride(0) if T > 1 else G), T
+    a.contrib, a.contrib_stride = out.data_ptr(), (out.stride(0) if n > 1 else out.shape[1])
+    with torch.cuda.device(dev):
+        # (the tail's scratch: its first bytes are the z rows there too, and a reduction still pending on its slabs is launched
+        # by the call before anything is overwritten)
+        ws = _tail_workspace(dev, int(lib.mkgnn_atom_contributions_workspace_bytes(K, H, G, n)))
+        _lib.check(lib.mkgnn_atom_contributions(ctypes.byref(a), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
+                   "mkgnn_atom_contributions")
+    del bk
+    return out[:, :T]
+
+
+def atom_contributions_torch(h: torch.Tensor, lin1: torch.nn.Linear, lin2: torch.nn.Linear, ffn: torch.nn.Linear) -> torch.Tensor:
+    """``contrib [N, T]`` from a dense ``h`` (the last layer's propagated output) with float32 PyTorch operators, in the
+    reference's order: ``ffn.weight`` applied to ``lin2(swish(lin1(h)))``, without the head's bias.  The route for shapes outside
+    ``atom_contributions_supported`` and for ``MKGNN_ATOM_CONTRIB=0``; the readout's dropout is not applied (evaluation mode)."""
+    return torch.nn.functional.linear(lin2(swish(lin1(h))), ffn.weight)
+
+
 def readout_dropout_mask(rng_pair: torch.Tensor, n_rows: int, H: int, p: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The keep multipliers ``[n_rows, H]`` (0, or 1 / (1 - p)) of the readout's dropout that the fused tail and the
     molecule-resident step draw for the generator pair ``rng_pair`` (``{seed, offset}``, int64 on the device -- the ``rng_used``

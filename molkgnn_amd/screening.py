@@ -22,6 +22,11 @@ Analogue search -- the library molecules whose graph embeddings lie closest, by 
 ``nearest_resident``                     ``sim[n_molecules, Q]`` of one resident shard, optionally feeding the ``Q`` lists
 ``nearest``                              shards -> the ``k`` nearest molecules per query
 ``rank_embeddings``                      the same ranking from a stored embedding matrix
+
+Why a hit scores what it scores -- every atom's exact share of every output (``GNNModel.atom_contributions``,
+``mkgnn_atom_contributions``):
+
+``explain_resident``                     ``contrib[atoms of the listed molecules, T]`` for a list of ids of one resident shard
 """
 from __future__ import annotations
 
@@ -392,6 +397,80 @@ def score_resident_tasks(model, resident, batch_size: int, *, topk: Optional[Top
     T = int(model.ffn.out_features)
     return _run_shard("score_resident_tasks", "scoring", model, resident, dev, batch_size, lambda data: model.predict_tasks(data)[0], (T,),
                       topk, TopKTasks, T, shard_tag=shard_tag, out=out)
+
+
+def explain_resident(model, resident, ids, batch_size: int = 256) -> dict:
+    """Why the molecules ``ids`` of one ``ResidentShard`` score what they score (the ``top_mol`` of a screen where ``top_shard`` is
+    this shard, say; repeats allowed, order kept): ``GNNModel.atom_contributions`` of every one of them, as a dict --
+
+    ``atom_ptr``  int64 numpy ``[len(ids) + 1]``, from the host's ``resident.mol_atoms``: molecule ``ids[i]`` owns the rows
+                  ``atom_ptr[i] .. atom_ptr[i + 1]``
+    ``contrib``   float32 ``[atom_ptr[-1], T]`` on the device: row ``atom_ptr[i] + a`` is atom ``a`` of molecule ``ids[i]`` in the
+                  shard's atom order, column ``t`` its exact share of output ``t``
+    ``bias``      ``[T]``: the head's bias (zeros for a head without one) -- a molecule's rows plus it sum to its ``predict_tasks``
+
+    Every molecule is explained IN THE BATCH THE SHARD PASS SCORES IT IN: the batches of ``score_resident`` / ``score_resident_tasks``
+    at this ``batch_size`` (ids ``k * batch_size ..``, the short tail filled up with its last id, the whole shard's shape) that hold
+    a listed molecule are gathered, expanded and given their receptive fields as there, ``atom_contributions`` runs on each, and
+    the listed molecules' rows are copied out.  So with the screen's ``batch_size`` a molecule's rows plus ``bias`` sum to the score
+    the screen reported, to float32 rounding.  That needs the same layout: the network's logit of a molecule is defined up to
+    the choice among mathematically tied neighbour permutations ("Ties"), which last-bit differences between batch
+    layouts decide -- in another batch a few molecules' logits differ in the third digit, and the contributions
+    with them.  At most ``len(set(ids))`` batches run, launched eagerly -- a hit list is a few thousand molecules at most.  A batch's
+    live slots come first, so their real atoms are one run at its head; one indexed copy per batch moves the listed molecules'
+    rows.  The gather's status word is read once, at the end: non-zero raises.  The model is put in evaluation mode and handed back
+    in the mode it came in.  Empty ``ids``, ids outside the shard, a model or a shard that is not on the GPU: ``ValueError`` before
+    a launch."""
+    from .receptive_field import attach_receptive_fields
+    from .shards import ResidentLoader
+    from .train import evaluation_mode
+    ids = np.asarray(ids.tolist() if torch.is_tensor(ids) else list(ids), dtype=np.int64).reshape(-1)
+    n, bs = int(resident.n_molecules), int(batch_size)
+    if ids.size == 0:
+        raise ValueError("explain_resident needs at least one molecule id")
+    if int(ids.min()) < 0 or int(ids.max()) >= n:
+        raise ValueError(f"molecule ids outside [0, {n})")
+    if bs < 1:
+        raise ValueError("batch_size >= 1")
+    dev = _check_device(model, resident)
+    T = int(model.ffn.out_features)
+    atom_ptr = np.zeros(ids.size + 1, dtype=np.int64)
+    np.cumsum(resident.mol_atoms[ids], out=atom_ptr[1:])
+    contrib = torch.empty((int(atom_ptr[-1]), T), dtype=torch.float32, device=dev)
+    bias = model.ffn.bias.detach().float().clone() if model.ffn.bias is not None else torch.zeros(T, dtype=torch.float32, device=dev)
+    # the shard pass's plan (host only: nothing is uploaded), and those of its batches that hold a listed molecule -- in order, so
+    # the short tail, if listed, is the last piece and is filled up as the pass fills it
+    whole = ResidentLoader(resident, bs, np.arange(n, dtype=np.int64), "cpu", drop_last=False)
+    pieces = np.unique(ids // bs)
+    loader = ResidentLoader(resident, bs, np.concatenate([np.arange(k * bs, min((k + 1) * bs, n), dtype=np.int64) for k in pieces]),
+                            dev, shape=whole.shape, drop_last=False)
+    # per batch: the rows of its head run to copy (src) and where they go (dst), for every listed molecule it holds
+    src, dst, cut = [], [], [0]
+    listed = np.argsort(ids // bs, kind="stable")
+    piece_of = (ids // bs)[listed]
+    for k in pieces:
+        start = np.zeros(bs + 1, dtype=np.int64)
+        members = np.arange(k * bs, min((k + 1) * bs, n))
+        np.cumsum(resident.mol_atoms[members], out=start[1:members.size + 1])
+        mine = listed[np.searchsorted(piece_of, k, "left"):np.searchsorted(piece_of, k, "right")]
+        for i in mine:
+            a = int(resident.mol_atoms[ids[i]])
+            src.append(start[ids[i] - k * bs] + np.arange(a, dtype=np.int64))
+            dst.append(atom_ptr[i] + np.arange(a, dtype=np.int64))
+        cut.append(cut[-1] + int(resident.mol_atoms[ids[mine]].sum()))
+    rows = torch.from_numpy(np.stack([np.concatenate(src), np.concatenate(dst)])).to(dev, non_blocking=True)
+    with evaluation_mode(model):
+        csb = static_batch_for(loader, resident)
+        for b, f_ids in enumerate(loader):
+            csb.gather(resident, f_ids)
+            csb.expand()
+            attach_receptive_fields(csb.data, sizes=csb.data.bucket_sizes, overlap=True)
+            lo, hi = cut[b], cut[b + 1]
+            contrib.index_copy_(0, rows[1, lo:hi], model.atom_contributions(csb.data).index_select(0, rows[0, lo:hi]))
+        status = csb.gather_status()                     # (the one host read)
+        if status:
+            raise RuntimeError(f"mkgnn_gather_compact reported status {status} while explaining the shard's molecules")
+    return {"atom_ptr": atom_ptr, "contrib": contrib, "bias": bias}
 
 
 def _over_shards(who: str, residents, check, make_lists, per_shard, keep: bool):

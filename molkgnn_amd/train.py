@@ -9,6 +9,7 @@ Scoring: ``GNNModel.predict``, ``evaluate`` (the reference's validation / test l
 ``evaluate_resident`` (the same from a device-resident shard; ranking a library: ``molkgnn_amd.screening``).
 Multi-task models: ``GNNModel.predict_tasks`` (all outputs of every molecule), ``evaluate_tasks``, ``evaluate_resident_tasks``.
 The graph embedding alone: ``GNNModel.embed`` (analogue search: ``screening.nearest``).
+Every atom's exact share of every output: ``GNNModel.atom_contributions`` (a hit list explained: ``screening.explain_resident``).
 All of them, and ``screening``'s shard passes, run the model inside ``evaluation_mode``.
 Logging, checkpoints, file output and the LR schedule are out of scope.
 """
@@ -120,6 +121,21 @@ class GNNModel(torch.nn.Module):
             else:
                 pred = self.ffn(graph_embedding[:n])
             return pred, graph_embedding[:n]
+
+    def atom_contributions(self, data):
+        """``contrib [N, T]``: the exact share of every atom in every output, for a model in evaluation mode, under
+        ``torch.no_grad()`` -- why a molecule scores what it scores.  ``lin2``, the add-pool and ``ffn`` are linear, so
+        ``predict_tasks(data)[0][g, t] = ffn.bias[t] + sum of contrib[n, t] over the atoms n of molecule g``, exactly (up to float32
+        rounding), for any ``task_dim``; for the docking-score model it explains the predicted score.  On the GPU, where
+        ``readout.atom_contributions_supported`` holds, the last convolution leaves its block rows and ``mkgnn_atom_contributions``
+        takes them (two launches; molecules of any size; the molecule-resident step is not taken); otherwise, and with
+        ``MKGNN_ATOM_CONTRIB=0``, the same quantity comes from ``h`` through PyTorch operators (``readout.atom_contributions_torch``).
+        ``N`` counts ALL atom rows of the batch: for a batch padded to a fixed shape the rows from ``n_valid_atoms`` on belong to
+        padding atoms -- cut them, and find a molecule's rows, with ``data.mol_ptr``.  Nothing is read back to the host.  In
+        training mode this raises, before the batch is looked at."""
+        self._needs_eval("atom_contributions")
+        with torch.no_grad():
+            return self.gnn_model(data, _atoms=self.ffn)
 
     def _loss_kind(self) -> Optional[str]:
         """The loss as a kind of the HIP head (``readout.LOSS_KINDS``), or None: any other loss takes the PyTorch route."""
