@@ -1012,6 +1012,53 @@ int mkgnn_topk_update_tasks(const float* scores, int64_t score_row_stride, int64
                             float* top_score, int32_t* top_shard, int32_t* top_mol, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* ---- the nearest reference of every library molecule (additive; the ABI version stays 8): how close each embedding row lies to a
+ * set of known molecules -- the known actives, the training set, a patent set -- for a novelty filter or an applicability domain
+ * in front of the running list.  With sim(i, r) the float32 value mkgnn_embed_cosine writes for row i and query refs[r], BIT FOR
+ * BIT (its evaluation order above: the two-values-per-lane products, the xor tree with offsets 16, 8, 4, 2, 1, the + 0.0,
+ * (dot * inv(e)) * inv(q); the tree is a fixed binary tree of commutative adds, which one thread evaluates serially in the same
+ * association), the winner of row i is the first r in the order mkgnn_topk_update ranks by:
+ *   1. non-NaN similarities before NaN ones
+ *   2. larger similarities first; -0.0 and +0.0 compare equal
+ *   3. then the lower r
+ * max_sim[i] carries the winner's bits (when the winner is a NaN: some NaN) and arg_ref[i] = r.  A row of NaN, or a set of NaN
+ * references, gives (NaN, 0).  emb [n_rows, H] with emb_stride >= H, refs [R, H] with ref_stride >= H, both RAW: the inverse norms
+ * of the references and of the rows are computed inside the call, into the workspace, so one captured call follows new contents
+ * of emb and of refs.  max_sim [n_rows] and arg_ref [n_rows] are contiguous; nothing else is written outside the workspace.
+ *
+ * Two launches on `stream`, three when the references are split over the grid (the per-part winners go through the workspace and
+ * a finishing launch combines them in reference order); capturable, no host round trip, no float atomics, no process-wide
+ * state, one writer per output.  The workspace (4-byte aligned, mkgnn_embed_max_cosine_workspace_bytes(n_rows, R) bytes; 0 for
+ * rejected sizes) needs no initialisation: it is read only where the same call wrote it.  The bits of (max_sim[i], arg_ref[i])
+ * depend on row i and on the reference set alone: not on n_rows, the row's place in the grid, the strides, or how the launch
+ * splits the references (the winner is the first element of a total order).  Plain FP32: the bit contract forbids the matrix
+ * instructions' summation order.  Against the exact cosine every sim(i, r) carries mkgnn_embed_cosine's error bound.
+ *
+ * Limits: 1 <= H <= 64; 1 <= R <= MKGNN_MAX_COSINE_MAX_REFS; 0 <= n_rows < 2^31.  MKGNN_MAX_COSINE_MAX_REFS is 2^20: a training set
+ * of a large assay fits in one call, while one thread's walk stays at R / 256 <= 4 096 references when the batch is small (the
+ * references are split into at most 256 parts, and no more than bring the grid to 2 048 blocks), R + n_rows and every index
+ * derived from r stay far inside int32, and the workspace stays at 4 (R + n_rows) bytes of norms plus 8 n_rows per part -- at
+ * most 4 MiB of winners, whatever n_rows.  More references: call per chunk and combine by the order above.
+ * n_rows == 0 is a no-op that returns 0, even with null pointers.  Anything else -- a limit, a stride below H, a null pointer, a
+ * workspace that is too small -- returns non-zero with mkgnn_last_error set, before any launch. */
+#define MKGNN_MAX_COSINE_MAX_REFS 1048576
+size_t mkgnn_embed_max_cosine_workspace_bytes(int64_t n_rows, int32_t R);
+int mkgnn_embed_max_cosine(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* refs, int64_t ref_stride,
+                           int32_t R, float* max_sim, int32_t* arg_ref, void* workspace, size_t workspace_bytes, void* stream);
+
+/* (additive; the ABI version stays 8) Stable compaction of a batch by a key -- the filter between a scoring step and
+ * mkgnn_topk_update.  The rows i < min(max(*n_valid, 0), B) with bounds[0] <= key[i] <= bounds[1] are kept (a NaN key fails both
+ * comparisons and is never kept; a key equal to a bound is kept; infinite bounds are allowed): their (scores[i], ids[i]) are written
+ * in order to out_scores[0 .. *n_kept) and out_ids[0 .. *n_kept), score bits carried over, and *n_kept is written by the launch.
+ * Slots from *n_kept on are not written.  n_valid (int32) and bounds (float[2]: lo, hi) are DEVICE scalars read when the launch
+ * runs, so one captured launch serves every batch and every pair of bounds.  What the launch writes -- out_scores, out_ids and
+ * *n_kept -- must not overlap scores, ids, key, *n_valid, bounds or each other (rejected).  Any B >= 1 in ONE launch of one workgroup (a block scan per 1 024 slots, looping over B: a batch
+ * is a few thousand slots); capturable, no atomics, no workspace, no state.  B < 1 or a null pointer returns non-zero with
+ * mkgnn_last_error set before the launch.  mkgnn_topk_update(out_scores, out_ids, B, n_kept, ...) takes the result as it is: it
+ * reads its count on the device and accepts a count of zero. */
+int mkgnn_select_rows(const float* scores, const int32_t* ids, const float* key, int32_t B, const int32_t* n_valid,
+                      const float* bounds, float* out_scores, int32_t* out_ids, int32_t* n_kept, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

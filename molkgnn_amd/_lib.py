@@ -21,6 +21,22 @@ ABI_VERSION = 8
 LOSS_BCE_MEAN, LOSS_SQERR_MEAN, LOSS_SQERR_SUM = 0, 1, 2
 TASK_HEAD_MAX_TASKS, TASK_HEAD_MAX_H = 32, 64   # MKGNN_TASK_HEAD_MAX_TASKS, the task-indexed head's widest embedding
 EMBED_COSINE_MAX_QUERIES, EMBED_COSINE_MAX_H = 32, 64   # MKGNN_EMBED_COSINE_MAX_QUERIES, mkgnn_embed_cosine's widest embedding
+MAX_COSINE_MAX_REFS, MAX_COSINE_MAX_H = 1 << 20, 64     # MKGNN_MAX_COSINE_MAX_REFS, mkgnn_embed_max_cosine's widest embedding
+# kgnn_max_cosine.hip's tiling (MC_ROWS, MC_TILE, MC_MAX_PARTS, MC_TARGET_BLOCKS; SEL_THREADS): rows per block, references per LDS
+# tile, the most parts a launch splits the references into, the blocks it aims at; the slots of one pass of mkgnn_select_rows
+MAX_COSINE_ROWS, MAX_COSINE_TILE, MAX_COSINE_MAX_PARTS, MAX_COSINE_TARGET_BLOCKS = 128, 32, 256, 2048
+SELECT_ROWS_PASS = 1024
+
+
+def max_cosine_split(n_rows: int, R: int):
+    """``(references per part, parts)`` of one ``mkgnn_embed_max_cosine`` launch (``mc_split``, kgnn_max_cosine.hip): whole tiles per
+    part, at most ``MAX_COSINE_MAX_PARTS`` parts and no more than bring the grid to ``MAX_COSINE_TARGET_BLOCKS`` blocks.  The result
+    of a call does not depend on it; the tests place their shapes around it."""
+    row_blocks = -(-int(n_rows) // MAX_COSINE_ROWS)
+    tiles = -(-int(R) // MAX_COSINE_TILE)
+    want = min(-(-MAX_COSINE_TARGET_BLOCKS // row_blocks), tiles, MAX_COSINE_MAX_PARTS)
+    per_part = -(-tiles // want)
+    return per_part * MAX_COSINE_TILE, -(-tiles // per_part)
 
 
 class KernelBank(C.Structure):
@@ -182,7 +198,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_gather_compact_workspace_bytes", "mkgnn_gather_compact_packed", "mkgnn_topk_update", "mkgnn_topk_workspace_bytes",
            "mkgnn_task_head_workspace_bytes", "mkgnn_task_head_forward", "mkgnn_task_head_backward", "mkgnn_task_head_fused",
            "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks", "mkgnn_embed_cosine",
-           "mkgnn_atom_contributions", "mkgnn_atom_contributions_workspace_bytes")
+           "mkgnn_atom_contributions", "mkgnn_atom_contributions_workspace_bytes", "mkgnn_embed_max_cosine",
+           "mkgnn_embed_max_cosine_workspace_bytes", "mkgnn_select_rows")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -376,6 +393,14 @@ def load() -> C.CDLL:
     # cosine of every row with every query: (emb, stride, n_rows, H, queries, stride, Q, sim, row stride, query stride, stream)
     lib.mkgnn_embed_cosine.restype = C.c_int
     lib.mkgnn_embed_cosine.argtypes = [P, I64, I64, I32, P, I64, I32, P, I64, I64, P]
+    # the nearest reference of every row: (emb, stride, n_rows, H, refs, stride, R, max_sim, arg_ref, workspace, bytes, stream)
+    lib.mkgnn_embed_max_cosine_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_embed_max_cosine_workspace_bytes.argtypes = [I64, I32]
+    lib.mkgnn_embed_max_cosine.restype = C.c_int
+    lib.mkgnn_embed_max_cosine.argtypes = [P, I64, I64, I32, P, I64, I32, P, P, P, C.c_size_t, P]
+    # stable compaction by a key: (scores, ids, key, B, n_valid, bounds, out_scores, out_ids, n_kept, stream)
+    lib.mkgnn_select_rows.restype = C.c_int
+    lib.mkgnn_select_rows.argtypes = [P, P, P, I32, P, P, P, P, P, P]
     lib.mkgnn_rf_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_rf_workspace_bytes.argtypes = [I64]
     lib.mkgnn_rf_count.restype = C.c_int

@@ -35,12 +35,8 @@ constexpr int EC_MAX_Q = MKGNN_EMBED_COSINE_MAX_QUERIES;
 static_assert(EC_MAX_Q <= 32, "one lane of a row's half-wave per query");
 static_assert(EC_MAX_Q <= MKGNN_TASK_HEAD_MAX_TASKS, "the queries' lists are a TopKTasks");
 
-// the sum of squares of an H-vector held as v0 = v[h], v1 = v[32 + h] by the 32 lanes of a half-wave: in every lane of it
-__device__ __forceinline__ float ec_sumsq(float v0, float v1, int h, int H) {
-    float s = h < H ? __fmul_rn(v0, v0) : 0.f;
-    if (32 + h < H) s = fmaf(v1, v1, s);
-    return half_wave_sum(s);
-}
+// the sum of squares of an H-vector held by a half-wave: half_wave_sumsq (kgnn_head_terms.h), shared with kgnn_max_cosine.hip
+__device__ __forceinline__ float ec_sumsq(float v0, float v1, int h, int H) { return half_wave_sumsq(v0, v1, h, H); }
 
 __global__ void __launch_bounds__(256) embed_cosine_kernel(const float* __restrict__ emb, int64_t es, int64_t n, int H, int Q,
                                                            const float* __restrict__ qry, int64_t qs, float* __restrict__ sim,

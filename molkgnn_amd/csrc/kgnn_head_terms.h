@@ -16,6 +16,15 @@ __device__ __forceinline__ float half_wave_sum(float v) {   // xor tree over the
     return v;
 }
 
+// the sum of squares of an H-vector (H <= 64) held as v0 = v[h], v1 = v[32 + h] by the 32 lanes of a half-wave, in every lane of it:
+// lane h forms v[h] * v[h] (+0.0 at h >= H), applies fmaf(v[32 + h], v[32 + h], .) where 32 + h < H, then the xor tree.  THE one
+// definition of a cosine's norm: mkgnn_embed_cosine and mkgnn_embed_max_cosine promise each other's bits through it
+__device__ __forceinline__ float half_wave_sumsq(float v0, float v1, int h, int H) {
+    float s = h < H ? __fmul_rn(v0, v0) : 0.f;
+    if (32 + h < H) s = fmaf(v1, v1, s);
+    return half_wave_sum(s);
+}
+
 // The loss kind LK (MKGNN_LOSS_*, ABI v8) is a template parameter of every head kernel: the BCE instantiations are the code
 // that was there before.  A row's loss term and its d loss / d pred, both before the 1 / B of the mean kinds:
 template <int LK>

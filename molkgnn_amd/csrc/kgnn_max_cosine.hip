@@ -1,0 +1,296 @@
+// The nearest reference of every embedding row (mkgnn_embed_max_cosine) and the stable compaction that hands the rows a filter
+// keeps to the running list (mkgnn_select_rows): novelty filter and applicability domain of a screen.
+//
+//     max_sim[i], arg_ref[i] = the first r, in the order of topk_update_reference (non-NaN before NaN, larger first with
+//                              -0.0 == +0.0, then the lower r), of sim(i, r) -- the float32 value mkgnn_embed_cosine writes for row i
+//                              and query refs[r], BIT FOR BIT
+//
+// THE BITS.  kgnn_embed_cosine.hip fixes one element's evaluation: lane h of 32 forms e[h] * q[h] (+0.0 at h >= H), applies
+// fmaf(e[32 + h], q[32 + h], .) where 32 + h < H, the 32 values go through the xor tree (offsets 16, 8, 4, 2, 1), then + (+0.0), then
+// (dot * inv(e)) * inv(q).  Every step of that tree is lane l forming v[l] + v[l ^ o]; float addition is commutative, so all lanes
+// hold the same bits and the tree is a fixed binary tree: level 16 adds x[j] + x[j + 16] for j < 16, level 8 adds those sums j and
+// j + 8, and so on.  ONE THREAD evaluates it serially in that association (mc_dot) and gets the same bits.  The row and the
+// reference are padded with +0.0 up to 32 (H <= 32) or 64 columns: a padded product is (+0.0) * (+0.0) = +0.0, what a lane
+// h >= H contributes there; a padded fmaf(+0.0, +0.0, x) is x + (+0.0), which differs from the skipped fmaf only where x is -0.0,
+// and the sign of a zero going into a tree of additions can change nothing but the sign of a zero coming out, which the
+// + (+0.0) behind the tree removes.  Nothing in this file may be contracted: the pragma below, and explicit fmaf where the
+// definition has one.  The inverse norms are NOT re-derived: norms_kernel runs half_wave_sumsq (kgnn_head_terms.h) -- the
+// function embed_cosine_kernel itself calls -- for every reference and every row, into the workspace.
+//
+// THE LAUNCHES (two, or three when the references are split; all on the caller's stream, capturable, no atomics, no state):
+//   norms_kernel       one half-wave per vector: 1 / max(||.||, eps) of the R references and the n rows -> workspace
+//   max_cosine_kernel  MC_ROWS rows per block, ONE THREAD PER ROW with the row in registers; grid.y = parts of the reference set;
+//                      per MC_TILE references the block stages the raw values (zero padded) and their inverse norms in LDS, every
+//                      lane then reads the same address -- a broadcast, conflict-free -- and walks the tile.  One part: it writes
+//                      max_sim / arg_ref itself.  More: every part writes its winner to workspace[part][row]
+//   combine_kernel     one half-wave per row: the parts' winners under the same rule, equals to the lower index -> max_sim / arg_ref
+// The winner is a total order's first element, so it does not depend on how the references are split; the split (mc_split; mirrored
+// by _lib.max_cosine_split) only has to fill the chip: a batch of 256 rows is two row blocks, so it is cut into up to MC_MAX_PARTS
+// parts of whole tiles, a batch of 4 096 rows against 16 384 references into 64 parts of 8 tiles (MC_TARGET_BLOCKS blocks in all).
+// Plain FP32 VALU: the bit contract forbids another summation order, and with it the matrix instructions.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include "kgnn_common.h"
+
+#include "kgnn_launch.h"
+#include "kgnn_head_terms.h"
+#include "../../include/molkgnn_hip.h"
+
+#pragma clang fp contract(off)
+
+namespace mkgnn {
+namespace {
+
+constexpr int MC_MAX_H = 64;
+constexpr int MC_ROWS = 128;              // rows (= threads) per block: two waves share one staged tile
+constexpr int MC_TILE = 32;               // references per LDS tile: 32 x 64 floats = 8 KB, twenty blocks' worth per CU
+constexpr int MC_MAX_PARTS = 256;         // parts of the reference set (grid.y); the workspace holds parts x rows winners
+constexpr int MC_TARGET_BLOCKS = 2048;    // eight blocks (sixteen waves) per CU
+constexpr int SEL_THREADS = 1024;         // mkgnn_select_rows: one workgroup, 1 024 slots per pass
+
+// how a launch splits R references for n rows: whole tiles per part, at most MC_MAX_PARTS parts, no more than fill the chip
+struct McSplit { int part_refs, parts; };
+inline McSplit mc_split(int64_t n, int R) {
+    const int64_t row_blocks = (n + MC_ROWS - 1) / MC_ROWS;
+    const int tiles = (R + MC_TILE - 1) / MC_TILE;
+    int64_t want = (MC_TARGET_BLOCKS + row_blocks - 1) / row_blocks;
+    if (want > tiles) want = tiles;
+    if (want > MC_MAX_PARTS) want = MC_MAX_PARTS;
+    const int tiles_per_part = (tiles + (int)want - 1) / (int)want;
+    return {tiles_per_part * MC_TILE, (tiles + tiles_per_part - 1) / tiles_per_part};
+}
+
+// vector v of [refs (R) | rows (n)]: inv[v] = 1 / max(||v||, eps); one half-wave per vector, 8 per block
+__global__ void __launch_bounds__(256) norms_kernel(const float* __restrict__ refs, int64_t rs, int R, const float* __restrict__ emb,
+                                                    int64_t es, int64_t n, int H, float* __restrict__ inv) {
+    const int h = threadIdx.x & 31;
+    const int64_t v = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5), total = (int64_t)R + n;
+    const int64_t vc = v < total ? v : total - 1;                 // (clamped: every lane of a half-wave takes part in the tree)
+    const float* row = vc < R ? refs + vc * rs : emb + (vc - R) * es;
+    const float s = half_wave_sumsq(row[h < H ? h : 0], row[32 + h < H ? 32 + h : 0], h, H);
+    if (h == 0 && v < total) inv[v] = 1.f / fmaxf(sqrtf(s), MKGNN_EPS);
+}
+
+// the dot product of the definition, serially: products, the optional fmaf, the xor tree's association, + (+0.0)
+template <int W>
+__device__ __forceinline__ float mc_dot(const float (&e)[W], const float* __restrict__ q) {
+#pragma clang fp contract(off)
+    // (plain operators under the pragma: __fmul_rn / __fadd_rn are header functions compiled under the header's own mode, and a
+    // product and the sum it feeds in ONE thread would be fused -- in embed_cosine_kernel a shuffle lies between them)
+    float x[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) x[j] = e[j] * q[j];
+    if constexpr (W == 64) {
+#pragma unroll
+        for (int j = 0; j < 32; ++j) x[j] = fmaf(e[32 + j], q[32 + j], x[j]);
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {
+#pragma unroll
+        for (int j = 0; j < o; ++j) x[j] = x[j] + x[j + o];
+    }
+    return x[0] + 0.f;
+}
+
+// the order: a non-NaN beats a NaN, a larger value beats a smaller one (-0.0 == +0.0: no strict >), the earlier one stays otherwise
+__device__ __forceinline__ bool mc_better(float s, float best) { return s == s && (best != best || s > best); }
+
+template <int W>
+__global__ void __launch_bounds__(MC_ROWS) max_cosine_kernel(const float* __restrict__ emb, int64_t es, int64_t n, int H,
+                                                             const float* __restrict__ refs, int64_t rs, int R, int part_refs,
+                                                             const float* __restrict__ inv, float* __restrict__ out_sim,
+                                                             int32_t* __restrict__ out_arg) {
+    __shared__ __attribute__((aligned(16))) float tile[MC_TILE * W];
+    __shared__ float tinv[MC_TILE];
+    const int t = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * MC_ROWS + t, ic = i < n ? i : n - 1;
+    float e[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) e[j] = j < H ? emb[ic * es + j] : 0.f;
+    const float ie = inv[R + ic];
+    const int r_begin = blockIdx.y * part_refs, r_end = min(R, r_begin + part_refs);
+    float best = __int_as_float(0x7fc00000);                    // "nothing yet": any first value replaces it, a NaN leaves it
+    int arg = r_begin;
+    for (int r0 = r_begin; r0 < r_end; r0 += MC_TILE) {
+        const int m = min(MC_TILE, r_end - r0);
+        __syncthreads();                                         // (the previous tile has been walked by every wave)
+        for (int j = t; j < m * W; j += MC_ROWS) {
+            const int r = j / W, c = j - r * W;
+            tile[j] = c < H ? refs[(int64_t)(r0 + r) * rs + c] : 0.f;
+        }
+        if (t < m) tinv[t] = inv[r0 + t];
+        __syncthreads();
+        // two references in flight -- one's LDS reads under the other's adds -- and selects, not branches, between them; an odd
+        // tile's last reference is taken twice, which the strict order ignores
+        for (int r = 0; r < m; r += 2) {
+            const int r1 = r + 1 < m ? r + 1 : r;
+            const float d0 = mc_dot<W>(e, tile + r * W), d1 = mc_dot<W>(e, tile + r1 * W);
+            const float s0 = (d0 * ie) * tinv[r], s1 = (d1 * ie) * tinv[r1];
+            const bool b0 = mc_better(s0, best);
+            best = b0 ? s0 : best;
+            arg = b0 ? r0 + r : arg;
+            const bool b1 = mc_better(s1, best);
+            best = b1 ? s1 : best;
+            arg = b1 ? r0 + r1 : arg;
+        }
+    }
+    if (i < n) {
+        const int64_t o = (int64_t)blockIdx.y * n + i;          // (one part: out_* are the outputs themselves, o = i)
+        out_sim[o] = best;
+        out_arg[o] = arg;
+    }
+}
+
+// the order between two candidates of DIFFERENT references: mc_better, and among equals (two NaNs, a == b) the lower index --
+// symmetric, so both lanes of an exchange keep the same one, and what a sequential walk in reference order keeps
+__device__ __forceinline__ bool mc_first(float s, int a, float t, int b) {
+    const bool tie = (s != s && t != t) || s == t;
+    return tie ? a < b : mc_better(s, t);
+}
+
+// one half-wave per row: lane l takes parts l, l + 32, ... (independent loads), then an xor tree under mc_first
+__global__ void __launch_bounds__(256) combine_kernel(const float* __restrict__ part_sim, const int32_t* __restrict__ part_arg,
+                                                      int64_t n, int parts, float* __restrict__ max_sim,
+                                                      int32_t* __restrict__ arg_ref) {
+    const int l = threadIdx.x & 31;
+    const int64_t i = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5), ic = i < n ? i : n - 1;
+    float best = __int_as_float(0x7fc00000);
+    int arg = 0x7fffffff;                                        // (no part: loses to every candidate, a NaN one included)
+    for (int p = l; p < parts; p += 32) {
+        const float s = part_sim[(int64_t)p * n + ic];
+        const int a = part_arg[(int64_t)p * n + ic];
+        if (mc_first(s, a, best, arg)) { best = s; arg = a; }
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {
+        const float s = __shfl_xor(best, o, 64);
+        const int a = __shfl_xor(arg, o, 64);
+        if (mc_first(s, a, best, arg)) { best = s; arg = a; }
+    }
+    if (l == 0 && i < n) {
+        max_sim[i] = best;
+        arg_ref[i] = arg;
+    }
+}
+
+// mkgnn_select_rows: one workgroup; per pass of SEL_THREADS slots a ballot per wave, the waves' counts through LDS, the kept
+// slots written behind the passes before -- in slot order, so the compaction is stable
+__global__ void __launch_bounds__(SEL_THREADS) select_rows_kernel(const float* __restrict__ scores, const int32_t* __restrict__ ids,
+                                                                  const float* __restrict__ key, int B,
+                                                                  const int32_t* __restrict__ n_valid,
+                                                                  const float* __restrict__ bounds, float* __restrict__ out_scores,
+                                                                  int32_t* __restrict__ out_ids, int32_t* __restrict__ n_kept) {
+    constexpr int NW = SEL_THREADS / 64;
+    __shared__ int wave_count[NW];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int nv = min(max(*n_valid, 0), B);
+    const float lo = bounds[0], hi = bounds[1];
+    int base = 0;
+    for (int b0 = 0; b0 < nv; b0 += SEL_THREADS) {               // (nv is the block's: every thread makes every pass)
+        const int i = b0 + t;
+        bool keep = false;
+        if (i < nv) {
+            const float k = key[i];
+            keep = lo <= k && k <= hi;                           // (a NaN key fails both)
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (lane == 0) wave_count[w] = __popcll(mask);
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int v = 0; v < NW; ++v) {
+            const int c = wave_count[v];
+            before += v < w ? c : 0;
+            all += c;
+        }
+        if (keep) {
+            const int o = base + before + __popcll(mask & ((1ull << lane) - 1ull));
+            out_scores[o] = scores[i];
+            out_ids[o] = ids[i];
+        }
+        base += all;
+        __syncthreads();                                         // (wave_count is rewritten by the next pass)
+    }
+    if (t == 0) *n_kept = base;
+}
+
+}  // namespace
+}  // namespace mkgnn
+
+using namespace mkgnn;
+
+static_assert(MKGNN_MAX_COSINE_MAX_REFS % MC_TILE == 0, "whole tiles");
+
+namespace {
+// [inverse norms: R + n floats, padded to 4][parts x n winners' values][parts x n winners' indices]
+inline size_t mc_norm_floats(int64_t n, int R) { return (size_t)(((int64_t)R + n + 3) / 4 * 4); }
+inline bool mc_sizes_ok(int64_t n, int R) {
+    return R >= 1 && R <= MKGNN_MAX_COSINE_MAX_REFS && n >= 1 && n <= 0x7fffffff;      // (every grid dimension fits)
+}
+}  // namespace
+
+extern "C" size_t mkgnn_embed_max_cosine_workspace_bytes(int64_t n_rows, int32_t R) {
+    if (!mc_sizes_ok(n_rows, R)) return 0;
+    const McSplit sp = mc_split(n_rows, R);
+    const size_t winners = sp.parts > 1 ? (size_t)sp.parts * (size_t)n_rows : 0;
+    return sizeof(float) * (mc_norm_floats(n_rows, R) + 2 * winners);
+}
+
+extern "C" int mkgnn_embed_max_cosine(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* refs,
+                                      int64_t ref_stride, int32_t R, float* max_sim, int32_t* arg_ref, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    const char* who = "mkgnn_embed_max_cosine";
+    if (R < 1 || R > MKGNN_MAX_COSINE_MAX_REFS)
+        return api_fail("%s: %d references outside [1, %d]", who, (int)R, MKGNN_MAX_COSINE_MAX_REFS);
+    if (H < 1 || H > MC_MAX_H) return api_fail("%s: embedding width %d outside [1, %d]", who, (int)H, MC_MAX_H);
+    if (n_rows < 0 || emb_stride < H || ref_stride < H) return api_fail("%s: bad shape", who);
+    if (n_rows == 0) return 0;
+    if (!emb || !refs || !max_sim || !arg_ref || !workspace) return api_fail("%s: null pointer", who);
+    if (!mc_sizes_ok(n_rows, R)) return api_fail("%s: %lld rows: at most 2^31 - 1 in one call", who, (long long)n_rows);
+    const size_t need = mkgnn_embed_max_cosine_workspace_bytes(n_rows, R);
+    if (workspace_bytes < need)
+        return api_fail("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    if (((uintptr_t)workspace & 3) != 0) return api_fail("%s: workspace not 4-byte aligned", who);
+    const hipStream_t st = (hipStream_t)stream;
+    const McSplit sp = mc_split(n_rows, R);
+    float* inv = (float*)workspace;
+    float* part_sim = inv + mc_norm_floats(n_rows, R);
+    int32_t* part_arg = (int32_t*)(part_sim + (size_t)sp.parts * (size_t)n_rows);
+    const int64_t vectors = (int64_t)R + n_rows;
+    norms_kernel<<<(unsigned)((vectors + 7) / 8), 256, 0, st>>>(refs, ref_stride, R, emb, emb_stride, n_rows, H, inv);
+    const dim3 grid((unsigned)((n_rows + MC_ROWS - 1) / MC_ROWS), (unsigned)sp.parts);
+    float* os = sp.parts > 1 ? part_sim : max_sim;
+    int32_t* oa = sp.parts > 1 ? part_arg : arg_ref;
+    if (H <= 32)
+        max_cosine_kernel<32><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, os, oa);
+    else
+        max_cosine_kernel<64><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, os, oa);
+    if (sp.parts > 1)
+        combine_kernel<<<(unsigned)((n_rows + 7) / 8), 256, 0, st>>>(part_sim, part_arg, n_rows, sp.parts, max_sim, arg_ref);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+extern "C" int mkgnn_select_rows(const float* scores, const int32_t* ids, const float* key, int32_t B, const int32_t* n_valid,
+                                 const float* bounds, float* out_scores, int32_t* out_ids, int32_t* n_kept, void* stream) {
+    const char* who = "mkgnn_select_rows";
+    if (B < 1) return api_fail("%s: %d slots: at least one is needed", who, (int)B);
+    if (!scores || !ids || !key || !n_valid || !bounds || !out_scores || !out_ids || !n_kept) return api_fail("%s: null pointer", who);
+    // what the launch writes -- out_scores, out_ids, *n_kept -- must not overlap what it reads, nor each other: thread 0 writes
+    // *n_kept after other threads have read the scalars and written the outputs
+    struct Span { const char* p; size_t n; };
+    const size_t bytes = (size_t)B * 4;
+    const Span wr[3] = {{(const char*)out_scores, bytes}, {(const char*)out_ids, bytes}, {(const char*)n_kept, 4}};
+    const Span rd[5] = {{(const char*)scores, bytes}, {(const char*)ids, bytes}, {(const char*)key, bytes},
+                        {(const char*)n_valid, 4}, {(const char*)bounds, 8}};
+    auto overlap = [](const Span& x, const Span& y) { return x.p < y.p + y.n && y.p < x.p + x.n; };
+    for (int w = 0; w < 3; ++w) {
+        for (int r = 0; r < 5; ++r)
+            if (overlap(wr[w], rd[r])) return api_fail("%s: an output (out_scores, out_ids, n_kept) aliases an input", who);
+        for (int v = w + 1; v < 3; ++v)
+            if (overlap(wr[w], wr[v])) return api_fail("%s: the outputs (out_scores, out_ids, n_kept) alias each other", who);
+    }
+    select_rows_kernel<<<1, SEL_THREADS, 0, (hipStream_t)stream>>>(scores, ids, key, B, n_valid, bounds, out_scores, out_ids, n_kept);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}

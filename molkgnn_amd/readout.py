@@ -919,6 +919,156 @@ def embedding_cosine(emb: torch.Tensor, queries: torch.Tensor, n_rows: Optional[
     return out
 
 
+def embedding_max_cosine_supported(R: int, H: int) -> bool:
+    """The shapes ``mkgnn_embed_max_cosine`` takes; anything else goes through torch operators on the GPU."""
+    return 1 <= R <= _lib.MAX_COSINE_MAX_REFS and 1 <= H <= _lib.MAX_COSINE_MAX_H
+
+
+MAX_COSINE_TORCH_CHUNK = 4096         # references per step of the torch route: no [n, R] matrix beyond [n, 4096] exists
+
+
+def _first_max(sim: torch.Tensor):
+    """``(value, index)`` per row of ``sim [n, c]`` by the order of ``screening.max_cosine_reference``: non-NaN before NaN, larger
+    first, the lower index among equals (``-0.0 == +0.0``); an all-NaN row gives ``(NaN, 0)``."""
+    c = sim.shape[1]
+    nan = torch.isnan(sim)
+    clean = torch.where(nan, torch.full_like(sim, float("-inf")), sim)
+    best = clean.max(dim=1, keepdim=True).values
+    col = torch.arange(c, device=sim.device)[None, :].expand_as(sim)
+    arg = torch.where((clean == best) & ~nan, col, torch.full_like(col, c)).min(dim=1).values
+    none = arg == c
+    arg = torch.where(none, torch.zeros_like(arg), arg)
+    value = sim.gather(1, arg[:, None])[:, 0]
+    return torch.where(none, torch.full_like(value, float("nan")), value), arg
+
+
+_MAX_COSINE_WS: dict = {}
+
+
+def _max_cosine_workspace(dev, nbytes: int, given: Optional[torch.Tensor]) -> torch.Tensor:
+    """The scratch of one ``mkgnn_embed_max_cosine``: the caller's ``workspace`` when given (uint8, on the device, large enough); a
+    fresh buffer inside a capture (the graph's pool keeps it, and no other graph shares it); otherwise one buffer per device that
+    only grows, so an eager loop over batches allocates once (eager calls on one stream are ordered; callers on several streams pass
+    their own)."""
+    if given is not None:
+        if not torch.is_tensor(given) or given.dtype != torch.uint8 or given.device != dev or not given.is_contiguous() \
+                or given.numel() < nbytes:
+            raise ValueError(f"workspace: a contiguous uint8 tensor of at least {nbytes} bytes on {dev}")
+        return given
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    held = _MAX_COSINE_WS.get(str(dev))
+    if held is None or held.numel() < nbytes:
+        held = _MAX_COSINE_WS[str(dev)] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)
+    return held
+
+
+def embedding_max_cosine(emb: torch.Tensor, refs: torch.Tensor, n_rows: Optional[int] = None, out=None,
+                         workspace: Optional[torch.Tensor] = None):
+    """``(max_sim float32 [n_rows], arg_ref int32 [n_rows])``: for each of the leading ``n_rows`` rows of a float32 CUDA ``emb [n, H]``
+    its nearest row of a float32 CUDA ``refs [R, H]`` by cosine similarity -- the similarity ``embedding_cosine`` gives for the pair,
+    BIT FOR BIT, and the winner the first ``r`` in the order of ``screening.topk_update_reference``: non-NaN before NaN, larger
+    first with ``-0.0 == +0.0``, then the lower ``r`` (``screening.max_cosine_reference`` is the definition in float64).  One
+    ``mkgnn_embed_max_cosine``: the references are read raw, their norms are taken inside the call, so a captured call follows the
+    contents of both tensors; no ``[n, R]`` matrix exists.  A row of NaN, or references that are all NaN, give ``(NaN, 0)``.  ``out``:
+    a pair of contiguous tensors ``(float32 [n_rows], int32 [n_rows])`` on the device to write into.  ``workspace``: a uint8 device
+    tensor of at least ``mkgnn_embed_max_cosine_workspace_bytes(n_rows, R)`` bytes to use as scratch; without it a per-device buffer
+    that only grows serves eager calls, and a call inside a capture allocates its own.  More than 2^20 references or an
+    embedding wider than 64: the same definition through torch operators on the GPU, ``MAX_COSINE_TORCH_CHUNK`` references at a time
+    (float64 products, rounded once: inside ``screening.cosine_bound``, not the kernel's bits).  It has no autograd node: called where
+    a gradient is being recorded for one of its inputs it raises instead of dropping it."""
+    if not (torch.is_tensor(emb) and torch.is_tensor(refs)) or emb.dim() != 2 or refs.dim() != 2 \
+            or emb.dtype != torch.float32 or refs.dtype != torch.float32 or refs.shape[1] != emb.shape[1]:
+        raise ValueError("embedding_max_cosine needs a float32 [n, H] embedding and float32 [R, H] references")
+    R, H = refs.shape
+    if R < 1 or H < 1:
+        raise ValueError(f"embedding_max_cosine needs at least one reference and one column, not {R} x {H}")
+    if not emb.is_cuda or refs.device != emb.device:
+        raise ValueError(f"embedding_max_cosine runs on the GPU: emb is on {emb.device}, refs on {refs.device} (there is no CPU "
+                         "path; screening.max_cosine_reference is the host form)")
+    if torch.is_grad_enabled() and (emb.requires_grad or refs.requires_grad):
+        raise RuntimeError("embedding_max_cosine is forward only: call it under torch.no_grad() (or on detached inputs)")
+    n = emb.shape[0] if n_rows is None else int(n_rows)
+    if not 0 <= n <= emb.shape[0]:
+        raise ValueError(f"n_rows = {n_rows} outside [0, {emb.shape[0]}]")
+    dev = emb.device
+    if out is None:
+        out = (torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+    else:
+        ok = isinstance(out, (tuple, list)) and len(out) == 2 and all(torch.is_tensor(o) for o in out)
+        if not ok or out[0].dtype != torch.float32 or out[1].dtype != torch.int32 \
+                or any(o.device != dev or tuple(o.shape) != (n,) or not o.is_contiguous() for o in out):
+            raise ValueError(f"out: a pair of contiguous tensors (float32 [{n}], int32 [{n}]) on {dev}")
+    max_sim, arg_ref = out
+    if n == 0:
+        return max_sim, arg_ref
+    if not embedding_max_cosine_supported(R, H):
+        e, eps = emb[:n].detach().double(), float(torch.tensor(COSINE_EPS, dtype=torch.float32))
+        ie = 1.0 / e.square().sum(dim=1).sqrt().clamp_min(eps)
+        best = arg = None
+        for a in range(0, R, MAX_COSINE_TORCH_CHUNK):
+            q = refs[a:a + MAX_COSINE_TORCH_CHUNK].detach().double()
+            iq = 1.0 / q.square().sum(dim=1).sqrt().clamp_min(eps)
+            value, index = _first_max(((e @ q.t() + 0.0) * ie[:, None] * iq[None, :]).float())
+            if best is None:
+                best, arg = value, index
+            else:                                        # (the earlier chunk keeps a tie: it holds the lower indices)
+                take = ~torch.isnan(value) & (torch.isnan(best) | (value > best))
+                best, arg = torch.where(take, value, best), torch.where(take, index + a, arg)
+        max_sim.copy_(best)
+        arg_ref.copy_(arg)
+        return max_sim, arg_ref
+    emb, refs = _row_major(emb.detach()), _row_major(refs.detach())
+    lib = _lib.load()
+    ws = _max_cosine_workspace(dev, int(lib.mkgnn_embed_max_cosine_workspace_bytes(n, R)), workspace)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkgnn_embed_max_cosine(emb.data_ptr(), _stride0(emb), n, H, refs.data_ptr(), _stride0(refs), R,
+                                              max_sim.data_ptr(), arg_ref.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              _lib.stream_ptr(dev)), "mkgnn_embed_max_cosine")
+    return max_sim, arg_ref
+
+
+def select_rows(scores: torch.Tensor, ids: torch.Tensor, key: torch.Tensor, n_valid, bounds: torch.Tensor, out=None):
+    """``(out_scores float32 [B], out_ids int32 [B], n_kept int32 [1])``: the stable compaction ``mkgnn_select_rows`` -- the slots
+    ``i < min(max(n_valid, 0), B)`` with ``bounds[0] <= key[i] <= bounds[1]`` (a NaN key is never kept), in order, at the head of the
+    outputs, score bits carried over; slots from ``n_kept`` on are not written (``screening.select_rows_reference`` is the
+    definition).  ``scores``, ``key`` float32 and ``ids`` int32, contiguous ``[B]`` on the GPU; ``bounds`` a float32 ``[2]`` device
+    tensor (lo, hi) and ``n_valid`` a one-element int32 device tensor, both read when the launch runs (an int ``n_valid`` is uploaded
+    first), so a captured call follows them.  ``out``: the three tensors to write into, which must not alias the inputs.  What it
+    returns is what ``TopK.update(out_scores, out_ids, n_valid=n_kept)`` takes."""
+    tensors = (scores, ids, key, bounds)
+    if not all(torch.is_tensor(t) for t in tensors) or scores.dtype != torch.float32 or key.dtype != torch.float32 \
+            or ids.dtype != torch.int32 or bounds.dtype != torch.float32:
+        raise ValueError("select_rows needs float32 scores and key, int32 ids and float32 bounds")
+    B = scores.numel()
+    if B < 1 or scores.dim() != 1 or tuple(ids.shape) != (B,) or tuple(key.shape) != (B,) or tuple(bounds.shape) != (2,) \
+            or not all(t.is_contiguous() for t in tensors):
+        raise ValueError("select_rows needs contiguous scores, ids and key of one length B >= 1 and bounds [2]")
+    dev = scores.device
+    if dev.type != "cuda" or any(t.device != dev for t in tensors):
+        raise ValueError(f"select_rows runs on the GPU: scores are on {dev} (there is no CPU path; screening.select_rows_reference "
+                         "is the host form)")
+    if torch.is_tensor(n_valid):
+        if n_valid.dtype != torch.int32 or n_valid.numel() != 1 or n_valid.device != dev:
+            raise ValueError("n_valid: one int32 on the scores' device, or an int")
+    else:
+        n_valid = torch.tensor([int(n_valid)], dtype=torch.int32, device=dev)
+    if out is None:
+        out = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(1, dtype=torch.int32, device=dev))
+    else:
+        ok = isinstance(out, (tuple, list)) and len(out) == 3 and all(torch.is_tensor(o) and o.device == dev and o.is_contiguous()
+                                                                      for o in out)
+        if not ok or out[0].dtype != torch.float32 or out[1].dtype != torch.int32 or out[2].dtype != torch.int32 \
+                or tuple(out[0].shape) != (B,) or tuple(out[1].shape) != (B,) or out[2].numel() != 1:
+            raise ValueError(f"out: contiguous (float32 [{B}], int32 [{B}], int32 [1]) on {dev}")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mkgnn_select_rows(scores.data_ptr(), ids.data_ptr(), key.data_ptr(), B, n_valid.data_ptr(),
+                                                 bounds.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                                 _lib.stream_ptr(dev)), "mkgnn_select_rows")
+    return tuple(out)
+
+
 # ------------------------------------------------------------------- the tail of a training step, fused --
 # MKGNN_FUSED_TAIL=0: readout_blocks + bce_head_loss as separate operators (nine launches; A/B, diagnostics)
 _FUSED_TAIL = os.environ.get("MKGNN_FUSED_TAIL", "1") != "0"

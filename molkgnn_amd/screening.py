@@ -27,6 +27,13 @@ Why a hit scores what it scores -- every atom's exact share of every output (``G
 ``mkgnn_atom_contributions``):
 
 ``explain_resident``                     ``contrib[atoms of the listed molecules, T]`` for a list of ids of one resident shard
+
+Novel hits -- how close every library molecule lies to a set of known ones (``mkgnn_embed_max_cosine``), and a ranking that keeps
+only the molecules inside a band of that similarity (``mkgnn_select_rows`` in front of the running list):
+
+``max_cosine_reference`` / ``select_rows_reference``  the two definitions in numpy
+``reference_similarity_resident``        ``(max_sim[n_molecules], arg_ref[n_molecules])`` of one resident shard
+``screen_novel``                         shards -> the top ``k`` of the molecules whose nearest reference passes the bounds
 """
 from __future__ import annotations
 
@@ -270,9 +277,13 @@ class _ScoringStep:
     (``score_resident``: ``model.predict`` as a vector), ``(T,)`` for ``ext [n + 1, T]`` (``score_resident_tasks``:
     ``model.predict_tasks``).  ``rank(pred, ids, n_live)``, when given, is called inside the capture with the batch's result, its id
     view and its live count (a one-element device int32 view); ``_run_shard`` passes the running list's ``update``,
-    tools/screen_timing.py other formulations.  The model is in evaluation mode already."""
+    tools/screen_timing.py other formulations.  The model is in evaluation mode already.
 
-    def __init__(self, model, resident, batch_size: int, predict, shape, rank=None):
+    ``extras``: further per-molecule results of one value each, as ``(dtype, filler)`` pairs -- ``predict`` then returns ``(pred,
+    *extras)``, one ``[batch]`` tensor per pair; each is scattered like ``pred`` into its own vector of ``more`` (``[n + 1]``, filled
+    with the filler first) and ``rank`` is called with them behind the live count.  Without them nothing is captured that was not."""
+
+    def __init__(self, model, resident, batch_size: int, predict, shape, rank=None, extras=()):
         from .receptive_field import attach_receptive_fields
         from .shards import ResidentLoader
         dev = resident.device
@@ -291,6 +302,7 @@ class _ScoringStep:
         f_ids, f_live, f_index = feed[:bs], feed[bs:bs + 1], feed[off:].view(torch.int64)
         self.csb = csb = static_batch_for(loader, resident)
         self.ext = ext = torch.full((n + 1, *shape), float("nan"), dtype=torch.float32, device=dev)
+        self.more = more = [torch.full((n + 1,), filler, dtype=dtype, device=dev) for dtype, filler in extras]
         self.n = n
 
         def step(rank):
@@ -298,9 +310,13 @@ class _ScoringStep:
             csb.expand()
             attach_receptive_fields(csb.data, sizes=csb.data.bucket_sizes, overlap=True)
             pred = predict(csb.data)
+            if more:
+                pred, *rest = pred
+                for vector, values in zip(more, rest):
+                    vector.index_copy_(0, f_index, values)
             ext.index_copy_(0, f_index, pred)
             if rank is not None:
-                rank(pred, f_ids, f_live)
+                rank(pred, f_ids, f_live, *rest) if more else rank(pred, f_ids, f_live)
 
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -327,13 +343,17 @@ def _check_out(out, shape, dev) -> None:
 
 
 def _run_shard(who: str, doing: str, model, resident, dev, batch_size: int, predict, shape, topk=None, list_class=TopK,
-               n_lists: Optional[int] = None, per_query: bool = False, shard_tag: int = 0, out=None) -> torch.Tensor:
+               n_lists: Optional[int] = None, per_query: bool = False, shard_tag: int = 0, out=None, extras=(), rank=None):
     """The one pass over a resident shard, behind the callers' own checks of model and shard (``dev``: their device): one captured
     ``_ScoringStep`` with ``predict`` (``shape``: the shape of one molecule's result) replayed over every batch; the ``[n, *shape]``
     result (copied into ``out`` when given, and ``out`` returned); the gather's status word read once, at the end.  ``topk``, when
     given, must be a ``list_class`` (a ``TopKTasks``: of ``n_lists`` lists, one per task, or ``per_query``) on ``dev``: every
     batch's live rows enter it under ``shard_tag``.  ``who`` names the entry point in a refusal, ``doing`` what a status interrupted.
-    The model runs in evaluation mode and is handed back in the mode it came in."""
+    The model runs in evaluation mode and is handed back in the mode it came in.
+
+    ``extras`` (``_ScoringStep``'s): ``predict`` gives further one-value results; the pass then returns ``(out, *vectors)``, the
+    vectors ``[n]`` each.  ``rank``: the caller's own ranking inside the capture, in the place of a running list's ``update``
+    (``topk``, when also given, is only checked, reserved and tagged)."""
     from .train import evaluation_mode
     bs, n = int(batch_size), int(resident.n_molecules)
     if bs < 1:
@@ -346,13 +366,13 @@ def _run_shard(who: str, doing: str, model, resident, dev, batch_size: int, pred
         if topk.device != dev:
             raise ValueError(f"the running {noun} {verb} on {topk.device}, the model on {dev}")
     _check_out(out, (n, *shape), dev)
-    rank = None
     if topk is not None:
         topk.reserve(bs)
         topk.shard_tag.fill_(int(shard_tag))
-        rank = lambda pred, ids, n_live: topk.update(pred, ids, n_valid=n_live)     # noqa: E731
+        if rank is None:
+            rank = lambda pred, ids, n_live: topk.update(pred, ids, n_valid=n_live)     # noqa: E731
     with evaluation_mode(model):
-        scoring = _ScoringStep(model, resident, bs, predict, shape, rank)
+        scoring = _ScoringStep(model, resident, bs, predict, shape, rank, extras)
         for b in range(len(scoring)):
             scoring.run(b)
         if out is None:
@@ -362,7 +382,7 @@ def _run_shard(who: str, doing: str, model, resident, dev, batch_size: int, pred
         status = scoring.csb.gather_status()             # (the one host read)
         if status:
             raise RuntimeError(f"mkgnn_gather_compact reported status {status} while {doing} the shard")
-        return out
+        return (out, *(vector[:n] for vector in scoring.more)) if extras else out
 
 
 def score_resident(model, resident, batch_size: int, *, topk: Optional[TopK] = None, shard_tag: int = 0,
@@ -721,3 +741,167 @@ def rank_embeddings(emb: torch.Tensor, query_emb: torch.Tensor, topk: TopKTasks,
     for a in range(0, n, chunk):
         b = min(a + chunk, n)
         topk.update(embedding_cosine(emb[a:b], query_emb), ids[a:b], n_valid=b - a, shard_tag=int(shard_tag))
+
+
+# ---------------------------------------------------------------------------------------------- novel hits --
+# The opposite question to ``nearest``: for EVERY library molecule, how close is it to what is already known -- the known actives,
+# the training set, a patent set of thousands of molecules?  ``mkgnn_embed_max_cosine`` answers it inside the captured scoring
+# step without an ``[n, R]`` matrix; ``mkgnn_select_rows`` compacts the batch to the molecules inside the bounds before the running
+# list sees it, so a filtered-out molecule never pushes another off the list.  ``max_sim`` alone is the novelty filter ("not a
+# near-copy of a known active"), ``min_sim`` alone the applicability domain ("only where the model can be trusted").
+def max_cosine_reference(emb, refs):
+    """The definition of ``mkgnn_embed_max_cosine`` (include/molkgnn_hip.h), on the host: ``(max float64 [n], arg int64 [n])`` -- per
+    row of ``cosine_reference(emb, refs)`` the first reference in the order of ``topk_update_reference``: non-NaN similarities before
+    NaN ones, larger first (``-0.0 == +0.0``), then the lower index.  A row without a non-NaN similarity gives ``(NaN, 0)``."""
+    sim = cosine_reference(emb, refs)
+    if sim.shape[1] < 1:
+        raise ValueError("at least one reference is needed")
+    nan = np.isnan(sim)
+    clean = np.where(nan, -np.inf, sim)
+    first = ((clean == clean.max(axis=1, keepdims=True)) & ~nan).argmax(axis=1)     # (argmax of booleans: the first True, else 0)
+    some = ~nan.all(axis=1)
+    arg = np.where(some, first, 0).astype(np.int64)
+    return np.where(some, sim[np.arange(sim.shape[0]), arg], np.nan), arg
+
+
+def select_rows_reference(scores, ids, key, n_valid, lo, hi):
+    """The definition of ``mkgnn_select_rows``, on the host: ``(scores, ids, n_kept)`` of the slots ``i < min(max(n_valid, 0), B)`` with
+    ``lo <= key[i] <= hi``, in slot order -- float32 scores with their bits, int32 ids.  A NaN key fails both comparisons; a key
+    equal to a bound is kept; infinite bounds are allowed."""
+    scores = np.asarray(scores, dtype=np.float32).reshape(-1)
+    ids, key = np.asarray(ids, dtype=np.int32).reshape(-1), np.asarray(key, dtype=np.float32).reshape(-1)
+    if not scores.shape == ids.shape == key.shape:
+        raise ValueError("one id and one key per score")
+    n = int(min(max(int(n_valid), 0), scores.shape[0]))
+    with np.errstate(invalid="ignore"):
+        keep = (np.float32(lo) <= key[:n]) & (key[:n] <= np.float32(hi))
+    return scores[:n][keep].copy(), ids[:n][keep].copy(), int(keep.sum())
+
+
+def _check_refs(who: str, ref_emb, G: int, dev=None) -> int:
+    """``R`` of a reference matrix: float32 ``[R, G]``, ``R >= 1``, on ``dev`` (a CUDA device) -- the value checks first, the device
+    last; ``ValueError`` otherwise, before anything is loaded or launched."""
+    if not torch.is_tensor(ref_emb) or ref_emb.dim() != 2:
+        raise ValueError(f"{who}: the references are a [R, {G}] tensor of embeddings")
+    if ref_emb.dtype != torch.float32:
+        raise ValueError(f"{who}: the references are float32, not {ref_emb.dtype}")
+    R = int(ref_emb.shape[0])
+    if R < 1:
+        raise ValueError(f"{who}: at least one reference is needed")
+    if int(ref_emb.shape[1]) != int(G):
+        raise ValueError(f"{who}: the references are {int(ref_emb.shape[1])} wide, the embedding is {int(G)} wide")
+    if ref_emb.device.type != "cuda" or (dev is not None and ref_emb.device != dev):
+        raise ValueError(f"{who}: the references are on {ref_emb.device}; they belong on the GPU of the library" +
+                         ("" if dev is None else f" ({dev})"))
+    return R
+
+
+def _embedding_f32(emb: torch.Tensor) -> torch.Tensor:
+    return emb if emb.dtype == torch.float32 else emb.float()
+
+
+def reference_similarity_resident(model, resident, ref_emb: torch.Tensor, batch_size: int, out=None):
+    """``(max_sim float32 [n_molecules], arg_ref int32 [n_molecules])`` on the device: for every molecule of the ``ResidentShard`` the
+    cosine similarity of its graph embedding with its NEAREST row of ``ref_emb`` (float32 ``[R, G]`` on the shard's GPU) and that
+    row's index (``max_cosine_reference``; ties to the lower index), in id order, the short tail included.  One pass as
+    ``embed_resident`` makes it -- one graph captured per call, replayed per batch -- whose scoring is
+    ``readout.embedding_max_cosine(model.embed(data), ref_emb)``: the references are read raw inside the captured call.  ``out``: a
+    pair of contiguous tensors ``(float32 [n_molecules], int32 [n_molecules])`` to fill; slots that were not written would show as
+    ``(NaN, -1)``.  The model may have any ``task_dim`` and comes back in the mode it came in; a wrong shape, dtype or device raises
+    ``ValueError`` before a launch."""
+    who = "reference_similarity_resident"
+    _check_refs(who, ref_emb, _embedding_width(model))
+    dev = _check_device(model, resident)
+    _check_refs(who, ref_emb, ref_emb.shape[1], dev)
+    n = int(resident.n_molecules)
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2 or not torch.is_tensor(out[1]) or out[1].dtype != torch.int32 \
+                or out[1].device != dev or tuple(out[1].shape) != (n,) or not out[1].is_contiguous():
+            raise ValueError(f"out: a pair of contiguous tensors (float32 [{n}], int32 [{n}]) on {dev}")
+    from .readout import embedding_max_cosine
+    refs = ref_emb.detach()
+    sim, arg = _run_shard(who, "embedding", model, resident, dev, batch_size,
+                          lambda data: embedding_max_cosine(_embedding_f32(model.embed(data)), refs), (),
+                          out=None if out is None else out[0], extras=((torch.int32, -1),))
+    if out is not None:
+        out[1].copy_(arg)
+        arg = out[1]
+    return sim, arg
+
+
+def screen_novel(model, residents, k: int, batch_size: int, ref_emb, max_sim: Optional[float] = None,
+                 min_sim: Optional[float] = None, return_scores: bool = False) -> dict:
+    """``screen`` with a filter in front of the running list: rank the molecules of a library whose NEAREST reference -- by cosine
+    similarity of the graph embeddings, ``max_cosine_reference`` -- lies inside ``[min_sim, max_sim]`` (a bound that is not given is
+    infinite; at least one must be).  ``max_sim=c`` is the novelty filter: the best ``k`` molecules that are not near-copies of a known
+    active.  ``min_sim=c`` is the applicability domain: only molecules close enough to the training set.  A molecule whose reference
+    similarity is NaN is never kept.  ``ref_emb``: a float32 ``[R, G]`` tensor on the model's GPU, or a ``ResidentShard`` of known
+    molecules, which is embedded with ``embed_resident`` first.  ``residents`` as in ``screen``; shard ``j`` carries tag ``j``.
+
+    Per batch ONE captured graph runs: ``model.predict`` (score and embedding from one run of the network, the forward-only tail),
+    ``readout.embedding_max_cosine``, ``readout.select_rows`` with the bounds and the batch's live count, ``TopK.update`` of the kept
+    rows with the kept count (both read on the device), and the running total of kept molecules.  A molecule outside the bounds
+    never enters the list, so it cannot push another one off it.
+
+    Returns ``top_score``, ``top_shard``, ``top_mol`` (trimmed to the occupied slots, best first); ``top_ref_sim`` and ``top_ref``, the
+    nearest reference of every hit (gathered at the end from the per-shard vectors, which stay on the device at 8 bytes per
+    molecule); ``n_scored`` and ``n_kept``; ``ref_emb`` (the ``[R, G]`` matrix that was compared with); and, with ``return_scores``,
+    ``scores``, ``ref_sims`` and ``refs`` per shard.  The gather's status word is read once per shard; the model comes back in the mode
+    it came in.  No bound, ``min_sim > max_sim``, a NaN bound, a multi-task model, a model, shard or references that are not on the
+    GPU: ``ValueError`` before a launch."""
+    from .shards import ResidentShard
+    who = "screen_novel"
+    if max_sim is None and min_sim is None:
+        raise ValueError(f"{who}: give max_sim (novelty filter), min_sim (applicability domain) or both; screen ranks without a filter")
+    lo = float("-inf") if min_sim is None else float(min_sim)
+    hi = float("inf") if max_sim is None else float(max_sim)
+    if lo != lo or hi != hi or lo > hi:
+        raise ValueError(f"{who}: min_sim = {min_sim} and max_sim = {max_sim} leave no similarity to keep")
+    G = _embedding_width(model)
+    if model.ffn.out_features != 1:
+        raise ValueError("screening ranks ONE score per molecule: a one-task model (task_dim = 1) is needed")
+    if isinstance(ref_emb, ResidentShard):
+        if int(ref_emb.n_molecules) < 1:
+            raise ValueError(f"{who}: a reference shard holds at least one molecule")
+        ref_emb = embed_resident(model, ref_emb, batch_size)
+    dev = next(model.parameters()).device
+    _check_refs(who, ref_emb, G, dev if dev.type == "cuda" else None)
+    if dev.type != "cuda":
+        raise ValueError(f"{who} runs on the GPU: move the model there (there is no CPU path)")
+    from .readout import embedding_max_cosine, select_rows
+    refs, bs = ref_emb.detach(), int(batch_size)
+    if bs < 1:
+        raise ValueError("batch_size >= 1")
+    bounds = torch.tensor([lo, hi], dtype=torch.float32, device=dev)
+    kept = (torch.empty(bs, dtype=torch.float32, device=dev), torch.empty(bs, dtype=torch.int32, device=dev),
+            torch.empty(1, dtype=torch.int32, device=dev))
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def predict(data):
+        pred, emb = model.predict(data)
+        return (pred.reshape(-1), *embedding_max_cosine(_embedding_f32(emb), refs))
+
+    def per_shard(resident, topk, tag):
+        def rank(pred, ids, n_live, sim, arg):
+            select_rows(pred, ids, sim, n_live, bounds, out=kept)
+            topk.update(kept[0], kept[1], n_valid=kept[2])
+            total.add_(kept[2])
+
+        scores, sims, args = _run_shard(who, "scoring", model, resident, dev, bs, predict, (), topk, TopK, shard_tag=tag,
+                                        extras=((torch.float32, float("nan")), (torch.int32, -1)), rank=rank)
+        return (scores if return_scores else None), sims.clone(), args.clone()     # (clones: without the spare slot's storage)
+
+    top_score, top_shard, top_mol, occupied, n_scored, shards = _over_shards(
+        who, residents, lambda r: _check_model(model, r), lambda dev: TopK(k, dev), per_shard, True)
+    top_shard, top_mol = top_shard[:occupied], top_mol[:occupied]
+    sizes = [int(sims.numel()) for _, sims, _ in shards]
+    first = torch.tensor(np.concatenate([[0], np.cumsum(sizes)[:-1]]), dtype=torch.int64, device=dev)
+    at = first[top_shard.long()] + top_mol.long()
+    result = {"top_score": top_score[:occupied], "top_shard": top_shard, "top_mol": top_mol,
+              "top_ref_sim": torch.cat([sims for _, sims, _ in shards])[at], "top_ref": torch.cat([args for _, _, args in shards])[at],
+              "n_scored": n_scored, "n_kept": int(total.item()), "ref_emb": ref_emb}
+    if return_scores:
+        result["scores"] = [scores for scores, _, _ in shards]
+        result["ref_sims"] = [sims for _, sims, _ in shards]
+        result["refs"] = [args for _, _, args in shards]
+    return result
