@@ -423,8 +423,25 @@ int mkgnn_tail_fused_readout_dropout(const mkgnn_tail_args* args, float readout_
  * pair at rng_pair on the device (the rng_used of a call, say); it reads the pair and advances nothing. */
 int mkgnn_readout_dropout_mask(const int64_t* rng_pair, int64_t n_rows, int32_t H, float p, float* keep, int64_t keep_stride,
                                void* stream);
-/* Launches a reduction that a mkgnn_tail_fused call with defer_reduce left pending on this thread, on `stream` (no-op: none). */
+/* Launches what a mkgnn_tail_fused call left pending on this device, on `stream` (no-op: nothing): a deferred projection
+ * (mkgnn_tail_defer_projection: the full launch, grad_sim and the dW1 partials) first, then the deferred reduction. */
 int mkgnn_tail_flush(void* stream);
+/* (additive; the ABI version stays 8) One-shot request, per device: the NEXT mkgnn_tail_fused / mkgnn_tail_fused_readout_dropout
+ * call on the current device, if it has defer_reduce set, also leaves out its projection launch
+ *     grad_sim[n, block(n)] = d z[n] . W1[:, block(n)],   dW1 partials = d z^T sim
+ * and keeps it pending beside the reduction.  grad_sim is then NOT written by that call.  The calling thread's next
+ * mkgnn_kernelsetconv_backward takes the projection over when it is the reader of grad_sim -- grad_out == grad_sim with the same
+ * stride, the streamed kernels without MKGNN_BACKWARD_THROUGH_NEIGHBOURS, MKGNN_BACKWARD_DEFER_BANK, a forked helper stream, the
+ * same degree blocks and buckets: its coefficient pre-pass forms every value from d z and W1 itself, in the term order of the
+ * projection kernel (its records are bit for bit those of the materialised grad_sim, which is never written), and the dW1
+ * partials are launched on the helper stream, in front of the deferred reduction.  Any other mkgnn_kernelsetconv_backward on the
+ * device, mkgnn_tail_flush, mkgnn_tail_score, mkgnn_atom_contributions and a further mkgnn_tail_fused* call first make the launch
+ * that was left out, on their stream: behind any of them grad_sim is what it would have been.  The flag clears itself with the
+ * next mkgnn_tail_fused* call whether that call defers or not.  MKGNN_TAIL_PROJECT_IN_PREPASS=0: requests are ignored. */
+int mkgnn_tail_defer_projection(int32_t on);
+/* diagnostics: launches since the library was loaded -- out[0] coefficient pre-passes with a projected source, out[1] projection
+ * launches that write grad_sim (made by the tail call or materialised later), out[2] projection launches for the dW1 partials only */
+int mkgnn_debug_tail_projection_launches(int64_t out[3]);
 /* The tail in evaluation mode, forward only (additive; the ABI version stays 8): pred_g = ffn( emb_g ) and emb_g of the formulas
  * above, no dropout, no loss, no gradient -- TWO launches: z = W1 sim on the matrix cores, then the forward phases of the training
  * tail's middle kernel with its work distribution and every summation order.  For the same inputs pred and emb are BIT FOR BIT

@@ -199,7 +199,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_task_head_workspace_bytes", "mkgnn_task_head_forward", "mkgnn_task_head_backward", "mkgnn_task_head_fused",
            "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks", "mkgnn_embed_cosine",
            "mkgnn_atom_contributions", "mkgnn_atom_contributions_workspace_bytes", "mkgnn_embed_max_cosine",
-           "mkgnn_embed_max_cosine_workspace_bytes", "mkgnn_select_rows")
+           "mkgnn_embed_max_cosine_workspace_bytes", "mkgnn_select_rows", "mkgnn_tail_defer_projection",
+           "mkgnn_debug_tail_projection_launches")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -280,6 +281,10 @@ def load() -> C.CDLL:
     lib.mkgnn_flat_copy.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     lib.mkgnn_tail_flush.restype = C.c_int
     lib.mkgnn_tail_flush.argtypes = [C.c_void_p]
+    lib.mkgnn_tail_defer_projection.restype = C.c_int
+    lib.mkgnn_tail_defer_projection.argtypes = [C.c_int32]
+    lib.mkgnn_debug_tail_projection_launches.restype = C.c_int
+    lib.mkgnn_debug_tail_projection_launches.argtypes = [C.POINTER(C.c_int64 * 3)]
     lib.mkgnn_rows_presplit.restype = C.c_int
     lib.mkgnn_rows_presplit.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.mkgnn_rows_split_supported.restype = C.c_int

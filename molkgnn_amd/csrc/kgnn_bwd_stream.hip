@@ -105,6 +105,13 @@ template <int OFF> __device__ __forceinline__ void lds_read_h16(uint32_t& dst, u
     asm volatile("ds_read_u16 %0, %1 offset:%2" : "=v"(dst) : "v"(byte_addr), "n"(OFF) : "memory");
 }
 
+template <int OFF> __device__ __forceinline__ f32x4 lds_read_raw128_at(uint32_t byte_addr) {      // (16-byte aligned address)
+    static_assert(OFF >= 0 && OFF < 65536 && OFF % 16 == 0, "ds_read offset field");
+    f32x4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(byte_addr), "n"(OFF) : "memory");
+    return v;
+}
+
 template <typename V> __device__ __forceinline__ void lds_fence(V& v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) : : "memory"); }
 
 template <int D, int A> __device__ __forceinline__ int perm_entry(int p) {
@@ -172,8 +179,16 @@ constexpr int PREP_RPB = MKGNN_PREP_RPB;                              // records
 // degree (the kernel is bound by its vector-memory instructions: TA busy 60 %), two of three of them redundant at degree 1 and
 // half of them at degree 2, the largest group.
 // CH: the degree keeps chirality signs (degree 4 of the last layer) -- otherwise their load is not issued at all.
-template <int NSRC, bool CH>
-__device__ __forceinline__ void coef_prepare_body(const BankStreamArgs& a, const int di) {
+// PJ: a projected source (BankStreamArgs.proj_dz; NSRC == 1 only, block-uniform like CH): the pair's dL/dsc is not loaded but
+// formed as d z[sel[n]] . W1[:, off + l] from the block's degree slice of W1 and the d z rows of its records' atoms, both staged
+// in LDS (pj_w1 [PJ_HP][PJ_LMAX], L columns used, zero beyond proj_H; pj_dz [PREP_RPB][16][PJ_LZ]).  The 32 terms go in the order of the matrix
+// instruction chain of block_project_bwd_mfma_kernel (kgnn_readout.hip), one fmaf per term from +0, so the records are those of
+// the materialised d sim.  The other instantiations are as they were.
+constexpr int PJ_HP = 32, PJ_LZ = PJ_HP + 4, PJ_LMAX = 64;
+template <int NSRC, bool CH, bool PJ = false>
+__device__ __forceinline__ void coef_prepare_body(const BankStreamArgs& a, const int di, [[maybe_unused]] float* pj_w1 = nullptr,
+                                                  [[maybe_unused]] float* pj_dz = nullptr) {
+    static_assert(!PJ || NSRC == 1, "a projected source stands for the focal atom's row");
     const BankStreamDeg& g = a.deg[di];
     const int tid = threadIdx.x;
     const int64_t blk = (int64_t)blockIdx.x - g.prep_blk0;
@@ -203,6 +218,30 @@ __device__ __forceinline__ void coef_prepare_body(const BankStreamArgs& a, const
 #pragma unroll
         for (int s = 0; s < NSRC; ++s) src[r][s] = a.through_nei ? g.nei[nc * D + s] : g.sel[nc];
     }
+    // (PJ) staging loads: this thread's 16-byte chunks of the records' d z rows (chunk tid & 7 of atom (tid >> 3) & 15 of record
+    // tid >> 7, + 2 per round) and its elements of the W1 slice -- issued with the loads below, stored once those are under way
+    constexpr int PJ_NST = PJ ? (PREP_RPB * 128 + 255) / 256 : 1, PJ_NW = PJ ? PJ_HP * PJ_LMAX / 256 : 1;
+    [[maybe_unused]] f32x4 pj_st[PJ_NST];
+    [[maybe_unused]] float pj_wv[PJ_NW];
+    [[maybe_unused]] int pj_lc[PREP_RPB];                  // the records' (clamped) kernel column of this thread
+    if constexpr (PJ) {
+#pragma unroll
+        for (int i = 0; i < PJ_NST; ++i) {
+            const int e = tid + 256 * i, r = (e >> 7) < PREP_RPB ? (e >> 7) : PREP_RPB - 1;
+            const int64_t rec = blk * PREP_RPB + r;
+            const int64_t rc = rec < nrec ? rec : nrec - 1;
+            const int64_t n = rc / g.nct * 16 + ((e >> 3) & 15);
+            const int64_t id = g.sel[n < g.n ? n : g.n - 1];
+            pj_st[i] = *(const f32x4*)(a.proj_dz + id * PJ_HP + 4 * (e & 7));
+        }
+#pragma unroll
+        for (int i = 0; i < PJ_NW; ++i) {
+            const int e = tid + 256 * i, ec = e < PJ_HP * g.L ? e : PJ_HP * g.L - 1;
+            const int h = ec / g.L, l = ec - h * g.L, hc = h < a.proj_H ? h : a.proj_H - 1;
+            const float w = a.proj_w1[(size_t)hc * a.proj_K + g.off + l];
+            pj_wv[i] = h < a.proj_H ? w : 0.f;
+        }
+    }
 #pragma unroll
     for (int r = 0; r < PREP_RPB; ++r) {
         const int64_t rec = blk * PREP_RPB + r;
@@ -213,16 +252,63 @@ __device__ __forceinline__ void coef_prepare_body(const BankStreamArgs& a, const
         const int64_t nc = n < g.n ? n : g.n - 1;
         const int l = ct * g.kpt + k, lc = l < g.L ? l : g.L - 1;
         const size_t o = (size_t)nc * g.L + lc;
-        float gs4[NSRC];
+        if constexpr (PJ) pj_lc[r] = lc;
+        if constexpr (!PJ) {
+            float gs4[NSRC];
 #pragma unroll
-        for (int s = 0; s < NSRC; ++s) gs4[s] = a.gout[src[r][s] * a.gs + g.off + lc];
-        gv[r] = gs4[0];
+            for (int s = 0; s < NSRC; ++s) gs4[s] = a.gout[src[r][s] * a.gs + g.off + lc];
+            gv[r] = gs4[0];
 #pragma unroll
-        for (int s = 1; s < NSRC; ++s) gv[r] += gs4[s];                  // (slot order, as before)
+            for (int s = 1; s < NSRC; ++s) gv[r] += gs4[s];              // (slot order, as before)
+        }
         const mkgnn_f32x4 pr = pair_load(g.pair, o);
         idx[r] = pair_index(pr);
         ch[r] = CH ? (int)chp[o] : 1;
         S[r] = pr[0]; C[r] = pr[1]; Ed[r] = pr[2];
+    }
+    if constexpr (PJ) {
+#pragma unroll
+        for (int i = 0; i < PJ_NST; ++i) {
+            const int e = tid + 256 * i;
+            if (e < PREP_RPB * 128) *(f32x4*)&pj_dz[(e >> 3) * PJ_LZ + 4 * (e & 7)] = pj_st[i];
+        }
+#pragma unroll
+        for (int i = 0; i < PJ_NW; ++i) {
+            const int e = tid + 256 * i;
+            if (e < PJ_HP * g.L) pj_w1[e / g.L * PJ_LMAX + e % g.L] = pj_wv[i];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < PREP_RPB; ++r) {
+            // (raw LDS reads, sixteen terms at a time: left to itself the compiler hoists the reads of all four records to the
+            // front -- 280 registers, one wave per SIMD, in a kernel that lives on its loads in flight)
+            const uint32_t dz_b = (uint32_t)(uintptr_t)(pj_dz + (r * 16 + atom) * PJ_LZ);
+            const uint32_t w_b = (uint32_t)(uintptr_t)(pj_w1 + pj_lc[r]);
+            // hidden unit 16 jh + 4 q + c is k-lane q of matrix instruction (jh, c): instructions in order, k ascending inside one
+            float acc = 0.f;
+            bs::static_for<0, PJ_HP / 16>([&](auto jhc) {
+                constexpr int jh = decltype(jhc)::value;
+                f32x4 d[4];
+                float w[16];
+                bs::static_for<0, 4>([&](auto qc) {
+                    constexpr int q = decltype(qc)::value;
+                    d[q] = bs::lds_read_raw128_at<4 * (16 * jh + 4 * q)>(dz_b);
+                });
+                bs::static_for<0, 16>([&](auto ic) {          // (a fixed row pitch: the offsets are immediates, one address register)
+                    constexpr int i = decltype(ic)::value;
+                    w[i] = bs::lds_read_raw_at<4 * (16 * jh + i) * PJ_LMAX>(w_b);
+                });
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]),
+                             "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]), "+v"(w[8]), "+v"(w[9]), "+v"(w[10]), "+v"(w[11]),
+                             "+v"(w[12]), "+v"(w[13]), "+v"(w[14]), "+v"(w[15]) : : "memory");
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc = fmaf(d[q][c], w[4 * q + c], acc);
+                asm volatile("" : "+v"(acc) : : "memory");       // (... and their sixteen terms before the next reads: or they all sink below)
+            });
+            gv[r] = acc;
+        }
     }
     float p0 = 0.f, p1 = 0.f, p2 = 0.f;
     constexpr int NEM = (PREP_RPB + 1) / 2;
@@ -304,6 +390,17 @@ __global__ void __launch_bounds__(256) coef_prepare_kernel(BankStreamArgs a) {
         case 3: coef_prepare_body<3, false>(a, di); break;
         default: coef_prepare_body<4, false>(a, di); break;
     }
+}
+
+// ... with a projected source (BankStreamArgs.proj_dz): a kernel of its own, so that the one above keeps its code and its LDS
+__global__ void __launch_bounds__(256) coef_prepare_proj_kernel(BankStreamArgs a) {
+    __shared__ __align__(16) float pj_w1[PJ_HP * PJ_LMAX];
+    __shared__ __align__(16) float pj_dz[PREP_RPB * 16 * PJ_LZ];
+    int di = 0;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) if (a.deg[k].prep_blocks > 0 && (int)blockIdx.x >= a.deg[k].prep_blk0) di = k;
+    if (a.deg[di].chir) coef_prepare_body<1, true, true>(a, di, pj_w1, pj_dz);
+    else coef_prepare_body<1, false, true>(a, di, pj_w1, pj_dz);
 }
 
 // ------------------------------------------------------------ main body ---
@@ -777,6 +874,7 @@ extern "C" int mkgnn_debug_set_bank_stream_stamps(void* device_ptr) {
 
 // Same conditions as the forward's streamed kernel (the pre-pass and the slab chunk capacity added).
 bool bank_stream_rows_split_supported(int F) { return (F + 15) / 16 <= 7 && bwd_split_mode() != 0; }
+bool bank_stream_projection_supported(int H, int HP, int L) { return HP == PJ_HP && H >= 1 && H <= PJ_HP && L >= 0 && L <= PJ_LMAX; }
 bool bank_stream_supported(int d, int F, int E, int L, int64_t n_atoms, int64_t x_stride, const float* e_unit) {
     return stream_forward_supported(d, F, E, L, n_atoms, x_stride, x_stride, e_unit);
 }
@@ -898,6 +996,13 @@ void plan_backward_bank_stream(const BwdArgs a4[4], const bool use[4], const flo
 // the pre-pass: its records feed the rows kernel and the bank kernel
 hipError_t launch_coef_prepare(const BankStreamLaunch& p, hipStream_t st) {
     if (p.prep_blocks == 0) return hipSuccess;
+    if (p.a.proj_dz) {                                   // (the caller has checked bank_stream_projection_supported)
+        if (p.a.through_nei || p.a.proj_HP != PJ_HP || p.a.proj_H < 1 || p.a.proj_H > PJ_HP) return hipErrorInvalidValue;
+        for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) if (p.a.deg[i].prep_blocks > 0 && p.a.deg[i].L > PJ_LMAX) return hipErrorInvalidValue;
+        g_tail_projection_launches[0].fetch_add(1);
+        coef_prepare_proj_kernel<<<p.prep_blocks, 256, 0, st>>>(p.a);
+        return hipGetLastError();
+    }
     coef_prepare_kernel<<<p.prep_blocks, 256, 0, st>>>(p.a);
     return hipGetLastError();
 }

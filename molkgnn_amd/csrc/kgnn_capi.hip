@@ -722,6 +722,24 @@ int mkgnn_kernelsetconv_backward(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE]
     ForkJoin fj;
     e = fj.begin(st, !g_time_bwd.load());            // (timed for bench.py: everything on the caller's stream)
     if (e != hipSuccess) return api_hip_fail("stream fork", e);
+    // a projection the fused tail left pending (mkgnn_tail_defer_projection): taken over when this call is the reader of its
+    // d sim and runs the streamed kernels beside a forked helper; anything else gets the launch that was left out, here and now
+    TailProjection tp;
+    bool project = false;
+    if (pending_tail_projection(&tp)) {
+        project = grad_out == tp.dsim && grad_out_stride == tp.dss && streamed && rows_streamed && !through_nei && defer_bank && fj.p != nullptr &&
+                  any_bank && K == tp.K;
+        for (int i = 0; i < 4 && project; ++i) {
+            const bool same = L[i] == tp.L[i] && bank_a[i].off == tp.off[i] && buckets[i].count == tp.cnt[i] &&
+                              (tp.cnt[i] == 0 || buckets[i].selected_index == tp.sel[i]);
+            const bool wanted = tp.cnt[i] > 0 && tp.L[i] > 0;        // (the projection kernel writes these rows of d sim)
+            project = same && (!wanted || bank_use[i]) && bank_stream_projection_supported(tp.H, tp.HP, L[i]);
+        }
+        if (!project) {
+            e = launch_pending_tail_projection(st, true);
+            if (e != hipSuccess) return api_hip_fail("deferred tail projection launch", e);
+        }
+    }
     bool bank_on_main = false;                       // some bank gradient was computed on the caller's stream
     for (int i = 0; i < 4; ++i) {                    // (the launch order of the degrees makes no measurable difference)
         const int d = i + 1;
@@ -770,6 +788,16 @@ int mkgnn_kernelsetconv_backward(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE]
         // the rows kernel here and the bank kernel on the helper
         plan_backward_bank_stream(bank_a, bank_use, e_unit4, coefq4, nchunk4, ntheta4, through_nei, &bsl);
         bsl.x_split = rows_split ? 1 : 0;
+        if (project) { bsl.a.proj_dz = tp.dz; bsl.a.proj_w1 = tp.w1; bsl.a.proj_H = tp.H; bsl.a.proj_HP = tp.HP; bsl.a.proj_K = tp.K; }
+        if (project && switches().tail_project_in_prepass >= 2) {
+            // the dW1 half of the projection (its slabs are what the deferred reduction sums) needs d z and sim only: the helper
+            // is forked in FRONT of the pre-pass for it, so that it runs beside the pre-pass and not beside the rows kernel, in
+            // front of the reduction and the bank kernel, which it held up there (47 us; measured)
+            e = fj.refork(1);
+            if (e != hipSuccess) return api_hip_fail("stream fork", e);
+            e = launch_pending_tail_projection(fj.p->aux[0], false);
+            if (e != hipSuccess) return api_hip_fail("deferred tail projection launch", e);
+        }
         { BwdTimer t(st, 0); e = launch_coef_prepare(bsl, st); }
         if (e != hipSuccess) return api_hip_fail("coefficient pre-pass launch", e);
         e = fj.refork(1);
@@ -783,6 +811,10 @@ int mkgnn_kernelsetconv_backward(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE]
     if (any_bank) {
         hipStream_t st_bank = fj.stream(1, &e);      // the helper (the caller's stream when nothing is forked)
         if (e != hipSuccess) return api_hip_fail("stream fork", e);
+        if (project) {                               // (no-op where the early fork in front of the pre-pass has launched it)
+            e = launch_pending_tail_projection(st_bank, false);
+            if (e != hipSuccess) return api_hip_fail("deferred tail projection launch", e);
+        }
         if (st_bank != st) {                         // a fused tail's deferred reduction rides in front of the bank kernel
             e = launch_pending_tail_reduce(st_bank);
             if (e != hipSuccess) return api_hip_fail("deferred tail reduction launch", e);

@@ -158,6 +158,7 @@ int bank_blocks_for(int d, int64_t n);
 hipError_t launch_backward_bank_fused(const BwdArgs a4[4], const bool use[4], int nchunk_out[4], int ntheta_out[4], hipStream_t st);
 // kgnn_bwd_stream.hip: streamed MFMA bank-gradient kernel (+ its coefficient pre-pass), all degrees in one launch
 bool bank_stream_supported(int d, int F, int E, int L, int64_t n_atoms, int64_t x_stride, const float* e_unit);
+bool bank_stream_projection_supported(int H, int HP, int L);   // the pre-pass with a projected source (BankStreamArgs.proj_dz)
 bool bank_stream_rows_split_supported(int F);        // pre-split atom rows: KC <= 7 and the split-fp16 products on
 struct BankStreamDeg {
     const int64_t* sel; const int64_t* nei; const float* e_unit;
@@ -182,6 +183,11 @@ struct BankStreamArgs {
     uint16_t grp_count[FUSED_MAX_GROUPS];
     uint8_t blk_group[FUSED_MAX_BLOCKS];
     uint16_t blk_rank[FUSED_MAX_BLOCKS];
+    // a projected source (the fused tail's pending projection; proj_dz == null: none -- only with through_nei == 0): instead of
+    // gout[sel[n] * gs + off + l] a pair's dL/dsc is the dot product of row sel[n] of proj_dz ([n_atoms, proj_HP]) with column
+    // off + l of proj_w1 ([proj_H, proj_K]), in the term order of block_project_bwd_mfma_kernel's matrix instructions
+    const float* proj_dz; const float* proj_w1;
+    int proj_H, proj_HP, proj_K;
 };
 
 // kgnn_tail.hip: the middle of the fused tail (mkgnn_tail_fused, kgnn_readout.hip) -- per chunk of whole molecules, on H-wide rows
@@ -205,6 +211,22 @@ constexpr int TAIL_B1 = 0, TAIL_W2 = 32, TAIL_B2 = 32 + 1024, TAIL_WH = TAIL_B2 
               TAIL_SLAB = (TAIL_LOSS + 1 + 3) / 4 * 4;
 // the fused tail's deferred reduction (mkgnn_tail_args.defer_reduce): launched on `st` if one is pending on this thread
 hipError_t launch_pending_tail_reduce(hipStream_t st, bool* launched = nullptr);
+// the fused tail's deferred projection (mkgnn_tail_defer_projection): d sim[n, block(n)] = d z[n] . W1[:, block(n)] and the dW1
+// slabs, left to the last convolution's backward.  What that backward needs to know to take it over:
+struct TailProjection {
+    const float* dsim; int64_t dss;         // where the projection kernel would write: the backward's grad_out when it is the reader
+    const float* dz; const float* w1;       // [n_atoms, HP], [H, K]
+    int H, HP, K;
+    int off[MKGNN_MAX_DEGREE], L[MKGNN_MAX_DEGREE];
+    const int64_t* sel[MKGNN_MAX_DEGREE]; int64_t cnt[MKGNN_MAX_DEGREE];
+};
+bool pending_tail_projection(TailProjection* out);           // one is pending on this device (it stays pending)
+// launches the pending projection kernel on `st` and clears the slot (no-op: none).  full: d sim and the dW1 slabs -- the launch
+// the tail left out; else the dW1 slabs only (the reader computes d sim itself)
+hipError_t launch_pending_tail_projection(hipStream_t st, bool full);
+// debug counters: [0] pre-pass launches with a projected source, [1] full projection launches of the fused tail (made at once or
+// materialised later), [2] dW1-only launches
+extern std::atomic<long long> g_tail_projection_launches[3];
 int tail_group_size(int64_t n_loss_mols);
 int tail_middle_blocks(int64_t n_loss_mols);
 // loss_kind: MKGNN_LOSS_*; a.rdrop_p > 0: the instantiations with the readout's dropout mask

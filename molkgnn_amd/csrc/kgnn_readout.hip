@@ -1074,6 +1074,33 @@ int mkgnn_readout_blocks_backward(const mkgnn_readout_params* p, const float* si
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }
 
+// (on == false: none) mkgnn_tail_defer_projection: step (3) of a fused tail call, left to the last convolution's backward -- its
+// coefficient pre-pass forms d sim itself and the dW1 half runs on the helper stream (launch_pending_tail_projection) -- or to
+// whoever flushes first.  Per device and under the pending reduction's mutex, for its reasons.
+struct PendingProject { BlockProjArgs b; int tpw; int64_t nb; size_t lds; bool on; };
+static PendingProject g_pending_project_dev[16];
+static bool g_defer_projection_dev[16];                  // the one-shot request of mkgnn_tail_defer_projection
+static int pending_device() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+    return dev;
+}
+// blocks of block_project_bwd_mfma_kernel for the buckets in b: 4 * tiles_per_wave tiles each, at most 2 * RO_ATOM_BLOCKS (the slabs)
+static int64_t project_bwd_blocks(const BlockProjArgs& b, int* tpw_out, int64_t nb_of[MKGNN_MAX_DEGREE]) {
+    int64_t tiles_all = 0;
+    for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) if (b.L[i] > 0) tiles_all += (b.cnt[i] + 15) / 16;
+    int tpw = (int)((tiles_all + 4 * (2 * RO_ATOM_BLOCKS - 4) - 1) / (4 * (2 * RO_ATOM_BLOCKS - 4)));
+    if (tpw < 1) tpw = 1;
+    int64_t nb = 0;
+    for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) {
+        const int64_t tiles = (b.cnt[i] + 15) / 16, per = 4 * (int64_t)tpw;
+        nb_of[i] = b.L[i] > 0 ? (tiles + per - 1) / per : 0;
+        nb += nb_of[i];
+    }
+    *tpw_out = tpw;
+    return nb;
+}
+
 // ---- the fused tail (ABI v6; kgnn_tail.hip): project | per-molecule middle | project^T + dW1 | one reduction ----
 struct TailWs { size_t z, dz, slab_atoms, slab_tail, total; int slab_atoms_stride; };
 static TailWs tail_ws(const ReadoutDims& d, int64_t n_atoms, int64_t n_mols) {
@@ -1108,7 +1135,8 @@ static int project_into_workspace(const char* who, const mkgnn_readout_params* r
     int64_t n_focal = 0;
     if (int rc = check_blocks(who, ro, num_kernels, buckets, n_atoms, sim_stride, sim, b, d, &n_focal)) return rc;
     if (!ws || ws_bytes < total) return api_fail("%s: workspace too small (%zu < %zu)", who, ws_bytes, total);
-    hipError_t e = launch_pending_tail_reduce(st);
+    hipError_t e = launch_pending_tail_projection(st, true);       // (it reads the d z rows and fills the slabs the reduction sums)
+    if (e == hipSuccess) e = launch_pending_tail_reduce(st);
     if (e == hipSuccess) e = project_blocks(b, d, n_focal, sim, sim_stride, n_atoms, (float*)ws, st);
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }
@@ -1170,23 +1198,24 @@ static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void*
     if (e != hipSuccess) return api_hip_fail(who, e);
     // (3) d sim[block] = W1[:, block]^T d z,  dW1 partials   (as mkgnn_readout_blocks_backward)
     b.dz = dz; b.dsim = p->grad_sim; b.dss = p->grad_sim_stride;
-    int64_t tiles_all = 0;
-    for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) if (b.L[i] > 0) tiles_all += (b.cnt[i] + 15) / 16;
-    int tpw = (int)((tiles_all + 4 * (2 * RO_ATOM_BLOCKS - 4) - 1) / (4 * (2 * RO_ATOM_BLOCKS - 4)));
-    if (tpw < 1) tpw = 1;
-    int64_t nb_of[MKGNN_MAX_DEGREE], nb = 0;
-    for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) {
-        const int64_t tiles = (b.cnt[i] + 15) / 16, per = 4 * (int64_t)tpw;
-        nb_of[i] = b.L[i] > 0 ? (tiles + per - 1) / per : 0;
-        nb += nb_of[i];
-    }
+    int tpw = 1;
+    int64_t nb_of[MKGNN_MAX_DEGREE];
+    const int64_t nb = project_bwd_blocks(b, &tpw, nb_of);
     if (nb > 2 * RO_ATOM_BLOCKS) return api_fail("%s: internal: %lld blocks for %d slabs", who, (long long)nb, 2 * RO_ATOM_BLOCKS);
     float* const slab_atoms = (float*)((char*)ws + w.slab_atoms);
     b.slab = slab_atoms; b.slab_stride = w.slab_atoms_stride;
-    if (nb > 0) {
-        const size_t img = (size_t)4 * (16 * (d.HP + 4) + 16 * 68);
-        const size_t lds = ((size_t)d.HP * 68 + (img > 4096 ? img : 4096)) * 4;
-        block_project_bwd_mfma_kernel<2><<<(unsigned)nb, 256, lds, st>>>(b, tpw);
+    const size_t proj_img = (size_t)4 * (16 * (d.HP + 4) + 16 * 68);
+    const size_t proj_lds = ((size_t)d.HP * 68 + (proj_img > 4096 ? proj_img : 4096)) * 4;
+    bool defer_proj = false;                             // mkgnn_tail_defer_projection: one-shot, and only beside a deferred reduction
+    {
+        std::lock_guard<std::mutex> lock(g_pending_reduce_mutex);
+        bool& want = g_defer_projection_dev[pending_device()];
+        defer_proj = want && p->defer_reduce && nb > 0 && switches().tail_project_in_prepass != 0;
+        want = false;
+    }
+    if (nb > 0 && !defer_proj) {
+        g_tail_projection_launches[1].fetch_add(1);
+        block_project_bwd_mfma_kernel<2><<<(unsigned)nb, 256, proj_lds, st>>>(b, tpw);
     }
     // (4) every partial slab -> its gradient, the loss; the dropout generator advances (once, for either dropout or both)
     SlabReduceArgs r{};
@@ -1226,11 +1255,31 @@ static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void*
         std::lock_guard<std::mutex> lock(g_pending_reduce_mutex);
         PendingReduce* slot = pending_reduce_slot();
         slot->r = r; slot->blk = blk;
+        if (defer_proj) {
+            PendingProject& pp = g_pending_project_dev[pending_device()];
+            pp.b = b; pp.tpw = tpw; pp.nb = nb; pp.lds = proj_lds; pp.on = true;
+        }
         return 0;
+    }
+    if (defer_proj) {                                    // (no reduction to ride with after all: blk == 0)
+        g_tail_projection_launches[1].fetch_add(1);
+        block_project_bwd_mfma_kernel<2><<<(unsigned)nb, 256, proj_lds, st>>>(b, tpw);
     }
     if (blk > 0) slab_reduce_kernel<<<blk, 256, 0, st>>>(r);
     e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+int mkgnn_tail_defer_projection(int32_t on) {
+    std::lock_guard<std::mutex> lock(g_pending_reduce_mutex);
+    g_defer_projection_dev[pending_device()] = on != 0;
+    return 0;
+}
+
+int mkgnn_debug_tail_projection_launches(int64_t out[3]) {
+    if (!out) return api_fail("mkgnn_debug_tail_projection_launches: null pointer");
+    for (int i = 0; i < 3; ++i) out[i] = (int64_t)g_tail_projection_launches[i].load();
+    return 0;
 }
 
 int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* stream) {
@@ -1348,11 +1397,36 @@ hipError_t launch_pending_tail_reduce(hipStream_t st, bool* launched) {
     if (launched) *launched = true;
     return hipGetLastError();
 }
+
+std::atomic<long long> g_tail_projection_launches[3];
+
+bool pending_tail_projection(TailProjection* out) {
+    std::lock_guard<std::mutex> lock(g_pending_reduce_mutex);
+    const PendingProject& pp = g_pending_project_dev[pending_device()];
+    if (!pp.on) return false;
+    const BlockProjArgs& b = pp.b;
+    out->dsim = b.dsim; out->dss = b.dss; out->dz = b.dz; out->w1 = b.w1; out->H = b.H; out->HP = b.HP; out->K = b.K;
+    for (int i = 0; i < MKGNN_MAX_DEGREE; ++i) { out->off[i] = b.off[i]; out->L[i] = b.L[i]; out->sel[i] = b.sel[i]; out->cnt[i] = b.cnt[i]; }
+    return true;
+}
+
+hipError_t launch_pending_tail_projection(hipStream_t st, bool full) {
+    std::lock_guard<std::mutex> lock(g_pending_reduce_mutex);
+    PendingProject& pp = g_pending_project_dev[pending_device()];
+    if (!pp.on) return hipSuccess;
+    pp.on = false;
+    BlockProjArgs b = pp.b;
+    if (!full) b.dsim = nullptr;
+    g_tail_projection_launches[full ? 1 : 2].fetch_add(1);
+    block_project_bwd_mfma_kernel<2><<<(unsigned)pp.nb, 256, pp.lds, st>>>(b, pp.tpw);
+    return hipGetLastError();
+}
 }  // namespace mkgnn
 }
 
 extern "C" int mkgnn_tail_flush(void* stream) {
-    const hipError_t e = launch_pending_tail_reduce((hipStream_t)stream);
+    hipError_t e = launch_pending_tail_projection((hipStream_t)stream, true);
+    if (e == hipSuccess) e = launch_pending_tail_reduce((hipStream_t)stream);
     return e == hipSuccess ? 0 : api_hip_fail("mkgnn_tail_flush", e);
 }
 

@@ -1112,12 +1112,14 @@ def tail_supported(K: int, H: int, G: int, blocks) -> bool:
 # gradient waits for.  Only ``train.training_step`` / ``train.CapturedSteps`` / bench.py open such a region, around
 # ``loss -> backward`` as ONE unit, and flush at its end; ``model.loss`` anywhere else returns a finished loss as before.
 _DEFER_TAIL_REDUCE = False
+_TAIL_PROJECT_NEXT = False   # the next _TailFn.forward may also leave its d sim projection to the last convolution's backward (tail_loss)
 _TAIL_HELD: list = []        # every tensor a pending reduction still reads or writes: referenced until the flush (the reduction runs on
                              # another stream, later than the allocator's stream-ordered reuse of a freed block would allow)
 
 
 def tail_flush(device) -> None:
-    """``mkgnn_tail_flush``: a reduction the fused tail left pending on this thread is launched on the current stream now."""
+    """``mkgnn_tail_flush``: what the fused tail left pending on this device -- a deferred projection, then the deferred reduction
+    -- is launched on the current stream now."""
     try:
         with torch.cuda.device(device):
             _lib.check(_lib.load().mkgnn_tail_flush(_lib.stream_ptr(device)), "mkgnn_tail_flush")
@@ -1182,6 +1184,8 @@ class _TailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind=_lib.LOSS_BCE_MEAN, p_readout=0.0):
+        global _TAIL_PROJECT_NEXT
+        project, _TAIL_PROJECT_NEXT = _TAIL_PROJECT_NEXT, False         # (tail_loss's one-shot: see there)
         lib = _lib.load()
         _lib.require_gpu_tensor(sim, "sim_sc")
         n, K = sim.shape
@@ -1223,6 +1227,11 @@ class _TailFn(torch.autograd.Function):
         ctx.dev = dev
         with torch.cuda.device(dev):
             ws = _tail_workspace(dev, int(lib.mkgnn_tail_workspace_bytes(K, H, G, n, seg.size)))
+            if ctx.deferred and project:
+                # the projection d sim = d z . W1[:, block] too (one-shot; MKGNN_TAIL_PROJECT_IN_PREPASS=0: ignored): the last
+                # convolution's backward, gsim's only reader, forms it in its coefficient pre-pass and gsim is never written --
+                # anything else that comes first (tail_flush, tail_score, another loss) makes the launch that was left out
+                _lib.check(lib.mkgnn_tail_defer_projection(1), "mkgnn_tail_defer_projection")
             if p_readout > 0.0:
                 _lib.check(lib.mkgnn_tail_fused_readout_dropout(ctypes.byref(a), float(p_readout), ws.data_ptr(), ws.numel(),
                                                                 _lib.stream_ptr(dev)), "mkgnn_tail_fused_readout_dropout")
@@ -1232,7 +1241,10 @@ class _TailFn(torch.autograd.Function):
         if ctx.deferred:
             # (their STORAGES: a second reference to a gradient TENSOR would make autograd copy it into .grad instead of adopting
             # it -- a copy made before the reduction has written it)
-            _TAIL_HELD.extend(t.untyped_storage() for t in (loss, gw1, gb1, gw2, gb2, gwh, gbh, rng, used, ws) if t is not None)
+            # (the pending projection: its late dW1 launch on the helper stream reads d z -- the workspace --, sim and W1, a
+            # materialising one writes gsim; sim is the convolution node's, W1 a parameter -- held all the same)
+            _TAIL_HELD.extend(t.untyped_storage() for t in (loss, gw1, gb1, gw2, gb2, gwh, gbh, rng, used, ws, gsim, sim, w1c)
+                              if t is not None)
         ctx.unit = (gsim, gw1, gb1, gw2, gb2, gwh.reshape(wh.shape), gbh)
         ctx.pred, ctx.rng_used = pred, used
         return loss
@@ -1246,6 +1258,8 @@ class _TailFn(torch.autograd.Function):
         params, ctx.params = ctx.params, None
         # a deferred reduction has not written the parameter gradients yet: fine as long as nothing on this stream touches them
         # before the region's flush -- a scale by the incoming gradient or an accumulation into an existing .grad would
+        # (the flush also materialises a pending projection: gsim is written before it is scaled or handed to anyone but the
+        # last convolution's backward, which takes the projection over itself)
         if ctx.deferred and (not _is_unit_seed(grad_loss) or torch.is_grad_enabled()
                              or any(p is not None and p.grad is not None for p in params)):
             tail_flush(ctx.dev)
@@ -1253,6 +1267,15 @@ class _TailFn(torch.autograd.Function):
             gl = grad_loss.reshape(()).float()
             grads = tuple(None if g is None else g * gl for g in grads)
         return (*grads, None, None, None, None, None, None, None, None)
+
+
+def _sole_reader_is_the_convolution(sim: torch.Tensor) -> bool:
+    """``sim`` comes straight out of a kernel convolution (its block rows, not propagated) and nothing is in the way of its
+    gradient: no hook on it and no ``retain_grad`` -- the gradient the tail hands back goes to that convolution's backward and
+    nowhere else, provided the caller (``MolKGNNNet.forward``) feeds ``sim`` to nothing but the tail."""
+    fn = sim.grad_fn
+    return (fn is not None and type(fn).__name__ == "_KernelSetConvFnBackward" and not sim._backward_hooks
+            and not getattr(sim, "retains_grad", False))
 
 
 def tail_loss(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torch.nn.Linear, ffn: torch.nn.Linear,
@@ -1268,8 +1291,14 @@ def tail_loss(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torc
         raise ValueError("tail_loss needs a one-output linear layer and one target per (leading) molecule")
     if not 0.0 <= readout_dropout_p < 1.0:
         raise ValueError(f"readout dropout probability {readout_dropout_p} outside [0, 1)")
-    return _TailFn.apply(sim, lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight, ffn.bias, target, seg, plan,
-                         tuple(blocks), float(dropout_p), n_rows, kind, float(readout_dropout_p))
+    # (what only this caller can see -- inside the operator `sim` has no history -- goes to the operator's forward beside its arguments)
+    global _TAIL_PROJECT_NEXT
+    _TAIL_PROJECT_NEXT = bool(_DEFER_TAIL_REDUCE and _sole_reader_is_the_convolution(sim))
+    try:
+        return _TailFn.apply(sim, lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight, ffn.bias, target, seg, plan,
+                             tuple(blocks), float(dropout_p), n_rows, kind, float(readout_dropout_p))
+    finally:
+        _TAIL_PROJECT_NEXT = False
 
 
 # MKGNN_SCORE_TAIL=0: GNNModel.predict runs the separate operators (readout_blocks, dropout, head) as before it existed (A/B)
