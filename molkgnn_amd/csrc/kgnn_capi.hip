@@ -102,6 +102,12 @@ struct ForkJoin {
         }
         return p->aux[i];
     }
+    // move the fork point behind everything enqueued on the caller's stream so far, for helpers that have not been taken yet
+    // (begin() recorded it; inside a capture it is recorded where a helper is first needed anyway)
+    hipError_t fork_here() {
+        if (!p || two_way) return hipSuccess;
+        return hipEventRecord(p->fork, main);
+    }
     // order the helper after everything enqueued on the caller's stream so far (a second fork point)
     hipError_t refork(int slot) {
         if (!p || slot == 0) return hipSuccess;
@@ -738,6 +744,10 @@ int mkgnn_kernelsetconv_backward(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE]
         if (!project) {
             e = launch_pending_tail_projection(st, true);
             if (e != hipSuccess) return api_hip_fail("deferred tail projection launch", e);
+            // it writes the d sim every degree's kernels read, and the helpers' fork point was recorded in front of it: a degree
+            // on a helper stream (generic or LDS kernels) would read grad_out before it is written
+            e = fj.fork_here();
+            if (e != hipSuccess) return api_hip_fail("stream fork", e);
         }
     }
     bool bank_on_main = false;                       // some bank gradient was computed on the caller's stream
