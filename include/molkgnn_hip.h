@@ -1076,6 +1076,40 @@ int mkgnn_embed_max_cosine(const float* emb, int64_t emb_stride, int64_t n_rows,
 int mkgnn_select_rows(const float* scores, const int32_t* ids, const float* key, int32_t B, const int32_t* n_valid,
                       const float* bounds, float* out_scores, int32_t* out_ids, int32_t* n_kept, void* stream);
 
+/* ---- diverse hits (additive; the ABI version stays 8): leader clustering of a ranked list -- the best molecule of every chemical
+ * series among the top of a screen, and the series every other hit belongs to.  emb [n_rows, H] (emb_stride >= H, RAW) holds the
+ * embeddings in RANK ORDER, best first.  The similarity is S[i, p] for p <= i: the float32 value mkgnn_embed_cosine writes for
+ * row i as the ROW and row p as the QUERY, BIT FOR BIT -- (dot * inv(e_i)) * inv(e_p); the orientation matters, the two
+ * multiplications do not commute in their last bit.  Only the lower triangle and the diagonal are read.  Walk i = 0, 1, ...:
+ *   1. S[i, i] is NaN (a NaN, infinite or overflowing row): row i is never picked and covers nothing -- leader[i] = -1,
+ *      leader_sim[i] = NaN -- whatever its similarity to a pick is
+ *   2. otherwise let p be the FIRST pick so far, in pick order, with S[i, p] > max_sim (strict: a similarity equal to max_sim
+ *      does not cover, a NaN never does): row i is covered, leader[i] = p (a row index), leader_sim[i] = S[i, p]
+ *   3. otherwise, while fewer than k_max picks exist, row i becomes a pick: it is appended to picks, leader[i] = i,
+ *      leader_sim[i] = S[i, i]
+ *   4. otherwise the list is full and nothing covers the row: leader[i] = -1, leader_sim[i] = NaN
+ * Rows behind the last pick are still assigned to the picks that cover them, so the cluster sizes count the whole list.
+ * Outputs, all contiguous: picks int32 [k_max] (unused slots -1), *n_picks, leader int32 [n_rows], leader_sim float32 [n_rows];
+ * nothing else is written outside the workspace.  They must not overlap emb, the workspace or each other (rejected).
+ *
+ * The rows go in tiles of 1 024 in rank order: one workgroup decides a tile (one thread per row, the alive
+ * set as one ballot word per wave), then a grid-wide launch lets every row behind the tile meet the picks the tile added; the
+ * pick count lives in device memory.  1 + 2 * tiles - 1 launches on `stream`, capturable, no host round trip, no atomics on
+ * global memory, no state between calls; the inverse norms and S[i, i] are computed inside the call, so a captured call follows
+ * new contents of emb.  The result is a function of emb, max_sim and k_max alone: not of the tile size, the stride or the grid.
+ * The workspace (4-byte aligned, mkgnn_diverse_pick_workspace_bytes(n_rows) bytes -- 8 per row and 16 more; 0 for rejected sizes)
+ * needs no initialisation.
+ *
+ * Limits: 1 <= H <= 64; 1 <= n_rows <= MKGNN_DIVERSE_MAX_ROWS (2^20: the selection is quadratic in the worst case -- every row a
+ * pick -- and every index fits an int); 1 <= k_max <= n_rows; max_sim finite.  n_rows == 0 is a no-op that returns 0, even with
+ * null pointers.  Anything else -- a limit, a NaN or infinite max_sim, a stride below H, a null pointer, a workspace that is too
+ * small or misaligned, overlapping buffers -- returns non-zero with mkgnn_last_error set, before any launch. */
+#define MKGNN_DIVERSE_MAX_ROWS 1048576
+size_t mkgnn_diverse_pick_workspace_bytes(int64_t n_rows);
+int mkgnn_diverse_pick(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, float max_sim, int32_t k_max,
+                       int32_t* picks, int32_t* n_picks, int32_t* leader, float* leader_sim, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,18 @@ MAX_COSINE_MAX_REFS, MAX_COSINE_MAX_H = 1 << 20, 64     # MKGNN_MAX_COSINE_MAX_R
 # tile, the most parts a launch splits the references into, the blocks it aims at; the slots of one pass of mkgnn_select_rows
 MAX_COSINE_ROWS, MAX_COSINE_TILE, MAX_COSINE_MAX_PARTS, MAX_COSINE_TARGET_BLOCKS = 128, 32, 256, 2048
 SELECT_ROWS_PASS = 1024
+DIVERSE_MAX_ROWS, DIVERSE_MAX_H = 1 << 20, 64           # MKGNN_DIVERSE_MAX_ROWS, mkgnn_diverse_pick's widest embedding
+# kgnn_diverse.hip's tiling (DV_COVER_ROWS, DV_COVER_TILE): rows per block and picks per LDS tile of the cover launch
+DIVERSE_COVER_ROWS, DIVERSE_COVER_TILE = 128, 32
+
+
+def diverse_tile(H: int) -> int:
+    """``DV_TILE`` of ``mkgnn_diverse_pick`` for an embedding of width ``H`` (``DvTile``, kgnn_diverse.hip): the rows one workgroup
+    decides per launch.  It is chosen per padded width (32 or 64 columns) from the compiler's resource report; both widths take
+    1 024.  The result of a call does not depend on it; the tests place their shapes around it."""
+    if not 1 <= int(H) <= DIVERSE_MAX_H:
+        raise ValueError(f"H = {H} outside [1, {DIVERSE_MAX_H}]")
+    return {32: 1024, 64: 1024}[32 if int(H) <= 32 else 64]
 
 
 def max_cosine_split(n_rows: int, R: int):
@@ -200,7 +212,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks", "mkgnn_embed_cosine",
            "mkgnn_atom_contributions", "mkgnn_atom_contributions_workspace_bytes", "mkgnn_embed_max_cosine",
            "mkgnn_embed_max_cosine_workspace_bytes", "mkgnn_select_rows", "mkgnn_tail_defer_projection",
-           "mkgnn_debug_tail_projection_launches")
+           "mkgnn_debug_tail_projection_launches", "mkgnn_diverse_pick", "mkgnn_diverse_pick_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -406,6 +418,10 @@ def load() -> C.CDLL:
     # stable compaction by a key: (scores, ids, key, B, n_valid, bounds, out_scores, out_ids, n_kept, stream)
     lib.mkgnn_select_rows.restype = C.c_int
     lib.mkgnn_select_rows.argtypes = [P, P, P, I32, P, P, P, P, P, P]
+    lib.mkgnn_diverse_pick_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_diverse_pick_workspace_bytes.argtypes = [I64]
+    lib.mkgnn_diverse_pick.restype = C.c_int
+    lib.mkgnn_diverse_pick.argtypes = [P, I64, I64, I32, C.c_float, I32, P, P, P, P, P, C.c_size_t, P]
     lib.mkgnn_rf_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_rf_workspace_bytes.argtypes = [I64]
     lib.mkgnn_rf_count.restype = C.c_int

@@ -68,29 +68,10 @@ __global__ void __launch_bounds__(256) norms_kernel(const float* __restrict__ re
     const int64_t vc = v < total ? v : total - 1;                 // (clamped: every lane of a half-wave takes part in the tree)
     const float* row = vc < R ? refs + vc * rs : emb + (vc - R) * es;
     const float s = half_wave_sumsq(row[h < H ? h : 0], row[32 + h < H ? 32 + h : 0], h, H);
-    if (h == 0 && v < total) inv[v] = 1.f / fmaxf(sqrtf(s), MKGNN_EPS);
+    if (h == 0 && v < total) inv[v] = inv_clamped_norm(s);
 }
 
-// the dot product of the definition, serially: products, the optional fmaf, the xor tree's association, + (+0.0)
-template <int W>
-__device__ __forceinline__ float mc_dot(const float (&e)[W], const float* __restrict__ q) {
-#pragma clang fp contract(off)
-    // (plain operators under the pragma: __fmul_rn / __fadd_rn are header functions compiled under the header's own mode, and a
-    // product and the sum it feeds in ONE thread would be fused -- in embed_cosine_kernel a shuffle lies between them)
-    float x[32];
-#pragma unroll
-    for (int j = 0; j < 32; ++j) x[j] = e[j] * q[j];
-    if constexpr (W == 64) {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) x[j] = fmaf(e[32 + j], q[32 + j], x[j]);
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-#pragma unroll
-        for (int j = 0; j < o; ++j) x[j] = x[j] + x[j + o];
-    }
-    return x[0] + 0.f;
-}
+// the dot product of the definition, serially: mc_dot (kgnn_head_terms.h), shared with kgnn_diverse.hip
 
 // the order: a non-NaN beats a NaN, a larger value beats a smaller one (-0.0 == +0.0: no strict >), the earlier one stays otherwise
 __device__ __forceinline__ bool mc_better(float s, float best) { return s == s && (best != best || s > best); }

@@ -1069,6 +1069,111 @@ def select_rows(scores: torch.Tensor, ids: torch.Tensor, key: torch.Tensor, n_va
     return tuple(out)
 
 
+def diverse_pick_supported(n: int, H: int) -> bool:
+    """The shapes ``mkgnn_diverse_pick`` takes; anything else goes through torch operators on the GPU."""
+    return 1 <= n <= _lib.DIVERSE_MAX_ROWS and 1 <= H <= _lib.DIVERSE_MAX_H
+
+
+def _diverse_pick_torch(emb: torch.Tensor, max_sim: float, k: int, picks, n_picks, leader, leader_sim) -> None:
+    """The walk of ``screening.diverse_pick_reference`` through torch operators on the GPU, for the shapes the kernel does not take:
+    the similarities are ``embedding_cosine(emb, emb[a:a + 32])`` -- group by group of 32 columns, so no ``[n, n]`` matrix exists --
+    and every row is one step of dependent masked updates without a host round trip.  Two passes over the groups: the diagonal
+    first (a row whose own similarity is NaN must not be covered by an earlier pick), then the walk."""
+    n, dev = emb.shape[0], emb.device
+    row = torch.arange(n, device=dev)
+    slot = torch.arange(k, device=dev)
+    diag = torch.empty(n, dtype=torch.float32, device=dev)
+    for a in range(0, n, 32):
+        b = min(a + 32, n)
+        diag[a:b] = embedding_cosine(emb, emb[a:b])[a:b].diagonal()
+    alive = ~torch.isnan(diag)
+    lead = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    lsim = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+    chosen = torch.full((k,), -1, dtype=torch.int64, device=dev)
+    count = torch.zeros((), dtype=torch.int64, device=dev)
+    for a in range(0, n, 32):
+        b = min(a + 32, n)
+        cols = embedding_cosine(emb, emb[a:b])
+        for i in range(a, b):
+            s = cols[:, i - a]
+            pick = alive[i] & (count < k)                        # (0-dim, on the device)
+            took = pick & alive & (row >= i) & ((s > max_sim) | (row == i))
+            lead = torch.where(took, i, lead)
+            lsim = torch.where(took, s, lsim)
+            chosen = torch.where(pick & (slot == count), i, chosen)
+            alive = alive & ~took
+            count = count + pick
+    picks.copy_(chosen)
+    n_picks.copy_(count.reshape(1))
+    leader.copy_(lead)
+    leader_sim.copy_(lsim)
+
+
+_DIVERSE_WS: dict = {}
+
+
+def diverse_pick(emb: torch.Tensor, max_sim: float, k: Optional[int] = None, out=None):
+    """``(picks int32 [k], n_picks int32 [1], leader int32 [n], leader_sim float32 [n])``: leader clustering of the rows of a
+    float32 CUDA ``emb [n, H]`` given in RANK ORDER, best first (``mkgnn_diverse_pick``; ``screening.diverse_pick_reference`` is the
+    definition).  With ``S[i, p]`` the similarity ``embedding_cosine`` gives for row ``i`` and query row ``p``, BIT FOR BIT: row ``i``
+    is covered by the FIRST pick so far with ``S[i, p] > max_sim`` (strict; a NaN never covers) -- ``leader[i] = p``, ``leader_sim[i] =
+    S[i, p]`` -- and becomes a pick itself otherwise while fewer than ``k`` exist (``leader[i] = i``); a row whose own similarity
+    ``S[i, i]`` is NaN, and a row nothing covers once the list is full, keep ``(-1, NaN)``.  ``picks`` holds the picks' row indices in
+    pick order, unused slots ``-1``.  ``k`` defaults to ``n`` (no cap); ``1 <= k <= n``, ``max_sim`` finite.  ``out``: the four
+    contiguous tensors to write into.  The launches read ``emb`` raw, so a captured call follows its contents; the scratch is a
+    per-device buffer that only grows for eager calls, and a call inside a capture allocates its own.  More than 2^20 rows or an
+    embedding wider than 64: the same definition through torch operators on the GPU (``embedding_cosine``'s own route and bits at
+    that width, one step of masked updates per row).  It has no autograd node: called where a gradient is being recorded for
+    ``emb`` it raises instead of dropping it."""
+    if not torch.is_tensor(emb) or emb.dim() != 2 or emb.dtype != torch.float32 or emb.shape[1] < 1:
+        raise ValueError("diverse_pick needs a float32 [n, H] embedding in rank order")
+    max_sim = float(max_sim)
+    if max_sim != max_sim or max_sim in (float("inf"), float("-inf")):
+        raise ValueError(f"diverse_pick: max_sim = {max_sim} is not a finite threshold")
+    if not emb.is_cuda:
+        raise ValueError(f"diverse_pick runs on the GPU: emb is on {emb.device} (there is no CPU path; "
+                         "screening.diverse_pick_reference is the host form)")
+    if torch.is_grad_enabled() and emb.requires_grad:
+        raise RuntimeError("diverse_pick is forward only: call it under torch.no_grad() (or on a detached input)")
+    n, H = int(emb.shape[0]), int(emb.shape[1])
+    k = n if k is None else int(k)
+    if n > 0 and not 1 <= k <= n:
+        raise ValueError(f"diverse_pick: k = {k} outside [1, {n}]")
+    dev = emb.device
+    if out is None:
+        out = (torch.empty(k, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
+               torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
+    else:
+        ok = isinstance(out, (tuple, list)) and len(out) == 4 and all(torch.is_tensor(o) and o.device == dev and o.is_contiguous()
+                                                                      for o in out)
+        if not ok or any(o.dtype != torch.int32 for o in out[:3]) or out[3].dtype != torch.float32 \
+                or tuple(out[0].shape) != (k,) or out[1].numel() != 1 or tuple(out[2].shape) != (n,) or tuple(out[3].shape) != (n,):
+            raise ValueError(f"out: contiguous (int32 [{k}], int32 [1], int32 [{n}], float32 [{n}]) on {dev}")
+    picks, n_picks, leader, leader_sim = out
+    if n == 0:
+        n_picks.zero_()
+        picks.fill_(-1)
+        return tuple(out)
+    emb = emb.detach()
+    if not diverse_pick_supported(n, H):
+        _diverse_pick_torch(emb, max_sim, k, picks, n_picks, leader, leader_sim)
+        return tuple(out)
+    emb = _row_major(emb)
+    lib = _lib.load()
+    nbytes = int(lib.mkgnn_diverse_pick_workspace_bytes(n))
+    if torch.cuda.is_current_stream_capturing():
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    else:
+        ws = _DIVERSE_WS.get(str(dev))
+        if ws is None or ws.numel() < nbytes:
+            ws = _DIVERSE_WS[str(dev)] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkgnn_diverse_pick(emb.data_ptr(), _stride0(emb), n, H, max_sim, k, picks.data_ptr(), n_picks.data_ptr(),
+                                          leader.data_ptr(), leader_sim.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _lib.stream_ptr(dev)), "mkgnn_diverse_pick")
+    return tuple(out)
+
+
 # ------------------------------------------------------------------- the tail of a training step, fused --
 # MKGNN_FUSED_TAIL=0: readout_blocks + bce_head_loss as separate operators (nine launches; A/B, diagnostics)
 _FUSED_TAIL = os.environ.get("MKGNN_FUSED_TAIL", "1") != "0"

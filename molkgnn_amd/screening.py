@@ -34,6 +34,13 @@ only the molecules inside a band of that similarity (``mkgnn_select_rows`` in fr
 ``max_cosine_reference`` / ``select_rows_reference``  the two definitions in numpy
 ``reference_similarity_resident``        ``(max_sim[n_molecules], arg_ref[n_molecules])`` of one resident shard
 ``screen_novel``                         shards -> the top ``k`` of the molecules whose nearest reference passes the bounds
+
+Diverse hits -- the best molecule of every chemical series among the top of a ranking, and the series every other hit belongs to
+(leader clustering of the ranked list by the cosine similarity of the graph embeddings, ``mkgnn_diverse_pick``):
+
+``diverse_pick_reference``               the walk in numpy over a given similarity matrix: the definition
+``pick_diverse_embeddings``              the stored-embedding route: embeddings and scores -> picks, leaders, cluster sizes
+``screen_diverse``                       shards -> a pool of the best ``pool`` molecules, and the ``k`` diverse picks among them
 """
 from __future__ import annotations
 
@@ -904,4 +911,201 @@ def screen_novel(model, residents, k: int, batch_size: int, ref_emb, max_sim: Op
         result["scores"] = [scores for scores, _, _ in shards]
         result["ref_sims"] = [sims for _, sims, _ in shards]
         result["refs"] = [args for _, _, args in shards]
+    return result
+
+
+# -------------------------------------------------------------------------------------------- diverse hits --
+# The step between "top k" and "which ones do we buy": the best thousand molecules of a library are mostly a few dozen chemical
+# series repeated.  Leader clustering of the ranked list keeps the best molecule of each series and says which series every other
+# hit belongs to.  The selection is sequential by definition; ``mkgnn_diverse_pick`` runs it on the device in rank-order tiles.
+def diverse_pick_reference(sim, max_sim, k_max):
+    """The definition of ``mkgnn_diverse_pick`` (include/molkgnn_hip.h), on the host, over a GIVEN square similarity matrix ``sim``
+    (float32 or float64; only ``sim[i, p]``, ``p <= i``, is read: ``sim[i, p]`` is the similarity of row ``i`` as the row with row
+    ``p`` as the query), rows in rank order: ``(picks int32 [k_max], n_picks, leader int32 [n], leader_sim [n]`` in ``sim``'s
+    dtype ``)``.  Walk ``i = 0, 1, ...``: a row with a NaN ``sim[i, i]`` is never picked, never covered and covers nothing (``-1``,
+    NaN); otherwise the FIRST pick ``p`` so far, in pick order, with ``sim[i, p] > max_sim`` (strict; a NaN never covers) is its
+    leader (``leader[i] = p``, ``leader_sim[i] = sim[i, p]``); without one it becomes a pick (``leader[i] = i``, ``leader_sim[i] =
+    sim[i, i]``) while fewer than ``k_max`` exist, and keeps ``(-1, NaN)`` once the list is full.  Unused slots of ``picks`` are
+    ``-1``.  The comparison is made in ``sim``'s own dtype: ``max_sim`` is rounded to it first."""
+    if torch.is_tensor(sim):
+        sim = sim.detach().cpu().numpy()
+    sim = np.asarray(sim)
+    if sim.ndim != 2 or sim.shape[0] != sim.shape[1] or sim.dtype not in (np.float32, np.float64):
+        raise ValueError("a square float32 or float64 similarity matrix is needed")
+    n, k_max = sim.shape[0], int(k_max)
+    if not 1 <= k_max <= max(n, 1):
+        raise ValueError(f"k_max = {k_max} outside [1, {n}]")
+    bound = sim.dtype.type(max_sim)
+    if np.isnan(bound):
+        raise ValueError("max_sim is NaN")
+    picks = np.full(k_max, -1, dtype=np.int32)
+    leader = np.full(n, -1, dtype=np.int32)
+    leader_sim = np.full(n, np.nan, dtype=sim.dtype)
+    chosen = []
+    for i in range(n):
+        if np.isnan(sim[i, i]):
+            continue
+        row = sim[i, chosen] if chosen else np.empty(0, dtype=sim.dtype)
+        with np.errstate(invalid="ignore"):
+            over = np.flatnonzero(row > bound)
+        if over.size:
+            p = chosen[int(over[0])]
+            leader[i], leader_sim[i] = p, sim[i, p]
+        elif len(chosen) < k_max:
+            picks[len(chosen)] = i
+            chosen.append(i)
+            leader[i], leader_sim[i] = i, sim[i, i]
+    return picks, len(chosen), leader, leader_sim
+
+
+def _check_max_sim(who: str, max_sim) -> float:
+    max_sim = float(max_sim)
+    if max_sim != max_sim or max_sim in (float("inf"), float("-inf")):
+        raise ValueError(f"{who}: max_sim = {max_sim} is not a finite similarity threshold")
+    return max_sim
+
+
+def rank_order(scores: torch.Tensor) -> torch.Tensor:
+    """The rows of a float32 score vector in the order of ``topk_update_reference``, as int64 indices on the scores' device: non-NaN
+    before NaN, descending with ``-0.0 == +0.0``, then the lower index.  (A descending torch sort alone puts NaN FIRST -- it ranks
+    NaN above every number -- so the NaN rows are ranked as ``-inf`` in a stable sort and then moved behind the rest by a second
+    stable sort, which keeps a true ``-inf`` score in front of them.)"""
+    nan = torch.isnan(scores)
+    key = torch.where(nan, torch.full_like(scores, float("-inf")), scores + 0.0)
+    order = torch.sort(key, descending=True, stable=True).indices
+    return order[torch.sort(nan[order].to(torch.int8), stable=True).indices]
+
+
+def _cluster_sizes(leader: torch.Tensor, picks: torch.Tensor, n: int) -> torch.Tensor:
+    """How many rows every pick leads, itself included: ``leader`` int ``[n]`` of row indices (``-1``: none), ``picks`` row indices."""
+    led = leader.long()
+    counts = torch.bincount(led[led >= 0], minlength=max(n, 1))
+    return counts[picks.long()]
+
+
+def pick_diverse_embeddings(emb: torch.Tensor, scores: torch.Tensor, max_sim: float, k: int,
+                            ids: Optional[torch.Tensor] = None) -> dict:
+    """The stored-embedding route: diverse hits among ANY scored set of molecules whose embeddings are kept -- the output of
+    ``embed_resident`` and ``score_resident`` of a shard, say, up to 2^20 rows -- WITHOUT running the network.  ``emb`` float32
+    ``[n, G]`` and ``scores`` float32 ``[n]`` on the GPU.  The rows are ranked by the order of ``topk_update_reference`` (non-NaN
+    before NaN, descending, ``-0.0 == +0.0``, then the lower row), gathered in that order, and ``readout.diverse_pick`` walks them
+    (``diverse_pick_reference`` is the definition): the best row of every cluster of cosine similarity above ``max_sim`` is a pick,
+    at most ``k`` of them.  Returns a dict in terms of the caller's rows -- ``ids[row]`` when ``ids`` (an integer ``[n]`` tensor on
+    the GPU) is given, the row numbers otherwise:
+
+    ``picks``         ``[n_picks]`` int64: the picks, best first
+    ``pick_score``    ``[n_picks]``: their scores
+    ``leader``        ``[n]`` int64, by the caller's row: the pick that covers the row (itself for a pick), ``-1`` for none
+    ``leader_sim``    ``[n]`` float32, by the caller's row: the similarity to that pick, NaN for none
+    ``cluster_size``  ``[n_picks]`` int64: the rows every pick leads, itself included
+    ``order``         ``[n]`` int64: the caller's rows in rank order (``order[0]`` is the best row)
+
+    One host read at the end (the number of picks).  A wrong shape, dtype or device, a NaN or infinite ``max_sim``, ``k`` outside
+    ``[1, n]``: ``ValueError`` before a launch."""
+    who = "pick_diverse_embeddings"
+    if not torch.is_tensor(emb) or emb.dim() != 2 or emb.dtype != torch.float32 or emb.shape[1] < 1:
+        raise ValueError(f"{who}: emb is a float32 [n, G] tensor")
+    n = int(emb.shape[0])
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32 or tuple(scores.shape) != (n,):
+        raise ValueError(f"{who}: scores is a float32 [{n}] tensor, one score per row of emb")
+    max_sim = _check_max_sim(who, max_sim)
+    k = int(k)
+    if not 1 <= k <= n:
+        raise ValueError(f"{who}: k = {k} outside [1, {n}]")
+    integer = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+    if ids is not None and (not torch.is_tensor(ids) or ids.dtype not in integer or tuple(ids.shape) != (n,)):
+        raise ValueError(f"{who}: ids is an integer [{n}] tensor")
+    dev = emb.device
+    if dev.type != "cuda" or scores.device != dev or (ids is not None and ids.device != dev):
+        raise ValueError(f"{who}: emb is on {dev}; the selection runs on the GPU, with scores and ids on the same device (there is "
+                         "no CPU path; diverse_pick_reference is the host form)")
+    from .readout import diverse_pick
+    emb, scores = emb.detach(), scores.detach()
+    order = rank_order(scores)
+    picks, n_picks, leader, leader_sim = diverse_pick(emb.index_select(0, order), max_sim, k)
+    picks = picks[:int(n_picks.item())].long()                   # (the one host read)
+    name = order if ids is None else ids.long().index_select(0, order)          # rank position -> what the caller calls the row
+    led = leader.long()
+    named = torch.where(led >= 0, name[led.clamp_min(0)], led)
+    by_row = torch.empty_like(named)
+    by_row[order] = named
+    sim_by_row = torch.empty_like(leader_sim)
+    sim_by_row[order] = leader_sim
+    return {"picks": name[picks], "pick_score": scores[order[picks]], "leader": by_row, "leader_sim": sim_by_row,
+            "cluster_size": _cluster_sizes(leader, picks, n), "order": order}
+
+
+DIVERSE_MAX_POOL = 1024                         # the pool of screen_diverse is a TopK: MKGNN_TOPK_MAX_K
+
+
+def screen_diverse(model, residents, k: int, batch_size: int, max_sim: float, pool: int = 1024,
+                   return_embeddings: bool = False) -> dict:
+    """``screen``, then the diverse hits among its best: the library is ranked into a pool of the best ``pool`` molecules (a
+    ``TopK(pool)``, ``pool <= 1024``), and ``readout.diverse_pick`` walks the pool best first -- a molecule whose graph embedding has
+    a cosine similarity above ``max_sim`` to an earlier pick belongs to that pick's cluster, one without becomes a pick, at most ``k
+    <= pool`` of them (``diverse_pick_reference`` is the definition).  ``residents`` as in ``screen``; shard ``j`` carries tag ``j``.
+
+    Per batch ONE captured graph runs ``model.predict`` once (score and embedding from one run of the network, the forward-only
+    tail): the embedding is the pass's main result and is scattered into the shard's ``[n_molecules, G]`` matrix, the score is
+    scattered into its vector and fed to the running list.  The per-shard embedding matrices stay on the device until the end --
+    ``4 G`` bytes per molecule of the library (128 bytes at ``G = 32``; a library too large for that is screened with ``screen`` and
+    its hits embedded again) -- because which molecules end up in the pool is known only then; the pool's rows are gathered from them
+    by ``(top_shard, top_mol)``.
+
+    Returns ``pool_score``, ``pool_shard``, ``pool_mol`` (the pool, trimmed to its occupied slots, best first: ``screen(..., k=pool)``'s
+    lists bit for bit) and ``pool_emb`` (``[pool, G]``); ``pool_leader`` (int64: the POSITION IN THE POOL of the pick that covers the
+    molecule, its own position for a pick, ``-1`` for none) and ``pool_leader_sim``; ``picks`` (int64 positions in the pool, best
+    first); ``top_score``, ``top_shard``, ``top_mol`` of the picks; ``cluster_size`` (per pick, itself included); ``n_scored``; and,
+    with ``return_embeddings``, ``embeddings``: the per-shard matrices.  The gather's status word is read once per shard; the model
+    comes back in the mode it came in.  A NaN or infinite ``max_sim``, ``pool`` outside ``[1, 1024]``, ``k`` outside ``[1, pool]``, a
+    multi-task model, a model or a shard that is not on the GPU: ``ValueError`` before a launch."""
+    who = "screen_diverse"
+    max_sim = _check_max_sim(who, max_sim)
+    k, pool, bs = int(k), int(pool), int(batch_size)
+    if not 1 <= pool <= DIVERSE_MAX_POOL:
+        raise ValueError(f"{who}: pool = {pool} outside [1, {DIVERSE_MAX_POOL}] (the pool is a running list: MKGNN_TOPK_MAX_K)")
+    if not 1 <= k <= pool:
+        raise ValueError(f"{who}: k = {k} outside [1, pool = {pool}]: the picks are chosen among the pool")
+    if bs < 1:
+        raise ValueError("batch_size >= 1")
+    G = _embedding_width(model)
+    if model.ffn.out_features != 1:
+        raise ValueError("screening ranks ONE score per molecule: a one-task model (task_dim = 1) is needed")
+    if next(model.parameters()).device.type != "cuda":
+        raise ValueError(f"{who} runs on the GPU: move the model there (there is no CPU path)")
+    from .readout import diverse_pick
+
+    def predict(data):
+        pred, emb = model.predict(data)
+        return _embedding_f32(emb), pred.reshape(-1)
+
+    def per_shard(resident, topk, tag):
+        dev = next(model.parameters()).device
+        emb, _ = _run_shard(who, "scoring", model, resident, dev, bs, predict, (G,), topk, TopK, shard_tag=tag,
+                            extras=((torch.float32, float("nan")),),
+                            rank=lambda emb, ids, n_live, score: topk.update(score, ids, n_valid=n_live))
+        return emb
+
+    top_score, top_shard, top_mol, occupied, n_scored, embs = _over_shards(
+        who, residents, lambda r: _check_model(model, r), lambda dev: TopK(pool, dev), per_shard, True)
+    top_score, top_shard, top_mol = top_score[:occupied], top_shard[:occupied], top_mol[:occupied]
+    dev = top_score.device
+    pool_emb = torch.zeros((occupied, G), dtype=torch.float32, device=dev)
+    for j, emb in enumerate(embs):                               # (no host read: a select per shard over at most 1 024 rows)
+        here = top_shard == j
+        if emb.shape[0] > 0:
+            pool_emb = torch.where(here[:, None], emb.index_select(0, torch.where(here, top_mol, 0).long()), pool_emb)
+    if occupied > 0:
+        picks, n_picks, leader, leader_sim = diverse_pick(pool_emb, max_sim, min(k, occupied))
+        picks = picks[:int(n_picks.item())].long()               # (the one host read of the selection)
+    else:
+        picks = torch.zeros(0, dtype=torch.int64, device=dev)
+        leader = torch.zeros(0, dtype=torch.int32, device=dev)
+        leader_sim = torch.zeros(0, dtype=torch.float32, device=dev)
+    result = {"pool_score": top_score, "pool_shard": top_shard, "pool_mol": top_mol, "pool_emb": pool_emb,
+              "pool_leader": leader.long(), "pool_leader_sim": leader_sim, "picks": picks, "top_score": top_score[picks],
+              "top_shard": top_shard[picks], "top_mol": top_mol[picks], "cluster_size": _cluster_sizes(leader, picks, occupied),
+              "n_scored": n_scored}
+    if return_embeddings:
+        result["embeddings"] = embs
     return result
