@@ -1110,6 +1110,47 @@ int mkgnn_diverse_pick(const float* emb, int64_t emb_stride, int64_t n_rows, int
                        int32_t* picks, int32_t* n_picks, int32_t* leader, float* leader_sim, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- what each kernel learned (additive; the ABI version stays 8): C running lists, one per kernel column of a convolution
+ * layer's output sim [n_atoms, C] (row n holds the num_kernels[d] scores of its own degree d + 1 in the columns [col_begin[d],
+ * col_begin[d] + num_kernels[d]); what lies elsewhere in the row is never read), each the K atoms of a library that column matches
+ * best.  List c is slots [c K, (c + 1) K) of top_score / top_shard / top_mol / top_atom ([C, K], contiguous), updated IN PLACE
+ * and always fully sorted.  An empty slot is (-inf, -1, -1, -1); a list starts out as K of them.
+ *
+ * The candidates come from the degree buckets of the batch: slot s < buckets[d].count names atom n = buckets[d].selected_index[s]
+ * (only count and selected_index of a bucket are read).  It is a candidate of every column of [col_begin[d], col_begin[d] +
+ * num_kernels[d]) and of no other, if  n < *n_valid_atoms  (a device int64 scalar; NULL: every atom) and  g = atom_mol[n] <
+ * min(max(*n_live, 0), B)  -- live molecules come first in a batch; fillers, padding molecules and padding atoms never enter,
+ * whatever they score.  Its entry in column c is (the bits of sim[n * sim_stride + c], *shard_tag, mol_ids[g], n - mol_ptr[g]):
+ * the atom's index inside its molecule.  atom_mol int32 [n_atoms], mol_ptr int32 [B + 1], mol_ids int32 [B]; n_live and shard_tag
+ * are device int32 scalars as in mkgnn_topk_update, so one captured launch serves every batch and shard.
+ *
+ * After the call list c holds the first K entries, sorted, of  old list c  U  the candidates of c  under mkgnn_topk_update's
+ * total order extended by the atom: occupied before empty (a real entry whose score is -inf ranks before an empty slot), non-NaN
+ * before NaN, score descending with -0.0 == +0.0, shard ascending, molecule ascending, atom ascending, and entries alike in all
+ * of that in their order of arrival -- the old list first, then degree-bucket slot order.  Score bits are copied, never recomputed.
+ *
+ * Two launches on `stream`, capturable: one workgroup per (tile of 128 slots of one degree, chunk of 64 of its columns) reads the
+ * atoms' scores once, decides per column whether any candidate of the tile displaces the list's last entry under the full order
+ * and, only then, leaves the tile's best entries as a sorted run; one wave per column merges the flagged runs into its list in
+ * tile order.  No host round trip, no atomics, no process-wide state; integer comparisons only; every output has one writer; the
+ * result is a function of the inputs alone.  The workspace (16-byte aligned, mkgnn_kernel_exemplars_workspace_bytes(counts,
+ * num_kernels, K, C) bytes; 0 for rejected sizes) needs no initialisation: it is read only where the same call wrote it.
+ *
+ * Limits: 1 <= K <= MKGNN_EXEMPLARS_MAX_K (K need not be a power of two); 1 <= C <= MKGNN_EXEMPLARS_MAX_COLUMNS; the four column
+ * blocks lie inside [0, C) and do not overlap (num_kernels[d] = 0 and count = 0 are allowed); sim_stride >= C; B >= 1;
+ * 1 <= n_atoms <= 2^30.  Anything else -- a null pointer, a negative count or one above n_atoms, a workspace that is too small or
+ * misaligned, an output aliasing an input or another output -- returns non-zero with mkgnn_last_error set, before any launch. */
+#define MKGNN_EXEMPLARS_MAX_K 64
+#define MKGNN_EXEMPLARS_MAX_COLUMNS 256
+size_t mkgnn_kernel_exemplars_workspace_bytes(const int64_t count[MKGNN_MAX_DEGREE], const int32_t num_kernels[MKGNN_MAX_DEGREE],
+                                              int32_t K, int32_t C);
+int mkgnn_kernel_exemplars_update(const float* sim, int64_t sim_stride, int64_t n_atoms,
+                                  const mkgnn_degree_bucket buckets[MKGNN_MAX_DEGREE], const int32_t col_begin[MKGNN_MAX_DEGREE],
+                                  const int32_t num_kernels[MKGNN_MAX_DEGREE], const int32_t* atom_mol, const int32_t* mol_ptr,
+                                  const int32_t* mol_ids, int32_t B, const int32_t* n_live, const int64_t* n_valid_atoms,
+                                  const int32_t* shard_tag, int32_t K, int32_t C, float* top_score, int32_t* top_shard,
+                                  int32_t* top_mol, int32_t* top_atom, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

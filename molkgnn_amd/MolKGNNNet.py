@@ -190,6 +190,59 @@ class MolKGNNNet(torch.nn.Module):
         # pool(lin2(dropout(act(lin1(h)))), batch) -- MolKGNNNet.py:144-146 -- as one operator
         return R.readout(node_representation, lin1, lin2, self.dropout, data.batch, getattr(data, 'num_graphs', None), segments=seg)
 
+    def kernel_column_layout(self, layer: int, device=None):
+        """``(column_degree, column_kernel)`` of convolution layer ``layer`` (int32 ``[K_layer]`` each): column ``c`` of that layer's
+        output is kernel ``column_kernel[c]`` of the bank of degree ``column_degree[c]`` (1 to 4).  Made once per (layer, device)
+        and kept, so a captured step copies nothing from the host."""
+        Ls = tuple(int(k) for k in self.gnn.layers[layer].L)
+        key = (int(layer), Ls, None if device is None else str(device))
+        kept = self.__dict__.setdefault("_column_layouts", {})
+        if key not in kept:
+            degree = torch.tensor([d + 1 for d, L in enumerate(Ls) for _ in range(L)], dtype=torch.int32)
+            kernel = torch.tensor([k for L in Ls for k in range(L)], dtype=torch.int32)
+            kept[key] = (degree.to(device), kernel.to(device)) if device is not None else (degree, kernel)
+        return kept[key]
+
+    def kernel_scores(self, data, layer: int):
+        """``(sim [N, K_layer], column_degree [K_layer], column_kernel [K_layer])``: the output of convolution layer ``layer`` (0 is
+        the 1-hop layer) of a model in evaluation mode, under ``torch.no_grad()`` -- ``sim[n, c]`` is how well kernel ``c`` matches
+        the neighbourhood of atom ``n``.  Row ``n`` holds the scores of its own degree ``d`` in the columns of that degree's bank
+        (``column_degree == d``; ``column_kernel`` is the index inside the bank); what lies elsewhere in the row is unspecified and
+        must not be read.  ``N`` counts all atom rows of the batch, padding atoms included.
+
+        It is this composition of the public modules, which is what runs: the node batch norm (``readout.batch_norm`` with the
+        batch's ``n_valid_atoms``), then for ``i = 0 .. layer`` ``gnn.layers[i](i == num_layers - 1, data=..., save_score=False)``
+        on ``x, p, edge_index, edge_attr`` and the twenty per-degree fields, with ``gnn.propagate(edge_index=..., sim_sc=...)``
+        between two layers.  The layers behind ``layer``, the readout and the head are not run.  The training and scoring forwards
+        (``forward``, ``predict``, the molecule-resident step) take other kernels for the same layers and may choose differently
+        among mathematically tied neighbour permutations in a few entries ("Ties"): their scores can differ from
+        these there.  In training mode, and for a ``layer`` outside ``[0, num_layers)``, this raises ``ValueError``."""
+        if self.training:
+            raise ValueError("MolKGNNNet.kernel_scores needs evaluation mode: call model.eval() first")
+        layer = int(layer)
+        if not 0 <= layer < self.num_layers:
+            raise ValueError(f"layer = {layer} outside [0, {self.num_layers})")
+        from .KernelLayer import Data
+        with torch.no_grad():
+            x = R.batch_norm(data.x, self.node_batch_norm, getattr(data, 'n_valid_atoms', None))
+            names = ('p_focal', 'nei_p', 'nei_edge_attr', 'selected_index', 'nei_index')
+            fields = {f'{nm}_deg{d}': getattr(data, f'{nm}_deg{d}') for nm in names for d in range(1, 5)}
+            if getattr(data, '_rf_ready', None) is not None:     # degree buckets still being built on the index stream
+                from .plan import plan_from_lists_cached
+                from .receptive_field import await_receptive_fields
+                await_receptive_fields(data)
+                # ... and behind them the batch's index plan (attach_receptive_fields(overlap=True) leaves it in the plan cache):
+                # forward's first propagate joins that stream; nothing here reads the plan, so it is joined now -- a captured step
+                # must not end with work of another stream still open
+                plan_from_lists_cached(data.x.shape[0], *[[fields[f'{nm}_deg{d}'] for d in range(1, 5)] for nm in names],
+                                       data.edge_index)._await()
+            step = Data(x=x, p=data.p, edge_index=data.edge_index, edge_attr=data.edge_attr, **fields)
+            for i in range(layer + 1):
+                sim = self.gnn.layers[i](i == self.num_layers - 1, data=step, save_score=False)
+                if i < layer:
+                    step.x = self.gnn.propagate(edge_index=data.edge_index, sim_sc=sim)
+            return (sim, *self.kernel_column_layout(layer, sim.device))
+
     @staticmethod
     def add_model_specific_args(parent_parser):
         parser = parent_parser.add_argument_group("MolKGNNNet")

@@ -29,6 +29,9 @@ SELECT_ROWS_PASS = 1024
 DIVERSE_MAX_ROWS, DIVERSE_MAX_H = 1 << 20, 64           # MKGNN_DIVERSE_MAX_ROWS, mkgnn_diverse_pick's widest embedding
 # kgnn_diverse.hip's tiling (DV_COVER_ROWS, DV_COVER_TILE): rows per block and picks per LDS tile of the cover launch
 DIVERSE_COVER_ROWS, DIVERSE_COVER_TILE = 128, 32
+EXEMPLARS_MAX_K, EXEMPLARS_MAX_COLUMNS = 64, 256        # MKGNN_EXEMPLARS_MAX_K, MKGNN_EXEMPLARS_MAX_COLUMNS
+# kgnn_exemplars.hip's tiling (EX_TILE, EX_CHUNK): degree-bucket slots per tile and columns per workgroup of the runs launch
+EXEMPLARS_TILE, EXEMPLARS_CHUNK = 128, 64
 
 
 def diverse_tile(H: int) -> int:
@@ -151,6 +154,7 @@ BankGrads4 = KernelBankGrad * MAX_DEGREE
 Buckets4 = DegreeBucket * MAX_DEGREE
 Saved4 = Saved * MAX_DEGREE
 Int32x4 = C.c_int32 * MAX_DEGREE
+Int64x4 = C.c_int64 * MAX_DEGREE
 
 MOLECULE_MAX_LAYERS = 4
 MOLECULE_MAX_ATOMS = 64
@@ -212,7 +216,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks", "mkgnn_embed_cosine",
            "mkgnn_atom_contributions", "mkgnn_atom_contributions_workspace_bytes", "mkgnn_embed_max_cosine",
            "mkgnn_embed_max_cosine_workspace_bytes", "mkgnn_select_rows", "mkgnn_tail_defer_projection",
-           "mkgnn_debug_tail_projection_launches", "mkgnn_diverse_pick", "mkgnn_diverse_pick_workspace_bytes")
+           "mkgnn_debug_tail_projection_launches", "mkgnn_diverse_pick", "mkgnn_diverse_pick_workspace_bytes",
+           "mkgnn_kernel_exemplars_update", "mkgnn_kernel_exemplars_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -422,6 +427,11 @@ def load() -> C.CDLL:
     lib.mkgnn_diverse_pick_workspace_bytes.argtypes = [I64]
     lib.mkgnn_diverse_pick.restype = C.c_int
     lib.mkgnn_diverse_pick.argtypes = [P, I64, I64, I32, C.c_float, I32, P, P, P, P, P, C.c_size_t, P]
+    lib.mkgnn_kernel_exemplars_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_kernel_exemplars_workspace_bytes.argtypes = [C.POINTER(Int64x4), C.POINTER(Int32x4), I32, I32]
+    lib.mkgnn_kernel_exemplars_update.restype = C.c_int
+    lib.mkgnn_kernel_exemplars_update.argtypes = [P, I64, I64, C.POINTER(Buckets4), C.POINTER(Int32x4), C.POINTER(Int32x4), P, P, P,
+                                                  I32, P, P, P, I32, I32, P, P, P, P, P, C.c_size_t, P]
     lib.mkgnn_rf_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_rf_workspace_bytes.argtypes = [I64]
     lib.mkgnn_rf_count.restype = C.c_int

@@ -41,6 +41,13 @@ Diverse hits -- the best molecule of every chemical series among the top of a ra
 ``diverse_pick_reference``               the walk in numpy over a given similarity matrix: the definition
 ``pick_diverse_embeddings``              the stored-embedding route: embeddings and scores -> picks, leaders, cluster sizes
 ``screen_diverse``                       shards -> a pool of the best ``pool`` molecules, and the ``k`` diverse picks among them
+
+What each kernel learned -- for every kernel column of a convolution layer the ``k`` atoms of the library it matches best
+(``GNNModel.kernel_scores``, ``mkgnn_kernel_exemplars_update``; one running list per column, a candidate is an atom):
+
+``kernel_exemplars_reference``           the definition in numpy
+``KernelExemplars``                      the running lists on the device (``[n_columns, k]`` tensors)
+``kernel_exemplars``                     shards -> ``top_score`` / ``top_shard`` / ``top_mol`` / ``top_atom`` per kernel column
 """
 from __future__ import annotations
 
@@ -1109,3 +1116,279 @@ def screen_diverse(model, residents, k: int, batch_size: int, max_sim: float, po
     if return_embeddings:
         result["embeddings"] = embs
     return result
+
+
+# ------------------------------------------------------------------------------------- what each kernel learned --
+# Every kernel of a ``KernelSetConv`` is a small learned neighbourhood pattern, and ``sim[n, c]`` -- the output of a convolution
+# layer (``GNNModel.kernel_scores``) -- is how well kernel ``c`` matches the neighbourhood of atom ``n``.  The ``k`` atoms of a whole
+# library that every kernel of a layer matches best are a picture book of those patterns; the same lists show the dead kernels (no
+# atom scores high) and the duplicates.  One running list per kernel column, a candidate is an ATOM, and it competes only in the
+# columns of its own degree: ``mkgnn_kernel_exemplars_update``.
+#
+# ``kernel_exemplars_reference``  the definition in numpy
+# ``KernelExemplars``             the running lists on the device (``[n_columns, k]`` tensors, updated in place, capturable)
+# ``kernel_exemplars``            shards -> the ``k`` best-matching atoms of every kernel of one layer
+EXEMPLARS_MAX_K, EXEMPLARS_MAX_COLUMNS = 64, 256               # MKGNN_EXEMPLARS_MAX_K, MKGNN_EXEMPLARS_MAX_COLUMNS
+
+
+def empty_exemplars(n_columns: int, k: int):
+    """``n_columns`` lists of ``k`` empty slots: ``(top_score float32, top_shard int32, top_mol int32, top_atom int32)``, ``[n_columns,
+    k]`` each; an empty slot is ``(-inf, -1, -1, -1)``."""
+    shape = (int(n_columns), int(k))
+    return (np.full(shape, -np.inf, dtype=np.float32), *(np.full(shape, -1, dtype=np.int32) for _ in range(3)))
+
+
+def _host(a, dtype) -> np.ndarray:
+    return np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=dtype)
+
+
+def _column_blocks(column_begin, num_kernels, n_columns: int):
+    """``(begin[4], L[4])`` as ints; without ``num_kernels`` the blocks are contiguous: every degree's block ends where the next one
+    begins, the last one at ``n_columns``."""
+    begin = [int(b) for b in column_begin]
+    if len(begin) != 4:
+        raise ValueError("column_begin: one first column per degree (4)")
+    L = [b - a for a, b in zip(begin, begin[1:] + [int(n_columns)])] if num_kernels is None else [int(x) for x in num_kernels]
+    if len(L) != 4:
+        raise ValueError("num_kernels: one count per degree (4)")
+    return begin, L
+
+
+def kernel_exemplars_reference(lists, sim, buckets, col_begin, L, atom_mol, mol_ptr, ids, n_live, n_valid_atoms, shard_tag):
+    """The definition of ``mkgnn_kernel_exemplars_update`` (include/molkgnn_hip.h), on the host, written for clarity.  ``lists =
+    (top_score, top_shard, top_mol, top_atom)``, ``[C, K]`` each -> the updated four arrays (copies).
+
+    ``buckets[d]`` lists the atoms of degree ``d + 1`` (``selected_index``), in slot order.  Atom ``n`` of it is a candidate of the
+    columns ``col_begin[d] .. col_begin[d] + L[d]`` -- and of no other -- if ``n < n_valid_atoms`` (None: every atom) and its
+    molecule ``g = atom_mol[n]`` is live, ``g < min(max(n_live, 0), len(ids))``.  Its entry in column ``c`` is ``(sim[n, c], shard_tag,
+    ids[g], n - mol_ptr[g])``; nothing else of ``sim`` is read.  List ``c`` becomes the first ``K``, sorted, of itself and its
+    candidates:
+
+    * occupied slots before empty ones (``(-inf, -1, -1, -1)``; a real entry whose score is ``-inf`` ranks before them),
+    * non-NaN scores before NaN scores, then score descending with ``-0.0 == +0.0``,
+    * then shard, molecule and atom ascending,
+    * entries alike in all of that in their order of arrival: the old list first, then the bucket's slots (``np.lexsort`` is
+      stable).
+
+    Score BITS are carried over (a NaN's payload, a zero's sign)."""
+    ts, th, tm, ta = (np.array(_host(a, dt), copy=True) for a, dt in zip(lists, (np.float32, np.int32, np.int32, np.int32)))
+    if ts.ndim != 2 or not (ts.shape == th.shape == tm.shape == ta.shape):
+        raise ValueError("lists: four [C, K] arrays")
+    C, K = ts.shape
+    sim = _host(sim, np.float32)
+    atom_mol, mol_ptr, ids = _host(atom_mol, np.int64), _host(mol_ptr, np.int64), _host(ids, np.int32).reshape(-1)
+    N = sim.shape[0]
+    n_real = N if n_valid_atoms is None else int(_host(n_valid_atoms, np.int64).reshape(-1)[0])
+    live = min(max(int(_host(n_live, np.int64).reshape(-1)[0]), 0), ids.shape[0])
+    tag = int(_host(shard_tag, np.int64).reshape(-1)[0])
+    neg_inf = np.float32(-np.inf).view(np.int32)
+    for d in range(4):
+        slots = _host(buckets[d], np.int64).reshape(-1)
+        keep = np.array([n < n_real and atom_mol[n] < live for n in slots], dtype=bool)
+        atoms = slots[keep]                                      # the candidates of this degree, in slot order
+        g = atom_mol[atoms]
+        mol, atom = ids[g].astype(np.int32), (atoms - mol_ptr[g]).astype(np.int32)
+        for c in range(int(col_begin[d]), int(col_begin[d]) + int(L[d])):
+            s = np.concatenate([ts[c], sim[atoms, c]])
+            h = np.concatenate([th[c], np.full(atoms.shape[0], tag, dtype=np.int32)])
+            m = np.concatenate([tm[c], mol])
+            a = np.concatenate([ta[c], atom])
+            empty = (s.view(np.int32) == neg_inf) & (h == -1) & (m == -1) & (a == -1)
+            nan = np.isnan(s)
+            with np.errstate(invalid="ignore"):
+                falling = np.where(nan, np.float32(0), -(s + np.float32(0)))    # (-0.0 + 0.0 = +0.0; descending by negation)
+            order = np.lexsort((a, m, h, falling, nan, empty))[:K]               # (the LAST key is the primary one)
+            ts[c], th[c], tm[c], ta[c] = s[order], h[order], m[order], a[order]
+    return ts, th, tm, ta
+
+
+class KernelExemplars(TopK):
+    """``n_columns`` running lists of ``k`` slots on ``device``, one per kernel column of a convolution layer: ``top_score`` float32,
+    ``top_shard``, ``top_mol``, ``top_atom`` int32, ``[n_columns, k]`` each, list ``c`` always sorted by the order of
+    ``kernel_exemplars_reference``.  ``TopK``'s contract otherwise: the live count (``self.n_valid``) and ``shard_tag`` are device
+    int32 scalars read when the launches run, so one captured ``update`` serves every batch of every shard; ``reserve`` before a
+    capture, nothing is allocated inside one."""
+
+    def __init__(self, n_columns: int, k: int, device):
+        from . import _lib
+        self.n_columns = int(n_columns)
+        if not 1 <= int(k) <= _lib.EXEMPLARS_MAX_K:
+            raise ValueError(f"k = {k} outside [1, {_lib.EXEMPLARS_MAX_K}] (MKGNN_EXEMPLARS_MAX_K)")
+        if not 1 <= self.n_columns <= _lib.EXEMPLARS_MAX_COLUMNS:
+            raise ValueError(f"n_columns = {n_columns} outside [1, {_lib.EXEMPLARS_MAX_COLUMNS}] (MKGNN_EXEMPLARS_MAX_COLUMNS)")
+        self.top_atom = None
+        self._allocate(k, device, (self.n_columns, int(k)))
+
+    def reset(self) -> None:
+        """All slots empty."""
+        super().reset()
+        if self.top_atom is None:
+            self.top_atom = torch.empty_like(self.top_mol)
+        self.top_atom.fill_(-1)
+
+    def _workspace_bytes(self, counts, num_kernels) -> int:
+        from . import _lib
+        return int(_lib.load().mkgnn_kernel_exemplars_workspace_bytes(_lib.Int64x4(*[int(c) for c in counts]),
+                                                                      _lib.Int32x4(*[int(x) for x in num_kernels]), self.k, self.n_columns))
+
+    def reserve(self, counts, num_kernels) -> None:
+        """Make the workspace large enough for updates with ``counts[d]`` slots and ``num_kernels[d]`` columns per degree (before
+        a capture: a captured update must not allocate)."""
+        need = self._workspace_bytes(counts, num_kernels)
+        if need == 0:
+            raise ValueError(f"buckets of {list(counts)} slots with {list(num_kernels)} columns cannot be ranked")
+        if self.workspace is None or self.workspace.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("KernelExemplars.update would allocate its workspace inside a capture: call reserve(counts, num_kernels) first")
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+
+    def update(self, sim: torch.Tensor, plan_or_buckets, column_begin, atom_mol: torch.Tensor, mol_ptr: torch.Tensor,
+               ids: torch.Tensor, n_live=None, n_valid_atoms: Optional[torch.Tensor] = None, shard_tag=None, num_kernels=None) -> None:
+        """One ``mkgnn_kernel_exemplars_update`` on the current stream.  ``sim``: float32 ``[N, >= n_columns]`` with unit column
+        stride (a layer's ``kernel_scores``; its row stride is passed on, nothing is copied).  ``plan_or_buckets``: a ``BatchPlan``,
+        or the four ``selected_index`` tensors (int64, contiguous) of the batch.  ``column_begin``: the first column of every
+        degree's block; the blocks are contiguous (the last one ends at ``n_columns``) unless ``num_kernels`` gives their widths.
+        ``atom_mol`` int32 ``[N]``, ``mol_ptr`` int32 ``[len(ids) + 1]`` or longer, ``ids`` int32.  ``n_live`` / ``shard_tag``: as
+        ``n_valid`` / ``shard_tag`` of ``TopK.update``; ``n_valid_atoms``: a one-element int64 device tensor, or None for every atom."""
+        from . import _lib
+        dev = self.device
+        sels = [b.sel for b in plan_or_buckets.buckets] if hasattr(plan_or_buckets, "buckets") else list(plan_or_buckets)
+        if len(sels) != 4 or any(s.dtype != torch.int64 or s.device != dev or not s.is_contiguous() for s in sels):
+            raise ValueError("buckets: the four selected_index tensors of the batch, int64 and contiguous on the lists' device")
+        if sim.dtype != torch.float32 or sim.device != dev or sim.dim() != 2 or sim.shape[1] < self.n_columns or sim.shape[0] < 1 \
+                or sim.stride(1) != 1:
+            raise ValueError(f"sim: float32 [N, >= {self.n_columns}] on the lists' device, unit column stride")
+        N, B = int(sim.shape[0]), int(ids.numel())
+        for name, t, n in (("atom_mol", atom_mol, N), ("mol_ptr", mol_ptr, B + 1), ("ids", ids, max(B, 1))):
+            if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() < n:
+                raise ValueError(f"{name}: a contiguous int32 tensor of at least {n} entries on the lists' device")
+        if n_valid_atoms is not None and (not torch.is_tensor(n_valid_atoms) or n_valid_atoms.dtype != torch.int64
+                                          or n_valid_atoms.numel() != 1 or n_valid_atoms.device != dev):
+            raise ValueError("n_valid_atoms: one int64 on the lists' device, or None")
+        begin, L = _column_blocks(column_begin, num_kernels, self.n_columns)
+        live, tag = self._scalar(self.n_valid, n_live), self._scalar(self.shard_tag, shard_tag)
+        counts = [int(s.numel()) for s in sels]
+        self.reserve(counts, L)
+        bk = _lib.Buckets4()
+        for d, s in enumerate(sels):
+            bk[d].count = counts[d]
+            bk[d].selected_index = s.data_ptr() if counts[d] else None
+        ws = self.workspace
+        stride = int(sim.stride(0)) if N > 1 else max(int(sim.stride(0)), self.n_columns)     # (one row: its stride means nothing)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().mkgnn_kernel_exemplars_update(
+                sim.data_ptr(), stride, N, bk, _lib.Int32x4(*begin),
+                _lib.Int32x4(*L), atom_mol.data_ptr(), mol_ptr.data_ptr(), ids.data_ptr(), B, live.data_ptr(),
+                _lib.ptr(n_valid_atoms), tag.data_ptr(), self.k, self.n_columns, self.top_score.data_ptr(), self.top_shard.data_ptr(),
+                self.top_mol.data_ptr(), self.top_atom.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
+                "mkgnn_kernel_exemplars_update")
+
+    def result(self):
+        """``(top_score, top_shard, top_mol, top_atom, occupied)``: the four ``[n_columns, k]`` tensors (not copies) and the number of
+        occupied slots of every list -- they come first -- as a host int64 tensor ``[n_columns]`` (this synchronises)."""
+        empty = (self.top_score == float("-inf")) & (self.top_shard == -1) & (self.top_mol == -1) & (self.top_atom == -1)
+        return self.top_score, self.top_shard, self.top_mol, self.top_atom, (self.k - empty.sum(dim=1)).cpu()
+
+
+class _ExemplarStep:
+    """The captured step of ``kernel_exemplars``, a sibling of ``_ScoringStep`` with its batches (``ResidentLoader`` over every id,
+    the short tail filled up) and its front -- ``gather`` -> ``expand`` -> ``attach_receptive_fields`` -- followed by
+    ``model.kernel_scores(data, layer)`` and ONE ``lists.update``.  Per batch the feed row is the ids and the live count.  The model
+    is in evaluation mode already."""
+
+    def __init__(self, model, resident, batch_size: int, layer: int, lists: KernelExemplars, Ls):
+        from .receptive_field import attach_receptive_fields
+        from .shards import ResidentLoader
+        dev = resident.device
+        bs, n = int(batch_size), int(resident.n_molecules)
+        self.loader = loader = ResidentLoader(resident, bs, np.arange(n, dtype=np.int64), dev, drop_last=False)
+        plan, n_live = loader.plan(), loader.n_live
+        rows = np.zeros((plan.shape[0], bs + 1), dtype=np.int32)
+        rows[:, :bs] = plan
+        rows[:, bs] = n_live
+        self.rows = torch.from_numpy(rows).pin_memory().to(dev, non_blocking=True)
+        self.feed = feed = torch.zeros(bs + 1, dtype=torch.int32, device=dev)
+        f_ids, f_live = feed[:bs], feed[bs:bs + 1]
+        self.csb = csb = static_batch_for(loader, resident)
+        begin = [sum(Ls[:d]) for d in range(4)]
+        lists.reserve(csb.data.bucket_sizes, Ls)
+
+        def step(update: bool):
+            csb.gather(resident, f_ids)
+            csb.expand()
+            attach_receptive_fields(csb.data, sizes=csb.data.bucket_sizes, overlap=True)
+            data = csb.data
+            sim = model.kernel_scores(data, layer)[0]
+            if update:
+                lists.update(sim, [getattr(data, f"selected_index_deg{d}") for d in range(1, 5)], begin, data.atom_mol, data.mol_ptr,
+                             f_ids, f_live, data.n_valid_atoms, num_kernels=Ls)
+
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            feed.copy_(self.rows[0], non_blocking=True)
+            step(False)                                  # (eager once: lazily made buffers exist before the capture; no update)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=side):
+                step(True)
+        torch.cuda.current_stream(dev).wait_stream(side)
+
+    def __len__(self):
+        return int(self.rows.shape[0])
+
+    def run(self, b: int) -> None:
+        """Batch ``b`` on the current stream: one small copy and the replay."""
+        self.feed.copy_(self.rows[b], non_blocking=True)
+        self.graph.replay()
+
+
+def kernel_exemplars(model, residents, layer: int, k: int, batch_size: int) -> dict:
+    """What each kernel of convolution layer ``layer`` (0: the 1-hop layer) learned: for every kernel column the ``k`` atoms of the
+    whole library it matches best.  ``residents`` as in ``screen`` (a sequence of ``ResidentShard``s, or a generator that uploads
+    them one at a time); shard ``j`` carries tag ``j``.  Any ``task_dim``: the head is not run.
+
+    Per shard ONE graph is captured and replayed per batch -- ``score_resident``'s batches at this ``batch_size``, the short tail
+    included: ``gather``, ``expand``, ``attach_receptive_fields``, ``model.kernel_scores(data, layer)`` and one
+    ``KernelExemplars.update`` (``mkgnn_kernel_exemplars_update``: only real atoms of live molecules enter, each in the columns of its
+    own degree).  Per batch the host enqueues one small copy and the replay; the gather's status word is read once per shard
+    (non-zero raises).  The model is put in evaluation mode and handed back in the mode it came in.
+
+    Returns ``top_score``, ``top_shard``, ``top_mol``, ``top_atom`` (``[K_layer, k]`` on the device, list ``c`` best first by the order
+    of ``kernel_exemplars_reference``, its empty slots -- ``(-inf, -1, -1, -1)`` -- at the end), ``occupied`` (int64 ``[K_layer]``, on
+    the host), ``column_degree`` and ``column_kernel`` (int32 ``[K_layer]``: column ``c`` is kernel ``column_kernel[c]`` of the bank of
+    degree ``column_degree[c]``) and ``n_scored``, the number of molecules.  ``top_atom`` is the atom's index inside its molecule in
+    the shard's atom order -- the index the rows of ``explain_resident``'s ``atom_ptr`` use.  A score is ``kernel_scores`` of the batch
+    the pass holds the molecule in: re-running that batch gives its bits.
+
+    ``k`` outside ``[1, 64]``, a layer with more than 256 kernels, ``layer`` outside ``[0, num_layers)``, a model or a shard that is
+    not on the GPU, no shard: ``ValueError`` before a launch."""
+    from .train import evaluation_mode
+    who = "kernel_exemplars"
+    k, layer, bs = int(k), int(layer), int(batch_size)
+    if not 1 <= k <= EXEMPLARS_MAX_K:
+        raise ValueError(f"{who}: k = {k} outside [1, {EXEMPLARS_MAX_K}] (MKGNN_EXEMPLARS_MAX_K)")
+    net = model.gnn_model
+    if not 0 <= layer < net.num_layers:
+        raise ValueError(f"{who}: layer = {layer} outside [0, {net.num_layers})")
+    Ls = [int(x) for x in net.gnn.layers[layer].L]
+    K_layer = sum(Ls)
+    if not 1 <= K_layer <= EXEMPLARS_MAX_COLUMNS:
+        raise ValueError(f"{who}: layer {layer} has {K_layer} kernels, outside [1, {EXEMPLARS_MAX_COLUMNS}] (MKGNN_EXEMPLARS_MAX_COLUMNS)")
+    if bs < 1:
+        raise ValueError("batch_size >= 1")
+
+    def per_shard(resident, lists, tag):
+        lists.shard_tag.fill_(int(tag))
+        with evaluation_mode(model):
+            step = _ExemplarStep(model, resident, bs, layer, lists, Ls)
+            for b in range(len(step)):
+                step.run(b)
+            status = step.csb.gather_status()            # (the one host read)
+            if status:
+                raise RuntimeError(f"mkgnn_gather_compact reported status {status} while scoring the shard's atoms")
+
+    top_score, top_shard, top_mol, top_atom, occupied, n_scored, _ = _over_shards(
+        who, residents, lambda r: _check_device(model, r), lambda dev: KernelExemplars(K_layer, k, dev), per_shard, False)
+    column_degree, column_kernel = net.kernel_column_layout(layer, top_score.device)
+    return {"top_score": top_score, "top_shard": top_shard, "top_mol": top_mol, "top_atom": top_atom, "occupied": occupied,
+            "column_degree": column_degree, "column_kernel": column_kernel, "n_scored": n_scored}

@@ -137,6 +137,20 @@ class GNNModel(torch.nn.Module):
         with torch.no_grad():
             return self.gnn_model(data, _atoms=self.ffn)
 
+    def kernel_scores(self, data, layer: int):
+        """``(sim [N, K_layer], column_degree [K_layer], column_kernel [K_layer])``: what every kernel of convolution layer ``layer``
+        (0: the 1-hop layer) scores on every atom, for a model in evaluation mode, under ``torch.no_grad()`` --
+        ``MolKGNNNet.kernel_scores``, which is the definition: the node batch norm, then the public ``KernelSetConv`` layers
+        ``0 .. layer`` with ``MolGCN.propagate`` between them; the layers behind, the readout and the head are not run, so any
+        ``task_dim`` will do.  Row ``n`` holds the scores of atom ``n``'s own degree in that degree's columns (``column_degree``,
+        ``column_kernel``: int32); nothing else of the row may be read.  The best-matching atoms of a library per kernel:
+        ``screening.kernel_exemplars``.  The training and scoring forwards may choose differently among mathematically tied
+        neighbour permutations in a few entries ("Ties"), so their scores can differ from these there.  In training
+        mode, and for a ``layer`` outside ``[0, num_layers)``, this raises ``ValueError``."""
+        self._needs_eval("kernel_scores")
+        with torch.no_grad():
+            return self.gnn_model.kernel_scores(data, layer)
+
     def _loss_kind(self) -> Optional[str]:
         """The loss as a kind of the HIP head (``readout.LOSS_KINDS``), or None: any other loss takes the PyTorch route."""
         lf = self.loss_func
