@@ -1151,6 +1151,57 @@ int mkgnn_kernel_exemplars_update(const float* sim, int64_t sim_stride, int64_t 
                                   const int32_t* shard_tag, int32_t K, int32_t C, float* top_score, int32_t* top_shard,
                                   int32_t* top_mol, int32_t* top_atom, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- analogue search for any number of queries (additive; the ABI version stays 8): fused cosine and top-k.  Q running lists of
+ * K slots each, one per query -- top_sim / top_shard / top_mol ([Q, K], contiguous), updated IN PLACE and always fully sorted; an
+ * empty slot is (-inf, -1, -1) and a list starts out as K of them -- take raw candidate embeddings and raw queries in; no [n, Q]
+ * similarity matrix exists.  Let s_q[i] be the float32 value mkgnn_embed_cosine writes for row i of emb as the ROW and
+ * queries[q] as the QUERY, BIT FOR BIT (its evaluation order above: the two-values-per-lane products, the xor tree with offsets
+ * 16, 8, 4, 2, 1 as a fixed binary tree, the + (+0.0), (dot * inv(row)) * inv(query) in that orientation).  After the call list
+ * q holds the first K entries, sorted, of  old list q  U  {(s_q[i], *shard_tag, ids[i]) : i < min(max(*n_valid, 0), n_rows)}
+ * under mkgnn_topk_update's total order:
+ *   1. occupied slots before empty ones (a real entry whose similarity is -inf ranks before an empty slot)
+ *   2. non-NaN similarities before NaN ones
+ *   3. larger similarities first; -0.0 and +0.0 compare equal
+ *   4. then the lower shard, then the lower id
+ *   5. entries alike in all of that in their order of arrival: the old list first, then the candidates by row
+ * Similarity bits are carried over; repeated (shard, id) pairs are kept; among NaN entries only NaN-ness is specified, not the
+ * payload.  A zero row or a zero query gives +0.0, so a zero query's list holds the lowest (shard, id) pairs; fewer candidates
+ * than K leave empty slots at the end.  ids int32 [n_rows] (NULL: the row index), n_valid and shard_tag DEVICE int32 scalars read
+ * when the launches run (NULL: every row; tag 0), so one captured call serves every batch of every shard.  emb [n_rows, H] with
+ * emb_stride >= H and queries [Q, H] with query_stride >= H, both RAW: the inverse norms are computed inside the call, into the
+ * workspace, so a captured call follows new contents of both.
+ *
+ * The lists of query q depend only on the old list q, the values and ids of the first min(max(*n_valid, 0), n_rows) rows, the
+ * tag and the H values of query q: not on Q or q's index, the rows behind n_valid (never read for their values), either stride,
+ * a row's place in block or grid, or how the launch splits the candidates.  Feeding the same candidates in one call or in
+ * several gives the same lists.
+ *
+ * Two launches on `stream`, three when the candidates are split: the norms; one wave per (query, part of the candidates) -- a
+ * lane takes a candidate, the four waves of a block share every tile of 64 rows through LDS, the list lives one slot per lane,
+ * a ballot under the full order finds the few lanes that get in; and, when Q is too small to fill the chip, a finishing launch
+ * that merges the old list and the parts' lists in part order.  The split: parts of whole tiles, at least two tiles each, at
+ * most 32 parts, and no more than bring the grid to 1 024 blocks of four queries -- so the candidates are split only where
+ * Q <= 4 092, and the parts' lists in the workspace never exceed 32 times the lists' own size, nor 2 047 * 4 * K entries of 12
+ * bytes (6 MiB at K = 64) whatever Q.  Capturable, no host round trip, no atomics, no process-wide or thread-local state, one
+ * writer per output; integer comparisons on the order's key.  The workspace (4-byte aligned,
+ * mkgnn_embed_knn_workspace_bytes(n_rows, Q, K) bytes -- 4 (Q + n_rows) of norms plus the parts' lists; 0 for rejected sizes)
+ * needs no initialisation: it is read only where the same call wrote it.  Plain FP32: the bit contract forbids the matrix
+ * instructions' summation order.
+ *
+ * Limits: 1 <= H <= 64; 1 <= K <= MKGNN_KNN_MAX_K (one slot per lane of a wave); 1 <= Q <= MKGNN_KNN_MAX_QUERIES;
+ * 0 <= n_rows <= MKGNN_KNN_MAX_ROWS (more rows: call per chunk -- the lists run on).  n_rows == 0 is a no-op that returns 0, even
+ * with null pointers.  Anything else -- a limit, a stride below H, a null emb, queries, list or workspace, a workspace that is too
+ * small or misaligned, list arrays that overlap an input, the workspace or each other -- returns non-zero with mkgnn_last_error
+ * set, before any launch. */
+#define MKGNN_KNN_MAX_K       64
+#define MKGNN_KNN_MAX_QUERIES 1048576
+#define MKGNN_KNN_MAX_ROWS    1048576
+size_t mkgnn_embed_knn_workspace_bytes(int64_t n_rows, int32_t Q, int32_t K);
+int mkgnn_embed_knn_update(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const int32_t* ids,
+                           const int32_t* n_valid, const int32_t* shard_tag, const float* queries, int64_t query_stride, int32_t Q,
+                           int32_t K, float* top_sim, int32_t* top_shard, int32_t* top_mol, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

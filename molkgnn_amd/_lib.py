@@ -32,6 +32,10 @@ DIVERSE_COVER_ROWS, DIVERSE_COVER_TILE = 128, 32
 EXEMPLARS_MAX_K, EXEMPLARS_MAX_COLUMNS = 64, 256        # MKGNN_EXEMPLARS_MAX_K, MKGNN_EXEMPLARS_MAX_COLUMNS
 # kgnn_exemplars.hip's tiling (EX_TILE, EX_CHUNK): degree-bucket slots per tile and columns per workgroup of the runs launch
 EXEMPLARS_TILE, EXEMPLARS_CHUNK = 128, 64
+KNN_MAX_K, KNN_MAX_QUERIES, KNN_MAX_ROWS, KNN_MAX_H = 64, 1 << 20, 1 << 20, 64   # MKGNN_KNN_MAX_*, mkgnn_embed_knn_update's widest embedding
+# kgnn_knn.hip's tiling (KNN_WAVES, KNN_TILE, KNN_MIN_PART_TILES, KNN_MAX_PARTS, KNN_TARGET_BLOCKS): queries (= waves) per block,
+# candidate rows per LDS tile, the fewest tiles of a part, the most parts a launch splits the candidates into, the blocks it aims at
+KNN_WAVES, KNN_TILE, KNN_MIN_PART_TILES, KNN_MAX_PARTS, KNN_TARGET_BLOCKS = 4, 64, 2, 32, 1024
 
 
 def diverse_tile(H: int) -> int:
@@ -52,6 +56,17 @@ def max_cosine_split(n_rows: int, R: int):
     want = min(-(-MAX_COSINE_TARGET_BLOCKS // row_blocks), tiles, MAX_COSINE_MAX_PARTS)
     per_part = -(-tiles // want)
     return per_part * MAX_COSINE_TILE, -(-tiles // per_part)
+
+
+def knn_split(n_rows: int, Q: int):
+    """``(rows per part, parts)`` of one ``mkgnn_embed_knn_update`` launch (``knn_split``, kgnn_knn.hip): whole tiles per part, at
+    least ``KNN_MIN_PART_TILES`` of them, at most ``KNN_MAX_PARTS`` parts and no more than bring the grid to ``KNN_TARGET_BLOCKS``
+    blocks of ``KNN_WAVES`` queries.  The result of a call does not depend on it; the tests place their shapes around it."""
+    query_blocks = -(-int(Q) // KNN_WAVES)
+    tiles = -(-int(n_rows) // KNN_TILE)
+    want = min(-(-KNN_TARGET_BLOCKS // query_blocks), KNN_MAX_PARTS)
+    per_part = max(-(-tiles // want), KNN_MIN_PART_TILES)
+    return per_part * KNN_TILE, max(-(-tiles // per_part), 1)
 
 
 class KernelBank(C.Structure):
@@ -217,7 +232,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_atom_contributions", "mkgnn_atom_contributions_workspace_bytes", "mkgnn_embed_max_cosine",
            "mkgnn_embed_max_cosine_workspace_bytes", "mkgnn_select_rows", "mkgnn_tail_defer_projection",
            "mkgnn_debug_tail_projection_launches", "mkgnn_diverse_pick", "mkgnn_diverse_pick_workspace_bytes",
-           "mkgnn_kernel_exemplars_update", "mkgnn_kernel_exemplars_workspace_bytes")
+           "mkgnn_kernel_exemplars_update", "mkgnn_kernel_exemplars_workspace_bytes", "mkgnn_embed_knn_update",
+           "mkgnn_embed_knn_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -432,6 +448,11 @@ def load() -> C.CDLL:
     lib.mkgnn_kernel_exemplars_update.restype = C.c_int
     lib.mkgnn_kernel_exemplars_update.argtypes = [P, I64, I64, C.POINTER(Buckets4), C.POINTER(Int32x4), C.POINTER(Int32x4), P, P, P,
                                                   I32, P, P, P, I32, I32, P, P, P, P, P, C.c_size_t, P]
+    # fused cosine and top-k: (emb, stride, n_rows, H, ids, n_valid, shard_tag, queries, stride, Q, K, the [Q, K] lists, workspace, bytes, stream)
+    lib.mkgnn_embed_knn_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_embed_knn_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.mkgnn_embed_knn_update.restype = C.c_int
+    lib.mkgnn_embed_knn_update.argtypes = [P, I64, I64, I32, P, P, P, P, I64, I32, I32, P, P, P, P, C.c_size_t, P]
     lib.mkgnn_rf_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_rf_workspace_bytes.argtypes = [I64]
     lib.mkgnn_rf_count.restype = C.c_int

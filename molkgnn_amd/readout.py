@@ -1069,6 +1069,133 @@ def select_rows(scores: torch.Tensor, ids: torch.Tensor, key: torch.Tensor, n_va
     return tuple(out)
 
 
+def embedding_knn_supported(H: int, K: int) -> bool:
+    """The shapes ``mkgnn_embed_knn_update`` takes: an embedding of ``1 <= H <= 64`` columns and lists of ``1 <= K <= 64`` slots.  A
+    wider embedding goes through torch operators on the GPU; longer lists are ``screening.rank_embeddings``'s."""
+    return 1 <= H <= _lib.KNN_MAX_H and 1 <= K <= _lib.KNN_MAX_K
+
+
+KNN_TORCH_CHUNK = 4096                # rows per step of the torch route: no similarity matrix beyond [4096, Q] exists
+
+
+def _knn_scalar(value, name: str, dev) -> Optional[torch.Tensor]:
+    if value is None:
+        return None
+    if torch.is_tensor(value):
+        if value.dtype != torch.int32 or value.numel() != 1 or value.device != dev:
+            raise ValueError(f"{name}: one int32 on the lists' device, or an int")
+        return value
+    return torch.tensor([int(value)], dtype=torch.int32, device=dev)
+
+
+def _knn_rank(sim: torch.Tensor, shard: torch.Tensor, mol: torch.Tensor) -> torch.Tensor:
+    """The similarity's rank of ``screening.topk_update_reference`` as an int64 key, smaller = earlier: non-NaN descending with
+    ``-0.0`` as ``+0.0``, then NaN, then an empty slot ``(-inf, -1, -1)``."""
+    bits = sim.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    b = torch.where(bits == 0x80000000, torch.zeros_like(bits), bits)
+    key = torch.where((b & 0x80000000) != 0, b, ~(b | 0x80000000) & 0xFFFFFFFF)
+    key = torch.where(torch.isnan(sim), torch.full_like(key, 0xFFFFFFFE), key)
+    empty = (bits == 0xFF800000) & (shard == -1) & (mol == -1)
+    return torch.where(empty, torch.full_like(key, 0xFFFFFFFF), key)
+
+
+def _knn_update_torch(emb, queries, top_sim, top_shard, top_mol, ids, n_valid, shard_tag) -> None:
+    """``embedding_knn_update`` for an embedding wider than the kernel takes: ``embedding_cosine``'s torch route per chunk of
+    ``KNN_TORCH_CHUNK`` rows, then the total order by three stable sorts (id, shard, rank) of ``[old list | chunk]`` per query.  No
+    host round trip: a row at or behind ``n_valid`` gets a rank behind the empty slot's and leaves as an empty slot."""
+    n, dev = emb.shape[0], emb.device
+    Q, K = top_sim.shape
+    for a in range(0, n, KNN_TORCH_CHUNK):
+        b = min(a + KNN_TORCH_CHUNK, n)
+        sim = embedding_cosine(emb[a:b], queries, query_major=True)                       # [Q, c]
+        row = torch.arange(a, b, dtype=torch.int32, device=dev)
+        mol = (row if ids is None else ids[a:b])[None, :].expand(Q, -1)
+        tag = torch.zeros(1, dtype=torch.int32, device=dev) if shard_tag is None else shard_tag.reshape(1)
+        shard = tag[None, :].expand(Q, b - a)
+        s, h, m = torch.cat([top_sim, sim], 1), torch.cat([top_shard, shard], 1), torch.cat([top_mol, mol], 1)
+        rank = _knn_rank(s, h, m)
+        if n_valid is not None:
+            out = torch.cat([torch.zeros(K, dtype=torch.bool, device=dev), row >= n_valid.reshape(1)])
+            rank = torch.where(out[None, :], torch.full_like(rank, 1 << 32), rank)
+        order = torch.sort(m, dim=1, stable=True).indices
+        order = order.gather(1, torch.sort(h.gather(1, order), dim=1, stable=True).indices)
+        order = order.gather(1, torch.sort(rank.gather(1, order), dim=1, stable=True).indices)[:, :K]
+        gone = rank.gather(1, order) == (1 << 32)
+        top_sim.copy_(torch.where(gone, torch.full_like(top_sim, float("-inf")), s.gather(1, order)))
+        top_shard.copy_(torch.where(gone, torch.full_like(top_shard, -1), h.gather(1, order)))
+        top_mol.copy_(torch.where(gone, torch.full_like(top_mol, -1), m.gather(1, order)))
+
+
+def embedding_knn_update(emb: torch.Tensor, queries: torch.Tensor, top_sim: torch.Tensor, top_shard: torch.Tensor,
+                         top_mol: torch.Tensor, ids: Optional[torch.Tensor] = None, n_valid=None, shard_tag=None,
+                         workspace: Optional[torch.Tensor] = None) -> None:
+    """Fused cosine and top-k for any number of queries: the running lists ``top_sim`` float32, ``top_shard`` int32, ``top_mol`` int32
+    (``[Q, K]``, contiguous, on the GPU; an empty slot is ``(-inf, -1, -1)``) are updated IN PLACE -- list ``q`` becomes
+    ``screening.topk_update_reference`` of itself and the entries ``(sim[i, q], shard_tag, ids[i])`` of the rows ``i < n_valid`` of a
+    float32 CUDA ``emb [n, H]``, where ``sim[i, q]`` is what ``embedding_cosine`` gives for row ``i`` and row ``q`` of a float32 CUDA
+    ``queries [Q, H]``, BIT FOR BIT.  One ``mkgnn_embed_knn_update``: both inputs are read raw, no ``[n, Q]`` matrix exists, and a
+    captured call follows the contents of ``emb``, ``queries``, ``ids`` and the device scalars.  ``ids``: contiguous int32 ``[n]`` on the
+    device (None: the row index).  ``n_valid`` / ``shard_tag``: one-element int32 device tensors read when the launch runs, or ints
+    (uploaded first), or None (every row; tag 0).  ``workspace``: as in ``embedding_max_cosine``.  The list of a query depends on its
+    old list, the candidates, the tag and the query's own values alone: not on ``Q``, the strides or how the launch splits the rows.
+
+    An embedding wider than 64 runs the same definition through torch operators on the GPU, ``KNN_TORCH_CHUNK`` rows at a time
+    (``embedding_cosine``'s float64 route: inside ``screening.cosine_bound``, not the kernel's bits).  ``K > 64`` raises: longer lists
+    are ``screening.rank_embeddings``'s.  Every check raises ``ValueError`` before a launch.  It has no autograd node: called where a
+    gradient is being recorded for one of its inputs it raises instead of dropping it."""
+    if not (torch.is_tensor(emb) and torch.is_tensor(queries)) or emb.dim() != 2 or queries.dim() != 2 \
+            or emb.dtype != torch.float32 or queries.dtype != torch.float32:
+        raise ValueError("embedding_knn_update needs a float32 [n, H] embedding and float32 [Q, H] queries")
+    if queries.shape[1] != emb.shape[1]:
+        raise ValueError(f"embedding_knn_update: the queries are {int(queries.shape[1])} wide, the embedding is {int(emb.shape[1])} wide")
+    (Q, H), n = queries.shape, emb.shape[0]
+    if H < 1 or not 1 <= Q <= _lib.KNN_MAX_QUERIES:
+        raise ValueError(f"embedding_knn_update needs 1 to {_lib.KNN_MAX_QUERIES} queries (MKGNN_KNN_MAX_QUERIES) and at least one "
+                         f"column, not {Q} x {H}")
+    lists = (top_sim, top_shard, top_mol)
+    if not all(torch.is_tensor(t) and t.dim() == 2 for t in lists) or top_sim.dtype != torch.float32 \
+            or top_shard.dtype != torch.int32 or top_mol.dtype != torch.int32:
+        raise ValueError("embedding_knn_update: the lists are top_sim float32, top_shard int32, top_mol int32, each [Q, K]")
+    K = int(top_sim.shape[1])
+    if K > _lib.KNN_MAX_K:
+        raise ValueError(f"embedding_knn_update: K = {K} above {_lib.KNN_MAX_K} (MKGNN_KNN_MAX_K: one slot per lane of a wave); longer "
+                         "lists are screening.rank_embeddings's, per group of 32 queries")
+    if K < 1:
+        raise ValueError(f"embedding_knn_update: K = {K} outside [1, {_lib.KNN_MAX_K}] (MKGNN_KNN_MAX_K)")
+    if any(tuple(t.shape) != (Q, K) for t in lists):
+        raise ValueError(f"embedding_knn_update: the lists are [{Q}, {K}] each, one row per query")
+    if not all(t.is_contiguous() for t in lists):
+        raise ValueError("embedding_knn_update: the lists are contiguous")
+    if n > _lib.KNN_MAX_ROWS:
+        raise ValueError(f"embedding_knn_update: {n} rows above {_lib.KNN_MAX_ROWS} (MKGNN_KNN_MAX_ROWS): call per chunk of rows "
+                         "(screening.nearest_embeddings does)")
+    dev = emb.device
+    if not emb.is_cuda or queries.device != dev or any(t.device != dev for t in lists):
+        raise ValueError(f"embedding_knn_update runs on the GPU: emb is on {emb.device}, queries on {queries.device}, the lists on "
+                         f"{top_sim.device} (there is no CPU path; screening.topk_update_tasks_reference is the host form)")
+    if ids is not None and (not torch.is_tensor(ids) or ids.dtype != torch.int32 or ids.device != dev or tuple(ids.shape) != (n,)
+                            or not ids.is_contiguous()):
+        raise ValueError(f"embedding_knn_update: ids is a contiguous int32 [{n}] tensor on {dev}")
+    if torch.is_grad_enabled() and (emb.requires_grad or queries.requires_grad):
+        raise RuntimeError("embedding_knn_update is forward only: call it under torch.no_grad() (or on detached inputs)")
+    n_valid, shard_tag = _knn_scalar(n_valid, "n_valid", dev), _knn_scalar(shard_tag, "shard_tag", dev)
+    if n == 0:
+        return
+    emb, queries = emb.detach(), queries.detach()
+    if not embedding_knn_supported(H, K):
+        _knn_update_torch(emb, queries, top_sim, top_shard, top_mol, ids, n_valid, shard_tag)
+        return
+    emb, queries = _row_major(emb), _row_major(queries)
+    lib = _lib.load()
+    ws = _max_cosine_workspace(dev, int(lib.mkgnn_embed_knn_workspace_bytes(n, Q, K)), workspace)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkgnn_embed_knn_update(emb.data_ptr(), _stride0(emb), n, H, None if ids is None else ids.data_ptr(),
+                                              None if n_valid is None else n_valid.data_ptr(),
+                                              None if shard_tag is None else shard_tag.data_ptr(), queries.data_ptr(),
+                                              _stride0(queries), Q, K, top_sim.data_ptr(), top_shard.data_ptr(), top_mol.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_embed_knn_update")
+
+
 def diverse_pick_supported(n: int, H: int) -> bool:
     """The shapes ``mkgnn_diverse_pick`` takes; anything else goes through torch operators on the GPU."""
     return 1 <= n <= _lib.DIVERSE_MAX_ROWS and 1 <= H <= _lib.DIVERSE_MAX_H

@@ -23,6 +23,15 @@ Analogue search -- the library molecules whose graph embeddings lie closest, by 
 ``nearest``                              shards -> the ``k`` nearest molecules per query
 ``rank_embeddings``                      the same ranking from a stored embedding matrix
 
+The analogues of ANY number of queries -- every confirmed active of an assay -- in one pass: fused cosine and top-k
+(``mkgnn_embed_knn_update``: raw embeddings and raw queries in, one sorted list per query updated in place, no similarity matrix;
+the similarities and the order are those above, bit for bit; lists of at most 64 entries):
+
+``NearestLists``                         ``Q`` running lists on the device (``[Q, k]`` tensors), ``k <= 64``, ``Q`` up to 2^20
+``nearest_many_resident``                one captured pass over a resident shard feeding the ``Q`` lists; returns its embeddings
+``nearest_many``                         shards -> the ``k`` nearest molecules per query, ``nearest``'s keys without ``sims``
+``nearest_embeddings``                   the same ranking from a stored embedding matrix
+
 Why a hit scores what it scores -- every atom's exact share of every output (``GNNModel.atom_contributions``,
 ``mkgnn_atom_contributions``):
 
@@ -690,8 +699,9 @@ def nearest(model, queries, residents, k: int, batch_size: int, return_sims: boo
     ``[n_molecules, Q]`` tensors.
 
     ``cos(e, e)`` is 1 only to within ``cosine_bound``; a query that is itself in the library is not excluded (it heads its list, or
-    ties with its duplicates); ties follow ``topk_update_reference``.  More than 32 queries: embed the library once
-    (``embed_resident``) and call ``rank_embeddings`` per group of 32."""
+    ties with its duplicates); ties follow ``topk_update_reference``.  More than 32 queries: ``nearest_many`` (lists of at most 64
+    entries, one pass over the library); for longer lists embed the library once (``embed_resident``) and call ``rank_embeddings``
+    per group of 32."""
     from .shards import ResidentShard
     G = _embedding_width(model)
     if isinstance(queries, ResidentShard):
@@ -755,6 +765,183 @@ def rank_embeddings(emb: torch.Tensor, query_emb: torch.Tensor, topk: TopKTasks,
     for a in range(0, n, chunk):
         b = min(a + chunk, n)
         topk.update(embedding_cosine(emb[a:b], query_emb), ids[a:b], n_valid=b - a, shard_tag=int(shard_tag))
+
+
+# ------------------------------------------------------------------------------- analogues of many queries --
+# "Show me the analogues of every confirmed active": a few hundred queries, not 32.  ``mkgnn_embed_knn_update`` takes raw
+# candidate embeddings and raw queries in and updates one sorted running list per query in place -- any number of queries, no
+# similarity matrix -- so the whole search is ONE pass over the library, inside the captured scoring step.  The similarities are
+# ``mkgnn_embed_cosine``'s bit for bit and the order is ``topk_update_reference``'s, so for ``Q <= 32`` the lists are those of
+# ``nearest`` / ``rank_embeddings``.  Lists hold at most 64 entries each (one slot per lane of a wave); longer ones stay with
+# ``rank_embeddings``.
+class NearestLists(TopK):
+    """``n_queries`` running lists of ``k`` slots each on ``device`` -- ``top_score`` (the similarity) float32, ``top_shard`` int32,
+    ``top_mol`` int32 of shape ``[n_queries, k]``, list ``q`` always sorted by the order of ``topk_update_reference`` -- fed by
+    ``mkgnn_embed_knn_update`` with candidate EMBEDDINGS and the queries themselves: ``TopKTasks`` without its cap of 32 lists
+    (``1 <= n_queries <= 2^20``) and with ``1 <= k <= 64``.  ``TopK``'s contract otherwise: ``n_valid`` and ``shard_tag`` are device
+    scalars read when the launch runs, so one captured ``update`` serves every batch of every shard; ``reserve`` before a capture,
+    nothing is allocated inside one."""
+
+    _WHOSE = "lists'"
+
+    def __init__(self, k: int, n_queries: int, device):
+        from . import _lib
+        self.n_queries = int(n_queries)
+        if not 1 <= int(k) <= _lib.KNN_MAX_K:
+            raise ValueError(f"k = {k} outside [1, {_lib.KNN_MAX_K}] (MKGNN_KNN_MAX_K: one slot per lane of a wave; longer lists are "
+                             "rank_embeddings's, per group of 32 queries)")
+        if not 1 <= self.n_queries <= _lib.KNN_MAX_QUERIES:
+            raise ValueError(f"n_queries = {n_queries} outside [1, {_lib.KNN_MAX_QUERIES}] (MKGNN_KNN_MAX_QUERIES)")
+        self._allocate(k, device, (self.n_queries, int(k)))
+
+    def _workspace_bytes(self, batch: int) -> int:
+        from . import _lib
+        return int(_lib.load().mkgnn_embed_knn_workspace_bytes(int(batch), self.n_queries, self.k))
+
+    def reserve(self, n_rows: int) -> None:
+        """Make the workspace large enough for updates of ``n_rows`` candidate rows (before a capture: a captured update must not
+        allocate)."""
+        super().reserve(n_rows)
+
+    def update(self, emb: torch.Tensor, queries: torch.Tensor, ids: Optional[torch.Tensor] = None, n_valid=None,
+               shard_tag=None) -> None:
+        """One ``readout.embedding_knn_update`` on the current stream: list ``q`` becomes the best ``k`` of itself and the first
+        ``n_valid`` entries ``(cosine(emb[i], queries[q]), shard_tag, ids[i])``.  ``emb`` float32 ``[n, G]`` and ``queries`` float32
+        ``[n_queries, G]`` on the lists' device, both read raw; ``ids`` contiguous int32 ``[n]`` (None: the row index).  ``n_valid`` /
+        ``shard_tag``: as in ``TopK.update``."""
+        from .readout import embedding_knn_update
+        if not torch.is_tensor(queries) or queries.dim() != 2 or int(queries.shape[0]) != self.n_queries:
+            raise ValueError(f"queries: a [{self.n_queries}, G] tensor, one row per list")
+        if not torch.is_tensor(emb) or emb.dim() != 2 or emb.device != self.device:
+            raise ValueError(f"emb: a float32 [n, G] tensor on the {self._WHOSE} device")
+        nv, tag = self._scalar(self.n_valid, n_valid), self._scalar(self.shard_tag, shard_tag)
+        from . import _lib
+        if 1 <= int(emb.shape[0]) <= _lib.KNN_MAX_ROWS:      # (anything else: embedding_knn_update says what is wrong)
+            self.reserve(int(emb.shape[0]))
+        embedding_knn_update(emb, queries, self.top_score, self.top_shard, self.top_mol, ids=ids, n_valid=nv, shard_tag=tag,
+                             workspace=self.workspace)
+
+    def result(self):
+        """``(top_sim, top_shard, top_mol, n_occupied)``: the three ``[n_queries, k]`` tensors (not copies) and the number of occupied
+        slots of every list -- they come first -- as a host int64 tensor ``[n_queries]`` (this synchronises)."""
+        empty = (self.top_score == float("-inf")) & (self.top_shard == -1) & (self.top_mol == -1)
+        return self.top_score, self.top_shard, self.top_mol, (self.k - empty.sum(dim=1)).cpu()
+
+
+def _check_many_queries(who: str, query_emb, G: int, dev=None) -> int:
+    """``_check_queries`` without the cap of 32: float32 ``[Q, G]``, ``1 <= Q <= 2^20``, on ``dev`` -- the value checks first, the device
+    last; ``ValueError`` otherwise, before anything is loaded or launched."""
+    from . import _lib
+    if not torch.is_tensor(query_emb) or query_emb.dim() != 2:
+        raise ValueError(f"{who}: the queries are a [Q, {G}] tensor of embeddings")
+    if query_emb.dtype != torch.float32:
+        raise ValueError(f"{who}: the queries are float32, not {query_emb.dtype}")
+    Q = int(query_emb.shape[0])
+    if not 1 <= Q <= _lib.KNN_MAX_QUERIES:
+        raise ValueError(f"{who}: {Q} queries outside [1, {_lib.KNN_MAX_QUERIES}] (MKGNN_KNN_MAX_QUERIES: one list per query)")
+    if int(query_emb.shape[1]) != int(G):
+        raise ValueError(f"{who}: the queries are {int(query_emb.shape[1])} wide, the embedding is {int(G)} wide")
+    if query_emb.device.type != "cuda" or (dev is not None and query_emb.device != dev):
+        raise ValueError(f"{who}: the queries are on {query_emb.device}; they belong on the GPU of the library" +
+                         ("" if dev is None else f" ({dev})"))
+    return Q
+
+
+def _check_lists(who: str, lists, Q: int, dev) -> None:
+    if not isinstance(lists, NearestLists) or lists.n_queries != Q:
+        raise ValueError(f"{who}: the running lists must be a NearestLists of {Q} lists, one per query")
+    if lists.device != dev:
+        raise ValueError(f"the running lists are on {lists.device}, the " + ("model" if who != "nearest_embeddings" else "embeddings") +
+                         f" on {dev}")
+
+
+def nearest_many_resident(model, resident, query_emb: torch.Tensor, batch_size: int, *, lists: NearestLists,
+                          shard_tag: int = 0) -> torch.Tensor:
+    """One pass over a ``ResidentShard`` that feeds every molecule's graph embedding to the ``Q`` running lists of ``lists`` (a
+    ``NearestLists`` of ``Q = query_emb.shape[0]`` lists) under ``shard_tag``; returns the shard's ``[n_molecules, G]`` embeddings
+    (float32, on the device), as ``embed_resident`` does.  One graph is captured per call and replayed per batch, as in
+    ``score_resident``: the step's result is ``model.embed(data)`` and its ranking, inside the capture, is
+    ``lists.update(emb, query_emb, ids, n_valid=n_live)`` -- ONE ``mkgnn_embed_knn_update`` behind the network, for any number of
+    queries, with no similarity matrix; fillers never enter a list.  ``query_emb``: float32 ``[Q, G]`` on the shard's GPU, read raw by
+    every replay.  A wrong ``Q``, ``G``, dtype or device, or ``lists`` that are not a ``NearestLists`` of ``Q`` lists on the model's
+    GPU, raises ``ValueError`` before a launch.  The model may have any ``task_dim`` and comes back in the mode it came in."""
+    G = _embedding_width(model)
+    Q = _check_many_queries("nearest_many_resident", query_emb, G)
+    dev = _check_device(model, resident)
+    _check_many_queries("nearest_many_resident", query_emb, G, dev)
+    _check_lists("nearest_many_resident", lists, Q, dev)
+    bs = int(batch_size)
+    if bs < 1:
+        raise ValueError("batch_size >= 1")
+    queries = query_emb.detach()
+    lists.reserve(bs)
+    lists.shard_tag.fill_(int(shard_tag))
+    return _run_shard("nearest_many_resident", "embedding", model, resident, dev, bs, model.embed, (G,),
+                      rank=lambda emb, ids, n_live: lists.update(emb, queries, ids, n_valid=n_live))
+
+
+def nearest_many(model, queries, residents, k: int, batch_size: int) -> dict:
+    """Analogue search for ANY number of queries: the ``k <= 64`` molecules of a library whose graph embeddings lie closest, by cosine
+    similarity, to each query -- ``nearest`` without its cap of 32 queries, in one pass over the library (the network runs once
+    per molecule, whatever ``Q`` is).  ``queries``: a float32 ``[Q, G]`` tensor of embeddings on the model's GPU, or a
+    ``ResidentShard`` of any number of query molecules (the confirmed actives of an assay), which is embedded with ``embed_resident``
+    first.  ``residents``: as in ``nearest``; shard ``j`` carries tag ``j``.  One ``NearestLists`` of ``Q x k`` slots is carried across
+    the shards on the device.  Returns ``nearest``'s keys: ``top_sim``, ``top_shard``, ``top_mol`` as ``[Q, k]`` tensors, list ``q``
+    nearest first with its empty slots -- ``(-inf, -1, -1)`` -- at the end; ``n_occupied`` (int64 ``[Q]``, on the host);
+    ``n_searched``; ``query_emb``.  There is no ``sims``: no such matrix exists.
+
+    The similarities are ``nearest``'s bit for bit and so are the lists.  ``cos(e, e)`` is 1 only to within ``cosine_bound``; a query
+    that is itself in the library is not excluded; ties follow ``topk_update_reference``."""
+    from . import _lib
+    from .shards import ResidentShard
+    G = _embedding_width(model)
+    if not 1 <= int(k) <= _lib.KNN_MAX_K:
+        raise ValueError(f"nearest_many: k = {k} outside [1, {_lib.KNN_MAX_K}] (MKGNN_KNN_MAX_K; longer lists are rank_embeddings's, per "
+                         "group of 32 queries)")
+    if isinstance(queries, ResidentShard):
+        if not 1 <= int(queries.n_molecules) <= _lib.KNN_MAX_QUERIES:
+            raise ValueError(f"nearest_many: a query shard holds 1 to {_lib.KNN_MAX_QUERIES} molecules, not {int(queries.n_molecules)}")
+        query_emb = embed_resident(model, queries, batch_size)
+    else:
+        query_emb = queries
+    dev = next(model.parameters()).device
+    Q = _check_many_queries("nearest_many", query_emb, G, dev if dev.type == "cuda" else None)
+    if dev.type != "cuda":
+        raise ValueError("nearest_many runs on the GPU: move the model there (there is no CPU path)")
+    top_sim, top_shard, top_mol, occupied, n_searched, _ = _over_shards(
+        "nearest_many", residents, lambda r: _check_device(model, r), lambda dev: NearestLists(k, Q, dev),
+        lambda r, lists, tag: nearest_many_resident(model, r, query_emb, batch_size, lists=lists, shard_tag=tag), False)
+    return {"top_sim": top_sim, "top_shard": top_shard, "top_mol": top_mol, "n_occupied": occupied, "n_searched": n_searched,
+            "query_emb": query_emb}
+
+
+def nearest_embeddings(emb: torch.Tensor, query_emb: torch.Tensor, lists: NearestLists, ids: Optional[torch.Tensor] = None,
+                       shard_tag: int = 0) -> None:
+    """The stored-embedding route for any number of queries: rank the rows of ``emb`` (float32 ``[n, G]`` on the GPU, e.g. kept from
+    ``embed_resident``) against ``query_emb`` (float32 ``[Q, G]``) into ``lists`` (a ``NearestLists`` of ``Q`` lists) WITHOUT running the
+    network: one ``lists.update`` -- one ``mkgnn_embed_knn_update`` -- per ``MKGNN_KNN_MAX_ROWS`` (2^20) rows, launched eagerly.  Row
+    ``i`` enters as ``(sim[i, q], shard_tag, ids[i])``; ``ids`` (int32 ``[n]`` on the GPU) defaults to ``arange(n)``.  For ``Q <= 32``
+    the lists are ``rank_embeddings``'s bit for bit.  ``cos(e, e)`` is 1 only to within ``cosine_bound``; a query that is itself in
+    the library is not excluded; ties follow ``topk_update_reference``."""
+    from . import _lib
+    if not torch.is_tensor(emb) or emb.dim() != 2 or emb.dtype != torch.float32 or emb.shape[1] < 1:
+        raise ValueError("nearest_embeddings: emb is a float32 [n, G] tensor")
+    n, G = int(emb.shape[0]), int(emb.shape[1])
+    Q = _check_many_queries("nearest_embeddings", query_emb, G)
+    if not emb.is_cuda:
+        raise ValueError(f"nearest_embeddings: emb is on {emb.device}; the ranking runs on the GPU (there is no CPU path)")
+    dev = emb.device
+    _check_many_queries("nearest_embeddings", query_emb, G, dev)
+    _check_lists("nearest_embeddings", lists, Q, dev)
+    if ids is not None and (not torch.is_tensor(ids) or ids.dtype != torch.int32 or ids.device != dev or ids.dim() != 1
+                            or ids.numel() != n or not ids.is_contiguous()):
+        raise ValueError(f"nearest_embeddings: ids is a contiguous int32 [{n}] tensor on {dev}")
+    emb, query_emb = emb.detach(), query_emb.detach()
+    step = _lib.KNN_MAX_ROWS
+    for a in range(0, n, step):
+        b = min(a + step, n)
+        piece = ids[a:b] if ids is not None else None if a == 0 else torch.arange(a, b, dtype=torch.int32, device=dev)
+        lists.update(emb[a:b], query_emb, piece, n_valid=b - a, shard_tag=int(shard_tag))
 
 
 # ---------------------------------------------------------------------------------------------- novel hits --
