@@ -22,6 +22,20 @@ int api_fail(const char* fmt, ...) {
     return 1;
 }
 int api_hip_fail(const char* what, hipError_t e) { return api_fail("%s: %s", what, hipGetErrorString(e)); }
+int spans_disjoint(const char* who, const Span* writes, int n_writes, const Span* reads, int n_reads, const char* reads_text,
+                   const char* writes_text) {
+    auto overlap = [](const Span& x, const Span& y) {
+        const char *xp = (const char*)x.p, *yp = (const char*)y.p;
+        return x.n && y.n && xp < yp + y.n && yp < xp + x.n;
+    };
+    for (int i = 0; i < n_writes; ++i) {
+        for (int j = 0; j < n_reads; ++j)
+            if (overlap(writes[i], reads[j])) return api_fail("%s: %s", who, reads_text);
+        for (int j = i + 1; j < n_writes; ++j)
+            if (overlap(writes[i], writes[j])) return api_fail("%s: %s", who, writes_text);
+    }
+    return 0;
+}
 }  // namespace mkgnn
 
 // The four degree buckets are independent.  At the batch sizes a molecule model sees, one bucket

@@ -6,7 +6,7 @@
 //     covered and covers nothing.  Otherwise the FIRST pick p so far (in pick order) with S[i, p] > max_sim (strict; a NaN never
 //     covers) is its leader; without one the row becomes a pick itself while fewer than k_max exist, and keeps (-1, NaN) after.
 //
-// THE BITS come from what exists: mc_dot and inv_clamped_norm (kgnn_head_terms.h) are the text kgnn_max_cosine.hip compiles, the
+// THE BITS come from what exists: mc_dot and inv_clamped_norm (kgnn_cosine.h) are the text kgnn_max_cosine.hip compiles, the
 // init launch runs half_wave_sumsq -- the function embed_cosine_kernel calls -- and forms S[i, i] from it the way that kernel
 // does (for a row against itself the dot product IS the sum of squares: the same products, fmaf and tree).  Nothing in this file
 // may be contracted.
@@ -38,7 +38,7 @@
 #include "kgnn_common.h"
 
 #include "kgnn_launch.h"
-#include "kgnn_head_terms.h"
+#include "kgnn_cosine.h"
 #include "../../include/molkgnn_hip.h"
 
 #pragma clang fp contract(off)
@@ -64,8 +64,7 @@ __global__ void __launch_bounds__(256) init_kernel(const float* __restrict__ emb
     const int h = threadIdx.x & 31;
     const int v = blockIdx.x * 8 + (threadIdx.x >> 5);           // (n <= 2^20: every index fits an int)
     const int vc = v < n ? v : n - 1;                             // (clamped: every lane of a half-wave takes part in the tree)
-    const float* row = emb + (int64_t)vc * es;
-    const float s = half_wave_sumsq(row[h < H ? h : 0], row[32 + h < H ? 32 + h : 0], h, H);
+    const float s = half_wave_row_sumsq(emb + (int64_t)vc * es, h, H);
     if (h != 0 || v >= n) return;
     const float ie = inv_clamped_norm(s);
     inv[v] = ie;
@@ -189,16 +188,9 @@ __global__ void __launch_bounds__(DV_COVER_ROWS) diverse_cover_kernel(const floa
     for (int r0 = c0; r0 < c1; r0 += DV_COVER_TILE) {
         const int m = min(DV_COVER_TILE, c1 - r0);
         if (!__syncthreads_or(open)) break;                      // (also: the previous tile has been walked by every wave)
-        for (int j = t; j < m * W; j += DV_COVER_ROWS) {
-            const int r = j / W, c = j - r * W;
-            const int p = min(max(picks[r0 + r], 0), n - 1);
-            tile[j] = c < H ? emb[(int64_t)p * es + c] : 0.f;
-        }
-        if (t < m) {
-            const int p = min(max(picks[r0 + t], 0), n - 1);
-            tinv[t] = inv[p];
-            tidx[t] = p;
-        }
+        const auto pick = [=](int r) { return min(max(picks[r0 + r], 0), n - 1); };      // (slot r: a row of emb, through picks)
+        stage_padded_tile<W, DV_COVER_ROWS>(tile, tinv, m, pick, emb, es, H, inv, t);
+        if (t < m) tidx[t] = pick(t);
         __syncthreads();
         if (open) {                                              // (no barrier inside; within the walk selects keep the first)
             for (int r = 0; r < m; ++r) {
@@ -260,19 +252,12 @@ extern "C" int mkgnn_diverse_pick(const float* emb, int64_t emb_stride, int64_t 
     if (((uintptr_t)workspace & 3) != 0) return api_fail("%s: workspace not 4-byte aligned", who);
     // what the launches write -- the four outputs and the workspace -- must not overlap emb, nor each other: every launch reads
     // emb, and each output has one writer per launch
-    struct Span { const char* p; size_t n; };
     const size_t rows = (size_t)n_rows * 4;
-    const Span rd = {(const char*)emb, ((size_t)(n_rows - 1) * (size_t)emb_stride + (size_t)H) * 4};
-    const Span wr[5] = {{(const char*)picks, (size_t)k_max * 4}, {(const char*)n_picks, 4}, {(const char*)leader, rows},
-                        {(const char*)leader_sim, rows}, {(const char*)workspace, need}};
-    auto overlap = [](const Span& x, const Span& y) { return x.p < y.p + y.n && y.p < x.p + x.n; };
-    for (int a = 0; a < 5; ++a) {
-        if (overlap(wr[a], rd))
-            return api_fail("%s: an output (picks, n_picks, leader, leader_sim) or the workspace aliases emb", who);
-        for (int b = a + 1; b < 5; ++b)
-            if (overlap(wr[a], wr[b]))
-                return api_fail("%s: the outputs (picks, n_picks, leader, leader_sim) and the workspace alias each other", who);
-    }
+    const Span rd = {emb, ((size_t)(n_rows - 1) * (size_t)emb_stride + (size_t)H) * 4};
+    const Span wr[5] = {{picks, (size_t)k_max * 4}, {n_picks, 4}, {leader, rows}, {leader_sim, rows}, {workspace, need}};
+    if (spans_disjoint(who, wr, 5, &rd, 1, "an output (picks, n_picks, leader, leader_sim) or the workspace aliases emb",
+                       "the outputs (picks, n_picks, leader, leader_sim) and the workspace alias each other"))
+        return 1;
     const hipStream_t st = (hipStream_t)stream;
     const int n = (int)n_rows;
     float* inv = (float*)workspace;

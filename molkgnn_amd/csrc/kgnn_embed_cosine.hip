@@ -11,20 +11,15 @@
 // written by lane q of row i alone.  The kernel is bound by its launch: plain FP32, no matrix instructions.
 //
 // THE EVALUATION ORDER of an element -- one per element, whatever n_rows, the row's place in block and grid, Q, q's index, the
-// strides or the output layout are (the bits of sim[i, q] depend on the H values of row i and of query q alone):
-//     sumsq(v)  lane h < 32 forms v[h] * v[h] (a plain multiply; +0.0 at lanes >= H), applies fmaf(v[32 + h], v[32 + h], .) where
-//               32 + h < H; the 32 values go through half_wave_sum (the xor tree, offsets 16, 8, 4, 2, 1)
-//     inv(v)    1 / fmaxf(sqrtf(sumsq(v)), eps)           (correctly rounded square root and division; a NaN sum clamps to eps)
-//     dot       lane h forms e[h] * q[h], applies fmaf(e[32 + h], q[32 + h], .), the same tree; then + (+0.0), which turns a sum
-//               of -0.0 products -- a zero row against negative query values -- into +0.0 and changes nothing else
-//     sim       (dot * inv(e)) * inv(q), two plain multiplies in that order
-// inv(q) is computed by a half-wave of the block with exactly the lane assignment above, whichever half-wave and whatever Q.
+// strides or the output layout are (the bits of sim[i, q] depend on the H values of row i and of query q alone) -- is kgnn_cosine.h's:
+// this kernel is that text called in order, (half_wave_dot * inv(e)) * inv(q).  inv(q) is computed by a half-wave of the block with
+// exactly the lane assignment of a row's, whichever half-wave and whatever Q.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "kgnn_common.h"
 
 #include "kgnn_launch.h"
-#include "kgnn_head_terms.h"
+#include "kgnn_cosine.h"
 #include "../../include/molkgnn_hip.h"
 
 namespace mkgnn {
@@ -34,9 +29,6 @@ constexpr int EC_MAX_H = 64;
 constexpr int EC_MAX_Q = MKGNN_EMBED_COSINE_MAX_QUERIES;
 static_assert(EC_MAX_Q <= 32, "one lane of a row's half-wave per query");
 static_assert(EC_MAX_Q <= MKGNN_TASK_HEAD_MAX_TASKS, "the queries' lists are a TopKTasks");
-
-// the sum of squares of an H-vector held by a half-wave: half_wave_sumsq (kgnn_head_terms.h), shared with kgnn_max_cosine.hip
-__device__ __forceinline__ float ec_sumsq(float v0, float v1, int h, int H) { return half_wave_sumsq(v0, v1, h, H); }
 
 __global__ void __launch_bounds__(256) embed_cosine_kernel(const float* __restrict__ emb, int64_t es, int64_t n, int H, int Q,
                                                            const float* __restrict__ qry, int64_t qs, float* __restrict__ sim,
@@ -51,8 +43,7 @@ __global__ void __launch_bounds__(256) embed_cosine_kernel(const float* __restri
     for (int k = 0; k < NP; ++k) {
         const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
         const int64_t ic = i < n ? i : n - 1;
-        e0[k] = emb[ic * es + (h < H ? h : 0)];
-        e1[k] = emb[ic * es + (32 + h < H ? 32 + h : 0)];
+        half_wave_load(emb + ic * es, h, H, e0[k], e1[k]);
     }
     for (int j = t; j < Q * H; j += 256) {
         const int q = j / H;
@@ -62,21 +53,17 @@ __global__ void __launch_bounds__(256) embed_cosine_kernel(const float* __restri
     // 1 / max(||query||, eps): half-wave g takes queries g, g + 8, ... (the trip count is the block's: no divergence round a shuffle)
     for (int q0 = 0; q0 < Q; q0 += 8) {
         const int q = q0 + g < Q ? q0 + g : Q - 1;
-        const float* qr = qv + q * H;
-        const float s = ec_sumsq(qr[h < H ? h : 0], qr[32 + h < H ? 32 + h : 0], h, H);
-        if (h == 0 && q0 + g < Q) qinv[q] = 1.f / fmaxf(sqrtf(s), MKGNN_EPS);
+        const float s = half_wave_row_sumsq(qv + q * H, h, H);
+        if (h == 0 && q0 + g < Q) qinv[q] = inv_clamped_norm(s);
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
-        const float ie = 1.f / fmaxf(sqrtf(ec_sumsq(e0[k], e1[k], h, H)), MKGNN_EPS);
+        const float ie = inv_clamped_norm(half_wave_sumsq(e0[k], e1[k], h, H));
         float mine = 0.f;
         for (int q = 0; q < Q; ++q) {
-            const float* qr = qv + q * H;
-            float x = h < H ? __fmul_rn(e0[k], qr[h]) : 0.f;       // (never contracted into the tree's first add)
-            if (32 + h < H) x = fmaf(e1[k], qr[32 + h], x);
-            const float d = half_wave_sum(x) + 0.f;                // (the xor tree leaves the sum in every lane of the row)
+            const float d = half_wave_dot(e0[k], e1[k], qv + q * H, h, H);
             const float r = __fmul_rn(__fmul_rn(d, ie), qinv[q]);
             if (h == q) mine = r;
         }

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "kgnn_launch.h"
+#include "kgnn_ranked.h"
 #include "../../include/molkgnn_hip.h"
 
 namespace mkgnn {
@@ -33,47 +34,23 @@ constexpr int EX_TILE = 128;              // slots per tile (mirrored by _lib.EX
 constexpr int EX_CHUNK = 64;              // columns per workgroup of the runs launch
 constexpr int EX_THREADS = 256;
 constexpr int EX_MERGE_COLUMNS = 4;       // columns (= waves) per workgroup of the merge launch
-constexpr uint32_t EX_NEG_INF = 0xFF800000u;
 static_assert(MKGNN_EXEMPLARS_MAX_K == 64, "one list slot per lane of a wave");
 static_assert(EX_TILE % 64 == 0 && EX_TILE <= EX_THREADS, "whole waves of slots, one thread per slot for the slot's facts");
 
 struct Entry { uint32_t bits; int32_t shard, mol, atom; uint32_t pos; };
 
-__device__ __forceinline__ Entry empty_entry(uint32_t pos) { return Entry{EX_NEG_INF, -1, -1, -1, pos}; }
+__device__ __forceinline__ Entry empty_entry(uint32_t pos) { return Entry{RANK_EMPTY_BITS, -1, -1, -1, pos}; }
+__device__ __forceinline__ bool is_empty(const Entry& e) { return e.bits == RANK_EMPTY_BITS && e.shard == -1 && e.mol == -1 && e.atom == -1; }
 
-// the score's rank as an unsigned key, smaller = earlier: non-NaN scores descending (-0.0 as +0.0), then NaN, then an empty slot
-__device__ __forceinline__ uint32_t rank_key(const Entry& e) {
-    if (e.bits == EX_NEG_INF && e.shard == -1 && e.mol == -1 && e.atom == -1) return 0xFFFFFFFFu;
-    if ((e.bits & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFEu;
-    const uint32_t b = e.bits == 0x80000000u ? 0u : e.bits;
-    return (b & 0x80000000u) ? b : ~(b | 0x80000000u);
-}
-
+// the order of kgnn_ranked.h; this list's trailing keys: the molecule, the atom, then the position
 __device__ __forceinline__ bool before(const Entry& a, const Entry& b) {
-    const uint64_t ah = ((uint64_t)rank_key(a) << 32) | ((uint32_t)a.shard ^ 0x80000000u);
-    const uint64_t bh = ((uint64_t)rank_key(b) << 32) | ((uint32_t)b.shard ^ 0x80000000u);
+    const uint64_t ah = rank_shard_key(score_rank(a.bits, is_empty(a)), a.shard);
+    const uint64_t bh = rank_shard_key(score_rank(b.bits, is_empty(b)), b.shard);
     if (ah != bh) return ah < bh;
-    const uint64_t am = ((uint64_t)((uint32_t)a.mol ^ 0x80000000u) << 32) | ((uint32_t)a.atom ^ 0x80000000u);
-    const uint64_t bm = ((uint64_t)((uint32_t)b.mol ^ 0x80000000u) << 32) | ((uint32_t)b.atom ^ 0x80000000u);
+    const uint64_t am = ((uint64_t)ordered(a.mol) << 32) | ordered(a.atom);
+    const uint64_t bm = ((uint64_t)ordered(b.mol) << 32) | ordered(b.atom);
     if (am != bm) return am < bm;
     return a.pos < b.pos;
-}
-
-__device__ __forceinline__ Entry lane_entry(const Entry& e, int from) {
-    return Entry{(uint32_t)__shfl((int)e.bits, from, 64), __shfl(e.shard, from, 64), __shfl(e.mol, from, 64), __shfl(e.atom, from, 64),
-                 (uint32_t)__shfl((int)e.pos, from, 64)};
-}
-
-// one compare-exchange stage inside a wave: lane l and lane l ^ j; the lane whose bit j is clear keeps the earlier entry when `up`
-__device__ __forceinline__ void exchange(Entry& e, int lane, int j, bool up) {
-    const Entry o = lane_entry(e, lane ^ j);
-    const bool keep_first = ((lane & j) == 0) == up;
-    if (before(o, e) == keep_first) e = o;
-}
-
-// a bitonic sequence of n entries (n a power of two <= 64, in every aligned group of n lanes) -> ascending
-__device__ __forceinline__ void merge_stages(Entry& e, int lane, int n) {
-    for (int j = n >> 1; j > 0; j >>= 1) exchange(e, lane, j, true);
 }
 
 // the layout of one call, by value: per degree its slots, its column block and where its flags and runs begin (in (tile, column)
@@ -157,13 +134,13 @@ __global__ void __launch_bounds__(EX_THREADS) exemplar_runs_kernel(const ExArgs 
             const uint32_t pos = (uint32_t)K + (uint32_t)(s0 + r);
             Entry e = row < 0 ? empty_entry(pos) : Entry{tile[r * pitch + j], tag, s_mol[r], s_atom[r], pos};
             for (int k = 2; k <= 64; k <<= 1)
-                for (int jj = k >> 1; jj > 0; jj >>= 1) exchange(e, lane, jj, (lane & k) == 0);
+                for (int jj = k >> 1; jj > 0; jj >>= 1) wave_exchange(e, lane, jj, (lane & k) == 0);
             if (h == 0) {
                 best = e;
             } else {                                     // the best 64 of both sorted halves, as a bitonic sequence; then sorted
                 const Entry o = lane_entry(e, 63 - lane);
                 if (before(o, best)) best = o;
-                merge_stages(best, lane, 64);
+                wave_merge_stages(best, lane, 64);
             }
         }
         if (lane < Kp) {
@@ -198,7 +175,7 @@ __global__ void __launch_bounds__(64 * EX_MERGE_COLUMNS) exemplar_merge_kernel(c
             const uint4 v = a.runs[at];
             const Entry run{v.x, (int32_t)v.y, (int32_t)v.z, (int32_t)v.w, a.run_pos[at]};
             if (lane < Kp && before(run, cur)) cur = run;
-            merge_stages(cur, lane, Kp);
+            wave_merge_stages(cur, lane, Kp);
             changed = true;
         }
     }
@@ -210,7 +187,6 @@ __global__ void __launch_bounds__(64 * EX_MERGE_COLUMNS) exemplar_merge_kernel(c
     }
 }
 
-inline int32_t pow2_at_least(int32_t k) { int32_t p = 1; while (p < k) p <<= 1; return p; }
 constexpr int64_t EX_MAX_COUNT = (int64_t)1 << 30;       // slots of one degree: positions K + s stay below 2^31
 
 // the column blocks: inside [0, C), disjoint; false otherwise
@@ -292,23 +268,16 @@ extern "C" int mkgnn_kernel_exemplars_update(const float* sim, int64_t sim_strid
     if (workspace_bytes < need) return api_fail("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
     if ((uintptr_t)workspace % 16) return api_fail("%s: workspace must be 16-byte aligned", who);
     // what the launches write -- the four lists and the workspace -- must not overlap what they read, nor each other
-    struct Span { const char* p; size_t n; };
     const size_t list = (size_t)C * (size_t)K * 4;
-    const Span wr[5] = {{(const char*)top_score, list}, {(const char*)top_shard, list}, {(const char*)top_mol, list},
-                        {(const char*)top_atom, list}, {(const char*)workspace, need}};
-    Span rd[11] = {{(const char*)sim, ((size_t)(n_atoms - 1) * (size_t)sim_stride + (size_t)C) * 4},
-                   {(const char*)atom_mol, (size_t)n_atoms * 4}, {(const char*)mol_ptr, ((size_t)B + 1) * 4},
-                   {(const char*)mol_ids, (size_t)B * 4}, {(const char*)n_live, 4}, {(const char*)shard_tag, 4},
-                   {(const char*)n_valid_atoms, n_valid_atoms ? (size_t)8 : (size_t)0}};
+    const Span wr[5] = {{top_score, list}, {top_shard, list}, {top_mol, list}, {top_atom, list}, {workspace, need}};
+    Span rd[7 + MKGNN_MAX_DEGREE] = {{sim, ((size_t)(n_atoms - 1) * (size_t)sim_stride + (size_t)C) * 4},
+                                     {atom_mol, (size_t)n_atoms * 4}, {mol_ptr, ((size_t)B + 1) * 4}, {mol_ids, (size_t)B * 4},
+                                     {n_live, 4}, {shard_tag, 4}, {n_valid_atoms, n_valid_atoms ? (size_t)8 : (size_t)0}};
     for (int d = 0; d < MKGNN_MAX_DEGREE; ++d)
-        rd[7 + d] = {(const char*)buckets[d].selected_index, buckets[d].selected_index ? (size_t)count[d] * 8 : (size_t)0};
-    auto overlap = [](const Span& x, const Span& y) { return x.n && y.n && x.p < y.p + y.n && y.p < x.p + x.n; };
-    for (int i = 0; i < 5; ++i) {
-        for (int j = 0; j < 11; ++j)
-            if (overlap(wr[i], rd[j])) return api_fail("%s: an output (a list or the workspace) aliases an input", who);
-        for (int j = i + 1; j < 5; ++j)
-            if (overlap(wr[i], wr[j])) return api_fail("%s: the lists and the workspace alias each other", who);
-    }
+        rd[7 + d] = {buckets[d].selected_index, buckets[d].selected_index ? (size_t)count[d] * 8 : (size_t)0};
+    if (spans_disjoint(who, wr, 5, rd, 7 + MKGNN_MAX_DEGREE, "an output (a list or the workspace) aliases an input",
+                       "the lists and the workspace alias each other"))
+        return 1;
     const int32_t Kp = pow2_at_least(K);
     int maxL = 1;
     for (int d = 0; d < MKGNN_MAX_DEGREE; ++d) {

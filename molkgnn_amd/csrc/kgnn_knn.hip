@@ -4,17 +4,12 @@
 //     list q  <-  topk_update_reference(list q, s_q, ids, n_valid, shard_tag),    s_q[i] = the float32 value mkgnn_embed_cosine
 //                 writes for row i of emb as the ROW and queries[q] as the QUERY, BIT FOR BIT
 //
-// THE BITS.  One similarity is evaluated as kgnn_max_cosine.hip evaluates it: the inverse norms by half_wave_sumsq /
-// inv_clamped_norm (knn_norms_kernel, one half-wave per vector, into the workspace), the dot product serially by ONE lane with
-// mc_dot (the xor tree as a fixed binary tree, + (+0.0)), then (dot * inv(row)) * inv(query) in that orientation.  Vectors are
-// padded with +0.0 up to 32 (H <= 32) or 64 columns; kgnn_max_cosine.hip says why that changes no bit.  Nothing in this file may
-// be contracted: the pragma below.
+// THE BITS are kgnn_cosine.h's, as kgnn_max_cosine.hip evaluates them: the inverse norms by half_wave_sumsq / inv_clamped_norm
+// (knn_norms_kernel, one half-wave per vector, into the workspace), the dot product serially by ONE lane with mc_dot, then
+// (dot * inv(row)) * inv(query) in that orientation.  Nothing in this file may be contracted: the pragma below.
 //
-// THE ORDER.  An entry is (similarity bits, shard, id); its key is three unsigned words compared lexicographically -- the rank of
-// the similarity (non-NaN descending with -0.0 as +0.0, then NaN, then the empty slot (-inf, -1, -1)), the shard, the id -- so every
-// comparison is an integer one, the (shard, id) tie-break and the empty and NaN ranks included.  Entries with equal keys keep their
-// order of arrival: a candidate enters only where it is STRICTLY before the list's last entry, behind every entry it is not
-// strictly before, and the candidates of a tile are taken in row order.
+// THE ORDER is kgnn_ranked.h's with the id as the only trailing key.  Entries with equal keys keep their order of arrival: a candidate
+// enters only where it is STRICTLY before the list's last entry, behind every entry it is not strictly before, in row order.
 //
 // THE LAUNCHES (two, or three when the candidates are split; all on the caller's stream, capturable, no atomics, no state):
 //   knn_norms_kernel   1 / max(||.||, eps) of the Q queries and of the rows below n_valid -> workspace
@@ -35,7 +30,8 @@
 #include "kgnn_common.h"
 
 #include "kgnn_launch.h"
-#include "kgnn_head_terms.h"
+#include "kgnn_cosine.h"
+#include "kgnn_ranked.h"
 #include "../../include/molkgnn_hip.h"
 
 #pragma clang fp contract(off)
@@ -49,7 +45,6 @@ constexpr int KNN_TILE = 64;                // candidate rows per LDS tile: one 
 constexpr int KNN_MIN_PART_TILES = 2;       // a part is at least two tiles: a finer split only grows the merge (_lib.KNN_MIN_PART_TILES)
 constexpr int KNN_MAX_PARTS = 32;           // parts of the candidates (grid.y); the workspace holds parts x Q lists (_lib.KNN_MAX_PARTS)
 constexpr int KNN_TARGET_BLOCKS = 1024;     // four blocks (sixteen waves) per CU (_lib.KNN_TARGET_BLOCKS)
-constexpr uint32_t KNN_NEG_INF = 0xFF800000u;
 static_assert(MKGNN_KNN_MAX_K == 64 && KNN_TILE == 64, "one list slot and one candidate per lane of a wave");
 static_assert(MKGNN_KNN_MAX_ROWS % KNN_TILE == 0, "whole tiles");
 
@@ -69,27 +64,15 @@ inline KnnSplit knn_split(int64_t n, int64_t Q) {
 
 struct Entry { uint32_t bits; int32_t shard, mol; };
 
-__device__ __forceinline__ Entry empty_entry() { return Entry{KNN_NEG_INF, -1, -1}; }
-__device__ __forceinline__ bool is_empty(const Entry& e) { return e.bits == KNN_NEG_INF && e.shard == -1 && e.mol == -1; }
+__device__ __forceinline__ Entry empty_entry() { return Entry{RANK_EMPTY_BITS, -1, -1}; }
+__device__ __forceinline__ bool is_empty(const Entry& e) { return e.bits == RANK_EMPTY_BITS && e.shard == -1 && e.mol == -1; }
 
-// the similarity's rank as an unsigned key, smaller = earlier: non-NaN descending (-0.0 as +0.0), then NaN, then an empty slot
-__device__ __forceinline__ uint32_t rank_key(const Entry& e) {
-    if (is_empty(e)) return 0xFFFFFFFFu;
-    if ((e.bits & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFEu;
-    const uint32_t b = e.bits == 0x80000000u ? 0u : e.bits;
-    return (b & 0x80000000u) ? b : ~(b | 0x80000000u);
-}
-
-// strictly before, under the full order
+// strictly before, under the order of kgnn_ranked.h; this list's trailing key: the id
 __device__ __forceinline__ bool before(const Entry& a, const Entry& b) {
-    const uint64_t ah = ((uint64_t)rank_key(a) << 32) | ((uint32_t)a.shard ^ 0x80000000u);
-    const uint64_t bh = ((uint64_t)rank_key(b) << 32) | ((uint32_t)b.shard ^ 0x80000000u);
+    const uint64_t ah = rank_shard_key(score_rank(a.bits, is_empty(a)), a.shard);
+    const uint64_t bh = rank_shard_key(score_rank(b.bits, is_empty(b)), b.shard);
     if (ah != bh) return ah < bh;
-    return ((uint32_t)a.mol ^ 0x80000000u) < ((uint32_t)b.mol ^ 0x80000000u);
-}
-
-__device__ __forceinline__ Entry lane_entry(const Entry& e, int from) {
-    return Entry{(uint32_t)__shfl((int)e.bits, from, 64), __shfl(e.shard, from, 64), __shfl(e.mol, from, 64)};
+    return ordered(a.mol) < ordered(b.mol);
 }
 
 // One tile of candidates into a wave's list.  mine: slot `lane` of the sorted list (lanes >= K hold what falls off its end); c: this
@@ -124,7 +107,7 @@ __global__ void __launch_bounds__(256) knn_norms_kernel(const float* __restrict_
     const int nv = knn_valid_rows(n_valid, n);
     const bool real = v < (int64_t)Q + nv;
     const float* row = !real ? qry : v < Q ? qry + v * qs : emb + (v - Q) * es;
-    const float s = half_wave_sumsq(row[h < H ? h : 0], row[32 + h < H ? 32 + h : 0], h, H);
+    const float s = half_wave_row_sumsq(row, h, H);
     if (h == 0 && real) inv[v] = inv_clamped_norm(s);
 }
 
@@ -263,21 +246,15 @@ extern "C" int mkgnn_embed_knn_update(const float* emb, int64_t emb_stride, int6
     if (workspace_bytes < need) return api_fail("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
     if (((uintptr_t)workspace & 3) != 0) return api_fail("%s: workspace not 4-byte aligned", who);
     // what the launches write -- the three lists and the workspace -- must not overlap what they read, nor each other
-    struct Span { const char* p; size_t n; };
     const size_t list = (size_t)Q * (size_t)K * 4;
-    const Span wr[4] = {{(const char*)top_sim, list}, {(const char*)top_shard, list}, {(const char*)top_mol, list},
-                        {(const char*)workspace, need}};
-    const Span rd[5] = {{(const char*)emb, ((size_t)(n_rows - 1) * (size_t)emb_stride + (size_t)H) * 4},
-                        {(const char*)queries, ((size_t)(Q - 1) * (size_t)query_stride + (size_t)H) * 4},
-                        {(const char*)ids, ids ? (size_t)n_rows * 4 : (size_t)0}, {(const char*)n_valid, n_valid ? (size_t)4 : (size_t)0},
-                        {(const char*)shard_tag, shard_tag ? (size_t)4 : (size_t)0}};
-    auto overlap = [](const Span& x, const Span& y) { return x.n && y.n && x.p < y.p + y.n && y.p < x.p + x.n; };
-    for (int i = 0; i < 4; ++i) {
-        for (int j = 0; j < 5; ++j)
-            if (overlap(wr[i], rd[j])) return api_fail("%s: an output (a list or the workspace) aliases an input", who);
-        for (int j = i + 1; j < 4; ++j)
-            if (overlap(wr[i], wr[j])) return api_fail("%s: the lists and the workspace alias each other", who);
-    }
+    const Span wr[4] = {{top_sim, list}, {top_shard, list}, {top_mol, list}, {workspace, need}};
+    const Span rd[5] = {{emb, ((size_t)(n_rows - 1) * (size_t)emb_stride + (size_t)H) * 4},
+                        {queries, ((size_t)(Q - 1) * (size_t)query_stride + (size_t)H) * 4},
+                        {ids, ids ? (size_t)n_rows * 4 : (size_t)0}, {n_valid, n_valid ? (size_t)4 : (size_t)0},
+                        {shard_tag, shard_tag ? (size_t)4 : (size_t)0}};
+    if (spans_disjoint(who, wr, 4, rd, 5, "an output (a list or the workspace) aliases an input",
+                       "the lists and the workspace alias each other"))
+        return 1;
     const hipStream_t st = (hipStream_t)stream;
     const KnnSplit sp = knn_split(n_rows, Q);
     KnnArgs a{};

@@ -318,6 +318,12 @@ inline void note_plan(int which, int blocks, int ng, const int64_t* tiles_of, co
 // error reporting shared by the C-ABI translation units (kgnn_capi.hip owns the thread-local message)
 int api_fail(const char* fmt, ...);
 int api_hip_fail(const char* what, hipError_t e);
+// The byte ranges a call's launches write must overlap neither what they read nor each other.  0 if so; otherwise the message
+// "<who>: <reads_text>" (a write overlaps a read) or "<who>: <writes_text>" (two writes overlap) is left and 1 returned.  A span of
+// no bytes -- an optional argument that was not given -- overlaps nothing
+struct Span { const void* p; size_t n; };
+int spans_disjoint(const char* who, const Span* writes, int n_writes, const Span* reads, int n_reads, const char* reads_text,
+                   const char* writes_text);
 
 // MKGNN_BWD_SPLIT / mkgnn_debug_set_backward_products: the streamed backward kernels' products as split fp16 (kgnn_split.h)
 int bwd_split_mode();

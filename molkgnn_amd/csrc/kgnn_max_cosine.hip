@@ -5,17 +5,9 @@
 //                              -0.0 == +0.0, then the lower r), of sim(i, r) -- the float32 value mkgnn_embed_cosine writes for row i
 //                              and query refs[r], BIT FOR BIT
 //
-// THE BITS.  kgnn_embed_cosine.hip fixes one element's evaluation: lane h of 32 forms e[h] * q[h] (+0.0 at h >= H), applies
-// fmaf(e[32 + h], q[32 + h], .) where 32 + h < H, the 32 values go through the xor tree (offsets 16, 8, 4, 2, 1), then + (+0.0), then
-// (dot * inv(e)) * inv(q).  Every step of that tree is lane l forming v[l] + v[l ^ o]; float addition is commutative, so all lanes
-// hold the same bits and the tree is a fixed binary tree: level 16 adds x[j] + x[j + 16] for j < 16, level 8 adds those sums j and
-// j + 8, and so on.  ONE THREAD evaluates it serially in that association (mc_dot) and gets the same bits.  The row and the
-// reference are padded with +0.0 up to 32 (H <= 32) or 64 columns: a padded product is (+0.0) * (+0.0) = +0.0, what a lane
-// h >= H contributes there; a padded fmaf(+0.0, +0.0, x) is x + (+0.0), which differs from the skipped fmaf only where x is -0.0,
-// and the sign of a zero going into a tree of additions can change nothing but the sign of a zero coming out, which the
-// + (+0.0) behind the tree removes.  Nothing in this file may be contracted: the pragma below, and explicit fmaf where the
-// definition has one.  The inverse norms are NOT re-derived: norms_kernel runs half_wave_sumsq (kgnn_head_terms.h) -- the
-// function embed_cosine_kernel itself calls -- for every reference and every row, into the workspace.
+// THE BITS are kgnn_cosine.h's: the inverse norms by half_wave_sumsq / inv_clamped_norm -- the functions embed_cosine_kernel itself
+// calls -- for every reference and every row (norms_kernel, into the workspace), the dot product serially by ONE THREAD with mc_dot,
+// then (dot * inv(e)) * inv(q).  Nothing in this file may be contracted: the pragma below.
 //
 // THE LAUNCHES (two, or three when the references are split; all on the caller's stream, capturable, no atomics, no state):
 //   norms_kernel       one half-wave per vector: 1 / max(||.||, eps) of the R references and the n rows -> workspace
@@ -33,7 +25,7 @@
 #include "kgnn_common.h"
 
 #include "kgnn_launch.h"
-#include "kgnn_head_terms.h"
+#include "kgnn_cosine.h"
 #include "../../include/molkgnn_hip.h"
 
 #pragma clang fp contract(off)
@@ -67,11 +59,9 @@ __global__ void __launch_bounds__(256) norms_kernel(const float* __restrict__ re
     const int64_t v = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5), total = (int64_t)R + n;
     const int64_t vc = v < total ? v : total - 1;                 // (clamped: every lane of a half-wave takes part in the tree)
     const float* row = vc < R ? refs + vc * rs : emb + (vc - R) * es;
-    const float s = half_wave_sumsq(row[h < H ? h : 0], row[32 + h < H ? 32 + h : 0], h, H);
+    const float s = half_wave_row_sumsq(row, h, H);
     if (h == 0 && v < total) inv[v] = inv_clamped_norm(s);
 }
-
-// the dot product of the definition, serially: mc_dot (kgnn_head_terms.h), shared with kgnn_diverse.hip
 
 // the order: a non-NaN beats a NaN, a larger value beats a smaller one (-0.0 == +0.0: no strict >), the earlier one stays otherwise
 __device__ __forceinline__ bool mc_better(float s, float best) { return s == s && (best != best || s > best); }
@@ -95,11 +85,7 @@ __global__ void __launch_bounds__(MC_ROWS) max_cosine_kernel(const float* __rest
     for (int r0 = r_begin; r0 < r_end; r0 += MC_TILE) {
         const int m = min(MC_TILE, r_end - r0);
         __syncthreads();                                         // (the previous tile has been walked by every wave)
-        for (int j = t; j < m * W; j += MC_ROWS) {
-            const int r = j / W, c = j - r * W;
-            tile[j] = c < H ? refs[(int64_t)(r0 + r) * rs + c] : 0.f;
-        }
-        if (t < m) tinv[t] = inv[r0 + t];
+        stage_padded_tile<W, MC_ROWS>(tile, tinv, m, [r0](int r) { return r0 + r; }, refs, rs, H, inv, t);
         __syncthreads();
         // two references in flight -- one's LDS reads under the other's adds -- and selects, not branches, between them; an odd
         // tile's last reference is taken twice, which the strict order ignores
@@ -259,18 +245,12 @@ extern "C" int mkgnn_select_rows(const float* scores, const int32_t* ids, const 
     if (!scores || !ids || !key || !n_valid || !bounds || !out_scores || !out_ids || !n_kept) return api_fail("%s: null pointer", who);
     // what the launch writes -- out_scores, out_ids, *n_kept -- must not overlap what it reads, nor each other: thread 0 writes
     // *n_kept after other threads have read the scalars and written the outputs
-    struct Span { const char* p; size_t n; };
     const size_t bytes = (size_t)B * 4;
-    const Span wr[3] = {{(const char*)out_scores, bytes}, {(const char*)out_ids, bytes}, {(const char*)n_kept, 4}};
-    const Span rd[5] = {{(const char*)scores, bytes}, {(const char*)ids, bytes}, {(const char*)key, bytes},
-                        {(const char*)n_valid, 4}, {(const char*)bounds, 8}};
-    auto overlap = [](const Span& x, const Span& y) { return x.p < y.p + y.n && y.p < x.p + x.n; };
-    for (int w = 0; w < 3; ++w) {
-        for (int r = 0; r < 5; ++r)
-            if (overlap(wr[w], rd[r])) return api_fail("%s: an output (out_scores, out_ids, n_kept) aliases an input", who);
-        for (int v = w + 1; v < 3; ++v)
-            if (overlap(wr[w], wr[v])) return api_fail("%s: the outputs (out_scores, out_ids, n_kept) alias each other", who);
-    }
+    const Span wr[3] = {{out_scores, bytes}, {out_ids, bytes}, {n_kept, 4}};
+    const Span rd[5] = {{scores, bytes}, {ids, bytes}, {key, bytes}, {n_valid, 4}, {bounds, 8}};
+    if (spans_disjoint(who, wr, 3, rd, 5, "an output (out_scores, out_ids, n_kept) aliases an input",
+                       "the outputs (out_scores, out_ids, n_kept) alias each other"))
+        return 1;
     select_rows_kernel<<<1, SEL_THREADS, 0, (hipStream_t)stream>>>(scores, ids, key, B, n_valid, bounds, out_scores, out_ids, n_kept);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);

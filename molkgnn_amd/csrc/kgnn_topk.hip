@@ -23,33 +23,27 @@
 // mkgnn_topk_update is the T = 1 call of the same launcher (strides 1 and 0).
 #include <cstdint>
 #include "kgnn_launch.h"
+#include "kgnn_ranked.h"
 #include "../../include/molkgnn_hip.h"
 
 namespace mkgnn {
 namespace {
 
 constexpr int TOPK_THREADS = 1024, TOPK_TILE = TOPK_THREADS;
-constexpr uint32_t NEG_INF_BITS = 0xFF800000u;
 static_assert(MKGNN_TOPK_MAX_K == TOPK_TILE, "one list entry per thread");
 
 struct Entry { uint32_t bits; int32_t shard, mol; uint32_t pos; };
 
-__device__ __forceinline__ Entry empty_entry(uint32_t pos) { return Entry{NEG_INF_BITS, -1, -1, pos}; }
+__device__ __forceinline__ Entry empty_entry(uint32_t pos) { return Entry{RANK_EMPTY_BITS, -1, -1, pos}; }
+__device__ __forceinline__ bool is_empty(const Entry& e) { return e.bits == RANK_EMPTY_BITS && e.shard == -1 && e.mol == -1; }
 
-// the score's rank as an unsigned key, smaller = earlier: non-NaN scores descending (-0.0 as +0.0), then NaN, then an empty slot
-__device__ __forceinline__ uint32_t rank_key(const Entry& e) {
-    if (e.bits == NEG_INF_BITS && e.shard == -1 && e.mol == -1) return 0xFFFFFFFFu;
-    if ((e.bits & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFEu;
-    const uint32_t b = e.bits == 0x80000000u ? 0u : e.bits;
-    return (b & 0x80000000u) ? b : ~(b | 0x80000000u);            // = ~(the ascending key): +inf -> 0x007FFFFF, -inf -> 0xFF800000
-}
-
+// the order of kgnn_ranked.h; this list's trailing keys: the molecule, then the position
 __device__ __forceinline__ bool before(const Entry& a, const Entry& b) {
-    const uint64_t ah = ((uint64_t)rank_key(a) << 32) | ((uint32_t)a.shard ^ 0x80000000u);
-    const uint64_t bh = ((uint64_t)rank_key(b) << 32) | ((uint32_t)b.shard ^ 0x80000000u);
+    const uint64_t ah = rank_shard_key(score_rank(a.bits, is_empty(a)), a.shard);
+    const uint64_t bh = rank_shard_key(score_rank(b.bits, is_empty(b)), b.shard);
     if (ah != bh) return ah < bh;
-    const uint64_t al = ((uint64_t)((uint32_t)a.mol ^ 0x80000000u) << 32) | a.pos;
-    const uint64_t bl = ((uint64_t)((uint32_t)b.mol ^ 0x80000000u) << 32) | b.pos;
+    const uint64_t al = ((uint64_t)ordered(a.mol) << 32) | a.pos;
+    const uint64_t bl = ((uint64_t)ordered(b.mol) << 32) | b.pos;
     return al < bl;
 }
 
@@ -62,10 +56,7 @@ __device__ __forceinline__ void exchange(Entry& e, int j, bool up, uint4 (*buf)[
     const int t = threadIdx.x;
     Entry o;
     if (j < 64) {
-        o.bits = __shfl_xor(e.bits, j, 64);
-        o.shard = __shfl_xor(e.shard, j, 64);
-        o.mol = __shfl_xor(e.mol, j, 64);
-        o.pos = __shfl_xor(e.pos, j, 64);
+        o = lane_entry(e, t ^ j);                        // (kgnn_ranked.h: the wave's own stage; the LDS stage shares the compare)
     } else {
         buf[flip][t] = pack(e);
         __syncthreads();
@@ -163,7 +154,6 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float* _
     }
 }
 
-inline int32_t pow2_at_least(int32_t k) { int32_t p = 1; while (p < k) p <<= 1; return p; }
 inline size_t n_tiles_of(int32_t B) { return ((size_t)B + TOPK_TILE - 1) / TOPK_TILE; }
 
 }  // namespace

@@ -628,23 +628,32 @@ def cosine_bound(emb, queries) -> np.ndarray:
     return (2 * H + 10) * 2.0 ** -24 * (np.abs(e) @ np.abs(q).T) * scale + H * 2.0 ** -149 * scale + 2.0 ** -149
 
 
-def _check_queries(who: str, query_emb, G: int, dev=None) -> int:
-    """``Q`` of a query matrix: float32 ``[Q, G]``, ``1 <= Q <= 32``, on ``dev`` (a CUDA device) -- the value checks first, the device
-    last; ``ValueError`` otherwise, before anything is loaded or launched."""
-    if not torch.is_tensor(query_emb) or query_emb.dim() != 2:
-        raise ValueError(f"{who}: the queries are a [Q, {G}] tensor of embeddings")
-    if query_emb.dtype != torch.float32:
-        raise ValueError(f"{who}: the queries are float32, not {query_emb.dtype}")
-    Q = int(query_emb.shape[0])
-    if not 1 <= Q <= MAX_QUERIES:
-        raise ValueError(f"{who}: {Q} queries outside [1, {MAX_QUERIES}] (MKGNN_EMBED_COSINE_MAX_QUERIES: one list per query; rank "
-                         "more queries group by group, screening.rank_embeddings)")
-    if int(query_emb.shape[1]) != int(G):
-        raise ValueError(f"{who}: the queries are {int(query_emb.shape[1])} wide, the embedding is {int(G)} wide")
-    if query_emb.device.type != "cuda" or (dev is not None and query_emb.device != dev):
-        raise ValueError(f"{who}: the queries are on {query_emb.device}; they belong on the GPU of the library" +
+def _check_vectors(who: str, t, G: int, dev, noun: str, cap, cap_hint: str) -> int:
+    """The number of rows of a matrix of ``noun`` ("queries", "references"): float32 ``[n, G]``, ``1 <= n <= cap`` (``cap`` None: any
+    ``n >= 1``), on ``dev`` (a CUDA device) -- the value checks first, the device last; ``ValueError`` otherwise, before anything is
+    loaded or launched."""
+    if not torch.is_tensor(t) or t.dim() != 2:
+        raise ValueError(f"{who}: the {noun} are a [{noun[0].upper()}, {G}] tensor of embeddings")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{who}: the {noun} are float32, not {t.dtype}")
+    n = int(t.shape[0])
+    if cap is None and n < 1:
+        raise ValueError(f"{who}: at least one {noun[:-1]} is needed")
+    if cap is not None and not 1 <= n <= cap:
+        raise ValueError(f"{who}: {n} {noun} outside [1, {cap}] ({cap_hint})")
+    if int(t.shape[1]) != int(G):
+        raise ValueError(f"{who}: the {noun} are {int(t.shape[1])} wide, the embedding is {int(G)} wide")
+    if t.device.type != "cuda" or (dev is not None and t.device != dev):
+        raise ValueError(f"{who}: the {noun} are on {t.device}; they belong on the GPU of the library" +
                          ("" if dev is None else f" ({dev})"))
-    return Q
+    return n
+
+
+def _check_queries(who: str, query_emb, G: int, dev=None) -> int:
+    """``Q`` of a query matrix: float32 ``[Q, G]``, ``1 <= Q <= 32``, on ``dev`` (``_check_vectors``)."""
+    return _check_vectors(who, query_emb, G, dev, "queries", MAX_QUERIES,
+                          "MKGNN_EMBED_COSINE_MAX_QUERIES: one list per query; rank more queries group by group, "
+                          "screening.rank_embeddings")
 
 
 def _embedding_width(model) -> int:
@@ -824,27 +833,13 @@ class NearestLists(TopK):
     def result(self):
         """``(top_sim, top_shard, top_mol, n_occupied)``: the three ``[n_queries, k]`` tensors (not copies) and the number of occupied
         slots of every list -- they come first -- as a host int64 tensor ``[n_queries]`` (this synchronises)."""
-        empty = (self.top_score == float("-inf")) & (self.top_shard == -1) & (self.top_mol == -1)
-        return self.top_score, self.top_shard, self.top_mol, (self.k - empty.sum(dim=1)).cpu()
+        return TopKTasks.result(self)
 
 
 def _check_many_queries(who: str, query_emb, G: int, dev=None) -> int:
-    """``_check_queries`` without the cap of 32: float32 ``[Q, G]``, ``1 <= Q <= 2^20``, on ``dev`` -- the value checks first, the device
-    last; ``ValueError`` otherwise, before anything is loaded or launched."""
+    """``_check_queries`` without the cap of 32: float32 ``[Q, G]``, ``1 <= Q <= 2^20``, on ``dev`` (``_check_vectors``)."""
     from . import _lib
-    if not torch.is_tensor(query_emb) or query_emb.dim() != 2:
-        raise ValueError(f"{who}: the queries are a [Q, {G}] tensor of embeddings")
-    if query_emb.dtype != torch.float32:
-        raise ValueError(f"{who}: the queries are float32, not {query_emb.dtype}")
-    Q = int(query_emb.shape[0])
-    if not 1 <= Q <= _lib.KNN_MAX_QUERIES:
-        raise ValueError(f"{who}: {Q} queries outside [1, {_lib.KNN_MAX_QUERIES}] (MKGNN_KNN_MAX_QUERIES: one list per query)")
-    if int(query_emb.shape[1]) != int(G):
-        raise ValueError(f"{who}: the queries are {int(query_emb.shape[1])} wide, the embedding is {int(G)} wide")
-    if query_emb.device.type != "cuda" or (dev is not None and query_emb.device != dev):
-        raise ValueError(f"{who}: the queries are on {query_emb.device}; they belong on the GPU of the library" +
-                         ("" if dev is None else f" ({dev})"))
-    return Q
+    return _check_vectors(who, query_emb, G, dev, "queries", _lib.KNN_MAX_QUERIES, "MKGNN_KNN_MAX_QUERIES: one list per query")
 
 
 def _check_lists(who: str, lists, Q: int, dev) -> None:
@@ -980,21 +975,8 @@ def select_rows_reference(scores, ids, key, n_valid, lo, hi):
 
 
 def _check_refs(who: str, ref_emb, G: int, dev=None) -> int:
-    """``R`` of a reference matrix: float32 ``[R, G]``, ``R >= 1``, on ``dev`` (a CUDA device) -- the value checks first, the device
-    last; ``ValueError`` otherwise, before anything is loaded or launched."""
-    if not torch.is_tensor(ref_emb) or ref_emb.dim() != 2:
-        raise ValueError(f"{who}: the references are a [R, {G}] tensor of embeddings")
-    if ref_emb.dtype != torch.float32:
-        raise ValueError(f"{who}: the references are float32, not {ref_emb.dtype}")
-    R = int(ref_emb.shape[0])
-    if R < 1:
-        raise ValueError(f"{who}: at least one reference is needed")
-    if int(ref_emb.shape[1]) != int(G):
-        raise ValueError(f"{who}: the references are {int(ref_emb.shape[1])} wide, the embedding is {int(G)} wide")
-    if ref_emb.device.type != "cuda" or (dev is not None and ref_emb.device != dev):
-        raise ValueError(f"{who}: the references are on {ref_emb.device}; they belong on the GPU of the library" +
-                         ("" if dev is None else f" ({dev})"))
-    return R
+    """``R`` of a reference matrix: float32 ``[R, G]``, ``R >= 1``, on ``dev`` (``_check_vectors``)."""
+    return _check_vectors(who, ref_emb, G, dev, "references", None, "")
 
 
 def _embedding_f32(emb: torch.Tensor) -> torch.Tensor:

@@ -42,13 +42,24 @@ def test_entry_points_are_additive_to_abi_8():
     with open(os.path.join(REPO, "molkgnn_amd", "csrc", "Makefile")) as f:
         assert re.search(r"^SRCS :=.*\bkgnn_diverse\.hip\b", f.read(), flags=re.M)
     texts = {}
-    for name in ("kgnn_head_terms.h", "kgnn_max_cosine.hip", "kgnn_diverse.hip"):
-        with open(os.path.join(REPO, "molkgnn_amd", "csrc", name)) as f:
-            texts[name] = f.read()
+    csrc = os.path.join(REPO, "molkgnn_amd", "csrc")
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".h", ".hip")):
+            with open(os.path.join(csrc, name)) as f:
+                texts[name] = f.read()
     defines = {name: len(re.findall(r"float mc_dot\(const float", text)) for name, text in texts.items()}
-    assert defines == {"kgnn_head_terms.h": 1, "kgnn_max_cosine.hip": 0, "kgnn_diverse.hip": 0}
+    assert defines.pop("kgnn_cosine.h") == 1 and not any(defines.values()), defines       # once, and in no .hip file (nor elsewhere)
     assert "mc_dot<W>(" in texts["kgnn_max_cosine.hip"] and "mc_dot<W>(" in texts["kgnn_diverse.hip"]
-    assert "#pragma clang fp contract(off)" in texts["kgnn_diverse.hip"] and "#pragma clang fp contract(off)" in texts["kgnn_head_terms.h"]
+    assert "#pragma clang fp contract(off)" in texts["kgnn_diverse.hip"] and "#pragma clang fp contract(off)" in texts["kgnn_cosine.h"]
+    # its siblings: every piece of a cosine's evaluation has one definition under csrc/, and the kernel the others are defined
+    # against spells none of them out by hand
+    for fn in ("half_wave_sumsq", "half_wave_dot", "inv_clamped_norm"):
+        defines = {name: len(re.findall(r"float %s\(" % fn, text)) for name, text in texts.items()}
+        assert defines.pop("kgnn_cosine.h") == 1 and not any(defines.values()), (fn, defines)
+    assert "sqrtf(" not in texts["kgnn_embed_cosine.hip"] and "ec_sumsq" not in texts["kgnn_embed_cosine.hip"]
+    with open(os.path.join(csrc, "Makefile")) as f:
+        hdrs = re.search(r"^HDRS :=(.*)$", f.read(), flags=re.M).group(1).split()
+    assert "kgnn_cosine.h" in hdrs and "kgnn_ranked.h" in hdrs
 
 
 def test_sizes_on_the_host():

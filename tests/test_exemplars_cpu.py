@@ -51,6 +51,34 @@ def test_entry_points_are_additive_to_abi_8():
     assert (screening.EXEMPLARS_MAX_K, screening.EXEMPLARS_MAX_COLUMNS) == (_lib.EXEMPLARS_MAX_K, _lib.EXEMPLARS_MAX_COLUMNS)
 
 
+def test_the_order_of_the_lists_and_the_span_check_have_one_text():
+    """The list kernels promise each other's bits, so the order they share is compiled from ``kgnn_ranked.h`` alone: one rank
+    function, one spelling of the empty slot's bits and one ``pow2_at_least`` under ``csrc/``, none of them in a ``.hip`` file; the
+    host's overlap check of a call's spans likewise has one definition, outside the ``.hip`` files."""
+    csrc = os.path.join(REPO, "molkgnn_amd", "csrc")
+    texts = {}
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".h", ".hip", ".cpp")):
+            with open(os.path.join(csrc, name)) as f:
+                texts[name] = f.read()
+    hips = [name for name in texts if name.endswith(".hip")]
+    assert {"kgnn_topk.hip", "kgnn_exemplars.hip", "kgnn_knn.hip"} <= set(hips)
+    for pattern in (r"uint32_t score_rank\(", r"0xFF800000", r"int32_t pow2_at_least\("):
+        count = {name: len(re.findall(pattern, text, flags=re.I)) for name, text in texts.items()}
+        assert count.pop("kgnn_ranked.h") == 1 and not any(count.values()), (pattern, count)
+    for name in ("kgnn_topk.hip", "kgnn_exemplars.hip", "kgnn_knn.hip"):
+        assert '#include "kgnn_ranked.h"' in texts[name] and "score_rank(" in texts[name], name
+        assert not re.search(r"\brank_key\b", texts[name]), name
+    count = {name: len(re.findall(r"\bstruct Span\b", text)) for name, text in texts.items()}
+    assert sum(count.values()) == 1 and not any(count[name] for name in hips), count
+    assert sum(len(re.findall(r"^int spans_disjoint\(", text, flags=re.M)) for text in texts.values()) == 2    # declared, defined
+    for name in ("kgnn_knn.hip", "kgnn_exemplars.hip", "kgnn_max_cosine.hip", "kgnn_diverse.hip"):
+        assert "spans_disjoint(who, " in texts[name] and "auto overlap" not in texts[name], name
+    with open(os.path.join(csrc, "Makefile")) as f:
+        hdrs = re.search(r"^HDRS :=(.*)$", f.read(), flags=re.M).group(1).split()
+    assert "kgnn_ranked.h" in hdrs and "kgnn_cosine.h" in hdrs
+
+
 def _size(counts, Ls, K, C):
     from molkgnn_amd import _lib
     return _lib.load().mkgnn_kernel_exemplars_workspace_bytes(_lib.Int64x4(*counts), _lib.Int32x4(*Ls), K, C)
