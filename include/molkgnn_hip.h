@@ -1202,6 +1202,37 @@ int mkgnn_embed_knn_update(const float* emb, int64_t emb_stride, int64_t n_rows,
                            int32_t K, float* top_sim, int32_t* top_shard, int32_t* top_mol, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- neighbour counts (additive; the ABI version stays 8): how many references lie within a similarity threshold of every
+ * embedding row -- the count a Taylor-Butina clustering ranks its rows by (refs = emb, then mkgnn_diverse_pick in count order),
+ * and the number of catalogue analogues of a hit.
+ *   counts[i] = #{ r in [0, R) : sim(i, r) > min_sim }
+ * with sim(i, r) the float32 value mkgnn_embed_cosine writes for row i as the ROW and refs[r] as the QUERY, BIT FOR BIT --
+ * (dot * inv(e_i)) * inv(refs[r]); the orientation matters, the two multiplications do not commute in their last bit.  It is the
+ * value mkgnn_diverse_pick compares, so a neighbour in the count is a neighbour in the walk.  The comparison is strict, as in
+ * mkgnn_diverse_pick; a NaN similarity never counts (a NaN, infinite or overflowing row counts nothing; a NaN reference is
+ * counted by no row).  The operator knows no "self": with refs = emb (the same pointer is allowed) the diagonal is a pair like
+ * any other.  min_sim is passed by value and must be finite.  emb [n_rows, H] with emb_stride >= H, refs [R, H] with ref_stride
+ * >= H, both RAW: the inverse norms are computed inside the call, into the workspace, so one captured call follows new contents
+ * of both.  counts [n_rows] is contiguous; nothing else is written outside the workspace, and counts and the workspace must
+ * overlap neither emb nor refs nor each other (rejected).
+ *
+ * It is mkgnn_embed_max_cosine's walk with another reduction: the same two launches on `stream`, three when the references are
+ * split over the grid (every part writes its partial count to the workspace and a finishing launch adds them); capturable, no
+ * host round trip, no atomics, no process-wide state, one writer per output.  counts[i] is a sum of integers: it depends on row
+ * i and on the reference SET alone -- not on n_rows, the row's place in the grid, the strides, the order of the references, how
+ * the launch splits them, or whether refs aliases emb.  The workspace (4-byte aligned,
+ * mkgnn_embed_count_within_workspace_bytes(n_rows, R) bytes; 0 for rejected sizes) is
+ *   [inverse norms: R + n_rows floats, padded to a multiple of 4][parts x n_rows int32 partial counts, when parts > 1]
+ * and needs no initialisation: it is read only where the same call wrote it.
+ *
+ * Limits as for mkgnn_embed_max_cosine: 1 <= H <= 64; 1 <= R <= MKGNN_MAX_COSINE_MAX_REFS; 0 <= n_rows < 2^31 (a count fits
+ * int32 with room to spare).  More references: call per slice and add.  n_rows == 0 is a no-op that returns 0, even with null
+ * pointers.  Anything else -- a limit, a stride below H, a min_sim that is NaN or infinite, a null pointer, a workspace that is
+ * too small or misaligned, an overlap -- returns non-zero with mkgnn_last_error set, before any launch. */
+size_t mkgnn_embed_count_within_workspace_bytes(int64_t n_rows, int32_t R);
+int mkgnn_embed_count_within(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* refs, int64_t ref_stride,
+                             int32_t R, float min_sim, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,14 @@ def max_cosine_split(n_rows: int, R: int):
     return per_part * MAX_COSINE_TILE, -(-tiles // per_part)
 
 
+def count_within_split(n_rows: int, R: int):
+    """``(references per part, parts)`` of one ``mkgnn_embed_count_within`` launch: the count is a second reduction over
+    ``mkgnn_embed_max_cosine``'s walk (one kernel text, one ``mc_split``), so it is ``max_cosine_split`` with ``MAX_COSINE_ROWS``,
+    ``MAX_COSINE_TILE`` and ``MAX_COSINE_MAX_PARTS`` as its tiling; a split launch keeps ``parts x n_rows`` int32 partial counts
+    in the workspace.  The result of a call does not depend on it; the tests place their shapes around it."""
+    return max_cosine_split(n_rows, R)
+
+
 def knn_split(n_rows: int, Q: int):
     """``(rows per part, parts)`` of one ``mkgnn_embed_knn_update`` launch (``knn_split``, kgnn_knn.hip): whole tiles per part, at
     least ``KNN_MIN_PART_TILES`` of them, at most ``KNN_MAX_PARTS`` parts and no more than bring the grid to ``KNN_TARGET_BLOCKS``
@@ -233,7 +241,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_embed_max_cosine_workspace_bytes", "mkgnn_select_rows", "mkgnn_tail_defer_projection",
            "mkgnn_debug_tail_projection_launches", "mkgnn_diverse_pick", "mkgnn_diverse_pick_workspace_bytes",
            "mkgnn_kernel_exemplars_update", "mkgnn_kernel_exemplars_workspace_bytes", "mkgnn_embed_knn_update",
-           "mkgnn_embed_knn_workspace_bytes")
+           "mkgnn_embed_knn_workspace_bytes", "mkgnn_embed_count_within", "mkgnn_embed_count_within_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -436,6 +444,11 @@ def load() -> C.CDLL:
     lib.mkgnn_embed_max_cosine_workspace_bytes.argtypes = [I64, I32]
     lib.mkgnn_embed_max_cosine.restype = C.c_int
     lib.mkgnn_embed_max_cosine.argtypes = [P, I64, I64, I32, P, I64, I32, P, P, P, C.c_size_t, P]
+    # the references above a threshold of every row: (emb, stride, n_rows, H, refs, stride, R, min_sim, counts, workspace, bytes, stream)
+    lib.mkgnn_embed_count_within_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_embed_count_within_workspace_bytes.argtypes = [I64, I32]
+    lib.mkgnn_embed_count_within.restype = C.c_int
+    lib.mkgnn_embed_count_within.argtypes = [P, I64, I64, I32, P, I64, I32, F32, P, P, C.c_size_t, P]
     # stable compaction by a key: (scores, ids, key, B, n_valid, bounds, out_scores, out_ids, n_kept, stream)
     lib.mkgnn_select_rows.restype = C.c_int
     lib.mkgnn_select_rows.argtypes = [P, P, P, I32, P, P, P, P, P, P]

@@ -1,4 +1,5 @@
-// The nearest reference of every embedding row (mkgnn_embed_max_cosine) and the stable compaction that hands the rows a filter
+// The nearest reference of every embedding row (mkgnn_embed_max_cosine), how many references lie above a threshold of it
+// (mkgnn_embed_count_within: the neighbour counts of a Butina clustering), and the stable compaction that hands the rows a filter
 // keeps to the running list (mkgnn_select_rows): novelty filter and applicability domain of a screen.
 //
 //     max_sim[i], arg_ref[i] = the first r, in the order of topk_update_reference (non-NaN before NaN, larger first with
@@ -20,6 +21,11 @@
 // by _lib.max_cosine_split) only has to fill the chip: a batch of 256 rows is two row blocks, so it is cut into up to MC_MAX_PARTS
 // parts of whole tiles, a batch of 4 096 rows against 16 384 references into 64 parts of 8 tiles (MC_TARGET_BLOCKS blocks in all).
 // Plain FP32 VALU: the bit contract forbids another summation order, and with it the matrix instructions.
+//
+// THE COUNT is a second reduction over the SAME walk: max_cosine_kernel takes what it does with every sim(i, r) as a policy --
+// McFirstMax keeps the first maximum, McCountAbove counts the r with sim(i, r) > min_sim (strict; a NaN fails it) -- so norms_kernel,
+// the split, the staging and the tile loop exist once.  counts[i] is a sum of integers: one part writes it itself, more parts write
+// workspace[part][row] and count_combine_kernel adds them, in any order the same number.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "kgnn_common.h"
@@ -66,11 +72,50 @@ __global__ void __launch_bounds__(256) norms_kernel(const float* __restrict__ re
 // the order: a non-NaN beats a NaN, a larger value beats a smaller one (-0.0 == +0.0: no strict >), the earlier one stays otherwise
 __device__ __forceinline__ bool mc_better(float s, float best) { return s == s && (best != best || s > best); }
 
-template <int W>
+// What a walk does with the similarities of one row: Out is what a launch writes to (and any scalar it compares with); take() sees
+// sim(i, r) of every reference of the part in order -- `live` is false where the walk hands the last reference of an odd tile in a
+// second time -- and store() writes the part's result to slot `at`.
+struct McFirstMax {                                              // the first maximum of the order above and its reference
+    struct Out { float* sim; int32_t* arg; };
+    float best;
+    int arg;
+    __device__ __forceinline__ McFirstMax(const Out&, int r_begin)
+        : best(__int_as_float(0x7fc00000)), arg(r_begin) {}      // "nothing yet": any first value replaces it, a NaN leaves it
+    __device__ __forceinline__ void take(float s, int r, bool) { // (a second look at the same reference: the strict order ignores it)
+        const bool b = mc_better(s, best);
+        best = b ? s : best;
+        arg = b ? r : arg;
+    }
+    __device__ __forceinline__ void store(const Out& o, int64_t at) const {
+        o.sim[at] = best;
+        o.arg[at] = arg;
+    }
+};
+
+struct McCountAbove {                                            // how many references lie above min_sim: strict, a NaN never counts
+    struct Out { int32_t* count; float min_sim; };
+    float bound;
+    int count;
+    __device__ __forceinline__ McCountAbove(const Out& o, int) : bound(o.min_sim), count(0) {}
+    // The empty asm emits nothing; it makes each similarity opaque where it arrives.  Without it the two comparisons of a pair of
+    // references are one two-wide operation to the compiler, which then packs EVERY step above them across the two references:
+    // v_pk_mul_f32 / v_pk_add_f32 on operands that are not neighbours in registers -- 232 registers at 32 columns, 256 and spills
+    // into the accumulation registers at 64, more moves than arithmetic, 1.4 / 1.8 times the first maximum's time.  With it each
+    // reference's products and tree levels are packed along the columns, whose operands are neighbours as they come from LDS: 77
+    // / 112 registers, the same bits (a packed operation rounds each element once).  -DMKGNN_COUNT_PLAIN: without
+    __device__ __forceinline__ void take(float s, int, bool live) {
+#ifndef MKGNN_COUNT_PLAIN
+        asm volatile("" : "+v"(s));
+#endif
+        count += (live && s > bound) ? 1 : 0;
+    }
+    __device__ __forceinline__ void store(const Out& o, int64_t at) const { o.count[at] = count; }
+};
+
+template <int W, typename Red>
 __global__ void __launch_bounds__(MC_ROWS) max_cosine_kernel(const float* __restrict__ emb, int64_t es, int64_t n, int H,
                                                              const float* __restrict__ refs, int64_t rs, int R, int part_refs,
-                                                             const float* __restrict__ inv, float* __restrict__ out_sim,
-                                                             int32_t* __restrict__ out_arg) {
+                                                             const float* __restrict__ inv, const typename Red::Out out) {
     __shared__ __attribute__((aligned(16))) float tile[MC_TILE * W];
     __shared__ float tinv[MC_TILE];
     const int t = threadIdx.x;
@@ -80,32 +125,24 @@ __global__ void __launch_bounds__(MC_ROWS) max_cosine_kernel(const float* __rest
     for (int j = 0; j < W; ++j) e[j] = j < H ? emb[ic * es + j] : 0.f;
     const float ie = inv[R + ic];
     const int r_begin = blockIdx.y * part_refs, r_end = min(R, r_begin + part_refs);
-    float best = __int_as_float(0x7fc00000);                    // "nothing yet": any first value replaces it, a NaN leaves it
-    int arg = r_begin;
+    Red red(out, r_begin);
     for (int r0 = r_begin; r0 < r_end; r0 += MC_TILE) {
         const int m = min(MC_TILE, r_end - r0);
         __syncthreads();                                         // (the previous tile has been walked by every wave)
         stage_padded_tile<W, MC_ROWS>(tile, tinv, m, [r0](int r) { return r0 + r; }, refs, rs, H, inv, t);
         __syncthreads();
         // two references in flight -- one's LDS reads under the other's adds -- and selects, not branches, between them; an odd
-        // tile's last reference is taken twice, which the strict order ignores
+        // tile's last reference is taken twice, the second time not `live`
         for (int r = 0; r < m; r += 2) {
-            const int r1 = r + 1 < m ? r + 1 : r;
+            const bool pair = r + 1 < m;
+            const int r1 = pair ? r + 1 : r;
             const float d0 = mc_dot<W>(e, tile + r * W), d1 = mc_dot<W>(e, tile + r1 * W);
             const float s0 = (d0 * ie) * tinv[r], s1 = (d1 * ie) * tinv[r1];
-            const bool b0 = mc_better(s0, best);
-            best = b0 ? s0 : best;
-            arg = b0 ? r0 + r : arg;
-            const bool b1 = mc_better(s1, best);
-            best = b1 ? s1 : best;
-            arg = b1 ? r0 + r1 : arg;
+            red.take(s0, r0 + r, true);
+            red.take(s1, r0 + r1, pair);
         }
     }
-    if (i < n) {
-        const int64_t o = (int64_t)blockIdx.y * n + i;          // (one part: out_* are the outputs themselves, o = i)
-        out_sim[o] = best;
-        out_arg[o] = arg;
-    }
+    if (i < n) red.store(out, (int64_t)blockIdx.y * n + i);      // (one part: out is the outputs themselves, slot i)
 }
 
 // the order between two candidates of DIFFERENT references: mc_better, and among equals (two NaNs, a == b) the lower index --
@@ -138,6 +175,18 @@ __global__ void __launch_bounds__(256) combine_kernel(const float* __restrict__ 
         max_sim[i] = best;
         arg_ref[i] = arg;
     }
+}
+
+// one half-wave per row: lane l adds the partial counts of parts l, l + 32, ..., then an xor tree of integer additions
+__global__ void __launch_bounds__(256) count_combine_kernel(const int32_t* __restrict__ part_count, int64_t n, int parts,
+                                                            int32_t* __restrict__ counts) {
+    const int l = threadIdx.x & 31;
+    const int64_t i = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5), ic = i < n ? i : n - 1;
+    int c = 0;
+    for (int p = l; p < parts; p += 32) c += part_count[(int64_t)p * n + ic];
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (l == 0 && i < n) counts[i] = c;
 }
 
 // mkgnn_select_rows: one workgroup; per pass of SEL_THREADS slots a ballot per wave, the waves' counts through LDS, the kept
@@ -226,14 +275,61 @@ extern "C" int mkgnn_embed_max_cosine(const float* emb, int64_t emb_stride, int6
     const int64_t vectors = (int64_t)R + n_rows;
     norms_kernel<<<(unsigned)((vectors + 7) / 8), 256, 0, st>>>(refs, ref_stride, R, emb, emb_stride, n_rows, H, inv);
     const dim3 grid((unsigned)((n_rows + MC_ROWS - 1) / MC_ROWS), (unsigned)sp.parts);
-    float* os = sp.parts > 1 ? part_sim : max_sim;
-    int32_t* oa = sp.parts > 1 ? part_arg : arg_ref;
+    const McFirstMax::Out out = {sp.parts > 1 ? part_sim : max_sim, sp.parts > 1 ? part_arg : arg_ref};
     if (H <= 32)
-        max_cosine_kernel<32><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, os, oa);
+        max_cosine_kernel<32, McFirstMax><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, out);
     else
-        max_cosine_kernel<64><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, os, oa);
+        max_cosine_kernel<64, McFirstMax><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, out);
     if (sp.parts > 1)
         combine_kernel<<<(unsigned)((n_rows + 7) / 8), 256, 0, st>>>(part_sim, part_arg, n_rows, sp.parts, max_sim, arg_ref);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+// [inverse norms: R + n floats, padded to 4][parts x n partial counts, when the references are split]
+extern "C" size_t mkgnn_embed_count_within_workspace_bytes(int64_t n_rows, int32_t R) {
+    if (!mc_sizes_ok(n_rows, R)) return 0;
+    const McSplit sp = mc_split(n_rows, R);
+    const size_t partials = sp.parts > 1 ? (size_t)sp.parts * (size_t)n_rows : 0;
+    return sizeof(float) * (mc_norm_floats(n_rows, R) + partials);
+}
+
+extern "C" int mkgnn_embed_count_within(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* refs,
+                                        int64_t ref_stride, int32_t R, float min_sim, int32_t* counts, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    const char* who = "mkgnn_embed_count_within";
+    if (R < 1 || R > MKGNN_MAX_COSINE_MAX_REFS)
+        return api_fail("%s: %d references outside [1, %d]", who, (int)R, MKGNN_MAX_COSINE_MAX_REFS);
+    if (H < 1 || H > MC_MAX_H) return api_fail("%s: embedding width %d outside [1, %d]", who, (int)H, MC_MAX_H);
+    if (n_rows < 0 || emb_stride < H || ref_stride < H) return api_fail("%s: bad shape", who);
+    if (!(min_sim - min_sim == 0.f)) return api_fail("%s: min_sim is not a finite threshold", who);
+    if (n_rows == 0) return 0;
+    if (!emb || !refs || !counts || !workspace) return api_fail("%s: null pointer", who);
+    if (!mc_sizes_ok(n_rows, R)) return api_fail("%s: %lld rows: at most 2^31 - 1 in one call", who, (long long)n_rows);
+    const size_t need = mkgnn_embed_count_within_workspace_bytes(n_rows, R);
+    if (workspace_bytes < need)
+        return api_fail("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    if (((uintptr_t)workspace & 3) != 0) return api_fail("%s: workspace not 4-byte aligned", who);
+    // what the launches write -- counts, the workspace -- must not overlap what they read, nor each other (refs may be emb)
+    const Span wr[2] = {{counts, (size_t)n_rows * 4}, {workspace, need}};
+    const Span rd[2] = {{emb, ((size_t)(n_rows - 1) * (size_t)emb_stride + (size_t)H) * 4},
+                        {refs, ((size_t)(R - 1) * (size_t)ref_stride + (size_t)H) * 4}};
+    if (spans_disjoint(who, wr, 2, rd, 2, "an output (counts, workspace) aliases an input", "counts and the workspace alias each other"))
+        return 1;
+    const hipStream_t st = (hipStream_t)stream;
+    const McSplit sp = mc_split(n_rows, R);
+    float* inv = (float*)workspace;
+    int32_t* part_count = (int32_t*)(inv + mc_norm_floats(n_rows, R));
+    const int64_t vectors = (int64_t)R + n_rows;
+    norms_kernel<<<(unsigned)((vectors + 7) / 8), 256, 0, st>>>(refs, ref_stride, R, emb, emb_stride, n_rows, H, inv);
+    const dim3 grid((unsigned)((n_rows + MC_ROWS - 1) / MC_ROWS), (unsigned)sp.parts);
+    const McCountAbove::Out out = {sp.parts > 1 ? part_count : counts, min_sim};
+    if (H <= 32)
+        max_cosine_kernel<32, McCountAbove><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, out);
+    else
+        max_cosine_kernel<64, McCountAbove><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, out);
+    if (sp.parts > 1)
+        count_combine_kernel<<<(unsigned)((n_rows + 7) / 8), 256, 0, st>>>(part_count, n_rows, sp.parts, counts);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }

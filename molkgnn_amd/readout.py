@@ -1028,6 +1028,73 @@ def embedding_max_cosine(emb: torch.Tensor, refs: torch.Tensor, n_rows: Optional
     return max_sim, arg_ref
 
 
+def embedding_count_within_supported(R: int, H: int) -> bool:
+    """The shapes ``mkgnn_embed_count_within`` takes; anything else goes through torch operators on the GPU."""
+    return 1 <= R <= _lib.MAX_COSINE_MAX_REFS and 1 <= H <= _lib.MAX_COSINE_MAX_H
+
+
+def embedding_count_within(emb: torch.Tensor, refs: torch.Tensor, min_sim: float, n_rows: Optional[int] = None,
+                           out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``counts int32 [n_rows]``: for each of the leading ``n_rows`` rows of a float32 CUDA ``emb [n, H]`` the number of rows ``r`` of a
+    float32 CUDA ``refs [R, H]`` with ``S[i, r] > min_sim`` -- ``S[i, r]`` the similarity ``embedding_cosine`` gives for the pair
+    (row ``i`` as the row, ``refs[r]`` as the query), BIT FOR BIT, which is also what ``diverse_pick`` compares; the comparison is
+    strict and a NaN never counts (``screening.count_within_reference`` is the definition over a given matrix).  There is no
+    "self": with ``refs`` the tensor ``emb`` itself the diagonal is a pair like any other.  One ``mkgnn_embed_count_within``: both
+    tensors are read raw, so a captured call follows their contents; no ``[n, R]`` matrix exists; a count is a sum of integers and
+    depends neither on the order of the references nor on how a launch splits them.  ``min_sim`` is finite.  ``out``: a contiguous
+    int32 ``[n_rows]`` tensor on the device to write into (not a view of ``emb`` or ``refs``).  ``workspace``: a uint8 device tensor
+    of at least ``mkgnn_embed_count_within_workspace_bytes(n_rows, R)`` bytes to use as scratch; without it a per-device buffer that
+    only grows serves eager calls, and a call inside a capture allocates its own.  More than 2^20 references or an embedding
+    wider than 64: the same definition through torch operators on the GPU, ``MAX_COSINE_TORCH_CHUNK`` references at a time
+    (float64 products, rounded once: inside ``screening.cosine_bound``, not the kernel's bits).  It has no autograd node: called
+    where a gradient is being recorded for one of its inputs it raises instead of dropping it."""
+    if not (torch.is_tensor(emb) and torch.is_tensor(refs)) or emb.dim() != 2 or refs.dim() != 2 \
+            or emb.dtype != torch.float32 or refs.dtype != torch.float32 or refs.shape[1] != emb.shape[1]:
+        raise ValueError("embedding_count_within needs a float32 [n, H] embedding and float32 [R, H] references")
+    R, H = refs.shape
+    if R < 1 or H < 1:
+        raise ValueError(f"embedding_count_within needs at least one reference and one column, not {R} x {H}")
+    min_sim = float(min_sim)
+    if min_sim != min_sim or min_sim in (float("inf"), float("-inf")):
+        raise ValueError(f"embedding_count_within: min_sim = {min_sim} is not a finite threshold")
+    if not emb.is_cuda or refs.device != emb.device:
+        raise ValueError(f"embedding_count_within runs on the GPU: emb is on {emb.device}, refs on {refs.device} (there is no CPU "
+                         "path; screening.count_within_reference is the host form)")
+    if torch.is_grad_enabled() and (emb.requires_grad or refs.requires_grad):
+        raise RuntimeError("embedding_count_within is forward only: call it under torch.no_grad() (or on detached inputs)")
+    n = emb.shape[0] if n_rows is None else int(n_rows)
+    if not 0 <= n <= emb.shape[0]:
+        raise ValueError(f"n_rows = {n_rows} outside [0, {emb.shape[0]}]")
+    dev = emb.device
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.int32 or out.device != dev or tuple(out.shape) != (n,) \
+            or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous int32 [{n}] tensor on {dev}")
+    if n == 0:
+        return out
+    if not embedding_count_within_supported(R, H):
+        e, eps = emb[:n].detach().double(), float(torch.tensor(COSINE_EPS, dtype=torch.float32))
+        ie = 1.0 / e.square().sum(dim=1).sqrt().clamp_min(eps)
+        total = torch.zeros(n, dtype=torch.int64, device=dev)
+        bound = torch.tensor(min_sim, dtype=torch.float32, device=dev)     # (rounded to float32, as the kernel's argument is)
+        for a in range(0, R, MAX_COSINE_TORCH_CHUNK):
+            q = refs[a:a + MAX_COSINE_TORCH_CHUNK].detach().double()
+            iq = 1.0 / q.square().sum(dim=1).sqrt().clamp_min(eps)
+            sim = ((e @ q.t() + 0.0) * ie[:, None] * iq[None, :]).float()
+            total += (sim > bound).sum(dim=1)                    # (strict; a NaN compares False)
+        out.copy_(total)
+        return out
+    emb, refs = _row_major(emb.detach()), _row_major(refs.detach())
+    lib = _lib.load()
+    ws = _max_cosine_workspace(dev, int(lib.mkgnn_embed_count_within_workspace_bytes(n, R)), workspace)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkgnn_embed_count_within(emb.data_ptr(), _stride0(emb), n, H, refs.data_ptr(), _stride0(refs), R, min_sim,
+                                                out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
+                   "mkgnn_embed_count_within")
+    return out
+
+
 def select_rows(scores: torch.Tensor, ids: torch.Tensor, key: torch.Tensor, n_valid, bounds: torch.Tensor, out=None):
     """``(out_scores float32 [B], out_ids int32 [B], n_kept int32 [1])``: the stable compaction ``mkgnn_select_rows`` -- the slots
     ``i < min(max(n_valid, 0), B)`` with ``bounds[0] <= key[i] <= bounds[1]`` (a NaN key is never kept), in order, at the head of the

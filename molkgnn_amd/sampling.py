@@ -4,6 +4,9 @@ The reference weights every training molecule by the inverse size of its class a
 per epoch with ``torch.utils.data.WeightedRandomSampler`` seeded from the run's seed.  Same weights, same sampler
 class, same generator seeding here -- so the same labels and seed give the same index stream -- computed from a label
 tensor in one pass instead of a Python loop over ``Data`` objects.
+
+``cluster_split`` is not the reference's: its split is random (``data.py``), which puts near-copies of a training molecule into
+the test set; given the clusters of ``screening.cluster_butina_embeddings`` it keeps every cluster in one fold.
 """
 from __future__ import annotations
 
@@ -28,6 +31,46 @@ def oversampling_sampler(labels: torch.Tensor, seed: int) -> WeightedRandomSampl
     generator = torch.Generator()
     generator.manual_seed(seed)
     return WeightedRandomSampler(weights=weights, num_samples=len(weights), generator=generator)
+
+
+def cluster_split(leader, fractions=(0.8, 0.1, 0.1), seed: int = 0) -> torch.Tensor:
+    """A cluster-based split: the fold (``0 .. len(fractions) - 1``; train / validation / test for the default) of every row, int64
+    ``[n]`` on the device of ``leader``, with WHOLE clusters per fold -- so near-copies of a training molecule do not sit in the test
+    set, which the reference's random split does not prevent.  ``leader`` is an integer ``[n]`` tensor naming every row's cluster, as
+    ``screening.cluster_butina_embeddings`` (or ``pick_diverse_embeddings``) returns it: rows with the same value ``>= 0`` form one
+    cluster, and a row with ``-1`` is a cluster of its own.  The clusters are taken in an order drawn from a ``torch.Generator``
+    seeded with ``seed`` (over the clusters by ascending name, the ``-1`` rows behind them in row order), and each goes to the fold
+    furthest below its target count ``fractions[f] / sum(fractions) * n`` at that moment, ties to the lower fold.  A fold below its
+    target exists while rows remain, so no fold is filled beyond its target by more than one cluster, and none ends further below
+    it than the largest cluster's size.  Host logic (the walk is sequential), deterministic in its arguments."""
+    lead = torch.as_tensor(leader)
+    if lead.dim() != 1 or lead.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError("cluster_split: leader is an integer [n] tensor")
+    share = [float(f) for f in fractions]
+    if not share or any(f != f or f < 0 or f == float("inf") for f in share) or sum(share) <= 0:
+        raise ValueError(f"cluster_split: fractions = {tuple(fractions)}: finite, not negative, and not all zero")
+    host = lead.detach().cpu().long()
+    n = host.numel()
+    if n and int(host.min()) < -1:
+        raise ValueError("cluster_split: leader holds a value below -1")
+    named = host >= 0
+    _, which = torch.unique(host[named], return_inverse=True)     # rows with a leader -> their cluster, by ascending name
+    n_named = int(which.max()) + 1 if which.numel() else 0
+    cluster = torch.empty(n, dtype=torch.int64)
+    cluster[named] = which
+    cluster[~named] = n_named + torch.arange(n - int(named.sum()))
+    sizes = torch.bincount(cluster, minlength=1)[:int(cluster.max()) + 1 if n else 0].tolist()
+    generator = torch.Generator()
+    generator.manual_seed(int(seed))
+    target = [f / sum(share) * n for f in share]
+    filled = [0] * len(share)
+    fold_of = [0] * len(sizes)
+    for c in torch.randperm(len(sizes), generator=generator).tolist():
+        f = max(range(len(share)), key=lambda j: (target[j] - filled[j], -j))
+        fold_of[c] = f
+        filled[f] += sizes[c]
+    folds = torch.tensor(fold_of, dtype=torch.int64)[cluster] if n else torch.zeros(0, dtype=torch.int64)
+    return folds.to(lead.device)
 
 
 def task_index(assay_id, assays) -> torch.Tensor:

@@ -51,6 +51,13 @@ Diverse hits -- the best molecule of every chemical series among the top of a ra
 ``pick_diverse_embeddings``              the stored-embedding route: embeddings and scores -> picks, leaders, cluster sizes
 ``screen_diverse``                       shards -> a pool of the best ``pool`` molecules, and the ``k`` diverse picks among them
 
+Neighbour counts and Butina clusters -- how many molecules lie above a similarity threshold of each (``mkgnn_embed_count_within``),
+and the clustering that ranks by that count and then does the leader walk (``mkgnn_diverse_pick``) in count order:
+
+``count_within_reference`` / ``butina_reference``  the two definitions in numpy over a given similarity matrix
+``neighbour_counts``                     stored embeddings against any number of references: analogue counts
+``cluster_butina_embeddings``            stored embeddings -> centroids, every row's cluster, the best-scoring member of each
+
 What each kernel learned -- for every kernel column of a convolution layer the ``k`` atoms of the library it matches best
 (``GNNModel.kernel_scores``, ``mkgnn_kernel_exemplars_update``; one running list per column, a candidate is an atom):
 
@@ -1195,20 +1202,34 @@ def pick_diverse_embeddings(emb: torch.Tensor, scores: torch.Tensor, max_sim: fl
     if dev.type != "cuda" or scores.device != dev or (ids is not None and ids.device != dev):
         raise ValueError(f"{who}: emb is on {dev}; the selection runs on the GPU, with scores and ids on the same device (there is "
                          "no CPU path; diverse_pick_reference is the host form)")
-    from .readout import diverse_pick
     emb, scores = emb.detach(), scores.detach()
     order = rank_order(scores)
+    picks, name, _, by_row, sim_by_row, sizes = _walk_in_order(emb, order, max_sim, k, ids)
+    return {"picks": name[picks], "pick_score": scores[order[picks]], "leader": by_row, "leader_sim": sim_by_row,
+            "cluster_size": sizes, "order": order}
+
+
+def _walk_in_order(emb: torch.Tensor, order: torch.Tensor, max_sim: float, k: int, ids: Optional[torch.Tensor]):
+    """``readout.diverse_pick`` over the rows of ``emb`` gathered in ``order`` (int64 ``[n]``, a permutation of the rows), mapped back
+    to the caller's rows: ``(picks, name, leader_row, leader, leader_sim, cluster_size)`` -- ``picks`` int64 POSITIONS in ``order`` in
+    pick order, ``name [n]`` what the caller calls the row at every position (``ids[order]``, or ``order`` itself), ``leader_row [n]``
+    by the caller's row the ROW of the pick that covers it (``-1``: none), ``leader`` the same as ``name``s, ``leader_sim [n]`` by the
+    caller's row, ``cluster_size`` the rows every pick leads.  One host read: the number of picks."""
+    from .readout import diverse_pick
     picks, n_picks, leader, leader_sim = diverse_pick(emb.index_select(0, order), max_sim, k)
     picks = picks[:int(n_picks.item())].long()                   # (the one host read)
     name = order if ids is None else ids.long().index_select(0, order)          # rank position -> what the caller calls the row
     led = leader.long()
-    named = torch.where(led >= 0, name[led.clamp_min(0)], led)
-    by_row = torch.empty_like(named)
-    by_row[order] = named
+    row_by_row = torch.empty_like(led)
+    row_by_row[order] = torch.where(led >= 0, order[led.clamp_min(0)], led)
+    if ids is None:
+        by_row = row_by_row
+    else:
+        by_row = torch.empty_like(led)
+        by_row[order] = torch.where(led >= 0, name[led.clamp_min(0)], led)
     sim_by_row = torch.empty_like(leader_sim)
     sim_by_row[order] = leader_sim
-    return {"picks": name[picks], "pick_score": scores[order[picks]], "leader": by_row, "leader_sim": sim_by_row,
-            "cluster_size": _cluster_sizes(leader, picks, n), "order": order}
+    return picks, name, row_by_row, by_row, sim_by_row, _cluster_sizes(leader, picks, int(emb.shape[0]))
 
 
 DIVERSE_MAX_POOL = 1024                         # the pool of screen_diverse is a TopK: MKGNN_TOPK_MAX_K
@@ -1284,6 +1305,159 @@ def screen_diverse(model, residents, k: int, batch_size: int, max_sim: float, po
               "n_scored": n_scored}
     if return_embeddings:
         result["embeddings"] = embs
+    return result
+
+
+# ------------------------------------------------------------------------- neighbour counts, Butina clusters --
+# Everything above asks for the nearest molecule or the first one above a threshold.  HOW MANY lie above it is what the standard
+# clustering of hit lists and screening decks (Taylor-Butina) ranks by: the molecule with the most neighbours is the first
+# centroid and takes its neighbours, the next unassigned molecule in count order is the next one.  With static counts that is the
+# leader walk (``mkgnn_diverse_pick``) in count order; the count is ``mkgnn_embed_count_within``, over the same similarity bits.
+#
+# ``count_within_reference`` / ``butina_reference``  the definitions in numpy, over a given similarity matrix
+# ``neighbour_counts``                               stored embeddings against any number of references: analogue counts
+# ``cluster_butina_embeddings``                      stored embeddings -> centroids, every row's cluster, the best member of each
+NEIGHBOUR_SLICE = 1 << 20                      # references per mkgnn_embed_count_within: MKGNN_MAX_COSINE_MAX_REFS
+BUTINA_MAX_ROWS = 1 << 20                      # MKGNN_DIVERSE_MAX_ROWS = MKGNN_MAX_COSINE_MAX_REFS: the walk and the self-join
+
+
+def count_within_reference(sim, min_sim) -> np.ndarray:
+    """The definition of ``mkgnn_embed_count_within`` (include/molkgnn_hip.h), on the host, over a GIVEN similarity matrix ``sim [n,
+    R]`` (float32 or float64; ``sim[i, r]`` is the similarity of row ``i`` as the row with reference ``r`` as the query): int64
+    ``[n]``, the number of ``r`` with ``sim[i, r] > min_sim`` -- strict; a NaN never counts.  The comparison is made in ``sim``'s own
+    dtype: ``min_sim`` is rounded to it first."""
+    if torch.is_tensor(sim):
+        sim = sim.detach().cpu().numpy()
+    sim = np.asarray(sim)
+    if sim.ndim != 2 or sim.dtype not in (np.float32, np.float64):
+        raise ValueError("a float32 or float64 [n, R] similarity matrix is needed")
+    bound = sim.dtype.type(min_sim)
+    if not np.isfinite(bound):
+        raise ValueError(f"min_sim = {min_sim} is not a finite similarity threshold")
+    with np.errstate(invalid="ignore"):
+        return (sim > bound).sum(axis=1).astype(np.int64)
+
+
+def butina_reference(sim, min_sim, k_max):
+    """Taylor-Butina clustering with static counts, on the host, over a GIVEN square similarity matrix (float32 or float64; ``sim[i,
+    p]`` is the similarity of row ``i`` as the row with row ``p`` as the query): ``(centroids int32 [k_max], n_clusters, leader int32
+    [n], leader_sim [n], counts int64 [n], order int64 [n])``.  ``counts = count_within_reference(sim, min_sim)`` (the diagonal is a
+    pair like any other); ``order`` is the rows by count descending, ties to the lower row; ``diverse_pick_reference`` walks ``sim``
+    permuted by ``order`` with ``min_sim`` as its threshold and at most ``k_max`` picks, and its indices are mapped back to rows.  A
+    composition: NaN rows, zero rows and a full list behave as the leader walk defines them.  ``centroids`` is in cluster order,
+    densest first, unused slots ``-1``; ``leader[i]`` is the centroid ROW of row ``i`` (``-1``: none), ``leader_sim[i]`` in ``sim``'s
+    dtype (NaN: none)."""
+    counts = count_within_reference(sim, min_sim)
+    if torch.is_tensor(sim):
+        sim = sim.detach().cpu().numpy()
+    sim = np.asarray(sim)
+    if sim.shape[0] != sim.shape[1]:
+        raise ValueError("a square float32 or float64 similarity matrix is needed")
+    n = sim.shape[0]
+    order = np.argsort(-counts, kind="stable").astype(np.int64)
+    picks, n_picks, lead, lead_sim = diverse_pick_reference(sim[np.ix_(order, order)], min_sim, k_max)
+    centroids = np.where(picks >= 0, order[np.maximum(picks, 0)], -1).astype(np.int32)
+    leader = np.full(n, -1, dtype=np.int32)
+    leader[order] = np.where(lead >= 0, order[np.maximum(lead, 0)], -1)
+    leader_sim = np.full(n, np.nan, dtype=sim.dtype)
+    leader_sim[order] = lead_sim
+    return centroids, n_picks, leader, leader_sim, counts, order
+
+
+def _check_embeddings(who: str, emb, what: str = "emb") -> None:
+    if not torch.is_tensor(emb) or emb.dim() != 2 or emb.dtype != torch.float32 or emb.shape[1] < 1:
+        raise ValueError(f"{who}: {what} is a float32 [n, G] tensor")
+
+
+def neighbour_counts(emb: torch.Tensor, refs: torch.Tensor, min_sim: float) -> torch.Tensor:
+    """The stored-embedding route for analogue counts ("SAR by catalogue"): int64 ``[n]``, for every row of ``emb`` (float32 ``[n,
+    G]`` on the GPU) the number of rows of ``refs`` (float32 ``[R, G]`` on the same device, ANY ``R >= 1``) whose cosine similarity to
+    it lies above ``min_sim`` -- ``readout.embedding_count_within``'s definition and bits (``count_within_reference`` is the host
+    form): strict, a NaN never counts, no "self".  The references go in slices of at most 2^20 rows, one
+    ``mkgnn_embed_count_within`` each, and the int32 results are added in int64; no ``[n, R]`` matrix exists and nothing is read
+    back to the host.  A wrong shape, dtype or device, a NaN or infinite ``min_sim``: ``ValueError`` before a launch."""
+    who = "neighbour_counts"
+    _check_embeddings(who, emb)
+    _check_embeddings(who, refs, "refs")
+    if refs.shape[1] != emb.shape[1] or refs.shape[0] < 1:
+        raise ValueError(f"{who}: refs holds at least one row as wide as emb ({emb.shape[1]}), not {tuple(refs.shape)}")
+    min_sim = _check_max_sim(who, min_sim)
+    dev = emb.device
+    if dev.type != "cuda" or refs.device != dev:
+        raise ValueError(f"{who}: emb is on {dev}, refs on {refs.device}; the count runs on the GPU, with both on the same device "
+                         "(there is no CPU path; count_within_reference is the host form)")
+    from .readout import embedding_count_within
+    emb, refs = emb.detach(), refs.detach()
+    total = torch.zeros(emb.shape[0], dtype=torch.int64, device=dev)
+    part = torch.empty(emb.shape[0], dtype=torch.int32, device=dev)
+    for a in range(0, int(refs.shape[0]), NEIGHBOUR_SLICE):
+        total += embedding_count_within(emb, refs[a:a + NEIGHBOUR_SLICE], min_sim, out=part)
+    return total
+
+
+def cluster_butina_embeddings(emb: torch.Tensor, min_sim: float, k: Optional[int] = None, scores: Optional[torch.Tensor] = None,
+                              ids: Optional[torch.Tensor] = None) -> dict:
+    """Taylor-Butina clustering (static counts) of ANY set of molecules whose embeddings are kept, up to 2^20 rows, WITHOUT running
+    the network: ``emb`` float32 ``[n, G]`` on the GPU.  Every row's neighbours above ``min_sim`` are counted
+    (``readout.embedding_count_within(emb, emb, min_sim)``: the self-join, the diagonal included), the rows are sorted by count
+    descending (stable: ties to the lower row), gathered in that order, and ``readout.diverse_pick`` walks them with ``min_sim`` as
+    its threshold and at most ``k`` picks (default: no cap) -- the count and the walk compare the same similarity bits, so a
+    neighbour in the count is a neighbour in the walk; ``butina_reference`` is the definition.  The densest row becomes the first
+    centroid and takes its neighbours, the next unassigned row in count order the next: a series is represented by its centre,
+    where ``pick_diverse_embeddings`` starts its clusters at whatever scores best.  Returns a dict in terms of the caller's rows --
+    ``ids[row]`` when ``ids`` (an integer ``[n]`` tensor on the GPU) is given, the row numbers otherwise:
+
+    ``centroids``        ``[n_clusters]`` int64: the centroids in cluster order, densest first
+    ``neighbour_count``  ``[n]`` int64, by the caller's row: the rows above ``min_sim`` of it, itself included
+    ``leader``           ``[n]`` int64, by the caller's row: the centroid of its cluster (itself for a centroid), ``-1`` for none
+    ``leader_sim``       ``[n]`` float32, by the caller's row: the similarity to that centroid, NaN for none
+    ``cluster_size``     ``[n_clusters]`` int64: the rows of every cluster, the centroid included
+    ``order``            ``[n]`` int64: the caller's rows in count order (``order[0]`` is the densest row)
+
+    and, when ``scores`` (float32 ``[n]`` on the GPU) is given, the molecule one buys from every series:
+
+    ``cluster_best``        ``[n_clusters]`` int64: the member of every cluster that comes first in ``rank_order(scores)``
+    ``cluster_best_score``  ``[n_clusters]`` float32: its score
+
+    The hit-list use needs no new pass over a library: ``r = screen_diverse(...)``, then ``cluster_butina_embeddings(r["pool_emb"],
+    min_sim, scores=r["pool_score"])``; the whole-shard use is ``embed_resident`` plus ``score_resident``, then this function.  One
+    host read (the number of clusters).  A wrong shape, dtype or device, a NaN or infinite ``min_sim``, ``n`` outside ``[1, 2^20]``,
+    ``k`` outside ``[1, n]``: ``ValueError`` before a launch."""
+    who = "cluster_butina_embeddings"
+    _check_embeddings(who, emb)
+    n = int(emb.shape[0])
+    if not 1 <= n <= BUTINA_MAX_ROWS:
+        raise ValueError(f"{who}: {n} rows outside [1, {BUTINA_MAX_ROWS}]")
+    min_sim = _check_max_sim(who, min_sim)
+    k = n if k is None else int(k)
+    if not 1 <= k <= n:
+        raise ValueError(f"{who}: k = {k} outside [1, {n}]")
+    if scores is not None and (not torch.is_tensor(scores) or scores.dtype != torch.float32 or tuple(scores.shape) != (n,)):
+        raise ValueError(f"{who}: scores is a float32 [{n}] tensor, one score per row of emb")
+    integer = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+    if ids is not None and (not torch.is_tensor(ids) or ids.dtype not in integer or tuple(ids.shape) != (n,)):
+        raise ValueError(f"{who}: ids is an integer [{n}] tensor")
+    dev = emb.device
+    if dev.type != "cuda" or (scores is not None and scores.device != dev) or (ids is not None and ids.device != dev):
+        raise ValueError(f"{who}: emb is on {dev}; the clustering runs on the GPU, with scores and ids on the same device (there is "
+                         "no CPU path; butina_reference is the host form)")
+    from .readout import embedding_count_within
+    emb = emb.detach()
+    counts = embedding_count_within(emb, emb, min_sim)
+    order = torch.sort(counts, descending=True, stable=True).indices
+    picks, name, leader_row, leader, leader_sim, sizes = _walk_in_order(emb, order, min_sim, k, ids)
+    result = {"centroids": name[picks], "neighbour_count": counts.long(), "leader": leader, "leader_sim": leader_sim,
+              "cluster_size": sizes, "order": order}
+    if scores is not None:
+        scores = scores.detach()
+        ranked = rank_order(scores)
+        place = torch.empty_like(ranked)
+        place[ranked] = torch.arange(n, device=dev)               # row -> its place in the ranking
+        first = torch.full((n + 1,), n, dtype=torch.int64, device=dev)             # (slot n: the rows without a cluster)
+        first.scatter_reduce_(0, torch.where(leader_row >= 0, leader_row, n), place, reduce="amin")   # centroid row -> its members' best place
+        best = ranked[first[order[picks]]]                         # (every centroid leads itself: its slot is set)
+        result["cluster_best"] = best if ids is None else ids.long()[best]
+        result["cluster_best_score"] = scores[best]
     return result
 
 
