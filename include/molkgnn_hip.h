@@ -1233,6 +1233,76 @@ size_t mkgnn_embed_count_within_workspace_bytes(int64_t n_rows, int32_t R);
 int mkgnn_embed_count_within(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* refs, int64_t ref_stride,
                              int32_t R, float min_sim, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- neighbour lists (additive; the ABI version stays 8): WHICH references lie within a similarity threshold of every embedding
+ * row -- the pairs mkgnn_embed_count_within counts, written into a CSR whose row pointers the caller made from those counts.
+ *   for row i, the r in [0, R) with sim(i, r) > min_sim, in ASCENDING r, as (nbr_ref, nbr_sim) = (r, sim(i, r)) in the slots
+ *   row_ptr[i], row_ptr[i] + 1, ...;   found[i] = the number of such r, whether written or not
+ * sim(i, r), the strict comparison and the NaN rule are mkgnn_embed_count_within's, BIT FOR BIT: nbr_sim holds the float32 values
+ * mkgnn_embed_cosine writes for row i as the ROW and refs[r] as the QUERY, and found is what the count returns.  With row_ptr the
+ * exclusive sum of the count's result for the same inputs and threshold (row_ptr[n_rows] <= capacity), every slot of
+ * [0, row_ptr[n_rows]) is written exactly once.  emb, refs, the strides, min_sim: as for the count (refs may be emb: the self-join,
+ * the diagonal a pair like any other).  row_ptr int64 [n_rows + 1] on the DEVICE, read when the launches run; nbr_ref int32 and
+ * nbr_sim float32 [capacity] each, found int32 [n_rows], contiguous.
+ *
+ * THE GUARD.  Row i writes only slots s with  0 <= row_ptr[i] <= s < min(row_ptr[i + 1], capacity)  -- WHATEVER row_ptr holds:
+ * counts of another threshold or of other contents, negative, non-monotone or huge values.  A row whose row_ptr[i] lies outside
+ * [0, capacity), or whose segment is empty or runs backwards, writes nothing; pairs beyond the end of a segment are counted in
+ * found and dropped, so found[i] > row_ptr[i + 1] - row_ptr[i] is how a caller sees that a list was cut (the prefix that was
+ * written is right).  Segments that overlap because row_ptr is not monotone are written by more than one row, inside those
+ * bounds.  capacity == 0 with null nbr_ref / nbr_sim is legal: found is still written.
+ *
+ * The count's walk with a third reduction.  References not split over the grid: the norms and ONE walk, which writes found itself.
+ * Split: the norms, the COUNT walk into the workspace's [parts][n_rows] partials, a small launch that turns each row's partials
+ * into exclusive offsets over the parts and writes found, then the FILL walk, every part starting at its offset -- so a split
+ * call walks the references twice (on top of the caller's own count).  Capturable, no host round trip, no atomics, no
+ * process-wide state, one writer per slot; plain FP32.  The lists depend on row i, the references and row_ptr alone -- not on
+ * n_rows, the row's place in the grid, the strides, how the launch splits the references, or whether refs aliases emb.  The
+ * workspace (4-byte aligned, mkgnn_embed_neighbours_within_workspace_bytes(n_rows, R) bytes; 0 for rejected sizes) is the count's:
+ *   [inverse norms: R + n_rows floats, padded to a multiple of 4][parts x n_rows int32, when parts > 1]
+ * and needs no initialisation.
+ *
+ * Limits as for the count: 1 <= H <= 64; 1 <= R <= MKGNN_MAX_COSINE_MAX_REFS; 0 <= n_rows < 2^31; 0 <= capacity.  n_rows == 0 is a
+ * no-op that returns 0, even with null pointers.  Anything else -- a limit, a stride below H, a min_sim that is NaN or infinite,
+ * a null emb, refs, row_ptr, found or workspace (or a null list with capacity > 0), a workspace that is too small or misaligned,
+ * an output (the lists, found, the workspace) that overlaps emb, refs, row_ptr or another output -- returns non-zero with
+ * mkgnn_last_error set, before any launch. */
+size_t mkgnn_embed_neighbours_within_workspace_bytes(int64_t n_rows, int32_t R);
+int mkgnn_embed_neighbours_within(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* refs,
+                                  int64_t ref_stride, int32_t R, float min_sim, const int64_t* row_ptr, int64_t capacity,
+                                  int32_t* nbr_ref, float* nbr_sim, int32_t* found, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+
+/* ---- connected components of CSR neighbour lists (additive; the ABI version stays 8): the single-linkage clusters of a
+ * threshold graph -- the finest partition with no linked pair across its parts.
+ *   labels[v] = the smallest vertex of v's component, in the graph on [0, n) where u and v are linked if col holds v in u's
+ *   segment [row_ptr[u], row_ptr[u + 1]) OR u in v's
+ * The union matters: sim(i, j) and sim(j, i) of the lists above round their two scalings in different orders, so a threshold
+ * graph can hold an edge in one direction only.  Self-loops and duplicate edges are harmless.  row_ptr int64 [n + 1] and col
+ * int32 [row_ptr[n]] on the device; labels int32 [n].
+ *
+ * Nothing is indexed with input that was not checked: a segment is walked only if 0 <= row_ptr[v] <= row_ptr[v + 1] <= row_ptr[n]
+ * and an edge used only if 0 <= col[e] < n; anything else is skipped and sets state[2] (so col must hold row_ptr[n] entries: that,
+ * the operator cannot check).  With resume = 1 a label outside [0, v] is replaced by v and sets state[2] too.
+ *
+ * Hook and compress, in rounds of two launches: the hook reads both endpoints' parents of the previous round (roots, after its
+ * compression; a snapshot) and lowers the larger root's entry of a copy to the smaller root with atomicMin; the compress makes
+ * every vertex point at its root.  The fixpoint is unique, so the result is deterministic although the atomics' order is not.  A
+ * call enqueues 2 ceil(log2 max(n, 2)) + 1 rounds; a per-round device flag makes every launch behind a round
+ * that changed nothing return at once.  No host round trip; capturable.  state int32 [4] on the device:
+ *   state[0] the rounds of this call that changed a label, state[1] 1 if the last enqueued round changed nothing (converged:
+ *   labels is the answer), state[2] 1 if something was skipped as described, state[3] 0
+ * resume: 0 starts from every vertex as its own label; 1 goes on from labels as an earlier call on the SAME graph left them --
+ * what a caller does while state[1] == 0 (every such call lowers a label or converges).  Bits 8 and up of resume, when non-zero,
+ * cap the rounds of the call below the number above (diagnostics: that is how the tests reach state[1] == 0).
+ * The workspace (4-byte aligned, mkgnn_graph_components_workspace_bytes(n) = 4 (2 n + 72) bytes; 0 for a rejected n) needs no
+ * initialisation.  0 <= n <= MKGNN_COMPONENTS_MAX_VERTICES; n == 0 writes state alone.  A limit, a resume that is neither, a null
+ * row_ptr, state or workspace (or labels with n > 0), a workspace that is too small or misaligned, an output that overlaps
+ * row_ptr or another output: non-zero with mkgnn_last_error set, before any launch. */
+#define MKGNN_COMPONENTS_MAX_VERTICES 134217728
+size_t mkgnn_graph_components_workspace_bytes(int32_t n);
+int mkgnn_graph_components(const int64_t* row_ptr, const int32_t* col, int32_t n, int32_t* labels, int32_t* state, int32_t resume,
+                           int32_t* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

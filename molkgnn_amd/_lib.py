@@ -66,6 +66,15 @@ def count_within_split(n_rows: int, R: int):
     return max_cosine_split(n_rows, R)
 
 
+COMPONENTS_MAX_VERTICES = 1 << 27               # MKGNN_COMPONENTS_MAX_VERTICES
+
+
+def components_rounds(n: int) -> int:
+    """The rounds one ``mkgnn_graph_components`` enqueues for ``n`` vertices (``cc_rounds``, kgnn_components.hip):
+    ``2 * ceil(log2(max(n, 2))) + 1``."""
+    return 2 * (max(int(n), 2) - 1).bit_length() + 1
+
+
 def knn_split(n_rows: int, Q: int):
     """``(rows per part, parts)`` of one ``mkgnn_embed_knn_update`` launch (``knn_split``, kgnn_knn.hip): whole tiles per part, at
     least ``KNN_MIN_PART_TILES`` of them, at most ``KNN_MAX_PARTS`` parts and no more than bring the grid to ``KNN_TARGET_BLOCKS``
@@ -241,7 +250,9 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_embed_max_cosine_workspace_bytes", "mkgnn_select_rows", "mkgnn_tail_defer_projection",
            "mkgnn_debug_tail_projection_launches", "mkgnn_diverse_pick", "mkgnn_diverse_pick_workspace_bytes",
            "mkgnn_kernel_exemplars_update", "mkgnn_kernel_exemplars_workspace_bytes", "mkgnn_embed_knn_update",
-           "mkgnn_embed_knn_workspace_bytes", "mkgnn_embed_count_within", "mkgnn_embed_count_within_workspace_bytes")
+           "mkgnn_embed_knn_workspace_bytes", "mkgnn_embed_count_within", "mkgnn_embed_count_within_workspace_bytes",
+           "mkgnn_embed_neighbours_within", "mkgnn_embed_neighbours_within_workspace_bytes", "mkgnn_graph_components",
+           "mkgnn_graph_components_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -449,6 +460,17 @@ def load() -> C.CDLL:
     lib.mkgnn_embed_count_within_workspace_bytes.argtypes = [I64, I32]
     lib.mkgnn_embed_count_within.restype = C.c_int
     lib.mkgnn_embed_count_within.argtypes = [P, I64, I64, I32, P, I64, I32, F32, P, P, C.c_size_t, P]
+    # those references themselves, into a CSR: (emb, stride, n_rows, H, refs, stride, R, min_sim, row_ptr, capacity, nbr_ref, nbr_sim,
+    # found, workspace, bytes, stream)
+    lib.mkgnn_embed_neighbours_within_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_embed_neighbours_within_workspace_bytes.argtypes = [I64, I32]
+    lib.mkgnn_embed_neighbours_within.restype = C.c_int
+    lib.mkgnn_embed_neighbours_within.argtypes = [P, I64, I64, I32, P, I64, I32, F32, P, I64, P, P, P, P, C.c_size_t, P]
+    # connected components of CSR lists: (row_ptr, col, n, labels, state, resume, workspace, bytes, stream)
+    lib.mkgnn_graph_components_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_graph_components_workspace_bytes.argtypes = [I32]
+    lib.mkgnn_graph_components.restype = C.c_int
+    lib.mkgnn_graph_components.argtypes = [P, P, I32, P, P, I32, P, C.c_size_t, P]
     # stable compaction by a key: (scores, ids, key, B, n_valid, bounds, out_scores, out_ids, n_kept, stream)
     lib.mkgnn_select_rows.restype = C.c_int
     lib.mkgnn_select_rows.argtypes = [P, P, P, I32, P, P, P, P, P, P]

@@ -26,6 +26,13 @@
 // McFirstMax keeps the first maximum, McCountAbove counts the r with sim(i, r) > min_sim (strict; a NaN fails it) -- so norms_kernel,
 // the split, the staging and the tile loop exist once.  counts[i] is a sum of integers: one part writes it itself, more parts write
 // workspace[part][row] and count_combine_kernel adds them, in any order the same number.
+//
+// THE LISTS (mkgnn_embed_neighbours_within) are a third reduction over the same walk: McFillAbove writes every (r, sim(i, r)) the
+// count counts, in ascending r, into the row's segment of a CSR whose row pointers the caller made from the counts.  A part of a
+// split launch has to know how many pairs the parts before it hold, so a split call runs the COUNT walk into workspace[part][row]
+// first, fill_offsets_kernel turns every row's partials into exclusive offsets (and writes found[i], their sum), and the FILL walk
+// starts each part at its offset: one writer per slot, no atomics.  THE GUARD: a row writes only slots s with
+// 0 <= row_ptr[i] <= s < min(row_ptr[i + 1], capacity) -- whatever row_ptr holds; what does not fit is counted and dropped.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "kgnn_common.h"
@@ -79,7 +86,7 @@ struct McFirstMax {                                              // the first ma
     struct Out { float* sim; int32_t* arg; };
     float best;
     int arg;
-    __device__ __forceinline__ McFirstMax(const Out&, int r_begin)
+    __device__ __forceinline__ McFirstMax(const Out&, int r_begin, int64_t, int64_t, bool)
         : best(__int_as_float(0x7fc00000)), arg(r_begin) {}      // "nothing yet": any first value replaces it, a NaN leaves it
     __device__ __forceinline__ void take(float s, int r, bool) { // (a second look at the same reference: the strict order ignores it)
         const bool b = mc_better(s, best);
@@ -96,7 +103,7 @@ struct McCountAbove {                                            // how many ref
     struct Out { int32_t* count; float min_sim; };
     float bound;
     int count;
-    __device__ __forceinline__ McCountAbove(const Out& o, int) : bound(o.min_sim), count(0) {}
+    __device__ __forceinline__ McCountAbove(const Out& o, int, int64_t, int64_t, bool) : bound(o.min_sim), count(0) {}
     // The empty asm emits nothing; it makes each similarity opaque where it arrives.  Without it the two comparisons of a pair of
     // references are one two-wide operation to the compiler, which then packs EVERY step above them across the two references:
     // v_pk_mul_f32 / v_pk_add_f32 on operands that are not neighbours in registers -- 232 registers at 32 columns, 256 and spills
@@ -112,6 +119,48 @@ struct McCountAbove {                                            // how many ref
     __device__ __forceinline__ void store(const Out& o, int64_t at) const { o.count[at] = count; }
 };
 
+// The references above min_sim themselves, in the order the walk meets them (ascending r), into the row's segment of a CSR.
+// `room` is THE GUARD: the slots the row may write, counted from its first one -- row_ptr[row] plus what the earlier parts of a
+// split launch found -- up to min(row_ptr[row + 1], capacity); 0 where row_ptr[row] lies outside [0, capacity), where the segment
+// is empty or runs backwards, where the earlier parts have filled it, and for the lanes behind the last row.  A pair found behind
+// `room` is counted and not stored, so nothing row_ptr holds can make a store leave [row_ptr[row], min(row_ptr[row + 1], capacity)).
+// One part: store() writes found[row] (every pair, stored or not).  More: fill_offsets_kernel has written it.
+struct McFillAbove {
+    struct Out {
+        int32_t* ref; float* sim; int32_t* found;                // (found: null in a split launch)
+        const int64_t* row_ptr; const int32_t* offset;           // (offset [parts][n]: null in a launch of one part)
+        int64_t capacity; float min_sim;
+    };
+    float bound;
+    int count, room;
+    int32_t* ref;
+    float* sim;
+    __device__ __forceinline__ McFillAbove(const Out& o, int, int64_t row, int64_t at, bool row_live)
+        : bound(o.min_sim), count(0), room(0), ref(o.ref), sim(o.sim) {
+        if (!row_live) return;
+        const int64_t lo = o.row_ptr[row], hi = min(o.row_ptr[row + 1], o.capacity);
+        if (lo < 0 || lo >= hi) return;                          // (so 0 <= lo < hi <= capacity from here on)
+        const int64_t left = hi - lo - (o.offset ? (int64_t)max(o.offset[at], 0) : 0);
+        if (left <= 0) return;
+        room = (int)min(left, (int64_t)0x7fffffff);
+        ref += hi - left;                                        // the part's first slot: lo + offset
+        sim += hi - left;
+    }
+    // (no empty asm as in McCountAbove::take: the conditional stores already keep the two references of a pair apart -- 86 / 150
+    // registers at 32 / 64 columns with it and without, no spills, the same bits: DESIGN.md 4.5l)
+    __device__ __forceinline__ void take(float s, int r, bool live) {
+        const bool hit = live && s > bound;
+        if (hit && count < room) {
+            ref[count] = r;
+            sim[count] = s;
+        }
+        count += hit ? 1 : 0;
+    }
+    __device__ __forceinline__ void store(const Out& o, int64_t at) const {
+        if (o.found) o.found[at] = count;
+    }
+};
+
 template <int W, typename Red>
 __global__ void __launch_bounds__(MC_ROWS) max_cosine_kernel(const float* __restrict__ emb, int64_t es, int64_t n, int H,
                                                              const float* __restrict__ refs, int64_t rs, int R, int part_refs,
@@ -125,7 +174,7 @@ __global__ void __launch_bounds__(MC_ROWS) max_cosine_kernel(const float* __rest
     for (int j = 0; j < W; ++j) e[j] = j < H ? emb[ic * es + j] : 0.f;
     const float ie = inv[R + ic];
     const int r_begin = blockIdx.y * part_refs, r_end = min(R, r_begin + part_refs);
-    Red red(out, r_begin);
+    Red red(out, r_begin, ic, (int64_t)blockIdx.y * n + ic, i < n);       // (the row, its slot of a part's results, a real row)
     for (int r0 = r_begin; r0 < r_end; r0 += MC_TILE) {
         const int m = min(MC_TILE, r_end - r0);
         __syncthreads();                                         // (the previous tile has been walked by every wave)
@@ -187,6 +236,20 @@ __global__ void __launch_bounds__(256) count_combine_kernel(const int32_t* __res
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
     if (l == 0 && i < n) counts[i] = c;
+}
+
+// one thread per row: the parts' partial counts become exclusive offsets over the parts, in place; found[i] is their sum
+__global__ void __launch_bounds__(256) fill_offsets_kernel(int32_t* __restrict__ part_count, int64_t n, int parts,
+                                                           int32_t* __restrict__ found) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int before = 0;
+    for (int p = 0; p < parts; ++p) {
+        const int c = part_count[(int64_t)p * n + i];
+        part_count[(int64_t)p * n + i] = before;
+        before += c;
+    }
+    found[i] = before;
 }
 
 // mkgnn_select_rows: one workgroup; per pass of SEL_THREADS slots a ballot per wave, the waves' counts through LDS, the kept
@@ -330,6 +393,63 @@ extern "C" int mkgnn_embed_count_within(const float* emb, int64_t emb_stride, in
         max_cosine_kernel<64, McCountAbove><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, out);
     if (sp.parts > 1)
         count_combine_kernel<<<(unsigned)((n_rows + 7) / 8), 256, 0, st>>>(part_count, n_rows, sp.parts, counts);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+// the count's workspace: [inverse norms][parts x n partial counts, then offsets, when the references are split]
+extern "C" size_t mkgnn_embed_neighbours_within_workspace_bytes(int64_t n_rows, int32_t R) {
+    return mkgnn_embed_count_within_workspace_bytes(n_rows, R);
+}
+
+extern "C" int mkgnn_embed_neighbours_within(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* refs,
+                                             int64_t ref_stride, int32_t R, float min_sim, const int64_t* row_ptr, int64_t capacity,
+                                             int32_t* nbr_ref, float* nbr_sim, int32_t* found, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+    const char* who = "mkgnn_embed_neighbours_within";
+    if (R < 1 || R > MKGNN_MAX_COSINE_MAX_REFS)
+        return api_fail("%s: %d references outside [1, %d]", who, (int)R, MKGNN_MAX_COSINE_MAX_REFS);
+    if (H < 1 || H > MC_MAX_H) return api_fail("%s: embedding width %d outside [1, %d]", who, (int)H, MC_MAX_H);
+    if (n_rows < 0 || emb_stride < H || ref_stride < H) return api_fail("%s: bad shape", who);
+    if (capacity < 0 || capacity > ((int64_t)1 << 60)) return api_fail("%s: bad shape: a capacity of %lld slots", who, (long long)capacity);
+    if (!(min_sim - min_sim == 0.f)) return api_fail("%s: min_sim is not a finite threshold", who);
+    if (n_rows == 0) return 0;
+    if (!emb || !refs || !row_ptr || !found || !workspace || (capacity > 0 && (!nbr_ref || !nbr_sim)))
+        return api_fail("%s: null pointer", who);
+    if (!mc_sizes_ok(n_rows, R)) return api_fail("%s: %lld rows: at most 2^31 - 1 in one call", who, (long long)n_rows);
+    const size_t need = mkgnn_embed_neighbours_within_workspace_bytes(n_rows, R);
+    if (workspace_bytes < need)
+        return api_fail("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    if (((uintptr_t)workspace & 3) != 0) return api_fail("%s: workspace not 4-byte aligned", who);
+    // what the launches write -- the lists, found, the workspace -- must not overlap what they read, nor each other (refs may be emb)
+    const Span wr[4] = {{nbr_ref, (size_t)capacity * 4}, {nbr_sim, (size_t)capacity * 4}, {found, (size_t)n_rows * 4}, {workspace, need}};
+    const Span rd[3] = {{emb, ((size_t)(n_rows - 1) * (size_t)emb_stride + (size_t)H) * 4},
+                        {refs, ((size_t)(R - 1) * (size_t)ref_stride + (size_t)H) * 4},
+                        {row_ptr, ((size_t)n_rows + 1) * 8}};
+    if (spans_disjoint(who, wr, 4, rd, 3, "an output (nbr_ref, nbr_sim, found, workspace) aliases an input",
+                       "the outputs (nbr_ref, nbr_sim, found, workspace) alias each other"))
+        return 1;
+    const hipStream_t st = (hipStream_t)stream;
+    const McSplit sp = mc_split(n_rows, R);
+    const bool split = sp.parts > 1;
+    float* inv = (float*)workspace;
+    int32_t* part_count = (int32_t*)(inv + mc_norm_floats(n_rows, R));
+    const int64_t vectors = (int64_t)R + n_rows;
+    norms_kernel<<<(unsigned)((vectors + 7) / 8), 256, 0, st>>>(refs, ref_stride, R, emb, emb_stride, n_rows, H, inv);
+    const dim3 grid((unsigned)((n_rows + MC_ROWS - 1) / MC_ROWS), (unsigned)sp.parts);
+    if (split) {                                                 // the parts' counts, then every part's first slot, and found
+        const McCountAbove::Out cnt = {part_count, min_sim};
+        if (H <= 32)
+            max_cosine_kernel<32, McCountAbove><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, cnt);
+        else
+            max_cosine_kernel<64, McCountAbove><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, cnt);
+        fill_offsets_kernel<<<(unsigned)((n_rows + 255) / 256), 256, 0, st>>>(part_count, n_rows, sp.parts, found);
+    }
+    const McFillAbove::Out out = {nbr_ref, nbr_sim, split ? nullptr : found, row_ptr, split ? part_count : nullptr, capacity, min_sim};
+    if (H <= 32)
+        max_cosine_kernel<32, McFillAbove><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, out);
+    else
+        max_cosine_kernel<64, McFillAbove><<<grid, MC_ROWS, 0, st>>>(emb, emb_stride, n_rows, H, refs, ref_stride, R, sp.part_refs, inv, out);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }

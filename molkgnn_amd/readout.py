@@ -1095,6 +1095,213 @@ def embedding_count_within(emb: torch.Tensor, refs: torch.Tensor, min_sim: float
     return out
 
 
+def embedding_neighbours_within_supported(R: int, H: int) -> bool:
+    """The shapes ``mkgnn_embed_neighbours_within`` takes; anything else goes through torch operators on the GPU."""
+    return 1 <= R <= _lib.MAX_COSINE_MAX_REFS and 1 <= H <= _lib.MAX_COSINE_MAX_H
+
+
+def _neighbours_by_torch(emb, refs, min_sim: float, counts: torch.Tensor):
+    """``(nbr int32 [nnz], nbr_sim float32 [nnz])`` of the torch route, rows ascending and references ascending inside a row: the
+    similarities of ``embedding_count_within``'s torch route, chunk by chunk, ``nonzero`` of the comparison, then the chunks'
+    pairs brought into row order by one stable sort."""
+    dev = emb.device
+    e, eps = emb.double(), float(torch.tensor(COSINE_EPS, dtype=torch.float32))
+    ie = 1.0 / e.square().sum(dim=1).sqrt().clamp_min(eps)
+    bound = torch.tensor(min_sim, dtype=torch.float32, device=dev)
+    rows, cols, sims = [], [], []
+    for a in range(0, refs.shape[0], MAX_COSINE_TORCH_CHUNK):
+        q = refs[a:a + MAX_COSINE_TORCH_CHUNK].double()
+        iq = 1.0 / q.square().sum(dim=1).sqrt().clamp_min(eps)
+        sim = ((e @ q.t() + 0.0) * ie[:, None] * iq[None, :]).float()
+        hit = (sim > bound).nonzero()                            # (row-major: by row, then by reference)
+        rows.append(hit[:, 0])
+        cols.append(hit[:, 1] + a)
+        sims.append(sim[hit[:, 0], hit[:, 1]])
+    rows, cols, sims = torch.cat(rows), torch.cat(cols), torch.cat(sims)
+    order = torch.sort(rows, stable=True).indices                # (the chunks come in reference order: stable keeps it inside a row)
+    if not torch.equal(torch.bincount(rows, minlength=counts.numel()), counts.long()):
+        raise RuntimeError("embedding_neighbours_within: the torch route's lists and counts disagree")
+    return cols[order].to(torch.int32), sims[order]
+
+
+def embedding_neighbours_within(emb: torch.Tensor, refs: torch.Tensor, min_sim: float, max_pairs: int = 1 << 28,
+                                n_rows: Optional[int] = None, row_ptr: Optional[torch.Tensor] = None, out=None,
+                                found: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """``(row_ptr int64 [n_rows + 1], nbr int32 [nnz], nbr_sim float32 [nnz])``: WHICH rows ``r`` of a float32 CUDA ``refs [R, H]``
+    ``embedding_count_within`` counts for each of the leading ``n_rows`` rows of a float32 CUDA ``emb [n, H]`` -- those with ``S[i, r] >
+    min_sim``, strict, a NaN never -- as CSR lists: row ``i`` owns the slots ``row_ptr[i] .. row_ptr[i + 1]``, ``nbr`` holds its
+    references in ASCENDING ``r`` and ``nbr_sim`` their similarities, the bits of ``embedding_cosine`` (``screening.neighbours_reference``
+    is the definition over a given matrix).  There is no "self": with ``refs`` the tensor ``emb`` itself the diagonal is a pair like any
+    other.  No ``[n, R]`` matrix exists.
+
+    Without ``row_ptr``: ``embedding_count_within``, a ``cumsum``, ONE host read (``nnz``, to allocate the lists), then one
+    ``mkgnn_embed_neighbours_within``; ``nnz > max_pairs`` raises ``ValueError`` naming it before anything of that size is allocated;
+    that the fill found what the count counted is asserted on the device.  ``nnz == 0`` gives empty lists.
+
+    With ``row_ptr`` (int64 ``[n_rows + 1]`` on the device) the raw form, which reads nothing back and can be captured: ``out`` is the
+    pair ``(int32 [capacity], float32 [capacity])`` to write into and ``found`` an int32 ``[n_rows]`` tensor that receives every row's
+    number of pairs, written or not; a row writes only inside ``[row_ptr[i], min(row_ptr[i + 1], capacity))`` whatever ``row_ptr``
+    holds, and pairs that do not fit are counted in ``found`` and dropped.  ``workspace``: as for the count
+    (``mkgnn_embed_neighbours_within_workspace_bytes``).  Returns ``(row_ptr, out[0], out[1])``.
+
+    More than 2^20 references or an embedding wider than 64 (``embedding_neighbours_within_supported``): the same definition through
+    torch operators, ``MAX_COSINE_TORCH_CHUNK`` references at a time (float64 products, rounded once: inside
+    ``screening.cosine_bound``, not the kernel's bits); that route has no raw form.  It has no autograd node: called where a gradient
+    is being recorded for one of its inputs it raises instead of dropping it."""
+    who = "embedding_neighbours_within"
+    if not (torch.is_tensor(emb) and torch.is_tensor(refs)) or emb.dim() != 2 or refs.dim() != 2 \
+            or emb.dtype != torch.float32 or refs.dtype != torch.float32 or refs.shape[1] != emb.shape[1]:
+        raise ValueError(f"{who} needs a float32 [n, H] embedding and float32 [R, H] references")
+    R, H = refs.shape
+    if R < 1 or H < 1:
+        raise ValueError(f"{who} needs at least one reference and one column, not {R} x {H}")
+    min_sim = float(min_sim)
+    if min_sim != min_sim or min_sim in (float("inf"), float("-inf")):
+        raise ValueError(f"{who}: min_sim = {min_sim} is not a finite threshold")
+    max_pairs = int(max_pairs)
+    if max_pairs < 0:
+        raise ValueError(f"{who}: max_pairs = {max_pairs} is negative")
+    if torch.is_grad_enabled() and (emb.requires_grad or refs.requires_grad):
+        raise RuntimeError(f"{who} is forward only: call it under torch.no_grad() (or on detached inputs)")
+    if row_ptr is None and (out is not None or found is not None):
+        raise ValueError(f"{who}: out and found belong to the raw form, which takes row_ptr")
+    if not emb.is_cuda or refs.device != emb.device:
+        raise ValueError(f"{who} runs on the GPU: emb is on {emb.device}, refs on {refs.device} (there is no CPU path; "
+                         "screening.neighbours_reference is the host form)")
+    n = emb.shape[0] if n_rows is None else int(n_rows)
+    if not 0 <= n <= emb.shape[0]:
+        raise ValueError(f"n_rows = {n_rows} outside [0, {emb.shape[0]}]")
+    dev = emb.device
+    raw = row_ptr is not None
+    if raw:
+        if not torch.is_tensor(row_ptr) or row_ptr.dtype != torch.int64 or row_ptr.device != dev or tuple(row_ptr.shape) != (n + 1,) \
+                or not row_ptr.is_contiguous():
+            raise ValueError(f"row_ptr: a contiguous int64 [{n + 1}] tensor on {dev}")
+        ok = isinstance(out, (tuple, list)) and len(out) == 2 and all(torch.is_tensor(o) for o in out)
+        if not ok or out[0].dtype != torch.int32 or out[1].dtype != torch.float32 or out[0].dim() != 1 \
+                or any(o.device != dev or o.shape != out[0].shape or not o.is_contiguous() for o in out):
+            raise ValueError(f"out: a pair of contiguous tensors (int32 [capacity], float32 [capacity]) on {dev}")
+        if not torch.is_tensor(found) or found.dtype != torch.int32 or found.device != dev or tuple(found.shape) != (n,) \
+                or not found.is_contiguous():
+            raise ValueError(f"found: a contiguous int32 [{n}] tensor on {dev}")
+        if not embedding_neighbours_within_supported(R, H):
+            raise ValueError(f"{who}: the raw form needs a shape the kernel takes (at most {_lib.MAX_COSINE_MAX_REFS} references "
+                             f"of at most {_lib.MAX_COSINE_MAX_H} columns), not {R} x {H}")
+        nbr, nbr_sim = out
+        if n == 0:
+            return row_ptr, nbr, nbr_sim
+    else:
+        counts = embedding_count_within(emb, refs, min_sim, n_rows=n, workspace=workspace)
+        row_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        row_ptr[1:] = torch.cumsum(counts, dim=0, dtype=torch.int64)
+        nnz = int(row_ptr[n])                                    # the one host read: the size of the lists
+        if nnz > max_pairs:
+            raise ValueError(f"{who}: nnz = {nnz} pairs lie above min_sim = {min_sim}, more than max_pairs = {max_pairs}")
+        if nnz == 0:
+            return row_ptr, torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+        if not embedding_neighbours_within_supported(R, H):
+            nbr, nbr_sim = _neighbours_by_torch(emb[:n].detach(), refs.detach(), min_sim, counts)
+            return row_ptr, nbr, nbr_sim
+        nbr = torch.empty(nnz, dtype=torch.int32, device=dev)
+        nbr_sim = torch.empty(nnz, dtype=torch.float32, device=dev)
+        found = torch.empty(n, dtype=torch.int32, device=dev)
+    emb, refs = _row_major(emb.detach()), _row_major(refs.detach())
+    lib = _lib.load()
+    ws = _max_cosine_workspace(dev, int(lib.mkgnn_embed_neighbours_within_workspace_bytes(n, R)), workspace)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkgnn_embed_neighbours_within(emb.data_ptr(), _stride0(emb), n, H, refs.data_ptr(), _stride0(refs), R, min_sim,
+                                                     row_ptr.data_ptr(), nbr.numel(), _lib.ptr(nbr), _lib.ptr(nbr_sim),
+                                                     found.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
+                   "mkgnn_embed_neighbours_within")
+    if not raw:
+        torch._assert_async((found == counts).all())             # (on the device: the fill found what the count counted)
+    return row_ptr, nbr, nbr_sim
+
+
+_COMPONENTS_WS: dict = {}
+
+
+def graph_components(row_ptr: torch.Tensor, col: torch.Tensor, n: int, return_rounds: bool = False, out: Optional[torch.Tensor] = None,
+                     state: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, resume: bool = False,
+                     _max_rounds: Optional[int] = None):
+    """``labels int32 [n]``: for every vertex the smallest vertex of its connected component, in the graph where ``u`` and ``v`` are
+    linked if the CSR lists ``(row_ptr int64 [n + 1], col int32 [row_ptr[n]])`` on the GPU hold ``v`` in ``u``'s segment OR ``u`` in
+    ``v``'s (``mkgnn_graph_components``; ``screening.components_reference`` is the definition) -- the single-linkage clusters of a
+    threshold when the lists are ``embedding_neighbours_within``'s self-join.  Self-loops and duplicate edges are harmless.  One
+    call enqueues ``_lib.components_rounds(n)`` hook-and-compress rounds without a host round trip; this function then reads the
+    operator's ``state`` ONCE, goes on with ``resume = 1`` while it says "not converged" (every such call lowers a label or
+    converges), and raises ``ValueError`` if a column outside ``[0, n)`` or a segment outside ``0 <= row_ptr[v] <= row_ptr[v + 1] <=
+    row_ptr[n]`` was met (they are skipped, never used as an index); before the launch it reads ``row_ptr[n]`` and refuses lists
+    longer than ``col``.  ``return_rounds=True``: ``(labels, rounds)``, the rounds that changed a label.
+
+    ``state`` (an int32 ``[4]`` device tensor) selects the raw form, which reads nothing back and can be captured: ONE call, after
+    which ``state`` holds (changing rounds, converged, skipped input, 0) for the caller to look at, and ``col`` must hold
+    ``row_ptr[n]`` entries.  ``out``: a contiguous int32 ``[n]`` tensor for the labels.  ``resume=True`` (with ``out``): go on from the
+    labels an earlier call on the same graph left in ``out`` -- what the raw form's caller does while ``state[1] == 0``.
+    ``workspace``: an int32 device tensor of at least ``mkgnn_graph_components_workspace_bytes(n)`` bytes.  ``_max_rounds`` is for the
+    tests: fewer rounds per call."""
+    who = "graph_components"
+    n = int(n)
+    if not 0 <= n <= _lib.COMPONENTS_MAX_VERTICES:
+        raise ValueError(f"{who}: n = {n} outside [0, {_lib.COMPONENTS_MAX_VERTICES}]")
+    if not (torch.is_tensor(row_ptr) and torch.is_tensor(col)) or row_ptr.dtype != torch.int64 or col.dtype != torch.int32 \
+            or tuple(row_ptr.shape) != (n + 1,) or col.dim() != 1 or not row_ptr.is_contiguous() or not col.is_contiguous():
+        raise ValueError(f"{who} needs a contiguous int64 [{n + 1}] row_ptr and a contiguous int32 [nnz] col")
+    dev = row_ptr.device
+    if dev.type != "cuda" or col.device != dev:
+        raise ValueError(f"{who} runs on the GPU: row_ptr is on {dev}, col on {col.device} (there is no CPU path; "
+                         "screening.components_reference is the host form)")
+    if out is None:
+        if resume:
+            raise ValueError(f"{who}: resume=True goes on from the labels in out, which was not given")
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.int32 or out.device != dev or tuple(out.shape) != (n,) or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous int32 [{n}] tensor on {dev}")
+    raw = state is not None
+    if raw and (not torch.is_tensor(state) or state.dtype != torch.int32 or state.device != dev or tuple(state.shape) != (4,)
+                or not state.is_contiguous()):
+        raise ValueError(f"state: a contiguous int32 [4] tensor on {dev}")
+    cap = 0 if _max_rounds is None else int(_max_rounds)
+    if not 0 <= cap <= 63:
+        raise ValueError(f"{who}: _max_rounds = {_max_rounds} outside [1, 63]")
+    lib = _lib.load()
+    need = int(lib.mkgnn_graph_components_workspace_bytes(n))
+    if workspace is not None:
+        if not torch.is_tensor(workspace) or workspace.dtype != torch.int32 or workspace.device != dev \
+                or not workspace.is_contiguous() or 4 * workspace.numel() < need:
+            raise ValueError(f"workspace: a contiguous int32 tensor of at least {need} bytes on {dev}")
+    elif torch.cuda.is_current_stream_capturing():
+        workspace = torch.empty(need // 4, dtype=torch.int32, device=dev)
+    else:
+        workspace = _COMPONENTS_WS.get(str(dev))
+        if workspace is None or 4 * workspace.numel() < need:
+            workspace = _COMPONENTS_WS[str(dev)] = torch.empty(max(need // 4, 1 << 14), dtype=torch.int32, device=dev)
+    if not raw:
+        nnz = int(row_ptr[n])                                    # (the operator takes col's length from row_ptr[n]: checked here)
+        if not 0 <= nnz <= col.numel():
+            raise ValueError(f"{who}: row_ptr[n] = {nnz} outside [0, {col.numel()}], the length of col")
+        state = torch.empty(4, dtype=torch.int32, device=dev)
+
+    def call(resume: int) -> None:
+        with torch.cuda.device(dev):
+            _lib.check(lib.mkgnn_graph_components(row_ptr.data_ptr(), _lib.ptr(col), n, _lib.ptr(out), state.data_ptr(),
+                                                  resume | (cap << 8), workspace.data_ptr(), 4 * workspace.numel(),
+                                                  _lib.stream_ptr(dev)), "mkgnn_graph_components")
+
+    call(1 if resume else 0)
+    if raw:
+        return (out, None) if return_rounds else out
+    rounds, converged, skipped, _ = state.tolist()
+    while not converged and not skipped:
+        call(1)
+        more, converged, skipped, _ = state.tolist()
+        rounds += more
+    if skipped:
+        raise ValueError(f"{who}: the lists hold a column outside [0, {n}) or a segment outside 0 <= row_ptr[v] <= row_ptr[v + 1] "
+                         "<= row_ptr[n]; they were skipped and the labels are not the components")
+    return (out, rounds) if return_rounds else out
+
+
 def select_rows(scores: torch.Tensor, ids: torch.Tensor, key: torch.Tensor, n_valid, bounds: torch.Tensor, out=None):
     """``(out_scores float32 [B], out_ids int32 [B], n_kept int32 [1])``: the stable compaction ``mkgnn_select_rows`` -- the slots
     ``i < min(max(n_valid, 0), B)`` with ``bounds[0] <= key[i] <= bounds[1]`` (a NaN key is never kept), in order, at the head of the

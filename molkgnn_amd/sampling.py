@@ -35,10 +35,14 @@ def oversampling_sampler(labels: torch.Tensor, seed: int) -> WeightedRandomSampl
 
 def cluster_split(leader, fractions=(0.8, 0.1, 0.1), seed: int = 0) -> torch.Tensor:
     """A cluster-based split: the fold (``0 .. len(fractions) - 1``; train / validation / test for the default) of every row, int64
-    ``[n]`` on the device of ``leader``, with WHOLE clusters per fold -- so near-copies of a training molecule do not sit in the test
-    set, which the reference's random split does not prevent.  ``leader`` is an integer ``[n]`` tensor naming every row's cluster, as
-    ``screening.cluster_butina_embeddings`` (or ``pick_diverse_embeddings``) returns it: rows with the same value ``>= 0`` form one
-    cluster, and a row with ``-1`` is a cluster of its own.  The clusters are taken in an order drawn from a ``torch.Generator``
+    ``[n]`` on the device of ``leader``, with WHOLE clusters per fold -- so the members of a cluster are not spread over training and
+    test set, which the reference's random split does not prevent.  What that is worth depends on the clusters.  "No pair above the
+    threshold across folds" holds for the labels of ``screening.cluster_components_embeddings`` (``["component"]``: the connected
+    components of the threshold graph, the only partition that carries it) and does NOT hold for Butina's or the leader walk's: a
+    row joins the FIRST centroid above the threshold, so rows of different clusters can be closer than it.
+    ``screening.split_leakage`` counts the pairs a split lets through.  ``leader`` is an integer ``[n]`` tensor naming every row's
+    cluster, as ``screening.cluster_components_embeddings``, ``cluster_butina_embeddings`` or ``pick_diverse_embeddings`` return it:
+    rows with the same value ``>= 0`` form one cluster, and a row with ``-1`` is a cluster of its own.  The clusters are taken in an order drawn from a ``torch.Generator``
     seeded with ``seed`` (over the clusters by ascending name, the ``-1`` rows behind them in row order), and each goes to the fold
     furthest below its target count ``fractions[f] / sum(fractions) * n`` at that moment, ties to the lower fold.  A fold below its
     target exists while rows remain, so no fold is filled beyond its target by more than one cluster, and none ends further below

@@ -58,6 +58,14 @@ and the clustering that ranks by that count and then does the leader walk (``mkg
 ``neighbour_counts``                     stored embeddings against any number of references: analogue counts
 ``cluster_butina_embeddings``            stored embeddings -> centroids, every row's cluster, the best-scoring member of each
 
+Neighbour lists and linked components -- which molecules lie above the threshold (``mkgnn_embed_neighbours_within``), and the
+connected components of that graph (``mkgnn_graph_components``), the one partition with no pair above it across its parts:
+
+``neighbours_reference`` / ``components_reference``  the two definitions on the host
+``neighbour_lists``                      stored embeddings against up to 2^20 references: the analogues of every row, as CSR lists
+``cluster_components_embeddings``        stored embeddings -> every row's component, their sizes, the lists, the best member of each
+``split_leakage``                        stored pairs by (fold of the row, fold of the reference): what a split lets through
+
 What each kernel learned -- for every kernel column of a convolution layer the ``k`` atoms of the library it matches best
 (``GNNModel.kernel_scores``, ``mkgnn_kernel_exemplars_update``; one running list per column, a candidate is an atom):
 
@@ -1459,6 +1467,205 @@ def cluster_butina_embeddings(emb: torch.Tensor, min_sim: float, k: Optional[int
         result["cluster_best"] = best if ids is None else ids.long()[best]
         result["cluster_best_score"] = scores[best]
     return result
+
+
+# ------------------------------------------------------------------- neighbour lists, linked components, leakage --
+# WHICH molecules lie above the threshold (``mkgnn_embed_neighbours_within``: the analogues themselves, and the threshold graph),
+# and that graph's connected components (``mkgnn_graph_components``): the single-linkage clusters, the ONLY partition -- and the
+# finest -- with no pair above the threshold across its parts.  A Butina row joins the first centroid above the threshold, so
+# rows of different Butina clusters can be closer than it; ``split_leakage`` counts such pairs for any split.
+#
+# ``neighbours_reference`` / ``components_reference``  the definitions on the host
+# ``neighbour_lists``                  stored embeddings against up to 2^20 references: the analogues of every row
+# ``cluster_components_embeddings``    stored embeddings -> every row's component, sizes, the self-join's lists, the best of each
+# ``split_leakage``                    stored pairs by (fold of the row, fold of the reference)
+NEIGHBOUR_MAX_PAIRS = 1 << 28                  # the default cap on the pairs of one list: 2 GiB of (reference, similarity)
+
+
+def neighbours_reference(sim, min_sim):
+    """The definition of ``mkgnn_embed_neighbours_within`` (include/molkgnn_hip.h), on the host, over a GIVEN similarity matrix ``sim
+    [n, R]`` (float32 or float64): ``(row_ptr int64 [n + 1], nbr int32 [nnz], nbr_sim [nnz])`` -- row ``i`` owns the slots ``row_ptr[i]
+    .. row_ptr[i + 1]``, which hold the ``r`` with ``sim[i, r] > min_sim`` in ascending ``r`` and those elements of ``sim``.  Strict; a
+    NaN never qualifies; the comparison is made in ``sim``'s own dtype (``min_sim`` is rounded to it first), as in
+    ``count_within_reference``, whose counts are ``diff(row_ptr)``."""
+    if torch.is_tensor(sim):
+        sim = sim.detach().cpu().numpy()
+    sim = np.asarray(sim)
+    if sim.ndim != 2 or sim.dtype not in (np.float32, np.float64):
+        raise ValueError("a float32 or float64 [n, R] similarity matrix is needed")
+    bound = sim.dtype.type(min_sim)
+    if not np.isfinite(bound):
+        raise ValueError(f"min_sim = {min_sim} is not a finite similarity threshold")
+    with np.errstate(invalid="ignore"):
+        above = sim > bound
+    row_ptr = np.zeros(sim.shape[0] + 1, dtype=np.int64)
+    np.cumsum(above.sum(axis=1), out=row_ptr[1:])
+    rows, cols = np.nonzero(above)                               # (row-major: by row, then by ascending reference)
+    return row_ptr, cols.astype(np.int32), sim[rows, cols]
+
+
+def components_reference(row_ptr, col, n) -> np.ndarray:
+    """The definition of ``mkgnn_graph_components``, on the host: int32 ``[n]``, for every vertex the smallest vertex of its component
+    in the graph where ``u`` and ``v`` are linked if ``col`` holds ``v`` in ``u``'s segment ``row_ptr[u] .. row_ptr[u + 1]`` or ``u`` in
+    ``v``'s.  A plain union-find, the smaller root kept.  A column outside ``[0, n)`` or a segment outside ``0 <= row_ptr[v] <=
+    row_ptr[v + 1] <= len(col)``: ``ValueError``."""
+    n = int(n)
+    row_ptr, col = _host(row_ptr, np.int64).reshape(-1), _host(col, np.int64).reshape(-1)
+    if n < 0 or row_ptr.shape[0] != n + 1:
+        raise ValueError(f"row_ptr holds n + 1 = {n + 1} entries")
+    parent = list(range(n))
+
+    def root(v):
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        return v
+
+    for u in range(n):
+        a, b = int(row_ptr[u]), int(row_ptr[u + 1])
+        if not 0 <= a <= b <= col.shape[0]:
+            raise ValueError(f"the segment of vertex {u}, [{a}, {b}), is not one of col [{col.shape[0]}]")
+        for v in col[a:b].tolist():
+            if not 0 <= v < n:
+                raise ValueError(f"col holds {v}, outside [0, {n})")
+            ru, rv = root(u), root(v)
+            if ru != rv:
+                parent[max(ru, rv)] = min(ru, rv)
+    return np.array([root(v) for v in range(n)], dtype=np.int32)
+
+
+def _check_max_pairs(who: str, max_pairs) -> int:
+    if isinstance(max_pairs, bool) or not isinstance(max_pairs, int) or max_pairs < 0:
+        raise ValueError(f"{who}: max_pairs = {max_pairs!r} is not a count of pairs (an int >= 0)")
+    return max_pairs
+
+
+def neighbour_lists(emb: torch.Tensor, refs: torch.Tensor, min_sim: float, max_pairs: int = NEIGHBOUR_MAX_PAIRS):
+    """The stored-embedding route to the analogues themselves ("SAR by catalogue" ends with them): ``(row_ptr int64 [n + 1], nbr int32
+    [nnz], nbr_sim float32 [nnz])`` -- for every row of ``emb`` (float32 ``[n, G]`` on the GPU) the rows of ``refs`` (float32 ``[R, G]``
+    on the same device, ``1 <= R <= 2^20``) whose cosine similarity to it lies above ``min_sim``, in ascending ``r``, with those
+    similarities: the pairs ``neighbour_counts`` counts, by ``readout.embedding_neighbours_within``'s definition and bits
+    (``neighbours_reference`` is the host form).  Strict, a NaN never qualifies, no "self".  No ``[n, R]`` matrix exists; one host read
+    (``nnz``, to allocate the lists); more than ``max_pairs`` pairs raise ``ValueError`` naming the number, before the lists are
+    allocated.  A wrong shape, dtype or device, a NaN or infinite ``min_sim``, a bad ``max_pairs``: ``ValueError`` before a launch."""
+    who = "neighbour_lists"
+    _check_embeddings(who, emb)
+    _check_embeddings(who, refs, "refs")
+    if refs.shape[1] != emb.shape[1] or not 1 <= refs.shape[0] <= NEIGHBOUR_SLICE:
+        raise ValueError(f"{who}: refs holds 1 to {NEIGHBOUR_SLICE} rows as wide as emb ({emb.shape[1]}), not {tuple(refs.shape)}")
+    min_sim = _check_max_sim(who, min_sim)
+    max_pairs = _check_max_pairs(who, max_pairs)
+    dev = emb.device
+    if dev.type != "cuda" or refs.device != dev:
+        raise ValueError(f"{who}: emb is on {dev}, refs on {refs.device}; the lists are made on the GPU, with both on the same device "
+                         "(there is no CPU path; neighbours_reference is the host form)")
+    from .readout import embedding_neighbours_within
+    return embedding_neighbours_within(emb.detach(), refs.detach(), min_sim, max_pairs=max_pairs)
+
+
+def cluster_components_embeddings(emb: torch.Tensor, min_sim: float, scores: Optional[torch.Tensor] = None,
+                                  ids: Optional[torch.Tensor] = None, max_pairs: int = NEIGHBOUR_MAX_PAIRS) -> dict:
+    """The connected components of the threshold graph -- single-linkage clusters at ``min_sim`` -- of ANY set of molecules whose
+    embeddings are kept, up to 2^20 rows, WITHOUT running the network: ``emb`` float32 ``[n, G]`` on the GPU.  The self-join's lists
+    (``readout.embedding_neighbours_within(emb, emb, min_sim)``, the diagonal included, as the count defines it) are the graph, and
+    ``readout.graph_components`` labels it; rows ``i`` and ``j`` are linked if ``S[i, j] > min_sim`` OR ``S[j, i] > min_sim`` (the two
+    differ in their last bit at most).  This is the one partition that guarantees NO PAIR ABOVE ``min_sim`` ACROSS ITS PARTS, and the
+    finest: what ``sampling.cluster_split`` needs for a leakage-free split, which Butina clusters do not give (``split_leakage``
+    measures it).  A chain of neighbours is one component however long it is.  A NaN row has no neighbours, not even itself, and is a
+    component of its own.  Returns a dict in terms of the caller's rows -- ``ids[row]`` when ``ids`` (an integer ``[n]`` tensor on the
+    GPU) is given, the row numbers otherwise:
+
+    ``component``        ``[n]`` int64, by the caller's row: the name of its component -- its smallest row
+    ``components``       ``[n_components]`` int64: those names, in the order of ascending smallest row
+    ``n_components``     their number
+    ``component_size``   ``[n_components]`` int64: the rows of every component, in that order
+    ``neighbour_count``  ``[n]`` int64: the rows above ``min_sim`` of every row, itself included
+    ``row_ptr``, ``neighbour``, ``neighbour_sim``   the self-join's lists (int64 ``[n + 1]``, int32 ``[nnz]`` of ROW numbers, float32 ``[nnz]``)
+
+    and, when ``scores`` (float32 ``[n]`` on the GPU) is given, under ``cluster_butina_embeddings``' ``cluster_best`` rule:
+
+    ``component_best``        ``[n_components]`` int64: the member of every component that comes first in ``rank_order(scores)``
+    ``component_best_score``  ``[n_components]`` float32: its score
+
+    Host reads: the size of the lists, the components' state, their number.  More than ``max_pairs`` pairs: ``ValueError`` naming the
+    number.  A wrong shape, dtype or device, a NaN or infinite ``min_sim``, ``n`` outside ``[1, 2^20]``: ``ValueError`` before a
+    launch."""
+    who = "cluster_components_embeddings"
+    _check_embeddings(who, emb)
+    n = int(emb.shape[0])
+    if not 1 <= n <= BUTINA_MAX_ROWS:
+        raise ValueError(f"{who}: {n} rows outside [1, {BUTINA_MAX_ROWS}]")
+    min_sim = _check_max_sim(who, min_sim)
+    max_pairs = _check_max_pairs(who, max_pairs)
+    if scores is not None and (not torch.is_tensor(scores) or scores.dtype != torch.float32 or tuple(scores.shape) != (n,)):
+        raise ValueError(f"{who}: scores is a float32 [{n}] tensor, one score per row of emb")
+    integer = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+    if ids is not None and (not torch.is_tensor(ids) or ids.dtype not in integer or tuple(ids.shape) != (n,)):
+        raise ValueError(f"{who}: ids is an integer [{n}] tensor")
+    dev = emb.device
+    if dev.type != "cuda" or (scores is not None and scores.device != dev) or (ids is not None and ids.device != dev):
+        raise ValueError(f"{who}: emb is on {dev}; the components are found on the GPU, with scores and ids on the same device "
+                         "(there is no CPU path; neighbours_reference and components_reference are the host forms)")
+    from .readout import embedding_neighbours_within, graph_components
+    emb = emb.detach()
+    row_ptr, nbr, nbr_sim = embedding_neighbours_within(emb, emb, min_sim, max_pairs=max_pairs)
+    label = graph_components(row_ptr, nbr, n).long()             # every row's component: its smallest row
+    sizes_by_row = torch.bincount(label, minlength=n)
+    roots = torch.nonzero(sizes_by_row, as_tuple=True)[0]        # ascending (a host read: their number)
+    name = torch.arange(n, device=dev) if ids is None else ids.long()
+    result = {"component": name[label], "components": name[roots], "n_components": int(roots.numel()),
+              "component_size": sizes_by_row[roots], "neighbour_count": row_ptr[1:] - row_ptr[:-1], "row_ptr": row_ptr,
+              "neighbour": nbr, "neighbour_sim": nbr_sim}
+    if scores is not None:
+        scores = scores.detach()
+        ranked = rank_order(scores)
+        place = torch.empty_like(ranked)
+        place[ranked] = torch.arange(n, device=dev)              # row -> its place in the ranking
+        first = torch.full((n,), n, dtype=torch.int64, device=dev)
+        first.scatter_reduce_(0, label, place, reduce="amin")    # smallest row of a component -> its members' best place
+        best = ranked[first[roots]]
+        result["component_best"] = name[best]
+        result["component_best_score"] = scores[best]
+    return result
+
+
+def split_leakage(row_ptr: torch.Tensor, neighbour: torch.Tensor, folds: torch.Tensor,
+                  ref_folds: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """How many stored pairs cross a split: int64 ``[F, F]`` on the lists' device, entry ``[a, b]`` the number of pairs ``(i, r)`` of the
+    CSR lists ``(row_ptr [n + 1], neighbour [nnz])`` -- ``neighbour_lists`` or ``cluster_components_embeddings`` made them -- with
+    ``folds[i] == a`` and ``ref_folds[r] == b``; ``F`` is one more than the largest fold named.  ``folds`` is an integer ``[n]`` tensor
+    of values ``>= 0`` (``sampling.cluster_split`` returns one), ``ref_folds`` one per reference, or ``None`` for a self-join, where the
+    references are the rows.  The matrix's total is ``nnz``; its OFF-DIAGONAL sum is the leakage, the ordered pairs above the
+    threshold whose two ends lie in different folds: 0 for a split over ``cluster_components_embeddings``' components, not for one
+    over Butina clusters.  With ``refs`` a test set and ``folds`` all zero but for the rows of interest it answers "how many training
+    molecules have a test neighbour" the same way.  Torch operators only, on whatever device the tensors share; the checks of the
+    lists and ``F`` are read on the host.  Lists that are not a CSR, a reference outside ``ref_folds``, a negative fold:
+    ``ValueError``."""
+    who = "split_leakage"
+    integer = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+    if not all(torch.is_tensor(t) and t.dim() == 1 and t.dtype in integer for t in (row_ptr, neighbour, folds)) \
+            or row_ptr.numel() != folds.numel() + 1:
+        raise ValueError(f"{who}: row_ptr [n + 1], neighbour [nnz] and folds [n] are integer tensors")
+    if ref_folds is None:
+        ref_folds = folds
+    elif not torch.is_tensor(ref_folds) or ref_folds.dim() != 1 or ref_folds.dtype not in integer:
+        raise ValueError(f"{who}: ref_folds is an integer [R] tensor")
+    dev = row_ptr.device
+    if any(t.device != dev for t in (neighbour, folds, ref_folds)):
+        raise ValueError(f"{who}: row_ptr, neighbour, folds and ref_folds lie on one device")
+    n = folds.numel()
+    row_ptr, nbr, folds, ref_folds = row_ptr.long(), neighbour.long(), folds.long(), ref_folds.long()
+    lengths = row_ptr[1:] - row_ptr[:-1]
+    bad_lists = n and (int(row_ptr[0]) != 0 or int(lengths.min()) < 0 or int(row_ptr[n]) != nbr.numel())
+    if bad_lists or (n == 0 and nbr.numel()):
+        raise ValueError(f"{who}: row_ptr is not the row pointers of neighbour [{nbr.numel()}]")
+    if nbr.numel() and (int(nbr.min()) < 0 or int(nbr.max()) >= ref_folds.numel()):
+        raise ValueError(f"{who}: neighbour names a reference outside [0, {ref_folds.numel()})")
+    if (n and int(folds.min()) < 0) or (ref_folds.numel() and int(ref_folds.min()) < 0):
+        raise ValueError(f"{who}: a fold is negative")
+    F = int(max(folds.max() if n else 0, ref_folds.max() if ref_folds.numel() else 0)) + 1
+    row = torch.repeat_interleave(torch.arange(n, device=dev), lengths)
+    return torch.bincount(folds[row] * F + ref_folds[nbr], minlength=F * F).view(F, F)
 
 
 # ------------------------------------------------------------------------------------- what each kernel learned --
