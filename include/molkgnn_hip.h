@@ -1303,6 +1303,45 @@ size_t mkgnn_graph_components_workspace_bytes(int32_t n);
 int mkgnn_graph_components(const int64_t* row_ptr, const int32_t* col, int32_t n, int32_t* labels, int32_t* state, int32_t resume,
                            int32_t* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- MaxMin picking (additive; the ABI version stays 8): the farthest-first traversal of stored embeddings -- k_max rows that
+ * are as different from each other as possible (RDKit's MaxMinPicker), the similarity at which each was taken, and the pick every
+ * other row lies nearest to.  emb [n_rows, H] (emb_stride >= H, RAW).  The similarity is S[i, p]: the float32 value
+ * mkgnn_embed_cosine writes for row i as the ROW and row p as the QUERY, BIT FOR BIT -- (dot * inv(e_i)) * inv(e_p), the
+ * orientation and text mkgnn_diverse_pick uses.  molkgnn_amd/screening.py::maxmin_pick_reference is the definition:
+ *   a row is VALID when S[i, i] is not NaN (a NaN, infinite or overflowing row is never picked, takes no part and keeps leader
+ *   -1, leader_sim NaN).  cur[i] starts at start_sim[i] (the row's similarity to what the caller already owns: the first output of
+ *   mkgnn_embed_max_cosine, say), or at -inf with start_sim null; a valid row whose start value is NaN is EXCLUDED: never picked,
+ *   but assigned like any other.  leader[i] starts at -1.  Round t = 0 .. k_max - 1: the candidate is the valid, not excluded, not
+ *   yet picked row with the SMALLEST cur (-0.0 == +0.0; among equals the lower row); without one, or unless cur < stop_sim
+ *   (strict), the rounds end.  picks[t] = i, pick_sim[t] = cur[i] (its bits), leader[i] = i, cur[i] = S[i, i] (final).  Every valid,
+ *   not picked row j then meets the pick: s = S[j, i] replaces cur[j], and i leader[j], when s is not NaN and cur[j] is NaN or
+ *   s > cur[j] (strict: among equally near picks the EARLIER one leads).
+ * Afterwards leader_sim[j] = cur[j] for the valid rows (a row nothing came nearer to than its start keeps -1 and its start
+ * value's bits); unused slots of picks are -1, of pick_sim NaN; *n_picks is the number of picks (device memory).  pick_sim is
+ * non-decreasing: it is the threshold a leader clustering would need for that many picks.
+ *
+ * Up to 1 024 rows ONE workgroup runs every round in one launch behind the init (a thread per row, the row in registers).  Beyond,
+ * a round is two launches: a one-workgroup select (reduces the blocks' partial arg-mins, applies the stop rule, stages the pick)
+ * and a grid-wide update (one pass over emb; every block leaves its new partial arg-min); 1 + 2 k_max launches are enqueued, and
+ * once the rounds have ended a device flag makes the remaining ones return at once.  The launch boundary is the only thing that
+ * orders workgroups against each other.  Everything runs on `stream`, is capturable, has no host round trip, no atomics and no
+ * state between calls; the inverse norms and S[i, i] are computed inside the call, so a captured call follows new contents of emb
+ * and start_sim.  The result is a function of emb, start_sim, stop_sim and k_max alone: not of the block size, the stride or which
+ * of the two forms ran.  The workspace (4-byte aligned, mkgnn_maxmin_pick_workspace_bytes(n_rows) =
+ * 4 (3 ceil4(n_rows) + 2 ceil4(ceil(n_rows / 256)) + 72) bytes, ceil4 rounding up to a multiple of 4; 0 for rejected sizes) needs no
+ * initialisation.
+ *
+ * Limits: 1 <= H <= 64; 1 <= n_rows <= MKGNN_MAXMIN_MAX_ROWS (2^20); 1 <= k_max <= min(n_rows, MKGNN_MAXMIN_MAX_PICKS); stop_sim
+ * not NaN (+inf: no stop; -inf: no pick).  n_rows == 0 is a no-op that returns 0, even with null pointers.  Anything else -- a
+ * limit, a NaN stop_sim, a stride below H, a null pointer other than start_sim, a workspace that is too small or misaligned,
+ * overlapping buffers -- returns non-zero with mkgnn_last_error set, before any launch. */
+#define MKGNN_MAXMIN_MAX_ROWS  1048576
+#define MKGNN_MAXMIN_MAX_PICKS 4096
+size_t mkgnn_maxmin_pick_workspace_bytes(int64_t n_rows);
+int mkgnn_maxmin_pick(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* start_sim /* [n_rows] or null */,
+                      float stop_sim, int32_t k_max, int32_t* picks, float* pick_sim, int32_t* n_picks, int32_t* leader,
+                      float* leader_sim, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,10 @@ SELECT_ROWS_PASS = 1024
 DIVERSE_MAX_ROWS, DIVERSE_MAX_H = 1 << 20, 64           # MKGNN_DIVERSE_MAX_ROWS, mkgnn_diverse_pick's widest embedding
 # kgnn_diverse.hip's tiling (DV_COVER_ROWS, DV_COVER_TILE): rows per block and picks per LDS tile of the cover launch
 DIVERSE_COVER_ROWS, DIVERSE_COVER_TILE = 128, 32
+# MKGNN_MAXMIN_MAX_ROWS, MKGNN_MAXMIN_MAX_PICKS, mkgnn_maxmin_pick's widest embedding
+MAXMIN_MAX_ROWS, MAXMIN_MAX_PICKS, MAXMIN_MAX_H = 1 << 20, 4096, 64
+# kgnn_maxmin.hip's tiling (MM_TILE, MM_ROWS): the rows ONE workgroup walks in one launch; rows per block of the grid-wide launches
+MAXMIN_TILE, MAXMIN_ROWS = 1024, 256
 EXEMPLARS_MAX_K, EXEMPLARS_MAX_COLUMNS = 64, 256        # MKGNN_EXEMPLARS_MAX_K, MKGNN_EXEMPLARS_MAX_COLUMNS
 # kgnn_exemplars.hip's tiling (EX_TILE, EX_CHUNK): degree-bucket slots per tile and columns per workgroup of the runs launch
 EXEMPLARS_TILE, EXEMPLARS_CHUNK = 128, 64
@@ -252,7 +256,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_kernel_exemplars_update", "mkgnn_kernel_exemplars_workspace_bytes", "mkgnn_embed_knn_update",
            "mkgnn_embed_knn_workspace_bytes", "mkgnn_embed_count_within", "mkgnn_embed_count_within_workspace_bytes",
            "mkgnn_embed_neighbours_within", "mkgnn_embed_neighbours_within_workspace_bytes", "mkgnn_graph_components",
-           "mkgnn_graph_components_workspace_bytes")
+           "mkgnn_graph_components_workspace_bytes", "mkgnn_maxmin_pick", "mkgnn_maxmin_pick_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -478,6 +482,11 @@ def load() -> C.CDLL:
     lib.mkgnn_diverse_pick_workspace_bytes.argtypes = [I64]
     lib.mkgnn_diverse_pick.restype = C.c_int
     lib.mkgnn_diverse_pick.argtypes = [P, I64, I64, I32, C.c_float, I32, P, P, P, P, P, C.c_size_t, P]
+    # (emb, stride, n_rows, H, start_sim or null, stop_sim, k_max, picks, pick_sim, n_picks, leader, leader_sim, workspace, bytes, stream)
+    lib.mkgnn_maxmin_pick_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_maxmin_pick_workspace_bytes.argtypes = [I64]
+    lib.mkgnn_maxmin_pick.restype = C.c_int
+    lib.mkgnn_maxmin_pick.argtypes = [P, I64, I64, I32, P, C.c_float, I32, P, P, P, P, P, P, C.c_size_t, P]
     lib.mkgnn_kernel_exemplars_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_kernel_exemplars_workspace_bytes.argtypes = [C.POINTER(Int64x4), C.POINTER(Int32x4), I32, I32]
     lib.mkgnn_kernel_exemplars_update.restype = C.c_int

@@ -1575,6 +1575,137 @@ def diverse_pick(emb: torch.Tensor, max_sim: float, k: Optional[int] = None, out
     return tuple(out)
 
 
+def maxmin_pick_supported(n: int, H: int, k: int) -> bool:
+    """The shapes ``mkgnn_maxmin_pick`` takes.  A wider embedding goes through torch operators on the GPU; more rows or more picks
+    than the kernel's limits are refused by ``maxmin_pick``."""
+    return 1 <= n <= _lib.MAXMIN_MAX_ROWS and 1 <= H <= _lib.MAXMIN_MAX_H and 1 <= k <= min(n, _lib.MAXMIN_MAX_PICKS)
+
+
+def _maxmin_pick_torch(emb: torch.Tensor, k: int, stop_sim: float, start_sim, picks, pick_sim, n_picks, leader, leader_sim) -> None:
+    """The rounds of ``screening.maxmin_pick_reference`` through torch operators on the GPU, for the widths the kernel does not
+    take: round ``t`` asks ``embedding_cosine(emb, emb[i:i + 1])`` for ONE column -- the similarities of that route at that width, so
+    no ``[n, n]`` matrix exists -- with ``i`` kept on the device (no host round trip inside the rounds; after the stop the rounds
+    still run and change nothing).  A row is valid when all its values are finite: beyond 64 columns ``embedding_cosine`` forms its
+    products in float64, where exactly those rows have a similarity to themselves that is not NaN."""
+    n, dev = emb.shape[0], emb.device
+    row = torch.arange(n, device=dev)
+    nan = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+    valid = torch.isfinite(emb).all(dim=1)
+    cur = torch.full((n,), float("-inf"), dtype=torch.float32, device=dev) if start_sim is None else start_sim.clone()
+    candidate = valid & ~torch.isnan(cur)
+    cur = torch.where(valid, cur, nan)
+    picked = torch.zeros(n, dtype=torch.bool, device=dev)
+    lead = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    chosen = torch.full((k,), -1, dtype=torch.int64, device=dev)
+    taken_at = torch.full((k,), float("nan"), dtype=torch.float32, device=dev)
+    done = torch.zeros((), dtype=torch.bool, device=dev)
+    count = torch.zeros((), dtype=torch.int64, device=dev)
+    for t in range(k):
+        key = torch.where(candidate, cur, torch.full_like(cur, float("inf")))
+        least = key.min()
+        i = torch.where(candidate & (key == least), row, torch.full_like(row, n)).min()     # (the lower row among equals; n: none)
+        go = (i < n) & (least < stop_sim) & ~done                # (0-dim, on the device)
+        done = done | ~go
+        i = i.clamp_max(n - 1)
+        col = embedding_cosine(emb, emb.index_select(0, i.reshape(1)))[:, 0]
+        it = go & (row == i)
+        chosen[t] = torch.where(go, i, chosen[t])
+        taken_at[t] = torch.where(go, cur.index_select(0, i.reshape(1))[0], taken_at[t])
+        meet = go & valid & ~picked & ~it & ~torch.isnan(col) & (torch.isnan(cur) | (col > cur))
+        cur = torch.where(it | meet, col, cur)
+        lead = torch.where(it | meet, i, lead)
+        picked = picked | it
+        candidate = candidate & ~it
+        count = count + go
+    picks.copy_(chosen)
+    pick_sim.copy_(taken_at)
+    n_picks.copy_(count.reshape(1))
+    leader.copy_(lead)
+    leader_sim.copy_(cur)
+
+
+_MAXMIN_WS: dict = {}
+
+
+def maxmin_pick(emb: torch.Tensor, k: int, stop_sim: Optional[float] = None, start_sim: Optional[torch.Tensor] = None, out=None):
+    """``(picks int32 [k], pick_sim float32 [k], n_picks int32 [1], leader int32 [n], leader_sim float32 [n])``: MaxMin picking --
+    the farthest-first traversal, RDKit's ``MaxMinPicker`` -- over the rows of a float32 CUDA ``emb [n, H]`` (``mkgnn_maxmin_pick``;
+    ``screening.maxmin_pick_reference`` is the definition).  With ``S[i, p]`` the similarity ``embedding_cosine`` gives for row ``i``
+    and query row ``p``, BIT FOR BIT, and ``cur[i]`` the largest similarity of row ``i`` to the selection so far (``start_sim[i]``, or
+    ``-inf`` without ``start_sim``, before anything nearer turns up): every round the candidate with the SMALLEST ``cur`` (``-0.0 ==
+    +0.0``, then the lower row) becomes the next pick while ``cur < stop_sim`` (strict; ``None``: no stop), at most ``k`` of them, and
+    every other valid row meets it -- a strictly larger similarity replaces ``cur`` and the row's leader.  ``picks`` holds the row
+    indices in pick order (unused slots ``-1``), ``pick_sim[t]`` how close pick ``t`` was to everything chosen before it (unused
+    slots NaN; non-decreasing), ``leader`` / ``leader_sim`` the nearest pick of every row and the similarity to it (a pick leads
+    itself).  A row whose own similarity ``S[i, i]`` is NaN is never picked and keeps ``(-1, NaN)``; a row nothing came nearer to
+    than its start value keeps ``-1`` and that value.  ``start_sim``: float32 ``[n]`` on the device, every row's similarity to what
+    the caller already owns (``embedding_max_cosine``'s first output); a NaN there EXCLUDES the row: never picked, still assigned.
+    ``1 <= k <= min(n, 4096)``, ``n <= 2^20``.  ``out``: the five contiguous tensors to write into.  The launches read ``emb`` and
+    ``start_sim`` raw, so a captured call follows their contents; the scratch is a per-device buffer that only grows for eager
+    calls, and a call inside a capture allocates its own.  An embedding wider than 64: the same definition through torch operators
+    on the GPU (``embedding_cosine``'s own route and bits at that width, one column per round).  It has no autograd node: called
+    where a gradient is being recorded for ``emb`` or ``start_sim`` it raises instead of dropping it."""
+    if not torch.is_tensor(emb) or emb.dim() != 2 or emb.dtype != torch.float32 or emb.shape[1] < 1:
+        raise ValueError("maxmin_pick needs a float32 [n, H] embedding")
+    n, H = int(emb.shape[0]), int(emb.shape[1])
+    k = int(k)
+    stop_sim = float("inf") if stop_sim is None else float(stop_sim)
+    if stop_sim != stop_sim:
+        raise ValueError("maxmin_pick: stop_sim is NaN")
+    if n > _lib.MAXMIN_MAX_ROWS:
+        raise ValueError(f"maxmin_pick: {n} rows: at most {_lib.MAXMIN_MAX_ROWS} (MKGNN_MAXMIN_MAX_ROWS) in one call")
+    if k > _lib.MAXMIN_MAX_PICKS or (n > 0 and not 1 <= k <= n) or k < 0:
+        raise ValueError(f"maxmin_pick: k = {k} outside [1, {min(n, _lib.MAXMIN_MAX_PICKS)}] (at most MKGNN_MAXMIN_MAX_PICKS = "
+                         f"{_lib.MAXMIN_MAX_PICKS} picks per call, and no more than there are rows)")
+    if start_sim is not None and (not torch.is_tensor(start_sim) or start_sim.dtype != torch.float32 or tuple(start_sim.shape) != (n,)):
+        raise ValueError(f"maxmin_pick: start_sim is a float32 [{n}] tensor, one value per row of emb")
+    if not emb.is_cuda or (start_sim is not None and start_sim.device != emb.device):
+        raise ValueError(f"maxmin_pick runs on the GPU: emb is on {emb.device}" +
+                         ("" if start_sim is None else f", start_sim on {start_sim.device}") +
+                         " (there is no CPU path; screening.maxmin_pick_reference is the host form)")
+    if torch.is_grad_enabled() and (emb.requires_grad or (start_sim is not None and start_sim.requires_grad)):
+        raise RuntimeError("maxmin_pick is forward only: call it under torch.no_grad() (or on detached inputs)")
+    dev = emb.device
+    if out is None:
+        out = (torch.empty(k, dtype=torch.int32, device=dev), torch.empty(k, dtype=torch.float32, device=dev),
+               torch.empty(1, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+               torch.empty(n, dtype=torch.float32, device=dev))
+    else:
+        ok = isinstance(out, (tuple, list)) and len(out) == 5 and all(torch.is_tensor(o) and o.device == dev and o.is_contiguous()
+                                                                      for o in out)
+        if not ok or any(out[j].dtype != torch.int32 for j in (0, 2, 3)) or any(out[j].dtype != torch.float32 for j in (1, 4)) \
+                or tuple(out[0].shape) != (k,) or tuple(out[1].shape) != (k,) or out[2].numel() != 1 \
+                or tuple(out[3].shape) != (n,) or tuple(out[4].shape) != (n,):
+            raise ValueError(f"out: contiguous (int32 [{k}], float32 [{k}], int32 [1], int32 [{n}], float32 [{n}]) on {dev}")
+    picks, pick_sim, n_picks, leader, leader_sim = out
+    if n == 0:
+        n_picks.zero_()
+        picks.fill_(-1)
+        pick_sim.fill_(float("nan"))
+        return tuple(out)
+    emb = emb.detach()
+    if start_sim is not None:
+        start_sim = start_sim.detach().contiguous()
+    if not maxmin_pick_supported(n, H, k):
+        _maxmin_pick_torch(emb, k, stop_sim, start_sim, picks, pick_sim, n_picks, leader, leader_sim)
+        return tuple(out)
+    emb = _row_major(emb)
+    lib = _lib.load()
+    nbytes = int(lib.mkgnn_maxmin_pick_workspace_bytes(n))
+    if torch.cuda.is_current_stream_capturing():
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    else:
+        ws = _MAXMIN_WS.get(str(dev))
+        if ws is None or ws.numel() < nbytes:
+            ws = _MAXMIN_WS[str(dev)] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkgnn_maxmin_pick(emb.data_ptr(), _stride0(emb), n, H, None if start_sim is None else start_sim.data_ptr(),
+                                         stop_sim, k, picks.data_ptr(), pick_sim.data_ptr(), n_picks.data_ptr(), leader.data_ptr(),
+                                         leader_sim.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
+                   "mkgnn_maxmin_pick")
+    return tuple(out)
+
+
 # ------------------------------------------------------------------- the tail of a training step, fused --
 # MKGNN_FUSED_TAIL=0: readout_blocks + bce_head_loss as separate operators (nine launches; A/B, diagnostics)
 _FUSED_TAIL = os.environ.get("MKGNN_FUSED_TAIL", "1") != "0"

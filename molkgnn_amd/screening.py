@@ -66,6 +66,13 @@ connected components of that graph (``mkgnn_graph_components``), the one partiti
 ``cluster_components_embeddings``        stored embeddings -> every row's component, their sizes, the lists, the best member of each
 ``split_leakage``                        stored pairs by (fold of the row, fold of the reference): what a split lets through
 
+MaxMin picking -- ``k`` molecules that are as different from each other as possible (the farthest-first traversal,
+``mkgnn_maxmin_pick``), and the similarity at which each was taken: the selection by budget instead of by threshold:
+
+``maxmin_pick_reference``                the rounds in numpy over a given similarity matrix: the definition
+``pick_maxmin_embeddings``               stored embeddings (a deck one owns, rows to leave out) -> picks, ``pick_sim``, nearest picks
+``select_maxmin``                        shards -> every molecule embedded, one selection over all of them
+
 What each kernel learned -- for every kernel column of a convolution layer the ``k`` atoms of the library it matches best
 (``GNNModel.kernel_scores``, ``mkgnn_kernel_exemplars_update``; one running list per column, a candidate is an atom):
 
@@ -1313,6 +1320,220 @@ def screen_diverse(model, residents, k: int, batch_size: int, max_sim: float, po
               "n_scored": n_scored}
     if return_embeddings:
         result["embeddings"] = embs
+    return result
+
+
+# ------------------------------------------------------------------------------------------ MaxMin picking --
+# Every selection above needs a similarity threshold chosen in advance and returns however many picks that threshold gives.  The
+# farthest-first traversal (MaxMin, RDKit's MaxMinPicker) takes the budget k instead -- buy k compounds of a hit pool, subsample an
+# over-represented class, extend a deck one owns with what it lacks most -- and returns the threshold as a by-product: pick_sim[t]
+# is how close pick t was to everything chosen before it, which is also the max_sim to give screen_diverse for t picks.
+#
+# ``maxmin_pick_reference``    the definition in numpy, over a given similarity matrix
+# ``pick_maxmin_embeddings``   stored embeddings (and a deck one owns, rows to leave out) -> the picks, every row's nearest pick
+# ``select_maxmin``            shards of a library -> embed every molecule, one selection over all of them
+MAXMIN_MAX_ROWS = 1 << 20                      # MKGNN_MAXMIN_MAX_ROWS
+MAXMIN_MAX_PICKS = 4096                        # MKGNN_MAXMIN_MAX_PICKS
+MAXMIN_DECK_SLICE = 1 << 20                    # deck rows per mkgnn_embed_max_cosine: MKGNN_MAX_COSINE_MAX_REFS
+
+
+def maxmin_pick_reference(sim, k_max, stop_sim=float("inf"), start_sim=None):
+    """The definition of ``mkgnn_maxmin_pick`` (include/molkgnn_hip.h), on the host, over a GIVEN square similarity matrix ``sim`` of
+    any float dtype (``sim[j, i]`` is the similarity of row ``j`` as the row with row ``i`` as the query): ``(picks int32 [k_max],
+    pick_sim [k_max], n_picks, leader int32 [n], leader_sim [n])``, the floats in ``sim``'s dtype.
+
+    Row ``i`` is VALID when ``sim[i, i]`` is not NaN; any other row is never picked, takes no part and ends with ``(-1, NaN)``.
+    ``cur[i]`` starts at ``start_sim[i]`` (rounded to ``sim``'s dtype), or at ``-inf`` without ``start_sim``; a valid row whose start
+    value is NaN is EXCLUDED: never picked, but assigned like any other.  Round ``t = 0 .. k_max - 1``: the candidate is the valid,
+    not excluded, not yet picked row with the SMALLEST ``cur`` (``-0.0 == +0.0``; among equals the lower row) -- none: stop; unless
+    ``cur[i] < stop_sim`` (strict, ``stop_sim`` rounded to ``sim``'s dtype): stop.  ``picks[t] = i``, ``pick_sim[t] = cur[i]``,
+    ``leader[i] = i``, ``cur[i] = sim[i, i]`` for good.  Every valid, not picked row ``j`` then meets the pick: with ``s = sim[j, i]``
+    not NaN and (``cur[j]`` NaN or ``s > cur[j]``, strict: the EARLIER of equally near picks leads), ``cur[j] = s`` and ``leader[j] =
+    i``.  Afterwards ``leader_sim[j] = cur[j]`` for the valid rows; unused slots of ``picks`` are ``-1``, of ``pick_sim`` NaN."""
+    if torch.is_tensor(sim):
+        sim = sim.detach().cpu().numpy()
+    sim = np.asarray(sim)
+    if sim.ndim != 2 or sim.shape[0] != sim.shape[1] or not np.issubdtype(sim.dtype, np.floating):
+        raise ValueError("a square similarity matrix of a float dtype is needed")
+    n, k_max = sim.shape[0], int(k_max)
+    if not 1 <= k_max <= max(n, 1):
+        raise ValueError(f"k_max = {k_max} outside [1, {n}]")
+    stop = sim.dtype.type(stop_sim)
+    if np.isnan(stop):
+        raise ValueError("stop_sim is NaN")
+    if start_sim is None:
+        cur = np.full(n, -np.inf, dtype=sim.dtype)
+    else:
+        if torch.is_tensor(start_sim):
+            start_sim = start_sim.detach().cpu().numpy()
+        cur = np.array(start_sim, dtype=sim.dtype)               # (a copy)
+        if cur.shape != (n,):
+            raise ValueError(f"start_sim holds one value per row: [{n}]")
+    valid = ~np.isnan(np.diagonal(sim))
+    candidate = valid & ~np.isnan(cur)
+    picked = np.zeros(n, dtype=bool)
+    picks = np.full(k_max, -1, dtype=np.int32)
+    pick_sim = np.full(k_max, np.nan, dtype=sim.dtype)
+    leader = np.full(n, -1, dtype=np.int32)
+    n_picks = 0
+    for t in range(k_max):
+        rows = np.flatnonzero(candidate)
+        if rows.size == 0:
+            break
+        i = int(rows[np.argmin(cur[rows])])                      # (the first of the smallest: -0.0 == +0.0, the lower row)
+        if not cur[i] < stop:
+            break
+        picks[t], pick_sim[t] = i, cur[i]
+        n_picks = t + 1
+        leader[i], cur[i] = i, sim[i, i]
+        picked[i] = True
+        candidate[i] = False
+        s = sim[:, i]
+        with np.errstate(invalid="ignore"):
+            meet = valid & ~picked & ~np.isnan(s) & (np.isnan(cur) | (s > cur))
+        cur[meet] = s[meet]
+        leader[meet] = i
+    return picks, pick_sim, n_picks, leader, np.where(valid, cur, sim.dtype.type(np.nan))
+
+
+def _check_stop_sim(who: str, stop_sim) -> Optional[float]:
+    if stop_sim is None:
+        return None
+    stop_sim = float(stop_sim)
+    if stop_sim != stop_sim:
+        raise ValueError(f"{who}: stop_sim is NaN")
+    return stop_sim
+
+
+def pick_maxmin_embeddings(emb: torch.Tensor, k: int, stop_sim: Optional[float] = None, deck: Optional[torch.Tensor] = None,
+                           exclude: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None) -> dict:
+    """MaxMin picking among ANY set of molecules whose embeddings are kept -- the output of ``embed_resident``, the ``pool_emb`` of
+    ``screen_diverse``, up to 2^20 rows -- WITHOUT running the network: ``k`` rows of ``emb`` (float32 ``[n, G]`` on the GPU) that are
+    as different from each other as possible (``readout.maxmin_pick``; ``maxmin_pick_reference`` is the definition).  Without a
+    deck the first pick is the first valid row, so a list in rank order starts at its best molecule.  ``stop_sim``: stop once every
+    remaining row lies within that similarity of the selection (strict; ``None``: only ``k`` ends it).  ``deck``: float32 ``[R, G]``
+    embeddings one already owns -- every row starts at its similarity to its nearest deck row (``readout.embedding_max_cosine``; a
+    deck beyond 2^20 rows goes in chunks combined by the maximum of what is not NaN), so the picks extend the deck with what it
+    lacks most.  ``exclude``: bool ``[n]``, rows never to pick (molecules one owns that are part
+    of ``emb``); they are still assigned to their nearest pick.  Returns a dict in terms of the caller's rows -- ``ids[row]`` when
+    ``ids`` (an integer ``[n]`` tensor on the GPU) is given, the row numbers otherwise:
+
+    ``picks``         ``[n_picks]`` int64: the picks, in pick order
+    ``pick_sim``      ``[n_picks]`` float32: how close each was to everything chosen before it (and to the deck); non-decreasing
+    ``n_picks``       their number
+    ``leader``        ``[n]`` int64, by the caller's row: the pick nearest to the row (itself for a pick); ``-1`` for a row that is
+                      NaN, and for one that no pick came nearer to than the deck
+    ``leader_sim``    ``[n]`` float32, by the caller's row: the similarity to that pick (or to the deck); NaN for a NaN row
+    ``cluster_size``  ``[n_picks]`` int64: the rows every pick leads, itself included
+    ``deck_sim``      ``[n]`` float32, with a deck: every row's similarity to its nearest deck row
+
+    One host read at the end (the number of picks).  A wrong shape, dtype or device, a NaN ``stop_sim``, ``k`` outside ``[1, min(n,
+    4096)]``, more than 2^20 rows: ``ValueError`` before a launch."""
+    who = "pick_maxmin_embeddings"
+    if not torch.is_tensor(emb) or emb.dim() != 2 or emb.dtype != torch.float32 or emb.shape[1] < 1:
+        raise ValueError(f"{who}: emb is a float32 [n, G] tensor")
+    n, G = int(emb.shape[0]), int(emb.shape[1])
+    if not 1 <= n <= MAXMIN_MAX_ROWS:
+        raise ValueError(f"{who}: {n} rows outside [1, {MAXMIN_MAX_ROWS}]")
+    k = int(k)
+    if not 1 <= k <= min(n, MAXMIN_MAX_PICKS):
+        raise ValueError(f"{who}: k = {k} outside [1, {min(n, MAXMIN_MAX_PICKS)}] (at most {MAXMIN_MAX_PICKS} picks per call, and no "
+                         "more than there are rows)")
+    stop_sim = _check_stop_sim(who, stop_sim)
+    if deck is not None and (not torch.is_tensor(deck) or deck.dim() != 2 or deck.dtype != torch.float32
+                             or int(deck.shape[1]) != G or int(deck.shape[0]) < 1):
+        raise ValueError(f"{who}: deck is a float32 [R, {G}] tensor of at least one embedding")
+    if exclude is not None and (not torch.is_tensor(exclude) or exclude.dtype != torch.bool or tuple(exclude.shape) != (n,)):
+        raise ValueError(f"{who}: exclude is a bool [{n}] tensor")
+    integer = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+    if ids is not None and (not torch.is_tensor(ids) or ids.dtype not in integer or tuple(ids.shape) != (n,)):
+        raise ValueError(f"{who}: ids is an integer [{n}] tensor")
+    dev = emb.device
+    if dev.type != "cuda" or any(t is not None and t.device != dev for t in (deck, exclude, ids)):
+        raise ValueError(f"{who}: emb is on {dev}; the selection runs on the GPU, with deck, exclude and ids on the same device (there "
+                         "is no CPU path; maxmin_pick_reference is the host form)")
+    from .readout import embedding_max_cosine, maxmin_pick
+    emb = emb.detach()
+    deck_sim = start = None
+    if deck is not None:
+        deck = deck.detach()
+        for a in range(0, int(deck.shape[0]), MAXMIN_DECK_SLICE):
+            part = embedding_max_cosine(emb, deck[a:a + MAXMIN_DECK_SLICE])[0]
+            deck_sim = part if deck_sim is None else torch.fmax(deck_sim, part)         # (the maximum of what is not NaN)
+        start = deck_sim
+    if exclude is not None:
+        if start is None:
+            start = torch.full((n,), float("-inf"), dtype=torch.float32, device=dev)
+        start = torch.where(exclude, torch.full_like(start, float("nan")), start)
+    picks, pick_sim, n_picks, leader, leader_sim = maxmin_pick(emb, k, stop_sim, start)
+    count = int(n_picks.item())                                  # (the one host read)
+    picks = picks[:count].long()
+    led = leader.long()
+    if ids is not None:
+        name = ids.long()
+        led, names = torch.where(led >= 0, name[led.clamp_min(0)], led), name[picks]
+    else:
+        names = picks
+    result = {"picks": names, "pick_sim": pick_sim[:count], "n_picks": count, "leader": led, "leader_sim": leader_sim,
+              "cluster_size": _cluster_sizes(leader, picks, n)}
+    if deck_sim is not None:
+        result["deck_sim"] = deck_sim
+    return result
+
+
+def select_maxmin(model, residents, k: int, batch_size: int, stop_sim: Optional[float] = None, deck=None) -> dict:
+    """MaxMin picking over a library: every molecule of every shard of ``residents`` (as in ``screen``; shard ``j`` carries tag
+    ``j``) is embedded with ``embed_resident``, and ONE ``pick_maxmin_embeddings`` runs over the concatenation -- up to 2^20 molecules
+    in all (128 bytes each at ``G = 32``).  The head is not run, so the model may have any ``task_dim``.  ``deck``: what one already
+    owns, a float32 ``[R, G]`` tensor of embeddings on the model's GPU or a ``ResidentShard``, which is embedded first.  Returns
+    ``top_shard``, ``top_mol`` and ``pick_sim`` of the picks, in pick order; ``picks`` (int64 positions in the concatenation) and
+    ``n_picks``; ``leader`` (per shard: int64 positions in the concatenation of every molecule's nearest pick, ``-1`` for none) and
+    ``leader_sim`` (per shard); ``cluster_size`` (per pick, itself included); ``n_embedded``; and, with a deck, ``deck_sim`` (per shard) and
+    ``deck_emb`` (the ``[R, G]`` matrix that was compared with).
+    The gather's status word is read once per shard; the model comes back in the mode it came in.  A NaN ``stop_sim``, ``k`` outside
+    ``[1, 4096]``, a model, shard or deck that is not on the GPU: ``ValueError`` before a launch; a library of more than 2^20
+    molecules: ``ValueError`` as soon as the shards seen so far hold that many, before the selection."""
+    from .shards import ResidentShard
+    who = "select_maxmin"
+    k, bs = int(k), int(batch_size)
+    if not 1 <= k <= MAXMIN_MAX_PICKS:
+        raise ValueError(f"{who}: k = {k} outside [1, {MAXMIN_MAX_PICKS}] (MKGNN_MAXMIN_MAX_PICKS)")
+    if bs < 1:
+        raise ValueError("batch_size >= 1")
+    stop_sim = _check_stop_sim(who, stop_sim)
+    G = _embedding_width(model)
+    if next(model.parameters()).device.type != "cuda":
+        raise ValueError(f"{who} runs on the GPU: move the model there (there is no CPU path)")
+    if not isinstance(residents, (list, tuple)):
+        residents = list(residents)
+    if not residents:
+        raise ValueError(f"{who} needs at least one shard")
+    sizes = [int(r.n_molecules) for r in residents]
+    if sum(sizes) > MAXMIN_MAX_ROWS:
+        raise ValueError(f"{who}: the shards hold {sum(sizes)} molecules; one selection takes at most {MAXMIN_MAX_ROWS} (2^20) in all "
+                         "-- select within parts of the library, then among the parts' picks")
+    if sum(sizes) < k:
+        raise ValueError(f"{who}: k = {k} picks among {sum(sizes)} molecules")
+    for r in residents:
+        _check_device(model, r)
+    if isinstance(deck, ResidentShard):
+        if int(deck.n_molecules) < 1:
+            raise ValueError(f"{who}: a deck shard holds at least one molecule")
+        deck = _embedding_f32(embed_resident(model, deck, bs))
+    dev = next(model.parameters()).device
+    if deck is not None:
+        _check_vectors(who, deck, G, dev, "deck embeddings", None, "")
+    emb = torch.cat([_embedding_f32(embed_resident(model, r, bs)) for r in residents])
+    r = pick_maxmin_embeddings(emb, k, stop_sim, deck)
+    first = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int64, device=dev)
+    picks = r["picks"]
+    shard = torch.bucketize(picks, first[1:], right=True)
+    result = {"top_shard": shard.to(torch.int32), "top_mol": (picks - first[shard]).to(torch.int32), "pick_sim": r["pick_sim"],
+              "picks": picks, "n_picks": r["n_picks"], "leader": list(torch.split(r["leader"], sizes)),
+              "leader_sim": list(torch.split(r["leader_sim"], sizes)), "cluster_size": r["cluster_size"], "n_embedded": sum(sizes)}
+    if deck is not None:
+        result["deck_sim"] = list(torch.split(r["deck_sim"], sizes))
+        result["deck_emb"] = deck
     return result
 
 
