@@ -622,6 +622,30 @@ int mkgnn_plan_build(const mkgnn_degree_bucket buckets[MKGNN_MAX_DEGREE], int64_
                      int32_t* in_col_packed, int32_t* out_rowptr, int32_t* out_col, int8_t* deg8, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* (ABI v8, additive) Present blocks.  Between two layers h = propagate(sim_sc), and row n of sim_sc is non-zero only in the column
+ * block of atom n's degree: block d of h[j] is +0 unless j has a bond partner of degree d, and the backward of the layer that made
+ * h reads block d of d loss / d h[j] under exactly that condition.
+ *   present8          [N] the blocks of atom j: the OR of 1 << (deg8[s] - 1) over the edges s -> j (edges from an atom in no bucket
+ *                     add nothing; 0 for an atom without such an edge, which the kernels read as "every block");
+ *   contrib_present8  [sum_d N_d (d+1)] present8 of every contribution row's target (the rows numbered as in the scatter CSR);
+ *                     may be NULL (skipped): no kernel of the step reads it -- it is what a mask on the producer of the
+ *                     contribution rows would read -- so it is made on request, not with every plan.
+ * One launch, behind the mkgnn_plan_build / mkgnn_index_build whose in_rowptr / in_col_packed it reads (same stream).  buckets:
+ * count, selected_index and nei_index are read.  in_col_packed NULL (a batch without edge_index): the arrays are zeroed. */
+int mkgnn_plan_present_blocks(const mkgnn_degree_bucket buckets[MKGNN_MAX_DEGREE], int64_t n_atoms, const int32_t* in_rowptr,
+                              const int32_t* in_col_packed, int8_t* present8, int8_t* contrib_present8, void* stream);
+/* The NEXT mkgnn_kernelsetconv_backward of the calling thread may leave d loss / d x undefined outside the present blocks of every
+ * atom: x is such an h, num_kernels the four block widths of its columns (their sum = F), present8 as above, alive until that
+ * call's kernels have run.  The call takes the hint whatever it does with it; where its masked gather does not apply (the generic
+ * kernels, MKGNN_GRAD_BLOCKS=0, an empty block, more than 255 columns) it writes whole rows, which is always correct.  The values
+ * in the present blocks, and every other result of the call, are those of the call without the hint, bit for bit.
+ * (NULL, NULL) withdraws a pending hint. */
+int mkgnn_backward_grad_blocks(const int8_t* present8, const int32_t num_kernels[MKGNN_MAX_DEGREE]);
+/* tests: the number of backward calls since the library was loaded whose gather ran on present blocks only;
+ * mkgnn_debug_poison_backward(1): every backward call fills its contribution rows and grad_x with NaN before its first launch */
+int64_t mkgnn_debug_grad_blocks_launches(void);
+int mkgnn_debug_poison_backward(int32_t enable);
+
 /* Tail of the training step for a single task (reference model.py:147-148, 190-198 with data.py:37):
  *     pred = graph_embedding @ ffn.weight[0] + ffn.bias;   loss = mean(BCEWithLogits(pred, target))
  * forward writes pred [n_rows] and loss [1]; backward takes d loss (one float on the device) and fully overwrites

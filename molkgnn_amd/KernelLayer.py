@@ -122,7 +122,7 @@ class MolGCN(MessagePassing):
             layer.variant = variant
             layer.backward_variant = backward_variant
 
-    def propagate(self, edge_index, sim_sc=None, **kwargs):
+    def propagate(self, edge_index, sim_sc=None, _grad_blocks=False, **kwargs):
         """``h[i] = sum_{j -> i} message(sim_sc[j])``; ``message`` is the identity (KernelLayer.py:122-123)."""
         plan = self._plan
         if plan is None or plan.edge_index is not edge_index:
@@ -131,7 +131,7 @@ class MolGCN(MessagePassing):
             plan = plan_from_lists(sim_sc.shape[0], [emptyf] * 4, [emptyf] * 4, [emptyf] * 4, [empty] * 4, [empty] * 4,
                                    edge_index)
         k = sim_sc.shape[1]
-        return Fn.propagate_add(sim_sc, plan, out_pad=(-k) % 4)
+        return Fn.propagate_add(sim_sc, plan, out_pad=(-k) % 4, grad_blocks=_grad_blocks)
 
     def forward(self, *argv, **kwargv):
         if len(argv) != 0:
@@ -195,10 +195,15 @@ class MolGCN(MessagePassing):
                 # which is handed out)
                 split_next = (_ROWS_SPLIT and not is_last_layer and not save_score and h.is_cuda
                               and self.layers[i + 1]._accepts_split_rows(self._plan, h))
-                sim_sc, propagated = self.layers[i]._run(h, self._plan, is_last_layer, save_score, block_rows=_BLOCK_ROWS,
-                                                         fuse_propagate=_FUSE_PROPAGATE, prepared=prepared[i],
-                                                         split_next=split_next)
-                h = sim_sc if propagated else self.propagate(edge_index=edge_index, sim_sc=sim_sc)
+                # (... and its gradient is read in its present blocks only, functional.mark_grad_blocks: tagged under the same
+                # conditions, on block rows -- never with MKGNN_DENSE_PROPAGATE=1, whose backward reads whole rows)
+                tag_next = _BLOCK_ROWS and not is_last_layer and not save_score and h.is_cuda
+                out = self.layers[i]._run(h, self._plan, is_last_layer, save_score, block_rows=_BLOCK_ROWS,
+                                          fuse_propagate=_FUSE_PROPAGATE, prepared=prepared[i],
+                                          split_next=split_next, grad_blocks=tag_next)
+                # (_run hands back the pair only where it was asked to fuse: MKGNN_DENSE_PROPAGATE / MKGNN_SPLIT_PROPAGATE get sim_sc)
+                sim_sc, propagated = out if _FUSE_PROPAGATE else (out, False)
+                h = sim_sc if propagated else self.propagate(edge_index=edge_index, sim_sc=sim_sc, _grad_blocks=tag_next)
         finally:
             self._plan = None
         return h

@@ -238,7 +238,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_batchnorm_backward", "mkgnn_bce_head_workspace_bytes", "mkgnn_bce_head_forward",
            "mkgnn_bce_head_backward", "mkgnn_rf_workspace_bytes", "mkgnn_rf_count", "mkgnn_rf_fill", "mkgnn_adamw_step", "mkgnn_adamw_state_floats",
            "mkgnn_bce_head_dropout_forward", "mkgnn_bce_head_dropout_backward", "mkgnn_segment_sum_block_rows",
-           "mkgnn_plan_workspace_bytes", "mkgnn_plan_build", "mkgnn_backward_join", "mkgnn_backward_streams", "mkgnn_bank_prepare", "mkgnn_bank_prepare_deferred", "mkgnn_bank_prepare_flush", "mkgnn_bank_prepare_withdraw", "mkgnn_touch_hint", "mkgnn_expand_batch", "mkgnn_bce_head_fused", "mkgnn_collate_compact", "mkgnn_collate_compact_bytes",
+           "mkgnn_plan_workspace_bytes", "mkgnn_plan_build", "mkgnn_plan_present_blocks", "mkgnn_backward_grad_blocks",
+           "mkgnn_debug_grad_blocks_launches", "mkgnn_debug_poison_backward", "mkgnn_backward_join", "mkgnn_backward_streams", "mkgnn_bank_prepare", "mkgnn_bank_prepare_deferred", "mkgnn_bank_prepare_flush", "mkgnn_bank_prepare_withdraw", "mkgnn_touch_hint", "mkgnn_expand_batch", "mkgnn_bce_head_fused", "mkgnn_collate_compact", "mkgnn_collate_compact_bytes",
            "mkgnn_readout_blocks_supported", "mkgnn_readout_blocks_forward", "mkgnn_readout_blocks_backward",
            "mkgnn_readout_blocks_workspace_bytes", "mkgnn_molecule_supported", "mkgnn_molecule_workspace_bytes",
            "mkgnn_molecule_step", "mkgnn_batchnorm_stats_workspace_bytes", "mkgnn_batchnorm_update_stats",
@@ -509,6 +510,14 @@ def load() -> C.CDLL:
     lib.mkgnn_plan_workspace_bytes.argtypes = [I64, I64, I64]
     lib.mkgnn_plan_build.restype = C.c_int
     lib.mkgnn_plan_build.argtypes = [Buckets4, I64, P, I64, P, P, P, P, P, P, P, P, P, C.c_size_t, P]
+    lib.mkgnn_plan_present_blocks.restype = C.c_int
+    lib.mkgnn_plan_present_blocks.argtypes = [Buckets4, I64, P, P, P, P, P]
+    lib.mkgnn_backward_grad_blocks.restype = C.c_int
+    lib.mkgnn_backward_grad_blocks.argtypes = [P, P]
+    lib.mkgnn_debug_grad_blocks_launches.restype = C.c_int64
+    lib.mkgnn_debug_grad_blocks_launches.argtypes = []
+    lib.mkgnn_debug_poison_backward.restype = C.c_int
+    lib.mkgnn_debug_poison_backward.argtypes = [I32]
     lib.mkgnn_index_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_index_workspace_bytes.argtypes = [I64, I64, I64]
     lib.mkgnn_index_build.restype = C.c_int

@@ -451,6 +451,44 @@ bool take_touch_hint(TouchArgs& out) {
 }  // namespace mkgnn
 }
 
+// Present blocks of d loss / d x (kgnn_launch.h GradBlocks): a thread-local hint, like the touch hint, that the NEXT
+// mkgnn_kernelsetconv_backward of this thread takes (and clears, whatever it does with it)
+static thread_local GradBlocks g_grad_blocks_hint;     // (present8 == null: none pending)
+static std::atomic<int> g_poison_bwd{0};
+extern "C++" {
+namespace mkgnn {
+std::atomic<long long> g_grad_blocks_launches;
+bool take_grad_blocks_hint(GradBlocks& out) {
+    out = g_grad_blocks_hint;
+    g_grad_blocks_hint = GradBlocks{};
+    return out.present8 != nullptr;
+}
+}  // namespace mkgnn
+}
+
+int mkgnn_backward_grad_blocks(const int8_t* present8, const int32_t num_kernels[MKGNN_MAX_DEGREE]) {
+    g_grad_blocks_hint = GradBlocks{};
+    if (!present8) return 0;                                       // withdrawn
+    if (!num_kernels) return api_fail("mkgnn_backward_grad_blocks: null pointer");
+    GradBlocks gb{present8, 0, 0};
+    int off = 0;
+    for (int d = 1; d <= 4; ++d) {
+        const int L = num_kernels[d - 1];
+        // (blocks of one byte per entry, every degree with columns: what the masked kernels take; anything else: no hint, whole rows)
+        if (L < 1 || off + L > 255) return 0;
+        gb.blk_off |= (uint64_t)off << (8 * d);
+        gb.blk_len |= (uint64_t)L << (8 * d);
+        off += L;
+    }
+    g_grad_blocks_hint = gb;
+    return 0;
+}
+
+// tests: backward calls since the library was loaded whose gather read and wrote present chunks only
+int64_t mkgnn_debug_grad_blocks_launches(void) { return g_grad_blocks_launches.load(); }
+// tests: a backward call fills its contribution rows and grad_x with NaN before anything is launched (what no kernel writes stays NaN)
+int mkgnn_debug_poison_backward(int32_t enable) { g_poison_bwd.store(enable ? 1 : 0); return 0; }
+
 int mkgnn_touch_hint(const void* const* arrays, const size_t* bytes, int32_t count) {
     if (count <= 0 || !arrays || !bytes) {
         const int had = g_touch_hint.count > 0 ? 1 : 0;
@@ -662,6 +700,8 @@ int mkgnn_kernelsetconv_backward(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE]
                                  const mkgnn_kernel_bank_grad grads[MKGNN_MAX_DEGREE], void* workspace,
                                  size_t workspace_bytes, int32_t workspace_from_forward, int32_t variant, void* stream) {
     const char* who = "mkgnn_kernelsetconv_backward";                           // ---- check
+    GradBlocks gb;
+    const bool gb_hint = take_grad_blocks_hint(gb);                             // (taken before any return: it is this call's alone)
     const bool defer_bank = (variant & MKGNN_BACKWARD_DEFER_BANK) != 0;
     const bool through_nei = (variant & MKGNN_BACKWARD_THROUGH_NEIGHBOURS) != 0;
     const bool rows_split = (variant & MKGNN_BACKWARD_ROWS_SPLIT) != 0;         // x is pre-split (kgnn_split.h)
@@ -694,6 +734,18 @@ int mkgnn_kernelsetconv_backward(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE]
         return api_fail("%s: MKGNN_BACKWARD_ROWS_SPLIT needs the streamed kernels with split-fp16 products for every degree "
                         "(mkgnn_rows_split_supported(..) tells)", who);
     const bool fuse_bank = plan.bank_fused, rows_streamed = plan.rows_streamed, streamed = plan.bank_streamed;
+    // present blocks: the gather where the pipelined one applies and the blocks are this call's columns (whatever kernels wrote the
+    // contribution rows wrote whole rows: the masked gather reads a part of them)
+    // (the conditions under which launch_backward_gather takes the pipelined kernel: contribution rows exist -- n_edges counts their
+    // neighbour slots -- and the shapes fit; F <= 255: one byte per block table entry)
+    bool gb_gather = gb_hint && switches().grad_blocks && variant != 1 && grad_x && n_edges > 0 && F <= 255 &&
+                     backward_gather_aligned_supported((const float*)((char*)workspace + w.contrib), (F + 3) / 4 * 4, scatter_rows, x, x_stride,
+                                                       n_atoms, F, grad_x, grad_x_stride);
+    if (gb_gather) {
+        int width = 0;
+        for (int d = 1; d <= 4; ++d) width += (int)((gb.blk_len >> (8 * d)) & 0xFF);
+        gb_gather = width == F;
+    }
     // ---- fill the argument blocks
     hipStream_t st = (hipStream_t)stream; char* ws = (char*)workspace;
     BwdArgs bank_a[4];
@@ -733,6 +785,14 @@ int mkgnn_kernelsetconv_backward(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE]
     const bool any_bank = bank_use[0] || bank_use[1] || bank_use[2] || bank_use[3];
     // ---- launch: the x-gradient chain (rows kernels, then the gather) and the bank chain (bank kernels, then the reduce)
     hipError_t e = hipSuccess;
+    if (g_poison_bwd.load() && grad_x && n_atoms) {
+        int64_t rows_all = 0;
+        for (int i = 0; i < 4; ++i) rows_all += buckets[i].count * (i + 2);
+        e = hipMemsetAsync(ws + w.contrib, 0xFF, (size_t)rows_all * ((F + 3) / 4 * 4) * sizeof(float), st);
+        if (e == hipSuccess)
+            e = hipMemset2DAsync(grad_x, (size_t)grad_x_stride * sizeof(float), 0xFF, (size_t)F * sizeof(float), (size_t)n_atoms, st);
+        if (e != hipSuccess) return api_hip_fail("poison", e);
+    }
     if (!workspace_from_forward) {                   // else the normalised bank of the forward call is still there
         e = launch_bank_prepare(banks, w, ws, F, E, st);
         if (e != hipSuccess) return api_hip_fail("bank_prepare", e);
@@ -873,6 +933,11 @@ int mkgnn_kernelsetconv_backward(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE]
         if (e != hipSuccess) return api_hip_fail("zero input gradient", e);
     } else if (grad_x) {
         BwdTimer t(st, 4);
+        if (gb_gather) {
+            e = launch_backward_gather_grad_blocks((const float*)(ws + w.contrib), (F + 3) / 4 * 4, scatter_rowptr, scatter_rows, x, x_stride,
+                                                   inv_norm, n_atoms, F, grad_x, grad_x_stride, st, rows_split, gb);
+            if (e == hipSuccess) g_grad_blocks_launches.fetch_add(1);
+        } else
         e = launch_backward_gather((const float*)(ws + w.contrib), (F + 3) / 4 * 4, base, scatter_rowptr, scatter_rows, x,
                                    x_stride, inv_norm, n_atoms, F, grad_x, grad_x_stride, variant != 1, st, rows_split);
         if (e != hipSuccess) return api_hip_fail("backward gather launch", e);

@@ -45,6 +45,9 @@ struct CsrArgs {
     // sixteen bytes per four floats -- exactly what the streamed kernels' matrix instructions take
     int split_out;                         // segment sum with inv_out: the written rows are pre-split
     int x_split;                           // gather: the forward's rows x are pre-split
+    // present blocks (PM, gather only; kgnn_launch.h GradBlocks): of destination row j only the 16-byte chunks that meet a block
+    // of present8[j] are summed, used and stored (blk_off / blk_len as above; a mask of 0 = every chunk)
+    const int8_t* present8;
 };
 
 template <int LPR>
@@ -84,9 +87,16 @@ __device__ __forceinline__ f32x4 mask_cols(f32x4 v, int col, int width) {
 // adding the values of lanes l and l + LPR (the xor tree's first step, offset LPR) and goes on with offsets LPR / 2 .. 1 --
 // here the lane adds its two chunks' values itself (the same two operands; an fp32 add commutes) and group_sum<LPR> does the
 // rest.  A chunk beyond the width contributes +0 in both forms.
-template <int LPR, bool GATHER, int BLK = 0, int CPL = 1>
+//
+// PM (gather): present blocks.  Every contribution row of destination j, the row x[j] and the row gx[j] matter only in the chunks
+// that meet a block of present8[j] (one byte per destination, fetched with its row pointers like BLK = 2's degree).  A lane whose
+// chunk is absent loads the first chunk of the row's lowest present block instead -- sixteen bytes the row's other lanes fetch
+// anyway -- masks the value to +0 and stores nothing: in such a chunk x is +0, so the dot product's terms there are +0 as well,
+// and what is stored in the present chunks is computed from the operands of the plain form in its order.
+template <int LPR, bool GATHER, int BLK = 0, int CPL = 1, bool PM = false>
 __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
     static_assert(!(GATHER && BLK), "block rows: segment sums only");
+    static_assert(!PM || GATHER, "present blocks: the gather only");
     static_assert(CPL == 1 || CPL == 2, "one or two chunks per lane");
     constexpr int RPW = 64 / LPR, SEG = 4;
     static_assert(LPR >= SEG, "one index per lane of a row group");
@@ -117,6 +127,7 @@ __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
         lo = a.rowptr[(uint32_t)jc];
         hi = a.rowptr[(uint32_t)jc + 1];
         if constexpr (BLK == 2) dg = a.deg8[(uint32_t)jc];
+        if constexpr (PM) dg = a.present8[(uint32_t)jc];
         if (j >= n || g >= ngroups) hi = lo;
         return jc;
     };
@@ -149,13 +160,40 @@ __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
             }
         }
     }
+    // PM: the blocks this lane's chunks meet, and the first chunk of every block (8 bits per degree) for the lanes that redirect
+    uint32_t pm_blocks[CPL], pm_first = 0;
+    int pm_c[CPL];                                      // per group: the columns this lane loads from, and whether it keeps them
+    bool pm_keep[CPL];
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) { pm_blocks[q] = 0; pm_c[q] = colc[q]; pm_keep[q] = true; }
+    if constexpr (PM) {
+#pragma unroll
+        for (int q = 0; q < CPL; ++q) pm_blocks[q] = active[q] ? grad_blocks_of_chunk(a.blk_off, a.blk_len, col[q]) : 0u;
+#pragma unroll
+        for (int d = 1; d <= 4; ++d) {
+            int b0, b1;
+            block_of(d, b0, b1);
+            pm_first |= (uint32_t)(b0 >> 2) << (8 * (d - 1));
+        }
+    }
+    auto present_of = [&](int mask8) {
+        if constexpr (PM) {
+            const uint32_t m = (uint32_t)mask8 & 15u;
+            const uint32_t first = (pm_first >> ((8 * (uint32_t)__builtin_ctz(m | 16u)) & 31u)) & 0xFFu;     // (m == 0: not used)
+#pragma unroll
+            for (int q = 0; q < CPL; ++q) {
+                pm_keep[q] = m == 0 || (m & pm_blocks[q]) != 0;
+                pm_c[q] = pm_keep[q] ? colc[q] : (int)(first << 2);
+            }
+        }
+    };
     // A chunk whose four columns miss the block reads the nearest 16 bytes of the block instead -- the same cache
     // lines the other lanes of its row fetch, so it adds no traffic (a fixed dummy address made one hot spot of a
     // few lines that every wave hammered) -- and its value is masked / never stored.
     auto row_load = [&](int rid_raw, int dst_b0, int dst_b1, f32x4 (&v)[CPL]) {
         int row = rid_raw, c[CPL];
 #pragma unroll
-        for (int q = 0; q < CPL; ++q) c[q] = colc[q];
+        for (int q = 0; q < CPL; ++q) c[q] = PM ? pm_c[q] : colc[q];
         if constexpr (BLK == 1) {
             const uint32_t d6 = 6 * ((uint32_t)rid_raw >> 28);
             row = rid_raw & 0x0FFFFFFF;
@@ -194,7 +232,7 @@ __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
         } else {
 #pragma unroll
             for (int q = 0; q < CPL; ++q) {
-                const f32x4 w = keep_if(v[q], valid);
+                const f32x4 w = keep_if(v[q], PM ? (valid && pm_keep[q]) : valid);
                 acc[q] = first ? w : acc[q] + w;
             }
         }
@@ -232,6 +270,7 @@ __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
         dg_nn = 0;
         int d0 = 0, d1 = 0;                                // BLK == 2: the destination's block
         if constexpr (BLK == 2) block_of(dg_c, d0, d1);
+        present_of(dg_c);
         int rid_c[SEG];
         idx_bcast(mine_c, rid_c);
         f32x4 v[SEG][CPL];
@@ -242,7 +281,7 @@ __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
         if constexpr (GATHER) {
             const float* xrow = a.x + (uint64_t)(uint32_t)j_c * (uint32_t)a.xs;
 #pragma unroll
-            for (int q = 0; q < CPL; ++q) xv[q] = *(const f32x4*)(xrow + colc[q]);
+            for (int q = 0; q < CPL; ++q) xv[q] = *(const f32x4*)(xrow + (PM ? pm_c[q] : colc[q]));
             iv = a.inv[j_c];
         }
         mine_n = idx_issue(lo_n, hi_n, lo_n);
@@ -276,6 +315,7 @@ __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
             for (int q = 0; q < CPL; ++q) {
                 if (a.x_split) { xv[q] = split_row_value(xv[q]); }
                 xh[q] = mask_cols(xv[q], active[q] ? col[q] : a.width, a.width) * xscale;
+                if constexpr (PM) xh[q] = keep_if(xh[q], pm_keep[q]);
                 float dq = acc[q][0] * xh[q][0];
                 dq = fmaf(acc[q][1], xh[q][1], dq); dq = fmaf(acc[q][2], xh[q][2], dq); dq = fmaf(acc[q][3], xh[q][3], dq);
                 dotp = q == 0 ? dq : dotp + dq;                     // the tree's first step (offset LPR) of the one-chunk form
@@ -288,7 +328,7 @@ __global__ void __launch_bounds__(256) csr_rows_kernel(CsrArgs a) {
                 f32x4 r;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) r[c] = clamped ? acc[q][c] * iv : (acc[q][c] - dotp * xh[q][c]) * iv;
-                if (row_ok && active[q]) *(f32x4*)(dst + col[q]) = r;
+                if (row_ok && active[q] && (!PM || pm_keep[q])) *(f32x4*)(dst + col[q]) = r;
             }
         } else if constexpr (BLK == 2) {
             // only the destination's own block is defined; the rest of its row is left as it is
@@ -471,24 +511,24 @@ static inline int csr_chunks() {
 }
 
 // lanes_per_row(width) lanes hold a row one chunk each; with two chunks per lane half as many do
-template <bool GATHER, int BLK>
+template <bool GATHER, int BLK, bool PM = false>
 static hipError_t launch_csr_rows(const CsrArgs& a_in, hipStream_t st) {
     CsrArgs a = a_in;
     a.fixed4 = switches().csr_fixed4;
     const int lpr = lanes_per_row(a.width);
     if (csr_chunks<GATHER, BLK>() == 2) {
         switch (lpr) {
-            case 8: csr_rows_kernel<4, GATHER, BLK, 2><<<csr_grid(a.n, 16), 256, 0, st>>>(a); break;
-            case 16: csr_rows_kernel<8, GATHER, BLK, 2><<<csr_grid(a.n, 8), 256, 0, st>>>(a); break;
-            case 32: csr_rows_kernel<16, GATHER, BLK, 2><<<csr_grid(a.n, 4), 256, 0, st>>>(a); break;
-            default: csr_rows_kernel<32, GATHER, BLK, 2><<<csr_grid(a.n, 2), 256, 0, st>>>(a); break;
+            case 8: csr_rows_kernel<4, GATHER, BLK, 2, PM><<<csr_grid(a.n, 16), 256, 0, st>>>(a); break;
+            case 16: csr_rows_kernel<8, GATHER, BLK, 2, PM><<<csr_grid(a.n, 8), 256, 0, st>>>(a); break;
+            case 32: csr_rows_kernel<16, GATHER, BLK, 2, PM><<<csr_grid(a.n, 4), 256, 0, st>>>(a); break;
+            default: csr_rows_kernel<32, GATHER, BLK, 2, PM><<<csr_grid(a.n, 2), 256, 0, st>>>(a); break;
         }
     } else {
         switch (lpr) {
-            case 8: csr_rows_kernel<8, GATHER, BLK><<<csr_grid(a.n, 8), 256, 0, st>>>(a); break;
-            case 16: csr_rows_kernel<16, GATHER, BLK><<<csr_grid(a.n, 4), 256, 0, st>>>(a); break;
-            case 32: csr_rows_kernel<32, GATHER, BLK><<<csr_grid(a.n, 2), 256, 0, st>>>(a); break;
-            default: csr_rows_kernel<64, GATHER, BLK><<<csr_grid(a.n, 1), 256, 0, st>>>(a); break;
+            case 8: csr_rows_kernel<8, GATHER, BLK, 1, PM><<<csr_grid(a.n, 8), 256, 0, st>>>(a); break;
+            case 16: csr_rows_kernel<16, GATHER, BLK, 1, PM><<<csr_grid(a.n, 4), 256, 0, st>>>(a); break;
+            case 32: csr_rows_kernel<32, GATHER, BLK, 1, PM><<<csr_grid(a.n, 2), 256, 0, st>>>(a); break;
+            default: csr_rows_kernel<64, GATHER, BLK, 1, PM><<<csr_grid(a.n, 1), 256, 0, st>>>(a); break;
         }
     }
     return hipGetLastError();
@@ -533,16 +573,31 @@ bool try_segment_sum_aligned(const float* in, int64_t is, const int32_t* rowptr,
     return true;
 }
 
+bool backward_gather_aligned_supported(const float* contrib, int64_t cs, const int32_t* rows, const float* x, int64_t xs, int64_t n, int F,
+                                       const float* gx, int64_t gxs) {
+    return n > 0 && n < (1 << 30) && rows && F <= 256 && aligned_rows(contrib, cs, F) && aligned_rows(x, xs, F) && aligned_rows(gx, gxs, F);
+}
+
 bool try_backward_gather_aligned(const float* contrib, int64_t cs, const int32_t* rowptr, const int32_t* rows, const float* x,
                                  int64_t xs, const float* inv, int64_t n, int F, float* gx, int64_t gxs, hipStream_t st,
                                  hipError_t* err, bool x_split) {
-    if (n == 0 || n >= (1 << 30) || !rows || F > 256 || !aligned_rows(contrib, cs, F) || !aligned_rows(x, xs, F) || !aligned_rows(gx, gxs, F))
-        return false;
+    if (!backward_gather_aligned_supported(contrib, cs, rows, x, xs, n, F, gx, gxs)) return false;
     CsrArgs a{};
     a.src = contrib; a.ss = cs; a.rowptr = rowptr; a.idx = rows; a.n = n; a.width = F; a.out = gx; a.os = gxs;
     a.x = x; a.xs = xs; a.inv = inv; a.x_split = x_split ? 1 : 0;
     *err = launch_csr<true>(a, st);
     return true;
+}
+
+// (the caller has asked backward_gather_aligned_supported, and F <= 255)
+hipError_t launch_backward_gather_grad_blocks(const float* contrib, int64_t cs, const int32_t* rowptr, const int32_t* rows,
+                                              const float* x, int64_t xs, const float* inv, int64_t n, int F, float* gx, int64_t gxs,
+                                              hipStream_t st, bool x_split, const GradBlocks& gb) {
+    CsrArgs a{};
+    a.src = contrib; a.ss = cs; a.rowptr = rowptr; a.idx = rows; a.n = n; a.width = F; a.out = gx; a.os = gxs;
+    a.x = x; a.xs = xs; a.inv = inv; a.x_split = x_split ? 1 : 0;
+    a.present8 = gb.present8; a.blk_off = gb.blk_off; a.blk_len = gb.blk_len;
+    return launch_csr_rows<true, 0, true>(a, st);
 }
 
 // tests: the pipelined gather on buffers the caller owns (the library runs it behind mkgnn_kernelsetconv_backward only);

@@ -253,6 +253,28 @@ void plan_backward_bank_stream(const BwdArgs a4[4], const bool use[4], const flo
                                int nchunk_out[4], int ntheta_out[4], bool through_nei, BankStreamLaunch* out);
 hipError_t launch_coef_prepare(const BankStreamLaunch& p, hipStream_t st);
 hipError_t launch_backward_bank_stream(const BankStreamLaunch& p, hipStream_t st);
+// Present blocks (MKGNN_GRAD_BLOCKS; mkgnn_backward_grad_blocks): x = h = propagate(sim_sc) of the layer below is non-zero only in the
+// column blocks of its atoms' bond partners' degrees, and the only reader of d loss / d x -- that layer's backward -- reads exactly
+// those blocks.  present8[j]: the blocks of atom j (bit d - 1: some bond partner has degree d; 0 = all) -- every contribution row
+// the gather sums for j has j as its target.  blk_off / blk_len: the blocks' columns, byte d of each (CsrArgs' form).  The
+// gather skips the 16-byte chunks of the contribution rows, of x and of grad_x that meet no present block: nothing reads that part
+// of grad_x, and in the gather's dot product those chunks are multiplied by the +0 of x.  (The rows kernel writes whole rows: with
+// the same mask in its finishing pass it wrote 66 instead of 143 MB and took as long -- DESIGN 4.2.)
+struct GradBlocks { const int8_t* present8; uint64_t blk_off, blk_len; };
+bool take_grad_blocks_hint(GradBlocks& out);   // this thread's pending hint, if any (kgnn_capi.hip); clears it
+extern std::atomic<long long> g_grad_blocks_launches;        // backward calls whose gather ran on present blocks only
+#ifdef __HIPCC__
+// the blocks (bit d - 1) that meet columns col .. col + 3
+__host__ __device__ __forceinline__ uint32_t grad_blocks_of_chunk(uint64_t blk_off, uint64_t blk_len, int col) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int d = 1; d <= 4; ++d) {
+        const int b0 = (int)((blk_off >> (8 * d)) & 0xFF), b1 = b0 + (int)((blk_len >> (8 * d)) & 0xFF);
+        if (b1 > b0 && col + 3 >= b0 && col < b1) m |= 1u << (d - 1);
+    }
+    return m;
+}
+#endif
 // kgnn_bwd_rows_stream.hip: streamed MFMA rows kernel (bank in registers), all degrees in one launch
 bool rows_stream_supported(int d, int F, int E, int L);
 // coefq / nct: the pre-pass's records (null: the kernel gathers its coefficients itself)
@@ -263,6 +285,13 @@ hipError_t launch_backward_rows_mfma(int d, const BwdArgs& a, int* ntheta_out, h
 hipError_t launch_backward_gather(const float* contrib, int64_t cs, int64_t n_contrib_rows, const int32_t* rowptr,
                                   const int32_t* rows, const float* x, int64_t xs, const float* inv, int64_t n, int F,
                                   float* gx, int64_t gxs, bool allow_fast, hipStream_t st, bool x_split = false);
+// the shapes the pipelined gather takes (what try_backward_gather_aligned tests before it launches)
+bool backward_gather_aligned_supported(const float* contrib, int64_t cs, const int32_t* rows, const float* x, int64_t xs, int64_t n, int F,
+                                       const float* gx, int64_t gxs);
+// ... on present blocks only (the caller has asked backward_gather_aligned_supported; F <= 255: one byte per block table entry)
+hipError_t launch_backward_gather_grad_blocks(const float* contrib, int64_t cs, const int32_t* rowptr, const int32_t* rows,
+                                              const float* x, int64_t xs, const float* inv, int64_t n, int F, float* gx, int64_t gxs,
+                                              hipStream_t st, bool x_split, const GradBlocks& gb);
 // kgnn_csr.hip: pipelined variants for 16-byte aligned rows of <= 256 floats; false = not applicable
 bool segment_sum_blocks_supported(const float* in, int64_t is, int64_t n, int width, const float* out, int64_t os);
 hipError_t launch_segment_sum_blocks(const float* in, int64_t is, const int32_t* rowptr, const int32_t* col, const int8_t* deg8,

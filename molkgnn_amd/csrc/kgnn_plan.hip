@@ -9,6 +9,7 @@
 // whatever the atomics did, and equal to the torch builder entry for entry.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstring>
 
 #include "kgnn_common.h"
 #include "kgnn_launch.h"
@@ -149,6 +150,30 @@ __global__ void __launch_bounds__(256) plan_sort_kernel(PlanArgs a) {
     }
 }
 
+// present blocks (mkgnn_plan_present_blocks): thread i < n writes present8[i]; where the per-row array is asked for (nothing in the
+// step reads it: it is not built with the plan), thread i < r the mask of contribution row i's target.
+// An atom's in-edges are a handful of entries: every thread walks its atom's segment itself, one launch, no atomics.
+__device__ __forceinline__ int plan_present_of(const int32_t* __restrict__ in_rowptr, const int32_t* __restrict__ in_col_packed, int64_t j) {
+    int m = 0;
+    const int lo = in_rowptr[j], hi = in_rowptr[j + 1];
+    for (int k = lo; k < hi; ++k) {
+        const int d = (in_col_packed[k] >> 28) & 7;
+        if (d >= 1 && d <= 4) m |= 1 << (d - 1);
+    }
+    return m;
+}
+
+__global__ void __launch_bounds__(256) plan_present_kernel(PlanArgs a, const int32_t* __restrict__ in_rowptr,
+                                                           const int32_t* __restrict__ in_col_packed, int8_t* __restrict__ present8,
+                                                           int8_t* __restrict__ contrib_present8) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < a.n) present8[i] = in_col_packed ? (int8_t)plan_present_of(in_rowptr, in_col_packed, i) : (int8_t)0;
+    if (contrib_present8 && i < a.r) {
+        const int64_t dest = plan_row_dest(a, i);
+        contrib_present8[i] = (in_col_packed && dest >= 0 && dest < a.n) ? (int8_t)plan_present_of(in_rowptr, in_col_packed, dest) : (int8_t)0;
+    }
+}
+
 // compact wire form -> collated batch tensors (mkgnn_expand_batch): thread t < n_bonds expands bond t, thread t < n_atoms
 // finds atom t's molecule by bisection of mol_ptr
 __global__ void __launch_bounds__(256) expand_batch_kernel(const int32_t* __restrict__ bond_ij, const uint8_t* __restrict__ bond_attr,
@@ -250,5 +275,28 @@ extern "C" int mkgnn_plan_build(const mkgnn_degree_bucket buckets[MKGNN_MAX_DEGR
     if (grid) plan_count_fill_kernel<true><<<grid, 256, 0, st>>>(a);
     plan_sort_kernel<<<(unsigned)((3 * n_atoms + 255) / 256), 256, 0, st>>>(a);
     e = hipGetLastError();
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+extern "C" int mkgnn_plan_present_blocks(const mkgnn_degree_bucket buckets[MKGNN_MAX_DEGREE], int64_t n_atoms, const int32_t* in_rowptr,
+                                         const int32_t* in_col_packed, int8_t* present8, int8_t* contrib_present8, void* stream) {
+    const char* who = "mkgnn_plan_present_blocks";
+    if (!buckets || n_atoms < 0) return api_fail("%s: bad arguments", who);
+    PlanArgs a;
+    memset(&a, 0, sizeof(a));
+    int64_t r = 0;
+    for (int d = 0; d < 4; ++d) {
+        a.sel[d] = buckets[d].selected_index; a.nei[d] = buckets[d].nei_index; a.count[d] = buckets[d].count;
+        if (a.count[d] < 0 || (a.count[d] > 0 && (!a.sel[d] || !a.nei[d]))) return api_fail("%s: degree %d bucket", who, d + 1);
+        a.row_base[d] = r;
+        r += a.count[d] * (d + 2);
+    }
+    a.row_base[4] = r;
+    a.n = n_atoms; a.r = r;
+    if ((n_atoms > 0 && !present8) || (in_col_packed && !in_rowptr)) return api_fail("%s: null pointer", who);
+    const int64_t work = (contrib_present8 && r > n_atoms) ? r : n_atoms;
+    if (work == 0) return 0;
+    plan_present_kernel<<<(unsigned)((work + 255) / 256), 256, 0, (hipStream_t)stream>>>(a, in_rowptr, in_col_packed, present8, contrib_present8);
+    const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }

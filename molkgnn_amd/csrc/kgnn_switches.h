@@ -32,6 +32,7 @@ struct Switches {        // (bool: is set, or on unless the value starts with '0
     bool fwd_stream;          // MKGNN_FWD_STREAM=0: round 1's LDS-bank forward kernel, not the streamed one
     bool bf16_stream;         // MKGNN_BF16_STREAM=0: the bf16 forward variant stays on the LDS-bank kernel
     bool rows_split;          // MKGNN_ROWS_SPLIT=0: mkgnn_rows_split_supported answers 0 (no pre-split rows)
+    bool grad_blocks;         // MKGNN_GRAD_BLOCKS=0: mkgnn_backward_grad_blocks is ignored (the backward writes whole rows of d loss / d h)
     int tail_project_in_prepass;    // MKGNN_TAIL_PROJECT_IN_PREPASS: 0 = the fused tail's d sim projection stays a launch of its own (A/B);
                                     //   1 = its dW1 half on the helper stream behind the pre-pass's fork, in front of the deferred reduction;
                                     //   2 (unset) = the helper forked in front of the pre-pass for it: it runs beside the pre-pass
@@ -61,7 +62,7 @@ inline const Switches& switches() {
         s.serial = is_set("MKGNN_SERIAL"); s.fork_in_graph = is_set("MKGNN_FORK_IN_GRAPH"); s.no_mfma_bwd = is_set("MKGNN_NO_MFMA_BWD");
         s.fork_mode = not_0("MKGNN_FORK_MODE"); s.bank_fused = not_0("MKGNN_BANK_FUSED"); s.rows_stream = not_0("MKGNN_ROWS_STREAM");
         s.bank_stream = not_0("MKGNN_BANK_STREAM"); s.fwd_stream = not_0("MKGNN_FWD_STREAM"); s.bf16_stream = not_0("MKGNN_BF16_STREAM");
-        s.rows_split = not_0("MKGNN_ROWS_SPLIT"); s.tail_project_in_prepass = number("MKGNN_TAIL_PROJECT_IN_PREPASS", 2);
+        s.rows_split = not_0("MKGNN_ROWS_SPLIT"); s.grad_blocks = not_0("MKGNN_GRAD_BLOCKS"); s.tail_project_in_prepass = number("MKGNN_TAIL_PROJECT_IN_PREPASS", 2);
         if (const char* e = getenv("MKGNN_BN_ONE_LAUNCH")) s.bn_one_launch = e[0] == '1';
         if (const char* e = getenv("MKGNN_HELPER_PRIORITY")) s.helper_priority = e[0];
         s.fwd_pp = number("MKGNN_FWD_PP", MKGNN_FWD_PP_DEFAULT); s.fwd_pp_env = number("MKGNN_FWD_PP", 0) != 0;

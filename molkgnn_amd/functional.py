@@ -151,6 +151,49 @@ def mark_rows_split(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
+# Present blocks (csrc/kgnn_launch.h GradBlocks): h = propagate(sim_sc) between two layers is structurally zero outside the column
+# blocks of every atom's bond partners' degrees (plan.present8), and the backward of the operator that made it reads d loss / d h
+# in exactly those blocks.  A producer whose h only the next layer reads tags it: *the gradient of this tensor is read in its
+# present blocks only; block layout = the producing layer's L*.  A consumer that understands the tag (kernelsetconv's fast
+# backward: its gather) then writes nothing else; any other consumer computes the whole gradient, which is a superset.  The tag
+# travels like the row norms and the pre-split mark: an attribute with the version counter, lost by an in-place change or a
+# detached copy, and void where somebody else will see the gradient (a hook on the tensor, ``retain_grad``, anomaly detection).  MKGNN_GRAD_BLOCKS=0 (read once, here and in the library): nobody sets or takes it.
+_GRAD_BLOCKS_ATTR = "_mkgnn_grad_blocks"
+GRAD_BLOCKS = os.environ.get("MKGNN_GRAD_BLOCKS", "1")[:1] != "0"
+
+
+def mark_grad_blocks(h: torch.Tensor, plan: BatchPlan, blocks) -> torch.Tensor:
+    """Tag ``h`` (see above).  Only for a tensor that is never handed out: ``MolGCN.forward`` asks for it between two layers."""
+    if GRAD_BLOCKS and h.is_cuda and plan.edge_index is not None:
+        setattr(h, _GRAD_BLOCKS_ATTR, (h._version, plan, tuple(int(v) for v in blocks)))
+    return h
+
+
+def grad_blocks_of(x: torch.Tensor, plan: BatchPlan):
+    """The block widths a valid tag on ``x`` carries for a consumer working on ``plan``, else None."""
+    tag = getattr(x, _GRAD_BLOCKS_ATTR, None)
+    if tag is None or not GRAD_BLOCKS:
+        return None
+    version, tag_plan, blocks = tag
+    if version != x._version or tag_plan is not plan or sum(blocks) != x.shape[1]:
+        return None
+    # a hook on the tensor, or a retained gradient, is another reader of the gradient: it gets whole rows -- and so does anomaly
+    # detection, which looks at every returned gradient (what is left unwritten may hold NaN bit patterns)
+    if getattr(x, "_backward_hooks", None) or x.retains_grad or torch.is_anomaly_enabled():
+        return None
+    return blocks
+
+
+def debug_grad_blocks_launches() -> int:
+    """Backward calls since the library was loaded whose gather ran on present blocks only."""
+    return int(_lib.load().mkgnn_debug_grad_blocks_launches())
+
+
+def debug_poison_backward(on: bool) -> None:
+    """Tests: every ``kernelsetconv`` backward fills its contribution rows and its input gradient with NaN before its first launch."""
+    _lib.check(_lib.load().mkgnn_debug_poison_backward(int(bool(on))), "mkgnn_debug_poison_backward")
+
+
 def presplit_rows(x: torch.Tensor) -> torch.Tensor:
     """``x`` rewritten as pre-split rows (``mkgnn_rows_presplit``), with its row norms attached: what ``kernelsetconv`` receives
     from the layer before it inside a model.  For benchmarks and tests that time or check a single layer on the operand form
@@ -204,6 +247,8 @@ def plan_touch_list(plan: BatchPlan) -> List[torch.Tensor]:
                 out.append(bk._e_unit)
     if plan._csr_in_packed is not None:
         out += [t for t in plan._csr_in_packed if t is not None]
+    if plan._present8 is not None:
+        out.append(plan._present8)                       # (the backward gathers': last, dropped first)
     return [t for t in out if t.is_cuda and t.numel() * t.element_size() >= 4096][:16]
 
 
@@ -482,6 +527,8 @@ class _KernelSetConvFn(torch.autograd.Function):
                 propagate, prepared, *params):
         need_grad = any(ctx.needs_input_grad) and getattr(_CALL, "grad_enabled", True)
         ctx.bwd_variant = int(bwd_variant)
+        # x is a tagged h: its gradient is read in the present blocks only (the fast backward's gather writes nothing else)
+        ctx.grad_blocks = grad_blocks_of(x, plan) if (need_grad and bwd_variant != BACKWARD_VARIANTS["generic"]) else None
         x, out_full, inv, saved_t, Ls, ws, x_split = _forward_impl(x, plan, is_last_layer, variant, out_pad, E, params, need_grad,
                                                                    inv, prepared)
         ctx.x_split = x_split
@@ -583,16 +630,28 @@ class _KernelSetConvFn(torch.autograd.Function):
                 # because .grad holds it)
                 _Deferred.held.append((x, inv, g, ws, ctx.saved_t, plan, params, [t for t in alive if t is not None and
                                                                                  all(t is not q for q in gparams)]))
+            hinted = ctx.grad_blocks is not None and gx is not None
+            present = plan.present8 if hinted else None
             if _USE_TORCH_OPS:
                 ps, bkl, counts, sv = _op_lists(plan, params, E, False, ctx.saved_t, dev)
-                _lib.load_torch_ops().kernelsetconv_backward(x, inv, ps, bkl, counts, E, bool(ctx.is_last), g, sv, rowptr, rows, gx,
-                                                             list(alive), ws, bool(reuse), bwd_variant)
-            else:
-                _lib.check(lib.mkgnn_kernelsetconv_backward(
-                    banks, buckets, x.data_ptr(), _stride0(x), inv.data_ptr(), n, F, E, int(ctx.is_last),
-                    g.data_ptr(), _stride0(g), saved, rowptr.data_ptr(), rows.data_ptr(),
-                    _lib.ptr(gx), F4, grads, ws.data_ptr(), ws_bytes, int(reuse), bwd_variant, _lib.stream_ptr(dev)),
-                    "mkgnn_kernelsetconv_backward")
+            try:
+                if hinted:
+                    # a thread-local hint that the library call right below takes (it decides whether its gather honours it);
+                    # should the call not be reached, the hint is withdrawn: it must never meet another call's x
+                    _lib.check(lib.mkgnn_backward_grad_blocks(present.data_ptr(), _lib.Int32x4(*ctx.grad_blocks)),
+                               "mkgnn_backward_grad_blocks")
+                if _USE_TORCH_OPS:
+                    _lib.load_torch_ops().kernelsetconv_backward(x, inv, ps, bkl, counts, E, bool(ctx.is_last), g, sv, rowptr, rows, gx,
+                                                                 list(alive), ws, bool(reuse), bwd_variant)
+                else:
+                    _lib.check(lib.mkgnn_kernelsetconv_backward(
+                        banks, buckets, x.data_ptr(), _stride0(x), inv.data_ptr(), n, F, E, int(ctx.is_last),
+                        g.data_ptr(), _stride0(g), saved, rowptr.data_ptr(), rows.data_ptr(),
+                        _lib.ptr(gx), F4, grads, ws.data_ptr(), ws_bytes, int(reuse), bwd_variant, _lib.stream_ptr(dev)),
+                        "mkgnn_kernelsetconv_backward")
+            finally:
+                if hinted:
+                    lib.mkgnn_backward_grad_blocks(None, None)       # (no-op where the call took it)
         del alive           # (freed memory is only handed out again in stream order, after the kernels above)
         return (gx, None, None, None, None, None, None, None, None, None, *gparams)
 
@@ -604,7 +663,7 @@ _BLOCKS_ATTR = "_mkgnn_block_rows"
 def kernelsetconv(x: torch.Tensor, plan: BatchPlan, is_last_layer: bool, params: Sequence[torch.Tensor],
                   edge_attr_dim: int, variant: str = "auto", out_pad: Optional[int] = None,
                   block_rows: bool = False, backward_variant: Optional[str] = None, propagate: bool = False,
-                  prepared: Optional[PreparedBank] = None) -> torch.Tensor:
+                  prepared: Optional[PreparedBank] = None, grad_blocks: bool = False) -> torch.Tensor:
     """``[N, F] -> [N, K]`` kernel convolution over the four degree buckets of ``plan``.
 
     ``params`` is the flat list, degree 1..4, of (x_center, x_support,
@@ -616,7 +675,8 @@ def kernelsetconv(x: torch.Tensor, plan: BatchPlan, is_last_layer: bool, params:
 
     ``propagate=True`` (with ``block_rows=True``) returns ``h = propagate_add(sim_sc)`` instead of ``sim_sc``: convolution and
     neighbour sum as one operator, whose backward skips the propagate step's own gradient pass where the kernels can fold
-    it in.  ``block_rows=True`` is for a caller that hands the result straight to ``propagate_add`` (as ``MolGCN.forward``
+    it in; ``grad_blocks=True`` tags that ``h`` (``mark_grad_blocks``) for a caller that hands it to the next layer and to
+    nobody else.  ``block_rows=True`` is for a caller that hands the result straight to ``propagate_add`` (as ``MolGCN.forward``
     does): only every atom's own column block is written -- the zeros elsewhere are implied, nothing reads them --
     and the gradient it gets back is defined only there.  The tensor carries the block sizes for ``propagate_add``.
     """
@@ -635,6 +695,8 @@ def kernelsetconv(x: torch.Tensor, plan: BatchPlan, is_last_layer: bool, params:
         setattr(h, _INV_ATTR, (inv_h, h._version))
         if propagate == "split":
             mark_rows_split(h)
+        if grad_blocks:
+            mark_grad_blocks(h, plan, [int(p.shape[0]) for p in params[0::7]])
         return h
     out = _KernelSetConvFn.apply(x, plan, is_last_layer, VARIANTS[variant] | (BLOCK_ROWS if block_rows else 0), out_pad,
                                  edge_attr_dim, _handed_inv_norm(x), BACKWARD_VARIANTS[backward_variant], False, prepared,
@@ -722,11 +784,14 @@ def _segment_sum(v: torch.Tensor, csr, out_pad: int, inv: Optional[torch.Tensor]
     return out[:, :w] if out_pad else out
 
 
-def propagate_add(sim_sc: torch.Tensor, plan: BatchPlan, out_pad: int = 0) -> torch.Tensor:
+def propagate_add(sim_sc: torch.Tensor, plan: BatchPlan, out_pad: int = 0, grad_blocks: bool = False) -> torch.Tensor:
     """MolGCN.propagate with aggr='add'.  The kernel also emits ``1 / max(||h_n||, 1e-8)``; it rides on the
     returned tensor so that the next kernel convolution does not make another pass over ``h`` for it.
-    A ``sim_sc`` made by ``kernelsetconv(..., block_rows=True)`` is summed block by block (5x fewer bytes per edge)."""
+    A ``sim_sc`` made by ``kernelsetconv(..., block_rows=True)`` is summed block by block (5x fewer bytes per edge);
+    ``grad_blocks=True`` tags the ``h`` of such block rows (``mark_grad_blocks``: the next layer is its only reader)."""
     blocks = getattr(sim_sc, _BLOCKS_ATTR, None)
     h, inv = _SegmentSumFn.apply(sim_sc, plan, out_pad, blocks)
     setattr(h, _INV_ATTR, (inv, h._version))
+    if grad_blocks and blocks is not None:           # (block rows only: their backward reads the present blocks of d h)
+        mark_grad_blocks(h, plan, blocks)
     return h

@@ -218,12 +218,13 @@ class BaseKernelSetConv(Module):
         return all(k is not None for k in self.trainable_kernelconv_set) and all(k is None for k in self.fixed_kernelconv_set)
 
     def _run(self, x, plan: BatchPlan, is_last_layer, save_score=False, block_rows=False, fuse_propagate=False, prepared=None,
-             split_next=False):
+             split_next=False, grad_blocks=False):
         """``sim_sc`` of this layer; with ``fuse_propagate`` (and block rows applicable) ``(h, True)`` where
         ``h = propagate(sim_sc)`` came out of the same operator (functional.kernelsetconv(propagate=True)), else
         ``(sim_sc, False)``.  ``split_next``: the only reader of that ``h`` is a layer that takes pre-split rows
-        (``_accepts_split_rows``): it is written in that form (functional.ROWS_SPLIT)."""
-        out = self._run_impl(x, plan, is_last_layer, save_score, block_rows, fuse_propagate, prepared, split_next)
+        (``_accepts_split_rows``): it is written in that form (functional.ROWS_SPLIT).  ``grad_blocks``: that ``h`` goes to the
+        next layer and nowhere else -- it is tagged (functional.mark_grad_blocks)."""
+        out = self._run_impl(x, plan, is_last_layer, save_score, block_rows, fuse_propagate, prepared, split_next, grad_blocks)
         return out if fuse_propagate else out[0]
 
     def _accepts_split_rows(self, plan: BatchPlan, template: torch.Tensor) -> bool:
@@ -258,7 +259,8 @@ class BaseKernelSetConv(Module):
         return Fn.kernelsetconv(x, plan, is_last_layer, params, E, self.variant, self.out_pad, block_rows=True,
                                 backward_variant=self.backward_variant, prepared=prepared)
 
-    def _run_impl(self, x, plan: BatchPlan, is_last_layer, save_score, block_rows, fuse_propagate, prepared=None, split_next=False):
+    def _run_impl(self, x, plan: BatchPlan, is_last_layer, save_score, block_rows, fuse_propagate, prepared=None, split_next=False,
+                  grad_blocks=False):
         for d in range(1, 5):
             if plan.buckets[d - 1].count and self.fixed_kernelconv_set[d - 1] is None \
                     and self.trainable_kernelconv_set[d - 1] is None:
@@ -273,7 +275,7 @@ class BaseKernelSetConv(Module):
             if block_rows and fuse_propagate:
                 return Fn.kernelsetconv(x, plan, is_last_layer, params, E, self.variant, self.out_pad, block_rows=True,
                                         backward_variant=self.backward_variant, propagate="split" if split_next else True,
-                                        prepared=prepared), True
+                                        prepared=prepared, grad_blocks=grad_blocks), True
             sc = Fn.kernelsetconv(x, plan, is_last_layer, params, E, self.variant, self.out_pad, block_rows=block_rows,
                                   backward_variant=self.backward_variant, prepared=prepared)
         else:

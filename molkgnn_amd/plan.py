@@ -89,6 +89,8 @@ class BatchPlan:
         self._csr_out = None
         self._deg8 = None
         self._csr_in_packed = None
+        self._present8 = None       # present blocks (mkgnn_plan_present_blocks): per atom, built with the plan
+        self._contrib_present8 = None   # ... per contribution row: nothing in the step reads it -- made on first request
         self._ready = None          # event of a build still running on the index stream (build_hip)
         self._build_ws = None
 
@@ -130,6 +132,7 @@ class BatchPlan:
         s_ptr, s_rows = i32(n + 1), i32(r)
         in_ptr, in_col, in_pk, out_ptr, out_col = i32(n + 1), i32(m), i32(m), i32(n + 1), i32(m)
         deg8 = torch.empty(max(n, 1), dtype=torch.int8, device=dev)
+        pres8 = torch.empty(max(n, 1), dtype=torch.int8, device=dev)
         with torch.cuda.device(dev):
             nbytes = int(lib.mkgnn_plan_workspace_bytes(n, m, r))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -141,6 +144,10 @@ class BatchPlan:
                 _lib.check(lib.mkgnn_plan_build(bk, n, _lib.ptr(ei), m, s_ptr.data_ptr(), s_rows.data_ptr(), in_ptr.data_ptr(),
                                                 in_col.data_ptr(), in_pk.data_ptr(), out_ptr.data_ptr(), out_col.data_ptr(),
                                                 deg8.data_ptr(), ws.data_ptr(), nbytes, _lib.stream_ptr(dev)), "mkgnn_plan_build")
+                # (one more launch behind the builder, on the same stream: beside the first convolution, not in front of it)
+                _lib.check(lib.mkgnn_plan_present_blocks(bk, n, in_ptr.data_ptr(), in_pk.data_ptr() if ei is not None else None,
+                                                         pres8.data_ptr(), None, _lib.stream_ptr(dev)),
+                           "mkgnn_plan_present_blocks")
                 if side is not None:
                     self._ready = torch.cuda.Event()
                     self._ready.record(side)
@@ -150,12 +157,13 @@ class BatchPlan:
                         # exception) hands these blocks back to the allocator of the CALLER's stream, whose next allocation --
                         # the next batch's builder -- would overwrite the workspace under the kernels still running here
                         # (seen as a GPU memory fault once in a few hundred batches).  The allocator now waits for this stream.
-                        for t in (ws, ei, s_ptr, s_rows, in_ptr, in_col, in_pk, out_ptr, out_col, deg8,
+                        for t in (ws, ei, s_ptr, s_rows, in_ptr, in_col, in_pk, out_ptr, out_col, deg8, pres8,
                                   *[x for b in self.buckets if b.count for x in (b.sel, b.nei)]):
                             if t is not None and t.is_cuda:
                                 t.record_stream(side)
         self._scatter = (s_ptr, s_rows[:r])
         self._deg8 = deg8[:n]
+        self._present8 = pres8[:n]
         if self.edge_index is not None:
             self._csr_in, self._csr_out = (in_ptr, in_col[:m]), (out_ptr, out_col[:m])
             self._csr_in_packed = (in_ptr, in_pk[:m])
@@ -167,6 +175,7 @@ class BatchPlan:
         if self.device.type != "cuda" or self._scatter is not None:
             return self._scatter is not None
         self._scatter, self._deg8 = parts["scatter"], parts["deg8"]
+        self._present8 = parts.get("present8")
         if self.edge_index is not None:
             self._csr_in, self._csr_out, self._csr_in_packed = parts["csr_in"], parts["csr_out"], parts["csr_in_packed"]
         self._build_ws = parts.get("keep")
@@ -177,7 +186,7 @@ class BatchPlan:
             self._ready.record(side)
             if not torch.cuda.is_current_stream_capturing():
                 keep = parts.get("keep") or ()
-                for t in (*self._scatter, self._deg8, *(self._csr_in or ()), *(self._csr_out or ()), *(self._csr_in_packed or ()),
+                for t in (*self._scatter, self._deg8, self._present8, *(self._csr_in or ()), *(self._csr_out or ()), *(self._csr_in_packed or ()),
                           *[x for x in keep if torch.is_tensor(x)]):
                     if t is not None and t.is_cuda:
                         t.record_stream(side)
@@ -262,6 +271,59 @@ class BatchPlan:
             packed = col | (self.deg8[col.long()].to(torch.int32) << 28)
             self._csr_in_packed = (rowptr, packed.contiguous())
         return self._csr_in_packed
+
+    # -- present blocks: where h = propagate(sim_sc) is not structurally zero, and its gradient is read -----
+    def _present_torch(self):
+        d8 = self.deg8.long()
+        present = torch.zeros(self.n_atoms, dtype=torch.int64, device=self.device)
+        if self.edge_index is not None and self.edge_index.numel():
+            src, dst = self.edge_index[0].long(), self.edge_index[1].long()
+            ds = d8[src]
+            for d in range(1, MAX_DEGREE + 1):
+                present[dst[ds == d]] |= 1 << (d - 1)
+        dest = [torch.cat([b.sel.view(-1, 1), b.nei.view(b.count, b.degree)], dim=1).reshape(-1) for b in self.buckets if b.count]
+        dest = torch.cat(dest) if dest else torch.zeros(0, dtype=torch.long, device=self.device)
+        self._present8, self._contrib_present8 = present.to(torch.int8), present[dest].to(torch.int8)
+
+    @property
+    def present8(self):
+        """[n_atoms] int8: the column blocks of ``h = propagate(sim_sc)`` that are not structurally zero in row ``j`` -- bit
+        ``d - 1`` is set when some bond partner of ``j`` (an edge ``s -> j``) is in degree bucket ``d``; the blocks of
+        ``d loss / d h[j]`` the layer below reads.  0: an atom no such edge ends in."""
+        if self._present8 is None:
+            self.build_hip()
+        self._await()
+        if self._present8 is None:
+            self._present_torch()
+        return self._present8
+
+    @property
+    def contrib_present8(self):
+        """[contribution rows] int8: ``present8`` of every contribution row's target (rows numbered as in ``scatter``): what a
+        mask on the producer of the contribution rows would read.  No kernel of the step reads it (the gather needs the
+        destination's mask only), so it is not built with the plan: made on the first request, on the current stream."""
+        if self._contrib_present8 is None:
+            present = self.present8                      # (builds and joins the plan)
+            if self.device.type == "cuda" and not os.environ.get("MKGNN_TORCH_PLAN"):
+                from . import _lib
+                bk = _lib.Buckets4()
+                for i, b in enumerate(self.buckets):
+                    bk[i].count = b.count
+                    if b.count:
+                        bk[i].selected_index, bk[i].nei_index = b.sel.data_ptr(), b.nei.data_ptr()
+                r = sum(b.count * (b.degree + 1) for b in self.buckets)
+                packed = self._csr_in_packed if self.edge_index is not None else None
+                again = torch.empty_like(present)        # (the per-atom array once more: the one in use is not written twice)
+                rows = torch.empty(max(r, 1), dtype=torch.int8, device=self.device)
+                with torch.cuda.device(self.device):
+                    _lib.check(_lib.load().mkgnn_plan_present_blocks(
+                        bk, self.n_atoms, None if packed is None else packed[0].data_ptr(),
+                        None if packed is None else packed[1].data_ptr(), again.data_ptr(), rows.data_ptr(),
+                        _lib.stream_ptr(self.device)), "mkgnn_plan_present_blocks")
+                self._contrib_present8 = rows[:r]
+            else:
+                self._present_torch()
+        return self._contrib_present8
 
     def block_rows_ok(self, K: int) -> bool:
         """Can propagate run on block rows (``functional.propagate_add(..., blocks=...)``) for this batch?"""

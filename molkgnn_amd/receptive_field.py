@@ -240,6 +240,9 @@ def build_index_hip(x: torch.Tensor, p: torch.Tensor, edge_index: torch.Tensor, 
                                          deg8.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes,
                                          None if rf_event is None else rf_event.cuda_event, _lib.stream_ptr(dev)),
                    "mkgnn_index_build")
+        pres8 = torch.empty(n, dtype=torch.int8, device=dev)
+        _lib.check(lib.mkgnn_plan_present_blocks(buckets, n, in_ptr.data_ptr(), in_pk.data_ptr(), pres8.data_ptr(), None,
+                                                 _lib.stream_ptr(dev)), "mkgnn_plan_present_blocks")
     for d in range(1, MAX_DEGREE + 1):
         if d not in raw:                         # shapes of the reference's empty fields (wrapper.py:627-630)
             out[f"p_focal_deg{d}"] = p.new_zeros((0, p.shape[1]))
@@ -257,7 +260,7 @@ def build_index_hip(x: torch.Tensor, p: torch.Tensor, edge_index: torch.Tensor, 
         out[f"selected_index_deg{d}"] = sel
         out[f"nei_index_deg{d}"] = nei
     parts = {"scatter": (s_ptr, s_rows[:r]), "deg8": deg8, "csr_in": (in_ptr, in_col[:m]), "csr_out": (out_ptr, out_col[:m]),
-             "csr_in_packed": (in_ptr, in_pk[:m]), "keep": (ws, ei, pf, ea, buckets)}
+             "csr_in_packed": (in_ptr, in_pk[:m]), "present8": pres8, "keep": (ws, ei, pf, ea, buckets)}
     return out, parts
 
 
