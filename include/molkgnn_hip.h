@@ -457,6 +457,42 @@ int mkgnn_debug_tail_projection_launches(int64_t out[3]);
  * workspace: mkgnn_tail_score_workspace_bytes (the z rows only; a mkgnn_tail_workspace_bytes buffer is large enough). */
 size_t mkgnn_tail_score_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols);
 int mkgnn_tail_score(const mkgnn_tail_args* args, void* workspace, size_t workspace_bytes, void* stream);
+/* Monte Carlo dropout on the forward-only tail (additive; the ABI version stays 8): n_samples stochastic predictions of every
+ * molecule -- evaluation-mode inputs, both dropouts left on -- with their mean, spread and an acquisition value, in TWO launches:
+ * z = W1 sim on the matrix cores, then ONE middle kernel.  Both dropouts sit behind the last convolution, so per chunk of
+ * molecules the window, the propagate step and swish run once; only what lies behind the masks runs per sample (with
+ * readout_dropout_p == 0 only the head's mask and its row sum do; pool and lin2 run once).  No atomics, one writer per output,
+ * no process-wide or thread-local state: the call is capturable.
+ * The sample convention: sample s, 0 <= s < n_samples, uses the generator pair {seed, offset + s} of rng_pair ({seed, offset},
+ * int64 on the device; READ, nothing is advanced).  The readout's elements are 2^62 + atom * H + h, the head's mol * G + j, the
+ * keep rule the one of the readout dropout mask convention above.  samples[g * samples_stride + s] is BIT FOR BIT the pred[g]
+ * that mkgnn_tail_fused_readout_dropout writes for the same inputs, the same two probabilities (args->dropout_p, the head's;
+ * readout_dropout_p) and generator state {seed, offset + s}; with both probabilities 0 every sample is mkgnn_tail_score's pred.
+ * A molecule's samples are sums over its own atoms in a fixed order under masks that are functions of (seed, offset + s, atom, h)
+ * and (seed, offset + s, mol, j): their bits do not depend on chunking, on the grid, or on padding atoms and molecules appended
+ * behind the real ones.
+ * The statistics, per molecule from its samples x_0 .. x_{S-1} in sample order, every step one IEEE round-to-nearest float32
+ * operation (no fused multiply-add), so that float32 arithmetic on the host reproduces them bit for bit:
+ *     sum = +0;  sum = sum + x_s;   mean = sum / S;   q = +0;  d = x_s - mean;  q = q + d * d;
+ *     std = S > 1 ? sqrt(q / (S - 1)) : 0  (unbiased);      acq = alpha * mean + beta * std   (two products, one sum)
+ * Takes mkgnn_tail_args as mkgnn_tail_score does and reads the same fields, and dropout_p.  args->pred [n_loss_mols] and args->emb
+ * are each optional here (NULL: not wanted); when given they receive exactly what mkgnn_tail_score writes, bit for bit.
+ * rng_state, rng_used, target, loss, grad_*, out_*, defer_reduce and loss_kind are ignored.  Every pointer of `out` may be NULL;
+ * with samples == NULL no [n, S] buffer exists anywhere (a chunk's samples live in LDS).
+ * Limits: those of mkgnn_tail_score; 1 <= n_samples <= MKGNN_TAIL_MC_MAX_SAMPLES; both probabilities in [0, 1);
+ * samples_stride >= n_samples.  Bad arguments, a NULL rng_pair or out and a workspace that is too small are refused before any
+ * launch.  A molecule beyond MKGNN_TAIL_MAX_ATOMS / MKGNN_TAIL_MAX_EDGES gets NaN in every output of its row (samples, mean, std,
+ * acq, pred, emb), the others their values.  A reduction or projection that a mkgnn_tail_fused call left pending is launched
+ * first, as mkgnn_tail_score does.  workspace: mkgnn_tail_score_mc_workspace_bytes (the z rows). */
+#define MKGNN_TAIL_MC_MAX_SAMPLES 64
+typedef struct mkgnn_tail_mc_out {
+    float* samples; int64_t samples_stride;   /* [n_loss_mols, S] or NULL */
+    float* mean; float* std; float* acq;      /* [n_loss_mols] each, or NULL */
+    float alpha, beta;                        /* acq = alpha * mean + beta * std */
+} mkgnn_tail_mc_out;
+size_t mkgnn_tail_score_mc_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols);
+int mkgnn_tail_score_mc(const mkgnn_tail_args* args, float readout_dropout_p, int32_t n_samples, const int64_t* rng_pair,
+                        const mkgnn_tail_mc_out* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* (additive; the ABI version stays 8) Every atom's exact share of every logit of the head, in evaluation mode -- why a molecule
  * scores what it scores.  Behind the last kernel convolution lin2, the add-pool and the head are linear, so with

@@ -77,7 +77,7 @@ class MolKGNNNet(torch.nn.Module):
         src = data.edge_index[0]
         return (ea, bn, src if src.is_contiguous() else src.contiguous(), nv)
 
-    def forward(self, *argv, save_score=False, _tail=None, _score=None, _atoms=None):
+    def forward(self, *argv, save_score=False, _tail=None, _score=None, _atoms=None, _mc=None):
         if len(argv) != 1:
             # the reference's 33-positional-argument form reads ``data`` afterwards and cannot work
             # (MolKGNNNet.py:70-89 then :115); only the single-``data`` form is meaningful
@@ -86,7 +86,7 @@ class MolKGNNNet(torch.nn.Module):
         # small batches (the reference's own regime, README.md:81): batch norm, every layer and the readout in ONE launch, a
         # workgroup per chunk of whole molecules (molkgnn_amd.molecule); None where the model or the batch does not qualify
         # (_atoms: the per-atom contributions are asked for -- the molecule-resident step sums them away inside LDS)
-        if data.x.is_cuda and not save_score and _atoms is None:
+        if data.x.is_cuda and not save_score and _atoms is None and _mc is None:
             from . import molecule as _mol
             emb = _mol.net_forward(self, data)
             if emb is not None:                          # (edge_batch_norm's statistics moved inside: molecule.net_forward)
@@ -149,8 +149,20 @@ class MolKGNNNet(torch.nn.Module):
             # with grad mode off and no readout dropout to draw, i.e. in evaluation mode)
             want_score = (_score is not None and R._FUSED_TAIL and R._SCORE_TAIL and not torch.is_grad_enabled() and p_readout == 0.0
                           and x.is_cuda and R.tail_supported(*dims, Ls))
+            # (private: train.GNNModel.predict_mc asks for Monte Carlo dropout samples -- readout.tail_score_mc, next to _score and
+            # under its conditions, with one difference: the readout's drop_ratio, which evaluation mode switches off, is handed
+            # on (it must be < 1).  _mc = None asks for nothing; a tuple (ffn, n_rows, n_samples, p_head, alpha, beta,
+            # return_samples) for the kernel route where it applies; and where it does not, or for _mc = (), the caller gets
+            # ("h", the last layer's propagated output) for its PyTorch route.)
+            want_mc = (bool(_mc) and R._FUSED_TAIL and R._SCORE_MC and not torch.is_grad_enabled() and p_readout == 0.0
+                       and self.dropout.p < 1.0 and x.is_cuda and not save_score and R.tail_supported(*dims, Ls))
             want = x.is_cuda and not save_score and (_PROJECT_FIRST == '1' or (_PROJECT_FIRST != '0' and (
                 x.shape[0] >= _PROJECT_FIRST_ATOMS or not R.readout_supported(*dims) or want_tail or want_score)))
+            if _mc is not None:                          # (block rows where the kernel takes them, h otherwise: nothing else)
+                want = want_mc
+                if want and seg is None:
+                    seg = R.molecule_segments(data.batch, getattr(data, 'num_graphs', None))
+                want = want and seg.sorted and seg.size > 0 and R._tail_limits_ok(seg, plan0)
             # (private: train.GNNModel.atom_contributions asks for every atom's share of every output of the head `_atoms` --
             # readout.atom_contributions, from the block rows, where that applies, else from h through PyTorch operators; it
             # needs no molecule segments, so none are derived, and it alone decides which of the two the last layer leaves)
@@ -174,6 +186,13 @@ class MolKGNNNet(torch.nn.Module):
                 sim_sc, plan, Ls = blocks_out[0]
                 return R.atom_contributions(sim_sc, plan, Ls, lin1, lin2, _atoms)
             return R.atom_contributions_torch(node_representation, lin1, lin2, _atoms)
+        if _mc is not None:
+            if node_representation is not None:
+                return ("h", node_representation)
+            sim_sc, plan, Ls = blocks_out[0]
+            ffn, n_rows, n_samples, p_head, alpha, beta, return_samples = _mc
+            return ("mc", R.tail_score_mc(sim_sc, plan, Ls, lin1, lin2, ffn, seg, n_samples, p_head, self.dropout.p, n_rows,
+                                          alpha, beta, return_samples=return_samples, return_pred=True))
         if node_representation is None:                     # the last propagate was left to the readout
             sim_sc, plan, Ls = blocks_out[0]
             # (private: train.GNNModel.loss asks for the loss itself -- readout, head, loss and all their gradients in one

@@ -133,6 +133,14 @@ class TailArgs(C.Structure):
 
 
 TAIL_MAX_ATOMS, TAIL_MAX_EDGES = 128, 512      # MKGNN_TAIL_MAX_ATOMS / _EDGES
+TAIL_MC_MAX_SAMPLES = 64                       # MKGNN_TAIL_MC_MAX_SAMPLES
+
+
+class TailMcOut(C.Structure):
+    """``mkgnn_tail_mc_out`` (include/molkgnn_hip.h): where ``mkgnn_tail_score_mc`` writes; every pointer may be NULL."""
+    _fields_ = [("samples", C.c_void_p), ("samples_stride", C.c_int64), ("mean", C.c_void_p), ("std", C.c_void_p),
+                ("acq", C.c_void_p), ("alpha", C.c_float), ("beta", C.c_float)]
+
 ATOM_CONTRIB_MAX_TASKS = 32                    # MKGNN_ATOM_CONTRIB_MAX_TASKS
 
 
@@ -257,7 +265,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_kernel_exemplars_update", "mkgnn_kernel_exemplars_workspace_bytes", "mkgnn_embed_knn_update",
            "mkgnn_embed_knn_workspace_bytes", "mkgnn_embed_count_within", "mkgnn_embed_count_within_workspace_bytes",
            "mkgnn_embed_neighbours_within", "mkgnn_embed_neighbours_within_workspace_bytes", "mkgnn_graph_components",
-           "mkgnn_graph_components_workspace_bytes", "mkgnn_maxmin_pick", "mkgnn_maxmin_pick_workspace_bytes")
+           "mkgnn_graph_components_workspace_bytes", "mkgnn_maxmin_pick", "mkgnn_maxmin_pick_workspace_bytes",
+           "mkgnn_tail_score_mc", "mkgnn_tail_score_mc_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -325,6 +334,12 @@ def load() -> C.CDLL:
     lib.mkgnn_tail_score_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
     lib.mkgnn_tail_score.restype = C.c_int
     lib.mkgnn_tail_score.argtypes = [C.POINTER(TailArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+    # Monte Carlo dropout samples: (args, readout dropout p, samples, {seed, offset} on the device, outputs, workspace, bytes, stream)
+    lib.mkgnn_tail_score_mc_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_tail_score_mc_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64]
+    lib.mkgnn_tail_score_mc.restype = C.c_int
+    lib.mkgnn_tail_score_mc.argtypes = [C.POINTER(TailArgs), C.c_float, C.c_int32, C.c_void_p, C.POINTER(TailMcOut), C.c_void_p,
+                                        C.c_size_t, C.c_void_p]
     # every atom's share of every logit: (args, workspace, workspace bytes, stream)
     lib.mkgnn_atom_contributions_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_atom_contributions_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64]

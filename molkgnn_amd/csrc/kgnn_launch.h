@@ -233,6 +233,16 @@ int tail_middle_blocks(int64_t n_loss_mols);
 hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st);
 // the forward-only form (mkgnn_tail_score): reads z, rin, cin, mol_ptr, the weights, H, G, n_mols, n_loss, mg; writes pred and emb
 hipError_t launch_tail_score(const TailMidArgs& a, int nb, hipStream_t st);
+// kgnn_tail_mc.hip: the Monte Carlo dropout form (mkgnn_tail_score_mc) -- the forward-only form's inputs in `m`, and of it also
+// drop_p, rdrop_p and rng (the {seed, offset} pair: read, never advanced); m.pred and m.emb may each be null
+struct TailMcArgs {
+    TailMidArgs m;
+    int S;                                  // samples per molecule, 1 .. MKGNN_TAIL_MC_MAX_SAMPLES
+    float* samples; int64_t ss;             // [n_loss, S] rows ss floats apart, or null
+    float *mean, *std, *acq;                // [n_loss] each, or null
+    float alpha, beta;                      // acq = alpha * mean + beta * std
+};
+hipError_t launch_tail_score_mc(const TailMcArgs& a, int nb, hipStream_t st);
 
 // kgnn_atom_contrib.hip: every atom's share of every logit (mkgnn_atom_contributions, kgnn_readout.hip) -- one launch over atoms
 struct AtomContribArgs {

@@ -1323,6 +1323,48 @@ int mkgnn_tail_score(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }
 
+// ---- Monte Carlo dropout on the forward-only tail: project | the middle's forward phases, the part behind the masks S times
+// (kgnn_tail_mc.hip) -- two launches; the generator pair is read, nothing is advanced, no state of the process is involved ----
+size_t mkgnn_tail_score_mc_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols) {
+    return mkgnn_tail_score_workspace_bytes(K, H, G, n_atoms, n_mols);      // (the z rows)
+}
+
+int mkgnn_tail_score_mc(const mkgnn_tail_args* p, float readout_dropout_p, int32_t n_samples, const int64_t* rng_pair,
+                        const mkgnn_tail_mc_out* out, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "mkgnn_tail_score_mc";
+    hipStream_t st = (hipStream_t)stream;
+    BlockProjArgs b{};
+    ReadoutDims d;
+    const float rp = readout_dropout_p;
+    auto own = [&]() {
+        const mkgnn_readout_params* ro = &p->readout;
+        if (!p->in_rowptr || !p->in_col || !p->mol_ptr || !p->atom_mol || !ro->lin1_weight || !ro->lin2_weight || !p->head_weight ||
+            !rng_pair || !out)
+            return api_fail("%s: null pointer", who);
+        if (n_samples < 1 || n_samples > MKGNN_TAIL_MC_MAX_SAMPLES)
+            return api_fail("%s: %d samples outside [1, %d]", who, (int)n_samples, MKGNN_TAIL_MC_MAX_SAMPLES);
+        if (!(p->dropout_p >= 0.f && p->dropout_p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, (double)p->dropout_p);
+        if (!(rp >= 0.f && rp < 1.f)) return api_fail("%s: readout dropout probability %g outside [0, 1)", who, (double)rp);
+        if (out->samples && out->samples_stride < n_samples)
+            return api_fail("%s: samples stride %lld below %d samples", who, (long long)out->samples_stride, (int)n_samples);
+        return 0;
+    };
+    if (int rc = tail_project(who, p, own, mkgnn_tail_score_mc_workspace_bytes, ws, ws_bytes, st, b, d)) return rc;
+    const mkgnn_readout_params* ro = &p->readout;
+    TailMcArgs q{};
+    TailMidArgs& m = q.m;
+    m.z = (float*)ws; m.rin = p->in_rowptr; m.cin = p->in_col; m.mol_ptr = p->mol_ptr; m.atom_mol = p->atom_mol;
+    m.n_atoms = p->n_atoms; m.n_mols = p->n_mols; m.n_loss = p->n_loss_mols;
+    m.b1 = ro->lin1_bias; m.w2 = ro->lin2_weight; m.b2 = ro->lin2_bias; m.wh = p->head_weight; m.bh = p->head_bias;
+    m.H = ro->H; m.G = ro->G; m.drop_p = p->dropout_p; m.rdrop_p = rp; m.rng = rng_pair;
+    m.emb = p->emb; m.es = p->emb_stride; m.pred = p->pred;
+    m.mg = tail_group_size(p->n_loss_mols);
+    q.S = n_samples; q.samples = out->samples; q.ss = out->samples_stride;
+    q.mean = out->mean; q.std = out->std; q.acq = out->acq; q.alpha = out->alpha; q.beta = out->beta;
+    const hipError_t e = launch_tail_score_mc(q, tail_middle_blocks(p->n_loss_mols), st);      // (hipGetLastError: both launches)
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
 // ---- every atom's share of every logit (evaluation mode): project | one kernel over atoms (kgnn_atom_contrib.hip) ----
 size_t mkgnn_atom_contributions_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms) {
     ReadoutDims d;

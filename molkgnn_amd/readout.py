@@ -1977,6 +1977,106 @@ def tail_score(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: tor
     return pred, emb
 
 
+# ---------------------------------------------------------------- Monte Carlo dropout samples on the forward-only tail --
+# MKGNN_SCORE_MC=0: GNNModel.predict_mc runs its PyTorch route (h once, S rounds of torch operators, torch's generator; A/B)
+_SCORE_MC = os.environ.get("MKGNN_SCORE_MC", "1") != "0"
+
+
+def mc_statistics_reference(samples, alpha: float = 1.0, beta: float = 0.0):
+    """The definition of ``mkgnn_tail_score_mc``'s statistics: ``(mean, std, acq)`` of every row of ``samples [n, S]``, float32
+    numpy arrays ``[n]``, in the kernel's own steps -- each ONE float32 round-to-nearest operation, in sample order:
+    ``sum = +0; sum = sum + x_s``; ``mean = sum / S``; ``q = +0; d = x_s - mean; q = q + d * d``; ``std = sqrt(q / (S - 1))``
+    (unbiased; exactly 0 for ``S = 1``); ``acq = alpha * mean + beta * std`` (two products, one sum).  The kernel's vectors equal
+    these bit for bit.  A row holding a NaN gives NaN (its ``std`` too, unless ``S = 1``)."""
+    import numpy as np
+    x = samples.detach().cpu().numpy() if torch.is_tensor(samples) else np.asarray(samples)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError("mc_statistics_reference needs samples [n, S] with S >= 1")
+    n, S = x.shape
+    f32 = np.float32
+    with np.errstate(invalid="ignore", over="ignore"):
+        total = np.zeros(n, dtype=f32)
+        for s in range(S):
+            total = (total + x[:, s]).astype(f32)
+        mean = (total / f32(S)).astype(f32)
+        q = np.zeros(n, dtype=f32)
+        for s in range(S):
+            d = (x[:, s] - mean).astype(f32)
+            q = (q + (d * d).astype(f32)).astype(f32)
+        std = np.sqrt((q / f32(S - 1)).astype(f32)).astype(f32) if S > 1 else np.zeros(n, dtype=f32)
+        acq = ((f32(alpha) * mean).astype(f32) + (f32(beta) * std).astype(f32)).astype(f32)
+    return mean, std, acq
+
+
+def _check_mc_samples(n_samples) -> int:
+    S = int(n_samples)
+    if S != n_samples or not 1 <= S <= _lib.TAIL_MC_MAX_SAMPLES:
+        raise ValueError(f"n_samples = {n_samples} outside [1, {_lib.TAIL_MC_MAX_SAMPLES}] (MKGNN_TAIL_MC_MAX_SAMPLES)")
+    return S
+
+
+def tail_score_mc(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torch.nn.Linear, ffn: torch.nn.Linear,
+                  seg: "MoleculeSegments", n_samples: int, dropout_p: float, readout_dropout_p: float,
+                  n_rows: Optional[int] = None, alpha: float = 1.0, beta: float = 0.0, rng_pair: Optional[torch.Tensor] = None,
+                  return_samples: bool = False, return_pred: bool = False) -> dict:
+    """Monte Carlo dropout behind the last convolution as two launches (``mkgnn_tail_score_mc``): ``n_samples`` stochastic
+    predictions of every one of the ``n_rows`` leading molecules -- evaluation-mode inputs, the head's dropout ``dropout_p`` and
+    the readout's ``readout_dropout_p`` left on -- reduced to ``mean``, ``std`` (unbiased) and ``acq = alpha * mean + beta * std``,
+    ``[n_rows]`` each (``mc_statistics_reference`` is their definition).  Sample ``s`` is bit for bit the ``pred`` of the training
+    tail (``tail_loss``) for generator state ``{seed, offset + s}``.  ``return_samples``: also ``samples [n_rows, n_samples]``
+    (otherwise no such matrix exists anywhere); ``return_pred``: also ``pred [n_rows]`` and ``emb [seg.size, G]``, ``tail_score``'s
+    bits.  ``rng_pair=None``: the pair is ``head_rng_state`` and its offset is advanced by ``n_samples`` behind the call, in place
+    on the same stream -- capturable: every replay of a captured call draws fresh masks.  A pair given (int64 ``{seed, offset}``
+    on the device) is read and nothing is advanced.  Forward only, as ``tail_score``: where a gradient is being recorded for one
+    of its inputs it raises instead of dropping it.  The caller has checked ``tail_supported`` and ``_tail_limits_ok``."""
+    params = (lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight, ffn.bias)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (sim, *params)):
+        raise RuntimeError("tail_score_mc is forward only: call it under torch.no_grad() (or on detached inputs); "
+                           "tail_loss is the operator with gradients")
+    S = _check_mc_samples(n_samples)
+    for name, p in (("dropout", dropout_p), ("readout dropout", readout_dropout_p)):
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"{name} probability {p} outside [0, 1)")
+    lib = _lib.load()
+    _lib.require_gpu_tensor(sim, "sim_sc")
+    n_rows = seg.size if n_rows is None else int(n_rows)
+    if ffn.out_features != 1 or n_rows <= 0 or n_rows > seg.size:
+        raise ValueError("tail_score_mc needs a one-output linear layer and 1 <= n_rows <= the batch's molecules")
+    n, K = sim.shape
+    dev = sim.device
+    advance = rng_pair is None
+    if advance:
+        rng_pair = head_rng_state(dev)
+    elif rng_pair.dtype != torch.int64 or rng_pair.numel() != 2 or not rng_pair.is_contiguous() or rng_pair.device != dev:
+        raise ValueError("rng_pair: two contiguous int64 values {seed, offset} on the batch's device")
+    w1, b1, w2, b2, wh, bh = (None if t is None else t.detach() for t in params)
+    w1c, w2c, whc = w1.contiguous(), w2.contiguous(), wh.reshape(-1).contiguous()
+    H, G = w1c.shape[0], w2c.shape[0]
+    result = {k: torch.empty(n_rows, dtype=torch.float32, device=dev) for k in ("mean", "std", "acq")}
+    a, keep = _tail_args(sim, plan, blocks, seg, n_rows, w1c, b1, w2c, b2, whc, bh)
+    a.dropout_p = float(dropout_p)
+    if return_pred:
+        result["pred"] = torch.empty(n_rows, dtype=torch.float32, device=dev)
+        result["emb"] = torch.empty((seg.size, G), dtype=torch.float32, device=dev)
+        a.pred, a.emb, a.emb_stride = result["pred"].data_ptr(), result["emb"].data_ptr(), G
+    out = _lib.TailMcOut()
+    out.mean, out.std, out.acq = (result[k].data_ptr() for k in ("mean", "std", "acq"))
+    out.alpha, out.beta = float(alpha), float(beta)
+    if return_samples:
+        result["samples"] = torch.empty((n_rows, S), dtype=torch.float32, device=dev)
+        out.samples, out.samples_stride = result["samples"].data_ptr(), S
+    with torch.cuda.device(dev):
+        # (the training tail's scratch, as tail_score: a reduction still pending on its slabs is launched by the call first)
+        ws = _tail_workspace(dev, int(lib.mkgnn_tail_score_mc_workspace_bytes(K, H, G, n, seg.size)))
+        _lib.check(lib.mkgnn_tail_score_mc(ctypes.byref(a), float(readout_dropout_p), S, rng_pair.data_ptr(), ctypes.byref(out),
+                                           ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_tail_score_mc")
+        if advance:
+            rng_pair[1:].add_(S)                             # (behind the kernel on its stream; inside a capture: a graph node)
+    del keep
+    return result
+
+
 # ------------------------------------------------------------- every atom's share of every logit (evaluation mode) --
 # MKGNN_ATOM_CONTRIB=0: GNNModel.atom_contributions runs the PyTorch operators on a dense h (atom_contributions_torch; A/B)
 _ATOM_CONTRIB = os.environ.get("MKGNN_ATOM_CONTRIB", "1") != "0"

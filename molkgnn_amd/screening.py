@@ -464,6 +464,92 @@ def score_resident_tasks(model, resident, batch_size: int, *, topk: Optional[Top
                       topk, TopKTasks, T, shard_tag=shard_tag, out=out)
 
 
+def _check_mc(who: str, model, n_samples, seed) -> None:
+    """What a Monte Carlo pass refuses before a launch, beyond ``_check_model``: ``GNNModel.predict_mc``'s own refusals (asked here,
+    before a shard is touched) and a seed that is no integer."""
+    from .readout import _check_mc_samples
+    _check_mc_samples(n_samples)
+    if float(model.dropout.p) == 0.0 and float(model.gnn_model.dropout.p) == 0.0:
+        raise ValueError(f"{who}: both dropouts of this model are 0 -- it has no dropout uncertainty (score_resident scores it)")
+    if seed is not None and int(seed) != seed:
+        raise ValueError(f"{who}: seed must be an integer or None")
+
+
+def _mc_pass(who: str, model, resident, dev, batch_size: int, n_samples: int, alpha: float, beta: float, topk=None, shard_tag: int = 0):
+    """One shard pass whose scoring is ``model.predict_mc``: ``(pred, mean, std, acq)``, ``[n_molecules]`` each; with ``topk`` the
+    batches' live rows enter that list ranked by ``acq``."""
+    def predict(data):
+        r = model.predict_mc(data, n_samples, alpha, beta)
+        return tuple(r[k].reshape(-1) for k in ("pred", "mean", "std", "acq"))
+
+    rank = None
+    if topk is not None:
+        rank = lambda pred, ids, n_live, mean, std, acq: topk.update(acq, ids, n_valid=n_live)     # noqa: E731
+    nan = float("nan")
+    return _run_shard(who, "scoring", model, resident, dev, batch_size, predict, (), topk, TopK, shard_tag=shard_tag,
+                      extras=((torch.float32, nan),) * 3, rank=rank)
+
+
+def score_resident_mc(model, resident, batch_size: int, n_samples: int, alpha: float = 1.0, beta: float = 0.0, seed=None):
+    """``(pred[n], mean[n], std[n], acq[n])`` (float32, on the device): ``model.predict_mc`` of every molecule of the
+    ``ResidentShard`` -- the point score, and mean, spread and acquisition value ``alpha * mean + beta * std`` of ``n_samples`` Monte
+    Carlo dropout samples -- in id order, the short tail included, as ``score_resident`` makes its pass: one graph captured per
+    call and replayed per batch, in which the model's scoring is ``predict_mc`` (on its kernel route two launches behind the last
+    convolution, ``readout.tail_score_mc``).  ``pred`` is ``score_resident``'s, bit for bit.  Every replay draws fresh masks: the
+    generator's offset advances on the device by ``n_samples`` per batch.  ``seed``: the head generator is reset to ``{seed, 0}``
+    (``readout.reset_head_rng``) before the pass.  A molecule's masks depend on its slot in its batch and on its atoms' rows
+    there, so the result is reproducible for a given ``(seed, batch_size)`` -- not across batch sizes.  (On ``predict_mc``'s
+    PyTorch route the masks come from PyTorch's generator, which a captured graph advances too; ``seed`` does not reach it.)
+    A one-task model on the shard's GPU with at least one dropout above 0, ``1 <= n_samples <= 64``: anything else raises
+    ``ValueError`` before a launch.  The model comes back in the mode it came in."""
+    who = "score_resident_mc"
+    dev = _check_model(model, resident)
+    _check_mc(who, model, n_samples, seed)
+    if seed is not None:
+        from .readout import reset_head_rng
+        reset_head_rng(dev, int(seed))
+    return _mc_pass(who, model, resident, dev, batch_size, int(n_samples), float(alpha), float(beta))
+
+
+def screen_acquisition(model, residents, k: int, batch_size: int, n_samples: int, alpha: float = 1.0, beta: float = 1.0,
+                       seed=None) -> dict:
+    """``screen`` ranked by an acquisition value instead of the point score: the ``k`` molecules of a library with the largest
+    ``acq = alpha * mean + beta * std`` of ``n_samples`` Monte Carlo dropout samples (``GNNModel.predict_mc``) -- the next batch of
+    an active-learning campaign: exploit with ``beta = 0``, explore with ``beta > 0``; ``alpha = -1`` serves a task where lower is
+    better, such as docking scores.  ``residents`` as in ``screen``; shard ``j`` carries tag ``j``; one ``TopK`` is carried across the
+    shards, fed by the running list's own ``update`` with ``acq`` as the key inside every batch's captured graph.
+
+    Returns ``top_score`` (the acquisition value), ``top_shard``, ``top_mol`` (trimmed to the occupied slots, best first);
+    ``top_pred``, ``top_mean``, ``top_std`` of the hits, gathered at the end from the per-shard vectors (which stay on the device at
+    12 bytes per molecule); and ``n_scored``.  ``seed``: the head generator is reset once, before the first shard; reproducible for
+    a given ``(seed, batch_size)`` and shard order, as ``score_resident_mc``.  Refusals as ``score_resident_mc``."""
+    who = "screen_acquisition"
+    if getattr(getattr(model, "ffn", None), "out_features", None) != 1:
+        raise ValueError("screening ranks ONE score per molecule: a one-task model (task_dim = 1) is needed")
+    _check_mc(who, model, n_samples, seed)
+    S, alpha, beta = int(n_samples), float(alpha), float(beta)
+    if seed is not None:
+        from .readout import reset_head_rng
+        dev = next(model.parameters()).device
+        if dev.type == "cuda":
+            reset_head_rng(dev, int(seed))
+
+    def per_shard(resident, topk, tag):
+        pred, mean, std, _ = _mc_pass(who, model, resident, topk.device, batch_size, S, alpha, beta, topk, tag)
+        return pred.clone(), mean.clone(), std.clone()   # (clones: without the spare slot's storage)
+
+    top_score, top_shard, top_mol, occupied, n_scored, shards = _over_shards(
+        who, residents, lambda r: _check_model(model, r), lambda dev: TopK(k, dev), per_shard, True)
+    top_shard, top_mol = top_shard[:occupied], top_mol[:occupied]
+    dev = top_score.device
+    sizes = [int(pred.numel()) for pred, _, _ in shards]
+    first = torch.tensor(np.concatenate([[0], np.cumsum(sizes)[:-1]]), dtype=torch.int64, device=dev)
+    at = first[top_shard.long()] + top_mol.long()
+    return {"top_score": top_score[:occupied], "top_shard": top_shard, "top_mol": top_mol,
+            "top_pred": torch.cat([v for v, _, _ in shards])[at], "top_mean": torch.cat([v for _, v, _ in shards])[at],
+            "top_std": torch.cat([v for _, _, v in shards])[at], "n_scored": n_scored}
+
+
 def explain_resident(model, resident, ids, batch_size: int = 256) -> dict:
     """Why the molecules ``ids`` of one ``ResidentShard`` score what they score (the ``top_mol`` of a screen where ``top_shard`` is
     this shard, say; repeats allowed, order kept): ``GNNModel.atom_contributions`` of every one of them, as a dict --

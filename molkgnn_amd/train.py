@@ -79,6 +79,68 @@ class GNNModel(torch.nn.Module):
             n = pred.shape[0] if nreal is None else int(nreal)
             return pred[:n], graph_embedding[:n]
 
+    def predict_mc(self, data, n_samples: int, alpha: float = 1.0, beta: float = 0.0, return_samples: bool = False) -> dict:
+        """Score with uncertainty -- Monte Carlo dropout: ``n_samples`` (1 to 64) stochastic predictions of every molecule from a
+        model in evaluation mode (the batch norms use their running statistics) with BOTH dropouts left on -- the head's
+        (``ffn_dropout_rate``) and the readout's (``dropout_ratio``) -- under ``torch.no_grad()``.  Returns a dict: ``pred``, the
+        evaluation-mode prediction (``predict``'s bits; the masks are inverted dropout in front of linear layers, so it is the
+        samples' expectation); ``mean`` and ``std`` (unbiased) of the samples; ``acq = alpha * mean + beta * std``, the
+        acquisition value of an active-learning round (``alpha = -1`` where lower is better, as for docking scores); each ``[n]``
+        for a one-task model (``n`` as in ``predict``); with ``return_samples`` also ``samples [n, n_samples]``.
+
+        Both dropouts sit behind the last convolution, so the network runs ONCE.  Where model and batch qualify as for ``predict``
+        (one task, CUDA, the fused tail's shapes and molecule sizes; ``dropout_ratio < 1``) everything behind the last
+        convolution is ``readout.tail_score_mc`` -- two launches for all samples, the statistics included, no ``[n, S]`` matrix
+        unless asked for; sample ``s`` is bit for bit the prediction of a training step with generator state ``{seed, offset +
+        s}`` of ``readout.head_rng_state``, whose offset the call advances by ``n_samples`` on the device (inside a captured
+        graph too: every replay draws fresh masks; ``MKGNN_MOLECULE=1`` does not reroute this call).  Otherwise -- more than one
+        task (then every result is ``[n, T]``, ``samples [n, n_samples, T]``, ``pred`` is ``predict_tasks``'s), a shape or a
+        molecule outside the fused tail, the CPU, ``MKGNN_SCORE_MC=0`` or ``MKGNN_FUSED_TAIL=0`` -- the PyTorch route: ``pred`` from
+        ``predict`` / ``predict_tasks``, then the last layer's ``h`` once and per sample ``F.dropout``, ``lin2``, add-pool,
+        ``F.dropout``, ``ffn``, then ``torch.var_mean``.  That is the same definition and the same distribution, but the masks come
+        from PyTorch's generator, so the samples differ from the kernel route's.
+
+        In training mode this raises, as ``predict`` does; a model whose two dropouts are both 0 has no dropout uncertainty:
+        ``ValueError``; so is ``n_samples`` outside ``[1, 64]`` -- all before the batch is looked at."""
+        from . import readout as R
+        self._needs_eval("predict_mc")
+        net = self.gnn_model
+        p_head, p_readout = float(self.dropout.p), float(net.dropout.p)
+        if p_head == 0.0 and p_readout == 0.0:
+            raise ValueError("GNNModel.predict_mc: both dropouts of this model are 0 -- it has no dropout uncertainty (predict scores it)")
+        S = R._check_mc_samples(n_samples)
+        one_task = self.ffn.out_features == 1
+        with torch.no_grad():
+            nreal = getattr(data, 'n_valid_molecules', None)
+            mc = (self.ffn, nreal, S, p_head, float(alpha), float(beta), bool(return_samples))
+            out = net(data, _mc=mc if (one_task and data.x.is_cuda and p_head < 1.0) else ())
+            if out[0] == "mc":
+                result = out[1]
+                result.pop("emb")
+                return result
+            # the PyTorch route: h once, the part behind the masks per sample
+            pred = self.predict(data)[0].reshape(-1) if one_task else self.predict_tasks(data)[0]
+            n, F = pred.shape[0], torch.nn.functional
+            act = R.swish(net.graph_embedding_lin1(out[1]))
+            slots = getattr(data, 'num_graphs', None)
+            draws = []
+            for _ in range(S):
+                emb = net.pool(net.graph_embedding_lin2(F.dropout(act, p_readout, True)), data.batch, slots)
+                draws.append(self.ffn(F.dropout(emb, p_head, True))[:n])
+            samples = torch.stack(draws, dim=1)             # [n, S, T]
+            if one_task:
+                samples = samples.reshape(n, S)
+            if S > 1:
+                var, mean = torch.var_mean(samples, dim=1, unbiased=True)
+                std = var.sqrt()
+            else:
+                mean = samples.select(1, 0).clone()
+                std = torch.zeros_like(mean)
+            result = {"pred": pred, "mean": mean, "std": std, "acq": float(alpha) * mean + float(beta) * std}
+            if return_samples:
+                result["samples"] = samples
+            return result
+
     def _embedding(self, data):
         """``(graph_embedding [all slots, G], n)`` of a model in evaluation mode, inside the caller's ``no_grad``: the route
         ``predict_tasks`` and ``embed`` share.  On the GPU the forward-only tail is handed a one-row view of the head (which it needs;
