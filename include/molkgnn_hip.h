@@ -591,6 +591,10 @@ int mkgnn_batchnorm_backward(const float* grad_out, int64_t grad_out_stride, con
                              const float* save_mean, const float* save_invstd, int32_t training,
                              float* grad_x, int64_t grad_x_stride, float* grad_weight, float* grad_bias,
                              const int64_t* n_valid_rows, void* workspace, size_t workspace_bytes, void* stream);
+/* tests: 0 = the batch norm merges its block partials in the loop form at every width (MKGNN_BN_MERGE=0; this call wins over the
+ * environment); 1 = out of registers where a thread's terms fit; negative = back to the default.  Every result of the three
+ * calls above is the same bits either way. */
+int mkgnn_debug_set_bn_merge(int32_t on);
 
 /* Receptive-field builder: the per-degree tensors of a collated batch, reference
  * wrapper.py:559-672 (ToXAndPAndEdgeAttrForDeg) + PyG collation.  edge_index is [2, M] int64 (row 0 sources, row 1

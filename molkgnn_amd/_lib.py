@@ -266,7 +266,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_embed_knn_workspace_bytes", "mkgnn_embed_count_within", "mkgnn_embed_count_within_workspace_bytes",
            "mkgnn_embed_neighbours_within", "mkgnn_embed_neighbours_within_workspace_bytes", "mkgnn_graph_components",
            "mkgnn_graph_components_workspace_bytes", "mkgnn_maxmin_pick", "mkgnn_maxmin_pick_workspace_bytes",
-           "mkgnn_tail_score_mc", "mkgnn_tail_score_mc_workspace_bytes")
+           "mkgnn_tail_score_mc", "mkgnn_tail_score_mc_workspace_bytes", "mkgnn_debug_set_bn_merge")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -434,6 +434,9 @@ def load() -> C.CDLL:
                                                        C.POINTER(BnStats), P, C.c_size_t, P]
     lib.mkgnn_batchnorm_backward.restype = C.c_int
     lib.mkgnn_batchnorm_backward.argtypes = [P, I64, P, I64, I64, I32, P, P, P, I32, P, I64, P, P, P, P, C.c_size_t, P]
+    # tests: 0 = the loop form of the batch norm's merges at every width, 1 = the register forms, < 0 = the default
+    lib.mkgnn_debug_set_bn_merge.restype = C.c_int
+    lib.mkgnn_debug_set_bn_merge.argtypes = [I32]
     lib.mkgnn_bce_head_forward.restype = C.c_int
     lib.mkgnn_bce_head_forward.argtypes = [P, I64, I64, I32, P, P, P, P, P, P, C.c_size_t, P]
     lib.mkgnn_bce_head_backward.restype = C.c_int

@@ -5,6 +5,7 @@
 // Batch norm.  Tall and skinny ([1e5, 28]): three short launches (column sums, centred squares, apply),
 // every block re-deriving the column statistics from the per-block partials in a fixed order.
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include "kgnn_common.h"
@@ -27,7 +28,13 @@ typedef mkgnn_f32x4 f32x4;
 #ifndef MKGNN_BN_BLOCKS                  // (A/B builds)
 #define MKGNN_BN_BLOCKS 256
 #endif
-constexpr int BN_MAIN_BLOCKS = MKGNN_BN_BLOCKS;        // (= BN_BLOCKS: the grid of the batch norm's own passes)
+// Attribution builds (their results are WRONG, they exist to be timed): make VARIANT=... EXTRA=-DMKGNN_BN_AB=n with
+// 1: the apply launch takes the saved statistics instead of merging the partials; 2: the apply launch without its row pass;
+// 3: the statistics launch without pass B
+#ifndef MKGNN_BN_AB
+#define MKGNN_BN_AB 0
+#endif
+constexpr int BN_MAIN_BLOCKS = MKGNN_BN_BLOCKS;       // (= BN_BLOCKS: the grid of the batch norm's own passes)
 constexpr int BN_SIDE_BLOCKS = 1024;                   // companion blocks at most (one loop trip per pass each where that is enough)
 struct BnSide {
     const float* x; int64_t xs; int64_t n; int C, CL, nblk;
@@ -36,6 +43,7 @@ struct BnSide {
     int64_t* nbt;
     const int64_t* key; const int64_t* key_limit;      // both or neither: row r counts iff key[r] < *key_limit
     float* part;
+    int merge;                                         // the totals from one set of loads where they fit (bn_merge_on)
 };
 
 struct BnArgs {
@@ -57,6 +65,7 @@ struct BnArgs {
     TouchArgs touch;
     int64_t* nbt;                  // forward, training: BatchNorm1d.num_batches_tracked, incremented
     const int64_t* nvalid;         // device scalar or null: only rows [0, *nvalid) enter the batch statistics (padded batches)
+    int merge;                     // the block partials merged out of registers where they fit (bn_merge_on; 0: the loop form)
     BnSide side;                   // statistics-only companion (blocks gridDim.x - side.nblk .. of the same launches); nblk = 0: none
 };
 
@@ -214,7 +223,7 @@ __device__ __forceinline__ void bn_block_stats(const BnArgs& a, int CL, float* s
         __syncthreads();
         const f32x4 mu = {bmean[cb], bmean[cb + 1], bmean[cb + 2], bmean[cb + 3]};
         s0 = z;
-        bn_pass_vec<1, BN_U>(a.x, a.xs, nullptr, 0, lo, hi, rsub, RS, cb, mu, z, s0, s1);
+        if (MKGNN_BN_AB != 3) bn_pass_vec<1, BN_U>(a.x, a.xs, nullptr, 0, lo, hi, rsub, RS, cb, mu, z, s0, s1);
         const f32x4 m2 = bn_reduce_rows(s0, LW, (f32x4*)sh);
         const f32x4 m1 = bn_reduce_rows(s1, LW, (f32x4*)sh);
         if (t < LW && act) {
@@ -287,6 +296,101 @@ __device__ __forceinline__ void bn_total_m2(const float* part1, const float* par
         const float d = left > 0 ? p1 / cnt - mu : 0.f;  // (an empty block: nothing)
         return fmaf(d, fmaf(cnt, d, 2.f * p3), p2);
     });
+}
+
+// ---- the totals out of registers ---------------------------------------------------------------------------------------------
+// bn_total_of asks memory for eight terms, waits, adds, and asks again; a second total starts when the first is through LDS.  At
+// 256 blocks and CL = 32 that is four dependent trips per total, eight for the mean and the squares -- in every block of the apply
+// launch, in front of its first row load, with nothing beside them to hide the latency.  Where a thread's terms are 8 KT <= 32
+// (nblk * CL <= 8192) it holds them all: the loads of every plane are issued at once, and the sums are formed from the registers IN
+// bn_total_of's ORDER -- accumulator t[u] takes the terms b = rsub + RS (u + 8 k) for k ascending, the eight combine as a tree, the
+// row lanes in ascending order through LDS -- so every total is the loop form's, bit for bit.  Wider rows keep the loop form.
+template <int KT>
+__device__ __forceinline__ void bn_load_terms(const float* part, int nblk, int C, int cc, int rsub, int RS, float (&v)[8 * KT]) {
+#pragma unroll
+    for (int j = 0; j < 8 * KT; ++j) {                   // (unconditional, clamped: a term past the end is loaded and not added)
+        const int b = rsub + RS * j;
+        v[j] = part[(int64_t)(b < nblk ? b : nblk - 1) * C + cc];
+    }
+}
+template <int KT>
+__device__ __forceinline__ float bn_sum_terms(const float (&v)[8 * KT], int nblk, int rsub, int RS) {
+    float t[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (rsub + RS * (u + 8 * k) < nblk) t[u] += v[8 * k + u];
+    return ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
+}
+// the row lanes' sums of a column, in ascending order: the result in the threads rsub == 0, c < C.  sh: 256 floats nobody still reads
+__device__ __forceinline__ float bn_sum_lanes(float s, int C, int CL, float* sh) {
+    const int c = threadIdx.x & (CL - 1), rsub = threadIdx.x / CL, RS = 256 / CL;
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    float t = 0.f;
+    if (rsub == 0 && c < C)
+        for (int k = 0; k < RS; ++k) t += sh[k * CL + c];
+    return t;
+}
+// ... two columns' worth behind one barrier.  sh: 512 floats
+__device__ __forceinline__ void bn_sum_lanes2(float& s0, float& s1, int C, int CL, float* sh) {
+    const int c = threadIdx.x & (CL - 1), rsub = threadIdx.x / CL, RS = 256 / CL;
+    sh[threadIdx.x] = s0;
+    sh[256 + threadIdx.x] = s1;
+    __syncthreads();
+    s0 = 0.f;
+    s1 = 0.f;
+    if (rsub == 0 && c < C)
+        for (int k = 0; k < RS; ++k) { s0 += sh[k * CL + c]; s1 += sh[256 + k * CL + c]; }
+}
+// how many trips of eight terms a thread's share of nblk partials is; 0: more than four, the loop form
+__device__ __forceinline__ int bn_term_trips(int merge, int nblk, int CL) {
+    if (!merge || nblk * CL > 4 * 2048) return 0;
+    return nblk * CL <= 2048 ? 1 : (nblk * CL <= 2 * 2048 ? 2 : 4);
+}
+
+// The forward merge: mean[c] = batch mean, m2[c] = squares about it (bn_total, the division, bn_total_m2) from one set of loads.
+// The rows of block b are `per` up to the last block that has any, whose count is what is left, and none behind it (bn_share):
+// two float constants and two comparisons per term where bn_total_m2 multiplies and clamps in 64 bits.  sh: 512 floats
+template <int KT>
+__device__ __forceinline__ void bn_merge_held(const BnArgs& a, int nblk, int CL, float* sh, float* mean, float* m2) {
+    const int c = threadIdx.x & (CL - 1), rsub = threadIdx.x / CL, RS = 256 / CL, cc = c < a.C ? c : 0;
+    float p1[8 * KT], p2[8 * KT], p3[8 * KT];
+    bn_load_terms<KT>(a.part1, nblk, a.C, cc, rsub, RS, p1);
+    bn_load_terms<KT>(a.part2, nblk, a.C, cc, rsub, RS, p2);
+    bn_load_terms<KT>(a.part3, nblk, a.C, cc, rsub, RS, p3);
+    const int64_t nv = bn_valid(a);
+    const int64_t per = (nv + nblk - 1) / nblk, full = nv / per;         // blocks [0, full) hold `per` rows, block `full` the rest
+    const float cnt_full = (float)per, cnt_last = (float)(nv - per * full);
+    __syncthreads();                                     // (sh may still be read)
+    const float tot = bn_sum_lanes(bn_sum_terms<KT>(p1, nblk, rsub, RS), a.C, CL, sh);
+    if (rsub == 0 && c < a.C) mean[c] = tot / (float)nv;
+    __syncthreads();
+    const float mu = mean[cc];
+#pragma unroll
+    for (int j = 0; j < 8 * KT; ++j) {
+        const int b = rsub + RS * j;
+        const float cnt = b < full ? cnt_full : (b == full ? cnt_last : 0.f);
+        const float d = cnt > 0.f ? p1[j] / cnt - mu : 0.f;              // (an empty block: nothing)
+        p2[j] = fmaf(d, fmaf(cnt, d, 2.f * p3[j]), p2[j]);
+    }
+    const float q = bn_sum_lanes(bn_sum_terms<KT>(p2, nblk, rsub, RS), a.C, CL, sh + 256);
+    if (rsub == 0 && c < a.C) m2[c] = q;                 // (read back by the thread that wrote it: t == c)
+}
+
+// two plain totals (the backward's column sums of dy and of dy xhat) from one set of loads.  sh: 512 floats
+template <int KT>
+__device__ __forceinline__ void bn_total_pair_held(const float* pa, const float* pb, int nblk, int C, int CL, float* sh, float* out_a, float* out_b) {
+    const int c = threadIdx.x & (CL - 1), rsub = threadIdx.x / CL, RS = 256 / CL, cc = c < C ? c : 0;
+    float va[8 * KT], vb[8 * KT];
+    bn_load_terms<KT>(pa, nblk, C, cc, rsub, RS, va);
+    bn_load_terms<KT>(pb, nblk, C, cc, rsub, RS, vb);
+    float sa = bn_sum_terms<KT>(va, nblk, rsub, RS), sb = bn_sum_terms<KT>(vb, nblk, rsub, RS);
+    __syncthreads();                                     // (sh may still be read)
+    bn_sum_lanes2(sa, sb, C, CL, sh);
+    if (rsub == 0 && c < C) { out_a[c] = sa; out_b[c] = sb; }
+    __syncthreads();
 }
 
 // Companion statistics, block `blk` of s.nblk: plane 0 column sums, plane 1 squares about the block's own column means,
@@ -450,23 +554,60 @@ __device__ __forceinline__ void bn_side_stats_any(const BnSide& s, int blk, floa
     }
 }
 
+// the companion's three totals from one set of loads (the loop form: bn_side_final's last branch); returns the counted rows.
+// sh: 512 floats
+template <int KT>
+__device__ __forceinline__ float bn_side_totals_held(const BnSide& s, const float* sums, const float* sqs, const float* cnts, float* sh,
+                                                     float* tot_sh, float* cnt_sh, float* mu_sh, float* sq_sh) {
+    const int CL = s.CL, c = threadIdx.x & (CL - 1), rsub = threadIdx.x / CL, RS = 256 / CL, cc = c < s.C ? c : 0;
+    float s_b[8 * KT], n_b[8 * KT], q_b[8 * KT];
+    bn_load_terms<KT>(sums, s.nblk, s.C, cc, rsub, RS, s_b);
+    bn_load_terms<KT>(cnts, s.nblk, s.C, cc, rsub, RS, n_b);
+    bn_load_terms<KT>(sqs, s.nblk, s.C, cc, rsub, RS, q_b);
+    float tot = bn_sum_terms<KT>(s_b, s.nblk, rsub, RS), n = bn_sum_terms<KT>(n_b, s.nblk, rsub, RS);
+    __syncthreads();                                     // (sh may still be read)
+    bn_sum_lanes2(tot, n, s.C, CL, sh);
+    if (rsub == 0 && c < s.C) { tot_sh[c] = tot; cnt_sh[c] = n; }
+    __syncthreads();
+    const float cnt = cnt_sh[0];
+    if ((int)threadIdx.x < s.C) mu_sh[threadIdx.x] = cnt > 0.f ? tot_sh[threadIdx.x] / cnt : 0.f;
+    __syncthreads();
+    const float mu = mu_sh[cc];
+#pragma unroll
+    for (int j = 0; j < 8 * KT; ++j) {
+        const float d = s_b[j] / fmaxf(n_b[j], 1.f) - mu;
+        q_b[j] = fmaf(n_b[j] * d, d, q_b[j]);
+    }
+    const float q = bn_sum_lanes(bn_sum_terms<KT>(q_b, s.nblk, rsub, RS), s.C, CL, sh);
+    if (rsub == 0 && c < s.C) sq_sh[c] = q;              // (read back by the thread that wrote it)
+    return cnt;
+}
+
 // running <- running + momentum (batch - running), unbiased variance, counter + 1 (one block)
+template <bool HELD = true>
 __device__ __forceinline__ void bn_side_final(const BnSide& s, float* sh) {
     __shared__ float tot_sh[256], sq_sh[256], cnt_sh[256], mu_sh[256];
     const float* const sums = s.part;
     const float* const sqs = s.part + (size_t)s.nblk * s.C;
     const float* const cnts = s.part + (size_t)2 * s.nblk * s.C;
-    bn_total(sums, s.nblk, s.C, s.CL, sh, tot_sh);
-    bn_total(cnts, s.nblk, s.C, s.CL, sh, cnt_sh);
     const int col = threadIdx.x;
-    const float cnt = cnt_sh[0];
-    if (col < s.C) mu_sh[col] = cnt > 0.f ? tot_sh[col] / cnt : 0.f;
-    __syncthreads();
-    bn_total_of(s.nblk, s.C, s.CL, sh, sq_sh, [&](int b, int c) {
-        const float n_b = cnts[(size_t)b * s.C + c], s_b = sums[(size_t)b * s.C + c], q_b = sqs[(size_t)b * s.C + c];     // (unconditional loads)
-        const float d = s_b / fmaxf(n_b, 1.f) - mu_sh[c];
-        return fmaf(n_b * d, d, q_b);
-    });
+    const int trips = HELD ? bn_term_trips(s.merge, s.nblk, s.CL) : 0;
+    float cnt;
+    if (trips == 1) cnt = bn_side_totals_held<1>(s, sums, sqs, cnts, sh, tot_sh, cnt_sh, mu_sh, sq_sh);
+    else if (trips == 2) cnt = bn_side_totals_held<2>(s, sums, sqs, cnts, sh, tot_sh, cnt_sh, mu_sh, sq_sh);
+    else if (trips == 4) cnt = bn_side_totals_held<4>(s, sums, sqs, cnts, sh, tot_sh, cnt_sh, mu_sh, sq_sh);
+    else {
+        bn_total(sums, s.nblk, s.C, s.CL, sh, tot_sh);
+        bn_total(cnts, s.nblk, s.C, s.CL, sh, cnt_sh);
+        cnt = cnt_sh[0];
+        if (col < s.C) mu_sh[col] = cnt > 0.f ? tot_sh[col] / cnt : 0.f;
+        __syncthreads();
+        bn_total_of(s.nblk, s.C, s.CL, sh, sq_sh, [&](int b, int c) {
+            const float n_b = cnts[(size_t)b * s.C + c], s_b = sums[(size_t)b * s.C + c], q_b = sqs[(size_t)b * s.C + c];     // (unconditional loads)
+            const float d = s_b / fmaxf(n_b, 1.f) - mu_sh[c];
+            return fmaf(n_b * d, d, q_b);
+        });
+    }
     // (BatchNorm1d raises on fewer than two values per channel in training mode; a kernel cannot: such a degenerate batch -- a
     // padded batch without a single real bond -- leaves the statistics AND the counter where they are: ADVICE round 5)
     if (col < s.C && cnt > 1.f) {
@@ -502,7 +643,7 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(BnArgs a, int CL) {
         bn_side_stats_any(a.side, blockIdx.x - BN_MAIN_BLOCKS, sh);
         if (a.side.nblk == 1) {                          // a companion of one block's worth of rows: all of it here, in this launch
             __syncthreads();                             // (its own global stores are visible to the block behind a barrier)
-            bn_side_final(a.side, sh);
+            bn_side_final<false>(a.side, sh);            // (one partial: the loop form is one trip; the launch keeps its registers)
         }
         return;
     }
@@ -521,7 +662,7 @@ __global__ void __launch_bounds__(256) bn_stats_prep_kernel(BnArgs a, int CL, Pr
         bn_side_stats_any(a.side, blockIdx.x - BN_MAIN_BLOCKS, sh);
         if (a.side.nblk == 1) {
             __syncthreads();
-            bn_side_final(a.side, sh);
+            bn_side_final<false>(a.side, sh);
         }
         return;
     }
@@ -557,10 +698,21 @@ __device__ __forceinline__ void bn_apply_body(const BnArgs& a, int CL, float* sh
     const int t = threadIdx.x;
     if (a.training) {
         const int64_t nv = bn_valid(a);
-        bn_total(a.part1, bn_nblk(), a.C, CL, sh, mean);
-        if (t < a.C) mean[t] = mean[t] / (float)nv;
-        __syncthreads();
-        bn_total_m2(a.part1, a.part2, a.part3, bn_nblk(), nv, a.C, CL, mean, sh, invstd);
+        const int trips = bn_term_trips(a.merge, bn_nblk(), CL);
+        if (MKGNN_BN_AB == 1) {
+            if (t < a.C) { mean[t] = a.save_mean[t]; invstd[t] = a.save_invstd[t]; }
+        } else if (trips == 1) {
+            bn_merge_held<1>(a, bn_nblk(), CL, sh, mean, invstd);
+        } else if (trips == 2) {
+            bn_merge_held<2>(a, bn_nblk(), CL, sh, mean, invstd);
+        } else if (trips == 4) {
+            bn_merge_held<4>(a, bn_nblk(), CL, sh, mean, invstd);
+        } else {
+            bn_total(a.part1, bn_nblk(), a.C, CL, sh, mean);
+            if (t < a.C) mean[t] = mean[t] / (float)nv;
+            __syncthreads();
+            bn_total_m2(a.part1, a.part2, a.part3, bn_nblk(), nv, a.C, CL, mean, sh, invstd);
+        }
         if (t < a.C) {
             const float mu = mean[t], var = invstd[t] / (float)nv;
             invstd[t] = 1.f / sqrtf(var + a.eps);
@@ -588,6 +740,7 @@ __device__ __forceinline__ void bn_apply_body(const BnArgs& a, int CL, float* sh
     __syncthreads();
     int64_t lo, hi;
     bn_rows(a, lo, hi);
+    if (MKGNN_BN_AB == 2) hi = lo;
     const int c = t & (CL - 1), rsub = t / CL, RS = 256 / CL;       // same thread layout as the column sums
     if (blockIdx.x == 0 && t == 0 && a.nbt && a.training) a.nbt[0] += 1;
     if (a.inv_out) {
@@ -700,8 +853,14 @@ __global__ void __launch_bounds__(256) bn_bwd_partial_kernel(BnArgs a, int CL) {
 template <bool VEC>
 __device__ __forceinline__ void bn_bwd_final_body(const BnArgs& a, int CL, int nblk_part, float* sh) {
     __shared__ float sdy[256], sdyx[256];
-    bn_total(a.part1, nblk_part, a.C, CL, sh, sdy);
-    bn_total(a.part2, nblk_part, a.C, CL, sh, sdyx);
+    const int trips = bn_term_trips(a.merge, nblk_part, CL);
+    if (trips == 1) bn_total_pair_held<1>(a.part1, a.part2, nblk_part, a.C, CL, sh, sdy, sdyx);
+    else if (trips == 2) bn_total_pair_held<2>(a.part1, a.part2, nblk_part, a.C, CL, sh, sdy, sdyx);
+    else if (trips == 4) bn_total_pair_held<4>(a.part1, a.part2, nblk_part, a.C, CL, sh, sdy, sdyx);
+    else {
+        bn_total(a.part1, nblk_part, a.C, CL, sh, sdy);
+        bn_total(a.part2, nblk_part, a.C, CL, sh, sdyx);
+    }
     const int t = threadIdx.x;
     if (blockIdx.x == 0 && t < a.C) {
         if (a.gbias) a.gbias[t] = sdy[t];
@@ -791,6 +950,18 @@ using namespace mkgnn;
 // ================================================================== C ABI ==========================
 static constexpr int BN_BLOCKS = BN_MAIN_BLOCKS;
 
+// MKGNN_BN_MERGE=0 and mkgnn_debug_set_bn_merge(0) (tests; it wins over the environment) keep the loop form of every merge at every
+// width: the in-process reference of the register forms.  The results are the same bits either way.
+static std::atomic<int> g_bn_merge_override{-1};
+extern "C" int mkgnn_debug_set_bn_merge(int32_t on) {
+    g_bn_merge_override.store(on < 0 ? -1 : (on ? 1 : 0));           // negative: back to the default
+    return 0;
+}
+static inline int bn_merge_on() {
+    const int forced = g_bn_merge_override.load();
+    return forced >= 0 ? forced : (switches().bn_merge ? 1 : 0);
+}
+
 extern "C" {
 
 size_t mkgnn_batchnorm_workspace_bytes(int32_t C) { return C > 0 ? (size_t)3 * BN_BLOCKS * C * 4 : 0; }
@@ -814,7 +985,7 @@ static int bn_side_setup(const char* who, const mkgnn_bn_stats* c, void* ws, siz
     s.CL = 1;
     while (s.CL < s.C) s.CL <<= 1;
     s.running_mean = c->running_mean; s.running_var = c->running_var; s.momentum = c->momentum; s.nbt = c->num_batches_tracked;
-    s.key = c->row_key; s.key_limit = c->key_limit; s.part = (float*)ws;
+    s.key = c->row_key; s.key_limit = c->key_limit; s.part = (float*)ws; s.merge = bn_merge_on();
     s.flat = (c->C <= 8 && c->x_stride == c->C && ((uintptr_t)c->x & 15) == 0) ? 1 : 0;
     const int64_t rows_per_pass = s.flat ? SIDE_FLAT_ROWS : 8 * (256 / s.CL);      // rows a block takes per loop trip
     int64_t nb = (c->n_rows + rows_per_pass - 1) / rows_per_pass;
@@ -871,7 +1042,7 @@ int mkgnn_batchnorm_forward_with_stats(const float* x, int64_t x_stride, int64_t
     a.out = out; a.os = out_stride; a.save_mean = save_mean; a.save_invstd = save_invstd;
     if (inv_norm && (C > 32 || C % 4 || x_stride % 4 || out_stride % 4 || ((uintptr_t)x & 15) || ((uintptr_t)out & 15)))
         return api_fail("mkgnn_batchnorm_forward: inv_norm needs C <= 32, a multiple of 4, and 16-byte aligned rows of x and out (C=%d)", C);
-    a.inv_out = inv_norm; a.split_out = split_rows ? 1 : 0; a.nbt = num_batches_tracked; a.nvalid = n_valid_rows;
+    a.inv_out = inv_norm; a.split_out = split_rows ? 1 : 0; a.nbt = num_batches_tracked; a.nvalid = n_valid_rows; a.merge = bn_merge_on();
     a.part1 = (float*)ws; a.part2 = a.part1 ? a.part1 + (size_t)BN_BLOCKS * C : nullptr;
     a.part3 = a.part1 ? a.part1 + (size_t)2 * BN_BLOCKS * C : nullptr;
     static_assert(BN_BLOCKS == BN_MAIN_BLOCKS, "the companion's blocks sit behind the batch norm's own");
@@ -924,7 +1095,7 @@ int mkgnn_batchnorm_backward(const float* grad_out, int64_t grad_out_stride, con
     a.save_mean = (float*)save_mean; a.save_invstd = (float*)save_invstd;
     a.part1 = (float*)ws; a.part2 = a.part1 + (size_t)BN_BLOCKS * C;
     a.gout = grad_out; a.gos = grad_out_stride; a.gx = grad_x; a.gxs = grad_x_stride;
-    a.gweight = grad_weight; a.gbias = grad_bias; a.nvalid = n_valid_rows;
+    a.gweight = grad_weight; a.gbias = grad_bias; a.nvalid = n_valid_rows; a.merge = bn_merge_on();
     const bool one_launch = switches().bn_one_launch;    // (opt-in: it lost)
     const bool vec = bn_vec_rows(x, x_stride, C) && bn_vec_rows(grad_out, grad_out_stride, C) && (!grad_x || bn_vec_rows(grad_x, grad_x_stride, C));
     if (one_launch && grad_x) {                          // partial sums | grid barrier | gradient rows

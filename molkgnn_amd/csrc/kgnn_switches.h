@@ -37,6 +37,7 @@ struct Switches {        // (bool: is set, or on unless the value starts with '0
                                     //   1 = its dW1 half on the helper stream behind the pre-pass's fork, in front of the deferred reduction;
                                     //   2 (unset) = the helper forked in front of the pre-pass for it: it runs beside the pre-pass
     bool bn_one_launch;       // MKGNN_BN_ONE_LAUNCH=1 (starts with '1'): batch norm statistics | grid barrier | apply in one launch (it lost)
+    bool bn_merge;            // MKGNN_BN_MERGE=0: the batch norm merges its block partials in the loop form at every width (A/B; the same bits)
     char helper_priority;     // MKGNN_HELPER_PRIORITY=low / high (first character): the helper streams at the least / greatest priority (0: default)
     int fwd_pp;               // MKGNN_FWD_PP: 1 = ping-pong forward blocks where they apply (unset: MKGNN_FWD_PP_DEFAULT)
     bool fwd_pp_env;          //   ... set to a non-zero value in the environment: no pre-split rows
@@ -64,6 +65,7 @@ inline const Switches& switches() {
         s.bank_stream = not_0("MKGNN_BANK_STREAM"); s.fwd_stream = not_0("MKGNN_FWD_STREAM"); s.bf16_stream = not_0("MKGNN_BF16_STREAM");
         s.rows_split = not_0("MKGNN_ROWS_SPLIT"); s.grad_blocks = not_0("MKGNN_GRAD_BLOCKS"); s.tail_project_in_prepass = number("MKGNN_TAIL_PROJECT_IN_PREPASS", 2);
         if (const char* e = getenv("MKGNN_BN_ONE_LAUNCH")) s.bn_one_launch = e[0] == '1';
+        s.bn_merge = not_0("MKGNN_BN_MERGE");
         if (const char* e = getenv("MKGNN_HELPER_PRIORITY")) s.helper_priority = e[0];
         s.fwd_pp = number("MKGNN_FWD_PP", MKGNN_FWD_PP_DEFAULT); s.fwd_pp_env = number("MKGNN_FWD_PP", 0) != 0;
         s.fwd_split = number("MKGNN_FWD_SPLIT", MKGNN_FWD_SPLIT_DEFAULT); s.bwd_split = number("MKGNN_BWD_SPLIT", MKGNN_BWD_SPLIT_DEFAULT);
