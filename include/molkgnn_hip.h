@@ -856,6 +856,44 @@ int64_t mkgnn_adamw_state_floats(int64_t numel);
 int mkgnn_adamw_step(const mkgnn_adamw_tensor* tensors, int32_t n_tensors, const mkgnn_adamw_group* groups,
                      int32_t n_groups, void* stream);
 
+/* The same step with the gradients clipped by their global norm and, optionally, skipped when that norm is not finite -- both
+ * decided on the device (ABI v8, additive: the three declarations above are unchanged).
+ *
+ * A tensor is STEPPED when its active flag is absent or does not read 0.  For a stepped tensor gg = fl32(+-grad * grad_scale),
+ * element by element (maximize's sign first, then the group's scale: the value mkgnn_adamw_step forms).  S = sum of gg^2 over all
+ * elements of all stepped tensors of the WHOLE table (not per launch of 80 tensors), accumulated in float64 in a fixed order;
+ * norm = sqrt(S), non-finite if and only if some gg is; coef = fl32(min(1, max_norm / (norm + 1e-6))) evaluated in double, a NaN
+ * kept: torch.nn.utils.clip_grad_norm_'s formula.  The update is mkgnn_adamw_step's with fl32(gg * coef) in place of gg: one
+ * more float32 multiply, nothing else reordered -- a step with coef = 1 is bit for bit mkgnn_adamw_step's (tested over three
+ * steps of a 161-tensor table).  grad is NOT written back (unlike clip_grad_norm_, the clip lives in the step).
+ * max_norm = +inf: coef = 1, the norm and the guard without clipping.
+ *
+ * skip_nonfinite != 0 and norm not finite: the step does not happen -- no parameter, moment, canonical or per-block step count
+ * changes by a bit, stats[2] goes up by one, and the next finite step continues from the old counts.  skip_nonfinite == 0: as
+ * torch does, an infinite norm gives coef = 0 (the infinite elements become NaN, the rest 0), a NaN norm coef = NaN.
+ *
+ * stats [4 floats, device]: [0] fl32(norm), the pre-clip norm clip_grad_norm_ returns; [1] coef; [2] the running count of skipped
+ * steps (the caller zeroes it once; this call only ever adds one); [3] reserved, not touched.  One workgroup writes them.
+ *
+ * workspace [mkgnn_adamw_clip_workspace_bytes(tensors, n_tensors) bytes, 8-byte aligned, device]: one float64 partial per
+ * 1024-element block of the table and one more double.  Every byte of it that a call reads the same call has written: it needs
+ * no initialisation and may be shared by calls that do not overlap in time.  The size is a function of the numel fields alone
+ * (host only, no GPU needed; 0 for an empty table).
+ *
+ * Launches, all on `stream`, all capturable, no atomics, no cooperative launch, no flag a workgroup waits on, no host round
+ * trip: one partial-sum launch per 80 tensors; then, only when the table has more than MKGNN_ADAMW_CLIP_PROLOGUE_BLOCKS blocks,
+ * a one-workgroup launch that reduces the partials to one double; then one update launch per 80 tensors, every block of which
+ * adds up the partials (or reads that double) in its prologue.  So a model of up to 80 tensors takes two launches.
+ *
+ * max_norm must be > 0 or +inf; a NaN, zero or negative max_norm, a workspace that is null, misaligned or shorter than
+ * mkgnn_adamw_clip_workspace_bytes says, a null stats, and everything mkgnn_adamw_step refuses return non-zero with
+ * mkgnn_last_error set before any launch. */
+#define MKGNN_ADAMW_CLIP_PROLOGUE_BLOCKS 512
+size_t mkgnn_adamw_clip_workspace_bytes(const mkgnn_adamw_tensor* tensors, int32_t n_tensors);
+int mkgnn_adamw_step_clipped(const mkgnn_adamw_tensor* tensors, int32_t n_tensors, const mkgnn_adamw_group* groups,
+                             int32_t n_groups, float max_norm, int32_t skip_nonfinite, void* workspace, size_t workspace_bytes,
+                             float* stats, void* stream);
+
 /* ---- Molecule-resident small-batch step (ABI v4).
  *
  * At the reference's own batch sizes (README.md:81 `--batch_size 16`, data.py:236 default 17; BASELINE configs[0] / [2]) a

@@ -245,6 +245,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_readout_backward", "mkgnn_batchnorm_workspace_bytes", "mkgnn_batchnorm_forward",
            "mkgnn_batchnorm_backward", "mkgnn_bce_head_workspace_bytes", "mkgnn_bce_head_forward",
            "mkgnn_bce_head_backward", "mkgnn_rf_workspace_bytes", "mkgnn_rf_count", "mkgnn_rf_fill", "mkgnn_adamw_step", "mkgnn_adamw_state_floats",
+           "mkgnn_adamw_clip_workspace_bytes", "mkgnn_adamw_step_clipped",
            "mkgnn_bce_head_dropout_forward", "mkgnn_bce_head_dropout_backward", "mkgnn_segment_sum_block_rows",
            "mkgnn_plan_workspace_bytes", "mkgnn_plan_build", "mkgnn_plan_present_blocks", "mkgnn_backward_grad_blocks",
            "mkgnn_debug_grad_blocks_launches", "mkgnn_debug_poison_backward", "mkgnn_backward_join", "mkgnn_backward_streams", "mkgnn_bank_prepare", "mkgnn_bank_prepare_deferred", "mkgnn_bank_prepare_flush", "mkgnn_bank_prepare_withdraw", "mkgnn_touch_hint", "mkgnn_expand_batch", "mkgnn_bce_head_fused", "mkgnn_collate_compact", "mkgnn_collate_compact_bytes",
@@ -544,6 +545,10 @@ def load() -> C.CDLL:
     lib.mkgnn_adamw_state_floats.restype = C.c_int64
     lib.mkgnn_adamw_state_floats.argtypes = [I64]
     lib.mkgnn_adamw_step.argtypes = [P, I32, P, I32, P]
+    lib.mkgnn_adamw_clip_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_adamw_clip_workspace_bytes.argtypes = [P, I32]
+    lib.mkgnn_adamw_step_clipped.restype = C.c_int
+    lib.mkgnn_adamw_step_clipped.argtypes = [P, I32, P, I32, C.c_float, I32, P, C.c_size_t, P, P]
     lib.mkgnn_molecule_supported.restype = C.c_int
     lib.mkgnn_molecule_supported.argtypes = [C.POINTER(MoleculeNet), I32]
     lib.mkgnn_molecule_workspace_bytes.restype = C.c_size_t

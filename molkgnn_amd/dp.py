@@ -13,6 +13,11 @@ bank's gradients ``None`` on that rank only.  The flat buffer therefore has a fi
 every parameter that CAN receive a gradient, zero-filled where this rank has none, so all
 ranks always reduce the same layout; a flag per parameter rides along so that every rank knows
 which parameters had a gradient somewhere.
+
+Gradient clipping by global norm and the non-finite guard (``FusedAdamW(max_grad_norm=..., skip_nonfinite=...)``) need
+nothing here: the step reads the all-reduced gradients with ``grad_scale = 1 / world`` and the same flags on every rank, so
+every rank forms the same sum of squares bit for bit, hence the same coefficient and the same decision to skip -- the
+replicas cannot drift apart over a clipped or a skipped step.
 """
 from __future__ import annotations
 

@@ -7,9 +7,14 @@ same update formula; the ~80 small tensors of the model are updated by one kerne
 (``csrc/kgnn_optim.hip``).  The step counters live on the device, so a step can be captured in a hipGraph; a
 learning-rate schedule reaches a captured step through ``lr`` given as a 0-dim CUDA tensor that the scheduler fills.
 fp32 CUDA parameters only; no CPU path (``MolKGNNLibraryError`` otherwise).
+
+``max_grad_norm`` / ``skip_nonfinite`` (both off by default: the step above, the same launch and the same bits) clip the
+gradients by their global norm and skip a step whose norm is not finite, inside the step and on the device
+(``mkgnn_adamw_step_clipped``): one more launch, nothing read back, capturable.
 """
 from __future__ import annotations
 
+import math
 from typing import List
 
 import torch
@@ -19,7 +24,18 @@ from . import _lib
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, maximize: bool = False,
-                 grad_scale: float = 1.0):
+                 grad_scale: float = 1.0, max_grad_norm=None, skip_nonfinite: bool = False):
+        """``max_grad_norm``: the gradients of one step are scaled by ``min(1, max_grad_norm / (norm + 1e-6))``, ``norm`` the
+        2-norm of ALL gradients the step reads, across the parameter groups, each after its group's ``maximize`` and
+        ``grad_scale`` -- ``torch.nn.utils.clip_grad_norm_``'s coefficient.  Unlike ``clip_grad_norm_`` the clip lives in the
+        step: ``.grad`` is NOT written back, a gradient read after ``step()`` is the unclipped one.  ``skip_nonfinite``: a step
+        whose norm is ``inf`` or NaN does not happen -- no parameter, moment or step count changes by a bit, and
+        ``skipped_steps`` goes up by one; decided on the device, so it works in a captured step.  Without it a non-finite norm
+        does what torch does (an infinite norm zeroes the finite gradients and turns the infinite ones into NaN; a NaN norm turns
+        all of them into NaN).  ``max_grad_norm=None`` with the guard on: the norm and the guard, no clipping.  ``grad_norm``
+        (the norm before clipping), ``clip_coef`` and ``skipped_steps`` are 0-dim CUDA tensors filled by the step; reading them
+        does not synchronise until their value is asked for.  Both settings are attributes of the optimiser, not keys of
+        ``param_groups`` (the norm spans the groups): ``state_dict()`` does not carry them."""
         if not isinstance(lr, torch.Tensor) and lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
@@ -34,6 +50,15 @@ class FusedAdamW(torch.optim.Optimizer):
                                       grad_scale=grad_scale))
         if len(self.param_groups) > 4:
             raise ValueError("FusedAdamW takes at most 4 parameter groups")
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:                      # (a NaN is refused here as well)
+                raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (> 0, or None)")
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clip_stats = None                              # [norm, coef, skipped steps, reserved] on the device
+        self._clip_ws = None                                 # one double per 1024-element block of the table, and one more
+        self._clip_need = 0
         self._table_key = None
         self._table = None
         self._active: dict = {}
@@ -54,6 +79,50 @@ class FusedAdamW(torch.optim.Optimizer):
         self._table_key = None
         self._ver += 1
         self.prepare_state(list(flags))                      # flagged parameters are stepped on the device's say-so: state must exist
+
+    # -- clipping: workspace and stats of mkgnn_adamw_step_clipped --
+    @property
+    def clipping(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _clip_buffers(self, dev, need: int):
+        """(workspace, stats) on ``dev``, the workspace of at least ``need`` bytes; allocated outside any capture."""
+        if self._clip_stats is None or self._clip_stats.device != dev or self._clip_ws.numel() * 8 < need:
+            if torch.cuda.is_current_stream_capturing():
+                # (a zero fill of the stats recorded into a graph would reset skipped_steps at every replay)
+                raise _lib.MolKGNNLibraryError(
+                    "FusedAdamW: the clipping workspace would be allocated inside a hipGraph capture -- call prepare_state() (or "
+                    "run one eager step in which every parameter has a gradient) before capturing")
+            if self._clip_stats is None or self._clip_stats.device != dev:
+                self._clip_stats = torch.zeros(4, dtype=torch.float32, device=dev)
+            self._clip_ws = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=dev)
+        return self._clip_ws, self._clip_stats
+
+    def _stat(self, i: int) -> torch.Tensor:
+        if not self.clipping:
+            raise RuntimeError("FusedAdamW: grad_norm / clip_coef / skipped_steps exist with max_grad_norm or skip_nonfinite set")
+        if self._clip_stats is None:
+            ps = [p for g in self.param_groups for p in g["params"] if p.numel()]
+            if not ps:
+                raise RuntimeError("FusedAdamW: no parameters")
+            _lib.require_gpu_tensor(ps[0], "parameter")
+            self._clip_buffers(ps[0].device, 8 * (sum((p.numel() + 1023) // 1024 for p in ps) + 1))
+        return self._clip_stats[i]
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """The global gradient norm of the last step before clipping (what ``clip_grad_norm_`` returns), a 0-dim CUDA tensor."""
+        return self._stat(0)
+
+    @property
+    def clip_coef(self) -> torch.Tensor:
+        """The coefficient the last step multiplied its gradients by, a 0-dim CUDA tensor."""
+        return self._stat(1)
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        """How many steps ``skip_nonfinite`` has skipped so far, a 0-dim CUDA tensor (float32)."""
+        return self._stat(2)
 
     # -- state: one buffer per parameter, [exp_avg | exp_avg_sq | step | 2 reserved | a step count per 1024 elements]
     # (mkgnn_adamw_state_floats); the three state entries are views of it --
@@ -96,6 +165,8 @@ class FusedAdamW(torch.optim.Optimizer):
             if p.numel():
                 _lib.require_gpu_tensor(p, "parameter")
                 self._packed_state(p)
+        if self.clipping:                                    # the workspace of a step in which every parameter has a gradient
+            self._stat(0)
 
     def state_dict(self):
         sd = super().state_dict()                            # the packed buffer is an implementation detail: its three views are saved
@@ -163,6 +234,7 @@ class FusedAdamW(torch.optim.Optimizer):
             for e, r in zip(table, rows):
                 e.param, e.grad, e.state, e.numel, e.group, e.active = r
             self._table, self._table_key = table, key
+            self._clip_need = int(lib.mkgnn_adamw_clip_workspace_bytes(table, len(rows))) if self.clipping else 0
         groups = (_lib.AdamWGroup * len(self.param_groups))()
         for e, group in zip(groups, self.param_groups):
             lr = group["lr"]
@@ -179,7 +251,16 @@ class FusedAdamW(torch.optim.Optimizer):
             e.eps, e.weight_decay, e.maximize = float(group["eps"]), float(group["weight_decay"]), int(bool(group["maximize"]))
             e.grad_scale = float(group.get("grad_scale", 1.0))
         with torch.cuda.device(dev):
-            _lib.check(lib.mkgnn_adamw_step(self._table, len(rows), groups, len(groups), _lib.stream_ptr(dev)),
-                       "mkgnn_adamw_step")
+            if not self.clipping:
+                _lib.check(lib.mkgnn_adamw_step(self._table, len(rows), groups, len(groups), _lib.stream_ptr(dev)),
+                           "mkgnn_adamw_step")
+            else:
+                if not self._clip_need:                      # (the settings were switched on after the table was built)
+                    self._clip_need = int(lib.mkgnn_adamw_clip_workspace_bytes(self._table, len(rows)))
+                ws, stats = self._clip_buffers(dev, self._clip_need)
+                max_norm = math.inf if self.max_grad_norm is None else float(self.max_grad_norm)
+                _lib.check(lib.mkgnn_adamw_step_clipped(self._table, len(rows), groups, len(groups), max_norm,
+                                                        int(self.skip_nonfinite), ws.data_ptr(), ws.numel() * 8, stats.data_ptr(),
+                                                        _lib.stream_ptr(dev)), "mkgnn_adamw_step_clipped")
         del keep
         return loss

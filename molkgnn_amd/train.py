@@ -488,8 +488,12 @@ def tune_torch_backends() -> None:
 
 
 def configure_optimizer(model: torch.nn.Module, weight_decay: float = 0.0, lr: float = 1e-3, fused: Optional[bool] = None,
-                        capturable: bool = False):
-    """AdamW with the kernel parameters exempt from weight decay, selected by name (model.py:373-382)."""
+                        capturable: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+    """AdamW with the kernel parameters exempt from weight decay, selected by name (model.py:373-382).
+
+    ``max_grad_norm`` / ``skip_nonfinite``: clip the gradients by their global norm (Lightning's ``gradient_clip_val`` with
+    ``gradient_clip_algorithm='norm'``) and skip a step whose norm is not finite, inside the fused step and on the device
+    (``optim.FusedAdamW``).  The ``torch.optim.AdamW`` route has neither: asking for one there is an error, not ignored."""
     decay, nodecay = [], []
     for name, p in model.named_parameters():
         if ('x_center' in name) or ('p_support' in name) or (
@@ -502,9 +506,12 @@ def configure_optimizer(model: torch.nn.Module, weight_decay: float = 0.0, lr: f
         fused = all(p.is_cuda and p.dtype == torch.float32 for p in model.parameters())
     if fused:
         from .optim import FusedAdamW     # one HIP launch for the whole model; step counters on the device (capturable)
-        opt = FusedAdamW(groups, lr=lr)
+        opt = FusedAdamW(groups, lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         opt.prepare_state()               # state exists before anything can be captured (a fill inside a graph would replay)
         return opt
+    if max_grad_norm is not None or skip_nonfinite:
+        raise ValueError("max_grad_norm / skip_nonfinite are part of the fused AdamW step (fused=True); with torch.optim.AdamW call "
+                         "torch.nn.utils.clip_grad_norm_ between backward and step")
     kw = {}
     if capturable:
         kw["capturable"] = True          # step counters live on the device: the step can be replayed from a hipGraph
