@@ -685,6 +685,17 @@ int mkgnn_backward_grad_blocks(const int8_t* present8, const int32_t num_kernels
  * mkgnn_debug_poison_backward(1): every backward call fills its contribution rows and grad_x with NaN before its first launch */
 int64_t mkgnn_debug_grad_blocks_launches(void);
 int mkgnn_debug_poison_backward(int32_t enable);
+/* tests: which kernel family every degree of a forward / backward call with these arguments would take.  The same decision the
+ * two entry points make (shapes, null-ness and alignment only: nothing is read through a pointer, nothing is launched).
+ * fwd_variant / bwd_variant as the entry points take them; want_grad_x == 0: as a backward call with grad_x == NULL.
+ *   out[0..3]   forward, per degree:  0 skip (no atoms or no kernels), 1 any-shape kernel, 2 LDS-bank kernel, 3 streamed kernel
+ *   out[4..7]   backward, per degree: 0 skip, 1 zero fill (atoms without kernels), 2 any-shape kernels, 3 per-degree LDS pair,
+ *               4 MFMA rows + LDS bank kernel, 5 streamed pair
+ *   out[8..10]  bank gradients of all degrees in one launch; the streamed rows launch; the streamed bank launch */
+int mkgnn_debug_conv_dispatch(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE], const mkgnn_degree_bucket buckets[MKGNN_MAX_DEGREE],
+                              const float* x, int64_t x_stride, int64_t out_stride, int64_t n_atoms, int32_t F, int32_t E,
+                              int32_t fwd_variant, int32_t bwd_variant, int32_t want_grad_x, const float* grad_x,
+                              int64_t grad_x_stride, int32_t out[11]);
 
 /* Tail of the training step for a single task (reference model.py:147-148, 190-198 with data.py:37):
  *     pred = graph_embedding @ ffn.weight[0] + ffn.bias;   loss = mean(BCEWithLogits(pred, target))

@@ -267,7 +267,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_embed_knn_workspace_bytes", "mkgnn_embed_count_within", "mkgnn_embed_count_within_workspace_bytes",
            "mkgnn_embed_neighbours_within", "mkgnn_embed_neighbours_within_workspace_bytes", "mkgnn_graph_components",
            "mkgnn_graph_components_workspace_bytes", "mkgnn_maxmin_pick", "mkgnn_maxmin_pick_workspace_bytes",
-           "mkgnn_tail_score_mc", "mkgnn_tail_score_mc_workspace_bytes", "mkgnn_debug_set_bn_merge")
+           "mkgnn_tail_score_mc", "mkgnn_tail_score_mc_workspace_bytes", "mkgnn_debug_set_bn_merge", "mkgnn_debug_conv_dispatch")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -325,6 +325,11 @@ def load() -> C.CDLL:
         C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p]
     lib.mkgnn_backward_streams.restype = C.c_int
     lib.mkgnn_backward_streams.argtypes = [Banks4, Buckets4, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32]
+    # diagnostics: (banks, buckets, x, x stride, out stride, atoms, F, E, forward variant, backward variant, grad x wanted, grad x,
+    # its stride, int32[11]) -> the kernel family of every degree, forward and backward; launches nothing
+    lib.mkgnn_debug_conv_dispatch.restype = C.c_int
+    lib.mkgnn_debug_conv_dispatch.argtypes = [Banks4, Buckets4, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32 * 11)]
     lib.mkgnn_tail_supported.restype = C.c_int
     lib.mkgnn_tail_supported.argtypes = [C.c_int32, C.c_int32, C.c_int32, Int32x4]
     lib.mkgnn_tail_workspace_bytes.restype = C.c_size_t

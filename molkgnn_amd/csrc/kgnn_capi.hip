@@ -964,6 +964,27 @@ int mkgnn_rows_split_supported(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE], 
     return rows_split_covered(s, plan_conv_forward(s, 0)) ? 1 : 0;
 }
 
+// Diagnostics: the family every degree of a forward / backward call with these arguments would take -- the same ConvShape and the
+// same two plan functions as the entry points, nothing enqueued.  out[0..3] FwdFamily, out[4..7] BwdFamily, out[8..10] = bank_fused,
+// rows_streamed, bank_streamed.  (variants as the entry points take them, flags masked off; want_grad_x == 0: as grad_x == NULL)
+int mkgnn_debug_conv_dispatch(const mkgnn_kernel_bank banks[MKGNN_MAX_DEGREE], const mkgnn_degree_bucket buckets[MKGNN_MAX_DEGREE],
+                              const float* x, int64_t x_stride, int64_t out_stride, int64_t n_atoms, int32_t F, int32_t E,
+                              int32_t fwd_variant, int32_t bwd_variant, int32_t want_grad_x, const float* grad_x, int64_t grad_x_stride,
+                              int32_t out[11]) {
+    const char* who = "mkgnn_debug_conv_dispatch";
+    if (!banks || !buckets || !out) return api_fail("%s: null pointer", who);
+    fwd_variant &= ~(MKGNN_VARIANT_BLOCK_ROWS | MKGNN_VARIANT_BANK_PREPARED | MKGNN_VARIANT_ROWS_SPLIT);
+    bwd_variant &= ~(MKGNN_BACKWARD_DEFER_BANK | MKGNN_BACKWARD_THROUGH_NEIGHBOURS | MKGNN_BACKWARD_ROWS_SPLIT);
+    if (fwd_variant < 0 || fwd_variant > 3 || bwd_variant < 0 || bwd_variant > 2)
+        return api_fail("%s: variants %d / %d", who, fwd_variant, bwd_variant);
+    const FwdDispatch fwd = plan_conv_forward(conv_shape(banks, buckets, F, E, n_atoms, x, x_stride, out_stride), fwd_variant);
+    const BwdDispatch bwd = plan_conv_backward(conv_shape(banks, buckets, F, E, n_atoms, x, x_stride, 0, want_grad_x ? grad_x : nullptr,
+                                                          grad_x_stride), bwd_variant);
+    for (int i = 0; i < 4; ++i) { out[i] = fwd.deg[i]; out[4 + i] = bwd.deg[i]; }
+    out[8] = bwd.bank_fused; out[9] = bwd.rows_streamed; out[10] = bwd.bank_streamed;
+    return 0;
+}
+
 int mkgnn_backward_join(void* stream) {
     DegreeStreams* p = degree_streams();
     if (!p || !p->deferred) return 0;

@@ -706,6 +706,29 @@ def kernelsetconv(x: torch.Tensor, plan: BatchPlan, is_last_layer: bool, params:
     return out
 
 
+FORWARD_FAMILIES = ("skip", "generic", "lds_bank", "streamed")
+BACKWARD_FAMILIES = ("skip", "zero_fill", "generic", "lds_pair", "mfma_lds", "streamed")
+
+
+def debug_conv_dispatch(x: torch.Tensor, plan: BatchPlan, params: Sequence[torch.Tensor], E: int, variant: str = "auto",
+                        backward_variant: Optional[str] = None):
+    """``mkgnn_debug_conv_dispatch``: the kernel family every degree of ``kernelsetconv(x, plan, .., params, E, variant,
+    backward_variant=..)`` and of its backward (with a gradient for ``x``) would take, as
+    ``(forward names [4], backward names [4], (bank_fused, rows_streamed, bank_streamed))``.  Launches nothing."""
+    if backward_variant is None:
+        backward_variant = "generic" if variant == "generic" else "auto"
+    x = _row_major(x) if variant == "generic" else _aligned_rows(x)        # (the rows the forward call would hand to the library)
+    n, F = x.shape
+    banks, Ls, keep = _banks([p.detach() for p in params], F, E)
+    buckets = _buckets(plan, E, False)
+    K, F4 = sum(Ls), F + (-F) % 4
+    out = (_lib.C.c_int32 * 11)()
+    # grad x as the backward allocates it: rows of F4 floats from the caching allocator (16-byte aligned) -- only its alignment counts
+    _lib.check(_lib.load().mkgnn_debug_conv_dispatch(banks, buckets, x.data_ptr(), _stride0(x), K + (-K) % 4, n, F, E, VARIANTS[variant],
+                                                     BACKWARD_VARIANTS[backward_variant], 1, 16, F4, out), "mkgnn_debug_conv_dispatch")
+    return ([FORWARD_FAMILIES[v] for v in out[0:4]], [BACKWARD_FAMILIES[v] for v in out[4:8]], tuple(int(v) for v in out[8:11]))
+
+
 _INV_ATTR = "_mkgnn_inv_norm"
 
 

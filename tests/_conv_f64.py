@@ -208,6 +208,40 @@ BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
 
 
+def register(cases):
+    """Cases of another table (tests/_conv_families.py) that ``build`` serves too; ``CASES`` -- what the any-shape modules run --
+    stays as it is."""
+    for c in cases:
+        assert BY_NAME.get(c.name, c) is c, c.name
+        BY_NAME[c.name] = c
+
+
+# Which kernels the automatic dispatch gives the cases above at F <= STREAM_MAX_F, as ``mkgnn_debug_conv_dispatch`` answers (read off
+# plan_conv_forward / plan_conv_backward, csrc/kgnn_capi.hip; the letters: ``dispatch_string`` below): forward / backward per degree /
+# bank_fused, rows_streamed, bank_streamed.  Rows of at most 160 floats, bonds of at most 8 and banks within the streamed kernels'
+# tables (<= 64 kernels of degree 4, <= 8 column parts) take the streamed kernels; one degree outside them takes every degree's
+# backward off the streamed pair, and past 112 floats (or at an odd width) round 1's kernels take nothing.
+_ALL_STREAMED = "SSSS/SSSS/111"
+_NOTHING_FAST = "gggg/gggg/000"
+AUTO_DISPATCH = {
+    **{f"width_f{F}": _ALL_STREAMED for F in (1, 2, 3, 63, 64, 65, 127, 128, 129, 160)},
+    **{f"bond_e{E}_f{F}": _ALL_STREAMED for E in (1, 8) for F in (20, 129)},
+    **{f"bond_e{E}_f{F}": _NOTHING_FAST for E in (9, 63, 64) for F in (20, 129)},
+    # 65 kernels of degree 3 are three column parts: 4 + 2 + 3 + 1 = 10 groups
+    "counts_63_64_65_6_f5": _ALL_STREAMED, "counts_63_64_65_6_f130": _ALL_STREAMED,
+    # 129 kernels of degree 1: nine column parts, the streamed kernels hold eight; round 1's forward splits them over two waves
+    # (five column tiles each); no backward but the any-shape one takes 129 (or an odd width, or 130 floats)
+    "counts_129_1_0_17_f5": "LS-S/ggzg/000", "counts_129_1_0_17_f130": "gS-S/ggzg/000",
+    "counts_0_0_0_5_f5": "---S/zzzS/111", "counts_0_0_0_5_f130": "---S/zzzS/111",
+    "counts_1_1_1_1_f5": _ALL_STREAMED, "counts_1_1_1_1_f130": _ALL_STREAMED,
+    **{f"table_l4_{L4}": _ALL_STREAMED for L4 in (5, 6, 16, 17)},
+    **{f"atoms_n4_{N4}": "S--S/S--S/111" for N4 in (1, 2, 255, 256, 257)},
+    "atoms_without_kernels": "S-SS/SzSS/111",
+    "grid_stride_last0": "SS-S/SS-S/111", "grid_stride_last1": "SS-S/SS-S/111",        # (no atom of degree 3)
+    "clamp_f129": _ALL_STREAMED, "chirality_f65": _ALL_STREAMED, "chirality_f129": _ALL_STREAMED,
+}
+
+
 def _star_centres(cpu):
     """Positions in the degree-4 bucket of the atoms whose four neighbours are all leaves (the centres of ``star(4)``)."""
     deg = T.degrees(cpu)
@@ -243,7 +277,7 @@ def _tweak_chirality(case, cpu, layer, x, g):
     stops short of it sees four equal rows and answers +1.  C: coplanar neighbours (every z equal; small integers, so the triple
     product is exactly zero in any precision and matches no kernel's sign)."""
     F = case.F
-    col = {65: 64, 129: 128, 256: 200}[F]
+    col = {32: 20, 112: 100, 65: 64, 129: 128, 256: 200}[F]
     kA, kB, kC = _star_centres(cpu)[:3]
     nei = cpu.nei_index_deg4.reshape(-1, 4)
     r = torch.randn(F, generator=g)
@@ -412,6 +446,7 @@ def run_build(built, dev, variant, bwd_variant, prepared=None):
     if bwd_variant == "fast" and not fast_backward_covers(plan, params, x, E):
         bwd_variant = "auto"
     layer.variant, layer.backward_variant = variant, bwd_variant
+    dispatch = dispatch_string(Fn.debug_conv_dispatch(x.detach(), plan, params, E, variant, bwd_variant))
     before = streamed_launches()
     out_d, saved = Fn.kernelsetconv_details(x.detach(), plan, case.last, params, E, variant)
     out = layer._run(x, plan, case.last, prepared=prepared)
@@ -424,7 +459,89 @@ def run_build(built, dev, variant, bwd_variant, prepared=None):
                            scores=[None if s[1] is None else s[1].cpu() for s in saved],
                            chir=[None if s[2] is None else s[2].cpu() for s in saved],
                            gx=x.grad.detach().cpu(), grads=grads, streamed=tuple(a - b for a, b in zip(after, before)),
-                           backward=bwd_variant)
+                           backward=bwd_variant, dispatch=dispatch)
+
+
+FWD_LETTERS = {"skip": "-", "generic": "g", "lds_bank": "L", "streamed": "S"}
+BWD_LETTERS = {"skip": "-", "zero_fill": "z", "generic": "g", "lds_pair": "P", "mfma_lds": "M", "streamed": "S"}
+
+
+def dispatch_string(answer) -> str:
+    """``functional.debug_conv_dispatch``'s answer as ``"SSSS/SSSS/111"``: a letter per degree for the forward (``-`` skip, ``g`` the
+    any-shape kernel, ``L`` round 1's LDS-bank kernel, ``S`` the streamed kernel) and for the backward (``-`` skip, ``z`` zero fill,
+    ``g`` any-shape, ``P`` the per-degree LDS pair, ``M`` MFMA rows + LDS bank kernel, ``S`` the streamed pair), then
+    ``bank_fused``, ``rows_streamed``, ``bank_streamed``."""
+    fwd, bwd, flags = answer
+    return "".join(FWD_LETTERS[f] for f in fwd) + "/" + "".join(BWD_LETTERS[b] for b in bwd) + "/" + "".join(str(int(v)) for v in flags)
+
+
+def check_streamed_counters(dispatch: str, streamed, tag) -> None:
+    """The three streamed launch counters against the dispatch's answer: the forward's advanced iff some degree is ``streamed``,
+    the rows kernel's iff ``rows_streamed``, the bank kernel's iff ``bank_streamed``."""
+    fwd, _, flags = dispatch.split("/")
+    assert (streamed[0] > 0) == ("S" in fwd), (tag, dispatch, streamed)
+    assert (streamed[1] > 0) == (flags[1] == "1"), (tag, dispatch, streamed)
+    assert (streamed[2] > 0) == (flags[2] == "1"), (tag, dispatch, streamed)
+
+
+def own_block_mask(built):
+    """[N, K] bool: column k belongs to the degree block of atom n."""
+    n, K = built.cot.shape
+    own = torch.zeros(n, K, dtype=torch.bool)
+    off = 0
+    for d in range(1, 5):
+        L = built.info.counts[d - 1]
+        own[getattr(built.cpu, f"selected_index_deg{d}"), off:off + L] = True
+        off += L
+    return own
+
+
+def check_against_float64(built, res, tag, oracle=None):
+    """What one run of a case (``run_build``'s result) must satisfy, whatever kernels ran -- the body of
+    tests/test_conv_anyshape_f64.py::test_case_against_float64, shared with tests/test_conv_families_gpu.py: nothing non-finite,
+    both output storages equal, zeros outside an atom's own block, the tie-aware criterion at ``FWD_TOL``, the three scores kept
+    for backward through ``tests/_f64.check`` at the build's permutation, chirality signs exactly, every gradient per element
+    within ``case.bound * sum |terms|`` of the float64 closed form, no gradient for a degenerate degree, and a tweak's marks.
+    ``oracle``: ``oracle_gradients_f64(built, res.idx)`` where the caller has it already.  Returns ``(worst err / lim, oracle)``."""
+    from tests.test_scale_parity import FWD_TOL
+    case, info = built.case, built.info
+    # ---- forward
+    assert torch.isfinite(res.out).all() and torch.isfinite(res.gx).all()
+    assert torch.equal(res.out, res.out_details)          # (padded and contiguous output storage: the same scores)
+    assert bool((res.out[~own_block_mask(built)] == 0).all())
+    per_degree = O.kernelset_params(built.state)
+    assert O.kernelset_tie_aware_mismatch(per_degree, built.x, built.cpu, case.last, res.out, res.idx, tol=FWD_TOL) == 0
+    # ---- the scores kept for backward, at the build's permutation
+    s32, s64 = pair_scores(built, res.idx, torch.float32), pair_scores(built, res.idx, torch.float64)
+    checked = 0
+    for d in range(4):
+        active = info.n[d] > 0 and info.counts[d] > 0
+        assert (res.scores[d] is not None) == active and (res.idx[d] is not None) == active, (tag, d)
+        if not active:
+            continue
+        names = ("support", "centre", "edge")
+        got = {f"deg{d + 1}.{nm}": res.scores[d][k] for k, nm in enumerate(names)}
+        checked += _f64.check(got, {f"deg{d + 1}.{nm}": s32[d][nm] for nm in names}, {f"deg{d + 1}.{nm}": s64[d][nm] for nm in names},
+                              list(tag) + ["pair scores"])
+        if d == 3 and case.last:
+            assert torch.equal(res.chir[3].double(), s64[3]["chirality"]), tag
+        else:
+            assert res.chir[d] is None
+    assert checked == 3 * sum(1 for n, L in zip(info.n, info.counts) if n and L)
+    if case.tweak == "chirality":
+        ch = res.chir[3]
+        assert bool((ch[:, info.kA] == 1).all()) and bool((ch[:, info.kB] == -1).any()) and bool((ch[:, info.kC] == -1).all()), tag
+    # ---- gradients, per element
+    if oracle is None:
+        oracle = oracle_gradients_f64(built, res.idx)
+    print(tag, "by group:", worst_by_group(res.gx, res.grads, oracle), "streamed launches:", res.streamed, "backward:", res.backward)
+    worst = _check_gradients_f64(res.gx, res.grads, oracle, tag, bound=case.bound, expect=expected_gradients(built))
+    # ---- degenerate buckets: a degree without atoms, or without kernels, has no gradient at all (not a zero one); atoms without
+    # kernels get a row of zeros and an x-gradient from their neighbours only
+    for d in range(4):
+        if info.n[d] == 0 or info.counts[d] == 0:
+            assert not any(k.startswith(f"trainable_kernelconv_set.{d}.") for k in res.grads), (tag, d, sorted(res.grads))
+    return worst, oracle
 
 
 def fast_backward_covers(plan, params, x, E) -> bool:

@@ -11,7 +11,8 @@ the automatic dispatch:
 * the three scores the kernels keep for backward against the float64 oracle at the build's permutation (``tests/_f64.check``), the
   chirality sign exactly;
 * grad x, every parameter gradient and the score weights per element within ``32 * 2^-24 * sum |terms|`` of the float64 closed form;
-* which kernels ran (the streamed launch counters).
+* which kernels ran: the streamed launch counters, and under the automatic dispatch at F <= 160 the family of every degree
+  (``mkgnn_debug_conv_dispatch`` against ``tests/_conv_f64.AUTO_DISPATCH``).
 
 Beside the table: banks prepared ahead (``prepare_banks``, direct and deferred) give the same bits, two runs give the same bits,
 and shapes outside the ABI's limits are refused before anything is written.
@@ -21,10 +22,7 @@ import copy
 import pytest
 import torch
 
-from oracle import kgnn_oracle as O
 from tests import _conv_f64 as C
-from tests import _f64
-from tests.test_scale_parity import FWD_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -37,66 +35,25 @@ def _dev():
     return torch.device("cuda:0")
 
 
-def _own_block_mask(built):
-    """[N, K] bool: column k belongs to the degree block of atom n."""
-    n, K = built.cot.shape
-    own = torch.zeros(n, K, dtype=torch.bool)
-    off = 0
-    for d in range(1, 5):
-        L = built.info.counts[d - 1]
-        own[getattr(built.cpu, f"selected_index_deg{d}"), off:off + L] = True
-        off += L
-    return own
-
-
 @pytest.mark.parametrize("path", C.PATHS, ids=PATH_IDS)
 @pytest.mark.parametrize("name", NAMES)
 def test_case_against_float64(name, path):
     dev = _dev()
     built = C.build(name)
-    case, info = built.case, built.info
+    case = built.case
     res = C.run_build(built, dev, *path)
     tag = (name, path[0])
-    # ---- forward
-    assert torch.isfinite(res.out).all() and torch.isfinite(res.gx).all()
-    assert torch.equal(res.out, res.out_details)          # (padded and contiguous output storage: the same scores)
-    assert bool((res.out[~_own_block_mask(built)] == 0).all())
-    per_degree = O.kernelset_params(built.state)
-    assert O.kernelset_tie_aware_mismatch(per_degree, built.x, built.cpu, case.last, res.out, res.idx, tol=FWD_TOL) == 0
-    # ---- the scores kept for backward, at the build's permutation
-    s32, s64 = C.pair_scores(built, res.idx, torch.float32), C.pair_scores(built, res.idx, torch.float64)
-    checked = 0
-    for d in range(4):
-        active = info.n[d] > 0 and info.counts[d] > 0
-        assert (res.scores[d] is not None) == active and (res.idx[d] is not None) == active, (tag, d)
-        if not active:
-            continue
-        names = ("support", "centre", "edge")
-        got = {f"deg{d + 1}.{nm}": res.scores[d][k] for k, nm in enumerate(names)}
-        checked += _f64.check(got, {f"deg{d + 1}.{nm}": s32[d][nm] for nm in names}, {f"deg{d + 1}.{nm}": s64[d][nm] for nm in names},
-                              list(tag) + ["pair scores"])
-        if d == 3 and case.last:
-            assert torch.equal(res.chir[3].double(), s64[3]["chirality"]), tag
-        else:
-            assert res.chir[d] is None
-    assert checked == 3 * sum(1 for n, L in zip(info.n, info.counts) if n and L)
-    if case.tweak == "chirality":
-        ch = res.chir[3]
-        assert bool((ch[:, info.kA] == 1).all()) and bool((ch[:, info.kB] == -1).any()) and bool((ch[:, info.kC] == -1).all()), tag
-    # ---- gradients, per element
-    oracle = C.oracle_gradients_f64(built, res.idx)
-    print(tag, "by group:", C.worst_by_group(res.gx, res.grads, oracle), "streamed launches:", res.streamed, "backward:", res.backward)
-    worst = C._check_gradients_f64(res.gx, res.grads, oracle, tag, bound=case.bound, expect=C.expected_gradients(built))
-    # ---- degenerate buckets: a degree without atoms, or without kernels, has no gradient at all (not a zero one); atoms without
-    # kernels get a row of zeros and an x-gradient from their neighbours only
-    for d in range(4):
-        if info.n[d] == 0 or info.counts[d] == 0:
-            assert not any(k.startswith(f"trainable_kernelconv_set.{d}.") for k in res.grads), (tag, d, sorted(res.grads))
+    worst, oracle = C.check_against_float64(built, res, tag)
     # ---- which kernels ran
     if path[0] == "generic":
         assert res.streamed == (0, 0, 0) and res.backward == "generic", (tag, res.streamed)
     elif case.F > C.STREAM_MAX_F:
         assert res.streamed == (0, 0, 0) and res.backward == "auto", (tag, res.streamed)
+    else:
+        # the automatic dispatch where the fast kernels exist: the families the plan functions name for this case, and the streamed
+        # launch counters' agreement with them (a case meant for the fast path that lands on the any-shape kernels fails here)
+        assert res.dispatch == C.AUTO_DISPATCH[name], (tag, res.dispatch)
+        C.check_streamed_counters(res.dispatch, res.streamed, tag)
     C.record({"case": name, "edge": case.edge, "path": path[0], "backward": res.backward, "streamed": list(res.streamed),
               "worst": worst, **C.worst_by_group(res.gx, res.grads, oracle)})
 
