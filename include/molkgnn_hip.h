@@ -794,6 +794,63 @@ int mkgnn_task_head_fused(int32_t loss_kind, const float* emb, int64_t emb_strid
                           float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
                           float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (additive; the ABI version stays 8) The task-indexed head with a weighted loss: a sample weight s_i per row and a positive
+ * weight p_t per task (torch's binary_cross_entropy_with_logits(x, y, weight = s, pos_weight = p), reduction 'mean').  For a
+ * labelled row with logit x, target y and task t:
+ *     BCE, pos_weight NULL :  term = s_i * (max(x, 0) - x y + log1p(e^-|x|))                    d term / d x = s_i * (sigmoid(x) - y)
+ *     BCE, pos_weight      :  L = 1 + (p_t - 1) y;  term = s_i * ((1 - y) x + L (log1p(e^-|x|) + max(-x, 0)))
+ *                                                                                              d term / d x = s_i * ((1 - y) - L sigmoid(-x))
+ *     squared error        :  term = s_i * (x - y)^2                                           d term / d x = s_i * 2 (x - y)
+ *     loss = sum of the labelled rows' terms / max(n_labelled, 1)     (SQERR_SUM: no division; NOT divided by the sum of the weights)
+ * Without pos_weight the term and its derivative are the unweighted entry points' multiplied by s_i FIRST (before grad_loss and
+ * 1 / n_labelled), so weights that are all exactly 1.0f give the unweighted bits.  Weights are plain multipliers and constants:
+ * a zero weight gives a zero contribution (and an all-zero grad_emb row), a NaN weight on a labelled row propagates, a weight of
+ * an unlabelled row or of a row >= n_rows is never used.  pos_weight with a squared-error kind is an error.
+ * mkgnn_task_head_weighted_forward / _backward / _fused take the arguments of mkgnn_task_head_forward / _backward / _fused and
+ * `weights` before the workspace; same workspace (mkgnn_task_head_workspace_bytes), same dropout generator protocol, same two
+ * launches, same fixed-order sums, same limits.  In these three entry points only, task == NULL means "every row has task 0" and
+ * requires T == 1 and row_ids == NULL (n_task is then not looked at): how a single-task model uses the same kernels.  weights ==
+ * NULL, or sample_weight and pos_weight both NULL, with task != NULL: the outputs of the unweighted entry point bit for bit (its
+ * own kernels are launched).  Refused before any launch, with mkgnn_last_error set: an unknown loss kind, pos_weight with a
+ * squared-error kind, task == NULL with T != 1, a non-NULL sample_weight with n_sample_weight < 1 (weight_ids given) or
+ * < n_rows (not given), and everything the unweighted entry points refuse (n_rows < 1 among it).  No atomics, no process-wide
+ * state, capturable, launched on `stream`. */
+typedef struct mkgnn_loss_weights {
+    const float*   sample_weight;    /* NULL: every row 1 */
+    const int32_t* weight_ids;       /* NULL: sample_weight[i]; else sample_weight[weight_ids[i]], outside [0, n_sample_weight): +0.0 */
+    int64_t        n_sample_weight;
+    const float*   pos_weight;       /* NULL: 1; [T]; BCE only */
+} mkgnn_loss_weights;
+int mkgnn_task_head_weighted_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                                     const float* weight, const float* bias, const float* target, const int32_t* task,
+                                     const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state,
+                                     int64_t* rng_used, float* pred, float* loss, const mkgnn_loss_weights* weights,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int mkgnn_task_head_weighted_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                                      const float* weight, const float* target, const int32_t* task, const int32_t* row_ids,
+                                      int64_t n_task, const float* pred, const float* grad_loss, float dropout_p,
+                                      const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
+                                      float* grad_bias, const mkgnn_loss_weights* weights, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+int mkgnn_task_head_weighted_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                                   const float* weight, const float* bias, const float* target, const int32_t* task,
+                                   const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state,
+                                   int64_t* rng_used, float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride,
+                                   float* grad_weight, float* grad_bias, const mkgnn_loss_weights* weights, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+/* (additive; the ABI version stays 8) mkgnn_tail_fused_readout_dropout with that weighted loss: a sample weight per molecule
+ * gi < args->n_loss_mols (sample_weight[gi], or sample_weight[weight_ids[gi]]) and ONE positive weight, pos_weight[0] (the tail is
+ * single-task).  Only a molecule's d loss / d logit and its loss term change -- the formulas above, the sample weight first, then
+ * the 1 / n_loss_mols of the mean kinds (the tail divides by the number of loss molecules: every one of them is labelled).  It
+ * obeys the whole pending-work protocol of mkgnn_tail_fused (defer_reduce, mkgnn_tail_defer_projection, mkgnn_tail_flush; what an
+ * earlier call left pending is launched before its own first launch), the same generator advance and the same MKGNN_TAIL_MAX_*
+ * rule.  weights == NULL, or sample_weight and pos_weight both NULL: mkgnn_tail_fused_readout_dropout bit for bit (its kernels are
+ * launched); sample weights that are all exactly 1.0f without pos_weight: its bits too.  Refused before any launch: pos_weight with
+ * a squared-error kind, a non-NULL sample_weight with n_sample_weight < 1 (weight_ids given) or < n_loss_mols (not given), and
+ * everything mkgnn_tail_fused_readout_dropout refuses. */
+int mkgnn_tail_fused_weighted(const mkgnn_tail_args* args, float readout_dropout_p, const mkgnn_loss_weights* weights,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* (additive; the ABI version stays 8) Every task's logit of every row -- the T-output ffn behind the readout in evaluation mode,
  * for ranking a library per assay:
  *     pred[i * pred_row_stride + t * pred_task_stride] = emb_i . weight[t] + bias[t]      for every i < n_rows, t < T

@@ -198,10 +198,11 @@ class MolKGNNNet(torch.nn.Module):
             # (private: train.GNNModel.loss asks for the loss itself -- readout, head, loss and all their gradients in one
             # launch, readout.tail_loss -- where that applies; it gets ("loss", value) back, or the embedding as usual)
             if want_tail and sim_sc.requires_grad and R._tail_limits_ok(seg, plan):
-                ffn, target, p_head, n_rows, *kind = _tail       # (ffn, y, dropout p, real molecules[, loss kind: "bce"])
+                # (ffn, y, dropout p, real molecules[, loss kind: "bce"[, the weighted loss's keywords of tail_loss]])
+                ffn, target, p_head, n_rows, *kind = _tail
                 loss = kind[0] if kind else "bce"
                 return ("loss", R.tail_loss(sim_sc, plan, Ls, lin1, lin2, ffn, target, seg, p_head, n_rows, loss,
-                                            readout_dropout_p=p_readout))
+                                            readout_dropout_p=p_readout, **(kind[1] if len(kind) > 1 else {})))
             if want_score and R._tail_limits_ok(seg, plan):      # ("score", pred, embedding), or the embedding as usual
                 ffn, n_rows = _score
                 return ("score", *R.tail_score(sim_sc, plan, Ls, lin1, lin2, ffn, seg, n_rows))

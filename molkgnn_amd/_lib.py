@@ -239,6 +239,12 @@ class MoleculeBatch(C.Structure):
                 ("atom_rank", C.c_void_p), ("buckets", Buckets4), ("x", C.c_void_p), ("x_stride", C.c_int64)]
 
 
+class LossWeights(C.Structure):
+    """``mkgnn_loss_weights``: the optional sample weights (direct, or a table read through ids) and per-task positive weights."""
+    _fields_ = [("sample_weight", C.c_void_p), ("weight_ids", C.c_void_p), ("n_sample_weight", C.c_int64),
+                ("pos_weight", C.c_void_p)]
+
+
 EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn_unit_rows8", "mkgnn_workspace_bytes",
            "mkgnn_kernelsetconv_forward", "mkgnn_kernelsetconv_backward", "mkgnn_segment_sum_rows",
            "mkgnn_readout_hidden_stride", "mkgnn_readout_workspace_bytes", "mkgnn_readout_forward",
@@ -259,6 +265,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_head_loss_dropout_backward", "mkgnn_head_loss_fused", "mkgnn_gather_compact",
            "mkgnn_gather_compact_workspace_bytes", "mkgnn_gather_compact_packed", "mkgnn_topk_update", "mkgnn_topk_workspace_bytes",
            "mkgnn_task_head_workspace_bytes", "mkgnn_task_head_forward", "mkgnn_task_head_backward", "mkgnn_task_head_fused",
+           "mkgnn_task_head_weighted_forward", "mkgnn_task_head_weighted_backward", "mkgnn_task_head_weighted_fused",
+           "mkgnn_tail_fused_weighted",
            "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks", "mkgnn_embed_cosine",
            "mkgnn_atom_contributions", "mkgnn_atom_contributions_workspace_bytes", "mkgnn_embed_max_cosine",
            "mkgnn_embed_max_cosine_workspace_bytes", "mkgnn_select_rows", "mkgnn_tail_defer_projection",
@@ -353,6 +361,9 @@ def load() -> C.CDLL:
     lib.mkgnn_atom_contributions.argtypes = [C.POINTER(AtomContribArgs), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mkgnn_tail_fused_readout_dropout.restype = C.c_int
     lib.mkgnn_tail_fused_readout_dropout.argtypes = [C.POINTER(TailArgs), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mkgnn_tail_fused_weighted.restype = C.c_int
+    lib.mkgnn_tail_fused_weighted.argtypes = [C.POINTER(TailArgs), C.c_float, C.POINTER(LossWeights), C.c_void_p, C.c_size_t,
+                                              C.c_void_p]
     lib.mkgnn_readout_dropout_mask.restype = C.c_int
     lib.mkgnn_readout_dropout_mask.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]
     lib.mkgnn_flat_copy.restype = C.c_int
@@ -473,6 +484,11 @@ def load() -> C.CDLL:
     lib.mkgnn_task_head_fused.restype = C.c_int
     lib.mkgnn_task_head_fused.argtypes = [I32, P, I64, I64, I32, I32, P, P, P, P, P, I64, C.c_float, P, P, P, P, P, I64, P, P, P,
                                           C.c_size_t, P]
+    # the weighted forms: the same arguments with a `const mkgnn_loss_weights*` in front of the workspace
+    for name in ("forward", "backward", "fused"):
+        args = list(getattr(lib, "mkgnn_task_head_" + name).argtypes)
+        getattr(lib, "mkgnn_task_head_weighted_" + name).restype = C.c_int
+        getattr(lib, "mkgnn_task_head_weighted_" + name).argtypes = args[:-3] + [C.POINTER(LossWeights)] + args[-3:]
     # every task's logit of every row: (emb, stride, n_rows, H, T, weight, bias, pred, row stride, task stride, stream)
     lib.mkgnn_task_scores.restype = C.c_int
     lib.mkgnn_task_scores.argtypes = [P, I64, I64, I32, I32, P, P, P, I64, I64, P]

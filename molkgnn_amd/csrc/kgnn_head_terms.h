@@ -30,6 +30,17 @@ __device__ __forceinline__ float head_dloss(float x, float y) {
     if constexpr (LK == MKGNN_LOSS_BCE_MEAN) return 1.f / (1.f + expf(-x)) - y;
     else return 2.f * (x - y);
 }
+// BCE with a positive weight p (torch's pos_weight): L = 1 + (p - 1) y;  term = (1 - y) x + L (log1p(e^-|x|) + max(-x, 0)),
+// d term / d x = (1 - y) - L sigmoid(-x).  Every product-and-add is an explicit fma, so every instantiation rounds alike;
+// expf(x) = inf at a large x gives sigmoid(-x) = 0, and x = -90, y = 1 gives exactly 90 L.
+__device__ __forceinline__ float head_loss_term_pos(float x, float y, float p) {
+    const float L = fmaf(p - 1.f, y, 1.f);
+    return fmaf(L, log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f), (1.f - y) * x);
+}
+__device__ __forceinline__ float head_dloss_pos(float x, float y, float p) {
+    const float L = fmaf(p - 1.f, y, 1.f);
+    return fmaf(-L, 1.f / (1.f + expf(x)), 1.f - y);
+}
 // the loss kind (MKGNN_LOSS_*) of a call as a template argument: f(std::integral_constant<int, LK>{}); false: unknown kind
 template <typename Fn>
 static bool with_loss_kind(int32_t lk, Fn&& f) {

@@ -204,6 +204,9 @@ struct TailMidArgs {
     float* slab; int slab_stride;           // [blocks][slab_stride]: TAIL_* below
     int mg;                                 // molecules per group: tail_group_size(n_loss)
     float rdrop_p;                          // the readout's dropout (only the readout-dropout instantiations read it)
+    // mkgnn_tail_fused_weighted (only the weighted instantiations read them; all null: the unweighted ones are launched)
+    const float* sw; const int32_t* wids; int64_t n_sw;   // per molecule gi < n_loss: sw[gi], or sw[wids[gi]] (outside [0, n_sw): +0.0)
+    const float* pw;                                      // [1]: the positive weight (BCE)
 };
 constexpr int TAIL_MAX_BLOCKS = 768;        // (three workgroups per CU)
 // a workgroup's slab (floats): b1 [32] | W2 [32][32] | b2 [32] | wh [32] | bh | loss

@@ -1160,8 +1160,9 @@ static int tail_project(const char* who, const mkgnn_tail_args* p, Own&& own, si
                                   need(ro->F, ro->H, ro->G, p->n_atoms, p->n_mols), ws, ws_bytes, st, b, d);
 }
 
-// rp: the readout's dropout (mkgnn_tail_fused_readout_dropout), 0 for mkgnn_tail_fused
-static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void* ws, size_t ws_bytes, void* stream) {
+// rp: the readout's dropout (mkgnn_tail_fused_readout_dropout), 0 for mkgnn_tail_fused; wt: mkgnn_tail_fused_weighted's weights
+static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void* ws, size_t ws_bytes, void* stream,
+                      const mkgnn_loss_weights* wt = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     BlockProjArgs b{};
     ReadoutDims d;
@@ -1176,6 +1177,9 @@ static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void*
         if (rp > 0.f && (!p->rng_state || !p->rng_used)) return api_fail("%s: readout dropout needs rng_state and rng_used", who);
         if (p->loss_kind < MKGNN_LOSS_BCE_MEAN || p->loss_kind > MKGNN_LOSS_SQERR_SUM) return api_fail("%s: unknown loss kind %d", who, (int)p->loss_kind);
         if (p->grad_sim_stride < ro->F) return api_fail("%s: bad grad_sim stride", who);
+        if (wt && wt->pos_weight && p->loss_kind != MKGNN_LOSS_BCE_MEAN) return api_fail("%s: pos_weight needs the BCE loss kind", who);
+        if (wt && wt->sample_weight && (wt->weight_ids ? wt->n_sample_weight < 1 : wt->n_sample_weight < p->n_loss_mols))
+            return api_fail("%s: sample_weight holds %lld entries", who, (long long)wt->n_sample_weight);
         return 0;
     };
     if (int rc = tail_project(who, p, own, mkgnn_tail_workspace_bytes, ws, ws_bytes, st, b, d)) return rc;
@@ -1193,6 +1197,10 @@ static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void*
     m.emb = p->emb; m.es = p->emb_stride; m.pred = p->pred;
     m.slab = (float*)((char*)ws + w.slab_tail); m.slab_stride = TAIL_SLAB;
     m.mg = tail_group_size(p->n_loss_mols);
+    if (wt) {
+        m.sw = wt->sample_weight; m.wids = wt->sample_weight ? wt->weight_ids : nullptr; m.n_sw = wt->n_sample_weight;
+        m.pw = wt->pos_weight;
+    }
     const int nbm = tail_middle_blocks(p->n_loss_mols);
     e = launch_tail_middle(m, nbm, p->loss_kind, st);
     if (e != hipSuccess) return api_hip_fail(who, e);
@@ -1288,6 +1296,11 @@ int mkgnn_tail_fused(const mkgnn_tail_args* p, void* ws, size_t ws_bytes, void* 
 
 int mkgnn_tail_fused_readout_dropout(const mkgnn_tail_args* p, float readout_dropout_p, void* ws, size_t ws_bytes, void* stream) {
     return tail_fused("mkgnn_tail_fused_readout_dropout", p, readout_dropout_p, ws, ws_bytes, stream);
+}
+
+int mkgnn_tail_fused_weighted(const mkgnn_tail_args* p, float readout_dropout_p, const mkgnn_loss_weights* weights, void* ws,
+                              size_t ws_bytes, void* stream) {
+    return tail_fused("mkgnn_tail_fused_weighted", p, readout_dropout_p, ws, ws_bytes, stream, weights);
 }
 
 // ---- the forward-only tail (evaluation mode): project | the middle's forward phases -- two launches, pred and emb only ----

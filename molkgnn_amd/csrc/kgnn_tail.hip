@@ -3,7 +3,8 @@
 //   h = propagate(sim_sc)                                   reference KernelLayer.py:119-123
 //   emb_g = pool_g( lin2( swish( lin1(h) ) ) )              reference MolKGNNNet.py:144-146
 //   loss = BCEWithLogits( ffn( dropout(emb) ), y )          reference model.py:147-150, 169, 190-198; data.py:37
-//          (or the squared error, mean or sum -- the docking-score task, data.py:49-53: the template parameter LK, ABI v8)
+//          (or the squared error, mean or sum -- the docking-score task, data.py:49-53: the template parameter LK, ABI v8;
+//           with a weight per molecule and a positive weight -- mkgnn_tail_fused_weighted: the template parameter WT)
 //
 // -- forward AND backward in FOUR launches instead of nine (mkgnn_tail_fused, kgnn_readout.hip).  The loss is a mean over
 // molecules, so d loss / d logit_g = (sigmoid(logit_g) - y_g) / B needs nothing but the molecule's own logit, and the chain back
@@ -63,9 +64,12 @@ constexpr int LDS_INTS = AC + 2 * (AC + 1) + 2 * EC + 3 * (MC + 1) + 4;
 // source as by target -- its edges lie inside it -- so the window cuts the same chunks without them), keeps neither pre nor any
 // gradient row or accumulator, and writes no slab and no d z.  The grid stays tail_middle_blocks': at most three workgroups per
 // CU exist, so the halved LDS cannot become occupancy and the bound stays 3 waves per SIMD.
-template <int LK, bool RD, bool FWD = false>
+// WT: the weighted loss (mkgnn_tail_fused_weighted) -- a sample weight per molecule gi < n_loss (a.sw, direct or through a.wids)
+// and a positive weight (a.pw[0], BCE); it changes d and acc_loss of the per-molecule phase and nothing else, and the
+// instantiations without it stay as they were.
+template <int LK, bool RD, bool FWD = false, bool WT = false>
 __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
-    static_assert(!FWD || (LK == MKGNN_LOSS_BCE_MEAN && !RD), "the forward-only form has no loss and no dropout");
+    static_assert(!FWD || (LK == MKGNN_LOSS_BCE_MEAN && !RD && !WT), "the forward-only form has no loss and no dropout");
     __shared__ __align__(16) float lds[FWD ? LDS_FLOATS_FWD + LDS_INTS_FWD : LDS_FLOATS + LDS_INTS];
     float* const W2s = lds;                              // [32][HP]
     float* const zp = W2s + 32 * WP;                     // [AC][HP]: pre, later d pre   (32 * 33 floats = 4 224 bytes: 16-byte aligned)
@@ -277,7 +281,46 @@ __global__ void __launch_bounds__(NT, 3) tail_middle_kernel(TailMidArgs a) {
                 continue;
             }
             float d = 0.f;
-            if (counted) {
+            if constexpr (WT) {
+                // the weighted loss: the unweighted d and term times the molecule's sample weight FIRST (then 1 / B), so weights of
+                // exactly 1 give the other branch's bits; with a positive weight p (BCE): L = 1 + (p - 1) y,
+                // term = (1 - y) x + L (log1p(e^-|x|) + max(-x, 0)),  d term / d x = (1 - y) - L sigmoid(-x)
+                if (counted) {
+                    const float yv = a.y[gi];
+                    float s = 1.f;
+                    if (a.sw) {
+                        if (a.wids) {
+                            const int64_t r = a.wids[gi];
+                            const bool in = r >= 0 && r < a.n_sw;      // (an id outside the table: weight +0.0)
+                            s = a.sw[in ? r : 0];
+                            if (!in) s = 0.f;
+                        } else {
+                            s = a.sw[gi];
+                        }
+                    }
+                    float d0, t0;
+                    if constexpr (LK == MKGNN_LOSS_BCE_MEAN) {
+                        if (a.pw) {
+                            const float L = fmaf(a.pw[0] - 1.f, yv, 1.f);
+                            d0 = fmaf(-L, sigmoidf_(-x), 1.f - yv);
+                            t0 = fmaf(L, log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f), (1.f - yv) * x);
+                        } else {
+                            d0 = sigmoidf_(x) - yv;
+                            t0 = fmaxf(x, 0.f) - x * yv + log1pf(expf(-fabsf(x)));
+                        }
+                    } else {
+                        const float r = x - yv;
+                        d0 = 2.f * r;
+                        t0 = r * r;
+                    }
+                    d = LK == MKGNN_LOSS_SQERR_SUM ? s * d0 : invB * (s * d0);
+                    if (j == 0) {
+                        a.pred[gi] = x;
+                        acc_loss += LK == MKGNN_LOSS_SQERR_SUM ? s * t0 : invB * (s * t0);
+                        acc_bh += d;
+                    }
+                }
+            } else if (counted) {
                 const float yv = a.y[gi];
                 if constexpr (LK == MKGNN_LOSS_BCE_MEAN) {
                     d = invB * (sigmoidf_(x) - yv);
@@ -428,12 +471,12 @@ extern "C" int mkgnn_debug_set_tail_stamps(void* device_ptr) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(tail::g_tail_stamps), &device_ptr, sizeof(void*));
 }
 
-template <bool RD>
+template <bool RD, bool WT = false>
 static hipError_t launch_tail_middle_rd(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st) {
     switch (loss_kind) {
-    case MKGNN_LOSS_BCE_MEAN: tail::tail_middle_kernel<MKGNN_LOSS_BCE_MEAN, RD><<<nb, tail::NT, 0, st>>>(a); break;
-    case MKGNN_LOSS_SQERR_MEAN: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_MEAN, RD><<<nb, tail::NT, 0, st>>>(a); break;
-    case MKGNN_LOSS_SQERR_SUM: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_SUM, RD><<<nb, tail::NT, 0, st>>>(a); break;
+    case MKGNN_LOSS_BCE_MEAN: tail::tail_middle_kernel<MKGNN_LOSS_BCE_MEAN, RD, false, WT><<<nb, tail::NT, 0, st>>>(a); break;
+    case MKGNN_LOSS_SQERR_MEAN: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_MEAN, RD, false, WT><<<nb, tail::NT, 0, st>>>(a); break;
+    case MKGNN_LOSS_SQERR_SUM: tail::tail_middle_kernel<MKGNN_LOSS_SQERR_SUM, RD, false, WT><<<nb, tail::NT, 0, st>>>(a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -448,6 +491,10 @@ hipError_t launch_tail_score(const TailMidArgs& a, int nb, hipStream_t st) {
 hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st) {
     if (a.mg < tail::MG_MIN || a.mg > tail::MG_MAX || a.mg > tail::MC) return hipErrorInvalidValue;
     if (a.rdrop_p > 0.f && !a.rng) return hipErrorInvalidValue;
+    if (a.sw || a.pw) {                                  // (mkgnn_tail_fused_weighted with a weight: the weighted instantiations)
+        if (a.pw && loss_kind != MKGNN_LOSS_BCE_MEAN) return hipErrorInvalidValue;
+        return a.rdrop_p > 0.f ? launch_tail_middle_rd<true, true>(a, nb, loss_kind, st) : launch_tail_middle_rd<false, true>(a, nb, loss_kind, st);
+    }
     return a.rdrop_p > 0.f ? launch_tail_middle_rd<true>(a, nb, loss_kind, st) : launch_tail_middle_rd<false>(a, nb, loss_kind, st);
 }
 

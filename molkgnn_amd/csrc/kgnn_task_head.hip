@@ -9,6 +9,8 @@
 //      (task, column) entries sums the block partials in a fixed order; the remaining blocks scale grad_emb.  Every block counts the
 //      labelled rows itself from the integer-valued per-block counts (exact in any order), so nothing waits on another block.
 // No float atomics, no "last block done" counter (kgnn_head.hip records why).
+// The weighted losses (mkgnn_task_head_weighted_*: a sample weight per row, a positive weight per task, a null task for a
+// one-output head) are the template parameter WT of the first kernel; the second one serves both.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "kgnn_common.h"
@@ -30,6 +32,9 @@ struct TaskHeadArgs {
     float drop_p;
     int64_t* rng;                  // forward / fused: {seed, offset}, offset advanced by one per call
     int64_t* rng_used;             // forward writes / backward reads the {seed, offset} of this call's mask
+    // the weighted entry points (WT) only: mkgnn_loss_weights, all optional
+    const float* sw; const int32_t* wids; int64_t n_sw;   // wids null: s_i = sw[i]; else sw[wids[i]], an id outside [0, n_sw): +0.0
+    const float* pw;                                      // [T] positive weights (BCE)
 };
 enum { TH_FORWARD = 0, TH_BACKWARD = 1, TH_FUSED = 2 };
 constexpr int TH_MAX_H = 64;        // LDS row of the staged keep * emb: a wave writes two rows, one per 32-lane half (the halves never
@@ -39,7 +44,11 @@ constexpr int TH_SCALE_BLOCKS = 64; // blocks of the final kernel that scale gra
 // a block's partial row: [T][H + 1] gradient entries (the gradient passes) | loss | labelled rows
 __device__ __host__ __forceinline__ int task_head_entries(int mode, int T, int H) { return mode == TH_FORWARD ? 0 : T * (H + 1); }
 
-template <int LK, int MODE>
+// WT: the weighted entry points (mkgnn_task_head_weighted_*) -- a sample weight per row, a positive weight per task, and a null
+// task meaning "every row has task 0"; a template parameter so that the instantiations without it stay as they were.  The
+// weights only scale a labelled row's loss term and its d loss / d pred, BEFORE grad_loss and the 1 / n_lab of the final kernel
+// (which is the unweighted one: it sees nothing of the weights): weights of exactly 1 give the unweighted bits.
+template <int LK, int MODE, bool WT = false>
 __global__ void __launch_bounds__(256) task_head_kernel(TaskHeadArgs a) {
     __shared__ float ek[HEAD_ROWS][TH_MAX_H];    // keep * emb of the block's rows
     __shared__ float dl[HEAD_ROWS], lt[HEAD_ROWS];   // d loss / d pred (before 1 / n_lab) and loss term: 0 for an unlabelled row
@@ -54,12 +63,15 @@ __global__ void __launch_bounds__(256) task_head_kernel(TaskHeadArgs a) {
     // all loads of the block's rows first (unconditional, clamped): row -> task -> the task's weight row, then the arithmetic
     int tv[NP];
     float xv[NP], yv[NP], pv[NP], w0[NP], bv[NP], ks0[NP], dv[NP];
+    float sv[WT ? NP : 1], pwv[WT ? NP : 1];             // (WT) the row's sample weight and its task's positive weight
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         const int64_t i = (int64_t)blockIdx.x * HEAD_ROWS + k * 8 + g;
         const int64_t ic = i < a.B ? i : a.B - 1;
         int32_t tid;
-        if (a.row_ids) {
+        if (WT && !a.task) {
+            tid = 0;                                         // (single-task: T == 1, checked by the host)
+        } else if (a.row_ids) {
             const int64_t r = a.row_ids[ic];
             const bool in = r >= 0 && r < a.n_task;          // (an id outside the table: no label)
             tid = a.task[in ? r : 0];
@@ -74,6 +86,21 @@ __global__ void __launch_bounds__(256) task_head_kernel(TaskHeadArgs a) {
         pv[k] = MODE == TH_BACKWARD ? a.pred[ic] : 0.f;
         w0[k] = h < a.H ? a.w[(size_t)tc * a.H + h] : 0.f;
         bv[k] = (MODE != TH_BACKWARD && a.b) ? a.b[tc] : 0.f;
+        if constexpr (WT) {
+            float s = 1.f;
+            if (a.sw) {
+                if (a.wids) {
+                    const int64_t r = a.wids[ic];
+                    const bool in = r >= 0 && r < a.n_sw;    // (an id outside the table: weight +0.0)
+                    s = a.sw[in ? r : 0];
+                    if (!in) s = 0.f;
+                } else {
+                    s = a.sw[ic];
+                }
+            }
+            sv[k] = s;
+            pwv[k] = (LK == MKGNN_LOSS_BCE_MEAN && a.pw) ? a.pw[tc] : 1.f;
+        }
     }
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
@@ -98,12 +125,16 @@ __global__ void __launch_bounds__(256) task_head_kernel(TaskHeadArgs a) {
             x = half_wave_sum(x) + bv[k];                           // (the xor tree leaves the sum in every lane of the row)
             if (!lab) x = 0.f;
         }
-        dv[k] = lab ? gl * head_dloss<LK>(x, yv[k]) : 0.f;
+        // (WT: the weight first, then grad_loss -- s = 1 without a positive weight is the unweighted expression bit for bit)
+        const bool pos = WT && LK == MKGNN_LOSS_BCE_MEAN && a.pw;
+        if constexpr (WT) dv[k] = lab ? gl * (sv[k] * (pos ? head_dloss_pos(x, yv[k], pwv[k]) : head_dloss<LK>(x, yv[k]))) : 0.f;
+        else dv[k] = lab ? gl * head_dloss<LK>(x, yv[k]) : 0.f;
         if (h == 0) {
             const int row = k * 8 + g;
             if (MODE != TH_BACKWARD && i < a.B) a.pred[i] = x;
             dl[row] = dv[k];
-            lt[row] = lab ? head_loss_term<LK>(x, yv[k]) : 0.f;
+            if constexpr (WT) lt[row] = lab ? sv[k] * (pos ? head_loss_term_pos(x, yv[k], pwv[k]) : head_loss_term<LK>(x, yv[k])) : 0.f;
+            else lt[row] = lab ? head_loss_term<LK>(x, yv[k]) : 0.f;
             tk[row] = tv[k];
         }
     }
@@ -234,12 +265,15 @@ using namespace mkgnn;
 static int64_t task_head_blocks(int64_t n_rows) { return (n_rows + HEAD_ROWS - 1) / HEAD_ROWS; }
 
 static int task_head_check(const char* who, int64_t n_rows, int32_t H, int32_t T, int64_t emb_stride, const int32_t* task,
-                           const int32_t* row_ids, int64_t n_task, float p, void* ws, size_t ws_bytes, TaskHeadArgs& a) {
+                           const int32_t* row_ids, int64_t n_task, float p, void* ws, size_t ws_bytes, TaskHeadArgs& a,
+                           bool weighted = false) {
     if (T < 1 || T > MKGNN_TASK_HEAD_MAX_TASKS) return api_fail("%s: %d tasks outside [1, %d]", who, (int)T, MKGNN_TASK_HEAD_MAX_TASKS);
     if (H < 1 || H > TH_MAX_H) return api_fail("%s: embedding width %d outside [1, %d]", who, (int)H, TH_MAX_H);
     if (n_rows < 1 || emb_stride < H || task_head_blocks(n_rows) > 0x7fffff00) return api_fail("%s: bad shape", who);
-    if (!task) return api_fail("%s: null task", who);
-    if (row_ids ? n_task < 1 : n_task < n_rows) return api_fail("%s: task holds %lld entries", who, (long long)n_task);
+    if (!task) {                                           // (the weighted entry points: every row has task 0)
+        if (!weighted) return api_fail("%s: null task", who);
+        if (T != 1 || row_ids) return api_fail("%s: a null task needs T == 1 and no row_ids (T = %d)", who, (int)T);
+    } else if (row_ids ? n_task < 1 : n_task < n_rows) return api_fail("%s: task holds %lld entries", who, (long long)n_task);
     if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, p);
     if (!ws || ws_bytes < mkgnn_task_head_workspace_bytes(n_rows, H, T) || ((uintptr_t)ws & 3))
         return api_fail("%s: workspace too small or misaligned", who);
@@ -248,8 +282,27 @@ static int task_head_check(const char* who, int64_t n_rows, int32_t H, int32_t T
     return 0;
 }
 
+// the weighted entry points' extra arguments -> a; returns whether the weighted instantiation is needed (-1: refused).  No
+// weight and a task per row: the unweighted instantiation, so the unweighted entry point's bits.
+static int task_head_weights(const char* who, int32_t lk, const mkgnn_loss_weights* wt, TaskHeadArgs& a) {
+    if (lk != MKGNN_LOSS_BCE_MEAN && lk != MKGNN_LOSS_SQERR_MEAN && lk != MKGNN_LOSS_SQERR_SUM) {
+        api_fail("%s: unknown loss kind %d", who, (int)lk);
+        return -1;
+    }
+    if (wt) {
+        if (wt->pos_weight && lk != MKGNN_LOSS_BCE_MEAN) { api_fail("%s: pos_weight needs the BCE loss kind", who); return -1; }
+        if (wt->sample_weight && (wt->weight_ids ? wt->n_sample_weight < 1 : wt->n_sample_weight < a.B)) {
+            api_fail("%s: sample_weight holds %lld entries", who, (long long)wt->n_sample_weight);
+            return -1;
+        }
+        a.sw = wt->sample_weight; a.wids = wt->sample_weight ? wt->weight_ids : nullptr; a.n_sw = wt->n_sample_weight;
+        a.pw = wt->pos_weight;
+    }
+    return (a.sw || a.pw || !a.task) ? 1 : 0;
+}
+
 template <int MODE>
-static int task_head_launch(const char* who, int32_t lk, const TaskHeadArgs& a, void* stream) {
+static int task_head_launch(const char* who, int32_t lk, const TaskHeadArgs& a, void* stream, bool weighted = false) {
     const int nblk = (int)task_head_blocks(a.B);
     const int Q = task_head_entries(MODE, a.T, a.H);
     const int ncol = (Q + 63) / 64;
@@ -259,7 +312,9 @@ static int task_head_launch(const char* who, int32_t lk, const TaskHeadArgs& a, 
         nscale = (int)(want < TH_SCALE_BLOCKS ? want : TH_SCALE_BLOCKS);
     }
     if (!with_loss_kind(lk, [&](auto K) {
-            task_head_kernel<decltype(K)::value, MODE><<<nblk, 256, 0, (hipStream_t)stream>>>(a);
+            if (weighted) task_head_kernel<decltype(K)::value, MODE, true><<<nblk, 256, 0, (hipStream_t)stream>>>(a);
+            else task_head_kernel<decltype(K)::value, MODE><<<nblk, 256, 0, (hipStream_t)stream>>>(a);
+            // (the second launch sees nothing of the weights: one instantiation serves both)
             task_head_final_kernel<decltype(K)::value, MODE><<<1 + ncol + nscale, 256, 0, (hipStream_t)stream>>>(a, nblk, ncol);
         }))
         return api_fail("%s: unknown loss kind %d", who, (int)lk);
@@ -317,6 +372,59 @@ int mkgnn_task_head_fused(int32_t loss_kind, const float* emb, int64_t emb_strid
     a.emb = emb; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss; a.rng = rng_state; a.rng_used = rng_used;
     a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
     return task_head_launch<TH_FUSED>(who, loss_kind, a, stream);
+}
+
+int mkgnn_task_head_weighted_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                                     const float* weight, const float* bias, const float* target, const int32_t* task,
+                                     const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state,
+                                     int64_t* rng_used, float* pred, float* loss, const mkgnn_loss_weights* weights, void* ws,
+                                     size_t ws_bytes, void* stream) {
+    const char* who = "mkgnn_task_head_weighted_forward";
+    TaskHeadArgs a{};
+    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a, true)) return rc;
+    if (!emb || !weight || !target || !pred || !loss) return api_fail("%s: null pointer", who);
+    if (dropout_p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
+    const int wt = task_head_weights(who, loss_kind, weights, a);
+    if (wt < 0) return 1;
+    a.emb = emb; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss; a.rng = rng_state; a.rng_used = rng_used;
+    return task_head_launch<TH_FORWARD>(who, loss_kind, a, stream, wt == 1);
+}
+
+int mkgnn_task_head_weighted_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                                      const float* weight, const float* target, const int32_t* task, const int32_t* row_ids,
+                                      int64_t n_task, const float* pred, const float* grad_loss, float dropout_p,
+                                      const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
+                                      float* grad_bias, const mkgnn_loss_weights* weights, void* ws, size_t ws_bytes,
+                                      void* stream) {
+    const char* who = "mkgnn_task_head_weighted_backward";
+    TaskHeadArgs a{};
+    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a, true)) return rc;
+    if (!emb || !weight || !target || !pred || !grad_loss || !grad_weight) return api_fail("%s: null pointer", who);
+    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
+    if (dropout_p > 0.f && !rng_used) return api_fail("%s: dropout needs the forward's rng_used", who);
+    const int wt = task_head_weights(who, loss_kind, weights, a);
+    if (wt < 0) return 1;
+    a.emb = emb; a.w = weight; a.y = target; a.pred = (float*)pred; a.gloss = grad_loss; a.rng_used = (int64_t*)rng_used;
+    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
+    return task_head_launch<TH_BACKWARD>(who, loss_kind, a, stream, wt == 1);
+}
+
+int mkgnn_task_head_weighted_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                                   const float* weight, const float* bias, const float* target, const int32_t* task,
+                                   const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state, int64_t* rng_used,
+                                   float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
+                                   float* grad_bias, const mkgnn_loss_weights* weights, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "mkgnn_task_head_weighted_fused";
+    TaskHeadArgs a{};
+    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a, true)) return rc;
+    if (!emb || !weight || !target || !pred || !loss || !grad_weight) return api_fail("%s: null pointer", who);
+    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
+    if (dropout_p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
+    const int wt = task_head_weights(who, loss_kind, weights, a);
+    if (wt < 0) return 1;
+    a.emb = emb; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss; a.rng = rng_state; a.rng_used = rng_used;
+    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
+    return task_head_launch<TH_FUSED>(who, loss_kind, a, stream, wt == 1);
 }
 
 }  // extern "C"

@@ -230,6 +230,12 @@ class CompactStaticBatch:
             self.data.task_table, self.data.task_rows = table, self.ids
         elif getattr(self.data, "task_table", None) is not None:
             self.data.task_table = self.data.task_rows = None
+        # ... and one that knows its molecules' loss weights (ResidentShard(..., weights=...)): the weight table of the weighted loss
+        table = resident.tensors.get("weight")
+        if table is not None:
+            self.data.weight_table, self.data.weight_rows = table, self.ids
+        elif getattr(self.data, "weight_table", None) is not None:
+            self.data.weight_table = self.data.weight_rows = None
 
     def gather_status(self) -> int:
         """The status word of the LAST gather (a host read: once per epoch, not per batch): 0, or ``_lib.GATHER_BAD_ID`` (an id

@@ -632,12 +632,23 @@ def bce_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor,
 
 
 def head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, loss: str = "bce", dropout_p: float = 0.0,
-              n_rows: Optional[int] = None) -> torch.Tensor:
+              n_rows: Optional[int] = None, sample_weight: Optional[torch.Tensor] = None,
+              pos_weight: Optional[torch.Tensor] = None, weight_table: Optional[torch.Tensor] = None,
+              row_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``bce_head_loss`` for any loss kind of ``LOSS_KINDS``: ``"bce"`` (``BCEWithLogitsLoss()``, the same bits as
     ``bce_head_loss``), ``"mse"`` (``MSELoss()``) or ``"mse_sum"`` (``MSELoss(reduction='sum')``, the reference's docking-score
     task) of ``ffn(dropout(emb)).view(-1)`` against ``target.view(-1).float()``.  Same kernels (the kind a template parameter),
-    same dropout mask for the same generator state, same padding rule."""
-    return _head_loss("head_loss", emb, ffn, target, loss_kind(loss), dropout_p, n_rows)
+    same dropout mask for the same generator state, same padding rule.
+
+    ``sample_weight [>= n_rows]`` (or ``weight_table [M]`` read through ``row_ids [>= n_rows]``) and ``pos_weight [1]``: the weighted
+    loss of ``task_head_reference`` with every row in task 0, on the task-indexed head's weighted kernels
+    (``mkgnn_task_head_weighted_*`` with a null task); with none of them given nothing changes."""
+    if sample_weight is None and pos_weight is None and weight_table is None:
+        return _head_loss("head_loss", emb, ffn, target, loss_kind(loss), dropout_p, n_rows)
+    if ffn.out_features != 1:
+        raise ValueError("head_loss needs a one-output linear layer")
+    return _weighted_task_head_loss("head_loss", emb, ffn, target, None, loss, dropout_p, n_rows, None, row_ids, sample_weight,
+                                    pos_weight, weight_table)
 
 
 # ---------------------------------------------------------------- task-indexed head with masked labels --
@@ -657,10 +668,50 @@ def _row_tasks(task, task_table, row_ids, n_rows: int) -> torch.Tensor:
     return torch.where(inside, task_table.reshape(-1).long()[ids.clamp(0, max(m - 1, 0))], torch.full_like(ids, -1))
 
 
+# MKGNN_WEIGHTED_LOSS=0 (A/B, diagnostics): a weighted loss runs its definition (task_head_reference) in torch operators on the GPU
+# instead of the weighted kernels; an unweighted loss is not touched by it
+_WEIGHTED_LOSS = os.environ.get("MKGNN_WEIGHTED_LOSS", "1") != "0"
+
+
+def _check_loss_weights(loss: str, T: int, sample_weight, pos_weight, weight_table, row_ids) -> None:
+    """What every weighted entry refuses: a weight that requires a gradient, ``pos_weight`` with a squared-error kind or of a
+    length other than ``T``, both weight forms at once, a table without ids."""
+    for name, w in (("sample_weight", sample_weight), ("pos_weight", pos_weight), ("weight_table", weight_table)):
+        if w is not None and w.requires_grad:
+            raise ValueError(f"{name} is a constant of the loss: it must not require a gradient")
+    if pos_weight is not None:
+        if loss != "bce":
+            raise ValueError(f"pos_weight belongs to the 'bce' loss, not to {loss!r}")
+        if pos_weight.numel() != T:
+            raise ValueError(f"pos_weight holds {pos_weight.numel()} elements for {T} task(s)")
+    if sample_weight is not None and weight_table is not None:
+        raise ValueError("either sample_weight or weight_table (with row_ids), not both")
+    if weight_table is not None and (row_ids is None or weight_table.numel() < 1):
+        raise ValueError("weight_table needs row_ids and at least one entry")
+
+
+def _row_weights(sample_weight, weight_table, row_ids, n_rows: int) -> Optional[torch.Tensor]:
+    """The sample weight of each of the leading ``n_rows`` rows, or None: ``sample_weight`` itself, or ``weight_table[row_ids]``
+    with an id outside the table read as +0.0."""
+    if sample_weight is not None:
+        if sample_weight.numel() < n_rows:
+            raise ValueError(f"sample_weight holds {sample_weight.numel()} elements for {n_rows} rows")
+        return sample_weight.detach().reshape(-1)[:n_rows]
+    if weight_table is None:
+        return None
+    table = weight_table.detach().reshape(-1)
+    ids = row_ids.reshape(-1)[:n_rows].long().to(table.device)
+    m = table.numel()
+    inside = (ids >= 0) & (ids < m)
+    return torch.where(inside, table[ids.clamp(0, m - 1)], torch.zeros((), dtype=table.dtype, device=table.device))
+
+
 def task_head_reference(emb: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], target: torch.Tensor,
                         task: Optional[torch.Tensor], loss: str = "bce", keep: Optional[torch.Tensor] = None,
                         n_rows: Optional[int] = None, task_table: Optional[torch.Tensor] = None,
-                        row_ids: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                        row_ids: Optional[torch.Tensor] = None, sample_weight: Optional[torch.Tensor] = None,
+                        pos_weight: Optional[torch.Tensor] = None,
+                        weight_table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(loss, pred [n_rows])`` of the task-indexed head in torch operators, in the dtype of ``emb``, differentiable: the
     DEFINITION of ``task_head_loss`` (and what it runs for more than 32 tasks or an embedding wider than 64).
 
@@ -668,11 +719,26 @@ def task_head_reference(emb: torch.Tensor, weight: torch.Tensor, bias: Optional[
     (-1 by convention otherwise); ``pred_i = (keep_i * emb_i) . weight[t_i] + bias[t_i]`` for a labelled row and +0.0 for any
     other; ``loss`` is the sum of the labelled rows' terms -- ``"bce"``: BCE with logits, ``"mse"`` / ``"mse_sum"``: squared
     error -- over ``max(n_labelled, 1)`` (``"mse_sum"``: not divided).  ``keep [n_rows, H]``: explicit dropout multipliers, or
-    None.  ``target`` of an unlabelled row is not used (a NaN there is harmless); rows from ``n_rows`` on take no part."""
+    None.  ``target`` of an unlabelled row is not used (a NaN there is harmless); rows from ``n_rows`` on take no part.
+
+    The weighted loss -- ``torch.nn.functional.binary_cross_entropy_with_logits(x, y, weight=s, pos_weight=p)`` with
+    ``reduction='mean'``, and its squared-error counterpart: a labelled row's term is multiplied by its sample weight ``s_i``
+    (``sample_weight[i]``, or ``weight_table[row_ids[i]]`` with an id outside the table read as +0.0; absent: 1), and with
+    ``pos_weight [T]`` (``"bce"`` only) the term is ``s_i ((1 - y) x + L (log1p(e^-|x|) + max(-x, 0)))`` with ``L = 1 + (p_t - 1) y``.
+    The mean still divides by the number of labelled rows, not by the sum of the weights.  Weights are constants (one that
+    requires a gradient raises ``ValueError``) and plain multipliers: zero gives zero, a NaN on a labelled row propagates, the
+    weight of an unlabelled row or of a row from ``n_rows`` on is never used.  Neither ``task`` nor ``task_table``: every row has
+    task 0 (``T`` must be 1)."""
     loss_kind(loss)
     n = emb.shape[0] if n_rows is None else int(n_rows)
     T = weight.shape[0]
-    t = _row_tasks(task, task_table, row_ids, n).to(emb.device)
+    _check_loss_weights(loss, T, sample_weight, pos_weight, weight_table, row_ids)
+    if task is None and task_table is None:
+        if T != 1:
+            raise ValueError("task_head_reference without task or task_table needs a one-output head")
+        t = torch.zeros(n, dtype=torch.int64, device=emb.device)
+    else:
+        t = _row_tasks(task, task_table, row_ids, n).to(emb.device)
     lab = (t >= 0) & (t < T)
     t = torch.where(lab, t, torch.zeros_like(t))
     e = emb[:n]
@@ -684,11 +750,19 @@ def task_head_reference(emb: torch.Tensor, weight: torch.Tensor, bias: Optional[
     zero = torch.zeros((), dtype=pred.dtype, device=pred.device)
     pred = torch.where(lab, pred, zero)
     y = torch.where(lab, target.reshape(-1)[:n].to(pred.dtype), zero)
-    if loss == "bce":
+    if loss == "bce" and pos_weight is not None:
+        # (1 - y) x + L log(1 + e^-x): torch's form in value, with (1 - y) - L sigmoid(-x) as its derivative
+        L = 1 + (pos_weight.detach().reshape(-1).to(device=pred.device, dtype=pred.dtype)[t] - 1) * y
+        term = (1 - y) * pred + L * torch.logaddexp(-pred, torch.zeros_like(pred))
+    elif loss == "bce":
         # log(1 + e^x) - x y: torch's max(x, 0) - x y + log1p(e^-|x|) in value, with sigmoid(x) - y as its derivative at x = 0 too
         term = torch.logaddexp(pred, torch.zeros_like(pred)) - pred * y
     else:
         term = (pred - y) ** 2
+    s = _row_weights(sample_weight, weight_table, row_ids, n)
+    if s is not None:
+        # (an unlabelled row's weight is not used: zeroed BEFORE the product, so a NaN there reaches neither value nor gradient)
+        term = torch.where(lab, s.to(device=pred.device, dtype=pred.dtype), zero) * term
     total = torch.where(lab, term, zero).sum()
     if loss != "mse_sum":
         total = total / lab.sum().clamp(min=1).to(pred.dtype)
@@ -783,16 +857,174 @@ class _TaskHeadFn(torch.autograd.Function):
         return gemb, gw, gb, None, None, None, None, None, None
 
 
+def _i32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    t = t.reshape(-1)
+    return t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
+
+
+def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    t = t.detach().reshape(-1)
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def _loss_weights(sw: Optional[torch.Tensor], wids: Optional[torch.Tensor], pw: Optional[torch.Tensor]) -> "_lib.LossWeights":
+    """``mkgnn_loss_weights`` over float32 / int32 contiguous device tensors (the caller keeps them alive across the call)."""
+    lw = _lib.LossWeights()
+    lw.sample_weight, lw.weight_ids, lw.pos_weight = _lib.ptr(sw), _lib.ptr(wids), _lib.ptr(pw)
+    lw.n_sample_weight = 0 if sw is None else sw.numel()
+    return lw
+
+
+class _WeightedTaskHeadFn(torch.autograd.Function):
+    """``mkgnn_task_head_weighted_*``: ``_TaskHeadFn`` with a sample weight per row (``sw``, read directly or through ``wids``), a
+    positive weight per task (``pw``), and ``task`` None for "every row has task 0" (a one-output head).  ``task_ids``: the ids the
+    TASK is read through (a task table); ``wids``: the ids the WEIGHT is read through -- one id vector may serve as both."""
+
+    @staticmethod
+    def forward(ctx, emb, weight, bias, target, task, task_ids, sw, wids, pw, p_drop, n_rows, kind):
+        lib = _lib.load()
+        emb = _row_major(emb if emb.dtype == torch.float32 else emb.float())
+        ctx.rows_total = emb.shape[0]
+        B, H = int(n_rows), emb.shape[1]         # the leading n_rows rows enter the loss (the rest: padding molecules)
+        T = weight.shape[0]
+        dev = emb.device
+        w = weight.contiguous()
+        y = target.reshape(-1).float().contiguous()
+        task, task_ids, wids, sw, pw = _i32(task), _i32(task_ids), _i32(wids), _f32(sw), _f32(pw)
+        idx = (_lib.ptr(task), _lib.ptr(task_ids), 0 if task is None else task.numel())
+        lw = _loss_weights(sw, wids, pw)
+        pred = torch.empty(B, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        rng = head_rng_state(dev) if p_drop > 0.0 else None
+        used = torch.empty(2, dtype=torch.int64, device=dev) if p_drop > 0.0 else None
+        ctx.unit = None
+        if any(ctx.needs_input_grad[:3]) and not _SPLIT_HEAD:
+            gemb = None
+            if ctx.needs_input_grad[0]:
+                gemb = torch.empty((ctx.rows_total, H), dtype=torch.float32, device=dev)
+                if ctx.rows_total > B:               # rows beyond B (padding molecules) get a zero gradient
+                    gemb[B:].zero_()
+            gw = torch.empty((T, H), dtype=torch.float32, device=dev)
+            gb = torch.empty(T, dtype=torch.float32, device=dev) if bias is not None else None
+            with torch.cuda.device(dev):
+                ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
+                _lib.check(lib.mkgnn_task_head_weighted_fused(
+                    int(kind), emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), *idx,
+                    float(p_drop), _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), _lib.ptr(gemb), H,
+                    gw.data_ptr(), _lib.ptr(gb), ctypes.byref(lw), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
+                    "mkgnn_task_head_weighted_fused")
+            ctx.unit = (gemb, gw, gb)
+        else:
+            with torch.cuda.device(dev):
+                ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
+                _lib.check(lib.mkgnn_task_head_weighted_forward(
+                    int(kind), emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), *idx,
+                    float(p_drop), _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), ctypes.byref(lw), ws.data_ptr(),
+                    ws.numel(), _lib.stream_ptr(dev)), "mkgnn_task_head_weighted_forward")
+        # (with ctx.unit, references only: a second backward over a retained graph takes the separate backward kernel)
+        ctx.save_for_backward(emb, w, y, pred, used, task, task_ids, sw, wids, pw)
+        ctx.kind, ctx.n_rows = int(kind), B
+        ctx.has_bias = bias is not None
+        ctx.p_drop = float(p_drop)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        none = (None,) * 9
+        if ctx.unit is not None:
+            gemb, gw, gb = ctx.unit
+            ctx.unit = None
+            if not _is_unit_seed(grad_loss):                 # d loss is not the registered 1: scale
+                gl = grad_loss.reshape(()).float()
+                gemb = None if gemb is None else gemb * gl
+                gw = gw * gl
+                gb = None if gb is None else gb * gl
+            return (gemb, gw, gb, *none)
+        lib = _lib.load()
+        emb, w, y, pred, used, task, task_ids, sw, wids, pw = ctx.saved_tensors
+        B, H, T = ctx.n_rows, emb.shape[1], w.shape[0]
+        dev = emb.device
+        gl = grad_loss.reshape(1).float().contiguous()
+        lw = _loss_weights(sw, wids, pw)
+        gemb = None
+        if ctx.needs_input_grad[0]:
+            gemb = torch.empty((ctx.rows_total, H), dtype=torch.float32, device=dev)
+            if ctx.rows_total > B:
+                gemb[B:].zero_()
+        gw = torch.empty((T, H), dtype=torch.float32, device=dev)
+        gb = torch.empty(T, dtype=torch.float32, device=dev) if ctx.has_bias else None
+        with torch.cuda.device(dev):
+            ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
+            _lib.check(lib.mkgnn_task_head_weighted_backward(
+                ctx.kind, emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), y.data_ptr(), _lib.ptr(task), _lib.ptr(task_ids),
+                0 if task is None else task.numel(), pred.data_ptr(), gl.data_ptr(), ctx.p_drop, _lib.ptr(used), _lib.ptr(gemb), H,
+                gw.data_ptr(), _lib.ptr(gb), ctypes.byref(lw), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
+                "mkgnn_task_head_weighted_backward")
+        return (gemb, gw, gb, *none)
+
+
+def _weighted_task_head_loss(who: str, emb, ffn, target, task, loss: str, dropout_p: float, n_rows, task_table, row_ids,
+                             sample_weight, pos_weight, weight_table) -> torch.Tensor:
+    """The weighted body of ``task_head_loss`` and ``head_loss`` (``task`` and ``task_table`` both None: every row has task 0)."""
+    _lib.require_gpu_tensor(emb, "graph_embedding")
+    kind = loss_kind(loss)
+    n_rows = emb.shape[0] if n_rows is None else int(n_rows)
+    T, H = ffn.weight.shape
+    if task is not None and task_table is not None:
+        raise ValueError(f"{who} needs either task, or task_table together with row_ids")
+    if task is None and task_table is None and T != 1:
+        raise ValueError(f"{who} without task or task_table needs a one-output linear layer")
+    if task_table is not None and (row_ids is None or task_table.numel() < 1):
+        raise ValueError(f"{who}: task_table needs row_ids and at least one entry")
+    _check_loss_weights(loss, T, sample_weight, pos_weight, weight_table, row_ids)
+    per_row = [t for t in (task, sample_weight, row_ids if (task_table is not None or weight_table is not None) else None)
+               if t is not None]
+    if emb.dim() != 2 or ffn.in_features != emb.shape[1] or n_rows <= 0 or n_rows > emb.shape[0] or target.numel() < n_rows \
+            or any(t.numel() < n_rows for t in per_row):
+        raise ValueError(f"{who} needs an [n, H] embedding, an H-input linear layer and a target, a task, a weight (or a row id) "
+                         "per (leading) row")
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"dropout probability {dropout_p} outside [0, 1)")
+    for name, t in (("task", task), ("task_table", task_table), ("row_ids", row_ids), ("target", target),
+                    ("sample_weight", sample_weight), ("pos_weight", pos_weight), ("weight_table", weight_table)):
+        if t is not None:
+            _lib.require_gpu_tensor(t, name)
+    if not task_head_supported(T, H) or not _WEIGHTED_LOSS:
+        keep = None
+        if dropout_p > 0.0:
+            keep = torch.empty((n_rows, H), dtype=emb.dtype, device=emb.device).bernoulli_(1.0 - dropout_p).mul_(1.0 / (1.0 - dropout_p))
+        return task_head_reference(emb, ffn.weight, ffn.bias, target, task, loss, keep, n_rows, task_table, row_ids,
+                                   sample_weight, pos_weight, weight_table)[0]
+    sw = sample_weight if sample_weight is not None else weight_table
+    return _WeightedTaskHeadFn.apply(emb, ffn.weight, ffn.bias, target, task if task is not None else task_table,
+                                     row_ids if task_table is not None else None, sw,
+                                     row_ids if weight_table is not None else None, pos_weight, float(dropout_p), n_rows, kind)
+
+
 def task_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, task: Optional[torch.Tensor] = None,
                    loss: str = "bce", dropout_p: float = 0.0, n_rows: Optional[int] = None,
-                   task_table: Optional[torch.Tensor] = None, row_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   task_table: Optional[torch.Tensor] = None, row_ids: Optional[torch.Tensor] = None,
+                   sample_weight: Optional[torch.Tensor] = None, pos_weight: Optional[torch.Tensor] = None,
+                   weight_table: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The masked multi-task loss of a ``T``-output ``ffn``: ``task_head_reference(dropout(emb), ffn.weight, ffn.bias, target,
     ...)[0]`` as two launches each way (``_TaskHeadFn``).  Every row names ONE task -- ``task [>= n_rows]`` (int32; -1, or anything
     outside ``[0, T)``: no label), or ``task_table [M]`` with ``row_ids [>= n_rows]`` (int32, on the device: row i has
     ``task_table[row_ids[i]]``; both may be static buffers a captured step refills) -- and contributes the loss of that output
     alone; the mean kinds divide by the number of labelled rows.  ``dropout_p``, its generator (``head_rng_state``) and mask,
     ``n_rows`` and the loss kinds are ``head_loss``'s.  More than 32 tasks or an embedding wider than 64: the same expression
-    through torch operators on the GPU."""
+    through torch operators on the GPU.
+
+    ``sample_weight [>= n_rows]`` (or ``weight_table [M]`` read through the same ``row_ids``) and ``pos_weight [T]``: the weighted
+    loss of ``task_head_reference`` on ``mkgnn_task_head_weighted_*`` (``_WeightedTaskHeadFn``), and then ``task`` and ``task_table``
+    may both be absent for a one-output ``ffn`` (every row has task 0).  ``MKGNN_WEIGHTED_LOSS=0`` runs the definition in torch
+    operators instead.  With none of the three given nothing changes."""
+    if sample_weight is not None or pos_weight is not None or weight_table is not None:
+        return _weighted_task_head_loss("task_head_loss", emb, ffn, target, task, loss, dropout_p, n_rows, task_table, row_ids,
+                                        sample_weight, pos_weight, weight_table)
     _lib.require_gpu_tensor(emb, "graph_embedding")
     kind = loss_kind(loss)
     n_rows = emb.shape[0] if n_rows is None else int(n_rows)
@@ -1821,6 +2053,12 @@ class _TailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind=_lib.LOSS_BCE_MEAN, p_readout=0.0):
+        return _TailFn._run(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind, p_readout, None)
+
+    @staticmethod
+    def _run(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind, p_readout, weights):
+        """The forward of ``_TailFn`` (``weights`` None) and of ``_WeightedTailFn`` (``weights``: (sw, wids, pw), float32 / int32
+        contiguous device tensors or None each -- ``mkgnn_tail_fused_weighted``)."""
         global _TAIL_PROJECT_NEXT
         project, _TAIL_PROJECT_NEXT = _TAIL_PROJECT_NEXT, False         # (tail_loss's one-shot: see there)
         lib = _lib.load()
@@ -1869,7 +2107,11 @@ class _TailFn(torch.autograd.Function):
                 # convolution's backward, gsim's only reader, forms it in its coefficient pre-pass and gsim is never written --
                 # anything else that comes first (tail_flush, tail_score, another loss) makes the launch that was left out
                 _lib.check(lib.mkgnn_tail_defer_projection(1), "mkgnn_tail_defer_projection")
-            if p_readout > 0.0:
+            if weights is not None:
+                lw = _loss_weights(*weights)
+                _lib.check(lib.mkgnn_tail_fused_weighted(ctypes.byref(a), float(p_readout), ctypes.byref(lw), ws.data_ptr(),
+                                                         ws.numel(), _lib.stream_ptr(dev)), "mkgnn_tail_fused_weighted")
+            elif p_readout > 0.0:
                 _lib.check(lib.mkgnn_tail_fused_readout_dropout(ctypes.byref(a), float(p_readout), ws.data_ptr(), ws.numel(),
                                                                 _lib.stream_ptr(dev)), "mkgnn_tail_fused_readout_dropout")
             else:
@@ -1906,6 +2148,21 @@ class _TailFn(torch.autograd.Function):
         return (*grads, None, None, None, None, None, None, None, None)
 
 
+class _WeightedTailFn(_TailFn):
+    """``_TailFn`` with the weighted loss (``mkgnn_tail_fused_weighted``): a sample weight per molecule (``sw``, read directly or
+    through ``wids``) and one positive weight (``pw [1]``).  Same deferral, hook and contiguity rules, same single backward."""
+
+    @staticmethod
+    def forward(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind, p_readout, sw, wids, pw):
+        weights = (_f32(sw), _i32(wids), _f32(pw))
+        ctx.weights = weights                  # (a deferred launch order does not read them: the middle kernel has run)
+        return _TailFn._run(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind, p_readout, weights)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        return (*_TailFn.backward(ctx, grad_loss), None, None, None)
+
+
 def _sole_reader_is_the_convolution(sim: torch.Tensor) -> bool:
     """``sim`` comes straight out of a kernel convolution (its block rows, not propagated) and nothing is in the way of its
     gradient: no hook on it and no ``retain_grad`` -- the gradient the tail hands back goes to that convolution's backward and
@@ -1917,13 +2174,26 @@ def _sole_reader_is_the_convolution(sim: torch.Tensor) -> bool:
 
 def tail_loss(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torch.nn.Linear, ffn: torch.nn.Linear,
               target: torch.Tensor, seg: "MoleculeSegments", dropout_p: float = 0.0, n_rows: Optional[int] = None,
-              loss: str = "bce", readout_dropout_p: float = 0.0) -> torch.Tensor:
+              loss: str = "bce", readout_dropout_p: float = 0.0, sample_weight: Optional[torch.Tensor] = None,
+              pos_weight: Optional[torch.Tensor] = None, weight_table: Optional[torch.Tensor] = None,
+              row_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``head_loss(readout_blocks(sim, ...), ffn, target, loss, dropout_p, n_rows)`` as ONE operator whose forward also takes
     every gradient (``_TailFn``).  ``readout_dropout_p``: the readout's own dropout (``MolKGNNNet``'s ``drop_ratio`` in training
     mode), its mask drawn in the kernels from ``head_rng_state`` as ``readout_dropout_mask`` gives it.  The caller has checked
-    ``tail_supported`` and ``_tail_limits_ok``."""
+    ``tail_supported`` and ``_tail_limits_ok``.  ``sample_weight`` (per molecule; or ``weight_table`` through ``row_ids``) and
+    ``pos_weight [1]``: ``head_loss``'s weighted loss, on ``mkgnn_tail_fused_weighted`` (``_WeightedTailFn``)."""
     kind = loss_kind(loss)
     n_rows = seg.size if n_rows is None else int(n_rows)
+    weighted = sample_weight is not None or pos_weight is not None or weight_table is not None
+    if weighted:
+        _check_loss_weights(loss, 1, sample_weight, pos_weight, weight_table, row_ids)
+        per_mol = sample_weight if sample_weight is not None else (row_ids if weight_table is not None else None)
+        if per_mol is not None and per_mol.numel() < n_rows:
+            raise ValueError("tail_loss needs a weight (or a row id) per (leading) molecule")
+        for name, t in (("sample_weight", sample_weight), ("pos_weight", pos_weight), ("weight_table", weight_table),
+                        ("row_ids", row_ids if weight_table is not None else None)):
+            if t is not None:
+                _lib.require_gpu_tensor(t, name)
     if ffn.out_features != 1 or n_rows <= 0 or n_rows > seg.size or target.numel() != n_rows:
         raise ValueError("tail_loss needs a one-output linear layer and one target per (leading) molecule")
     if not 0.0 <= readout_dropout_p < 1.0:
@@ -1932,6 +2202,11 @@ def tail_loss(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torc
     global _TAIL_PROJECT_NEXT
     _TAIL_PROJECT_NEXT = bool(_DEFER_TAIL_REDUCE and _sole_reader_is_the_convolution(sim))
     try:
+        if weighted:
+            return _WeightedTailFn.apply(sim, lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight, ffn.bias, target, seg,
+                                         plan, tuple(blocks), float(dropout_p), n_rows, kind, float(readout_dropout_p),
+                                         sample_weight if sample_weight is not None else weight_table,
+                                         row_ids if weight_table is not None else None, pos_weight)
         return _TailFn.apply(sim, lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight, ffn.bias, target, seg, plan,
                              tuple(blocks), float(dropout_p), n_rows, kind, float(readout_dropout_p))
     finally:

@@ -93,6 +93,25 @@ def task_index(assay_id, assays) -> torch.Tensor:
     return out
 
 
+def pos_weights(labels, tasks=None, num_tasks: int = 1) -> torch.Tensor:
+    """``BCEWithLogitsLoss``'s ``pos_weight`` per task: float32 ``[num_tasks]`` with ``n_negative / n_positive`` over the task's
+    labelled molecules (``tasks``: one task index per molecule, anything outside ``[0, num_tasks)``: no label; None: every
+    molecule has task 0).  A task without a positive or without a molecule gets 1."""
+    y = torch.as_tensor(labels).reshape(-1).cpu()
+    t = torch.zeros(y.numel(), dtype=torch.int64) if tasks is None else torch.as_tensor(tasks).reshape(-1).cpu().long()
+    if y.numel() != t.numel():
+        raise ValueError("labels and tasks differ in length")
+    if num_tasks < 1:
+        raise ValueError("pos_weights needs at least one task")
+    out = torch.ones(int(num_tasks), dtype=torch.float32)
+    active = y != 0
+    for task in range(int(num_tasks)):
+        pos, neg = int(((t == task) & active).sum()), int(((t == task) & ~active).sum())
+        if pos > 0:
+            out[task] = neg / pos
+    return out
+
+
 def task_oversampling_weights(labels: torch.Tensor, tasks: torch.Tensor) -> torch.Tensor:
     """``oversampling_weights`` per task: a labelled molecule (``tasks >= 0``) gets ``1 / #(molecules of its task and its
     class)``, so every (task, class) cell draws the same total weight; an unlabelled one gets 0 and is never drawn.  For one

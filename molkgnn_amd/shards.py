@@ -718,9 +718,13 @@ class ResidentShard:
 
     ``assays`` (a list of assay ids: the tasks of a mixed-assay model, in output order) keeps ``task`` -- every molecule's task
     index on the host, ``sampling.task_index(shard.assay_id, assays)`` -- and uploads it as ``tensors["task"]`` (int32 ``[M]``):
-    ``CompactStaticBatch.gather`` hands it to the batch as the task table of the masked multi-task loss."""
+    ``CompactStaticBatch.gather`` hands it to the batch as the task table of the masked multi-task loss.
 
-    def __init__(self, shard_or_path, device="cpu", packed: bool = False, byte_cols=None, assays=None):
+    ``weights`` (a float ``[M]`` tensor or array: one loss weight per molecule -- importance weights that undo an oversampling
+    draw, label confidence, down-weighted inactives) is kept as ``weight`` (float32, on the host) and uploaded as
+    ``tensors["weight"]``: ``CompactStaticBatch.gather`` hands it to the batch as the weight table of the weighted loss."""
+
+    def __init__(self, shard_or_path, device="cpu", packed: bool = False, byte_cols=None, assays=None, weights=None):
         sh = shard_or_path if isinstance(shard_or_path, Shard) else Shard(str(shard_or_path))
         if not sh.compact_ok:
             raise ValueError(f"{sh.path}: bonds are not reversed pairs with shared byte-valued attributes: no compact form")
@@ -739,6 +743,12 @@ class ResidentShard:
             from .sampling import task_index
             self.assays = tuple(int(a) for a in assays)
             self.task = task_index(torch.from_numpy(np.array(sh.assay_id)), self.assays)
+        self.weight = None
+        if weights is not None:
+            self.weight = torch.as_tensor(np.asarray(weights) if not torch.is_tensor(weights) else weights.detach().cpu()) \
+                .reshape(-1).to(torch.float32).contiguous()
+            if self.weight.numel() != sh.n_molecules:
+                raise ValueError(f"weights holds {self.weight.numel()} entries for {sh.n_molecules} molecules")
         self.packed = bool(packed)
         self.x_col = self.x_rec = self.rec_bytes = self.byte_columns = None
         if byte_cols is not None and not self.packed:
@@ -768,6 +778,8 @@ class ResidentShard:
                 self.view.x_col, self.view.rec_bytes = self.x_col.ctypes.data, self.rec_bytes       # (a host pointer: self.x_col lives as long)
             if self.task is not None:                        # (not a field of the view: the gather does not read it)
                 self.tensors["task"] = self.task.to(self.device)
+            if self.weight is not None:                      # (nor this one)
+                self.tensors["weight"] = self.weight.to(self.device)
 
     def nbytes(self) -> int:
         """Bytes of device memory the shard takes (0 for an unpacked shard on the CPU, which uploads nothing; the packed form

@@ -237,7 +237,100 @@ class GNNModel(torch.nn.Module):
         return task_head_loss(graph_embedding, self.ffn, data.y, task, kind, dropout_p=p,
                               n_rows=getattr(data, 'n_valid_molecules', None), task_table=table, row_ids=rows)
 
+    def _weighted_loss(self, data):
+        """``(kind, pos_weight, sample_weight, weight_table, weight_rows)`` when the loss is one of the HIP head's WEIGHTED losses
+        (``readout.task_head_reference``), else None -- ``_loss_kind`` knows nothing of weights and stays as it is.
+        ``pos_weight``: ``BCEWithLogitsLoss(reduction='mean', weight=None, pos_weight=p)`` with ``p`` a float32 tensor on the batch's
+        device (a buffer of ``loss_func``: ``model.to(device)`` moves it) of ``task_dim`` elements, or of one, broadcast once and
+        kept by tensor identity and version.  Sample weights: with any loss kind of ``_loss_kind`` (or that ``pos_weight`` loss), a
+        batch that carries ``weight`` (float32, one per molecule) or ``weight_table`` with ``weight_rows`` (a resident shard's
+        weights and the batch's molecule ids, ``padding.CompactStaticBatch.gather``).  A model with several outputs needs the
+        batch's tasks (``task`` / ``task_table``) as well."""
+        lf, T, dev = self.loss_func, self.ffn.out_features, data.x.device
+        kind, pw = self._loss_kind(), None
+        if kind is None and type(lf) is BCEWithLogitsLoss and lf.reduction == "mean" and lf.weight is None and lf.pos_weight is not None:
+            p = lf.pos_weight
+            if p.dtype != torch.float32 or p.device != dev or p.numel() not in (1, T):
+                return None
+            kind, pw = "bce", p.detach().reshape(-1)
+            if pw.numel() != T:
+                held = getattr(self, "_pos_weight_held", None)
+                if held is None or held[0] is not p or held[1] != p._version:
+                    held = self._pos_weight_held = (p, p._version, pw.expand(T).contiguous())
+                pw = held[2]
+        if kind is None:
+            return None
+        sw = getattr(data, 'weight', None)
+        table, rows = (None, None) if sw is not None else (getattr(data, 'weight_table', None), getattr(data, 'weight_rows', None))
+        if table is None or rows is None:
+            table = rows = None
+        if sw is not None and not (torch.is_tensor(sw) and sw.dtype == torch.float32 and sw.device == dev):
+            raise ValueError("batch.weight must be a float32 tensor on the batch's device (one loss weight per molecule)")
+        if pw is None and sw is None and table is None:
+            return None
+        multi = getattr(data, 'task', None) is not None or (
+            getattr(data, 'task_table', None) is not None and getattr(data, 'task_rows', None) is not None)
+        if T != 1 and not multi:
+            return None
+        return kind, pw, sw, table, rows
+
+    def _weighted(self, data, kind: str, pw, sw, table, rows):
+        """The weighted loss on its HIP route: mixed-assay batches on the task-indexed head (as ``_task_loss``), single-task ones on
+        the fused tail where model and batch qualify and on the separate readout operators + the weighted head otherwise
+        (``MKGNN_WEIGHTED_LOSS=0``: the definition in torch operators behind the separate readout).  The molecule-resident step is
+        not taken."""
+        from . import readout as R
+        p = self.dropout.p if self.training else 0.0
+        nreal = getattr(data, 'n_valid_molecules', None)
+        task = getattr(data, 'task', None)
+        ttable, trows = (None, None) if task is not None else (getattr(data, 'task_table', None), getattr(data, 'task_rows', None))
+        if ttable is None or trows is None:
+            ttable = trows = None
+        if task is not None or ttable is not None:
+            graph_embedding = self.gnn_model(data)
+            if table is not None and trows is not None and rows is not trows:
+                # (two id vectors: the kernels read ONE -- the weights are looked up here)
+                n = graph_embedding.shape[0] if nreal is None else int(nreal)
+                sw, table, rows = R._row_weights(None, table, rows, n), None, None
+            return R.task_head_loss(graph_embedding, self.ffn, data.y, task, kind, dropout_p=p, n_rows=nreal, task_table=ttable,
+                                    row_ids=trows if trows is not None else rows, sample_weight=sw, pos_weight=pw,
+                                    weight_table=table)
+        kw = dict(sample_weight=sw, pos_weight=pw, weight_table=table, row_ids=rows)
+        tail = (self.ffn, data.y, p, nreal, kind, kw) if R._WEIGHTED_LOSS else None
+        graph_embedding = self.gnn_model(data, _tail=tail)
+        if isinstance(graph_embedding, tuple):
+            return graph_embedding[1]
+        return R.head_loss(graph_embedding, self.ffn, data.y, kind, dropout_p=p, n_rows=nreal, **kw)
+
+    def _weighted_definition(self, data, kind: str, pw, sw, table, rows):
+        """The weighted loss as its definition in torch operators (``readout.task_head_reference``) behind the separate readout
+        and ``self.dropout``: what a batch with weights gets where the HIP route does not apply (head dropout ``p >= 1``)."""
+        from .readout import task_head_reference
+        graph_embedding = self.dropout(self.gnn_model(data))
+        task = getattr(data, 'task', None)
+        ttable, trows = (None, None) if task is not None else (getattr(data, 'task_table', None), getattr(data, 'task_rows', None))
+        if ttable is None or trows is None:
+            ttable = trows = None
+        nreal = getattr(data, 'n_valid_molecules', None)
+        if table is not None and trows is not None and rows is not trows:
+            from .readout import _row_weights
+            sw, table = _row_weights(None, table, rows, graph_embedding.shape[0] if nreal is None else int(nreal)), None
+        return task_head_reference(graph_embedding, self.ffn.weight, self.ffn.bias, data.y, task, kind, None, nreal, ttable,
+                                   trows if trows is not None else rows, sw, pw, table)[0]
+
     def loss(self, data):
+        # a batch that carries loss weights gets them, or an error: never the unweighted loss in silence
+        carries = getattr(data, 'weight', None) is not None or (
+            getattr(data, 'weight_table', None) is not None and getattr(data, 'weight_rows', None) is not None)
+        weighted = self._weighted_loss(data) if data.x.is_cuda else None
+        if weighted is not None:
+            if not (self.training and self.dropout.p >= 1.0):
+                return self._weighted(data, *weighted)
+            if carries:                                      # (head dropout p >= 1 keeps its route; with weights: their definition)
+                return self._weighted_definition(data, *weighted)
+        elif carries:
+            raise ValueError("the batch carries loss weights (weight / weight_table), which GNNModel.loss takes on a CUDA batch with "
+                             "BCEWithLogitsLoss (optionally pos_weight) or MSELoss, and for several outputs with the batch's tasks")
         if data.x.is_cuda and (getattr(data, 'task', None) is not None or (
                 getattr(data, 'task_table', None) is not None and getattr(data, 'task_rows', None) is not None)):
             kind = self._loss_kind()
