@@ -1512,6 +1512,53 @@ int mkgnn_maxmin_pick(const float* emb, int64_t emb_stride, int64_t n_rows, int3
                       float stop_sim, int32_t k_max, int32_t* picks, float* pick_sim, int32_t* n_picks, int32_t* leader,
                       float* leader_sim, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Bootstrap replicates of AUC and logAUC (additive; the ABI version stays 8): B resamples of n scored rows, evaluated without
+ * sorting any of them.  The caller sorts ONCE (scores descending, stable) and passes
+ *   rank [n] int32     the rank of row i, the rows in the caller's order or, for a stratified bootstrap, class-major: the `split`
+ *                      actives first, then the inactives
+ *   y_sorted [n] uint8    non-zero where the row at a rank is active
+ *   group_last [n] uint8  non-zero where a rank ends its tie group (the next rank's score differs)
+ * Replicate b (b = 0 .. B - 1) draws, for every row i, the row
+ *   j = lo + ((uint64) philox_word(seed, offset + b, i) * size >> 32),   (lo, size) = (0, split) for i < split, (split, n - split) else
+ * (philox_word as the dropout kernels draw it: Philox4x32-10 keyed by seed, counter (i / 4, offset + b), word i % 4), and
+ * c[rank[j]] grows by one.  The call consumes the offsets offset .. offset + B - 1; with split = n the bootstrap is unstratified.
+ * molkgnn_amd/evaluation.py::bootstrap_reference is the definition of what follows: per tie group gt and gf, the drawn actives
+ * and inactives; a group with none does not exist in the replicate; the ROC points are the running sums (fps, tps) at the end of
+ * each remaining group; T and F the totals.
+ *   n_pos[b] = T (F = n - T)
+ *   two_u[b] = sum over the groups of gf * (2 * tps_before + gt), an exact integer
+ *   auc[b]   = (double) two_u / (double) (2 T F): one float64 division, bit for bit on every route
+ *   logauc[b] = the area under the curve over log10(FPR) in [lower, upper], divided by log10(upper) - log10(lower): the points
+ *               thinned as sklearn.roc_curve(drop_intermediate=True) thins them (the first and last stay, an interior point iff its
+ *               group's (gf, gt) differs from the next existing group's), (0, 0) in front, every consecutive pair clipped to
+ *               [lower, upper] in linear FPR with np.interp's formula, then (log10(b) - log10(a)) * (ya + yb) / 2
+ *   T == 0 or F == 0: auc[b] and logauc[b] are NaN.
+ * A replicate's four outputs are a function of (rank, y_sorted, group_last, n, split, seed, offset + b, lower, upper) alone: not
+ * of B, of where the call's replicates start, of the workspace's size, of which form ran or of the run.  The integers and the
+ * AUC are exact; the log-area is a float64 sum in one fixed order (tiles of 1 024 ranks in rank order, a tile's trapezoids by a
+ * fixed tree).  A rank outside [0, n) is skipped, never used as an address (its replicate's totals then fall short of n).
+ *
+ * Up to 8 192 rows ONE launch does everything: one workgroup per replicate holds the multiplicities in LDS, draws, counts and
+ * walks; the workspace is not touched.  Beyond, the call passes over the replicates, as many at a time as the workspace holds --
+ * floor(workspace_bytes / (4 ceil4(n))), at least one --: a launch that clears the pass's multiplicities and n_pos, a grid-wide draw-and-
+ * count launch (integer atomicAdd; no float atomics anywhere) and a walk launch of one workgroup per replicate.  The launch
+ * boundary is the only thing that orders workgroups against each other.  Everything runs on `stream`, is capturable, has no host
+ * round trip and no state between calls.  mkgnn_bootstrap_roc_workspace_bytes(n, replicates_per_pass) = 4 ceil4(n) *
+ * replicates_per_pass bytes beyond 8 192 rows, 16 up to there, 0 for rejected sizes; it is host arithmetic only.  Callers keep the
+ * workspace at or under MKGNN_BOOTSTRAP_WORKSPACE_CAP (1 GiB: 256 replicates of 2^20 rows in flight, 64 of 2^22) and let the call
+ * chunk B; the workspace is 16-byte aligned and needs no initialisation.
+ *
+ * Limits: 1 <= n <= MKGNN_BOOTSTRAP_MAX_ROWS (2^22: every count and 2 T F stay exact); 1 <= B <= MKGNN_BOOTSTRAP_MAX_REPLICATES
+ * per call; 0 <= split <= n; 0 < lower < upper <= 1.  Anything else -- a limit, a null pointer, a workspace that is misaligned or
+ * holds no replicate, overlapping buffers -- returns non-zero with mkgnn_last_error set, before any launch. */
+#define MKGNN_BOOTSTRAP_MAX_ROWS       4194304
+#define MKGNN_BOOTSTRAP_MAX_REPLICATES 4096
+#define MKGNN_BOOTSTRAP_WORKSPACE_CAP  1073741824
+size_t mkgnn_bootstrap_roc_workspace_bytes(int64_t n, int32_t replicates_per_pass);
+int mkgnn_bootstrap_roc(const int32_t* rank, const uint8_t* y_sorted, const uint8_t* group_last, int64_t n, int64_t split, int32_t B,
+                        uint64_t seed, uint64_t offset, double lower, double upper, double* auc, double* logauc, int64_t* two_u,
+                        int32_t* n_pos, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,11 @@ KNN_MAX_K, KNN_MAX_QUERIES, KNN_MAX_ROWS, KNN_MAX_H = 64, 1 << 20, 1 << 20, 64  
 # kgnn_knn.hip's tiling (KNN_WAVES, KNN_TILE, KNN_MIN_PART_TILES, KNN_MAX_PARTS, KNN_TARGET_BLOCKS): queries (= waves) per block,
 # candidate rows per LDS tile, the fewest tiles of a part, the most parts a launch splits the candidates into, the blocks it aims at
 KNN_WAVES, KNN_TILE, KNN_MIN_PART_TILES, KNN_MAX_PARTS, KNN_TARGET_BLOCKS = 4, 64, 2, 32, 1024
+# MKGNN_BOOTSTRAP_MAX_ROWS, MKGNN_BOOTSTRAP_MAX_REPLICATES, MKGNN_BOOTSTRAP_WORKSPACE_CAP (bytes the wrapper keeps the scratch under)
+BOOTSTRAP_MAX_ROWS, BOOTSTRAP_MAX_REPLICATES, BOOTSTRAP_WORKSPACE_CAP = 1 << 22, 4096, 1 << 30
+# kgnn_bootstrap.hip's tiling (BS_TILE, BS_DRAW_ROWS, BS_LDS_MAX_N): ranks per tile of the walk, rows per block of the draw launch,
+# the most rows whose multiplicities one workgroup keeps in LDS (beyond: the workspace and three launches per pass)
+BOOTSTRAP_TILE, BOOTSTRAP_DRAW_ROWS, BOOTSTRAP_LDS_MAX_N = 1024, 1024, 8192
 
 
 def diverse_tile(H: int) -> int:
@@ -275,7 +280,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_embed_knn_workspace_bytes", "mkgnn_embed_count_within", "mkgnn_embed_count_within_workspace_bytes",
            "mkgnn_embed_neighbours_within", "mkgnn_embed_neighbours_within_workspace_bytes", "mkgnn_graph_components",
            "mkgnn_graph_components_workspace_bytes", "mkgnn_maxmin_pick", "mkgnn_maxmin_pick_workspace_bytes",
-           "mkgnn_tail_score_mc", "mkgnn_tail_score_mc_workspace_bytes", "mkgnn_debug_set_bn_merge", "mkgnn_debug_conv_dispatch")
+           "mkgnn_tail_score_mc", "mkgnn_tail_score_mc_workspace_bytes", "mkgnn_debug_set_bn_merge", "mkgnn_debug_conv_dispatch",
+           "mkgnn_bootstrap_roc", "mkgnn_bootstrap_roc_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -528,6 +534,13 @@ def load() -> C.CDLL:
     lib.mkgnn_maxmin_pick_workspace_bytes.argtypes = [I64]
     lib.mkgnn_maxmin_pick.restype = C.c_int
     lib.mkgnn_maxmin_pick.argtypes = [P, I64, I64, I32, P, C.c_float, I32, P, P, P, P, P, P, C.c_size_t, P]
+    # bootstrap replicates of AUC and logAUC: (rank, y_sorted, group_last, n, split, B, seed, offset, lower, upper, auc, logauc, two_u,
+    # n_pos, workspace, bytes, stream); the sizing takes (n, replicates per pass)
+    lib.mkgnn_bootstrap_roc_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_bootstrap_roc_workspace_bytes.argtypes = [I64, I32]
+    lib.mkgnn_bootstrap_roc.restype = C.c_int
+    lib.mkgnn_bootstrap_roc.argtypes = [P, P, P, I64, I64, I32, C.c_uint64, C.c_uint64, C.c_double, C.c_double, P, P, P, P, P,
+                                        C.c_size_t, P]
     lib.mkgnn_kernel_exemplars_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_kernel_exemplars_workspace_bytes.argtypes = [C.POINTER(Int64x4), C.POINTER(Int32x4), I32, I32]
     lib.mkgnn_kernel_exemplars_update.restype = C.c_int

@@ -24,17 +24,25 @@ int api_fail(const char* fmt, ...) {
 int api_hip_fail(const char* what, hipError_t e) { return api_fail("%s: %s", what, hipGetErrorString(e)); }
 int spans_disjoint(const char* who, const Span* writes, int n_writes, const Span* reads, int n_reads, const char* reads_text,
                    const char* writes_text) {
-    auto overlap = [](const Span& x, const Span& y) {
+    // Every pair is looked at and the conflict that begins at the LOWEST address is the one reported (among equals the first in the
+    // order: write i against the reads, then against the writes behind it).  A buffer that starts inside another one and runs on past
+    // its end is then reported against the one it starts in, whatever the allocator happened to place behind that.
+    auto overlap_start = [](const Span& x, const Span& y) -> const char* {
         const char *xp = (const char*)x.p, *yp = (const char*)y.p;
-        return x.n && y.n && xp < yp + y.n && yp < xp + x.n;
+        return x.n && y.n && xp < yp + y.n && yp < xp + x.n ? (xp > yp ? xp : yp) : nullptr;
     };
+    const char *first = nullptr, *text = nullptr;
     for (int i = 0; i < n_writes; ++i) {
-        for (int j = 0; j < n_reads; ++j)
-            if (overlap(writes[i], reads[j])) return api_fail("%s: %s", who, reads_text);
-        for (int j = i + 1; j < n_writes; ++j)
-            if (overlap(writes[i], writes[j])) return api_fail("%s: %s", who, writes_text);
+        for (int j = 0; j < n_reads; ++j) {
+            const char* at = overlap_start(writes[i], reads[j]);
+            if (at && (!first || at < first)) { first = at; text = reads_text; }
+        }
+        for (int j = i + 1; j < n_writes; ++j) {
+            const char* at = overlap_start(writes[i], writes[j]);
+            if (at && (!first || at < first)) { first = at; text = writes_text; }
+        }
     }
-    return 0;
+    return first ? api_fail("%s: %s", who, text) : 0;
 }
 }  // namespace mkgnn
 

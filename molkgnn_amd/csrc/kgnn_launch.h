@@ -361,8 +361,9 @@ inline void note_plan(int which, int blocks, int ng, const int64_t* tiles_of, co
 int api_fail(const char* fmt, ...);
 int api_hip_fail(const char* what, hipError_t e);
 // The byte ranges a call's launches write must overlap neither what they read nor each other.  0 if so; otherwise the message
-// "<who>: <reads_text>" (a write overlaps a read) or "<who>: <writes_text>" (two writes overlap) is left and 1 returned.  A span of
-// no bytes -- an optional argument that was not given -- overlaps nothing
+// "<who>: <reads_text>" (a write overlaps a read) or "<who>: <writes_text>" (two writes overlap) is left and 1 returned: with several
+// conflicts, the one that begins at the lowest address.  A span of no bytes -- an optional argument that was not given -- overlaps
+// nothing
 struct Span { const void* p; size_t n; };
 int spans_disjoint(const char* who, const Span* writes, int n_writes, const Span* reads, int n_reads, const char* reads_text,
                    const char* writes_text);

@@ -2464,3 +2464,70 @@ def readout_dropout_mask(rng_pair: torch.Tensor, n_rows: int, H: int, p: float, 
                                                   _stride0(out) if n_rows > 0 else int(H), _lib.stream_ptr(dev)),
                    "mkgnn_readout_dropout_mask")
     return out
+
+
+def bootstrap_roc_replicates_per_pass(n: int, n_boot: int) -> int:
+    """The replicates ``bootstrap_roc`` keeps in flight when it sizes its own scratch: all ``n_boot`` where their multiplicities fit
+    under ``_lib.BOOTSTRAP_WORKSPACE_CAP`` bytes (``4 * ceil4(n)`` each), otherwise as many as do, at least one."""
+    per = 4 * ((int(n) + 3) // 4 * 4)
+    return max(1, min(int(n_boot), _lib.BOOTSTRAP_WORKSPACE_CAP // per))
+
+
+def bootstrap_roc(rank: torch.Tensor, y_sorted: torch.Tensor, group_last: torch.Tensor, split: int, n_boot: int, seed: int,
+                  offset: int, lower: float, upper: float, workspace: Optional[torch.Tensor] = None):
+    """``(auc float64 [n_boot], logauc float64 [n_boot], two_u int64 [n_boot], n_pos int32 [n_boot])``: ``n_boot`` bootstrap replicates
+    of the ROC curve of ``n`` rows whose scores were sorted ONCE (descending, stable) -- ``rank int32 [n]`` the rank of row ``i`` of the
+    caller's or class-major order, ``y_sorted uint8 [n]`` the labels by rank, ``group_last uint8 [n]`` 1 where a rank ends its tie
+    group, all contiguous CUDA tensors.  Replicate ``b`` draws with ``philox_word(seed, offset + b, i)``; ``split`` rows in front form
+    one stratum, the rest another (``split = n``: unstratified).  ``evaluation.bootstrap_reference`` is the definition: ``two_u``,
+    ``n_pos`` and ``auc`` agree with it exactly, ``logauc`` within the rounding of a float64 sum; a replicate with one class only has
+    NaN in both.  One ``mkgnn_bootstrap_roc``: no sort, no host round trip, capturable; a replicate's outputs do not depend on
+    ``n_boot``, on where the replicates start or on the scratch's size.  ``workspace``: a uint8 device tensor to use as scratch, at
+    least ``mkgnn_bootstrap_roc_workspace_bytes(n, 1)`` bytes -- the call passes over the replicates as many at a time as it holds;
+    without it a per-device buffer that only grows serves eager calls (sized for ``bootstrap_roc_replicates_per_pass``), and a call
+    inside a capture allocates its own.  Up to ``_lib.BOOTSTRAP_LDS_MAX_N`` rows no scratch is used.  It has no autograd node: called
+    where a gradient is being recorded for one of its inputs it raises."""
+    if not all(torch.is_tensor(x) and x.dim() == 1 for x in (rank, y_sorted, group_last)) or rank.dtype != torch.int32 \
+            or y_sorted.dtype != torch.uint8 or group_last.dtype != torch.uint8 \
+            or not (rank.numel() == y_sorted.numel() == group_last.numel()):
+        raise ValueError("bootstrap_roc needs rank int32 [n], y_sorted uint8 [n] and group_last uint8 [n]")
+    if not rank.is_cuda or y_sorted.device != rank.device or group_last.device != rank.device:
+        raise ValueError(f"bootstrap_roc runs on the GPU: rank is on {rank.device}, y_sorted on {y_sorted.device}, group_last on "
+                         f"{group_last.device} (there is no CPU path; evaluation.bootstrap_reference is the host form)")
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (rank, y_sorted, group_last)):
+        raise RuntimeError("bootstrap_roc is forward only: call it under torch.no_grad() (or on detached inputs)")
+    n, split, B = rank.numel(), int(split), int(n_boot)
+    if not 1 <= n <= _lib.BOOTSTRAP_MAX_ROWS:
+        raise ValueError(f"bootstrap_roc: {n} rows outside [1, {_lib.BOOTSTRAP_MAX_ROWS}]")
+    if not 1 <= B <= _lib.BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"bootstrap_roc: n_boot = {n_boot} outside [1, {_lib.BOOTSTRAP_MAX_REPLICATES}] per call")
+    if not 0 <= split <= n:
+        raise ValueError(f"bootstrap_roc: split = {split} outside [0, {n}]")
+    lower, upper = float(lower), float(upper)
+    if not (0.0 < lower < upper <= 1.0):
+        raise ValueError(f"bootstrap_roc: FPR window ({lower}, {upper}): 0 < lower < upper <= 1 is required")
+    seed, offset = int(seed), int(offset)
+    if not (0 <= seed < 1 << 64 and 0 <= offset and offset + B <= 1 << 64):
+        raise ValueError("bootstrap_roc: seed and offset .. offset + n_boot - 1 are unsigned 64-bit values")
+    if not (rank.is_contiguous() and y_sorted.is_contiguous() and group_last.is_contiguous()):
+        raise ValueError("bootstrap_roc needs contiguous tensors")
+    dev = rank.device
+    auc = torch.empty(B, dtype=torch.float64, device=dev)
+    logauc = torch.empty(B, dtype=torch.float64, device=dev)
+    two_u = torch.empty(B, dtype=torch.int64, device=dev)
+    n_pos = torch.empty(B, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    if n <= _lib.BOOTSTRAP_LDS_MAX_N:
+        ws_ptr, ws_bytes = None, 0
+    else:
+        want = workspace.numel() if workspace is not None else \
+            int(lib.mkgnn_bootstrap_roc_workspace_bytes(n, bootstrap_roc_replicates_per_pass(n, B)))
+        if workspace is not None and want < int(lib.mkgnn_bootstrap_roc_workspace_bytes(n, 1)):
+            raise ValueError(f"workspace: at least {int(lib.mkgnn_bootstrap_roc_workspace_bytes(n, 1))} bytes (one replicate)")
+        ws = _max_cosine_workspace(dev, want, workspace)
+        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkgnn_bootstrap_roc(rank.data_ptr(), y_sorted.data_ptr(), group_last.data_ptr(), n, split, B, seed, offset,
+                                           lower, upper, auc.data_ptr(), logauc.data_ptr(), two_u.data_ptr(), n_pos.data_ptr(),
+                                           ws_ptr, ws_bytes, _lib.stream_ptr(dev)), "mkgnn_bootstrap_roc")
+    return auc, logauc, two_u, n_pos

@@ -455,18 +455,32 @@ def evaluation_mode(model):
         model.train(was_training)
 
 
-def _results(model, pred_y: torch.Tensor, true_y: torch.Tensor, metrics, table: dict) -> dict:
+def _check_bootstrap(bootstrap) -> Optional[int]:
+    """The ``bootstrap`` keyword of the evaluate functions: ``None`` (no bootstrap: results and launches as without the keyword) or
+    the number of replicates, an integer of at least 1; anything else raises before a batch is run."""
+    if bootstrap is None:
+        return None
+    if isinstance(bootstrap, bool) or not isinstance(bootstrap, int) or bootstrap < 1:
+        raise ValueError(f"bootstrap = {bootstrap!r}: None, or the number of replicates (an integer >= 1)")
+    return bootstrap
+
+
+def _results(model, pred_y: torch.Tensor, true_y: torch.Tensor, metrics, table: dict, bootstrap: Optional[int] = None) -> dict:
     """The second half of ``evaluate`` and of ``evaluate_resident``: ``validation_epoch_end`` + ``get_evaluations`` on the whole
-    vectors -- the model's loss, every metric, and the two vectors themselves."""
+    vectors -- the model's loss, every metric, and the two vectors themselves; with ``bootstrap`` replicates also
+    ``evaluation.bootstrap_metrics`` of them (``results['bootstrap']``)."""
     with torch.no_grad():
         results = {'loss': model.loss_func(pred_y, true_y.float())}
     for m in metrics:
         results[m] = table[m](true_y, pred_y)
+    if bootstrap is not None:
+        from .evaluation import bootstrap_metrics
+        results['bootstrap'] = bootstrap_metrics(true_y, pred_y.detach(), n_boot=bootstrap)
     results['pred_y'], results['true_y'] = pred_y, true_y
     return results
 
 
-def evaluate(model, batches, metrics=()) -> dict:
+def evaluate(model, batches, metrics=(), bootstrap: Optional[int] = None) -> dict:
     """The reference's validation / test loop without Lightning: ``validation_step`` per batch (``model.py:221-244``:
     ``pred_y = self(batch)[0].view(-1)``, ``true_y = batch.y.view(-1)``), then ``validation_epoch_end`` + ``get_evaluations``
     (``model.py:246-296, 483-522``) on the concatenated vectors: ``loss = model.loss_func(all_pred, all_true.float())`` and
@@ -477,8 +491,12 @@ def evaluate(model, batches, metrics=()) -> dict:
     The model is put in evaluation mode and handed back in the mode it came in, also when a batch raises.  Predictions come
     from ``model.predict``; they and the labels (the first ``len(pred)`` of a batch's ``y``: a padded batch's real molecules)
     stay on their device, and nothing synchronises with the host before the last batch is launched.  Writing files and
-    logging are the caller's."""
+    logging are the caller's.
+
+    ``bootstrap``: ``None``, or a number of replicates -- then ``results['bootstrap']`` is ``evaluation.bootstrap_metrics(true_y,
+    pred_y, n_boot=bootstrap)``: the percentile intervals of AUC and ``logAUC_0.001_0.1`` under resampling of the molecules."""
     table = _check_metrics(metrics)
+    bootstrap = _check_bootstrap(bootstrap)
     with evaluation_mode(model):
         all_pred, all_true = [], []
         for batch in batches:
@@ -488,10 +506,11 @@ def evaluate(model, batches, metrics=()) -> dict:
             all_true.append(batch.y.view(-1)[:pred.shape[0]])
         if not all_pred:
             raise ValueError("evaluate needs at least one batch")
-        return _results(model, torch.cat(all_pred), torch.cat(all_true), metrics, table)
+        return _results(model, torch.cat(all_pred), torch.cat(all_true), metrics, table, bootstrap)
 
 
-def _task_results(pred: torch.Tensor, true_y: torch.Tensor, task: torch.Tensor, T: int, kind: str, metrics, table: dict) -> dict:
+def _task_results(pred: torch.Tensor, true_y: torch.Tensor, task: torch.Tensor, T: int, kind: str, metrics, table: dict,
+                  bootstrap: Optional[int] = None) -> dict:
     """The second half of ``evaluate_tasks`` and of ``evaluate_resident_tasks``: from ``pred [n, >= 1]``, the labels and every
     molecule's task (int64) to the result dictionary -- the column selection, ``evaluation.per_task`` per metric and the masked
     multi-task loss (``readout.task_head_reference`` on the selected column)."""
@@ -510,19 +529,25 @@ def _task_results(pred: torch.Tensor, true_y: torch.Tensor, task: torch.Tensor, 
         results[m] = per_task(true_y, pred_y, torch.where(lab, task, torch.full_like(task, -1)), table[m], T)
         defined = [float(v) for v in results[m] if not math.isnan(float(v))]
         results[m + '_mean'] = sum(defined) / len(defined) if defined else float("nan")
+    if bootstrap is not None:                    # (per task: evaluation.bootstrap_per_task, None for a task it cannot resample)
+        from .evaluation import bootstrap_per_task
+        results['bootstrap'] = bootstrap_per_task(true_y, pred_y.detach(), torch.where(lab, task, torch.full_like(task, -1)), T,
+                                                  n_boot=bootstrap)
     results['pred_y'], results['true_y'], results['task'] = pred_y, true_y, task
     return results
 
 
-def evaluate_tasks(model, batches, metrics=(), num_tasks: Optional[int] = None) -> dict:
+def evaluate_tasks(model, batches, metrics=(), num_tasks: Optional[int] = None, bootstrap: Optional[int] = None) -> dict:
     """``evaluate`` for a multi-task model on mixed-assay batches that carry ``task`` (one task index per molecule, -1: no label;
     ``sampling.task_index``): ``model.predict`` per batch, keeping ``pred [n, T]``.  ``results[m]`` is the list of metric ``m``
     per task over that task's labelled molecules (``evaluation.per_task``; ``nan`` for a task without any), ``results[m + '_mean']``
     its mean over the tasks with a defined (non-NaN) value, ``results['loss']`` the masked multi-task loss of the concatenated
     vectors (``readout.task_head_reference`` on the model's loss kind), ``pred_y`` every molecule's prediction for ITS task (NaN
     where it has none), ``true_y`` and ``task``.  ``num_tasks`` defaults to the model's outputs.  The model is put in evaluation
-    mode and handed back in the mode it came in, also when a batch raises."""
+    mode and handed back in the mode it came in, also when a batch raises.  ``bootstrap``: ``None``, or a number of replicates --
+    then ``results['bootstrap']`` is ``evaluation.bootstrap_per_task`` of the vectors, one entry per task."""
     table = _check_metrics(metrics)
+    bootstrap = _check_bootstrap(bootstrap)
     kind = _required_loss_kind(model, "evaluate_tasks")
     T = model.ffn.out_features if num_tasks is None else int(num_tasks)
     with evaluation_mode(model):
@@ -538,37 +563,40 @@ def evaluate_tasks(model, batches, metrics=(), num_tasks: Optional[int] = None) 
             all_task.append(task.view(-1)[:n].to(pred.device))
         if not all_pred:
             raise ValueError("evaluate_tasks needs at least one batch")
-        return _task_results(torch.cat(all_pred), torch.cat(all_true), torch.cat(all_task).long(), T, kind, metrics, table)
+        return _task_results(torch.cat(all_pred), torch.cat(all_true), torch.cat(all_task).long(), T, kind, metrics, table,
+                             bootstrap)
 
 
-def evaluate_resident(model, resident, batch_size: int, metrics=()) -> dict:
+def evaluate_resident(model, resident, batch_size: int, metrics=(), bootstrap: Optional[int] = None) -> dict:
     """``evaluate`` for a data set that lives in device memory (``shards.ResidentShard``): the same result dictionary, with
     ``pred_y`` from ``screening.score_resident`` -- every molecule of the shard in id order, the short tail included, from one
     captured graph -- and ``true_y`` from ``resident.y``.  Unknown metric names raise before anything is launched; the model
-    comes back in the mode it came in."""
+    comes back in the mode it came in.  ``bootstrap``: as in ``evaluate``."""
     from .screening import score_resident
     table = _check_metrics(metrics)
+    bootstrap = _check_bootstrap(bootstrap)
     pred_y = score_resident(model, resident, batch_size)
-    return _results(model, pred_y, resident.y.to(pred_y.device).view(-1), metrics, table)
+    return _results(model, pred_y, resident.y.to(pred_y.device).view(-1), metrics, table, bootstrap)
 
 
-def evaluate_resident_tasks(model, resident, batch_size: int, metrics=()) -> dict:
+def evaluate_resident_tasks(model, resident, batch_size: int, metrics=(), bootstrap: Optional[int] = None) -> dict:
     """``evaluate_tasks`` for a mixed-assay data set that lives in device memory (``shards.ResidentShard(..., assays=...)``): the
     same result dictionary, from ``screening.score_resident_tasks`` -- all ``T`` outputs of every molecule of the shard in id
     order, the short tail included, from one captured graph -- with ``resident.y`` as the labels and ``resident.task`` as every
     molecule's task; then exactly what ``evaluate_tasks`` does with its concatenated vectors (``_task_results``).  The predictions
     are ``readout.task_scores``' (``evaluate_tasks`` takes ``model.predict``'s, a GEMM: equal in value, not in every bit).  Unknown
     metric names, a shard without ``assays`` and a loss that is none of the head's kinds raise before anything is launched; the
-    model comes back in the mode it came in."""
+    model comes back in the mode it came in.  ``bootstrap``: as in ``evaluate_tasks``."""
     from .screening import score_resident_tasks
     table = _check_metrics(metrics)
+    bootstrap = _check_bootstrap(bootstrap)
     if getattr(resident, "task", None) is None:
         raise ValueError("evaluate_resident_tasks needs a shard that knows every molecule's task: ResidentShard(..., assays=...)")
     kind = _required_loss_kind(model, "evaluate_resident_tasks")
     pred = score_resident_tasks(model, resident, batch_size)
     true_y = resident.y.to(pred.device).view(-1)
     task = resident.task.to(pred.device).view(-1).long()
-    return _task_results(pred, true_y, task, model.ffn.out_features, kind, metrics, table)
+    return _task_results(pred, true_y, task, model.ffn.out_features, kind, metrics, table, bootstrap)
 
 
 def tune_torch_backends() -> None:
