@@ -962,6 +962,45 @@ int mkgnn_adamw_step_clipped(const mkgnn_adamw_tensor* tensors, int32_t n_tensor
                              int32_t n_groups, float max_norm, int32_t skip_nonfinite, void* workspace, size_t workspace_bytes,
                              float* stats, void* stream);
 
+/* The same steps with an average of the weights kept inside the update launch (ABI v8, additive: every declaration above is
+ * unchanged): Polyak / EMA averaging, or the equal-weight mean of the iterates (torch.optim.swa_utils.AveragedModel), with no
+ * launch of its own, and decided on the device -- a step that the guard skipped or a tensor whose flag read 0 is not averaged.
+ *
+ * Per tensor the average lies directly behind the packed state: `state` holds mkgnn_adamw_state_floats(numel) +
+ * mkgnn_adamw_average_floats(numel) floats, the second part [avg (numel) | n_averaged | one n_averaged per 1024 elements]
+ * (numel + 1 + ceil(numel / 1024) floats; 0 for numel < 1).  The counts are floats, exact to 2^24, one copy per block of the
+ * update as for the step count: no block reads what another writes; block 0 also writes the canonical copy.  The caller
+ * initialises avg (to the parameter) and zeroes the counts; a caller that sets the count sets every copy.
+ *
+ * A tensor's step is TAKEN when mkgnn_adamw_step / mkgnn_adamw_step_clipped would change it.  After a taken step that produced
+ * p_new and the step count t:
+ *   t <= start:                  avg = p_new (the same bits), n_averaged stays 0
+ *   t >  start, n_averaged == 0: avg = p_new, n_averaged = 1
+ *   t >  start, n = n_averaged:  avg = avg + fl32(w * fl32(p_new - avg)), n_averaged = n + 1 -- three float32 operations, each
+ *                                rounded, no fused multiply-add; w == 1 copies p_new instead
+ * w is formed per block in double and rounded once to float32: mean: 1 / (n + 1); ema: 1 - d with d = decay, or with warmup
+ * d = min(decay, (1 + n) / (10 + n)).  A step that is not taken changes neither avg nor any count by a bit.
+ *
+ * Parameters, moments, step counts and stats are bit for bit those of mkgnn_adamw_step (when max_norm == +inf, skip_nonfinite ==
+ * 0 and stats == NULL: one launch per 80 tensors, workspace ignored) and of mkgnn_adamw_step_clipped (otherwise: that entry's
+ * launches, checks, workspace and stats).  The two reserved floats of the state stay as they are.  Capturable, no atomics.
+ * A null `avg`, a mode that is neither constant, decay outside [0, 1) or NaN, start < 0 and everything the underlying entry
+ * refuses return non-zero with mkgnn_last_error set before any launch. */
+#define MKGNN_ADAMW_AVERAGE_EMA 0
+#define MKGNN_ADAMW_AVERAGE_MEAN 1
+typedef struct { int32_t mode; float decay; int32_t warmup; int32_t start; } mkgnn_adamw_average;
+int64_t mkgnn_adamw_average_floats(int64_t numel);
+int mkgnn_adamw_step_averaged(const mkgnn_adamw_tensor* tensors, int32_t n_tensors, const mkgnn_adamw_group* groups,
+                              int32_t n_groups, const mkgnn_adamw_average* avg, float max_norm, int32_t skip_nonfinite,
+                              void* workspace, size_t workspace_bytes, float* stats, void* stream);
+
+/* n_items pairs of small float tensors, the contents of each pair exchanged, in one launch per 120 items (ceil(numel / 1024)
+ * blocks each; both loads, then both stores): the averaged weights into the model and the live ones out, and back.  No two
+ * tensors of a call may overlap -- not a and b of one item, not tensors of different items.  Capturable (pointers are baked in).
+ * A negative n_items, a null pointer or numel outside 1 .. 2^30 returns non-zero with mkgnn_last_error set before any launch. */
+typedef struct mkgnn_swap_item { float* a; float* b; int64_t numel; } mkgnn_swap_item;
+int mkgnn_flat_swap(const mkgnn_swap_item* items, int32_t n_items, void* stream);
+
 /* ---- Molecule-resident small-batch step (ABI v4).
  *
  * At the reference's own batch sizes (README.md:81 `--batch_size 16`, data.py:236 default 17; BASELINE configs[0] / [2]) a

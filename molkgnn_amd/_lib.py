@@ -172,6 +172,19 @@ class AdamWGroup(C.Structure):
                 ("eps", C.c_float), ("weight_decay", C.c_float), ("maximize", C.c_int32), ("grad_scale", C.c_float)]
 
 
+class AdamWAverage(C.Structure):
+    """``mkgnn_adamw_average``; ``mode``: ``ADAMW_AVERAGE_EMA`` or ``ADAMW_AVERAGE_MEAN``."""
+    _fields_ = [("mode", C.c_int32), ("decay", C.c_float), ("warmup", C.c_int32), ("start", C.c_int32)]
+
+
+ADAMW_AVERAGE_EMA, ADAMW_AVERAGE_MEAN = 0, 1
+
+
+class SwapItem(C.Structure):
+    """``mkgnn_swap_item``."""
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("numel", C.c_int64)]
+
+
 class ShardView(C.Structure):
     _fields_ = [("x", C.c_void_p), ("p", C.c_void_p), ("edge_src", C.c_void_p), ("edge_dst", C.c_void_p),
                 ("edge_attr", C.c_void_p), ("y", C.c_void_p), ("mol_atom_ptr", C.c_void_p), ("mol_edge_ptr", C.c_void_p),
@@ -257,6 +270,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_batchnorm_backward", "mkgnn_bce_head_workspace_bytes", "mkgnn_bce_head_forward",
            "mkgnn_bce_head_backward", "mkgnn_rf_workspace_bytes", "mkgnn_rf_count", "mkgnn_rf_fill", "mkgnn_adamw_step", "mkgnn_adamw_state_floats",
            "mkgnn_adamw_clip_workspace_bytes", "mkgnn_adamw_step_clipped",
+           "mkgnn_adamw_average_floats", "mkgnn_adamw_step_averaged", "mkgnn_flat_swap",
            "mkgnn_bce_head_dropout_forward", "mkgnn_bce_head_dropout_backward", "mkgnn_segment_sum_block_rows",
            "mkgnn_plan_workspace_bytes", "mkgnn_plan_build", "mkgnn_plan_present_blocks", "mkgnn_backward_grad_blocks",
            "mkgnn_debug_grad_blocks_launches", "mkgnn_debug_poison_backward", "mkgnn_backward_join", "mkgnn_backward_streams", "mkgnn_bank_prepare", "mkgnn_bank_prepare_deferred", "mkgnn_bank_prepare_flush", "mkgnn_bank_prepare_withdraw", "mkgnn_touch_hint", "mkgnn_expand_batch", "mkgnn_bce_head_fused", "mkgnn_collate_compact", "mkgnn_collate_compact_bytes",
@@ -583,6 +597,12 @@ def load() -> C.CDLL:
     lib.mkgnn_adamw_clip_workspace_bytes.argtypes = [P, I32]
     lib.mkgnn_adamw_step_clipped.restype = C.c_int
     lib.mkgnn_adamw_step_clipped.argtypes = [P, I32, P, I32, C.c_float, I32, P, C.c_size_t, P, P]
+    lib.mkgnn_adamw_average_floats.restype = C.c_int64
+    lib.mkgnn_adamw_average_floats.argtypes = [I64]
+    lib.mkgnn_adamw_step_averaged.restype = C.c_int
+    lib.mkgnn_adamw_step_averaged.argtypes = [P, I32, P, I32, C.POINTER(AdamWAverage), C.c_float, I32, P, C.c_size_t, P, P]
+    lib.mkgnn_flat_swap.restype = C.c_int
+    lib.mkgnn_flat_swap.argtypes = [P, I32, P]
     lib.mkgnn_molecule_supported.restype = C.c_int
     lib.mkgnn_molecule_supported.argtypes = [C.POINTER(MoleculeNet), I32]
     lib.mkgnn_molecule_workspace_bytes.restype = C.c_size_t

@@ -17,6 +17,11 @@
 // table (adamw_sq_partial_kernel); EVERY block of the update adds up all partials in its prologue, in one fixed order, so all
 // blocks of all launches of the step hold the same sum bit for bit: the same coefficient everywhere, and a non-finite norm
 // skips the step in every block or in none, with no signalling between blocks.  No atomics, no host round trip.
+//
+// Averaged forms (mkgnn_adamw_step_averaged): an EMA or running mean of every parameter, updated from the p_new the block holds
+// in a register -- one more load and store per element, no launch (torch.optim.swa_utils.AveragedModel is two multi-tensor
+// launches behind the step), and only for a step that was taken: the decision is the device's.  mkgnn_flat_swap exchanges the
+// parameters with their averages for an evaluation, in one launch.
 #include <type_traits>
 #include "kgnn_launch.h"
 #include "../../include/molkgnn_hip.h"
@@ -41,6 +46,11 @@ struct AdamArgs {
 struct AdamClip { const double* partial; int32_t np; float max_norm; int32_t skip_nonfinite; float* stats; };
 struct AdamClipArgs : AdamArgs { AdamClip c; };
 static_assert(sizeof(AdamClipArgs) <= 4096, "kernel arguments of the clipped update");
+// the averaged forms: the settings of the weight average behind either argument block.  The average itself needs no pointer: it
+// lies behind the tensor's packed state (80 more pointers would not fit the 4096 bytes).
+struct AdamAvgArgs : AdamArgs { mkgnn_adamw_average v; };
+struct AdamClipAvgArgs : AdamClipArgs { mkgnn_adamw_average v; };
+static_assert(sizeof(AdamClipAvgArgs) <= 4096 && sizeof(AdamAvgArgs) <= 4096, "kernel arguments of the averaged update");
 
 // Sum of one double per lane over the 256 lanes of a block, in one fixed order, the same bits in every lane: a butterfly inside
 // each wave (both partners of an exchange form the same a + b), then the four wave sums ((w0 + w1) + w2) + w3.
@@ -59,14 +69,28 @@ __device__ __forceinline__ float mul_rounded(float a, float b) {
     return a * b;
 }
 
+// One update of the weight average, avg + fl32(w * fl32(p - avg)): three float32 operations, each rounded, none contracted -- the
+// form separate torch operators on the CPU reproduce bit for bit.
+__device__ __forceinline__ float lerp_rounded(float avg, float p, float w) {
+#pragma clang fp contract(off)
+    const float d = p - avg;
+    const float wd = w * d;
+    return avg + wd;
+}
+
 // state of a tensor: [exp_avg | exp_avg_sq | step | 2 reserved | one step counter per block of the tensor].  Every block
 // advances ITS OWN copy of the step count and derives the bias corrections from it (two double-precision pow per block), so
 // no block reads a counter another block writes: the separate one-block counting kernel of round 2 (a dependent launch,
 // 4 us of every step) is gone.  Block 0 also writes the canonical `step` the caller's state_dict reads.
-template <class Args>
+//
+// AVG (Args carries `v`): the average of the weights, [avg | canonical n_averaged | one n_averaged per block] directly behind the
+// state.  A block that takes the step loads its chunk of avg with the other loads; thread 0 derives the block's weight w from ITS
+// copy of the count (in double, rounded once) next to the bias corrections and advances that copy; w == 1 copies p_new, anything
+// else is lerp_rounded.  A block that returns early -- idle tensor, skipped step -- has touched neither avg nor a count.
+template <class Args, bool AVG = false>
 __global__ void __launch_bounds__(256) adamw_step_kernel(Args a) {
-    constexpr bool CLIP = std::is_same_v<Args, AdamClipArgs>;
-    __shared__ float bc[2];
+    constexpr bool CLIP = std::is_base_of_v<AdamClipArgs, Args>;
+    __shared__ float bc[AVG ? 3 : 2];                        // the bias corrections, and the average's weight
     // block -> tensor: the last ti with blk_start[ti] <= blockIdx.x
     int lo = 0, hi = a.nt - 1;
     while (lo < hi) {
@@ -90,11 +114,15 @@ __global__ void __launch_bounds__(256) adamw_step_kernel(Args a) {
     const int blk = (int)blockIdx.x - a.blk_start[lo];
     const int base = blk * ADAM_CHUNK;
     float g[ADAM_CHUNK / 256], p[ADAM_CHUNK / 256], mi[ADAM_CHUNK / 256], vi[ADAM_CHUNK / 256];
+    [[maybe_unused]] float av[ADAM_CHUNK / 256];
+    [[maybe_unused]] float* avg = nullptr;
+    if constexpr (AVG) avg = T.state + 2 * (size_t)T.n + 3 + (T.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
 #pragma unroll
     for (int k = 0; k < ADAM_CHUNK / 256; ++k) {          // all loads first (clamped), then the arithmetic
         const int i = base + 256 * k + (int)threadIdx.x;
         const int ic = i < T.n ? i : T.n - 1;
         g[k] = T.g[ic]; p[k] = T.p[ic]; mi[k] = m[ic]; vi[k] = v[ic];
+        if constexpr (AVG) av[k] = avg[ic];
     }
     float coef = 1.f;
     if constexpr (CLIP) {
@@ -122,9 +150,27 @@ __global__ void __launch_bounds__(256) adamw_step_kernel(Args a) {
         if (blk == 0) tail[0] = (float)t;
         bc[0] = (float)(1.0 - pow((double)G.beta1, t));
         bc[1] = sqrtf((float)(1.0 - pow((double)G.beta2, t)));
+        if constexpr (AVG) {
+            float w = 1.f;                                   // t <= start, or the first update: avg = p_new
+            if (t > (double)a.v.start) {
+                float* cnt = avg + T.n;                      // [canonical | one per block]
+                const double n = (double)cnt[1 + blk];
+                if (n >= 1.0) {
+                    double d = (double)a.v.decay;
+                    if (a.v.warmup) { const double dw = (1.0 + n) / (10.0 + n); d = dw < d ? dw : d; }
+                    w = a.v.mode == MKGNN_ADAMW_AVERAGE_MEAN ? (float)(1.0 / (n + 1.0)) : (float)(1.0 - d);
+                }
+                const float n1 = (float)(n + 1.0);
+                cnt[1 + blk] = n1;
+                if (blk == 0) cnt[0] = n1;
+            }
+            bc[2] = w;
+        }
     }
     __syncthreads();
     const float bc1 = bc[0], bc2_sqrt = bc[1];
+    [[maybe_unused]] float w = 1.f;
+    if constexpr (AVG) w = bc[2];
     const float step_size = lr / bc1;
 #pragma unroll
     for (int k = 0; k < ADAM_CHUNK / 256; ++k) {
@@ -133,10 +179,18 @@ __global__ void __launch_bounds__(256) adamw_step_kernel(Args a) {
             float gg = (G.maximize ? -g[k] : g[k]) * G.gscale;
             if constexpr (CLIP) gg = mul_rounded(gg, coef);
             float pp = p[k];
-            pp -= lr * G.wd * pp;
+            if constexpr (!AVG) {
+                pp -= lr * G.wd * pp;
+            } else {
+                // The averaged instantiations spell out every choice the compiler makes in the two above -- which multiply goes
+                // into which multiply-add depends on the code around it, and here it chose otherwise (measured: the unclipped
+                // averaged step's exp_avg and exp_avg_sq were not the unclipped step's): the rounded gg, and this multiply-add.
+                if constexpr (!CLIP) gg = mul_rounded(G.maximize ? -g[k] : g[k], G.gscale);
+                pp = fmaf(-(lr * G.wd), pp, pp);
+            }
             const float mm = fmaf(1.f - G.beta1, gg - mi[k], mi[k]);
             float vv;
-            if constexpr (!CLIP) {
+            if constexpr (!CLIP && !AVG) {
                 vv = G.beta2 * vi[k] + (1.f - G.beta2) * gg * gg;
             } else {
                 // What the compiler makes of the line above there, spelt out: a multiply-add on the rounded b2 v.  Left to
@@ -146,6 +200,7 @@ __global__ void __launch_bounds__(256) adamw_step_kernel(Args a) {
             const float denom = sqrtf(vv) / bc2_sqrt + G.eps;
             pp -= step_size * mm / denom;
             T.p[i] = pp; m[i] = mm; v[i] = vv;
+            if constexpr (AVG) avg[i] = w == 1.f ? pp : lerp_rounded(av[k], pp, w);
         }
     }
 }
@@ -219,9 +274,62 @@ __global__ void __launch_bounds__(256) flat_copy_kernel(CopyArgs a) {
     }
 }
 
+// The contents of many small tensor pairs exchanged in ONE launch: the averaged weights into the model and the live ones out of it
+// (optim.FusedAdamW.swap_averaged), and back.  flat_copy_kernel's shape: both loads first, then the two stores.
+struct SwapItem { float* a; float* b; int32_t n; int32_t pad; };
+struct SwapArgs { SwapItem t[COPY_MAX_ITEMS]; int32_t blk_start[COPY_MAX_ITEMS + 1]; int32_t nt; };
+static_assert(sizeof(SwapArgs) <= 4096, "kernel arguments of the swap");
+__global__ void __launch_bounds__(256) flat_swap_kernel(SwapArgs a) {
+    int lo = 0, hi = a.nt - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.blk_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const SwapItem T = a.t[lo];
+    const int base = ((int)blockIdx.x - a.blk_start[lo]) * ADAM_CHUNK;
+    float va[ADAM_CHUNK / 256], vb[ADAM_CHUNK / 256];
+#pragma unroll
+    for (int k = 0; k < ADAM_CHUNK / 256; ++k) {
+        const int i = base + 256 * k + (int)threadIdx.x;
+        const int ic = i < T.n ? i : T.n - 1;
+        va[k] = T.a[ic]; vb[k] = T.b[ic];
+    }
+#pragma unroll
+    for (int k = 0; k < ADAM_CHUNK / 256; ++k) {
+        const int i = base + 256 * k + (int)threadIdx.x;
+        if (i < T.n) { T.a[i] = vb[k]; T.b[i] = va[k]; }
+    }
+}
+
 }  // namespace mkgnn
 
 using namespace mkgnn;
+
+extern "C" int mkgnn_flat_swap(const mkgnn_swap_item* items, int32_t n_items, void* stream) {
+    if (n_items < 0) return api_fail("mkgnn_flat_swap: %d items", n_items);
+    if (n_items == 0) return 0;
+    if (!items) return api_fail("mkgnn_flat_swap: null pointer");
+    for (int32_t i = 0; i < n_items; ++i)                     // every item is looked at before anything is launched
+        if (!items[i].a || !items[i].b || items[i].numel < 1 || items[i].numel > (1 << 30))
+            return api_fail("mkgnn_flat_swap: item %d: null pointer or numel %lld out of range", i, (long long)items[i].numel);
+    hipStream_t st = (hipStream_t)stream;
+    SwapArgs a{};
+    for (int32_t first = 0; first < n_items; first += COPY_MAX_ITEMS) {
+        const int nt = n_items - first < COPY_MAX_ITEMS ? n_items - first : COPY_MAX_ITEMS;
+        int blocks = 0;
+        for (int i = 0; i < nt; ++i) {
+            const mkgnn_swap_item& s = items[first + i];
+            a.t[i] = SwapItem{s.a, s.b, (int32_t)s.numel, 0};
+            a.blk_start[i] = blocks;
+            blocks += (int)((s.numel + ADAM_CHUNK - 1) / ADAM_CHUNK);
+        }
+        a.blk_start[nt] = blocks;
+        a.nt = nt;
+        flat_swap_kernel<<<blocks, 256, 0, st>>>(a);
+    }
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : api_hip_fail("mkgnn_flat_swap", e);
+}
 
 extern "C" int mkgnn_flat_copy(const mkgnn_copy_item* items, int32_t n_items, void* stream) {
     if (n_items < 0) return api_fail("mkgnn_flat_copy: %d items", n_items);
@@ -281,23 +389,39 @@ static int adam_fill_launch(AdamArgs& a, const mkgnn_adamw_tensor* tensors, int3
     return 0;
 }
 
-extern "C" int mkgnn_adamw_step(const mkgnn_adamw_tensor* tensors, int32_t n_tensors, const mkgnn_adamw_group* groups,
-                                int32_t n_groups, void* stream) {
+// The unclipped step of `Args` (AdamArgs, or AdamAvgArgs with the average's settings `v`): one launch per 80 tensors.
+template <class Args>
+static int adam_step(const char* who, const mkgnn_adamw_tensor* tensors, int32_t n_tensors, const mkgnn_adamw_group* groups,
+                     int32_t n_groups, const mkgnn_adamw_average* v, void* stream) {
+    constexpr bool AVG = std::is_same_v<Args, AdamAvgArgs>;
     if (n_tensors < 0 || n_groups < 1 || n_groups > ADAM_MAX_GROUPS)
-        return api_fail("mkgnn_adamw_step: %d tensors, %d groups (1..%d groups)", n_tensors, n_groups, ADAM_MAX_GROUPS);
+        return api_fail("%s: %d tensors, %d groups (1..%d groups)", who, n_tensors, n_groups, ADAM_MAX_GROUPS);
     if (n_tensors == 0) return 0;
-    if (!tensors || !groups) return api_fail("mkgnn_adamw_step: null pointer");
+    if (!tensors || !groups) return api_fail("%s: null pointer", who);
     hipStream_t st = (hipStream_t)stream;
-    AdamArgs a{};
-    if (int rc = adam_fill_groups(a, groups, n_groups, "mkgnn_adamw_step")) return rc;
+    Args a{};
+    if constexpr (AVG) a.v = *v;
+    if (int rc = adam_fill_groups(a, groups, n_groups, who)) return rc;
+    if constexpr (AVG) {                                     // the averaged entry looks at every tensor before anything is launched
+        for (int32_t first = 0; first < n_tensors; first += ADAM_MAX_TENSORS) {
+            const int nt = n_tensors - first < ADAM_MAX_TENSORS ? n_tensors - first : ADAM_MAX_TENSORS;
+            int blocks = 0;
+            if (int rc = adam_fill_launch(a, tensors, first, nt, n_groups, who, &blocks)) return rc;
+        }
+    }
     for (int32_t first = 0; first < n_tensors; first += ADAM_MAX_TENSORS) {
         const int nt = n_tensors - first < ADAM_MAX_TENSORS ? n_tensors - first : ADAM_MAX_TENSORS;
         int blocks = 0;
-        if (int rc = adam_fill_launch(a, tensors, first, nt, n_groups, "mkgnn_adamw_step", &blocks)) return rc;
-        adamw_step_kernel<AdamArgs><<<blocks, 256, 0, st>>>(a);
+        if (int rc = adam_fill_launch(a, tensors, first, nt, n_groups, who, &blocks)) return rc;
+        adamw_step_kernel<Args, AVG><<<blocks, 256, 0, st>>>(a);
     }
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail("mkgnn_adamw_step", e);
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+extern "C" int mkgnn_adamw_step(const mkgnn_adamw_tensor* tensors, int32_t n_tensors, const mkgnn_adamw_group* groups,
+                                int32_t n_groups, void* stream) {
+    return adam_step<AdamArgs>("mkgnn_adamw_step", tensors, n_tensors, groups, n_groups, nullptr, stream);
 }
 
 // blocks of the whole table (a tensor without elements has none)
@@ -314,10 +438,12 @@ extern "C" size_t mkgnn_adamw_clip_workspace_bytes(const mkgnn_adamw_tensor* ten
     return blocks ? sizeof(double) * (size_t)(blocks + 1) : 0;
 }
 
-extern "C" int mkgnn_adamw_step_clipped(const mkgnn_adamw_tensor* tensors, int32_t n_tensors, const mkgnn_adamw_group* groups,
-                                        int32_t n_groups, float max_norm, int32_t skip_nonfinite, void* workspace,
-                                        size_t workspace_bytes, float* stats, void* stream) {
-    const char* who = "mkgnn_adamw_step_clipped";
+// The clipped step of `Args` (AdamClipArgs, or AdamClipAvgArgs with the average's settings `v`).
+template <class Args>
+static int adam_step_clipped(const char* who, const mkgnn_adamw_tensor* tensors, int32_t n_tensors, const mkgnn_adamw_group* groups,
+                             int32_t n_groups, const mkgnn_adamw_average* v, float max_norm, int32_t skip_nonfinite, void* workspace,
+                             size_t workspace_bytes, float* stats, void* stream) {
+    constexpr bool AVG = std::is_same_v<Args, AdamClipAvgArgs>;
     if (n_tensors < 0 || n_groups < 1 || n_groups > ADAM_MAX_GROUPS)
         return api_fail("%s: %d tensors, %d groups (1..%d groups)", who, n_tensors, n_groups, ADAM_MAX_GROUPS);
     if (!(max_norm > 0.f)) return api_fail("%s: max_norm %g (> 0, or +inf for the norm and the guard alone)", who, max_norm);
@@ -325,7 +451,8 @@ extern "C" int mkgnn_adamw_step_clipped(const mkgnn_adamw_tensor* tensors, int32
     if (n_tensors == 0) return 0;
     if (!tensors || !groups) return api_fail("%s: null pointer", who);
     hipStream_t st = (hipStream_t)stream;
-    AdamClipArgs a{};
+    Args a{};
+    if constexpr (AVG) a.v = *v;
     if (int rc = adam_fill_groups(a, groups, n_groups, who)) return rc;
     int blocks = 0;
     for (int32_t first = 0; first < n_tensors; first += ADAM_MAX_TENSORS) {   // every tensor is looked at before anything is launched
@@ -355,9 +482,35 @@ extern "C" int mkgnn_adamw_step_clipped(const mkgnn_adamw_tensor* tensors, int32
     for (int32_t first = 0; first < n_tensors; first += ADAM_MAX_TENSORS) {
         const int nt = n_tensors - first < ADAM_MAX_TENSORS ? n_tensors - first : ADAM_MAX_TENSORS;
         adam_fill_launch(a, tensors, first, nt, n_groups, who, &blocks);
-        adamw_step_kernel<AdamClipArgs><<<blocks, 256, 0, st>>>(a);
+        adamw_step_kernel<Args, AVG><<<blocks, 256, 0, st>>>(a);
         c.stats = nullptr;                                   // block 0 of the first launch alone writes them
     }
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
+extern "C" int mkgnn_adamw_step_clipped(const mkgnn_adamw_tensor* tensors, int32_t n_tensors, const mkgnn_adamw_group* groups,
+                                        int32_t n_groups, float max_norm, int32_t skip_nonfinite, void* workspace,
+                                        size_t workspace_bytes, float* stats, void* stream) {
+    return adam_step_clipped<AdamClipArgs>("mkgnn_adamw_step_clipped", tensors, n_tensors, groups, n_groups, nullptr, max_norm,
+                                           skip_nonfinite, workspace, workspace_bytes, stats, stream);
+}
+
+extern "C" int64_t mkgnn_adamw_average_floats(int64_t numel) {
+    return numel < 1 ? 0 : numel + 1 + (numel + ADAM_CHUNK - 1) / ADAM_CHUNK;
+}
+
+extern "C" int mkgnn_adamw_step_averaged(const mkgnn_adamw_tensor* tensors, int32_t n_tensors, const mkgnn_adamw_group* groups,
+                                         int32_t n_groups, const mkgnn_adamw_average* avg, float max_norm, int32_t skip_nonfinite,
+                                         void* workspace, size_t workspace_bytes, float* stats, void* stream) {
+    const char* who = "mkgnn_adamw_step_averaged";
+    if (!avg) return api_fail("%s: null average settings", who);
+    if (avg->mode != MKGNN_ADAMW_AVERAGE_EMA && avg->mode != MKGNN_ADAMW_AVERAGE_MEAN)
+        return api_fail("%s: unknown average mode %d", who, avg->mode);
+    if (!(avg->decay >= 0.f && avg->decay < 1.f)) return api_fail("%s: average decay %g (0 <= decay < 1)", who, avg->decay);
+    if (avg->start < 0) return api_fail("%s: average start %d (>= 0)", who, avg->start);
+    if (max_norm == INFINITY && !skip_nonfinite && !stats)
+        return adam_step<AdamAvgArgs>(who, tensors, n_tensors, groups, n_groups, avg, stream);
+    return adam_step_clipped<AdamClipAvgArgs>(who, tensors, n_tensors, groups, n_groups, avg, max_norm, skip_nonfinite, workspace,
+                                              workspace_bytes, stats, stream);
 }

@@ -11,9 +11,14 @@ fp32 CUDA parameters only; no CPU path (``MolKGNNLibraryError`` otherwise).
 ``max_grad_norm`` / ``skip_nonfinite`` (both off by default: the step above, the same launch and the same bits) clip the
 gradients by their global norm and skip a step whose norm is not finite, inside the step and on the device
 (``mkgnn_adamw_step_clipped``): one more launch, nothing read back, capturable.
+
+``average='ema' | 'mean'`` (off by default: the steps above, the same launches, bits and state size) keeps an average of the
+weights inside the same launch (``mkgnn_adamw_step_averaged``): ``state[p]['param_avg']`` / ``['n_averaged']``,
+``averaged_parameters()``, ``swap_averaged()`` and the context manager ``averaged_weights()``.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import List
 
@@ -24,7 +29,8 @@ from . import _lib
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, maximize: bool = False,
-                 grad_scale: float = 1.0, max_grad_norm=None, skip_nonfinite: bool = False):
+                 grad_scale: float = 1.0, max_grad_norm=None, skip_nonfinite: bool = False, average=None,
+                 average_decay: float = 0.999, average_warmup: bool = True, average_start: int = 0):
         """``max_grad_norm``: the gradients of one step are scaled by ``min(1, max_grad_norm / (norm + 1e-6))``, ``norm`` the
         2-norm of ALL gradients the step reads, across the parameter groups, each after its group's ``maximize`` and
         ``grad_scale`` -- ``torch.nn.utils.clip_grad_norm_``'s coefficient.  Unlike ``clip_grad_norm_`` the clip lives in the
@@ -35,7 +41,16 @@ class FusedAdamW(torch.optim.Optimizer):
         all of them into NaN).  ``max_grad_norm=None`` with the guard on: the norm and the guard, no clipping.  ``grad_norm``
         (the norm before clipping), ``clip_coef`` and ``skipped_steps`` are 0-dim CUDA tensors filled by the step; reading them
         does not synchronise until their value is asked for.  Both settings are attributes of the optimiser, not keys of
-        ``param_groups`` (the norm spans the groups): ``state_dict()`` does not carry them."""
+        ``param_groups`` (the norm spans the groups): ``state_dict()`` does not carry them.
+
+        ``average``: ``'ema'`` or ``'mean'`` keeps, per parameter, an average of the iterates in ``state[p]['param_avg']`` with the
+        number of iterates in it in ``state[p]['n_averaged']`` -- ``torch.optim.swa_utils.AveragedModel``'s update, made inside the
+        step's launch.  A parameter's step that does not happen (no gradient, an active flag of 0, a step ``skip_nonfinite``
+        skipped) is not averaged.  Until a parameter's step count exceeds ``average_start`` its average tracks it.  ``'ema'``:
+        ``avg += (1 - d) (p - avg)`` with ``d = average_decay`` or, with ``average_warmup``, ``min(average_decay, (1 + n) /
+        (10 + n))``; ``'mean'``: ``avg += (p - avg) / (n + 1)``.  Only parameters are averaged: buffers (the batch-norm
+        running statistics) are the live model's.  Settings of the optimiser, not of its groups; the two state entries travel in
+        ``state_dict()``."""
         if not isinstance(lr, torch.Tensor) and lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
@@ -56,6 +71,18 @@ class FusedAdamW(torch.optim.Optimizer):
                 raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (> 0, or None)")
         self.max_grad_norm = max_grad_norm
         self.skip_nonfinite = bool(skip_nonfinite)
+        if average not in (None, "ema", "mean"):
+            raise ValueError(f"Invalid average: {average!r} (None, 'ema' or 'mean')")
+        average_decay = float(average_decay)
+        if not 0.0 <= average_decay < 1.0:                   # (a NaN is refused here as well)
+            raise ValueError(f"Invalid average_decay: {average_decay} (0 <= decay < 1)")
+        if int(average_start) != average_start or average_start < 0:
+            raise ValueError(f"Invalid average_start: {average_start} (an integer >= 0)")
+        self.average = average
+        self.average_decay, self.average_warmup, self.average_start = average_decay, bool(average_warmup), int(average_start)
+        self._in_averaged = False                            # inside averaged_weights(): the parameters hold the averages
+        self._swap_key = None
+        self._swap_table = None
         self._clip_stats = None                              # [norm, coef, skipped steps, reserved] on the device
         self._clip_ws = None                                 # one double per 1024-element block of the table, and one more
         self._clip_need = 0
@@ -125,33 +152,54 @@ class FusedAdamW(torch.optim.Optimizer):
         return self._stat(2)
 
     # -- state: one buffer per parameter, [exp_avg | exp_avg_sq | step | 2 reserved | a step count per 1024 elements]
-    # (mkgnn_adamw_state_floats); the three state entries are views of it --
+    # (mkgnn_adamw_state_floats); the three state entries are views of it.  With averaging [param_avg | n_averaged | an
+    # n_averaged per 1024 elements] (mkgnn_adamw_average_floats) follows in the same buffer, two more views --
     @staticmethod
     def _state_floats(n: int) -> int:
         return 2 * n + 3 + (n + 1023) // 1024
+
+    @staticmethod
+    def _average_floats(n: int) -> int:
+        return n + 1 + (n + 1023) // 1024
+
+    def _packed_floats(self, n: int) -> int:
+        return self._state_floats(n) + (self._average_floats(n) if self.average is not None else 0)
 
     def _packed_state(self, p: torch.Tensor) -> torch.Tensor:
         st = self.state[p]
         n = p.numel()
         buf = st.get("_packed")
-        if buf is not None and st["exp_avg"].data_ptr() == buf.data_ptr() and st["step"].data_ptr() == buf[2 * n:].data_ptr() and buf.numel() == self._state_floats(n):
-            return buf
+        if buf is not None and st["exp_avg"].data_ptr() == buf.data_ptr() and st["step"].data_ptr() == buf[2 * n:].data_ptr() and buf.numel() == self._packed_floats(n):
+            if self.average is None or ("param_avg" in st and st["param_avg"].data_ptr() == buf[self._state_floats(n):].data_ptr()):
+                return buf
         if p.is_cuda and torch.cuda.is_current_stream_capturing():
             # a zero fill recorded into a graph would reset exp_avg / exp_avg_sq / step at EVERY replay (and, data-parallel,
             # on this rank only: the replicas would drift apart silently)
             raise _lib.MolKGNNLibraryError(
                 "FusedAdamW: optimiser state would be allocated inside a hipGraph capture -- call prepare_state() (or run "
                 "one eager step in which every parameter has a gradient) before capturing")
-        new = torch.zeros(self._state_floats(n), dtype=torch.float32, device=p.device)
+        new = torch.zeros(self._packed_floats(n), dtype=torch.float32, device=p.device)
         if "exp_avg" in st:                                  # e.g. loaded from a state_dict (ours or torch.optim.AdamW's)
             new[:n] = st["exp_avg"].reshape(-1).to(new)
             new[n:2 * n] = st["exp_avg_sq"].reshape(-1).to(new)
             new[2 * n] = float(st["step"])
-            new[2 * n + 3:] = float(st["step"])              # (the update's per-block copies of the step count)
+            new[2 * n + 3:self._state_floats(n)] = float(st["step"])     # (the update's per-block copies of the step count)
         st["_packed"] = new
         st["exp_avg"] = new[:n].view_as(p)
         st["exp_avg_sq"] = new[n:2 * n].view_as(p)
         st["step"] = new[2 * n:2 * n + 1].view(())
+        if self.average is not None:
+            off = self._state_floats(n)
+            if "param_avg" in st and "n_averaged" in st:     # loaded, or carried over from a buffer that is being replaced
+                new[off:off + n] = st["param_avg"].reshape(-1).to(new)
+                new[off + n:] = float(st["n_averaged"])      # (the canonical count and the update's per-block copies)
+            else:                                            # a fresh average: the parameter itself, nothing averaged yet
+                new[off:off + n] = p.detach().reshape(-1)
+            st["param_avg"] = new[off:off + n].view_as(p)
+            st["n_averaged"] = new[off + n:off + n + 1].view(())
+        else:                                                # (a state saved by an averaging optimiser, loaded into one that is not)
+            st.pop("param_avg", None)
+            st.pop("n_averaged", None)
         self._table_key = None
         self._ver += 1
         return new
@@ -182,8 +230,62 @@ class FusedAdamW(torch.optim.Optimizer):
                 self.state[p].pop("_packed", None)
                 self._packed_state(p)
 
+    # -- the average of the weights --
+    def _require_average(self, who: str) -> None:
+        if self.average is None:
+            raise RuntimeError(f"FusedAdamW.{who}: the optimiser was built without average='ema' | 'mean'")
+
+    def averaged_parameters(self) -> dict:
+        """``{parameter: its average}`` for every parameter that has state, each a view of the optimiser's state shaped like the
+        parameter (``prepare_state()`` gives every parameter state)."""
+        self._require_average("averaged_parameters")
+        return {p: st["param_avg"] for p, st in self.state.items() if "_packed" in st and "param_avg" in st}
+
+    @torch.no_grad()
+    def swap_averaged(self) -> None:
+        """Exchange every parameter that has state with its average, in place, in one launch (``mkgnn_flat_swap``): the model then
+        computes with the averaged weights, and a second call restores it bit for bit.  Capturable.  The parameters' storage does
+        not move, so a captured training step stays valid; stepping while swapped would train the average -- use
+        ``averaged_weights()``, which refuses that."""
+        self._require_average("swap_averaged")
+        pairs = [(p, a) for p, a in self.averaged_parameters().items() if p.numel()]
+        if not pairs:
+            return
+        key = tuple((p.data_ptr(), a.data_ptr(), p.numel()) for p, a in pairs)
+        if key != self._swap_key:
+            dev = pairs[0][0].device
+            for p, _ in pairs:
+                _lib.require_gpu_tensor(p, "parameter")
+                if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
+                    raise _lib.MolKGNNLibraryError("FusedAdamW needs contiguous float32 parameters on one device")
+            table = (_lib.SwapItem * len(key))()
+            for e, (a, b, n) in zip(table, key):
+                e.a, e.b, e.numel = a, b, n
+            self._swap_table, self._swap_key = table, key
+        dev = pairs[0][0].device
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            _lib.check(lib.mkgnn_flat_swap(self._swap_table, len(key), _lib.stream_ptr(dev)), "mkgnn_flat_swap")
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """``with opt.averaged_weights(): ...`` -- the parameters hold their averages inside the block (``swap_averaged()`` on
+        entry) and their live values again after it, also when the block raises.  ``step()`` inside the block raises."""
+        self._require_average("averaged_weights")
+        if self._in_averaged:
+            raise RuntimeError("FusedAdamW.averaged_weights: already inside averaged_weights()")
+        self.swap_averaged()
+        self._in_averaged = True
+        try:
+            yield self
+        finally:
+            self._in_averaged = False
+            self.swap_averaged()
+
     @torch.no_grad()
     def step(self, closure=None):
+        if self._in_averaged:
+            raise RuntimeError("FusedAdamW.step inside averaged_weights(): the parameters hold the averages, a step would train them")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -192,7 +294,7 @@ class FusedAdamW(torch.optim.Optimizer):
         rows: List[tuple] = []
         keep = []                                            # tensors the enqueued kernel reads: referenced until the call returns
         dev = None
-        sig = (self._ver, tuple(len(g["params"]) for g in self.param_groups))
+        sig = (self._ver, tuple(len(g["params"]) for g in self.param_groups), self.average)
         if sig != self._fast_sig:                            # (param_groups, state or flags changed: look everything up again)
             self._fast = [[p, gi, None, p.numel(), None] for gi, group in enumerate(self.param_groups) for p in group["params"] if p.numel()]
             self._fast_sig = sig
@@ -250,17 +352,30 @@ class FusedAdamW(torch.optim.Optimizer):
             e.beta1, e.beta2 = float(group["betas"][0]), float(group["betas"][1])
             e.eps, e.weight_decay, e.maximize = float(group["eps"]), float(group["weight_decay"]), int(bool(group["maximize"]))
             e.grad_scale = float(group.get("grad_scale", 1.0))
+        avg = None
+        if self.average is not None:
+            avg = _lib.AdamWAverage(_lib.ADAMW_AVERAGE_EMA if self.average == "ema" else _lib.ADAMW_AVERAGE_MEAN, self.average_decay,
+                                    int(self.average_warmup), self.average_start)
         with torch.cuda.device(dev):
             if not self.clipping:
-                _lib.check(lib.mkgnn_adamw_step(self._table, len(rows), groups, len(groups), _lib.stream_ptr(dev)),
-                           "mkgnn_adamw_step")
+                if avg is None:
+                    _lib.check(lib.mkgnn_adamw_step(self._table, len(rows), groups, len(groups), _lib.stream_ptr(dev)),
+                               "mkgnn_adamw_step")
+                else:                                        # (+inf, no guard, no stats: the unclipped step, one launch)
+                    _lib.check(lib.mkgnn_adamw_step_averaged(self._table, len(rows), groups, len(groups), avg, math.inf, 0, None, 0,
+                                                             None, _lib.stream_ptr(dev)), "mkgnn_adamw_step_averaged")
             else:
                 if not self._clip_need:                      # (the settings were switched on after the table was built)
                     self._clip_need = int(lib.mkgnn_adamw_clip_workspace_bytes(self._table, len(rows)))
                 ws, stats = self._clip_buffers(dev, self._clip_need)
                 max_norm = math.inf if self.max_grad_norm is None else float(self.max_grad_norm)
-                _lib.check(lib.mkgnn_adamw_step_clipped(self._table, len(rows), groups, len(groups), max_norm,
-                                                        int(self.skip_nonfinite), ws.data_ptr(), ws.numel() * 8, stats.data_ptr(),
-                                                        _lib.stream_ptr(dev)), "mkgnn_adamw_step_clipped")
+                if avg is not None:
+                    _lib.check(lib.mkgnn_adamw_step_averaged(self._table, len(rows), groups, len(groups), avg, max_norm,
+                                                             int(self.skip_nonfinite), ws.data_ptr(), ws.numel() * 8,
+                                                             stats.data_ptr(), _lib.stream_ptr(dev)), "mkgnn_adamw_step_averaged")
+                else:
+                    _lib.check(lib.mkgnn_adamw_step_clipped(self._table, len(rows), groups, len(groups), max_norm,
+                                                            int(self.skip_nonfinite), ws.data_ptr(), ws.numel() * 8, stats.data_ptr(),
+                                                            _lib.stream_ptr(dev)), "mkgnn_adamw_step_clipped")
         del keep
         return loss

@@ -609,12 +609,18 @@ def tune_torch_backends() -> None:
 
 
 def configure_optimizer(model: torch.nn.Module, weight_decay: float = 0.0, lr: float = 1e-3, fused: Optional[bool] = None,
-                        capturable: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                        capturable: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
+                        average: Optional[str] = None, average_decay: float = 0.999, average_warmup: bool = True,
+                        average_start: int = 0):
     """AdamW with the kernel parameters exempt from weight decay, selected by name (model.py:373-382).
 
     ``max_grad_norm`` / ``skip_nonfinite``: clip the gradients by their global norm (Lightning's ``gradient_clip_val`` with
     ``gradient_clip_algorithm='norm'``) and skip a step whose norm is not finite, inside the fused step and on the device
-    (``optim.FusedAdamW``).  The ``torch.optim.AdamW`` route has neither: asking for one there is an error, not ignored."""
+    (``optim.FusedAdamW``).  The ``torch.optim.AdamW`` route has neither: asking for one there is an error, not ignored.
+
+    ``average='ema' | 'mean'`` (with ``average_decay`` / ``average_warmup`` / ``average_start``): an average of the weights kept
+    inside the fused step (``optim.FusedAdamW``); evaluate with it through ``averaged_weights(model, optimizer)``.  The
+    ``torch.optim.AdamW`` route has none: asking for it there is an error (``torch.optim.swa_utils.AveragedModel`` is torch's)."""
     decay, nodecay = [], []
     for name, p in model.named_parameters():
         if ('x_center' in name) or ('p_support' in name) or (
@@ -627,16 +633,55 @@ def configure_optimizer(model: torch.nn.Module, weight_decay: float = 0.0, lr: f
         fused = all(p.is_cuda and p.dtype == torch.float32 for p in model.parameters())
     if fused:
         from .optim import FusedAdamW     # one HIP launch for the whole model; step counters on the device (capturable)
-        opt = FusedAdamW(groups, lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        opt = FusedAdamW(groups, lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, average=average,
+                         average_decay=average_decay, average_warmup=average_warmup, average_start=average_start)
         opt.prepare_state()               # state exists before anything can be captured (a fill inside a graph would replay)
         return opt
     if max_grad_norm is not None or skip_nonfinite:
         raise ValueError("max_grad_norm / skip_nonfinite are part of the fused AdamW step (fused=True); with torch.optim.AdamW call "
                          "torch.nn.utils.clip_grad_norm_ between backward and step")
+    if average is not None:
+        raise ValueError("average is part of the fused AdamW step (fused=True); with torch.optim.AdamW wrap the model in "
+                         "torch.optim.swa_utils.AveragedModel")
     kw = {}
     if capturable:
         kw["capturable"] = True          # step counters live on the device: the step can be replayed from a hipGraph
     return torch.optim.AdamW(groups, lr=lr, **kw)
+
+
+def _averaging(optimizer, who: str):
+    from .optim import FusedAdamW
+    if not isinstance(optimizer, FusedAdamW) or optimizer.average is None:
+        raise ValueError(f"{who}: the optimiser keeps no average (configure_optimizer(..., average='ema' | 'mean'))")
+    return optimizer
+
+
+@contextmanager
+def averaged_weights(model, optimizer):
+    """``with averaged_weights(model, optimizer): evaluate(model, ...)`` -- inside the block ``model``'s parameters hold the
+    averages the optimiser keeps (exchanged in place in one launch, ``FusedAdamW.swap_averaged``), after it the live weights
+    again, also when the block raises; ``optimizer.step()`` inside it raises.  The banks are prepared from the parameters on every
+    forward call, so nothing cached needs invalidating.  Buffers -- the batch-norm running statistics -- are the live model's."""
+    opt = _averaging(optimizer, "averaged_weights")
+    held = opt.averaged_parameters()
+    missing = [n for n, p in model.named_parameters() if p.numel() and p not in held]
+    if missing:
+        raise ValueError(f"averaged_weights: the optimiser holds no average of {missing[:3]} ({len(missing)} parameters)")
+    with opt.averaged_weights():
+        yield model
+
+
+def averaged_state_dict(model, optimizer) -> dict:
+    """``model.state_dict()`` with a copy of the averaged value in place of every parameter the optimiser averages; buffers, and
+    parameters the optimiser does not hold, as they stand."""
+    held = _averaging(optimizer, "averaged_state_dict").averaged_parameters()
+    sd = model.state_dict()
+    prefix_of = {id(p): n for n, p in model.named_parameters()}
+    for p, avg in held.items():
+        name = prefix_of.get(id(p))
+        if name is not None and name in sd:
+            sd[name] = avg.detach().clone()
+    return sd
 
 
 class CapturedSteps:
