@@ -1598,6 +1598,37 @@ int mkgnn_bootstrap_roc(const int32_t* rank, const uint8_t* y_sorted, const uint
                         uint64_t seed, uint64_t offset, double lower, double upper, double* auc, double* logauc, int64_t* two_u,
                         int32_t* n_pos, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Early-recognition functionals of the same replicates (additive; the ABI version stays 8): mkgnn_bootstrap_roc's call with
+ * three more outputs per replicate, formed in the same walk behind the same draw -- the same clear and draw kernels, the same
+ * number of launches, only the walk kernel differs.  molkgnn_amd/evaluation.py::early_reference is the definition.  With the
+ * groups of the replicate as above, P_g the drawn rows in front of group g, sg = gt + gf its rows, tps_g the actives up to and
+ * including it, N = n:
+ *   ap[b]          = sum over the groups with gt > 0 of (gt / (double) T) * (tps_g / (double) (P_g + sg))
+ *                    (sklearn.metrics.average_precision_score with the multiplicities as sample weights; 0 without an active)
+ *   hits[b, j]     = (double) (tps_g - gt) + (double) gt * (double) (cuts[j] - P_g) / (double) sg  for the ONE group with
+ *                    P_g < cuts[j] <= P_g + sg: the expected actives among the first cuts[j] drawn rows when a tie group's rows
+ *                    are in random order.  Bit for bit the definition's
+ *   rie[b, a]      = sum over the groups with gt > 0 of
+ *                    gt * exp(-(alpha (P_g + 1)) / N) * (-expm1(-(alpha sg) / N)) / (-expm1(-alpha / N)) / sg
+ *                    (the sum over the drawn actives of exp(-alpha r / N), a tied active taking the mean over its group's positions)
+ * ap and rie are float64 sums in the log-area's fixed order; they agree with the definition within a relative (m + 16) 2^-53 for m
+ * positive terms plus the device's exp and expm1.  The enrichment factor, BEDROC and average precision follow from them, T and N
+ * on the host (evaluation.early_derived).  The points are taken BEFORE the thinning, which concerns the logAUC alone.
+ *   cuts [J] int32 and alphas [A] float64 are DEVICE arrays (a captured call follows new values written into them);
+ *   0 <= J <= MKGNN_BOOTSTRAP_MAX_CUTS, 0 <= A <= MKGNN_BOOTSTRAP_MAX_ALPHAS; with J == 0 cuts and hits may be null, with A == 0
+ *   alphas and rie.  hits is [B, J] and rie [B, A], row-major.
+ * A cut outside [1, n], and an alpha outside (0, 500] or not finite, is never an address and enters no sum: its column of hits or
+ * rie is NaN and nothing else changes.  auc, logauc, two_u and n_pos are bit for bit mkgnn_bootstrap_roc's for the same arguments,
+ * and a replicate's outputs are a function of (rank, y_sorted, group_last, n, split, seed, offset + b, lower, upper, cuts,
+ * alphas) alone.  The workspace rule is mkgnn_bootstrap_roc_workspace_bytes'.  The limits and refusals are mkgnn_bootstrap_roc's,
+ * with J, A, the five new pointers (8-byte aligned; cuts 4-byte) and the aliasing of ap, hits and rie against everything else. */
+#define MKGNN_BOOTSTRAP_MAX_CUTS   8
+#define MKGNN_BOOTSTRAP_MAX_ALPHAS 4
+int mkgnn_bootstrap_early(const int32_t* rank, const uint8_t* y_sorted, const uint8_t* group_last, int64_t n, int64_t split, int32_t B,
+                          uint64_t seed, uint64_t offset, double lower, double upper, const int32_t* cuts, int32_t J,
+                          const double* alphas, int32_t A, double* auc, double* logauc, int64_t* two_u, int32_t* n_pos, double* ap,
+                          double* hits, double* rie, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

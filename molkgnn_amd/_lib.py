@@ -42,6 +42,8 @@ KNN_MAX_K, KNN_MAX_QUERIES, KNN_MAX_ROWS, KNN_MAX_H = 64, 1 << 20, 1 << 20, 64  
 KNN_WAVES, KNN_TILE, KNN_MIN_PART_TILES, KNN_MAX_PARTS, KNN_TARGET_BLOCKS = 4, 64, 2, 32, 1024
 # MKGNN_BOOTSTRAP_MAX_ROWS, MKGNN_BOOTSTRAP_MAX_REPLICATES, MKGNN_BOOTSTRAP_WORKSPACE_CAP (bytes the wrapper keeps the scratch under)
 BOOTSTRAP_MAX_ROWS, BOOTSTRAP_MAX_REPLICATES, BOOTSTRAP_WORKSPACE_CAP = 1 << 22, 4096, 1 << 30
+# MKGNN_BOOTSTRAP_MAX_CUTS, MKGNN_BOOTSTRAP_MAX_ALPHAS: the enrichment cuts and BEDROC alphas one mkgnn_bootstrap_early takes
+BOOTSTRAP_MAX_CUTS, BOOTSTRAP_MAX_ALPHAS = 8, 4
 # kgnn_bootstrap.hip's tiling (BS_TILE, BS_DRAW_ROWS, BS_LDS_MAX_N): ranks per tile of the walk, rows per block of the draw launch,
 # the most rows whose multiplicities one workgroup keeps in LDS (beyond: the workspace and three launches per pass)
 BOOTSTRAP_TILE, BOOTSTRAP_DRAW_ROWS, BOOTSTRAP_LDS_MAX_N = 1024, 1024, 8192
@@ -295,7 +297,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_embed_neighbours_within", "mkgnn_embed_neighbours_within_workspace_bytes", "mkgnn_graph_components",
            "mkgnn_graph_components_workspace_bytes", "mkgnn_maxmin_pick", "mkgnn_maxmin_pick_workspace_bytes",
            "mkgnn_tail_score_mc", "mkgnn_tail_score_mc_workspace_bytes", "mkgnn_debug_set_bn_merge", "mkgnn_debug_conv_dispatch",
-           "mkgnn_bootstrap_roc", "mkgnn_bootstrap_roc_workspace_bytes")
+           "mkgnn_bootstrap_roc", "mkgnn_bootstrap_roc_workspace_bytes", "mkgnn_bootstrap_early")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -555,6 +557,11 @@ def load() -> C.CDLL:
     lib.mkgnn_bootstrap_roc.restype = C.c_int
     lib.mkgnn_bootstrap_roc.argtypes = [P, P, P, I64, I64, I32, C.c_uint64, C.c_uint64, C.c_double, C.c_double, P, P, P, P, P,
                                         C.c_size_t, P]
+    # the same with the early-recognition sums: (.., lower, upper, cuts, J, alphas, A, auc, logauc, two_u, n_pos, ap, hits, rie,
+    # workspace, bytes, stream)
+    lib.mkgnn_bootstrap_early.restype = C.c_int
+    lib.mkgnn_bootstrap_early.argtypes = [P, P, P, I64, I64, I32, C.c_uint64, C.c_uint64, C.c_double, C.c_double, P, I32, P, I32,
+                                          P, P, P, P, P, P, P, P, C.c_size_t, P]
     lib.mkgnn_kernel_exemplars_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_kernel_exemplars_workspace_bytes.argtypes = [C.POINTER(Int64x4), C.POINTER(Int32x4), I32, I32]
     lib.mkgnn_kernel_exemplars_update.restype = C.c_int

@@ -26,6 +26,10 @@
 // holds, of which form ran, or of the run.  The integers and the AUC do not depend on BS_TILE either; the log-area is summed tile
 // by tile in rank order, each tile's trapezoids by one fixed tree (four per thread in curve order, a butterfly over the wave, the
 // waves in order), so its last bits are a function of BS_TILE, a constant of this file.
+//
+// mkgnn_bootstrap_early is the same call with the early-recognition functionals of the curve -- the raw sums of average precision,
+// of the enrichment factor's hits and of BEDROC's RIE -- taken in the same walk: walk_replicate is ONE text with a compile-time
+// policy, the clear and draw kernels and the launch count are shared, and walk_replicate<RocOnly> is the walk described above.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
@@ -177,15 +181,100 @@ struct WalkLds {
     double dslot[BS_NW];
 };
 
+// ---- the early-recognition functionals of the same curve (mkgnn_bootstrap_early) ----
+// The walk's policy.  RocOnly adds nothing: walk_replicate<RocOnly> is mkgnn_bootstrap_roc's walk.  Early also takes every
+// consecutive pair S_{g-1}, S_g BEFORE the thinning -- the tie group g with P = f + t of S_{g-1} drawn rows in front, gt = dt
+// actives among its sg = dP rows, tps = t of S_g -- and forms from it (evaluation.early_reference is the definition)
+//   ap      += (gt / T) * (tps / (P + sg))                                        (gt > 0)
+//   rie[a]  += gt * exp(-(alpha (P + 1)) / N) * -expm1(-(alpha sg) / N) / -expm1(-alpha / N) / sg          (gt > 0)
+//   hits[j]  = (tps - gt) + gt * (k_j - P) / sg     by the ONE thread whose group holds the cut, P < k_j <= P + sg
+// with N = n.  A cut outside [1, n] and an alpha outside (0, 500] (or not finite) match no group and enter no sum: their
+// entries are NaN.  ap and rie go through the log-area's tree: four per thread in curve order, the butterfly, the waves in order,
+// tile by tile.
+struct RocOnly {
+    static constexpr bool early = false;
+};
+struct Early {
+    static constexpr bool early = true;
+    const int32_t* __restrict__ cuts;    // [J] device
+    const double* __restrict__ alphas;   // [A] device
+    int J, A;
+    double* __restrict__ ap;             // this replicate's: one value, [J], [A]
+    double* __restrict__ hits;
+    double* __restrict__ rie;
+    double (*eslot)[BS_NW];              // LDS: [1 + MKGNN_BOOTSTRAP_MAX_ALPHAS][BS_NW]
+};
+constexpr int BS_MAX_CUTS = MKGNN_BOOTSTRAP_MAX_CUTS, BS_MAX_ALPHAS = MKGNN_BOOTSTRAP_MAX_ALPHAS;
+
+// what a thread knows of the call's cuts and alphas (the same values in every thread)
+struct EarlyConsts {
+    int cut[BS_MAX_CUTS];                // 0: no cut (matches no group)
+    double alpha[BS_MAX_ALPHAS];         // 0: no alpha
+    double den[BS_MAX_ALPHAS];           // -expm1(-alpha / N)
+    double dN;
+};
+__device__ __forceinline__ void early_consts(const Early& P, int n, EarlyConsts& K) {
+    K.dN = (double)n;
+#pragma unroll
+    for (int j = 0; j < BS_MAX_CUTS; ++j) {
+        const int k = j < P.J ? P.cuts[j] : 0;
+        K.cut[j] = k >= 1 && k <= n ? k : 0;
+    }
+#pragma unroll
+    for (int a = 0; a < BS_MAX_ALPHAS; ++a) {
+        const double al = a < P.A ? P.alphas[a] : 0.0;
+        K.alpha[a] = al > 0.0 && al <= 500.0 ? al : 0.0;          // (a NaN fails both)
+        K.den[a] = -expm1(-K.alpha[a] / K.dN);
+    }
+}
+// the group that leads from a to b: its terms of ap and rie into acc[0], acc[1 + a]; its cuts' hits to memory
+__device__ __forceinline__ void early_segment(const Early& P, const EarlyConsts& K, Pt a, Pt b, double dT,
+                                              double (&acc)[1 + BS_MAX_ALPHAS]) {
+    const int before = a.f + a.t, sg = b.f + b.t - before, gt = b.t - a.t;
+#pragma unroll
+    for (int j = 0; j < BS_MAX_CUTS; ++j) {
+        const int k = K.cut[j];
+        if (k > before && k <= before + sg)
+            P.hits[j] = (double)a.t + (double)gt * (double)(k - before) / (double)sg;
+    }
+    if (gt > 0) {
+        acc[0] += ((double)gt / dT) * ((double)b.t / (double)(before + sg));
+#pragma unroll
+        for (int q = 0; q < BS_MAX_ALPHAS; ++q) {
+            const double al = K.alpha[q];
+            if (al > 0.0)
+                acc[1 + q] += (double)gt * exp(-(al * (double)(before + 1)) / K.dN) * (-expm1(-(al * (double)sg) / K.dN)) / K.den[q] /
+                              (double)sg;
+        }
+    }
+}
+// the wave's butterfly of the 1 + A sums, in block_sum's order; lane 0 leaves them in eslot (read after block_sum's barriers)
+__device__ __forceinline__ void early_wave_sums(const Early& P, const double (&acc)[1 + BS_MAX_ALPHAS]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 1 + BS_MAX_ALPHAS; ++q) {
+        if (q <= P.A) {                  // (uniform: the whole wave takes the butterfly or none of it does)
+            double d = acc[q];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) d += __longlong_as_double((long long)shfl_xor64((uint64_t)__double_as_longlong(d), o));
+            if (lane == 0) P.eslot[q][w] = d;
+        }
+    }
+}
+
 // One workgroup walks one replicate: cnt[r] its multiplicities (global memory or LDS), T its drawn actives.  Thread 0 writes the
-// four outputs.
+// four outputs (and, under the Early policy, ap, rie and the NaN entries).
+template <class Policy>
 __device__ __forceinline__ void walk_replicate(const uint32_t* __restrict__ cnt, const uint8_t* __restrict__ ys,
                                                const uint8_t* __restrict__ glast, int n, int T, double lower, double upper,
                                                WalkLds& L, double* __restrict__ auc, double* __restrict__ logauc,
-                                               int64_t* __restrict__ two_u, int32_t* __restrict__ n_pos) {
+                                               int64_t* __restrict__ two_u, int32_t* __restrict__ n_pos, const Policy& policy) {
     const int t = threadIdx.x;
     const int F = n - T;
     const double dT = (double)T, dF = (double)F;
+    EarlyConsts K;
+    double early_sum[1 + BS_MAX_ALPHAS] = {};        // ap, rie[a] so far (every thread carries the same values)
+    if constexpr (Policy::early) early_consts(policy, n, K);
     if (t < 2) L.pts[t] = Pt{0, 0};
     if (t == 0) L.kept[0] = Pt{0, 0};
     uint64_t cum = 0;                    // the running sums before this tile: drawn rows in the low word, drawn actives in the high
@@ -256,6 +345,7 @@ __device__ __forceinline__ void walk_replicate(const uint32_t* __restrict__ cnt,
         bool keep[BS_PER];
         uint64_t n_keep = 0;
         int64_t term = 0;
+        double e4[1 + BS_MAX_ALPHAS] = {};
 #pragma unroll
         for (int k = 0; k < BS_PER; ++k) {
             const int i = 2 + t * BS_PER + k, g = emitted + i - 2;
@@ -263,6 +353,7 @@ __device__ __forceinline__ void walk_replicate(const uint32_t* __restrict__ cnt,
             if (i < 2 + found && g >= 2) {
                 const Pt a = L.pts[i - 2], b = L.pts[i - 1], cpt = L.pts[i];
                 term += two_u_term(a, b);
+                if constexpr (Policy::early) early_segment(policy, K, a, b, dT, e4);
                 keep[k] = g == 2 || step_differs(a, b, cpt);
                 keep_pt[k] = b;
             }
@@ -282,7 +373,19 @@ __device__ __forceinline__ void walk_replicate(const uint32_t* __restrict__ cnt,
             if (j <= n_kept) a4 += log_trapezoid(L.kept[j - 1], L.kept[j], dT, dF, lower, upper);
         }
         const Pt tail0 = L.pts[found], tail1 = L.pts[found + 1], last_kept = L.kept[n_kept];
+        if constexpr (Policy::early) early_wave_sums(policy, e4);   // (eslot was last read before the previous tile's closing barrier)
         block_sum(term, a4, L.slot, L.dslot);        // (its first barrier: every read of pts and kept above is done)
+        if constexpr (Policy::early) {
+#pragma unroll
+            for (int q = 0; q < 1 + BS_MAX_ALPHAS; ++q) {
+                if (q <= policy.A) {
+                    double dt = 0.0;
+#pragma unroll
+                    for (int u = 0; u < BS_NW; ++u) dt += policy.eslot[q][u];
+                    early_sum[q] += dt;
+                }
+            }
+        }
         if (t == 0) {
             L.pts[0] = tail0;
             L.pts[1] = tail1;
@@ -310,6 +413,17 @@ __device__ __forceinline__ void walk_replicate(const uint32_t* __restrict__ cnt,
         area += log_trapezoid(k, end, dT, dF, lower, upper);
         const bool defined = T > 0 && F > 0;
         const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        if constexpr (Policy::early) {
+            if (emitted >= 2) early_segment(policy, K, a, b, dT, early_sum);
+            early_segment(policy, K, b, end, dT, early_sum);
+            *policy.ap = early_sum[0];
+#pragma unroll
+            for (int q = 0; q < BS_MAX_ALPHAS; ++q)
+                if (q < policy.A) policy.rie[q] = K.alpha[q] > 0.0 ? early_sum[1 + q] : nan;
+#pragma unroll
+            for (int j = 0; j < BS_MAX_CUTS; ++j)
+                if (j < policy.J && K.cut[j] == 0) policy.hits[j] = nan;
+        }
         *auc = defined ? (double)u2 / (double)(2ll * (int64_t)T * (int64_t)F) : nan;
         *logauc = defined ? area / (log10(upper) - log10(lower)) : nan;
         *two_u = u2;
@@ -324,13 +438,9 @@ __device__ __forceinline__ int block_count(int v, unsigned long long* slot) {
     return (int)total;
 }
 
-__global__ void __launch_bounds__(BS_THREADS) bootstrap_lds_kernel(const int32_t* __restrict__ rank, const uint8_t* __restrict__ ys,
-                                                                   const uint8_t* __restrict__ glast, int n, int split, uint64_t seed,
-                                                                   uint64_t offset, double lower, double upper,
-                                                                   double* __restrict__ auc, double* __restrict__ logauc,
-                                                                   int64_t* __restrict__ two_u, int32_t* __restrict__ n_pos) {
-    __shared__ __attribute__((aligned(16))) uint32_t cnt[BS_LDS_MAX_N];
-    __shared__ WalkLds L;
+// the LDS form's draw: replicate (seed, offset + b)'s multiplicities into cnt (LDS); returns its drawn actives, in every thread
+__device__ __forceinline__ int draw_into_lds(const int32_t* __restrict__ rank, const uint8_t* __restrict__ ys, int n, int split,
+                                             uint64_t seed, uint64_t offset, uint32_t* cnt, unsigned long long* slot) {
     const int t = threadIdx.x, b = blockIdx.x;
     for (int r = t; r < n; r += BS_THREADS) cnt[r] = 0u;
     __syncthreads();
@@ -350,9 +460,41 @@ __global__ void __launch_bounds__(BS_THREADS) bootstrap_lds_kernel(const int32_t
             }
         }
     }
-    const int T = block_count(actives, L.slot);      // (its barriers: every add to cnt is done before the walk reads)
+    const int T = block_count(actives, slot);        // (its barriers: every add to cnt is done before the walk reads)
     __syncthreads();
-    walk_replicate(cnt, ys, glast, n, T, lower, upper, L, auc + b, logauc + b, two_u + b, n_pos + b);
+    return T;
+}
+
+__global__ void __launch_bounds__(BS_THREADS) bootstrap_lds_kernel(const int32_t* __restrict__ rank, const uint8_t* __restrict__ ys,
+                                                                   const uint8_t* __restrict__ glast, int n, int split, uint64_t seed,
+                                                                   uint64_t offset, double lower, double upper,
+                                                                   double* __restrict__ auc, double* __restrict__ logauc,
+                                                                   int64_t* __restrict__ two_u, int32_t* __restrict__ n_pos) {
+    __shared__ __attribute__((aligned(16))) uint32_t cnt[BS_LDS_MAX_N];
+    __shared__ WalkLds L;
+    const int b = blockIdx.x;
+    const int T = draw_into_lds(rank, ys, n, split, seed, offset, cnt, L.slot);
+    walk_replicate(cnt, ys, glast, n, T, lower, upper, L, auc + b, logauc + b, two_u + b, n_pos + b, RocOnly{});
+}
+
+// the replicate's Early policy: block b's rows of the three outputs
+__device__ __forceinline__ Early early_of(const int32_t* cuts, int J, const double* alphas, int A, double* ap, double* hits,
+                                          double* rie, double (*eslot)[BS_NW], int b) {
+    return Early{cuts, alphas, J, A, ap + b, hits + (size_t)b * (size_t)J, rie + (size_t)b * (size_t)A, eslot};
+}
+
+__global__ void __launch_bounds__(BS_THREADS) bootstrap_lds_early_kernel(
+    const int32_t* __restrict__ rank, const uint8_t* __restrict__ ys, const uint8_t* __restrict__ glast, int n, int split, uint64_t seed,
+    uint64_t offset, double lower, double upper, const int32_t* __restrict__ cuts, int J, const double* __restrict__ alphas, int A,
+    double* __restrict__ auc, double* __restrict__ logauc, int64_t* __restrict__ two_u, int32_t* __restrict__ n_pos,
+    double* __restrict__ ap, double* __restrict__ hits, double* __restrict__ rie) {
+    __shared__ __attribute__((aligned(16))) uint32_t cnt[BS_LDS_MAX_N];
+    __shared__ WalkLds L;
+    __shared__ double eslot[1 + BS_MAX_ALPHAS][BS_NW];
+    const int b = blockIdx.x;
+    const int T = draw_into_lds(rank, ys, n, split, seed, offset, cnt, L.slot);
+    walk_replicate(cnt, ys, glast, n, T, lower, upper, L, auc + b, logauc + b, two_u + b, n_pos + b,
+                   early_of(cuts, J, alphas, A, ap, hits, rie, eslot, b));
 }
 
 // the pass's multiplicities (words16 chunks of four words) and drawn actives start at zero.  (A launch: a hipMemsetAsync of a few
@@ -401,7 +543,21 @@ __global__ void __launch_bounds__(BS_THREADS) bootstrap_walk_kernel(const uint32
     const int b = blockIdx.x;
     const int T = min(max(__builtin_amdgcn_readfirstlane(n_pos[b]), 0), n);
     __syncthreads();                                 // (every thread has read n_pos[b] before thread 0 writes it back)
-    walk_replicate(cnt + (size_t)b * pitch, ys, glast, n, T, lower, upper, L, auc + b, logauc + b, two_u + b, n_pos + b);
+    walk_replicate(cnt + (size_t)b * pitch, ys, glast, n, T, lower, upper, L, auc + b, logauc + b, two_u + b, n_pos + b, RocOnly{});
+}
+
+__global__ void __launch_bounds__(BS_THREADS) bootstrap_walk_early_kernel(
+    const uint32_t* __restrict__ cnt, size_t pitch, const uint8_t* __restrict__ ys, const uint8_t* __restrict__ glast, int n,
+    double lower, double upper, const int32_t* __restrict__ cuts, int J, const double* __restrict__ alphas, int A,
+    double* __restrict__ auc, double* __restrict__ logauc, int64_t* __restrict__ two_u, int32_t* __restrict__ n_pos,
+    double* __restrict__ ap, double* __restrict__ hits, double* __restrict__ rie) {
+    __shared__ WalkLds L;
+    __shared__ double eslot[1 + BS_MAX_ALPHAS][BS_NW];
+    const int b = blockIdx.x;
+    const int T = min(max(__builtin_amdgcn_readfirstlane(n_pos[b]), 0), n);
+    __syncthreads();                                 // (every thread has read n_pos[b] before thread 0 writes it back)
+    walk_replicate(cnt + (size_t)b * pitch, ys, glast, n, T, lower, upper, L, auc + b, logauc + b, two_u + b, n_pos + b,
+                   early_of(cuts, J, alphas, A, ap, hits, rie, eslot, b));
 }
 
 inline size_t bs_pitch(int64_t n) { return (size_t)((n + 3) / 4 * 4); }      // words of one replicate's multiplicities
@@ -418,11 +574,20 @@ extern "C" size_t mkgnn_bootstrap_roc_workspace_bytes(int64_t n, int32_t replica
     return sizeof(uint32_t) * bs_pitch(n) * (size_t)replicates_per_pass;
 }
 
-extern "C" int mkgnn_bootstrap_roc(const int32_t* rank, const uint8_t* y_sorted, const uint8_t* group_last, int64_t n, int64_t split,
-                                   int32_t B, uint64_t seed, uint64_t offset, double lower, double upper, double* auc,
-                                   double* logauc, int64_t* two_u, int32_t* n_pos, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
-    const char* who = "mkgnn_bootstrap_roc";
+namespace {
+// mkgnn_bootstrap_early's additions to mkgnn_bootstrap_roc's arguments; null for the ROC-only call
+struct EarlyCall {
+    const int32_t* cuts;
+    int32_t J;
+    const double* alphas;
+    int32_t A;
+    double *ap, *hits, *rie;
+};
+
+// Both entries: every check, then the launches.  Only the walk differs between them.
+int bootstrap_run(const char* who, const EarlyCall* e, const int32_t* rank, const uint8_t* y_sorted, const uint8_t* group_last, int64_t n,
+                  int64_t split, int32_t B, uint64_t seed, uint64_t offset, double lower, double upper, double* auc, double* logauc,
+                  int64_t* two_u, int32_t* n_pos, void* workspace, size_t workspace_bytes, void* stream) {
     static_assert(MKGNN_BOOTSTRAP_MAX_REPLICATES <= 65535, "the draw launch puts a pass's replicates on the grid's y axis");
     if (n < 1 || n > MKGNN_BOOTSTRAP_MAX_ROWS)
         return api_fail("%s: %lld rows outside [1, %d]", who, (long long)n, MKGNN_BOOTSTRAP_MAX_ROWS);
@@ -434,6 +599,16 @@ extern "C" int mkgnn_bootstrap_roc(const int32_t* rank, const uint8_t* y_sorted,
     if (!rank || !y_sorted || !group_last || !auc || !logauc || !two_u || !n_pos) return api_fail("%s: null pointer", who);
     if ((((uintptr_t)auc | (uintptr_t)logauc | (uintptr_t)two_u) & 7) != 0 || ((uintptr_t)n_pos & 3) != 0 || ((uintptr_t)rank & 3) != 0)
         return api_fail("%s: misaligned rank or output", who);
+    if (e) {
+        if (e->J < 0 || e->J > MKGNN_BOOTSTRAP_MAX_CUTS)
+            return api_fail("%s: %d cuts outside [0, %d]", who, (int)e->J, MKGNN_BOOTSTRAP_MAX_CUTS);
+        if (e->A < 0 || e->A > MKGNN_BOOTSTRAP_MAX_ALPHAS)
+            return api_fail("%s: %d alphas outside [0, %d]", who, (int)e->A, MKGNN_BOOTSTRAP_MAX_ALPHAS);
+        if (!e->ap || (e->J > 0 && (!e->cuts || !e->hits)) || (e->A > 0 && (!e->alphas || !e->rie)))
+            return api_fail("%s: null pointer (cuts, alphas, ap, hits or rie)", who);
+        if ((((uintptr_t)e->ap | (uintptr_t)e->hits | (uintptr_t)e->rie | (uintptr_t)e->alphas) & 7) != 0 || ((uintptr_t)e->cuts & 3) != 0)
+            return api_fail("%s: misaligned cuts, alphas, ap, hits or rie", who);
+    }
     const bool lds = n <= BS_LDS_MAX_N;
     const size_t pitch = bs_pitch(n), per = sizeof(uint32_t) * pitch;
     int per_pass = B;
@@ -445,16 +620,29 @@ extern "C" int mkgnn_bootstrap_roc(const int32_t* rank, const uint8_t* y_sorted,
         if (fit < (size_t)B) per_pass = (int)fit;
     }
     const size_t used = lds ? 0 : per * (size_t)per_pass;
-    const Span rd[3] = {{rank, (size_t)n * 4}, {y_sorted, (size_t)n}, {group_last, (size_t)n}};
-    const Span wr[5] = {{auc, (size_t)B * 8}, {logauc, (size_t)B * 8}, {two_u, (size_t)B * 8}, {n_pos, (size_t)B * 4}, {workspace, used}};
-    if (spans_disjoint(who, wr, 5, rd, 3, "an output (auc, logauc, two_u, n_pos) or the workspace aliases rank, y_sorted or group_last",
-                       "the outputs (auc, logauc, two_u, n_pos) and the workspace alias each other"))
+    const size_t J = e ? (size_t)e->J : 0, A = e ? (size_t)e->A : 0;
+    const Span rd[5] = {{rank, (size_t)n * 4}, {y_sorted, (size_t)n}, {group_last, (size_t)n}, {e ? e->cuts : nullptr, J * 4},
+                        {e ? e->alphas : nullptr, A * 8}};
+    const Span wr[8] = {{auc, (size_t)B * 8}, {logauc, (size_t)B * 8}, {two_u, (size_t)B * 8}, {n_pos, (size_t)B * 4}, {workspace, used},
+                        {e ? e->ap : nullptr, e ? (size_t)B * 8 : 0}, {e ? e->hits : nullptr, (size_t)B * J * 8},
+                        {e ? e->rie : nullptr, (size_t)B * A * 8}};
+    if (e ? spans_disjoint(who, wr, 8, rd, 5,
+                           "an output (auc, logauc, two_u, n_pos, ap, hits, rie) or the workspace aliases rank, y_sorted, group_last, "
+                           "cuts or alphas",
+                           "the outputs (auc, logauc, two_u, n_pos, ap, hits, rie) and the workspace alias each other")
+          : spans_disjoint(who, wr, 5, rd, 3, "an output (auc, logauc, two_u, n_pos) or the workspace aliases rank, y_sorted or group_last",
+                           "the outputs (auc, logauc, two_u, n_pos) and the workspace alias each other"))
         return 1;
     const hipStream_t st = (hipStream_t)stream;
     const int ni = (int)n, sp = (int)split;
     if (lds) {
-        bootstrap_lds_kernel<<<(unsigned)B, BS_THREADS, 0, st>>>(rank, y_sorted, group_last, ni, sp, seed, offset, lower, upper, auc,
-                                                                 logauc, two_u, n_pos);
+        if (e)
+            bootstrap_lds_early_kernel<<<(unsigned)B, BS_THREADS, 0, st>>>(rank, y_sorted, group_last, ni, sp, seed, offset, lower, upper,
+                                                                           e->cuts, e->J, e->alphas, e->A, auc, logauc, two_u, n_pos,
+                                                                           e->ap, e->hits, e->rie);
+        else
+            bootstrap_lds_kernel<<<(unsigned)B, BS_THREADS, 0, st>>>(rank, y_sorted, group_last, ni, sp, seed, offset, lower, upper, auc,
+                                                                     logauc, two_u, n_pos);
     } else {
         uint32_t* const cnt = (uint32_t*)workspace;
         const unsigned row_blocks = (unsigned)((n + BS_DRAW_ROWS - 1) / BS_DRAW_ROWS);
@@ -465,10 +653,34 @@ extern "C" int mkgnn_bootstrap_roc(const int32_t* rank, const uint8_t* y_sorted,
                                                                                                                n_pos + b0, nb);
             bootstrap_draw_kernel<<<dim3(row_blocks, (unsigned)nb), BS_THREADS, 0, st>>>(rank, y_sorted, ni, sp, pitch, seed,
                                                                                          offset + (uint64_t)b0, cnt, n_pos + b0);
-            bootstrap_walk_kernel<<<(unsigned)nb, BS_THREADS, 0, st>>>(cnt, pitch, y_sorted, group_last, ni, lower, upper, auc + b0,
-                                                                       logauc + b0, two_u + b0, n_pos + b0);
+            if (e)
+                bootstrap_walk_early_kernel<<<(unsigned)nb, BS_THREADS, 0, st>>>(
+                    cnt, pitch, y_sorted, group_last, ni, lower, upper, e->cuts, e->J, e->alphas, e->A, auc + b0, logauc + b0, two_u + b0,
+                    n_pos + b0, e->ap + b0, e->hits + (size_t)b0 * J, e->rie + (size_t)b0 * A);
+            else
+                bootstrap_walk_kernel<<<(unsigned)nb, BS_THREADS, 0, st>>>(cnt, pitch, y_sorted, group_last, ni, lower, upper, auc + b0,
+                                                                           logauc + b0, two_u + b0, n_pos + b0);
         }
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? 0 : api_hip_fail(who, err);
+}
+}  // namespace
+
+extern "C" int mkgnn_bootstrap_roc(const int32_t* rank, const uint8_t* y_sorted, const uint8_t* group_last, int64_t n, int64_t split,
+                                   int32_t B, uint64_t seed, uint64_t offset, double lower, double upper, double* auc,
+                                   double* logauc, int64_t* two_u, int32_t* n_pos, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    return bootstrap_run("mkgnn_bootstrap_roc", nullptr, rank, y_sorted, group_last, n, split, B, seed, offset, lower, upper, auc, logauc,
+                         two_u, n_pos, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mkgnn_bootstrap_early(const int32_t* rank, const uint8_t* y_sorted, const uint8_t* group_last, int64_t n, int64_t split,
+                                     int32_t B, uint64_t seed, uint64_t offset, double lower, double upper, const int32_t* cuts,
+                                     int32_t J, const double* alphas, int32_t A, double* auc, double* logauc, int64_t* two_u,
+                                     int32_t* n_pos, double* ap, double* hits, double* rie, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    const EarlyCall e = {cuts, J, alphas, A, ap, hits, rie};
+    return bootstrap_run("mkgnn_bootstrap_early", &e, rank, y_sorted, group_last, n, split, B, seed, offset, lower, upper, auc, logauc,
+                         two_u, n_pos, workspace, workspace_bytes, stream);
 }

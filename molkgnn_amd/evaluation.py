@@ -263,13 +263,21 @@ def bootstrap_reference(true_y, predicted_score, n_boot: int, FPR_range=(0.001, 
     ``np.interp``'s formula), ``(log10(b) - log10(a)) * (ya + yb) / 2`` summed and divided by the window's width.  With ``T == 0`` or
     ``F == 0`` both metrics of the replicate are NaN (not the reference's ``-1``: a replicate is not a caller) and it counts in
     ``n_undefined``."""
-    import numpy as np
     lower, upper = _check_fpr_range(FPR_range)
+    rank, y_sorted, group_last, split = _reference_sorted_inputs(true_y, predicted_score, n_boot, seed, offset, stratified)
+    return bootstrap_reference_sorted(rank, y_sorted, group_last, split, int(n_boot), int(seed), int(offset), lower, upper)
+
+
+def _reference_sorted_inputs(true_y, predicted_score, n_boot, seed, offset, stratified: bool):
+    """``(rank, y_sorted, group_last, split)`` of ``bootstrap_reference`` and ``early_reference`` in numpy: the rows in
+    ``bootstrap_order``, ranked by score descending (stable), tie groups the runs of equal score; sizes and non-finite scores are
+    refused here."""
+    import numpy as np
     y_t, s_t = _as_vectors(true_y, predicted_score)
     y = y_t.detach().cpu().numpy() == 1.0
     s = s_t.detach().cpu().numpy()
-    n, B, seed, offset = s.size, int(n_boot), int(seed), int(offset)
-    _check_bootstrap_sizes(n, B, seed, offset)
+    n = s.size
+    _check_bootstrap_sizes(n, int(n_boot), int(seed), int(offset))
     if not np.isfinite(s).all():
         raise ValueError("predicted_score holds a NaN or an infinite value")
     perm, split = bootstrap_order(y, stratified)
@@ -279,7 +287,7 @@ def bootstrap_reference(true_y, predicted_score, n_boot: int, FPR_range=(0.001, 
     rank[order] = np.arange(n)
     ss = s[order]
     group_last = np.concatenate([ss[1:] != ss[:-1], [True]])
-    return bootstrap_reference_sorted(rank, y[order], group_last, split, B, seed, offset, lower, upper)
+    return rank, y[order], group_last, split
 
 
 def bootstrap_reference_sorted(rank, y_sorted, group_last, split: int, n_boot: int, seed: int, offset: int, lower: float,
@@ -306,9 +314,268 @@ def bootstrap_reference_sorted(rank, y_sorted, group_last, split: int, n_boot: i
     return out
 
 
-def _bootstrap_replicates(true_y, predicted_score, n_boot: int, FPR_range, seed: int, offset: int, stratified: bool):
+# ---- early recognition: average precision, enrichment factor, BEDROC ----
+# Three functionals of the curve the bootstrap already walks.  Per replicate the raw sums ap, hits[j] and rie[a] are formed from the
+# tie groups (early_reference is the definition; mkgnn_bootstrap_early forms them in the ROC walk); early_derived turns them, the
+# actives T and the rows N into the metrics on either route.
+
+BOOTSTRAP_MAX_CUTS, BOOTSTRAP_MAX_ALPHAS = 8, 4  # (MKGNN_BOOTSTRAP_MAX_CUTS, MKGNN_BOOTSTRAP_MAX_ALPHAS)
+EARLY_MAX_ALPHA = 500.0                          # (exp(alpha) and sinh(alpha / 2) stay finite in float64)
+
+
+def early_cut(fraction: float, n: int) -> int:
+    """The number of top-ranked rows an enrichment factor at ``fraction`` looks at: ``max(1, min(n, ceil(fraction * n)))``."""
+    return max(1, min(int(n), math.ceil(_check_fraction(fraction) * int(n))))
+
+
+def _check_fraction(fraction: float) -> float:
+    fraction = float(fraction)
+    if not 0.0 < fraction <= 1.0:
+        raise ValueError(f"enrichment fraction {fraction} outside (0, 1]")
+    return fraction
+
+
+def _check_alpha(alpha: float) -> float:
+    alpha = float(alpha)
+    if not 0.0 < alpha <= EARLY_MAX_ALPHA:
+        raise ValueError(f"BEDROC alpha {alpha} outside (0, {EARLY_MAX_ALPHA:g}]")
+    return alpha
+
+
+def _replicate_early(c, y, gid, n_groups: int, cuts, alphas):
+    """One replicate from its multiplicities ``c`` over the ranks: ``(ap, hits [J], rie [A], T)``."""
+    import numpy as np
+    n = c.size
+    gt = np.bincount(gid, weights=c * y, minlength=n_groups).astype(np.int64)
+    gf = np.bincount(gid, weights=c * (1 - y), minlength=n_groups).astype(np.int64)
+    exists = (gt + gf) > 0
+    gt, sg = gt[exists], (gt + gf)[exists]
+    end, tps = np.cumsum(sg), np.cumsum(gt)
+    before = end - sg
+    T, N = int(tps[-1]), int(end[-1])
+    pos = gt > 0
+    ap = float(np.sum((gt[pos] / np.float64(T)) * (tps[pos] / end[pos].astype(np.float64)))) if T > 0 else 0.0
+    hits = np.full(len(cuts), np.nan)
+    for j, k in enumerate(cuts):
+        k = int(k)
+        if not 1 <= k <= n:
+            continue
+        if k > N:
+            hits[j] = np.float64(T)
+            continue
+        g = int(np.searchsorted(end, k, side="left"))             # (before[g] < k <= end[g])
+        hits[j] = np.float64(tps[g] - gt[g]) + np.float64(gt[g]) * np.float64(k - before[g]) / np.float64(sg[g])
+    rie = np.full(len(alphas), np.nan)
+    for a, alpha in enumerate(alphas):
+        alpha = float(alpha)
+        if not 0.0 < alpha <= EARLY_MAX_ALPHA:                    # (a NaN fails both)
+            continue
+        den = -np.expm1(-alpha / N)
+        rie[a] = float(np.sum(gt[pos] * np.exp(-(alpha * (before[pos] + 1)) / N) * (-np.expm1(-(alpha * sg[pos]) / N)) / den / sg[pos]))
+    return ap, hits, rie, T
+
+
+def early_reference_sorted(rank, y_sorted, group_last, split: int, n_boot: int, seed: int, offset: int, cuts, alphas) -> dict:
+    """The definition of the early-recognition sums behind the sort -- the host form of ``readout.bootstrap_early`` /
+    ``mkgnn_bootstrap_early``, with ``bootstrap_reference_sorted``'s arguments, draw, order and tie groups: ``{'ap': float64 [B], 'hits':
+    float64 [B, J], 'rie': float64 [B, A], 'n_pos': int32 [B], 'n_undefined': int}``.
+
+    Per replicate, ``c`` the multiplicities over the ranks and the groups the tie groups with a drawn row: group ``g`` has ``gt`` drawn
+    actives, ``gf`` drawn inactives, ``sg = gt + gf`` rows, ``P_g`` drawn rows in front of it and ``tps_g`` actives up to and including
+    it; ``T`` and ``F`` are the totals and ``N = T + F``.  In exactly this order of operations:
+
+    ``ap = sum_{g: gt > 0} (gt / float64(T)) * (tps_g / float64(P_g + sg))`` -- ``sklearn.metrics.average_precision_score`` with the
+    multiplicities as sample weights (a group without a drawn active adds an exact zero; without any active the sum is empty, 0).
+
+    ``hits[j]`` for a cut ``1 <= k_j <= n``: the expected number of actives among the first ``k_j`` drawn rows when a tie group's rows
+    are in random order -- ``float64(tps_g - gt) + float64(gt) * float64(k_j - P_g) / float64(sg)`` for the one group with ``P_g < k_j
+    <= P_g + sg``, and ``float64(T)`` for ``k_j > N``.
+
+    ``rie[a] = sum_{g: gt > 0} gt * exp(-(alpha * (P_g + 1)) / N) * (-expm1(-(alpha * sg) / N)) / (-expm1(-alpha / N)) / sg`` -- the
+    sum over the drawn actives of ``exp(-alpha r / N)``, a tied active taking the mean over its group's positions (a geometric sum;
+    the ``expm1`` form keeps the digits a difference of two ``exp`` would lose for a group of one).
+
+    A cut outside ``[1, n]``, and an alpha outside ``(0, 500]`` or not finite, gives NaN in its column.  ``n_undefined`` counts the
+    replicates with ``T == 0`` or ``F == 0``, whose derived metrics (``early_derived``) are NaN."""
+    import numpy as np
+    rank = np.asarray(rank).astype(np.int64)
+    ys = (np.asarray(y_sorted) != 0).astype(np.int64)
+    last = np.asarray(group_last) != 0
+    n, split, B = rank.size, int(split), int(n_boot)
+    _check_bootstrap_sizes(n, B, int(seed), int(offset))
+    if not 0 <= split <= n:
+        raise ValueError(f"split = {split} outside [0, {n}]")
+    cuts, alphas = [int(k) for k in cuts], [float(a) for a in alphas]
+    if len(cuts) > BOOTSTRAP_MAX_CUTS or len(alphas) > BOOTSTRAP_MAX_ALPHAS:
+        raise ValueError(f"at most {BOOTSTRAP_MAX_CUTS} cuts and {BOOTSTRAP_MAX_ALPHAS} alphas")
+    gid = np.concatenate([[0], np.cumsum(last[:-1])]).astype(np.int64)
+    n_groups = int(gid[-1]) + 1
+    out = {"ap": np.empty(B), "hits": np.empty((B, len(cuts))), "rie": np.empty((B, len(alphas))), "n_pos": np.empty(B, dtype=np.int32)}
+    for b in range(B):
+        c = np.bincount(rank[bootstrap_draw(n, split, int(seed), int(offset) + b)], minlength=n).astype(np.int64)
+        out["ap"][b], out["hits"][b], out["rie"][b], out["n_pos"][b] = _replicate_early(c, ys, gid, n_groups, cuts, alphas)
+    out["n_undefined"] = int(((out["n_pos"] == 0) | (out["n_pos"] == n)).sum())
+    return out
+
+
+def early_reference(true_y, predicted_score, n_boot: int, cuts, alphas, seed: int = 0, offset: int = 0,
+                    stratified: bool = False) -> dict:
+    """``early_reference_sorted`` of labels and scores, prepared as ``bootstrap_reference`` prepares them (the same resamples, order,
+    tie groups and refusal of non-finite scores)."""
+    rank, y_sorted, group_last, split = _reference_sorted_inputs(true_y, predicted_score, n_boot, seed, offset, stratified)
+    return early_reference_sorted(rank, y_sorted, group_last, split, int(n_boot), int(seed), int(offset), cuts, alphas)
+
+
+def early_derived(ap, hits, rie, n_pos, n: int, cuts, alphas) -> dict:
+    """The metrics from the raw sums, on either route (float64 tensors on the sums' device): ``{'AP': [B], 'EF': [B, J], 'BEDROC': [B,
+    A]}`` from ``ap [B]``, ``hits [B, J]``, ``rie [B, A]``, the actives ``n_pos [B]``, the rows ``n`` and the host values ``cuts`` and
+    ``alphas``.  ``AP = ap``; ``EF = (hits / k) / (T / N)``; BEDROC by Truchon & Bayly (2007), eq. 36, as RDKit's ``CalcBEDROC``
+    evaluates it: ``Ra = T / N``, ``RIE = rie / T / ((1 / N) * (1 - exp(-alpha)) / (exp(alpha / N) - 1))``, ``BEDROC = RIE * Ra * sinh(alpha
+    / 2) / (cosh(alpha / 2) - cosh(alpha / 2 - alpha * Ra)) + 1 / (1 - exp(alpha * (1 - Ra)))``.  All three are NaN where ``T == 0`` or
+    ``T == N``."""
+    ap = torch.as_tensor(ap, dtype=torch.float64)
+    dev = ap.device
+    hits = torch.as_tensor(hits, dtype=torch.float64, device=dev).reshape(ap.numel(), -1)
+    rie = torch.as_tensor(rie, dtype=torch.float64, device=dev).reshape(ap.numel(), -1)
+    T = torch.as_tensor(n_pos, device=dev).to(torch.float64).reshape(-1, 1)
+    N = torch.tensor(float(n), dtype=torch.float64, device=dev)  # (a tensor: torch divides by it; by a Python number it may multiply
+    #                                                              by the reciprocal on one device and divide on the other)
+    k = torch.tensor([float(v) for v in cuts], dtype=torch.float64, device=dev).reshape(1, -1)
+    alpha = torch.tensor([float(v) for v in alphas], dtype=torch.float64, device=dev).reshape(1, -1)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    undefined = (T == 0) | (T == N)
+    Ra = T / N
+    ef = (hits / k) / Ra
+    RIE = rie / T / ((1.0 / N) * (1.0 - torch.exp(-alpha)) / (torch.exp(alpha / N) - 1.0))
+    bedroc = RIE * Ra * torch.sinh(alpha / 2) / (torch.cosh(alpha / 2) - torch.cosh(alpha / 2 - alpha * Ra)) \
+        + 1.0 / (1.0 - torch.exp(alpha * (1.0 - Ra)))
+    return {"AP": torch.where(undefined.reshape(-1), nan, ap.reshape(-1)), "EF": torch.where(undefined, nan, ef),
+            "BEDROC": torch.where(undefined, nan, bedroc)}
+
+
+def _early_point(true_y, predicted_score, cuts, alphas):
+    """The definition with every multiplicity equal to 1, in torch operators on the scores' device: ``(ap [1], hits [1, J], rie [1, A],
+    T)``."""
+    y, s = _as_vectors(true_y, predicted_score)
+    y, s = y.detach(), s.detach()
+    n, dev = s.numel(), s.device
+    order = torch.sort(s, descending=True, stable=True)
+    ys, ss = y[order.indices], order.values
+    last = torch.ones(n, dtype=torch.bool, device=dev)
+    last[:-1] = ss[1:] != ss[:-1]
+    idx = torch.nonzero(last).reshape(-1)
+    end = (idx + 1).to(torch.float64)                             # rows up to and including each tie group
+    tps = torch.cumsum(ys, 0)[idx]
+    zero = torch.zeros(1, dtype=torch.float64, device=dev)
+    before, tps_before = torch.cat([zero, end[:-1]]), torch.cat([zero, tps[:-1]])
+    gt, sg = tps - tps_before, end - before
+    T, N = float(tps[-1]), float(n)
+    pos = gt > 0
+    ap = ((gt[pos] / T) * (tps[pos] / end[pos])).sum().reshape(1) if T > 0 else zero.clone()
+    k = torch.tensor([float(v) for v in cuts], dtype=torch.float64, device=dev)
+    g = torch.searchsorted(end, k).clamp(max=end.numel() - 1)     # (before[g] < k <= end[g])
+    hits = (tps_before[g] + gt[g] * (k - before[g]) / sg[g]).reshape(1, -1)
+    rie = torch.stack([(gt[pos] * torch.exp(-(a * (before[pos] + 1)) / N) * (-torch.expm1(-(a * sg[pos]) / N))
+                        / (-math.expm1(-a / N)) / sg[pos]).sum() for a in (float(v) for v in alphas)]).reshape(1, -1) \
+        if len(alphas) else torch.zeros((1, 0), dtype=torch.float64, device=dev)
+    return ap, hits, rie, T
+
+
+def _point_or_minus_one(true_y, predicted_score, cuts, alphas, key: str):
+    y, s = _as_vectors(true_y, predicted_score)
+    if y.numel() == 0 or float(y.sum()) == 0.0 or float(y.sum()) == float(y.numel()):
+        return -1
+    ap, hits, rie, T = _early_point(true_y, predicted_score, cuts, alphas)
+    return float(early_derived(ap, hits, rie, torch.tensor([T], dtype=torch.float64, device=ap.device), y.numel(), cuts,
+                               alphas)[key].reshape(-1)[0])
+
+
+def calculate_average_precision(true_y, predicted_score) -> float:
+    """Average precision (the area under the precision-recall curve as ``sklearn.metrics.average_precision_score`` sums it: one step
+    per distinct score), or ``-1`` when a class is absent."""
+    return _point_or_minus_one(true_y, predicted_score, (), (), "AP")
+
+
+def calculate_enrichment_factor(true_y, predicted_score, fraction: float = 0.01) -> float:
+    """The enrichment factor at ``fraction``: the share of actives among the top ``k = early_cut(fraction, n)`` rows over their share
+    among all rows, rows of equal score counted in random order (their expectation); ``-1`` when a class is absent."""
+    y, _ = _as_vectors(true_y, predicted_score)
+    return _point_or_minus_one(true_y, predicted_score, (early_cut(fraction, max(1, y.numel())),), (), "EF")
+
+
+def calculate_bedroc(true_y, predicted_score, alpha: float = 20.0) -> float:
+    """BEDROC (Truchon & Bayly 2007; RDKit's ``CalcBEDROC``) at ``alpha``, a tied active taking the mean over its group's positions;
+    ``-1`` when a class is absent."""
+    return _point_or_minus_one(true_y, predicted_score, (), (_check_alpha(alpha),), "BEDROC")
+
+
+class EarlySpec:
+    """The early-recognition names of a call, parsed: ``names`` in the caller's order, the distinct ``fractions`` and ``alphas`` they
+    need, and per name ``('AP', None)``, ``('EF', column of fractions)`` or ``('BEDROC', column of alphas)``."""
+
+    def __init__(self, names):
+        if isinstance(names, str):
+            raise ValueError("early: a tuple of names, not one string")
+        self.names, self.fractions, self.alphas, self.where = tuple(names), [], [], {}
+        for name in self.names:
+            kind, value = parse_early_name(name)
+            if kind == "AP":
+                self.where[name] = ("AP", None)
+                continue
+            column = self.fractions if kind == "EF" else self.alphas
+            if value not in column:
+                column.append(value)
+            self.where[name] = (kind, column.index(value))
+        if len(self.fractions) > BOOTSTRAP_MAX_CUTS:
+            raise ValueError(f"early: {len(self.fractions)} distinct enrichment fractions, at most {BOOTSTRAP_MAX_CUTS} per call")
+        if len(self.alphas) > BOOTSTRAP_MAX_ALPHAS:
+            raise ValueError(f"early: {len(self.alphas)} distinct BEDROC alphas, at most {BOOTSTRAP_MAX_ALPHAS} per call")
+
+    def cuts(self, n: int) -> list:
+        return [early_cut(x, n) for x in self.fractions]
+
+    def pick(self, derived: dict) -> dict:
+        """``{name: [B]}`` out of ``early_derived``'s result."""
+        return {name: derived[kind] if col is None else derived[kind][:, col] for name, (kind, col) in self.where.items()}
+
+
+def parse_early_name(name):
+    """``('AP', None)``, ``('EF', fraction)`` or ``('BEDROC', alpha)`` for ``'AP'``, ``'EF_<fraction>'`` (``0 < fraction <= 1``) or
+    ``'BEDROC_<alpha>'`` (``0 < alpha <= 500``); anything else raises ``ValueError``."""
+    if name == "AP":
+        return "AP", None
+    if isinstance(name, str):
+        for kind, check in (("EF", _check_fraction), ("BEDROC", _check_alpha)):
+            if name.startswith(kind + "_"):
+                try:
+                    value = float(name[len(kind) + 1:])
+                except ValueError:
+                    raise ValueError(f"early-recognition metric {name!r}: '{kind}_<number>' is required") from None
+                return kind, check(value)
+    raise ValueError(f"unknown early-recognition metric {name!r}: 'AP', 'EF_<fraction>' or 'BEDROC_<alpha>'")
+
+
+def is_early_name(name) -> bool:
+    """Whether ``name`` spells an early-recognition metric (``'EF_'`` / ``'BEDROC_'`` names with a bad number raise)."""
+    if name == "AP":
+        return True
+    return isinstance(name, str) and name.startswith(("EF_", "BEDROC_")) and parse_early_name(name) is not None
+
+
+def early_points(true_y, predicted_score, spec: "EarlySpec") -> dict:
+    """``{name: value}`` on the full data (every multiplicity 1), from one sort."""
+    y, _ = _as_vectors(true_y, predicted_score)
+    cuts = spec.cuts(y.numel())
+    ap, hits, rie, T = _early_point(true_y, predicted_score, cuts, spec.alphas)
+    derived = early_derived(ap, hits, rie, torch.tensor([T], dtype=torch.float64, device=ap.device), y.numel(), cuts, spec.alphas)
+    return {name: float(v[0]) for name, v in spec.pick(derived).items()}
+
+
+def _bootstrap_replicates(true_y, predicted_score, n_boot: int, FPR_range, seed: int, offset: int, stratified: bool, spec=None):
     """``(auc, logauc, two_u, n_pos)`` tensors ``[n_boot]`` on the scores' device: CUDA scores through one stable sort and
-    ``readout.bootstrap_roc`` (at most ``BOOTSTRAP_MAX_REPLICATES`` per launch sequence), CPU scores through ``bootstrap_reference``."""
+    ``readout.bootstrap_roc`` (at most ``BOOTSTRAP_MAX_REPLICATES`` per launch sequence), CPU scores through ``bootstrap_reference``.
+    With an ``EarlySpec`` that names something, also ``(ap [n_boot], hits [n_boot, J], rie [n_boot, A])`` behind them: the launch is
+    ``readout.bootstrap_early`` then, and the host route adds ``early_reference``."""
     lower, upper = _check_fpr_range(FPR_range)
     y, s = _as_vectors(true_y, predicted_score)
     y, s = y.detach(), s.detach()
@@ -316,17 +583,34 @@ def _bootstrap_replicates(true_y, predicted_score, n_boot: int, FPR_range, seed:
     _check_bootstrap_sizes(n, B, seed, offset)
     if not bool(torch.isfinite(s).all()):
         raise ValueError("predicted_score holds a NaN or an infinite value")
+    early = spec is not None and bool(spec.names)
+    cuts = spec.cuts(n) if early else None
     if not s.is_cuda:
         ref = bootstrap_reference(y, s, B, (lower, upper), seed, offset, stratified)
-        return (torch.from_numpy(ref["AUC"]), torch.from_numpy(ref["logAUC"]), torch.from_numpy(ref["two_u"]),
-                torch.from_numpy(ref["n_pos"]))
+        out = (torch.from_numpy(ref["AUC"]), torch.from_numpy(ref["logAUC"]), torch.from_numpy(ref["two_u"]),
+               torch.from_numpy(ref["n_pos"]))
+        if early:
+            e = early_reference(y, s, B, cuts, spec.alphas, seed, offset, stratified)
+            out += (torch.from_numpy(e["ap"]), torch.from_numpy(e["hits"]), torch.from_numpy(e["rie"]))
+        return out
     from . import _lib, readout
     rank, y_sorted, group_last, split = bootstrap_prepare(y == 1.0, s, stratified)
+    if early:
+        cuts_t = torch.tensor(cuts, dtype=torch.int32).to(s.device)
+        alphas_t = torch.tensor(spec.alphas, dtype=torch.float64).to(s.device)
     parts = []
     for b0 in range(0, B, _lib.BOOTSTRAP_MAX_REPLICATES):
         nb = min(_lib.BOOTSTRAP_MAX_REPLICATES, B - b0)
-        parts.append(readout.bootstrap_roc(rank, y_sorted, group_last, split, nb, seed, offset + b0, lower, upper))
-    return tuple(torch.cat([p[k] for p in parts]) if len(parts) > 1 else parts[0][k] for k in range(4))
+        if early:
+            parts.append(readout.bootstrap_early(rank, y_sorted, group_last, split, nb, seed, offset + b0, lower, upper, cuts_t, alphas_t))
+        else:
+            parts.append(readout.bootstrap_roc(rank, y_sorted, group_last, split, nb, seed, offset + b0, lower, upper))
+    return tuple(torch.cat([p[k] for p in parts]) if len(parts) > 1 else parts[0][k] for k in range(len(parts[0])))
+
+
+def _early_replicates(spec, reps, n: int) -> dict:
+    """``{name: [B]}`` of the spec's names from ``_bootstrap_replicates``' seven tensors."""
+    return spec.pick(early_derived(reps[4], reps[5], reps[6], reps[3], n, spec.cuts(n), spec.alphas))
 
 
 def bootstrap_prepare(y_active: torch.Tensor, score: torch.Tensor, stratified: bool = False):
@@ -378,45 +662,71 @@ def _check_two_classes(true_y, predicted_score) -> None:
 
 
 def bootstrap_metrics(true_y, predicted_score, n_boot: int = 1000, FPR_range=(0.001, 0.1), confidence: float = 0.95,
-                      seed: int = 0, offset: int = 0, stratified: bool = False) -> dict:
+                      seed: int = 0, offset: int = 0, stratified: bool = False, early=()) -> dict:
     """Non-parametric bootstrap of AUC and ``logAUC_{FPR_range}``: ``point`` (the existing functions on the full data), ``replicates``
     (``{'AUC': [B], 'logAUC': [B]}`` on the scores' device; NaN where a resample holds one class only), per metric ``mean``, ``std``
     (unbiased) and the percentile interval ``ci`` over the defined replicates, ``n_undefined``, ``n_pos`` (the actives of each
     replicate, int32 ``[B]``) and the ``seed``, ``offset`` and ``n_boot`` used (the call consumes ``offset .. offset + n_boot - 1``).
     CUDA scores are evaluated by ``mkgnn_bootstrap_roc`` behind one sort, CPU scores by ``bootstrap_reference``; the resamples are
     the same either way.  ``stratified`` resamples actives and inactives separately.  Only one class in the full data raises
-    ``ValueError``."""
+    ``ValueError``.
+
+    ``early``: a tuple of names out of ``'AP'`` (average precision), ``'EF_<fraction>'`` (enrichment factor) and ``'BEDROC_<alpha>'``, at
+    most 8 distinct fractions and 4 distinct alphas; an unknown or malformed name raises ``ValueError`` before any launch.  Empty (the
+    default), the result and the launch (``mkgnn_bootstrap_roc``) are exactly as described above.  Otherwise every name gets its
+    ``point``, ``replicates`` and ``mean`` / ``std`` / ``ci`` as AUC has them, from the SAME resamples and one ``mkgnn_bootstrap_early``
+    per chunk of replicates (CPU scores: ``early_reference``), and ``cuts`` maps every ``'EF_'`` name to the rows it looked at."""
     _check_confidence(confidence)
     _check_fpr_range(FPR_range)
+    spec = EarlySpec(early)
     _check_two_classes(true_y, predicted_score)
-    auc, logauc, _, n_pos = _bootstrap_replicates(true_y, predicted_score, n_boot, FPR_range, seed, offset, stratified)
+    reps = _bootstrap_replicates(true_y, predicted_score, n_boot, FPR_range, seed, offset, stratified, spec)
+    auc, logauc, n_pos = reps[0], reps[1], reps[3]
     out = {"point": {"AUC": calculate_auc(true_y, predicted_score), "logAUC": calculate_logAUC(true_y, predicted_score, FPR_range)},
            "replicates": {"AUC": auc, "logAUC": logauc}, "AUC": _interval(auc, confidence), "logAUC": _interval(logauc, confidence),
            "n_undefined": int(torch.isnan(auc).sum()), "n_pos": n_pos, "seed": int(seed), "offset": int(offset),
            "n_boot": int(n_boot), "confidence": float(confidence), "FPR_range": tuple(float(v) for v in FPR_range),
            "stratified": bool(stratified)}
+    if spec.names:
+        n = torch.as_tensor(predicted_score).numel()
+        out["point"].update(early_points(true_y, predicted_score, spec))
+        for name, values in _early_replicates(spec, reps, n).items():
+            out["replicates"][name] = values
+            out[name] = _interval(values, confidence)
+        out["cuts"] = {name: spec.cuts(n)[col] for name, (kind, col) in spec.where.items() if kind == "EF"}
     return out
 
 
 def bootstrap_compare(true_y, score_a, score_b, n_boot: int = 1000, FPR_range=(0.001, 0.1), confidence: float = 0.95, seed: int = 0,
-                      offset: int = 0, stratified: bool = False) -> dict:
+                      offset: int = 0, stratified: bool = False, early=()) -> dict:
     """The paired bootstrap of two score vectors on the same labels: both see the SAME resamples (a draw depends on ``(seed, offset +
     b, i, n, split)`` alone).  Per metric: ``diff`` (the replicate differences ``a - b``, ``[B]``), their ``mean``, ``std`` and
     ``ci``, and ``p_a_better``, the share of defined replicates with a positive difference; also ``point`` (``a``, ``b`` and ``diff`` on
-    the full data), ``n_undefined`` and the ``seed``, ``offset`` and ``n_boot`` used."""
+    the full data), ``n_undefined`` and the ``seed``, ``offset`` and ``n_boot`` used.  ``early``: as in ``bootstrap_metrics`` -- every
+    name is compared as AUC is, and the result carries ``cuts``."""
     _check_confidence(confidence)
     _check_fpr_range(FPR_range)
+    spec = EarlySpec(early)
     _check_two_classes(true_y, score_a)
-    a = _bootstrap_replicates(true_y, score_a, n_boot, FPR_range, seed, offset, stratified)
-    b = _bootstrap_replicates(true_y, score_b, n_boot, FPR_range, seed, offset, stratified)
+    a = _bootstrap_replicates(true_y, score_a, n_boot, FPR_range, seed, offset, stratified, spec)
+    b = _bootstrap_replicates(true_y, score_b, n_boot, FPR_range, seed, offset, stratified, spec)
     if not torch.equal(a[3].cpu(), b[3].cpu()):
         raise RuntimeError("bootstrap_compare: the two score vectors saw different resamples")
     point_a = {"AUC": calculate_auc(true_y, score_a), "logAUC": calculate_logAUC(true_y, score_a, FPR_range)}
     point_b = {"AUC": calculate_auc(true_y, score_b), "logAUC": calculate_logAUC(true_y, score_b, FPR_range)}
     out = {"point": {"a": point_a, "b": point_b, "diff": {k: point_a[k] - point_b[k] for k in point_a}},
            "n_undefined": int(torch.isnan(a[0]).sum()), "seed": int(seed), "offset": int(offset), "n_boot": int(n_boot)}
-    for name, k in (("AUC", 0), ("logAUC", 1)):
-        diff = a[k] - b[k].to(a[k].device)
+    pairs = {"AUC": (a[0], b[0]), "logAUC": (a[1], b[1])}
+    if spec.names:
+        n = torch.as_tensor(score_a).numel()
+        point_a.update(early_points(true_y, score_a, spec))
+        point_b.update(early_points(true_y, score_b, spec))
+        out["point"]["diff"] = {k: point_a[k] - point_b[k] for k in point_a}
+        early_a, early_b = _early_replicates(spec, a, n), _early_replicates(spec, b, n)
+        pairs.update({name: (early_a[name], early_b[name]) for name in early_a})
+        out["cuts"] = {name: spec.cuts(n)[col] for name, (kind, col) in spec.where.items() if kind == "EF"}
+    for name, (va, vb) in pairs.items():
+        diff = va - vb.to(va.device)
         defined = diff[~torch.isnan(diff)]
         entry = _interval(diff, confidence)
         entry["diff"] = diff
@@ -426,9 +736,11 @@ def bootstrap_compare(true_y, score_a, score_b, n_boot: int = 1000, FPR_range=(0
 
 
 def bootstrap_per_task(true_y, pred_y, task, num_tasks: int, n_boot: int = 1000, FPR_range=(0.001, 0.1), confidence: float = 0.95,
-                       seed: int = 0, offset: int = 0, stratified: bool = False) -> list:
+                       seed: int = 0, offset: int = 0, stratified: bool = False, early=()) -> list:
     """``bootstrap_metrics`` over each task's labelled rows, as ``per_task`` selects them; task ``t`` uses the offsets ``offset + t *
-    n_boot .. offset + (t + 1) * n_boot - 1``.  A task without a row, or with one class only, gives ``None``."""
+    n_boot .. offset + (t + 1) * n_boot - 1``.  A task without a row, or with one class only, gives ``None``.  ``early``: as in
+    ``bootstrap_metrics`` (refused here, before any task is run)."""
+    EarlySpec(early)
     y = torch.as_tensor(true_y).reshape(-1)
     s = torch.as_tensor(pred_y).reshape(-1)
     t = torch.as_tensor(task).reshape(-1).to(s.device)
@@ -443,5 +755,6 @@ def bootstrap_per_task(true_y, pred_y, task, num_tasks: int, n_boot: int = 1000,
         if yk.numel() == 0 or active == 0 or active == yk.numel():
             out.append(None)
             continue
-        out.append(bootstrap_metrics(yk, s[rows], n_boot, FPR_range, confidence, seed, int(offset) + k * int(n_boot), stratified))
+        out.append(bootstrap_metrics(yk, s[rows], n_boot, FPR_range, confidence, seed, int(offset) + k * int(n_boot), stratified,
+                                     early))
     return out

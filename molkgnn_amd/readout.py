@@ -2473,6 +2473,47 @@ def bootstrap_roc_replicates_per_pass(n: int, n_boot: int) -> int:
     return max(1, min(int(n_boot), _lib.BOOTSTRAP_WORKSPACE_CAP // per))
 
 
+def _bootstrap_checked(who: str, rank, y_sorted, group_last, split, n_boot, seed, offset, lower, upper):
+    """The checks ``bootstrap_roc`` and ``bootstrap_early`` share: ``(n, split, B, seed, offset, lower, upper)`` as Python numbers."""
+    if not all(torch.is_tensor(x) and x.dim() == 1 for x in (rank, y_sorted, group_last)) or rank.dtype != torch.int32 \
+            or y_sorted.dtype != torch.uint8 or group_last.dtype != torch.uint8 \
+            or not (rank.numel() == y_sorted.numel() == group_last.numel()):
+        raise ValueError(f"{who} needs rank int32 [n], y_sorted uint8 [n] and group_last uint8 [n]")
+    if not rank.is_cuda or y_sorted.device != rank.device or group_last.device != rank.device:
+        raise ValueError(f"{who} runs on the GPU: rank is on {rank.device}, y_sorted on {y_sorted.device}, group_last on "
+                         f"{group_last.device} (there is no CPU path; evaluation.bootstrap_reference is the host form)")
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (rank, y_sorted, group_last)):
+        raise RuntimeError(f"{who} is forward only: call it under torch.no_grad() (or on detached inputs)")
+    n, split, B = rank.numel(), int(split), int(n_boot)
+    if not 1 <= n <= _lib.BOOTSTRAP_MAX_ROWS:
+        raise ValueError(f"{who}: {n} rows outside [1, {_lib.BOOTSTRAP_MAX_ROWS}]")
+    if not 1 <= B <= _lib.BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"{who}: n_boot = {n_boot} outside [1, {_lib.BOOTSTRAP_MAX_REPLICATES}] per call")
+    if not 0 <= split <= n:
+        raise ValueError(f"{who}: split = {split} outside [0, {n}]")
+    lower, upper = float(lower), float(upper)
+    if not (0.0 < lower < upper <= 1.0):
+        raise ValueError(f"{who}: FPR window ({lower}, {upper}): 0 < lower < upper <= 1 is required")
+    seed, offset = int(seed), int(offset)
+    if not (0 <= seed < 1 << 64 and 0 <= offset and offset + B <= 1 << 64):
+        raise ValueError(f"{who}: seed and offset .. offset + n_boot - 1 are unsigned 64-bit values")
+    if not (rank.is_contiguous() and y_sorted.is_contiguous() and group_last.is_contiguous()):
+        raise ValueError(f"{who} needs contiguous tensors")
+    return n, split, B, seed, offset, lower, upper
+
+
+def _bootstrap_scratch(lib, dev, n: int, B: int, workspace):
+    """``(pointer, bytes)`` of the scratch of a bootstrap call: none up to ``_lib.BOOTSTRAP_LDS_MAX_N`` rows."""
+    if n <= _lib.BOOTSTRAP_LDS_MAX_N:
+        return None, 0
+    want = workspace.numel() if workspace is not None else \
+        int(lib.mkgnn_bootstrap_roc_workspace_bytes(n, bootstrap_roc_replicates_per_pass(n, B)))
+    if workspace is not None and want < int(lib.mkgnn_bootstrap_roc_workspace_bytes(n, 1)):
+        raise ValueError(f"workspace: at least {int(lib.mkgnn_bootstrap_roc_workspace_bytes(n, 1))} bytes (one replicate)")
+    ws = _max_cosine_workspace(dev, want, workspace)
+    return ws.data_ptr(), ws.numel()
+
+
 def bootstrap_roc(rank: torch.Tensor, y_sorted: torch.Tensor, group_last: torch.Tensor, split: int, n_boot: int, seed: int,
                   offset: int, lower: float, upper: float, workspace: Optional[torch.Tensor] = None):
     """``(auc float64 [n_boot], logauc float64 [n_boot], two_u int64 [n_boot], n_pos int32 [n_boot])``: ``n_boot`` bootstrap replicates
@@ -2487,47 +2528,67 @@ def bootstrap_roc(rank: torch.Tensor, y_sorted: torch.Tensor, group_last: torch.
     without it a per-device buffer that only grows serves eager calls (sized for ``bootstrap_roc_replicates_per_pass``), and a call
     inside a capture allocates its own.  Up to ``_lib.BOOTSTRAP_LDS_MAX_N`` rows no scratch is used.  It has no autograd node: called
     where a gradient is being recorded for one of its inputs it raises."""
-    if not all(torch.is_tensor(x) and x.dim() == 1 for x in (rank, y_sorted, group_last)) or rank.dtype != torch.int32 \
-            or y_sorted.dtype != torch.uint8 or group_last.dtype != torch.uint8 \
-            or not (rank.numel() == y_sorted.numel() == group_last.numel()):
-        raise ValueError("bootstrap_roc needs rank int32 [n], y_sorted uint8 [n] and group_last uint8 [n]")
-    if not rank.is_cuda or y_sorted.device != rank.device or group_last.device != rank.device:
-        raise ValueError(f"bootstrap_roc runs on the GPU: rank is on {rank.device}, y_sorted on {y_sorted.device}, group_last on "
-                         f"{group_last.device} (there is no CPU path; evaluation.bootstrap_reference is the host form)")
-    if torch.is_grad_enabled() and any(x.requires_grad for x in (rank, y_sorted, group_last)):
-        raise RuntimeError("bootstrap_roc is forward only: call it under torch.no_grad() (or on detached inputs)")
-    n, split, B = rank.numel(), int(split), int(n_boot)
-    if not 1 <= n <= _lib.BOOTSTRAP_MAX_ROWS:
-        raise ValueError(f"bootstrap_roc: {n} rows outside [1, {_lib.BOOTSTRAP_MAX_ROWS}]")
-    if not 1 <= B <= _lib.BOOTSTRAP_MAX_REPLICATES:
-        raise ValueError(f"bootstrap_roc: n_boot = {n_boot} outside [1, {_lib.BOOTSTRAP_MAX_REPLICATES}] per call")
-    if not 0 <= split <= n:
-        raise ValueError(f"bootstrap_roc: split = {split} outside [0, {n}]")
-    lower, upper = float(lower), float(upper)
-    if not (0.0 < lower < upper <= 1.0):
-        raise ValueError(f"bootstrap_roc: FPR window ({lower}, {upper}): 0 < lower < upper <= 1 is required")
-    seed, offset = int(seed), int(offset)
-    if not (0 <= seed < 1 << 64 and 0 <= offset and offset + B <= 1 << 64):
-        raise ValueError("bootstrap_roc: seed and offset .. offset + n_boot - 1 are unsigned 64-bit values")
-    if not (rank.is_contiguous() and y_sorted.is_contiguous() and group_last.is_contiguous()):
-        raise ValueError("bootstrap_roc needs contiguous tensors")
+    n, split, B, seed, offset, lower, upper = _bootstrap_checked("bootstrap_roc", rank, y_sorted, group_last, split, n_boot, seed, offset,
+                                                                 lower, upper)
     dev = rank.device
     auc = torch.empty(B, dtype=torch.float64, device=dev)
     logauc = torch.empty(B, dtype=torch.float64, device=dev)
     two_u = torch.empty(B, dtype=torch.int64, device=dev)
     n_pos = torch.empty(B, dtype=torch.int32, device=dev)
     lib = _lib.load()
-    if n <= _lib.BOOTSTRAP_LDS_MAX_N:
-        ws_ptr, ws_bytes = None, 0
-    else:
-        want = workspace.numel() if workspace is not None else \
-            int(lib.mkgnn_bootstrap_roc_workspace_bytes(n, bootstrap_roc_replicates_per_pass(n, B)))
-        if workspace is not None and want < int(lib.mkgnn_bootstrap_roc_workspace_bytes(n, 1)):
-            raise ValueError(f"workspace: at least {int(lib.mkgnn_bootstrap_roc_workspace_bytes(n, 1))} bytes (one replicate)")
-        ws = _max_cosine_workspace(dev, want, workspace)
-        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
+    ws_ptr, ws_bytes = _bootstrap_scratch(lib, dev, n, B, workspace)
     with torch.cuda.device(dev):
         _lib.check(lib.mkgnn_bootstrap_roc(rank.data_ptr(), y_sorted.data_ptr(), group_last.data_ptr(), n, split, B, seed, offset,
                                            lower, upper, auc.data_ptr(), logauc.data_ptr(), two_u.data_ptr(), n_pos.data_ptr(),
                                            ws_ptr, ws_bytes, _lib.stream_ptr(dev)), "mkgnn_bootstrap_roc")
     return auc, logauc, two_u, n_pos
+
+
+def _early_vector(who: str, what: str, values, dtype, limit: int, dev) -> torch.Tensor:
+    """``cuts`` / ``alphas`` of ``bootstrap_early`` as a contiguous device vector: a tensor is taken as it is (no host read: a
+    captured call re-reads it), a sequence is copied over."""
+    if torch.is_tensor(values):
+        if values.dim() != 1 or values.dtype != dtype or values.device != dev or not values.is_contiguous():
+            raise ValueError(f"{who}: {what} as a tensor is a contiguous {dtype} vector on {dev}")
+        v = values
+    else:
+        v = torch.tensor(list(values), dtype=dtype).reshape(-1).to(dev)
+    if v.numel() > limit:
+        raise ValueError(f"{who}: {v.numel()} {what}, at most {limit}")
+    return v
+
+
+def bootstrap_early(rank: torch.Tensor, y_sorted: torch.Tensor, group_last: torch.Tensor, split: int, n_boot: int, seed: int,
+                    offset: int, lower: float, upper: float, cuts, alphas, workspace: Optional[torch.Tensor] = None):
+    """``bootstrap_roc`` with the early-recognition sums of the same replicates, from the same walk behind the same draw (one
+    ``mkgnn_bootstrap_early``): ``(auc, logauc, two_u, n_pos, ap float64 [n_boot], hits float64 [n_boot, J], rie float64 [n_boot,
+    A])``.  ``cuts``: up to ``_lib.BOOTSTRAP_MAX_CUTS`` integers ``1 <= k <= n`` (an int32 device tensor, or a sequence) --
+    ``hits[b, j]`` is the expected number of actives among the first ``cuts[j]`` drawn rows, a tie group's rows in random order;
+    ``alphas``: up to ``_lib.BOOTSTRAP_MAX_ALPHAS`` values in ``(0, 500]`` (a float64 device tensor, or a sequence) -- ``rie[b, a]``
+    is the sum over the drawn actives of ``exp(-alpha r / n)``; ``ap`` is the weighted average precision.  ``evaluation.
+    early_reference_sorted`` is the definition (``hits`` agrees bit for bit, ``ap`` and ``rie`` within the rounding of a float64 sum)
+    and ``evaluation.early_derived`` turns the sums into AP, EF and BEDROC.  The first four outputs are ``bootstrap_roc``'s bit for
+    bit.  A cut or an alpha outside its range gives a NaN column and changes nothing else.  Checks, scratch and capture: as
+    ``bootstrap_roc``."""
+    who = "bootstrap_early"
+    n, split, B, seed, offset, lower, upper = _bootstrap_checked(who, rank, y_sorted, group_last, split, n_boot, seed, offset, lower, upper)
+    dev = rank.device
+    cuts = _early_vector(who, "cuts", cuts, torch.int32, _lib.BOOTSTRAP_MAX_CUTS, dev)
+    alphas = _early_vector(who, "alphas", alphas, torch.float64, _lib.BOOTSTRAP_MAX_ALPHAS, dev)
+    J, A = cuts.numel(), alphas.numel()
+    auc = torch.empty(B, dtype=torch.float64, device=dev)
+    logauc = torch.empty(B, dtype=torch.float64, device=dev)
+    two_u = torch.empty(B, dtype=torch.int64, device=dev)
+    n_pos = torch.empty(B, dtype=torch.int32, device=dev)
+    ap = torch.empty(B, dtype=torch.float64, device=dev)
+    hits = torch.empty((B, J), dtype=torch.float64, device=dev)
+    rie = torch.empty((B, A), dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    ws_ptr, ws_bytes = _bootstrap_scratch(lib, dev, n, B, workspace)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkgnn_bootstrap_early(rank.data_ptr(), y_sorted.data_ptr(), group_last.data_ptr(), n, split, B, seed, offset,
+                                             lower, upper, cuts.data_ptr() if J else None, J, alphas.data_ptr() if A else None, A,
+                                             auc.data_ptr(), logauc.data_ptr(), two_u.data_ptr(), n_pos.data_ptr(), ap.data_ptr(),
+                                             hits.data_ptr() if J else None, rie.data_ptr() if A else None, ws_ptr, ws_bytes,
+                                             _lib.stream_ptr(dev)), "mkgnn_bootstrap_early")
+    return auc, logauc, two_u, n_pos, ap, hits, rie

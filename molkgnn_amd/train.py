@@ -427,13 +427,43 @@ def _metric_functions() -> dict:
     }
 
 
+def _early_metric(name):
+    """``f(true_y, pred_y)`` for an early-recognition name (``'AP'``, ``'EF_<fraction>'``, ``'BEDROC_<alpha>'``), ``None`` for any other
+    name; a malformed one raises ``ValueError``."""
+    from . import evaluation as E
+    if not E.is_early_name(name):
+        return None
+    kind, value = E.parse_early_name(name)
+    if kind == 'AP':
+        return E.calculate_average_precision
+    if kind == 'EF':
+        return lambda true_y, pred_y: E.calculate_enrichment_factor(true_y, pred_y, value)
+    return lambda true_y, pred_y: E.calculate_bedroc(true_y, pred_y, value)
+
+
 def _check_metrics(metrics) -> dict:
-    """``_metric_functions()``, once every name in ``metrics`` is known to be one of them."""
+    """``_metric_functions()`` and the early-recognition names among ``metrics``, once every name in ``metrics`` is known to be one
+    of them."""
     table = _metric_functions()
+    for m in metrics:
+        if m not in table:
+            fn = _early_metric(m)
+            if fn is not None:
+                table[m] = fn
     unknown = [m for m in metrics if m not in table]
     if unknown:
-        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(table)}")
+        raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(_metric_functions())}, 'AP', 'EF_<fraction>' or "
+                         f"'BEDROC_<alpha>'")
+    _early_names(metrics)
     return table
+
+
+def _early_names(metrics) -> tuple:
+    """The early-recognition names among ``metrics``, which the evaluate functions hand to the bootstrap."""
+    from .evaluation import EarlySpec, is_early_name
+    names = tuple(m for m in metrics if is_early_name(m))
+    EarlySpec(names)                             # (too many distinct fractions or alphas: refused before anything is launched)
+    return names
 
 
 def _required_loss_kind(model, who: str) -> str:
@@ -475,7 +505,7 @@ def _results(model, pred_y: torch.Tensor, true_y: torch.Tensor, metrics, table: 
         results[m] = table[m](true_y, pred_y)
     if bootstrap is not None:
         from .evaluation import bootstrap_metrics
-        results['bootstrap'] = bootstrap_metrics(true_y, pred_y.detach(), n_boot=bootstrap)
+        results['bootstrap'] = bootstrap_metrics(true_y, pred_y.detach(), n_boot=bootstrap, early=_early_names(metrics))
     results['pred_y'], results['true_y'] = pred_y, true_y
     return results
 
@@ -494,7 +524,11 @@ def evaluate(model, batches, metrics=(), bootstrap: Optional[int] = None) -> dic
     logging are the caller's.
 
     ``bootstrap``: ``None``, or a number of replicates -- then ``results['bootstrap']`` is ``evaluation.bootstrap_metrics(true_y,
-    pred_y, n_boot=bootstrap)``: the percentile intervals of AUC and ``logAUC_0.001_0.1`` under resampling of the molecules."""
+    pred_y, n_boot=bootstrap)``: the percentile intervals of AUC and ``logAUC_0.001_0.1`` under resampling of the molecules.
+
+    ``metrics`` also takes the early-recognition names ``'AP'``, ``'EF_<fraction>'`` and ``'BEDROC_<alpha>'`` (``evaluation.
+    calculate_average_precision``, ``calculate_enrichment_factor``, ``calculate_bedroc``); with ``bootstrap`` those named are handed on as
+    ``bootstrap_metrics(..., early=...)`` and get their intervals from the same resamples.  A call that names none behaves as before."""
     table = _check_metrics(metrics)
     bootstrap = _check_bootstrap(bootstrap)
     with evaluation_mode(model):
@@ -532,7 +566,7 @@ def _task_results(pred: torch.Tensor, true_y: torch.Tensor, task: torch.Tensor, 
     if bootstrap is not None:                    # (per task: evaluation.bootstrap_per_task, None for a task it cannot resample)
         from .evaluation import bootstrap_per_task
         results['bootstrap'] = bootstrap_per_task(true_y, pred_y.detach(), torch.where(lab, task, torch.full_like(task, -1)), T,
-                                                  n_boot=bootstrap)
+                                                  n_boot=bootstrap, early=_early_names(metrics))
     results['pred_y'], results['true_y'], results['task'] = pred_y, true_y, task
     return results
 
