@@ -1629,6 +1629,58 @@ int mkgnn_bootstrap_early(const int32_t* rank, const uint8_t* y_sorted, const ui
                           const double* alphas, int32_t A, double* auc, double* logauc, int64_t* two_u, int32_t* n_pos, double* ap,
                           double* hits, double* rie, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Bootstrap replicates of the regression metrics (additive; the ABI version stays 8): the raw sums of RMSE, MAE, R2, Pearson,
+ * Spearman and top-fraction recall of B resamples of n rows with a prediction p and a truth t each, none of which is ever sorted.
+ * The caller sorts BOTH vectors once (best first, stable, the same direction for both) and passes
+ *   rank_p [n] int32                 row i -> its prediction rank (what the draw scatters through)
+ *   first_p, last_p [n] int32        by prediction rank: the first and the last rank of the rank's tie group
+ *   cross [n] int32                  truth rank -> the prediction rank of the same row
+ *   first_t, last_t [n] int32        by truth rank: the first and the last rank of the rank's tie group
+ *   p_sorted, t_by_prank [n] float64 by prediction rank: the row's prediction and its truth
+ *   centre [2] float64, DEVICE       the values the moments are centred on (the full sample's mean of p and of t)
+ *   cuts [J] int32, DEVICE           the top-k sizes, 0 <= J <= MKGNN_BOOTSTRAP_MAX_CUTS (J == 0: cuts and hits may be null)
+ * Replicate b draws as the unstratified mkgnn_bootstrap_roc does (split = n): row i draws row j = (uint64) philox_word(seed,
+ * offset + b, i) * n >> 32 and c[rank_p[j]] grows by one, so a regression fold and a classification fold with the same (seed,
+ * offset, n) see the same rows.  With Cp and Ct the inclusive prefix sums of c by prediction rank and by truth rank (Cp[-1] = 0)
+ * and N = the drawn rows, molkgnn_amd/evaluation.py::regression_reference_sorted is the definition of
+ *   mom[b, 0..6]       sum c dp, sum c dt, sum c dp^2, sum c dt^2, sum c dp dt, sum c |p - t|, sum c (p - t)^2 with dp = p -
+ *                      centre[0], dt = t - centre[1]; every term (double) c * (product), the product formed first, over the rows
+ *                      with c > 0.  float64 sums in one fixed order (tiles of 1 024 prediction ranks in rank order, a tile's terms
+ *                      by a fixed tree): |mom - definition| <= (m + 16) 2^-53 sum c |term| for m terms
+ *   rank_sums[b, 0..2] sum c a b, sum c a^2, sum c b^2 with a = 2 midrank_p - (N + 1) = Cp[first_p - 1] + Cp[last_p] - N of the
+ *                      row's tie group in prediction order and b the same in truth order: exact integers (|sum| <= n (n - 1)^2 <
+ *                      2^63 up to MKGNN_BOOTSTRAP_REG_MAX_ROWS).  Spearman = xy / sqrt(xx yy)
+ *   hits[b, j]         sum over the rows of min(clamp(cuts[j] - (Cp[q] - c), 0, c), clamp(cuts[j] - (Ct[r] - c), 0, c)), q and r the
+ *                      row's two ranks: the drawn copies that lie among the first cuts[j] copies in BOTH orders, copies ordered by
+ *                      (stable rank, copy number).  Exact.  A cut outside [1, n] is never used: its column is -1, nothing else changes
+ *   n_drawn[b]         N (n, unless a rank_p entry was out of range)
+ * evaluation.regression_derived turns them into the metrics.  A replicate's outputs are a function of (the ten arrays, n, seed,
+ * offset + b) alone: not of B, of where the call's replicates start, of the workspace's size or of the run.  Every index read from
+ * rank_p, cross, first_* and last_* is compared against n before it is an address: a drawn row whose rank_p is out of range is
+ * not drawn, a truth rank whose cross is out of range holds no copy, and a row with a first_* or last_* out of range enters no
+ * integer sum.
+ *
+ * The call passes over the replicates, as many at a time as the workspace holds -- floor(workspace_bytes / (8 ceil4(n))), at least
+ * one; mkgnn_bootstrap_regression_workspace_bytes(n, replicates_per_pass) = 2 * 4 ceil4(n) * replicates_per_pass, 0 for rejected
+ * sizes --: mkgnn_bootstrap_roc's clear and draw launches (integer atomicAdd; no float atomics anywhere), then ONE walk launch of one
+ * workgroup per replicate that sweeps the ranks three times -- prediction order (Cp in place of c, the moments), truth order (Ct),
+ * truth order again (the gathers and the integer sums).  The launch boundary is the only thing that orders workgroups against
+ * each other; no cooperative launch, no flag a workgroup waits on, no host round trip, no state between calls; capturable, and a
+ * captured call follows new values in every array, centre and cuts included.  The workspace is 16-byte aligned, needs no
+ * initialisation and stays at or under MKGNN_BOOTSTRAP_WORKSPACE_CAP by the caller's choice of replicates per pass.
+ *
+ * Limits: 1 <= n <= MKGNN_BOOTSTRAP_REG_MAX_ROWS (2^20); 1 <= B <= MKGNN_BOOTSTRAP_MAX_REPLICATES per call; 0 <= J <=
+ * MKGNN_BOOTSTRAP_MAX_CUTS.  Anything else -- a limit, a null pointer, a misaligned array (4 bytes for int32, 8 for float64 and
+ * int64, 16 for the workspace), a workspace that holds no replicate, overlapping buffers -- returns non-zero with mkgnn_last_error
+ * set, before any launch. */
+#define MKGNN_BOOTSTRAP_REG_MAX_ROWS 1048576
+size_t mkgnn_bootstrap_regression_workspace_bytes(int64_t n, int32_t replicates_per_pass);
+int mkgnn_bootstrap_regression(const int32_t* rank_p, const int32_t* first_p, const int32_t* last_p, const int32_t* cross,
+                               const int32_t* first_t, const int32_t* last_t, const double* p_sorted, const double* t_by_prank,
+                               const double* centre, const int32_t* cuts, int32_t J, int64_t n, int32_t B, uint64_t seed,
+                               uint64_t offset, double* mom, int64_t* rank_sums, int64_t* hits, int32_t* n_drawn, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

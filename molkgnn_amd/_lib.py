@@ -47,6 +47,8 @@ BOOTSTRAP_MAX_CUTS, BOOTSTRAP_MAX_ALPHAS = 8, 4
 # kgnn_bootstrap.hip's tiling (BS_TILE, BS_DRAW_ROWS, BS_LDS_MAX_N): ranks per tile of the walk, rows per block of the draw launch,
 # the most rows whose multiplicities one workgroup keeps in LDS (beyond: the workspace and three launches per pass)
 BOOTSTRAP_TILE, BOOTSTRAP_DRAW_ROWS, BOOTSTRAP_LDS_MAX_N = 1024, 1024, 8192
+# MKGNN_BOOTSTRAP_REG_MAX_ROWS: the rows of one mkgnn_bootstrap_regression (the int64 rank sums, at most n (n - 1)^2, stay exact)
+BOOTSTRAP_REG_MAX_ROWS = 1 << 20
 
 
 def diverse_tile(H: int) -> int:
@@ -297,7 +299,8 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_embed_neighbours_within", "mkgnn_embed_neighbours_within_workspace_bytes", "mkgnn_graph_components",
            "mkgnn_graph_components_workspace_bytes", "mkgnn_maxmin_pick", "mkgnn_maxmin_pick_workspace_bytes",
            "mkgnn_tail_score_mc", "mkgnn_tail_score_mc_workspace_bytes", "mkgnn_debug_set_bn_merge", "mkgnn_debug_conv_dispatch",
-           "mkgnn_bootstrap_roc", "mkgnn_bootstrap_roc_workspace_bytes", "mkgnn_bootstrap_early")
+           "mkgnn_bootstrap_roc", "mkgnn_bootstrap_roc_workspace_bytes", "mkgnn_bootstrap_early",
+           "mkgnn_bootstrap_regression", "mkgnn_bootstrap_regression_workspace_bytes")
 
 _lib: Optional[C.CDLL] = None
 TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmolkgnn_torch.so")
@@ -562,6 +565,13 @@ def load() -> C.CDLL:
     lib.mkgnn_bootstrap_early.restype = C.c_int
     lib.mkgnn_bootstrap_early.argtypes = [P, P, P, I64, I64, I32, C.c_uint64, C.c_uint64, C.c_double, C.c_double, P, I32, P, I32,
                                           P, P, P, P, P, P, P, P, C.c_size_t, P]
+    # bootstrap replicates of the regression metrics: (rank_p, first_p, last_p, cross, first_t, last_t, p_sorted, t_by_prank, centre,
+    # cuts, J, n, B, seed, offset, mom, rank_sums, hits, n_drawn, workspace, bytes, stream); the sizing takes (n, replicates per pass)
+    lib.mkgnn_bootstrap_regression_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_bootstrap_regression_workspace_bytes.argtypes = [I64, I32]
+    lib.mkgnn_bootstrap_regression.restype = C.c_int
+    lib.mkgnn_bootstrap_regression.argtypes = [P, P, P, P, P, P, P, P, P, P, I32, I64, I32, C.c_uint64, C.c_uint64, P, P, P, P, P,
+                                               C.c_size_t, P]
     lib.mkgnn_kernel_exemplars_workspace_bytes.restype = C.c_size_t
     lib.mkgnn_kernel_exemplars_workspace_bytes.argtypes = [C.POINTER(Int64x4), C.POINTER(Int32x4), I32, I32]
     lib.mkgnn_kernel_exemplars_update.restype = C.c_int

@@ -30,6 +30,11 @@
 // mkgnn_bootstrap_early is the same call with the early-recognition functionals of the curve -- the raw sums of average precision,
 // of the enrichment factor's hits and of BEDROC's RIE -- taken in the same walk: walk_replicate is ONE text with a compile-time
 // policy, the clear and draw kernels and the launch count are shared, and walk_replicate<RocOnly> is the walk described above.
+//
+// mkgnn_bootstrap_regression bootstraps the regression metrics (RMSE, MAE, R2, Pearson, Spearman, top-fraction recall) of rows with a
+// prediction and a truth, BOTH sorted once: the same clear and draw kernels (the unstratified draw, scattered through the
+// prediction ranks), then bootstrap_regression_walk_kernel, one workgroup per replicate, which needs prefix counts in two orders
+// at once and so is another walk -- see the comment in front of it.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
@@ -560,6 +565,209 @@ __global__ void __launch_bounds__(BS_THREADS) bootstrap_walk_early_kernel(
                    early_of(cuts, J, alphas, A, ap, hits, rie, eslot, b));
 }
 
+// ---- the regression walk (mkgnn_bootstrap_regression) ----
+// One workgroup per replicate, three sweeps over tiles of BS_TILE ranks with a carried prefix.  Cp starts as the replicate's
+// multiplicities by PREDICTION rank (the clear and draw launches above) and becomes their inclusive prefix sums in place; Ct gets
+// the prefix sums by TRUTH rank.  Both rows are ceil4(n) words, written and read by this workgroup alone: a barrier orders the
+// sweeps.  evaluation.regression_reference_sorted is the definition.
+//   sweep 1  prediction order: Cp, and the seven moment sums in float64 -- tiles in rank order, a tile's terms four per thread in
+//            rank order, the wave's butterfly, the waves in order (the log-area's rule)
+//   sweep 2  truth order: c = Cp[x] - Cp[x - 1] with x = cross[r], scanned into Ct
+//   sweep 3  truth order: every drawn row gathers a, b and the copies in front of it in both orders; the 3 + J integer sums are
+//            exact in any order, so a thread keeps its own until one reduction at the end
+// Every index read from cross, first_* and last_* is compared against n before it is an address; a row with one out of range
+// enters no sum.
+constexpr int BS_REG_MOM = 7, BS_REG_RANK = 3, BS_REG_INT = BS_REG_RANK + BS_MAX_CUTS;
+
+struct RegLds {
+    unsigned long long slot[BS_NW];
+    double mslot[2][BS_REG_MOM][BS_NW];              // by tile parity: written before a tile's scan, read behind it
+    unsigned long long islot[BS_REG_INT][BS_NW];
+};
+
+__device__ __forceinline__ bool in_rows(int v, int n) { return (uint32_t)v < (uint32_t)n; }
+
+__global__ void __launch_bounds__(BS_THREADS) bootstrap_regression_walk_kernel(
+    uint32_t* cp_all, uint32_t* ct_all, size_t pitch, const int32_t* __restrict__ first_p, const int32_t* __restrict__ last_p,
+    const int32_t* __restrict__ cross, const int32_t* __restrict__ first_t, const int32_t* __restrict__ last_t,
+    const double* __restrict__ p_sorted, const double* __restrict__ t_by_prank, const double* __restrict__ centre,
+    const int32_t* __restrict__ cuts, int J, int n, double* __restrict__ mom, int64_t* __restrict__ rank_sums,
+    int64_t* __restrict__ hits, int32_t* __restrict__ n_drawn) {
+    __shared__ RegLds L;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, b = blockIdx.x;
+    uint32_t* const Cp = cp_all + (size_t)b * pitch;
+    uint32_t* const Ct = ct_all + (size_t)b * pitch;
+    const double cen_p = centre[0], cen_t = centre[1];
+    // sweep 1
+    double msum[BS_REG_MOM] = {};                    // (every thread carries the same values)
+    uint32_t carry = 0;
+    int parity = 0;
+    for (int base = 0; base < n; base += BS_TILE, parity ^= 1) {
+        const int r0 = base + t * BS_PER;
+        uint32_t c[BS_PER] = {0u, 0u, 0u, 0u};
+        if (r0 < n) {                                // (a row is ceil4(n) words, r0 a multiple of 4; the padding was cleared)
+            const uint4 v = *(const uint4*)(Cp + r0);
+            c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w;
+        }
+        double m4[BS_REG_MOM] = {};
+#pragma unroll
+        for (int k = 0; k < BS_PER; ++k) {
+            // (the loads do not wait for c: a rank without a copy adds an exact 0.0, whatever its products are)
+            const int r = min(r0 + k, n - 1);
+            const bool live = r0 + k < n && c[k] > 0u;
+            const double pv = p_sorted[r], tv = t_by_prank[r], dp = pv - cen_p, dt = tv - cen_t, e = pv - tv, cw = (double)c[k];
+            m4[0] += live ? cw * dp : 0.0;
+            m4[1] += live ? cw * dt : 0.0;
+            m4[2] += live ? cw * (dp * dp) : 0.0;
+            m4[3] += live ? cw * (dt * dt) : 0.0;
+            m4[4] += live ? cw * (dp * dt) : 0.0;
+            m4[5] += live ? cw * fabs(e) : 0.0;
+            m4[6] += live ? cw * (e * e) : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < BS_REG_MOM; ++q) {
+            double d = m4[q];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) d += __longlong_as_double((long long)shfl_xor64((uint64_t)__double_as_longlong(d), o));
+            if (lane == 0) L.mslot[parity][q][w] = d;
+        }
+        uint64_t tile_sum;
+        uint32_t run = carry + (uint32_t)block_excl_sum((uint64_t)c[0] + c[1] + c[2] + c[3], L.slot, tile_sum);
+        if (r0 < n) {
+            uint4 v;
+            v.x = run += c[0]; v.y = run += c[1]; v.z = run += c[2]; v.w = run += c[3];
+            *(uint4*)(Cp + r0) = v;
+        }
+#pragma unroll
+        for (int q = 0; q < BS_REG_MOM; ++q) {
+            double d = 0.0;
+#pragma unroll
+            for (int u = 0; u < BS_NW; ++u) d += L.mslot[parity][q][u];
+            msum[q] += d;
+        }
+        carry += (uint32_t)tile_sum;
+    }
+    const int N = (int)carry;
+    __syncthreads();                                 // (Cp is whole before anyone gathers from it)
+    // sweep 2
+    carry = 0;
+    for (int base = 0; base < n; base += BS_TILE) {
+        const int r0 = base + t * BS_PER;
+        uint32_t c[BS_PER] = {0u, 0u, 0u, 0u};
+        if (r0 < n) {                                // (no branch between the loads: a thread's four gathers are in flight together)
+            int x[BS_PER];
+#pragma unroll
+            for (int k = 0; k < BS_PER; ++k) x[k] = cross[min(r0 + k, n - 1)];
+#pragma unroll
+            for (int k = 0; k < BS_PER; ++k) {
+                const bool ok = r0 + k < n && in_rows(x[k], n);
+                const int xs = ok ? x[k] : 0;
+                const uint32_t hi = Cp[xs], lo = Cp[max(xs - 1, 0)];
+                c[k] = ok ? hi - (xs > 0 ? lo : 0u) : 0u;
+            }
+        }
+        uint64_t tile_sum;
+        uint32_t run = carry + (uint32_t)block_excl_sum((uint64_t)c[0] + c[1] + c[2] + c[3], L.slot, tile_sum);
+        if (r0 < n) {
+            uint4 v;
+            v.x = run += c[0]; v.y = run += c[1]; v.z = run += c[2]; v.w = run += c[3];
+            *(uint4*)(Ct + r0) = v;
+        }
+        carry += (uint32_t)tile_sum;
+    }
+    __syncthreads();                                 // (Ct is whole)
+    // sweep 3
+    int cut[BS_MAX_CUTS];
+#pragma unroll
+    for (int j = 0; j < BS_MAX_CUTS; ++j) {
+        const int k = j < J ? cuts[j] : 0;
+        cut[j] = k >= 1 && k <= n ? k : 0;           // (0: no copy lies in front of it, the column's sum stays 0)
+    }
+    uint64_t acc[BS_REG_RANK] = {};
+    uint32_t hit[BS_MAX_CUTS] = {};                  // (a column's sum is at most its cut, <= n: 32 bits hold a thread's share)
+    for (int base = 0; base < n; base += BS_TILE) {
+        const int r0 = base + t * BS_PER;
+        if (r0 >= n) continue;
+        // no branch between the loads: the gathers of a thread's four rows are in flight together, and a row that is not drawn
+        // or has an index out of range reads rank 0 and counts with c = 0
+        const uint4 v = *(const uint4*)(Ct + r0);
+        const uint32_t incl[BS_PER] = {v.x, v.y, v.z, v.w};
+        const uint32_t front = Ct[max(r0 - 1, 0)];
+        int x[BS_PER], ft[BS_PER], lt[BS_PER], fp[BS_PER], lp[BS_PER];
+        bool ok[BS_PER];
+#pragma unroll
+        for (int k = 0; k < BS_PER; ++k) {
+            const int r = min(r0 + k, n - 1);
+            x[k] = cross[r];
+            ft[k] = first_t[r];
+            lt[k] = last_t[r];
+        }
+#pragma unroll
+        for (int k = 0; k < BS_PER; ++k) {
+            ok[k] = r0 + k < n && in_rows(x[k], n) && in_rows(ft[k], n) && in_rows(lt[k], n);
+            if (!ok[k]) x[k] = ft[k] = lt[k] = 0;
+            fp[k] = first_p[x[k]];
+            lp[k] = last_p[x[k]];
+        }
+        uint32_t cpx[BS_PER], cpf[BS_PER], cpl[BS_PER], ctf[BS_PER], ctl[BS_PER];
+#pragma unroll
+        for (int k = 0; k < BS_PER; ++k) {
+            if (!in_rows(fp[k], n) || !in_rows(lp[k], n)) {
+                ok[k] = false;
+                fp[k] = lp[k] = 0;
+            }
+            cpx[k] = Cp[x[k]];
+            cpf[k] = Cp[max(fp[k] - 1, 0)];
+            cpl[k] = Cp[lp[k]];
+            ctf[k] = Ct[max(ft[k] - 1, 0)];
+            ctl[k] = Ct[lt[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < BS_PER; ++k) {
+            const uint32_t before = k == 0 ? (r0 > 0 ? front : 0u) : incl[k - 1];
+            const int c = ok[k] ? (int)(incl[k] - before) : 0;
+            const int64_t a = (int64_t)(fp[k] > 0 ? cpf[k] : 0u) + (int64_t)cpl[k] - (int64_t)N;
+            const int64_t bb = (int64_t)(ft[k] > 0 ? ctf[k] : 0u) + (int64_t)ctl[k] - (int64_t)N;
+            const int64_t ca = (int64_t)c * a, cb = (int64_t)c * bb;
+            acc[0] += (uint64_t)(ca * bb);
+            acc[1] += (uint64_t)(ca * a);
+            acc[2] += (uint64_t)(cb * bb);
+            const int ep = (int)cpx[k] - c, et = (int)incl[k] - c;       // (the copies in front of the row's in the two orders)
+#pragma unroll
+            for (int j = 0; j < BS_MAX_CUTS; ++j)
+                hit[j] += (uint32_t)min(min(max(cut[j] - ep, 0), c), min(max(cut[j] - et, 0), c));
+        }
+    }
+    const auto wave_total = [&](uint64_t s, int q) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += shfl_xor64(s, o);
+        if (lane == 0) L.islot[q][w] = s;
+    };
+#pragma unroll
+    for (int q = 0; q < BS_REG_RANK; ++q) wave_total(acc[q], q);
+#pragma unroll
+    for (int j = 0; j < BS_MAX_CUTS; ++j)
+        if (j < J) wave_total((uint64_t)hit[j], BS_REG_RANK + j);       // (uniform)
+    __syncthreads();
+    if (t == 0) {
+#pragma unroll
+        for (int q = 0; q < BS_REG_MOM; ++q) mom[(size_t)b * BS_REG_MOM + q] = msum[q];
+#pragma unroll
+        for (int q = 0; q < BS_REG_INT; ++q) {
+            if (q < BS_REG_RANK + J) {
+                uint64_t s = 0;
+#pragma unroll
+                for (int u = 0; u < BS_NW; ++u) s += L.islot[q][u];
+                if (q < BS_REG_RANK)
+                    rank_sums[(size_t)b * BS_REG_RANK + q] = (int64_t)s;
+                else
+                    hits[(size_t)b * (size_t)J + (q - BS_REG_RANK)] = cut[q - BS_REG_RANK] != 0 ? (int64_t)s : (int64_t)-1;
+            }
+        }
+        n_drawn[b] = N;
+    }
+}
+
 inline size_t bs_pitch(int64_t n) { return (size_t)((n + 3) / 4 * 4); }      // words of one replicate's multiplicities
 inline bool bs_sizes_ok(int64_t n, int64_t reps) { return n >= 1 && n <= MKGNN_BOOTSTRAP_MAX_ROWS && reps >= 1 && reps <= MKGNN_BOOTSTRAP_MAX_REPLICATES; }
 
@@ -683,4 +891,65 @@ extern "C" int mkgnn_bootstrap_early(const int32_t* rank, const uint8_t* y_sorte
     const EarlyCall e = {cuts, J, alphas, A, ap, hits, rie};
     return bootstrap_run("mkgnn_bootstrap_early", &e, rank, y_sorted, group_last, n, split, B, seed, offset, lower, upper, auc, logauc,
                          two_u, n_pos, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t mkgnn_bootstrap_regression_workspace_bytes(int64_t n, int32_t replicates_per_pass) {
+    if (n < 1 || n > MKGNN_BOOTSTRAP_REG_MAX_ROWS || replicates_per_pass < 1 || replicates_per_pass > MKGNN_BOOTSTRAP_MAX_REPLICATES)
+        return 0;
+    return 2 * sizeof(uint32_t) * bs_pitch(n) * (size_t)replicates_per_pass;
+}
+
+extern "C" int mkgnn_bootstrap_regression(const int32_t* rank_p, const int32_t* first_p, const int32_t* last_p, const int32_t* cross,
+                                          const int32_t* first_t, const int32_t* last_t, const double* p_sorted,
+                                          const double* t_by_prank, const double* centre, const int32_t* cuts, int32_t J, int64_t n,
+                                          int32_t B, uint64_t seed, uint64_t offset, double* mom, int64_t* rank_sums, int64_t* hits,
+                                          int32_t* n_drawn, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* const who = "mkgnn_bootstrap_regression";
+    static_assert(MKGNN_BOOTSTRAP_REG_MAX_ROWS <= MKGNN_BOOTSTRAP_MAX_ROWS, "the draw launch is mkgnn_bootstrap_roc's");
+    if (n < 1 || n > MKGNN_BOOTSTRAP_REG_MAX_ROWS)
+        return api_fail("%s: %lld rows outside [1, %d]", who, (long long)n, MKGNN_BOOTSTRAP_REG_MAX_ROWS);
+    if (B < 1 || B > MKGNN_BOOTSTRAP_MAX_REPLICATES)
+        return api_fail("%s: %d replicates outside [1, %d]", who, (int)B, MKGNN_BOOTSTRAP_MAX_REPLICATES);
+    if (J < 0 || J > MKGNN_BOOTSTRAP_MAX_CUTS) return api_fail("%s: %d cuts outside [0, %d]", who, (int)J, MKGNN_BOOTSTRAP_MAX_CUTS);
+    if (!rank_p || !first_p || !last_p || !cross || !first_t || !last_t || !p_sorted || !t_by_prank || !centre || !mom || !rank_sums ||
+        !n_drawn || (J > 0 && (!cuts || !hits)))
+        return api_fail("%s: null pointer", who);
+    if ((((uintptr_t)rank_p | (uintptr_t)first_p | (uintptr_t)last_p | (uintptr_t)cross | (uintptr_t)first_t | (uintptr_t)last_t |
+          (uintptr_t)cuts | (uintptr_t)n_drawn) & 3) != 0 ||
+        (((uintptr_t)p_sorted | (uintptr_t)t_by_prank | (uintptr_t)centre | (uintptr_t)mom | (uintptr_t)rank_sums | (uintptr_t)hits) & 7) != 0)
+        return api_fail("%s: misaligned input or output", who);
+    if (!workspace) return api_fail("%s: null workspace", who);
+    if (((uintptr_t)workspace & 15) != 0) return api_fail("%s: workspace not 16-byte aligned", who);
+    const size_t pitch = bs_pitch(n), per = 2 * sizeof(uint32_t) * pitch;
+    const size_t fit = workspace_bytes / per;
+    if (fit < 1) return api_fail("%s: workspace of %zu bytes, %zu needed for one replicate", who, workspace_bytes, per);
+    const int per_pass = fit < (size_t)B ? (int)fit : (int)B;
+    const size_t rows4 = (size_t)n * 4, rows8 = (size_t)n * 8, Jz = (size_t)J;
+    const Span rd[10] = {{rank_p, rows4}, {first_p, rows4}, {last_p, rows4},     {cross, rows4}, {first_t, rows4},
+                         {last_t, rows4}, {p_sorted, rows8}, {t_by_prank, rows8}, {centre, 16},   {cuts, Jz * 4}};
+    const Span wr[5] = {{mom, (size_t)B * BS_REG_MOM * 8}, {rank_sums, (size_t)B * BS_REG_RANK * 8}, {hits, (size_t)B * Jz * 8},
+                        {n_drawn, (size_t)B * 4}, {workspace, per * (size_t)per_pass}};
+    if (spans_disjoint(who, wr, 5, rd, 10, "an output (mom, rank_sums, hits, n_drawn) or the workspace aliases an input",
+                       "the outputs (mom, rank_sums, hits, n_drawn) and the workspace alias each other"))
+        return 1;
+    const hipStream_t st = (hipStream_t)stream;
+    const int ni = (int)n;
+    uint32_t* const cp = (uint32_t*)workspace;       // the pass's Cp rows, then its Ct rows
+    uint32_t* const ct = cp + pitch * (size_t)per_pass;
+    const unsigned row_blocks = (unsigned)((n + BS_DRAW_ROWS - 1) / BS_DRAW_ROWS);
+    for (int b0 = 0; b0 < B; b0 += per_pass) {
+        const int nb = B - b0 < per_pass ? B - b0 : per_pass;
+        const size_t words16 = pitch / 4 * (size_t)nb;
+        // the shared clear and draw: the draw's count of "actives" is not used -- the first n bytes of p_sorted stand in for its
+        // labels and n_drawn for its counter, which the walk overwrites
+        bootstrap_clear_kernel<<<(unsigned)((words16 + BS_THREADS - 1) / BS_THREADS), BS_THREADS, 0, st>>>((uint4*)cp, words16,
+                                                                                                           n_drawn + b0, nb);
+        bootstrap_draw_kernel<<<dim3(row_blocks, (unsigned)nb), BS_THREADS, 0, st>>>(rank_p, (const uint8_t*)p_sorted, ni, ni, pitch, seed,
+                                                                                     offset + (uint64_t)b0, cp, n_drawn + b0);
+        bootstrap_regression_walk_kernel<<<(unsigned)nb, BS_THREADS, 0, st>>>(
+            cp, ct, pitch, first_p, last_p, cross, first_t, last_t, p_sorted, t_by_prank, centre, cuts, J, ni,
+            mom + (size_t)b0 * BS_REG_MOM, rank_sums + (size_t)b0 * BS_REG_RANK, hits + (size_t)b0 * Jz, n_drawn + b0);
+    }
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? 0 : api_hip_fail(who, err);
 }

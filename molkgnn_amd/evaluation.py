@@ -758,3 +758,368 @@ def bootstrap_per_task(true_y, pred_y, task, num_tasks: int, n_boot: int = 1000,
         out.append(bootstrap_metrics(yk, s[rows], n_boot, FPR_range, confidence, seed, int(offset) + k * int(n_boot), stratified,
                                      early))
     return out
+
+
+# ---- regression: MAE, R2, Pearson, Spearman, top-fraction recall, and the bootstrap of all of them with RMSE ----
+# Both vectors are sorted ONCE, best first.  A replicate is the SAME vector of multiplicities the unstratified classification
+# bootstrap draws, and everything a metric needs is a sum over the rows of a function of the row, its multiplicity and the prefix
+# sums of the multiplicities in the two orders: seven float64 moments, three exact integer rank sums (Spearman by midranks) and
+# one exact integer per top-k cut.  regression_reference is the definition in numpy; CUDA inputs take mkgnn_bootstrap_regression
+# (readout.bootstrap_regression); regression_derived turns the sums into the metrics on either route.
+
+BOOTSTRAP_REG_MAX_ROWS = 1 << 20                 # (MKGNN_BOOTSTRAP_REG_MAX_ROWS: sum c a^2 <= n (n - 1)^2 < 2^63 up to here)
+REGRESSION_METRICS = ("RMSE", "MAE", "R2", "pearson", "spearman")
+REGRESSION_SMALLER_IS_BETTER = ("RMSE", "MAE")
+
+
+def top_name(fraction: float) -> str:
+    """The name of the top-fraction recall at ``fraction``: ``'top_' + repr(float(fraction))``, e.g. ``'top_0.01'``."""
+    return "top_" + repr(_check_fraction(fraction))
+
+
+def parse_top_name(name) -> float:
+    """The fraction of ``'top_<fraction>'`` (``0 < fraction <= 1``); anything else raises ``ValueError``."""
+    if isinstance(name, str) and name.startswith("top_"):
+        try:
+            value = float(name[4:])
+        except ValueError:
+            raise ValueError(f"top-fraction recall {name!r}: 'top_<number>' is required") from None
+        return _check_fraction(value)
+    raise ValueError(f"unknown top-fraction recall {name!r}: 'top_<fraction>'")
+
+
+def is_top_name(name) -> bool:
+    """Whether ``name`` spells a top-fraction recall (a ``'top_'`` name with a bad number raises)."""
+    return isinstance(name, str) and name.startswith("top_") and parse_top_name(name) > 0.0
+
+
+def _regression_vectors(true_y, pred) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(t, p)`` as detached float64 vectors on the predictions' device."""
+    p = torch.as_tensor(pred).detach().reshape(-1).to(torch.float64)
+    t = torch.as_tensor(true_y).detach().reshape(-1).to(device=p.device, dtype=torch.float64)
+    if t.numel() != p.numel():
+        raise ValueError("true_y and pred differ in length")
+    return t, p
+
+
+def _check_regression_sizes(n: int, n_boot: int, seed: int, offset: int) -> None:
+    if not 1 <= n <= BOOTSTRAP_REG_MAX_ROWS:
+        raise ValueError(f"the regression bootstrap takes 1 .. {BOOTSTRAP_REG_MAX_ROWS} rows, not {n}")
+    if n_boot < 1:
+        raise ValueError(f"n_boot = {n_boot}: at least one replicate")
+    if not (0 <= seed < 1 << 64 and 0 <= offset and offset + n_boot <= 1 << 64):
+        raise ValueError("seed and offset .. offset + n_boot - 1 are unsigned 64-bit values")
+
+
+def _check_cuts(cuts) -> list:
+    cuts = [int(k) for k in cuts]
+    if len(cuts) > BOOTSTRAP_MAX_CUTS:
+        raise ValueError(f"{len(cuts)} cuts, at most {BOOTSTRAP_MAX_CUTS} per call")
+    return cuts
+
+
+def _top_cuts(top, n: int):
+    """``(names, cuts)`` of the fractions ``top``: ``top_name`` and ``early_cut`` of each; at most ``BOOTSTRAP_MAX_CUTS`` distinct ones."""
+    if isinstance(top, (str, float, int)):
+        raise ValueError("top: a tuple of fractions")
+    fractions = []
+    for f in top:
+        f = _check_fraction(f)
+        if f not in fractions:
+            fractions.append(f)
+    if len(fractions) > BOOTSTRAP_MAX_CUTS:
+        raise ValueError(f"top: {len(fractions)} distinct fractions, at most {BOOTSTRAP_MAX_CUTS} per call")
+    return [top_name(f) for f in fractions], [early_cut(f, n) for f in fractions]
+
+
+def _tie_ends_numpy(v):
+    """``(first, last)`` by rank of a sorted numpy vector: the ends of the maximal run of equal values every rank lies in."""
+    import numpy as np
+    n = v.size
+    change = v[1:] != v[:-1]
+    idx = np.arange(n)
+    first = np.maximum.accumulate(np.where(np.concatenate([[True], change]), idx, 0))
+    last = np.minimum.accumulate(np.where(np.concatenate([change, [True]]), idx, n - 1)[::-1])[::-1]
+    return first.astype(np.int32), last.astype(np.int32)
+
+
+def regression_reference_inputs(true_y, pred, lower_is_better: bool = True):
+    """The arguments of ``regression_reference_sorted`` (and of ``mkgnn_bootstrap_regression``) in numpy, by numpy's stable sorts:
+    ``(rank_p, first_p, last_p, cross, first_t, last_t, p_sorted, t_by_prank, centre)``.  Best first is ascending with
+    ``lower_is_better``, descending (the stable sort of the negated values) otherwise, for both vectors; ``centre`` is ``(mean p,
+    mean t)``.  A NaN or an infinite value raises ``ValueError``."""
+    import numpy as np
+    t_t, p_t = _regression_vectors(true_y, pred)
+    t, p = t_t.cpu().numpy(), p_t.cpu().numpy()
+    n = p.size
+    if not 1 <= n <= BOOTSTRAP_REG_MAX_ROWS:
+        raise ValueError(f"the regression bootstrap takes 1 .. {BOOTSTRAP_REG_MAX_ROWS} rows, not {n}")
+    if not (np.isfinite(p).all() and np.isfinite(t).all()):
+        raise ValueError("true_y or pred holds a NaN or an infinite value")
+    order_p = np.argsort(p if lower_is_better else -p, kind="stable")
+    order_t = np.argsort(t if lower_is_better else -t, kind="stable")
+    rank_p = np.empty(n, dtype=np.int32)
+    rank_p[order_p] = np.arange(n, dtype=np.int32)
+    first_p, last_p = _tie_ends_numpy(p[order_p])
+    first_t, last_t = _tie_ends_numpy(t[order_t])
+    return (rank_p, first_p, last_p, rank_p[order_t], first_t, last_t, p[order_p], t[order_p],
+            np.array([p.mean(), t.mean()], dtype=np.float64))
+
+
+def regression_reference_sorted(rank_p, first_p, last_p, cross, first_t, last_t, p_sorted, t_by_prank, centre, cuts, n_boot: int,
+                                seed: int = 0, offset: int = 0) -> dict:
+    """The definition of the regression bootstrap's raw sums behind the two sorts -- the host form of ``readout.bootstrap_regression``
+    / ``mkgnn_bootstrap_regression``, with the same arguments as numpy arrays: ``{'mom': float64 [B, 7], 'rank_sums': int64 [B, 3],
+    'hits': int64 [B, J], 'n_drawn': int32 [B]}`` and, for error bounds, ``'mom_abs'`` (``sum c |term|`` per column) and ``'n_terms'``
+    (the ranks with ``c > 0``).
+
+    Replicate ``b`` draws ``bootstrap_draw(n, n, seed, offset + b)`` -- the unstratified classification bootstrap's rows -- and ``c``
+    counts them by prediction rank (``rank_p`` of the drawn row; one outside ``[0, n)`` is not drawn).  ``Cp`` is the inclusive prefix
+    sum of ``c`` over the prediction ranks, ``N = Cp[n - 1]`` (``n_drawn``); the multiplicity at truth rank ``r`` is that of prediction
+    rank ``cross[r]`` (0 where that is out of range) and ``Ct`` its inclusive prefix sum; ``Cp[-1] = Ct[-1] = 0``.
+
+    ``mom``: over the prediction ranks with ``c > 0``, ``float64(c) * term`` summed for the terms ``dp``, ``dt``, ``dp * dp``, ``dt * dt``,
+    ``dp * dt``, ``|p - t|`` and ``(p - t) * (p - t)``, with ``dp = p - centre[0]`` and ``dt = t - centre[1]``.
+
+    ``rank_sums``: ``sum c a b``, ``sum c a a``, ``sum c b b`` over the truth ranks ``r`` with ``x = cross[r]``, ``a = Cp[first_p[x] - 1] +
+    Cp[last_p[x]] - N`` (twice the row's midrank among the drawn copies in prediction order, less ``N + 1``) and ``b = Ct[first_t[r] - 1]
+    + Ct[last_t[r]] - N``, in int64.
+
+    ``hits[j]``: ``sum min(clamp(k_j - (Cp[x] - c), 0, c), clamp(k_j - (Ct[r] - c), 0, c))`` -- the drawn copies among the first ``k_j``
+    copies in both orders, copies ordered by (stable rank, copy number); ``-1`` for a cut outside ``[1, n]``.
+
+    A truth rank with ``first_*`` or ``last_*`` out of range enters neither ``rank_sums`` nor ``hits``."""
+    import numpy as np
+    ints = [np.asarray(a).astype(np.int64) for a in (rank_p, first_p, last_p, cross, first_t, last_t)]
+    rank_p, first_p, last_p, cross, first_t, last_t = ints
+    p = np.asarray(p_sorted, dtype=np.float64)
+    t = np.asarray(t_by_prank, dtype=np.float64)
+    centre = np.asarray(centre, dtype=np.float64).reshape(2)
+    n, B = rank_p.size, int(n_boot)
+    if any(a.size != n for a in ints) or p.size != n or t.size != n:
+        raise ValueError("the eight arrays differ in length")
+    _check_regression_sizes(n, B, int(seed), int(offset))
+    cuts = _check_cuts(cuts)
+    dp, dt, e = p - centre[0], t - centre[1], p - t
+    terms = np.stack([dp, dt, dp * dp, dt * dt, dp * dt, np.abs(e), e * e], axis=1)
+    inside = lambda a: (a >= 0) & (a < n)
+    x_ok = inside(cross)
+    x = np.where(x_ok, cross, 0)
+    ok = x_ok & inside(first_t) & inside(last_t) & inside(first_p[x]) & inside(last_p[x])
+    fp, lp = np.where(ok, first_p[x], 0), np.where(ok, last_p[x], 0)
+    ft, lt = np.where(ok, first_t, 0), np.where(ok, last_t, 0)
+    out = {"mom": np.empty((B, 7)), "rank_sums": np.empty((B, 3), dtype=np.int64), "hits": np.empty((B, len(cuts)), dtype=np.int64),
+           "n_drawn": np.empty(B, dtype=np.int32), "mom_abs": np.empty((B, 7)), "n_terms": np.empty(B, dtype=np.int64)}
+    for b in range(B):
+        drawn = rank_p[bootstrap_draw(n, n, int(seed), int(offset) + b)]
+        c = np.bincount(drawn[inside(drawn)], minlength=n).astype(np.int64)
+        live = c > 0
+        weighted = c[live].astype(np.float64)[:, None] * terms[live]
+        out["mom"][b], out["mom_abs"][b], out["n_terms"][b] = weighted.sum(axis=0), np.abs(weighted).sum(axis=0), int(live.sum())
+        Cp0 = np.concatenate([[0], np.cumsum(c)])                 # Cp0[i] = Cp[i - 1]
+        N = int(Cp0[-1])
+        ct = np.where(x_ok, c[x], 0)
+        Ct0 = np.concatenate([[0], np.cumsum(ct)])
+        cr = np.where(ok, ct, 0)
+        a = Cp0[fp] + Cp0[lp + 1] - N
+        bb = Ct0[ft] + Ct0[lt + 1] - N
+        out["rank_sums"][b] = int(np.sum(cr * a * bb)), int(np.sum(cr * a * a)), int(np.sum(cr * bb * bb))
+        ep, et = Cp0[x + 1] - ct, Ct0[1:] - ct
+        for j, k in enumerate(cuts):
+            out["hits"][b, j] = int(np.sum(np.minimum(np.clip(k - ep, 0, cr), np.clip(k - et, 0, cr)))) if 1 <= k <= n else -1
+        out["n_drawn"][b] = N
+    return out
+
+
+def regression_reference(true_y, pred, n_boot: int, cuts=(), seed: int = 0, offset: int = 0, lower_is_better: bool = True) -> dict:
+    """``regression_reference_sorted`` of truths and predictions, prepared by ``regression_reference_inputs``; the result also holds the
+    ``centre`` used."""
+    inputs = regression_reference_inputs(true_y, pred, lower_is_better)
+    out = regression_reference_sorted(*inputs, cuts, int(n_boot), int(seed), int(offset))
+    out["centre"] = inputs[8]
+    return out
+
+
+def regression_derived(mom, rank_sums, hits, n_drawn, cuts, centre=None) -> dict:
+    """The metrics from the raw sums, on either route (float64 tensors on the sums' device): ``{'RMSE', 'MAE', 'R2', 'pearson',
+    'spearman': [B], 'top': [B, J]}`` from ``mom [B, 7]``, ``rank_sums [B, 3]`` (``xy``, ``xx``, ``yy``), ``hits [B, J]``, the drawn rows
+    ``n_drawn [B]`` (``N``) and the host values ``cuts``.  ``RMSE = sqrt(mom6 / N)``; ``MAE = mom5 / N``; with ``Sxx = mom2 - mom0^2 / N``,
+    ``Syy = mom3 - mom1^2 / N`` and ``Sxy = mom4 - mom0 mom1 / N``, ``pearson = Sxy / sqrt(Sxx Syy)`` (kept inside ``[-1, 1]``) and ``R2 = 1 -
+    mom6 / Syy``; ``spearman = xy / sqrt(float64(xx) float64(yy))``; ``top = hits / k``.  A variance that is not positive makes the metrics
+    that divide by it NaN -- and a vector is constant in a replicate exactly when its integer rank sum (``xx`` or ``yy``) is 0, which is
+    tested first, so rounding in the centred moments cannot turn a constant resample into a correlation.  A cut whose ``hits`` is
+    ``-1`` gives NaN.  The moments are centred sums, so the metrics do not depend on ``centre``; it is accepted for symmetry with the
+    operator's arguments."""
+    mom = torch.as_tensor(mom, dtype=torch.float64)
+    dev, B = mom.device, mom.shape[0]
+    rs = torch.as_tensor(rank_sums, device=dev).to(torch.int64).reshape(B, 3)
+    hits = torch.as_tensor(hits, device=dev).to(torch.int64).reshape(B, -1)
+    N = torch.as_tensor(n_drawn, device=dev).to(torch.float64).reshape(B)
+    k = torch.tensor([float(v) for v in cuts], dtype=torch.float64, device=dev).reshape(1, -1)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    m = [mom[:, q] for q in range(7)]
+    xy, xx, yy = rs[:, 0].to(torch.float64), rs[:, 1].to(torch.float64), rs[:, 2].to(torch.float64)
+    const_p, const_t = rs[:, 1] == 0, rs[:, 2] == 0
+    Sxx, Syy, Sxy = m[2] - m[0] * m[0] / N, m[3] - m[1] * m[1] / N, m[4] - m[0] * m[1] / N
+    bad_p, bad_t = const_p | ~(Sxx > 0), const_t | ~(Syy > 0)
+    return {"RMSE": torch.sqrt(m[6] / N), "MAE": m[5] / N, "R2": torch.where(bad_t, nan, 1.0 - m[6] / Syy),
+            "pearson": torch.where(bad_p | bad_t, nan, (Sxy / torch.sqrt(Sxx * Syy)).clamp(-1.0, 1.0)),
+            "spearman": torch.where(const_p | const_t, nan, xy / torch.sqrt(xx * yy)),
+            "top": torch.where(hits < 0, nan, hits.to(torch.float64) / k)}
+
+
+def _tie_ends(v: torch.Tensor):
+    """``(first, last)`` int32 by rank of a sorted vector, with two running extrema (no sort, no host read)."""
+    n, dev = v.numel(), v.device
+    idx = torch.arange(n, dtype=torch.int64, device=dev)
+    change = v[1:] != v[:-1]
+    one = torch.ones(1, dtype=torch.bool, device=dev)
+    first = torch.cummax(torch.where(torch.cat([one, change]), idx, torch.zeros_like(idx)), 0).values
+    ends = torch.where(torch.cat([change, one]), idx, torch.full_like(idx, n - 1))
+    last = torch.flip(torch.cummin(torch.flip(ends, [0]), 0).values, [0])
+    return first.to(torch.int32), last.to(torch.int32)
+
+
+def regression_prepare(true_y, pred, lower_is_better: bool = True):
+    """``(rank_p, first_p, last_p, cross, first_t, last_t, p_sorted, t_by_prank)`` for ``readout.bootstrap_regression`` from truths and
+    finite predictions on one device, with torch operators: TWO stable sorts (best first: ascending with ``lower_is_better``,
+    descending otherwise, the same for both), nothing else sorts, and nothing is read back to the host."""
+    t, p = _regression_vectors(true_y, pred)
+    n, dev = p.numel(), p.device
+    sp = torch.sort(p, descending=not lower_is_better, stable=True)
+    st = torch.sort(t, descending=not lower_is_better, stable=True)
+    rank_p = torch.empty(n, dtype=torch.int32, device=dev)
+    rank_p[sp.indices] = torch.arange(n, dtype=torch.int32, device=dev)
+    first_p, last_p = _tie_ends(sp.values)
+    first_t, last_t = _tie_ends(st.values)
+    return rank_p, first_p, last_p, rank_p[st.indices].contiguous(), first_t, last_t, sp.values.contiguous(), t[sp.indices].contiguous()
+
+
+def regression_points(true_y, pred, top=(), lower_is_better: bool = True) -> dict:
+    """``{'RMSE', 'MAE', 'R2', 'pearson', 'spearman', 'top_<f>' ..: float}`` on the full data: the definition's sums with every
+    multiplicity equal to 1, in torch operators on the predictions' device, through ``regression_derived``.  An undefined metric (a
+    constant vector) is NaN."""
+    t, p = _regression_vectors(true_y, pred)
+    n, dev = p.numel(), p.device
+    if n == 0:
+        raise ValueError("the regression metrics need at least one sample")
+    names, cuts = _top_cuts(top, n)
+    rank_p, first_p, last_p, cross, first_t, last_t, ps, ts = regression_prepare(t, p, lower_is_better)
+    dp, dt, e = ps - ps.mean(), ts - ts.mean(), ps - ts
+    mom = torch.stack([dp.sum(), dt.sum(), (dp * dp).sum(), (dt * dt).sum(), (dp * dt).sum(), e.abs().sum(), (e * e).sum()]).reshape(1, 7)
+    x = cross.long()
+    a = (first_p.long() + last_p.long() + 1 - n)[x]               # Cp[i] = i + 1
+    b = first_t.long() + last_t.long() + 1 - n
+    rank_sums = torch.stack([(a * b).sum(), (a * a).sum(), (b * b).sum()]).reshape(1, 3)
+    r = torch.arange(n, device=dev)
+    hits = torch.stack([((x < k) & (r < k)).sum() for k in cuts]).reshape(1, -1) if cuts else torch.zeros((1, 0), dtype=torch.int64, device=dev)
+    d = regression_derived(mom, rank_sums, hits, torch.tensor([n], device=dev), cuts)
+    out = {name: float(d[name][0]) for name in REGRESSION_METRICS}
+    out.update({name: float(d["top"][0, j]) for j, name in enumerate(names)})
+    return out
+
+
+def calculate_mae(true_y, pred) -> float:
+    """Mean absolute error, in float64 on the predictions' device."""
+    return regression_points(true_y, pred)["MAE"]
+
+
+def calculate_r2(true_y, pred) -> float:
+    """The coefficient of determination ``1 - sum (p - t)^2 / sum (t - mean t)^2`` (``sklearn.metrics.r2_score``); NaN for constant truths."""
+    return regression_points(true_y, pred)["R2"]
+
+
+def calculate_pearson(true_y, pred) -> float:
+    """Pearson's correlation of predictions and truths; NaN when either is constant."""
+    return regression_points(true_y, pred)["pearson"]
+
+
+def calculate_spearman(true_y, pred) -> float:
+    """Spearman's rank correlation with midranks for ties (``scipy.stats.spearmanr``); NaN when either vector is constant."""
+    return regression_points(true_y, pred)["spearman"]
+
+
+def calculate_top_recall(true_y, pred, fraction: float = 0.01, lower_is_better: bool = True) -> float:
+    """The share of the truly best ``k = early_cut(fraction, n)`` rows that are among the model's best ``k``, both taken best first by
+    a stable sort (ties between rows follow their order)."""
+    return regression_points(true_y, pred, (fraction,), lower_is_better)[top_name(fraction)]
+
+
+def _regression_sums(t: torch.Tensor, p: torch.Tensor, n_boot: int, seed: int, offset: int, cuts, lower_is_better: bool):
+    """``(mom, rank_sums, hits, n_drawn)`` tensors of ``n_boot`` replicates on the predictions' device: CUDA through two stable sorts and
+    ``readout.bootstrap_regression`` (at most ``BOOTSTRAP_MAX_REPLICATES`` per launch sequence), CPU through ``regression_reference``."""
+    n, B = p.numel(), int(n_boot)
+    _check_regression_sizes(n, B, int(seed), int(offset))
+    if not (bool(torch.isfinite(p).all()) and bool(torch.isfinite(t).all())):
+        raise ValueError("true_y or pred holds a NaN or an infinite value")
+    if not p.is_cuda:
+        ref = regression_reference(t, p, B, cuts, seed, offset, lower_is_better)
+        return tuple(torch.from_numpy(ref[k]) for k in ("mom", "rank_sums", "hits", "n_drawn"))
+    from . import _lib, readout
+    prepared = regression_prepare(t, p, lower_is_better)
+    centre = torch.stack([p.mean(), t.mean()])
+    cuts_t = torch.tensor(list(cuts), dtype=torch.int32).to(p.device)
+    parts = [readout.bootstrap_regression(*prepared, centre, cuts_t, min(_lib.BOOTSTRAP_MAX_REPLICATES, B - b0), seed, offset + b0)
+             for b0 in range(0, B, _lib.BOOTSTRAP_MAX_REPLICATES)]
+    return tuple(torch.cat([q[k] for q in parts]) if len(parts) > 1 else parts[0][k] for k in range(4))
+
+
+def _regression_replicates(true_y, pred, n_boot, seed, offset, top, lower_is_better):
+    """``({metric: [B]}, n_drawn [B], {top name: k})`` of one prediction vector."""
+    t, p = _regression_vectors(true_y, pred)
+    names, cuts = _top_cuts(top, max(1, p.numel()))
+    mom, rank_sums, hits, n_drawn = _regression_sums(t, p, n_boot, int(seed), int(offset), cuts, bool(lower_is_better))
+    d = regression_derived(mom, rank_sums, hits, n_drawn, cuts)
+    reps = {name: d[name] for name in REGRESSION_METRICS}
+    reps.update({name: d["top"][:, j] for j, name in enumerate(names)})
+    return reps, n_drawn, dict(zip(names, cuts))
+
+
+def bootstrap_regression(true_y, pred, n_boot: int = 1000, confidence: float = 0.95, seed: int = 0, offset: int = 0, top=(0.01,),
+                         lower_is_better: bool = True) -> dict:
+    """Non-parametric bootstrap of the regression metrics ``RMSE``, ``MAE``, ``R2``, ``pearson``, ``spearman`` and, per fraction in ``top``,
+    ``top_<fraction>`` (``top_name``: the share of the truly best ``k = early_cut(fraction, n)`` rows among the model's best ``k``; best is
+    lowest with ``lower_is_better``, highest otherwise; at most 8 distinct fractions): ``point`` (``regression_points`` on the full
+    data), ``replicates`` (``{metric: [B]}`` on the predictions' device; NaN where a resample makes the metric undefined -- a constant
+    vector), per metric ``mean``, ``std`` (unbiased) and the percentile interval ``ci`` over the defined replicates, ``n_undefined`` per
+    metric, ``cuts`` (every ``top_`` name's ``k``), ``n_drawn`` and the ``seed``, ``offset``, ``n_boot`` and ``confidence`` used (the call
+    consumes ``offset .. offset + n_boot - 1``).  The resamples are those of the unstratified ``bootstrap_metrics`` for the same
+    ``(seed, offset, n)``.  CUDA inputs are evaluated by ``mkgnn_bootstrap_regression`` behind two sorts, CPU inputs by
+    ``regression_reference``; the resamples are the same either way.  A NaN or infinite value, no row, or more than
+    ``BOOTSTRAP_REG_MAX_ROWS`` rows raises ``ValueError`` before any launch."""
+    _check_confidence(confidence)
+    reps, n_drawn, cuts = _regression_replicates(true_y, pred, n_boot, seed, offset, top, lower_is_better)
+    out = {"point": regression_points(true_y, pred, top, lower_is_better), "replicates": reps,
+           "n_undefined": {name: int(torch.isnan(v).sum()) for name, v in reps.items()}, "cuts": cuts, "n_drawn": n_drawn,
+           "seed": int(seed), "offset": int(offset), "n_boot": int(n_boot), "confidence": float(confidence),
+           "lower_is_better": bool(lower_is_better)}
+    for name, values in reps.items():
+        out[name] = _interval(values, confidence)
+    return out
+
+
+def bootstrap_regression_compare(true_y, pred_a, pred_b, n_boot: int = 1000, confidence: float = 0.95, seed: int = 0, offset: int = 0,
+                                 top=(0.01,), lower_is_better: bool = True) -> dict:
+    """The paired bootstrap of two prediction vectors on the same truths: both see the SAME resamples.  Per metric: ``diff`` (the
+    replicate differences ``a - b``, ``[B]``), their ``mean``, ``std`` and ``ci``, and ``p_a_better``, the share of defined replicates in
+    which ``a`` is the better one -- the smaller for ``RMSE`` and ``MAE``, the larger for the rest; also ``point`` (``a``, ``b`` and ``diff`` on
+    the full data), ``n_undefined`` per metric, ``cuts`` and the ``seed``, ``offset`` and ``n_boot`` used."""
+    _check_confidence(confidence)
+    a, drawn_a, cuts = _regression_replicates(true_y, pred_a, n_boot, seed, offset, top, lower_is_better)
+    b, drawn_b, _ = _regression_replicates(true_y, pred_b, n_boot, seed, offset, top, lower_is_better)
+    if not torch.equal(drawn_a.cpu(), drawn_b.cpu()):
+        raise RuntimeError("bootstrap_regression_compare: the two prediction vectors saw different resamples")
+    point_a = regression_points(true_y, pred_a, top, lower_is_better)
+    point_b = regression_points(true_y, pred_b, top, lower_is_better)
+    out = {"point": {"a": point_a, "b": point_b, "diff": {k: point_a[k] - point_b[k] for k in point_a}}, "n_undefined": {},
+           "cuts": cuts, "seed": int(seed), "offset": int(offset), "n_boot": int(n_boot)}
+    for name, va in a.items():
+        diff = va - b[name].to(va.device)
+        defined = diff[~torch.isnan(diff)]
+        better = defined < 0 if name in REGRESSION_SMALLER_IS_BETTER else defined > 0
+        entry = _interval(diff, confidence)
+        entry["diff"] = diff
+        entry["p_a_better"] = float(better.double().mean()) if defined.numel() else float("nan")
+        out[name] = entry
+        out["n_undefined"][name] = int(torch.isnan(diff).sum())
+    return out

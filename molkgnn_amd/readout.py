@@ -2592,3 +2592,76 @@ def bootstrap_early(rank: torch.Tensor, y_sorted: torch.Tensor, group_last: torc
                                              hits.data_ptr() if J else None, rie.data_ptr() if A else None, ws_ptr, ws_bytes,
                                              _lib.stream_ptr(dev)), "mkgnn_bootstrap_early")
     return auc, logauc, two_u, n_pos, ap, hits, rie
+
+
+def bootstrap_regression_replicates_per_pass(n: int, n_boot: int) -> int:
+    """The replicates ``bootstrap_regression`` keeps in flight when it sizes its own scratch: all ``n_boot`` where their two prefix-sum
+    rows fit under ``_lib.BOOTSTRAP_WORKSPACE_CAP`` bytes (``2 * 4 * ceil4(n)`` each), otherwise as many as do, at least one."""
+    per = 8 * ((int(n) + 3) // 4 * 4)
+    return max(1, min(int(n_boot), _lib.BOOTSTRAP_WORKSPACE_CAP // per))
+
+
+def bootstrap_regression(rank_p: torch.Tensor, first_p: torch.Tensor, last_p: torch.Tensor, cross: torch.Tensor, first_t: torch.Tensor,
+                         last_t: torch.Tensor, p_sorted: torch.Tensor, t_by_prank: torch.Tensor, centre: torch.Tensor, cuts, n_boot: int,
+                         seed: int, offset: int, workspace: Optional[torch.Tensor] = None):
+    """``(mom float64 [n_boot, 7], rank_sums int64 [n_boot, 3], hits int64 [n_boot, J], n_drawn int32 [n_boot])``: the raw sums of the
+    regression metrics of ``n_boot`` bootstrap replicates of ``n`` rows whose predictions and truths were each sorted ONCE (best
+    first, stable; ``evaluation.regression_prepare`` builds the arguments) -- ``rank_p int32 [n]`` the prediction rank of row ``i``,
+    ``first_p`` / ``last_p int32 [n]`` the ends of every prediction rank's tie group, ``cross int32 [n]`` the prediction rank of the row
+    at every truth rank, ``first_t`` / ``last_t`` the tie groups by truth rank, ``p_sorted`` / ``t_by_prank float64 [n]`` the two values
+    by prediction rank, ``centre float64 [2]`` the values the moments are centred on, all contiguous CUDA tensors; ``cuts``: up to
+    ``_lib.BOOTSTRAP_MAX_CUTS`` top-k sizes ``1 <= k <= n`` (an int32 device tensor, or a sequence).  Replicate ``b`` draws as the
+    unstratified ``bootstrap_roc`` does, with ``philox_word(seed, offset + b, i)``.  ``evaluation.regression_reference_sorted`` is the
+    definition: ``rank_sums``, ``hits`` and ``n_drawn`` agree with it exactly, ``mom`` within the rounding of a float64 sum; a cut outside
+    ``[1, n]`` gives a column of ``-1`` and changes nothing else; ``evaluation.regression_derived`` turns the sums into RMSE, MAE, R2,
+    Pearson, Spearman and top-fraction recall.  One ``mkgnn_bootstrap_regression``: no sort, no host round trip, capturable (``centre``
+    and a ``cuts`` tensor are re-read by a replay); a replicate's outputs do not depend on ``n_boot``, on where the replicates start
+    or on the scratch's size.  ``workspace``: a uint8 device tensor to use as scratch, at least
+    ``mkgnn_bootstrap_regression_workspace_bytes(n, 1)`` bytes -- the call passes over the replicates as many at a time as it holds;
+    without it a per-device buffer that only grows serves eager calls (sized for ``bootstrap_regression_replicates_per_pass``), and a
+    call inside a capture allocates its own.  At most ``_lib.BOOTSTRAP_REG_MAX_ROWS`` rows; there is no fallback beyond.  It has no
+    autograd node: called where a gradient is being recorded for one of its inputs it raises."""
+    who = "bootstrap_regression"
+    ints, reals = (rank_p, first_p, last_p, cross, first_t, last_t), (p_sorted, t_by_prank)
+    if not all(torch.is_tensor(x) and x.dim() == 1 for x in ints + reals) or any(x.dtype != torch.int32 for x in ints) \
+            or any(x.dtype != torch.float64 for x in reals) or len({x.numel() for x in ints + reals}) != 1:
+        raise ValueError(f"{who} needs rank_p, first_p, last_p, cross, first_t, last_t int32 [n] and p_sorted, t_by_prank float64 [n]")
+    dev = rank_p.device
+    if not rank_p.is_cuda or any(x.device != dev for x in ints + reals):
+        raise ValueError(f"{who} runs on the GPU: rank_p is on {dev} and the other arrays on {sorted({str(x.device) for x in ints + reals})} "
+                         f"(there is no CPU path; evaluation.regression_reference_sorted is the host form)")
+    if not torch.is_tensor(centre) or centre.dtype != torch.float64 or centre.numel() != 2 or centre.device != dev \
+            or not centre.is_contiguous():
+        raise ValueError(f"{who}: centre is a contiguous float64 tensor of two values on {dev}")
+    if torch.is_grad_enabled() and any(x.requires_grad for x in reals + (centre,)):
+        raise RuntimeError(f"{who} is forward only: call it under torch.no_grad() (or on detached inputs)")
+    n, B, seed, offset = rank_p.numel(), int(n_boot), int(seed), int(offset)
+    if not 1 <= n <= _lib.BOOTSTRAP_REG_MAX_ROWS:
+        raise ValueError(f"{who}: {n} rows outside [1, {_lib.BOOTSTRAP_REG_MAX_ROWS}]")
+    if not 1 <= B <= _lib.BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"{who}: n_boot = {n_boot} outside [1, {_lib.BOOTSTRAP_MAX_REPLICATES}] per call")
+    if not (0 <= seed < 1 << 64 and 0 <= offset and offset + B <= 1 << 64):
+        raise ValueError(f"{who}: seed and offset .. offset + n_boot - 1 are unsigned 64-bit values")
+    if not all(x.is_contiguous() for x in ints + reals):
+        raise ValueError(f"{who} needs contiguous tensors")
+    cuts = _early_vector(who, "cuts", cuts, torch.int32, _lib.BOOTSTRAP_MAX_CUTS, dev)
+    J = cuts.numel()
+    mom = torch.empty((B, 7), dtype=torch.float64, device=dev)
+    rank_sums = torch.empty((B, 3), dtype=torch.int64, device=dev)
+    hits = torch.empty((B, J), dtype=torch.int64, device=dev)
+    n_drawn = torch.empty(B, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    one = int(lib.mkgnn_bootstrap_regression_workspace_bytes(n, 1))
+    if workspace is not None and workspace.numel() < one:
+        raise ValueError(f"workspace: at least {one} bytes (one replicate)")
+    want = workspace.numel() if workspace is not None else \
+        int(lib.mkgnn_bootstrap_regression_workspace_bytes(n, bootstrap_regression_replicates_per_pass(n, B)))
+    ws = _max_cosine_workspace(dev, want, workspace)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkgnn_bootstrap_regression(rank_p.data_ptr(), first_p.data_ptr(), last_p.data_ptr(), cross.data_ptr(),
+                                                  first_t.data_ptr(), last_t.data_ptr(), p_sorted.data_ptr(), t_by_prank.data_ptr(),
+                                                  centre.data_ptr(), cuts.data_ptr() if J else None, J, n, B, seed, offset,
+                                                  mom.data_ptr(), rank_sums.data_ptr(), hits.data_ptr() if J else None,
+                                                  n_drawn.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
+                   "mkgnn_bootstrap_regression")
+    return mom, rank_sums, hits, n_drawn

@@ -441,21 +441,48 @@ def _early_metric(name):
     return lambda true_y, pred_y: E.calculate_bedroc(true_y, pred_y, value)
 
 
-def _check_metrics(metrics) -> dict:
-    """``_metric_functions()`` and the early-recognition names among ``metrics``, once every name in ``metrics`` is known to be one
-    of them."""
+def _regression_metric(name, lower_is_better: bool = True):
+    """``f(true_y, pred_y)`` for a regression name beyond ``'RMSE'`` (``'MAE'``, ``'R2'``, ``'pearson'``, ``'spearman'``,
+    ``'top_<fraction>'``), ``None`` for any other name; a malformed ``'top_'`` name raises ``ValueError``."""
+    from . import evaluation as E
+    plain = {'MAE': E.calculate_mae, 'R2': E.calculate_r2, 'pearson': E.calculate_pearson, 'spearman': E.calculate_spearman}
+    if isinstance(name, str) and name in plain:
+        return plain[name]
+    if not E.is_top_name(name):
+        return None
+    fraction = E.parse_top_name(name)
+    return lambda true_y, pred_y: E.calculate_top_recall(true_y, pred_y, fraction, lower_is_better)
+
+
+def _check_metrics(metrics, lower_is_better: bool = True) -> dict:
+    """``_metric_functions()`` and the early-recognition and regression names among ``metrics``, once every name in ``metrics`` is
+    known to be one of them."""
     table = _metric_functions()
     for m in metrics:
         if m not in table:
-            fn = _early_metric(m)
+            fn = _early_metric(m) or _regression_metric(m, lower_is_better)
             if fn is not None:
                 table[m] = fn
     unknown = [m for m in metrics if m not in table]
     if unknown:
         raise ValueError(f"unknown metric(s) {unknown}: one of {sorted(_metric_functions())}, 'AP', 'EF_<fraction>' or "
-                         f"'BEDROC_<alpha>'")
+                         f"'BEDROC_<alpha>', or the regression metrics 'MAE', 'R2', 'pearson', 'spearman' or 'top_<fraction>'")
     _early_names(metrics)
+    _top_fractions(metrics)
     return table
+
+
+def _top_fractions(metrics) -> tuple:
+    """The distinct fractions of the ``'top_<fraction>'`` names among ``metrics``, which the evaluate functions hand to the regression
+    bootstrap (too many: refused before anything is launched)."""
+    from .evaluation import BOOTSTRAP_MAX_CUTS, is_top_name, parse_top_name
+    fractions = []
+    for m in metrics:
+        if is_top_name(m) and parse_top_name(m) not in fractions:
+            fractions.append(parse_top_name(m))
+    if len(fractions) > BOOTSTRAP_MAX_CUTS:
+        raise ValueError(f"{len(fractions)} distinct top fractions, at most {BOOTSTRAP_MAX_CUTS} per call")
+    return tuple(fractions)
 
 
 def _early_names(metrics) -> tuple:
@@ -495,22 +522,30 @@ def _check_bootstrap(bootstrap) -> Optional[int]:
     return bootstrap
 
 
-def _results(model, pred_y: torch.Tensor, true_y: torch.Tensor, metrics, table: dict, bootstrap: Optional[int] = None) -> dict:
+def _results(model, pred_y: torch.Tensor, true_y: torch.Tensor, metrics, table: dict, bootstrap: Optional[int] = None,
+             lower_is_better: bool = True) -> dict:
     """The second half of ``evaluate`` and of ``evaluate_resident``: ``validation_epoch_end`` + ``get_evaluations`` on the whole
     vectors -- the model's loss, every metric, and the two vectors themselves; with ``bootstrap`` replicates also
-    ``evaluation.bootstrap_metrics`` of them (``results['bootstrap']``)."""
+    ``evaluation.bootstrap_metrics`` of them (``results['bootstrap']``), or, for a model that trains a squared error (``_loss_kind()``
+    ``'mse'`` or ``'mse_sum'``), ``evaluation.bootstrap_regression``."""
     with torch.no_grad():
         results = {'loss': model.loss_func(pred_y, true_y.float())}
     for m in metrics:
         results[m] = table[m](true_y, pred_y)
     if bootstrap is not None:
-        from .evaluation import bootstrap_metrics
-        results['bootstrap'] = bootstrap_metrics(true_y, pred_y.detach(), n_boot=bootstrap, early=_early_names(metrics))
+        kind = getattr(model, '_loss_kind', None)
+        if kind is not None and kind() in ('mse', 'mse_sum'):
+            from .evaluation import bootstrap_regression
+            results['bootstrap'] = bootstrap_regression(true_y, pred_y.detach(), n_boot=bootstrap, top=_top_fractions(metrics),
+                                                        lower_is_better=lower_is_better)
+        else:
+            from .evaluation import bootstrap_metrics
+            results['bootstrap'] = bootstrap_metrics(true_y, pred_y.detach(), n_boot=bootstrap, early=_early_names(metrics))
     results['pred_y'], results['true_y'] = pred_y, true_y
     return results
 
 
-def evaluate(model, batches, metrics=(), bootstrap: Optional[int] = None) -> dict:
+def evaluate(model, batches, metrics=(), bootstrap: Optional[int] = None, lower_is_better: bool = True) -> dict:
     """The reference's validation / test loop without Lightning: ``validation_step`` per batch (``model.py:221-244``:
     ``pred_y = self(batch)[0].view(-1)``, ``true_y = batch.y.view(-1)``), then ``validation_epoch_end`` + ``get_evaluations``
     (``model.py:246-296, 483-522``) on the concatenated vectors: ``loss = model.loss_func(all_pred, all_true.float())`` and
@@ -528,8 +563,15 @@ def evaluate(model, batches, metrics=(), bootstrap: Optional[int] = None) -> dic
 
     ``metrics`` also takes the early-recognition names ``'AP'``, ``'EF_<fraction>'`` and ``'BEDROC_<alpha>'`` (``evaluation.
     calculate_average_precision``, ``calculate_enrichment_factor``, ``calculate_bedroc``); with ``bootstrap`` those named are handed on as
-    ``bootstrap_metrics(..., early=...)`` and get their intervals from the same resamples.  A call that names none behaves as before."""
-    table = _check_metrics(metrics)
+    ``bootstrap_metrics(..., early=...)`` and get their intervals from the same resamples.  A call that names none behaves as before.
+
+    The regression names ``'MAE'``, ``'R2'``, ``'pearson'``, ``'spearman'`` and ``'top_<fraction>'`` (``evaluation.calculate_mae``,
+    ``calculate_r2``, ``calculate_pearson``, ``calculate_spearman``, ``calculate_top_recall``) are taken too; ``lower_is_better`` (lower
+    docking scores are the better ones) is read by the ``'top_'`` names alone.  For a model whose loss is ``MSELoss`` (mean or sum)
+    ``bootstrap`` gives ``results['bootstrap'] = evaluation.bootstrap_regression(true_y, pred_y, n_boot=bootstrap, top=<the fractions
+    named>, lower_is_better=...)`` -- intervals for RMSE, MAE, R2, Pearson, Spearman and every named recall; a model with any other loss,
+    and a call that names none of these, behaves as before."""
+    table = _check_metrics(metrics, lower_is_better)
     bootstrap = _check_bootstrap(bootstrap)
     with evaluation_mode(model):
         all_pred, all_true = [], []
@@ -540,7 +582,7 @@ def evaluate(model, batches, metrics=(), bootstrap: Optional[int] = None) -> dic
             all_true.append(batch.y.view(-1)[:pred.shape[0]])
         if not all_pred:
             raise ValueError("evaluate needs at least one batch")
-        return _results(model, torch.cat(all_pred), torch.cat(all_true), metrics, table, bootstrap)
+        return _results(model, torch.cat(all_pred), torch.cat(all_true), metrics, table, bootstrap, lower_is_better)
 
 
 def _task_results(pred: torch.Tensor, true_y: torch.Tensor, task: torch.Tensor, T: int, kind: str, metrics, table: dict,
@@ -601,16 +643,17 @@ def evaluate_tasks(model, batches, metrics=(), num_tasks: Optional[int] = None, 
                              bootstrap)
 
 
-def evaluate_resident(model, resident, batch_size: int, metrics=(), bootstrap: Optional[int] = None) -> dict:
+def evaluate_resident(model, resident, batch_size: int, metrics=(), bootstrap: Optional[int] = None,
+                      lower_is_better: bool = True) -> dict:
     """``evaluate`` for a data set that lives in device memory (``shards.ResidentShard``): the same result dictionary, with
     ``pred_y`` from ``screening.score_resident`` -- every molecule of the shard in id order, the short tail included, from one
     captured graph -- and ``true_y`` from ``resident.y``.  Unknown metric names raise before anything is launched; the model
-    comes back in the mode it came in.  ``bootstrap``: as in ``evaluate``."""
+    comes back in the mode it came in.  ``bootstrap`` and ``lower_is_better``: as in ``evaluate``."""
     from .screening import score_resident
-    table = _check_metrics(metrics)
+    table = _check_metrics(metrics, lower_is_better)
     bootstrap = _check_bootstrap(bootstrap)
     pred_y = score_resident(model, resident, batch_size)
-    return _results(model, pred_y, resident.y.to(pred_y.device).view(-1), metrics, table, bootstrap)
+    return _results(model, pred_y, resident.y.to(pred_y.device).view(-1), metrics, table, bootstrap, lower_is_better)
 
 
 def evaluate_resident_tasks(model, resident, batch_size: int, metrics=(), bootstrap: Optional[int] = None) -> dict:
