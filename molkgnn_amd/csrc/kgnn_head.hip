@@ -326,6 +326,50 @@ __global__ void __launch_bounds__(256) head_fused_final_kernel(HeadArgs a, int n
 using namespace mkgnn;
 
 // ================================================================== C ABI ==========================
+enum { HEAD_FORWARD = 0, HEAD_BACKWARD = 1, HEAD_FUSED = 2 };
+
+// The one argument path of the ten entries below: the shape, pointer, stride, dropout and workspace checks of MODE, the HeadArgs
+// fill and MODE's two launches.  An argument an entry does not have arrives null / 0 and stays so in the kernels' struct.
+template <int MODE>
+static int head_run(const char* who, int32_t lk, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
+                    const float* weight, const float* bias, const float* target, float p, int64_t* rng_state,
+                    const int64_t* rng_used, const float* pred, float* loss, const float* grad_loss, float* grad_emb,
+                    int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
+    if (n_rows < 1 || H < 1 || emb_stride < H) return api_fail("%s: bad shape", who);
+    constexpr bool BWD = MODE == HEAD_BACKWARD;
+    if (!emb || !weight || !target || !pred || (BWD ? !grad_loss : !loss) || (MODE != HEAD_FORWARD && !grad_weight))
+        return api_fail("%s: null pointer", who);
+    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
+    if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, p);
+    if (p > 0.f && BWD && !rng_used) return api_fail("%s: dropout needs the forward's rng_used", who);
+    if (p > 0.f && !BWD && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
+    if (!ws || ws_bytes < mkgnn_bce_head_workspace_bytes(n_rows, H) || ((uintptr_t)ws & 3))
+        return api_fail("%s: workspace too small or misaligned", who);
+    HeadArgs a{};
+    a.partial = (float*)((char*)ws + 16);
+    a.emb = emb; a.es = emb_stride; a.B = n_rows; a.H = H; a.w = weight; a.b = bias; a.y = target;
+    a.pred = (float*)pred; a.loss = loss; a.gloss = grad_loss; a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
+    a.drop_p = p; a.rng = rng_state; a.rng_used = (int64_t*)rng_used;
+    const int nblk = (int)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS);
+    hipStream_t s = (hipStream_t)stream;
+    if (!with_loss_kind(lk, [&](auto K) {
+            constexpr int LK = decltype(K)::value;
+            if constexpr (MODE == HEAD_FUSED) {
+                head_fused_kernel<LK><<<nblk, 256, 0, s>>>(a);
+                head_fused_final_kernel<LK><<<1, 256, 0, s>>>(a, nblk);
+            } else if constexpr (MODE == HEAD_FORWARD) {
+                head_forward_kernel<LK><<<nblk, 256, 0, s>>>(a);
+                head_forward_final_kernel<LK><<<1, 256, 0, s>>>(a, nblk);
+            } else {
+                head_backward_kernel<LK><<<nblk, 256, 0, s>>>(a);
+                head_backward_final_kernel<<<1, 256, 0, s>>>(a, nblk);
+            }
+        }))
+        return api_fail("%s: unknown loss kind %d", who, (int)lk);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+}
+
 extern "C" {
 
 size_t mkgnn_bce_head_workspace_bytes(int64_t n_rows, int32_t H) {
@@ -333,157 +377,89 @@ size_t mkgnn_bce_head_workspace_bytes(int64_t n_rows, int32_t H) {
     return 16 + (size_t)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS) * (H + 2) * 4;
 }
 
-static int head_fused(const char* who, int32_t lk, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
-                      const float* weight, const float* bias, const float* target, float dropout_p, int64_t* rng_state,
-                      int64_t* rng_used, float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
-                      float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
-    if (n_rows < 1 || H < 1 || emb_stride < H) return api_fail("%s: bad shape", who);
-    if (!emb || !weight || !target || !pred || !loss || !grad_weight) return api_fail("%s: null pointer", who);
-    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
-    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, dropout_p);
-    if (dropout_p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
-    HeadArgs a{};
-    if (!ws || ws_bytes < mkgnn_bce_head_workspace_bytes(n_rows, H) || ((uintptr_t)ws & 3))
-        return api_fail("%s: workspace too small or misaligned", who);
-    a.partial = (float*)((char*)ws + 16);
-    a.emb = emb; a.es = emb_stride; a.B = n_rows; a.H = H; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss;
-    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
-    a.drop_p = dropout_p; a.rng = rng_state; a.rng_used = rng_used;
-    const int nblk = (int)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS);
-    if (!with_loss_kind(lk, [&](auto K) {
-            head_fused_kernel<decltype(K)::value><<<nblk, 256, 0, (hipStream_t)stream>>>(a);
-            head_fused_final_kernel<decltype(K)::value><<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
-        }))
-        return api_fail("%s: unknown loss kind %d", who, (int)lk);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail(who, e);
-}
-
 int mkgnn_bce_head_fused(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight, const float* bias,
                          const float* target, float dropout_p, int64_t* rng_state, int64_t* rng_used, float* pred, float* loss,
                          float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws,
                          size_t ws_bytes, void* stream) {
-    return head_fused("mkgnn_bce_head_fused", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target, dropout_p,
-                      rng_state, rng_used, pred, loss, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
+    return head_run<HEAD_FUSED>("mkgnn_bce_head_fused", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target,
+                                dropout_p, rng_state, rng_used, pred, loss, nullptr, grad_emb, grad_emb_stride, grad_weight,
+                                grad_bias, ws, ws_bytes, stream);
 }
 
 int mkgnn_head_loss_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
                           const float* bias, const float* target, float dropout_p, int64_t* rng_state, int64_t* rng_used,
                           float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
                           float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
-    return head_fused("mkgnn_head_loss_fused", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, dropout_p,
-                      rng_state, rng_used, pred, loss, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
-}
-
-static int head_ws(const char* who, int64_t n_rows, int32_t H, void* ws, size_t ws_bytes, HeadArgs& a) {
-    if (!ws || ws_bytes < mkgnn_bce_head_workspace_bytes(n_rows, H) || ((uintptr_t)ws & 3))
-        return api_fail("%s: workspace too small or misaligned", who);
-    a.partial = (float*)((char*)ws + 16);
-    return 0;
-}
-
-static int head_forward(const char* who, int32_t lk, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
-                        const float* weight, const float* bias, const float* target, float p, int64_t* rng_state,
-                        int64_t* rng_used, float* pred, float* loss, void* ws, size_t ws_bytes, void* stream) {
-    if (n_rows < 1 || H < 1 || emb_stride < H) return api_fail("%s: bad shape", who);
-    if (!emb || !weight || !target || !pred || !loss) return api_fail("%s: null pointer", who);
-    if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, p);
-    if (p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
-    HeadArgs a{};
-    if (int rc = head_ws(who, n_rows, H, ws, ws_bytes, a)) return rc;
-    a.emb = emb; a.es = emb_stride; a.B = n_rows; a.H = H; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss;
-    a.drop_p = p; a.rng = rng_state; a.rng_used = rng_used;
-    const int nblk = (int)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS);
-    if (!with_loss_kind(lk, [&](auto K) {
-            head_forward_kernel<decltype(K)::value><<<nblk, 256, 0, (hipStream_t)stream>>>(a);
-            head_forward_final_kernel<decltype(K)::value><<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
-        }))
-        return api_fail("%s: unknown loss kind %d", who, (int)lk);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail(who, e);
-}
-
-static int head_backward(const char* who, int32_t lk, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
-                         const float* weight, const float* target, const float* pred, const float* grad_loss, float p,
-                         const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias,
-                         void* ws, size_t ws_bytes, void* stream) {
-    if (n_rows < 1 || H < 1 || emb_stride < H) return api_fail("%s: bad shape", who);
-    if (!emb || !weight || !target || !pred || !grad_loss || !grad_weight) return api_fail("%s: null pointer", who);
-    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
-    if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, p);
-    if (p > 0.f && !rng_used) return api_fail("%s: dropout needs the forward's rng_used", who);
-    HeadArgs a{};
-    if (int rc = head_ws(who, n_rows, H, ws, ws_bytes, a)) return rc;
-    a.emb = emb; a.es = emb_stride; a.B = n_rows; a.H = H; a.w = weight; a.y = target; a.pred = (float*)pred;
-    a.gloss = grad_loss; a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
-    a.drop_p = p; a.rng_used = (int64_t*)rng_used;
-    const int nblk = (int)((n_rows + HEAD_ROWS - 1) / HEAD_ROWS);
-    if (!with_loss_kind(lk, [&](auto K) { head_backward_kernel<decltype(K)::value><<<nblk, 256, 0, (hipStream_t)stream>>>(a); }))
-        return api_fail("%s: unknown loss kind %d", who, (int)lk);
-    head_backward_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(a, nblk);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : api_hip_fail(who, e);
+    return head_run<HEAD_FUSED>("mkgnn_head_loss_fused", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, dropout_p,
+                                rng_state, rng_used, pred, loss, nullptr, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws,
+                                ws_bytes, stream);
 }
 
 int mkgnn_bce_head_forward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
                            const float* bias, const float* target, float* pred, float* loss, void* ws, size_t ws_bytes,
                            void* stream) {
-    return head_forward("mkgnn_bce_head_forward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target, 0.f,
-                        nullptr, nullptr, pred, loss, ws, ws_bytes, stream);
+    return head_run<HEAD_FORWARD>("mkgnn_bce_head_forward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target,
+                                  0.f, nullptr, nullptr, pred, loss, nullptr, nullptr, 0, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 int mkgnn_bce_head_backward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
                             const float* target, const float* pred, const float* grad_loss, float* grad_emb,
                             int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws, size_t ws_bytes,
                             void* stream) {
-    return head_backward("mkgnn_bce_head_backward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, target, pred,
-                         grad_loss, 0.f, nullptr, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
+    return head_run<HEAD_BACKWARD>("mkgnn_bce_head_backward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, nullptr,
+                                   target, 0.f, nullptr, nullptr, pred, nullptr, grad_loss, grad_emb, grad_emb_stride, grad_weight,
+                                   grad_bias, ws, ws_bytes, stream);
 }
 
 int mkgnn_bce_head_dropout_forward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
                                    const float* bias, const float* target, float dropout_p, int64_t* rng_state,
                                    int64_t* rng_used, float* pred, float* loss, void* ws, size_t ws_bytes, void* stream) {
-    return head_forward("mkgnn_bce_head_dropout_forward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias, target,
-                        dropout_p, rng_state, rng_used, pred, loss, ws, ws_bytes, stream);
+    return head_run<HEAD_FORWARD>("mkgnn_bce_head_dropout_forward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, bias,
+                                  target, dropout_p, rng_state, rng_used, pred, loss, nullptr, nullptr, 0, nullptr, nullptr, ws,
+                                  ws_bytes, stream);
 }
 
 int mkgnn_bce_head_dropout_backward(const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, const float* weight,
                                     const float* target, const float* pred, const float* grad_loss, float dropout_p,
                                     const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
                                     float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
-    return head_backward("mkgnn_bce_head_dropout_backward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight, target, pred,
-                         grad_loss, dropout_p, rng_used, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
+    return head_run<HEAD_BACKWARD>("mkgnn_bce_head_dropout_backward", MKGNN_LOSS_BCE_MEAN, emb, emb_stride, n_rows, H, weight,
+                                   nullptr, target, dropout_p, nullptr, rng_used, pred, nullptr, grad_loss, grad_emb,
+                                   grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
 }
 
 int mkgnn_head_loss_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
                             const float* weight, const float* bias, const float* target, float* pred, float* loss, void* ws,
                             size_t ws_bytes, void* stream) {
-    return head_forward("mkgnn_head_loss_forward", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, 0.f, nullptr,
-                        nullptr, pred, loss, ws, ws_bytes, stream);
+    return head_run<HEAD_FORWARD>("mkgnn_head_loss_forward", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, 0.f,
+                                  nullptr, nullptr, pred, loss, nullptr, nullptr, 0, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 int mkgnn_head_loss_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
                              const float* weight, const float* target, const float* pred, const float* grad_loss,
                              float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws,
                              size_t ws_bytes, void* stream) {
-    return head_backward("mkgnn_head_loss_backward", loss_kind, emb, emb_stride, n_rows, H, weight, target, pred, grad_loss, 0.f,
-                         nullptr, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
+    return head_run<HEAD_BACKWARD>("mkgnn_head_loss_backward", loss_kind, emb, emb_stride, n_rows, H, weight, nullptr, target, 0.f,
+                                   nullptr, nullptr, pred, nullptr, grad_loss, grad_emb, grad_emb_stride, grad_weight, grad_bias,
+                                   ws, ws_bytes, stream);
 }
 
 int mkgnn_head_loss_dropout_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
                                     const float* weight, const float* bias, const float* target, float dropout_p,
                                     int64_t* rng_state, int64_t* rng_used, float* pred, float* loss, void* ws, size_t ws_bytes,
                                     void* stream) {
-    return head_forward("mkgnn_head_loss_dropout_forward", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target, dropout_p,
-                        rng_state, rng_used, pred, loss, ws, ws_bytes, stream);
+    return head_run<HEAD_FORWARD>("mkgnn_head_loss_dropout_forward", loss_kind, emb, emb_stride, n_rows, H, weight, bias, target,
+                                  dropout_p, rng_state, rng_used, pred, loss, nullptr, nullptr, 0, nullptr, nullptr, ws, ws_bytes,
+                                  stream);
 }
 
 int mkgnn_head_loss_dropout_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H,
                                      const float* weight, const float* target, const float* pred, const float* grad_loss,
                                      float dropout_p, const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride,
                                      float* grad_weight, float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
-    return head_backward("mkgnn_head_loss_dropout_backward", loss_kind, emb, emb_stride, n_rows, H, weight, target, pred,
-                         grad_loss, dropout_p, rng_used, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
+    return head_run<HEAD_BACKWARD>("mkgnn_head_loss_dropout_backward", loss_kind, emb, emb_stride, n_rows, H, weight, nullptr,
+                                   target, dropout_p, nullptr, rng_used, pred, nullptr, grad_loss, grad_emb, grad_emb_stride,
+                                   grad_weight, grad_bias, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -264,24 +264,6 @@ using namespace mkgnn;
 // ================================================================== C ABI ==========================
 static int64_t task_head_blocks(int64_t n_rows) { return (n_rows + HEAD_ROWS - 1) / HEAD_ROWS; }
 
-static int task_head_check(const char* who, int64_t n_rows, int32_t H, int32_t T, int64_t emb_stride, const int32_t* task,
-                           const int32_t* row_ids, int64_t n_task, float p, void* ws, size_t ws_bytes, TaskHeadArgs& a,
-                           bool weighted = false) {
-    if (T < 1 || T > MKGNN_TASK_HEAD_MAX_TASKS) return api_fail("%s: %d tasks outside [1, %d]", who, (int)T, MKGNN_TASK_HEAD_MAX_TASKS);
-    if (H < 1 || H > TH_MAX_H) return api_fail("%s: embedding width %d outside [1, %d]", who, (int)H, TH_MAX_H);
-    if (n_rows < 1 || emb_stride < H || task_head_blocks(n_rows) > 0x7fffff00) return api_fail("%s: bad shape", who);
-    if (!task) {                                           // (the weighted entry points: every row has task 0)
-        if (!weighted) return api_fail("%s: null task", who);
-        if (T != 1 || row_ids) return api_fail("%s: a null task needs T == 1 and no row_ids (T = %d)", who, (int)T);
-    } else if (row_ids ? n_task < 1 : n_task < n_rows) return api_fail("%s: task holds %lld entries", who, (long long)n_task);
-    if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, p);
-    if (!ws || ws_bytes < mkgnn_task_head_workspace_bytes(n_rows, H, T) || ((uintptr_t)ws & 3))
-        return api_fail("%s: workspace too small or misaligned", who);
-    a.partial = (float*)((char*)ws + 16);
-    a.B = n_rows; a.H = H; a.T = T; a.es = emb_stride; a.task = task; a.row_ids = row_ids; a.n_task = n_task; a.drop_p = p;
-    return 0;
-}
-
 // the weighted entry points' extra arguments -> a; returns whether the weighted instantiation is needed (-1: refused).  No
 // weight and a task per row: the unweighted instantiation, so the unweighted entry point's bits.
 static int task_head_weights(const char* who, int32_t lk, const mkgnn_loss_weights* wt, TaskHeadArgs& a) {
@@ -322,6 +304,43 @@ static int task_head_launch(const char* who, int32_t lk, const TaskHeadArgs& a, 
     return e == hipSuccess ? 0 : api_hip_fail(who, e);
 }
 
+// The one argument path of the six entries below: the checks of MODE, the TaskHeadArgs fill, the optional weights and the launch.
+// An argument an entry does not have arrives null / 0 and stays so in the kernels' struct.  ``weighted_entry``: the
+// mkgnn_task_head_weighted_* entries, which take a null ``task`` (every row has task 0) and ``weights``.
+template <int MODE>
+static int task_head_run(const char* who, bool weighted_entry, const mkgnn_loss_weights* weights, int32_t lk, const float* emb,
+                         int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T, const float* weight, const float* bias,
+                         const float* target, const int32_t* task, const int32_t* row_ids, int64_t n_task, float p,
+                         int64_t* rng_state, const int64_t* rng_used, const float* pred, float* loss, const float* grad_loss,
+                         float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws, size_t ws_bytes,
+                         void* stream) {
+    if (T < 1 || T > MKGNN_TASK_HEAD_MAX_TASKS) return api_fail("%s: %d tasks outside [1, %d]", who, (int)T, MKGNN_TASK_HEAD_MAX_TASKS);
+    if (H < 1 || H > TH_MAX_H) return api_fail("%s: embedding width %d outside [1, %d]", who, (int)H, TH_MAX_H);
+    if (n_rows < 1 || emb_stride < H || task_head_blocks(n_rows) > 0x7fffff00) return api_fail("%s: bad shape", who);
+    if (!task) {                                           // (the weighted entry points: every row has task 0)
+        if (!weighted_entry) return api_fail("%s: null task", who);
+        if (T != 1 || row_ids) return api_fail("%s: a null task needs T == 1 and no row_ids (T = %d)", who, (int)T);
+    } else if (row_ids ? n_task < 1 : n_task < n_rows) return api_fail("%s: task holds %lld entries", who, (long long)n_task);
+    if (!(p >= 0.f && p < 1.f)) return api_fail("%s: dropout probability %g outside [0, 1)", who, p);
+    if (!ws || ws_bytes < mkgnn_task_head_workspace_bytes(n_rows, H, T) || ((uintptr_t)ws & 3))
+        return api_fail("%s: workspace too small or misaligned", who);
+    constexpr bool BWD = MODE == TH_BACKWARD;
+    if (!emb || !weight || !target || !pred || (BWD ? !grad_loss : !loss) || (MODE != TH_FORWARD && !grad_weight))
+        return api_fail("%s: null pointer", who);
+    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
+    if (p > 0.f && BWD && !rng_used) return api_fail("%s: dropout needs the forward's rng_used", who);
+    if (p > 0.f && !BWD && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
+    TaskHeadArgs a{};
+    a.partial = (float*)((char*)ws + 16);
+    a.B = n_rows; a.H = H; a.T = T; a.es = emb_stride; a.task = task; a.row_ids = row_ids; a.n_task = n_task; a.drop_p = p;
+    a.emb = emb; a.w = weight; a.b = bias; a.y = target; a.pred = (float*)pred; a.loss = loss; a.gloss = grad_loss;
+    a.rng = rng_state; a.rng_used = (int64_t*)rng_used;
+    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
+    const int wt = weighted_entry ? task_head_weights(who, lk, weights, a) : 0;
+    if (wt < 0) return 1;
+    return task_head_launch<MODE>(who, lk, a, stream, wt == 1);
+}
+
 extern "C" {
 
 size_t mkgnn_task_head_workspace_bytes(int64_t n_rows, int32_t H, int32_t T) {
@@ -333,13 +352,9 @@ int mkgnn_task_head_forward(int32_t loss_kind, const float* emb, int64_t emb_str
                             const float* weight, const float* bias, const float* target, const int32_t* task,
                             const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state, int64_t* rng_used,
                             float* pred, float* loss, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "mkgnn_task_head_forward";
-    TaskHeadArgs a{};
-    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a)) return rc;
-    if (!emb || !weight || !target || !pred || !loss) return api_fail("%s: null pointer", who);
-    if (dropout_p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
-    a.emb = emb; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss; a.rng = rng_state; a.rng_used = rng_used;
-    return task_head_launch<TH_FORWARD>(who, loss_kind, a, stream);
+    return task_head_run<TH_FORWARD>("mkgnn_task_head_forward", false, nullptr, loss_kind, emb, emb_stride, n_rows, H, T, weight,
+                                     bias, target, task, row_ids, n_task, dropout_p, rng_state, rng_used, pred, loss, nullptr,
+                                     nullptr, 0, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 int mkgnn_task_head_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
@@ -347,15 +362,9 @@ int mkgnn_task_head_backward(int32_t loss_kind, const float* emb, int64_t emb_st
                              int64_t n_task, const float* pred, const float* grad_loss, float dropout_p, const int64_t* rng_used,
                              float* grad_emb, int64_t grad_emb_stride, float* grad_weight, float* grad_bias, void* ws,
                              size_t ws_bytes, void* stream) {
-    const char* who = "mkgnn_task_head_backward";
-    TaskHeadArgs a{};
-    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a)) return rc;
-    if (!emb || !weight || !target || !pred || !grad_loss || !grad_weight) return api_fail("%s: null pointer", who);
-    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
-    if (dropout_p > 0.f && !rng_used) return api_fail("%s: dropout needs the forward's rng_used", who);
-    a.emb = emb; a.w = weight; a.y = target; a.pred = (float*)pred; a.gloss = grad_loss; a.rng_used = (int64_t*)rng_used;
-    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
-    return task_head_launch<TH_BACKWARD>(who, loss_kind, a, stream);
+    return task_head_run<TH_BACKWARD>("mkgnn_task_head_backward", false, nullptr, loss_kind, emb, emb_stride, n_rows, H, T, weight,
+                                      nullptr, target, task, row_ids, n_task, dropout_p, nullptr, rng_used, pred, nullptr,
+                                      grad_loss, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
 }
 
 int mkgnn_task_head_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
@@ -363,15 +372,9 @@ int mkgnn_task_head_fused(int32_t loss_kind, const float* emb, int64_t emb_strid
                           const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state, int64_t* rng_used,
                           float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
                           float* grad_bias, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "mkgnn_task_head_fused";
-    TaskHeadArgs a{};
-    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a)) return rc;
-    if (!emb || !weight || !target || !pred || !loss || !grad_weight) return api_fail("%s: null pointer", who);
-    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
-    if (dropout_p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
-    a.emb = emb; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss; a.rng = rng_state; a.rng_used = rng_used;
-    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
-    return task_head_launch<TH_FUSED>(who, loss_kind, a, stream);
+    return task_head_run<TH_FUSED>("mkgnn_task_head_fused", false, nullptr, loss_kind, emb, emb_stride, n_rows, H, T, weight, bias,
+                                   target, task, row_ids, n_task, dropout_p, rng_state, rng_used, pred, loss, nullptr, grad_emb,
+                                   grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
 }
 
 int mkgnn_task_head_weighted_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
@@ -379,15 +382,9 @@ int mkgnn_task_head_weighted_forward(int32_t loss_kind, const float* emb, int64_
                                      const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state,
                                      int64_t* rng_used, float* pred, float* loss, const mkgnn_loss_weights* weights, void* ws,
                                      size_t ws_bytes, void* stream) {
-    const char* who = "mkgnn_task_head_weighted_forward";
-    TaskHeadArgs a{};
-    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a, true)) return rc;
-    if (!emb || !weight || !target || !pred || !loss) return api_fail("%s: null pointer", who);
-    if (dropout_p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
-    const int wt = task_head_weights(who, loss_kind, weights, a);
-    if (wt < 0) return 1;
-    a.emb = emb; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss; a.rng = rng_state; a.rng_used = rng_used;
-    return task_head_launch<TH_FORWARD>(who, loss_kind, a, stream, wt == 1);
+    return task_head_run<TH_FORWARD>("mkgnn_task_head_weighted_forward", true, weights, loss_kind, emb, emb_stride, n_rows, H, T,
+                                     weight, bias, target, task, row_ids, n_task, dropout_p, rng_state, rng_used, pred, loss,
+                                     nullptr, nullptr, 0, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 int mkgnn_task_head_weighted_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
@@ -396,17 +393,9 @@ int mkgnn_task_head_weighted_backward(int32_t loss_kind, const float* emb, int64
                                       const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
                                       float* grad_bias, const mkgnn_loss_weights* weights, void* ws, size_t ws_bytes,
                                       void* stream) {
-    const char* who = "mkgnn_task_head_weighted_backward";
-    TaskHeadArgs a{};
-    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a, true)) return rc;
-    if (!emb || !weight || !target || !pred || !grad_loss || !grad_weight) return api_fail("%s: null pointer", who);
-    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
-    if (dropout_p > 0.f && !rng_used) return api_fail("%s: dropout needs the forward's rng_used", who);
-    const int wt = task_head_weights(who, loss_kind, weights, a);
-    if (wt < 0) return 1;
-    a.emb = emb; a.w = weight; a.y = target; a.pred = (float*)pred; a.gloss = grad_loss; a.rng_used = (int64_t*)rng_used;
-    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
-    return task_head_launch<TH_BACKWARD>(who, loss_kind, a, stream, wt == 1);
+    return task_head_run<TH_BACKWARD>("mkgnn_task_head_weighted_backward", true, weights, loss_kind, emb, emb_stride, n_rows, H, T,
+                                      weight, nullptr, target, task, row_ids, n_task, dropout_p, nullptr, rng_used, pred, nullptr,
+                                      grad_loss, grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
 }
 
 int mkgnn_task_head_weighted_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
@@ -414,17 +403,9 @@ int mkgnn_task_head_weighted_fused(int32_t loss_kind, const float* emb, int64_t 
                                    const int32_t* row_ids, int64_t n_task, float dropout_p, int64_t* rng_state, int64_t* rng_used,
                                    float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride, float* grad_weight,
                                    float* grad_bias, const mkgnn_loss_weights* weights, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "mkgnn_task_head_weighted_fused";
-    TaskHeadArgs a{};
-    if (int rc = task_head_check(who, n_rows, H, T, emb_stride, task, row_ids, n_task, dropout_p, ws, ws_bytes, a, true)) return rc;
-    if (!emb || !weight || !target || !pred || !loss || !grad_weight) return api_fail("%s: null pointer", who);
-    if (grad_emb && grad_emb_stride < H) return api_fail("%s: bad grad_emb stride", who);
-    if (dropout_p > 0.f && (!rng_state || !rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
-    const int wt = task_head_weights(who, loss_kind, weights, a);
-    if (wt < 0) return 1;
-    a.emb = emb; a.w = weight; a.b = bias; a.y = target; a.pred = pred; a.loss = loss; a.rng = rng_state; a.rng_used = rng_used;
-    a.gemb = grad_emb; a.ges = grad_emb_stride; a.gw = grad_weight; a.gb = grad_bias;
-    return task_head_launch<TH_FUSED>(who, loss_kind, a, stream, wt == 1);
+    return task_head_run<TH_FUSED>("mkgnn_task_head_weighted_fused", true, weights, loss_kind, emb, emb_stride, n_rows, H, T,
+                                   weight, bias, target, task, row_ids, n_task, dropout_p, rng_state, rng_used, pred, loss, nullptr,
+                                   grad_emb, grad_emb_stride, grad_weight, grad_bias, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -522,91 +522,124 @@ def loss_kind(loss: str) -> int:
     return LOSS_KINDS[loss]
 
 
-def _head_call(lib, name: str, kind: Optional[int], *args) -> None:
-    """``mkgnn_bce_head_<name>(*args)`` (kind None: the BCE entry points as they were), else ``mkgnn_head_loss_<name>(kind, *args)``."""
-    if kind is None:
-        _lib.check(getattr(lib, "mkgnn_bce_head_" + name)(*args), "mkgnn_bce_head_" + name)
-    else:
-        _lib.check(getattr(lib, "mkgnn_head_loss_" + name)(int(kind), *args), "mkgnn_head_loss_" + name)
+def _i32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    t = t.reshape(-1)
+    return t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
 
 
-class _BceHeadFn(torch.autograd.Function):
+def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    t = t.detach().reshape(-1)
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+class _HeadFnBase(torch.autograd.Function):
+    """The one forward (``_run``) and the one backward of the three head Functions: the fused entry (forward and the gradients for
+    d loss = 1 in the same two launches) when a gradient is needed, the split forward / backward entries otherwise, under
+    ``MKGNN_SPLIT_HEAD=1``, and for a second backward over a retained graph.  A subclass describes its entry-point family:
+    ``SYMS``, the C symbols of the fused / forward / backward entry; ``_weight(weight)``, the weight as the kernels read it, whose
+    shape is ``gw``'s -- ``[H]`` (``gb [1]``) for the single-task head, ``[T, H]`` (``gb [T]``) otherwise; ``_workspace_bytes``; and
+    ``_extra(w, vectors)``, the family's extra positional arguments ``(dims, index, tail)`` -- behind ``H``, behind the target,
+    ahead of the workspace -- from ``vectors``, the index / weight vectors its forward handed ``_run`` (``_i32`` / ``_f32``)."""
+    SYMS: tuple = ()
+
+    @classmethod
+    def _entries(cls, kind):
+        return cls.SYMS, (int(kind),)                    # (the symbols, the arguments ahead of ``emb``)
+
+    @classmethod
+    def _call(cls, which: int, kind, emb, B: int, w, vectors, mid_a: tuple, mid_b: tuple) -> None:
+        """``SYMS[which](lead, emb, stride, B, H, dims, w, *mid_a, index, *mid_b, tail, workspace, stream)``."""
+        lib, dev, H = _lib.load(), emb.device, emb.shape[1]
+        names, lead = cls._entries(kind)
+        dims, index, tail = cls._extra(w, vectors)
+        with torch.cuda.device(dev):
+            ws = _head_workspace(dev, int(cls._workspace_bytes(lib, B, H, w)))
+            _lib.check(getattr(lib, names[which])(*lead, emb.data_ptr(), _stride0(emb), B, H, *dims, w.data_ptr(), *mid_a, *index,
+                                                  *mid_b, *tail, ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), names[which])
+
     @staticmethod
-    def forward(ctx, emb, weight, bias, target, p_drop, n_rows, kind=None):
-        lib = _lib.load()
-        ctx.kind = kind
+    def _grads(ctx, emb, w):
+        """``(gemb, gw, gb)`` to be written and their arguments; rows beyond ``n_rows`` (padding molecules) get a zero gradient:
+        one small fill, only when there are any."""
+        H, dev = emb.shape[1], emb.device
+        gemb = None
+        if ctx.needs_input_grad[0]:
+            gemb = torch.empty((emb.shape[0], H), dtype=torch.float32, device=dev)
+            if emb.shape[0] > ctx.n_rows:
+                gemb[ctx.n_rows:].zero_()
+        gw = torch.empty(w.shape, dtype=torch.float32, device=dev)
+        gb = torch.empty(w.numel() // H, dtype=torch.float32, device=dev) if ctx.has_bias else None
+        return (gemb, gw, gb), (_lib.ptr(gemb), H, gw.data_ptr(), _lib.ptr(gb))
+
+    @classmethod
+    def _run(cls, ctx, emb, weight, bias, target, p_drop, n_rows, kind, vectors: tuple = ()):
         emb = _row_major(emb if emb.dtype == torch.float32 else emb.float())
-        ctx.rows_total = emb.shape[0]
-        B, H = int(n_rows), emb.shape[1]         # the leading n_rows rows enter the loss (the rest: padding molecules)
-        dev = emb.device
-        w = weight.reshape(-1).contiguous()
-        y = target.reshape(-1).float().contiguous()
+        w, y = cls._weight(weight), _f32(target)
+        B, dev = int(n_rows), emb.device                 # the leading n_rows rows enter the loss (the rest: padding molecules)
+        ctx.family, ctx.kind, ctx.n_rows = cls, kind, B
+        ctx.wshape, ctx.has_bias, ctx.p_drop = weight.shape, bias is not None, float(p_drop)
         pred = torch.empty(B, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         rng = head_rng_state(dev) if p_drop > 0.0 else None
         used = torch.empty(2, dtype=torch.int64, device=dev) if p_drop > 0.0 else None
+        mid_a = (_lib.ptr(bias), y.data_ptr())
+        mid_b = (ctx.p_drop, _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr())
         ctx.unit = None
         if any(ctx.needs_input_grad[:3]) and not _SPLIT_HEAD:
-            # a training step: forward and the gradients for d loss = 1 in the same two launches (mkgnn_bce_head_fused)
-            gemb = None
-            if ctx.needs_input_grad[0]:
-                gemb = torch.empty((ctx.rows_total, H), dtype=torch.float32, device=dev)
-                if ctx.rows_total > B:               # rows beyond B (padding molecules) get a zero gradient
-                    gemb[B:].zero_()
-            gw = torch.empty(H, dtype=torch.float32, device=dev)
-            gb = torch.empty(1, dtype=torch.float32, device=dev) if bias is not None else None
-            with torch.cuda.device(dev):
-                ws = _head_workspace(dev, int(lib.mkgnn_bce_head_workspace_bytes(B, H)))
-                _head_call(lib, "fused", kind,
-                           emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), float(p_drop),
-                           _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), _lib.ptr(gemb), H, gw.data_ptr(),
-                           _lib.ptr(gb), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
-            ctx.unit = (gemb, gw, gb)
+            # a training step: forward and the gradients for d loss = 1 in the same two launches
+            ctx.unit, gargs = cls._grads(ctx, emb, w)
+            cls._call(0, kind, emb, B, w, vectors, mid_a, mid_b + gargs)
         else:
-            with torch.cuda.device(dev):
-                ws = _head_workspace(dev, int(lib.mkgnn_bce_head_workspace_bytes(B, H)))
-                _head_call(lib, "dropout_forward", kind,
-                           emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), float(p_drop),
-                           _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(),
-                           _lib.stream_ptr(dev))
+            cls._call(1, kind, emb, B, w, vectors, mid_a, mid_b)
         # (with ctx.unit, references only: a second backward over a retained graph takes the separate backward kernel)
-        ctx.save_for_backward(emb, w, y, pred, used)
-        ctx.wshape = weight.shape
-        ctx.has_bias = bias is not None
-        ctx.p_drop = float(p_drop)
+        ctx.save_for_backward(emb, w, y, pred, used, *vectors)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
         if ctx.unit is not None:
-            gemb, gw, gb = ctx.unit
-            ctx.unit = None
+            grads, ctx.unit = ctx.unit, None
             if not _is_unit_seed(grad_loss):                 # d loss is not the registered 1: scale
                 gl = grad_loss.reshape(()).float()
-                gemb = None if gemb is None else gemb * gl
-                gw = gw * gl
-                gb = None if gb is None else gb * gl
-            return gemb, gw.reshape(ctx.wshape), gb, None, None, None, None
-        lib = _lib.load()
-        emb, w, y, pred, used = ctx.saved_tensors
-        B, H = y.numel(), emb.shape[1]
-        dev = emb.device
-        gl = grad_loss.reshape(1).float().contiguous()
-        gemb = None
-        if ctx.needs_input_grad[0]:
-            # rows beyond B (padding molecules) get a zero gradient: one small fill, only when there are any
-            gemb = torch.empty((ctx.rows_total, H), dtype=torch.float32, device=dev)
-            if ctx.rows_total > B:
-                gemb[B:].zero_()
-        gw = torch.empty(H, dtype=torch.float32, device=dev)
-        gb = torch.empty(1, dtype=torch.float32, device=dev) if ctx.has_bias else None
-        with torch.cuda.device(dev):
-            ws = _head_workspace(dev, int(lib.mkgnn_bce_head_workspace_bytes(B, H)))
-            _head_call(lib, "dropout_backward", ctx.kind,
-                       emb.data_ptr(), _stride0(emb), B, H, w.data_ptr(), y.data_ptr(), pred.data_ptr(), gl.data_ptr(),
-                       ctx.p_drop, _lib.ptr(used), _lib.ptr(gemb), H, gw.data_ptr(), _lib.ptr(gb), ws.data_ptr(), ws.numel(),
-                       _lib.stream_ptr(dev))
-        return gemb, gw.reshape(ctx.wshape), gb, None, None, None, None
+                grads = tuple(None if g is None else g * gl for g in grads)
+        else:
+            emb, w, y, pred, used, *vectors = ctx.saved_tensors
+            gl = grad_loss.reshape(1).float().contiguous()
+            grads, gargs = ctx.family._grads(ctx, emb, w)
+            ctx.family._call(2, ctx.kind, emb, ctx.n_rows, w, vectors, (y.data_ptr(),),
+                             (pred.data_ptr(), gl.data_ptr(), ctx.p_drop, _lib.ptr(used)) + gargs)
+        gemb, gw, gb = grads
+        return (gemb, gw if gw.shape == ctx.wshape else gw.reshape(ctx.wshape), gb) + (None,) * (len(ctx.needs_input_grad) - 3)
+
+
+class _BceHeadFn(_HeadFnBase):
+    """The single-task head: ``mkgnn_bce_head_*`` (``kind`` None: the BCE entry points as they were) and ``mkgnn_head_loss_*``."""
+    SYMS = ("mkgnn_bce_head_fused", "mkgnn_bce_head_dropout_forward", "mkgnn_bce_head_dropout_backward")
+    SYMS_KIND = ("mkgnn_head_loss_fused", "mkgnn_head_loss_dropout_forward", "mkgnn_head_loss_dropout_backward")
+
+    @classmethod
+    def _entries(cls, kind):
+        return (cls.SYMS, ()) if kind is None else (cls.SYMS_KIND, (int(kind),))
+
+    @staticmethod
+    def _weight(weight):
+        return weight.reshape(-1).contiguous()
+
+    @staticmethod
+    def _workspace_bytes(lib, B, H, w):
+        return lib.mkgnn_bce_head_workspace_bytes(B, H)
+
+    @staticmethod
+    def _extra(w, vectors):
+        return (), (), ()
+
+    @staticmethod
+    def forward(ctx, emb, weight, bias, target, p_drop, n_rows, kind=None):
+        return _BceHeadFn._run(ctx, emb, weight, bias, target, p_drop, n_rows, kind)
 
 
 def _head_loss(who: str, emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, kind: Optional[int], dropout_p: float,
@@ -628,7 +661,7 @@ def bce_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor,
     zeroing an element of ``emb`` (``nn.Dropout(ffn_dropout_rate)`` in training mode; 0 otherwise), its mask drawn
     inside the kernels from ``head_rng_state``.  ``n_rows``: only the leading rows of ``emb`` enter the loss (a padded batch's
     real molecules); the others get a zero gradient."""
-    return _head_loss("bce_head_loss", emb, ffn, target, None, dropout_p, n_rows)             # (None: the v7 entry points)
+    return _head_loss("bce_head_loss", emb, ffn, target, None, dropout_p, n_rows)             # (None: mkgnn_bce_head_*)
 
 
 def head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, loss: str = "bce", dropout_p: float = 0.0,
@@ -647,8 +680,8 @@ def head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor, los
         return _head_loss("head_loss", emb, ffn, target, loss_kind(loss), dropout_p, n_rows)
     if ffn.out_features != 1:
         raise ValueError("head_loss needs a one-output linear layer")
-    return _weighted_task_head_loss("head_loss", emb, ffn, target, None, loss, dropout_p, n_rows, None, row_ids, sample_weight,
-                                    pos_weight, weight_table)
+    return _task_head_loss("head_loss", emb, ffn, target, None, loss, dropout_p, n_rows, None, row_ids, sample_weight, pos_weight,
+                           weight_table)
 
 
 # ---------------------------------------------------------------- task-indexed head with masked labels --
@@ -769,106 +802,26 @@ def task_head_reference(emb: torch.Tensor, weight: torch.Tensor, bias: Optional[
     return total, pred
 
 
-class _TaskHeadFn(torch.autograd.Function):
-    """``mkgnn_task_head_*``: the fused entry (forward and the gradients for d loss = 1 in the same two launches) when a gradient
-    is needed, the split forward / backward entries otherwise or under ``MKGNN_SPLIT_HEAD=1`` -- ``_BceHeadFn`` with a task per row."""
+class _TaskHeadFn(_HeadFnBase):
+    """``mkgnn_task_head_*``: ``_BceHeadFn`` with a task per row (``task [>= n_rows]``, or a task table read through ``row_ids``)."""
+    SYMS = ("mkgnn_task_head_fused", "mkgnn_task_head_forward", "mkgnn_task_head_backward")
+
+    @staticmethod
+    def _weight(weight):
+        return weight.contiguous()
+
+    @staticmethod
+    def _workspace_bytes(lib, B, H, w):
+        return lib.mkgnn_task_head_workspace_bytes(B, H, w.shape[0])
+
+    @staticmethod
+    def _extra(w, vectors):
+        task, row_ids = vectors[:2]
+        return (w.shape[0],), (_lib.ptr(task), _lib.ptr(row_ids), 0 if task is None else task.numel()), ()
 
     @staticmethod
     def forward(ctx, emb, weight, bias, target, task, row_ids, p_drop, n_rows, kind):
-        lib = _lib.load()
-        emb = _row_major(emb if emb.dtype == torch.float32 else emb.float())
-        ctx.rows_total = emb.shape[0]
-        B, H = int(n_rows), emb.shape[1]         # the leading n_rows rows enter the loss (the rest: padding molecules)
-        T = weight.shape[0]
-        dev = emb.device
-        w = weight.contiguous()
-        y = target.reshape(-1).float().contiguous()
-        task = task.reshape(-1)
-        if task.dtype != torch.int32 or not task.is_contiguous():
-            task = task.to(torch.int32).contiguous()
-        if row_ids is not None:
-            row_ids = row_ids.reshape(-1)
-            if row_ids.dtype != torch.int32 or not row_ids.is_contiguous():
-                row_ids = row_ids.to(torch.int32).contiguous()
-        idx = (task.data_ptr(), _lib.ptr(row_ids), task.numel())
-        pred = torch.empty(B, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        rng = head_rng_state(dev) if p_drop > 0.0 else None
-        used = torch.empty(2, dtype=torch.int64, device=dev) if p_drop > 0.0 else None
-        ctx.unit = None
-        if any(ctx.needs_input_grad[:3]) and not _SPLIT_HEAD:
-            gemb = None
-            if ctx.needs_input_grad[0]:
-                gemb = torch.empty((ctx.rows_total, H), dtype=torch.float32, device=dev)
-                if ctx.rows_total > B:               # rows beyond B (padding molecules) get a zero gradient
-                    gemb[B:].zero_()
-            gw = torch.empty((T, H), dtype=torch.float32, device=dev)
-            gb = torch.empty(T, dtype=torch.float32, device=dev) if bias is not None else None
-            with torch.cuda.device(dev):
-                ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
-                _lib.check(lib.mkgnn_task_head_fused(
-                    int(kind), emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), *idx,
-                    float(p_drop), _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), _lib.ptr(gemb), H,
-                    gw.data_ptr(), _lib.ptr(gb), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_task_head_fused")
-            ctx.unit = (gemb, gw, gb)
-        else:
-            with torch.cuda.device(dev):
-                ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
-                _lib.check(lib.mkgnn_task_head_forward(
-                    int(kind), emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), *idx,
-                    float(p_drop), _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(),
-                    _lib.stream_ptr(dev)), "mkgnn_task_head_forward")
-        # (with ctx.unit, references only: a second backward over a retained graph takes the separate backward kernel)
-        ctx.save_for_backward(emb, w, y, pred, used, task, row_ids)
-        ctx.kind, ctx.n_rows = int(kind), B
-        ctx.has_bias = bias is not None
-        ctx.p_drop = float(p_drop)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        if ctx.unit is not None:
-            gemb, gw, gb = ctx.unit
-            ctx.unit = None
-            if not _is_unit_seed(grad_loss):                 # d loss is not the registered 1: scale
-                gl = grad_loss.reshape(()).float()
-                gemb = None if gemb is None else gemb * gl
-                gw = gw * gl
-                gb = None if gb is None else gb * gl
-            return gemb, gw, gb, None, None, None, None, None, None
-        lib = _lib.load()
-        emb, w, y, pred, used, task, row_ids = ctx.saved_tensors
-        B, H, T = ctx.n_rows, emb.shape[1], w.shape[0]
-        dev = emb.device
-        gl = grad_loss.reshape(1).float().contiguous()
-        gemb = None
-        if ctx.needs_input_grad[0]:
-            gemb = torch.empty((ctx.rows_total, H), dtype=torch.float32, device=dev)
-            if ctx.rows_total > B:
-                gemb[B:].zero_()
-        gw = torch.empty((T, H), dtype=torch.float32, device=dev)
-        gb = torch.empty(T, dtype=torch.float32, device=dev) if ctx.has_bias else None
-        with torch.cuda.device(dev):
-            ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
-            _lib.check(lib.mkgnn_task_head_backward(
-                ctx.kind, emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), y.data_ptr(), task.data_ptr(), _lib.ptr(row_ids),
-                task.numel(), pred.data_ptr(), gl.data_ptr(), ctx.p_drop, _lib.ptr(used), _lib.ptr(gemb), H, gw.data_ptr(),
-                _lib.ptr(gb), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_task_head_backward")
-        return gemb, gw, gb, None, None, None, None, None, None
-
-
-def _i32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    t = t.reshape(-1)
-    return t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
-
-
-def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    t = t.detach().reshape(-1)
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+        return _TaskHeadFn._run(ctx, emb, weight, bias, target, p_drop, n_rows, kind, (_i32(task), _i32(row_ids)))
 
 
 def _loss_weights(sw: Optional[torch.Tensor], wids: Optional[torch.Tensor], pw: Optional[torch.Tensor]) -> "_lib.LossWeights":
@@ -879,102 +832,35 @@ def _loss_weights(sw: Optional[torch.Tensor], wids: Optional[torch.Tensor], pw: 
     return lw
 
 
-class _WeightedTaskHeadFn(torch.autograd.Function):
+class _WeightedTaskHeadFn(_TaskHeadFn):
     """``mkgnn_task_head_weighted_*``: ``_TaskHeadFn`` with a sample weight per row (``sw``, read directly or through ``wids``), a
     positive weight per task (``pw``), and ``task`` None for "every row has task 0" (a one-output head).  ``task_ids``: the ids the
     TASK is read through (a task table); ``wids``: the ids the WEIGHT is read through -- one id vector may serve as both."""
+    SYMS = ("mkgnn_task_head_weighted_fused", "mkgnn_task_head_weighted_forward", "mkgnn_task_head_weighted_backward")
+
+    @staticmethod
+    def _extra(w, vectors):
+        dims, index, _ = _TaskHeadFn._extra(w, vectors)
+        return dims, index, (ctypes.byref(_loss_weights(*vectors[2:])),)
 
     @staticmethod
     def forward(ctx, emb, weight, bias, target, task, task_ids, sw, wids, pw, p_drop, n_rows, kind):
-        lib = _lib.load()
-        emb = _row_major(emb if emb.dtype == torch.float32 else emb.float())
-        ctx.rows_total = emb.shape[0]
-        B, H = int(n_rows), emb.shape[1]         # the leading n_rows rows enter the loss (the rest: padding molecules)
-        T = weight.shape[0]
-        dev = emb.device
-        w = weight.contiguous()
-        y = target.reshape(-1).float().contiguous()
-        task, task_ids, wids, sw, pw = _i32(task), _i32(task_ids), _i32(wids), _f32(sw), _f32(pw)
-        idx = (_lib.ptr(task), _lib.ptr(task_ids), 0 if task is None else task.numel())
-        lw = _loss_weights(sw, wids, pw)
-        pred = torch.empty(B, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        rng = head_rng_state(dev) if p_drop > 0.0 else None
-        used = torch.empty(2, dtype=torch.int64, device=dev) if p_drop > 0.0 else None
-        ctx.unit = None
-        if any(ctx.needs_input_grad[:3]) and not _SPLIT_HEAD:
-            gemb = None
-            if ctx.needs_input_grad[0]:
-                gemb = torch.empty((ctx.rows_total, H), dtype=torch.float32, device=dev)
-                if ctx.rows_total > B:               # rows beyond B (padding molecules) get a zero gradient
-                    gemb[B:].zero_()
-            gw = torch.empty((T, H), dtype=torch.float32, device=dev)
-            gb = torch.empty(T, dtype=torch.float32, device=dev) if bias is not None else None
-            with torch.cuda.device(dev):
-                ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
-                _lib.check(lib.mkgnn_task_head_weighted_fused(
-                    int(kind), emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), *idx,
-                    float(p_drop), _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), _lib.ptr(gemb), H,
-                    gw.data_ptr(), _lib.ptr(gb), ctypes.byref(lw), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
-                    "mkgnn_task_head_weighted_fused")
-            ctx.unit = (gemb, gw, gb)
-        else:
-            with torch.cuda.device(dev):
-                ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
-                _lib.check(lib.mkgnn_task_head_weighted_forward(
-                    int(kind), emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), _lib.ptr(bias), y.data_ptr(), *idx,
-                    float(p_drop), _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), loss.data_ptr(), ctypes.byref(lw), ws.data_ptr(),
-                    ws.numel(), _lib.stream_ptr(dev)), "mkgnn_task_head_weighted_forward")
-        # (with ctx.unit, references only: a second backward over a retained graph takes the separate backward kernel)
-        ctx.save_for_backward(emb, w, y, pred, used, task, task_ids, sw, wids, pw)
-        ctx.kind, ctx.n_rows = int(kind), B
-        ctx.has_bias = bias is not None
-        ctx.p_drop = float(p_drop)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        none = (None,) * 9
-        if ctx.unit is not None:
-            gemb, gw, gb = ctx.unit
-            ctx.unit = None
-            if not _is_unit_seed(grad_loss):                 # d loss is not the registered 1: scale
-                gl = grad_loss.reshape(()).float()
-                gemb = None if gemb is None else gemb * gl
-                gw = gw * gl
-                gb = None if gb is None else gb * gl
-            return (gemb, gw, gb, *none)
-        lib = _lib.load()
-        emb, w, y, pred, used, task, task_ids, sw, wids, pw = ctx.saved_tensors
-        B, H, T = ctx.n_rows, emb.shape[1], w.shape[0]
-        dev = emb.device
-        gl = grad_loss.reshape(1).float().contiguous()
-        lw = _loss_weights(sw, wids, pw)
-        gemb = None
-        if ctx.needs_input_grad[0]:
-            gemb = torch.empty((ctx.rows_total, H), dtype=torch.float32, device=dev)
-            if ctx.rows_total > B:
-                gemb[B:].zero_()
-        gw = torch.empty((T, H), dtype=torch.float32, device=dev)
-        gb = torch.empty(T, dtype=torch.float32, device=dev) if ctx.has_bias else None
-        with torch.cuda.device(dev):
-            ws = _head_workspace(dev, int(lib.mkgnn_task_head_workspace_bytes(B, H, T)))
-            _lib.check(lib.mkgnn_task_head_weighted_backward(
-                ctx.kind, emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), y.data_ptr(), _lib.ptr(task), _lib.ptr(task_ids),
-                0 if task is None else task.numel(), pred.data_ptr(), gl.data_ptr(), ctx.p_drop, _lib.ptr(used), _lib.ptr(gemb), H,
-                gw.data_ptr(), _lib.ptr(gb), ctypes.byref(lw), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
-                "mkgnn_task_head_weighted_backward")
-        return (gemb, gw, gb, *none)
+        return _WeightedTaskHeadFn._run(ctx, emb, weight, bias, target, p_drop, n_rows, kind,
+                                        (_i32(task), _i32(task_ids), _f32(sw), _i32(wids), _f32(pw)))
 
 
-def _weighted_task_head_loss(who: str, emb, ffn, target, task, loss: str, dropout_p: float, n_rows, task_table, row_ids,
-                             sample_weight, pos_weight, weight_table) -> torch.Tensor:
-    """The weighted body of ``task_head_loss`` and ``head_loss`` (``task`` and ``task_table`` both None: every row has task 0)."""
+def _task_head_loss(who: str, emb, ffn, target, task, loss: str, dropout_p: float, n_rows, task_table, row_ids,
+                    sample_weight, pos_weight, weight_table) -> torch.Tensor:
+    """The body of ``task_head_loss`` and of a weighted ``head_loss``: the checks, then ``_TaskHeadFn``, or with any of the three
+    weights ``_WeightedTaskHeadFn`` (where ``task`` and ``task_table`` may both be None: every row has task 0), or the definition
+    in torch operators for a shape the kernels do not take."""
+    weighted = sample_weight is not None or pos_weight is not None or weight_table is not None
     _lib.require_gpu_tensor(emb, "graph_embedding")
     kind = loss_kind(loss)
     n_rows = emb.shape[0] if n_rows is None else int(n_rows)
     T, H = ffn.weight.shape
-    if task is not None and task_table is not None:
+    if (task is not None and task_table is not None) or (not weighted and (
+            (task is None) == (task_table is None) or (task_table is None) != (row_ids is None))):
         raise ValueError(f"{who} needs either task, or task_table together with row_ids")
     if task is None and task_table is None and T != 1:
         raise ValueError(f"{who} without task or task_table needs a one-output linear layer")
@@ -993,15 +879,17 @@ def _weighted_task_head_loss(who: str, emb, ffn, target, task, loss: str, dropou
                     ("sample_weight", sample_weight), ("pos_weight", pos_weight), ("weight_table", weight_table)):
         if t is not None:
             _lib.require_gpu_tensor(t, name)
-    if not task_head_supported(T, H) or not _WEIGHTED_LOSS:
+    if not task_head_supported(T, H) or (weighted and not _WEIGHTED_LOSS):
         keep = None
         if dropout_p > 0.0:
             keep = torch.empty((n_rows, H), dtype=emb.dtype, device=emb.device).bernoulli_(1.0 - dropout_p).mul_(1.0 / (1.0 - dropout_p))
         return task_head_reference(emb, ffn.weight, ffn.bias, target, task, loss, keep, n_rows, task_table, row_ids,
                                    sample_weight, pos_weight, weight_table)[0]
-    sw = sample_weight if sample_weight is not None else weight_table
-    return _WeightedTaskHeadFn.apply(emb, ffn.weight, ffn.bias, target, task if task is not None else task_table,
-                                     row_ids if task_table is not None else None, sw,
+    tasks, task_ids = (task, None) if task_table is None else (task_table, row_ids)
+    if not weighted:
+        return _TaskHeadFn.apply(emb, ffn.weight, ffn.bias, target, tasks, task_ids, float(dropout_p), n_rows, kind)
+    return _WeightedTaskHeadFn.apply(emb, ffn.weight, ffn.bias, target, tasks, task_ids,
+                                     sample_weight if sample_weight is not None else weight_table,
                                      row_ids if weight_table is not None else None, pos_weight, float(dropout_p), n_rows, kind)
 
 
@@ -1022,32 +910,8 @@ def task_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor
     loss of ``task_head_reference`` on ``mkgnn_task_head_weighted_*`` (``_WeightedTaskHeadFn``), and then ``task`` and ``task_table``
     may both be absent for a one-output ``ffn`` (every row has task 0).  ``MKGNN_WEIGHTED_LOSS=0`` runs the definition in torch
     operators instead.  With none of the three given nothing changes."""
-    if sample_weight is not None or pos_weight is not None or weight_table is not None:
-        return _weighted_task_head_loss("task_head_loss", emb, ffn, target, task, loss, dropout_p, n_rows, task_table, row_ids,
-                                        sample_weight, pos_weight, weight_table)
-    _lib.require_gpu_tensor(emb, "graph_embedding")
-    kind = loss_kind(loss)
-    n_rows = emb.shape[0] if n_rows is None else int(n_rows)
-    if (task is None) == (task_table is None) or (task_table is None) != (row_ids is None):
-        raise ValueError("task_head_loss needs either task, or task_table together with row_ids")
-    per_row = task if task is not None else row_ids
-    if emb.dim() != 2 or ffn.in_features != emb.shape[1] or n_rows <= 0 or n_rows > emb.shape[0] or target.numel() < n_rows \
-            or per_row.numel() < n_rows or (task_table is not None and task_table.numel() < 1):
-        raise ValueError("task_head_loss needs an [n, H] embedding, an H-input linear layer and a target and a task (or row id) "
-                         "per (leading) row")
-    if not 0.0 <= dropout_p < 1.0:
-        raise ValueError(f"dropout probability {dropout_p} outside [0, 1)")
-    for name, t in (("task", task), ("task_table", task_table), ("row_ids", row_ids), ("target", target)):
-        if t is not None:
-            _lib.require_gpu_tensor(t, name)
-    T, H = ffn.weight.shape
-    if not task_head_supported(T, H):
-        keep = None
-        if dropout_p > 0.0:
-            keep = torch.empty((n_rows, H), dtype=emb.dtype, device=emb.device).bernoulli_(1.0 - dropout_p).mul_(1.0 / (1.0 - dropout_p))
-        return task_head_reference(emb, ffn.weight, ffn.bias, target, task, loss, keep, n_rows, task_table, row_ids)[0]
-    return _TaskHeadFn.apply(emb, ffn.weight, ffn.bias, target, task if task is not None else task_table, row_ids,
-                             float(dropout_p), n_rows, kind)
+    return _task_head_loss("task_head_loss", emb, ffn, target, task, loss, dropout_p, n_rows, task_table, row_ids, sample_weight,
+                           pos_weight, weight_table)
 
 
 def task_scores(emb: torch.Tensor, ffn: torch.nn.Linear, n_rows: Optional[int] = None, out: Optional[torch.Tensor] = None,

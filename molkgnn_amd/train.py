@@ -232,8 +232,7 @@ class GNNModel(torch.nn.Module):
         graph_embedding = self.gnn_model(data)
         if self.training and self.dropout.p >= 1.0:
             graph_embedding = self.dropout(graph_embedding)
-        task = getattr(data, 'task', None)                   # (given directly, it is taken before a table)
-        table, rows = (None, None) if task is not None else (data.task_table, data.task_rows)
+        task, table, rows = _batch_tasks(data)
         return task_head_loss(graph_embedding, self.ffn, data.y, task, kind, dropout_p=p,
                               n_rows=getattr(data, 'n_valid_molecules', None), task_table=table, row_ids=rows)
 
@@ -260,17 +259,12 @@ class GNNModel(torch.nn.Module):
                 pw = held[2]
         if kind is None:
             return None
-        sw = getattr(data, 'weight', None)
-        table, rows = (None, None) if sw is not None else (getattr(data, 'weight_table', None), getattr(data, 'weight_rows', None))
-        if table is None or rows is None:
-            table = rows = None
+        sw, table, rows = _batch_weight_fields(data)
         if sw is not None and not (torch.is_tensor(sw) and sw.dtype == torch.float32 and sw.device == dev):
             raise ValueError("batch.weight must be a float32 tensor on the batch's device (one loss weight per molecule)")
         if pw is None and sw is None and table is None:
             return None
-        multi = getattr(data, 'task', None) is not None or (
-            getattr(data, 'task_table', None) is not None and getattr(data, 'task_rows', None) is not None)
-        if T != 1 and not multi:
+        if T != 1 and not _has_tasks(data):
             return None
         return kind, pw, sw, table, rows
 
@@ -282,19 +276,12 @@ class GNNModel(torch.nn.Module):
         from . import readout as R
         p = self.dropout.p if self.training else 0.0
         nreal = getattr(data, 'n_valid_molecules', None)
-        task = getattr(data, 'task', None)
-        ttable, trows = (None, None) if task is not None else (getattr(data, 'task_table', None), getattr(data, 'task_rows', None))
-        if ttable is None or trows is None:
-            ttable = trows = None
+        task, ttable, trows = _batch_tasks(data)
         if task is not None or ttable is not None:
             graph_embedding = self.gnn_model(data)
-            if table is not None and trows is not None and rows is not trows:
-                # (two id vectors: the kernels read ONE -- the weights are looked up here)
-                n = graph_embedding.shape[0] if nreal is None else int(nreal)
-                sw, table, rows = R._row_weights(None, table, rows, n), None, None
+            sw, table, ids = _weights_for(graph_embedding, nreal, sw, table, rows, trows)
             return R.task_head_loss(graph_embedding, self.ffn, data.y, task, kind, dropout_p=p, n_rows=nreal, task_table=ttable,
-                                    row_ids=trows if trows is not None else rows, sample_weight=sw, pos_weight=pw,
-                                    weight_table=table)
+                                    row_ids=ids, sample_weight=sw, pos_weight=pw, weight_table=table)
         kw = dict(sample_weight=sw, pos_weight=pw, weight_table=table, row_ids=rows)
         tail = (self.ffn, data.y, p, nreal, kind, kw) if R._WEIGHTED_LOSS else None
         graph_embedding = self.gnn_model(data, _tail=tail)
@@ -307,32 +294,26 @@ class GNNModel(torch.nn.Module):
         and ``self.dropout``: what a batch with weights gets where the HIP route does not apply (head dropout ``p >= 1``)."""
         from .readout import task_head_reference
         graph_embedding = self.dropout(self.gnn_model(data))
-        task = getattr(data, 'task', None)
-        ttable, trows = (None, None) if task is not None else (getattr(data, 'task_table', None), getattr(data, 'task_rows', None))
-        if ttable is None or trows is None:
-            ttable = trows = None
+        task, ttable, trows = _batch_tasks(data)
         nreal = getattr(data, 'n_valid_molecules', None)
-        if table is not None and trows is not None and rows is not trows:
-            from .readout import _row_weights
-            sw, table = _row_weights(None, table, rows, graph_embedding.shape[0] if nreal is None else int(nreal)), None
-        return task_head_reference(graph_embedding, self.ffn.weight, self.ffn.bias, data.y, task, kind, None, nreal, ttable,
-                                   trows if trows is not None else rows, sw, pw, table)[0]
+        sw, table, ids = _weights_for(graph_embedding, nreal, sw, table, rows, trows)
+        return task_head_reference(graph_embedding, self.ffn.weight, self.ffn.bias, data.y, task, kind, None, nreal, ttable, ids,
+                                   sw, pw, table)[0]
 
     def loss(self, data):
         # a batch that carries loss weights gets them, or an error: never the unweighted loss in silence
-        carries = getattr(data, 'weight', None) is not None or (
-            getattr(data, 'weight_table', None) is not None and getattr(data, 'weight_rows', None) is not None)
+        carries = any(f is not None for f in _batch_weight_fields(data))
         weighted = self._weighted_loss(data) if data.x.is_cuda else None
+        full_dropout = self.training and self.dropout.p >= 1.0           # (head dropout p >= 1 keeps the PyTorch operator)
         if weighted is not None:
-            if not (self.training and self.dropout.p >= 1.0):
+            if not full_dropout:
                 return self._weighted(data, *weighted)
             if carries:                                      # (head dropout p >= 1 keeps its route; with weights: their definition)
                 return self._weighted_definition(data, *weighted)
         elif carries:
             raise ValueError("the batch carries loss weights (weight / weight_table), which GNNModel.loss takes on a CUDA batch with "
                              "BCEWithLogitsLoss (optionally pos_weight) or MSELoss, and for several outputs with the batch's tasks")
-        if data.x.is_cuda and (getattr(data, 'task', None) is not None or (
-                getattr(data, 'task_table', None) is not None and getattr(data, 'task_rows', None) is not None)):
+        if data.x.is_cuda and _has_tasks(data):
             kind = self._loss_kind()
             if kind is not None:
                 return self._task_loss(data, kind)
@@ -341,8 +322,8 @@ class GNNModel(torch.nn.Module):
             from .readout import bce_head_loss, head_loss
             # dropout -> ffn -> loss in one kernel each way (same formula, 2 kernels instead of ~25; the dropout mask
             # comes from the kernels' own counter-based generator, see readout.head_rng_state)
-            p = self.dropout.p if (self.training and self.dropout.p < 1.0) else 0.0
-            if not (self.training and self.dropout.p >= 1.0):
+            p = self.dropout.p if (self.training and not full_dropout) else 0.0
+            if not full_dropout:
                 # small batches: forward, loss and (when a gradient will be asked for) the whole backward in one launch
                 from . import molecule as _mol
                 fused = _mol.loss_forward(self, data, p, kind)
@@ -351,11 +332,11 @@ class GNNModel(torch.nn.Module):
             nreal = getattr(data, 'n_valid_molecules', None)
             # large batches: everything behind the last convolution -- readout, head, loss and their gradients -- in one launch
             # (readout.tail_loss) where the model and the batch qualify; the embedding otherwise
-            tail = None if (self.training and self.dropout.p >= 1.0) else (self.ffn, data.y, p, nreal, kind)
+            tail = None if full_dropout else (self.ffn, data.y, p, nreal, kind)
             graph_embedding = self.gnn_model(data, _tail=tail)
             if isinstance(graph_embedding, tuple):
                 return graph_embedding[1]
-            if self.training and self.dropout.p >= 1.0:
+            if full_dropout:
                 graph_embedding = self.dropout(graph_embedding)
             # (a padded batch: the padding molecules' rows take no part in the loss -- the head reads the first nreal rows)
             if kind != "bce":
@@ -363,6 +344,34 @@ class GNNModel(torch.nn.Module):
             return bce_head_loss(graph_embedding, self.ffn, data.y, dropout_p=p, n_rows=nreal)
         pred, _ = self(data)
         return self.loss_func(pred.view(-1), data.y.view(-1).float())
+
+
+def _batch_fields(data, direct: str = 'task', table: str = 'task_table', rows: str = 'task_rows'):
+    """``(task, task_table, task_rows)`` of a batch (or the weight fields, by name): one given directly is taken before a table; a
+    table needs its rows."""
+    d, t, r = (getattr(data, name, None) for name in (direct, table, rows))
+    return (d, None, None) if (d is not None or t is None or r is None) else (None, t, r)
+
+
+def _batch_tasks(data):
+    return _batch_fields(data)
+
+
+def _has_tasks(data) -> bool:
+    return any(f is not None for f in _batch_fields(data))
+
+
+def _batch_weight_fields(data):
+    return _batch_fields(data, 'weight', 'weight_table', 'weight_rows')
+
+
+def _weights_for(graph_embedding, nreal, sw, table, rows, trows):
+    """``(sample_weight, weight_table, row_ids)`` for a weighted call whose tasks are read through ``trows`` (or None): the kernels
+    read ONE id vector, so a weight table read through a different one than the task table is looked up here."""
+    if table is not None and trows is not None and rows is not trows:
+        from .readout import _row_weights
+        return _row_weights(None, table, rows, graph_embedding.shape[0] if nreal is None else int(nreal)), None, trows
+    return sw, table, trows if trows is not None else rows
 
 
 _ONES: dict = {}
