@@ -838,6 +838,53 @@ int mkgnn_task_head_weighted_fused(int32_t loss_kind, const float* emb, int64_t 
                                    int64_t* rng_used, float* pred, float* loss, float* grad_emb, int64_t grad_emb_stride,
                                    float* grad_weight, float* grad_bias, const mkgnn_loss_weights* weights, void* workspace,
                                    size_t workspace_bytes, void* stream);
+/* (additive; the ABI version stays 8) The label-matrix head: the same T-output ffn, but every row carries a ROW of labels with
+ * holes instead of naming one task -- the network runs once per molecule, not once per (molecule, assay) pair.  Row i < n_rows has
+ * the labels  labels[i * label_stride + t]  (row_ids NULL; n_label_rows >= n_rows rows)  or  labels[row_ids[i] * label_stride + t]
+ * (labels: a table of n_label_rows rows, e.g. one per molecule of a resident shard; row_ids int32 [n_rows]; an id outside
+ * [0, n_label_rows) is "no label in any task").  Entry (i, t) is labelled iff its label is not NaN -- only NaN means missing, an
+ * infinite label is a label:
+ *     pred[i * pred_stride + t] = (keep_i * emb_i) . weight[t] + bias[t]          for EVERY i < n_rows, t < T, labelled or not
+ *     loss = sum over the labelled entries of s_i * term(pred[i, t], labels[i, t]) / max(n_labelled_entries, 1)
+ * (SQERR_SUM: no division; never divided by the sum of the weights).  term, s_i (weights->sample_weight, direct or through
+ * weights->weight_ids, which is that same row_ids vector or NULL) and pos_weight [T] are the weighted task head's above; weights may
+ * be NULL.  Sample weights that are all exactly 1.0f give the bits of a call without them.  An unlabelled entry is removed by a
+ * select: its label, and the sample weight of a row without labels, reach neither a value nor a gradient.  keep: the heads' dropout
+ * multipliers -- element i * H + h of the same generator, same rng_state / rng_used protocol, so a call draws the mask the other
+ * heads draw from the same {seed, offset}; dropout_p in [0, 1).
+ * BITS: pred[i, t] is bit for bit what mkgnn_task_head_forward writes for row i labelled with task t under the same generator
+ * state (at dropout_p = 0: mkgnn_task_scores' value).  The loss and the gradients are NOT the task head's bits (a row's terms are
+ * summed in an xor tree over its tasks first); they are bit-reproducible run to run, and the fused entry's gradients are the
+ * forward + backward pair's at grad_loss = 1.
+ * Gradients: grad_emb[i, h] = keep[i, h] * sum over t ascending of d[i, t] * weight[t, h] (grad_emb may be NULL), grad_weight [T, H],
+ * grad_bias [T] or NULL.  EXACT zeros: grad_weight[t, :] and grad_bias[t] of a task without a labelled entry in the call, grad_emb[i, :]
+ * of a row without one, and with no labelled entry at all the loss and every gradient (count clamped to 1); pred is still written
+ * everywhere.  Nothing is read or written at rows >= n_rows, nor between padded strides.  forward / backward / fused mirror the task
+ * head's (backward: d loss from the device, pred from the forward, only the mask is recomputed).  Two launches per call -- the
+ * second is the task head's own final kernel --, fixed-order sums, no atomics, no process-wide state, nothing read back, capturable:
+ * labels, ids and weights are device buffers a captured step may refill.
+ * Limits: 1 <= T <= MKGNN_TASK_HEAD_MAX_TASKS, 1 <= H <= 64, n_rows >= 1, n_rows * T < 2^31 (the labelled-entry count stays an exact
+ * int), label_stride >= T, pred_stride >= T, emb_stride >= H; anything else, an unknown loss kind, pos_weight with a squared-error
+ * kind and a short sample_weight return non-zero with mkgnn_last_error set before any launch.  workspace:
+ * mkgnn_label_head_workspace_bytes (0 outside the limits). */
+size_t mkgnn_label_head_workspace_bytes(int64_t n_rows, int32_t H, int32_t T);
+int mkgnn_label_head_forward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                             const float* weight, const float* bias, const float* labels, int64_t label_stride,
+                             const int32_t* row_ids, int64_t n_label_rows, float dropout_p, int64_t* rng_state, int64_t* rng_used,
+                             float* pred, int64_t pred_stride, float* loss, const mkgnn_loss_weights* weights, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int mkgnn_label_head_backward(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                              const float* weight, const float* labels, int64_t label_stride, const int32_t* row_ids,
+                              int64_t n_label_rows, const float* pred, int64_t pred_stride, const float* grad_loss,
+                              float dropout_p, const int64_t* rng_used, float* grad_emb, int64_t grad_emb_stride,
+                              float* grad_weight, float* grad_bias, const mkgnn_loss_weights* weights, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int mkgnn_label_head_fused(int32_t loss_kind, const float* emb, int64_t emb_stride, int64_t n_rows, int32_t H, int32_t T,
+                           const float* weight, const float* bias, const float* labels, int64_t label_stride,
+                           const int32_t* row_ids, int64_t n_label_rows, float dropout_p, int64_t* rng_state, int64_t* rng_used,
+                           float* pred, int64_t pred_stride, float* loss, float* grad_emb, int64_t grad_emb_stride,
+                           float* grad_weight, float* grad_bias, const mkgnn_loss_weights* weights, void* workspace,
+                           size_t workspace_bytes, void* stream);
 /* (additive; the ABI version stays 8) mkgnn_tail_fused_readout_dropout with that weighted loss: a sample weight per molecule
  * gi < args->n_loss_mols (sample_weight[gi], or sample_weight[weight_ids[gi]]) and ONE positive weight, pos_weight[0] (the tail is
  * single-task).  Only a molecule's d loss / d logit and its loss term change -- the formulas above, the sample weight first, then

@@ -290,6 +290,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_task_head_workspace_bytes", "mkgnn_task_head_forward", "mkgnn_task_head_backward", "mkgnn_task_head_fused",
            "mkgnn_task_head_weighted_forward", "mkgnn_task_head_weighted_backward", "mkgnn_task_head_weighted_fused",
            "mkgnn_tail_fused_weighted",
+           "mkgnn_label_head_workspace_bytes", "mkgnn_label_head_forward", "mkgnn_label_head_backward", "mkgnn_label_head_fused",
            "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks", "mkgnn_embed_cosine",
            "mkgnn_atom_contributions", "mkgnn_atom_contributions_workspace_bytes", "mkgnn_embed_max_cosine",
            "mkgnn_embed_max_cosine_workspace_bytes", "mkgnn_select_rows", "mkgnn_tail_defer_projection",
@@ -514,6 +515,20 @@ def load() -> C.CDLL:
         args = list(getattr(lib, "mkgnn_task_head_" + name).argtypes)
         getattr(lib, "mkgnn_task_head_weighted_" + name).restype = C.c_int
         getattr(lib, "mkgnn_task_head_weighted_" + name).argtypes = args[:-3] + [C.POINTER(LossWeights)] + args[-3:]
+    # the label-matrix head: (loss_kind, emb, stride, n_rows, H, T, weight, [bias,] labels, label stride, row_ids, n_label_rows, ...,
+    # pred, pred stride, ..., weights, workspace, bytes, stream)
+    LW = C.POINTER(LossWeights)
+    lib.mkgnn_label_head_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_label_head_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.mkgnn_label_head_forward.restype = C.c_int
+    lib.mkgnn_label_head_forward.argtypes = [I32, P, I64, I64, I32, I32, P, P, P, I64, P, I64, C.c_float, P, P, P, I64, P, LW, P,
+                                             C.c_size_t, P]
+    lib.mkgnn_label_head_backward.restype = C.c_int
+    lib.mkgnn_label_head_backward.argtypes = [I32, P, I64, I64, I32, I32, P, P, I64, P, I64, P, I64, P, C.c_float, P, P, I64, P, P,
+                                              LW, P, C.c_size_t, P]
+    lib.mkgnn_label_head_fused.restype = C.c_int
+    lib.mkgnn_label_head_fused.argtypes = [I32, P, I64, I64, I32, I32, P, P, P, I64, P, I64, C.c_float, P, P, P, I64, P, P, I64, P,
+                                           P, LW, P, C.c_size_t, P]
     # every task's logit of every row: (emb, stride, n_rows, H, T, weight, bias, pred, row stride, task stride, stream)
     lib.mkgnn_task_scores.restype = C.c_int
     lib.mkgnn_task_scores.argtypes = [P, I64, I64, I32, I32, P, P, P, I64, I64, P]

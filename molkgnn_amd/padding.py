@@ -236,6 +236,12 @@ class CompactStaticBatch:
             self.data.weight_table, self.data.weight_rows = table, self.ids
         elif getattr(self.data, "weight_table", None) is not None:
             self.data.weight_table = self.data.weight_rows = None
+        # ... and one that holds a label matrix (ResidentShard(..., labels=...)): the label table of the multi-label loss
+        table = resident.tensors.get("labels")
+        if table is not None:
+            self.data.label_table, self.data.label_rows = table, self.ids
+        elif getattr(self.data, "label_table", None) is not None:
+            self.data.label_table = self.data.label_rows = None
 
     def gather_status(self) -> int:
         """The status word of the LAST gather (a host read: once per epoch, not per batch): 0, or ``_lib.GATHER_BAD_ID`` (an id

@@ -914,6 +914,194 @@ def task_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, target: torch.Tensor
                            pos_weight, weight_table)
 
 
+# ------------------------------------------------------------------- label-matrix head: labels [n, T] with holes --
+def label_head_supported(T: int, H: int) -> bool:
+    """The shapes ``mkgnn_label_head_*`` take (the task-indexed head's); anything else goes through ``label_head_reference`` on
+    the GPU.  (A call must also keep ``n_rows * T`` below 2^31: the labelled-entry count is an exact int.)"""
+    return task_head_supported(T, H)
+
+
+# MKGNN_LABEL_HEAD=0 (A/B, diagnostics): the label-matrix loss runs its definition (label_head_reference) in torch operators on
+# the GPU instead of the kernels
+_LABEL_HEAD = os.environ.get("MKGNN_LABEL_HEAD", "1") != "0"
+
+
+def _row_labels(labels, label_table, row_ids, n_rows: int) -> torch.Tensor:
+    """The label row of each of the leading ``n_rows`` rows ``[n_rows, T]``: ``labels`` itself, or ``label_table[row_ids]`` with an
+    id outside the table read as a row of NaN."""
+    if labels is not None:
+        return labels[:n_rows]
+    ids = row_ids.reshape(-1)[:n_rows].long().to(label_table.device)
+    m = label_table.shape[0]
+    inside = (ids >= 0) & (ids < m)
+    rows = label_table[ids.clamp(0, max(m - 1, 0))]
+    return torch.where(inside[:, None], rows, torch.full_like(rows, float("nan")))
+
+
+def label_head_reference(emb: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], labels: Optional[torch.Tensor],
+                         loss: str = "bce", keep: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
+                         label_table: Optional[torch.Tensor] = None, row_ids: Optional[torch.Tensor] = None,
+                         sample_weight: Optional[torch.Tensor] = None, pos_weight: Optional[torch.Tensor] = None,
+                         weight_table: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(loss, pred [n_rows, T])`` of the label-matrix head in torch operators, in the dtype of ``emb``, differentiable: the
+    DEFINITION of ``label_head_loss`` (and what it runs outside the kernels' limits).
+
+    Row ``i < n_rows`` has the labels ``labels[i, :]`` (float, ``[>= n_rows, T]``), or ``label_table[row_ids[i], :]`` with an id
+    outside the table read as "no label in any task".  Entry ``(i, t)`` is labelled iff its label is not NaN -- only NaN means
+    missing, an infinite label is a label.  ``pred[i, t] = (keep_i * emb_i) . weight[t] + bias[t]`` for EVERY ``(i, t)``, labelled
+    or not; a labelled entry's term is ``task_head_reference``'s for that kind -- ``"bce"`` (with ``pos_weight[t]``: ``(1 - y) x + L
+    log(1 + e^-x)``, ``L = 1 + (p_t - 1) y``), ``"mse"``, ``"mse_sum"`` -- multiplied by the row's sample weight (``sample_weight[i]``,
+    or ``weight_table[row_ids[i]]`` with an id outside the table read as +0.0); ``loss`` is the sum of the labelled terms over
+    ``max(n_labelled_entries, 1)`` (``"mse_sum"``: not divided; never the sum of the weights).  An unlabelled entry is removed by a
+    select, not by a product: its label, and the weight of a row without labels, reach neither the value nor any gradient.  Rows
+    from ``n_rows`` on take no part.  Weights are constants (one that requires a gradient raises ``ValueError``).  With exactly one
+    labelled entry per row this is ``task_head_reference`` with that task; with ``T == 1`` and no NaN the single-task head's
+    definition."""
+    loss_kind(loss)
+    n = emb.shape[0] if n_rows is None else int(n_rows)
+    T = weight.shape[0]
+    if (labels is None) == (label_table is None):
+        raise ValueError("label_head_reference needs either labels, or label_table together with row_ids")
+    if label_table is not None and row_ids is None:
+        raise ValueError("label_table needs row_ids")
+    _check_loss_weights(loss, T, sample_weight, pos_weight, weight_table, row_ids)
+    e = emb[:n]
+    if keep is not None:
+        e = e * keep[:n].to(e.dtype)
+    pred = e @ weight.t()
+    if bias is not None:
+        pred = pred + bias
+    yl = _row_labels(labels, label_table, row_ids, n).to(device=pred.device)
+    lab = ~torch.isnan(yl)
+    zero = torch.zeros((), dtype=pred.dtype, device=pred.device)
+    y = torch.where(lab, yl.to(pred.dtype), zero)
+    x = torch.where(lab, pred, zero)                      # (an unlabelled entry's logit takes no part: selected out before the term)
+    if loss == "bce" and pos_weight is not None:
+        L = 1 + (pos_weight.detach().reshape(-1).to(device=pred.device, dtype=pred.dtype) - 1) * y
+        term = (1 - y) * x + L * torch.logaddexp(-x, torch.zeros_like(x))
+    elif loss == "bce":
+        term = torch.logaddexp(x, torch.zeros_like(x)) - x * y
+    else:
+        term = (x - y) ** 2
+    s = _row_weights(sample_weight, weight_table, row_ids, n)
+    if s is not None:
+        # (the weight of an unlabelled entry is not used: zeroed BEFORE the product, so a NaN there reaches nothing)
+        term = torch.where(lab, s.to(device=pred.device, dtype=pred.dtype)[:, None].expand_as(term), zero) * term
+    total = torch.where(lab, term, zero).sum()
+    if loss != "mse_sum":
+        total = total / lab.sum().clamp(min=1).to(pred.dtype)
+    return total, pred
+
+
+class _LabelHeadFn(_HeadFnBase):
+    """``mkgnn_label_head_*`` on the ``_HeadFnBase`` pattern: the fused entry when a gradient will be asked for, the forward /
+    backward pair otherwise, the unit-seed shortcut.  Returns ``(loss, pred [n_rows, T])``; ``pred`` carries no gradient."""
+    SYMS = ("mkgnn_label_head_fused", "mkgnn_label_head_forward", "mkgnn_label_head_backward")
+
+    @classmethod
+    def _launch(cls, which: int, kind, emb, B, w, y, ids, weights, before: tuple, after: tuple) -> None:
+        """``SYMS[which](kind, emb, stride, B, H, T, w, *before, labels, T, ids, rows, *after, weights, workspace, stream)``."""
+        lib, dev, (T, H) = _lib.load(), emb.device, w.shape
+        with torch.cuda.device(dev):
+            ws = _head_workspace(dev, int(lib.mkgnn_label_head_workspace_bytes(B, H, T)))
+            _lib.check(getattr(lib, cls.SYMS[which])(int(kind), emb.data_ptr(), _stride0(emb), B, H, T, w.data_ptr(), *before,
+                                                     y.data_ptr(), T, _lib.ptr(ids), y.numel() // T, *after,
+                                                     ctypes.byref(_loss_weights(*weights)), ws.data_ptr(), ws.numel(),
+                                                     _lib.stream_ptr(dev)), cls.SYMS[which])
+
+    @staticmethod
+    def forward(ctx, emb, weight, bias, labels, ids, sw, wids, pw, p_drop, n_rows, kind):
+        cls = _LabelHeadFn
+        emb = _row_major(emb if emb.dtype == torch.float32 else emb.float())
+        w, y = weight.contiguous(), _f32(labels)
+        ids, weights = _i32(ids), (_f32(sw), _i32(wids), _f32(pw))
+        B, dev, T = int(n_rows), emb.device, weight.shape[0]
+        ctx.family, ctx.kind, ctx.n_rows = cls, kind, B
+        ctx.wshape, ctx.has_bias, ctx.p_drop = weight.shape, bias is not None, float(p_drop)
+        pred = torch.empty((B, T), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        rng = head_rng_state(dev) if p_drop > 0.0 else None
+        used = torch.empty(2, dtype=torch.int64, device=dev) if p_drop > 0.0 else None
+        after = (ctx.p_drop, _lib.ptr(rng), _lib.ptr(used), pred.data_ptr(), T, loss.data_ptr())
+        ctx.unit = None
+        if any(ctx.needs_input_grad[:3]) and not _SPLIT_HEAD:
+            ctx.unit, gargs = cls._grads(ctx, emb, w)
+            cls._launch(0, kind, emb, B, w, y, ids, weights, (_lib.ptr(bias),), after + gargs)
+        else:
+            cls._launch(1, kind, emb, B, w, y, ids, weights, (_lib.ptr(bias),), after)
+        ctx.save_for_backward(emb, w, y, pred, used, ids, *weights)
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_pred=None):
+        if ctx.unit is not None:
+            grads, ctx.unit = ctx.unit, None
+            if not _is_unit_seed(grad_loss):                 # d loss is not the registered 1: scale
+                gl = grad_loss.reshape(()).float()
+                grads = tuple(None if g is None else g * gl for g in grads)
+        else:
+            emb, w, y, pred, used, ids, *weights = ctx.saved_tensors
+            gl = grad_loss.reshape(1).float().contiguous()
+            grads, gargs = ctx.family._grads(ctx, emb, w)
+            ctx.family._launch(2, ctx.kind, emb, ctx.n_rows, w, y, ids, weights, (),
+                               (pred.data_ptr(), w.shape[0], gl.data_ptr(), ctx.p_drop, _lib.ptr(used)) + gargs)
+        gemb, gw, gb = grads
+        return (gemb, gw, gb) + (None,) * (len(ctx.needs_input_grad) - 3)
+
+
+def label_head_loss(emb: torch.Tensor, ffn: torch.nn.Linear, labels: Optional[torch.Tensor] = None, loss: str = "bce",
+                    dropout_p: float = 0.0, n_rows: Optional[int] = None, label_table: Optional[torch.Tensor] = None,
+                    row_ids: Optional[torch.Tensor] = None, sample_weight: Optional[torch.Tensor] = None,
+                    pos_weight: Optional[torch.Tensor] = None, weight_table: Optional[torch.Tensor] = None,
+                    return_pred: bool = False):
+    """The multi-label loss of a ``T``-output ``ffn`` on a label matrix with holes: ``label_head_reference(dropout(emb), ffn.weight,
+    ffn.bias, labels, ...)[0]`` as two launches each way (``_LabelHeadFn``, ``mkgnn_label_head_*``).  Every row carries a row of
+    labels -- ``labels [>= n_rows, T]`` (float32, NaN: not measured), or ``label_table [M, T]`` with ``row_ids [>= n_rows]`` (int32,
+    on the device; both may be static buffers a captured step refills) -- so the network runs once per molecule, not once per
+    (molecule, assay) pair as with ``task_head_loss``.  ``dropout_p``, its generator (``head_rng_state``) and mask, ``n_rows``, the
+    loss kinds and the weights (``sample_weight [>= n_rows]``, or ``weight_table [M]`` read through the same ``row_ids``; ``pos_weight
+    [T]``, ``"bce"`` only) are ``task_head_loss``'s.  ``return_pred``: ``(loss, pred [n_rows, T])``, ``pred`` without a gradient and,
+    on the kernels, bit for bit ``task_scores`` at dropout 0.  Outside ``label_head_supported`` (or ``n_rows * T >= 2^31``), and with
+    ``MKGNN_LABEL_HEAD=0``, the definition runs in torch operators on the GPU."""
+    who = "label_head_loss"
+    _lib.require_gpu_tensor(emb, "graph_embedding")
+    kind = loss_kind(loss)
+    n_rows = emb.shape[0] if n_rows is None else int(n_rows)
+    T, H = ffn.weight.shape
+    if (labels is None) == (label_table is None):
+        raise ValueError(f"{who} needs either labels, or label_table together with row_ids")
+    if label_table is not None and (row_ids is None or label_table.dim() != 2 or label_table.shape[0] < 1):
+        raise ValueError(f"{who}: label_table [M, T] needs row_ids and at least one row")
+    mat = labels if labels is not None else label_table
+    if mat.dim() != 2 or mat.shape[1] != T or not mat.is_floating_point():
+        raise ValueError(f"{who}: the labels must be a float [rows, {T}] matrix for a {T}-output linear layer, not {tuple(mat.shape)}")
+    _check_loss_weights(loss, T, sample_weight, pos_weight, weight_table, row_ids)
+    per_row = [t for t in (sample_weight, row_ids if (label_table is not None or weight_table is not None) else None)
+               if t is not None]
+    if emb.dim() != 2 or ffn.in_features != emb.shape[1] or n_rows <= 0 or n_rows > emb.shape[0] \
+            or (labels is not None and labels.shape[0] < n_rows) or any(t.numel() < n_rows for t in per_row):
+        raise ValueError(f"{who} needs an [n, H] embedding, an H-input linear layer and a label row, a weight (or a row id) per "
+                         "(leading) row")
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"dropout probability {dropout_p} outside [0, 1)")
+    for name, t in (("labels", labels), ("label_table", label_table), ("row_ids", row_ids), ("sample_weight", sample_weight),
+                    ("pos_weight", pos_weight), ("weight_table", weight_table)):
+        if t is not None:
+            _lib.require_gpu_tensor(t, name)
+    if not label_head_supported(T, H) or n_rows * T >= 2 ** 31 or not _LABEL_HEAD:
+        keep = None
+        if dropout_p > 0.0:
+            keep = torch.empty((n_rows, H), dtype=emb.dtype, device=emb.device).bernoulli_(1.0 - dropout_p).mul_(1.0 / (1.0 - dropout_p))
+        out, pred = label_head_reference(emb, ffn.weight, ffn.bias, labels, loss, keep, n_rows, label_table, row_ids,
+                                         sample_weight, pos_weight, weight_table)
+        return (out, pred.detach()) if return_pred else out
+    sw = sample_weight if sample_weight is not None else weight_table
+    out, pred = _LabelHeadFn.apply(emb, ffn.weight, ffn.bias, mat, row_ids if label_table is not None else None, sw,
+                                   row_ids if weight_table is not None else None, pos_weight, float(dropout_p), n_rows, kind)
+    return (out, pred) if return_pred else out
+
+
 def task_scores(emb: torch.Tensor, ffn: torch.nn.Linear, n_rows: Optional[int] = None, out: Optional[torch.Tensor] = None,
                 task_major: bool = False) -> torch.Tensor:
     """``pred [n_rows, T]`` (``task_major``: ``[T, n_rows]``): EVERY output of a ``T``-output ``ffn`` for the leading ``n_rows`` rows of

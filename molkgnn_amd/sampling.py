@@ -112,6 +112,22 @@ def pos_weights(labels, tasks=None, num_tasks: int = 1) -> torch.Tensor:
     return out
 
 
+def label_pos_weights(labels) -> torch.Tensor:
+    """``pos_weights`` for a label matrix with holes (``labels [n, T]``, NaN: not measured; ``readout.label_head_loss``): float32
+    ``[T]`` with ``n_negative / n_positive`` per column over its non-NaN entries, 1 for a column without a positive.  With a label
+    matrix a molecule carries many labels at once, so oversampling cannot balance (task, class) cells: this is what does."""
+    y = torch.as_tensor(labels).detach().cpu()
+    if y.dim() != 2 or not y.is_floating_point():
+        raise ValueError("label_pos_weights needs a float [n, T] label matrix (NaN: not measured)")
+    known = ~torch.isnan(y)
+    pos = (known & (y != 0)).sum(dim=0)
+    neg = (known & (y == 0)).sum(dim=0)
+    out = torch.ones(y.shape[1], dtype=torch.float32)
+    has = pos > 0
+    out[has] = (neg[has].double() / pos[has].double()).float()
+    return out
+
+
 def task_oversampling_weights(labels: torch.Tensor, tasks: torch.Tensor) -> torch.Tensor:
     """``oversampling_weights`` per task: a labelled molecule (``tasks >= 0``) gets ``1 / #(molecules of its task and its
     class)``, so every (task, class) cell draws the same total weight; an unlabelled one gets 0 and is never drawn.  For one

@@ -722,9 +722,14 @@ class ResidentShard:
 
     ``weights`` (a float ``[M]`` tensor or array: one loss weight per molecule -- importance weights that undo an oversampling
     draw, label confidence, down-weighted inactives) is kept as ``weight`` (float32, on the host) and uploaded as
-    ``tensors["weight"]``: ``CompactStaticBatch.gather`` hands it to the batch as the weight table of the weighted loss."""
+    ``tensors["weight"]``: ``CompactStaticBatch.gather`` hands it to the batch as the weight table of the weighted loss.
 
-    def __init__(self, shard_or_path, device="cpu", packed: bool = False, byte_cols=None, assays=None, weights=None):
+    ``labels`` (a float ``[M, T]`` tensor or array, NaN for "not measured": the label matrix of a multi-label model, every molecule
+    once with all its assays) is kept as ``labels`` (float32, on the host) and uploaded as ``tensors["labels"]``:
+    ``CompactStaticBatch.gather`` hands it to the batch as the label table of ``readout.label_head_loss``.  Not together with
+    ``assays``: a molecule names one task, or carries a row of labels."""
+
+    def __init__(self, shard_or_path, device="cpu", packed: bool = False, byte_cols=None, assays=None, weights=None, labels=None):
         sh = shard_or_path if isinstance(shard_or_path, Shard) else Shard(str(shard_or_path))
         if not sh.compact_ok:
             raise ValueError(f"{sh.path}: bonds are not reversed pairs with shared byte-valued attributes: no compact form")
@@ -749,6 +754,14 @@ class ResidentShard:
                 .reshape(-1).to(torch.float32).contiguous()
             if self.weight.numel() != sh.n_molecules:
                 raise ValueError(f"weights holds {self.weight.numel()} entries for {sh.n_molecules} molecules")
+        self.labels = None
+        if labels is not None:
+            if assays is not None:
+                raise ValueError("labels (a label matrix) and assays (one task per molecule) exclude each other")
+            self.labels = torch.as_tensor(np.asarray(labels) if not torch.is_tensor(labels) else labels.detach().cpu()) \
+                .to(torch.float32).contiguous()
+            if self.labels.dim() != 2 or self.labels.shape[0] != sh.n_molecules or self.labels.shape[1] < 1:
+                raise ValueError(f"labels must be [{sh.n_molecules}, T], not {tuple(self.labels.shape)}")
         self.packed = bool(packed)
         self.x_col = self.x_rec = self.rec_bytes = self.byte_columns = None
         if byte_cols is not None and not self.packed:
@@ -780,6 +793,8 @@ class ResidentShard:
                 self.tensors["task"] = self.task.to(self.device)
             if self.weight is not None:                      # (nor this one)
                 self.tensors["weight"] = self.weight.to(self.device)
+            if self.labels is not None:                      # (nor this one)
+                self.tensors["labels"] = self.labels.to(self.device)
 
     def nbytes(self) -> int:
         """Bytes of device memory the shard takes (0 for an unpacked shard on the CPU, which uploads nothing; the packed form

@@ -7,7 +7,8 @@ loss the data module selects -- ``BCEWithLogitsLoss()`` for the QSAR assays (``d
 for the docking-score set (``data.py:49-53``) -- and the AdamW groups chosen by parameter name (``model.py:373-382``).
 Scoring: ``GNNModel.predict``, ``evaluate`` (the reference's validation / test loop, ``model.py:221-358, 483-522``) and
 ``evaluate_resident`` (the same from a device-resident shard; ranking a library: ``molkgnn_amd.screening``).
-Multi-task models: ``GNNModel.predict_tasks`` (all outputs of every molecule), ``evaluate_tasks``, ``evaluate_resident_tasks``.
+Multi-task models: ``GNNModel.predict_tasks`` (all outputs of every molecule), ``evaluate_tasks``, ``evaluate_resident_tasks``;
+on a label matrix with holes (``batch.labels``, NaN: not measured): ``evaluate_labels``, ``evaluate_resident_labels``.
 The graph embedding alone: ``GNNModel.embed`` (analogue search: ``screening.nearest``).
 Every atom's exact share of every output: ``GNNModel.atom_contributions`` (a hit list explained: ``screening.explain_resident``).
 All of them, and ``screening``'s shard passes, run the model inside ``evaluation_mode``.
@@ -236,6 +237,31 @@ class GNNModel(torch.nn.Module):
         return task_head_loss(graph_embedding, self.ffn, data.y, task, kind, dropout_p=p,
                               n_rows=getattr(data, 'n_valid_molecules', None), task_table=table, row_ids=rows)
 
+    def _kind_and_pos_weight(self, dev):
+        """``(kind, pos_weight)``: ``_loss_kind()`` with no positive weight, or ``("bce", p [task_dim])`` for
+        ``BCEWithLogitsLoss(reduction='mean', weight=None, pos_weight=p)`` (see ``_weighted_loss``); ``(None, None)`` otherwise."""
+        lf, T = self.loss_func, self.ffn.out_features
+        kind, pw = self._loss_kind(), None
+        if kind is None and type(lf) is BCEWithLogitsLoss and lf.reduction == "mean" and lf.weight is None and lf.pos_weight is not None:
+            p = lf.pos_weight
+            if p.dtype != torch.float32 or p.device != dev or p.numel() not in (1, T):
+                return None, None
+            kind, pw = "bce", p.detach().reshape(-1)
+            if pw.numel() != T:
+                held = getattr(self, "_pos_weight_held", None)
+                if held is None or held[0] is not p or held[1] != p._version:
+                    held = self._pos_weight_held = (p, p._version, pw.expand(T).contiguous())
+                pw = held[2]
+        return kind, pw
+
+    def _label_eval_kind(self, who: str) -> str:
+        """The loss kind an evaluation of a label matrix reports (unweighted): ``_loss_kind()``, or ``"bce"`` for the ``pos_weight``
+        BCE a multi-label model trains with."""
+        lf = self.loss_func
+        if type(lf) is BCEWithLogitsLoss and lf.reduction == "mean" and lf.weight is None:
+            return "bce"
+        return _required_loss_kind(self, who)
+
     def _weighted_loss(self, data):
         """``(kind, pos_weight, sample_weight, weight_table, weight_rows)`` when the loss is one of the HIP head's WEIGHTED losses
         (``readout.task_head_reference``), else None -- ``_loss_kind`` knows nothing of weights and stays as it is.
@@ -245,18 +271,8 @@ class GNNModel(torch.nn.Module):
         batch that carries ``weight`` (float32, one per molecule) or ``weight_table`` with ``weight_rows`` (a resident shard's
         weights and the batch's molecule ids, ``padding.CompactStaticBatch.gather``).  A model with several outputs needs the
         batch's tasks (``task`` / ``task_table``) as well."""
-        lf, T, dev = self.loss_func, self.ffn.out_features, data.x.device
-        kind, pw = self._loss_kind(), None
-        if kind is None and type(lf) is BCEWithLogitsLoss and lf.reduction == "mean" and lf.weight is None and lf.pos_weight is not None:
-            p = lf.pos_weight
-            if p.dtype != torch.float32 or p.device != dev or p.numel() not in (1, T):
-                return None
-            kind, pw = "bce", p.detach().reshape(-1)
-            if pw.numel() != T:
-                held = getattr(self, "_pos_weight_held", None)
-                if held is None or held[0] is not p or held[1] != p._version:
-                    held = self._pos_weight_held = (p, p._version, pw.expand(T).contiguous())
-                pw = held[2]
+        T, dev = self.ffn.out_features, data.x.device
+        kind, pw = self._kind_and_pos_weight(dev)
         if kind is None:
             return None
         sw, table, rows = _batch_weight_fields(data)
@@ -300,7 +316,36 @@ class GNNModel(torch.nn.Module):
         return task_head_reference(graph_embedding, self.ffn.weight, self.ffn.bias, data.y, task, kind, None, nreal, ttable, ids,
                                    sw, pw, table)[0]
 
+    def _label_loss(self, data):
+        """The multi-label loss on a label matrix with holes (``readout.label_head_loss``): every molecule carries a row of labels
+        -- ``data.labels`` (float32 ``[n, T]``, NaN: not measured) or ``data.label_table`` + ``data.label_rows`` (a resident shard's
+        matrix and the batch's molecule ids, ``padding.CompactStaticBatch.gather``) -- so the network runs once per molecule.  The
+        loss is one of ``_loss_kind()`` or the ``pos_weight`` BCE of ``_weighted_loss``; ``batch.weight`` / ``weight_table`` are passed
+        on; ``n_valid_molecules`` is honoured.  The embedding comes from the separate readout operators, as for the task head.  A
+        CPU batch, or head dropout ``p >= 1``, takes the definition (``readout.label_head_reference``) behind ``self.dropout``."""
+        from . import readout as R
+        if _has_tasks(data):
+            raise ValueError("the batch carries both tasks (task / task_table) and a label matrix (labels / label_table): one "
+                             "molecule names one task, or carries a row of labels, not both")
+        kind, pw = self._kind_and_pos_weight(data.x.device)
+        if kind is None:
+            raise ValueError("the batch carries a label matrix (labels / label_table), which GNNModel.loss takes with "
+                             "BCEWithLogitsLoss (optionally pos_weight) or MSELoss; it is never trained on batch.y instead")
+        labels, ltable, lrows = _batch_fields(data, 'labels', 'label_table', 'label_rows')
+        sw, table, rows = _batch_weight_fields(data)
+        nreal = getattr(data, 'n_valid_molecules', None)
+        graph_embedding = self.gnn_model(data)
+        sw, table, ids = _weights_for(graph_embedding, nreal, sw, table, rows, lrows)
+        if data.x.is_cuda and not (self.training and self.dropout.p >= 1.0):
+            return R.label_head_loss(graph_embedding, self.ffn, labels, kind, dropout_p=self.dropout.p if self.training else 0.0,
+                                     n_rows=nreal, label_table=ltable, row_ids=ids, sample_weight=sw, pos_weight=pw,
+                                     weight_table=table)
+        return R.label_head_reference(self.dropout(graph_embedding), self.ffn.weight, self.ffn.bias, labels, kind, None, nreal,
+                                      ltable, ids, sw, pw, table)[0]
+
     def loss(self, data):
+        if _has_labels(data):                                # (new field names: no batch without them changes its route)
+            return self._label_loss(data)
         # a batch that carries loss weights gets them, or an error: never the unweighted loss in silence
         carries = any(f is not None for f in _batch_weight_fields(data))
         weighted = self._weighted_loss(data) if data.x.is_cuda else None
@@ -359,6 +404,10 @@ def _batch_tasks(data):
 
 def _has_tasks(data) -> bool:
     return any(f is not None for f in _batch_fields(data))
+
+
+def _has_labels(data) -> bool:
+    return any(f is not None for f in _batch_fields(data, 'labels', 'label_table', 'label_rows'))
 
 
 def _batch_weight_fields(data):
@@ -683,6 +732,58 @@ def evaluate_resident_tasks(model, resident, batch_size: int, metrics=(), bootst
     true_y = resident.y.to(pred.device).view(-1)
     task = resident.task.to(pred.device).view(-1).long()
     return _task_results(pred, true_y, task, model.ffn.out_features, kind, metrics, table, bootstrap)
+
+
+def _label_results(model, who: str, pred: torch.Tensor, labels: torch.Tensor, metrics, table: dict, bootstrap) -> dict:
+    """The second half of ``evaluate_labels`` and ``evaluate_resident_labels``: the labelled (non-NaN) entries of ``labels [n, T]``,
+    in row-major order, as ``(true, pred row, task)`` triples for ``_task_results``; plus ``n_labelled`` per task."""
+    T = model.ffn.out_features
+    if labels.dim() != 2 or tuple(labels.shape) != (pred.shape[0], T):
+        raise ValueError(f"{who}: the labels must be [{pred.shape[0]}, {T}], not {tuple(labels.shape)}")
+    lab = ~torch.isnan(labels)
+    row, task = lab.nonzero(as_tuple=True)
+    results = _task_results(pred[row], labels[row, task].to(pred.dtype), task, T, model._label_eval_kind(who), metrics, table,
+                            bootstrap)
+    results['n_labelled'] = lab.sum(dim=0).tolist()
+    return results
+
+
+def evaluate_labels(model, batches, metrics=(), bootstrap: Optional[int] = None) -> dict:
+    """``evaluate_tasks`` for a multi-label model on batches that carry a label matrix ``labels`` (float ``[n, T]``, NaN: not
+    measured): ``model.predict_tasks`` per batch (the network runs once per molecule), the labelled entries flattened to ``(true,
+    pred, task)`` triples in row-major order and handed to the per-task machinery of ``evaluate_tasks`` (``_task_results``,
+    ``evaluation.bootstrap_per_task``).  The result has ``evaluate_tasks``' keys -- ``pred_y``, ``true_y`` and ``task`` have one
+    element per labelled ENTRY, ``loss`` is the unweighted multi-label loss -- plus ``n_labelled``, the labelled entries per task."""
+    table = _check_metrics(metrics)
+    bootstrap = _check_bootstrap(bootstrap)
+    model._label_eval_kind("evaluate_labels")
+    with evaluation_mode(model):
+        all_pred, all_labels = [], []
+        for batch in batches:
+            labels = getattr(batch, 'labels', None)
+            if labels is None:
+                raise ValueError("evaluate_labels needs batch.labels (float [n, T], NaN: not measured)")
+            pred, _ = model.predict_tasks(batch)
+            all_pred.append(pred)
+            all_labels.append(labels[:pred.shape[0]].to(pred.device))
+        if not all_pred:
+            raise ValueError("evaluate_labels needs at least one batch")
+        return _label_results(model, "evaluate_labels", torch.cat(all_pred), torch.cat(all_labels), metrics, table, bootstrap)
+
+
+def evaluate_resident_labels(model, resident, batch_size: int, metrics=(), bootstrap: Optional[int] = None) -> dict:
+    """``evaluate_labels`` for a multi-label data set that lives in device memory (``shards.ResidentShard(..., labels=...)``): the
+    same result dictionary, from ``screening.score_resident_tasks`` -- all ``T`` outputs of every molecule of the shard in id
+    order from one captured graph -- with ``resident.labels`` as the label matrix.  Unknown metric names, a shard without
+    ``labels`` and a loss that is none of the head's kinds raise before anything is launched."""
+    from .screening import score_resident_tasks
+    table = _check_metrics(metrics)
+    bootstrap = _check_bootstrap(bootstrap)
+    if getattr(resident, "labels", None) is None:
+        raise ValueError("evaluate_resident_labels needs a shard that holds a label matrix: ResidentShard(..., labels=...)")
+    model._label_eval_kind("evaluate_resident_labels")
+    pred = score_resident_tasks(model, resident, batch_size)
+    return _label_results(model, "evaluate_resident_labels", pred, resident.labels.to(pred.device), metrics, table, bootstrap)
 
 
 def tune_torch_backends() -> None:
