@@ -897,6 +897,40 @@ int mkgnn_label_head_fused(int32_t loss_kind, const float* emb, int64_t emb_stri
  * everything mkgnn_tail_fused_readout_dropout refuses. */
 int mkgnn_tail_fused_weighted(const mkgnn_tail_args* args, float readout_dropout_p, const mkgnn_loss_weights* weights,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* (additive; the ABI version stays 8) The fused tail for SEVERAL outputs: mkgnn_tail_fused_weighted with a T-output head behind
+ * the readout -- the label-matrix head's definition (labels != NULL: labels[i, t], NaN = not measured) or the task-indexed head's
+ * (task != NULL: molecule i names ONE task, -1 or anything outside [0, T) = none, and its label is args->target[i]).  Exactly one
+ * of labels / task is set.  args->head_weight is [T, G], args->head_bias [T] or NULL, args->grad_head_weight [T, G],
+ * args->grad_head_bias [T]; args->pred is ignored and args->target only read with task.
+ *     pred[i * pred_stride + t] = (keep_i * emb_i) . head_weight[t] + head_bias[t]       for EVERY i < n_loss_mols, t < T
+ *     loss = sum over the labelled (i, t) of s_i * term(pred[i, t], y[i, t]) / max(n_labelled, 1)
+ * (SQERR_SUM: not divided; never divided by the sum of the weights), term, s_i and pos_weight [T] as for mkgnn_label_head_*;
+ * a pos_weight entry of exactly 1.0f and sample weights of exactly 1.0f give the bits of a call without them.  An unlabelled
+ * entry is removed by a select: its label and its weight reach nothing.  row_ids == NULL: row i of labels / task (n_label_rows /
+ * n_task >= n_loss_mols); else labels[row_ids[i]] / task[row_ids[i]] of a table with n_label_rows / n_task >= 1 rows, an id outside
+ * it: no label.  The head's dropout element is mol * G + j and the readout's the convention above: the masks are the two heads' and
+ * the tail's for the same {seed, offset}, and the generator advances by exactly one per call that draws.
+ * EXACT: padding molecules (i >= n_loss_mols) get zero gradients; a molecule without a labelled entry exactly zero grad_sim rows,
+ * a task without one exactly zero rows of grad_head_weight / grad_head_bias; no labelled entry at all: loss 0 and every gradient 0.
+ * With T == 1 and a dense label column: the bits of mkgnn_tail_fused_readout_dropout on the same inputs.
+ * The labelled-entry count is taken on the device by a small integer count launch in front of the middle kernel (no read-back, no
+ * float atomics, nothing depends on workgroup arrival order, capturable; it counts the first n_loss_mols rows only).  The entry
+ * obeys the whole pending-work protocol of mkgnn_tail_fused (defer_reduce, mkgnn_tail_defer_projection, mkgnn_tail_flush).
+ * Limits: mkgnn_tail_supported, 1 <= T <= MKGNN_TASK_HEAD_MAX_TASKS, n_loss_mols * T < 2^31 and the MKGNN_TAIL_MAX_* rule (a molecule
+ * beyond it: NaN loss, as in mkgnn_tail_fused).  Refused before any launch: T out of range, both or neither label source,
+ * pos_weight with a squared-error kind, label_stride or pred_stride < T, emb_stride < G, a NULL pred, a table or a vector shorter
+ * than stated above, and everything mkgnn_tail_fused_weighted refuses.  workspace: mkgnn_tail_labels_workspace_bytes (0 for bad
+ * shapes; at least mkgnn_tail_workspace_bytes). */
+typedef struct mkgnn_tail_labels {
+    int32_t n_tasks;                                                       /* T */
+    const float*   labels;  int64_t label_stride;  int64_t n_label_rows;   /* label matrix, NaN = not measured; OR */
+    const int32_t* task;    int64_t n_task;                                /* one task per molecule (-1: none), its label in args->target */
+    const int32_t* row_ids;                                                /* NULL: row i; else the row of the table */
+    float* pred; int64_t pred_stride;                                      /* [n_loss_mols, T], every entry written */
+} mkgnn_tail_labels;
+size_t mkgnn_tail_labels_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols, int32_t T);
+int mkgnn_tail_fused_labels(const mkgnn_tail_args* args, float readout_dropout_p, const mkgnn_tail_labels* labels,
+                            const mkgnn_loss_weights* weights, void* workspace, size_t workspace_bytes, void* stream);
 
 /* (additive; the ABI version stays 8) Every task's logit of every row -- the T-output ffn behind the readout in evaluation mode,
  * for ranking a library per assay:

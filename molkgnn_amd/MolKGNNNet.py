@@ -86,7 +86,12 @@ class MolKGNNNet(torch.nn.Module):
         # small batches (the reference's own regime, README.md:81): batch norm, every layer and the readout in ONE launch, a
         # workgroup per chunk of whole molecules (molkgnn_amd.molecule); None where the model or the batch does not qualify
         # (_atoms: the per-atom contributions are asked for -- the molecule-resident step sums them away inside LDS)
-        if data.x.is_cuda and not save_score and _atoms is None and _mc is None:
+        # (private: a dict as _tail asks for the MULTI-OUTPUT fused tail, readout.tail_labels_loss -- train.GNNModel with
+        # multi_output_tail on.  Where model and mode qualify the molecule-resident step, which hands back an embedding, is not
+        # taken: the tail is asked first.  What only the batch decides -- _tail_limits_ok -- is seen below; the embedding then comes
+        # from the separate readout operators as usual.)
+        multi_tail = isinstance(_tail, dict) and self._multi_tail_applies(_tail, data)
+        if data.x.is_cuda and not save_score and _atoms is None and _mc is None and not multi_tail:
             from . import molecule as _mol
             emb = _mol.net_forward(self, data)
             if emb is not None:                          # (edge_batch_norm's statistics moved inside: molecule.net_forward)
@@ -144,7 +149,7 @@ class MolKGNNNet(torch.nn.Module):
             # (the readout's dropout, p < 1, runs inside the fused tail; p >= 1 keeps the separate operators)
             p_readout = self.dropout.p if (self.dropout is not None and self.dropout.training) else 0.0
             want_tail = (_tail is not None and R._FUSED_TAIL and torch.is_grad_enabled() and p_readout < 1.0 and x.is_cuda
-                         and R.tail_supported(*dims, Ls))
+                         and R.tail_supported(*dims, Ls) and (multi_tail or not isinstance(_tail, dict)))
             # (private: train.GNNModel.predict asks for the predictions themselves -- the forward-only tail, readout.tail_score --
             # with grad mode off and no readout dropout to draw, i.e. in evaluation mode)
             want_score = (_score is not None and R._FUSED_TAIL and R._SCORE_TAIL and not torch.is_grad_enabled() and p_readout == 0.0
@@ -198,6 +203,10 @@ class MolKGNNNet(torch.nn.Module):
             # (private: train.GNNModel.loss asks for the loss itself -- readout, head, loss and all their gradients in one
             # launch, readout.tail_loss -- where that applies; it gets ("loss", value) back, or the embedding as usual)
             if want_tail and sim_sc.requires_grad and R._tail_limits_ok(seg, plan):
+                if multi_tail:                               # {ffn, p_head, n_rows, loss, kw: tail_labels_loss's label source and weights}
+                    return ("loss", R.tail_labels_loss(sim_sc, plan, Ls, lin1, lin2, _tail["ffn"], seg, loss=_tail["loss"],
+                                                       dropout_p=_tail["p_head"], n_rows=_tail["n_rows"],
+                                                       readout_dropout_p=p_readout, **_tail["kw"]))
                 # (ffn, y, dropout p, real molecules[, loss kind: "bce"[, the weighted loss's keywords of tail_loss]])
                 ffn, target, p_head, n_rows, *kind = _tail
                 loss = kind[0] if kind else "bce"
@@ -209,6 +218,16 @@ class MolKGNNNet(torch.nn.Module):
             return R.readout_blocks(sim_sc, plan, Ls, lin1, lin2, self.dropout, seg)
         # pool(lin2(dropout(act(lin1(h)))), batch) -- MolKGNNNet.py:144-146 -- as one operator
         return R.readout(node_representation, lin1, lin2, self.dropout, data.batch, getattr(data, 'num_graphs', None), segments=seg)
+
+    def _multi_tail_applies(self, tail: dict, data) -> bool:
+        """What model and mode decide about the multi-output fused tail, before anything runs: ``want_tail``'s conditions in
+        ``forward`` and a head of at most 32 outputs."""
+        if not (data.x.is_cuda and R._FUSED_TAIL and torch.is_grad_enabled()):
+            return False
+        p_readout = self.dropout.p if (self.dropout is not None and self.dropout.training) else 0.0
+        Ls = self.gnn.layers[-1].L
+        dims = (sum(Ls), self.graph_embedding_lin1.weight.shape[0], self.graph_embedding_lin2.weight.shape[0])
+        return p_readout < 1.0 and R.tail_labels_supported(tail["ffn"].out_features) and R.tail_supported(*dims, Ls)
 
     def kernel_column_layout(self, layer: int, device=None):
         """``(column_degree, column_kernel)`` of convolution layer ``layer`` (int32 ``[K_layer]`` each): column ``c`` of that layer's

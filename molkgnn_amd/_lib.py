@@ -267,6 +267,14 @@ class LossWeights(C.Structure):
                 ("pos_weight", C.c_void_p)]
 
 
+class TailLabels(C.Structure):
+    """``mkgnn_tail_labels``: the T-output head of ``mkgnn_tail_fused_labels`` -- a label matrix with holes or a task per molecule
+    (exactly one), optionally read through row ids, and where ``pred [n_loss_mols, T]`` goes."""
+    _fields_ = [("n_tasks", C.c_int32), ("labels", C.c_void_p), ("label_stride", C.c_int64), ("n_label_rows", C.c_int64),
+                ("task", C.c_void_p), ("n_task", C.c_int64), ("row_ids", C.c_void_p), ("pred", C.c_void_p),
+                ("pred_stride", C.c_int64)]
+
+
 EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn_unit_rows8", "mkgnn_workspace_bytes",
            "mkgnn_kernelsetconv_forward", "mkgnn_kernelsetconv_backward", "mkgnn_segment_sum_rows",
            "mkgnn_readout_hidden_stride", "mkgnn_readout_workspace_bytes", "mkgnn_readout_forward",
@@ -289,7 +297,7 @@ EXPORTS = ("mkgnn_abi_version", "mkgnn_last_error", "mkgnn_row_inv_norm", "mkgnn
            "mkgnn_gather_compact_workspace_bytes", "mkgnn_gather_compact_packed", "mkgnn_topk_update", "mkgnn_topk_workspace_bytes",
            "mkgnn_task_head_workspace_bytes", "mkgnn_task_head_forward", "mkgnn_task_head_backward", "mkgnn_task_head_fused",
            "mkgnn_task_head_weighted_forward", "mkgnn_task_head_weighted_backward", "mkgnn_task_head_weighted_fused",
-           "mkgnn_tail_fused_weighted",
+           "mkgnn_tail_fused_weighted", "mkgnn_tail_labels_workspace_bytes", "mkgnn_tail_fused_labels",
            "mkgnn_label_head_workspace_bytes", "mkgnn_label_head_forward", "mkgnn_label_head_backward", "mkgnn_label_head_fused",
            "mkgnn_task_scores", "mkgnn_topk_tasks_workspace_bytes", "mkgnn_topk_update_tasks", "mkgnn_embed_cosine",
            "mkgnn_atom_contributions", "mkgnn_atom_contributions_workspace_bytes", "mkgnn_embed_max_cosine",
@@ -390,6 +398,11 @@ def load() -> C.CDLL:
     lib.mkgnn_tail_fused_weighted.restype = C.c_int
     lib.mkgnn_tail_fused_weighted.argtypes = [C.POINTER(TailArgs), C.c_float, C.POINTER(LossWeights), C.c_void_p, C.c_size_t,
                                               C.c_void_p]
+    lib.mkgnn_tail_labels_workspace_bytes.restype = C.c_size_t
+    lib.mkgnn_tail_labels_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32]
+    lib.mkgnn_tail_fused_labels.restype = C.c_int
+    lib.mkgnn_tail_fused_labels.argtypes = [C.POINTER(TailArgs), C.c_float, C.POINTER(TailLabels), C.POINTER(LossWeights), C.c_void_p,
+                                            C.c_size_t, C.c_void_p]
     lib.mkgnn_readout_dropout_mask.restype = C.c_int
     lib.mkgnn_readout_dropout_mask.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]
     lib.mkgnn_flat_copy.restype = C.c_int

@@ -236,6 +236,24 @@ int tail_middle_blocks(int64_t n_loss_mols);
 hipError_t launch_tail_middle(const TailMidArgs& a, int nb, int loss_kind, hipStream_t st);
 // the forward-only form (mkgnn_tail_score): reads z, rin, cin, mol_ptr, the weights, H, G, n_mols, n_loss, mg; writes pred and emb
 hipError_t launch_tail_score(const TailMidArgs& a, int nb, hipStream_t st);
+// kgnn_tail_labels.hip: the training form for a T-output head (mkgnn_tail_fused_labels) -- m as for launch_tail_middle, but
+// m.wh [T, G], m.bh [T] or null, m.pw [T] or null, m.y the task source's labels (unused with a label matrix), m.pred unused
+struct TailLabelArgs {
+    TailMidArgs m;
+    int T;
+    const float* labels; int64_t ls; int64_t n_label_rows;      // the label matrix (NaN: not measured), OR
+    const int32_t* task; int64_t n_task;                        // one task per molecule
+    const int32_t* row_ids;                                     // null: row gi; else the row of the table (outside it: no label)
+    float* pred; int64_t ps;                                    // [n_loss, T]
+    int* counts; int n_counts;                                  // [n_counts] partial labelled-entry counts: tail_label_count_blocks
+};
+constexpr int TAIL_LABEL_MAX_COUNTS = 64;   // (one wave of the middle kernel's prologue adds them up)
+// a workgroup's slab: b1 [32] | W2 [32][32] | b2 [32] | wh [T][32] (room for 32 tasks) | bh [32] | loss
+constexpr int TAILL_B1 = 0, TAILL_W2 = 32, TAILL_B2 = 32 + 1024, TAILL_WH = TAILL_B2 + 32, TAILL_BH = TAILL_WH + 32 * 32,
+              TAILL_LOSS = TAILL_BH + 32, TAILL_SLAB = (TAILL_LOSS + 1 + 3) / 4 * 4;
+int tail_label_count_blocks(int64_t n_loss_mols, int T);
+// the count launch (a.n_counts blocks), then the middle kernel: loss_kind and a.m.rdrop_p as for launch_tail_middle
+hipError_t launch_tail_labels_middle(const TailLabelArgs& a, int nb, int loss_kind, hipStream_t st);
 // kgnn_tail_mc.hip: the Monte Carlo dropout form (mkgnn_tail_score_mc) -- the forward-only form's inputs in `m`, and of it also
 // drop_p, rdrop_p and rng (the {seed, offset} pair: read, never advanced); m.pred and m.emb may each be null
 struct TailMcArgs {

@@ -1103,7 +1103,7 @@ static int64_t project_bwd_blocks(const BlockProjArgs& b, int* tpw_out, int64_t 
 
 // ---- the fused tail (ABI v6; kgnn_tail.hip): project | per-molecule middle | project^T + dW1 | one reduction ----
 struct TailWs { size_t z, dz, slab_atoms, slab_tail, total; int slab_atoms_stride; };
-static TailWs tail_ws(const ReadoutDims& d, int64_t n_atoms, int64_t n_mols) {
+static TailWs tail_ws(const ReadoutDims& d, int64_t n_atoms, int64_t n_mols, int slab_floats = TAIL_SLAB) {
     TailWs w;
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     w.slab_atoms_stride = d.HP * d.FP + d.HP;
@@ -1111,7 +1111,7 @@ static TailWs tail_ws(const ReadoutDims& d, int64_t n_atoms, int64_t n_mols) {
     w.dz = up(w.z + (size_t)n_atoms * 32 * 4);
     w.slab_atoms = up(w.dz + (size_t)n_atoms * 32 * 4);
     w.slab_tail = up(w.slab_atoms + (size_t)2 * RO_ATOM_BLOCKS * w.slab_atoms_stride * 4);
-    w.total = up(w.slab_tail + (size_t)(n_mols < TAIL_MAX_BLOCKS ? n_mols : TAIL_MAX_BLOCKS) * TAIL_SLAB * 4);   // (an upper bound for any n_loss_mols <= n_mols)
+    w.total = up(w.slab_tail + (size_t)(n_mols < TAIL_MAX_BLOCKS ? n_mols : TAIL_MAX_BLOCKS) * slab_floats * 4);   // (an upper bound for any n_loss_mols <= n_mols)
     return w;
 }
 
@@ -1160,17 +1160,39 @@ static int tail_project(const char* who, const mkgnn_tail_args* p, Own&& own, si
                                   need(ro->F, ro->H, ro->G, p->n_atoms, p->n_mols), ws, ws_bytes, st, b, d);
 }
 
-// rp: the readout's dropout (mkgnn_tail_fused_readout_dropout), 0 for mkgnn_tail_fused; wt: mkgnn_tail_fused_weighted's weights
+// the multi-output tail's workspace: the tail's with slabs for a [32][32] head gradient, then the partial labelled-entry counts
+static size_t tail_labels_need(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols) {
+    ReadoutDims d;
+    if (!blocks_dims(K, H, G, d) || n_atoms < 1 || n_mols < 1) return 0;
+    return tail_ws(d, n_atoms, n_mols, TAILL_SLAB).total + 256;
+}
+size_t mkgnn_tail_labels_workspace_bytes(int32_t K, int32_t H, int32_t G, int64_t n_atoms, int64_t n_mols, int32_t T) {
+    if (T < 1 || T > MKGNN_TASK_HEAD_MAX_TASKS || H > 32 || G > 32) return 0;
+    return tail_labels_need(K, H, G, n_atoms, n_mols);   // (the same for every T: a captured step's workspace does not move)
+}
+
+// rp: the readout's dropout (mkgnn_tail_fused_readout_dropout), 0 for mkgnn_tail_fused; wt: mkgnn_tail_fused_weighted's weights;
+// lb: mkgnn_tail_fused_labels' T-output head and its labels (kgnn_tail_labels.hip in place of the single-task middle kernel)
 static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void* ws, size_t ws_bytes, void* stream,
-                      const mkgnn_loss_weights* wt = nullptr) {
+                      const mkgnn_loss_weights* wt = nullptr, const mkgnn_tail_labels* lb = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     BlockProjArgs b{};
     ReadoutDims d;
     auto own = [&]() {                                   // what the training tail asks beyond the scoring one
         const mkgnn_readout_params* ro = &p->readout;
         if (!p->in_rowptr || !p->in_col || !p->out_rowptr || !p->out_col || !p->mol_ptr || !p->atom_mol || !ro->lin1_weight ||
-            !ro->lin2_weight || !p->head_weight || !p->target || !p->pred || !p->loss || !p->grad_sim)
+            !ro->lin2_weight || !p->head_weight || (!p->target && (!lb || lb->task)) || (lb ? !lb->pred : !p->pred) || !p->loss || !p->grad_sim)
             return api_fail("%s: null pointer", who);
+        if (lb) {
+            const int32_t T = lb->n_tasks;
+            if (T < 1 || T > MKGNN_TASK_HEAD_MAX_TASKS) return api_fail("%s: %d tasks outside [1, %d]", who, (int)T, MKGNN_TASK_HEAD_MAX_TASKS);
+            if ((lb->labels == nullptr) == (lb->task == nullptr)) return api_fail("%s: exactly one of labels and task", who);
+            if (p->n_loss_mols * T >= (int64_t)1 << 31)
+                return api_fail("%s: %lld molecules of %d tasks: the labelled-entry count needs n_loss_mols * T < 2^31", who, (long long)p->n_loss_mols, (int)T);
+            if (lb->pred_stride < T || (lb->labels && lb->label_stride < T)) return api_fail("%s: label or pred row stride below T = %d", who, (int)T);
+            const int64_t rows = lb->labels ? lb->n_label_rows : lb->n_task;
+            if (lb->row_ids ? rows < 1 : rows < p->n_loss_mols) return api_fail("%s: the label source holds %lld rows", who, (long long)rows);
+        }
         if (p->dropout_p < 0.f || p->dropout_p >= 1.f) return api_fail("%s: dropout probability %g outside [0, 1)", who, (double)p->dropout_p);
         if (p->dropout_p > 0.f && (!p->rng_state || !p->rng_used)) return api_fail("%s: dropout needs rng_state and rng_used", who);
         if (!(rp >= 0.f && rp < 1.f)) return api_fail("%s: readout dropout probability %g outside [0, 1)", who, (double)rp);
@@ -1182,9 +1204,9 @@ static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void*
             return api_fail("%s: sample_weight holds %lld entries", who, (long long)wt->n_sample_weight);
         return 0;
     };
-    if (int rc = tail_project(who, p, own, mkgnn_tail_workspace_bytes, ws, ws_bytes, st, b, d)) return rc;
+    if (int rc = tail_project(who, p, own, lb ? tail_labels_need : mkgnn_tail_workspace_bytes, ws, ws_bytes, st, b, d)) return rc;
     const mkgnn_readout_params* ro = &p->readout;
-    const TailWs w = tail_ws(d, p->n_atoms, p->n_mols);
+    const TailWs w = tail_ws(d, p->n_atoms, p->n_mols, lb ? TAILL_SLAB : TAIL_SLAB);
     float* const z = (float*)((char*)ws + w.z);
     float* const dz = (float*)((char*)ws + w.dz);
     hipError_t e = hipSuccess;
@@ -1195,14 +1217,25 @@ static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void*
     m.b1 = ro->lin1_bias; m.w2 = ro->lin2_weight; m.b2 = ro->lin2_bias; m.wh = p->head_weight; m.bh = p->head_bias; m.y = p->target;
     m.H = ro->H; m.G = ro->G; m.drop_p = p->dropout_p; m.rng = p->rng_state; m.rdrop_p = rp;
     m.emb = p->emb; m.es = p->emb_stride; m.pred = p->pred;
-    m.slab = (float*)((char*)ws + w.slab_tail); m.slab_stride = TAIL_SLAB;
+    m.slab = (float*)((char*)ws + w.slab_tail); m.slab_stride = lb ? TAILL_SLAB : TAIL_SLAB;
     m.mg = tail_group_size(p->n_loss_mols);
     if (wt) {
         m.sw = wt->sample_weight; m.wids = wt->sample_weight ? wt->weight_ids : nullptr; m.n_sw = wt->n_sample_weight;
         m.pw = wt->pos_weight;
     }
     const int nbm = tail_middle_blocks(p->n_loss_mols);
-    e = launch_tail_middle(m, nbm, p->loss_kind, st);
+    if (lb) {                                            // (the count launch, then the T-output middle kernel)
+        TailLabelArgs la{};
+        la.m = m; la.m.pred = nullptr;
+        la.T = lb->n_tasks;
+        la.labels = lb->labels; la.ls = lb->label_stride; la.n_label_rows = lb->n_label_rows;
+        la.task = lb->task; la.n_task = lb->n_task; la.row_ids = lb->row_ids;
+        la.pred = lb->pred; la.ps = lb->pred_stride;
+        la.counts = (int*)((char*)ws + w.total); la.n_counts = tail_label_count_blocks(p->n_loss_mols, lb->n_tasks);
+        e = launch_tail_labels_middle(la, nbm, p->loss_kind, st);
+    } else {
+        e = launch_tail_middle(m, nbm, p->loss_kind, st);
+    }
     if (e != hipSuccess) return api_hip_fail(who, e);
     // (3) d sim[block] = W1[:, block]^T d z,  dW1 partials   (as mkgnn_readout_blocks_backward)
     b.dz = dz; b.dsim = p->grad_sim; b.dss = p->grad_sim_stride;
@@ -1250,12 +1283,21 @@ static int tail_fused(const char* who, const mkgnn_tail_args* p, float rp, void*
         e = hipMemsetAsync(p->grad_lin1_weight, 0, (size_t)ro->H * b.K * 4, st);
         if (e != hipSuccess) return api_hip_fail(who, e);
     }
+    if (lb) {                                            // (the head's segments: [T][32] and [T], reduced in block order as the others)
+        add(m.slab + TAILL_B1, TAILL_SLAB, nbm, 32, 1, ro->H, p->grad_lin1_bias, 0);
+        add(m.slab + TAILL_W2, TAILL_SLAB, nbm, 32, ro->G, ro->H, p->grad_lin2_weight, 0);
+        add(m.slab + TAILL_B2, TAILL_SLAB, nbm, 32, 1, ro->G, p->grad_lin2_bias, 0);
+        add(m.slab + TAILL_WH, TAILL_SLAB, nbm, 32, lb->n_tasks, ro->G, p->grad_head_weight, 0);
+        add(m.slab + TAILL_BH, TAILL_SLAB, nbm, 32, 1, lb->n_tasks, p->grad_head_bias, 0);
+        add(m.slab + TAILL_LOSS, TAILL_SLAB, nbm, 1, 1, 1, p->loss, 0);
+    } else {
     add(m.slab + TAIL_B1, TAIL_SLAB, nbm, 32, 1, ro->H, p->grad_lin1_bias, 0);
     add(m.slab + TAIL_W2, TAIL_SLAB, nbm, 32, ro->G, ro->H, p->grad_lin2_weight, 0);
     add(m.slab + TAIL_B2, TAIL_SLAB, nbm, 32, 1, ro->G, p->grad_lin2_bias, 0);
     add(m.slab + TAIL_WH, TAIL_SLAB, nbm, 32, 1, ro->G, p->grad_head_weight, 0);
     add(m.slab + TAIL_BH, TAIL_SLAB, nbm, 1, 1, 1, p->grad_head_bias, 0);
     add(m.slab + TAIL_LOSS, TAIL_SLAB, nbm, 1, 1, 1, p->loss, 0);
+    }
     r.drop_p = p->dropout_p > 0.f ? p->dropout_p : rp; r.rng = p->rng_state; r.rng_used = p->rng_used;
     if (p->defer_reduce && blk > 0) {                    // round 6: off the critical chain -- see mkgnn_tail_args.defer_reduce
         e = hipGetLastError();                           // (this call's launches so far: a failed one is reported, not left pending)
@@ -1301,6 +1343,12 @@ int mkgnn_tail_fused_readout_dropout(const mkgnn_tail_args* p, float readout_dro
 int mkgnn_tail_fused_weighted(const mkgnn_tail_args* p, float readout_dropout_p, const mkgnn_loss_weights* weights, void* ws,
                               size_t ws_bytes, void* stream) {
     return tail_fused("mkgnn_tail_fused_weighted", p, readout_dropout_p, ws, ws_bytes, stream, weights);
+}
+
+int mkgnn_tail_fused_labels(const mkgnn_tail_args* p, float readout_dropout_p, const mkgnn_tail_labels* labels,
+                            const mkgnn_loss_weights* weights, void* ws, size_t ws_bytes, void* stream) {
+    if (!labels) return api_fail("mkgnn_tail_fused_labels: null argument");
+    return tail_fused("mkgnn_tail_fused_labels", p, readout_dropout_p, ws, ws_bytes, stream, weights, labels);
 }
 
 // ---- the forward-only tail (evaluation mode): project | the middle's forward phases -- two launches, pred and emb only ----

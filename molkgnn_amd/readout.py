@@ -2108,9 +2108,10 @@ class _TailFn(torch.autograd.Function):
         return _TailFn._run(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind, p_readout, None)
 
     @staticmethod
-    def _run(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind, p_readout, weights):
+    def _run(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind, p_readout, weights, labels=None):
         """The forward of ``_TailFn`` (``weights`` None) and of ``_WeightedTailFn`` (``weights``: (sw, wids, pw), float32 / int32
-        contiguous device tensors or None each -- ``mkgnn_tail_fused_weighted``)."""
+        contiguous device tensors or None each -- ``mkgnn_tail_fused_weighted``); ``labels``: ``_TailLabelsFn``'s (label matrix,
+        task vector, row ids) -- ``mkgnn_tail_fused_labels``, a ``T``-output ``wh [T, G]`` with ``pred [n_rows, T]``."""
         global _TAIL_PROJECT_NEXT
         project, _TAIL_PROJECT_NEXT = _TAIL_PROJECT_NEXT, False         # (tail_loss's one-shot: see there)
         lib = _lib.load()
@@ -2120,16 +2121,16 @@ class _TailFn(torch.autograd.Function):
         w1c, w2c = w1.contiguous(), w2.contiguous()
         H, G = w1c.shape[0], w2c.shape[0]
         whc = wh.reshape(-1).contiguous()
-        y = target.reshape(-1).float().contiguous()
+        y = target.reshape(-1).float().contiguous() if target is not None else None
         B = int(n_rows)
-        pred = torch.empty(B, dtype=torch.float32, device=dev)
+        pred = torch.empty(B if labels is None else (B, wh.shape[0]), dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         K4 = K + (-K) % 4
         gsim = torch.empty((n, K4), dtype=torch.float32, device=dev)[:, :K]     # block rows: only every atom's own block is written
         gw1, gw2, gwh = torch.empty_like(w1c), torch.empty_like(w2c), torch.empty_like(whc)
         gb1 = torch.empty_like(b1) if b1 is not None else None
         gb2 = torch.empty_like(b2) if b2 is not None else None
-        gbh = torch.empty(1, dtype=torch.float32, device=dev) if bh is not None else None
+        gbh = torch.empty(1 if labels is None else wh.shape[0], dtype=torch.float32, device=dev) if bh is not None else None
         # (one generator state for the head's dropout and the readout's: read once, advanced by one -- mkgnn_readout_dropout_mask
         # gives the readout's mask for the pair left in ctx.rng_used)
         drop = p_drop > 0.0 or p_readout > 0.0
@@ -2138,7 +2139,7 @@ class _TailFn(torch.autograd.Function):
         a, keep = _tail_args(sim, plan, blocks, seg, B, w1c, b1, w2c, b2, whc, bh)
         rout, cout = plan.csr_out
         a.out_rowptr, a.out_col = rout.data_ptr(), cout.data_ptr()
-        a.target = y.data_ptr()
+        a.target = _lib.ptr(y)
         a.dropout_p, a.rng_state, a.rng_used = float(p_drop), _lib.ptr(rng), _lib.ptr(used)
         a.pred, a.loss = pred.data_ptr(), loss.data_ptr()
         a.grad_sim, a.grad_sim_stride = gsim.data_ptr(), K4
@@ -2153,13 +2154,27 @@ class _TailFn(torch.autograd.Function):
         ctx.params = (w1, b1, w2, b2, wh, bh)
         ctx.dev = dev
         with torch.cuda.device(dev):
-            ws = _tail_workspace(dev, int(lib.mkgnn_tail_workspace_bytes(K, H, G, n, seg.size)))
+            if labels is None:
+                ws = _tail_workspace(dev, int(lib.mkgnn_tail_workspace_bytes(K, H, G, n, seg.size)))
+            else:
+                ws = _tail_workspace(dev, int(lib.mkgnn_tail_labels_workspace_bytes(K, H, G, n, seg.size, wh.shape[0])))
             if ctx.deferred and project:
                 # the projection d sim = d z . W1[:, block] too (one-shot; MKGNN_TAIL_PROJECT_IN_PREPASS=0: ignored): the last
                 # convolution's backward, gsim's only reader, forms it in its coefficient pre-pass and gsim is never written --
                 # anything else that comes first (tail_flush, tail_score, another loss) makes the launch that was left out
                 _lib.check(lib.mkgnn_tail_defer_projection(1), "mkgnn_tail_defer_projection")
-            if weights is not None:
+            if labels is not None:
+                mat, task, ids = labels
+                tl, T = _lib.TailLabels(), wh.shape[0]
+                tl.n_tasks, tl.row_ids, tl.pred, tl.pred_stride = T, _lib.ptr(ids), pred.data_ptr(), T
+                if mat is not None:
+                    tl.labels, tl.label_stride, tl.n_label_rows = mat.data_ptr(), T, mat.numel() // T
+                else:
+                    tl.task, tl.n_task = task.data_ptr(), task.numel()
+                lw = _loss_weights(*weights)
+                _lib.check(lib.mkgnn_tail_fused_labels(ctypes.byref(a), float(p_readout), ctypes.byref(tl), ctypes.byref(lw),
+                                                       ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "mkgnn_tail_fused_labels")
+            elif weights is not None:
                 lw = _loss_weights(*weights)
                 _lib.check(lib.mkgnn_tail_fused_weighted(ctypes.byref(a), float(p_readout), ctypes.byref(lw), ws.data_ptr(),
                                                          ws.numel(), _lib.stream_ptr(dev)), "mkgnn_tail_fused_weighted")
@@ -2213,6 +2228,89 @@ class _WeightedTailFn(_TailFn):
     @staticmethod
     def backward(ctx, grad_loss):
         return (*_TailFn.backward(ctx, grad_loss), None, None, None)
+
+
+class _TailLabelsFn(_TailFn):
+    """``_TailFn`` for a ``T``-output head (``mkgnn_tail_fused_labels``): a label matrix with holes (``mat [rows, T]``, NaN: not
+    measured) or a task per molecule (``task``, its label in ``target``), either read directly or through ``ids``; sample weights
+    and ``pw [T]`` as ``_WeightedTailFn``'s.  Same deferral, hook and contiguity rules, same single backward; ``ctx.pred`` is
+    ``[n_rows, T]``."""
+
+    @staticmethod
+    def forward(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind, p_readout, mat, task, ids, sw, wids, pw):
+        weights = (_f32(sw), _i32(wids), _f32(pw))
+        labels = (_f32(mat), _i32(task), _i32(ids))
+        ctx.weights, ctx.labels = weights, labels           # (held for the launches in flight; a deferred launch order reads neither)
+        return _TailFn._run(ctx, sim, w1, b1, w2, b2, wh, bh, target, seg, plan, blocks, p_drop, n_rows, kind, p_readout, weights, labels)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        return (*_TailFn.backward(ctx, grad_loss), None, None, None, None, None, None)
+
+
+# MKGNN_MULTI_TAIL=1: GNNModel.loss takes the multi-output fused tail for label-matrix and task-indexed batches where
+# GNNModel.multi_output_tail is None (the default: off)
+_MULTI_TAIL = os.environ.get("MKGNN_MULTI_TAIL", "0") == "1"
+
+
+def tail_labels_supported(T: int) -> bool:
+    """The head widths ``mkgnn_tail_fused_labels`` takes (beside ``tail_supported`` and ``_tail_limits_ok``)."""
+    return 1 <= int(T) <= _lib.TASK_HEAD_MAX_TASKS
+
+
+def tail_labels_loss(sim: torch.Tensor, plan, blocks, lin1: torch.nn.Linear, lin2: torch.nn.Linear, ffn: torch.nn.Linear,
+                     seg: "MoleculeSegments", labels: Optional[torch.Tensor] = None, label_table: Optional[torch.Tensor] = None,
+                     task: Optional[torch.Tensor] = None, task_table: Optional[torch.Tensor] = None,
+                     target: Optional[torch.Tensor] = None, row_ids: Optional[torch.Tensor] = None, loss: str = "bce",
+                     dropout_p: float = 0.0, n_rows: Optional[int] = None, readout_dropout_p: float = 0.0,
+                     sample_weight: Optional[torch.Tensor] = None, pos_weight: Optional[torch.Tensor] = None,
+                     weight_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``label_head_loss(readout_blocks(sim, ...), ffn, labels, ...)`` or ``task_head_loss(readout_blocks(sim, ...), ffn, target,
+    task, ...)`` -- the two multi-output heads' definitions (``label_head_reference`` / ``task_head_reference``) behind the tail's
+    readout -- as ONE operator whose forward also takes every gradient (``_TailLabelsFn``, ``mkgnn_tail_fused_labels``).  Exactly
+    one label source: ``labels [>= n_rows, T]`` (float32, NaN: not measured), ``label_table [M, T]`` with ``row_ids``, ``task
+    [>= n_rows]`` (int32, -1: none) with ``target``, or ``task_table [M]`` with ``row_ids`` and ``target``.  ``weight_table`` is read
+    through the same ``row_ids``.  ``pred [n_rows, T]`` (every entry) stays on the node (``loss.grad_fn.pred``), as ``_TailFn``'s.
+    The caller has checked ``tail_supported``, ``tail_labels_supported`` and ``_tail_limits_ok``."""
+    who = "tail_labels_loss"
+    kind = loss_kind(loss)
+    n_rows = seg.size if n_rows is None else int(n_rows)
+    T = ffn.out_features
+    if sum(t is not None for t in (labels, label_table, task, task_table)) != 1:
+        raise ValueError(f"{who} needs exactly one of labels, label_table, task and task_table")
+    table = label_table if label_table is not None else task_table
+    if table is not None and (row_ids is None or table.shape[0] < 1):
+        raise ValueError(f"{who}: a table needs row_ids and at least one row")
+    mat = labels if labels is not None else label_table
+    if mat is not None and (mat.dim() != 2 or mat.shape[1] != T or not mat.is_floating_point()):
+        raise ValueError(f"{who}: the labels must be a float [rows, {T}] matrix for a {T}-output linear layer, not {tuple(mat.shape)}")
+    tsk = task if task is not None else task_table
+    if tsk is not None and (target is None or target.numel() < n_rows):
+        raise ValueError(f"{who}: a task per molecule needs a target per (leading) molecule")
+    if not tail_labels_supported(T) or n_rows * T >= 2 ** 31:
+        raise ValueError(f"{who}: {T} outputs for {n_rows} molecules outside the multi-output tail")
+    _check_loss_weights(loss, T, sample_weight, pos_weight, weight_table, row_ids)
+    uses_ids = table is not None or weight_table is not None
+    per_mol = [t for t in (labels, task, sample_weight, row_ids if uses_ids else None) if t is not None]
+    if n_rows <= 0 or n_rows > seg.size or any(t.shape[0] < n_rows for t in per_mol):
+        raise ValueError(f"{who} needs a label row or a task, a weight (or a row id) per (leading) molecule")
+    if not 0.0 <= dropout_p < 1.0 or not 0.0 <= readout_dropout_p < 1.0:
+        raise ValueError(f"dropout probabilities {dropout_p}, {readout_dropout_p} outside [0, 1)")
+    for name, t in (("labels", labels), ("label_table", label_table), ("task", task), ("task_table", task_table),
+                    ("target", target if tsk is not None else None), ("row_ids", row_ids if uses_ids else None),
+                    ("sample_weight", sample_weight), ("pos_weight", pos_weight), ("weight_table", weight_table)):
+        if t is not None:
+            _lib.require_gpu_tensor(t, name)
+    global _TAIL_PROJECT_NEXT
+    _TAIL_PROJECT_NEXT = bool(_DEFER_TAIL_REDUCE and _sole_reader_is_the_convolution(sim))
+    try:
+        return _TailLabelsFn.apply(sim, lin1.weight, lin1.bias, lin2.weight, lin2.bias, ffn.weight, ffn.bias,
+                                   target if tsk is not None else None, seg, plan, tuple(blocks), float(dropout_p), n_rows, kind,
+                                   float(readout_dropout_p), mat, tsk, row_ids if table is not None else None,
+                                   sample_weight if sample_weight is not None else weight_table,
+                                   row_ids if weight_table is not None else None, pos_weight)
+    finally:
+        _TAIL_PROJECT_NEXT = False
 
 
 def _sole_reader_is_the_convolution(sim: torch.Tensor) -> bool:

@@ -44,8 +44,29 @@ class GNNModel(torch.nn.Module):
         self.activate_func = ReLU()
         self.loss_func = BCEWithLogitsLoss() if loss_func is None else loss_func     # model.py:156: the data module's loss
 
+    # The multi-output fused tail (readout.tail_labels_loss) for label-matrix and task-indexed batches: None follows
+    # MKGNN_MULTI_TAIL (read once at import; the default is off), True / False force it.  Where it does not apply -- a CPU batch,
+    # head dropout p >= 1, more than 32 outputs, a molecule beyond a chunk, an unknown batch inside a capture -- the loss takes
+    # exactly the route it takes with the attribute off.
+    multi_output_tail: Optional[bool] = None
+
     def forward(self, data):
         return self._head(self.dropout(self.gnn_model(data)))
+
+    def _multi_tail_embedding(self, data, kind: str, pw, source: dict, srows, sw, table, rows, nreal):
+        """``self.gnn_model(data)`` for a multi-output loss -- with ``multi_output_tail`` on, asked for the fused tail first:
+        ``("loss", value)`` where it applies, the embedding as usual where it does not.  ``source``: ``tail_labels_loss``'s label
+        source (read through ``srows``); ``sw, table, rows``: the batch's weight fields."""
+        from . import readout as R
+        on = R._MULTI_TAIL if self.multi_output_tail is None else bool(self.multi_output_tail)
+        # (a weight table read through other ids than the labels' is looked up per molecule: that needs the molecule count)
+        known = not (table is not None and srows is not None and rows is not srows and nreal is None)
+        if not (on and data.x.is_cuda and known and not (self.training and self.dropout.p >= 1.0)):
+            return self.gnn_model(data)
+        w, wtable, ids = _weights_for(None, nreal, sw, table, rows, srows)
+        kw = dict(source, row_ids=ids, sample_weight=w, pos_weight=pw, weight_table=wtable)
+        return self.gnn_model(data, _tail=dict(ffn=self.ffn, p_head=self.dropout.p if self.training else 0.0, n_rows=nreal,
+                                               loss=kind, kw=kw))
 
     def _head(self, graph_embedding):
         if self.ffn.out_features == 1 and self.ffn.bias is not None and graph_embedding.dim() == 2:
@@ -227,13 +248,17 @@ class GNNModel(torch.nn.Module):
         """The masked multi-task loss (``readout.task_head_loss``): every molecule contributes the loss of the ONE output its task
         names -- ``data.task`` (one int32 task index per molecule, -1: no label; ``sampling.task_index``) or ``data.task_table`` +
         ``data.task_rows`` (a resident shard's table and the batch's molecule ids, ``padding.CompactStaticBatch.gather``).  The
-        embedding comes from the separate readout operators: the fused tail and the molecule-resident step are single-task."""
+        embedding comes from the separate readout operators (the molecule-resident step is single-task); with
+        ``multi_output_tail`` on, the multi-output fused tail is asked first (``_multi_tail_embedding``)."""
         from .readout import task_head_loss
         p = self.dropout.p if (self.training and self.dropout.p < 1.0) else 0.0
-        graph_embedding = self.gnn_model(data)
+        task, table, rows = _batch_tasks(data)
+        graph_embedding = self._multi_tail_embedding(data, kind, None, dict(task=task, task_table=table, target=data.y), rows,
+                                                     None, None, None, getattr(data, 'n_valid_molecules', None))
+        if isinstance(graph_embedding, tuple):               # (multi_output_tail: the fused tail took it)
+            return graph_embedding[1]
         if self.training and self.dropout.p >= 1.0:
             graph_embedding = self.dropout(graph_embedding)
-        task, table, rows = _batch_tasks(data)
         return task_head_loss(graph_embedding, self.ffn, data.y, task, kind, dropout_p=p,
                               n_rows=getattr(data, 'n_valid_molecules', None), task_table=table, row_ids=rows)
 
@@ -294,7 +319,10 @@ class GNNModel(torch.nn.Module):
         nreal = getattr(data, 'n_valid_molecules', None)
         task, ttable, trows = _batch_tasks(data)
         if task is not None or ttable is not None:
-            graph_embedding = self.gnn_model(data)
+            graph_embedding = self._multi_tail_embedding(data, kind, pw, dict(task=task, task_table=ttable, target=data.y), trows,
+                                                         sw, table, rows, nreal)
+            if isinstance(graph_embedding, tuple):           # (multi_output_tail: the fused tail took it)
+                return graph_embedding[1]
             sw, table, ids = _weights_for(graph_embedding, nreal, sw, table, rows, trows)
             return R.task_head_loss(graph_embedding, self.ffn, data.y, task, kind, dropout_p=p, n_rows=nreal, task_table=ttable,
                                     row_ids=ids, sample_weight=sw, pos_weight=pw, weight_table=table)
@@ -321,7 +349,8 @@ class GNNModel(torch.nn.Module):
         -- ``data.labels`` (float32 ``[n, T]``, NaN: not measured) or ``data.label_table`` + ``data.label_rows`` (a resident shard's
         matrix and the batch's molecule ids, ``padding.CompactStaticBatch.gather``) -- so the network runs once per molecule.  The
         loss is one of ``_loss_kind()`` or the ``pos_weight`` BCE of ``_weighted_loss``; ``batch.weight`` / ``weight_table`` are passed
-        on; ``n_valid_molecules`` is honoured.  The embedding comes from the separate readout operators, as for the task head.  A
+        on; ``n_valid_molecules`` is honoured.  The embedding comes from the separate readout operators, as for the task head (with
+        ``multi_output_tail`` on, the multi-output fused tail is asked first).  A
         CPU batch, or head dropout ``p >= 1``, takes the definition (``readout.label_head_reference``) behind ``self.dropout``."""
         from . import readout as R
         if _has_tasks(data):
@@ -334,7 +363,10 @@ class GNNModel(torch.nn.Module):
         labels, ltable, lrows = _batch_fields(data, 'labels', 'label_table', 'label_rows')
         sw, table, rows = _batch_weight_fields(data)
         nreal = getattr(data, 'n_valid_molecules', None)
-        graph_embedding = self.gnn_model(data)
+        graph_embedding = self._multi_tail_embedding(data, kind, pw, dict(labels=labels, label_table=ltable), lrows, sw, table,
+                                                     rows, nreal)
+        if isinstance(graph_embedding, tuple):               # (multi_output_tail: the fused tail took it)
+            return graph_embedding[1]
         sw, table, ids = _weights_for(graph_embedding, nreal, sw, table, rows, lrows)
         if data.x.is_cuda and not (self.training and self.dropout.p >= 1.0):
             return R.label_head_loss(graph_embedding, self.ffn, labels, kind, dropout_p=self.dropout.p if self.training else 0.0,
